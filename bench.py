@@ -14,6 +14,9 @@ forward, forward, backward, Adam; with N > 1 one RCCL all-reduce of the flat gra
 gives `grad_steps_per_sec` (also inside `config.train_only` and `roofline`, where the driver's record keeps it), the env-only leg
 `env_only_steps_per_sec`.  Everything is device
 resident when the timed region starts; nothing crosses PCIe inside it.
+Every leg times exactly --steps steps once (the train-only leg in whole graphs of 10); `ms_per_step` is the full loop's.
+--dump-outputs DIR writes what the full loop's last timed step computed to DIR/<name>.npy (dump_outputs); all inputs are seeded, so
+two runs with the same arguments start from the same state.
 """
 import argparse
 import json
@@ -45,6 +48,24 @@ ADAM_BYTES = 28                 # per parameter
 ENV_BYTES = 6_400 + 64          # per env-step
 
 
+def dump_outputs(out_dir, step, env, net):
+    """What the full loop's step hands its caller, after the last timed step, as DIR/<name>.npy (float32; float64 for the int64 replay
+    indices): the actions, the env step's rewards / terminals / scores and frames (u8 0 / 255 pixels, unpacked from the 6400-bit packed
+    frame), the minibatch random.sample drew (ring indices, actions, rewards, terminals), the loss, and the online parameters Adam left.
+    1024 envs: ~30 MB in all."""
+    import torch
+    torch.cuda.synchronize()
+    n = env.n
+    pixels = np.unpackbits(env.frame_bits.cpu().numpy().view(np.uint8), axis=1, bitorder="little").reshape(n, 80, 80) * 255
+    out = {"actions": step.actions, "reward": env.reward, "terminal": env.terminal, "score": env.score, "frame": pixels,
+           "batch_index": step.idx, "batch_action": step.a, "batch_reward": step.r, "batch_terminal": step.t, "loss": step.loss,
+           "params": net.store_params()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in out.items():
+        x = x.cpu().numpy() if hasattr(x, "cpu") else x
+        np.save(os.path.join(out_dir, name + ".npy"), x.astype(np.float64 if x.dtype == np.int64 else np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -53,7 +74,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-legs", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the configs[2] / configs[3] legs (tools/profile_round.sh: the rocprofv3 kernel statistics then hold the headline workload's launches only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the full loop's last timed step computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -70,6 +94,7 @@ def main():
     dev_index = 0 if os.environ.get("FB_BENCH_SINGLE_DEVICE") else local_rank
     backend = os.environ.get("FB_BENCH_BACKEND", "nccl")     # "nccl" is RCCL on ROCm
     torch.cuda.set_device(dev_index)
+    torch.manual_seed(0)                                    # (the env-only legs' random actions)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         kw = {"device_id": torch.device("cuda", dev_index)} if backend == "nccl" else {}
@@ -151,31 +176,19 @@ def main():
                 dist.all_reduce(grad)
             net.apply_adam(grad)
 
-    local_times = []
-
     def timed(fn, k, first=0):
+        """The contract's measurement: exactly k steps between barrier + synchronize.  -> (MAX over ranks, this rank's own time)"""
         barrier()
         t0 = time.perf_counter()
         for i in range(k):
             fn(first + i)
         barrier()
         dt = time.perf_counter() - t0
-        local_times.append(dt)                              # (this rank's own clock, before the MAX over ranks)
         if world > 1:
             tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-            dt = tt.item()
-        return dt
-
-    def timed_repeat(fn, k, first=0, min_total=0.2, max_rep=400):
-        """The contract's measurement -- exactly k steps between barrier + synchronize, MAX over ranks -- repeated until the
-        measurements add up to >= min_total seconds: with the driver's --steps 20 one measurement is a 3 ms single shot that one
-        scheduler hiccup can spoil.  Returns the list of per-measurement times (identical on every rank, so every rank takes
-        the same number of repeats); callers report the median."""
-        dts = []
-        while sum(dts) < min_total and len(dts) < max_rep:
-            dts.append(timed(fn, k, first + len(dts) * k))
-        return dts
+            return tt.item(), dt
+        return dt, dt
 
     def median(xs):
         xs = sorted(xs)
@@ -184,11 +197,11 @@ def main():
     # ---------------------------------------------------------------- leg A: the full loop (value)
     for i in range(args.warmup):
         full_step(i)
-    dts_full = timed_repeat(full_step, args.steps, first=args.warmup)
-    dts_full_local = list(local_times)
-    dt = median(dts_full)
+    dt, dt_local = timed(full_step, args.steps, first=args.warmup)
     ms_per_step = dt / args.steps * 1e3
     env_steps_per_s = world * N_ENVS * args.steps / dt
+    if args.dump_outputs and rank == 0:                      # (before the legs below move the same env / replay / net on)
+        dump_outputs(args.dump_outputs, one_step, env, net)
     # which schedule the loop ran in: fb_vec_step's split schedule (train chain on the caller's stream BESIDE acting + env on the net's
     # side stream; same results as one stream, bit for bit) -- how many steps took it, and how many of their minibatches could start
     # beside their env step (the rest hold a transition the step itself appends and wait for it).  Then the same loop on ONE stream,
@@ -197,16 +210,13 @@ def main():
     L.check(L.lib().fb_vec_step_set_schedule(0), "fb_vec_step_set_schedule")
     for i in range(args.warmup):
         full_step(i)
-    n_before = len(local_times)
-    dts_one = timed_repeat(full_step, args.steps, first=args.warmup, min_total=0.1)
-    del local_times[n_before:]
+    dt_one, _ = timed(full_step, args.steps, first=args.warmup)
     L.check(L.lib().fb_vec_step_set_schedule(1), "fb_vec_step_set_schedule")
-    one_stream_ms = median(dts_one) / args.steps * 1e3
+    one_stream_ms = dt_one / args.steps * 1e3
 
     # ---------------------------------------------------------------- leg B: env only
     acts = (torch.rand(N_ENVS, device="cuda") < 0.1).to(torch.uint8)
-    dts_env = timed_repeat(lambda i: env.frame_step(acts, want_u8=False), args.steps)
-    dt_env = median(dts_env)
+    dt_env, _ = timed(lambda i: env.frame_step(acts, want_u8=False), args.steps)
     env_only = world * N_ENVS * args.steps / dt_env
 
     env_by_n = {str(N_ENVS): round(env_only, 1)}
@@ -246,15 +256,13 @@ def main():
             print(f"[bench] hipGraph capture unavailable ({type(e).__name__}: {e}); eager train leg", file=sys.stderr)
     if graph_used:
         reps = max(1, args.steps // 10)
-        dts_tr = timed_repeat(lambda i: g.replay(), reps)
+        dt_tr, _ = timed(lambda i: g.replay(), reps)
         grad_steps = 10 * reps
     else:
-        dts_tr = timed_repeat(train, args.steps)
+        dt_tr, _ = timed(train, args.steps)
         grad_steps = args.steps
-    dt_tr = median(dts_tr)
     grad_steps_per_s = world * grad_steps / dt_tr
-    dts_tr_eager = timed_repeat(train, args.steps)
-    dt_tr_eager = median(dts_tr_eager)
+    dt_tr_eager, _ = timed(train, args.steps)
     grad_steps_eager = world * args.steps / dt_tr_eager
 
     # ---------------------------------------------------------------- N > 1: the data-parallel invariant, checked on the run itself
@@ -295,7 +303,7 @@ def main():
         tt = torch.tensor([median(ts)], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         allreduce_us = round(tt.item(), 2)
-        mine = torch.tensor([median(dts_full_local) / args.steps * 1e3], dtype=torch.float64, device="cuda")
+        mine = torch.tensor([dt_local / args.steps * 1e3], dtype=torch.float64, device="cuda")
         lo, hi = mine.clone(), mine.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
@@ -556,11 +564,7 @@ def main():
             "grad_steps_per_sec_eager": round(grad_steps_eager, 1),
             "env_only_steps_per_sec": round(env_only, 1), "env_only_steps_per_sec_by_n_envs": env_by_n,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-            # every leg: the K-step measurement of the contract repeated until >= 200 ms have been timed; value / ms_per_step /
-            # grad_steps_per_sec are the MEDIAN measurement, min and max beside it (ms per step of the full loop)
-            "repeats": {"full_loop": len(dts_full), "env_only": len(dts_env), "train_only": len(dts_tr), "train_only_eager": len(dts_tr_eager)},
-            "ms_per_step_min_max": [round(min(dts_full) / args.steps * 1e3, 4), round(max(dts_full) / args.steps * 1e3, 4)],
-            "timed_seconds": round(sum(dts_full) + sum(dts_env) + sum(dts_tr) + sum(dts_tr_eager), 3),
+            "timed_seconds": round(dt + dt_env + dt_tr + dt_tr_eager, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "configs[1]: 1024 vectorised envs + BrainDQN uniform replay, batch 32, fp32, per GPU",
                        "n_envs_per_gpu": N_ENVS, "batch": BATCH, "replay_slots": CAPACITY, "fc_width": 512,
