@@ -20,6 +20,7 @@ ALGO_DQN, ALGO_NATURE, ALGO_DOUBLE, ALGO_PER, ALGO_PG = 0, 1, 2, 3, 4
 DTYPE_F32, DTYPE_BF16 = 0, 1
 PER_EXACT, PER_FAST = 0, 1
 NIB_PITCH, NIB_ROWS, NIB_STRIDE = 44, 84, 3712       # include/fbdqn.h FB_NIB_*
+EVAL_MAX_ENVS, EVAL_MAX_EPISODES = 65536, 64         # include/fbdqn.h FB_EVAL_MAX_*
 
 _vp, _i, _i64, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 
@@ -96,6 +97,11 @@ SIGNATURES = {
     "fb_profile_ring_kernel": [_vp, _vp, _i, _i, _i, _i] + [_vp] * 6,
     "fb_qnet_kernel_name": [_i],
     "fb_vec_step": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _i, _d, _vp],
+    "fb_eval_create": [_i, _vp, _sz, _vp],
+    "fb_eval_destroy": [_vp],
+    "fb_eval_run": [_vp, _vp, _i, _i, _i64, _f, _u64, _u64, _vp, _vp, _vp, _vp, _vp],
+    "fb_eval_stats": [_vp, _vp, _vp],
+    "fb_eval_q": [_vp, _vp, _i, _vp, _vp],
 }
 
 

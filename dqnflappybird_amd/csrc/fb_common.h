@@ -64,6 +64,7 @@ __device__ __forceinline__ void fb_flag_wait(const unsigned long long *flag, uns
 #define FB_STREAM_SAMPLE 2u   // uniform replay (FB_RNG_PHILOX)
 #define FB_STREAM_PER 3u      // PER segment uniforms (FB_RNG_PHILOX)
 #define FB_STREAM_INIT 4u     // truncated-normal weight init
+#define FB_STREAM_EVAL 5u     // epsilon-greedy of fb_eval_run, counter = (env id, eval step): never the training acting stream
 
 struct fb_u4 { uint32_t x, y, z, w; };
 
@@ -103,6 +104,18 @@ struct HeadCore {
 // on_arrival (split schedule, or NULL): a word the launch that carries the rider stores when it arrives -- the launch in front of it (the
 // acting forward's fc1 launch) has retired then
 struct FbHeadRider { HeadCore c; const float *params; int on; unsigned long long *on_arrival; unsigned long long arrival_val; };
+// fb_eval_run's step launch (fb_env.hip, env_kernel<true, true>): the launch walks rows of the evaluation's compacted buffers, env_of maps
+// a row to its env id (the key of its gap and epsilon streams); per-env counters and the records are indexed by env id, so compaction
+// moves only the row-indexed state, nibble image and map
+struct FbEvalRider {
+    const int32_t *env_of;                     // [rows of the launch]
+    int32_t *ep_k, *ep_len;                    // [env] episodes ended / frame_steps of the running episode
+    int32_t *score, *length; uint8_t *trunc;   // [env][episodes] records (caller owned)
+    int episodes;
+    unsigned *live;                            // envs that have not ended `episodes` episodes yet
+    unsigned long long *done_step;             // the latest vector step (1-based) at which an env ended its last episode
+    unsigned long long step;                   // this launch's vector step (0-based)
+};
 // fb_replay_gather as a rider of another module's launch (fb_gather.h; B == 0: no rider): what the kernel needs of the ring
 struct FbGatherCtx {
     long long cap; int n_envs, t_f, kind;
@@ -170,6 +183,11 @@ struct FbPushRider { unsigned long long *bits; uint8_t *act; float *rew; uint8_t
 int fb_env_step_rider(fb_env_t h, const uint8_t *actions, uint8_t *frames, uint64_t *frame_bits, float *reward, uint8_t *terminal,
                       int32_t *score, const FbSampleRider *rider, const FbPushRider *push, const FbHeadRider *head, void *stream);
 int fb_qnet_num_actions(fb_qnet_t h);
+// fb_eval_run's acting forward: conv1 .. fc1 of n nibble states (1 <= n <= 3 * max_batch) through the fused two-plane trunk at ANY n (the
+// acting path switches to the small-batch kernels below 256 states), the head described in *head for the eval step launch
+int fb_qnet_eval_trunk(fb_qnet_t h, const uint8_t *nib_states, int n, FbHeadRider *head, void *stream);
+int fb_qnet_max_rows(fb_qnet_t h);            // 3 * max_batch: the most states one acting forward takes
+hipStream_t fb_qnet_side_stream(fb_qnet_t h); // the split schedule's side stream if the net has one, else NULL (never creates it)
 void *fb_qnet_get_grad_event(fb_qnet_t h);                 // the event fb_qnet_set_grad_event installed, or NULL
 // the event the LAST gradient-exporting train step recorded behind its fc1 backward launch (NULL: none was recorded); reading clears it
 void *fb_qnet_take_grad_event_recorded(fb_qnet_t h);

@@ -143,13 +143,16 @@ __device__ __forceinline__ int resize_gray_bit(uint32_t s00, uint32_t s01, uint3
 __device__ __forceinline__ int nib_word(int w) { return (w / 10 + 2) * (FB_NIB_PITCH / 4) + 1 + w % 10; }
 
 // ------------------------------------------------------------------ the step kernel
-template <bool STEP>
+// EVAL (fb_eval_run, STEP and the head rider on): `env` below is a ROW of the evaluation's compacted buffers, ev.env_of[row] the env id
+// that keys its gap and epsilon streams; rows whose env has ended its episodes are skipped, an episode end is recorded (FbEvalRider).
+// With EVAL = false every line of it compiles away.
+template <bool STEP, bool EVAL = false>
 __global__ __launch_bounds__(ENV_THREADS, 8) void env_kernel(EnvParams p, const uint8_t *__restrict__ actions,
                                                   uint8_t *__restrict__ frames,
                                                   unsigned long long *__restrict__ frame_bits,
                                                   float *__restrict__ reward, uint8_t *__restrict__ terminal,
                                                   int32_t *__restrict__ score, FbSampleRider rider, FbPushRider push,
-                                                  FbHeadRider head) {
+                                                  FbHeadRider head, FbEvalRider ev) {
     __shared__ EnvLds L;
     __shared__ unsigned long long fw[100];          // the frame being assembled, 1 bit / pixel
     __shared__ unsigned long long rowm[OBS];        // columns 0..62 of every output row
@@ -195,7 +198,8 @@ __global__ __launch_bounds__(ENV_THREADS, 8) void env_kernel(EnvParams p, const 
         if (STEP && head.on) {
             const int hw = threadIdx.x >> 6, he = env + hw * nblk;
             if (he < p.n_envs) {
-                const int a = head_one_t<2>(head.c, head.params, he, threadIdx.x & 63);      // the game has two actions (the host checks)
+                const int a = EVAL ? head_one_t<2>(head.c, head.params, he, threadIdx.x & 63, ev.env_of[he], FB_STREAM_EVAL)
+                                   : head_one_t<2>(head.c, head.params, he, threadIdx.x & 63);      // the game has two actions (the host checks)
                 if ((threadIdx.x & 63) == 0) act_mail[hw] = a;     // handed to the other waves through LDS
             }
         }
@@ -222,6 +226,8 @@ __global__ __launch_bounds__(ENV_THREADS, 8) void env_kernel(EnvParams p, const 
 #pragma unroll
             for (int i = 0; i < 16; i++) st[i] = p.state[(size_t)env * 16 + i];
         }
+        const int gid = EVAL ? ev.env_of[env] : env;              // the env id: key of the gap stream
+        if (EVAL && ev.ep_k[gid] >= ev.episodes) continue;        // finished: masked until the next compaction (uniform per workgroup)
 
         float rew = 0.1f;
         int term = 0, score_ret = st[5], bad = 0, act = 0;
@@ -245,7 +251,7 @@ __global__ __launch_bounds__(ENV_THREADS, 8) void env_kernel(EnvParams p, const 
 #pragma unroll
                 for (int i = 0; i < 3; i++) if (i < st[6]) st[7 + i] -= 4;            // :126-128
                 if (0 < st[7] && st[7] < 5) {                     // :131-134
-                    const int g = draw_gap(p, env, st);
+                    const int g = draw_gap(p, gid, st);
                     if (st[6] == 2) { st[9] = 298; st[12] = g; } else { st[8] = 298; st[11] = g; }
                     st[6] += 1;
                 }
@@ -293,11 +299,22 @@ __global__ __launch_bounds__(ENV_THREADS, 8) void env_kernel(EnvParams p, const 
                 if (STEP) return;
 #endif
                 score_ret = st[5];                                // :155
-                if (crash) { term = 1; env_reset(p, env, st); rew = -3.0f; }          // :157-162
+                if (crash) { term = 1; env_reset(p, gid, st); rew = -3.0f; }          // :157-162
             }
         }
         if (threadIdx.x == 0) {
-            if (STEP) {
+            if (STEP && EVAL) {
+#pragma unroll
+                for (int i = 0; i < 16; i++) p.state[(size_t)env * 16 + i] = st[i];
+                const int len = ev.ep_len[gid] + 1;                  // frame_steps of this episode, the crashing one included
+                if (term) {
+                    const int k = ev.ep_k[gid];
+                    const size_t o = (size_t)gid * ev.episodes + k;
+                    ev.score[o] = score_ret; ev.length[o] = len; ev.trunc[o] = 0;
+                    ev.ep_k[gid] = k + 1; ev.ep_len[gid] = 0;
+                    if (k + 1 == ev.episodes) { atomicSub(ev.live, 1u); atomicMax(ev.done_step, ev.step + 1ull); }
+                } else ev.ep_len[gid] = len;
+            } else if (STEP) {
 #pragma unroll
                 for (int i = 0; i < 16; i++) p.state[(size_t)env * 16 + i] = st[i];
                 reward[env] = bad ? 0.f : rew;
@@ -699,7 +716,7 @@ int fb_env_step_rider(fb_env_t h, const uint8_t *actions, uint8_t *frames, uint6
     if (push) q = *push;
     if (head) hd = *head;
     hipLaunchKernelGGL(env_kernel<true>, dim3(h->grid + (r.k ? 1 : 0)), dim3(ENV_THREADS), 0, fb_stream(stream), h->p, actions, frames,
-                       (unsigned long long *)frame_bits, reward, terminal, score, r, q, hd);
+                       (unsigned long long *)frame_bits, reward, terminal, score, r, q, hd, FbEvalRider{});
     FB_LAUNCH_CHECK();
     return FB_OK;
 }
@@ -708,7 +725,7 @@ extern "C" int fb_env_observe(fb_env_t h, uint8_t *frames, uint64_t *frame_bits,
     FB_REQUIRE(h && (frames || frame_bits), "fb_env_observe: NULL argument");
     hipLaunchKernelGGL(env_kernel<false>, dim3(h->grid), dim3(ENV_THREADS), 0, fb_stream(stream), h->p,
                        (const uint8_t *)nullptr, frames, (unsigned long long *)frame_bits, (float *)nullptr,
-                       (uint8_t *)nullptr, (int32_t *)nullptr, FbSampleRider{}, FbPushRider{}, FbHeadRider{});
+                       (uint8_t *)nullptr, (int32_t *)nullptr, FbSampleRider{}, FbPushRider{}, FbHeadRider{}, FbEvalRider{});
     FB_LAUNCH_CHECK();
     return FB_OK;
 }
@@ -788,5 +805,237 @@ extern "C" int fb_env_error_count(fb_env_t h, int64_t *count_host) {
     unsigned long long v = 0;
     FB_CHECK_HIP(hipMemcpy(&v, h->p.err_count, sizeof(v), hipMemcpyDeviceToHost));
     *count_host = (int64_t)v;
+    return FB_OK;
+}
+
+// ------------------------------------------------------------------ evaluation (include/fbdqn.h "evaluation")
+// fb_eval_run plays n fresh games greedily (or epsilon-greedily on a stream of its own) on rows of its own buffers: row -> env id map,
+// 16-int env states and nibble images, in ping-pong pairs.  A vector step is the fused acting trunk + its fc1 launch over rows
+// [0, n_rows) (fb_qnet_eval_trunk) and env_kernel<true, true>, which computes each row's head, steps the row's game if its env is
+// live and records episode ends.  At chunk boundaries the host reads the live count and, when it has fallen, compacts the rows of
+// live envs to the front in one launch (stable order): the next chunk's grids cover only them.
+namespace {
+
+constexpr int EVAL_CHUNK = 32;            // vector steps between two reads of the live count (one host sync per chunk)
+constexpr int NIB_U4 = FB_NIB_STRIDE / 16;
+static_assert(FB_NIB_STRIDE % 16 == 0, "nibble rows move as uint4");
+
+__global__ void eval_init_kernel(int n, int32_t *__restrict__ env_of, int32_t *__restrict__ ep_k, int32_t *__restrict__ ep_len,
+                                 unsigned *__restrict__ live) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < n) { env_of[r] = r; ep_k[r] = 0; ep_len[r] = 0; }
+    if (r == 0) { live[0] = (unsigned)n; *reinterpret_cast<unsigned long long *>(live + 2) = 0ull; }
+}
+
+// rows of live envs of [0, n_rows) -> the front of the other buffers, in row order.  Workgroup b takes rows [256 b, 256 b + 256): it
+// counts the live rows in front of its block itself (no second launch), ranks its own rows by ballot, then moves them.
+__global__ __launch_bounds__(256) void eval_compact_kernel(int n_rows, int episodes, const int32_t *__restrict__ ep_k,
+                                                           const int32_t *__restrict__ env_in, const int32_t *__restrict__ st_in,
+                                                           const uint4 *__restrict__ nib_in, int32_t *__restrict__ env_out,
+                                                           int32_t *__restrict__ st_out, uint4 *__restrict__ nib_out) {
+    __shared__ int wsum[4], wbase[4], src[256], dst[256];
+    __shared__ int nlive;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r0 = blockIdx.x * 256;
+    int before = 0;
+    for (int r = tid; r < r0; r += 256) before += ep_k[env_in[r]] < episodes;
+    for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
+    if (lane == 0) wsum[wave] = before;
+    __syncthreads();
+    const int base = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+    const int r = r0 + tid;
+    const bool live = r < n_rows && ep_k[env_in[r]] < episodes;
+    const unsigned long long m = __ballot(live);
+    if (lane == 0) wsum[wave] = __popcll(m);
+    __syncthreads();
+    if (tid == 0) {
+        int acc = 0;
+        for (int w = 0; w < 4; w++) { wbase[w] = acc; acc += wsum[w]; }
+        nlive = acc;
+    }
+    __syncthreads();
+    const int loc = wbase[wave] + __popcll(m & ((1ull << lane) - 1ull));
+    if (live) {
+        const int d = base + loc;
+        src[loc] = r; dst[loc] = d;
+        env_out[d] = env_in[r];
+#pragma unroll
+        for (int i = 0; i < 16; i++) st_out[(size_t)d * 16 + i] = st_in[(size_t)r * 16 + i];
+    }
+    __syncthreads();
+    const int nl = nlive;
+    for (int i = tid; i < nl * NIB_U4; i += 256) {
+        const int k = i / NIB_U4, w = i - k * NIB_U4;
+        nib_out[(size_t)dst[k] * NIB_U4 + w] = nib_in[(size_t)src[k] * NIB_U4 + w];
+    }
+}
+
+// the step cap: every env still running records its in-progress episode (its score and frame_steps so far) as truncated
+__global__ void eval_truncate_kernel(int n_rows, const int32_t *__restrict__ st, FbEvalRider ev) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const int gid = ev.env_of[r], k = ev.ep_k[gid], len = ev.ep_len[gid];
+    if (k >= ev.episodes || len == 0) return;
+    const size_t o = (size_t)gid * ev.episodes + k;
+    ev.score[o] = st[(size_t)r * 16 + 5]; ev.length[o] = len; ev.trunc[o] = 1;
+}
+
+}  // namespace
+
+struct fb_eval {
+    fb_env_t env;                        // the sprite tables (its own state buffer stays unused)
+    int cap;
+    int32_t *state[2], *env_of[2];
+    uint8_t *nib[2];
+    int32_t *ep_k, *ep_len;
+    unsigned *live;                      // [0] live envs, [2..3] done_step (u64): read together at chunk boundaries
+    uint8_t *actions;                    // the head's outputs per row of a pass (only the eval step reads them)
+    float *q;
+    unsigned *live_host;                 // pinned copy of `live`
+    int64_t rows_launched, compactions;
+};
+
+extern "C" int fb_eval_destroy(fb_eval_t ev) {
+    if (!ev) return FB_OK;
+    (void)hipDeviceSynchronize();
+    if (ev->env) fb_env_destroy(ev->env);
+    for (int i = 0; i < 2; i++) {
+        if (ev->state[i]) (void)hipFree(ev->state[i]);
+        if (ev->env_of[i]) (void)hipFree(ev->env_of[i]);
+        if (ev->nib[i]) (void)hipFree(ev->nib[i]);
+    }
+    if (ev->ep_k) (void)hipFree(ev->ep_k);
+    if (ev->ep_len) (void)hipFree(ev->ep_len);
+    if (ev->live) (void)hipFree(ev->live);
+    if (ev->actions) (void)hipFree(ev->actions);
+    if (ev->q) (void)hipFree(ev->q);
+    if (ev->live_host) (void)hipHostFree(ev->live_host);
+    delete ev;
+    return FB_OK;
+}
+
+extern "C" int fb_eval_create(int max_envs, const void *sprite_blob, size_t blob_bytes, fb_eval_t *out) {
+    FB_REQUIRE(out, "fb_eval_create: out is NULL");
+    *out = nullptr;
+    FB_REQUIRE(max_envs >= 1 && max_envs <= FB_EVAL_MAX_ENVS, "fb_eval_create: max_envs=%d outside 1..%d", max_envs, FB_EVAL_MAX_ENVS);
+    FB_REQUIRE(sprite_blob, "fb_eval_create: sprite blob is NULL");
+    fb_eval *ev = new fb_eval();
+    memset(ev, 0, sizeof(*ev));
+    ev->cap = max_envs;
+    int rc = fb_env_create(1, 0, 0, sprite_blob, blob_bytes, &ev->env);
+    if (rc != FB_OK) { delete ev; return rc; }
+    const size_t n = (size_t)max_envs;
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; i++) {
+        e = hipMalloc(&ev->state[i], n * 16 * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc(&ev->env_of[i], n * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc(&ev->nib[i], n * FB_NIB_STRIDE);
+    }
+    if (e == hipSuccess) e = hipMalloc(&ev->ep_k, n * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&ev->ep_len, n * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(&ev->live, 4 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMalloc(&ev->actions, n);
+    if (e == hipSuccess) e = hipMalloc(&ev->q, n * MAXA * sizeof(float));
+    if (e == hipSuccess) e = hipHostMalloc(&ev->live_host, 4 * sizeof(unsigned));
+    if (e != hipSuccess) {
+        fb_set_error(FB_ERR_HIP, "fb_eval_create: %s", hipGetErrorString(e));
+        fb_eval_destroy(ev);
+        return FB_ERR_HIP;
+    }
+    *out = ev;
+    return FB_OK;
+}
+
+extern "C" int fb_eval_stats(fb_eval_t ev, int64_t *rows_launched_host, int64_t *compactions_host) {
+    FB_REQUIRE(ev, "fb_eval_stats: NULL handle");
+    if (rows_launched_host) *rows_launched_host = ev->rows_launched;
+    if (compactions_host) *compactions_host = ev->compactions;
+    return FB_OK;
+}
+
+extern "C" int fb_eval_run(fb_eval_t ev, fb_qnet_t net, int n_envs, int episodes, int64_t max_steps, float epsilon, uint64_t env_seed,
+                           uint64_t act_seed, int32_t *score, int32_t *length, uint8_t *truncated, int64_t *steps_host, void *stream) {
+    // every argument is checked before anything is launched
+    FB_REQUIRE(ev, "fb_eval_run: NULL eval handle");
+    FB_REQUIRE(net, "fb_eval_run: NULL net");
+    FB_REQUIRE(fb_qnet_num_actions(net) == 2, "fb_eval_run: the net has %d actions, the game takes 2", fb_qnet_num_actions(net));
+    FB_REQUIRE(n_envs >= 1 && n_envs <= FB_EVAL_MAX_ENVS, "fb_eval_run: n_envs=%d outside 1..%d", n_envs, FB_EVAL_MAX_ENVS);
+    FB_REQUIRE(n_envs <= ev->cap, "fb_eval_run: n_envs=%d exceeds the handle's max_envs=%d", n_envs, ev->cap);
+    FB_REQUIRE(episodes >= 1 && episodes <= FB_EVAL_MAX_EPISODES, "fb_eval_run: episodes=%d outside 1..%d", episodes, FB_EVAL_MAX_EPISODES);
+    FB_REQUIRE(max_steps >= 1, "fb_eval_run: max_steps=%lld < 1", (long long)max_steps);
+    FB_REQUIRE(epsilon >= 0.f && epsilon <= 1.f, "fb_eval_run: epsilon=%g outside [0, 1]", (double)epsilon);      // (NaN fails too)
+    FB_REQUIRE(score && length && truncated && steps_host, "fb_eval_run: NULL output");
+    hipStream_t S = fb_stream(stream);
+    // the acting forward writes the net's acting scratch (hf_act / hp_act, the activation planes, the plane versions), which the split
+    // schedule's side stream also writes: whatever that stream still holds finishes first (and this call returns synchronised)
+    if (hipStream_t side = fb_qnet_side_stream(net)) FB_CHECK_HIP(hipStreamSynchronize(side));
+    ev->rows_launched = 0; ev->compactions = 0;
+    const int n = n_envs, P = fb_qnet_max_rows(net);        // rows per acting pass
+    EnvParams p = ev->env->p;
+    p.n_envs = n; p.seed_lo = (uint32_t)env_seed; p.seed_hi = (uint32_t)(env_seed >> 32);
+    p.tape = nullptr; p.tape_len = 0; p.stats = nullptr;
+    p.state = ev->state[0]; p.nib = ev->nib[0];
+    const size_t nrec = (size_t)n * episodes;
+    FB_CHECK_HIP(hipMemsetAsync(score, 0, nrec * sizeof(int32_t), S));
+    FB_CHECK_HIP(hipMemsetAsync(length, 0, nrec * sizeof(int32_t), S));      // length 0 = no such episode
+    FB_CHECK_HIP(hipMemsetAsync(truncated, 0, nrec, S));
+    hipLaunchKernelGGL(eval_init_kernel, dim3((n + 255) / 256), dim3(256), 0, S, n, ev->env_of[0], ev->ep_k, ev->ep_len, ev->live);
+    // start: env e as env e of fb_env_create(n, env_seed): reset (gap stream (env_seed, e)), then the first frame stack (fb_env_observe)
+    hipLaunchKernelGGL(env_reset_kernel, dim3((n + 255) / 256), dim3(256), 0, S, p);
+    hipLaunchKernelGGL((env_kernel<false>), dim3(n < 2048 ? n : 2048), dim3(ENV_THREADS), 0, S, p, (const uint8_t *)nullptr,
+                       (uint8_t *)nullptr, (unsigned long long *)nullptr, (float *)nullptr, (uint8_t *)nullptr, (int32_t *)nullptr,
+                       FbSampleRider{}, FbPushRider{}, FbHeadRider{}, FbEvalRider{});
+    FB_LAUNCH_CHECK();
+    FbEvalRider er;
+    er.ep_k = ev->ep_k; er.ep_len = ev->ep_len; er.score = score; er.length = length; er.trunc = truncated;
+    er.episodes = episodes; er.live = ev->live; er.done_step = reinterpret_cast<unsigned long long *>(ev->live + 2);
+    int cur = 0, rows = n;
+    int64_t step = 0;
+    unsigned live = (unsigned)n;
+    while (step < max_steps && live > 0) {
+        const int64_t chunk = max_steps - step < EVAL_CHUNK ? max_steps - step : EVAL_CHUNK;
+        for (int64_t i = 0; i < chunk; i++, step++) {
+            for (int r0 = 0; r0 < rows; r0 += P) {
+                const int nb = rows - r0 < P ? rows - r0 : P;
+                uint8_t *nib = ev->nib[cur] + (size_t)r0 * FB_NIB_STRIDE;
+                FbHeadRider hd;
+                memset(&hd, 0, sizeof(hd));
+                int rc = fb_qnet_eval_trunk(net, nib, nb, &hd, stream);
+                if (rc != FB_OK) return rc;
+                hd.c.actions = ev->actions; hd.c.q = ev->q; hd.c.epsilon = epsilon;
+                hd.c.seed_lo = (uint32_t)act_seed; hd.c.seed_hi = (uint32_t)(act_seed >> 32);
+                hd.c.step_lo = (uint32_t)step; hd.c.step_hi = (uint32_t)((uint64_t)step >> 32);
+                EnvParams pp = p;
+                pp.n_envs = nb; pp.state = ev->state[cur] + (size_t)r0 * 16; pp.nib = nib;
+                er.env_of = ev->env_of[cur] + r0; er.step = (unsigned long long)step;
+                // a wave of the head per row of a workgroup (<= 4 rows each), and never more workgroups than rows
+                const int grid = nb <= 2048 ? nb : (nb <= 8192 ? 2048 : (nb + 3) / 4);
+                hipLaunchKernelGGL((env_kernel<true, true>), dim3(grid), dim3(ENV_THREADS), 0, S, pp, (const uint8_t *)nullptr,
+                                   (uint8_t *)nullptr, (unsigned long long *)nullptr, (float *)nullptr, (uint8_t *)nullptr,
+                                   (int32_t *)nullptr, FbSampleRider{}, FbPushRider{}, hd, er);
+                FB_LAUNCH_CHECK();
+            }
+            ev->rows_launched += rows;
+        }
+        FB_CHECK_HIP(hipMemcpyAsync(ev->live_host, ev->live, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, S));
+        FB_CHECK_HIP(hipStreamSynchronize(S));
+        live = *ev->live_host;
+        if (live > 0 && (int)live < rows && step < max_steps) {
+            hipLaunchKernelGGL(eval_compact_kernel, dim3((rows + 255) / 256), dim3(256), 0, S, rows, episodes, (const int32_t *)ev->ep_k,
+                               (const int32_t *)ev->env_of[cur], (const int32_t *)ev->state[cur], (const uint4 *)ev->nib[cur],
+                               ev->env_of[cur ^ 1], ev->state[cur ^ 1], (uint4 *)ev->nib[cur ^ 1]);
+            FB_LAUNCH_CHECK();
+            cur ^= 1; rows = (int)live;
+            ev->compactions += 1;
+        }
+    }
+    if (live > 0) {
+        er.env_of = ev->env_of[cur];
+        hipLaunchKernelGGL(eval_truncate_kernel, dim3((rows + 255) / 256), dim3(256), 0, S, rows, (const int32_t *)ev->state[cur], er);
+        FB_LAUNCH_CHECK();
+    }
+    FB_CHECK_HIP(hipStreamSynchronize(S));
+    // every env finished: the run ended at the step the last one did (the rest of that chunk's steps were masked no-ops)
+    *steps_host = live > 0 ? step : (int64_t)*reinterpret_cast<const unsigned long long *>(ev->live_host + 2);
     return FB_OK;
 }

@@ -12,11 +12,13 @@ __device__ __forceinline__ float4 sel4(bool ok, float4 v) {
 
 // P = the network's flat parameters, smp = row of the state in hf / q / actions.  Returns the action (0 without C.actions).
 // AT = the number of actions when it is known at compile time (2: the game's), MAXA = read it from C.A.
+// key / stream: the epsilon draw's counter (default: the row smp on FB_STREAM_EPS; fb_eval_run: the env id on FB_STREAM_EVAL).
 // No load sits under a branch (hipcc waits vmcnt(0) at the join: with a run-time `if (a < A)` around every fc2 weight this
 // was a chain of ~40 dependent L2 round trips): every parameter is fetched from a clamped, valid address -- the tail
 // parameters (b_q, b_v) together with the first round's partial sums -- and masked by selects.
 template <int AT>
-__device__ __forceinline__ int head_one_t(const HeadCore &C, const float *__restrict__ P, int smp, int lane) {
+__device__ __forceinline__ int head_one_t(const HeadCore &C, const float *__restrict__ P, int smp, int lane, int key = -1,
+                                          uint32_t stream = FB_STREAM_EPS) {
     const int A = AT == MAXA ? C.A : AT;
     int action = 0;
     float acc[AT + 1], bqv[AT];
@@ -73,7 +75,7 @@ __device__ __forceinline__ int head_one_t(const HeadCore &C, const float *__rest
             int best = 0;
 #pragma unroll
             for (int a = 1; a < AT; a++) if (a < A && qv[a] > qv[best]) best = a;           // np.argmax: first maximum
-            const fb_u4 o = fb_philox(C.seed_lo, C.seed_hi, (uint32_t)smp, C.step_lo, FB_STREAM_EPS, C.step_hi);
+            const fb_u4 o = fb_philox(C.seed_lo, C.seed_hi, (uint32_t)(key < 0 ? smp : key), C.step_lo, stream, C.step_hi);
             const float u = (float)(o.x >> 8) * (1.0f / 16777216.0f);                      // random.random()
             if (u <= C.epsilon) best = (int)(((unsigned long long)o.y * (unsigned)A) >> 32);   // randrange(A)
             C.actions[smp] = (uint8_t)best;

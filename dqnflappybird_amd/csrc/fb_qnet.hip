@@ -3442,6 +3442,9 @@ struct Plan {
     // the split schedule (fb_common.hip).  Acting plan: the fc1 launch stores trunk_done.  Train plan: gate workgroups in the fc1 backward
     // launch (trunk_done) and the conv backward launch (fc1_done), the Adam launch's last thread waits for env_done
     const FbSplitCtx *split;
+    // fb_eval_run / fb_eval_q: the fused acting trunk (five states per workgroup) at ANY state count, so that a state's Q values do not
+    // depend on how many other states share the launch (the small-batch kernels below 256 states round differently)
+    bool any_rows;
 };
 
 static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
@@ -3449,7 +3452,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
     int maxc = 0, total = 0;
     for (int z = 0; z < p.ns; z++) { if (p.sl.s[z].count > maxc) maxc = p.sl.s[z].count; total += p.sl.s[z].count; }
     // >= 256 samples in a slice: thousands of tiles, one wave per tile (no K split); below: K split over waves
-    const bool big = maxc >= 256;
+    const bool big = maxc >= 256 || p.any_rows;
     // >= 256 states per slice: the LDS-staged two-plane-fp16 kernels (conv1_sp / conv23_sp / fc1_sp).  Forward-only plans take
     // them with one slice; TRAINING plans run them in passes, one per run of consecutive slices that go through the same net
     // (DQN: s and s' in one pass; Nature / PER: s online, s' target; Double: s, s' online + s' target), with fp32 side outputs
@@ -3507,7 +3510,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             const int t1p = (rows * 100 + 7) / 8, gsp = min(256, (t1p + C1_WAVES - 1) / C1_WAVES);      // one 12-wave workgroup per CU, the waves stride over the tiles
             // the acting path on nibble states: conv1 + conv2 + conv3 in ONE launch (conv23_sp_kernel<., 4, true>), four states per workgroup
             static const bool fuse_on = !(getenv("FB_ACT_FUSED") && atoi(getenv("FB_ACT_FUSED")) == 0);      // A/B knob
-            const bool fused = fuse_on && p.nib && !p.train && !trunk && z1 - z0 == 1 && p.ns == 1;
+            const bool fused = (fuse_on || p.any_rows) && p.nib && !p.train && !trunk && z1 - z0 == 1 && p.ns == 1;
             acting_fused = fused;
             if (!trunk && !fused) FB_K(K_CONV1) {
                 if (p.nib) hipLaunchKernelGGL(conv1_sp_kernel<true>, dim3(gsp), dim3(64 * C1_WAVES), 0, st, sl, (const uint8_t *)h->zeros, h->a1s, pl1, nsp, h->wsp[which], h->FC, pver, (const unsigned *)wver, side, &h->adam->ovf);
@@ -3538,7 +3541,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             // five states per workgroup (125 of the 128 MFMA rows; 1024 envs = 205 workgroups: alone it costs what four per workgroup on
             // all 256 CUs cost, and in the split schedule the fifth of the chip it leaves is where the train chain runs beside it)
             static const int act_spw = getenv("FB_ACT_SPW") && atoi(getenv("FB_ACT_SPW")) == 4 ? 4 : 5;      // A/B knob: states per workgroup of the fused acting trunk
-            const bool spw5 = fused && (act_spw == 5 || p.split);
+            const bool spw5 = fused && (act_spw == 5 || p.split || p.any_rows);
             const dim3 gc((rows + 4) / 5), gc4(spw5 ? (rows + 4) / 5 : (rows + 3) / 4), gf(((rows_f + 127) / 128) * (h->FC / 64) * FC1_SP_KS);    // FC % 128 == 0 (fb_qnet_create)
             // split schedule, more than one round of trunk workgroups (one per CU, 256 CUs) with a partial last round: that round's first
             // workgroup says when it has been placed -- the train chain on the other stream starts then (fb_sampler.h)
@@ -3784,6 +3787,28 @@ extern "C" int fb_qnet_act_nib(fb_qnet_t h, const uint8_t *nib_states, int n, fl
 }
 
 int fb_qnet_num_actions(fb_qnet_t h) { return h ? h->A : 0; }
+int fb_qnet_max_rows(fb_qnet_t h) { return h ? 3 * h->max_batch : 0; }
+hipStream_t fb_qnet_side_stream(fb_qnet_t h) { return h && h->split ? h->split->tstream : nullptr; }
+
+int fb_qnet_eval_trunk(fb_qnet_t h, const uint8_t *nib_states, int n, FbHeadRider *head, void *stream) {
+    FB_REQUIRE(h && nib_states && head, "fb_qnet_eval_trunk: NULL argument");
+    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_qnet_eval_trunk: n %d exceeds 3*max_batch", n);
+    Plan p = forward_plan(h, 0, nib_states, n);
+    p.nib = true; p.any_rows = true;
+    p.head_rider = head;
+    return run_plan(h, p, -1, fb_stream(stream));
+}
+
+extern "C" int fb_eval_q(fb_qnet_t h, const uint8_t *nib_states, int n, float *q, void *stream) {
+    FB_REQUIRE(h && nib_states && q, "fb_eval_q: NULL argument");
+    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_eval_q: n %d exceeds 3*max_batch", n);
+    Plan p = forward_plan(h, 0, nib_states, n);
+    p.nib = true; p.any_rows = true;
+    int rc = run_plan(h, p, -1, fb_stream(stream));
+    if (rc != FB_OK) return rc;
+    FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)n * h->A, hipMemcpyDeviceToDevice, fb_stream(stream)));
+    return FB_OK;
+}
 
 int fb_qnet_check_step(fb_qnet_t h, int n_envs, int train_batch) {
     FB_REQUIRE(h, "fb_vec_step: NULL net");

@@ -177,6 +177,12 @@ class VecBrain:
         self.timeStep += 1
         self.onlineTimeStep += 1
 
+    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0):
+        """Greedy play of n_envs fresh games with the online net as it stands (dqnflappybird_amd.evaluate): changes nothing the
+        training that follows reads -- nets, Adam, envs, frame stacks, stats, replay, the step counters."""
+        from .evaluate import evaluate
+        return evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed)
+
     def set_dtype(self, dtype="f32"):
         """'bf16' = BASELINE.json configs[2]'s arithmetic for acting AND training (fp32 master weights / Adam); 'f32' = default."""
         self.net.set_inference_dtype(dtype)

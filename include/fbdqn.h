@@ -431,6 +431,41 @@ int fb_dist_all_reduce(fb_dist_t d, float *buf, int64_t count, void *stream);
 int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int batch, int n_steps, int64_t *idx, uint8_t *s, uint8_t *s2,
                    uint8_t *a, float *r, uint8_t *t, float *loss, double gamma, void *stream);
 
+/* ------------------------------------------------------------------ evaluation: greedy play of many games with a fixed net
+ * What it evaluates: the reference's play loop (FlappyBirdDQN.py:72-76) with getAction (BrainDQN.py:99-116) at a fixed epsilon and
+ * no training.  fb_eval_run(ev, net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed, ...):
+ *   start    env e (0 <= e < n_envs) starts as env e of fb_env_create(n_envs, env_seed, ...) does (gap stream keyed (env_seed, e)),
+ *            its first frame stack as fb_env_observe leaves it;
+ *   step     every live env takes the epsilon-greedy action of the net's ONLINE parameters (its inference dtype, plain or dueling)
+ *            and makes one frame_step.  epsilon = 0: the argmax of the Q values fb_qnet_act_nib computes for that state (same tie
+ *            rule).  epsilon > 0: fb_qnet_act's rule (uniform <= epsilon, then a uniform action) on a stream of its own, keyed
+ *            (act_seed, env id, eval step) -- never the training acting stream, independent of the row an env occupies;
+ *   records  when env e ends its k-th episode: score[e][k] = the score_return fb_env_step reports, length[e][k] = its frame_steps
+ *            (the crashing one included), truncated[e][k] = 0.  After `episodes` episodes the env takes no more steps;
+ *   stop     when every env is finished or after max_steps vector steps.  An env still running then records its in-progress
+ *            episode (score and frame_steps so far, truncated = 1) if it has made a step of it.  Entries never reached keep
+ *            length = 0 (score 0, truncated 0).  *steps_host = the vector steps taken;
+ *   effects  none on anything a later training call reads (net parameters, target, Adam, step counter, env handles, replay,
+ *            split schedule); the acting forward may re-split the net's inference planes of the same parameters (bit-identical).
+ * score / length: i32[n_envs][episodes], truncated: u8[n_envs][episodes], [dev] caller owned.  1 <= n_envs <= min(FB_EVAL_MAX_ENVS,
+ * the handle's max_envs), 1 <= episodes <= FB_EVAL_MAX_EPISODES, max_steps >= 1, 0 <= epsilon <= 1, a 2-action net: anything else is
+ * FB_ERR_INVALID before any launch.
+ * SYNCHRONOUS and NOT capturable: the work goes on `stream` behind what it holds (and behind the net's side stream, if it has one),
+ * the call reads a live-env count through pinned memory once per 32 vector steps and returns with `stream` synchronised.  The
+ * acting forward runs in passes of <= 3 * max_batch rows (the net's acting capacity).
+ * fb_eval_stats: acting rows launched and compactions of the last fb_eval_run (host counters, no sync).
+ * fb_eval_q: the Q values (f32[n][A], [dev]) of the acting forward fb_eval_run uses, for n nibble states (1 <= n <= 3 * max_batch):
+ * the fused trunk at every n, so a state's Q values do not depend on n or on its row. */
+#define FB_EVAL_MAX_ENVS 65536
+#define FB_EVAL_MAX_EPISODES 64
+typedef struct fb_eval *fb_eval_t;
+int fb_eval_create(int max_envs, const void *sprite_blob, size_t blob_bytes, fb_eval_t *out);
+int fb_eval_destroy(fb_eval_t ev);
+int fb_eval_run(fb_eval_t ev, fb_qnet_t net, int n_envs, int episodes, int64_t max_steps, float epsilon, uint64_t env_seed,
+                uint64_t act_seed, int32_t *score, int32_t *length, uint8_t *truncated, int64_t *steps_host, void *stream);
+int fb_eval_stats(fb_eval_t ev, int64_t *rows_launched_host, int64_t *compactions_host);
+int fb_eval_q(fb_qnet_t net, const uint8_t *nib_states, int n, float *q, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
