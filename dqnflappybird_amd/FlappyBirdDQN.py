@@ -3,6 +3,7 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
 
     python -m dqnflappybird_amd.FlappyBirdDQN --model dqn [--steps N] [--quiet]
     python -m dqnflappybird_amd.FlappyBirdDQN --model dqn --vec 1024 --steps N      (vectorised loop)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model dqn --vec 1024 --n-step 3     (... learning from 3-step returns)
 
 `actorcritic` / `policygradient` are out of scope (broken in the reference).
 """
@@ -67,7 +68,15 @@ def main():
     parser.add_argument("--steps", type=int, default=None)
     parser.add_argument("--quiet", action="store_true")
     parser.add_argument("--vec", type=int, default=0, help="run N vectorised envs (device-resident loop)")
+    parser.add_argument("--n-step", type=int, default=1, help="learn from K-step returns (--vec, uniform replay; 1 = the reference's one-step TD)")
     args = parser.parse_args()
+    if args.n_step != 1:                                 # (refused before anything touches the GPU)
+        if not 1 <= args.n_step <= L.NSTEP_MAX:
+            parser.error(f"--n-step must be in 1..{L.NSTEP_MAX}")
+        if not args.vec:
+            parser.error("--n-step needs --vec: the single-env agents are the reference's one-step algorithms")
+        if args.model == "prioritydqn":
+            parser.error("--n-step needs a uniform replay memory: prioritydqn takes --n-step 1")
     if args.vec:
         # one process per GPU (python -m torch.distributed.run --nproc-per-node N -m dqnflappybird_amd.FlappyBirdDQN ...):
         # --vec envs PER RANK, rank-local replay, one RCCL all-reduce of the flat gradient per train step
@@ -77,7 +86,7 @@ def main():
         if args.model in ("actorcritic", "policygradient"):
             raise SystemExit("--vec runs the DQN family; the actor-critic / policy-gradient agents are single-env (as in the reference)")
         algo = {"dqn": "dqn", "ddqn": "nature", "dqnnature": "nature", "duelingdqn": "nature", "prioritydqn": "per"}[args.model]
-        vb = VecBrain(args.vec, algo=algo, rank=rank, world=world)
+        vb = VecBrain(args.vec, algo=algo, rank=rank, world=world, n_step=args.n_step)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)
     else:
         playFlappyBird(args.model, args.steps, verbose=not args.quiet)

@@ -21,6 +21,7 @@ DTYPE_F32, DTYPE_BF16 = 0, 1
 PER_EXACT, PER_FAST = 0, 1
 NIB_PITCH, NIB_ROWS, NIB_STRIDE = 44, 84, 3712       # include/fbdqn.h FB_NIB_*
 EVAL_MAX_ENVS, EVAL_MAX_EPISODES = 65536, 64         # include/fbdqn.h FB_EVAL_MAX_*
+NSTEP_MAX = 16                                        # include/fbdqn.h FB_NSTEP_MAX
 
 _vp, _i, _i64, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 
@@ -55,6 +56,8 @@ SIGNATURES = {
     "fb_replay_profile_gather": [_vp, _i] + [_vp] * 6 + [_i, _vp],
     "fb_replay_update_priorities": [_vp, _i, _vp, _vp, _vp, _vp],
     "fb_replay_set_per_mode": [_vp, _i],
+    "fb_replay_set_n_step": [_vp, _i, _d],
+    "fb_replay_get_n_step": [_vp, _vp, _vp],
     "fb_replay_size": [_vp, _vp],
     "fb_replay_per_tree": [_vp] * 5,
     "fb_replay_state_bytes": [_vp, _vp],

@@ -117,9 +117,11 @@ struct FbEvalRider {
     unsigned long long step;                   // this launch's vector step (0-based)
 };
 // fb_replay_gather as a rider of another module's launch (fb_gather.h; B == 0: no rider): what the kernel needs of the ring
+// nstep / gamma: the memory's n-step view (fb_replay_set_n_step; nstep = 1: the one-step transition, gamma unused)
 struct FbGatherCtx {
     long long cap; int n_envs, t_f, kind;
     const unsigned long long *bits; const uint8_t *act; const float *rew; const uint8_t *term; int *error;
+    int nstep; double gamma;
 };
 struct FbGatherRider { FbGatherCtx c; long long steps; int B; const long long *idx; uint8_t *s, *s2, *a; float *r; uint8_t *t; };
 int fb_replay_gather_rider(fb_replay_t h, int batch, const int64_t *idx, uint8_t *s, uint8_t *s2, uint8_t *a, float *r, uint8_t *t,
@@ -197,6 +199,10 @@ int fb_qnet_check_step(fb_qnet_t h, int n_envs, int train_batch);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);
+// n-step memories (fb_replay_set_n_step): the gamma a ring-fed training call was given must be the memory's (FB_OK, else FB_ERR_INVALID
+// with fb_last_error naming `who`); the discount its bootstrap then takes is Gamma = gamma^n (the running product), `gamma` itself at n = 1
+int fb_replay_check_gamma(fb_replay_t h, double gamma, const char *who);
+double fb_replay_bootstrap_gamma(fb_replay_t h, double gamma);
 int fb_replay_update_priorities_keep(fb_replay_t h, int batch, const int64_t *idx, const float *abs_err, void *stream);       // in line, abs_err left untouched (fb_vec_step)
 int fb_replay_update_priorities_ahead(fb_replay_t h, int batch, const int64_t *idx, const float *abs_err, void *stream);      // batch_update on the side stream (see fb_replay.hip); 1 when issued
 int fb_replay_per_store_ahead(fb_replay_t h, void *stream);

@@ -103,7 +103,10 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
     FB_REQUIRE(replay && net && idx && s && s2 && a && r && t && loss && n_steps >= 1, "fb_train_steps: bad argument");
     FB_REQUIRE(algo != FB_ALGO_PER, "fb_train_steps: prioritized replay needs the importance weights: use the separate calls");
     static const bool gathered_form = getenv("FB_TRAIN_STEPS_GATHER") && atoi(getenv("FB_TRAIN_STEPS_GATHER")) == 1;
-    int rc = fb_replay_sample(replay, batch, nullptr, idx, nullptr, stream);
+    int rc = fb_replay_check_gamma(replay, gamma, "fb_train_steps");
+    if (rc != FB_OK) return rc;
+    gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: the ring readers / gathers deliver (R, done), the target takes Gamma)
+    rc = fb_replay_sample(replay, batch, nullptr, idx, nullptr, stream);
     if (!gathered_form) {
         for (int i = 0; rc == FB_OK && i < n_steps; i++) {
             int64_t *cur = idx + (size_t)(i & 1) * batch, *nxt = idx + (size_t)((i + 1) & 1) * batch;
@@ -267,7 +270,10 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     {
         const int rc0 = fb_qnet_check_step(net, n_envs, train ? batch : -1);
         if (rc0 != FB_OK) return rc0;
+        const int rc1 = fb_replay_check_gamma(replay, gamma, "fb_vec_step");
+        if (rc1 != FB_OK) return rc1;
     }
+    gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: every train step below bootstraps with Gamma = gamma^n)
     // ---- The split schedule (uniform memory, small batches): act(k) and train(k) of the reference's loop BOTH read the weights Adam(k - 1)
     // left -- what orders them is the replay append between them (FlappyBirdDQN.py:72-76, BrainDQN.py:236-240), and that only matters when
     // the minibatch holds one of the n_envs transitions this very step appends (32 draws from a million slots: ~3 % of the steps).  So
@@ -407,8 +413,11 @@ extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo,
     FB_REQUIRE(algo >= 0 && algo <= 3, "fb_train_from_replay: unknown algo %d", algo);
     FB_REQUIRE(algo != FB_ALGO_PER || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
     FB_REQUIRE(batch >= 1 && batch <= 256, "fb_train_from_replay: batch must be in 1..256");
+    int rc = fb_replay_check_gamma(replay, gamma, "fb_train_from_replay");
+    if (rc != FB_OK) return rc;
+    gamma = fb_replay_bootstrap_gamma(replay, gamma);
     FbRingSrc ring;
-    int rc = fb_replay_ring_src(replay, batch, idx, a, r, t, &ring);
+    rc = fb_replay_ring_src(replay, batch, idx, a, r, t, &ring);
     if (rc != FB_OK) return rc;
     // the conv planes are always current (adam_fused_kernel; init / load / sync re-split eagerly).  Only a batch of >= 256 also reads
     // W_fc1's planes (fc1_sp_kernel), which Adam leaves stale: re-split them on sight (two guarded launches)

@@ -20,10 +20,41 @@ __device__ __forceinline__ void fb_ring_locate(const FbGatherCtx &P, long long s
         g = d + P.cap * ((total - 1 - d) / P.cap);  // newest transition living in data slot d
     } else {
         const long long size = total < P.cap ? total : P.cap;
-        if (j < 0 || j >= size) { if (flag) *P.error = 1; j = 0; }
+        // (n-step view: the newest (n - 1) x N positions are not complete yet -- their frame t + n has not been pushed)
+        if (j < 0 || j >= size - (long long)(P.nstep - 1) * P.n_envs) { if (flag) *P.error = 1; j = 0; }
         g = total - size + j;                       // deque position j, 0 = oldest
     }
     tt = g / P.n_envs; e = (int)(g - tt * P.n_envs);
+}
+
+// The n-step return of transition (tt, e) of a memory viewed with n = P.nstep > 1 steps (include/fbdqn.h fb_replay_set_n_step):
+// m = n, or k + 1 for the first k < n with term[tt + k] = 1; R = (float) sum_{k < m} g_k * (double) rew[tt + k], ascending k, g_0 = 1,
+// g_{k+1} = g_k * gamma; done = some term[tt + k] = 1, k < n.  All n row loads are issued before any of them is used.  Rows tt .. tt + n - 1
+// are n consecutive time slots: slot (tt % t_f) + k wraps at most once because n <= FB_NSTEP_MAX and cap >= n * N give t_f >= n + 6.
+__device__ __forceinline__ void fb_nstep_return(const FbGatherCtx &P, long long tt, int e, float &R, uint8_t &done) {
+    const int n = P.nstep, s0 = (int)(tt % P.t_f);
+    float rw[FB_NSTEP_MAX];
+    uint8_t tm[FB_NSTEP_MAX];
+#pragma unroll
+    for (int k = 0; k < FB_NSTEP_MAX; k++) {
+        rw[k] = 0.0f; tm[k] = 0;
+        if (k < n) {
+            const int sk = s0 + k < P.t_f ? s0 + k : s0 + k - P.t_f;
+            const size_t mo = (size_t)sk * P.n_envs + e;
+            rw[k] = P.rew[mo]; tm[k] = P.term[mo];
+        }
+    }
+    double acc = 0.0, g = 1.0;
+    bool stop = false;
+#pragma unroll
+    for (int k = 0; k < FB_NSTEP_MAX; k++) {
+        if (k < n && !stop) {
+            acc += g * (double)rw[k];
+            g *= P.gamma;
+            stop = tm[k] != 0;
+        }
+    }
+    R = (float)acc; done = stop ? 1 : 0;
 }
 
 // One thread expands 4 pixels x 4 stacked frames = 16 contiguous bytes of s (and of s').
@@ -56,12 +87,18 @@ __device__ __forceinline__ void gather_body(const FbGatherCtx &P, long long step
     o.z = expand4(n[0], n[1], n[2], n[3], 2); o.w = expand4(n[0], n[1], n[2], n[3], 3);
     s[tid] = o;
     if (!CURRENT) {
+        if (P.nstep > 1) {                              // n-step view: s' = frames tt + n - 3 .. tt + n (n[4] went unused)
+#pragma unroll
+            for (int k = 1; k < 5; k++) n[k] = (uint32_t)(P.bits[fb_frame_off(P, tt + P.nstep - 4 + k, e) + w] >> sh) & 0xFu;
+        }
         o.x = expand4(n[1], n[2], n[3], n[4], 0); o.y = expand4(n[1], n[2], n[3], n[4], 1);
         o.z = expand4(n[1], n[2], n[3], n[4], 2); o.w = expand4(n[1], n[2], n[3], n[4], 3);
         s2[tid] = o;
         if (chunk == 0) {
             const size_t mo = (size_t)(tt % P.t_f) * P.n_envs + e;
-            a[b] = P.act[mo]; r[b] = P.rew[mo]; t[b] = P.term[mo];
+            a[b] = P.act[mo];
+            if (P.nstep > 1) fb_nstep_return(P, tt, e, r[b], t[b]);
+            else { r[b] = P.rew[mo]; t[b] = P.term[mo]; }
         }
     }
 }

@@ -905,7 +905,11 @@ struct C23T {
 #define C23T_EXIT 0
 #endif
 // W16 (ring-fed, small batches): sixteen waves per workgroup -- conv1's 13 tiles in ONE round instead of two; waves 8 .. 15 leave after it
-template <int NS, bool RING, bool W16 = false>
+// NST (ring-fed, a memory viewed with n > 1 steps, fb_replay_set_n_step): the s' slices read frames tt + n - 3 .. tt + n (their fshift is n,
+// set on the host), and the workgroup that writes a / r / t forms the n-step return: lanes 0 .. n - 1 of wave 0 load row tt + k each (all
+// n loads in flight at once), a ballot finds the first terminal and the rewards are summed through shuffles in ascending k
+// (fb_nstep_return's arithmetic); lane 0 writes.  NST = false is the one-step kernel as it was.
+template <int NS, bool RING, bool W16 = false, bool NST = false>
 __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_eu(4))) void conv23_t_kernel(C23T a) {      // <= 128 registers: two workgroups per CU
     constexpr int NPL = NS == 3 ? 2 : 1, P0 = NS == 3 ? 0 : 2;
     constexpr int IN_P = 400, C2_P = 200, C2O = NPL * IN_P, ZOFF = C2O + NPL * C2_P, RED = ZOFF + 16;
@@ -958,16 +962,41 @@ __global__ __launch_bounds__(W16 ? 1024 : 512) __attribute__((amdgpu_waves_per_e
         const int t5 = tid & 511;                                             // (W16: threads 512 .. 1023 repeat the first half's copies)
         const uint4 wc0 = w1g[t5], wc1 = w1g[t5 + 512], wc2 = w1g[t5 + 1024], wc3 = w1g[t5 + 1536];
         // ---- where the state lives: frames tt - 3 + fshift .. of env e (four threads, one frame offset each)
-        if (tid < 4) {
-            long long tt; int e;
-            fb_ring_locate(a.ring.c, a.ring.steps, a.ring.idx[blockIdx.x], tid == 0 && blockIdx.y == 0, tt, e);
-            const unsigned long long o = fb_frame_off(a.ring.c, tt - 3 + s.fshift + tid, e);
-            fo[tid] = o;
-            if (blockIdx.y == 0) {
-                a.ring_fo[blockIdx.x * 4 + tid] = o;                   // conv1's weight-gradient kernel builds its image from the same frames
-                if (tid == 0) {
-                    const size_t mo = (size_t)(tt % a.ring.c.t_f) * a.ring.c.n_envs + e;
-                    a.ring.a[blockIdx.x] = a.ring.c.act[mo]; a.ring.r[blockIdx.x] = a.ring.c.rew[mo]; a.ring.t[blockIdx.x] = a.ring.c.term[mo];
+        if constexpr (!NST) {
+            if (tid < 4) {
+                long long tt; int e;
+                fb_ring_locate(a.ring.c, a.ring.steps, a.ring.idx[blockIdx.x], tid == 0 && blockIdx.y == 0, tt, e);
+                const unsigned long long o = fb_frame_off(a.ring.c, tt - 3 + s.fshift + tid, e);
+                fo[tid] = o;
+                if (blockIdx.y == 0) {
+                    a.ring_fo[blockIdx.x * 4 + tid] = o;                   // conv1's weight-gradient kernel builds its image from the same frames
+                    if (tid == 0) {
+                        const size_t mo = (size_t)(tt % a.ring.c.t_f) * a.ring.c.n_envs + e;
+                        a.ring.a[blockIdx.x] = a.ring.c.act[mo]; a.ring.r[blockIdx.x] = a.ring.c.rew[mo]; a.ring.t[blockIdx.x] = a.ring.c.term[mo];
+                    }
+                }
+            }
+        } else {
+            if (tid < FB_NSTEP_MAX) {                                      // (lanes of wave 0)
+                long long tt; int e;
+                fb_ring_locate(a.ring.c, a.ring.steps, a.ring.idx[blockIdx.x], tid == 0 && blockIdx.y == 0, tt, e);
+                if (tid < 4) {
+                    const unsigned long long o = fb_frame_off(a.ring.c, tt - 3 + s.fshift + tid, e);
+                    fo[tid] = o;
+                    if (blockIdx.y == 0) a.ring_fo[blockIdx.x * 4 + tid] = o;
+                }
+                if (blockIdx.y == 0) {
+                    // lane k < n: row tt + k (rows are consecutive time slots, wrapping at most once: t_f >= n + 6); lanes past n read row tt
+                    const FbGatherCtx &c = a.ring.c;
+                    const int n = c.nstep, k = tid < n ? tid : 0, s0 = (int)(tt % c.t_f), sk = s0 + k < c.t_f ? s0 + k : s0 + k - c.t_f;
+                    const size_t mo = (size_t)sk * c.n_envs + e;
+                    const float rw = c.rew[mo];
+                    const unsigned long long tmask = __ballot(tid < n && c.term[mo] != 0);
+                    if (tid == 0) a.ring.a[blockIdx.x] = c.act[mo];
+                    const int m = tmask ? __builtin_ctzll(tmask) + 1 : n;       // (uniform) the first terminal ends the sum
+                    double acc = 0.0, g = 1.0;
+                    for (int q = 0; q < m; q++) { acc += g * (double)__shfl(rw, q); g *= c.gamma; }
+                    if (tid == 0) { a.ring.r[blockIdx.x] = (float)acc; a.ring.t[blockIdx.x] = tmask ? 1 : 0; }
                 }
             }
         }
@@ -3486,7 +3515,13 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         if (sp) { c23t.a3s = h->a3s; c23t.pl3 = pl2; }      // >= 256 states per slice: fc1_sp_kernel follows and reads conv3's output as planes
         c23t.ring = *p.ring; c23t.p1o = h->p1; c23t.amax = h->amax; c23t.ring_fo = h->ring_fo;
         const bool w16 = maxc * p.ns <= 256;          // at most one workgroup per CU anyway: spend the idle SIMD slots on conv1's second round
-        if (nsp == 3 && w16) hipLaunchKernelGGL((conv23_t_kernel<3, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
+        if (p.ring->c.nstep > 1) {                    // n-step view: the same kernels with the n-step return (NST)
+            if (nsp == 3 && w16) hipLaunchKernelGGL((conv23_t_kernel<3, true, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
+            else if (nsp == 3) hipLaunchKernelGGL((conv23_t_kernel<3, true, false, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
+            else if (w16) hipLaunchKernelGGL((conv23_t_kernel<1, true, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
+            else hipLaunchKernelGGL((conv23_t_kernel<1, true, false, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
+        }
+        else if (nsp == 3 && w16) hipLaunchKernelGGL((conv23_t_kernel<3, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
         else if (nsp == 3) hipLaunchKernelGGL((conv23_t_kernel<3, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
         else if (w16) hipLaunchKernelGGL((conv23_t_kernel<1, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
         else hipLaunchKernelGGL((conv23_t_kernel<1, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
@@ -3900,6 +3935,8 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     p.G = flat_grad ? flat_grad : h->grad;
     p.apply_adam = flat_grad == nullptr; p.tick = true;
     p.ring = ring;
+    if (ring && ring->c.nstep > 1)                   // n-step view: s' = frames tt + n - 3 .. tt + n
+        for (int z = 0; z < p.ns; z++) if (p.sl.s[z].fshift) p.sl.s[z].fshift = ring->c.nstep;
     *out = p;
     return FB_OK;
 }

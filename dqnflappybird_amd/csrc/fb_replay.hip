@@ -16,6 +16,14 @@
 //   with N = 1 this is exactly the reference's deque, with N > 1 it is the deque that N envs
 //   appending in env order would build.  T_f = ceil(cap / N) + 6 time slots keep every frame a
 //   live transition needs.
+//   n-step view (fb_replay_set_n_step, n <= 16, cap >= n N): transition (t, e) reads frames t-3..t (s),
+//   t+n-3..t+n (s') and rows t..t+n-1.  After S pushes frames 0..S and rows 0..S-1 exist; the
+//   population is the oldest min(len, cap) - (n-1) N deque positions, i.e. t <= S - n, so the newest
+//   frame read is S and the newest row S - 1.  The oldest live transition is the one of n = 1:
+//   t0 = floor((S N - min(S N, cap)) / N) >= S - ceil(cap / N), its oldest frame t0 - 3.  Frames
+//   t0-3 .. S span S - t0 + 4 <= ceil(cap / N) + 4 < T_f slots, and the push in flight (frame S+1, row
+//   S) lands on slots t0-3 .. S do not use (S + 1 - (t0 - 3) <= ceil(cap / N) + 4 < T_f): the ring
+//   needs no extra slot for any n.
 //   PER: tree/maxt/mint f64[2*cap-1] array heaps.  `tree` is the reference's SumTree, updated with
 //   the same sequence of floating-point operations (so its bytes are the reference's bytes);
 //   maxt / mint replace the reference's O(capacity) np.max / min scans (max and min are exact and
@@ -48,6 +56,7 @@ struct ReplayParams {
     FbMT *mt;
     int rng_kind;
     uint32_t seed_lo, seed_hi;
+    int nstep; double gamma;         // n-step view (fb_replay_set_n_step): host-side setting, passed by value into every launch
 };
 
 #include "fb_sampler.h"
@@ -106,7 +115,14 @@ __global__ __launch_bounds__(64) void push_kernel(ReplayParams P, long long step
 
 // ------------------------------------------------------------------ gather (minibatch assembly): fb_gather.h
 __host__ __device__ __forceinline__ FbGatherCtx gather_ctx(const ReplayParams &P) {
-    return FbGatherCtx{P.cap, P.n_envs, P.t_f, P.kind, P.bits, P.act, P.rew, P.term, &P.dev->error};
+    return FbGatherCtx{P.cap, P.n_envs, P.t_f, P.kind, P.bits, P.act, P.rew, P.term, &P.dev->error, P.nstep, P.gamma};
+}
+
+// the sampleable population after `steps` pushes: min(len, cap) minus the (n - 1) N newest positions an n-step view cannot complete
+// yet (may be <= 0: the sampler then fails like random.sample on a too small population)
+__host__ __device__ __forceinline__ long long population(const ReplayParams &P, long long steps) {
+    const long long total = steps * P.n_envs;
+    return (total < P.cap ? total : P.cap) - (long long)(P.nstep - 1) * P.n_envs;
 }
 
 template <bool CURRENT>
@@ -119,8 +135,7 @@ __global__ __launch_bounds__(256) void gather_kernel(ReplayParams P, long long s
 
 // ------------------------------------------------------------------ MT19937 on one wave + random.sample: fb_sampler.h
 __device__ __forceinline__ FbSampleCtx sample_ctx(const ReplayParams &P, long long steps) {
-    const long long total = steps * P.n_envs;
-    return FbSampleCtx{P.mt, &P.dev->error, total < P.cap ? total : P.cap};
+    return FbSampleCtx{P.mt, &P.dev->error, population(P, steps)};
 }
 
 __global__ __launch_bounds__(64) void sample_cpython_kernel(ReplayParams P, int k, long long setsize,
@@ -169,8 +184,7 @@ __global__ __launch_bounds__(64) void push_sample_kernel(ReplayParams P, long lo
 
 __global__ void sample_philox_kernel(ReplayParams P, int k, long long *__restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = P.dev->steps * P.n_envs;
-    const long long n = total < P.cap ? total : P.cap;
+    const long long n = population(P, P.dev->steps);
     const unsigned int call = P.dev->philox_calls;
     if (i < k) {
         const fb_u4 o = fb_philox(P.seed_lo, P.seed_hi, (uint32_t)i, call, FB_STREAM_SAMPLE, 0u);
@@ -765,6 +779,7 @@ extern "C" int fb_replay_create(int64_t capacity, int n_envs, int kind, fb_repla
     memset(h, 0, sizeof(*h));
     ReplayParams &P = h->P;
     P.cap = capacity; P.n_envs = n_envs; P.kind = kind;
+    P.nstep = 1; P.gamma = 0.0;
     P.t_f = (int)((capacity + n_envs - 1) / n_envs) + 6;
     const size_t slots = (size_t)P.t_f * n_envs;
     // (the ring and its rows start as zeros: slots that have never been pushed to hold nothing of an earlier allocation, and equal
@@ -971,6 +986,36 @@ extern "C" int fb_replay_push_sample(fb_replay_t h, const uint8_t *frames, const
 
 int fb_replay_num_envs(fb_replay_t h) { return h ? h->P.n_envs : 0; }
 
+extern "C" int fb_replay_set_n_step(fb_replay_t h, int n, double gamma) {
+    FB_REQUIRE(h, "fb_replay_set_n_step: NULL handle");
+    FB_REQUIRE(h->P.kind == FB_REPLAY_UNIFORM, "fb_replay_set_n_step: n-step returns need a uniform memory");
+    FB_REQUIRE(n >= 1 && n <= FB_NSTEP_MAX, "fb_replay_set_n_step: n = %d is outside 1..%d", n, FB_NSTEP_MAX);
+    FB_REQUIRE(h->P.cap >= (long long)n * h->P.n_envs, "fb_replay_set_n_step: capacity %lld < n x n_envs = %lld", (long long)h->P.cap,
+               (long long)n * h->P.n_envs);
+    h->P.nstep = n;
+    h->P.gamma = n > 1 ? gamma : 0.0;
+    return FB_OK;
+}
+
+extern "C" int fb_replay_get_n_step(fb_replay_t h, int *n_host, double *gamma_host) {
+    FB_REQUIRE(h && n_host && gamma_host, "fb_replay_get_n_step: NULL argument");
+    *n_host = h->P.nstep; *gamma_host = h->P.gamma;
+    return FB_OK;
+}
+
+int fb_replay_check_gamma(fb_replay_t h, double gamma, const char *who) {
+    FB_REQUIRE(h->P.nstep == 1 || gamma == h->P.gamma, "%s: gamma %.17g differs from the gamma %.17g of the memory's %d-step view", who, gamma,
+               h->P.gamma, h->P.nstep);
+    return FB_OK;
+}
+
+double fb_replay_bootstrap_gamma(fb_replay_t h, double gamma) {
+    if (h->P.nstep == 1) return gamma;
+    double g = 1.0;                                      // g_n of the running product (the same products the kernels form for g_k)
+    for (int k = 0; k < h->P.nstep; k++) g *= h->P.gamma;
+    return g;
+}
+
 int fb_replay_is_prioritized(fb_replay_t h) { return h && h->P.kind == FB_REPLAY_PER; }
 
 int fb_replay_begin_push_rider(fb_replay_t h, FbPushRider *push) {
@@ -995,8 +1040,7 @@ int fb_replay_gather_rider(fb_replay_t h, int batch, const int64_t *idx, uint8_t
 int fb_replay_sample_rider(fb_replay_t h, int batch, int64_t *idx, FbSampleRider *rider, int pushes_ahead) {
     const ReplayParams &P = h->P;
     if (P.kind != FB_REPLAY_UNIFORM || P.rng_kind != FB_RNG_CPYTHON || batch < 1 || batch > MAXB || !idx) return 0;
-    const long long total = (h->host_steps + pushes_ahead) * P.n_envs;
-    rider->ctx = FbSampleCtx{P.mt, &P.dev->error, total < P.cap ? total : P.cap};
+    rider->ctx = FbSampleCtx{P.mt, &P.dev->error, population(P, h->host_steps + pushes_ahead)};
     rider->k = batch; rider->setsize = cpython_setsize(batch); rider->out = (long long *)idx;
     return 1;
 }
@@ -1005,7 +1049,9 @@ int fb_replay_sample_gated(fb_replay_t h, int batch, int64_t *idx, const FbSplit
     FbSampleRider r;
     if (!h || !ctx || !fb_replay_sample_rider(h, batch, idx, &r, 1)) return 0;
     r.ctx.gate = ctx->f; r.ctx.gate_val = ctx->seq; r.ctx.wait_last_round = wait_last_round;
-    r.ctx.newest_from = r.ctx.n - h->P.n_envs;          // deque positions of the transitions the coming push appends
+    // deque positions whose data the coming push writes: at n = 1 the transitions it appends; in an n-step view the transitions that read
+    // its row S or its frame S + 1 -- time slot S + 1 - n, the newest N positions of the n-step population (r.ctx.n is that population)
+    r.ctx.newest_from = r.ctx.n - h->P.n_envs;
     hipLaunchKernelGGL(sample_gated_kernel, dim3(1), dim3(64), 0, fb_stream(stream), r);
     return hipGetLastError() == hipSuccess;
 }

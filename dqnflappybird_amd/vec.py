@@ -213,6 +213,24 @@ class VecReplay:
         L.check(L.lib().fb_replay_set_per_mode(self.h, {"exact": L.PER_EXACT, "fast": L.PER_FAST}[mode]),
                 "fb_replay_set_per_mode")
 
+    def set_n_step(self, n, gamma):
+        """View the memory with n-step returns (fb_replay_set_n_step; uniform memories, 1 <= n <= 16, capacity >= n * n_envs): sample /
+        gather / the ring-fed train calls then see (s_t, a_t, R, s_{t+n}, done) and bootstrap with gamma^n.  n = 1 restores the one-step
+        memory.  Nothing stored changes; the training calls on it must be given this gamma."""
+        L.check(L.lib().fb_replay_set_n_step(self.h, int(n), float(gamma)), "fb_replay_set_n_step")
+
+    @property
+    def n_step(self):
+        """(n, gamma) of the memory's view; (1, 0.0) for the one-step memory."""
+        n, g = C.c_int(), C.c_double()
+        L.check(L.lib().fb_replay_get_n_step(self.h, C.byref(n), C.byref(g)), "fb_replay_get_n_step")
+        return n.value, g.value
+
+    @property
+    def population(self):
+        """deque positions sample() draws from: len(memory) less the (n - 1) * n_envs newest an n-step view cannot complete yet."""
+        return max(0, len(self) - (self.n_step[0] - 1) * self.n)
+
     def __len__(self):
         v = C.c_int64()
         L.check(L.lib().fb_replay_size(self.h, C.byref(v)), "fb_replay_size")
@@ -240,6 +258,17 @@ class VecReplay:
 
 
 ALGOS = {"dqn": L.ALGO_DQN, "nature": L.ALGO_NATURE, "double": L.ALGO_DOUBLE, "per": L.ALGO_PER, "pg": L.ALGO_PG}
+
+
+def bootstrap_gamma(gamma, n):
+    """Gamma = g_n of the n-step return (g_0 = 1, g_{k+1} = g_k * gamma in float64): the discount an n-step target bootstraps with,
+    and what QNet.train_step takes on a minibatch gathered from an n-step memory.  gamma itself at n = 1."""
+    if int(n) == 1:
+        return float(gamma)
+    g = 1.0
+    for _ in range(int(n)):
+        g *= float(gamma)
+    return g
 
 
 class QNet:
@@ -405,6 +434,7 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
     """replay.gather(idx) + net.train_step(...) without the gathered copies (fb_train_from_replay): the conv trunk reads the sampled
     transitions' 1-bit frames in the ring directly.  Same results as the two calls (batch <= 256).  Prioritized replay: idx are the
     SumTree leaf indices of replay.sample, isw its importance weights; want_abs_err returns |TD error| for update_priorities.
+    An n-step memory (replay.set_n_step) is read as (s, a, R, s', done) and bootstrapped with gamma^n; gamma must be the memory's.
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, abs_err f32[B]]) on the device."""
     if (replay.prioritized or algo == "per") and isw is None:
         raise ValueError("the prioritized step needs the importance weights (isw)")
@@ -423,7 +453,8 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
 
 class TrainSteps:
     """n x (random.sample -> minibatch -> _trainQNetwork) on a uniform memory that is not being pushed to, as one host call
-    (fb_train_steps): the separate calls' results, with the next step's random.sample riding in the conv3 backward launch."""
+    (fb_train_steps): the separate calls' results, with the next step's random.sample riding in the conv3 backward launch.  On an
+    n-step memory gamma must be the memory's (the steps bootstrap with gamma^n)."""
 
     def __init__(self, replay, net, batch=32, algo="dqn", gamma=0.99):
         if replay.prioritized or algo == "per":

@@ -80,10 +80,23 @@ class HipVecBackend:
 class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99,
-                 replace_target_iter=500, sampler=None, rank=0, world=1, backend=None):
+                 replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1):
+        """n_step > 1: learn from n-step returns (the replay's n-step view, include/fbdqn.h fb_replay_set_n_step) -- uniform replay only."""
+        n_step = int(n_step)
+        if not 1 <= n_step <= 16:
+            raise ValueError(f"n_step must be in 1..16, got {n_step}")
+        if n_step > 1 and algo == "per":
+            raise ValueError("n-step returns need a uniform replay memory: algo 'per' takes n_step = 1")
         be = backend or HipVecBackend()
         self.be = be
         self.n, self.algo, self.batch, self.gamma = n_envs, algo, batch, gamma
+        self.n_step = n_step
+        self.boot_gamma = float(gamma)                       # Gamma = gamma^n as the running product (vec.bootstrap_gamma)
+        if n_step > 1:
+            g = 1.0
+            for _ in range(n_step):
+                g *= float(gamma)
+            self.boot_gamma = g
         self.rank, self.world = rank, world
         self.observe, self.explore = observe, explore
         self.epsilon, self.initial_epsilon, self.final_epsilon = initial_epsilon, initial_epsilon, final_epsilon
@@ -92,6 +105,10 @@ class VecBrain:
         self.env = be.env(n_envs, seed + 1000003 * rank)     # envs shard by rank: every rank plays its own games
         self.replay = be.replay(capacity, n_envs, algo == "per")     # ... into its own replay shard
         self.replay.seed(seed + rank, sampler)
+        if n_step > 1:                                       # (only then: a backend without n-step memories keeps working at n = 1)
+            if not hasattr(self.replay, "set_n_step"):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend's replay has no n-step view (n_step = {n_step})")
+            self.replay.set_n_step(n_step, gamma)
         self.net = be.net(2, fc_width, arch, max(n_envs, batch))
         self.net.init_params(seed=seed, which=0)             # the same draw on every rank
         self.net.init_params(seed=seed + 1, which=1)
@@ -137,7 +154,7 @@ class VecBrain:
             loss, abs_err = self.be.train_from_replay(self.replay, self.net, self.algo, idx, isw, self.gamma, self.grad, self.algo == "per")
         else:
             s, a, r, s2, t = self.replay.gather(idx)
-            loss, abs_err, _ = self.net.train_step(self.algo, s, a, r, s2, t, isw=isw, gamma=self.gamma, flat_grad=self.grad,
+            loss, abs_err, _ = self.net.train_step(self.algo, s, a, r, s2, t, isw=isw, gamma=self.boot_gamma, flat_grad=self.grad,
                                                    want_aux=self.algo == "per")
         if self.grad is not None:
             self.reduce()
@@ -218,7 +235,7 @@ class VecBrain:
             m, v, pows = self.net.adam_state()
             shared = dict(online=host(self.net.store_params(0)), target=host(self.net.store_params(1)), adam_m=host(m), adam_v=host(v),
                           beta_pows=np.asarray(pows, np.float32), scalars=np.array([self.timeStep, self.onlineTimeStep, self.world, self.seed], np.int64),
-                          epsilon=np.array([self.epsilon], np.float64))
+                          epsilon=np.array([self.epsilon], np.float64), n_step=np.array([self.n_step], np.int64))
         if self.world == 1:
             np.savez(self._npz(path), **shared, **local)
             return
@@ -235,6 +252,9 @@ class VecBrain:
         saved_world = int(z["scalars"][2]) if len(z["scalars"]) > 2 else 1
         if saved_world != self.world:
             raise ValueError(f"checkpoint {path} was written by {saved_world} rank(s), this job has {self.world}")
+        saved_n = int(z["n_step"][0]) if "n_step" in z.files else 1          # (checkpoints from before n-step returns: one-step)
+        if saved_n != self.n_step:
+            raise ValueError(f"checkpoint {path} was trained with n_step = {saved_n}, this VecBrain has n_step = {self.n_step}")
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         self.net.load_params(z["online"], 0)

@@ -202,6 +202,31 @@ int fb_replay_update_priorities(fb_replay_t h, int batch, const int64_t *idx, fl
 #define FB_PER_EXACT 0
 #define FB_PER_FAST 1
 int fb_replay_set_per_mode(fb_replay_t h, int mode);
+/* n-step returns (Ape-X / R2D2 style) as a different READ of the same ring -- nothing new is stored, the state blob is unchanged.
+ * With n steps and discount gamma, transition t of env e (the deque position j of the one-step memory, see below) is
+ *   s      frames t-3 .. t of env e (as at n = 1), a = act[t]
+ *   R      m = n, or k + 1 for the first k < n with term[t+k] = 1;  R = (float) sum_{k<m} g_k * (double) rew[t+k], summed in ascending k,
+ *          g_0 = 1.0, g_{k+1} = g_k * gamma in double (rounded to float once)
+ *   done   1 iff some term[t+k] = 1, k < n
+ *   s'     frames t+n-3 .. t+n of env e, always (when done the target masks it out)
+ *   target y = done ? R : R + Gamma * maxQ'(s') in float64, Gamma = g_n: the one-step formula with (r, term, gamma) -> (R, done, Gamma);
+ *          Double / dueling unchanged.
+ * Population: after S pushes transition t is complete once frame t+n exists (t <= S-n): the sampleable population is the oldest
+ * min(len, cap) - (n-1) * N deque positions, and deque position j names the same transition as at n = 1.  random.sample (CPython
+ * generator, bit-exact against random.sample(range(population), B)) and the Philox sampler draw over that population; an index beyond
+ * it is an out-of-range index for fb_replay_gather / fb_train_from_replay.  fb_replay_size stays len(memory).
+ * Split schedule of fb_vec_step: the only transitions whose data the coming push writes (frame S+1, row S) are those of time slot S+1-n,
+ * the NEWEST N positions of the post-push n-step population -- so the gated draw's dirty rule "some index >= population - N" stays exact.
+ * fb_replay_set_n_step: uniform memories only, 1 <= n <= FB_NSTEP_MAX, capacity >= n * n_envs; anything else is FB_ERR_INVALID and
+ *   changes nothing.  n = 1 restores the one-step memory exactly (gamma is then ignored).  A host-side setting read by the calls issued
+ *   after it: a hipGraph captured earlier keeps the value it was captured with.
+ * Ring-fed training calls on an n > 1 memory (fb_vec_step, fb_vec_step_dp, fb_train_from_replay, fb_train_steps) take `gamma` = the
+ * memory's gamma (anything else is FB_ERR_INVALID before any counter moves or any launch) and bootstrap with Gamma; fb_replay_gather
+ * returns (s, a, R, s', done); fb_qnet_train_step on gathered tensors is unchanged -- pass it Gamma.
+ * fb_replay_get_n_step: the current (n, gamma) [host] (gamma = 0 at n = 1). */
+#define FB_NSTEP_MAX 16
+int fb_replay_set_n_step(fb_replay_t h, int n, double gamma);
+int fb_replay_get_n_step(fb_replay_t h, int *n_host, double *gamma_host);
 /* host-side queries (synchronous): len(replayMemory); PER: tree copy f64[2*cap-1] [host] */
 int fb_replay_size(fb_replay_t h, int64_t *size_host);
 int fb_replay_per_tree(fb_replay_t h, double *tree_host, int64_t *data_pointer, int64_t *size, double *beta);

@@ -6,10 +6,13 @@ across episode ends.  A score curve can.  The reference's own evidence is logs_b
 2 - 4 M single-env steps, BrainDQNNature.py:149-197); no target score is set here, only "clearly above the untrained policy's".
 
     python tools/learn_curve.py [--envs 16,1024] [--lrs 1e-6,1e-5] [--steps 2000000] [--window 50000] [--algo nature] [--out FILE]
+                                [--n-step K] [--eval-envs 4096]
 
 One VecBrain run per (envs, lr); one train step per loop step once onlineTimeStep > OBSERVE, as in the reference.  Every `window`
 steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and zeroed, so each
 row is the window's own figure, not a running average.  Rows go to stdout and to --out as they are produced.
+--n-step K trains from K-step returns (VecBrain(n_step=K)); the summary gives the train steps at which the windowed mean score first
+passed 1 / 10 / 100, and --eval-envs M (> 0) ends each run with VecBrain.evaluate() on M fresh greedy games.
 """
 import argparse
 import os
@@ -23,10 +26,10 @@ import torch  # noqa: E402
 from dqnflappybird_amd.vecbrain import VecBrain  # noqa: E402
 
 
-def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore):
-    vb = VecBrain(n_envs, algo=algo, arch=arch, capacity=1_000_000, seed=seed, explore=explore)
+def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore, n_step=1, eval_envs=0):
+    vb = VecBrain(n_envs, algo=algo, arch=arch, capacity=1_000_000, seed=seed, explore=explore, n_step=n_step)
     vb.net.set_hparams(lr=lr)
-    head = f"# envs {n_envs}  algo {algo}/{arch}  lr {lr:g}  batch {vb.batch}  observe {vb.observe}  explore {vb.explore}  eps {vb.initial_epsilon} -> {vb.final_epsilon}  target sync / {vb.replace_target_iter}"
+    head = f"# envs {n_envs}  algo {algo}/{arch}  n_step {n_step}  lr {lr:g}  batch {vb.batch}  observe {vb.observe}  explore {vb.explore}  eps {vb.initial_epsilon} -> {vb.final_epsilon}  target sync / {vb.replace_target_iter}"
     cols = "#   train_steps   env_steps  epsilon  episodes  mean_score  max_score  pipes/episode      loss   steps/s"
     for f in (sys.stdout, out):
         print(head, file=f); print(cols, file=f); f.flush()
@@ -57,9 +60,19 @@ def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore):
     first = rows[0][4]
     best = max(r[4] for r in rows)
     last = sum(r[4] for r in rows[-3:]) / len(rows[-3:])
+    passed = {lvl: next((r[0] for r in rows if r[4] > lvl), None) for lvl in (1, 10, 100)}
+    cross = ", ".join(f"> {lvl}: {'never' if v is None else v}" for lvl, v in passed.items())
     for f in (sys.stdout, out):
-        print(f"# summary envs {n_envs} lr {lr:g}: mean score first window {first:.3f}, best window {best:.3f}, last three windows {last:.3f}, max score of the run {max(r[5] for r in rows)}; split schedule: {issued} steps, {clean} minibatches beside their env step\n", file=f)
+        print(f"# summary envs {n_envs} n_step {n_step} lr {lr:g}: mean score first window {first:.3f}, best window {best:.3f}, last three windows {last:.3f}, max score of the run {max(r[5] for r in rows)}; split schedule: {issued} steps, {clean} minibatches beside their env step", file=f)
+        print(f"# windowed mean score first passed (train steps): {cross}", file=f)
         f.flush()
+    if eval_envs:
+        res = vb.evaluate(n_envs=eval_envs)
+        for f in (sys.stdout, out):
+            print(f"# evaluate() on {eval_envs} games: mean {res.mean_score:.3f} median {res.median_score:.1f} max {res.max_score}  ({res.summary()})", file=f)
+            f.flush()
+    for f in (sys.stdout, out):
+        print("", file=f)
     del vb
     torch.cuda.synchronize()
 
@@ -74,6 +87,8 @@ def main():
     ap.add_argument("--arch", default="plain")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--explore", type=int, default=1_000_000)
+    ap.add_argument("--n-step", type=int, default=1)
+    ap.add_argument("--eval-envs", type=int, default=0, help="end each run with VecBrain.evaluate() on this many games (0 = no evaluation)")
     ap.add_argument("--budget-s", type=float, default=0.0, help="stop a run after this many seconds (0 = run all its steps)")
     ap.add_argument("--out", default="gpurun_out/learning.txt")
     a = ap.parse_args()
@@ -82,7 +97,7 @@ def main():
         print(f"# tools/learn_curve.py on {torch.cuda.get_device_name(0)}: {' '.join(sys.argv[1:])}", file=out)
         for n_envs in [int(x) for x in a.envs.split(",")]:
             for lr in [float(x) for x in a.lrs.split(",")]:
-                run(n_envs, lr, a.steps, a.window, a.algo, a.arch, a.seed, out, a.budget_s, a.explore)
+                run(n_envs, lr, a.steps, a.window, a.algo, a.arch, a.seed, out, a.budget_s, a.explore, a.n_step, a.eval_envs)
 
 
 if __name__ == "__main__":
