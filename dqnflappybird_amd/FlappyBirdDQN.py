@@ -76,7 +76,8 @@ def main():
         if not args.vec:
             parser.error("--n-step needs --vec: the single-env agents are the reference's one-step algorithms")
         if args.model == "prioritydqn":
-            parser.error("--n-step needs a uniform replay memory: prioritydqn takes --n-step 1")
+            parser.error("--n-step on this command line needs uniform replay: prioritydqn takes --n-step 1 here "
+                         "(prioritized replay with n-step returns is VecBrain(algo='per', n_step=K))")
     if args.vec:
         # one process per GPU (python -m torch.distributed.run --nproc-per-node N -m dqnflappybird_amd.FlappyBirdDQN ...):
         # --vec envs PER RANK, rank-local replay, one RCCL all-reduce of the flat gradient per train step

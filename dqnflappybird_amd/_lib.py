@@ -58,6 +58,7 @@ SIGNATURES = {
     "fb_replay_set_per_mode": [_vp, _i],
     "fb_replay_set_n_step": [_vp, _i, _d],
     "fb_replay_get_n_step": [_vp, _vp, _vp],
+    "fb_replay_create_nstep": [_i64, _i, _i, _i, _d, _vp],
     "fb_replay_size": [_vp, _vp],
     "fb_replay_per_tree": [_vp] * 5,
     "fb_replay_state_bytes": [_vp, _vp],

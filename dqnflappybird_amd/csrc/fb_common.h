@@ -202,6 +202,9 @@ int fb_replay_is_prioritized(fb_replay_t h);
 // n-step memories (fb_replay_set_n_step): the gamma a ring-fed training call was given must be the memory's (FB_OK, else FB_ERR_INVALID
 // with fb_last_error naming `who`); the discount its bootstrap then takes is Gamma = gamma^n (the running product), `gamma` itself at n = 1
 int fb_replay_check_gamma(fb_replay_t h, double gamma, const char *who);
+// prioritized n-step memories (fb_replay_create_nstep): FB_ERR_STATE (fb_last_error naming `who`) when the tree will still be empty
+// once `pushes_ahead` more pushes are counted -- fewer than n pushes since the reset; FB_OK for every other memory
+int fb_replay_check_complete(fb_replay_t h, int pushes_ahead, const char *who);
 double fb_replay_bootstrap_gamma(fb_replay_t h, double gamma);
 int fb_replay_update_priorities_keep(fb_replay_t h, int batch, const int64_t *idx, const float *abs_err, void *stream);       // in line, abs_err left untouched (fb_vec_step)
 int fb_replay_update_priorities_ahead(fb_replay_t h, int batch, const int64_t *idx, const float *abs_err, void *stream);      // batch_update on the side stream (see fb_replay.hip); 1 when issued

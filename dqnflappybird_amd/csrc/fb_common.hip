@@ -272,6 +272,9 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
         if (rc0 != FB_OK) return rc0;
         const int rc1 = fb_replay_check_gamma(replay, gamma, "fb_vec_step");
         if (rc1 != FB_OK) return rc1;
+        // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
+        const int rc2 = train ? fb_replay_check_complete(replay, 1, "fb_vec_step") : FB_OK;
+        if (rc2 != FB_OK) return rc2;
     }
     gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: every train step below bootstraps with Gamma = gamma^n)
     // ---- The split schedule (uniform memory, small batches): act(k) and train(k) of the reference's loop BOTH read the weights Adam(k - 1)
@@ -414,6 +417,8 @@ extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo,
     FB_REQUIRE(algo != FB_ALGO_PER || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
     FB_REQUIRE(batch >= 1 && batch <= 256, "fb_train_from_replay: batch must be in 1..256");
     int rc = fb_replay_check_gamma(replay, gamma, "fb_train_from_replay");
+    if (rc != FB_OK) return rc;
+    rc = fb_replay_check_complete(replay, 0, "fb_train_from_replay");
     if (rc != FB_OK) return rc;
     gamma = fb_replay_bootstrap_gamma(replay, gamma);
     FbRingSrc ring;

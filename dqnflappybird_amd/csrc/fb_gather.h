@@ -15,9 +15,11 @@ __device__ __forceinline__ void fb_ring_locate(const FbGatherCtx &P, long long s
     const long long total = steps * P.n_envs;
     long long g;
     if (P.kind == FB_REPLAY_PER) {
+        // (n-step memory: the tree has received C = max(0, steps - n + 1) N stores, one per COMPLETED transition; C = total at n = 1)
+        const long long cs = steps - (P.nstep - 1), C = cs > 0 ? cs * P.n_envs : 0;
         long long d = j - (P.cap - 1);
-        if (d < 0 || d >= P.cap || d >= total) { if (flag) *P.error = 1; d = 0; }
-        g = d + P.cap * ((total - 1 - d) / P.cap);  // newest transition living in data slot d
+        if (d < 0 || d >= P.cap || d >= C) { if (flag) *P.error = 1; d = 0; }
+        g = C > 0 ? d + P.cap * ((C - 1 - d) / P.cap) : 0;      // newest transition living in data slot d (empty tree: transition 0)
     } else {
         const long long size = total < P.cap ? total : P.cap;
         // (n-step view: the newest (n - 1) x N positions are not complete yet -- their frame t + n has not been pushed)

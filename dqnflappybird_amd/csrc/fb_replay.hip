@@ -24,6 +24,14 @@
 //   t0-3 .. S span S - t0 + 4 <= ceil(cap / N) + 4 < T_f slots, and the push in flight (frame S+1, row
 //   S) lands on slots t0-3 .. S do not use (S + 1 - (t0 - 3) <= ceil(cap / N) + 4 < T_f): the ring
 //   needs no extra slot for any n.
+//   Prioritized n-step memory (fb_replay_create_nstep): the tree holds the newest min(C, cap)
+//   COMPLETED transitions, C = max(0, S - n + 1) N, i.e. deque positions g with C - min(C, cap) <= g < C:
+//   the newest is t = S - n (frames up to S, rows up to S - 1, as above), the oldest
+//   t0 = floor((C - min(C, cap)) / N) >= S - n + 1 - ceil(cap / N), n - 1 slots older than at n = 1.
+//   Its oldest frame t0 - 3 to frame S spans S - t0 + 4 <= ceil(cap / N) + n + 3 slots, and the push in
+//   flight (frame S+1, row S) lands S + 1 - (t0 - 3) <= ceil(cap / N) + n + 3 slots after t0 - 3: with
+//   T_f = ceil(cap / N) + n + 5 > ceil(cap / N) + n + 3 neither wraps onto a slot a live transition
+//   reads (the same 2-slot margin as T_f = ceil(cap / N) + 6 at n = 1, which it equals there).
 //   PER: tree/maxt/mint f64[2*cap-1] array heaps.  `tree` is the reference's SumTree, updated with
 //   the same sequence of floating-point operations (so its bytes are the reference's bytes);
 //   maxt / mint replace the reference's O(capacity) np.max / min scans (max and min are exact and
@@ -770,17 +778,15 @@ static int per_join(fb_replay *h, hipStream_t st) {
     return FB_OK;
 }
 
-extern "C" int fb_replay_create(int64_t capacity, int n_envs, int kind, fb_replay_t *out) {
-    FB_REQUIRE(out, "fb_replay_create: out is NULL");
-    FB_REQUIRE(capacity >= 1 && capacity < (1ll << 22), "fb_replay_create: capacity %lld out of range", (long long)capacity);
-    FB_REQUIRE(n_envs >= 1 && n_envs <= (1 << 22), "fb_replay_create: n_envs out of range");
-    FB_REQUIRE(kind == FB_REPLAY_UNIFORM || kind == FB_REPLAY_PER, "fb_replay_create: kind must be 0 or 1");
+// fb_replay_create / fb_replay_create_nstep once the arguments are checked.  `ring_n`: the n of a prioritized n-step memory (its ring
+// keeps n - 1 extra time slots, see the layout above), 1 otherwise
+static int replay_create(int64_t capacity, int n_envs, int kind, int ring_n, fb_replay_t *out) {
     fb_replay *h = new fb_replay();
     memset(h, 0, sizeof(*h));
     ReplayParams &P = h->P;
     P.cap = capacity; P.n_envs = n_envs; P.kind = kind;
     P.nstep = 1; P.gamma = 0.0;
-    P.t_f = (int)((capacity + n_envs - 1) / n_envs) + 6;
+    P.t_f = (int)((capacity + n_envs - 1) / n_envs) + ring_n + 5;
     const size_t slots = (size_t)P.t_f * n_envs;
     // (the ring and its rows start as zeros: slots that have never been pushed to hold nothing of an earlier allocation, and equal
     // memories save equal checkpoint blobs)
@@ -825,6 +831,30 @@ extern "C" int fb_replay_create(int64_t capacity, int n_envs, int kind, fb_repla
     int rc = fb_replay_seed(h, kind == FB_REPLAY_PER ? FB_RNG_NUMPY : FB_RNG_CPYTHON, 0);
     if (rc != FB_OK) return rc;
     return fb_replay_reset(h, nullptr, nullptr, nullptr);
+}
+
+extern "C" int fb_replay_create(int64_t capacity, int n_envs, int kind, fb_replay_t *out) {
+    FB_REQUIRE(out, "fb_replay_create: out is NULL");
+    FB_REQUIRE(capacity >= 1 && capacity < (1ll << 22), "fb_replay_create: capacity %lld out of range", (long long)capacity);
+    FB_REQUIRE(n_envs >= 1 && n_envs <= (1 << 22), "fb_replay_create: n_envs out of range");
+    FB_REQUIRE(kind == FB_REPLAY_UNIFORM || kind == FB_REPLAY_PER, "fb_replay_create: kind must be 0 or 1");
+    return replay_create(capacity, n_envs, kind, 1, out);
+}
+
+// n fixed from the first push (include/fbdqn.h): every argument is checked before anything is allocated
+extern "C" int fb_replay_create_nstep(int64_t capacity, int n_envs, int kind, int n, double gamma, fb_replay_t *out) {
+    FB_REQUIRE(out, "fb_replay_create_nstep: out is NULL");
+    FB_REQUIRE(capacity >= 1 && capacity < (1ll << 22), "fb_replay_create_nstep: capacity %lld out of range", (long long)capacity);
+    FB_REQUIRE(n_envs >= 1 && n_envs <= (1 << 22), "fb_replay_create_nstep: n_envs out of range");
+    FB_REQUIRE(kind == FB_REPLAY_UNIFORM || kind == FB_REPLAY_PER, "fb_replay_create_nstep: kind must be 0 or 1");
+    FB_REQUIRE(n >= 1 && n <= FB_NSTEP_MAX, "fb_replay_create_nstep: n = %d is outside 1..%d", n, FB_NSTEP_MAX);
+    FB_REQUIRE(capacity >= (long long)n * n_envs, "fb_replay_create_nstep: capacity %lld < n x n_envs = %lld", (long long)capacity,
+               (long long)n * n_envs);
+    const int rc = replay_create(capacity, n_envs, kind, kind == FB_REPLAY_PER ? n : 1, out);
+    if (rc != FB_OK) return rc;
+    (*out)->P.nstep = n;                                 // (the uniform memory: what fb_replay_set_n_step would set)
+    (*out)->P.gamma = n > 1 ? gamma : 0.0;
+    return FB_OK;
 }
 
 extern "C" int fb_replay_destroy(fb_replay_t h) {
@@ -910,6 +940,7 @@ int fb_replay_finish_push(fb_replay_t h, void *stream) {
             FB_CHECK_HIP(hipStreamWaitEvent(st, h->ev_store, 0));
             return FB_OK;
         }
+        if (h->host_steps < P.nstep) return FB_OK;      // n-step memory: push S completes time slot S - n; pushes 1 .. n-1 complete nothing
         const int rcj = per_join(h, st);
         if (rcj != FB_OK) return rcj;
         if (h->per_mode == FB_PER_FAST) hipLaunchKernelGGL(per_store_fast_kernel, dim3(1), dim3(1024), 0, st, P, P.n_envs);
@@ -927,6 +958,7 @@ int fb_replay_finish_push(fb_replay_t h, void *stream) {
 int fb_replay_per_store_ahead(fb_replay_t h, void *stream) {
     // (reference-order mode only: the level-wise FB_PER_FAST store takes ~8 us, less than the two cross-stream hops cost)
     if (!h || h->P.kind != FB_REPLAY_PER || h->store_ahead || h->per_mode == FB_PER_FAST) return 0;
+    if (h->host_steps + 1 < h->P.nstep) return 0;        // (n-step memory: the coming push stores nothing -- fb_replay_finish_push skips it too)
     if (!per_side_usable(h, stream)) return 0;
     hipStream_t st = fb_stream(stream);
     // (behind a run-ahead batch_update the side stream is already ordered after the caller's last touch of the tree -- that update's own
@@ -988,7 +1020,7 @@ int fb_replay_num_envs(fb_replay_t h) { return h ? h->P.n_envs : 0; }
 
 extern "C" int fb_replay_set_n_step(fb_replay_t h, int n, double gamma) {
     FB_REQUIRE(h, "fb_replay_set_n_step: NULL handle");
-    FB_REQUIRE(h->P.kind == FB_REPLAY_UNIFORM, "fb_replay_set_n_step: n-step returns need a uniform memory");
+    FB_REQUIRE(h->P.kind == FB_REPLAY_UNIFORM, "fb_replay_set_n_step: a prioritized memory's n is fixed when it is created: use fb_replay_create_nstep");
     FB_REQUIRE(n >= 1 && n <= FB_NSTEP_MAX, "fb_replay_set_n_step: n = %d is outside 1..%d", n, FB_NSTEP_MAX);
     FB_REQUIRE(h->P.cap >= (long long)n * h->P.n_envs, "fb_replay_set_n_step: capacity %lld < n x n_envs = %lld", (long long)h->P.cap,
                (long long)n * h->P.n_envs);
@@ -1007,6 +1039,12 @@ int fb_replay_check_gamma(fb_replay_t h, double gamma, const char *who) {
     FB_REQUIRE(h->P.nstep == 1 || gamma == h->P.gamma, "%s: gamma %.17g differs from the gamma %.17g of the memory's %d-step view", who, gamma,
                h->P.gamma, h->P.nstep);
     return FB_OK;
+}
+
+int fb_replay_check_complete(fb_replay_t h, int pushes_ahead, const char *who) {
+    if (h->P.kind != FB_REPLAY_PER || h->host_steps + pushes_ahead >= h->P.nstep) return FB_OK;
+    return fb_set_error(FB_ERR_STATE, "%s: the %d-step prioritized memory holds no complete transition before %d pushes since its reset (%lld)", who,
+                        h->P.nstep, h->P.nstep, h->host_steps + pushes_ahead);
 }
 
 double fb_replay_bootstrap_gamma(fb_replay_t h, double gamma) {
@@ -1078,6 +1116,8 @@ int fb_replay_sample_f32(fb_replay_t h, int batch, const double *uniforms, int64
     hipStream_t st = fb_stream(stream);
     if (P.kind == FB_REPLAY_PER) {
         FB_REQUIRE(isw, "fb_replay_sample: PER needs isw");
+        const int rcc = fb_replay_check_complete(h, 0, "fb_replay_sample");
+        if (rcc != FB_OK) return rcc;
         const int rcj = per_join(h, st);
         if (rcj != FB_OK) return rcj;
         hipLaunchKernelGGL(per_sample_kernel, dim3(1), dim3(256), 0, st, P, batch, uniforms, (long long *)idx, isw, isw32);
@@ -1303,9 +1343,15 @@ extern "C" int fb_replay_load_state(fb_replay_t h, const void *blob_host, size_t
     size_t need = 0;
     fb_replay_state_bytes(h, &need);
     FB_REQUIRE(hd.magic == REPLAY_BLOB_MAGIC && hd.version == 1, "fb_replay_load_state: not a replay checkpoint");
-    FB_REQUIRE(hd.cap == h->P.cap && hd.n_envs == h->P.n_envs && hd.kind == h->P.kind && hd.t_f == h->P.t_f && hd.total_bytes == need && bytes >= need,
+    FB_REQUIRE(hd.cap == h->P.cap && hd.n_envs == h->P.n_envs && hd.kind == h->P.kind,
                "fb_replay_load_state: the checkpoint is of a memory with capacity %lld, %d envs, kind %d; this one has %lld, %d, %d",
                (long long)hd.cap, hd.n_envs, hd.kind, (long long)h->P.cap, h->P.n_envs, h->P.kind);
+    // (same capacity, envs and kind: a prioritized memory's ring size T_f = ceil(cap / N) + n + 5 names its n)
+    const int t_f1 = (int)((h->P.cap + h->P.n_envs - 1) / h->P.n_envs) + 6;
+    FB_REQUIRE(hd.t_f == h->P.t_f, "fb_replay_load_state: the checkpoint is of a prioritized memory with n = %d (a ring of %d time slots); this one has "
+               "n = %d (%d)", hd.t_f - t_f1 + 1, hd.t_f, h->P.t_f - t_f1 + 1, h->P.t_f);
+    FB_REQUIRE(hd.total_bytes == need && bytes >= need, "fb_replay_load_state: the checkpoint holds %llu bytes, this memory's state is %zu (%zu given)",
+               (unsigned long long)hd.total_bytes, need, bytes);
     FB_CHECK_HIP(hipDeviceSynchronize());
     BlobPart parts[9];
     const int n = blob_parts(h, parts);

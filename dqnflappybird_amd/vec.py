@@ -115,13 +115,27 @@ class VecReplay:
     """Replay memory in HBM for N envs (BrainDQN.py:36,69-72,197-201;
     BrainPrioritizedReplyDQN.py:32-151).  Frames are stored once, 1 bit per pixel."""
 
-    def __init__(self, capacity, n_envs=1, prioritized=False, device="cuda"):
+    def __init__(self, capacity, n_envs=1, prioritized=False, device="cuda", n_step=1, gamma=None):
+        """n_step > 1: n-step returns from the first push (fb_replay_create_nstep; 1 <= n_step <= 16, capacity >= n_step * n_envs,
+        gamma required).  The only way to give a PRIORITIZED memory n-step returns: its tree stores each transition once it is
+        complete, so n is fixed at creation (include/fbdqn.h).  A uniform memory created so equals one given set_n_step(n_step, gamma)."""
+        self.h = C.c_void_p()
+        n_step = int(n_step)
+        if not 1 <= n_step <= L.NSTEP_MAX:
+            raise ValueError(f"n_step must be in 1..{L.NSTEP_MAX}, got {n_step}")
+        if n_step > 1 and gamma is None:
+            raise ValueError(f"an n-step memory (n_step = {n_step}) needs the gamma of its returns")
+        if int(capacity) < n_step * int(n_envs):
+            raise ValueError(f"capacity {int(capacity)} < n_step x n_envs = {n_step * int(n_envs)}")
         L.require_gpu()
         self.capacity, self.n, self.prioritized = int(capacity), int(n_envs), bool(prioritized)
         self.device = torch.device(device)
-        self.h = C.c_void_p()
-        L.check(L.lib().fb_replay_create(self.capacity, self.n, L.REPLAY_PER if prioritized else L.REPLAY_UNIFORM,
-                                         C.byref(self.h)), "fb_replay_create")
+        kind = L.REPLAY_PER if prioritized else L.REPLAY_UNIFORM
+        if n_step == 1:
+            L.check(L.lib().fb_replay_create(self.capacity, self.n, kind, C.byref(self.h)), "fb_replay_create")
+        else:
+            L.check(L.lib().fb_replay_create_nstep(self.capacity, self.n, kind, n_step, float(gamma), C.byref(self.h)),
+                    "fb_replay_create_nstep")
         self._buf = {}
 
     def __del__(self):
@@ -216,7 +230,8 @@ class VecReplay:
     def set_n_step(self, n, gamma):
         """View the memory with n-step returns (fb_replay_set_n_step; uniform memories, 1 <= n <= 16, capacity >= n * n_envs): sample /
         gather / the ring-fed train calls then see (s_t, a_t, R, s_{t+n}, done) and bootstrap with gamma^n.  n = 1 restores the one-step
-        memory.  Nothing stored changes; the training calls on it must be given this gamma."""
+        memory.  Nothing stored changes; the training calls on it must be given this gamma.  A prioritized memory's n is fixed at
+        creation (VecReplay(..., prioritized=True, n_step=K, gamma=g)): this raises for it."""
         L.check(L.lib().fb_replay_set_n_step(self.h, int(n), float(gamma)), "fb_replay_set_n_step")
 
     @property
@@ -228,7 +243,11 @@ class VecReplay:
 
     @property
     def population(self):
-        """deque positions sample() draws from: len(memory) less the (n - 1) * n_envs newest an n-step view cannot complete yet."""
+        """transitions sample() draws from.  Uniform: deque positions, len(memory) less the (n - 1) * n_envs newest an n-step view
+        cannot complete yet.  Prioritized: the tree's filled leaves, min(C, capacity) with C = max(0, pushes - n + 1) * n_envs
+        completed transitions stored since the reset (len(memory) at n = 1)."""
+        if self.prioritized:
+            return self.per_state(want_tree=False)[2]
         return max(0, len(self) - (self.n_step[0] - 1) * self.n)
 
     def __len__(self):

@@ -19,14 +19,16 @@ class HipVecBackend:
     in the world-size-2 gloo tests without a GPU; the product never uses anything else than this class.)"""
     name = "hip-gfx950"
     per_one_step = True                                      # fb_vec_step runs the prioritized step too (store, Memory.sample, train, batch_update)
+    per_n_step = True                                        # prioritized memories with n-step returns (replay(..., n_step, gamma))
 
     def env(self, n_envs, seed):
         from .vec import VecGameState
         return VecGameState(n_envs, seed=seed)
 
-    def replay(self, capacity, n_envs, prioritized):
+    def replay(self, capacity, n_envs, prioritized, n_step=1, gamma=None):
+        """n_step > 1: the memory has n-step returns from its creation (the way a prioritized memory gets them)"""
         from .vec import VecReplay
-        return VecReplay(capacity, n_envs, prioritized=prioritized)
+        return VecReplay(capacity, n_envs, prioritized=prioritized, n_step=n_step, gamma=gamma)
 
     def net(self, actions, fc_width, arch, max_batch):
         from .vec import QNet
@@ -81,13 +83,15 @@ class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99,
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1):
-        """n_step > 1: learn from n-step returns (the replay's n-step view, include/fbdqn.h fb_replay_set_n_step) -- uniform replay only."""
+        """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
+        memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step)."""
         n_step = int(n_step)
         if not 1 <= n_step <= 16:
             raise ValueError(f"n_step must be in 1..16, got {n_step}")
-        if n_step > 1 and algo == "per":
-            raise ValueError("n-step returns need a uniform replay memory: algo 'per' takes n_step = 1")
         be = backend or HipVecBackend()
+        if n_step > 1 and algo == "per" and not getattr(be, "per_n_step", False):
+            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend offers n-step returns on uniform replay only: "
+                             f"algo 'per' takes n_step = 1 there")
         self.be = be
         self.n, self.algo, self.batch, self.gamma = n_envs, algo, batch, gamma
         self.n_step = n_step
@@ -103,9 +107,12 @@ class VecBrain:
         self.replace_target_iter = replace_target_iter
         self.seed = seed
         self.env = be.env(n_envs, seed + 1000003 * rank)     # envs shard by rank: every rank plays its own games
-        self.replay = be.replay(capacity, n_envs, algo == "per")     # ... into its own replay shard
+        if n_step > 1 and algo == "per":                     # ... into its own replay shard (a prioritized one gets n at creation)
+            self.replay = be.replay(capacity, n_envs, True, n_step=n_step, gamma=gamma)
+        else:
+            self.replay = be.replay(capacity, n_envs, algo == "per")
         self.replay.seed(seed + rank, sampler)
-        if n_step > 1:                                       # (only then: a backend without n-step memories keeps working at n = 1)
+        if n_step > 1 and algo != "per":                     # (only then: a backend without n-step memories keeps working at n = 1)
             if not hasattr(self.replay, "set_n_step"):
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend's replay has no n-step view (n_step = {n_step})")
             self.replay.set_n_step(n_step, gamma)

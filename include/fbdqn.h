@@ -223,10 +223,34 @@ int fb_replay_set_per_mode(fb_replay_t h, int mode);
  * Ring-fed training calls on an n > 1 memory (fb_vec_step, fb_vec_step_dp, fb_train_from_replay, fb_train_steps) take `gamma` = the
  * memory's gamma (anything else is FB_ERR_INVALID before any counter moves or any launch) and bootstrap with Gamma; fb_replay_gather
  * returns (s, a, R, s', done); fb_qnet_train_step on gathered tensors is unchanged -- pass it Gamma.
- * fb_replay_get_n_step: the current (n, gamma) [host] (gamma = 0 at n = 1). */
+ * fb_replay_get_n_step: the current (n, gamma) [host] (gamma = 0 at n = 1), for both kinds.
+ *
+ * Prioritized memories with n-step returns (Ape-X: a prioritized memory fed with COMPLETED transitions).  n is fixed at creation
+ * (fb_replay_create_nstep): the ring size and the tree's contents both depend on it from the first push.  N = n_envs, cap = capacity,
+ * S = pushes since the last reset.
+ *   Stores   push S completes the N transitions of time slot S - n; Memory.store's tree part of push S stores exactly those N leaves
+ *            (max priority, env order, the reference's operations, every store path and mode unchanged).  Pushes 1 .. n-1 after a reset
+ *            store nothing.  After S pushes the tree has received C = max(0, S - n + 1) * N stores: its bytes, data_pointer, size and
+ *            beta are those of the reference's Memory after C store calls (FB_PER_EXACT bit for bit), i.e. those of an n = 1
+ *            prioritized memory of the same cap and N after S - n + 1 pushes.
+ *   Leaves   leaf d (data slot d) names the newest complete transition living in slot d: g = d + cap * floor((C - 1 - d) / cap),
+ *            (t, e) = divmod(g, N); valid iff d < min(C, cap) (an index beyond that raises the memory's error flag as at n = 1).
+ *   Reads    as in the uniform n-step view above: (s, a, R, s', done) of transition t, the target bootstrapped with Gamma; importance
+ *            weights, beta and batch_update are unchanged (the |TD errors| written back are those of the n-step target).
+ *   Population  min(C, cap): the tree always holds up to cap complete transitions (the uniform n-step population is
+ *            min(S N, cap) - (n-1) N instead).  fb_replay_size stays len(memory) = min(S N, cap); fb_replay_per_tree's size is min(C, cap).
+ *   Ring     cap complete transitions reach n - 1 time slots further back than at n = 1: the ring keeps T_f = ceil(cap / N) + n + 5 time
+ *            slots (ceil(cap / N) + 6 at n = 1, as fb_replay_create), (n - 1) * N * 806 bytes more.  The state blob records T_f, so a blob
+ *            of a prioritized memory with another n is refused by fb_replay_load_state.
+ *   Order    fb_replay_sample before n pushes since the reset is FB_ERR_STATE (the tree is empty), and so is fb_vec_step(train = 1)
+ *            or fb_train_from_replay when fewer than n pushes will exist when it samples; both before any launch.
+ * fb_replay_create_nstep: fb_replay_create with n-step returns from the start.  Uniform memories: fb_replay_create followed by
+ *   fb_replay_set_n_step.  Prioritized memories: the memory above (fb_replay_set_n_step refuses them).  1 <= n <= FB_NSTEP_MAX and
+ *   capacity >= n * n_envs, else FB_ERR_INVALID and nothing is allocated.  n = 1 is fb_replay_create exactly (gamma ignored). */
 #define FB_NSTEP_MAX 16
 int fb_replay_set_n_step(fb_replay_t h, int n, double gamma);
 int fb_replay_get_n_step(fb_replay_t h, int *n_host, double *gamma_host);
+int fb_replay_create_nstep(int64_t capacity, int n_envs, int kind, int n, double gamma, fb_replay_t *out);
 /* host-side queries (synchronous): len(replayMemory); PER: tree copy f64[2*cap-1] [host] */
 int fb_replay_size(fb_replay_t h, int64_t *size_host);
 int fb_replay_per_tree(fb_replay_t h, double *tree_host, int64_t *data_pointer, int64_t *size, double *beta);

@@ -11,7 +11,7 @@ across episode ends.  A score curve can.  The reference's own evidence is logs_b
 One VecBrain run per (envs, lr); one train step per loop step once onlineTimeStep > OBSERVE, as in the reference.  Every `window`
 steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and zeroed, so each
 row is the window's own figure, not a running average.  Rows go to stdout and to --out as they are produced.
---n-step K trains from K-step returns (VecBrain(n_step=K)); the summary gives the train steps at which the windowed mean score first
+--n-step K trains from K-step returns (VecBrain(n_step=K); with --algo per a prioritized memory created with K-step returns); the summary gives the train steps at which the windowed mean score first
 passed 1 / 10 / 100, and --eval-envs M (> 0) ends each run with VecBrain.evaluate() on M fresh greedy games.
 """
 import argparse
@@ -29,7 +29,7 @@ from dqnflappybird_amd.vecbrain import VecBrain  # noqa: E402
 def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore, n_step=1, eval_envs=0):
     vb = VecBrain(n_envs, algo=algo, arch=arch, capacity=1_000_000, seed=seed, explore=explore, n_step=n_step)
     vb.net.set_hparams(lr=lr)
-    head = f"# envs {n_envs}  algo {algo}/{arch}  n_step {n_step}  lr {lr:g}  batch {vb.batch}  observe {vb.observe}  explore {vb.explore}  eps {vb.initial_epsilon} -> {vb.final_epsilon}  target sync / {vb.replace_target_iter}"
+    head = f"# envs {n_envs}  algo {algo}/{arch}  n_step {n_step}  lr {lr:g}  batch {vb.batch}  observe {vb.observe}  explore {vb.explore}  eps {vb.initial_epsilon} -> {vb.final_epsilon}  {'target never synced (PER: the reference agent never syncs it)' if algo == 'per' else f'target sync / {vb.replace_target_iter}'}"
     cols = "#   train_steps   env_steps  epsilon  episodes  mean_score  max_score  pipes/episode      loss   steps/s"
     for f in (sys.stdout, out):
         print(head, file=f); print(cols, file=f); f.flush()
