@@ -14,9 +14,11 @@ ASSET_BLOB = os.path.join(_HERE, "assets", "sprites.bin")
 FB_OK = 0
 REPLAY_UNIFORM, REPLAY_PER = 0, 1
 RNG_CPYTHON, RNG_PHILOX, RNG_NUMPY = 0, 1, 2
-ARCH_PLAIN, ARCH_DUELING = 0, 1
+ARCH_PLAIN, ARCH_DUELING, ARCH_C51 = 0, 1, 2
 NET_ONLINE, NET_TARGET = 0, 1
 ALGO_DQN, ALGO_NATURE, ALGO_DOUBLE, ALGO_PER, ALGO_PG = 0, 1, 2, 3, 4
+ALGO_C51, ALGO_C51_DOUBLE = 5, 6
+C51_MAX_ATOMS = 64                                    # include/fbdqn.h FB_C51_MAX_ATOMS
 DTYPE_F32, DTYPE_BF16 = 0, 1
 PER_EXACT, PER_FAST = 0, 1
 NIB_PITCH, NIB_ROWS, NIB_STRIDE = 44, 84, 3712       # include/fbdqn.h FB_NIB_*
@@ -65,6 +67,9 @@ SIGNATURES = {
     "fb_replay_save_state": [_vp, _vp, _sz],
     "fb_replay_load_state": [_vp, _vp, _sz],
     "fb_qnet_create": [_i, _i, _i, _i, _vp],
+    "fb_qnet_create_c51": [_i, _i, _i, _f, _f, _i, _vp],
+    "fb_qnet_get_support": [_vp] * 4,
+    "fb_qnet_forward_dist": [_vp, _i, _vp, _i, _vp, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],

@@ -185,6 +185,10 @@ struct FbPushRider { unsigned long long *bits; uint8_t *act; float *rew; uint8_t
 int fb_env_step_rider(fb_env_t h, const uint8_t *actions, uint8_t *frames, uint64_t *frame_bits, float *reward, uint8_t *terminal,
                       int32_t *score, const FbSampleRider *rider, const FbPushRider *push, const FbHeadRider *head, void *stream);
 int fb_qnet_num_actions(fb_qnet_t h);
+int fb_qnet_is_c51(fb_qnet_t h);              // 1: a distributional net (fb_qnet_create_c51)
+// fb_eval_run on a C51 net: launch the head fb_qnet_eval_trunk described in *hd (q / actions / epsilon / seeds filled in by the caller),
+// epsilon draws keyed key_of[row] on FB_STREAM_EVAL; the eval step launch then reads the actions (its head rider stays off)
+int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32_t *key_of, void *stream);
 // fb_eval_run's acting forward: conv1 .. fc1 of n nibble states (1 <= n <= 3 * max_batch) through the fused two-plane trunk at ANY n (the
 // acting path switches to the small-batch kernels below 256 states), the head described in *head for the eval step launch
 int fb_qnet_eval_trunk(fb_qnet_t h, const uint8_t *nib_states, int n, FbHeadRider *head, void *stream);

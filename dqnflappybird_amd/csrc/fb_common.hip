@@ -102,6 +102,13 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
                               uint8_t *s2, uint8_t *a, float *r, uint8_t *t, float *loss, double gamma, void *stream) {
     FB_REQUIRE(replay && net && idx && s && s2 && a && r && t && loss && n_steps >= 1, "fb_train_steps: bad argument");
     FB_REQUIRE(algo != FB_ALGO_PER, "fb_train_steps: prioritized replay needs the importance weights: use the separate calls");
+    // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
+    // here as well so that it comes before any counter moves
+    if (algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || fb_qnet_is_c51(net)) {
+        FB_REQUIRE((algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE) == (fb_qnet_is_c51(net) != 0),
+                   "%s: a C51 net takes FB_ALGO_C51 or FB_ALGO_C51_DOUBLE, and those algos take a C51 net only (algo %d)", "fb_train_steps", algo);
+        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_steps");
+    }
     static const bool gathered_form = getenv("FB_TRAIN_STEPS_GATHER") && atoi(getenv("FB_TRAIN_STEPS_GATHER")) == 1;
     int rc = fb_replay_check_gamma(replay, gamma, "fb_train_steps");
     if (rc != FB_OK) return rc;
@@ -262,7 +269,14 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // every argument check of the calls below happens HERE, before the replay's push counter moves or anything is launched: a
     // rejected step must leave the handles exactly as they were (a counted push without its env launch would make every later
     // gather address a ring slot that was never written)
-    FB_REQUIRE(algo >= 0 && algo <= 3, "fb_vec_step: unknown algo %d", algo);
+    FB_REQUIRE((algo >= 0 && algo <= 3) || algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE, "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51, FB_ALGO_C51_DOUBLE)", algo);
+    // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
+    // here as well so that it comes before any counter moves
+    if (algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || fb_qnet_is_c51(net)) {
+        FB_REQUIRE((algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE) == (fb_qnet_is_c51(net) != 0),
+                   "%s: a C51 net takes FB_ALGO_C51 or FB_ALGO_C51_DOUBLE, and those algos take a C51 net only (algo %d)", "fb_vec_step", algo);
+        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_vec_step");
+    }
     FB_REQUIRE(per == (fb_replay_is_prioritized(replay) != 0), "fb_vec_step: algo %d and the memory's kind (uniform / prioritized) do not match", algo);
     FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_vec_step: n_envs %d does not match the env (%d) / replay (%d) handles",
                n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
@@ -290,7 +304,9 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // for the env launch's head rider) -> the launch in front of it does not retire before the fc1 launch has; workspaces -> the fused
     // acting forward has its own (hf_act / hp_act); the acting forward against the previous step's Adam and whatever else the caller's
     // stream held at entry -> c_entry.
-    if (fb_vec_split_enabled() && train && !per && n_envs >= 256 && batch < 256 && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2) {
+    // (C51 nets: the one-stream order below -- the split schedule is specified for the 2-output scalar heads)
+    if (fb_vec_split_enabled() && train && !per && n_envs >= 256 && batch < 256 && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 &&
+        !fb_qnet_is_c51(net)) {
         hipStream_t A = fb_stream(stream);
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(A, &cap);
@@ -351,7 +367,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // an env workgroup has a wave for each of its envs there (up to four envs per workgroup: 8192 envs)
     FbHeadRider hrider;
     static const bool head_rides = !(getenv("FB_VEC_HEAD_RIDER") && atoi(getenv("FB_VEC_HEAD_RIDER")) == 0);      // tuning knob
-    const int have_h = head_rides && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2;
+    const int have_h = head_rides && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 && !fb_qnet_is_c51(net);      // (C51: its own launch)
     int rc = have_h ? fb_qnet_act_nib_rider(net, b->nib, n_envs, epsilon, seed, step, b->actions, &hrider, stream)
                     : fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
     if (rc != FB_OK) return rc;
@@ -413,7 +429,14 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
 extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo, int batch, const int64_t *idx, const float *isw, uint8_t *a,
                                     float *r, uint8_t *t, double gamma, float *loss, float *abs_err, float *flat_grad, void *stream) {
     FB_REQUIRE(replay && net && idx && a && r && t && loss, "fb_train_from_replay: NULL argument");
-    FB_REQUIRE(algo >= 0 && algo <= 3, "fb_train_from_replay: unknown algo %d", algo);
+    FB_REQUIRE((algo >= 0 && algo <= 3) || algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE, "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51, FB_ALGO_C51_DOUBLE)", algo);
+    // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
+    // here as well so that it comes before any counter moves
+    if (algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || fb_qnet_is_c51(net)) {
+        FB_REQUIRE((algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE) == (fb_qnet_is_c51(net) != 0),
+                   "%s: a C51 net takes FB_ALGO_C51 or FB_ALGO_C51_DOUBLE, and those algos take a C51 net only (algo %d)", "fb_train_from_replay", algo);
+        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_from_replay");
+    }
     FB_REQUIRE(algo != FB_ALGO_PER || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
     FB_REQUIRE(batch >= 1 && batch <= 256, "fb_train_from_replay: batch must be in 1..256");
     int rc = fb_replay_check_gamma(replay, gamma, "fb_train_from_replay");

@@ -966,6 +966,7 @@ extern "C" int fb_eval_run(fb_eval_t ev, fb_qnet_t net, int n_envs, int episodes
     FB_REQUIRE(epsilon >= 0.f && epsilon <= 1.f, "fb_eval_run: epsilon=%g outside [0, 1]", (double)epsilon);      // (NaN fails too)
     FB_REQUIRE(score && length && truncated && steps_host, "fb_eval_run: NULL output");
     hipStream_t S = fb_stream(stream);
+    const bool c51 = fb_qnet_is_c51(net) != 0;
     // the acting forward writes the net's acting scratch (hf_act / hp_act, the activation planes, the plane versions), which the split
     // schedule's side stream also writes: whatever that stream still holds finishes first (and this call returns synchronised)
     if (hipStream_t side = fb_qnet_side_stream(net)) FB_CHECK_HIP(hipStreamSynchronize(side));
@@ -1005,12 +1006,18 @@ extern "C" int fb_eval_run(fb_eval_t ev, fb_qnet_t net, int n_envs, int episodes
                 hd.c.actions = ev->actions; hd.c.q = ev->q; hd.c.epsilon = epsilon;
                 hd.c.seed_lo = (uint32_t)act_seed; hd.c.seed_hi = (uint32_t)(act_seed >> 32);
                 hd.c.step_lo = (uint32_t)step; hd.c.step_hi = (uint32_t)((uint64_t)step >> 32);
+                const uint8_t *acts = nullptr;
+                if (c51) {                                   // C51: the distributional head as its own launch, the step launch reads its actions
+                    rc = fb_qnet_c51_eval_head(net, &hd, nb, ev->env_of[cur] + r0, stream);
+                    if (rc != FB_OK) return rc;
+                    hd.on = 0; acts = ev->actions;
+                }
                 EnvParams pp = p;
                 pp.n_envs = nb; pp.state = ev->state[cur] + (size_t)r0 * 16; pp.nib = nib;
                 er.env_of = ev->env_of[cur] + r0; er.step = (unsigned long long)step;
                 // a wave of the head per row of a workgroup (<= 4 rows each), and never more workgroups than rows
                 const int grid = nb <= 2048 ? nb : (nb <= 8192 ? 2048 : (nb + 3) / 4);
-                hipLaunchKernelGGL((env_kernel<true, true>), dim3(grid), dim3(ENV_THREADS), 0, S, pp, (const uint8_t *)nullptr,
+                hipLaunchKernelGGL((env_kernel<true, true>), dim3(grid), dim3(ENV_THREADS), 0, S, pp, acts,
                                    (uint8_t *)nullptr, (unsigned long long *)nullptr, (float *)nullptr, (uint8_t *)nullptr,
                                    (int32_t *)nullptr, FbSampleRider{}, FbPushRider{}, hd, er);
                 FB_LAUNCH_CHECK();

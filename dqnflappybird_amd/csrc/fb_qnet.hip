@@ -1508,6 +1508,240 @@ __global__ void adam_tick_kernel(AdamDev *ad) {
 __global__ void bump_pver_kernel(AdamDev *ad, int which) { ad->pver[which] += 1; }
 __global__ void mark_split_kernel(AdamDev *ad, int which) { ad->wver[which] = ad->pver[which]; ad->wverc[which] = ad->pver[which]; }
 
+// ================================================================== distributional (C51) head: acting, evaluation and training
+// include/fbdqn.h pins the semantics.  logits[a][i] = relu(h_fc1) . W[:, a N + i] + b[a N + i], p = softmax_i, Q[a] = sum_i z_i p[a][i].
+// One wave per state.  Lane i holds atom i of EVERY action (register a = action a): the softmax of an action, its Q and the projection
+// are then whole-wave reductions, and the loads of one weight row are contiguous across the lanes.  Lanes >= N read the clamped column
+// N - 1 and are masked by selects: no load sits under a branch (head_one_t's rule).
+struct C51Sup { int N; float vmin, vmax, dz; };
+__device__ __forceinline__ float rdlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ float wave_sum(float v) {          // xor butterfly: every lane ends with the same bits
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// the logits of state `row` (fc1 partial sums hf[nks][stot][FC]) through the head parameters P: 64 units per round, each unit's
+// activation broadcast from the lane that computed it (v_readlane: a scalar operand of the FMAs)
+template <int AT>
+__device__ __forceinline__ void c51_logits(const float *__restrict__ hf, int stot, int nks, int FC, const float *__restrict__ P, const NetOff &off,
+                                           int A, int N, int row, int lane, float (&lg)[AT]) {
+    const int AN = A * N, il = lane < N ? lane : N - 1;
+#pragma unroll
+    for (int a = 0; a < AT; a++) lg[a] = 0.f;
+    for (int j0 = 0; j0 < FC; j0 += 64) {                         // (FC % 128 == 0)
+        const float x = fc1_out(hf, stot, FC, row, j0 + lane, P[off.bf1 + j0 + lane], nks);
+        const float *__restrict__ w = P + off.wq + (size_t)j0 * AN + il;
+#pragma unroll 8
+        for (int k = 0; k < 64; k++) {
+            const float xs = rdlane(x, k);
+#pragma unroll
+            for (int a = 0; a < AT; a++) lg[a] = fmaf(xs, w[(size_t)k * AN + (a < A ? a : 0) * N], lg[a]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < AT; a++) lg[a] += P[off.bq + (a < A ? a : 0) * N + il];
+}
+// softmax of one action's logits over the N atoms: p on this lane (0 past N), and the log of the normaliser (max + log sum)
+__device__ __forceinline__ float c51_softmax(float lg, bool on, float &lse) {
+    const float m = wave_max(on ? lg : -INFINITY);
+    const float e = on ? expf(lg - m) : 0.f;
+    const float s = wave_sum(e);
+    lse = m + logf(s);
+    return e / s;
+}
+template <int AT>
+__device__ __forceinline__ void c51_q(const float (&lg)[AT], bool on, float z, float (&qv)[AT]) {
+#pragma unroll
+    for (int a = 0; a < AT; a++) {
+        float lse;
+        qv[a] = wave_sum(c51_softmax(lg[a], on, lse) * z);
+    }
+}
+
+// acting / evaluation head of ONE state: Q = E[Z], argmax (first maximum) and head_one_t's epsilon rule, bit for bit the same draws
+struct C51Core {
+    const float *hf; int stot, nks; float *q, *probs; int FC, A; NetOff off; C51Sup sup;      // probs: f32[row][A][N] or NULL
+    uint8_t *actions; float epsilon; uint32_t seed_lo, seed_hi, step_lo, step_hi;
+    const int32_t *key_of; uint32_t stream;      // epsilon counter: key_of[row] on `stream` (fb_eval_run), or the row on FB_STREAM_EPS
+};
+template <int AT>
+__device__ __forceinline__ void c51_head_one(const C51Core &C, const float *__restrict__ P, int smp, int lane) {
+    const int A = AT == MAXA ? C.A : AT, N = C.sup.N;
+    const bool on = lane < N;
+    const int key = C.key_of ? C.key_of[smp] : smp;
+    float lg[AT], qv[AT];
+    c51_logits<AT>(C.hf, C.stot, C.nks, C.FC, P, C.off, A, N, smp, lane, lg);
+    const float z = C.sup.vmin + (float)(on ? lane : 0) * C.sup.dz;
+    if (C.probs) {                                                // (a kernel argument decides: uniform branch)
+        float *row = C.probs + (size_t)smp * A * N + lane;
+#pragma unroll
+        for (int a = 0; a < AT; a++) {
+            float lse;
+            const float p = c51_softmax(lg[a], on, lse);
+            if (on && a < A) row[a * N] = p;
+            qv[a] = wave_sum(p * z);
+        }
+    } else c51_q<AT>(lg, on, z, qv);
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < AT; a++) if (a < A) C.q[(size_t)smp * A + a] = qv[a];
+        if (C.actions) {                                         // BrainDQN.py:103-108
+            int best = 0;
+#pragma unroll
+            for (int a = 1; a < AT; a++) if (a < A && qv[a] > qv[best]) best = a;           // np.argmax: first maximum
+            const fb_u4 o = fb_philox(C.seed_lo, C.seed_hi, (uint32_t)key, C.step_lo, C.stream, C.step_hi);
+            const float u = (float)(o.x >> 8) * (1.0f / 16777216.0f);                      // random.random()
+            if (u <= C.epsilon) best = (int)(((unsigned long long)o.y * (unsigned)A) >> 32);   // randrange(A)
+            C.actions[smp] = (uint8_t)best;
+        }
+    }
+}
+// params != NULL: every row reads that copy of the head parameters (fb_eval_run: the one the fused acting forward's fc1 launch took)
+struct C51HeadArgs { Slices sl; int nslices; const float *params; C51Core c; };
+template <int AT>
+__global__ __launch_bounds__(256) void c51_head_kernel(C51HeadArgs H) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int sidx = blockIdx.x * 4 + wave;
+    const float *P = nullptr;
+    int smp = -1;
+    for (int z = 0; z < H.nslices; z++) {
+        if (sidx < H.sl.s[z].count) { P = H.sl.s[z].params; smp = H.sl.s[z].s_off + sidx; break; }
+        sidx -= H.sl.s[z].count;
+    }
+    if (smp < 0) return;
+    c51_head_one<AT>(H.c, H.params ? H.params : P, smp, lane);
+}
+
+// ---- training, launch 1 of 2: one wave per sample.  Rows of hf: s (online net, 0 .. B-1), s' through p_next (B ..), and for
+// FB_ALGO_C51_DOUBLE s' through the target net (2B ..).  Forms a* and the target distribution, projects it onto the support
+// (m, a deterministic gather: lane i adds up, in order j = 0 .. N-1, what atom j sends it -- no atomics), the sample's loss term, the
+// logit gradient (p - m) / B of the taken action (dl[b][64]), and from it the fc1 pre-activation gradient row dhf[b][FC] (and the
+// activation row xs[b][FC] the second launch reads).
+struct C51LossArgs {
+    int algo, B, FC, A, nks, stot; NetOff off; C51Sup sup;
+    const float *p_on, *p_next, *p_tgt;
+    const float *hf; const uint8_t *act; const float *rew; const uint8_t *term; double gamma;
+    float *dl, *xs, *lterm, *dhf;
+};
+template <int AT>
+__global__ __launch_bounds__(256) void c51_loss_kernel(C51LossArgs L) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= L.B) return;                                        // (wave-uniform)
+    const int A = AT == MAXA ? L.A : AT, N = L.sup.N, B = L.B, FC = L.FC;
+    const bool on = lane < N;
+    const float vmin = L.sup.vmin, vmax = L.sup.vmax, dz = L.sup.dz;
+    const float z = vmin + (float)(on ? lane : 0) * dz;
+    const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;  // (an action past the head reads the last one: stays in bounds)
+    const float r = L.rew[b];
+    const int done = L.term[b];
+    float ls[AT], ln[AT], lt[AT];
+    c51_logits<AT>(L.hf, L.stot, L.nks, FC, L.p_on, L.off, A, N, b, lane, ls);
+    c51_logits<AT>(L.hf, L.stot, L.nks, FC, L.p_next, L.off, A, N, B + b, lane, ln);
+    if (L.algo == FB_ALGO_C51_DOUBLE) c51_logits<AT>(L.hf, L.stot, L.nks, FC, L.p_tgt, L.off, A, N, 2 * B + b, lane, lt);
+    else {
+#pragma unroll
+        for (int a = 0; a < AT; a++) lt[a] = ln[a];
+    }
+    // a* = argmax_a Q(s', a) of p_next's distribution (C51: the target net, double: the online net), first maximum
+    float qn[AT];
+    c51_q<AT>(ln, on, z, qn);
+    int best = 0;
+#pragma unroll
+    for (int a = 1; a < AT; a++) if (a < A && qn[a] > qn[best]) best = a;
+    float d = lt[0], la = ls[0];
+#pragma unroll
+    for (int a = 1; a < AT; a++) { d = a == best ? lt[a] : d; la = a == ab ? ls[a] : la; }
+    float lse_n, lse_s;
+    const float pn = c51_softmax(d, on, lse_n);                  // the target distribution p(s', a*)
+    // projection of Tz_j = clamp(R + Gamma (1 - done) z_j, vmin, vmax) onto the support
+    const float G = done ? 0.f : (float)L.gamma;
+    float tz = r + G * z;
+    tz = fminf(fmaxf(tz, vmin), vmax);
+    float bj = (tz - vmin) / dz;
+    bj = fminf(fmaxf(bj, 0.f), (float)(N - 1));                  // ((vmax - vmin) / dz may round past N - 1)
+    float m = 0.f;
+    for (int j = 0; j < N; j++) {
+        const float pj = rdlane(pn, j), bb = rdlane(bj, j);
+        const float lf = floorf(bb), uf = ceilf(bb);
+        const int l = (int)lf, u = (int)uf;
+        const float wl = l == u ? pj : pj * (uf - bb), wu = pj * (bb - lf);   // l == u: the whole mass stays on the atom
+        m += lane == l ? wl : 0.f;
+        m += lane == u && u != l ? wu : 0.f;
+    }
+    // loss -sum_i m_i log_softmax(logits(s, a_b))_i and its logit gradient (p - m) / B
+    const float ps = c51_softmax(la, on, lse_s);
+    const float lossb = wave_sum(on ? -m * (la - lse_s) : 0.f);
+    const float g = on ? (ps - m) / (float)B : 0.f;
+    L.dl[(size_t)b * 64 + lane] = g;
+    if (lane == 0) L.lterm[b] = lossb;
+    const int AN = A * N;
+    for (int j0 = 0; j0 < FC; j0 += 64) {
+        const int j = j0 + lane;
+        const float x = fc1_out(L.hf, L.stot, FC, b, j, L.p_on[L.off.bf1 + j], L.nks);
+        const float *__restrict__ w = L.p_on + L.off.wq + (size_t)j * AN + ab * N;
+        float dh = 0.f;
+        for (int i = 0; i < N; i++) dh = fmaf(rdlane(g, i), w[i], dh);
+        L.dhf[(size_t)b * FC + j] = x > 0.f ? dh : 0.f;
+        L.xs[(size_t)b * FC + j] = x;
+    }
+}
+
+// ---- training, launch 2 of 2: one workgroup per 16 fc1 units (grid FC / 16, the grid of loss_head_kernel): b_fc1's gradient and the
+// tile's maximum |dhf| (gmax: fc1_bwd_big_kernel's pre-scale), then W_fc2's gradient for those units -- thread (c, ug) owns column c
+// of units 8 ug .. 8 ug + 7 and walks the samples in order -- and, in workgroup 0, b_fc2's gradient, the loss and the Adam tick.
+struct C51GradArgs { int B, FC, A, N; NetOff off; const float *dl, *xs, *lterm, *dhf; const uint8_t *act; float *grad, *loss, *gmax; AdamDev *adam; int tick; };
+__global__ __launch_bounds__(256) void c51_grad_kernel(C51GradArgs L) {
+    __shared__ float dlt[MAXTB * 64];
+    __shared__ float xt[MAXTB * 16];
+    __shared__ int at[MAXTB];
+    __shared__ float part[16][16];
+    __shared__ float wmax[4];
+    const int tid = threadIdx.x, B = L.B, FC = L.FC, j00 = blockIdx.x * 16;
+    for (int k = tid; k < B * 64; k += 256) dlt[k] = L.dl[k];
+    for (int k = tid; k < B * 16; k += 256) xt[k] = L.xs[(size_t)(k >> 4) * FC + j00 + (k & 15)];
+    for (int k = tid; k < B; k += 256) at[k] = L.act[k] < L.A ? L.act[k] : L.A - 1;
+    const int jl = tid & 15, bg = tid >> 4;
+    float s = 0.f, mx = 0.f;
+    for (int b = bg; b < B; b += 16) { const float d = L.dhf[(size_t)b * FC + j00 + jl]; s += d; mx = fmaxf(mx, fabsf(d)); }
+    part[bg][jl] = s;
+    wg_max_write(mx, wmax, tid >> 6, tid & 63);
+    __syncthreads();
+    if (tid == 0) L.gmax[blockIdx.x] = wg_max_read<4>(wmax);
+    if (bg == 0) {
+        float v = part[0][jl];
+#pragma unroll
+        for (int q = 1; q < 16; q++) v += part[q][jl];
+        L.grad[L.off.bf1 + j00 + jl] = v;
+    }
+    const int AN = L.A * L.N, c = tid & 127, ug = tid >> 7;
+    const int cc = c < AN ? c : 0, ac = cc / L.N, ic = cc - ac * L.N;
+    float acc[8], gb = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; u++) acc[u] = 0.f;
+    for (int b = 0; b < B; b++) {
+        const float w = at[b] == ac ? dlt[b * 64 + ic] : 0.f;
+        gb += w;
+#pragma unroll
+        for (int u = 0; u < 8; u++) acc[u] = fmaf(xt[b * 16 + ug * 8 + u], w, acc[u]);
+    }
+    if (c < AN) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) L.grad[L.off.wq + (size_t)(j00 + ug * 8 + u) * AN + c] = acc[u];
+        if (blockIdx.x == 0 && ug == 0) L.grad[L.off.bq + c] = gb;
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        float t = 0.f;
+        for (int b = 0; b < B; b++) t += L.lterm[b];
+        *L.loss = t / (float)B;
+        if (L.tick && L.adam->ticks == L.adam->applies) {        // (as loss_head_body)
+            AdamDev &ad = *L.adam;
+            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
+            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
+            ad.ticks += 1;
+        }
+    }
+}
+
 // ================================================================== fc1 + loss, small batches (training, < 256 states)
 // fc1 with the WHOLE reduction in one workgroup.  Round 1's fc1_kernel split K = 1600 over 5 workgroups, which leaves five partial
 // sums per unit that only a further launch can add up -- so Q (and with it the loss and every gradient) sat two launches
@@ -3212,10 +3446,12 @@ struct fb_qnet {
     // start its Adam launch as soon as that fc1 launch is through
     float *hf_act, *hp_act;
     FbSplitCtx *split;               // fb_qnet_split_ctx
+    C51Sup sup;                      // C51 nets: the support (sup.N = 0: a scalar head)
+    float *c51_dl, *c51_xs, *c51_lt; // C51 training: logit gradients [max_batch][64], fc1 activations of s [max_batch][FC], loss terms [max_batch]
     bool split_adam_pending;         // a split step exported its gradient: the fb_qnet_apply_adam that completes it takes over the Adam launch's waits
 };
 
-static NetOff make_off(int FC, int A, int dueling) {
+static NetOff make_off(int FC, int A, int dueling) {      // A: the head's columns (C51: actions x atoms)
     NetOff o;
     o.bf1 = OFF_WF1 + 1600 * FC;
     int p = o.bf1 + FC;
@@ -3224,16 +3460,37 @@ static NetOff make_off(int FC, int A, int dueling) {
     return o;
 }
 
+static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out);
+
 extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
     FB_REQUIRE(out, "fb_qnet_create: out is NULL");
+    FB_REQUIRE(arch != FB_ARCH_C51, "fb_qnet_create: a C51 net is made by fb_qnet_create_c51 (it needs the support)");
     FB_REQUIRE(arch == FB_ARCH_PLAIN || arch == FB_ARCH_DUELING, "fb_qnet_create: arch must be 0 or 1");
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create: fc_width must be a multiple of 128");
     FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create: n_actions must be in 1..%d", MAXA);
     FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "fb_qnet_create: max_batch out of range");
+    return qnet_create(arch, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
+}
+
+extern "C" int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
+    FB_REQUIRE(out, "fb_qnet_create_c51: out is NULL");
+    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create_c51: fc_width must be a multiple of 128");
+    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create_c51: n_actions must be in 1..%d", MAXA);
+    FB_REQUIRE(n_atoms >= 2 && n_atoms <= FB_C51_MAX_ATOMS, "fb_qnet_create_c51: n_atoms=%d outside 2..%d", n_atoms, FB_C51_MAX_ATOMS);
+    FB_REQUIRE(n_actions * n_atoms <= 128, "fb_qnet_create_c51: n_actions * n_atoms = %d exceeds 128", n_actions * n_atoms);
+    FB_REQUIRE(isfinite(v_min) && isfinite(v_max) && v_min < v_max, "fb_qnet_create_c51: the support needs finite v_min < v_max (got %g, %g)",
+               (double)v_min, (double)v_max);
+    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "fb_qnet_create_c51: max_batch out of range");
+    const float dz = (v_max - v_min) / (float)(n_atoms - 1);
+    FB_REQUIRE(isfinite(dz) && dz > 0.f, "fb_qnet_create_c51: the atom spacing (v_max - v_min) / (n_atoms - 1) is not a positive finite float");
+    return qnet_create(FB_ARCH_C51, fc_width, n_actions, C51Sup{n_atoms, v_min, v_max, dz}, max_batch, out);
+}
+
+static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out) {
     fb_qnet *h = new fb_qnet();
     memset(h, 0, sizeof(*h));
-    h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch;
-    h->off = make_off(fc_width, n_actions, arch == FB_ARCH_DUELING);
+    h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
+    h->off = make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
     h->n = h->off.n;
     h->zmax = 64;
     const size_t S = (size_t)3 * max_batch, nb = sizeof(float) * (size_t)h->n;
@@ -3260,6 +3517,7 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
     alloc((void **)&h->dh2, Bm * 1600 * 4); alloc((void **)&h->dp1, Bm * 3200 * 4);
     alloc((void **)&h->gmax, (size_t)(fc_width / 16) * 4);
     alloc((void **)&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc((void **)&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
+    if (sup.N) { alloc((void **)&h->c51_dl, Bm * 64 * 4); alloc((void **)&h->c51_xs, Bm * fc_width * 4); alloc((void **)&h->c51_lt, Bm * 4); }
     if (e != hipSuccess) {
         fb_set_error(e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP, "fb_qnet_create: %s", hipGetErrorString(e));
         fb_qnet_destroy(h);
@@ -3277,7 +3535,8 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
 extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     if (!h) return FB_OK;
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
-                    h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act};
+                    h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
+                    h->c51_dl, h->c51_xs, h->c51_lt};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -3395,7 +3654,7 @@ static void resplit_now(fb_qnet *h, int which, hipStream_t st) {
 extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *stream) {
     FB_REQUIRE(h && (which == 0 || which == 1), "fb_qnet_init_params: bad argument");
     hipLaunchKernelGGL(init_params_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, fb_stream(stream),
-                       h->params[which], h->n, h->off, h->FC, h->A, h->arch == FB_ARCH_DUELING, (uint32_t)seed,
+                       h->params[which], h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING, (uint32_t)seed,
                        (uint32_t)(seed >> 32));
     hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, fb_stream(stream), h->params[which], h->w1s[which], &h->adam->pver[which]);
     resplit_now(h, which, fb_stream(stream));
@@ -3474,6 +3733,7 @@ struct Plan {
     // fb_eval_run / fb_eval_q: the fused acting trunk (five states per workgroup) at ANY state count, so that a state's Q values do not
     // depend on how many other states share the launch (the small-batch kernels below 256 states round differently)
     bool any_rows;
+    float *probs;                            // C51 forward plans: the head also writes the probabilities f32[row][A][N] (fb_qnet_forward_dist)
 };
 
 static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
@@ -3606,13 +3866,30 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
     }
     // small batches: the whole K per workgroup (fc1_fk_kernel), which lets training skip the head and loss launches
     const bool fk = !sp && !big;
+    const bool c51 = h->sup.N > 0;
     if (fk) FB_K(K_FC1) {
         FkArgs fa;
-        fa.sl = p.sl; fa.h3 = h->h3; fa.hf = h->hf; fa.qpart = p.train ? h->qpart : nullptr; fa.FC = h->FC; fa.A = h->A;
+        fa.sl = p.sl; fa.h3 = h->h3; fa.hf = h->hf; fa.qpart = p.train && !c51 ? h->qpart : nullptr; fa.FC = h->FC; fa.A = h->A;      // (C51: the head is the loss launches' own work)
         fa.dueling = h->arch == FB_ARCH_DUELING; fa.stot = stot; fa.off = h->off;
         hipLaunchKernelGGL(fc1_fk_kernel, dim3((maxc + 15) / 16, h->FC / 16, p.ns), dim3(512), 0, st, fa);
     }
-    if (!(fk && p.train)) FB_K(K_HEAD) {            // (small-batch training gets Q from fc1_fk_kernel's shares instead)
+    if (c51 && !p.train) FB_K(K_HEAD) {             // C51: the distributional head (stand-alone launch only; no env rider)
+        C51HeadArgs H;
+        H.sl = p.sl; H.nslices = p.ns; H.params = nullptr;
+        C51Core &C = H.c;
+        C.hf = acting_fused ? h->hf_act : h->hf; C.stot = stot; C.nks = sp ? FC1_SP_KS : 1; C.q = h->q; C.probs = p.probs; C.FC = h->FC; C.A = h->A;
+        C.off = h->off; C.sup = h->sup; C.actions = p.actions; C.epsilon = p.epsilon;
+        C.seed_lo = (uint32_t)p.seed; C.seed_hi = (uint32_t)(p.seed >> 32);
+        C.step_lo = (uint32_t)p.step; C.step_hi = (uint32_t)(p.step >> 32);
+        C.key_of = nullptr; C.stream = FB_STREAM_EPS;
+        if (p.head_rider) {                          // fb_eval_run: describe the work (fb_qnet_c51_eval_head launches it)
+            memset(p.head_rider, 0, sizeof(*p.head_rider));
+            p.head_rider->c.hf = C.hf; p.head_rider->c.stot = stot; p.head_rider->c.nks = C.nks;
+            p.head_rider->params = acting_fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;
+        } else if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((total + 3) / 4), dim3(256), 0, st, H);
+        else hipLaunchKernelGGL(c51_head_kernel<MAXA>, dim3((total + 3) / 4), dim3(256), 0, st, H);
+    }
+    if (!c51 && !(fk && p.train)) FB_K(K_HEAD) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
         HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns;
         HeadCore &C = H.c;
@@ -3627,7 +3904,19 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
     if (p.train) {
         const int B = p.B, FC = h->FC, rbt = h->nsplit_train == 1;       // bf16 training: operands rounded to bf16
         float *G = p.G;
-        if (!fk) FB_K(K_LOSS) {
+        if (c51) FB_K(K_LOSS) {                     // C51: per-sample distribution / projection / dhf, then the per-unit reductions
+            if (p.tick) h->adam_ticked = !p.apply_adam;
+            C51LossArgs L;
+            L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->off; L.sup = h->sup;
+            L.p_on = h->params[0]; L.p_next = p.sl.s[1].params; L.p_tgt = p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params;
+            L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
+            L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
+            if (h->A == 2) hipLaunchKernelGGL(c51_loss_kernel<2>, dim3((B + 3) / 4), dim3(256), 0, st, L);
+            else hipLaunchKernelGGL(c51_loss_kernel<MAXA>, dim3((B + 3) / 4), dim3(256), 0, st, L);
+            const C51GradArgs gA{B, FC, h->A, h->sup.N, h->off, h->c51_dl, h->c51_xs, h->c51_lt, h->dhf, p.a, G, p.loss, h->gmax, h->adam, p.tick};
+            hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);
+        }
+        if (!fk && !c51) FB_K(K_LOSS) {
             LossArgs L;
             L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.off = h->off;
             L.params = h->params[0]; L.q = h->q; L.hf = h->hf; L.stot = stot; L.nks = FC1_SP_KS; L.act = p.a; L.rew = p.r; L.term = p.t; L.isw = p.isw;      // (only large batches come here: fc1_sp_kernel's 4 K slices)
@@ -3645,7 +3934,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         if (z1 > h->zmax) z1 = h->zmax;
         const size_t ss = CONV_PARAMS;
         const int ndx1 = ((B + 31) / 32) * 50;
-        if (fk) { FB_K(K_FC1_BWD) {
+        if (fk && !c51) { FB_K(K_FC1_BWD) {
             Bw1Args L;
             L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.stot = stot; L.n_dx = ndx1; L.off = h->off;
             L.params = h->params[0]; L.pnext = p.sl.s[1].params; L.ptarget = p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params;
@@ -3822,6 +4111,40 @@ extern "C" int fb_qnet_act_nib(fb_qnet_t h, const uint8_t *nib_states, int n, fl
 }
 
 int fb_qnet_num_actions(fb_qnet_t h) { return h ? h->A : 0; }
+int fb_qnet_is_c51(fb_qnet_t h) { return h && h->sup.N > 0; }
+
+extern "C" int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host) {
+    FB_REQUIRE(h && n_atoms_host && v_min_host && v_max_host, "fb_qnet_get_support: NULL argument");
+    *n_atoms_host = h->sup.N; *v_min_host = h->sup.vmin; *v_max_host = h->sup.vmax;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream) {
+    FB_REQUIRE(h && states && probs && (which == 0 || which == 1), "fb_qnet_forward_dist: bad argument");
+    FB_REQUIRE(h->sup.N > 0, "fb_qnet_forward_dist: not a C51 net (fb_qnet_create_c51)");
+    FB_REQUIRE(batch >= 1 && batch <= 3 * h->max_batch, "fb_qnet_forward_dist: batch %d exceeds 3*max_batch", batch);
+    Plan p = forward_plan(h, which, states, batch);
+    p.probs = probs;
+    return run_plan(h, p, -1, fb_stream(stream));
+}
+
+// fb_eval_run on a C51 net: the head fb_qnet_eval_trunk described (hd->c.hf / stot / nks, hd->params), with the caller's q / actions /
+// epsilon / seeds in hd->c, keyed by key_of[row] on FB_STREAM_EVAL -- as the env launch's head rider keys a scalar net's draws
+int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32_t *key_of, void *stream) {
+    FB_REQUIRE(h && hd && key_of && h->sup.N > 0, "fb_qnet_c51_eval_head: bad argument");
+    C51HeadArgs H;
+    memset(&H, 0, sizeof(H));
+    H.sl.s[0] = Slice{hd->params, nullptr, 0, n, nullptr, 0}; H.nslices = 1; H.params = hd->params;
+    C51Core &C = H.c;
+    C.hf = hd->c.hf; C.stot = hd->c.stot; C.nks = hd->c.nks; C.q = hd->c.q; C.probs = nullptr; C.FC = h->FC; C.A = h->A;
+    C.off = h->off; C.sup = h->sup; C.actions = hd->c.actions; C.epsilon = hd->c.epsilon;
+    C.seed_lo = hd->c.seed_lo; C.seed_hi = hd->c.seed_hi; C.step_lo = hd->c.step_lo; C.step_hi = hd->c.step_hi;
+    C.key_of = key_of; C.stream = FB_STREAM_EVAL;
+    if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
+    else hipLaunchKernelGGL(c51_head_kernel<MAXA>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
 int fb_qnet_max_rows(fb_qnet_t h) { return h ? 3 * h->max_batch : 0; }
 hipStream_t fb_qnet_side_stream(fb_qnet_t h) { return h && h->split ? h->split->tstream : nullptr; }
 
@@ -3856,6 +4179,7 @@ int fb_qnet_check_step(fb_qnet_t h, int n_envs, int train_batch) {
 int fb_qnet_act_nib_rider(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
                           uint8_t *actions, FbHeadRider *head, void *stream, const FbSplitCtx *split) {
     FB_REQUIRE(h && nib_states && actions && head, "fb_qnet_act_nib_rider: NULL argument");
+    FB_REQUIRE(h->sup.N == 0, "fb_qnet_act_nib_rider: a C51 net's head does not ride in the env launch");
     FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_qnet_act_nib: n %d exceeds 3*max_batch", n);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true;
@@ -3918,7 +4242,12 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
                       const uint8_t *t, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
     FB_REQUIRE(h && a && r && t && loss && (ring || (s && s2)), "fb_qnet_train_step: NULL argument");
-    FB_REQUIRE(algo >= 0 && algo <= FB_ALGO_PG, "fb_qnet_train_step: unknown algo %d", algo);
+    FB_REQUIRE(algo >= 0 && algo <= FB_ALGO_C51_DOUBLE, "fb_qnet_train_step: unknown algo %d", algo);
+    {
+        const bool c51a = algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE;
+        FB_REQUIRE(c51a == (h->sup.N > 0), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
+                                                : "fb_qnet_train_step: a C51 net trains with FB_ALGO_C51 or FB_ALGO_C51_DOUBLE only (got algo %d)", algo);
+    }
     FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "fb_qnet_train_step: batch %d exceeds min(max_batch, %d)", B, MAXTB);
     FB_REQUIRE(algo != FB_ALGO_PG || (B <= 128 && !ring && gamma >= (double)B), "fb_qnet_train_step: FB_ALGO_PG takes chunks of <= 128 gathered states and gamma = the whole batch's sample count (>= %d)", B);
     FB_REQUIRE(algo != FB_ALGO_PER || isw, "fb_qnet_train_step: PER needs isw");
@@ -3927,8 +4256,8 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     p.ns = 2;
     p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
     if (algo == FB_ALGO_DQN || algo == FB_ALGO_PG) p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};               // BrainDQN.py:205 (same net); PG: s2 is forwarded and ignored
-    else if (algo == FB_ALGO_DOUBLE) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
-    else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net
+    else if (algo == FB_ALGO_DOUBLE || algo == FB_ALGO_C51_DOUBLE) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
+    else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net (Nature, PER, C51)
     p.sl.rb = h->nsplit_train == 1;
     p.train = true; p.algo = algo; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.isw = isw; p.gamma = gamma;
     p.loss = loss; p.abs_err = abs_err; p.y = q_target;

@@ -276,7 +276,23 @@ class VecReplay:
         return tree, ptr_.value, size.value, beta.value
 
 
-ALGOS = {"dqn": L.ALGO_DQN, "nature": L.ALGO_NATURE, "double": L.ALGO_DOUBLE, "per": L.ALGO_PER, "pg": L.ALGO_PG}
+ALGOS = {"dqn": L.ALGO_DQN, "nature": L.ALGO_NATURE, "double": L.ALGO_DOUBLE, "per": L.ALGO_PER, "pg": L.ALGO_PG,
+         "c51": L.ALGO_C51, "c51double": L.ALGO_C51_DOUBLE}
+C51_ALGOS = ("c51", "c51double")
+C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
+
+
+def check_support(n_atoms, v_min, v_max, actions=2):
+    """the argument checks of fb_qnet_create_c51, on the host (-> (n_atoms, v_min, v_max) as int, float32-rounded floats)"""
+    n_atoms = int(n_atoms)
+    if not 2 <= n_atoms <= L.C51_MAX_ATOMS:
+        raise ValueError(f"n_atoms must be in 2..{L.C51_MAX_ATOMS}, got {n_atoms}")
+    if int(actions) * n_atoms > 128:
+        raise ValueError(f"actions x n_atoms must be <= 128, got {int(actions)} x {n_atoms}")
+    v_min, v_max = float(np.float32(v_min)), float(np.float32(v_max))
+    if not (np.isfinite(v_min) and np.isfinite(v_max) and v_min < v_max):
+        raise ValueError(f"the support needs finite v_min < v_max, got [{v_min}, {v_max}]")
+    return n_atoms, v_min, v_max
 
 
 def bootstrap_gamma(gamma, n):
@@ -294,14 +310,24 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
-    def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda"):
+    def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
+                 v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2]):
+        """arch='c51': the distributional head of include/fbdqn.h (n_atoms atoms on [v_min, v_max]; the support args are ignored otherwise)"""
+        if arch not in ("plain", "dueling", "c51"):
+            raise ValueError(f"arch must be 'plain', 'dueling' or 'c51', got {arch!r}")
+        if arch == "c51":
+            n_atoms, v_min, v_max = check_support(n_atoms, v_min, v_max, actions)
         L.require_gpu()
         self.A, self.FC, self.max_batch = int(actions), int(fc_width), int(max_batch)
         self.dueling = arch == "dueling"
+        self.arch = arch
         self.device = torch.device(device)
         self.h = C.c_void_p()
-        L.check(L.lib().fb_qnet_create(L.ARCH_DUELING if self.dueling else L.ARCH_PLAIN, self.FC, self.A, self.max_batch,
-                                       C.byref(self.h)), "fb_qnet_create")
+        if arch == "c51":
+            L.check(L.lib().fb_qnet_create_c51(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)), "fb_qnet_create_c51")
+        else:
+            L.check(L.lib().fb_qnet_create(L.ARCH_DUELING if self.dueling else L.ARCH_PLAIN, self.FC, self.A, self.max_batch,
+                                           C.byref(self.h)), "fb_qnet_create")
         n = C.c_int64()
         L.check(L.lib().fb_qnet_num_params(self.h, C.byref(n)), "fb_qnet_num_params")
         self.n_params = n.value
@@ -389,7 +415,36 @@ class QNet:
     def sync_target(self):
         L.check(L.lib().fb_qnet_sync_target(self.h, L.current_stream()), "fb_qnet_sync_target")
 
+    @property
+    def support(self):
+        """(n_atoms, v_min, v_max) of a C51 net (fb_qnet_get_support), None for a scalar head"""
+        n, lo, hi = C.c_int(), C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_get_support(self.h, C.byref(n), C.byref(lo), C.byref(hi)), "fb_qnet_get_support")
+        return (n.value, lo.value, hi.value) if n.value else None
+
+    def atoms(self):
+        """the support values z_i = v_min + i * dz as float32 (the device's arithmetic), or None"""
+        sup = self.support
+        if sup is None:
+            return None
+        n, lo, hi = sup
+        dz = (np.float32(hi) - np.float32(lo)) / np.float32(n - 1)
+        return np.float32(lo) + np.arange(n, dtype=np.float32) * np.float32(dz)
+
     # -- compute --------------------------------------------------------------------
+    def forward_dist(self, states, which=L.NET_ONLINE):
+        """C51 nets: the return distributions p f32[B, A, n_atoms] of u8 states (fb_qnet_forward_dist)"""
+        _dev_check(states)
+        sup = self.support
+        if sup is None:
+            raise ValueError("forward_dist needs a C51 net (arch='c51')")
+        B = states.shape[0]
+        if states.dtype != torch.uint8 or tuple(states.shape[1:]) != (80, 80, 4):
+            raise ValueError("states must be uint8[B,80,80,4]")
+        p = torch.empty((B, self.A, sup[0]), dtype=torch.float32, device=self.device)
+        L.check(L.lib().fb_qnet_forward_dist(self.h, which, L.ptr(states), B, L.ptr(p), L.current_stream()), "fb_qnet_forward_dist")
+        return p
+
     def forward(self, states, which=L.NET_ONLINE):
         _dev_check(states)
         B = states.shape[0]
@@ -506,6 +561,10 @@ class VecStep:
         """flat_grad: export the gradient instead of applying Adam (data parallel; the caller all-reduces and calls net.apply_adam).
         dist: a dist.NativeDP -- then the call is fb_vec_step_dp: the step, the all-reduce of flat_grad through the library's own
         RCCL communicator (overlapped with the conv backward) and Adam, all in the one host call; mean_loss divides by the world size."""
+        if algo in C51_ALGOS and replay.prioritized:
+            raise ValueError(f"algo {algo!r} trains from a uniform memory only (prioritized replay with C51 is not supported)")
+        if algo in C51_ALGOS and dist is not None:
+            raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (one GPU only)")
         if replay.prioritized != (algo == "per"):
             raise ValueError("algo 'per' goes with a prioritized memory, every other algo with a uniform one")
         if dist is not None and flat_grad is None:

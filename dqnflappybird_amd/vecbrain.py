@@ -10,7 +10,9 @@ timeStep % 500 == 0, PER never does.
 """
 from . import dist as fdist
 
-MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True}
+MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True}
+C51_ALGOS = ("c51", "c51double")                             # distributional Q-learning (include/fbdqn.h)
+TARGET_SYNC = ("nature", "double") + C51_ALGOS              # algos whose target net is synced every replace_target_iter steps
 
 
 class HipVecBackend:
@@ -30,8 +32,12 @@ class HipVecBackend:
         from .vec import VecReplay
         return VecReplay(capacity, n_envs, prioritized=prioritized, n_step=n_step, gamma=gamma)
 
-    def net(self, actions, fc_width, arch, max_batch):
+    c51 = True                                               # distributional nets (net(..., support=(n_atoms, v_min, v_max)))
+
+    def net(self, actions, fc_width, arch, max_batch, support=None):
         from .vec import QNet
+        if support is not None:
+            return QNet(actions, fc_width, "c51", max_batch=max_batch, n_atoms=support[0], v_min=support[1], v_max=support[2])
         return QNet(actions, fc_width, arch, max_batch=max_batch)
 
     def step(self, env, replay, net, batch, algo, gamma, flat_grad, dist=None, mean_loss=False):
@@ -79,16 +85,39 @@ class HipVecBackend:
         return lambda: fdist.allreduce_gradients(flat_grad, mean_loss)
 
 
+def check_checkpoint_support(z, support, path):
+    """a checkpoint's head must be this brain's: C51 with the same support (n_atoms, v_min, v_max), or a scalar head on both sides"""
+    saved = tuple(z["support"].tolist()) if "support" in z.files else None
+    if saved is None and support is not None:
+        raise ValueError(f"checkpoint {path} holds a scalar-head net, this VecBrain trains a C51 net (support {support})")
+    if saved is not None and support is None:
+        raise ValueError(f"checkpoint {path} holds a C51 net (support {saved}), this VecBrain has a scalar head")
+    if saved is not None and (int(saved[0]), float(saved[1]), float(saved[2])) != (int(support[0]), float(support[1]), float(support[2])):
+        raise ValueError(f"checkpoint {path} was trained on the support {saved} (n_atoms, v_min, v_max), this VecBrain has {tuple(support)}")
+
+
 class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99,
-                 replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1):
+                 replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
-        memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step)."""
+        memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
+        algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk)."""
         n_step = int(n_step)
         if not 1 <= n_step <= 16:
             raise ValueError(f"n_step must be in 1..16, got {n_step}")
         be = backend or HipVecBackend()
+        self.support = None
+        if algo in C51_ALGOS:
+            from .vec import check_support
+            if arch not in ("plain", "c51"):
+                raise ValueError(f"algo {algo!r} builds a C51 head on the plain trunk: arch {arch!r} (dueling C51) is not supported")
+            if world > 1:
+                raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (world = {world}; one GPU only)")
+            if not getattr(be, "c51", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no C51 nets")
+            self.support = check_support(n_atoms, v_min, v_max)
+            arch = "c51"
         if n_step > 1 and algo == "per" and not getattr(be, "per_n_step", False):
             raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend offers n-step returns on uniform replay only: "
                              f"algo 'per' takes n_step = 1 there")
@@ -116,7 +145,8 @@ class VecBrain:
             if not hasattr(self.replay, "set_n_step"):
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend's replay has no n-step view (n_step = {n_step})")
             self.replay.set_n_step(n_step, gamma)
-        self.net = be.net(2, fc_width, arch, max(n_envs, batch))
+        self.arch = arch
+        self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support) if self.support else be.net(2, fc_width, arch, max(n_envs, batch))
         self.net.init_params(seed=seed, which=0)             # the same draw on every rank
         self.net.init_params(seed=seed + 1, which=1)
         if world > 1:                                        # replicas start from rank 0's parameters, bit for bit
@@ -151,7 +181,7 @@ class VecBrain:
             self.one_step = be.step(self.env, self.replay, self.net, batch, algo, gamma, self.grad)
 
     def train_step(self, idx=None):
-        if self.algo in ("nature", "double") and self.timeStep % self.replace_target_iter == 0:
+        if self.algo in TARGET_SYNC and self.timeStep % self.replace_target_iter == 0:
             self.net.sync_target()
         isw = None
         if idx is None:
@@ -173,7 +203,7 @@ class VecBrain:
     def step(self):
         if self.one_step is not None:
             training = self.onlineTimeStep > self.observe
-            if training and self.algo in ("nature", "double") and self.timeStep % self.replace_target_iter == 0:
+            if training and self.algo in TARGET_SYNC and self.timeStep % self.replace_target_iter == 0:
                 self.net.sync_target()                       # acting reads the online net only: same result as syncing before training
             self.one_step(self.epsilon, seed=self.seed + self.rank, step=self.timeStep, train=training)
             if self.epsilon > self.final_epsilon and self.onlineTimeStep > self.observe:
@@ -243,6 +273,8 @@ class VecBrain:
             shared = dict(online=host(self.net.store_params(0)), target=host(self.net.store_params(1)), adam_m=host(m), adam_v=host(v),
                           beta_pows=np.asarray(pows, np.float32), scalars=np.array([self.timeStep, self.onlineTimeStep, self.world, self.seed], np.int64),
                           epsilon=np.array([self.epsilon], np.float64), n_step=np.array([self.n_step], np.int64))
+            if self.support is not None:                     # (scalar-head checkpoints carry no support)
+                shared["support"] = np.array(self.support, np.float64)
         if self.world == 1:
             np.savez(self._npz(path), **shared, **local)
             return
@@ -262,6 +294,7 @@ class VecBrain:
         saved_n = int(z["n_step"][0]) if "n_step" in z.files else 1          # (checkpoints from before n-step returns: one-step)
         if saved_n != self.n_step:
             raise ValueError(f"checkpoint {path} was trained with n_step = {saved_n}, this VecBrain has n_step = {self.n_step}")
+        check_checkpoint_support(z, self.support, path)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         self.net.load_params(z["online"], 0)

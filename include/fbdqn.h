@@ -274,6 +274,7 @@ int fb_replay_load_state(fb_replay_t h, const void *blob_host, size_t bytes);
  *   W_conv1[8,8,4,32] b[32] W_conv2[4,4,32,64] b[64] W_conv3[3,3,64,64] b[64] W_fc1[1600,FC] b[FC]
  *   then  W_fc2[FC,A] b[A]            (plain)
  *   or    W_v[FC,1] b_v[1] W_a[FC,A] b_a[A]   (dueling)
+ *   or    W_fc2[FC,A*N] b[A*N]        (C51, below)
  */
 typedef struct fb_qnet *fb_qnet_t;
 
@@ -291,6 +292,32 @@ typedef struct fb_qnet *fb_qnet_t;
  * <= 128 that export their gradient (flat_grad), the caller adds them up and calls fb_qnet_apply_adam once; s2 / t are ignored (pass
  * s / zeros), abs_err / q_target are not meaningful; loss = this chunk's share of the mean.  Not available through fb_vec_step. */
 #define FB_ALGO_PG 4
+
+/* ------------------------------------------------------------------ distributional Q-learning (C51, Bellemare, Dabney & Munos 2017)
+ * A C51 net (FB_ARCH_C51, fb_qnet_create_c51) has the plain trunk and fc1, then the head  W_fc2[FC, A*N] b[A*N]  (N = n_atoms; column
+ * a*N + i is atom i of action a; fb_qnet_init_params: the same truncated-normal weights / 0.01 biases).
+ *   support     z_i = v_min + i * dz, dz = (v_max - v_min) / (N - 1), fixed at creation; 2 <= N <= 64, A * N <= 128, v_min < v_max finite
+ *   head        logits[b][a][i] = relu(h_fc1[b]) . W[:, a*N + i] + b[a*N + i],  p[b][a][.] = softmax_i(logits[b][a][.]),
+ *               Q[b][a] = sum_i z_i p[b][a][i].  fb_qnet_forward / _act / _act_nib / fb_eval_q / fb_eval_run return that Q; acting
+ *               and evaluation take its argmax (first maximum) and the plain net's epsilon rule (same Philox draws)
+ *   target      a* = argmax_a Q(s', a) of the target net (FB_ALGO_C51) or of the online net (FB_ALGO_C51_DOUBLE, Rainbow); the
+ *               distribution p' = p_target(s', a*)
+ *   projection  Tz_j = clamp(R + Gamma (1 - done) z_j, v_min, v_max), b_j = (Tz_j - v_min) / dz (then clamped to [0, N-1]),
+ *               l = floor(b_j), u = ceil(b_j): m_l += p'_j (u - b_j), m_u += p'_j (b_j - l); when l == u, m_l += p'_j.
+ *               Gamma = gamma^n as DESIGN.md section 10 forms it (n-step memories work unchanged)
+ *   loss        mean_b -sum_i m_i log_softmax(logits[b][a_b])_i, fp32, targets constant; dLoss/dlogits = (p - m) / B on the taken
+ *               action, 0 elsewhere.  abs_err / q_target of fb_qnet_train_step are not written.
+ * Accepted: fb_qnet_train_step, fb_train_from_replay, fb_train_steps and fb_vec_step with a UNIFORM memory, 1 <= B <= min(max_batch,
+ * 256), any n, fused Adam or flat_grad.  FB_ERR_INVALID before any launch or counter change: a C51 algo on another net or another
+ * algo on a C51 net, a prioritized memory, fb_vec_step_dp.  fb_vec_step runs the one-stream schedule with the head as its own launch.
+ * fb_qnet_forward_dist: the probabilities p (f32[B][A][N], [dev]) of `which` net for u8 states, 1 <= B <= 3 * max_batch. */
+#define FB_ARCH_C51 2
+#define FB_ALGO_C51 5
+#define FB_ALGO_C51_DOUBLE 6
+#define FB_C51_MAX_ATOMS 64
+int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out);
+int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host);      /* n_atoms = 0: not a C51 net */
+int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream);
 
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
