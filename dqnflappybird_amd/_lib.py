@@ -18,6 +18,7 @@ ARCH_PLAIN, ARCH_DUELING, ARCH_C51 = 0, 1, 2
 NET_ONLINE, NET_TARGET = 0, 1
 ALGO_DQN, ALGO_NATURE, ALGO_DOUBLE, ALGO_PER, ALGO_PG = 0, 1, 2, 3, 4
 ALGO_C51, ALGO_C51_DOUBLE = 5, 6
+ALGO_C51_PER, ALGO_C51_DOUBLE_PER = 7, 8                # C51 with prioritized replay (include/fbdqn.h)
 C51_MAX_ATOMS = 64                                    # include/fbdqn.h FB_C51_MAX_ATOMS
 DTYPE_F32, DTYPE_BF16 = 0, 1
 PER_EXACT, PER_FAST = 0, 1

@@ -28,6 +28,15 @@ int fb_set_error(int code, const char *fmt, ...);
 
 static inline hipStream_t fb_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// ---------------------------------------------------------------- algo families (include/fbdqn.h)
+static inline bool is_c51_algo(int algo) {          // trains a C51 net
+    return algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || algo == FB_ALGO_C51_PER || algo == FB_ALGO_C51_DOUBLE_PER;
+}
+static inline bool is_double_c51(int algo) { return algo == FB_ALGO_C51_DOUBLE || algo == FB_ALGO_C51_DOUBLE_PER; }     // a* online
+static inline bool is_per_algo(int algo) {          // prioritized memory, importance weights, |TD error| / priority out
+    return algo == FB_ALGO_PER || algo == FB_ALGO_C51_PER || algo == FB_ALGO_C51_DOUBLE_PER;
+}
+
 // Hand-offs between kernels of two streams through device words (fb_vec_step's split schedule).  A word only ever grows (the step
 // number).  Stores and polls are relaxed agent-scope atomics (they go to the coherent level, past the XCD's own L2); a reader that goes
 // on to READ what the other kernel wrote adds fb_flag_acquire() -- the L2s of the eight XCDs are not coherent with each other inside a

@@ -101,12 +101,12 @@ void fb_mt_init_by_array_host(FbMT *s, const uint32_t *key, int key_length) {
 extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int batch, int n_steps, int64_t *idx, uint8_t *s,
                               uint8_t *s2, uint8_t *a, float *r, uint8_t *t, float *loss, double gamma, void *stream) {
     FB_REQUIRE(replay && net && idx && s && s2 && a && r && t && loss && n_steps >= 1, "fb_train_steps: bad argument");
-    FB_REQUIRE(algo != FB_ALGO_PER, "fb_train_steps: prioritized replay needs the importance weights: use the separate calls");
+    FB_REQUIRE(!is_per_algo(algo), "fb_train_steps: prioritized replay needs the importance weights: use the separate calls (algo %d)", algo);
     // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
     // here as well so that it comes before any counter moves
-    if (algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || fb_qnet_is_c51(net)) {
-        FB_REQUIRE((algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE) == (fb_qnet_is_c51(net) != 0),
-                   "%s: a C51 net takes FB_ALGO_C51 or FB_ALGO_C51_DOUBLE, and those algos take a C51 net only (algo %d)", "fb_train_steps", algo);
+    if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
+        FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
+                   "%s: a C51 net takes a C51 algo (FB_ALGO_C51 or FB_ALGO_C51_DOUBLE), and those algos take a C51 net only (algo %d)", "fb_train_steps", algo);
         FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_steps");
     }
     static const bool gathered_form = getenv("FB_TRAIN_STEPS_GATHER") && atoi(getenv("FB_TRAIN_STEPS_GATHER")) == 1;
@@ -264,18 +264,20 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
                            int batch, float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
     FB_REQUIRE(env && replay && net && b, "fb_vec_step: NULL handle");
     FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "fb_vec_step: NULL env buffer");
-    const bool per = algo == FB_ALGO_PER;
+    const bool per = is_per_algo(algo);      // (FB_ALGO_PER, FB_ALGO_C51_PER, FB_ALGO_C51_DOUBLE_PER)
     if (per && train) FB_REQUIRE(b->isw && b->isw32 && b->abs_err, "fb_vec_step: the prioritized step needs the isw / isw32 / abs_err buffers");
     // every argument check of the calls below happens HERE, before the replay's push counter moves or anything is launched: a
     // rejected step must leave the handles exactly as they were (a counted push without its env launch would make every later
     // gather address a ring slot that was never written)
-    FB_REQUIRE((algo >= 0 && algo <= 3) || algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE, "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51, FB_ALGO_C51_DOUBLE)", algo);
-    // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
-    // here as well so that it comes before any counter moves
-    if (algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || fb_qnet_is_c51(net)) {
-        FB_REQUIRE((algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE) == (fb_qnet_is_c51(net) != 0),
-                   "%s: a C51 net takes FB_ALGO_C51 or FB_ALGO_C51_DOUBLE, and those algos take a C51 net only (algo %d)", "fb_vec_step", algo);
-        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_vec_step");
+    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_C51_DOUBLE_PER)", algo);
+    // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
+    // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
+    // counter moves
+    if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
+        FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
+                   "%s: a C51 net takes a C51 algo (FB_ALGO_C51, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a C51 net only (algo %d)", "fb_vec_step", algo);
+        if (!is_per_algo(algo))
+            FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_vec_step");
     }
     FB_REQUIRE(per == (fb_replay_is_prioritized(replay) != 0), "fb_vec_step: algo %d and the memory's kind (uniform / prioritized) do not match", algo);
     FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_vec_step: n_envs %d does not match the env (%d) / replay (%d) handles",
@@ -429,15 +431,19 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
 extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo, int batch, const int64_t *idx, const float *isw, uint8_t *a,
                                     float *r, uint8_t *t, double gamma, float *loss, float *abs_err, float *flat_grad, void *stream) {
     FB_REQUIRE(replay && net && idx && a && r && t && loss, "fb_train_from_replay: NULL argument");
-    FB_REQUIRE((algo >= 0 && algo <= 3) || algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE, "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51, FB_ALGO_C51_DOUBLE)", algo);
-    // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
-    // here as well so that it comes before any counter moves
-    if (algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || fb_qnet_is_c51(net)) {
-        FB_REQUIRE((algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE) == (fb_qnet_is_c51(net) != 0),
-                   "%s: a C51 net takes FB_ALGO_C51 or FB_ALGO_C51_DOUBLE, and those algos take a C51 net only (algo %d)", "fb_train_from_replay", algo);
-        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_from_replay");
+    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_C51_DOUBLE_PER)", algo);
+    // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
+    // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
+    // counter moves
+    if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
+        FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
+                   "%s: a C51 net takes a C51 algo (FB_ALGO_C51, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a C51 net only (algo %d)", "fb_train_from_replay", algo);
+        if (!is_per_algo(algo))
+            FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_from_replay");
     }
-    FB_REQUIRE(algo != FB_ALGO_PER || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
+    FB_REQUIRE(!is_per_algo(algo) || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
+    if (is_c51_algo(algo) && is_per_algo(algo))
+        FB_REQUIRE(fb_replay_is_prioritized(replay), "fb_train_from_replay: algo %d (C51 with prioritized replay) trains from a prioritized memory only", algo);
     FB_REQUIRE(batch >= 1 && batch <= 256, "fb_train_from_replay: batch must be in 1..256");
     int rc = fb_replay_check_gamma(replay, gamma, "fb_train_from_replay");
     if (rc != FB_OK) return rc;

@@ -1622,8 +1622,12 @@ struct C51LossArgs {
     const float *p_on, *p_next, *p_tgt;
     const float *hf; const uint8_t *act; const float *rew; const uint8_t *term; double gamma;
     float *dl, *xs, *lterm, *dhf;
+    const float *isw; float *abs_err;                            // PW only: importance weights f32[B]; priorities f32[B] out or NULL
 };
-template <int AT>
+// PW (FB_ALGO_C51_PER / _DOUBLE_PER): the loss term and the logit gradient are weighted by isw[b] -- g = ((p - m) / B) * w, so that
+// dhf, the second launch's gradients and the loss all carry the weight and w = 1 gives the unweighted results bit for bit -- and the
+// sample's priority max(0, KL(m || p)) goes to abs_err[b].  (L.algo: the target's form only, FB_ALGO_C51 or FB_ALGO_C51_DOUBLE.)
+template <int AT, bool PW = false>
 __global__ __launch_bounds__(256) void c51_loss_kernel(C51LossArgs L) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= L.B) return;                                        // (wave-uniform)
@@ -1670,8 +1674,17 @@ __global__ __launch_bounds__(256) void c51_loss_kernel(C51LossArgs L) {
     }
     // loss -sum_i m_i log_softmax(logits(s, a_b))_i and its logit gradient (p - m) / B
     const float ps = c51_softmax(la, on, lse_s);
-    const float lossb = wave_sum(on ? -m * (la - lse_s) : 0.f);
-    const float g = on ? (ps - m) / (float)B : 0.f;
+    float lossb = wave_sum(on ? -m * (la - lse_s) : 0.f);
+    float g = on ? (ps - m) / (float)B : 0.f;
+    if constexpr (PW) {
+        // KL(m || p) = sum_i m_i (log m_i - log p_i) over the atoms with m_i > 0 (log m_i through a select: no branch around it)
+        const float w = L.isw[b];
+        const bool pos = on && m > 0.f;
+        const float kl = wave_sum(pos ? m * (logf(pos ? m : 1.f) - (la - lse_s)) : 0.f);
+        if (L.abs_err && lane == 0) L.abs_err[b] = fmaxf(kl, 0.f);
+        lossb *= w;
+        g *= w;
+    }
     L.dl[(size_t)b * 64 + lane] = g;
     if (lane == 0) L.lterm[b] = lossb;
     const int AN = A * N;
@@ -3907,11 +3920,16 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         if (c51) FB_K(K_LOSS) {                     // C51: per-sample distribution / projection / dhf, then the per-unit reductions
             if (p.tick) h->adam_ticked = !p.apply_adam;
             C51LossArgs L;
-            L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->off; L.sup = h->sup;
+            const bool pw = is_per_algo(p.algo);     // (prioritized: weighted loss, KL priorities)
+            L.algo = is_double_c51(p.algo) ? FB_ALGO_C51_DOUBLE : FB_ALGO_C51;
+            L.B = B; L.FC = FC; L.A = h->A; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->off; L.sup = h->sup;
             L.p_on = h->params[0]; L.p_next = p.sl.s[1].params; L.p_tgt = p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params;
             L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
             L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
-            if (h->A == 2) hipLaunchKernelGGL(c51_loss_kernel<2>, dim3((B + 3) / 4), dim3(256), 0, st, L);
+            L.isw = pw ? p.isw : nullptr; L.abs_err = pw ? p.abs_err : nullptr;
+            if (pw && h->A == 2) hipLaunchKernelGGL((c51_loss_kernel<2, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
+            else if (pw) hipLaunchKernelGGL((c51_loss_kernel<MAXA, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
+            else if (h->A == 2) hipLaunchKernelGGL(c51_loss_kernel<2>, dim3((B + 3) / 4), dim3(256), 0, st, L);
             else hipLaunchKernelGGL(c51_loss_kernel<MAXA>, dim3((B + 3) / 4), dim3(256), 0, st, L);
             const C51GradArgs gA{B, FC, h->A, h->sup.N, h->off, h->c51_dl, h->c51_xs, h->c51_lt, h->dhf, p.a, G, p.loss, h->gmax, h->adam, p.tick};
             hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);
@@ -4242,22 +4260,23 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
                       const uint8_t *t, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
     FB_REQUIRE(h && a && r && t && loss && (ring || (s && s2)), "fb_qnet_train_step: NULL argument");
-    FB_REQUIRE(algo >= 0 && algo <= FB_ALGO_C51_DOUBLE, "fb_qnet_train_step: unknown algo %d", algo);
+    FB_REQUIRE(algo >= 0 && algo <= FB_ALGO_C51_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
     {
-        const bool c51a = algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE;
+        const bool c51a = is_c51_algo(algo);
         FB_REQUIRE(c51a == (h->sup.N > 0), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
-                                                : "fb_qnet_train_step: a C51 net trains with FB_ALGO_C51 or FB_ALGO_C51_DOUBLE only (got algo %d)", algo);
+                                                : "fb_qnet_train_step: a C51 net trains with FB_ALGO_C51, FB_ALGO_C51_PER, FB_ALGO_C51_DOUBLE_PER "
+                                                  "or FB_ALGO_C51_DOUBLE only (got algo %d)", algo);
     }
     FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "fb_qnet_train_step: batch %d exceeds min(max_batch, %d)", B, MAXTB);
     FB_REQUIRE(algo != FB_ALGO_PG || (B <= 128 && !ring && gamma >= (double)B), "fb_qnet_train_step: FB_ALGO_PG takes chunks of <= 128 gathered states and gamma = the whole batch's sample count (>= %d)", B);
-    FB_REQUIRE(algo != FB_ALGO_PER || isw, "fb_qnet_train_step: PER needs isw");
+    FB_REQUIRE(!is_per_algo(algo) || isw, "fb_qnet_train_step: PER needs isw (algo %d)", algo);
     Plan p; memset(&p, 0, sizeof(p));
     // forward: s through the online net, s' through the net(s) the algorithm asks for
     p.ns = 2;
     p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
     if (algo == FB_ALGO_DQN || algo == FB_ALGO_PG) p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};               // BrainDQN.py:205 (same net); PG: s2 is forwarded and ignored
-    else if (algo == FB_ALGO_DOUBLE || algo == FB_ALGO_C51_DOUBLE) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
-    else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net (Nature, PER, C51)
+    else if (algo == FB_ALGO_DOUBLE || is_double_c51(algo)) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
+    else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net (Nature, PER, C51, C51_PER)
     p.sl.rb = h->nsplit_train == 1;
     p.train = true; p.algo = algo; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.isw = isw; p.gamma = gamma;
     p.loss = loss; p.abs_err = abs_err; p.y = q_target;
@@ -4305,7 +4324,7 @@ int fb_qnet_refresh_planes(fb_qnet_t h, void *stream) {
 
 int fb_qnet_profile_ring(fb_qnet_t h, int kernel, int reps, int algo, int B, const FbRingSrc *ring, float *loss, void *stream) {
     FB_REQUIRE(h && ring && kernel >= 0 && kernel < K_COUNT && reps >= 1, "fb_qnet_profile_ring: bad argument");
-    FB_REQUIRE(algo != FB_ALGO_PER, "fb_qnet_profile_ring: uniform memories only");
+    FB_REQUIRE(!is_per_algo(algo), "fb_qnet_profile_ring: uniform memories only");
     Plan p;
     int rc = train_plan(h, algo, B, nullptr, ring->a, ring->r, nullptr, ring->t, nullptr, 0.99, loss, nullptr, nullptr, nullptr, &p, ring);
     if (rc != FB_OK) return rc;

@@ -277,8 +277,10 @@ class VecReplay:
 
 
 ALGOS = {"dqn": L.ALGO_DQN, "nature": L.ALGO_NATURE, "double": L.ALGO_DOUBLE, "per": L.ALGO_PER, "pg": L.ALGO_PG,
-         "c51": L.ALGO_C51, "c51double": L.ALGO_C51_DOUBLE}
-C51_ALGOS = ("c51", "c51double")
+         "c51": L.ALGO_C51, "c51double": L.ALGO_C51_DOUBLE, "c51per": L.ALGO_C51_PER, "c51doubleper": L.ALGO_C51_DOUBLE_PER}
+C51_ALGOS = ("c51", "c51double")                            # C51 on a uniform memory
+C51_PER_ALGOS = ("c51per", "c51doubleper")                  # C51 on a prioritized memory (weighted loss, KL priorities)
+PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the algos that take a prioritized memory and its importance weights
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
 
 
@@ -510,7 +512,7 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
     SumTree leaf indices of replay.sample, isw its importance weights; want_abs_err returns |TD error| for update_priorities.
     An n-step memory (replay.set_n_step) is read as (s, a, R, s', done) and bootstrapped with gamma^n; gamma must be the memory's.
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, abs_err f32[B]]) on the device."""
-    if (replay.prioritized or algo == "per") and isw is None:
+    if (replay.prioritized or algo in PER_ALGOS) and isw is None:
         raise ValueError("the prioritized step needs the importance weights (isw)")
     _dev_check(idx, flat_grad, isw)
     B, dev = int(idx.numel()), idx.device
@@ -531,7 +533,7 @@ class TrainSteps:
     n-step memory gamma must be the memory's (the steps bootstrap with gamma^n)."""
 
     def __init__(self, replay, net, batch=32, algo="dqn", gamma=0.99):
-        if replay.prioritized or algo == "per":
+        if replay.prioritized or algo in PER_ALGOS:
             raise ValueError("TrainSteps is for uniform replay (PER needs the importance weights: use the separate calls)")
         self.replay, self.net, self.batch, self.algo, self.gamma = replay, net, batch, ALGOS[algo], float(gamma)
         dev, B = replay.device, batch
@@ -563,10 +565,10 @@ class VecStep:
         RCCL communicator (overlapped with the conv backward) and Adam, all in the one host call; mean_loss divides by the world size."""
         if algo in C51_ALGOS and replay.prioritized:
             raise ValueError(f"algo {algo!r} trains from a uniform memory only (prioritized replay with C51 is not supported)")
-        if algo in C51_ALGOS and dist is not None:
+        if algo in C51_ALGOS + C51_PER_ALGOS and dist is not None:
             raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (one GPU only)")
-        if replay.prioritized != (algo == "per"):
-            raise ValueError("algo 'per' goes with a prioritized memory, every other algo with a uniform one")
+        if replay.prioritized != (algo in PER_ALGOS):
+            raise ValueError(f"algos {PER_ALGOS} go with a prioritized memory, every other algo with a uniform one (algo {algo!r})")
         if dist is not None and flat_grad is None:
             raise ValueError("VecStep(dist=...) needs the flat_grad buffer the gradient is reduced in")
         self.dist, self.mean_loss = dist, int(bool(mean_loss))
@@ -584,7 +586,7 @@ class VecStep:
         self.r = torch.empty(B, dtype=torch.float32, device=dev)
         self.t = torch.empty(B, dtype=torch.uint8, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        per = algo == "per"                                # Memory.sample's weights (f64, and as the float32 placeholder takes them), |TD errors|
+        per = algo in PER_ALGOS                            # Memory.sample's weights (f64, and as the float32 placeholder takes them), |TD errors|
         self.isw = torch.zeros(B, dtype=torch.float64, device=dev) if per else None
         self.isw32 = torch.zeros(B, dtype=torch.float32, device=dev) if per else None
         self.abs_err = torch.zeros(B, dtype=torch.float32, device=dev) if per else None

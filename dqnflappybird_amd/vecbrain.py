@@ -6,13 +6,16 @@ envs per GPU, entirely device resident: no tensor leaves HBM between getAction a
 
 Host-side schedule follows the reference: training starts once onlineTimeStep > OBSERVE, epsilon
 decays by (INITIAL - FINAL) / EXPLORE per step after that, Nature/Double sync the target net when
-timeStep % 500 == 0, PER never does.
+timeStep % 500 == 0, PER never does (the reference agent's quirk, kept for algo 'per' only); C51 and C51 with prioritized
+replay ('c51per' / 'c51doubleper') sync every replace_target_iter steps.
 """
 from . import dist as fdist
 
-MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True}
+MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True, "c51per": True, "c51doubleper": True}
 C51_ALGOS = ("c51", "c51double")                             # distributional Q-learning (include/fbdqn.h, DESIGN.md section 11)
-TARGET_SYNC = ("nature", "double") + C51_ALGOS              # algos whose target net is synced every replace_target_iter steps
+C51_PER_ALGOS = ("c51per", "c51doubleper")                   # ... with prioritized replay: weighted loss, KL priorities
+PER_ALGOS = ("per",) + C51_PER_ALGOS                         # algos with a prioritized memory
+TARGET_SYNC = ("nature", "double") + C51_ALGOS + C51_PER_ALGOS   # algos whose target net is synced every replace_target_iter steps
 
 
 class HipVecBackend:
@@ -102,13 +105,14 @@ class VecBrain:
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
-        algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk)."""
+        algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
+        'c51per' / 'c51doubleper': the same with prioritized replay (importance-weighted loss, KL priorities; n_step at creation)."""
         n_step = int(n_step)
         if not 1 <= n_step <= 16:
             raise ValueError(f"n_step must be in 1..16, got {n_step}")
         be = backend or HipVecBackend()
         self.support = None
-        if algo in C51_ALGOS:
+        if algo in C51_ALGOS + C51_PER_ALGOS:
             from .vec import check_support
             if arch not in ("plain", "c51"):
                 raise ValueError(f"algo {algo!r} builds a C51 head on the plain trunk: arch {arch!r} (dueling C51) is not supported")
@@ -116,11 +120,14 @@ class VecBrain:
                 raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (world = {world}; one GPU only)")
             if not getattr(be, "c51", False):
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no C51 nets")
+            if algo in C51_PER_ALGOS and not getattr(be, "per_one_step", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
+                                 f"algo {algo!r} needs it")
             self.support = check_support(n_atoms, v_min, v_max)
             arch = "c51"
-        if n_step > 1 and algo == "per" and not getattr(be, "per_n_step", False):
+        if n_step > 1 and algo in PER_ALGOS and not getattr(be, "per_n_step", False):
             raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend offers n-step returns on uniform replay only: "
-                             f"algo 'per' takes n_step = 1 there")
+                             f"algo {algo!r} takes n_step = 1 there")
         self.be = be
         self.n, self.algo, self.batch, self.gamma = n_envs, algo, batch, gamma
         self.n_step = n_step
@@ -136,12 +143,12 @@ class VecBrain:
         self.replace_target_iter = replace_target_iter
         self.seed = seed
         self.env = be.env(n_envs, seed + 1000003 * rank)     # envs shard by rank: every rank plays its own games
-        if n_step > 1 and algo == "per":                     # ... into its own replay shard (a prioritized one gets n at creation)
+        if n_step > 1 and algo in PER_ALGOS:                 # ... into its own replay shard (a prioritized one gets n at creation)
             self.replay = be.replay(capacity, n_envs, True, n_step=n_step, gamma=gamma)
         else:
-            self.replay = be.replay(capacity, n_envs, algo == "per")
+            self.replay = be.replay(capacity, n_envs, algo in PER_ALGOS)
         self.replay.seed(seed + rank, sampler)
-        if n_step > 1 and algo != "per":                     # (only then: a backend without n-step memories keeps working at n = 1)
+        if n_step > 1 and algo not in PER_ALGOS:             # (only then: a backend without n-step memories keeps working at n = 1)
             if not hasattr(self.replay, "set_n_step"):
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend's replay has no n-step view (n_step = {n_step})")
             self.replay.set_n_step(n_step, gamma)
@@ -171,9 +178,9 @@ class VecBrain:
         # the whole step is one host call (fb_vec_step): uniform replay with the head, random.sample and the Memory append riding in the
         # env launch; prioritized replay with store -> Memory.sample -> weighted train -> batch_update as launches of the same call
         self.native = None
-        if self.grad is not None and algo != "per" and hasattr(be, "native"):
+        if self.grad is not None and algo not in PER_ALGOS and hasattr(be, "native"):
             self.native = be.native(rank, world)
-        if algo == "per" and not getattr(be, "per_one_step", False):
+        if algo in PER_ALGOS and not getattr(be, "per_one_step", False):
             self.one_step = None                             # (a backend without the fused prioritized step: the separate calls below)
         elif self.native is not None:
             self.one_step = be.step(self.env, self.replay, self.net, batch, algo, gamma, self.grad, dist=self.native, mean_loss=MEAN_LOSS[algo])
@@ -188,15 +195,15 @@ class VecBrain:
             idx, isw = self.replay.sample(self.batch)
         if hasattr(self.be, "train_from_replay") and self.batch <= 256:
             # the conv trunk reads the sampled transitions' frame bits in the ring: no gather launch, no u8 copies
-            loss, abs_err = self.be.train_from_replay(self.replay, self.net, self.algo, idx, isw, self.gamma, self.grad, self.algo == "per")
+            loss, abs_err = self.be.train_from_replay(self.replay, self.net, self.algo, idx, isw, self.gamma, self.grad, self.algo in PER_ALGOS)
         else:
             s, a, r, s2, t = self.replay.gather(idx)
             loss, abs_err, _ = self.net.train_step(self.algo, s, a, r, s2, t, isw=isw, gamma=self.boot_gamma, flat_grad=self.grad,
-                                                   want_aux=self.algo == "per")
+                                                   want_aux=self.algo in PER_ALGOS)
         if self.grad is not None:
             self.reduce()
             self.net.apply_adam(self.grad)
-        if self.algo == "per":
+        if self.algo in PER_ALGOS:
             self.replay.update_priorities(idx, abs_err=abs_err)
         self.last_loss = loss
 
@@ -222,7 +229,7 @@ class VecBrain:
         _, reward, terminal, _ = self.env.frame_step(actions, want_u8=False)
         training = self.onlineTimeStep > self.observe
         idx = None
-        if training and self.algo != "per":                  # store + random.sample in one launch (same indices)
+        if training and self.algo not in PER_ALGOS:          # store + random.sample in one launch (same indices)
             idx = self.replay.push_sample(self.env.frame_bits, actions, reward, terminal, self.batch)
         else:
             self.replay.push(self.env.frame_bits, actions, reward, terminal)

@@ -309,11 +309,30 @@ typedef struct fb_qnet *fb_qnet_t;
  *               action, 0 elsewhere.  abs_err / q_target of fb_qnet_train_step are not written.
  * Accepted: fb_qnet_train_step, fb_train_from_replay, fb_train_steps and fb_vec_step with a UNIFORM memory, 1 <= B <= min(max_batch,
  * 256), any n, fused Adam or flat_grad.  FB_ERR_INVALID before any launch or counter change: a C51 algo on another net or another
- * algo on a C51 net, a prioritized memory, fb_vec_step_dp.  fb_vec_step runs the one-stream schedule with the head as its own launch.
+ * algo on a C51 net, a prioritized memory (FB_ALGO_C51_PER below takes one), fb_vec_step_dp.  fb_vec_step runs the one-stream schedule with the head as its own launch.
  * fb_qnet_forward_dist: the probabilities p (f32[B][A][N], [dev]) of `which` net for u8 states, 1 <= B <= 3 * max_batch. */
 #define FB_ARCH_C51 2
 #define FB_ALGO_C51 5
 #define FB_ALGO_C51_DOUBLE 6
+/* C51 with prioritized replay (Rainbow without dueling / noisy nets).  Two algos of their own: the memory's kind never switches what
+ * FB_ALGO_C51 / _DOUBLE do (those keep refusing a prioritized memory).
+ *   FB_ALGO_C51_PER        target as FB_ALGO_C51,        a PRIORITIZED memory only
+ *   FB_ALGO_C51_DOUBLE_PER target as FB_ALGO_C51_DOUBLE, a PRIORITIZED memory only
+ * Support, projection and Gamma = gamma^n exactly as above.  With the importance weights w_b (isw, f32[B], required: the float32 form
+ * of Memory.sample's ISWeights, what FB_ALGO_PER reads):
+ *   loss        (1/B) sum_b w_b CE_b,  CE_b = -sum_i m_i log p_i(s_b, a_b)  (the reference PER agent's mean(ISW * sq), with CE for sq)
+ *   gradient    dLoss/dlogits = ((p - m) / B) * w_b on the taken action, formed in that order: with w = 1 the results are FB_ALGO_C51's
+ *               (_DOUBLE's) bit for bit
+ *   abs_err[b]  (when non-NULL) the priority max(0, KL_b), KL_b = sum_i [m_i > 0] m_i (log m_i - log p_i) in fp32, no w_b factor (the
+ *               Rainbow paper's choice: KL goes to 0 as the fit improves, CE only to H(m) -- up to log 2 for mass split over two atoms).
+ *               Memory.batch_update is unchanged, min(err + 0.01, 1)^0.6; early in training KL ~ log N - H(m) (~3 for 51 atoms), so
+ *               priorities sit at the clip 1 until the head fits.  q_target is not written.
+ * Accepted: fb_qnet_train_step (a C51 net, isw), fb_train_from_replay (isw, a prioritized memory) and fb_vec_step (isw / isw32 / abs_err
+ * buffers): FB_ALGO_PER's path there (sample ahead, ring-fed train from 256 envs, batch_update ahead or in line), the head as its own
+ * launch, the one-stream schedule.  FB_ERR_INVALID before any launch or counter change: fb_train_steps (no weights), fb_vec_step_dp, a
+ * uniform memory, a scalar net, no isw. */
+#define FB_ALGO_C51_PER 7
+#define FB_ALGO_C51_DOUBLE_PER 8
 #define FB_C51_MAX_ATOMS 64
 int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out);
 int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host);      /* n_atoms = 0: not a C51 net */
@@ -427,7 +446,7 @@ typedef struct {
     uint8_t *s, *s2, *a, *t; float *r;              /* gathered minibatch: u8[B,80,80,4] x2, u8[B], u8[B], f32[B] */
     float *loss;                                    /* f32[1] out */
     float *flat_grad;                               /* f32[n_params] or NULL */
-    /* prioritized replay (algo = FB_ALGO_PER) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
+    /* prioritized replay (algo = FB_ALGO_PER, FB_ALGO_C51_PER, FB_ALGO_C51_DOUBLE_PER) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
      * float32 placeholder takes them (f32[B]), and the |TD errors| Memory.batch_update receives (f32[B]).
      * With the reference-order tree and 4096 envs or more Memory.batch_update of a step runs on the memory's own side stream, beside the NEXT step's acting
      * forward (its result is first needed by that step's Memory.store, which follows it there): idx and abs_err are read after

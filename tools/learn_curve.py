@@ -6,12 +6,12 @@ across episode ends.  A score curve can.  The reference's own evidence is logs_b
 2 - 4 M single-env steps, BrainDQNNature.py:149-197); no target score is set here, only "clearly above the untrained policy's".
 
     python tools/learn_curve.py [--envs 16,1024] [--lrs 1e-6,1e-5] [--steps 2000000] [--window 50000] [--algo nature] [--out FILE]
-                                [--n-step K] [--eval-envs 4096] [--algo c51|c51double --atoms 51 --vmin -10 --vmax 10]
+                                [--n-step K] [--eval-envs 4096] [--algo c51|c51double|c51per|c51doubleper --atoms 51 --vmin -10 --vmax 10]
 
 One VecBrain run per (envs, lr); one train step per loop step once onlineTimeStep > OBSERVE, as in the reference.  Every `window`
 steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and zeroed, so each
 row is the window's own figure, not a running average.  Rows go to stdout and to --out as they are produced.
---n-step K trains from K-step returns (VecBrain(n_step=K); with --algo per a prioritized memory created with K-step returns); the summary gives the train steps at which the windowed mean score first
+--n-step K trains from K-step returns (VecBrain(n_step=K); with --algo per / c51per / c51doubleper a prioritized memory created with K-step returns); the summary gives the train steps at which the windowed mean score first
 passed 1 / 10 / 100, and --eval-envs M (> 0) ends each run with VecBrain.evaluate() on M fresh greedy games.
 """
 import argparse
@@ -91,7 +91,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--explore", type=int, default=1_000_000)
     ap.add_argument("--n-step", type=int, default=1)
-    ap.add_argument("--atoms", type=int, default=51, help="--algo c51 / c51double: atoms of the support")
+    ap.add_argument("--atoms", type=int, default=51, help="--algo c51 / c51double / c51per / c51doubleper: atoms of the support")
     ap.add_argument("--vmin", type=float, default=-10.0)
     ap.add_argument("--vmax", type=float, default=10.0)
     ap.add_argument("--eval-envs", type=int, default=0, help="end each run with VecBrain.evaluate() on this many games (0 = no evaluation)")
