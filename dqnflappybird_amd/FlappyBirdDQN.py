@@ -7,6 +7,8 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
     python -m dqnflappybird_amd.FlappyBirdDQN --model c51 --vec 1024                (distributional C51, vectorised loop only)
     python -m dqnflappybird_amd.FlappyBirdDQN --model c51per --vec 1024 --n-step 3  (C51 + prioritized replay + 3-step returns;
                                                                                        c51doubleper: with the double target)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 (the same with the dueling C51 head: Rainbow
+                                                                                       without noisy nets)
 
 `actorcritic` / `policygradient` are out of scope (broken in the reference).
 """
@@ -73,7 +75,7 @@ def main():
     parser.add_argument("--vec", type=int, default=0, help="run N vectorised envs (device-resident loop)")
     parser.add_argument("--n-step", type=int, default=1, help="learn from K-step returns (--vec, uniform replay; 1 = the reference's one-step TD)")
     args = parser.parse_args()
-    if args.model in ("c51", "c51per", "c51doubleper") and not args.vec:    # (not reference agents: the single-env dispatch stays the reference's)
+    if args.model in ("c51", "c51per", "c51doubleper", "rainbow") and not args.vec:    # (not reference agents: the single-env dispatch stays the reference's)
         parser.error(f"--model {args.model} needs --vec: distributional C51 runs in the vectorised loop only")
     if args.n_step != 1:                                 # (refused before anything touches the GPU)
         if not 1 <= args.n_step <= L.NSTEP_MAX:
@@ -92,8 +94,9 @@ def main():
         if args.model in ("actorcritic", "policygradient"):
             raise SystemExit("--vec runs the DQN family; the actor-critic / policy-gradient agents are single-env (as in the reference)")
         algo = {"dqn": "dqn", "ddqn": "nature", "dqnnature": "nature", "duelingdqn": "nature", "prioritydqn": "per", "c51": "c51",
-                "c51per": "c51per", "c51doubleper": "c51doubleper"}[args.model]
-        vb = VecBrain(args.vec, algo=algo, rank=rank, world=world, n_step=args.n_step)
+                "c51per": "c51per", "c51doubleper": "c51doubleper", "rainbow": "c51doubleper"}[args.model]
+        arch = "c51dueling" if args.model == "rainbow" else "plain"      # rainbow: dueling C51 head, double target, prioritized replay
+        vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)
     else:
         playFlappyBird(args.model, args.steps, verbose=not args.quiet)

@@ -14,7 +14,7 @@ ASSET_BLOB = os.path.join(_HERE, "assets", "sprites.bin")
 FB_OK = 0
 REPLAY_UNIFORM, REPLAY_PER = 0, 1
 RNG_CPYTHON, RNG_PHILOX, RNG_NUMPY = 0, 1, 2
-ARCH_PLAIN, ARCH_DUELING, ARCH_C51 = 0, 1, 2
+ARCH_PLAIN, ARCH_DUELING, ARCH_C51, ARCH_C51_DUELING = 0, 1, 2, 3
 NET_ONLINE, NET_TARGET = 0, 1
 ALGO_DQN, ALGO_NATURE, ALGO_DOUBLE, ALGO_PER, ALGO_PG = 0, 1, 2, 3, 4
 ALGO_C51, ALGO_C51_DOUBLE = 5, 6
@@ -69,6 +69,7 @@ SIGNATURES = {
     "fb_replay_load_state": [_vp, _vp, _sz],
     "fb_qnet_create": [_i, _i, _i, _i, _vp],
     "fb_qnet_create_c51": [_i, _i, _i, _f, _f, _i, _vp],
+    "fb_qnet_create_c51_dueling": [_i, _i, _i, _f, _f, _i, _vp],
     "fb_qnet_get_support": [_vp] * 4,
     "fb_qnet_forward_dist": [_vp, _i, _vp, _i, _vp, _vp],
     "fb_qnet_destroy": [_vp],

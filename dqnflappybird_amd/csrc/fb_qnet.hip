@@ -1702,8 +1702,12 @@ __global__ __launch_bounds__(256) void c51_loss_kernel(C51LossArgs L) {
 // ---- training, launch 2 of 2: one workgroup per 16 fc1 units (grid FC / 16, the grid of loss_head_kernel): b_fc1's gradient and the
 // tile's maximum |dhf| (gmax: fc1_bwd_big_kernel's pre-scale), then W_fc2's gradient for those units -- thread (c, ug) owns column c
 // of units 8 ug .. 8 ug + 7 and walks the samples in order -- and, in workgroup 0, b_fc2's gradient, the loss and the Adam tick.
+// DUEL (c51d_grad_kernel, a dueling C51 net): the tile's W_eff / b_eff gradients go through LDS and unfold into the net's own head
+// (L.off: W_v b_v W_a b_a), dW_v[:, i] = sum_a dW_eff[:, a N + i], dW_a = dW_eff - (1/A) sum_a' dW_eff[:, a' N + i] -- N + A N <= 192
+// columns per unit, walked by the whole workgroup.
 struct C51GradArgs { int B, FC, A, N; NetOff off; const float *dl, *xs, *lterm, *dhf; const uint8_t *act; float *grad, *loss, *gmax; AdamDev *adam; int tick; };
-__global__ __launch_bounds__(256) void c51_grad_kernel(C51GradArgs L) {
+template <bool DUEL>
+__device__ __forceinline__ void c51_grad_body(const C51GradArgs &L) {
     __shared__ float dlt[MAXTB * 64];
     __shared__ float xt[MAXTB * 16];
     __shared__ int at[MAXTB];
@@ -1737,7 +1741,33 @@ __global__ __launch_bounds__(256) void c51_grad_kernel(C51GradArgs L) {
 #pragma unroll
         for (int u = 0; u < 8; u++) acc[u] = fmaf(xt[b * 16 + ug * 8 + u], w, acc[u]);
     }
-    if (c < AN) {
+    if constexpr (DUEL) {
+        constexpr int ES = 129;                                  // (row stride of the exchange: 16 x 129 + 128 floats in dlt's space)
+        float *ge = dlt, *gbe = dlt + 16 * ES;
+        __syncthreads();                                         // (every thread is through dlt)
+        if (c < AN) {
+#pragma unroll
+            for (int u = 0; u < 8; u++) ge[(ug * 8 + u) * ES + c] = acc[u];
+            if (ug == 0) gbe[c] = gb;
+        }
+        __syncthreads();
+        const int N = L.N, A = L.A, W = N + AN;                  // output columns of a unit: dW_v (N), then dW_a (A N)
+        for (int k = tid; k < 16 * W; k += 256) {
+            const int u = k / W, col = k - u * W, i = col < N ? col : (col - N) % N;
+            const float *e = ge + u * ES;
+            float sm = 0.f;
+            for (int q = 0; q < A; q++) sm += e[q * N + i];
+            if (col < N) L.grad[L.off.wv + (size_t)(j00 + u) * N + col] = sm;
+            else L.grad[L.off.wq + (size_t)(j00 + u) * AN + (col - N)] = e[col - N] - sm / (float)A;
+        }
+        if (blockIdx.x == 0 && tid < W) {
+            const int i = tid < N ? tid : (tid - N) % N;
+            float sm = 0.f;
+            for (int q = 0; q < A; q++) sm += gbe[q * N + i];
+            if (tid < N) L.grad[L.off.bv + tid] = sm;
+            else L.grad[L.off.bq + (tid - N)] = gbe[tid - N] - sm / (float)A;
+        }
+    } else if (c < AN) {
 #pragma unroll
         for (int u = 0; u < 8; u++) L.grad[L.off.wq + (size_t)(j00 + ug * 8 + u) * AN + c] = acc[u];
         if (blockIdx.x == 0 && ug == 0) L.grad[L.off.bq + c] = gb;
@@ -1753,6 +1783,26 @@ __global__ __launch_bounds__(256) void c51_grad_kernel(C51GradArgs L) {
             ad.ticks += 1;
         }
     }
+}
+__global__ __launch_bounds__(256) void c51_grad_kernel(C51GradArgs L) { c51_grad_body<false>(L); }
+__global__ __launch_bounds__(256) void c51d_grad_kernel(C51GradArgs L) { c51_grad_body<true>(L); }
+
+// ---- dueling C51 (FB_ARCH_C51_DUELING): V_i + Adv_{a,i} - (1/A) sum_a' Adv_{a',i} is linear in h, so the head folds into an effective
+// C51 head, W_eff[:, a N + i] = W_v[:, i] + (W_a[:, a N + i] - (1/A) sum_a' W_a[:, a' N + i]) and b_eff likewise, and every C51 kernel
+// above reads it unchanged.  heff = [b_fc1 | W_eff | b_eff]: the C51 layout from b_fc1 on (the net's hoff), refolded whenever the
+// net's parameters change.
+struct C51dFoldArgs { const float *p; float *heff; NetOff off; int FC, A, N; };
+__global__ __launch_bounds__(256) void c51d_fold_kernel(C51dFoldArgs F) {
+    const int AN = F.A * F.N, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= F.FC + (F.FC + 1) * AN) return;
+    if (k < F.FC) { F.heff[k] = F.p[F.off.bf1 + k]; return; }
+    const int kk = k - F.FC, row = kk / AN, c = kk - row * AN, a = c / F.N, i = c - a * F.N;
+    const bool bias = row == F.FC;                               // (the last row: b_eff)
+    const float *wa = F.p + (bias ? F.off.bq : F.off.wq + row * AN) + i;
+    const float v = F.p[bias ? F.off.bv + i : F.off.wv + row * F.N + i];
+    float sm = 0.f;
+    for (int q = 0; q < F.A; q++) sm += wa[q * F.N];
+    F.heff[k] = v + (wa[a * F.N] - sm / (float)F.A);
 }
 
 // ================================================================== fc1 + loss, small batches (training, < 256 states)
@@ -3461,6 +3511,10 @@ struct fb_qnet {
     FbSplitCtx *split;               // fb_qnet_split_ctx
     C51Sup sup;                      // C51 nets: the support (sup.N = 0: a scalar head)
     float *c51_dl, *c51_xs, *c51_lt; // C51 training: logit gradients [max_batch][64], fc1 activations of s [max_batch][FC], loss terms [max_batch]
+    // what the C51 head / loss / eval kernels read: hoff (the C51 layout; = off but for a dueling C51 net) from head_base(params[w]).
+    // A dueling C51 net (FB_ARCH_C51_DUELING): heff[w] = [b_fc1 | W_eff | b_eff], the folded head of params[w] (c51d_fold_kernel)
+    NetOff hoff;
+    float *heff[2];
     bool split_adam_pending;         // a split step exported its gradient: the fb_qnet_apply_adam that completes it takes over the Adam launch's waits
 };
 
@@ -3473,11 +3527,35 @@ static NetOff make_off(int FC, int A, int dueling) {      // A: the head's colum
     return o;
 }
 
+// a dueling C51 net: the trunk, W_fc1 b_fc1, then W_v[FC, N] b_v[N] W_a[FC, A N] b_a[A N] (wq / bq: the advantage head)
+static NetOff make_off_c51d(int FC, int A, int N) {
+    NetOff o;
+    o.bf1 = OFF_WF1 + 1600 * FC;
+    o.wv = o.bf1 + FC; o.bv = o.wv + FC * N;
+    o.wq = o.bv + N; o.bq = o.wq + FC * A * N; o.n = o.bq + A * N;
+    return o;
+}
+static bool is_c51d(const fb_qnet *h) { return h->arch == FB_ARCH_C51_DUELING; }
+// the parameters the C51 kernels read, with h->hoff, for the net whose parameters are `params` (a virtual base for a dueling C51 net:
+// hoff.bf1 lands on heff[w][0], as the acting forward's hp_act copy is read)
+static const float *head_base(const fb_qnet *h, const float *params) {
+    if (!is_c51d(h)) return params;
+    return h->heff[params == h->params[1] ? 1 : 0] - h->off.bf1;
+}
+// refold a dueling C51 net's head after its parameters changed (no-op for other nets)
+static void c51d_fold(fb_qnet *h, int which, hipStream_t st) {
+    if (!is_c51d(h)) return;
+    const C51dFoldArgs F{h->params[which], h->heff[which], h->off, h->FC, h->A, h->sup.N};
+    const int tot = h->FC + (h->FC + 1) * h->A * h->sup.N;
+    hipLaunchKernelGGL(c51d_fold_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, F);
+}
+
 static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out);
 
 extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
     FB_REQUIRE(out, "fb_qnet_create: out is NULL");
     FB_REQUIRE(arch != FB_ARCH_C51, "fb_qnet_create: a C51 net is made by fb_qnet_create_c51 (it needs the support)");
+    FB_REQUIRE(arch != FB_ARCH_C51_DUELING, "fb_qnet_create: a dueling C51 net is made by fb_qnet_create_c51_dueling (it needs the support)");
     FB_REQUIRE(arch == FB_ARCH_PLAIN || arch == FB_ARCH_DUELING, "fb_qnet_create: arch must be 0 or 1");
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create: fc_width must be a multiple of 128");
     FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create: n_actions must be in 1..%d", MAXA);
@@ -3485,25 +3563,36 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
     return qnet_create(arch, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
 }
 
-extern "C" int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
-    FB_REQUIRE(out, "fb_qnet_create_c51: out is NULL");
-    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create_c51: fc_width must be a multiple of 128");
-    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create_c51: n_actions must be in 1..%d", MAXA);
-    FB_REQUIRE(n_atoms >= 2 && n_atoms <= FB_C51_MAX_ATOMS, "fb_qnet_create_c51: n_atoms=%d outside 2..%d", n_atoms, FB_C51_MAX_ATOMS);
-    FB_REQUIRE(n_actions * n_atoms <= 128, "fb_qnet_create_c51: n_actions * n_atoms = %d exceeds 128", n_actions * n_atoms);
-    FB_REQUIRE(isfinite(v_min) && isfinite(v_max) && v_min < v_max, "fb_qnet_create_c51: the support needs finite v_min < v_max (got %g, %g)",
-               (double)v_min, (double)v_max);
-    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "fb_qnet_create_c51: max_batch out of range");
+// the checks of fb_qnet_create_c51 / _c51_dueling, before any allocation (`fn` names the caller in the message)
+static int c51_create(const char *fn, int arch, int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
+    FB_REQUIRE(out, "%s: out is NULL", fn);
+    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
+    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "%s: n_actions must be in 1..%d", fn, MAXA);
+    FB_REQUIRE(n_atoms >= 2 && n_atoms <= FB_C51_MAX_ATOMS, "%s: n_atoms=%d outside 2..%d", fn, n_atoms, FB_C51_MAX_ATOMS);
+    FB_REQUIRE(n_actions * n_atoms <= 128, "%s: n_actions * n_atoms = %d exceeds 128", fn, n_actions * n_atoms);
+    FB_REQUIRE(isfinite(v_min) && isfinite(v_max) && v_min < v_max, "%s: the support needs finite v_min < v_max (got %g, %g)",
+               fn, (double)v_min, (double)v_max);
+    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
     const float dz = (v_max - v_min) / (float)(n_atoms - 1);
-    FB_REQUIRE(isfinite(dz) && dz > 0.f, "fb_qnet_create_c51: the atom spacing (v_max - v_min) / (n_atoms - 1) is not a positive finite float");
-    return qnet_create(FB_ARCH_C51, fc_width, n_actions, C51Sup{n_atoms, v_min, v_max, dz}, max_batch, out);
+    FB_REQUIRE(isfinite(dz) && dz > 0.f, "%s: the atom spacing (v_max - v_min) / (n_atoms - 1) is not a positive finite float", fn);
+    return qnet_create(arch, fc_width, n_actions, C51Sup{n_atoms, v_min, v_max, dz}, max_batch, out);
+}
+
+extern "C" int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
+    return c51_create("fb_qnet_create_c51", FB_ARCH_C51, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out);
+}
+
+extern "C" int fb_qnet_create_c51_dueling(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
+    return c51_create("fb_qnet_create_c51_dueling", FB_ARCH_C51_DUELING, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out);
 }
 
 static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out) {
     fb_qnet *h = new fb_qnet();
     memset(h, 0, sizeof(*h));
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
-    h->off = make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
+    h->off = arch == FB_ARCH_C51_DUELING ? make_off_c51d(fc_width, n_actions, sup.N)
+                                         : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
+    h->hoff = arch == FB_ARCH_C51_DUELING ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
     h->n = h->off.n;
     h->zmax = 64;
     const size_t S = (size_t)3 * max_batch, nb = sizeof(float) * (size_t)h->n;
@@ -3531,6 +3620,7 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     alloc((void **)&h->gmax, (size_t)(fc_width / 16) * 4);
     alloc((void **)&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc((void **)&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
     if (sup.N) { alloc((void **)&h->c51_dl, Bm * 64 * 4); alloc((void **)&h->c51_xs, Bm * fc_width * 4); alloc((void **)&h->c51_lt, Bm * 4); }
+    if (arch == FB_ARCH_C51_DUELING) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
     if (e != hipSuccess) {
         fb_set_error(e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP, "fb_qnet_create: %s", hipGetErrorString(e));
         fb_qnet_destroy(h);
@@ -3549,7 +3639,7 @@ extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     if (!h) return FB_OK;
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
                     h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
-                    h->c51_dl, h->c51_xs, h->c51_lt};
+                    h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1]};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -3667,8 +3757,15 @@ static void resplit_now(fb_qnet *h, int which, hipStream_t st) {
 extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *stream) {
     FB_REQUIRE(h && (which == 0 || which == 1), "fb_qnet_init_params: bad argument");
     hipLaunchKernelGGL(init_params_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, fb_stream(stream),
-                       h->params[which], h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING, (uint32_t)seed,
+                       h->params[which], h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING || is_c51d(h), (uint32_t)seed,
                        (uint32_t)(seed >> 32));
+    if (is_c51d(h)) {                            // (init_params_kernel's dueling bias is one entry: b_v has N)
+        const float b = 0.01f;
+        uint32_t bits;
+        memcpy(&bits, &b, 4);
+        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->off.bv), (int)bits, (size_t)h->sup.N, fb_stream(stream)));
+    }
+    c51d_fold(h, which, fb_stream(stream));
     hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, fb_stream(stream), h->params[which], h->w1s[which], &h->adam->pver[which]);
     resplit_now(h, which, fb_stream(stream));
     FB_LAUNCH_CHECK();
@@ -3679,6 +3776,7 @@ extern "C" int fb_qnet_load_params(fb_qnet_t h, int which, const float *flat, vo
     FB_REQUIRE(h && flat && (which == 0 || which == 1), "fb_qnet_load_params: bad argument");
     FB_CHECK_HIP(hipMemcpyAsync(h->params[which], flat, sizeof(float) * (size_t)h->n, hipMemcpyDeviceToDevice, fb_stream(stream)));
     hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, fb_stream(stream), h->params[which], h->w1s[which], &h->adam->pver[which]);
+    c51d_fold(h, which, fb_stream(stream));
     resplit_now(h, which, fb_stream(stream));
     FB_LAUNCH_CHECK();
     return FB_OK;
@@ -3829,7 +3927,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
                         s0.states, s0.w1s, s0.params + OFF_B1, s0.params, h->wsp[which], h->FC, &h->adam->ovf};
             Fc1Args af{h->a3s + (size_t)row0 * 1600, pl2, h->zeros, h->wsp[which] + WSP_WF1, (fused ? h->hf_act : h->hf) + (size_t)row0 * h->FC, stot, rows, h->FC,
                        fused ? pver : nullptr, fused ? wver : nullptr, nullptr, 0,
-                       fused ? s0.params + h->off.bf1 : nullptr, fused ? h->hp_act : nullptr, fused ? (int)(h->n - h->off.bf1) : 0,
+                       fused ? head_base(h, s0.params) + h->off.bf1 : nullptr, fused ? h->hp_act : nullptr, fused ? (int)(h->hoff.n - h->off.bf1) : 0,
                        fused && p.split && only < 0 ? &p.split->f->trunk_done : nullptr, p.split ? p.split->seq : 0};
             // behind the ring-fed trunk the groups only differ in fc1's weights: when the next group (the target net's slices) follows this
             // one row for row and starts on a tile boundary, ONE fc1 launch takes both (two launches of 128 + 64 workgroups each left
@@ -3889,16 +3987,17 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
     if (c51 && !p.train) FB_K(K_HEAD) {             // C51: the distributional head (stand-alone launch only; no env rider)
         C51HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns; H.params = nullptr;
+        for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (a dueling C51 net: its folded head)
         C51Core &C = H.c;
         C.hf = acting_fused ? h->hf_act : h->hf; C.stot = stot; C.nks = sp ? FC1_SP_KS : 1; C.q = h->q; C.probs = p.probs; C.FC = h->FC; C.A = h->A;
-        C.off = h->off; C.sup = h->sup; C.actions = p.actions; C.epsilon = p.epsilon;
+        C.off = h->hoff; C.sup = h->sup; C.actions = p.actions; C.epsilon = p.epsilon;
         C.seed_lo = (uint32_t)p.seed; C.seed_hi = (uint32_t)(p.seed >> 32);
         C.step_lo = (uint32_t)p.step; C.step_hi = (uint32_t)(p.step >> 32);
         C.key_of = nullptr; C.stream = FB_STREAM_EPS;
         if (p.head_rider) {                          // fb_eval_run: describe the work (fb_qnet_c51_eval_head launches it)
             memset(p.head_rider, 0, sizeof(*p.head_rider));
             p.head_rider->c.hf = C.hf; p.head_rider->c.stot = stot; p.head_rider->c.nks = C.nks;
-            p.head_rider->params = acting_fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;
+            p.head_rider->params = acting_fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params;
         } else if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((total + 3) / 4), dim3(256), 0, st, H);
         else hipLaunchKernelGGL(c51_head_kernel<MAXA>, dim3((total + 3) / 4), dim3(256), 0, st, H);
     }
@@ -3922,8 +4021,9 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             C51LossArgs L;
             const bool pw = is_per_algo(p.algo);     // (prioritized: weighted loss, KL priorities)
             L.algo = is_double_c51(p.algo) ? FB_ALGO_C51_DOUBLE : FB_ALGO_C51;
-            L.B = B; L.FC = FC; L.A = h->A; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->off; L.sup = h->sup;
-            L.p_on = h->params[0]; L.p_next = p.sl.s[1].params; L.p_tgt = p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params;
+            L.B = B; L.FC = FC; L.A = h->A; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->hoff; L.sup = h->sup;
+            L.p_on = head_base(h, h->params[0]); L.p_next = head_base(h, p.sl.s[1].params);
+            L.p_tgt = head_base(h, p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params);
             L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
             L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
             L.isw = pw ? p.isw : nullptr; L.abs_err = pw ? p.abs_err : nullptr;
@@ -3932,7 +4032,8 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             else if (h->A == 2) hipLaunchKernelGGL(c51_loss_kernel<2>, dim3((B + 3) / 4), dim3(256), 0, st, L);
             else hipLaunchKernelGGL(c51_loss_kernel<MAXA>, dim3((B + 3) / 4), dim3(256), 0, st, L);
             const C51GradArgs gA{B, FC, h->A, h->sup.N, h->off, h->c51_dl, h->c51_xs, h->c51_lt, h->dhf, p.a, G, p.loss, h->gmax, h->adam, p.tick};
-            hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);
+            if (is_c51d(h)) hipLaunchKernelGGL(c51d_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);      // (gA.off: W_v b_v W_a b_a)
+            else hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);
         }
         if (!fk && !c51) FB_K(K_LOSS) {
             LossArgs L;
@@ -4080,6 +4181,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             af.split = p.split && only < 0 ? p.split->f : nullptr; af.split_val = p.split ? p.split->seq : 0;
             af.n_rest = (int)((nrest4 * af.lanes + 255) / 256);
             hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest + ngb), dim3(256), 0, st, af, gr);
+            c51d_fold(h, 0, st);
         }
     }
 #undef FB_K
@@ -4155,7 +4257,7 @@ int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32
     H.sl.s[0] = Slice{hd->params, nullptr, 0, n, nullptr, 0}; H.nslices = 1; H.params = hd->params;
     C51Core &C = H.c;
     C.hf = hd->c.hf; C.stot = hd->c.stot; C.nks = hd->c.nks; C.q = hd->c.q; C.probs = nullptr; C.FC = h->FC; C.A = h->A;
-    C.off = h->off; C.sup = h->sup; C.actions = hd->c.actions; C.epsilon = hd->c.epsilon;
+    C.off = h->hoff; C.sup = h->sup; C.actions = hd->c.actions; C.epsilon = hd->c.epsilon;
     C.seed_lo = hd->c.seed_lo; C.seed_hi = hd->c.seed_hi; C.step_lo = hd->c.step_lo; C.step_hi = hd->c.step_hi;
     C.key_of = key_of; C.stream = FB_STREAM_EVAL;
     if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
@@ -4226,6 +4328,7 @@ extern "C" int fb_qnet_apply_adam(fb_qnet_t h, const float *flat_grad, void *str
     af.split = h->split_adam_pending && h->split && h->split->tstream ? h->split->f : nullptr; af.split_val = af.split ? h->split->seq : 0;
     h->split_adam_pending = false;
     hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest), dim3(256), 0, st, af, FbGatherRider{});
+    c51d_fold(h, 0, st);
     FB_LAUNCH_CHECK();
     return FB_OK;
 }
@@ -4252,6 +4355,7 @@ extern "C" int fb_qnet_sync_target(fb_qnet_t h, void *stream) {
     FB_CHECK_HIP(hipMemcpyAsync(h->w1s[1], h->w1s[0], 3 * 8192 * 2, hipMemcpyDeviceToDevice, fb_stream(stream)));
     hipLaunchKernelGGL(bump_pver_kernel, dim3(1), dim3(1), 0, fb_stream(stream), h->adam, 1);
     resplit_now(h, 1, fb_stream(stream));
+    c51d_fold(h, 1, fb_stream(stream));
     FB_LAUNCH_CHECK();
     return FB_OK;
 }

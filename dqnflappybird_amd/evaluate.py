@@ -101,16 +101,20 @@ def evaluate(net, n_envs, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0
 
 
 def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
-    """The online net of a VecBrain.save checkpoint (plain or dueling, told apart by the parameter count; C51 by its recorded support).  max_batch sizes the net's
+    """The online net of a VecBrain.save checkpoint (plain or dueling, told apart by the parameter count; C51 by its recorded support, and
+    C51 or dueling C51 by its recorded head -- 'c51' where none is recorded).  max_batch sizes the net's
     workspace: evaluation runs its acting forward in passes of up to 3 * max_batch rows."""
     from .vec import QNet
     z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz")
     online = np.ascontiguousarray(z["online"], np.float32)
     if "support" in z.files:                                 # a C51 net (VecBrain records its support)
         n_atoms, v_min, v_max = z["support"].tolist()
-        net = QNet(2, fc_width, "c51", max_batch=max_batch, n_atoms=int(n_atoms), v_min=v_min, v_max=v_max)
+        head = str(z["head"][0]) if "head" in z.files else "c51"
+        if head not in ("c51", "c51dueling"):
+            raise ValueError(f"{path}: unknown C51 head {head!r}")
+        net = QNet(2, fc_width, head, max_batch=max_batch, n_atoms=int(n_atoms), v_min=v_min, v_max=v_max)
         if net.n_params != online.size:
-            raise ValueError(f"{path}: {online.size} online parameters do not match a C51 net of width {fc_width} and {int(n_atoms)} atoms")
+            raise ValueError(f"{path}: {online.size} online parameters do not match a {head} net of width {fc_width} and {int(n_atoms)} atoms")
         net.load_params(online, 0)
         net.set_inference_dtype(dtype)
         return net

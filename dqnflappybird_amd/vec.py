@@ -282,6 +282,7 @@ C51_ALGOS = ("c51", "c51double")                            # C51 on a uniform m
 C51_PER_ALGOS = ("c51per", "c51doubleper")                  # C51 on a prioritized memory (weighted loss, KL priorities)
 PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the algos that take a prioritized memory and its importance weights
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
+C51_ARCHS = ("c51", "c51dueling")                         # distributional heads: C51, and the dueling C51 head (Rainbow's)
 
 
 def check_support(n_atoms, v_min, v_max, actions=2):
@@ -312,12 +313,15 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
+    ARCHS = ("plain", "dueling") + C51_ARCHS
+
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
                  v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2]):
-        """arch='c51': the distributional head of include/fbdqn.h (n_atoms atoms on [v_min, v_max]; the support args are ignored otherwise)"""
-        if arch not in ("plain", "dueling", "c51"):
-            raise ValueError(f"arch must be 'plain', 'dueling' or 'c51', got {arch!r}")
-        if arch == "c51":
+        """arch='c51': the distributional head of include/fbdqn.h (n_atoms atoms on [v_min, v_max]; the support args are ignored otherwise);
+        arch='c51dueling': the dueling C51 head (value and advantage distributions, include/fbdqn.h) on the same support"""
+        if arch not in self.ARCHS:
+            raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
+        if arch in C51_ARCHS:
             n_atoms, v_min, v_max = check_support(n_atoms, v_min, v_max, actions)
         L.require_gpu()
         self.A, self.FC, self.max_batch = int(actions), int(fc_width), int(max_batch)
@@ -327,6 +331,9 @@ class QNet:
         self.h = C.c_void_p()
         if arch == "c51":
             L.check(L.lib().fb_qnet_create_c51(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)), "fb_qnet_create_c51")
+        elif arch == "c51dueling":
+            L.check(L.lib().fb_qnet_create_c51_dueling(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)),
+                    "fb_qnet_create_c51_dueling")
         else:
             L.check(L.lib().fb_qnet_create(L.ARCH_DUELING if self.dueling else L.ARCH_PLAIN, self.FC, self.A, self.max_batch,
                                            C.byref(self.h)), "fb_qnet_create")
@@ -439,7 +446,7 @@ class QNet:
         _dev_check(states)
         sup = self.support
         if sup is None:
-            raise ValueError("forward_dist needs a C51 net (arch='c51')")
+            raise ValueError("forward_dist needs a C51 net (arch='c51' or 'c51dueling')")
         B = states.shape[0]
         if states.dtype != torch.uint8 or tuple(states.shape[1:]) != (80, 80, 4):
             raise ValueError("states must be uint8[B,80,80,4]")

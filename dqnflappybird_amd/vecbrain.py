@@ -7,7 +7,8 @@ envs per GPU, entirely device resident: no tensor leaves HBM between getAction a
 Host-side schedule follows the reference: training starts once onlineTimeStep > OBSERVE, epsilon
 decays by (INITIAL - FINAL) / EXPLORE per step after that, Nature/Double sync the target net when
 timeStep % 500 == 0, PER never does (the reference agent's quirk, kept for algo 'per' only); C51 and C51 with prioritized
-replay ('c51per' / 'c51doubleper') sync every replace_target_iter steps.
+replay ('c51per' / 'c51doubleper') sync every replace_target_iter steps.  arch='c51dueling' gives any of the C51 algos the dueling
+C51 head (Rainbow's, with 'c51doubleper' and n-step returns: FlappyBirdDQN.py --model rainbow).
 """
 from . import dist as fdist
 
@@ -16,6 +17,7 @@ C51_ALGOS = ("c51", "c51double")                             # distributional Q-
 C51_PER_ALGOS = ("c51per", "c51doubleper")                   # ... with prioritized replay: weighted loss, KL priorities
 PER_ALGOS = ("per",) + C51_PER_ALGOS                         # algos with a prioritized memory
 TARGET_SYNC = ("nature", "double") + C51_ALGOS + C51_PER_ALGOS   # algos whose target net is synced every replace_target_iter steps
+C51_HEADS = ("c51", "c51dueling")                            # the heads a C51 algo trains (arch; 'plain' means 'c51')
 
 
 class HipVecBackend:
@@ -36,11 +38,13 @@ class HipVecBackend:
         return VecReplay(capacity, n_envs, prioritized=prioritized, n_step=n_step, gamma=gamma)
 
     c51 = True                                               # distributional nets (net(..., support=(n_atoms, v_min, v_max)))
+    c51_dueling = True                                       # ... with the dueling C51 head as well (net(..., arch='c51dueling', support=...))
 
     def net(self, actions, fc_width, arch, max_batch, support=None):
         from .vec import QNet
         if support is not None:
-            return QNet(actions, fc_width, "c51", max_batch=max_batch, n_atoms=support[0], v_min=support[1], v_max=support[2])
+            return QNet(actions, fc_width, arch if arch in C51_HEADS else "c51", max_batch=max_batch, n_atoms=support[0], v_min=support[1],
+                        v_max=support[2])
         return QNet(actions, fc_width, arch, max_batch=max_batch)
 
     def step(self, env, replay, net, batch, algo, gamma, flat_grad, dist=None, mean_loss=False):
@@ -88,6 +92,14 @@ class HipVecBackend:
         return lambda: fdist.allreduce_gradients(flat_grad, mean_loss)
 
 
+def check_checkpoint_head(z, head, path):
+    """a C51 checkpoint's head kind must be this brain's ('c51' or 'c51dueling'; checkpoints that record none hold a C51 head)"""
+    saved = str(z["head"][0]) if "head" in z.files else "c51"
+    if saved != head:
+        raise ValueError(f"checkpoint {path} holds a {saved} head, this VecBrain has a {head} head (C51 and dueling C51 parameters "
+                         "do not convert)")
+
+
 def check_checkpoint_support(z, support, path):
     """a checkpoint's head must be this brain's: C51 with the same support (n_atoms, v_min, v_max), or a scalar head on both sides"""
     saved = tuple(z["support"].tolist()) if "support" in z.files else None
@@ -106,7 +118,8 @@ class VecBrain:
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
-        'c51per' / 'c51doubleper': the same with prioritized replay (importance-weighted loss, KL priorities; n_step at creation)."""
+        'c51per' / 'c51doubleper': the same with prioritized replay (importance-weighted loss, KL priorities; n_step at creation).
+        arch='c51dueling' (C51 algos only): the dueling C51 head -- value and advantage distributions (include/fbdqn.h)."""
         n_step = int(n_step)
         if not 1 <= n_step <= 16:
             raise ValueError(f"n_step must be in 1..16, got {n_step}")
@@ -114,17 +127,23 @@ class VecBrain:
         self.support = None
         if algo in C51_ALGOS + C51_PER_ALGOS:
             from .vec import check_support
-            if arch not in ("plain", "c51"):
-                raise ValueError(f"algo {algo!r} builds a C51 head on the plain trunk: arch {arch!r} (dueling C51) is not supported")
+            if arch not in ("plain",) + C51_HEADS:
+                raise ValueError(f"algo {algo!r} builds a C51 head on the plain trunk: arch {arch!r} is not one "
+                                 f"(dueling C51 is arch='c51dueling')")
             if world > 1:
                 raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (world = {world}; one GPU only)")
             if not getattr(be, "c51", False):
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no C51 nets")
+            if arch == "c51dueling" and not getattr(be, "c51_dueling", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no dueling C51 nets")
             if algo in C51_PER_ALGOS and not getattr(be, "per_one_step", False):
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
                                  f"algo {algo!r} needs it")
             self.support = check_support(n_atoms, v_min, v_max)
-            arch = "c51"
+            arch = "c51dueling" if arch == "c51dueling" else "c51"
+        elif arch == "c51dueling":
+            raise ValueError(f"arch {arch!r} is a C51 head: it trains with a C51 algo ('c51', 'c51double', 'c51per', 'c51doubleper'), "
+                             f"not {algo!r}")
         if n_step > 1 and algo in PER_ALGOS and not getattr(be, "per_n_step", False):
             raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend offers n-step returns on uniform replay only: "
                              f"algo {algo!r} takes n_step = 1 there")
@@ -282,6 +301,7 @@ class VecBrain:
                           epsilon=np.array([self.epsilon], np.float64), n_step=np.array([self.n_step], np.int64))
             if self.support is not None:                     # (scalar-head checkpoints carry no support)
                 shared["support"] = np.array(self.support, np.float64)
+                shared["head"] = np.array([self.arch])       # 'c51' or 'c51dueling' (checkpoints without it: 'c51')
         if self.world == 1:
             np.savez(self._npz(path), **shared, **local)
             return
@@ -302,6 +322,8 @@ class VecBrain:
         if saved_n != self.n_step:
             raise ValueError(f"checkpoint {path} was trained with n_step = {saved_n}, this VecBrain has n_step = {self.n_step}")
         check_checkpoint_support(z, self.support, path)
+        if self.support is not None:
+            check_checkpoint_head(z, self.arch, path)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         self.net.load_params(z["online"], 0)

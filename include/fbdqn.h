@@ -275,6 +275,7 @@ int fb_replay_load_state(fb_replay_t h, const void *blob_host, size_t bytes);
  *   then  W_fc2[FC,A] b[A]            (plain)
  *   or    W_v[FC,1] b_v[1] W_a[FC,A] b_a[A]   (dueling)
  *   or    W_fc2[FC,A*N] b[A*N]        (C51, below)
+ *   or    W_v[FC,N] b_v[N] W_a[FC,A*N] b_a[A*N]   (dueling C51, below)
  */
 typedef struct fb_qnet *fb_qnet_t;
 
@@ -335,6 +336,22 @@ typedef struct fb_qnet *fb_qnet_t;
 #define FB_ALGO_C51_DOUBLE_PER 8
 #define FB_C51_MAX_ATOMS 64
 int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out);
+/* Dueling C51 (the Rainbow paper's dueling distributional head; Rainbow without noisy nets).  A dueling C51 net (FB_ARCH_C51_DUELING,
+ * fb_qnet_create_c51_dueling: the same arguments and support checks as fb_qnet_create_c51, made before any allocation) has the plain
+ * trunk and fc1, then two heads that read the same h = relu(h_fc1):
+ *   value       V_i = h . W_v[:, i] + b_v[i]                                  W_v[FC, N] b_v[N]
+ *   advantage   Adv[a][i] = h . W_a[:, a*N + i] + b_a[a*N + i]                W_a[FC, A*N] b_a[A*N] (column a*N + i: atom i of action a)
+ *   logits      logits[a][i] = V_i + Adv[a][i] - (1/A) sum_a' Adv[a'][i]
+ * Flat order: the trunk, W_fc1 b_fc1, then W_v b_v W_a b_a (FC 512, N 51, A 2: 78 489 head parameters).  fb_qnet_init_params: the same
+ * truncated-normal weights, 0.01 for all N entries of b_v and the other biases.  Softmax, Q, acting / evaluation, the target, the
+ * projection, the loss, the KL priorities and every entry point are exactly the C51 ones above (all four C51 algos; fb_qnet_is_c51,
+ * fb_qnet_get_support and fb_qnet_forward_dist as for a C51 net); refused as for a C51 net: a scalar algo, fb_vec_step_dp, and
+ * fb_qnet_create with arch 2 or 3.
+ * (The head is linear: the library folds it into an effective C51 head, W_eff[:, a*N + i] = W_v[:, i] + W_a[:, a*N + i] - (1/A)
+ * sum_a' W_a[:, a'*N + i], whenever the net's parameters change -- init, load, target sync, every Adam update -- and its gradients
+ * unfold from that head's.  The results agree with the formulas above to float rounding, not bit for bit.) */
+#define FB_ARCH_C51_DUELING 3
+int fb_qnet_create_c51_dueling(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out);
 int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host);      /* n_atoms = 0: not a C51 net */
 int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream);
 
