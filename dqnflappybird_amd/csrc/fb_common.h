@@ -74,6 +74,7 @@ __device__ __forceinline__ void fb_flag_wait(const unsigned long long *flag, uns
 #define FB_STREAM_PER 3u      // PER segment uniforms (FB_RNG_PHILOX)
 #define FB_STREAM_INIT 4u     // truncated-normal weight init
 #define FB_STREAM_EVAL 5u     // epsilon-greedy of fb_eval_run, counter = (env id, eval step): never the training acting stream
+#define FB_STREAM_NOISE 6u    // noisy nets' factorised noise, counter = (element, step_lo, 6, 2 step_hi + net) (fb_qnet_reset_noise)
 
 struct fb_u4 { uint32_t x, y, z, w; };
 

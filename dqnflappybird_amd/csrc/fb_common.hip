@@ -102,6 +102,8 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
                               uint8_t *s2, uint8_t *a, float *r, uint8_t *t, float *loss, double gamma, void *stream) {
     FB_REQUIRE(replay && net && idx && s && s2 && a && r && t && loss && n_steps >= 1, "fb_train_steps: bad argument");
     FB_REQUIRE(!is_per_algo(algo), "fb_train_steps: prioritized replay needs the importance weights: use the separate calls (algo %d)", algo);
+    FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_train_steps: a noisy net needs a noise key per step, which this call has none of: use fb_vec_step or "
+               "fb_qnet_reset_noise + fb_train_from_replay");
     // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
     // here as well so that it comes before any counter moves
     if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
@@ -293,6 +295,14 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
         if (rc2 != FB_OK) return rc2;
     }
     gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: every train step below bootstraps with Gamma = gamma^n)
+    // a noisy net: the online net's noise of this step, drawn before acting (acting and the train step below share it); the target net's
+    // is drawn in front of the train step (target_noise)
+    const bool noisy = fb_qnet_is_noisy(net) != 0;
+    if (noisy) {
+        const int rc0 = fb_qnet_reset_noise(net, 0, seed, step, FB_NOISE_SAMPLE, stream);
+        if (rc0 != FB_OK) return rc0;
+    }
+    auto target_noise = [&]() { return noisy ? fb_qnet_reset_noise(net, 1, seed, step, FB_NOISE_SAMPLE, stream) : FB_OK; };
     // ---- The split schedule (uniform memory, small batches): act(k) and train(k) of the reference's loop BOTH read the weights Adam(k - 1)
     // left -- what orders them is the replay append between them (FlappyBirdDQN.py:72-76, BrainDQN.py:236-240), and that only matters when
     // the minibatch holds one of the n_envs transitions this very step appends (32 draws from a million slots: ~3 % of the steps).  So
@@ -397,6 +407,8 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
         // (fb_replay_sample above wrote the tree indices; its weights come as f64, the loss takes them as the float32 placeholder did)
         if (!sampled) rc = fb_replay_sample_f32(replay, batch, nullptr, b->idx, b->isw, b->isw32, stream);      // (else: joined with the push)
         if (rc != FB_OK) return rc;
+        rc = target_noise();
+        if (rc != FB_OK) return rc;
         if (n_envs >= 256) {
             FbRingSrc ring;
             rc = fb_replay_ring_src(replay, batch, b->idx, b->a, b->r, b->t, &ring);
@@ -416,6 +428,8 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // (conv trunk per state) and leaves a / r / t behind; the split conv planes it needs are current because the acting forward above
     // has just refreshed them.  (b->s / b->s2 stay untouched then.)
     static const bool ring_on = !(getenv("FB_VEC_RING") && atoi(getenv("FB_VEC_RING")) == 0);      // tuning / A-B knob
+    rc = target_noise();
+    if (rc != FB_OK) return rc;
     if (ring_on && n_envs >= 256) {
         FbRingSrc ring;
         rc = fb_replay_ring_src(replay, batch, b->idx, b->a, b->r, b->t, &ring);

@@ -142,6 +142,7 @@ extern "C" int fb_dist_set_overlap(fb_dist_t d, int overlap) {
 
 extern "C" int fb_vec_step_dp(fb_dist_t d, fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int algo,
                               int batch, float epsilon, uint64_t seed, uint64_t step, int train, double gamma, int mean_loss, void *stream) {
+    FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_vec_step_dp: data parallel does not take a noisy net (noisy nets are C51 nets: one GPU only)");
     FB_REQUIRE(!fb_qnet_is_c51(net) && !is_c51_algo(algo),
                "fb_vec_step_dp: data-parallel C51 is not supported (C51 trains through fb_vec_step, fb_train_from_replay, fb_train_steps)");
     FB_REQUIRE(d && b && (!train || b->flat_grad), "fb_vec_step_dp: NULL handle / flat_grad buffer");

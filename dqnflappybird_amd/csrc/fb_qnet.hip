@@ -1805,6 +1805,75 @@ __global__ __launch_bounds__(256) void c51d_fold_kernel(C51dFoldArgs F) {
     F.heff[k] = v + (wa[a * F.N] - sm / (float)F.A);
 }
 
+// ---- noisy C51 nets (include/fbdqn.h): fc1 and every head layer are factorised Gaussian layers.  The master vector of a net is
+// [mu | sigma]: mu in the net's own layout (n floats), then sigma of every parameter from W_fc1 on (sigma of q at n + q - OFF_WF1).  What
+// every other kernel reads is the effective vector of the same layout as mu, materialised after each change of mu, sigma or the noise:
+// the trunk copied, q >= OFF_WF1 as mu + sigma * e(q), e(q) = f(eps_out_j) f(eps_in_i) for a weight, f(eps_out_j) for a bias.
+// Layer l: W[fin][fout] at w, then b[fout]; the layers are consecutive from OFF_WF1 on (fc1, then the head's one or two).  The noise
+// vector of a net: per layer f(eps_in)[fin] at ein, then f(eps_out)[fout] at eout.
+struct NoisyLayer { int w, fin, fout, ein, eout; float sig; };      // sig: the initial sigma, sigma0 / sqrt(fin)
+struct NoisyNet { NoisyLayer l[3]; int nl, n, nz; };
+__device__ __forceinline__ NoisyLayer noisy_layer(const NoisyNet &N, int q) {      // (selects, no dynamic index: no scratch)
+    NoisyLayer L = N.l[0];
+    if (N.nl > 1 && q >= N.l[1].w) L = N.l[1];
+    if (N.nl > 2 && q >= N.l[2].w) L = N.l[2];
+    return L;
+}
+__device__ __forceinline__ float noisy_factor(const NoisyNet &N, const float *__restrict__ nz, int q) {
+    const NoisyLayer L = noisy_layer(N, q);
+    const int r = q - L.w, i = r / L.fout, j = r - i * L.fout;
+    const float fo = nz[L.eout + j];
+    return i < L.fin ? fo * nz[L.ein + i] : fo;                  // (row fin: the bias)
+}
+
+// one draw of a net's noise vector: element k of net `which` at (seed, step) is z = Box-Muller of Philox(key = seed, counter = (k,
+// step_lo, FB_STREAM_NOISE, 2 step_hi + which)), the formula of init_params_kernel without its truncation, stored as f(z) =
+// sign(z) sqrt|z|.  mean: zeros (the effective weights are mu exactly)
+__global__ __launch_bounds__(256) void noise_draw_kernel(float *__restrict__ nz, int len, uint32_t seed_lo, uint32_t seed_hi, uint32_t step_lo,
+                                                         uint32_t c3, int mean) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= len) return;
+    float f = 0.f;
+    if (!mean) {
+        const fb_u4 r = fb_philox(seed_lo, seed_hi, (uint32_t)k, step_lo, FB_STREAM_NOISE, c3);
+        const float u1 = ((r.x >> 8) + 1) * (1.0f / 16777216.0f), u2 = (r.y >> 8) * (1.0f / 16777216.0f);
+        const float z = sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+        f = copysignf(sqrtf(fabsf(z)), z);
+    }
+    nz[k] = f;
+}
+
+// the effective parameters of a net from q0 on (0: the trunk changed as well).  ad (or NULL): a new parameter version for the W_fc1
+// planes the forward re-splits, the conv planes staying current if they were
+struct NoisyMat { const float *mst; float *eff; const float *nz; NoisyNet N; int q0, which; AdamDev *ad; };
+__global__ __launch_bounds__(256) void noisy_mat_kernel(NoisyMat a) {
+    if (a.ad && blockIdx.x == 0 && threadIdx.x == 0) {
+        const unsigned v = a.ad->pver[a.which];
+        if (a.ad->wverc[a.which] == v) a.ad->wverc[a.which] = v + 1;
+        a.ad->pver[a.which] = v + 1;
+    }
+    const int q = a.q0 + blockIdx.x * 256 + threadIdx.x;
+    if (q >= a.N.n) return;
+    const float mu = a.mst[q];
+    if (q < OFF_WF1) { a.eff[q] = mu; return; }
+    const float s = a.mst[a.N.n + q - OFF_WF1], e = noisy_factor(a.N, a.nz, q);
+    a.eff[q] = s == 0.f || e == 0.f ? mu : fmaf(s, e, mu);           // (exactly mu without noise)
+}
+
+// sigma's gradient, behind every gradient of the effective parameters: g[n + q - OFF_WF1] = g[q] e(q)
+__global__ __launch_bounds__(256) void noisy_sgrad_kernel(float *__restrict__ g, const float *__restrict__ nz, NoisyNet N) {
+    const int q = OFF_WF1 + blockIdx.x * 256 + threadIdx.x;
+    if (q >= N.n) return;
+    g[N.n + q - OFF_WF1] = g[q] * noisy_factor(N, nz, q);
+}
+
+// sigma's initial values, sigma0 / sqrt(fan_in) per layer (weights and biases)
+__global__ __launch_bounds__(256) void noisy_sigma_init_kernel(float *__restrict__ p, NoisyNet N) {
+    const int q = OFF_WF1 + blockIdx.x * 256 + threadIdx.x;
+    if (q >= N.n) return;
+    p[N.n + q - OFF_WF1] = noisy_layer(N, q).sig;
+}
+
 // ================================================================== fc1 + loss, small batches (training, < 256 states)
 // fc1 with the WHOLE reduction in one workgroup.  Round 1's fc1_kernel split K = 1600 over 5 workgroups, which leaves five partial
 // sums per unit that only a further launch can add up -- so Q (and with it the loss and every gradient) sat two launches
@@ -3515,6 +3584,13 @@ struct fb_qnet {
     // A dueling C51 net (FB_ARCH_C51_DUELING): heff[w] = [b_fc1 | W_eff | b_eff], the folded head of params[w] (c51d_fold_kernel)
     NetOff hoff;
     float *heff[2];
+    // a noisy C51 net (fb_qnet_create_c51_noisy): mst[w] = [mu | sigma] (ntot floats: what Adam updates, load / store / sync move);
+    // params[w] is then the EFFECTIVE vector (n floats, mu + sigma * noise, noisy_mat_kernel) every forward / backward kernel reads.
+    // nz[w]: the net's current f(eps) sample (nnet.nz floats; zeros = mean mode).  Other nets: ntot = n, mst / nz NULL
+    bool noisy;
+    long long ntot;
+    NoisyNet nnet;
+    float *mst[2], *nz[2];
     bool split_adam_pending;         // a split step exported its gradient: the fb_qnet_apply_adam that completes it takes over the Adam launch's waits
 };
 
@@ -3550,7 +3626,22 @@ static void c51d_fold(fb_qnet *h, int which, hipStream_t st) {
     hipLaunchKernelGGL(c51d_fold_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, F);
 }
 
-static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out);
+// the vector Adam updates and load / store / sync move: [mu | sigma] of a noisy net, the parameters themselves otherwise
+static float *master(const fb_qnet *h, int which) { return h->noisy ? h->mst[which] : h->params[which]; }
+// a noisy net: rebuild params[which] from its master vector and noise, from q0 on (0 after a change of mu's trunk); bump: a new parameter
+// version (noise only: the conv planes stay current).  No-op for other nets
+static void noisy_materialise(fb_qnet *h, int which, int q0, bool bump, hipStream_t st) {
+    if (!h->noisy) return;
+    const NoisyMat a{h->mst[which], h->params[which], h->nz[which], h->nnet, q0, which, bump ? h->adam : nullptr};
+    hipLaunchKernelGGL(noisy_mat_kernel, dim3((unsigned)((h->n - q0 + 255) / 256)), dim3(256), 0, st, a);
+}
+// a noisy net: sigma's gradient into g[n ..) from the effective parameters' gradient in g[OFF_WF1, n)
+static void noisy_sgrad(fb_qnet *h, float *g, hipStream_t st) {
+    if (!h->noisy) return;
+    hipLaunchKernelGGL(noisy_sgrad_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, st, g, (const float *)h->nz[0], h->nnet);
+}
+
+static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out, float sigma0 = -1.f);
 
 extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
     FB_REQUIRE(out, "fb_qnet_create: out is NULL");
@@ -3564,7 +3655,8 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
 }
 
 // the checks of fb_qnet_create_c51 / _c51_dueling, before any allocation (`fn` names the caller in the message)
-static int c51_create(const char *fn, int arch, int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
+static int c51_create(const char *fn, int arch, int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out,
+                      float sigma0 = -1.f) {
     FB_REQUIRE(out, "%s: out is NULL", fn);
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
     FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "%s: n_actions must be in 1..%d", fn, MAXA);
@@ -3575,7 +3667,7 @@ static int c51_create(const char *fn, int arch, int fc_width, int n_actions, int
     FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
     const float dz = (v_max - v_min) / (float)(n_atoms - 1);
     FB_REQUIRE(isfinite(dz) && dz > 0.f, "%s: the atom spacing (v_max - v_min) / (n_atoms - 1) is not a positive finite float", fn);
-    return qnet_create(arch, fc_width, n_actions, C51Sup{n_atoms, v_min, v_max, dz}, max_batch, out);
+    return qnet_create(arch, fc_width, n_actions, C51Sup{n_atoms, v_min, v_max, dz}, max_batch, out, sigma0);
 }
 
 extern "C" int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
@@ -3586,7 +3678,32 @@ extern "C" int fb_qnet_create_c51_dueling(int fc_width, int n_actions, int n_ato
     return c51_create("fb_qnet_create_c51_dueling", FB_ARCH_C51_DUELING, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out);
 }
 
-static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out) {
+extern "C" int fb_qnet_create_c51_noisy(int arch, int fc_width, int n_actions, int n_atoms, float v_min, float v_max, float sigma0, int max_batch,
+                                        fb_qnet_t *out) {
+    FB_REQUIRE(out, "fb_qnet_create_c51_noisy: out is NULL");
+    FB_REQUIRE(arch == FB_ARCH_C51 || arch == FB_ARCH_C51_DUELING, "fb_qnet_create_c51_noisy: arch must be FB_ARCH_C51 (2) or FB_ARCH_C51_DUELING (3), "
+               "got %d (noisy layers are offered on the C51 heads only)", arch);
+    FB_REQUIRE(isfinite(sigma0) && sigma0 >= 0.f, "fb_qnet_create_c51_noisy: sigma0 must be finite and >= 0 (got %g)", (double)sigma0);
+    return c51_create("fb_qnet_create_c51_noisy", arch, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out, sigma0);
+}
+
+// the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
+static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, float sigma0) {
+    NoisyNet nn;
+    memset(&nn, 0, sizeof(nn));
+    auto add = [&](int w, int fin, int fout) {
+        NoisyLayer &L = nn.l[nn.nl++];
+        L.w = w; L.fin = fin; L.fout = fout; L.ein = nn.nz; L.eout = nn.nz + fin; nn.nz += fin + fout;
+        L.sig = (float)((double)sigma0 / sqrt((double)fin));
+    };
+    add(OFF_WF1, 1600, FC);
+    if (arch == FB_ARCH_C51_DUELING) add(o.wv, FC, N);
+    add(o.wq, FC, A * N);
+    nn.n = o.n;
+    return nn;
+}
+
+static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out, float sigma0) {
     fb_qnet *h = new fb_qnet();
     memset(h, 0, sizeof(*h));
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
@@ -3594,12 +3711,16 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
                                          : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
     h->hoff = arch == FB_ARCH_C51_DUELING ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
     h->n = h->off.n;
+    h->noisy = sigma0 >= 0.f;                    // (fb_qnet_create_c51_noisy: C51 archs, finite sigma0 >= 0)
+    h->ntot = h->noisy ? 2 * h->n - OFF_WF1 : h->n;
+    if (h->noisy) h->nnet = make_noisy(h->off, arch, fc_width, n_actions, sup.N, sigma0);
     h->zmax = 64;
-    const size_t S = (size_t)3 * max_batch, nb = sizeof(float) * (size_t)h->n;
+    const size_t S = (size_t)3 * max_batch, nb = sizeof(float) * (size_t)h->n, nbt = sizeof(float) * (size_t)h->ntot;
     hipError_t e = hipSuccess;
     auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); };
     alloc((void **)&h->params[0], nb); alloc((void **)&h->params[1], nb);
-    alloc((void **)&h->adam_m, nb); alloc((void **)&h->adam_v, nb); alloc((void **)&h->grad, nb);
+    alloc((void **)&h->adam_m, nbt); alloc((void **)&h->adam_v, nbt); alloc((void **)&h->grad, nbt);
+    if (h->noisy) for (int w = 0; w < 2; w++) { alloc((void **)&h->mst[w], nbt); alloc((void **)&h->nz[w], sizeof(float) * (size_t)h->nnet.nz); }      // (zero noise: mean mode)
     alloc((void **)&h->slabs, sizeof(float) * (size_t)h->zmax * CONV_PARAMS);
     if (2 * max_batch > h->zmax) alloc((void **)&h->slabs1, sizeof(float) * (size_t)2 * (max_batch < MAXTB ? max_batch : MAXTB) * CONV1_PARAMS);      // two sub-slabs per sample
     alloc((void **)&h->adam, sizeof(AdamDev));
@@ -3639,7 +3760,7 @@ extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     if (!h) return FB_OK;
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
                     h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
-                    h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1]};
+                    h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1]};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -3706,7 +3827,7 @@ extern "C" int fb_qnet_split_stats(fb_qnet_t h, int64_t *steps_host, int64_t *cl
 
 extern "C" int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host) {
     FB_REQUIRE(h && n_host, "fb_qnet_num_params: NULL argument");
-    *n_host = h->n;
+    *n_host = h->ntot;
     return FB_OK;
 }
 
@@ -3757,14 +3878,17 @@ static void resplit_now(fb_qnet *h, int which, hipStream_t st) {
 extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *stream) {
     FB_REQUIRE(h && (which == 0 || which == 1), "fb_qnet_init_params: bad argument");
     hipLaunchKernelGGL(init_params_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, fb_stream(stream),
-                       h->params[which], h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING || is_c51d(h), (uint32_t)seed,
+                       master(h, which), h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING || is_c51d(h), (uint32_t)seed,
                        (uint32_t)(seed >> 32));
     if (is_c51d(h)) {                            // (init_params_kernel's dueling bias is one entry: b_v has N)
         const float b = 0.01f;
         uint32_t bits;
         memcpy(&bits, &b, 4);
-        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->off.bv), (int)bits, (size_t)h->sup.N, fb_stream(stream)));
+        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(master(h, which) + h->off.bv), (int)bits, (size_t)h->sup.N, fb_stream(stream)));
     }
+    if (h->noisy)                                // (mu as the plain net's, then sigma0 / sqrt(fan_in))
+        hipLaunchKernelGGL(noisy_sigma_init_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, fb_stream(stream), h->mst[which], h->nnet);
+    noisy_materialise(h, which, 0, false, fb_stream(stream));
     c51d_fold(h, which, fb_stream(stream));
     hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, fb_stream(stream), h->params[which], h->w1s[which], &h->adam->pver[which]);
     resplit_now(h, which, fb_stream(stream));
@@ -3774,7 +3898,8 @@ extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *
 
 extern "C" int fb_qnet_load_params(fb_qnet_t h, int which, const float *flat, void *stream) {
     FB_REQUIRE(h && flat && (which == 0 || which == 1), "fb_qnet_load_params: bad argument");
-    FB_CHECK_HIP(hipMemcpyAsync(h->params[which], flat, sizeof(float) * (size_t)h->n, hipMemcpyDeviceToDevice, fb_stream(stream)));
+    FB_CHECK_HIP(hipMemcpyAsync(master(h, which), flat, sizeof(float) * (size_t)h->ntot, hipMemcpyDeviceToDevice, fb_stream(stream)));
+    noisy_materialise(h, which, 0, false, fb_stream(stream));
     hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, fb_stream(stream), h->params[which], h->w1s[which], &h->adam->pver[which]);
     c51d_fold(h, which, fb_stream(stream));
     resplit_now(h, which, fb_stream(stream));
@@ -3784,14 +3909,14 @@ extern "C" int fb_qnet_load_params(fb_qnet_t h, int which, const float *flat, vo
 
 extern "C" int fb_qnet_store_params(fb_qnet_t h, int which, float *flat, void *stream) {
     FB_REQUIRE(h && flat && (which == 0 || which == 1), "fb_qnet_store_params: bad argument");
-    FB_CHECK_HIP(hipMemcpyAsync(flat, h->params[which], sizeof(float) * (size_t)h->n, hipMemcpyDeviceToDevice, fb_stream(stream)));
+    FB_CHECK_HIP(hipMemcpyAsync(flat, master(h, which), sizeof(float) * (size_t)h->ntot, hipMemcpyDeviceToDevice, fb_stream(stream)));
     return FB_OK;
 }
 
 extern "C" int fb_qnet_get_adam_state(fb_qnet_t h, float *m, float *v, float *beta_pows_host) {
     FB_REQUIRE(h, "fb_qnet_get_adam_state: NULL handle");
     FB_CHECK_HIP(hipDeviceSynchronize());
-    const size_t nb = sizeof(float) * (size_t)h->n;
+    const size_t nb = sizeof(float) * (size_t)h->ntot;
     if (m) FB_CHECK_HIP(hipMemcpy(m, h->adam_m, nb, hipMemcpyDeviceToDevice));
     if (v) FB_CHECK_HIP(hipMemcpy(v, h->adam_v, nb, hipMemcpyDeviceToDevice));
     if (beta_pows_host) {
@@ -3805,7 +3930,7 @@ extern "C" int fb_qnet_get_adam_state(fb_qnet_t h, float *m, float *v, float *be
 extern "C" int fb_qnet_set_adam_state(fb_qnet_t h, const float *m, const float *v, const float *beta_pows_host) {
     FB_REQUIRE(h, "fb_qnet_set_adam_state: NULL handle");
     FB_CHECK_HIP(hipDeviceSynchronize());
-    const size_t nb = sizeof(float) * (size_t)h->n;
+    const size_t nb = sizeof(float) * (size_t)h->ntot;
     if (m) FB_CHECK_HIP(hipMemcpy(h->adam_m, m, nb, hipMemcpyDeviceToDevice));
     if (v) FB_CHECK_HIP(hipMemcpy(h->adam_v, v, nb, hipMemcpyDeviceToDevice));
     if (beta_pows_host) {
@@ -4089,8 +4214,8 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         // is the latency-bound chains beside it, wherever it rides -- so the default stays "all of it beside the data-gradient chain")
         static const int span_pct = getenv("FB_SPAN_SPLIT") ? atoi(getenv("FB_SPAN_SPLIT")) : 100;     // tuning knob: per cent of the span in the first launch
         const int spanm = span0 + (int)(((long long)(span1 - span0) * span_pct / 100) & ~511LL);
-        const AdamSpan span{h->params[0], h->adam_m, h->adam_v, G, h->adam, span0, spanm};
-        const AdamSpan span_b{h->params[0], h->adam_m, h->adam_v, G, h->adam, spanm, span1};
+        const AdamSpan span{master(h, 0), h->adam_m, h->adam_v, G, h->adam, span0, spanm};
+        const AdamSpan span_b{master(h, 0), h->adam_m, h->adam_v, G, h->adam, spanm, span1};
         // split schedule: the fc1 backward launch has waited for the acting trunk on the other stream (its gate workgroup), so W_fc1's Adam
         // span may ride in the launches below; the last of them waits for that stream's fc1 launch, so the Adam launch may follow
         FbGate gate_fc1{nullptr, 0, nullptr};
@@ -4125,7 +4250,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
                     float *s1 = fold1 ? h->slabs1 : h->slabs;
                     const size_t st1 = fold1 ? (size_t)CONV1_PARAMS : ss;
                     const dim3 g(BW_WGS * B + n_adam5 + n_adam5b + (srider.k ? 1 : 0) + (gate_fc1.flag ? 1 : 0));
-                    const AdamSpan span_all{h->params[0], h->adam_m, h->adam_v, G, h->adam, span0, span1};
+                    const AdamSpan span_all{master(h, 0), h->adam_m, h->adam_v, G, h->adam, span0, span1};
                     const int n_ad = n_adam5 + n_adam5b;
                     if (h->nsplit_train == 3) {
                         if (p.ring) hipLaunchKernelGGL((conv_bw_kernel<3, true>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_ad, span_all, srider, rbt, gate_fc1);
@@ -4164,6 +4289,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         const int z2 = z3;
         if (p.split && only < 0) h->split_adam_pending = !p.apply_adam;
         if (!p.apply_adam) FB_K(K_SLAB) hipLaunchKernelGGL(slab_reduce_kernel, dim3((CONV_PARAMS / 4 + 255) / 256), dim3(256), 0, st, h->slabs, ss, z1, z2, z3, G);
+        if (only < 0) noisy_sgrad(h, G, st);         // (a noisy net: sigma's gradient, from the gradient of the effective W_fc1 b_fc1 and head)
         // split schedule: the Adam launch rewrites the conv planes / biases the acting trunk reads and the parameters its fc1 launch copies for the head
 
         if (p.apply_adam) FB_K(K_ADAM)
@@ -4173,14 +4299,15 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             if (p.gather_rider) gr = *p.gather_rider;
             const int ngb = (int)(((long long)gr.B * 1600 + 255) / 256);
             AdamFused af;
-            af.p = h->params[0]; af.m = h->adam_m; af.v = h->adam_v; af.g = G; af.n = h->n; af.ad = h->adam;
+            af.p = master(h, 0); af.m = h->adam_m; af.v = h->adam_v; af.g = G; af.n = h->ntot; af.ad = h->adam;
             af.slabs = h->slabs; af.slab_stride = ss; af.z1 = z1; af.z2 = z2; af.z3 = z3;
             af.w1s = h->w1s[0]; af.wsp = h->wsp[0]; af.FC = FC; af.tail0 = span1;
-            const long long nrest4 = OFF_W2 / 4 + (OFF_W3 - OFF_B2) / 4 + (OFF_WF1 - OFF_B3) / 4 + (h->n / 4 - span1);
+            const long long nrest4 = OFF_W2 / 4 + (OFF_W3 - OFF_B2) / 4 + (OFF_WF1 - OFF_B3) / 4 + (h->ntot / 4 - span1);
             af.lanes = 4;                                    // slab mode: one chunk of <= 16 slabs per lane
             af.split = p.split && only < 0 ? p.split->f : nullptr; af.split_val = p.split ? p.split->seq : 0;
             af.n_rest = (int)((nrest4 * af.lanes + 255) / 256);
             hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest + ngb), dim3(256), 0, st, af, gr);
+            noisy_materialise(h, 0, 0, false, st);
             c51d_fold(h, 0, st);
         }
     }
@@ -4232,6 +4359,28 @@ extern "C" int fb_qnet_act_nib(fb_qnet_t h, const uint8_t *nib_states, int n, fl
 
 int fb_qnet_num_actions(fb_qnet_t h) { return h ? h->A : 0; }
 int fb_qnet_is_c51(fb_qnet_t h) { return h && h->sup.N > 0; }
+extern "C" int fb_qnet_is_noisy(fb_qnet_t h) { return h && h->noisy ? 1 : 0; }
+
+extern "C" int fb_qnet_reset_noise(fb_qnet_t h, int which, uint64_t seed, uint64_t step, int mode, void *stream) {
+    FB_REQUIRE(h && (which == 0 || which == 1), "fb_qnet_reset_noise: bad argument");
+    FB_REQUIRE(h->noisy, "fb_qnet_reset_noise: not a noisy net (fb_qnet_create_c51_noisy)");
+    FB_REQUIRE(mode == FB_NOISE_SAMPLE || mode == FB_NOISE_MEAN, "fb_qnet_reset_noise: mode must be FB_NOISE_SAMPLE or FB_NOISE_MEAN (got %d)", mode);
+    hipStream_t st = fb_stream(stream);
+    hipLaunchKernelGGL(noise_draw_kernel, dim3((h->nnet.nz + 255) / 256), dim3(256), 0, st, h->nz[which], h->nnet.nz, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       (uint32_t)step, (uint32_t)(step >> 32) * 2u + (uint32_t)which, mode == FB_NOISE_MEAN ? 1 : 0);
+    noisy_materialise(h, which, OFF_WF1, true, st);      // (the trunk is mu: unchanged)
+    c51d_fold(h, which, st);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_noise(fb_qnet_t h, int which, float *out) {
+    FB_REQUIRE(h && out && (which == 0 || which == 1), "fb_qnet_get_noise: bad argument");
+    FB_REQUIRE(h->noisy, "fb_qnet_get_noise: not a noisy net (fb_qnet_create_c51_noisy)");
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    FB_CHECK_HIP(hipMemcpy(out, h->nz[which], sizeof(float) * (size_t)h->nnet.nz, hipMemcpyDefault));
+    return FB_OK;
+}
 
 extern "C" int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host) {
     FB_REQUIRE(h && n_atoms_host && v_min_host && v_max_host, "fb_qnet_get_support: NULL argument");
@@ -4320,7 +4469,7 @@ extern "C" int fb_qnet_apply_adam(fb_qnet_t h, const float *flat_grad, void *str
     if (!h->adam_ticked || cap != hipStreamCaptureStatusNone) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, st, h->adam);
     h->adam_ticked = false;
     AdamFused af;
-    af.p = h->params[0]; af.m = h->adam_m; af.v = h->adam_v; af.g = flat_grad; af.n = h->n; af.ad = h->adam;
+    af.p = master(h, 0); af.m = h->adam_m; af.v = h->adam_v; af.g = flat_grad; af.n = h->ntot; af.ad = h->adam;
     af.slabs = nullptr; af.slab_stride = 0; af.z1 = af.z2 = af.z3 = 0;
     af.w1s = h->w1s[0]; af.wsp = h->wsp[0]; af.FC = h->FC; af.tail0 = OFF_WF1 / 4;
     af.n_rest = ADAM_GRID; af.lanes = 1;
@@ -4328,6 +4477,7 @@ extern "C" int fb_qnet_apply_adam(fb_qnet_t h, const float *flat_grad, void *str
     af.split = h->split_adam_pending && h->split && h->split->tstream ? h->split->f : nullptr; af.split_val = af.split ? h->split->seq : 0;
     h->split_adam_pending = false;
     hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest), dim3(256), 0, st, af, FbGatherRider{});
+    noisy_materialise(h, 0, 0, false, st);
     c51d_fold(h, 0, st);
     FB_LAUNCH_CHECK();
     return FB_OK;
@@ -4351,9 +4501,10 @@ extern "C" int64_t fb_qnet_grad_split(fb_qnet_t h) { return h ? (int64_t)CONV_PA
 
 extern "C" int fb_qnet_sync_target(fb_qnet_t h, void *stream) {
     FB_REQUIRE(h, "fb_qnet_sync_target: NULL handle");
-    FB_CHECK_HIP(hipMemcpyAsync(h->params[1], h->params[0], sizeof(float) * (size_t)h->n, hipMemcpyDeviceToDevice, fb_stream(stream)));
+    FB_CHECK_HIP(hipMemcpyAsync(master(h, 1), master(h, 0), sizeof(float) * (size_t)h->ntot, hipMemcpyDeviceToDevice, fb_stream(stream)));
     FB_CHECK_HIP(hipMemcpyAsync(h->w1s[1], h->w1s[0], 3 * 8192 * 2, hipMemcpyDeviceToDevice, fb_stream(stream)));
     hipLaunchKernelGGL(bump_pver_kernel, dim3(1), dim3(1), 0, fb_stream(stream), h->adam, 1);
+    noisy_materialise(h, 1, 0, false, fb_stream(stream));      // (with the target net's own noise)
     resplit_now(h, 1, fb_stream(stream));
     c51d_fold(h, 1, fb_stream(stream));
     FB_LAUNCH_CHECK();

@@ -92,17 +92,29 @@ class Evaluator:
         return EvalResult(score.cpu().numpy(), length.cpu().numpy(), trunc.cpu().numpy(), steps.value, wall, rows.value, comp.value)
 
 
-def evaluate(net, n_envs, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0):
+NOISE_MODES = ("mean", "sample")
+
+
+def evaluate(net, n_envs, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0, noise="mean"):
     """Play `episodes` episodes in each of n_envs fresh games (env e = env e of VecGameState(n_envs, env_seed)) with the online
-    parameters of `net` (vec.QNet, in its current inference dtype), at most max_steps vector steps.  -> EvalResult."""
+    parameters of `net` (vec.QNet, in its current inference dtype), at most max_steps vector steps.  A noisy net plays with its mean
+    weights (noise='mean': mu), or noise='sample' with one sample of its online noise keyed by (act_seed, step 0); either leaves
+    the net's online sample set that way.  -> EvalResult."""
     if not 1 <= int(n_envs) <= L.EVAL_MAX_ENVS:               # (the library checks it too; this keeps the handle's size sane)
         raise ValueError(f"evaluate: n_envs={n_envs} outside 1..{L.EVAL_MAX_ENVS}")
+    if noise not in NOISE_MODES:
+        raise ValueError(f"evaluate: noise must be one of {NOISE_MODES}, got {noise!r}")
+    if getattr(net, "noisy", False):
+        net.reset_noise(L.NET_ONLINE, int(act_seed), 0, mean=noise == "mean")
+    elif noise != "mean":
+        raise ValueError("evaluate: noise='sample' needs a noisy net")
     return Evaluator(n_envs).run(net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed)
 
 
 def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
     """The online net of a VecBrain.save checkpoint (plain or dueling, told apart by the parameter count; C51 by its recorded support, and
-    C51 or dueling C51 by its recorded head -- 'c51' where none is recorded).  max_batch sizes the net's
+    C51 or dueling C51 by its recorded head -- 'c51' where none is recorded; a noisy net by its recorded `noisy` / `sigma0`, in mean
+    mode).  max_batch sizes the net's
     workspace: evaluation runs its acting forward in passes of up to 3 * max_batch rows."""
     from .vec import QNet
     z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz")
@@ -112,9 +124,12 @@ def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
         head = str(z["head"][0]) if "head" in z.files else "c51"
         if head not in ("c51", "c51dueling"):
             raise ValueError(f"{path}: unknown C51 head {head!r}")
-        net = QNet(2, fc_width, head, max_batch=max_batch, n_atoms=int(n_atoms), v_min=v_min, v_max=v_max)
+        noisy = "noisy" in z.files and bool(z["noisy"][0])
+        kw = dict(noisy=True, sigma0=float(z["sigma0"][0])) if noisy else {}
+        net = QNet(2, fc_width, head, max_batch=max_batch, n_atoms=int(n_atoms), v_min=v_min, v_max=v_max, **kw)
         if net.n_params != online.size:
-            raise ValueError(f"{path}: {online.size} online parameters do not match a {head} net of width {fc_width} and {int(n_atoms)} atoms")
+            raise ValueError(f"{path}: {online.size} online parameters do not match a {'noisy ' if noisy else ''}{head} net of width "
+                             f"{fc_width} and {int(n_atoms)} atoms")
         net.load_params(online, 0)
         net.set_inference_dtype(dtype)
         return net
@@ -138,9 +153,10 @@ def main(argv=None):
     ap.add_argument("--fc-width", type=int, default=512)
     ap.add_argument("--env-seed", type=int, default=0)
     ap.add_argument("--act-seed", type=int, default=0)
+    ap.add_argument("--noise", choices=NOISE_MODES, default="mean", help="noisy nets: play with the mean weights, or one noise sample keyed by --act-seed")
     a = ap.parse_args(argv)
     net = qnet_from_checkpoint(a.checkpoint, a.fc_width, a.dtype)
-    res = evaluate(net, a.envs, a.episodes, a.max_steps, a.epsilon, a.env_seed, a.act_seed)
+    res = evaluate(net, a.envs, a.episodes, a.max_steps, a.epsilon, a.env_seed, a.act_seed, noise=a.noise)
     print(res.summary(), flush=True)
     return res
 

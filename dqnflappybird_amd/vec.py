@@ -283,6 +283,21 @@ C51_PER_ALGOS = ("c51per", "c51doubleper")                  # C51 on a prioritiz
 PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the algos that take a prioritized memory and its importance weights
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
 C51_ARCHS = ("c51", "c51dueling")                         # distributional heads: C51, and the dueling C51 head (Rainbow's)
+NOISY_DEFAULT_SIGMA0 = 0.5                                # noisy nets: sigma = sigma0 / sqrt(fan_in) at init (Fortunato et al.)
+
+
+def check_sigma0(sigma0):
+    """the sigma0 check of fb_qnet_create_c51_noisy, on the host (-> float32-rounded float)"""
+    s = float(np.float32(sigma0))
+    if not (np.isfinite(s) and s >= 0.0):
+        raise ValueError(f"sigma0 must be finite and >= 0, got {sigma0}")
+    return s
+
+
+def noise_size(fc_width, actions, n_atoms, arch):
+    """the length of a noisy net's f(eps) vector (fb_qnet_get_noise): per layer fan_in + fan_out -- fc1, then the head's layer(s)"""
+    fc, an = int(fc_width), int(actions) * int(n_atoms)
+    return 1600 + fc + (fc + int(n_atoms) if arch == "c51dueling" else 0) + fc + an
 
 
 def check_support(n_atoms, v_min, v_max, actions=2):
@@ -316,11 +331,19 @@ class QNet:
     ARCHS = ("plain", "dueling") + C51_ARCHS
 
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
-                 v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2]):
+                 v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0):
         """arch='c51': the distributional head of include/fbdqn.h (n_atoms atoms on [v_min, v_max]; the support args are ignored otherwise);
-        arch='c51dueling': the dueling C51 head (value and advantage distributions, include/fbdqn.h) on the same support"""
+        arch='c51dueling': the dueling C51 head (value and advantage distributions, include/fbdqn.h) on the same support.
+        noisy=True (C51 archs only): factorised Gaussian noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the flat
+        vector is [mu | sigma], and the net starts in mean mode (reset_noise, noise; include/fbdqn.h)"""
         if arch not in self.ARCHS:
             raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
+        self.noisy = bool(noisy)
+        self.sigma0 = None
+        if self.noisy:
+            if arch not in C51_ARCHS:
+                raise ValueError(f"noisy layers are offered on the C51 heads only ({C51_ARCHS}), not arch {arch!r}")
+            self.sigma0 = check_sigma0(sigma0)
         if arch in C51_ARCHS:
             n_atoms, v_min, v_max = check_support(n_atoms, v_min, v_max, actions)
         L.require_gpu()
@@ -329,7 +352,10 @@ class QNet:
         self.arch = arch
         self.device = torch.device(device)
         self.h = C.c_void_p()
-        if arch == "c51":
+        if self.noisy:
+            L.check(L.lib().fb_qnet_create_c51_noisy(L.ARCH_C51 if arch == "c51" else L.ARCH_C51_DUELING, self.FC, self.A, n_atoms, v_min, v_max,
+                                                     self.sigma0, self.max_batch, C.byref(self.h)), "fb_qnet_create_c51_noisy")
+        elif arch == "c51":
             L.check(L.lib().fb_qnet_create_c51(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)), "fb_qnet_create_c51")
         elif arch == "c51dueling":
             L.check(L.lib().fb_qnet_create_c51_dueling(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)),
@@ -423,6 +449,33 @@ class QNet:
 
     def sync_target(self):
         L.check(L.lib().fb_qnet_sync_target(self.h, L.current_stream()), "fb_qnet_sync_target")
+
+    # -- noise (noisy nets) ---------------------------------------------------------
+    def _need_noisy(self, what):
+        if not self.noisy:
+            raise ValueError(f"{what} needs a noisy net (QNet(..., noisy=True))")
+
+    def reset_noise(self, which=L.NET_ONLINE, seed=0, step=0, mean=False):
+        """draw net `which`'s noise at (seed, step) (fb_qnet_reset_noise), or mean=True: zero noise, the effective weights are mu"""
+        self._need_noisy("reset_noise")
+        L.check(L.lib().fb_qnet_reset_noise(self.h, int(which), int(seed), int(step), L.NOISE_MEAN if mean else L.NOISE_SAMPLE,
+                                            L.current_stream()), "fb_qnet_reset_noise")
+
+    def mean_noise(self, which=L.NET_ONLINE):
+        """mean mode for net `which`: zero noise"""
+        self.reset_noise(which, mean=True)
+
+    @property
+    def noise_size(self):
+        sup = self.support
+        return noise_size(self.FC, self.A, sup[0], self.arch) if self.noisy else 0
+
+    def noise(self, which=L.NET_ONLINE):
+        """net `which`'s current f(eps) vector, float32[noise_size] on the device (per layer: f(eps_in), then f(eps_out))"""
+        self._need_noisy("noise")
+        out = torch.empty(self.noise_size, dtype=torch.float32, device=self.device)
+        L.check(L.lib().fb_qnet_get_noise(self.h, int(which), L.ptr(out)), "fb_qnet_get_noise")
+        return out
 
     @property
     def support(self):

@@ -8,7 +8,9 @@ Host-side schedule follows the reference: training starts once onlineTimeStep > 
 decays by (INITIAL - FINAL) / EXPLORE per step after that, Nature/Double sync the target net when
 timeStep % 500 == 0, PER never does (the reference agent's quirk, kept for algo 'per' only); C51 and C51 with prioritized
 replay ('c51per' / 'c51doubleper') sync every replace_target_iter steps.  arch='c51dueling' gives any of the C51 algos the dueling
-C51 head (Rainbow's, with 'c51doubleper' and n-step returns: FlappyBirdDQN.py --model rainbow).
+C51 head (Rainbow's, with 'c51doubleper' and n-step returns: FlappyBirdDQN.py --model rainbow).  noisy=True gives a C51 algo's net
+noisy fc1 and head layers (NoisyNet; with arch='c51dueling', 'c51doubleper' and n-step returns: full Rainbow, --model rainbow --noisy):
+fb_vec_step draws the nets' noise every step, and the epsilon schedule defaults to 0.
 """
 from . import dist as fdist
 
@@ -39,12 +41,13 @@ class HipVecBackend:
 
     c51 = True                                               # distributional nets (net(..., support=(n_atoms, v_min, v_max)))
     c51_dueling = True                                       # ... with the dueling C51 head as well (net(..., arch='c51dueling', support=...))
+    c51_noisy = True                                         # ... and noisy C51 nets (net(..., support=..., noisy=True, sigma0=s))
 
-    def net(self, actions, fc_width, arch, max_batch, support=None):
+    def net(self, actions, fc_width, arch, max_batch, support=None, noisy=False, sigma0=0.5):
         from .vec import QNet
         if support is not None:
             return QNet(actions, fc_width, arch if arch in C51_HEADS else "c51", max_batch=max_batch, n_atoms=support[0], v_min=support[1],
-                        v_max=support[2])
+                        v_max=support[2], noisy=noisy, sigma0=sigma0)
         return QNet(actions, fc_width, arch, max_batch=max_batch)
 
     def step(self, env, replay, net, batch, algo, gamma, flat_grad, dist=None, mean_loss=False):
@@ -100,6 +103,15 @@ def check_checkpoint_head(z, head, path):
                          "do not convert)")
 
 
+def check_checkpoint_noisy(z, noisy, sigma0, path):
+    """a checkpoint's net must be noisy exactly when this brain's is (checkpoints that record nothing hold a non-noisy net)"""
+    saved = bool(z["noisy"][0]) if "noisy" in z.files else False
+    if saved != bool(noisy):
+        kind = lambda b: "a noisy net" if b else "a non-noisy net"
+        raise ValueError(f"checkpoint {path} holds {kind(saved)}, this VecBrain has {kind(noisy)} (noisy=True / False: the parameter "
+                         "vectors [mu | sigma] and [mu] do not convert)")
+
+
 def check_checkpoint_support(z, support, path):
     """a checkpoint's head must be this brain's: C51 with the same support (n_atoms, v_min, v_max), or a scalar head on both sides"""
     saved = tuple(z["support"].tolist()) if "support" in z.files else None
@@ -113,14 +125,20 @@ def check_checkpoint_support(z, support, path):
 
 class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
-                 observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99,
-                 replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0):
+                 observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
+                 replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0,
+                 noisy=False, sigma0=0.5):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
         'c51per' / 'c51doubleper': the same with prioritized replay (importance-weighted loss, KL priorities; n_step at creation).
-        arch='c51dueling' (C51 algos only): the dueling C51 head -- value and advantage distributions (include/fbdqn.h)."""
+        arch='c51dueling' (C51 algos only): the dueling C51 head -- value and advantage distributions (include/fbdqn.h).
+        noisy=True (C51 algos only): noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the exploration comes from
+        the noise, so initial_epsilon defaults to 0 (0.03 without noise, the reference's); an explicit initial_epsilon is honoured."""
         n_step = int(n_step)
+        noisy = bool(noisy)
+        if initial_epsilon is None:
+            initial_epsilon = 0.0 if noisy else 0.03
         if not 1 <= n_step <= 16:
             raise ValueError(f"n_step must be in 1..16, got {n_step}")
         be = backend or HipVecBackend()
@@ -139,8 +157,13 @@ class VecBrain:
             if algo in C51_PER_ALGOS and not getattr(be, "per_one_step", False):
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
                                  f"algo {algo!r} needs it")
+            if noisy and not getattr(be, "c51_noisy", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no noisy C51 nets")
             self.support = check_support(n_atoms, v_min, v_max)
             arch = "c51dueling" if arch == "c51dueling" else "c51"
+        elif noisy:
+            raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, which train with a C51 algo ('c51', 'c51double', "
+                             f"'c51per', 'c51doubleper'), not {algo!r}")
         elif arch == "c51dueling":
             raise ValueError(f"arch {arch!r} is a C51 head: it trains with a C51 algo ('c51', 'c51double', 'c51per', 'c51doubleper'), "
                              f"not {algo!r}")
@@ -172,7 +195,14 @@ class VecBrain:
                 raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend's replay has no n-step view (n_step = {n_step})")
             self.replay.set_n_step(n_step, gamma)
         self.arch = arch
-        self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support) if self.support else be.net(2, fc_width, arch, max(n_envs, batch))
+        self.noisy = noisy
+        self.sigma0 = None
+        if noisy:
+            from .vec import check_sigma0
+            self.sigma0 = check_sigma0(sigma0)
+            self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support, noisy=True, sigma0=self.sigma0)
+        else:
+            self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support) if self.support else be.net(2, fc_width, arch, max(n_envs, batch))
         self.net.init_params(seed=seed, which=0)             # the same draw on every rank
         self.net.init_params(seed=seed + 1, which=1)
         if world > 1:                                        # replicas start from rank 0's parameters, bit for bit
@@ -257,11 +287,18 @@ class VecBrain:
         self.timeStep += 1
         self.onlineTimeStep += 1
 
-    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0):
+    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0, noise="mean"):
         """Greedy play of n_envs fresh games with the online net as it stands (dqnflappybird_amd.evaluate): changes nothing the
-        training that follows reads -- nets, Adam, envs, frame stacks, stats, replay, the step counters."""
+        training that follows reads -- nets, Adam, envs, frame stacks, stats, replay, the step counters.  A noisy net plays with its
+        mean weights (noise='sample': one sample keyed by act_seed); its online sample is put back afterwards (the last step's draw)."""
         from .evaluate import evaluate
-        return evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed)
+        res = evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed, noise=noise)
+        if self.noisy:                                       # (fb_vec_step drew the online noise at (seed + rank, timeStep - 1) last)
+            if self.timeStep > 0:
+                self.net.reset_noise(0, self.seed + self.rank, self.timeStep - 1)
+            else:
+                self.net.mean_noise(0)
+        return res
 
     def set_dtype(self, dtype="f32"):
         """'bf16' = BASELINE.json configs[2]'s arithmetic for acting AND training (fp32 master weights / Adam); 'f32' = default."""
@@ -302,6 +339,9 @@ class VecBrain:
             if self.support is not None:                     # (scalar-head checkpoints carry no support)
                 shared["support"] = np.array(self.support, np.float64)
                 shared["head"] = np.array([self.arch])       # 'c51' or 'c51dueling' (checkpoints without it: 'c51')
+            if self.noisy:                                   # online / target / Adam hold [mu | sigma] (checkpoints without it: not noisy)
+                shared["noisy"] = np.array([1], np.int64)
+                shared["sigma0"] = np.array([self.sigma0], np.float64)
         if self.world == 1:
             np.savez(self._npz(path), **shared, **local)
             return
@@ -324,6 +364,7 @@ class VecBrain:
         check_checkpoint_support(z, self.support, path)
         if self.support is not None:
             check_checkpoint_head(z, self.arch, path)
+        check_checkpoint_noisy(z, self.noisy, self.sigma0, path)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         self.net.load_params(z["online"], 0)

@@ -352,6 +352,47 @@ int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, fl
  * unfold from that head's.  The results agree with the formulas above to float rounding, not bit for bit.) */
 #define FB_ARCH_C51_DUELING 3
 int fb_qnet_create_c51_dueling(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out);
+/* Noisy C51 nets (NoisyNet, Fortunato et al. 2018: with the dueling C51 head, the double target, prioritized replay and n-step returns,
+ * full Rainbow).  A noisy net is a C51 (arch 2) or dueling C51 (arch 3) net whose fully connected layers are factorised Gaussian noisy
+ * layers: fc1 and every head layer (W_fc2 b for C51; W_v b_v and W_a b_a, two separate layers, for dueling C51).  The conv trunk stays
+ * deterministic.  Made by fb_qnet_create_c51_noisy (arch 2 or 3, the support checks of fb_qnet_create_c51, sigma0 finite and >= 0; all
+ * before any allocation).
+ *   layer       y = (mu_W + sigma_W (.) (f(eps_out) x f(eps_in))) . x + mu_b + sigma_b (.) f(eps_out),  f(z) = sign(z) sqrt|z|
+ *               (W[in][out] as everywhere here: sigma_W[i][j] multiplies f(eps_in_i) f(eps_out_j)); eps_in has fan_in entries, eps_out fan_out
+ *   layout      the flat vector (fb_qnet_num_params, load / store_params, flat_grad, fb_qnet_apply_adam, the Adam state, fb_qnet_sync_target)
+ *               is [mu | sigma]: mu in the net's C51 / dueling C51 layout above, unchanged, then sigma in the same tensor order from W_fc1
+ *               on (sigma_W_fc1 sigma_b_fc1, then the sigma of each head tensor): sigma of mu entry q sits at n_mu + q - 77984
+ *               (n_mu = the non-noisy net's count; FC 512, 51 atoms, A 2: 950 022 + 872 038 for C51, 976 185 + 898 201 for dueling C51)
+ *   init        fb_qnet_init_params: mu exactly as the non-noisy net's (the same Philox draws), then sigma = sigma0 / sqrt(fan_in) for the
+ *               weights and the biases of each layer (fan_in 1600 for fc1, FC for the head layers), in float64 rounded to float
+ *   noise       each net (online 0, target 1) holds a current sample: the vector f(eps) of nz floats, per layer in the order above f(eps_in)
+ *               [fan_in] then f(eps_out)[fan_out] (nz = 1600 + FC + FC + A*N for C51, 1600 + FC + FC + N + FC + A*N for dueling C51: 2 726 and 3 289
+ *               at FC 512, 51 atoms, A 2).
+ *               FB_NOISE_SAMPLE at (seed, step): element k of net w is z = sqrt(-2 log u1) cos(2 pi u2) (no truncation; fp32 logf / cosf),
+ *               u1 = ((r.x >> 8) + 1) / 2^24, u2 = (r.y >> 8) / 2^24, r = Philox4x32-10(key = (seed_lo, seed_hi), counter = (k, step_lo,
+ *               FB_STREAM_NOISE = 6, 2 step_hi + w)), stored as f(z); the online and target nets draw independent vectors for the same key.
+ *               FB_NOISE_MEAN: every element 0, so the effective weights are mu exactly.  A new net is in mean mode.  Only
+ *               fb_qnet_reset_noise and fb_vec_step change a sample; forward, act, act_nib, forward_dist, fb_eval_q, fb_eval_run,
+ *               fb_qnet_train_step and fb_train_from_replay use the current one and never resample.  fb_qnet_get_noise copies a net's
+ *               current f(eps) (nz floats, host or device memory; synchronous).  Init, load, sync and Adam keep each net's sample.
+ *   gradient    G = the loss gradient of the effective weights: d/dmu = G, d/dsigma_W[i][j] = G[i][j] f(eps_in_i) f(eps_out_j),
+ *               d/dsigma_b[j] = G_b[j] f(eps_out_j); TF Adam with the net's hyper-parameters updates all of [mu | sigma].  The online
+ *               prediction and the double target's a* use the online net's sample, the target distribution the target net's sample.
+ *   fb_vec_step on a noisy net: before acting, fb_qnet_reset_noise(net 0, seed, step); before the train step (train != 0),
+ *               fb_qnet_reset_noise(net 1, seed, step); acting and the train step of the call share the online sample (one sample per
+ *               net per step for all envs, not one per env); epsilon-greedy as passed (0 for Rainbow).  Bit for bit the composed calls
+ *               reset_noise(0) -> act_nib -> env step (+ push / sample) -> reset_noise(1) -> train, for all four C51 algos, both memories, any n.
+ *   refused     FB_ERR_INVALID before any launch or counter change: a scalar arch, fb_vec_step_dp, fb_train_steps (no per-step noise key);
+ *               fb_qnet_reset_noise / fb_qnet_get_noise on a net that is not noisy.  (The TF bundle export refuses it in Python.)
+ * (The library keeps an effective vector mu + sigma (.) noise per net, rebuilt after every change of mu, sigma or the noise -- init, load,
+ * sync, Adam, reset -- which every forward and backward kernel reads; sigma's gradient is formed from the effective one's.) */
+#define FB_NOISE_SAMPLE 0
+#define FB_NOISE_MEAN 1
+int fb_qnet_create_c51_noisy(int arch, int fc_width, int n_actions, int n_atoms, float v_min, float v_max, float sigma0, int max_batch,
+                             fb_qnet_t *out);
+int fb_qnet_is_noisy(fb_qnet_t h);                                                      /* 1: a noisy net, 0: not (or NULL) */
+int fb_qnet_reset_noise(fb_qnet_t h, int which, uint64_t seed, uint64_t step, int mode, void *stream);
+int fb_qnet_get_noise(fb_qnet_t h, int which, float *out);
 int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host);      /* n_atoms = 0: not a C51 net */
 int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream);
 

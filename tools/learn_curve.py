@@ -12,7 +12,8 @@ One VecBrain run per (envs, lr); one train step per loop step once onlineTimeSte
 steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and zeroed, so each
 row is the window's own figure, not a running average.  Rows go to stdout and to --out as they are produced.
 --n-step K trains from K-step returns (VecBrain(n_step=K); with --algo per / c51per / c51doubleper a prioritized memory created with K-step returns); the summary gives the train steps at which the windowed mean score first
-passed 1 / 10 / 100, and --eval-envs M (> 0) ends each run with VecBrain.evaluate() on M fresh greedy games.
+passed 1 / 10 / 100, and --eval-envs M (> 0) ends each run with VecBrain.evaluate() on M fresh greedy games.  --noisy gives a C51 algo's
+net noisy layers (epsilon 0 unless --initial-epsilon says otherwise).
 """
 import argparse
 import os
@@ -26,13 +27,16 @@ import torch  # noqa: E402
 from dqnflappybird_amd.vecbrain import VecBrain  # noqa: E402
 
 
-def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore, n_step=1, eval_envs=0, support=(51, -10.0, 10.0)):
+def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore, n_step=1, eval_envs=0, support=(51, -10.0, 10.0), noisy=False,
+        initial_epsilon=None):
     vb = VecBrain(n_envs, algo=algo, arch=arch, capacity=1_000_000, seed=seed, explore=explore, n_step=n_step,
-                  n_atoms=support[0], v_min=support[1], v_max=support[2])
+                  n_atoms=support[0], v_min=support[1], v_max=support[2], noisy=noisy, initial_epsilon=initial_epsilon)
     vb.net.set_hparams(lr=lr)
     head = f"# envs {n_envs}  algo {algo}/{arch}  n_step {n_step}  lr {lr:g}  batch {vb.batch}  observe {vb.observe}  explore {vb.explore}  eps {vb.initial_epsilon} -> {vb.final_epsilon}  {'target never synced (PER: the reference agent never syncs it)' if algo == 'per' else f'target sync / {vb.replace_target_iter}'}"
     if vb.support:
         head += f"  support {vb.support[0]} atoms on [{vb.support[1]:g}, {vb.support[2]:g}]"
+    if vb.noisy:
+        head += f"  noisy (sigma0 {vb.sigma0:g})"
     cols = "#   train_steps   env_steps  epsilon  episodes  mean_score  max_score  pipes/episode      loss   steps/s"
     for f in (sys.stdout, out):
         print(head, file=f); print(cols, file=f); f.flush()
@@ -96,6 +100,8 @@ def main():
     ap.add_argument("--vmax", type=float, default=10.0)
     ap.add_argument("--eval-envs", type=int, default=0, help="end each run with VecBrain.evaluate() on this many games (0 = no evaluation)")
     ap.add_argument("--budget-s", type=float, default=0.0, help="stop a run after this many seconds (0 = run all its steps)")
+    ap.add_argument("--noisy", action="store_true", help="a C51 algo's net with noisy fc1 and head layers (VecBrain(noisy=True))")
+    ap.add_argument("--initial-epsilon", type=float, default=None, help="the epsilon schedule's start (default: VecBrain's, 0 when --noisy)")
     ap.add_argument("--out", default="gpurun_out/learning.txt")
     a = ap.parse_args()
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
@@ -103,7 +109,8 @@ def main():
         print(f"# tools/learn_curve.py on {torch.cuda.get_device_name(0)}: {' '.join(sys.argv[1:])}", file=out)
         for n_envs in [int(x) for x in a.envs.split(",")]:
             for lr in [float(x) for x in a.lrs.split(",")]:
-                run(n_envs, lr, a.steps, a.window, a.algo, a.arch, a.seed, out, a.budget_s, a.explore, a.n_step, a.eval_envs, (a.atoms, a.vmin, a.vmax))
+                run(n_envs, lr, a.steps, a.window, a.algo, a.arch, a.seed, out, a.budget_s, a.explore, a.n_step, a.eval_envs, (a.atoms, a.vmin, a.vmax),
+                    a.noisy, a.initial_epsilon)
 
 
 if __name__ == "__main__":
