@@ -126,16 +126,13 @@ struct FbEvalRider {
     unsigned long long *done_step;             // the latest vector step (1-based) at which an env ended its last episode
     unsigned long long step;                   // this launch's vector step (0-based)
 };
-// fb_replay_gather as a rider of another module's launch (fb_gather.h; B == 0: no rider): what the kernel needs of the ring
+// What a kernel needs of the replay's frame ring to read transitions from it (fb_gather.h)
 // nstep / gamma: the memory's n-step view (fb_replay_set_n_step; nstep = 1: the one-step transition, gamma unused)
 struct FbGatherCtx {
     long long cap; int n_envs, t_f, kind;
     const unsigned long long *bits; const uint8_t *act; const float *rew; const uint8_t *term; int *error;
     int nstep; double gamma;
 };
-struct FbGatherRider { FbGatherCtx c; long long steps; int B; const long long *idx; uint8_t *s, *s2, *a; float *r; uint8_t *t; };
-int fb_replay_gather_rider(fb_replay_t h, int batch, const int64_t *idx, uint8_t *s, uint8_t *s2, uint8_t *a, float *r, uint8_t *t,
-                           FbGatherRider *rider);
 // A sampled minibatch described by where it lives in the frame ring instead of by gathered copies: the train step's first kernel reads
 // the 1-bit frames itself (no gather launch, no u8 expansion) and fills a / r / t (u8 / f32 / u8 [B], [dev]) for the loss.
 struct FbRingSrc { FbGatherCtx c; long long steps; const long long *idx; uint8_t *a; float *r; uint8_t *t; };
@@ -239,10 +236,5 @@ int fb_replay_sample_f32(fb_replay_t h, int batch, const double *uniforms, int64
 // the rider for "fb_replay_push; fb_replay_sample(batch) -> idx" (memory as it will be after `pushes_ahead` more pushes).  Returns 1 and
 // fills *rider for a uniform memory with the CPython generator, 0 when the sampler cannot ride (PER, other generators).
 int fb_replay_sample_rider(fb_replay_t h, int batch, int64_t *idx, FbSampleRider *rider, int pushes_ahead = 1);
-// fb_qnet_train_step (fused Adam) with a random.sample rider in its conv3 backward launch and the NEXT step's gather in its
-// Adam launch (either may be NULL)
-int fb_qnet_train_step_rider(fb_qnet_t h, int algo, int batch, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
-                             const uint8_t *t, double gamma, float *loss, const FbSampleRider *rider, const FbGatherRider *gather,
-                             void *stream);
 void fb_mt_init_genrand_host(FbMT *s, uint32_t seed);
 void fb_mt_init_by_array_host(FbMT *s, const uint32_t *key, int n);

@@ -96,8 +96,7 @@ void fb_mt_init_by_array_host(FbMT *s, const uint32_t *key, int key_length) {
 // draw for step i + 1 rides in step i's conv3 backward launch (it needs the generator and len(memory), nothing of step i).  What lets
 // a step start with the trunk: the Adam launch leaves the split planes of W_conv1 / W_conv2 / W_conv3 behind (adam_fused_kernel), and
 // every other writer of the parameters re-splits eagerly, so the conv planes are current without an acting forward in between.
-// idx holds two index buffers used alternately; the indices of step i end up in idx[(i & 1) * batch ..).  s / s2 (the u8 minibatch
-// of the gathered form) are only written when FB_TRAIN_STEPS_GATHER=1 selects that form (A/B knob: 7 launches per step).
+// idx holds two index buffers used alternately; the indices of step i end up in idx[(i & 1) * batch ..).  s / s2 are not written.
 extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int batch, int n_steps, int64_t *idx, uint8_t *s,
                               uint8_t *s2, uint8_t *a, float *r, uint8_t *t, float *loss, double gamma, void *stream) {
     FB_REQUIRE(replay && net && idx && s && s2 && a && r && t && loss && n_steps >= 1, "fb_train_steps: bad argument");
@@ -111,36 +110,18 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
                    "%s: a C51 net takes a C51 algo (FB_ALGO_C51 or FB_ALGO_C51_DOUBLE), and those algos take a C51 net only (algo %d)", "fb_train_steps", algo);
         FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_steps");
     }
-    static const bool gathered_form = getenv("FB_TRAIN_STEPS_GATHER") && atoi(getenv("FB_TRAIN_STEPS_GATHER")) == 1;
     int rc = fb_replay_check_gamma(replay, gamma, "fb_train_steps");
     if (rc != FB_OK) return rc;
-    gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: the ring readers / gathers deliver (R, done), the target takes Gamma)
+    gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: the ring readers deliver (R, done), the target takes Gamma)
     rc = fb_replay_sample(replay, batch, nullptr, idx, nullptr, stream);
-    if (!gathered_form) {
-        for (int i = 0; rc == FB_OK && i < n_steps; i++) {
-            int64_t *cur = idx + (size_t)(i & 1) * batch, *nxt = idx + (size_t)((i + 1) & 1) * batch;
-            FbRingSrc ring;
-            rc = fb_replay_ring_src(replay, batch, cur, a, r, t, &ring);
-            if (rc != FB_OK) break;
-            FbSampleRider srider;
-            const int rides = i + 1 < n_steps && fb_replay_sample_rider(replay, batch, nxt, &srider, 0);
-            rc = fb_qnet_train_step_ring(net, algo, batch, &ring, nullptr, gamma, loss, nullptr, nullptr, stream, rides ? &srider : nullptr);
-            if (rc == FB_OK && i + 1 < n_steps && !rides) rc = fb_replay_sample(replay, batch, nullptr, nxt, nullptr, stream);
-        }
-        return rc;
-    }
-    bool gathered = false;                               // the minibatch of step i is already in s / s2 / a / r / t
     for (int i = 0; rc == FB_OK && i < n_steps; i++) {
         int64_t *cur = idx + (size_t)(i & 1) * batch, *nxt = idx + (size_t)((i + 1) & 1) * batch;
-        if (!gathered) rc = fb_replay_gather(replay, batch, cur, s, s2, a, r, t, stream);
+        FbRingSrc ring;
+        rc = fb_replay_ring_src(replay, batch, cur, a, r, t, &ring);
         if (rc != FB_OK) break;
         FbSampleRider srider;
-        FbGatherRider grider;
-        const int rides = i + 1 < n_steps && fb_replay_sample_rider(replay, batch, nxt, &srider, 0) &&
-                          fb_replay_gather_rider(replay, batch, nxt, s, s2, a, r, t, &grider);
-        rc = fb_qnet_train_step_rider(net, algo, batch, s, a, r, s2, t, gamma, loss, rides ? &srider : nullptr,
-                                      rides ? &grider : nullptr, stream);
-        gathered = rides;
+        const int rides = i + 1 < n_steps && fb_replay_sample_rider(replay, batch, nxt, &srider, 0);
+        rc = fb_qnet_train_step_ring(net, algo, batch, &ring, nullptr, gamma, loss, nullptr, nullptr, stream, rides ? &srider : nullptr);
         if (rc == FB_OK && i + 1 < n_steps && !rides) rc = fb_replay_sample(replay, batch, nullptr, nxt, nullptr, stream);
     }
     return rc;
@@ -253,12 +234,8 @@ hipStream_t fb_side_stream_beside(hipStream_t C, int priority, hipStream_t curre
     return current;
 }
 
-// which schedule fb_vec_step uses where both apply: 1 (default; FB_VEC_SPLIT=0 starts the process with 0) = the split schedule
-static int fb_vec_split_flag = -1;
-static bool fb_vec_split_enabled() {
-    if (fb_vec_split_flag < 0) fb_vec_split_flag = !(getenv("FB_VEC_SPLIT") && atoi(getenv("FB_VEC_SPLIT")) == 0);
-    return fb_vec_split_flag != 0;
-}
+// which schedule fb_vec_step uses where both apply: 1 (default) = the split schedule, 0 = one stream
+static int fb_vec_split_flag = 1;
 extern "C" int fb_vec_step_set_schedule(int split) { fb_vec_split_flag = split ? 1 : 0; return FB_OK; }
 
 // One step of the vectorised loop as a single host call: the five C-ABI calls of FlappyBirdDQN.py:72-76 back to back.
@@ -317,7 +294,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // acting forward has its own (hf_act / hp_act); the acting forward against the previous step's Adam and whatever else the caller's
     // stream held at entry -> c_entry.
     // (C51 nets: the one-stream order below -- the split schedule is specified for the 2-output scalar heads)
-    if (fb_vec_split_enabled() && train && !per && n_envs >= 256 && batch < 256 && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 &&
+    if (fb_vec_split_flag && train && !per && n_envs >= 256 && batch < 256 && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 &&
         !fb_qnet_is_c51(net)) {
         hipStream_t A = fb_stream(stream);
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -348,8 +325,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
             // partial -- 4096 envs: 52 of 820 -- : the train chain then starts with that last round, when most of the chip falls idle, and
             // the full rounds run undisturbed: 205 -> 200 us per step at 4096 envs; at 2048 envs what is left of the side chain by then is
             // shorter than the train chain, 123 -> 125, hence the threshold)
-            static const bool last_round_on = !(getenv("FB_SPLIT_LAST_ROUND") && atoi(getenv("FB_SPLIT_LAST_ROUND")) == 0);      // A/B knob
-            const int trunk_wgs = (n_envs + 4) / 5, wait_last_round = last_round_on && n_envs >= 4096 && trunk_wgs % 256 != 0;
+            const int trunk_wgs = (n_envs + 4) / 5, wait_last_round = n_envs >= 4096 && trunk_wgs % 256 != 0;
             if (!fb_replay_sample_gated(replay, batch, b->idx, sc, C, wait_last_round)) { sc->seq -= 1; return fb_set_error(FB_ERR_HIP, "fb_vec_step: the gated draw could not be launched"); }
             int rc = fb_split_wait(sc, &F->c_entry, sc->seq, S);
             FbHeadRider hrider;
@@ -371,15 +347,13 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     }
     // prioritized memory: Memory.store's tree update of this step's push goes out FIRST, on the memory's side stream -- it depends on the
     // tree as the previous step left it and on the env count, nothing else -- and runs beside the acting forward and the env step
-    static const bool store_ahead = !(getenv("FB_PER_STORE_AHEAD") && atoi(getenv("FB_PER_STORE_AHEAD")) == 0);      // A/B knob
     int sampled = 0;                                 // ... and, behind it on that stream, Memory.sample of this step (it needs that tree and the memory's generator)
-    if (per && store_ahead && fb_replay_per_store_ahead(replay, stream) && train)
+    if (per && fb_replay_per_store_ahead(replay, stream) && train)
         sampled = fb_replay_sample_ahead(replay, batch, b->idx, b->isw, b->isw32, stream);
     // the acting path's last kernel (fc2 + epsilon-greedy action, one wave per env) rides in the env launch as well when
     // an env workgroup has a wave for each of its envs there (up to four envs per workgroup: 8192 envs)
     FbHeadRider hrider;
-    static const bool head_rides = !(getenv("FB_VEC_HEAD_RIDER") && atoi(getenv("FB_VEC_HEAD_RIDER")) == 0);      // tuning knob
-    const int have_h = head_rides && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 && !fb_qnet_is_c51(net);      // (C51: its own launch)
+    const int have_h = fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 && !fb_qnet_is_c51(net);      // (C51: its own launch)
     int rc = have_h ? fb_qnet_act_nib_rider(net, b->nib, n_envs, epsilon, seed, step, b->actions, &hrider, stream)
                     : fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
     if (rc != FB_OK) return rc;
@@ -388,8 +362,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // ring.  Memories that cannot ride keep their own launches (same results).
     FbSampleRider srider;
     FbPushRider prider;
-    static const bool sample_rides = !(getenv("FB_VEC_SAMPLE_RIDER") && atoi(getenv("FB_VEC_SAMPLE_RIDER")) == 0);      // A/B knob
-    const int have_s = train && sample_rides ? fb_replay_sample_rider(replay, batch, b->idx, &srider) : 0;      // before the push is counted
+    const int have_s = train ? fb_replay_sample_rider(replay, batch, b->idx, &srider) : 0;      // before the push is counted
     const int have_p = fb_replay_begin_push_rider(replay, &prider);
     rc = fb_env_step_rider(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, have_s ? &srider : nullptr,
                            have_p ? &prider : nullptr, have_h ? &hrider : nullptr, stream);
@@ -427,10 +400,9 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // No gather (256 envs or more).  The train step's first launch reads the sampled transitions' 1-bit frames in the ring itself
     // (conv trunk per state) and leaves a / r / t behind; the split conv planes it needs are current because the acting forward above
     // has just refreshed them.  (b->s / b->s2 stay untouched then.)
-    static const bool ring_on = !(getenv("FB_VEC_RING") && atoi(getenv("FB_VEC_RING")) == 0);      // tuning / A-B knob
     rc = target_noise();
     if (rc != FB_OK) return rc;
-    if (ring_on && n_envs >= 256) {
+    if (n_envs >= 256) {
         FbRingSrc ring;
         rc = fb_replay_ring_src(replay, batch, b->idx, b->a, b->r, b->t, &ring);
         if (rc != FB_OK) return rc;

@@ -1,6 +1,5 @@
-// Minibatch assembly from the packed frame ring -- device code shared by the replay kernels (fb_replay.hip) and the Adam
-// kernel, which can carry the NEXT train step's gather as a rider (fb_qnet.hip, fb_train_steps).  Included inside each
-// translation unit's anonymous namespace.
+// Minibatch assembly from the packed frame ring -- device code shared by the replay kernels (fb_replay.hip) and the ring-fed
+// train trunk (fb_qnet.hip).  Included inside each translation unit's anonymous namespace.
 #pragma once
 
 __device__ __forceinline__ size_t fb_frame_off(const FbGatherCtx &P, long long f, int e) {

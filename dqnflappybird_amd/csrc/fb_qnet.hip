@@ -36,7 +36,7 @@ constexpr int OFF_W1 = 0, OFF_B1 = 8192, OFF_W2 = 8224, OFF_B2 = 40992, OFF_W3 =
 constexpr int CONV_PARAMS = OFF_WF1;         // everything in front of W_fc1
 #include "fb_head.h"               // MAXA, FC1_KS, sel4, head_one
 #include "fb_sampler.h"            // the replay sampler can ride in the conv3 backward launch (fb_train_steps)
-#include "fb_gather.h"             // ... and the next step's minibatch gather in the Adam launch
+#include "fb_gather.h"             // the ring readers of the ring-fed train trunk
 constexpr int MAXTB = 256;
 
 
@@ -396,12 +396,12 @@ __global__ __launch_bounds__(256) void conv1_pool_kernel(Slices sl, float *__res
 // Activations travel between the layers as two fp16 planes (one bf16 plane in bf16 mode) [plane][row][channel]; the weights are
 // re-split whenever the parameters changed: wsp[k/8][plane][N] x 8 halves (16 B).
 // NS = 3: the fp32-equivalent path; NS = 1 uses the bf16 plane only = plain bf16 arithmetic.
-// conv1 of that path.  The small-batch kernel's wave re-reads all 32 KB of split weights for every tile (400 MB of
-// L1/L2 traffic at 1024 states); here a workgroup parks them in LDS once and its waves walk over tiles, the
-// next tile's input bytes in flight while the current one is in the MFMAs.  The vector ALU is the scarce unit here
-// (32 MFMAs per tile leave room for ~170 vector instructions): taps are immediate offsets into the SAME-padded nibble
-// image, the 2x2 pool is a max over four registers of a lane, and a quad transpose hands every lane 4 consecutive
-// channels of one pooled pixel for an 8-byte store per plane (512 B per wave, contiguous).
+// conv1 of that path on u8 states (the acting path's nibble states go through conv23_sp_kernel<., 5, true> instead).  The small-batch
+// kernel's wave re-reads all 32 KB of split weights for every tile (400 MB of L1/L2 traffic at 1024 states); here a workgroup parks them
+// in LDS once and its waves walk over tiles, the next tile's input bytes in flight while the current one is in the MFMAs.  The vector
+// ALU is the scarce unit here (32 MFMAs per tile leave room for ~170 vector instructions): the 2x2 pool is a max over four registers of
+// a lane, and a quad transpose hands every lane 4 consecutive channels of one pooled pixel for an 8-byte store per plane (512 B per
+// wave, contiguous).
 // One workgroup of 12 waves per CU (3 per SIMD, <= 168 VGPRs): one copy of the weights per CU, and 12800 tiles over
 // 3072 waves leave every SIMD 12 or 13 tiles (640 workgroups of 4 waves left some CUs with 3 workgroups = 15 tiles
 // per SIMD and others with 2).  When the step changed the parameters every thread first re-splits at most one
@@ -427,13 +427,11 @@ __device__ __forceinline__ void quad_transpose(float (&v)[4], int l) {
 // pooled activations and the position of each pool's maximum (first maximum, like conv1_pool_kernel).
 struct C1Side { const uint8_t *st1, *st2; int per; float *p1; uint8_t *amax; };
 
-template <bool NIB>
 __global__ __launch_bounds__(64 * C1_WAVES) void conv1_sp_kernel(Slice s, const uint8_t *__restrict__ zeros, uint16_t *__restrict__ p1s,
                                                                   size_t p1plane, int nsplit, uint4 *__restrict__ wsp, int FC,
                                                                   const unsigned *__restrict__ pver, const unsigned *__restrict__ wver, C1Side side,
                                                                   unsigned *__restrict__ ovf) {
     __shared__ uint4 wl[2 * 16 * 64];
-    __shared__ uint4 lut[NIB ? 256 : 1];
     const int bid = blockIdx.x, nblk = gridDim.x;
     // this workgroup's weight copy goes out first, the re-split items' loads right behind it (one round trip, not two)
     // (named registers: as an array hipcc "promoted" the staging copy to LDS -- 36 KB more per workgroup and 18 -> 30 us)
@@ -451,9 +449,8 @@ __global__ __launch_bounds__(64 * C1_WAVES) void conv1_sp_kernel(Slice s, const 
     if (wq0 < WQ) wl[wq0] = wc0;
     if (wq1 < WQ) wl[wq1] = wc1;
     if (wq2 < WQ) wl[wq2] = wc2;
-    if (NIB && threadIdx.x < 256) lut[threadIdx.x] = nib_lut_entry(threadIdx.x);
     __syncthreads();
-    typedef typename std::conditional<NIB, unsigned, uint2>::type Raw;
+    typedef uint2 Raw;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hl = lane >> 5, j = lane & 31, pp = j >> 2, pos = j & 3;
     const int npool = s.count * 100, ntiles = (npool + 7) / 8, stride = nblk * C1_WAVES;
     const float bias = s.params[OFF_B1 + j];
@@ -464,28 +461,17 @@ __global__ __launch_bounds__(64 * C1_WAVES) void conv1_sp_kernel(Slice s, const 
         const int oy = 2 * py + (pos >> 1), ox = 2 * px + (pos & 1);
         const uint8_t *sbase = s.states;
         if (side.per) { const int blk = b / side.per; b -= blk * side.per; sbase = blk == 0 ? s.states : blk == 1 ? side.st1 : side.st2; }
-        if constexpr (NIB) {
-            // the nibble image carries conv1's SAME padding (FB_NIB_*): every tap is base + ky * pitch + 2 * kq, no bounds
-            // check, no select -- 16 byte loads at immediate offsets from one address
-            const uint8_t *base = sbase + (size_t)b * FB_NIB_STRIDE + (4 * oy) * FB_NIB_PITCH + 3 + 2 * ox + hl;
-#pragma unroll
-            for (int ky = 0; ky < 8; ky++)
-#pragma unroll
-                for (int kq = 0; kq < 2; kq++) raw[ky * 2 + kq] = base[ky * FB_NIB_PITCH + 2 * kq];
-            return;
-        }
 #pragma unroll
         for (int ky = 0; ky < 8; ky++) {
             const int iy = oy * 4 + ky - 2;
             const bool rowok = P < npool && iy >= 0 && iy < 80;
-            const uint8_t *row = sbase + (((size_t)b * 80 + (rowok ? iy : 0)) * 80) * (NIB ? 1 : 8) / 2;
+            const uint8_t *row = sbase + (((size_t)b * 80 + (rowok ? iy : 0)) * 80) * 8 / 2;
 #pragma unroll
             for (int kq = 0; kq < 2; kq++) {
                 const int ix = ox * 4 - 2 + 4 * kq + 2 * hl;
                 const bool ok = rowok && ix >= 0 && ix < 80;
-                // padding taps read the zero page (LUT entry 0 = zeros): no branch, so no vmcnt(0) at a join
-                if constexpr (NIB) raw[ky * 2 + kq] = *(ok ? row + (ix >> 1) : zeros);
-                else raw[ky * 2 + kq] = *reinterpret_cast<const uint2 *>(ok ? row + (size_t)ix * 4 : zeros);
+                // padding taps read the zero page: no branch, so no vmcnt(0) at a join
+                raw[ky * 2 + kq] = *reinterpret_cast<const uint2 *>(ok ? row + (size_t)ix * 4 : zeros);
             }
         }
     };
@@ -505,9 +491,7 @@ __global__ __launch_bounds__(64 * C1_WAVES) void conv1_sp_kernel(Slice s, const 
         f32x16 acc = {0}, acl = {0};
 #pragma unroll
         for (int c = 0; c < 16; c++) {
-            uint4 A;
-            if constexpr (NIB) A = lut[cur[c]];
-            else A = u8x8_to_f16(cur[c]);
+            const uint4 A = u8x8_to_f16(cur[c]);
             acc = mfma_h(A, wlz[(0 * 16 + c) * 64 + lane], acc);
             acl = mfma_h(A, wlz[(1 * 16 + c) * 64 + lane], acl);
         }
@@ -593,13 +577,13 @@ struct C23Args {
 #ifndef C23_EXIT
 #define C23_EXIT 0
 #endif
-// SPW = states per workgroup (5: 125 of the 128 MFMA rows; the fused acting trunk takes 4: 1024 envs = 256 workgroups = every CU).
+// SPW = states per workgroup (5: 125 of the 128 MFMA rows; every launch takes 5).
 // C1 = true: THE ACTING TRUNK -- conv1 + pool of the SPW states run in this kernel too, on the SAME-padded nibble states (one byte = 2
-// pixels x 4 frames; the MFMA operand is a 256-entry table lookup, as in conv1_sp_kernel<nib>): 8 waves x 6-7 tiles of 8 pooled pixels,
+// pixels x 4 frames; the MFMA operand is a 256-entry table lookup, as in conv1_pool_kernel<true>): 8 waves x 6-7 tiles of 8 pooled pixels,
 // each wave holding all 32 weight fragments of W_conv1's two planes in REGISTERS for its tiles (conv1_sp_kernel re-reads them from LDS
 // for every tile: 32 KB of LDS reads per tile, 2.4 MB per CU -- that kernel is as much LDS- as MFMA-bound), and the pooled output is
-// split straight into conv2's LDS image: the 13 + 13 MB of fp16 planes conv1_sp_kernel writes and this kernel read back, and one
-// launch boundary, are gone.  The nibble images, the table and the staged conv1 weights live where the weight ring and the exchange
+// split straight into conv2's LDS image: the 13 + 13 MB of fp16 planes a separate conv1 launch would write and this kernel read back,
+// and one launch boundary, are gone.  The nibble images, the table and the staged conv1 weights live where the weight ring and the exchange
 // area will be (both idle until conv2 starts).
 template <int NS, int SPW = 5, bool C1 = false>
 __global__ __launch_bounds__(512) void conv23_sp_kernel(C23Args a) {
@@ -651,7 +635,7 @@ __global__ __launch_bounds__(512) void conv23_sp_kernel(C23Args a) {
         const uint4 *w1g = reinterpret_cast<const uint4 *>(a.w1s);
         const uint4 wc0 = w1g[threadIdx.x], wc1 = w1g[threadIdx.x + 512], wc2 = w1g[threadIdx.x + 1024], wc3 = w1g[threadIdx.x + 1536];
         const uint4 *ng = reinterpret_cast<const uint4 *>(a.nib + (size_t)s0 * FB_NIB_STRIDE);
-        const int i0 = threadIdx.x, i1 = threadIdx.x + 512, i2 = threadIdx.x + 1024;      // (SPW * NIB_U4 = 928 entries at SPW = 4: two per thread; 1160 at 5: three)
+        const int i0 = threadIdx.x, i1 = threadIdx.x + 512, i2 = threadIdx.x + 1024;      // (SPW * NIB_U4 = 1160 entries at SPW = 5: three per thread)
         static_assert(SPW * NIB_U4 <= 1536, "at most three image entries per thread");
         const uint4 n0 = ng[i0 < nloc * NIB_U4 ? i0 : 0], n1 = ng[i1 < nloc * NIB_U4 ? i1 : 0];
         uint4 n2 = make_uint4(0u, 0u, 0u, 0u);
@@ -2902,13 +2886,11 @@ __global__ __launch_bounds__(512) void conv_bx_kernel(BxArgs bx, int B, int nz, 
     adam_span_body(t - 38 * nz, n_adam, span);
 }
 
-// (the SECOND part of W_fc1's Adam span rides here as n_adam trailing workgroups: the 22.9 MB of the whole span made conv_bx_kernel
-// HBM-bound -- 11 us in the loop against ~8 for its conv chain -- while this launch is latency-bound with ~190 idle CUs as well)
 template <int NSP, bool RING>
 __global__ __launch_bounds__(512) void conv_dw21_kernel(int nz, int B, const float *__restrict__ p1, const float *__restrict__ dh2,
                                                         const uint8_t *__restrict__ states, const float *__restrict__ dp1,
                                                         const uint8_t *__restrict__ amax, float *__restrict__ slabs, size_t slab_stride,
-                                                        float *__restrict__ slabs1, size_t stride1, int rb, Dw1Ring ring, int n_adam, AdamSpan span, FbGate gate) {
+                                                        float *__restrict__ slabs1, size_t stride1, int rb, Dw1Ring ring, FbGate gate) {
     if (fb_gate_workgroup(gate)) return;
     const int n2 = 34 * nz;                       // (slabs1 / stride1: where conv1's slabs go -- the common slab set, or the fold buffer)
     __shared__ uint4 pool[Dw1Lds<NSP>::U4];
@@ -2918,8 +2900,7 @@ __global__ __launch_bounds__(512) void conv_dw21_kernel(int nz, int B, const flo
         conv_dw_body<2>(blockIdx.x % 34, blockIdx.x / 34, nz, red, B, p1, dh2, slabs, slab_stride, rb);
         return;
     }
-    if ((int)blockIdx.x < n2 + NSP * B) { conv1_dw2_body<NSP, RING>((int)blockIdx.x - n2, states, dp1, amax, slabs1, stride1, pool, ring); return; }
-    adam_span_body((int)blockIdx.x - n2 - NSP * B, n_adam, span);
+    if ((int)blockIdx.x < n2 + NSP * B) conv1_dw2_body<NSP, RING>((int)blockIdx.x - n2, states, dp1, amax, slabs1, stride1, pool, ring);
 }
 
 // ==================================================================================================================================
@@ -3423,7 +3404,6 @@ static_assert(OFF_W2 % 4 == 0 && OFF_W3 % 4 == 0 && CONV_PARAMS % 4 == 0, "slab 
 //   workgroups [64, 136)    W_conv3 likewise (72 tiles)
 //   then n_rest             everything else from tail0 on: W_conv1 + b_conv1 (W_conv1's planes via split_w1), b_conv2, b_conv3, [W_fc1,]
 //                           b_fc1 and the head; `lanes` (4 with slabs: one chunk per lane; 1 without) lanes per float4
-//   then                    fb_train_steps' gather rider, if any
 constexpr int ADAMF_T2 = 64, ADAMF_T3 = 72;
 struct AdamFused {
     float *p, *m, *v; const float *g; long long n; AdamDev *ad;
@@ -3438,14 +3418,9 @@ struct AdamFused {
     FbSplitFlags *split; unsigned long long split_val;
 };
 __device__ __forceinline__ float4 shfl4(float4 v, int src) { return make_float4(__shfl(v.x, src), __shfl(v.y, src), __shfl(v.z, src), __shfl(v.w, src)); }
-__global__ __launch_bounds__(256) void adam_fused_kernel(AdamFused a, FbGatherRider gr) {
+__global__ __launch_bounds__(256) void adam_fused_kernel(AdamFused a) {
     __shared__ float tile[8][68];
     const int bid = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-    const int n_adam = ADAMF_T2 + ADAMF_T3 + a.n_rest;
-    if (bid >= n_adam) {
-        gather_body<false>(gr.c, gr.steps, gr.B, gr.idx, (uint4 *)gr.s, (uint4 *)gr.s2, gr.a, gr.r, gr.t, (long long)(bid - n_adam) * 256 + tid);
-        return;
-    }
     const float alpha = a.ad->alpha, omb1 = 1.f - a.ad->b1, omb2 = 1.f - a.ad->b2, eps = a.ad->eps;
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     if (bid < ADAMF_T2 + ADAMF_T3) {
@@ -3961,7 +3936,6 @@ struct Plan {
     float *loss, *abs_err, *y, *G; bool apply_adam, tick;
     FbHeadRider *head_rider;                 // acting path: describe the head work instead of launching it (fb_vec_step)
     const FbSampleRider *sample_rider;       // train plan: random.sample for the next step rides in the conv3 backward launch
-    const FbGatherRider *gather_rider;       // ... and its minibatch gather in the Adam launch
     const FbRingSrc *ring;                   // the minibatch lives in the replay's frame ring (no gathered copies): conv trunk in one launch
     // the split schedule (fb_common.hip).  Acting plan: the fc1 launch stores trunk_done.  Train plan: gate workgroups in the fc1 backward
     // launch (trunk_done) and the conv backward launch (fc1_done), the Adam launch's last thread waits for env_done
@@ -4039,14 +4013,12 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             if (z1 - z0 > 1) { side.per = s0.count; side.st1 = p.sl.s[z0 + 1].states; side.st2 = z1 - z0 > 2 ? p.sl.s[z0 + 2].states : p.sl.s[z0 + 1].states; }
             if (p.train) { side.p1 = h->p1; side.amax = h->amax; }
             const int t1p = (rows * 100 + 7) / 8, gsp = min(256, (t1p + C1_WAVES - 1) / C1_WAVES);      // one 12-wave workgroup per CU, the waves stride over the tiles
-            // the acting path on nibble states: conv1 + conv2 + conv3 in ONE launch (conv23_sp_kernel<., 4, true>), four states per workgroup
-            static const bool fuse_on = !(getenv("FB_ACT_FUSED") && atoi(getenv("FB_ACT_FUSED")) == 0);      // A/B knob
-            const bool fused = (fuse_on || p.any_rows) && p.nib && !p.train && !trunk && z1 - z0 == 1 && p.ns == 1;
+            // the acting path on nibble states (forward-only plans of one slice): conv1 + conv2 + conv3 in ONE launch
+            // (conv23_sp_kernel<., 5, true>), five states per workgroup
+            const bool fused = p.nib && !p.train && !trunk && z1 - z0 == 1 && p.ns == 1;
             acting_fused = fused;
-            if (!trunk && !fused) FB_K(K_CONV1) {
-                if (p.nib) hipLaunchKernelGGL(conv1_sp_kernel<true>, dim3(gsp), dim3(64 * C1_WAVES), 0, st, sl, (const uint8_t *)h->zeros, h->a1s, pl1, nsp, h->wsp[which], h->FC, pver, (const unsigned *)wver, side, &h->adam->ovf);
-                else hipLaunchKernelGGL(conv1_sp_kernel<false>, dim3(gsp), dim3(64 * C1_WAVES), 0, st, sl, (const uint8_t *)h->zeros, h->a1s, pl1, nsp, h->wsp[which], h->FC, pver, (const unsigned *)wver, side, &h->adam->ovf);
-            }
+            if (!trunk && !fused) FB_K(K_CONV1)
+                hipLaunchKernelGGL(conv1_sp_kernel, dim3(gsp), dim3(64 * C1_WAVES), 0, st, sl, (const uint8_t *)h->zeros, h->a1s, pl1, nsp, h->wsp[which], h->FC, pver, (const unsigned *)wver, side, &h->adam->ovf);
             C23Args c23{h->a1s + (size_t)row0 * 3200, pl1, h->wsp[which] + WSP_W2, s0.params + OFF_B2, s0.params + OFF_B3, h->a3s + (size_t)row0 * 1600, pl2, rows, pver, wver, only < 0 ? &h->adam->wverc[which] : nullptr,
                         p.train ? h->h2 + (size_t)row0 * 1600 : nullptr, p.train ? h->h3 + (size_t)row0 * 1600 : nullptr,
                         s0.states, s0.w1s, s0.params + OFF_B1, s0.params, h->wsp[which], h->FC, &h->adam->ovf};
@@ -4071,20 +4043,16 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             const int rows_f = af.M;
             // five states per workgroup (125 of the 128 MFMA rows; 1024 envs = 205 workgroups: alone it costs what four per workgroup on
             // all 256 CUs cost, and in the split schedule the fifth of the chip it leaves is where the train chain runs beside it)
-            static const int act_spw = getenv("FB_ACT_SPW") && atoi(getenv("FB_ACT_SPW")) == 4 ? 4 : 5;      // A/B knob: states per workgroup of the fused acting trunk
-            const bool spw5 = fused && (act_spw == 5 || p.split || p.any_rows);
-            const dim3 gc((rows + 4) / 5), gc4(spw5 ? (rows + 4) / 5 : (rows + 3) / 4), gf(((rows_f + 127) / 128) * (h->FC / 64) * FC1_SP_KS);    // FC % 128 == 0 (fb_qnet_create)
+            const dim3 gc((rows + 4) / 5), gf(((rows_f + 127) / 128) * (h->FC / 64) * FC1_SP_KS);    // FC % 128 == 0 (fb_qnet_create)
             // split schedule, more than one round of trunk workgroups (one per CU, 256 CUs) with a partial last round: that round's first
             // workgroup says when it has been placed -- the train chain on the other stream starts then (fb_sampler.h)
-            if (fused && p.split && only < 0 && gc4.x > 256 && gc4.x % 256 != 0) { c23.round_flag = &p.split->f->last_round; c23.round_val = p.split->seq; c23.round_blk = (int)(gc4.x / 256) * 256; }
+            if (fused && p.split && only < 0 && gc.x > 256 && gc.x % 256 != 0) { c23.round_flag = &p.split->f->last_round; c23.round_val = p.split->seq; c23.round_blk = (int)(gc.x / 256) * 256; }
             if (nsp == 3) {
-                if (spw5) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<3, 5, true>), gc4, dim3(512), 0, st, c23); }
-                else if (fused) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<3, 4, true>), gc4, dim3(512), 0, st, c23); }      // conv1 .. conv3
+                if (fused) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<3, 5, true>), gc, dim3(512), 0, st, c23); }      // conv1 .. conv3
                 else if (!trunk) { FB_K(K_CONV2) hipLaunchKernelGGL(conv23_sp_kernel<3>, gc, dim3(512), 0, st, c23); }      // conv3 rides in the same launch
                 FB_K(K_FC1) hipLaunchKernelGGL(fc1_sp_kernel<3>, gf, dim3(256), 0, st, af);
             } else {
-                if (spw5) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<1, 5, true>), gc4, dim3(512), 0, st, c23); }
-                else if (fused) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<1, 4, true>), gc4, dim3(512), 0, st, c23); }
+                if (fused) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<1, 5, true>), gc, dim3(512), 0, st, c23); }
                 else if (!trunk) { FB_K(K_CONV2) hipLaunchKernelGGL(conv23_sp_kernel<1>, gc, dim3(512), 0, st, c23); }
                 FB_K(K_FC1) hipLaunchKernelGGL(fc1_sp_kernel<1>, gf, dim3(256), 0, st, af);
             }
@@ -4207,15 +4175,12 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             h->grad_ev_recorded = nullptr;
             if (h->grad_ev) { FB_CHECK_HIP(hipEventRecord(h->grad_ev, st)); h->grad_ev_recorded = h->grad_ev; }
         }
-        // fused single-GPU update: W_fc1's Adam rides in this launch (AdamSpan); the data-parallel path exports the gradient instead
+        // fused single-GPU update: W_fc1's Adam rides in the conv backward launch below (AdamSpan), beside the conv data-gradient chain
+        // (measured, profiles/r03_notes.md: splitting it between that launch and the conv weight gradients' costs the same ~3.5 us in all
+        // -- the span is HBM traffic at ~6.5 TB/s and what it slows is the latency-bound chains beside it, wherever it rides); the
+        // data-parallel path exports the gradient instead
         const int span0 = OFF_WF1 / 4, span1 = p.apply_adam ? (OFF_WF1 + 1600 * FC) / 4 : span0;
-        // ... in two parts: [span0, spanm) beside the conv data-gradient chain, [spanm, span1) beside the conv weight gradients
-        // (measured, profiles/r03_notes.md: any split costs the same ~3.5 us in all -- the span is HBM traffic at ~6.5 TB/s and what it slows
-        // is the latency-bound chains beside it, wherever it rides -- so the default stays "all of it beside the data-gradient chain")
-        static const int span_pct = getenv("FB_SPAN_SPLIT") ? atoi(getenv("FB_SPAN_SPLIT")) : 100;     // tuning knob: per cent of the span in the first launch
-        const int spanm = span0 + (int)(((long long)(span1 - span0) * span_pct / 100) & ~511LL);
-        const AdamSpan span{master(h, 0), h->adam_m, h->adam_v, G, h->adam, span0, spanm};
-        const AdamSpan span_b{master(h, 0), h->adam_m, h->adam_v, G, h->adam, spanm, span1};
+        const AdamSpan span{master(h, 0), h->adam_m, h->adam_v, G, h->adam, span0, span1};
         // split schedule: the fc1 backward launch has waited for the acting trunk on the other stream (its gate workgroup), so W_fc1's Adam
         // span may ride in the launches below; the last of them waits for that stream's fc1 launch, so the Adam launch may follow
         FbGate gate_fc1{nullptr, 0, nullptr};
@@ -4230,16 +4195,14 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             const bool fold1 = 2 * B > h->zmax;
             const int fold = (2 * B + h->zmax - 1) / h->zmax;
             z1 = fold1 ? (2 * B + fold - 1) / fold : 2 * B;
-            static const int span_cap = getenv("FB_SPAN_BLOCKS") ? atoi(getenv("FB_SPAN_BLOCKS")) : 1 << 30;      // tuning knob: at most this many span workgroups per launch (grid-stride)
-            const int n_adam5 = min(span_cap, (spanm - span0 + 511) / 512), n_adam5b = min(span_cap, (span1 - spanm + 511) / 512);
+            const int n_adam5 = (span1 - span0 + 511) / 512;
             const BxArgs bx{h->dh3, h->h2, h->p1, h->dh2, h->dp1, h->wsp[0] + wsp_w3t(FC), h->wsp[0] + wsp_w2t(FC)};
             // large batches (multiples of 16): conv3's and conv2's weight gradients per group of 16 samples in a launch of their own
             // (conv_dwg_kernel) instead of as 38 + 34 tiles per slab inside the two launches below; one slab per group
             const bool dwg = big && B % 16 == 0;
             const int zt3 = dwg ? 0 : z3, zt2 = zt3;
             // small batches: the whole conv backward per sample in ONE launch (conv_bw_kernel); one conv2 / conv3 slab per sample
-            static const bool bw_on = !(getenv("FB_BW_MERGED") && atoi(getenv("FB_BW_MERGED")) == 0);      // A/B knob: 0 = the two-launch form
-            const bool bw = bw_on && fk && B <= h->zmax;
+            const bool bw = fk && B <= h->zmax;
             // split schedule: W_fc1's Adam span rides in the next launch, and the acting trunk running beside this step on another stream
             // re-splits W_fc1's planes from those very parameters in its first microseconds
 
@@ -4249,15 +4212,13 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
                     const Dw1Ring dr{p.ring ? p.ring->c.bits : nullptr, h->ring_fo};
                     float *s1 = fold1 ? h->slabs1 : h->slabs;
                     const size_t st1 = fold1 ? (size_t)CONV1_PARAMS : ss;
-                    const dim3 g(BW_WGS * B + n_adam5 + n_adam5b + (srider.k ? 1 : 0) + (gate_fc1.flag ? 1 : 0));
-                    const AdamSpan span_all{master(h, 0), h->adam_m, h->adam_v, G, h->adam, span0, span1};
-                    const int n_ad = n_adam5 + n_adam5b;
+                    const dim3 g(BW_WGS * B + n_adam5 + (srider.k ? 1 : 0) + (gate_fc1.flag ? 1 : 0));
                     if (h->nsplit_train == 3) {
-                        if (p.ring) hipLaunchKernelGGL((conv_bw_kernel<3, true>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_ad, span_all, srider, rbt, gate_fc1);
-                        else hipLaunchKernelGGL((conv_bw_kernel<3, false>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_ad, span_all, srider, rbt, gate_fc1);
+                        if (p.ring) hipLaunchKernelGGL((conv_bw_kernel<3, true>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
+                        else hipLaunchKernelGGL((conv_bw_kernel<3, false>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
                     } else {
-                        if (p.ring) hipLaunchKernelGGL((conv_bw_kernel<1, true>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_ad, span_all, srider, rbt, gate_fc1);
-                        else hipLaunchKernelGGL((conv_bw_kernel<1, false>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_ad, span_all, srider, rbt, gate_fc1);
+                        if (p.ring) hipLaunchKernelGGL((conv_bw_kernel<1, true>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
+                        else hipLaunchKernelGGL((conv_bw_kernel<1, false>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
                     }
                 }
                 if (fold1) FB_K(K_CONV2_BWD) hipLaunchKernelGGL(slab_fold_kernel, dim3((CONV1_PARAMS + 255) / 256, z1), dim3(256), 0, st, h->slabs1, 2 * B, fold, h->slabs, ss);
@@ -4279,8 +4240,9 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
                 const Dw1Ring dr{p.ring ? p.ring->c.bits : nullptr, h->ring_fo};
                 float *s1 = fold1 ? h->slabs1 : h->slabs;
                 const size_t st1 = fold1 ? (size_t)CONV1_PARAMS : ss;
-                if (p.ring) hipLaunchKernelGGL((conv_dw21_kernel<2, true>), dim3(34 * zt2 + 2 * B + n_adam5b + (gate_fc1.flag ? 1 : 0)), dim3(512), 0, st, zt2, B, h->p1, h->dh2, p.s, h->dp1, h->amax, h->slabs, ss, s1, st1, rbt, dr, n_adam5b, span_b, gate_fc1);
-                else hipLaunchKernelGGL((conv_dw21_kernel<2, false>), dim3(34 * zt2 + 2 * B + n_adam5b + (gate_fc1.flag ? 1 : 0)), dim3(512), 0, st, zt2, B, h->p1, h->dh2, p.s, h->dp1, h->amax, h->slabs, ss, s1, st1, rbt, dr, n_adam5b, span_b, gate_fc1);
+                const dim3 g(34 * zt2 + 2 * B + (gate_fc1.flag ? 1 : 0));
+                if (p.ring) hipLaunchKernelGGL((conv_dw21_kernel<2, true>), g, dim3(512), 0, st, zt2, B, h->p1, h->dh2, p.s, h->dp1, h->amax, h->slabs, ss, s1, st1, rbt, dr, gate_fc1);
+                else hipLaunchKernelGGL((conv_dw21_kernel<2, false>), g, dim3(512), 0, st, zt2, B, h->p1, h->dh2, p.s, h->dp1, h->amax, h->slabs, ss, s1, st1, rbt, dr, gate_fc1);
                 if (fold1) hipLaunchKernelGGL(slab_fold_kernel, dim3((CONV1_PARAMS + 255) / 256, z1), dim3(256), 0, st, h->slabs1, 2 * B, fold, h->slabs, ss);
             }
             }
@@ -4294,10 +4256,6 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
 
         if (p.apply_adam) FB_K(K_ADAM)
         {
-            FbGatherRider gr;
-            memset(&gr, 0, sizeof(gr));
-            if (p.gather_rider) gr = *p.gather_rider;
-            const int ngb = (int)(((long long)gr.B * 1600 + 255) / 256);
             AdamFused af;
             af.p = master(h, 0); af.m = h->adam_m; af.v = h->adam_v; af.g = G; af.n = h->ntot; af.ad = h->adam;
             af.slabs = h->slabs; af.slab_stride = ss; af.z1 = z1; af.z2 = z2; af.z3 = z3;
@@ -4306,7 +4264,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             af.lanes = 4;                                    // slab mode: one chunk of <= 16 slabs per lane
             af.split = p.split && only < 0 ? p.split->f : nullptr; af.split_val = p.split ? p.split->seq : 0;
             af.n_rest = (int)((nrest4 * af.lanes + 255) / 256);
-            hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest + ngb), dim3(256), 0, st, af, gr);
+            hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest), dim3(256), 0, st, af);
             noisy_materialise(h, 0, 0, false, st);
             c51d_fold(h, 0, st);
         }
@@ -4476,7 +4434,7 @@ extern "C" int fb_qnet_apply_adam(fb_qnet_t h, const float *flat_grad, void *str
     // (the update that completes a split step: its stores wait for that step's acting forward, and it does not retire before that step's env launch)
     af.split = h->split_adam_pending && h->split && h->split->tstream ? h->split->f : nullptr; af.split_val = af.split ? h->split->seq : 0;
     h->split_adam_pending = false;
-    hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest), dim3(256), 0, st, af, FbGatherRider{});
+    hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest), dim3(256), 0, st, af);
     noisy_materialise(h, 0, 0, false, st);
     c51d_fold(h, 0, st);
     FB_LAUNCH_CHECK();
@@ -4589,16 +4547,6 @@ int fb_qnet_profile_ring(fb_qnet_t h, int kernel, int reps, int algo, int B, con
     return rc;
 }
 
-int fb_qnet_train_step_rider(fb_qnet_t h, int algo, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
-                             const uint8_t *t, double gamma, float *loss, const FbSampleRider *rider, const FbGatherRider *gather,
-                             void *stream) {
-    Plan p;
-    int rc = train_plan(h, algo, B, s, a, r, s2, t, nullptr, gamma, loss, nullptr, nullptr, nullptr, &p);
-    if (rc != FB_OK) return rc;
-    p.sample_rider = rider; p.gather_rider = gather;
-    return run_plan(h, p, -1, fb_stream(stream));
-}
-
 extern "C" int fb_qnet_train_step(fb_qnet_t h, int algo, int B, const uint8_t *s, const uint8_t *a, const float *r,
                                   const uint8_t *s2, const uint8_t *t, const float *isw, double gamma, float *loss,
                                   float *abs_err, float *q_target, float *flat_grad, void *stream) {
@@ -4639,7 +4587,7 @@ extern "C" int fb_qnet_profile_kernel(fb_qnet_t h, int kernel, int reps, int alg
 extern "C" const char *fb_qnet_kernel_name(int kernel) {
     // the launches of the SMALL-batch plans (what bench.py profiles at B = 32); ids that are no launch of their own there time as ~0:
     // conv3 rides in conv23_t_kernel, head / loss in fc1_fk_kernel / fc1_bwd2_kernel, every conv weight gradient in conv_bw_kernel
-    // (batches of 65 .. 255 and FB_BW_MERGED=0 run conv_bx_kernel + conv_dw21_kernel under the same two ids)
+    // (batches of 65 .. 255 run conv_bx_kernel + conv_dw21_kernel under the same two ids)
     static const char *names[K_COUNT] = {"conv1_pool_kernel", "conv23_t_kernel", "(conv3: in conv23_t)", "fc1_fk_kernel", "head_kernel",
                                          "(loss: in fc1_bwd2)", "fc1_bwd2_kernel", "conv_bw_kernel", "(conv2 / conv1 dW: in conv_bw)",
                                          "(conv1 dW: in conv_bw)", "slab_reduce_kernel", "adam_fused_kernel"};

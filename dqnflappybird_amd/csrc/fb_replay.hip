@@ -965,8 +965,7 @@ int fb_replay_per_store_ahead(fb_replay_t h, void *stream) {
     // fork -- and nothing on the caller's stream has touched the tree since: no second fork)
     h->store_forked = !h->upd_pending;
     if (!h->upd_pending && (hipEventRecord(h->ev_fork, st) != hipSuccess || hipStreamWaitEvent(h->side, h->ev_fork, 0) != hipSuccess)) return 0;
-    if (h->per_mode == FB_PER_FAST) hipLaunchKernelGGL(per_store_fast_kernel, dim3(1), dim3(1024), 0, h->side, h->P, h->P.n_envs);
-    else hipLaunchKernelGGL(per_store_slim_kernel, dim3(1), dim3(256), 0, h->side, h->P, h->P.n_envs);     // (the shape that fits beside the acting trunk)
+    hipLaunchKernelGGL(per_store_slim_kernel, dim3(1), dim3(256), 0, h->side, h->P, h->P.n_envs);     // (the shape that fits beside the acting trunk)
     if (hipEventRecord(h->ev_store, h->side) != hipSuccess) { (void)hipStreamWaitEvent(st, h->ev_fork, 0); return 0; }
     h->store_ahead = true;
     return 1;
@@ -976,8 +975,7 @@ int fb_replay_per_store_ahead(fb_replay_t h, void *stream) {
 // the tree as that store leaves it and the memory's own generator -- nothing of the env step -- so it follows the store there and the
 // push's join covers it (ev_store is recorded again behind it).  Returns 1 when issued.
 int fb_replay_sample_ahead(fb_replay_t h, int batch, int64_t *idx, double *isw, float *isw32, void *stream) {
-    static const bool on = !(getenv("FB_PER_SAMPLE_AHEAD") && atoi(getenv("FB_PER_SAMPLE_AHEAD")) == 0);      // A/B knob
-    if (!on || !h || h->P.kind != FB_REPLAY_PER || !h->store_ahead || !idx || !isw || batch < 1 || batch > MAXB) return 0;
+    if (!h || h->P.kind != FB_REPLAY_PER || !h->store_ahead || !idx || !isw || batch < 1 || batch > MAXB) return 0;
     // the draw WRITES the caller's idx / isw buffers: it goes behind whatever the caller's stream holds so far (readers of the previous
     // step's indices) -- the store in front of it may have been issued without a fork of its own (behind a run-ahead batch_update)
     // (fb_vec_step issues it right behind the store: that store's own fork, if it made one, covers both)
@@ -1064,14 +1062,6 @@ int fb_replay_begin_push_rider(fb_replay_t h, FbPushRider *push) {
     push->act = P.act + mo; push->rew = P.rew + mo; push->term = P.term + mo;
     push->steps_dev = &P.dev->steps; push->steps_new = steps + 1;
     h->host_steps += 1;
-    return 1;
-}
-
-int fb_replay_gather_rider(fb_replay_t h, int batch, const int64_t *idx, uint8_t *s, uint8_t *s2, uint8_t *a, float *r, uint8_t *t,
-                           FbGatherRider *rider) {
-    if (!h || !idx || !s || !s2 || !a || !r || !t || batch < 1) return 0;
-    rider->c = gather_ctx(h->P); rider->steps = h->host_steps; rider->B = batch; rider->idx = (const long long *)idx;
-    rider->s = s; rider->s2 = s2; rider->a = a; rider->r = r; rider->t = t;
     return 1;
 }
 
@@ -1214,10 +1204,9 @@ int fb_replay_update_priorities_ahead(fb_replay_t h, int batch, const int64_t *i
     // Only where the acting phase it hides behind is long enough: the kernel (139 registers per lane) cannot share a CU with a workgroup of
     // the acting trunk (2 waves x 224 registers per SIMD), so it starts when the trunk's first round of workgroups retires -- 30 us in --
     // and at 1024 / 2048 envs (one / two rounds) the side stream then finishes AFTER the env step: measured 185 / 206 us per step against
-    // 164 / 196 in line; at 4096 envs (four rounds) 272 against 286.  FB_PER_UPDATE_AHEAD=0 / 1 forces the in-line / run-ahead form.
-    static const int knob = getenv("FB_PER_UPDATE_AHEAD") ? atoi(getenv("FB_PER_UPDATE_AHEAD")) : -1;
-    if (knob == 0 || !h || h->P.kind != FB_REPLAY_PER || h->per_mode != FB_PER_EXACT || !h->side || !idx || !abs_err || batch < 1 || batch > MAXB) return 0;
-    if (knob < 0 && h->P.n_envs < 4096) return 0;
+    // 164 / 196 in line; at 4096 envs (four rounds) 272 against 286.
+    if (!h || h->P.kind != FB_REPLAY_PER || h->per_mode != FB_PER_EXACT || !h->side || !idx || !abs_err || batch < 1 || batch > MAXB) return 0;
+    if (h->P.n_envs < 4096) return 0;
     if (h->store_ahead || h->upd_pending) return 0;                        // (not in the loop's order: take the ordinary path)
     if (!per_side_usable(h, stream)) return 0;
     hipStream_t st = fb_stream(stream);

@@ -21,22 +21,7 @@
  *   - one handle per GPU; handles are not thread-safe; distinct handles are
  *     independent.
  *
- * Environment variables libfbdqn.so reads (each ONCE, at the first call that consults it).  Every default is the product
- * path; the other value selects a form the tests pin to the default bit for bit (an A/B or tuning switch, never a result):
- *   FB_ACT_FUSED=0            acting forward as two launches (conv1, then conv2 + conv3) instead of the fused trunk
- *   FB_VEC_HEAD_RIDER=0       fb_vec_step: head_kernel as its own launch instead of riding in the env launch
- *   FB_VEC_SAMPLE_RIDER=0     fb_vec_step: random.sample as its own launch instead of riding in the env launch
- *   FB_VEC_SPLIT=0            fb_vec_step keeps acting + env on the caller's stream in front of the train step instead of beside it on a second stream
- *   FB_SPLIT_LAST_ROUND=0     split schedule at >= 4096 envs: the train chain starts with the draw instead of with the acting trunk's last round of workgroups
- *   FB_ACT_SPW=4              four states per workgroup of the fused acting trunk outside the split schedule (default 5)
- *   FB_VEC_RING=0             fb_vec_step trains through fb_replay_gather + fb_qnet_train_step (u8 minibatch) instead of from the ring
- *   FB_TRAIN_STEPS_GATHER=1   the same for fb_train_steps
- *   FB_BW_MERGED=0            small-batch conv backward as two launches (conv_bx, conv_dw21) instead of conv_bw_kernel
- *   FB_SPAN_SPLIT=p, FB_SPAN_BLOCKS=n   (two-launch form only) share / workgroup cap of W_fc1's Adam span in the first launch
- *   FB_PER_STORE_AHEAD=0      Memory.store's tree update in line instead of on the memory's side stream (and with it the run-ahead sample)
- *   FB_PER_SAMPLE_AHEAD=0     Memory.sample in line
- *   FB_PER_UPDATE_AHEAD=0|1   Memory.batch_update in line / on the side stream whatever the env count (default: ahead from 4096 envs on)
- *   FB_ENV_GRID_CAP=n, FB_ENV_GRID=n    env workgroups before they stride over envs
+ * Environment variables libfbdqn.so reads: diagnostics only, neither selects a code path nor changes a result:
  *   FB_ABORT_LOG=path         file the SIGABRT hook appends the native back-trace to (fb_debug_abort_backtrace)
  *   FB_SIDE_PROBE_DEBUG=1     print what the side-stream checks measured (fb_streams_concurrent, csrc/fb_common.hip) to stderr
  * The Python side reads FB_LIB (another build of this library), FB_DP_NATIVE / FB_DP_OVERLAP (which data-parallel path, dist.py).
@@ -529,8 +514,8 @@ typedef struct {
  *   fb_qnet_split_stats -> [host] steps issued that way / how many of their minibatches started beside the env step (synchronous);
  *                          FB_ERR_INVALID with the per-site counts if any wait between the chains gave up. */
 int fb_qnet_split_stats(fb_qnet_t net, int64_t *steps_host, int64_t *clean_host);
-/* Process-wide A/B switch of the above (both schedules give the same results): split = 0 keeps every later fb_vec_step on one stream,
- * 1 (the default; the environment variable FB_VEC_SPLIT=0 starts the process with 0) takes the split schedule where it applies. */
+/* Process-wide choice of the above (both schedules give the same results): split = 0 keeps every later fb_vec_step on one stream,
+ * 1 (the default) takes the split schedule where it applies. */
 int fb_vec_step_set_schedule(int split);
 int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int algo, int batch,
                 float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream);
@@ -577,10 +562,11 @@ void *fb_dist_grad_event(fb_dist_t d);
  * (bench.py config.allreduce_us) and for callers that schedule their own step. */
 int fb_dist_all_reduce(fb_dist_t d, float *buf, int64_t count, void *stream);
 
-/* n_steps x (fb_replay_sample -> fb_replay_gather -> fb_qnet_train_step) on a uniform memory in ONE call, same results: only
- * the first draw and the first gather are launches of their own, the draw of step i + 1 rides in step i's conv3 backward
- * launch and its gather in step i's Adam launch (CPython generator; other generators keep their launches).  idx: i64[2 * batch] [dev], two buffers used alternately (step i: idx + (i & 1) * batch);
- * s, s2, a, r, t, loss as in fb_qnet_train_step. */
+/* n_steps x (fb_replay_sample -> fb_replay_gather -> fb_qnet_train_step) on a uniform memory in ONE call, same results: each step
+ * trains from the replay's frame ring as fb_train_from_replay does (no gather), only the first draw is a launch of its own, and the
+ * draw of step i + 1 rides in step i's conv3 backward launch (CPython generator; other generators keep their launches).
+ * idx: i64[2 * batch] [dev], two buffers used alternately (step i: idx + (i & 1) * batch); a, r, t, loss as in fb_train_from_replay;
+ * s, s2 must not be NULL but are not written. */
 int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int batch, int n_steps, int64_t *idx, uint8_t *s, uint8_t *s2,
                    uint8_t *a, float *r, uint8_t *t, float *loss, double gamma, void *stream);
 

@@ -1,10 +1,7 @@
 """n-step returns (include/fbdqn.h fb_replay_set_n_step) on the MI355X: the n-step view of the replay ring against its one-step
 view composed in numpy (tests/test_nstep_host.py's restatement), every training path that reads it against the gathered form, the
 sampler against CPython, the oracle's gradients, and the argument checks."""
-import os
 import random
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,7 +9,6 @@ import pytest
 from tests.test_nstep_host import nstep_return
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAMMA = 0.99
 
 
@@ -438,38 +434,30 @@ def test_rejected_arguments_leave_the_memory_alone(torch_cuda):
     assert len(rep) == size + N
 
 
-_FORMS_CHILD = r"""
-import hashlib, sys
-import numpy as np, torch
-sys.path.insert(0, sys.argv[1])
-from dqnflappybird_amd.vec import QNet, TrainSteps, VecGameState, VecReplay, VecStep
-torch.cuda.set_device(0)
-h = hashlib.sha256()
-N, B = 256, 32
-env, rep, net = VecGameState(N, seed=5), VecReplay(16000, N), QNet(max_batch=N)
-rep.seed(9, "cpython"); net.init_params(3, which=0); net.init_params(4, which=1); rep.set_n_step(3, 0.99)
-env.track_state(); env.observe(); rep.reset(env.frame_bits)
-one = VecStep(env, rep, net, B, "nature", 0.99)
-for step in range(60):
-    train = step >= 5
-    a = one(0.05, seed=1, step=step, train=train)
-    h.update(a.cpu().numpy().tobytes())
-    if train:
-        h.update(one.idx.cpu().numpy().tobytes()); h.update(one.loss.cpu().numpy().tobytes())
-TrainSteps(rep, net, B, "nature", 0.99)(6)
-h.update(net.store_params().cpu().numpy().tobytes())
-print("DIGEST", h.hexdigest())
-"""
-
-
-def test_every_ab_form_gives_the_default_results_at_n3(torch_cuda):
-    """FB_VEC_RING=0 (gather + train step with Gamma), FB_TRAIN_STEPS_GATHER=1 (the gather rider in the Adam launch), FB_VEC_SAMPLE_RIDER=0
-    and FB_VEC_SPLIT=0 each give the default form's actions, indices, losses and parameters at n = 3 (one fresh process per form: the
-    library reads each variable once)"""
-    digests = {}
-    for form in ({}, {"FB_VEC_RING": "0"}, {"FB_TRAIN_STEPS_GATHER": "1"}, {"FB_VEC_SAMPLE_RIDER": "0"}, {"FB_VEC_SPLIT": "0"}):
-        env = dict(os.environ, **form)
-        p = subprocess.run([sys.executable, "-c", _FORMS_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, (form, p.returncode, p.stderr[-2000:])
-        digests[tuple(form.items())] = [l for l in p.stdout.splitlines() if l.startswith("DIGEST")][0]
-    assert len(set(digests.values())) == 1, digests
+def test_vec_step_n3_gather_and_own_draw_equal_separate_calls(torch_cuda):
+    """the one-stream forms of fb_vec_step that its input selects at n = 3 == act_nib -> frame_step -> push -> sample ->
+    train_from_replay over 40 steps: below 256 envs (64, CPython generator) the gather + train step with Gamma, with a generator that
+    cannot ride in the env launch (256 envs, philox) the draw as a launch of its own; actions, indices, a / R / done, loss, parameters"""
+    torch = torch_cuda
+    from dqnflappybird_amd.vec import VecStep, train_from_replay
+    B, steps = 32, 40
+    for N, rng in ((64, "cpython"), (256, "philox")):
+        e1, r1, n1, nib1, _ = _pipeline(N, 20000, B, "nature", 3)
+        e2, r2, n2, nib2, _ = _pipeline(N, 20000, B, "nature", 3)
+        r1.seed(9, rng); r2.seed(9, rng)
+        one = VecStep(e2, r2, n2, B, "nature", GAMMA)
+        for step in range(steps):
+            train = step >= 6
+            a1 = n1.act_nib(nib1, 0.05, seed=1, step=step)
+            e1.frame_step(a1, want_u8=False)
+            r1.push(e1.frame_bits, a1, e1.reward, e1.terminal)
+            if train:
+                idx, _ = r1.sample(B)
+                loss, a, r, t = train_from_replay(r1, n1, "nature", idx, gamma=GAMMA)
+            a2 = one(0.05, seed=1, step=step, train=train)
+            assert torch.equal(a1, a2), (N, step)
+            if train:
+                assert torch.equal(idx, one.idx) and torch.equal(loss, one.loss), (N, step)
+                assert torch.equal(a, one.a) and torch.equal(r, one.r) and torch.equal(t, one.t), (N, step)
+        assert torch.equal(n1.store_params(), n2.store_params()) and (e1.get_state() == e2.get_state()).all(), N
+        assert n2.split_stats()[0] == 0, N                   # (neither input takes the split schedule)

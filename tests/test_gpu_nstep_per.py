@@ -2,9 +2,6 @@
 tree of an n = 1 memory two pushes behind (and the reference's SumTree driven with the lagged stores), every leaf reads the transition
 the header names with its n-step return (a numpy restatement over the recorded pushes), the ring-fed train step and fb_vec_step equal
 the separate calls, the state blob and VecBrain checkpoints continue bit for bit, and every refusal leaves the memory as it was."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -12,7 +9,6 @@ import pytest
 from tests.test_nstep_host import nstep_return
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAMMA = 0.99
 
 
@@ -304,44 +300,6 @@ def test_vec_step_per_n3_equals_separate_calls(torch_cuda, N, mode):
     assert r2.population == cap                             # the tree has wrapped
     assert (e1.get_state() == e2.get_state()).all() and torch.equal(n1.store_params(), n2.store_params())
     assert np.array_equal(np.asarray(r1.state_blob()), np.asarray(r2.state_blob()))
-
-
-_FORMS_CHILD = r"""
-import hashlib, sys
-import numpy as np, torch
-sys.path.insert(0, sys.argv[1])
-from dqnflappybird_amd.vec import QNet, VecGameState, VecReplay, VecStep
-torch.cuda.set_device(0)
-h = hashlib.sha256()
-N, B = 4096, 32
-env, net = VecGameState(N, seed=5), QNet(max_batch=N)
-rep = VecReplay(6 * N + 13, N, prioritized=True, n_step=3, gamma=0.99)
-rep.seed(9, "numpy"); net.init_params(3, which=0); net.init_params(4, which=1)
-env.track_state(); env.observe(); rep.reset(env.frame_bits)
-one = VecStep(env, rep, net, B, "per", 0.99)
-for step in range(14):
-    train = step >= 2
-    a = one(0.05, seed=1, step=step, train=train)
-    h.update(a.cpu().numpy().tobytes())
-    if train:
-        for x in (one.idx, one.isw, one.loss, one.abs_err):
-            h.update(x.cpu().numpy().tobytes())
-h.update(net.store_params().cpu().numpy().tobytes())
-h.update(np.asarray(rep.state_blob()).tobytes())
-print("DIGEST", h.hexdigest())
-"""
-
-
-def test_every_per_ab_form_gives_the_default_results_at_n3(torch_cuda):
-    """FB_PER_STORE_AHEAD=0, FB_PER_SAMPLE_AHEAD=0 and FB_PER_UPDATE_AHEAD=0 / 1 each give the default form's actions, indices, weights,
-    losses, |TD errors|, parameters and state blob at n = 3 and 4096 envs (one fresh process per form, under a time limit)"""
-    digests = {}
-    for form in ({}, {"FB_PER_STORE_AHEAD": "0"}, {"FB_PER_SAMPLE_AHEAD": "0"}, {"FB_PER_UPDATE_AHEAD": "0"}, {"FB_PER_UPDATE_AHEAD": "1"}):
-        env = dict(os.environ, **form)
-        p = subprocess.run([sys.executable, "-c", _FORMS_CHILD, ROOT], env=env, capture_output=True, text=True, timeout=300)
-        assert p.returncode == 0, (form, p.returncode, p.stderr[-2000:])
-        digests[tuple(form.items())] = [l for l in p.stdout.splitlines() if l.startswith("DIGEST")][0]
-    assert len(set(digests.values())) == 1, digests
 
 
 def test_state_blob_round_trip_and_refusals(torch_cuda):
