@@ -11,6 +11,8 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
                                                                                        without noisy nets)
     python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy   (full Rainbow: noisy fc1 and head
                                                                                        layers, epsilon 0; --noisy takes any C51 model)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy --acting-noise env
+                                                                                      (... acting with independent noise per env)
 
 `actorcritic` / `policygradient` are out of scope (broken in the reference).
 """
@@ -77,7 +79,11 @@ def main():
     parser.add_argument("--vec", type=int, default=0, help="run N vectorised envs (device-resident loop)")
     parser.add_argument("--n-step", type=int, default=1, help="learn from K-step returns (--vec, uniform replay; 1 = the reference's one-step TD)")
     parser.add_argument("--noisy", action="store_true", help="noisy fc1 and head layers, epsilon 0 (--model c51 | c51per | c51doubleper | rainbow, --vec)")
+    parser.add_argument("--acting-noise", choices=("shared", "env"), default="shared",
+                        help="--noisy: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
     args = parser.parse_args()
+    if args.acting_noise != "shared" and not args.noisy:      # (refused before anything touches the GPU)
+        parser.error(f"--acting-noise {args.acting_noise} needs --noisy")
     if args.noisy:                                       # (refused before anything touches the GPU)
         if args.model not in ("c51", "c51per", "c51doubleper", "rainbow"):
             parser.error(f"--noisy needs a C51 model (c51, c51per, c51doubleper, rainbow), not --model {args.model}")
@@ -104,7 +110,8 @@ def main():
         algo = {"dqn": "dqn", "ddqn": "nature", "dqnnature": "nature", "duelingdqn": "nature", "prioritydqn": "per", "c51": "c51",
                 "c51per": "c51per", "c51doubleper": "c51doubleper", "rainbow": "c51doubleper"}[args.model]
         arch = "c51dueling" if args.model == "rainbow" else "plain"      # rainbow: dueling C51 head, double target, prioritized replay
-        vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step, noisy=args.noisy)
+        vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step, noisy=args.noisy,
+                      acting_noise=args.acting_noise)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)
     else:
         playFlappyBird(args.model, args.steps, verbose=not args.quiet)

@@ -21,6 +21,7 @@ ALGO_C51, ALGO_C51_DOUBLE = 5, 6
 ALGO_C51_PER, ALGO_C51_DOUBLE_PER = 7, 8                # C51 with prioritized replay (include/fbdqn.h)
 C51_MAX_ATOMS = 64                                    # include/fbdqn.h FB_C51_MAX_ATOMS
 NOISE_SAMPLE, NOISE_MEAN = 0, 1                       # include/fbdqn.h FB_NOISE_* (fb_qnet_reset_noise)
+ACT_NOISE_SHARED, ACT_NOISE_PER_ENV = 0, 1            # include/fbdqn.h FB_ACT_NOISE_* (fb_qnet_set_acting_noise)
 DTYPE_F32, DTYPE_BF16 = 0, 1
 PER_EXACT, PER_FAST = 0, 1
 NIB_PITCH, NIB_ROWS, NIB_STRIDE = 44, 84, 3712       # include/fbdqn.h FB_NIB_*
@@ -75,6 +76,8 @@ SIGNATURES = {
     "fb_qnet_is_noisy": [_vp],
     "fb_qnet_reset_noise": [_vp, _i, _u64, _u64, _i, _vp],
     "fb_qnet_get_noise": [_vp, _i, _vp],
+    "fb_qnet_set_acting_noise": [_vp, _i],
+    "fb_qnet_act_nib_env_noise": [_vp, _vp, _i, _f, _u64, _u64, _vp, _vp, _vp],
     "fb_qnet_get_support": [_vp] * 4,
     "fb_qnet_forward_dist": [_vp, _i, _vp, _i, _vp, _vp],
     "fb_qnet_destroy": [_vp],

@@ -75,6 +75,7 @@ __device__ __forceinline__ void fb_flag_wait(const unsigned long long *flag, uns
 #define FB_STREAM_INIT 4u     // truncated-normal weight init
 #define FB_STREAM_EVAL 5u     // epsilon-greedy of fb_eval_run, counter = (env id, eval step): never the training acting stream
 #define FB_STREAM_NOISE 6u    // noisy nets' factorised noise, counter = (element, step_lo, 6, 2 step_hi + net) (fb_qnet_reset_noise)
+#define FB_STREAM_ENV_NOISE 7u  // per-env acting noise of noisy nets, counter = (env * nz + element, step_lo, 7, step_hi) (fb_qnet_act_nib_env_noise)
 
 struct fb_u4 { uint32_t x, y, z, w; };
 
@@ -207,6 +208,13 @@ void *fb_qnet_take_grad_event_recorded(fb_qnet_t h);
 // argument checks fb_vec_step makes BEFORE any counter moves or any launch goes out (0 = fine, else the error code with
 // fb_last_error set): the batch the train step would reject / the env count the acting forward would reject
 int fb_qnet_check_step(fb_qnet_t h, int n_envs, int train_batch);
+// noisy nets' acting noise (include/fbdqn.h): the mode fb_qnet_set_acting_noise set (FB_ACT_NOISE_SHARED for any other net); the checks
+// fb_qnet_act_nib_env_noise makes for n states (FB_OK, else the error code with fb_last_error set); that call without its final restore of
+// the online net's effective parameters (fb_vec_step: the fb_qnet_reset_noise(0) behind it rebuilds them anyway)
+int fb_qnet_acting_noise(fb_qnet_t h);
+int fb_qnet_check_env_noise(fb_qnet_t h, int n, const char *who);
+int fb_qnet_act_nib_env_noise_keep(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
+                                   uint8_t *actions, float *q, void *stream);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);

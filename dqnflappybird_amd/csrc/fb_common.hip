@@ -275,7 +275,14 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // a noisy net: the online net's noise of this step, drawn before acting (acting and the train step below share it); the target net's
     // is drawn in front of the train step (target_noise)
     const bool noisy = fb_qnet_is_noisy(net) != 0;
-    if (noisy) {
+    // (per-env acting noise: the acting forward draws its own noise per env from mu and sigma; the online sample of this step is drawn
+    // behind the env step instead, and the train step reads it as in the shared mode)
+    const bool env_noise = noisy && fb_qnet_acting_noise(net) == FB_ACT_NOISE_PER_ENV;
+    if (env_noise) {
+        const int rc0 = fb_qnet_check_env_noise(net, n_envs, "fb_vec_step");
+        if (rc0 != FB_OK) return rc0;
+    }
+    if (noisy && !env_noise) {
         const int rc0 = fb_qnet_reset_noise(net, 0, seed, step, FB_NOISE_SAMPLE, stream);
         if (rc0 != FB_OK) return rc0;
     }
@@ -355,7 +362,8 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     FbHeadRider hrider;
     const int have_h = fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 && !fb_qnet_is_c51(net);      // (C51: its own launch)
     int rc = have_h ? fb_qnet_act_nib_rider(net, b->nib, n_envs, epsilon, seed, step, b->actions, &hrider, stream)
-                    : fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
+             : env_noise ? fb_qnet_act_nib_env_noise_keep(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream)
+                         : fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
     if (rc != FB_OK) return rc;
     // Riders of the env launch (uniform memory): random.sample of this step -- it only needs the size the memory will have
     // after the push, not the frames -- and the push itself: every env workgroup stores its transition straight into the
@@ -374,6 +382,8 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
         rc = fb_replay_finish_push(replay, stream);      // (prioritized memory: the tree part of the push the env launch carried)
         if (rc == FB_OK && train && !have_s && !per) rc = fb_replay_sample(replay, batch, nullptr, b->idx, nullptr, stream);
     }
+    // per-env acting noise: the online net's sample of this step (it also rebuilds the effective parameters the acting forward left at mu)
+    if (rc == FB_OK && env_noise) rc = fb_qnet_reset_noise(net, 0, seed, step, FB_NOISE_SAMPLE, stream);
     if (rc != FB_OK || !train) return rc;
     if (per) {
         // BrainPrioritizedReplyDQN.py:277-329 from the sample on: importance weights -> weighted loss -> |TD errors| back into the tree

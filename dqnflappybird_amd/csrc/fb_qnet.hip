@@ -1858,6 +1858,169 @@ __global__ __launch_bounds__(256) void noisy_sigma_init_kernel(float *__restrict
     p[N.n + q - OFF_WF1] = noisy_layer(N, q).sig;
 }
 
+// ---- per-env acting noise (fb_qnet_act_nib_env_noise, include/fbdqn.h): env e acts through mu + sigma (.) (f(eps_out_e) x f(eps_in_e))
+// on fc1 and every head layer.  The mu part is the acting forward as it stands (mu materialised into params[0] for the call); what the
+// noise adds: fc1's sigma term t[e][j] = sum_k sigma_W[k][j] f(eps_in_e,k) x[e][k] as a second fc1_sp_kernel launch over split planes of
+// sigma_W_fc1 and of the scaled activations x (.) f(eps_in_e), and per-env noisy head logits (env_noise_head_kernel).
+// Element k of env e at (seed, step): noise_draw_kernel's u1 / u2 / z / f(z) from Philox(key = seed, counter = (e nz + k, step_lo,
+// FB_STREAM_ENV_NOISE, step_hi)).
+__device__ __forceinline__ float env_noise_f(uint32_t seed_lo, uint32_t seed_hi, uint32_t c0, uint32_t step_lo, uint32_t step_hi) {
+    const fb_u4 r = fb_philox(seed_lo, seed_hi, c0, step_lo, FB_STREAM_ENV_NOISE, step_hi);
+    const float u1 = ((r.x >> 8) + 1) * (1.0f / 16777216.0f), u2 = (r.y >> 8) * (1.0f / 16777216.0f);
+    const float z = sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+    return copysignf(sqrtf(fabsf(z)), z);
+}
+
+// sigma_W_fc1 (sig: a base with sig + OFF_WF1 = sigma_W_fc1) into W_fc1's plane layout at wsp + WSP_WF1 (wsplit_item's fc1 items), unless
+// *seen says they were built at the current Adam count (AdamDev::applies: every Adam update of the online net moves it; init / load
+// reset *seen).  env_noise_scale_kernel, the next launch, records the count
+__global__ __launch_bounds__(256) void env_noise_sigsplit_kernel(const float *__restrict__ sig, uint4 *__restrict__ wsp, int FC, const AdamDev *ad,
+                                                                const int *seen) {
+    if (*seen == ad->applies) return;
+    const int id = blockIdx.x * 256 + threadIdx.x;
+    if (id < 200 * FC) wsplit_item(sig, wsp, FC, IT_CONV + id);
+}
+
+// x (.) f(eps_in_e) of fc1 for every (env e < n, k < 1600), split as two fp16 planes ([plane][e][1600], plane stride pl) for
+// fc1_sp_kernel.  x: conv3's output, from its two planes a3 (>= 256 states) or in fp32 from h3.  Two k per thread
+struct EnvScale { const uint16_t *a3; const float *h3; size_t pl; uint16_t *out; int n, nz; uint32_t seed_lo, seed_hi, step_lo, step_hi;
+                  const AdamDev *ad; int *seen; unsigned *ovf; };
+__global__ __launch_bounds__(256) void env_noise_scale_kernel(EnvScale a) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.seen = a.ad->applies;
+    const int id = blockIdx.x * 256 + threadIdx.x, e = min(id / 800, a.n - 1), k = 2 * (id - (id / 800) * 800);
+    const bool on = id < a.n * 800;
+    const size_t o = (size_t)e * 1600 + k;
+    float x0, x1;
+    if (a.a3) {
+        const uint32_t hi = *reinterpret_cast<const uint32_t *>(a.a3 + o), lo = *reinterpret_cast<const uint32_t *>(a.a3 + a.pl + o);
+        const f32x2 h = __builtin_convertvector(__builtin_bit_cast(f16x2, hi), f32x2), l = __builtin_convertvector(__builtin_bit_cast(f16x2, lo), f32x2);
+        x0 = fmaf(l.x, F16_LO_UNSCALE, h.x); x1 = fmaf(l.y, F16_LO_UNSCALE, h.y);
+    } else { x0 = a.h3[o]; x1 = a.h3[o + 1]; }
+    const uint32_t c = (uint32_t)e * (uint32_t)a.nz + (uint32_t)k;
+    const float y0 = x0 * env_noise_f(a.seed_lo, a.seed_hi, c, a.step_lo, a.step_hi), y1 = x1 * env_noise_f(a.seed_lo, a.seed_hi, c + 1u, a.step_lo, a.step_hi);
+    uint32_t hi, lo;
+    split2x2(y0, y1, hi, lo);
+    if (on) { *reinterpret_cast<uint32_t *>(a.out + o) = hi; *reinterpret_cast<uint32_t *>(a.out + a.pl + o) = lo; }
+    note_overflow(on && out_of_f16_range(y0, y1, 0.f, 0.f), a.ovf);
+}
+
+// the per-env noisy head: one wave per env, c51_head_one's layout (lane i = atom i of every action).  h_j = relu((mu partials + b_j) +
+// f(eps_out_j) (t_j + sigma_b_j)); the mu logits exactly as c51_logits forms them (P, hoff: the folded head for dueling C51), then each
+// head layer's noise term f(eps_out_o) (sum_j sigma_W[j][o] f(eps_in_j) h_j + sigma_b_o) -- dueling C51: V_n + A_n - mean_a A_n per atom --
+// added after it; softmax, Q, argmax and epsilon as c51_head_one.  sig: sigma of mu entry q at sig[q] (off: the net's own layout).
+struct EnvNoiseHead {
+    const float *hf, *ht; int stot, nks;     // mu fc1 partials [nks][stot][FC], sigma's t partials [FC1_SP_KS][stot][FC]
+    const float *P; NetOff hoff; const float *sig; NetOff off; NoisyNet N;
+    int n, FC, A; C51Sup sup; float *q; uint8_t *actions; float epsilon; uint32_t seed_lo, seed_hi, step_lo, step_hi;
+    const int32_t *key_of; uint32_t stream;  // epsilon counter and noise: key_of[row] (or the row), epsilon on `stream`
+};
+// Eight envs per workgroup, one wave each.  The head's weights are the same for every env: the workgroup stages KC rows of the mu
+// head, of sigma's Q / advantage layer and (dueling) of sigma's V layer in LDS at a time -- coalesced loads, one round trip per stage --
+// and each wave runs its FMA chains from there (a wave that reads the rows from global memory itself waits on a round trip every few k)
+constexpr int ENH_WAVES = 8;
+template <int AT> struct EnhLds { static constexpr int KC = AT == 2 ? 64 : 16, PER = (KC * AT * 64 + 511) / 512, PERV = (KC * 64 + 511) / 512; };
+template <int AT, bool DUEL>
+__global__ __launch_bounds__(64 * ENH_WAVES) void env_noise_head_kernel(EnvNoiseHead H) {
+    constexpr int KC = EnhLds<AT>::KC, PER = EnhLds<AT>::PER, PERV = EnhLds<AT>::PERV, WQ = KC * AT * 64;
+    __shared__ float lw[2 * WQ + (DUEL ? KC * 64 : 0)];          // [mu rows | sigma rows | sigma V rows], row pitch AN (V: N)
+    const int tid = threadIdx.x, lane = tid & 63, row = blockIdx.x * ENH_WAVES + (tid >> 6);
+    const bool live = row < H.n;
+    const int smp = live ? row : H.n - 1;                        // (a wave past n stages and waits with the others, stores nothing)
+    const int A = AT == MAXA ? H.A : AT, N = H.sup.N, AN = A * N, il = lane < N ? lane : N - 1, FC = H.FC;
+    const bool on = lane < N;
+    const int key = H.key_of ? H.key_of[smp] : smp;
+    const uint32_t base = (uint32_t)key * (uint32_t)H.N.nz;
+    auto draw = [&](int k) { return env_noise_f(H.seed_lo, H.seed_hi, base + (uint32_t)k, H.step_lo, H.step_hi); };
+    const NoisyLayer L0 = H.N.l[0], LV = H.N.l[1], LQ = H.N.l[DUEL ? 2 : 1];      // fc1, (V,) the Q / advantage layer
+    float lg[AT], ns[AT], nv = 0.f;
+#pragma unroll
+    for (int a = 0; a < AT; a++) { lg[a] = 0.f; ns[a] = 0.f; }
+    float x = 0.f, xq = 0.f, xv = 0.f;
+    for (int k0 = 0; k0 < FC; k0 += KC) {
+        // rows k0 .. k0 + KC of the three matrices (contiguous: KC AN, KC AN, KC N floats): the loads go out first, none under a branch
+        const int cq = KC * AN, cv = KC * N;
+        const float *__restrict__ gm = H.P + H.hoff.wq + (size_t)k0 * AN, *__restrict__ gq = H.sig + H.off.wq + (size_t)k0 * AN;
+        const float *__restrict__ gv = H.sig + H.off.wv + (size_t)k0 * N;
+        float tm[PER], tq[PER], tv[DUEL ? PERV : 1];
+#pragma unroll
+        for (int r = 0; r < PER; r++) { const int i = min(tid + r * 512, cq - 1); tm[r] = gm[i]; tq[r] = gq[i]; }
+        if (DUEL) {
+#pragma unroll
+            for (int r = 0; r < PERV; r++) tv[r] = gv[min(tid + r * 512, cv - 1)];
+        }
+        if (k0 % 64 == 0) {                                       // this wave's fc1 activations of units k0 .. k0 + 63 (lane = unit)
+            const int j = k0 + lane;
+            float v = H.hf[(size_t)smp * FC + j], t[FC1_KS];            // (fc1_out's sum, before its relu)
+#pragma unroll
+            for (int ks = 1; ks < FC1_KS; ks++) {
+                const float y = H.hf[((size_t)(ks < H.nks ? ks : 0) * H.stot + smp) * FC + j];
+                t[ks] = ks < H.nks ? y : 0.f;
+            }
+#pragma unroll
+            for (int ks = 1; ks < FC1_KS; ks++) v += t[ks];
+            const float pre = v + H.P[H.hoff.bf1 + j];
+            float tt = H.ht[(size_t)smp * FC + j];
+#pragma unroll
+            for (int ks = 1; ks < FC1_SP_KS; ks++) tt += H.ht[((size_t)ks * H.stot + smp) * FC + j];
+            x = fmaxf(pre + draw(L0.eout + j) * (tt + H.sig[H.off.bf1 + j]), 0.f);
+            xq = x * draw(LQ.ein + j);
+            xv = DUEL ? x * draw(LV.ein + j) : 0.f;
+        }
+        __syncthreads();                                          // (the previous stage's rows are no longer read)
+#pragma unroll
+        for (int r = 0; r < PER; r++) { const int i = tid + r * 512; if (i < cq) { lw[i] = tm[r]; lw[WQ + i] = tq[r]; } }
+        if (DUEL) {
+#pragma unroll
+            for (int r = 0; r < PERV; r++) { const int i = tid + r * 512; if (i < cv) lw[2 * WQ + i] = tv[r]; }
+        }
+        __syncthreads();
+        const int kl = k0 % 64;                                   // (the stage's first unit among the lanes of x)
+#pragma unroll 8
+        for (int k = 0; k < KC; k++) {                            // c51_logits' order of the mu sums: unit by unit
+            const float xs = rdlane(x, kl + k), xqs = rdlane(xq, kl + k);
+#pragma unroll
+            for (int a = 0; a < AT; a++) {
+                const int o = k * AN + (a < A ? a : 0) * N + il;
+                lg[a] = fmaf(xs, lw[o], lg[a]);
+                ns[a] = fmaf(xqs, lw[WQ + o], ns[a]);
+            }
+            if (DUEL) nv = fmaf(rdlane(xv, kl + k), lw[2 * WQ + k * N + il], nv);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < AT; a++) lg[a] += H.P[H.hoff.bq + (a < A ? a : 0) * N + il];
+    float nq[AT], mean = 0.f;
+#pragma unroll
+    for (int a = 0; a < AT; a++) {
+        const int o = (a < A ? a : 0) * N + il;
+        nq[a] = draw(LQ.eout + o) * (ns[a] + H.sig[H.off.bq + o]);
+        if (a < A) mean += nq[a];
+    }
+    if (DUEL) {
+        mean /= (float)A;
+        const float vn = draw(LV.eout + il) * (nv + H.sig[H.off.bv + il]);
+#pragma unroll
+        for (int a = 0; a < AT; a++) lg[a] += (vn + nq[a]) - mean;
+    } else {
+#pragma unroll
+        for (int a = 0; a < AT; a++) lg[a] += nq[a];
+    }
+    float qv[AT];
+    const float z = H.sup.vmin + (float)(on ? lane : 0) * H.sup.dz;
+    c51_q<AT>(lg, on, z, qv);
+    if (lane == 0 && live) {                                      // (c51_head_one's)
+#pragma unroll
+        for (int a = 0; a < AT; a++) if (a < A) H.q[(size_t)smp * A + a] = qv[a];
+        int best = 0;
+#pragma unroll
+        for (int a = 1; a < AT; a++) if (a < A && qv[a] > qv[best]) best = a;
+        const fb_u4 o = fb_philox(H.seed_lo, H.seed_hi, (uint32_t)key, H.step_lo, H.stream, H.step_hi);
+        const float u = (float)(o.x >> 8) * (1.0f / 16777216.0f);
+        if (u <= H.epsilon) best = (int)(((unsigned long long)o.y * (unsigned)A) >> 32);
+        H.actions[smp] = (uint8_t)best;
+    }
+}
+
 // ================================================================== fc1 + loss, small batches (training, < 256 states)
 // fc1 with the WHOLE reduction in one workgroup.  Round 1's fc1_kernel split K = 1600 over 5 workgroups, which leaves five partial
 // sums per unit that only a further launch can add up -- so Q (and with it the loss and every gradient) sat two launches
@@ -3566,6 +3729,14 @@ struct fb_qnet {
     long long ntot;
     NoisyNet nnet;
     float *mst[2], *nz[2];
+    // per-env acting noise (fb_qnet_act_nib_env_noise; noisy nets only): the mode fb_vec_step acts in (FB_ACT_NOISE_*); nz_zero: a zero
+    // noise vector (mu materialised for the call); wsig: sigma_W_fc1 as W_fc1's planes (wsig + WSP_WF1), built at the Adam count *sig_seen;
+    // a3n: the scaled activations' planes (a3s's shape); ht: sigma's fc1 partials (hf_act's shape)
+    int act_noise;
+    float *nz_zero, *ht;
+    uint4 *wsig;
+    uint16_t *a3n;
+    int *sig_seen;
     bool split_adam_pending;         // a split step exported its gradient: the fb_qnet_apply_adam that completes it takes over the Adam launch's waits
 };
 
@@ -3609,6 +3780,10 @@ static void noisy_materialise(fb_qnet *h, int which, int q0, bool bump, hipStrea
     if (!h->noisy) return;
     const NoisyMat a{h->mst[which], h->params[which], h->nz[which], h->nnet, q0, which, bump ? h->adam : nullptr};
     hipLaunchKernelGGL(noisy_mat_kernel, dim3((unsigned)((h->n - q0 + 255) / 256)), dim3(256), 0, st, a);
+}
+// a noisy net whose online sigma the host replaced (init / load): the per-env acting path's sigma_W_fc1 planes are stale
+static void env_noise_invalidate(fb_qnet *h, int which, hipStream_t st) {
+    if (h->noisy && which == 0) (void)hipMemsetD32Async((hipDeviceptr_t)h->sig_seen, -1, 1, st);
 }
 // a noisy net: sigma's gradient into g[n ..) from the effective parameters' gradient in g[OFF_WF1, n)
 static void noisy_sgrad(fb_qnet *h, float *g, hipStream_t st) {
@@ -3696,6 +3871,14 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     alloc((void **)&h->params[0], nb); alloc((void **)&h->params[1], nb);
     alloc((void **)&h->adam_m, nbt); alloc((void **)&h->adam_v, nbt); alloc((void **)&h->grad, nbt);
     if (h->noisy) for (int w = 0; w < 2; w++) { alloc((void **)&h->mst[w], nbt); alloc((void **)&h->nz[w], sizeof(float) * (size_t)h->nnet.nz); }      // (zero noise: mean mode)
+    if (h->noisy) {
+        alloc((void **)&h->nz_zero, sizeof(float) * (size_t)h->nnet.nz);
+        alloc((void **)&h->wsig, sizeof(uint4) * (size_t)wsp_w3t(fc_width));
+        alloc((void **)&h->a3n, S * 1600 * 6 + 256);
+        alloc((void **)&h->ht, S * fc_width * 4 * FC1_SP_KS);
+        alloc((void **)&h->sig_seen, sizeof(int));
+        if (e == hipSuccess) e = hipMemset(h->sig_seen, 0xff, sizeof(int));      // (no planes yet)
+    }
     alloc((void **)&h->slabs, sizeof(float) * (size_t)h->zmax * CONV_PARAMS);
     if (2 * max_batch > h->zmax) alloc((void **)&h->slabs1, sizeof(float) * (size_t)2 * (max_batch < MAXTB ? max_batch : MAXTB) * CONV1_PARAMS);      // two sub-slabs per sample
     alloc((void **)&h->adam, sizeof(AdamDev));
@@ -3735,7 +3918,8 @@ extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     if (!h) return FB_OK;
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
                     h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
-                    h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1]};
+                    h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1],
+                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -3864,6 +4048,7 @@ extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *
     if (h->noisy)                                // (mu as the plain net's, then sigma0 / sqrt(fan_in))
         hipLaunchKernelGGL(noisy_sigma_init_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, fb_stream(stream), h->mst[which], h->nnet);
     noisy_materialise(h, which, 0, false, fb_stream(stream));
+    env_noise_invalidate(h, which, fb_stream(stream));
     c51d_fold(h, which, fb_stream(stream));
     hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, fb_stream(stream), h->params[which], h->w1s[which], &h->adam->pver[which]);
     resplit_now(h, which, fb_stream(stream));
@@ -3875,6 +4060,7 @@ extern "C" int fb_qnet_load_params(fb_qnet_t h, int which, const float *flat, vo
     FB_REQUIRE(h && flat && (which == 0 || which == 1), "fb_qnet_load_params: bad argument");
     FB_CHECK_HIP(hipMemcpyAsync(master(h, which), flat, sizeof(float) * (size_t)h->ntot, hipMemcpyDeviceToDevice, fb_stream(stream)));
     noisy_materialise(h, which, 0, false, fb_stream(stream));
+    env_noise_invalidate(h, which, fb_stream(stream));
     hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, fb_stream(stream), h->params[which], h->w1s[which], &h->adam->pver[which]);
     c51d_fold(h, which, fb_stream(stream));
     resplit_now(h, which, fb_stream(stream));
@@ -3944,6 +4130,7 @@ struct Plan {
     // depend on how many other states share the launch (the small-batch kernels below 256 states round differently)
     bool any_rows;
     float *probs;                            // C51 forward plans: the head also writes the probabilities f32[row][A][N] (fb_qnet_forward_dist)
+    bool no_head;                            // C51 forward plans: conv1 .. fc1 only (fb_qnet_act_nib_env_noise launches its own head)
 };
 
 static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
@@ -4077,7 +4264,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         fa.dueling = h->arch == FB_ARCH_DUELING; fa.stot = stot; fa.off = h->off;
         hipLaunchKernelGGL(fc1_fk_kernel, dim3((maxc + 15) / 16, h->FC / 16, p.ns), dim3(512), 0, st, fa);
     }
-    if (c51 && !p.train) FB_K(K_HEAD) {             // C51: the distributional head (stand-alone launch only; no env rider)
+    if (c51 && !p.train && !p.no_head) FB_K(K_HEAD) {             // C51: the distributional head (stand-alone launch only; no env rider)
         C51HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns; H.params = nullptr;
         for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (a dueling C51 net: its folded head)
@@ -4338,6 +4525,88 @@ extern "C" int fb_qnet_get_noise(fb_qnet_t h, int which, float *out) {
     FB_CHECK_HIP(hipDeviceSynchronize());
     FB_CHECK_HIP(hipMemcpy(out, h->nz[which], sizeof(float) * (size_t)h->nnet.nz, hipMemcpyDefault));
     return FB_OK;
+}
+
+extern "C" int fb_qnet_set_acting_noise(fb_qnet_t h, int mode) {
+    FB_REQUIRE(h, "fb_qnet_set_acting_noise: NULL handle");
+    FB_REQUIRE(h->noisy, "fb_qnet_set_acting_noise: not a noisy net (fb_qnet_create_c51_noisy)");
+    FB_REQUIRE(mode == FB_ACT_NOISE_SHARED || mode == FB_ACT_NOISE_PER_ENV,
+               "fb_qnet_set_acting_noise: mode must be FB_ACT_NOISE_SHARED or FB_ACT_NOISE_PER_ENV (got %d)", mode);
+    h->act_noise = mode;
+    return FB_OK;
+}
+int fb_qnet_acting_noise(fb_qnet_t h) { return h && h->noisy ? h->act_noise : FB_ACT_NOISE_SHARED; }
+
+int fb_qnet_check_env_noise(fb_qnet_t h, int n, const char *who) {
+    FB_REQUIRE(h, "%s: NULL handle", who);
+    FB_REQUIRE(h->noisy, "%s: per-env acting noise needs a noisy net (fb_qnet_create_c51_noisy)", who);
+    FB_REQUIRE(h->nsplit == 3, "%s: per-env acting noise takes FB_DTYPE_F32 inference only (the net is set to FB_DTYPE_BF16)", who);
+    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "%s: n %d exceeds 3*max_batch", who, n);
+    FB_REQUIRE((unsigned long long)n * (unsigned long long)h->nnet.nz < (1ull << 32), "%s: n * nz = %d * %d must stay below 2^32 (the noise counter)",
+               who, n, h->nnet.nz);
+    return FB_OK;
+}
+
+// the per-env acting forward (include/fbdqn.h): mu into params[0] (zero noise), the acting forward's conv1 .. fc1 on it, then the
+// noise: sigma_W_fc1's planes (when sigma moved), the scaled activations' planes, sigma's fc1 GEMM (fc1_sp_kernel, unchanged), the
+// per-env noisy head.  restore: rebuild params[0] (and the folded head) from the net's own sample -- the same launches that built them
+static int act_env_noise(fb_qnet *h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step, uint8_t *actions, float *q,
+                         bool restore, hipStream_t st) {
+    const NoisyMat mu{h->mst[0], h->params[0], h->nz_zero, h->nnet, OFF_WF1, 0, h->adam};
+    hipLaunchKernelGGL(noisy_mat_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, st, mu);
+    c51d_fold(h, 0, st);
+    Plan p = forward_plan(h, 0, nib_states, n);
+    p.nib = true; p.no_head = true;
+    int rc = run_plan(h, p, -1, st);
+    if (rc != FB_OK) return rc;
+    const bool sp = n >= 256;                    // (run_plan's: the fused two-plane trunk + fc1_sp_kernel, else the small-batch kernels)
+    const int FC = h->FC, stot = 3 * h->max_batch;
+    const size_t pl2 = (size_t)stot * 1600;
+    const float *sig = h->mst[0] + h->n - OFF_WF1;      // (sigma of mu entry q at sig[q])
+    hipLaunchKernelGGL(env_noise_sigsplit_kernel, dim3((unsigned)((200 * FC + 255) / 256)), dim3(256), 0, st, sig, h->wsig, FC, (const AdamDev *)h->adam,
+                       (const int *)h->sig_seen);
+    const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32), step_lo = (uint32_t)step, step_hi = (uint32_t)(step >> 32);
+    const EnvScale es{sp ? h->a3s : nullptr, sp ? nullptr : h->h3, pl2, h->a3n, n, h->nnet.nz, seed_lo, seed_hi, step_lo, step_hi, h->adam,
+                      h->sig_seen, &h->adam->ovf};
+    hipLaunchKernelGGL(env_noise_scale_kernel, dim3((unsigned)(((long long)n * 800 + 255) / 256)), dim3(256), 0, st, es);
+    const Fc1Args af{h->a3n, pl2, h->zeros, h->wsig + WSP_WF1, h->ht, stot, n, FC, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
+    hipLaunchKernelGGL(fc1_sp_kernel<3>, dim3(((n + 127) / 128) * (FC / 64) * FC1_SP_KS), dim3(256), 0, st, af);
+    EnvNoiseHead H;
+    H.hf = sp ? h->hf_act : h->hf; H.ht = h->ht; H.stot = stot; H.nks = sp ? FC1_SP_KS : 1;
+    H.P = head_base(h, h->params[0]); H.hoff = h->hoff; H.sig = sig; H.off = h->off; H.N = h->nnet;
+    H.n = n; H.FC = FC; H.A = h->A; H.sup = h->sup; H.q = h->q; H.actions = actions; H.epsilon = epsilon;
+    H.seed_lo = seed_lo; H.seed_hi = seed_hi; H.step_lo = step_lo; H.step_hi = step_hi;
+    H.key_of = nullptr; H.stream = FB_STREAM_EPS;
+    const dim3 gh((n + ENH_WAVES - 1) / ENH_WAVES);
+    if (is_c51d(h)) {
+        if (h->A == 2) hipLaunchKernelGGL((env_noise_head_kernel<2, true>), gh, dim3(64 * ENH_WAVES), 0, st, H);
+        else hipLaunchKernelGGL((env_noise_head_kernel<MAXA, true>), gh, dim3(64 * ENH_WAVES), 0, st, H);
+    } else {
+        if (h->A == 2) hipLaunchKernelGGL((env_noise_head_kernel<2, false>), gh, dim3(64 * ENH_WAVES), 0, st, H);
+        else hipLaunchKernelGGL((env_noise_head_kernel<MAXA, false>), gh, dim3(64 * ENH_WAVES), 0, st, H);
+    }
+    if (restore) {
+        noisy_materialise(h, 0, OFF_WF1, true, st);
+        c51d_fold(h, 0, st);
+    }
+    FB_LAUNCH_CHECK();
+    if (q) FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)n * h->A, hipMemcpyDeviceToDevice, st));
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_act_nib_env_noise(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
+                                         uint8_t *actions, float *q, void *stream) {
+    FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib_env_noise: NULL argument");
+    const int rc = fb_qnet_check_env_noise(h, n, "fb_qnet_act_nib_env_noise");
+    if (rc != FB_OK) return rc;
+    return act_env_noise(h, nib_states, n, epsilon, seed, step, actions, q, true, fb_stream(stream));
+}
+int fb_qnet_act_nib_env_noise_keep(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
+                                   uint8_t *actions, float *q, void *stream) {
+    FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib_env_noise: NULL argument");
+    const int rc = fb_qnet_check_env_noise(h, n, "fb_qnet_act_nib_env_noise");
+    if (rc != FB_OK) return rc;
+    return act_env_noise(h, nib_states, n, epsilon, seed, step, actions, q, false, fb_stream(stream));
 }
 
 extern "C" int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host) {

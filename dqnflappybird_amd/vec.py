@@ -283,6 +283,7 @@ C51_PER_ALGOS = ("c51per", "c51doubleper")                  # C51 on a prioritiz
 PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the algos that take a prioritized memory and its importance weights
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
 C51_ARCHS = ("c51", "c51dueling")                         # distributional heads: C51, and the dueling C51 head (Rainbow's)
+ACTING_NOISE_MODES = ("shared", "env")                  # noisy nets: one noise sample for all envs when acting, or one per env
 NOISY_DEFAULT_SIGMA0 = 0.5                                # noisy nets: sigma = sigma0 / sqrt(fan_in) at init (Fortunato et al.)
 
 
@@ -340,6 +341,7 @@ class QNet:
             raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
         self.noisy = bool(noisy)
         self.sigma0 = None
+        self.acting_noise = "shared"
         if self.noisy:
             if arch not in C51_ARCHS:
                 raise ValueError(f"noisy layers are offered on the C51 heads only ({C51_ARCHS}), not arch {arch!r}")
@@ -465,6 +467,16 @@ class QNet:
         """mean mode for net `which`: zero noise"""
         self.reset_noise(which, mean=True)
 
+    def set_acting_noise(self, mode="shared"):
+        """the noise fb_vec_step acts with (fb_qnet_set_acting_noise): 'shared' -- the online net's current sample, one for all envs
+        (the default) -- or 'env': independent noise per env (act_nib_env_noise); training is the same in both"""
+        self._need_noisy("set_acting_noise")
+        if mode not in ACTING_NOISE_MODES:
+            raise ValueError(f"acting noise must be one of {ACTING_NOISE_MODES}, got {mode!r}")
+        L.check(L.lib().fb_qnet_set_acting_noise(self.h, L.ACT_NOISE_PER_ENV if mode == "env" else L.ACT_NOISE_SHARED),
+                "fb_qnet_set_acting_noise")
+        self.acting_noise = mode
+
     @property
     def noise_size(self):
         sup = self.support
@@ -533,6 +545,18 @@ class QNet:
         q = self._get(f"qa{n}", (n, self.A), torch.float32) if want_q else None
         L.check(L.lib().fb_qnet_act_nib(self.h, L.ptr(nib_states), n, float(epsilon), seed, step, L.ptr(actions), L.ptr(q),
                                         L.current_stream()), "fb_qnet_act_nib")
+        return (actions, q) if want_q else actions
+
+    def act_nib_env_noise(self, nib_states, epsilon, seed=0, step=0, want_q=False):
+        """act_nib with independent noise per env (fb_qnet_act_nib_env_noise): env e acts through mu + sigma * its own noise, drawn
+        at (seed, step); the net's own samples and parameters stay as they were"""
+        self._need_noisy("act_nib_env_noise")
+        _dev_check(nib_states)
+        n = nib_states.shape[0]
+        actions = self._get(f"act{n}", (n,), torch.uint8)
+        q = self._get(f"qa{n}", (n, self.A), torch.float32) if want_q else None
+        L.check(L.lib().fb_qnet_act_nib_env_noise(self.h, L.ptr(nib_states), n, float(epsilon), int(seed), int(step), L.ptr(actions), L.ptr(q),
+                                                  L.current_stream()), "fb_qnet_act_nib_env_noise")
         return (actions, q) if want_q else actions
 
     def train_step(self, algo, s, a, r, s2, t, isw=None, gamma=0.99, flat_grad=None, want_aux=True):

@@ -42,6 +42,7 @@ class HipVecBackend:
     c51 = True                                               # distributional nets (net(..., support=(n_atoms, v_min, v_max)))
     c51_dueling = True                                       # ... with the dueling C51 head as well (net(..., arch='c51dueling', support=...))
     c51_noisy = True                                         # ... and noisy C51 nets (net(..., support=..., noisy=True, sigma0=s))
+    acting_noise_env = True                                  # ... which can act with noise per env (net.set_acting_noise('env'))
 
     def net(self, actions, fc_width, arch, max_batch, support=None, noisy=False, sigma0=0.5):
         from .vec import QNet
@@ -127,21 +128,30 @@ class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0,
-                 noisy=False, sigma0=0.5):
+                 noisy=False, sigma0=0.5, acting_noise="shared"):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
         'c51per' / 'c51doubleper': the same with prioritized replay (importance-weighted loss, KL priorities; n_step at creation).
         arch='c51dueling' (C51 algos only): the dueling C51 head -- value and advantage distributions (include/fbdqn.h).
         noisy=True (C51 algos only): noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the exploration comes from
-        the noise, so initial_epsilon defaults to 0 (0.03 without noise, the reference's); an explicit initial_epsilon is honoured."""
+        the noise, so initial_epsilon defaults to 0 (0.03 without noise, the reference's); an explicit initial_epsilon is honoured.
+        acting_noise (noisy nets): 'shared' -- one noise sample per step for all envs -- or 'env': independent noise per env when acting
+        (include/fbdqn.h); training is the same in both, and checkpoints do not record it."""
         n_step = int(n_step)
         noisy = bool(noisy)
+        if acting_noise not in ("shared", "env"):
+            raise ValueError(f"acting_noise must be 'shared' or 'env', got {acting_noise!r}")
+        if acting_noise == "env" and not noisy:
+            raise ValueError("acting_noise='env' needs a noisy net (noisy=True)")
         if initial_epsilon is None:
             initial_epsilon = 0.0 if noisy else 0.03
         if not 1 <= n_step <= 16:
             raise ValueError(f"n_step must be in 1..16, got {n_step}")
         be = backend or HipVecBackend()
+        if acting_noise == "env" and not getattr(be, "acting_noise_env", False):
+            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no per-env acting noise (acting_noise_env): "
+                             f"acting_noise='env' needs it")
         self.support = None
         if algo in C51_ALGOS + C51_PER_ALGOS:
             from .vec import check_support
@@ -203,6 +213,9 @@ class VecBrain:
             self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support, noisy=True, sigma0=self.sigma0)
         else:
             self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support) if self.support else be.net(2, fc_width, arch, max(n_envs, batch))
+        self.acting_noise = acting_noise
+        if acting_noise == "env":
+            self.net.set_acting_noise("env")                 # (fb_vec_step reads it: act with per-env noise, draw the online sample after)
         self.net.init_params(seed=seed, which=0)             # the same draw on every rank
         self.net.init_params(seed=seed + 1, which=1)
         if world > 1:                                        # replicas start from rank 0's parameters, bit for bit

@@ -378,6 +378,32 @@ int fb_qnet_create_c51_noisy(int arch, int fc_width, int n_actions, int n_atoms,
 int fb_qnet_is_noisy(fb_qnet_t h);                                                      /* 1: a noisy net, 0: not (or NULL) */
 int fb_qnet_reset_noise(fb_qnet_t h, int which, uint64_t seed, uint64_t step, int mode, void *stream);
 int fb_qnet_get_noise(fb_qnet_t h, int which, float *out);
+/* Per-env acting noise (noisy nets only).  The default, FB_ACT_NOISE_SHARED, is the behaviour above: acting reads the online net's
+ * current sample, one for all envs.  FB_ACT_NOISE_PER_ENV draws independent noise per env when acting; training is the same in both modes.
+ *   acting      for env (row) e, Q comes from the weights mu + sigma (.) (f(eps_out_e) x f(eps_in_e)) on fc1 and on every head layer (W_fc2 b
+ *               for C51; W_v b_v and W_a b_a, separately, for dueling C51), the layer formula, f, the per-layer order (f(eps_in)[fan_in] then
+ *               f(eps_out)[fan_out]) and nz of the shared sample; the conv trunk stays deterministic.  Softmax, Q, argmax (first maximum) and
+ *               epsilon (the same FB_STREAM_EPS draws) are the C51 head's.
+ *   draw        element k of env e at (seed, step): z and f(z) formed as FB_NOISE_SAMPLE's from r = Philox4x32-10(key = (seed_lo, seed_hi),
+ *               counter = (e nz + k, step_lo, FB_STREAM_ENV_NOISE = 7, step_hi)); the online net only (no target-net draws).  n nz >= 2^32
+ *               is refused (more than ~1.3 M envs).
+ *   mu, sigma   from the master vector [mu | sigma].  The call never reads the net's current sample and leaves both nets' samples,
+ *               effective vectors, folded heads, parameters and Adam state as they were.
+ *   where       each noise term is added after the mu sum it perturbs: fc1 unit j = relu((sum of the mu partials + b_j) + f(eps_out_j)
+ *               (t_j + sigma_b_j)), t_j = sum_k sigma_W[k][j] f(eps_in_k) x_k; a head logit = (the mu logit) + its noise term, for
+ *               dueling C51 V_n + A_n - mean_a A_n per atom.  With sigma = 0, per-env acting is acting in mean mode bit for bit.
+ *   refused     FB_ERR_INVALID before any launch or counter change: a net that is not noisy, a bad mode, per-env mode with
+ *               FB_DTYPE_BF16 inference (fb_qnet_act_nib_env_noise and fb_vec_step).
+ *   fb_qnet_act_nib_env_noise: fb_qnet_act_nib's arguments and n range (1 <= n <= 3 max_batch), q f32[n][A] or NULL.
+ *   fb_vec_step on a noisy net in FB_ACT_NOISE_PER_ENV mode: bit for bit the composed calls fb_qnet_act_nib_env_noise(seed, step) ->
+ *               env step (+ push / sample) -> reset_noise(0, FB_NOISE_SAMPLE, seed, step) -> (train != 0) reset_noise(1, ...) -> train, for
+ *               all four C51 algos, both memories, any n: the step still leaves the online sample (seed, step) in place.
+ *   fb_qnet_set_acting_noise sets the mode fb_vec_step reads (a net starts in FB_ACT_NOISE_SHARED); fb_eval_run is not affected. */
+#define FB_ACT_NOISE_SHARED 0
+#define FB_ACT_NOISE_PER_ENV 1
+int fb_qnet_set_acting_noise(fb_qnet_t h, int mode);
+int fb_qnet_act_nib_env_noise(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
+                              uint8_t *actions, float *q, void *stream);
 int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host);      /* n_atoms = 0: not a C51 net */
 int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream);
 

@@ -13,7 +13,7 @@ steps the device stats buffer (episodes ended, score sum, score max, pipes passe
 row is the window's own figure, not a running average.  Rows go to stdout and to --out as they are produced.
 --n-step K trains from K-step returns (VecBrain(n_step=K); with --algo per / c51per / c51doubleper a prioritized memory created with K-step returns); the summary gives the train steps at which the windowed mean score first
 passed 1 / 10 / 100, and --eval-envs M (> 0) ends each run with VecBrain.evaluate() on M fresh greedy games.  --noisy gives a C51 algo's
-net noisy layers (epsilon 0 unless --initial-epsilon says otherwise).
+net noisy layers (epsilon 0 unless --initial-epsilon says otherwise), and --acting-noise env makes such a net act with independent noise per env.
 """
 import argparse
 import os
@@ -28,15 +28,16 @@ from dqnflappybird_amd.vecbrain import VecBrain  # noqa: E402
 
 
 def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore, n_step=1, eval_envs=0, support=(51, -10.0, 10.0), noisy=False,
-        initial_epsilon=None):
+        initial_epsilon=None, acting_noise="shared"):
     vb = VecBrain(n_envs, algo=algo, arch=arch, capacity=1_000_000, seed=seed, explore=explore, n_step=n_step,
-                  n_atoms=support[0], v_min=support[1], v_max=support[2], noisy=noisy, initial_epsilon=initial_epsilon)
+                  n_atoms=support[0], v_min=support[1], v_max=support[2], noisy=noisy, initial_epsilon=initial_epsilon,
+                  acting_noise=acting_noise)
     vb.net.set_hparams(lr=lr)
     head = f"# envs {n_envs}  algo {algo}/{arch}  n_step {n_step}  lr {lr:g}  batch {vb.batch}  observe {vb.observe}  explore {vb.explore}  eps {vb.initial_epsilon} -> {vb.final_epsilon}  {'target never synced (PER: the reference agent never syncs it)' if algo == 'per' else f'target sync / {vb.replace_target_iter}'}"
     if vb.support:
         head += f"  support {vb.support[0]} atoms on [{vb.support[1]:g}, {vb.support[2]:g}]"
     if vb.noisy:
-        head += f"  noisy (sigma0 {vb.sigma0:g})"
+        head += f"  noisy (sigma0 {vb.sigma0:g}, acting noise {vb.acting_noise})"
     cols = "#   train_steps   env_steps  epsilon  episodes  mean_score  max_score  pipes/episode      loss   steps/s"
     for f in (sys.stdout, out):
         print(head, file=f); print(cols, file=f); f.flush()
@@ -102,6 +103,7 @@ def main():
     ap.add_argument("--budget-s", type=float, default=0.0, help="stop a run after this many seconds (0 = run all its steps)")
     ap.add_argument("--noisy", action="store_true", help="a C51 algo's net with noisy fc1 and head layers (VecBrain(noisy=True))")
     ap.add_argument("--initial-epsilon", type=float, default=None, help="the epsilon schedule's start (default: VecBrain's, 0 when --noisy)")
+    ap.add_argument("--acting-noise", choices=("shared", "env"), default="shared", help="--noisy: one noise sample per step for all envs, or per env")
     ap.add_argument("--out", default="gpurun_out/learning.txt")
     a = ap.parse_args()
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
@@ -110,7 +112,7 @@ def main():
         for n_envs in [int(x) for x in a.envs.split(",")]:
             for lr in [float(x) for x in a.lrs.split(",")]:
                 run(n_envs, lr, a.steps, a.window, a.algo, a.arch, a.seed, out, a.budget_s, a.explore, a.n_step, a.eval_envs, (a.atoms, a.vmin, a.vmax),
-                    a.noisy, a.initial_epsilon)
+                    a.noisy, a.initial_epsilon, a.acting_noise)
 
 
 if __name__ == "__main__":
