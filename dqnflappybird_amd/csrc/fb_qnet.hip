@@ -2217,10 +2217,11 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem) {
 #pragma unroll
         for (int c = 0; c <= AT; c++) {
             keep(x0[0][c]); keep(x1[0][c]); keep(x2[0][c]); keep(x0[1][c]); keep(x1[1][c]); keep(x2[1][c]);
-            const bool on = c < A || (c == A && L.dueling), on1 = on && j + 16 < ntile;
-            qsv[c] = (on ? x0[0][c] : 0.f) + (on1 ? x0[1][c] : 0.f);
-            qnv[c] = (on ? x1[0][c] : 0.f) + (on1 ? x1[1][c] : 0.f);
-            q3v[c] = (on ? x2[0][c] : 0.f) + (on1 ? x2[1][c] : 0.f);
+            // (FC = 128: 8 tiles, so lanes j >= 8 have no first share -- tc = 0 would count tile 0 again)
+            const bool on = c < A || (c == A && L.dueling), on0 = on && j < ntile, on1 = on && j + 16 < ntile;
+            qsv[c] = (on0 ? x0[0][c] : 0.f) + (on1 ? x0[1][c] : 0.f);
+            qnv[c] = (on0 ? x1[0][c] : 0.f) + (on1 ? x1[1][c] : 0.f);
+            q3v[c] = (on0 ? x2[0][c] : 0.f) + (on1 ? x2[1][c] : 0.f);
         }
         for (int tile = j + 32; tile < ntile; tile += 16) {              // FC > 512 only
             const float *q0 = L.qpart + ((size_t)bc * ntile + tile) * qs;

@@ -10,12 +10,19 @@ import pytest
 from tests.test_c51_host import np_project
 from tests.test_gpu_eval import composed as composed_eval
 from tests.test_gpu_nstep import played
-from tests.test_oracle_qnet import rand_states, torch_forward
+from tests.test_oracle_qnet import rand_states, tensor_bounds, torch_forward
 
 pytestmark = pytest.mark.gpu
 GAMMA = 0.99
 FC = 512
-HEAD0 = 77984 + 1600 * FC + FC          # W_fc2 starts here (b_fc1 ends)
+
+
+def head0(fc=FC):
+    """W_fc2's first entry (b_fc1 ends) in a net of fc1 width fc"""
+    return 77984 + 1600 * fc + fc
+
+
+HEAD0 = head0()
 
 
 @pytest.fixture(scope="module")
@@ -27,16 +34,16 @@ def torch_cuda():
     return torch
 
 
-def make_c51(N=51, vmin=-10.0, vmax=10.0, max_batch=256, seed=3, head_scale=1.0):
+def make_c51(N=51, vmin=-10.0, vmax=10.0, max_batch=256, seed=3, head_scale=1.0, A=2, fc=FC):
     """a C51 net whose ReLUs switch and whose head gives distinctly non-uniform distributions (weights x 3, as the scalar tests do;
     head_scale multiplies the C51 head further -- x 10 makes the distributions nearly one-hot, with logit gaps of tens)"""
     from dqnflappybird_amd.vec import QNet
-    net = QNet(2, FC, "c51", max_batch=max_batch, n_atoms=N, v_min=vmin, v_max=vmax)
+    net = QNet(A, fc, "c51", max_batch=max_batch, n_atoms=N, v_min=vmin, v_max=vmax)
     ps = []
     for which in (0, 1):
         net.init_params(seed + which, which)
         p = net.store_params(which).cpu().numpy() * 3.0
-        p[HEAD0:] *= head_scale
+        p[head0(fc):] *= head_scale
         net.load_params(p, which)
         ps.append(p)
     return net, ps[0], ps[1]
@@ -47,10 +54,20 @@ def support(N, vmin, vmax):
     return vmin + (vmax - vmin) / (N - 1) * torch.arange(N, dtype=torch.float64)
 
 
-def ref_logits(p, s, N):
-    """[B, 2, N] float64: the plain trunk with a 2N-column head is exactly the C51 logits"""
+def ref_logits(p, s, N, A=2, fc=FC):
+    """[B, A, N] float64: the plain trunk with an A N-column head is exactly the C51 logits"""
     import torch
-    return torch_forward(p, torch.as_tensor(s, dtype=torch.float64), FC, 2 * N).view(len(s), 2, N)
+    return torch_forward(p, torch.as_tensor(s, dtype=torch.float64), fc, A * N).view(len(s), A, N)
+
+
+def greedy_next(q, dev_astar):
+    """argmax_a q [B, A]; where the best two are within 1e-4 of each other (a tie at fp32 rounding) the device's choice dev_astar"""
+    import torch
+    astar = q.argmax(1)
+    if dev_astar is None or q.shape[1] < 2:
+        return astar
+    top = q.topk(2, 1).values
+    return torch.where((top[:, 0] - top[:, 1]).abs() < 1e-4, torch.as_tensor(dev_astar, dtype=torch.long), astar)
 
 
 def torch_project(pn, r, done, G, N, vmin, vmax):
@@ -66,26 +83,23 @@ def torch_project(pn, r, done, G, N, vmin, vmax):
     return m
 
 
-def ref_train(p_on, p_tg, s, a, r, s2, t, G, algo, N, vmin, vmax, dev_astar=None):
+def ref_train(p_on, p_tg, s, a, r, s2, t, G, algo, N, vmin, vmax, dev_astar=None, A=2, fc=FC):
     """-> (loss, flat gradient, m) in float64, with autograd; a* ties within 1e-4 take the device's choice"""
     import torch
     P = torch.tensor(p_on, dtype=torch.float64, requires_grad=True)
     z = support(N, vmin, vmax)
     B = len(s)
     with torch.no_grad():
-        pt = torch.softmax(ref_logits(torch.tensor(p_tg, dtype=torch.float64), s2, N), -1)
-        sel = torch.softmax(ref_logits(P.detach(), s2, N), -1) if algo == "c51double" else pt
+        pt = torch.softmax(ref_logits(torch.tensor(p_tg, dtype=torch.float64), s2, N, A, fc), -1)
+        sel = torch.softmax(ref_logits(P.detach(), s2, N, A, fc), -1) if algo == "c51double" else pt
         q = (sel * z).sum(-1)
-        astar = q.argmax(1)
-        if dev_astar is not None:
-            tie = (q[:, 0] - q[:, 1]).abs() < 1e-4
-            astar = torch.where(tie, torch.as_tensor(dev_astar, dtype=torch.long), astar)
+        astar = greedy_next(q, dev_astar)
         pn = pt[torch.arange(B), astar]
         rr = torch.as_tensor(r.astype(np.float64))
         dd = torch.as_tensor(t.astype(np.float64))
         m = torch_project(pn, rr, dd, G, N, vmin, vmax)
         np.testing.assert_allclose(m.numpy(), np_project(pn.numpy(), r, t, G, N, vmin, vmax), rtol=0, atol=1e-12)
-    lg = ref_logits(P, s, N)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)]
+    lg = ref_logits(P, s, N, A, fc)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)]
     loss = -(m * torch.log_softmax(lg, -1)).sum(-1).mean()
     loss.backward()
     return loss.item(), P.grad.numpy(), m.numpy()
@@ -128,11 +142,12 @@ def _batch(rng, B, ints=False):
     return s, a, r, s2, t
 
 
-def _check_grads(g, g0, n_head_cols):
+def _check_grads(g, g0, n_head_cols, fc=FC):
     """per tensor.  The head's gradients are continuous in the activations: elementwise, with the scalar tests' bounds.  The rest
     pass through ReLU / max-pool derivatives, which flip for the rare unit within rounding distance of its kink: relative L2."""
-    bounds = [0, 8192, 8224, 40992, 41056, 77920, 77984, HEAD0 - FC, HEAD0, HEAD0 + FC * n_head_cols, len(g0)]
-    for k, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:])):
+    tensors = tensor_bounds(fc, 1, "c51", n_head_cols)
+    assert tensors[-1][2] == len(g0)
+    for k, (_, lo, hi) in enumerate(tensors):
         ref, got = g0[lo:hi], g[lo:hi]
         scale = np.abs(ref).max()
         assert scale > 0, (lo, hi)

@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 
 from tests.test_c51_per_host import np_kl_priority
-from tests.test_gpu_c51 import FC, GAMMA, HEAD0, _batch, support, torch_project
+from tests.test_gpu_c51 import FC, GAMMA, HEAD0, _batch, greedy_next, head0, support, torch_project
 from tests.test_gpu_eval import composed as composed_eval
 from tests.test_gpu_nstep import played
 from tests.test_gpu_nstep_per import per_memory
-from tests.test_oracle_qnet import rand_states, torch_forward
+from tests.test_oracle_qnet import rand_states, tensor_bounds, torch_forward
 
 pytestmark = pytest.mark.gpu
 ALGOS = ("c51", "c51double", "c51per", "c51doubleper")
@@ -29,74 +29,71 @@ def torch_cuda():
     return torch
 
 
-def head_size(N, A=2):
-    return FC * N + N + FC * A * N + A * N
+def head_size(N, A=2, fc=FC):
+    return fc * N + N + fc * A * N + A * N
 
 
-def make_c51d(N=51, vmin=-10.0, vmax=10.0, max_batch=256, seed=3, head_scale=1.0):
+def make_c51d(N=51, vmin=-10.0, vmax=10.0, max_batch=256, seed=3, head_scale=1.0, A=2, fc=FC):
     """a dueling C51 net scaled as tests/test_gpu_c51.py::make_c51 scales a C51 net (weights x 3, the head x head_scale more)"""
     from dqnflappybird_amd.vec import QNet
-    net = QNet(2, FC, "c51dueling", max_batch=max_batch, n_atoms=N, v_min=vmin, v_max=vmax)
+    net = QNet(A, fc, "c51dueling", max_batch=max_batch, n_atoms=N, v_min=vmin, v_max=vmax)
     ps = []
     for which in (0, 1):
         net.init_params(seed + which, which)
         p = net.store_params(which).cpu().numpy() * 3.0
-        p[HEAD0:] *= head_scale
+        p[head0(fc):] *= head_scale
         net.load_params(p, which)
         ps.append(p)
     return net, ps[0], ps[1]
 
 
-def ref_logits_d(P, s, N, A=2):
+def ref_logits_d(P, s, N, A=2, fc=FC):
     """[B, A, N] float64: h = relu(fc1) through torch_forward's trunk (an identity head returns h itself), then the dueling head"""
     import torch
     P = torch.as_tensor(P, dtype=torch.float64)
-    ident = torch.cat([P[:HEAD0], torch.eye(FC, dtype=torch.float64).flatten(), torch.zeros(FC, dtype=torch.float64)])
-    h = torch_forward(ident, torch.as_tensor(s, dtype=torch.float64), FC, FC)
-    o = HEAD0
-    wv = P[o:o + FC * N].view(FC, N); o += FC * N
+    o = head0(fc)
+    ident = torch.cat([P[:o], torch.eye(fc, dtype=torch.float64).flatten(), torch.zeros(fc, dtype=torch.float64)])
+    h = torch_forward(ident, torch.as_tensor(s, dtype=torch.float64), fc, fc)
+    wv = P[o:o + fc * N].view(fc, N); o += fc * N
     bv = P[o:o + N]; o += N
-    wa = P[o:o + FC * A * N].view(FC, A * N); o += FC * A * N
+    wa = P[o:o + fc * A * N].view(fc, A * N); o += fc * A * N
     ba = P[o:o + A * N]
     v = h @ wv + bv
     adv = (h @ wa + ba).view(len(s), A, N)
     return v[:, None, :] + (adv - adv.mean(1, keepdim=True))
 
 
-def ref_q(p, s, N, vmin=-10.0, vmax=10.0):
+def ref_q(p, s, N, vmin=-10.0, vmax=10.0, A=2, fc=FC):
     import torch
     with torch.no_grad():
-        return (torch.softmax(ref_logits_d(p, s, N), -1) * support(N, vmin, vmax)).sum(-1).numpy()
+        return (torch.softmax(ref_logits_d(p, s, N, A, fc), -1) * support(N, vmin, vmax)).sum(-1).numpy()
 
 
-def ref_train(p_on, p_tg, s, a, r, s2, t, w, G, algo, N, vmin, vmax, dev_astar):
+def ref_train(p_on, p_tg, s, a, r, s2, t, w, G, algo, N, vmin, vmax, dev_astar, A=2, fc=FC):
     """-> (loss, flat gradient, KL per sample) in float64 with autograd; w = None: the uniform algos' mean"""
     import torch
     P = torch.tensor(p_on, dtype=torch.float64, requires_grad=True)
     z = support(N, vmin, vmax)
     B = len(s)
     with torch.no_grad():
-        pt = torch.softmax(ref_logits_d(p_tg, s2, N), -1)
-        sel = torch.softmax(ref_logits_d(P.detach(), s2, N), -1) if algo in ("c51double", "c51doubleper") else pt
+        pt = torch.softmax(ref_logits_d(p_tg, s2, N, A, fc), -1)
+        sel = torch.softmax(ref_logits_d(P.detach(), s2, N, A, fc), -1) if algo in ("c51double", "c51doubleper") else pt
         q = (sel * z).sum(-1)
-        tie = (q[:, 0] - q[:, 1]).abs() < 1e-4
-        astar = torch.where(tie, torch.as_tensor(dev_astar, dtype=torch.long), q.argmax(1))
+        astar = greedy_next(q, dev_astar)
         m = torch_project(pt[torch.arange(B), astar], torch.as_tensor(r.astype(np.float64)), torch.as_tensor(t.astype(np.float64)),
                           G, N, vmin, vmax)
-    logp = torch.log_softmax(ref_logits_d(P, s, N)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)], -1)
+    logp = torch.log_softmax(ref_logits_d(P, s, N, A, fc)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)], -1)
     ce = -(m * logp).sum(-1)
     loss = (torch.as_tensor(w, dtype=torch.float64) * ce).mean() if w is not None else ce.mean()
     loss.backward()
     return loss.item(), P.grad.numpy(), np_kl_priority(m.numpy(), logp.detach().exp().numpy())
 
 
-def check_grads(g, g0, N, A=2):
+def check_grads(g, g0, N, A=2, fc=FC):
     """tests/test_gpu_c51.py::_check_grads's tolerances, per tensor: the four head tensors elementwise, the rest relative L2"""
-    bounds = [0, 8192, 8224, 40992, 41056, 77920, 77984, HEAD0 - FC, HEAD0]
-    for k in (FC * N, N, FC * A * N, A * N):
-        bounds.append(bounds[-1] + k)
-    assert bounds[-1] == len(g0)
-    for k, (lo, hi) in enumerate(zip(bounds[:-1], bounds[1:])):
+    tensors = tensor_bounds(fc, A, "c51dueling", N)
+    assert tensors[-1][2] == len(g0)
+    for k, (_, lo, hi) in enumerate(tensors):
         ref, got = g0[lo:hi], g[lo:hi]
         scale = np.abs(ref).max()
         assert scale > 0, (lo, hi)

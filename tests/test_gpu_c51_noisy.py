@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests.test_c51_per_host import np_kl_priority
-from tests.test_gpu_c51 import FC, GAMMA, HEAD0, _batch, _check_grads, ref_logits, support, torch_project
+from tests.test_gpu_c51 import FC, GAMMA, _batch, _check_grads, greedy_next, head0, ref_logits, support, torch_project
 from tests.test_gpu_c51_dueling import check_grads as check_grads_d
 from tests.test_gpu_c51_dueling import head_size, ref_logits_d
 from tests.test_gpu_eval import composed as composed_eval
@@ -35,17 +35,17 @@ def torch_cuda():
     return torch
 
 
-def n_mu(head, N):
-    return HEAD0 + (FC * 2 * N + 2 * N if head == "c51" else head_size(N))
+def n_mu(head, N, A=2, fc=FC):
+    return head0(fc) + (fc * A * N + A * N if head == "c51" else head_size(N, A, fc))
 
 
-def layers(head, N):
+def layers(head, N, A=2, fc=FC):
     """(w, fan_in, fan_out) of the noisy layers in flat order, and their noise offsets (ein, eout)"""
-    o, out, e = HEAD0, [(TRUNK, 1600, FC)], 0
+    o, out, e = head0(fc), [(TRUNK, 1600, fc)], 0
     if head == "c51dueling":
-        out.append((o, FC, N))
-        o += FC * N + N
-    out.append((o, FC, 2 * N))
+        out.append((o, fc, N))
+        o += fc * N + N
+    out.append((o, fc, A * N))
     res = []
     for w, fi, fo in out:
         res.append((w, fi, fo, e, e + fi))
@@ -53,40 +53,40 @@ def layers(head, N):
     return res, e
 
 
-def factors(head, N, nz):
+def factors(head, N, nz, A=2, fc=FC):
     """e(q) for q in [TRUNK, n_mu): f(eps_out_j) f(eps_in_i) for a weight, f(eps_out_j) for a bias -- float64 [n_mu - TRUNK]"""
     nz = np.asarray(nz, np.float64)
     parts = []
-    for w, fi, fo, ein, eout in layers(head, N)[0]:
+    for w, fi, fo, ein, eout in layers(head, N, A, fc)[0]:
         parts += [np.outer(nz[ein:ein + fi], nz[eout:eout + fo]).ravel(), nz[eout:eout + fo]]
     e = np.concatenate(parts)
-    assert e.size == n_mu(head, N) - TRUNK
+    assert e.size == n_mu(head, N, A, fc) - TRUNK
     return e
 
 
-def factors32(head, N, nz):
+def factors32(head, N, nz, A=2, fc=FC):
     """the same products in float32, as the device forms them (f(eps_out) * f(eps_in))"""
     nz = np.asarray(nz, np.float32)
     parts = []
-    for w, fi, fo, ein, eout in layers(head, N)[0]:
+    for w, fi, fo, ein, eout in layers(head, N, A, fc)[0]:
         parts += [(nz[None, eout:eout + fo] * nz[ein:ein + fi, None]).ravel(), nz[eout:eout + fo]]
     return np.concatenate(parts)
 
 
-def effective(P, nz, head, N):
+def effective(P, nz, head, N, A=2, fc=FC):
     """float64 torch: the effective parameters mu + sigma (.) e of a master vector P = [mu | sigma] (differentiable in P)"""
     import torch
-    n = n_mu(head, N)
-    E = torch.as_tensor(factors(head, N, nz))
+    n = n_mu(head, N, A, fc)
+    E = torch.as_tensor(factors(head, N, nz, A, fc))
     P = torch.as_tensor(P, dtype=torch.float64)
     return torch.cat([P[:TRUNK], P[TRUNK:n] + P[n:] * E])
 
 
-def logits(head, P_eff, s, N):
+def logits(head, P_eff, s, N, A=2, fc=FC):
     import torch
     if head == "c51":
-        return ref_logits(torch.as_tensor(P_eff, dtype=torch.float64), s, N)
-    return ref_logits_d(P_eff, s, N)
+        return ref_logits(torch.as_tensor(P_eff, dtype=torch.float64), s, N, A, fc)
+    return ref_logits_d(P_eff, s, N, A, fc)
 
 
 def np_noise(seed, step, which, size):
@@ -104,11 +104,11 @@ def np_noise(seed, step, which, size):
     return z64, f32
 
 
-def make_noisy(head="c51", N=51, max_batch=256, seed=3, sigma0=0.5, sigma_scale=1.0):
+def make_noisy(head="c51", N=51, max_batch=256, seed=3, sigma0=0.5, sigma_scale=1.0, A=2, fc=FC):
     """a noisy net with mu scaled as tests/test_gpu_c51.py::make_c51 scales a C51 net (x 3), sigma as initialised (x sigma_scale)"""
     from dqnflappybird_amd.vec import QNet
-    net = QNet(2, FC, head, max_batch=max_batch, n_atoms=N, noisy=True, sigma0=sigma0)
-    n = n_mu(head, N)
+    net = QNet(A, fc, head, max_batch=max_batch, n_atoms=N, noisy=True, sigma0=sigma0)
+    n = n_mu(head, N, A, fc)
     ps = []
     for which in (0, 1):
         net.init_params(seed + which, which)
@@ -129,10 +129,10 @@ def plain_twin(head, N, mu_on, mu_tg, max_batch=256):
     return net
 
 
-def ref_q(head, P_eff, s, N):
+def ref_q(head, P_eff, s, N, A=2, fc=FC):
     import torch
     with torch.no_grad():
-        return (torch.softmax(logits(head, P_eff, s, N), -1) * support(N, -10.0, 10.0)).sum(-1).numpy()
+        return (torch.softmax(logits(head, P_eff, s, N, A, fc), -1) * support(N, -10.0, 10.0)).sum(-1).numpy()
 
 
 def frozen(net):
@@ -244,40 +244,39 @@ def test_forward_dist_and_eval_q_match_the_restatement(torch_cuda, head, N):
 
 
 # ---------------------------------------------------------------------------------------------------------------- training
-def ref_train(head, m_on, nz_on, m_tg, nz_tg, s, a, r, s2, t, w, G, algo, N, dev_astar):
+def ref_train(head, m_on, nz_on, m_tg, nz_tg, s, a, r, s2, t, w, G, algo, N, dev_astar, A=2, fc=FC):
     """-> (loss, gradient of [mu | sigma], KL per sample) in float64 with autograd through mu + sigma (.) e"""
     import torch
     P = torch.tensor(m_on, dtype=torch.float64, requires_grad=True)
     z = support(N, -10.0, 10.0)
     B = len(s)
-    eff = effective(P, nz_on, head, N)
+    eff = effective(P, nz_on, head, N, A, fc)
     with torch.no_grad():
-        pt = torch.softmax(logits(head, effective(m_tg, nz_tg, head, N), s2, N), -1)
-        sel = torch.softmax(logits(head, eff.detach(), s2, N), -1) if algo in ("c51double", "c51doubleper") else pt
+        pt = torch.softmax(logits(head, effective(m_tg, nz_tg, head, N, A, fc), s2, N, A, fc), -1)
+        sel = torch.softmax(logits(head, eff.detach(), s2, N, A, fc), -1) if algo in ("c51double", "c51doubleper") else pt
         q = (sel * z).sum(-1)
-        tie = (q[:, 0] - q[:, 1]).abs() < 1e-4
-        astar = torch.where(tie, torch.as_tensor(dev_astar, dtype=torch.long), q.argmax(1))
+        astar = greedy_next(q, dev_astar)
         m = torch_project(pt[torch.arange(B), astar], torch.as_tensor(r.astype(np.float64)), torch.as_tensor(t.astype(np.float64)),
                           G, N, -10.0, 10.0)
-    logp = torch.log_softmax(logits(head, eff, s, N)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)], -1)
+    logp = torch.log_softmax(logits(head, eff, s, N, A, fc)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)], -1)
     ce = -(m * logp).sum(-1)
     loss = (torch.as_tensor(w, dtype=torch.float64) * ce).mean() if w is not None else ce.mean()
     loss.backward()
     return loss.item(), P.grad.numpy(), np_kl_priority(m.numpy(), logp.detach().exp().numpy())
 
 
-def check_noisy_grads(g, g0, head, N, nz_on):
+def check_noisy_grads(g, g0, head, N, nz_on, A=2, fc=FC):
     """mu: the non-noisy tests' per-tensor tolerances; sigma: exactly the device's mu gradient x e(q) in float32, and against
     autograd per layer (fc1 in relative L2 -- ReLU kinks -- the head elementwise)"""
-    n = n_mu(head, N)
+    n = n_mu(head, N, A, fc)
     if head == "c51":
-        _check_grads(g[:n], g0[:n], 2 * N)
+        _check_grads(g[:n], g0[:n], A * N, fc)
     else:
-        check_grads_d(g[:n], g0[:n], N)
+        check_grads_d(g[:n], g0[:n], N, A, fc)
     gs, gs0 = g[n:], g0[n:]
-    assert np.array_equal(gs, g[TRUNK:n] * factors32(head, N, nz_on))
+    assert np.array_equal(gs, g[TRUNK:n] * factors32(head, N, nz_on, A, fc))
     o = 0
-    for k, (w, fi, fo, _, _) in enumerate(layers(head, N)[0]):
+    for k, (w, fi, fo, _, _) in enumerate(layers(head, N, A, fc)[0]):
         for lo, hi in ((o, o + fi * fo), (o + fi * fo, o + (fi + 1) * fo)):
             ref, got = gs0[lo:hi], gs[lo:hi]
             scale = np.abs(ref).max()

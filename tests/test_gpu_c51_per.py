@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests.test_c51_per_host import np_kl_priority, np_priority
-from tests.test_gpu_c51 import FC, GAMMA, _batch, _check_grads, make_c51, ref_logits, support, torch_project
+from tests.test_gpu_c51 import FC, GAMMA, _batch, _check_grads, greedy_next, make_c51, ref_logits, support, torch_project
 from tests.test_gpu_nstep_per import Tape, heaps, per_memory, push
 
 pytestmark = pytest.mark.gpu
@@ -25,21 +25,20 @@ def torch_cuda():
     return torch
 
 
-def ref_train_weighted(p_on, p_tg, s, a, r, s2, t, w, G, algo, N, vmin, vmax, dev_astar):
+def ref_train_weighted(p_on, p_tg, s, a, r, s2, t, w, G, algo, N, vmin, vmax, dev_astar, A=2, fc=FC):
     """-> (loss, flat gradient, KL per sample) in float64 with autograd: loss = mean_b w_b CE_b, KL_b = sum_{m_i > 0} m_i log(m_i / p_i)"""
     import torch
     P = torch.tensor(p_on, dtype=torch.float64, requires_grad=True)
     z = support(N, vmin, vmax)
     B = len(s)
     with torch.no_grad():
-        pt = torch.softmax(ref_logits(torch.tensor(p_tg, dtype=torch.float64), s2, N), -1)
-        sel = torch.softmax(ref_logits(P.detach(), s2, N), -1) if algo == "c51doubleper" else pt
+        pt = torch.softmax(ref_logits(torch.tensor(p_tg, dtype=torch.float64), s2, N, A, fc), -1)
+        sel = torch.softmax(ref_logits(P.detach(), s2, N, A, fc), -1) if algo == "c51doubleper" else pt
         q = (sel * z).sum(-1)
-        tie = (q[:, 0] - q[:, 1]).abs() < 1e-4
-        astar = torch.where(tie, torch.as_tensor(dev_astar, dtype=torch.long), q.argmax(1))
+        astar = greedy_next(q, dev_astar)
         m = torch_project(pt[torch.arange(B), astar], torch.as_tensor(r.astype(np.float64)), torch.as_tensor(t.astype(np.float64)),
                           G, N, vmin, vmax)
-    logp = torch.log_softmax(ref_logits(P, s, N)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)], -1)
+    logp = torch.log_softmax(ref_logits(P, s, N, A, fc)[torch.arange(B), torch.as_tensor(a, dtype=torch.long)], -1)
     ce = -(m * logp).sum(-1)
     loss = (torch.as_tensor(w, dtype=torch.float64) * ce).mean()
     loss.backward()

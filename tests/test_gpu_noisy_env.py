@@ -53,7 +53,8 @@ def restate(net, head, N, s, seed, step, envs):
     """float64 Q of the given envs (rows of the u8 states s) through their own effective weights"""
     P = net.store_params(0).cpu().numpy()
     nz = net.noise_size
-    return np.stack([ref_q(head, effective(P, env_noise(seed, step, e, nz), head, N), s[e:e + 1], N)[0] for e in envs])
+    return np.stack([ref_q(head, effective(P, env_noise(seed, step, e, nz), head, N, net.A, net.FC), s[e:e + 1], N, net.A, net.FC)[0]
+                     for e in envs])
 
 
 def chosen(n):

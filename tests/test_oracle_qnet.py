@@ -40,6 +40,21 @@ def rand_states(rng, B):
     return (rng.random((B, 80, 80, 4)) < 0.37).astype(np.uint8) * 255
 
 
+def tensor_bounds(fc=512, A=2, arch="plain", N=51):
+    """[(name, lo, hi)] of every parameter tensor in the flat vector of a net (fb_qnet_create*; N: the C51 atoms), in order"""
+    sizes = [("W_conv1", 8192), ("b_conv1", 32), ("W_conv2", 32768), ("b_conv2", 64), ("W_conv3", 36864), ("b_conv3", 64),
+             ("W_fc1", 1600 * fc), ("b_fc1", fc)]
+    sizes += {"plain": [("W_q", fc * A), ("b_q", A)],
+              "dueling": [("W_v", fc), ("b_v", 1), ("W_q", fc * A), ("b_q", A)],
+              "c51": [("W_head", fc * A * N), ("b_head", A * N)],
+              "c51dueling": [("W_v", fc * N), ("b_v", N), ("W_adv", fc * A * N), ("b_adv", A * N)]}[arch]
+    out, o = [], 0
+    for name, k in sizes:
+        out.append((name, o, o + k))
+        o += k
+    return out
+
+
 @pytest.mark.parametrize("dueling", [False, True])
 def test_forward_backward_vs_torch(oracle, dueling):
     rng = np.random.default_rng(0)
@@ -60,6 +75,35 @@ def test_forward_backward_vs_torch(oracle, dueling):
     gt = pt.grad.numpy()
     scale = np.abs(gt).max()
     np.testing.assert_allclose(g, gt, rtol=2e-4, atol=2e-6 * scale)
+
+
+@pytest.mark.parametrize("fc,A,dueling", [(128, 1, False), (384, 3, True), (1024, 8, False), (4096, 2, True)])
+def test_forward_backward_vs_torch_at_other_shapes(oracle, fc, A, dueling):
+    """the same comparison at the widths and action counts fb_qnet_create accepts besides the reference's 512 / 2 (the GPU tests of
+    tests/test_gpu_shapes.py trust the oracle there), per tensor so that the head cannot hide behind W_fc1"""
+    rng = np.random.default_rng(fc + A)
+    cfg = oracle.qcfg(fc, A, dueling)
+    bounds = tensor_bounds(fc, A, "dueling" if dueling else "plain")
+    assert oracle.nparams(cfg) == bounds[-1][2]
+    params = oracle.init_params(cfg, seed=fc)
+    params *= 3.0
+    params[bounds[8][1]:] *= np.float32(np.sqrt(512 / fc))         # Q stays O(1..10) at every width
+    B = 3
+    s = rand_states(rng, B)
+    q, acts = oracle.forward(params, cfg, s, keep=True)
+    assert q.shape == (B, A)
+    pt = torch.tensor(params, dtype=torch.float64, requires_grad=True)
+    qt = torch_forward(pt, torch.tensor(s, dtype=torch.float64), fc, A, dueling)
+    assert np.abs(q).max() > 0.05
+    np.testing.assert_allclose(q, qt.detach().numpy(), rtol=0, atol=2e-5 * max(1.0, np.abs(q).max()))
+    dq = rng.standard_normal((B, A)).astype(np.float32)
+    g = oracle.backward(params, cfg, s, acts, dq)
+    (qt * torch.tensor(dq, dtype=torch.float64)).sum().backward()
+    gt = pt.grad.numpy()
+    for name, lo, hi in bounds:
+        scale = np.abs(gt[lo:hi]).max()
+        assert scale > 0, name
+        np.testing.assert_allclose(g[lo:hi], gt[lo:hi], rtol=2e-4, atol=2e-6 * scale, err_msg=name)
 
 
 def test_init_distribution(oracle):
