@@ -11,6 +11,10 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
                                                                                        without noisy nets)
     python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy   (full Rainbow: noisy fc1 and head
                                                                                        layers, epsilon 0; --noisy takes any C51 model)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model qrdqn --vec 1024               (QR-DQN: quantile head, quantile Huber loss;
+                                                                                       qrdqnper: with prioritized replay; qrrainbow:
+                                                                                       dueling QR head, double target, PER; --n-quantiles,
+                                                                                       --kappa)
     python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy --acting-noise env
                                                                                       (... acting with independent noise per env)
 
@@ -81,7 +85,22 @@ def main():
     parser.add_argument("--noisy", action="store_true", help="noisy fc1 and head layers, epsilon 0 (--model c51 | c51per | c51doubleper | rainbow, --vec)")
     parser.add_argument("--acting-noise", choices=("shared", "env"), default="shared",
                         help="--noisy: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
+    parser.add_argument("--n-quantiles", type=int, default=None, help="QR models: the number of quantiles N (default 51)")
+    parser.add_argument("--kappa", type=float, default=None, help="QR models: the quantile Huber loss's threshold (default 1)")
     args = parser.parse_args()
+    qr_models = ("qrdqn", "qrdqnper", "qrrainbow")
+    if args.model in qr_models:                          # (refused before anything touches the GPU)
+        if not args.vec:
+            parser.error(f"--model {args.model} needs --vec: QR-DQN runs in the vectorised loop only")
+        if args.noisy:
+            parser.error(f"--noisy needs a C51 model (c51, c51per, c51doubleper, rainbow), not --model {args.model}")
+        from .vec import check_quantiles
+        try:
+            check_quantiles(51 if args.n_quantiles is None else args.n_quantiles, 1.0 if args.kappa is None else args.kappa)
+        except ValueError as e:
+            parser.error(str(e))
+    elif args.n_quantiles is not None or args.kappa is not None:
+        parser.error(f"--n-quantiles / --kappa need a QR model ({', '.join(qr_models)}), not --model {args.model}")
     if args.acting_noise != "shared" and not args.noisy:      # (refused before anything touches the GPU)
         parser.error(f"--acting-noise {args.acting_noise} needs --noisy")
     if args.noisy:                                       # (refused before anything touches the GPU)
@@ -108,10 +127,15 @@ def main():
         if args.model in ("actorcritic", "policygradient"):
             raise SystemExit("--vec runs the DQN family; the actor-critic / policy-gradient agents are single-env (as in the reference)")
         algo = {"dqn": "dqn", "ddqn": "nature", "dqnnature": "nature", "duelingdqn": "nature", "prioritydqn": "per", "c51": "c51",
-                "c51per": "c51per", "c51doubleper": "c51doubleper", "rainbow": "c51doubleper"}[args.model]
+                "c51per": "c51per", "c51doubleper": "c51doubleper", "rainbow": "c51doubleper", "qrdqn": "qr", "qrdqnper": "qrper",
+                "qrrainbow": "qrdoubleper"}[args.model]
         arch = "c51dueling" if args.model == "rainbow" else "plain"      # rainbow: dueling C51 head, double target, prioritized replay
+        qkw = {}
+        if args.model in qr_models:                      # qrrainbow: dueling QR head, double target, prioritized replay
+            arch = "qrdueling" if args.model == "qrrainbow" else "qr"
+            qkw = dict(n_quantiles=51 if args.n_quantiles is None else args.n_quantiles, kappa=1.0 if args.kappa is None else args.kappa)
         vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step, noisy=args.noisy,
-                      acting_noise=args.acting_noise)
+                      acting_noise=args.acting_noise, **qkw)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)
     else:
         playFlappyBird(args.model, args.steps, verbose=not args.quiet)

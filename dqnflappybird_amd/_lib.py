@@ -20,6 +20,8 @@ ALGO_DQN, ALGO_NATURE, ALGO_DOUBLE, ALGO_PER, ALGO_PG = 0, 1, 2, 3, 4
 ALGO_C51, ALGO_C51_DOUBLE = 5, 6
 ALGO_C51_PER, ALGO_C51_DOUBLE_PER = 7, 8                # C51 with prioritized replay (include/fbdqn.h)
 C51_MAX_ATOMS = 64                                    # include/fbdqn.h FB_C51_MAX_ATOMS
+ARCH_QR, ARCH_QR_DUELING = 4, 5                       # quantile-regression heads (include/fbdqn.h)
+ALGO_QR, ALGO_QR_DOUBLE, ALGO_QR_PER, ALGO_QR_DOUBLE_PER = 9, 10, 11, 12
 NOISE_SAMPLE, NOISE_MEAN = 0, 1                       # include/fbdqn.h FB_NOISE_* (fb_qnet_reset_noise)
 ACT_NOISE_SHARED, ACT_NOISE_PER_ENV = 0, 1            # include/fbdqn.h FB_ACT_NOISE_* (fb_qnet_set_acting_noise)
 DTYPE_F32, DTYPE_BF16 = 0, 1
@@ -80,6 +82,9 @@ SIGNATURES = {
     "fb_qnet_act_nib_env_noise": [_vp, _vp, _i, _f, _u64, _u64, _vp, _vp, _vp],
     "fb_qnet_get_support": [_vp] * 4,
     "fb_qnet_forward_dist": [_vp, _i, _vp, _i, _vp, _vp],
+    "fb_qnet_create_qr": [_i, _i, _i, _i, _f, _i, _vp],
+    "fb_qnet_get_quantiles": [_vp, _vp, _vp],
+    "fb_qnet_forward_quantiles": [_vp, _i, _vp, _i, _vp, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],

@@ -33,8 +33,13 @@ static inline bool is_c51_algo(int algo) {          // trains a C51 net
     return algo == FB_ALGO_C51 || algo == FB_ALGO_C51_DOUBLE || algo == FB_ALGO_C51_PER || algo == FB_ALGO_C51_DOUBLE_PER;
 }
 static inline bool is_double_c51(int algo) { return algo == FB_ALGO_C51_DOUBLE || algo == FB_ALGO_C51_DOUBLE_PER; }     // a* online
+static inline bool is_qr_algo(int algo) {           // trains a QR net
+    return algo == FB_ALGO_QR || algo == FB_ALGO_QR_DOUBLE || algo == FB_ALGO_QR_PER || algo == FB_ALGO_QR_DOUBLE_PER;
+}
+static inline bool is_double_qr(int algo) { return algo == FB_ALGO_QR_DOUBLE || algo == FB_ALGO_QR_DOUBLE_PER; }       // a* online
 static inline bool is_per_algo(int algo) {          // prioritized memory, importance weights, |TD error| / priority out
-    return algo == FB_ALGO_PER || algo == FB_ALGO_C51_PER || algo == FB_ALGO_C51_DOUBLE_PER;
+    return algo == FB_ALGO_PER || algo == FB_ALGO_C51_PER || algo == FB_ALGO_C51_DOUBLE_PER || algo == FB_ALGO_QR_PER ||
+           algo == FB_ALGO_QR_DOUBLE_PER;
 }
 
 // Hand-offs between kernels of two streams through device words (fb_vec_step's split schedule).  A word only ever grows (the step
@@ -193,8 +198,11 @@ struct FbPushRider { unsigned long long *bits; uint8_t *act; float *rew; uint8_t
 int fb_env_step_rider(fb_env_t h, const uint8_t *actions, uint8_t *frames, uint64_t *frame_bits, float *reward, uint8_t *terminal,
                       int32_t *score, const FbSampleRider *rider, const FbPushRider *push, const FbHeadRider *head, void *stream);
 int fb_qnet_num_actions(fb_qnet_t h);
-int fb_qnet_is_c51(fb_qnet_t h);              // 1: a distributional net (fb_qnet_create_c51)
-// fb_eval_run on a C51 net: launch the head fb_qnet_eval_trunk described in *hd (q / actions / epsilon / seeds filled in by the caller),
+int fb_qnet_is_c51(fb_qnet_t h);              // 1: a C51 net (fb_qnet_create_c51 / _c51_dueling / _c51_noisy)
+int fb_qnet_is_qr(fb_qnet_t h);               // 1: a QR net (fb_qnet_create_qr)
+// 1: a distributional head (C51 or QR): the head is its own launch (no env rider, the one-stream order of fb_vec_step)
+int fb_qnet_is_dist(fb_qnet_t h);
+// fb_eval_run on a distributional (C51 or QR) net: launch the head fb_qnet_eval_trunk described in *hd (q / actions / epsilon / seeds filled in by the caller),
 // epsilon draws keyed key_of[row] on FB_STREAM_EVAL; the eval step launch then reads the actions (its head rider stays off)
 int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32_t *key_of, void *stream);
 // fb_eval_run's acting forward: conv1 .. fc1 of n nibble states (1 <= n <= 3 * max_batch) through the fused two-plane trunk at ANY n (the

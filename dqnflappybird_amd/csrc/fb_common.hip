@@ -90,6 +90,20 @@ void fb_mt_init_by_array_host(FbMT *s, const uint32_t *key, int key_length) {
     s->idx = 624;
 }
 
+// QR (include/fbdqn.h): a QR net and a QR algo go together; FB_ALGO_QR / _DOUBLE take a uniform memory, FB_ALGO_QR_PER / _DOUBLE_PER a
+// prioritized one.  Checked by the ring-fed calls before any counter moves or any launch, as the C51 checks beside them
+static int qr_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *who) {
+    if (!is_qr_algo(algo) && !fb_qnet_is_qr(net)) return FB_OK;
+    FB_REQUIRE(is_qr_algo(algo) == (fb_qnet_is_qr(net) != 0),
+               "%s: a QR net takes a QR algo (FB_ALGO_QR, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a QR net only (algo %d)", who, algo);
+    if (is_per_algo(algo))
+        FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: algo %d (QR with prioritized replay) trains from a prioritized memory only", who, algo);
+    else
+        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: algo %d (QR) trains from a uniform memory only (FB_ALGO_QR_PER / _DOUBLE_PER take a "
+                   "prioritized one)", who, algo);
+    return FB_OK;
+}
+
 // n x (random.sample -> minibatch -> _trainQNetwork) on a memory that is not being pushed to, as one host call.  Each step is the six
 // launches of the ring-fed train step (conv trunk of the 2B states straight from the 1-bit frame ring -> fc1 -> loss + fc1 backward ->
 // conv data gradients -> conv weight gradients -> Adam): no gather, no u8 minibatch.  Only the first draw gets a launch of its own: the
@@ -109,6 +123,10 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
         FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
                    "%s: a C51 net takes a C51 algo (FB_ALGO_C51 or FB_ALGO_C51_DOUBLE), and those algos take a C51 net only (algo %d)", "fb_train_steps", algo);
         FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_steps");
+    }
+    {
+        const int rq = qr_check(replay, net, algo, "fb_train_steps");
+        if (rq != FB_OK) return rq;
     }
     int rc = fb_replay_check_gamma(replay, gamma, "fb_train_steps");
     if (rc != FB_OK) return rc;
@@ -248,7 +266,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // every argument check of the calls below happens HERE, before the replay's push counter moves or anything is launched: a
     // rejected step must leave the handles exactly as they were (a counted push without its env launch would make every later
     // gather address a ring slot that was never written)
-    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_C51_DOUBLE_PER)", algo);
+    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo) || is_qr_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER)", algo);
     // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
     // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
     // counter moves
@@ -257,6 +275,10 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
                    "%s: a C51 net takes a C51 algo (FB_ALGO_C51, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a C51 net only (algo %d)", "fb_vec_step", algo);
         if (!is_per_algo(algo))
             FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_vec_step");
+    }
+    {
+        const int rq = qr_check(replay, net, algo, "fb_vec_step");
+        if (rq != FB_OK) return rq;
     }
     FB_REQUIRE(per == (fb_replay_is_prioritized(replay) != 0), "fb_vec_step: algo %d and the memory's kind (uniform / prioritized) do not match", algo);
     FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_vec_step: n_envs %d does not match the env (%d) / replay (%d) handles",
@@ -300,9 +322,9 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // for the env launch's head rider) -> the launch in front of it does not retire before the fc1 launch has; workspaces -> the fused
     // acting forward has its own (hf_act / hp_act); the acting forward against the previous step's Adam and whatever else the caller's
     // stream held at entry -> c_entry.
-    // (C51 nets: the one-stream order below -- the split schedule is specified for the 2-output scalar heads)
+    // (C51 and QR nets: the one-stream order below -- the split schedule is specified for the 2-output scalar heads)
     if (fb_vec_split_flag && train && !per && n_envs >= 256 && batch < 256 && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 &&
-        !fb_qnet_is_c51(net)) {
+        !fb_qnet_is_dist(net)) {
         hipStream_t A = fb_stream(stream);
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(A, &cap);
@@ -360,7 +382,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // the acting path's last kernel (fc2 + epsilon-greedy action, one wave per env) rides in the env launch as well when
     // an env workgroup has a wave for each of its envs there (up to four envs per workgroup: 8192 envs)
     FbHeadRider hrider;
-    const int have_h = fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 && !fb_qnet_is_c51(net);      // (C51: its own launch)
+    const int have_h = fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 && !fb_qnet_is_dist(net);     // (C51 / QR: its own launch)
     int rc = have_h ? fb_qnet_act_nib_rider(net, b->nib, n_envs, epsilon, seed, step, b->actions, &hrider, stream)
              : env_noise ? fb_qnet_act_nib_env_noise_keep(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream)
                          : fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
@@ -427,7 +449,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
 extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo, int batch, const int64_t *idx, const float *isw, uint8_t *a,
                                     float *r, uint8_t *t, double gamma, float *loss, float *abs_err, float *flat_grad, void *stream) {
     FB_REQUIRE(replay && net && idx && a && r && t && loss, "fb_train_from_replay: NULL argument");
-    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_C51_DOUBLE_PER)", algo);
+    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo) || is_qr_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER)", algo);
     // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
     // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
     // counter moves
@@ -436,6 +458,10 @@ extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo,
                    "%s: a C51 net takes a C51 algo (FB_ALGO_C51, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a C51 net only (algo %d)", "fb_train_from_replay", algo);
         if (!is_per_algo(algo))
             FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_from_replay");
+    }
+    {
+        const int rq = qr_check(replay, net, algo, "fb_train_from_replay");
+        if (rq != FB_OK) return rq;
     }
     FB_REQUIRE(!is_per_algo(algo) || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
     if (is_c51_algo(algo) && is_per_algo(algo))

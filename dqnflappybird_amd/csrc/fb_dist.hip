@@ -145,6 +145,8 @@ extern "C" int fb_vec_step_dp(fb_dist_t d, fb_env_t env, fb_replay_t replay, fb_
     FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_vec_step_dp: data parallel does not take a noisy net (noisy nets are C51 nets: one GPU only)");
     FB_REQUIRE(!fb_qnet_is_c51(net) && !is_c51_algo(algo),
                "fb_vec_step_dp: data-parallel C51 is not supported (C51 trains through fb_vec_step, fb_train_from_replay, fb_train_steps)");
+    FB_REQUIRE(!fb_qnet_is_qr(net) && !is_qr_algo(algo),
+               "fb_vec_step_dp: data-parallel QR is not supported (QR trains through fb_vec_step, fb_train_from_replay, fb_train_steps)");
     FB_REQUIRE(d && b && (!train || b->flat_grad), "fb_vec_step_dp: NULL handle / flat_grad buffer");
     void *prev = fb_qnet_get_grad_event(net);          // (an event the caller installed for its own schedule is put back afterwards)
     int rc = fb_qnet_set_grad_event(net, d->overlap ? d->grad_ready : nullptr);

@@ -964,7 +964,7 @@ extern "C" int fb_eval_run(fb_eval_t ev, fb_qnet_t net, int n_envs, int episodes
     FB_REQUIRE(epsilon >= 0.f && epsilon <= 1.f, "fb_eval_run: epsilon=%g outside [0, 1]", (double)epsilon);      // (NaN fails too)
     FB_REQUIRE(score && length && truncated && steps_host, "fb_eval_run: NULL output");
     hipStream_t S = fb_stream(stream);
-    const bool c51 = fb_qnet_is_c51(net) != 0;
+    const bool c51 = fb_qnet_is_dist(net) != 0;     // (C51 or QR: the head is its own launch)
     // the acting forward writes the net's acting scratch (hf_act / hp_act, the activation planes, the plane versions), which the split
     // schedule's side stream also writes: whatever that stream still holds finishes first (and this call returns synchronised)
     if (hipStream_t side = fb_qnet_side_stream(net)) FB_CHECK_HIP(hipStreamSynchronize(side));

@@ -1548,7 +1548,8 @@ struct C51Core {
     uint8_t *actions; float epsilon; uint32_t seed_lo, seed_hi, step_lo, step_hi;
     const int32_t *key_of; uint32_t stream;      // epsilon counter: key_of[row] on `stream` (fb_eval_run), or the row on FB_STREAM_EPS
 };
-template <int AT>
+// QR (qr_head_kernel, a QR net): lg holds the quantiles theta, Q = (1/N) sum_i theta_i, and `probs` receives theta
+template <int AT, bool QR = false>
 __device__ __forceinline__ void c51_head_one(const C51Core &C, const float *__restrict__ P, int smp, int lane) {
     const int A = AT == MAXA ? C.A : AT, N = C.sup.N;
     const bool on = lane < N;
@@ -1556,7 +1557,14 @@ __device__ __forceinline__ void c51_head_one(const C51Core &C, const float *__re
     float lg[AT], qv[AT];
     c51_logits<AT>(C.hf, C.stot, C.nks, C.FC, P, C.off, A, N, smp, lane, lg);
     const float z = C.sup.vmin + (float)(on ? lane : 0) * C.sup.dz;
-    if (C.probs) {                                                // (a kernel argument decides: uniform branch)
+    if constexpr (QR) {
+        float *row = C.probs ? C.probs + (size_t)smp * A * N + lane : nullptr;
+#pragma unroll
+        for (int a = 0; a < AT; a++) {
+            if (row && on && a < A) row[a * N] = lg[a];
+            qv[a] = wave_sum(on ? lg[a] : 0.f) * (1.f / (float)N);
+        }
+    } else if (C.probs) {                                                // (a kernel argument decides: uniform branch)
         float *row = C.probs + (size_t)smp * A * N + lane;
 #pragma unroll
         for (int a = 0; a < AT; a++) {
@@ -1594,6 +1602,20 @@ __global__ __launch_bounds__(256) void c51_head_kernel(C51HeadArgs H) {
     }
     if (smp < 0) return;
     c51_head_one<AT>(H.c, H.params ? H.params : P, smp, lane);
+}
+// the QR head (a QR net): c51_head_kernel's layout and slices, Q = the mean of the quantiles
+template <int AT>
+__global__ __launch_bounds__(256) void qr_head_kernel(C51HeadArgs H) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int sidx = blockIdx.x * 4 + wave;
+    const float *P = nullptr;
+    int smp = -1;
+    for (int z = 0; z < H.nslices; z++) {
+        if (sidx < H.sl.s[z].count) { P = H.sl.s[z].params; smp = H.sl.s[z].s_off + sidx; break; }
+        sidx -= H.sl.s[z].count;
+    }
+    if (smp < 0) return;
+    c51_head_one<AT, true>(H.c, H.params ? H.params : P, smp, lane);
 }
 
 // ---- training, launch 1 of 2: one wave per sample.  Rows of hf: s (online net, 0 .. B-1), s' through p_next (B ..), and for
@@ -1666,6 +1688,80 @@ __global__ __launch_bounds__(256) void c51_loss_kernel(C51LossArgs L) {
         const bool pos = on && m > 0.f;
         const float kl = wave_sum(pos ? m * (logf(pos ? m : 1.f) - (la - lse_s)) : 0.f);
         if (L.abs_err && lane == 0) L.abs_err[b] = fmaxf(kl, 0.f);
+        lossb *= w;
+        g *= w;
+    }
+    L.dl[(size_t)b * 64 + lane] = g;
+    if (lane == 0) L.lterm[b] = lossb;
+    const int AN = A * N;
+    for (int j0 = 0; j0 < FC; j0 += 64) {
+        const int j = j0 + lane;
+        const float x = fc1_out(L.hf, L.stot, FC, b, j, L.p_on[L.off.bf1 + j], L.nks);
+        const float *__restrict__ w = L.p_on + L.off.wq + (size_t)j * AN + ab * N;
+        float dh = 0.f;
+        for (int i = 0; i < N; i++) dh = fmaf(rdlane(g, i), w[i], dh);
+        L.dhf[(size_t)b * FC + j] = x > 0.f ? dh : 0.f;
+        L.xs[(size_t)b * FC + j] = x;
+    }
+}
+
+// ---- QR training, launch 1 of 2 (include/fbdqn.h): c51_loss_kernel's grid and rows, one wave per sample, lane i = quantile i of every
+// action.  Forms a* (the first maximum of the mean of p_next's quantiles), the targets T_j = R + Gamma (1 - done) theta_target(s', a*)_j,
+// then the pairwise quantile Huber loss: lane i walks j = 0 .. N-1 in order with T_j broadcast by v_readlane (deterministic, no atomics).
+// dl[b][64] = dl_b/dtheta / B on the taken action, and the dhf / xs rows exactly as c51_loss_kernel's tail: c51_grad_kernel /
+// c51d_grad_kernel follow unchanged.  PW (FB_ALGO_QR_PER / _DOUBLE_PER): the loss term and dl carry isw[b] (g = (dl_b / B) * w), the
+// priority abs_err[b] = l_b does not.  (L.algo: the target's form only, FB_ALGO_QR or FB_ALGO_QR_DOUBLE.)
+struct QRLossArgs {
+    int algo, B, FC, A, N, nks, stot; NetOff off; float kappa;
+    const float *p_on, *p_next, *p_tgt;
+    const float *hf; const uint8_t *act; const float *rew; const uint8_t *term; double gamma;
+    float *dl, *xs, *lterm, *dhf;
+    const float *isw; float *abs_err;                            // PW only: importance weights f32[B]; priorities f32[B] out or NULL
+};
+template <int AT, bool PW = false>
+__global__ __launch_bounds__(256) void qr_loss_kernel(QRLossArgs L) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= L.B) return;                                        // (wave-uniform)
+    const int A = AT == MAXA ? L.A : AT, N = L.N, B = L.B, FC = L.FC;
+    const bool on = lane < N;
+    const float kappa = L.kappa, invN = 1.f / (float)N;
+    const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;  // (an action past the head reads the last one: stays in bounds)
+    const float r = L.rew[b];
+    const int done = L.term[b];
+    float ts[AT], tn[AT], tt[AT];
+    c51_logits<AT>(L.hf, L.stot, L.nks, FC, L.p_on, L.off, A, N, b, lane, ts);
+    c51_logits<AT>(L.hf, L.stot, L.nks, FC, L.p_next, L.off, A, N, B + b, lane, tn);
+    if (L.algo == FB_ALGO_QR_DOUBLE) c51_logits<AT>(L.hf, L.stot, L.nks, FC, L.p_tgt, L.off, A, N, 2 * B + b, lane, tt);
+    else {
+#pragma unroll
+        for (int a = 0; a < AT; a++) tt[a] = tn[a];
+    }
+    // a* = argmax_a of the mean quantile of p_next (QR: the target net, double: the online net), first maximum
+    float qn[AT];
+#pragma unroll
+    for (int a = 0; a < AT; a++) qn[a] = wave_sum(on ? tn[a] : 0.f) * invN;
+    int best = 0;
+#pragma unroll
+    for (int a = 1; a < AT; a++) if (a < A && qn[a] > qn[best]) best = a;
+    float d = tt[0], th = ts[0];
+#pragma unroll
+    for (int a = 1; a < AT; a++) { d = a == best ? tt[a] : d; th = a == ab ? ts[a] : th; }
+    const float T = done ? r : r + (float)L.gamma * d;           // target quantile j on lane j
+    const float tau = (float)(2 * lane + 1) / (float)(2 * N);
+    float ls = 0.f, gs = 0.f;
+    for (int j = 0; j < N; j++) {
+        const float u = rdlane(T, j) - th, au = fabsf(u);
+        const float wt = fabsf(tau - (u < 0.f ? 1.f : 0.f));
+        const float hub = au <= kappa ? 0.5f * u * u : kappa * (au - 0.5f * kappa);
+        ls += wt * hub / kappa;
+        gs += wt * fminf(fmaxf(u, -kappa), kappa) / kappa;
+    }
+    const float lb = wave_sum(on ? ls : 0.f) * invN;             // l_b
+    float lossb = lb;
+    float g = on ? (-gs * invN) / (float)B : 0.f;
+    if constexpr (PW) {
+        const float w = L.isw[b];
+        if (L.abs_err && lane == 0) L.abs_err[b] = lb;
         lossb *= w;
         g *= w;
     }
@@ -3717,7 +3813,8 @@ struct fb_qnet {
     // start its Adam launch as soon as that fc1 launch is through
     float *hf_act, *hp_act;
     FbSplitCtx *split;               // fb_qnet_split_ctx
-    C51Sup sup;                      // C51 nets: the support (sup.N = 0: a scalar head)
+    C51Sup sup;                      // C51 nets: the support (sup.N = 0: a scalar head); QR nets: sup.N = n_quantiles, the rest 0
+    float kappa;                     // QR nets: the quantile Huber loss's threshold
     float *c51_dl, *c51_xs, *c51_lt; // C51 training: logit gradients [max_batch][64], fc1 activations of s [max_batch][FC], loss terms [max_batch]
     // what the C51 head / loss / eval kernels read: hoff (the C51 layout; = off but for a dueling C51 net) from head_base(params[w]).
     // A dueling C51 net (FB_ARCH_C51_DUELING): heff[w] = [b_fc1 | W_eff | b_eff], the folded head of params[w] (c51d_fold_kernel)
@@ -3758,7 +3855,9 @@ static NetOff make_off_c51d(int FC, int A, int N) {
     o.wq = o.bv + N; o.bq = o.wq + FC * A * N; o.n = o.bq + A * N;
     return o;
 }
-static bool is_c51d(const fb_qnet *h) { return h->arch == FB_ARCH_C51_DUELING; }
+// a folded head: a dueling C51 or dueling QR net (the same layout and fold)
+static bool is_c51d(const fb_qnet *h) { return h->arch == FB_ARCH_C51_DUELING || h->arch == FB_ARCH_QR_DUELING; }
+static bool is_qr(const fb_qnet *h) { return h->arch == FB_ARCH_QR || h->arch == FB_ARCH_QR_DUELING; }
 // the parameters the C51 kernels read, with h->hoff, for the net whose parameters are `params` (a virtual base for a dueling C51 net:
 // hoff.bf1 lands on heff[w][0], as the acting forward's hp_act copy is read)
 static const float *head_base(const fb_qnet *h, const float *params) {
@@ -3798,6 +3897,7 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
     FB_REQUIRE(out, "fb_qnet_create: out is NULL");
     FB_REQUIRE(arch != FB_ARCH_C51, "fb_qnet_create: a C51 net is made by fb_qnet_create_c51 (it needs the support)");
     FB_REQUIRE(arch != FB_ARCH_C51_DUELING, "fb_qnet_create: a dueling C51 net is made by fb_qnet_create_c51_dueling (it needs the support)");
+    FB_REQUIRE(arch != FB_ARCH_QR && arch != FB_ARCH_QR_DUELING, "fb_qnet_create: a QR net is made by fb_qnet_create_qr (it needs N and kappa)");
     FB_REQUIRE(arch == FB_ARCH_PLAIN || arch == FB_ARCH_DUELING, "fb_qnet_create: arch must be 0 or 1");
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create: fc_width must be a multiple of 128");
     FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create: n_actions must be in 1..%d", MAXA);
@@ -3838,6 +3938,21 @@ extern "C" int fb_qnet_create_c51_noisy(int arch, int fc_width, int n_actions, i
     return c51_create("fb_qnet_create_c51_noisy", arch, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out, sigma0);
 }
 
+extern "C" int fb_qnet_create_qr(int arch, int fc_width, int n_actions, int n_quantiles, float kappa, int max_batch, fb_qnet_t *out) {
+    const char *fn = "fb_qnet_create_qr";
+    FB_REQUIRE(out, "%s: out is NULL", fn);
+    FB_REQUIRE(arch == FB_ARCH_QR || arch == FB_ARCH_QR_DUELING, "%s: arch must be FB_ARCH_QR (4) or FB_ARCH_QR_DUELING (5), got %d", fn, arch);
+    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
+    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "%s: n_actions must be in 1..%d", fn, MAXA);
+    FB_REQUIRE(n_quantiles >= 2 && n_quantiles <= FB_C51_MAX_ATOMS, "%s: n_quantiles=%d outside 2..%d", fn, n_quantiles, FB_C51_MAX_ATOMS);
+    FB_REQUIRE(n_actions * n_quantiles <= 128, "%s: n_actions * n_quantiles = %d exceeds 128", fn, n_actions * n_quantiles);
+    FB_REQUIRE(isfinite(kappa) && kappa > 0.f, "%s: kappa must be finite and > 0 (got %g)", fn, (double)kappa);
+    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
+    const int rc = qnet_create(arch, fc_width, n_actions, C51Sup{n_quantiles, 0.f, 0.f, 0.f}, max_batch, out);
+    if (rc == FB_OK) (*out)->kappa = kappa;
+    return rc;
+}
+
 // the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
 static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, float sigma0) {
     NoisyNet nn;
@@ -3858,9 +3973,9 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     fb_qnet *h = new fb_qnet();
     memset(h, 0, sizeof(*h));
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
-    h->off = arch == FB_ARCH_C51_DUELING ? make_off_c51d(fc_width, n_actions, sup.N)
-                                         : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
-    h->hoff = arch == FB_ARCH_C51_DUELING ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
+    h->off = is_c51d(h) ? make_off_c51d(fc_width, n_actions, sup.N)
+                        : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
+    h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
     h->n = h->off.n;
     h->noisy = sigma0 >= 0.f;                    // (fb_qnet_create_c51_noisy: C51 archs, finite sigma0 >= 0)
     h->ntot = h->noisy ? 2 * h->n - OFF_WF1 : h->n;
@@ -3900,7 +4015,7 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     alloc((void **)&h->gmax, (size_t)(fc_width / 16) * 4);
     alloc((void **)&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc((void **)&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
     if (sup.N) { alloc((void **)&h->c51_dl, Bm * 64 * 4); alloc((void **)&h->c51_xs, Bm * fc_width * 4); alloc((void **)&h->c51_lt, Bm * 4); }
-    if (arch == FB_ARCH_C51_DUELING) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
+    if (is_c51d(h)) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
     if (e != hipSuccess) {
         fb_set_error(e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP, "fb_qnet_create: %s", hipGetErrorString(e));
         fb_qnet_destroy(h);
@@ -4244,6 +4359,12 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
                 else if (!trunk) { FB_K(K_CONV2) hipLaunchKernelGGL(conv23_sp_kernel<1>, gc, dim3(512), 0, st, c23); }
                 FB_K(K_FC1) hipLaunchKernelGGL(fc1_sp_kernel<1>, gf, dim3(256), 0, st, af);
             }
+            // the fc1 launch copies one head parameter per thread: a distributional head (C51 / QR, A N columns) can outgrow a small
+            // launch's threads, and the rest of the copy follows it on the same stream (these nets take the one-stream order)
+            if (fused && (only < 0 || only == K_FC1) && (long long)af.hp_n > (long long)gf.x * 256) {
+                const size_t done = (size_t)gf.x * 256;
+                FB_CHECK_HIP(hipMemcpyAsync(h->hp_act + done, af.hp_src + done, sizeof(float) * ((size_t)af.hp_n - done), hipMemcpyDeviceToDevice, st));
+            }
             z0 = z1;
         }
     }
@@ -4279,7 +4400,9 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
             memset(p.head_rider, 0, sizeof(*p.head_rider));
             p.head_rider->c.hf = C.hf; p.head_rider->c.stot = stot; p.head_rider->c.nks = C.nks;
             p.head_rider->params = acting_fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params;
-        } else if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((total + 3) / 4), dim3(256), 0, st, H);
+        } else if (is_qr(h) && h->A == 2) hipLaunchKernelGGL(qr_head_kernel<2>, dim3((total + 3) / 4), dim3(256), 0, st, H);
+        else if (is_qr(h)) hipLaunchKernelGGL(qr_head_kernel<MAXA>, dim3((total + 3) / 4), dim3(256), 0, st, H);
+        else if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((total + 3) / 4), dim3(256), 0, st, H);
         else hipLaunchKernelGGL(c51_head_kernel<MAXA>, dim3((total + 3) / 4), dim3(256), 0, st, H);
     }
     if (!c51 && !(fk && p.train)) FB_K(K_HEAD) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
@@ -4297,7 +4420,26 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
     if (p.train) {
         const int B = p.B, FC = h->FC, rbt = h->nsplit_train == 1;       // bf16 training: operands rounded to bf16
         float *G = p.G;
-        if (c51) FB_K(K_LOSS) {                     // C51: per-sample distribution / projection / dhf, then the per-unit reductions
+        if (c51 && is_qr(h)) FB_K(K_LOSS) {         // QR: per-sample targets / quantile Huber loss / dhf, then C51's per-unit reductions
+            if (p.tick) h->adam_ticked = !p.apply_adam;
+            QRLossArgs L;
+            const bool pw = is_per_algo(p.algo);     // (prioritized: weighted loss, l_b priorities)
+            L.algo = is_double_qr(p.algo) ? FB_ALGO_QR_DOUBLE : FB_ALGO_QR;
+            L.B = B; L.FC = FC; L.A = h->A; L.N = h->sup.N; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->hoff; L.kappa = h->kappa;
+            L.p_on = head_base(h, h->params[0]); L.p_next = head_base(h, p.sl.s[1].params);
+            L.p_tgt = head_base(h, p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params);
+            L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
+            L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
+            L.isw = pw ? p.isw : nullptr; L.abs_err = pw ? p.abs_err : nullptr;
+            if (pw && h->A == 2) hipLaunchKernelGGL((qr_loss_kernel<2, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
+            else if (pw) hipLaunchKernelGGL((qr_loss_kernel<MAXA, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
+            else if (h->A == 2) hipLaunchKernelGGL(qr_loss_kernel<2>, dim3((B + 3) / 4), dim3(256), 0, st, L);
+            else hipLaunchKernelGGL(qr_loss_kernel<MAXA>, dim3((B + 3) / 4), dim3(256), 0, st, L);
+            const C51GradArgs gA{B, FC, h->A, h->sup.N, h->off, h->c51_dl, h->c51_xs, h->c51_lt, h->dhf, p.a, G, p.loss, h->gmax, h->adam, p.tick};
+            if (is_c51d(h)) hipLaunchKernelGGL(c51d_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);      // (gA.off: W_v b_v W_a b_a)
+            else hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);
+        }
+        if (c51 && !is_qr(h)) FB_K(K_LOSS) {        // C51: per-sample distribution / projection / dhf, then the per-unit reductions
             if (p.tick) h->adam_ticked = !p.apply_adam;
             C51LossArgs L;
             const bool pw = is_per_algo(p.algo);     // (prioritized: weighted loss, KL priorities)
@@ -4504,7 +4646,9 @@ extern "C" int fb_qnet_act_nib(fb_qnet_t h, const uint8_t *nib_states, int n, fl
 }
 
 int fb_qnet_num_actions(fb_qnet_t h) { return h ? h->A : 0; }
-int fb_qnet_is_c51(fb_qnet_t h) { return h && h->sup.N > 0; }
+int fb_qnet_is_c51(fb_qnet_t h) { return h && h->sup.N > 0 && !is_qr(h); }
+int fb_qnet_is_qr(fb_qnet_t h) { return h && is_qr(h); }
+int fb_qnet_is_dist(fb_qnet_t h) { return h && h->sup.N > 0; }
 extern "C" int fb_qnet_is_noisy(fb_qnet_t h) { return h && h->noisy ? 1 : 0; }
 
 extern "C" int fb_qnet_reset_noise(fb_qnet_t h, int which, uint64_t seed, uint64_t step, int mode, void *stream) {
@@ -4612,13 +4756,28 @@ int fb_qnet_act_nib_env_noise_keep(fb_qnet_t h, const uint8_t *nib_states, int n
 
 extern "C" int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host) {
     FB_REQUIRE(h && n_atoms_host && v_min_host && v_max_host, "fb_qnet_get_support: NULL argument");
-    *n_atoms_host = h->sup.N; *v_min_host = h->sup.vmin; *v_max_host = h->sup.vmax;
+    *n_atoms_host = is_qr(h) ? 0 : h->sup.N; *v_min_host = h->sup.vmin; *v_max_host = h->sup.vmax;      // (a QR net: no support)
     return FB_OK;
+}
+
+extern "C" int fb_qnet_get_quantiles(fb_qnet_t h, int *n_quantiles_host, float *kappa_host) {
+    FB_REQUIRE(h && n_quantiles_host && kappa_host, "fb_qnet_get_quantiles: NULL argument");
+    *n_quantiles_host = is_qr(h) ? h->sup.N : 0; *kappa_host = is_qr(h) ? h->kappa : 0.f;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_forward_quantiles(fb_qnet_t h, int which, const uint8_t *states, int batch, float *theta, void *stream) {
+    FB_REQUIRE(h && states && theta && (which == 0 || which == 1), "fb_qnet_forward_quantiles: bad argument");
+    FB_REQUIRE(is_qr(h), "fb_qnet_forward_quantiles: not a QR net (fb_qnet_create_qr)");
+    FB_REQUIRE(batch >= 1 && batch <= 3 * h->max_batch, "fb_qnet_forward_quantiles: batch %d exceeds 3*max_batch", batch);
+    Plan p = forward_plan(h, which, states, batch);
+    p.probs = theta;                             // (the QR head writes theta there)
+    return run_plan(h, p, -1, fb_stream(stream));
 }
 
 extern "C" int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream) {
     FB_REQUIRE(h && states && probs && (which == 0 || which == 1), "fb_qnet_forward_dist: bad argument");
-    FB_REQUIRE(h->sup.N > 0, "fb_qnet_forward_dist: not a C51 net (fb_qnet_create_c51)");
+    FB_REQUIRE(h->sup.N > 0 && !is_qr(h), "fb_qnet_forward_dist: not a C51 net (fb_qnet_create_c51; a QR net: fb_qnet_forward_quantiles)");
     FB_REQUIRE(batch >= 1 && batch <= 3 * h->max_batch, "fb_qnet_forward_dist: batch %d exceeds 3*max_batch", batch);
     Plan p = forward_plan(h, which, states, batch);
     p.probs = probs;
@@ -4637,7 +4796,9 @@ int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32
     C.off = h->hoff; C.sup = h->sup; C.actions = hd->c.actions; C.epsilon = hd->c.epsilon;
     C.seed_lo = hd->c.seed_lo; C.seed_hi = hd->c.seed_hi; C.step_lo = hd->c.step_lo; C.step_hi = hd->c.step_hi;
     C.key_of = key_of; C.stream = FB_STREAM_EVAL;
-    if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
+    if (is_qr(h) && h->A == 2) hipLaunchKernelGGL(qr_head_kernel<2>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
+    else if (is_qr(h)) hipLaunchKernelGGL(qr_head_kernel<MAXA>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
+    else if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
     else hipLaunchKernelGGL(c51_head_kernel<MAXA>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
     FB_LAUNCH_CHECK();
     return FB_OK;
@@ -4676,7 +4837,7 @@ int fb_qnet_check_step(fb_qnet_t h, int n_envs, int train_batch) {
 int fb_qnet_act_nib_rider(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
                           uint8_t *actions, FbHeadRider *head, void *stream, const FbSplitCtx *split) {
     FB_REQUIRE(h && nib_states && actions && head, "fb_qnet_act_nib_rider: NULL argument");
-    FB_REQUIRE(h->sup.N == 0, "fb_qnet_act_nib_rider: a C51 net's head does not ride in the env launch");
+    FB_REQUIRE(h->sup.N == 0, "fb_qnet_act_nib_rider: a C51 or QR net's head does not ride in the env launch");
     FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_qnet_act_nib: n %d exceeds 3*max_batch", n);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true;
@@ -4743,12 +4904,15 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
                       const uint8_t *t, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
     FB_REQUIRE(h && a && r && t && loss && (ring || (s && s2)), "fb_qnet_train_step: NULL argument");
-    FB_REQUIRE(algo >= 0 && algo <= FB_ALGO_C51_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
+    FB_REQUIRE(algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
     {
-        const bool c51a = is_c51_algo(algo);
-        FB_REQUIRE(c51a == (h->sup.N > 0), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
+        const bool c51a = is_c51_algo(algo), qra = is_qr_algo(algo);
+        FB_REQUIRE(c51a == (h->sup.N > 0 && !is_qr(h)), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
                                                 : "fb_qnet_train_step: a C51 net trains with FB_ALGO_C51, FB_ALGO_C51_PER, FB_ALGO_C51_DOUBLE_PER "
                                                   "or FB_ALGO_C51_DOUBLE only (got algo %d)", algo);
+        FB_REQUIRE(qra == is_qr(h), qra ? "fb_qnet_train_step: algo %d (QR) needs a QR net (fb_qnet_create_qr)"
+                                        : "fb_qnet_train_step: a QR net trains with FB_ALGO_QR, FB_ALGO_QR_DOUBLE, FB_ALGO_QR_PER or "
+                                          "FB_ALGO_QR_DOUBLE_PER only (got algo %d)", algo);
     }
     FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "fb_qnet_train_step: batch %d exceeds min(max_batch, %d)", B, MAXTB);
     FB_REQUIRE(algo != FB_ALGO_PG || (B <= 128 && !ring && gamma >= (double)B), "fb_qnet_train_step: FB_ALGO_PG takes chunks of <= 128 gathered states and gamma = the whole batch's sample count (>= %d)", B);
@@ -4758,7 +4922,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     p.ns = 2;
     p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
     if (algo == FB_ALGO_DQN || algo == FB_ALGO_PG) p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};               // BrainDQN.py:205 (same net); PG: s2 is forwarded and ignored
-    else if (algo == FB_ALGO_DOUBLE || is_double_c51(algo)) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
+    else if (algo == FB_ALGO_DOUBLE || is_double_c51(algo) || is_double_qr(algo)) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
     else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net (Nature, PER, C51, C51_PER)
     p.sl.rb = h->nsplit_train == 1;
     p.train = true; p.algo = algo; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.isw = isw; p.gamma = gamma;

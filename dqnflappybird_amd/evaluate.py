@@ -114,11 +114,22 @@ def evaluate(net, n_envs, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0
 def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
     """The online net of a VecBrain.save checkpoint (plain or dueling, told apart by the parameter count; C51 by its recorded support, and
     C51 or dueling C51 by its recorded head -- 'c51' where none is recorded; a noisy net by its recorded `noisy` / `sigma0`, in mean
-    mode).  max_batch sizes the net's
+    mode; a QR net by its recorded `quantiles` and head).  max_batch sizes the net's
     workspace: evaluation runs its acting forward in passes of up to 3 * max_batch rows."""
     from .vec import QNet
     z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz")
     online = np.ascontiguousarray(z["online"], np.float32)
+    if "quantiles" in z.files:                               # a QR net (VecBrain records its head and (N, kappa))
+        n_q, kappa = z["quantiles"].tolist()
+        head = str(z["head"][0])
+        if head not in ("qr", "qrdueling"):
+            raise ValueError(f"{path}: unknown QR head {head!r}")
+        net = QNet(2, fc_width, head, max_batch=max_batch, n_quantiles=int(n_q), kappa=kappa)
+        if net.n_params != online.size:
+            raise ValueError(f"{path}: {online.size} online parameters do not match a {head} net of width {fc_width} and {int(n_q)} quantiles")
+        net.load_params(online, 0)
+        net.set_inference_dtype(dtype)
+        return net
     if "support" in z.files:                                 # a C51 net (VecBrain records its support)
         n_atoms, v_min, v_max = z["support"].tolist()
         head = str(z["head"][0]) if "head" in z.files else "c51"

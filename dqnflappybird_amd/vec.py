@@ -277,12 +277,18 @@ class VecReplay:
 
 
 ALGOS = {"dqn": L.ALGO_DQN, "nature": L.ALGO_NATURE, "double": L.ALGO_DOUBLE, "per": L.ALGO_PER, "pg": L.ALGO_PG,
-         "c51": L.ALGO_C51, "c51double": L.ALGO_C51_DOUBLE, "c51per": L.ALGO_C51_PER, "c51doubleper": L.ALGO_C51_DOUBLE_PER}
+         "c51": L.ALGO_C51, "c51double": L.ALGO_C51_DOUBLE, "c51per": L.ALGO_C51_PER, "c51doubleper": L.ALGO_C51_DOUBLE_PER,
+         "qr": L.ALGO_QR, "qrdouble": L.ALGO_QR_DOUBLE, "qrper": L.ALGO_QR_PER, "qrdoubleper": L.ALGO_QR_DOUBLE_PER}
 C51_ALGOS = ("c51", "c51double")                            # C51 on a uniform memory
 C51_PER_ALGOS = ("c51per", "c51doubleper")                  # C51 on a prioritized memory (weighted loss, KL priorities)
-PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the algos that take a prioritized memory and its importance weights
+QR_ALGOS = ("qr", "qrdouble")                               # QR-DQN on a uniform memory
+QR_PER_ALGOS = ("qrper", "qrdoubleper")                     # QR-DQN on a prioritized memory (weighted loss, l_b priorities)
+PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the scalar and C51 algos that take a prioritized memory
+PRIORITIZED_ALGOS = PER_ALGOS + QR_PER_ALGOS                # every algo that takes a prioritized memory and its importance weights
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
 C51_ARCHS = ("c51", "c51dueling")                         # distributional heads: C51, and the dueling C51 head (Rainbow's)
+QR_ARCHS = ("qr", "qrdueling")                            # quantile heads: QR-DQN, and its dueling form
+QR_DEFAULT_QUANTILES = (51, 1.0)                          # n_quantiles, kappa (include/fbdqn.h; the size of C51's default head)
 ACTING_NOISE_MODES = ("shared", "env")                  # noisy nets: one noise sample for all envs when acting, or one per env
 NOISY_DEFAULT_SIGMA0 = 0.5                                # noisy nets: sigma = sigma0 / sqrt(fan_in) at init (Fortunato et al.)
 
@@ -314,6 +320,19 @@ def check_support(n_atoms, v_min, v_max, actions=2):
     return n_atoms, v_min, v_max
 
 
+def check_quantiles(n_quantiles, kappa, actions=2):
+    """the argument checks of fb_qnet_create_qr, on the host (-> (n_quantiles, kappa) as int, float32-rounded float)"""
+    n = int(n_quantiles)
+    if not 2 <= n <= L.C51_MAX_ATOMS:
+        raise ValueError(f"n_quantiles must be in 2..{L.C51_MAX_ATOMS}, got {n}")
+    if int(actions) * n > 128:
+        raise ValueError(f"actions x n_quantiles must be <= 128, got {int(actions)} x {n}")
+    k = float(np.float32(kappa))
+    if not (np.isfinite(k) and k > 0.0):
+        raise ValueError(f"kappa must be finite and > 0, got {kappa}")
+    return n, k
+
+
 def bootstrap_gamma(gamma, n):
     """Gamma = g_n of the n-step return (g_0 = 1, g_{k+1} = g_k * gamma in float64): the discount an n-step target bootstraps with,
     and what QNet.train_step takes on a minibatch gathered from an n-step memory.  gamma itself at n = 1."""
@@ -329,12 +348,15 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
-    ARCHS = ("plain", "dueling") + C51_ARCHS
+    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS
 
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
-                 v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0):
+                 v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0,
+                 n_quantiles=QR_DEFAULT_QUANTILES[0], kappa=QR_DEFAULT_QUANTILES[1]):
         """arch='c51': the distributional head of include/fbdqn.h (n_atoms atoms on [v_min, v_max]; the support args are ignored otherwise);
         arch='c51dueling': the dueling C51 head (value and advantage distributions, include/fbdqn.h) on the same support.
+        arch='qr' / 'qrdueling': the quantile head of QR-DQN (n_quantiles quantiles, quantile Huber loss with threshold kappa; include/fbdqn.h)
+        and its dueling form; n_quantiles / kappa are ignored otherwise.
         noisy=True (C51 archs only): factorised Gaussian noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the flat
         vector is [mu | sigma], and the net starts in mean mode (reset_noise, noise; include/fbdqn.h)"""
         if arch not in self.ARCHS:
@@ -348,6 +370,8 @@ class QNet:
             self.sigma0 = check_sigma0(sigma0)
         if arch in C51_ARCHS:
             n_atoms, v_min, v_max = check_support(n_atoms, v_min, v_max, actions)
+        if arch in QR_ARCHS:
+            n_quantiles, kappa = check_quantiles(n_quantiles, kappa, actions)
         L.require_gpu()
         self.A, self.FC, self.max_batch = int(actions), int(fc_width), int(max_batch)
         self.dueling = arch == "dueling"
@@ -362,6 +386,9 @@ class QNet:
         elif arch == "c51dueling":
             L.check(L.lib().fb_qnet_create_c51_dueling(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)),
                     "fb_qnet_create_c51_dueling")
+        elif arch in QR_ARCHS:
+            L.check(L.lib().fb_qnet_create_qr(L.ARCH_QR if arch == "qr" else L.ARCH_QR_DUELING, self.FC, self.A, n_quantiles, kappa,
+                                              self.max_batch, C.byref(self.h)), "fb_qnet_create_qr")
         else:
             L.check(L.lib().fb_qnet_create(L.ARCH_DUELING if self.dueling else L.ARCH_PLAIN, self.FC, self.A, self.max_batch,
                                            C.byref(self.h)), "fb_qnet_create")
@@ -496,6 +523,12 @@ class QNet:
         L.check(L.lib().fb_qnet_get_support(self.h, C.byref(n), C.byref(lo), C.byref(hi)), "fb_qnet_get_support")
         return (n.value, lo.value, hi.value) if n.value else None
 
+    def quantiles(self):
+        """(n_quantiles, kappa) of a QR net (fb_qnet_get_quantiles), None for any other head"""
+        n, k = C.c_int(), C.c_float()
+        L.check(L.lib().fb_qnet_get_quantiles(self.h, C.byref(n), C.byref(k)), "fb_qnet_get_quantiles")
+        return (n.value, k.value) if n.value else None
+
     def atoms(self):
         """the support values z_i = v_min + i * dz as float32 (the device's arithmetic), or None"""
         sup = self.support
@@ -518,6 +551,19 @@ class QNet:
         p = torch.empty((B, self.A, sup[0]), dtype=torch.float32, device=self.device)
         L.check(L.lib().fb_qnet_forward_dist(self.h, which, L.ptr(states), B, L.ptr(p), L.current_stream()), "fb_qnet_forward_dist")
         return p
+
+    def forward_quantiles(self, states, which=L.NET_ONLINE):
+        """QR nets: the quantiles theta f32[B, A, n_quantiles] of u8 states (fb_qnet_forward_quantiles)"""
+        _dev_check(states)
+        qs = self.quantiles()
+        if qs is None:
+            raise ValueError("forward_quantiles needs a QR net (arch='qr' or 'qrdueling')")
+        B = states.shape[0]
+        if states.dtype != torch.uint8 or tuple(states.shape[1:]) != (80, 80, 4):
+            raise ValueError("states must be uint8[B,80,80,4]")
+        th = torch.empty((B, self.A, qs[0]), dtype=torch.float32, device=self.device)
+        L.check(L.lib().fb_qnet_forward_quantiles(self.h, which, L.ptr(states), B, L.ptr(th), L.current_stream()), "fb_qnet_forward_quantiles")
+        return th
 
     def forward(self, states, which=L.NET_ONLINE):
         _dev_check(states)
@@ -596,7 +642,7 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
     SumTree leaf indices of replay.sample, isw its importance weights; want_abs_err returns |TD error| for update_priorities.
     An n-step memory (replay.set_n_step) is read as (s, a, R, s', done) and bootstrapped with gamma^n; gamma must be the memory's.
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, abs_err f32[B]]) on the device."""
-    if (replay.prioritized or algo in PER_ALGOS) and isw is None:
+    if (replay.prioritized or algo in PRIORITIZED_ALGOS) and isw is None:
         raise ValueError("the prioritized step needs the importance weights (isw)")
     _dev_check(idx, flat_grad, isw)
     B, dev = int(idx.numel()), idx.device
@@ -617,7 +663,7 @@ class TrainSteps:
     n-step memory gamma must be the memory's (the steps bootstrap with gamma^n)."""
 
     def __init__(self, replay, net, batch=32, algo="dqn", gamma=0.99):
-        if replay.prioritized or algo in PER_ALGOS:
+        if replay.prioritized or algo in PRIORITIZED_ALGOS:
             raise ValueError("TrainSteps is for uniform replay (PER needs the importance weights: use the separate calls)")
         self.replay, self.net, self.batch, self.algo, self.gamma = replay, net, batch, ALGOS[algo], float(gamma)
         dev, B = replay.device, batch
@@ -651,8 +697,12 @@ class VecStep:
             raise ValueError(f"algo {algo!r} trains from a uniform memory only (prioritized replay with C51 is not supported)")
         if algo in C51_ALGOS + C51_PER_ALGOS and dist is not None:
             raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (one GPU only)")
-        if replay.prioritized != (algo in PER_ALGOS):
-            raise ValueError(f"algos {PER_ALGOS} go with a prioritized memory, every other algo with a uniform one (algo {algo!r})")
+        if algo in QR_ALGOS and replay.prioritized:
+            raise ValueError(f"algo {algo!r} trains from a uniform memory only (QR with prioritized replay is 'qrper' / 'qrdoubleper')")
+        if algo in QR_ALGOS + QR_PER_ALGOS and dist is not None:
+            raise ValueError(f"algo {algo!r}: data-parallel QR is not supported (one GPU only)")
+        if replay.prioritized != (algo in PRIORITIZED_ALGOS):
+            raise ValueError(f"algos {PRIORITIZED_ALGOS} go with a prioritized memory, every other algo with a uniform one (algo {algo!r})")
         if dist is not None and flat_grad is None:
             raise ValueError("VecStep(dist=...) needs the flat_grad buffer the gradient is reduced in")
         self.dist, self.mean_loss = dist, int(bool(mean_loss))
@@ -670,7 +720,7 @@ class VecStep:
         self.r = torch.empty(B, dtype=torch.float32, device=dev)
         self.t = torch.empty(B, dtype=torch.uint8, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        per = algo in PER_ALGOS                            # Memory.sample's weights (f64, and as the float32 placeholder takes them), |TD errors|
+        per = algo in PRIORITIZED_ALGOS                    # Memory.sample's weights (f64, and as the float32 placeholder takes them), |TD errors|
         self.isw = torch.zeros(B, dtype=torch.float64, device=dev) if per else None
         self.isw32 = torch.zeros(B, dtype=torch.float32, device=dev) if per else None
         self.abs_err = torch.zeros(B, dtype=torch.float32, device=dev) if per else None

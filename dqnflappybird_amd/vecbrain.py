@@ -10,16 +10,21 @@ timeStep % 500 == 0, PER never does (the reference agent's quirk, kept for algo 
 replay ('c51per' / 'c51doubleper') sync every replace_target_iter steps.  arch='c51dueling' gives any of the C51 algos the dueling
 C51 head (Rainbow's, with 'c51doubleper' and n-step returns: FlappyBirdDQN.py --model rainbow).  noisy=True gives a C51 algo's net
 noisy fc1 and head layers (NoisyNet; with arch='c51dueling', 'c51doubleper' and n-step returns: full Rainbow, --model rainbow --noisy):
-fb_vec_step draws the nets' noise every step, and the epsilon schedule defaults to 0.
+fb_vec_step draws the nets' noise every step, and the epsilon schedule defaults to 0.  QR-DQN ('qr', 'qrdouble', 'qrper',
+'qrdoubleper') trains a quantile head (arch 'qr', or 'qrdueling' for its dueling form) on one GPU and syncs as C51 does.
 """
 from . import dist as fdist
 
-MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True, "c51per": True, "c51doubleper": True}
+MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True, "c51per": True, "c51doubleper": True,
+             "qr": True, "qrdouble": True, "qrper": True, "qrdoubleper": True}
 C51_ALGOS = ("c51", "c51double")                             # distributional Q-learning (include/fbdqn.h, DESIGN.md section 11)
 C51_PER_ALGOS = ("c51per", "c51doubleper")                   # ... with prioritized replay: weighted loss, KL priorities
-PER_ALGOS = ("per",) + C51_PER_ALGOS                         # algos with a prioritized memory
-TARGET_SYNC = ("nature", "double") + C51_ALGOS + C51_PER_ALGOS   # algos whose target net is synced every replace_target_iter steps
+QR_ALGOS = ("qr", "qrdouble")                                # quantile regression (QR-DQN; include/fbdqn.h, DESIGN.md section 12)
+QR_PER_ALGOS = ("qrper", "qrdoubleper")                      # ... with prioritized replay: weighted loss, l_b priorities
+PER_ALGOS = ("per",) + C51_PER_ALGOS + QR_PER_ALGOS          # algos with a prioritized memory
+TARGET_SYNC = ("nature", "double") + C51_ALGOS + C51_PER_ALGOS + QR_ALGOS + QR_PER_ALGOS   # algos whose target net is synced every replace_target_iter steps
 C51_HEADS = ("c51", "c51dueling")                            # the heads a C51 algo trains (arch; 'plain' means 'c51')
+QR_HEADS = ("qr", "qrdueling")                               # the heads a QR algo trains (arch; 'plain' means 'qr')
 
 
 class HipVecBackend:
@@ -43,9 +48,12 @@ class HipVecBackend:
     c51_dueling = True                                       # ... with the dueling C51 head as well (net(..., arch='c51dueling', support=...))
     c51_noisy = True                                         # ... and noisy C51 nets (net(..., support=..., noisy=True, sigma0=s))
     acting_noise_env = True                                  # ... which can act with noise per env (net.set_acting_noise('env'))
+    qr = True                                                # quantile nets (net(..., arch='qr' | 'qrdueling', quantiles=(n_quantiles, kappa)))
 
-    def net(self, actions, fc_width, arch, max_batch, support=None, noisy=False, sigma0=0.5):
+    def net(self, actions, fc_width, arch, max_batch, support=None, noisy=False, sigma0=0.5, quantiles=None):
         from .vec import QNet
+        if quantiles is not None:
+            return QNet(actions, fc_width, arch, max_batch=max_batch, n_quantiles=quantiles[0], kappa=quantiles[1])
         if support is not None:
             return QNet(actions, fc_width, arch if arch in C51_HEADS else "c51", max_batch=max_batch, n_atoms=support[0], v_min=support[1],
                         v_max=support[2], noisy=noisy, sigma0=sigma0)
@@ -104,6 +112,35 @@ def check_checkpoint_head(z, head, path):
                          "do not convert)")
 
 
+def checkpoint_head(z):
+    """the head a checkpoint holds: its recorded `head`, else 'c51' where it records a support, else 'scalar'"""
+    if "head" in z.files:
+        return str(z["head"][0])
+    return "c51" if "support" in z.files else "scalar"
+
+
+def check_checkpoint_quantiles(z, quantiles, head, path):
+    """a QR checkpoint goes into a QR brain with the same head, N and kappa only, and a QR brain takes a QR checkpoint only (C51 and
+    N = 51 QR heads have the same parameter count: the recorded head is what tells them apart)"""
+    saved_head = checkpoint_head(z)
+    saved_qr = saved_head in QR_HEADS
+    if saved_qr and quantiles is None:
+        raise ValueError(f"checkpoint {path} holds a {saved_head} (QR) head, this VecBrain has a {head} head (QR and other parameters "
+                         "do not convert)")
+    if not saved_qr and quantiles is not None:
+        raise ValueError(f"checkpoint {path} holds a {saved_head} head, this VecBrain has a {head} (QR) head (QR and other parameters "
+                         "do not convert)")
+    if quantiles is None:
+        return
+    if saved_head != head:
+        raise ValueError(f"checkpoint {path} holds a {saved_head} head, this VecBrain has a {head} head (QR and dueling QR parameters "
+                         "do not convert)")
+    n, k = z["quantiles"].tolist()
+    if (int(n), float(k)) != (int(quantiles[0]), float(quantiles[1])):
+        raise ValueError(f"checkpoint {path} was trained with (n_quantiles, kappa) = ({int(n)}, {float(k)}), this VecBrain has "
+                         f"({int(quantiles[0])}, {float(quantiles[1])})")
+
+
 def check_checkpoint_noisy(z, noisy, sigma0, path):
     """a checkpoint's net must be noisy exactly when this brain's is (checkpoints that record nothing hold a non-noisy net)"""
     saved = bool(z["noisy"][0]) if "noisy" in z.files else False
@@ -128,7 +165,7 @@ class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0,
-                 noisy=False, sigma0=0.5, acting_noise="shared"):
+                 noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
@@ -137,7 +174,9 @@ class VecBrain:
         noisy=True (C51 algos only): noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the exploration comes from
         the noise, so initial_epsilon defaults to 0 (0.03 without noise, the reference's); an explicit initial_epsilon is honoured.
         acting_noise (noisy nets): 'shared' -- one noise sample per step for all envs -- or 'env': independent noise per env when acting
-        (include/fbdqn.h); training is the same in both, and checkpoints do not record it."""
+        (include/fbdqn.h); training is the same in both, and checkpoints do not record it.
+        algo 'qr' / 'qrdouble' / 'qrper' / 'qrdoubleper': QR-DQN with n_quantiles quantiles and the quantile Huber loss's kappa (one GPU,
+        any n_step; the PER forms on a prioritized memory), on arch 'qr' ('plain' means it) or 'qrdueling'; no noisy QR nets."""
         n_step = int(n_step)
         noisy = bool(noisy)
         if acting_noise not in ("shared", "env"):
@@ -153,7 +192,25 @@ class VecBrain:
             raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no per-env acting noise (acting_noise_env): "
                              f"acting_noise='env' needs it")
         self.support = None
-        if algo in C51_ALGOS + C51_PER_ALGOS:
+        self.quantiles = None
+        if algo in QR_ALGOS + QR_PER_ALGOS:
+            from .vec import check_quantiles
+            if arch not in ("plain",) + QR_HEADS:
+                raise ValueError(f"algo {algo!r} builds a QR head on the plain trunk: arch {arch!r} is not one (dueling QR is arch='qrdueling')")
+            if world > 1:
+                raise ValueError(f"algo {algo!r}: data-parallel QR is not supported (world = {world}; one GPU only)")
+            if noisy:
+                raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with the QR algo {algo!r}")
+            if not getattr(be, "qr", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no QR nets")
+            if algo in QR_PER_ALGOS and not getattr(be, "per_one_step", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
+                                 f"algo {algo!r} needs it")
+            self.quantiles = check_quantiles(n_quantiles, kappa)
+            arch = "qrdueling" if arch == "qrdueling" else "qr"
+        elif arch in QR_HEADS:
+            raise ValueError(f"arch {arch!r} is a QR head: it trains with a QR algo ('qr', 'qrdouble', 'qrper', 'qrdoubleper'), not {algo!r}")
+        elif algo in C51_ALGOS + C51_PER_ALGOS:
             from .vec import check_support
             if arch not in ("plain",) + C51_HEADS:
                 raise ValueError(f"algo {algo!r} builds a C51 head on the plain trunk: arch {arch!r} is not one "
@@ -211,6 +268,8 @@ class VecBrain:
             from .vec import check_sigma0
             self.sigma0 = check_sigma0(sigma0)
             self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support, noisy=True, sigma0=self.sigma0)
+        elif self.quantiles:
+            self.net = be.net(2, fc_width, arch, max(n_envs, batch), quantiles=self.quantiles)
         else:
             self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support) if self.support else be.net(2, fc_width, arch, max(n_envs, batch))
         self.acting_noise = acting_noise
@@ -352,6 +411,9 @@ class VecBrain:
             if self.support is not None:                     # (scalar-head checkpoints carry no support)
                 shared["support"] = np.array(self.support, np.float64)
                 shared["head"] = np.array([self.arch])       # 'c51' or 'c51dueling' (checkpoints without it: 'c51')
+            if self.quantiles is not None:                   # QR: the head ('qr' / 'qrdueling') and (N, kappa)
+                shared["head"] = np.array([self.arch])
+                shared["quantiles"] = np.array(self.quantiles, np.float64)
             if self.noisy:                                   # online / target / Adam hold [mu | sigma] (checkpoints without it: not noisy)
                 shared["noisy"] = np.array([1], np.int64)
                 shared["sigma0"] = np.array([self.sigma0], np.float64)
@@ -374,6 +436,7 @@ class VecBrain:
         saved_n = int(z["n_step"][0]) if "n_step" in z.files else 1          # (checkpoints from before n-step returns: one-step)
         if saved_n != self.n_step:
             raise ValueError(f"checkpoint {path} was trained with n_step = {saved_n}, this VecBrain has n_step = {self.n_step}")
+        check_checkpoint_quantiles(z, self.quantiles, self.arch, path)
         check_checkpoint_support(z, self.support, path)
         if self.support is not None:
             check_checkpoint_head(z, self.arch, path)

@@ -407,6 +407,43 @@ int fb_qnet_act_nib_env_noise(fb_qnet_t h, const uint8_t *nib_states, int n, flo
 int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_host, float *v_max_host);      /* n_atoms = 0: not a C51 net */
 int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream);
 
+/* ------------------------------------------------------------------ quantile regression (QR-DQN, Dabney, Rowland, Bellemare & Munos 2018)
+ * A QR net keeps the plain trunk and fc1; its head has the C51 head's shape (N = n_quantiles, column a*N + i is quantile i of action a):
+ *   FB_ARCH_QR          W_fc2[FC, A*N] b[A*N]
+ *   FB_ARCH_QR_DUELING  W_v[FC, N] b_v[N] W_a[FC, A*N] b_a[A*N]; theta[a][i] = V_i + Adv[a][i] - (1/A) sum_a' Adv[a'][i], as dueling C51
+ * 2 <= N <= 64, A * N <= 128, kappa finite and > 0, all checked by fb_qnet_create_qr before any allocation.  fb_qnet_init_params makes the
+ * same draws as the C51 net of the same shape and seed (equal parameters bit for bit).
+ *   quantiles   theta[b][a][i] = relu(h_fc1[b]) . W[:, a*N + i] + b[a*N + i] (through the folded head for the dueling form)
+ *   midpoints   tau_i = (2i + 1) / (2N)
+ *   Q           Q[b][a] = (1/N) sum_i theta[b][a][i]: what fb_qnet_forward / _act / _act_nib / fb_eval_q / fb_eval_run return; acting and
+ *               evaluation take its first maximum and the plain net's epsilon rule (same Philox draws)
+ *   target      a* = argmax_a Q(s', a) of the target net (FB_ALGO_QR) or of the online net (FB_ALGO_QR_DOUBLE); the quantiles always come
+ *               from the target net: T_j = R + Gamma (1 - done) theta_target(s', a*)_j.  No clamp, no projection; Gamma = gamma^n as DESIGN.md
+ *               section 10 forms it (n-step memories work unchanged)
+ *   loss        u_ij = T_j - theta_i (the taken action a_b, targets constant), L_k(u) = u^2 / 2 if |u| <= k else k (|u| - k / 2),
+ *               rho_ij = |tau_i - 1{u_ij < 0}| L_k(u_ij) / k, l_b = (1/N) sum_i sum_j rho_ij, loss = mean_b l_b in fp32
+ *   gradient    dl_b/dtheta_i = -(1/N) sum_j |tau_i - 1{u_ij < 0}| clamp(u_ij, -k, k) / k on the taken action (0 elsewhere), divided by B.
+ *               Lane i sums over j = 0 .. N-1 in that order: deterministic, no atomics.  abs_err / q_target are not written (uniform algos).
+ *   worked case N = 2, k = 1, theta = [0, 1], T = [0.5, 3]: l = 0.90625, dl/dtheta = [-0.1875, -0.3125]
+ *   prioritized FB_ALGO_QR_PER (target as FB_ALGO_QR) and FB_ALGO_QR_DOUBLE_PER (target as _DOUBLE) take a prioritized memory and isw only:
+ *               loss = (1/B) sum_b w_b l_b; gradient = (that of l_b / B) * w_b, formed in that order (w = 1 gives the uniform algo's results
+ *               bit for bit); abs_err[b] = l_b, without the weight (>= 0).  Memory.batch_update is unchanged.
+ * FB_ALGO_QR / _DOUBLE take a uniform memory only.  The target net syncs as for C51.  Every entry point that takes a C51 net takes a QR
+ * net with a QR algo, but for these: FB_ERR_INVALID before any launch or counter change for a QR algo on another net or another algo on a
+ * QR net, fb_vec_step_dp, fb_qnet_forward_dist, noisy / per-env acting noise calls; fb_qnet_create refuses archs 4 and 5;
+ * fb_qnet_get_support reports n_atoms = 0.
+ * fb_qnet_get_quantiles: N and kappa of a QR net (n = 0 for any other net).  fb_qnet_forward_quantiles: theta (f32[B][A][N], [dev]) of
+ * `which` net for u8 states, 1 <= B <= 3 * max_batch. */
+#define FB_ARCH_QR 4
+#define FB_ARCH_QR_DUELING 5
+#define FB_ALGO_QR 9
+#define FB_ALGO_QR_DOUBLE 10
+#define FB_ALGO_QR_PER 11
+#define FB_ALGO_QR_DOUBLE_PER 12
+int fb_qnet_create_qr(int arch, int fc_width, int n_actions, int n_quantiles, float kappa, int max_batch, fb_qnet_t *out);
+int fb_qnet_get_quantiles(fb_qnet_t h, int *n_quantiles_host, float *kappa_host);
+int fb_qnet_forward_quantiles(fb_qnet_t h, int which, const uint8_t *states, int batch, float *theta, void *stream);
+
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
 int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host);
