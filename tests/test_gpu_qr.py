@@ -140,16 +140,16 @@ def test_initial_parameters_equal_the_c51_nets(torch_cuda, arch, c51arch):
 
 
 # ---------------------------------------------------------------------------------------------------------------- training
-def _run_grad_case(torch, net, p_on, p_tg, algo, s, a, r, s2, t, G, N, kappa, arch="qr", w=None):
+def _run_grad_case(torch, net, p_on, p_tg, algo, s, a, r, s2, t, G, N, kappa, arch="qr", w=None, A=2, fc=FC):
     d = lambda x: torch.from_numpy(x).cuda()
     dev_astar = net.forward(d(s2), 0 if algo in DOUBLE else 1).argmax(1).cpu().numpy()
     grad = torch.zeros(net.n_params, dtype=torch.float32, device="cuda")
     before = net.store_params().clone()
     isw = d(w.astype(np.float32)) if w is not None else None
     loss, ae, _ = net.train_step(algo, d(s), d(a), d(r), d(s2), d(t), isw=isw, gamma=G, flat_grad=grad)
-    loss0, g0, lb, umax = ref_train(p_on, p_tg, s, a, r, s2, t, w, G, algo, N, kappa, dev_astar, arch)
+    loss0, g0, lb, umax = ref_train(p_on, p_tg, s, a, r, s2, t, w, G, algo, N, kappa, dev_astar, arch, A, fc)
     np.testing.assert_allclose(loss.item(), loss0, rtol=1e-4, atol=1e-6)
-    check_grads(grad.cpu().numpy(), g0, N, arch)
+    check_grads(grad.cpu().numpy(), g0, N, arch, A, fc)
     if w is not None:
         np.testing.assert_allclose(ae.cpu().numpy(), lb, rtol=1e-4, atol=1e-6)
     assert torch.equal(net.store_params(), before)              # gradient export leaves the parameters alone

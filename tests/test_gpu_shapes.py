@@ -22,6 +22,11 @@ Which case reaches which instantiation (dqnflappybird_amd/csrc/):
   wsplit / hf_act sizing                                       test_scalar_act_nib (the fused acting trunk), test_c51_forward
   adam_fused_kernel tail (n & 3)                               test_scalar_adam_bit_exact: parameter counts = 0, 1, 2, 3 (mod 4)
   C51 bf16 operands (fb_qnet_set_inference / train_dtype)      test_c51_bf16_inference, test_c51_bf16_training
+  qr_head_kernel<2 | MAXA>, qr_loss_kernel<2 | MAXA, *>,        tests/test_gpu_qr_shapes.py (written after QR-DQN was added; its docstring
+  QR bf16 operands                                             maps each instantiation to its cases): test_qr_forward, test_qr_acting,
+                                                               test_qr_train_step, test_qr_dueling_train_step, test_qr_bf16_*
+  first maximum on exact ties (every head kind), the QR        tests/test_gpu_exact_heads.py
+  loss's worked case and kinks on the kernel
 """
 import zlib
 
