@@ -4230,7 +4230,6 @@ enum KernelId {
 
 struct Plan {
     Slices sl; int ns;                       // forward slices
-    int which;                               // forward-only plans: the net the single slice runs through
     bool nib;                                // states are the env's nibble state (acting path)
     uint8_t *actions; float epsilon; uint64_t seed, step;
     bool train;                              // forward only when false
@@ -4249,256 +4248,360 @@ struct Plan {
     bool no_head;                            // C51 forward plans: conv1 .. fc1 only (fb_qnet_act_nib_env_noise launches its own head)
 };
 
-static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
-#define FB_K(id) if (only < 0 || only == (id))
-    int maxc = 0, total = 0;
-    for (int z = 0; z < p.ns; z++) { if (p.sl.s[z].count > maxc) maxc = p.sl.s[z].count; total += p.sl.s[z].count; }
+// A runtime value as a template argument: f is a generic lambda and gets a tag whose ::value is a constant expression, so that a kernel
+// template has ONE launch statement per call site, hipLaunchKernelGGL((kernel<decltype(tag)::value, ...>), ...), not one per instantiation
+#include <type_traits>
+template <int V> using IntTag = std::integral_constant<int, V>;
+template <class F> static void with_nsp(int nsp, F f) { if (nsp == 3) f(IntTag<3>{}); else f(IntTag<1>{}); }
+template <class F> static void with_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_actions(int A, F f) { if (A == 2) f(IntTag<2>{}); else f(IntTag<MAXA>{}); }
+
+template <class T> static void put_seed_words(T &c, uint64_t seed, uint64_t step) {      // the four words the head kernels take
+    c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
+    c.step_lo = (uint32_t)step; c.step_hi = (uint32_t)(step >> 32);
+}
+
+// What the stages of a plan share: where it runs and the values derived from the plan.  run_plan below is the sequence of the stages.
+struct PlanCtx {
+    int only; hipStream_t st;                // `only` < 0: the whole plan; else the launches of that KernelId alone
+    int maxc, total;                         // states of the largest slice / of all slices
+    bool big, trunk, fused, c51;
+    int nsp, stot; size_t pl1, pl2;          // stot: rows of the workspace; pl1 / pl2: its plane pitch after conv1 / conv2, conv3
+};
+static bool runs(const PlanCtx &c, int id) { return c.only < 0 || c.only == id; }      // the launches of KernelId `id` are part of this run
+
+static PlanCtx plan_ctx(const fb_qnet *h, const Plan &p, int only, hipStream_t st) {
+    PlanCtx c{only, st, 0, 0};
+    for (int z = 0; z < p.ns; z++) { if (p.sl.s[z].count > c.maxc) c.maxc = p.sl.s[z].count; c.total += p.sl.s[z].count; }
     // >= 256 samples in a slice: thousands of tiles, one wave per tile (no K split); below: K split over waves
-    const bool big = maxc >= 256 || p.any_rows;
     // >= 256 states per slice: the LDS-staged two-plane-fp16 kernels (conv1_sp / conv23_sp / fc1_sp).  Forward-only plans take
     // them with one slice; TRAINING plans run them in passes, one per run of consecutive slices that go through the same net
     // (DQN: s and s' in one pass; Nature / PER: s online, s' target; Double: s, s' online + s' target), with fp32 side outputs
     // (pooled conv1 + pool positions, conv2, conv3) for the backward kernels.  nsp: 3 = fp32-equivalent, 1 = bf16 operands.
-    const bool sp = big;
-    const int nsp = p.train ? h->nsplit_train : h->nsplit;
-    const int t1 = (maxc * 100 + 7) / 8;
-    const size_t S = (size_t)3 * h->max_batch, pl1 = S * 3200, pl2 = S * 1600;
-    const int stot = 3 * h->max_batch;
-    // small batches: conv2 + conv3 in one launch on the split planes (conv23_t_kernel); the conv1 launch in front re-splits the conv
-    // weights of every net of the plan whose parameters moved (decided on the device), the conv2+conv3 launch records it
-    SplitJob job;
+    c.big = c.maxc >= 256 || p.any_rows;
+    c.nsp = p.train ? h->nsplit_train : h->nsplit;
+    c.stot = 3 * h->max_batch; c.pl1 = (size_t)c.stot * 3200; c.pl2 = (size_t)c.stot * 1600;
+    c.trunk = p.ring != nullptr;                 // ring-fed minibatch (any batch size): the whole conv trunk per state in one launch
+    // the acting path on nibble states (forward-only plans of one slice): conv1 + conv2 + conv3 in ONE launch
+    // (conv23_sp_kernel<., 5, true>), five states per workgroup.  Its fc1 partial sums are in hf_act, its head parameters in hp_act
+    c.fused = c.big && p.nib && !p.train && !c.trunk && p.ns == 1;
+    c.c51 = h->sup.N > 0;
+    return c;
+}
+
+// small batches: conv2 + conv3 in one launch on the split planes (conv23_t_kernel); the conv1 launch in front re-splits the conv
+// weights of every net of the plan whose parameters moved (decided on the device), the conv2+conv3 launch records it
+static C23T trunk_args(fb_qnet *h, const Plan &p, const PlanCtx &c, SplitJob *job) {      // job: conv1_pool_kernel's
     C23T c23t;
-    memset(&job, 0, sizeof(job)); memset(&c23t, 0, sizeof(c23t));
-    const bool trunk = p.ring != nullptr;        // ring-fed minibatch (any batch size): the whole conv trunk per state in one launch
-    bool acting_fused = false;                   // the fused acting forward ran: its fc1 partial sums are in hf_act, its head parameters in hp_act
-    if (!sp || trunk) {
-        job.FC = h->FC;
-        c23t.sl = p.sl; c23t.p1 = h->p1; c23t.h2 = h->h2; c23t.h3 = h->h3; c23t.ovf = &h->adam->ovf;
-        for (int z = 0; z < p.ns; z++) {
-            const int which = p.sl.s[z].params == h->params[1] ? 1 : 0;
-            c23t.w[z] = h->wsp[which] + WSP_W2;
-            if (only < 0) {
-                job.params[which] = h->params[which]; job.wsp[which] = h->wsp[which];
-                job.pver[which] = &h->adam->pver[which]; job.wverc[which] = &h->adam->wverc[which];
-                c23t.pver[which] = &h->adam->pver[which]; c23t.wverc[which] = &h->adam->wverc[which];
-            }
+    memset(job, 0, sizeof(*job)); memset(&c23t, 0, sizeof(c23t));
+    job->FC = h->FC;
+    c23t.sl = p.sl; c23t.p1 = h->p1; c23t.h2 = h->h2; c23t.h3 = h->h3; c23t.ovf = &h->adam->ovf;
+    for (int z = 0; z < p.ns; z++) {
+        const int which = p.sl.s[z].params == h->params[1] ? 1 : 0;
+        c23t.w[z] = h->wsp[which] + WSP_W2;
+        if (c.only < 0) {
+            job->params[which] = h->params[which]; job->wsp[which] = h->wsp[which];
+            job->pver[which] = &h->adam->pver[which]; job->wverc[which] = &h->adam->wverc[which];
+            c23t.pver[which] = &h->adam->pver[which]; c23t.wverc[which] = &h->adam->wverc[which];
         }
     }
-    if (trunk) FB_K(K_CONV2) {                       // conv1 + pool + conv2 + conv3 of every state in ONE launch
-        if (sp) { c23t.a3s = h->a3s; c23t.pl3 = pl2; }      // >= 256 states per slice: fc1_sp_kernel follows and reads conv3's output as planes
-        c23t.ring = *p.ring; c23t.p1o = h->p1; c23t.amax = h->amax; c23t.ring_fo = h->ring_fo;
-        const bool w16 = maxc * p.ns <= 256;          // at most one workgroup per CU anyway: spend the idle SIMD slots on conv1's second round
-        if (p.ring->c.nstep > 1) {                    // n-step view: the same kernels with the n-step return (NST)
-            if (nsp == 3 && w16) hipLaunchKernelGGL((conv23_t_kernel<3, true, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
-            else if (nsp == 3) hipLaunchKernelGGL((conv23_t_kernel<3, true, false, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
-            else if (w16) hipLaunchKernelGGL((conv23_t_kernel<1, true, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
-            else hipLaunchKernelGGL((conv23_t_kernel<1, true, false, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
-        }
-        else if (nsp == 3 && w16) hipLaunchKernelGGL((conv23_t_kernel<3, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
-        else if (nsp == 3) hipLaunchKernelGGL((conv23_t_kernel<3, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
-        else if (w16) hipLaunchKernelGGL((conv23_t_kernel<1, true, true>), dim3(maxc, p.ns), dim3(1024), 0, st, c23t);
-        else hipLaunchKernelGGL((conv23_t_kernel<1, true>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
-    }
-    if (sp) {
-        for (int z0 = 0; z0 < p.ns;) {
-            int z1 = z0 + 1;
-            while (z1 < p.ns && p.sl.s[z1].params == p.sl.s[z0].params && p.sl.s[z1].count == p.sl.s[z0].count && p.sl.s[z1].s_off == p.sl.s[z1 - 1].s_off + p.sl.s[z1 - 1].count) z1++;
-            const Slice s0 = p.sl.s[z0];
-            const int which = s0.params == h->params[1] ? 1 : 0, row0 = s0.s_off, rows = s0.count * (z1 - z0);
-            // stale split weights are refreshed by the leading workgroups of the conv1 launch, decided on the device from
-            // AdamDev::pver / wver (a single profiled kernel never re-splits: fb_qnet_profile_kernel brings wsp up to date once)
-            const unsigned *pver = only < 0 ? &h->adam->pver[which] : nullptr;
-            unsigned *wver = only < 0 ? &h->adam->wver[which] : nullptr;
-            Slice sl = s0;
-            sl.count = rows;
-            C1Side side;
-            memset(&side, 0, sizeof(side));
-            if (z1 - z0 > 1) { side.per = s0.count; side.st1 = p.sl.s[z0 + 1].states; side.st2 = z1 - z0 > 2 ? p.sl.s[z0 + 2].states : p.sl.s[z0 + 1].states; }
-            if (p.train) { side.p1 = h->p1; side.amax = h->amax; }
-            const int t1p = (rows * 100 + 7) / 8, gsp = min(256, (t1p + C1_WAVES - 1) / C1_WAVES);      // one 12-wave workgroup per CU, the waves stride over the tiles
-            // the acting path on nibble states (forward-only plans of one slice): conv1 + conv2 + conv3 in ONE launch
-            // (conv23_sp_kernel<., 5, true>), five states per workgroup
-            const bool fused = p.nib && !p.train && !trunk && z1 - z0 == 1 && p.ns == 1;
-            acting_fused = fused;
-            if (!trunk && !fused) FB_K(K_CONV1)
-                hipLaunchKernelGGL(conv1_sp_kernel, dim3(gsp), dim3(64 * C1_WAVES), 0, st, sl, (const uint8_t *)h->zeros, h->a1s, pl1, nsp, h->wsp[which], h->FC, pver, (const unsigned *)wver, side, &h->adam->ovf);
-            C23Args c23{h->a1s + (size_t)row0 * 3200, pl1, h->wsp[which] + WSP_W2, s0.params + OFF_B2, s0.params + OFF_B3, h->a3s + (size_t)row0 * 1600, pl2, rows, pver, wver, only < 0 ? &h->adam->wverc[which] : nullptr,
-                        p.train ? h->h2 + (size_t)row0 * 1600 : nullptr, p.train ? h->h3 + (size_t)row0 * 1600 : nullptr,
-                        s0.states, s0.w1s, s0.params + OFF_B1, s0.params, h->wsp[which], h->FC, &h->adam->ovf};
-            Fc1Args af{h->a3s + (size_t)row0 * 1600, pl2, h->zeros, h->wsp[which] + WSP_WF1, (fused ? h->hf_act : h->hf) + (size_t)row0 * h->FC, stot, rows, h->FC,
-                       fused ? pver : nullptr, fused ? wver : nullptr, nullptr, 0,
-                       fused ? head_base(h, s0.params) + h->off.bf1 : nullptr, fused ? h->hp_act : nullptr, fused ? (int)(h->hoff.n - h->off.bf1) : 0,
-                       fused && p.split && only < 0 ? &p.split->f->trunk_done : nullptr, p.split ? p.split->seq : 0};
-            // behind the ring-fed trunk the groups only differ in fc1's weights: when the next group (the target net's slices) follows this
-            // one row for row and starts on a tile boundary, ONE fc1 launch takes both (two launches of 128 + 64 workgroups each left
-            // half the chip idle twice: 8.9 + 8.5 us at B = 256 against one of 192)
-            if (trunk && z1 < p.ns && rows % 128 == 0) {
-                int z2 = z1 + 1;
-                while (z2 < p.ns && p.sl.s[z2].params == p.sl.s[z1].params && p.sl.s[z2].s_off == p.sl.s[z2 - 1].s_off + p.sl.s[z2 - 1].count) z2++;
-                const Slice sn = p.sl.s[z1];
-                if (z2 == p.ns && sn.s_off == row0 + rows && sn.params != s0.params) {
-                    int rows2 = 0;
-                    for (int z = z1; z < z2; z++) rows2 += p.sl.s[z].count;
-                    af.w2 = h->wsp[sn.params == h->params[1] ? 1 : 0] + WSP_WF1; af.m_split = rows; af.M = rows + rows2;
-                    z1 = z2;
-                }
-            }
-            const int rows_f = af.M;
-            // five states per workgroup (125 of the 128 MFMA rows; 1024 envs = 205 workgroups: alone it costs what four per workgroup on
-            // all 256 CUs cost, and in the split schedule the fifth of the chip it leaves is where the train chain runs beside it)
-            const dim3 gc((rows + 4) / 5), gf(((rows_f + 127) / 128) * (h->FC / 64) * FC1_SP_KS);    // FC % 128 == 0 (fb_qnet_create)
-            // split schedule, more than one round of trunk workgroups (one per CU, 256 CUs) with a partial last round: that round's first
-            // workgroup says when it has been placed -- the train chain on the other stream starts then (fb_sampler.h)
-            if (fused && p.split && only < 0 && gc.x > 256 && gc.x % 256 != 0) { c23.round_flag = &p.split->f->last_round; c23.round_val = p.split->seq; c23.round_blk = (int)(gc.x / 256) * 256; }
-            if (nsp == 3) {
-                if (fused) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<3, 5, true>), gc, dim3(512), 0, st, c23); }      // conv1 .. conv3
-                else if (!trunk) { FB_K(K_CONV2) hipLaunchKernelGGL(conv23_sp_kernel<3>, gc, dim3(512), 0, st, c23); }      // conv3 rides in the same launch
-                FB_K(K_FC1) hipLaunchKernelGGL(fc1_sp_kernel<3>, gf, dim3(256), 0, st, af);
-            } else {
-                if (fused) { FB_K(K_CONV2) hipLaunchKernelGGL((conv23_sp_kernel<1, 5, true>), gc, dim3(512), 0, st, c23); }
-                else if (!trunk) { FB_K(K_CONV2) hipLaunchKernelGGL(conv23_sp_kernel<1>, gc, dim3(512), 0, st, c23); }
-                FB_K(K_FC1) hipLaunchKernelGGL(fc1_sp_kernel<1>, gf, dim3(256), 0, st, af);
-            }
-            // the fc1 launch copies one head parameter per thread: a distributional head (C51 / QR, A N columns) can outgrow a small
-            // launch's threads, and the rest of the copy follows it on the same stream (these nets take the one-stream order)
-            if (fused && (only < 0 || only == K_FC1) && (long long)af.hp_n > (long long)gf.x * 256) {
-                const size_t done = (size_t)gf.x * 256;
-                FB_CHECK_HIP(hipMemcpyAsync(h->hp_act + done, af.hp_src + done, sizeof(float) * ((size_t)af.hp_n - done), hipMemcpyDeviceToDevice, st));
-            }
-            z0 = z1;
+    return c23t;
+}
+
+// the ring-fed trunk: conv1 + pool + conv2 + conv3 of every state in ONE launch
+static void ring_trunk(fb_qnet *h, const Plan &p, const PlanCtx &c) {
+    SplitJob job;                                     // (unused here: the ring-fed trunk has no conv1_pool launch in front of it)
+    C23T c23t = trunk_args(h, p, c, &job);
+    if (c.big) { c23t.a3s = h->a3s; c23t.pl3 = c.pl2; }     // >= 256 states per slice: fc1_sp_kernel follows and reads conv3's output as planes
+    c23t.ring = *p.ring; c23t.p1o = h->p1; c23t.amax = h->amax; c23t.ring_fo = h->ring_fo;
+    const bool w16 = c.maxc * p.ns <= 256;            // at most one workgroup per CU anyway: spend the idle SIMD slots on conv1's second round
+    const bool nst = p.ring->c.nstep > 1;             // n-step view: the same kernels with the n-step return (NST)
+    with_nsp(c.nsp, [&](auto ns) { with_bool(w16, [&](auto w) { with_bool(nst, [&](auto nv) {
+        constexpr bool W16 = decltype(w)::value;
+        hipLaunchKernelGGL((conv23_t_kernel<decltype(ns)::value, true, W16, decltype(nv)::value>), dim3(c.maxc, p.ns), dim3(W16 ? 1024 : 512), 0, c.st, c23t);
+    }); }); });
+}
+
+// one large-batch pass, conv1_sp -> conv23_sp -> fc1_sp (behind the ring-fed trunk fc1 alone), from slice *z to the next pass's first
+static int large_pass(fb_qnet *h, const Plan &p, const PlanCtx &c, int *z) {
+    const int z0 = *z;
+    int z1 = z0 + 1;
+    while (z1 < p.ns && p.sl.s[z1].params == p.sl.s[z0].params && p.sl.s[z1].count == p.sl.s[z0].count && p.sl.s[z1].s_off == p.sl.s[z1 - 1].s_off + p.sl.s[z1 - 1].count) z1++;
+    const Slice s0 = p.sl.s[z0];
+    const int which = s0.params == h->params[1] ? 1 : 0, row0 = s0.s_off, rows = s0.count * (z1 - z0);
+    // stale split weights are refreshed by the leading workgroups of the conv1 launch, decided on the device from
+    // AdamDev::pver / wver (a single profiled kernel never re-splits: fb_qnet_profile_kernel brings wsp up to date once)
+    const unsigned *pver = c.only < 0 ? &h->adam->pver[which] : nullptr;
+    unsigned *wver = c.only < 0 ? &h->adam->wver[which] : nullptr;
+    Slice sl = s0;
+    sl.count = rows;
+    C1Side side;
+    memset(&side, 0, sizeof(side));
+    if (z1 - z0 > 1) { side.per = s0.count; side.st1 = p.sl.s[z0 + 1].states; side.st2 = z1 - z0 > 2 ? p.sl.s[z0 + 2].states : p.sl.s[z0 + 1].states; }
+    if (p.train) { side.p1 = h->p1; side.amax = h->amax; }
+    const int t1p = (rows * 100 + 7) / 8, gsp = min(256, (t1p + C1_WAVES - 1) / C1_WAVES);      // one 12-wave workgroup per CU, the waves stride over the tiles
+    if (!c.trunk && !c.fused && runs(c, K_CONV1))
+        hipLaunchKernelGGL(conv1_sp_kernel, dim3(gsp), dim3(64 * C1_WAVES), 0, c.st, sl, (const uint8_t *)h->zeros, h->a1s, c.pl1, c.nsp, h->wsp[which], h->FC, pver, (const unsigned *)wver, side, &h->adam->ovf);
+    C23Args c23{h->a1s + (size_t)row0 * 3200, c.pl1, h->wsp[which] + WSP_W2, s0.params + OFF_B2, s0.params + OFF_B3, h->a3s + (size_t)row0 * 1600, c.pl2, rows, pver, wver, c.only < 0 ? &h->adam->wverc[which] : nullptr,
+                p.train ? h->h2 + (size_t)row0 * 1600 : nullptr, p.train ? h->h3 + (size_t)row0 * 1600 : nullptr,
+                s0.states, s0.w1s, s0.params + OFF_B1, s0.params, h->wsp[which], h->FC, &h->adam->ovf};
+    Fc1Args af{h->a3s + (size_t)row0 * 1600, c.pl2, h->zeros, h->wsp[which] + WSP_WF1, (c.fused ? h->hf_act : h->hf) + (size_t)row0 * h->FC, c.stot, rows, h->FC,
+               c.fused ? pver : nullptr, c.fused ? wver : nullptr, nullptr, 0,
+               c.fused ? head_base(h, s0.params) + h->off.bf1 : nullptr, c.fused ? h->hp_act : nullptr, c.fused ? (int)(h->hoff.n - h->off.bf1) : 0,
+               c.fused && p.split && c.only < 0 ? &p.split->f->trunk_done : nullptr, p.split ? p.split->seq : 0};
+    // behind the ring-fed trunk the groups only differ in fc1's weights: when the next group (the target net's slices) follows this
+    // one row for row and starts on a tile boundary, ONE fc1 launch takes both (two launches of 128 + 64 workgroups each left
+    // half the chip idle twice: 8.9 + 8.5 us at B = 256 against one of 192)
+    if (c.trunk && z1 < p.ns && rows % 128 == 0) {
+        int z2 = z1 + 1;
+        while (z2 < p.ns && p.sl.s[z2].params == p.sl.s[z1].params && p.sl.s[z2].s_off == p.sl.s[z2 - 1].s_off + p.sl.s[z2 - 1].count) z2++;
+        const Slice sn = p.sl.s[z1];
+        if (z2 == p.ns && sn.s_off == row0 + rows && sn.params != s0.params) {
+            int rows2 = 0;
+            for (int z = z1; z < z2; z++) rows2 += p.sl.s[z].count;
+            af.w2 = h->wsp[sn.params == h->params[1] ? 1 : 0] + WSP_WF1; af.m_split = rows; af.M = rows + rows2;
+            z1 = z2;
         }
     }
-    if (!sp && !trunk) FB_K(K_CONV1) {
-        const dim3 g1((t1 + 3) / 4, 1, p.ns);
-        if (p.nib) hipLaunchKernelGGL(conv1_pool_kernel<true>, g1, dim3(256), 0, st, p.sl, h->p1, h->amax, job);
-        else hipLaunchKernelGGL(conv1_pool_kernel<false>, g1, dim3(256), 0, st, p.sl, h->p1, h->amax, job);
+    *z = z1;
+    // five states per workgroup (125 of the 128 MFMA rows; 1024 envs = 205 workgroups: alone it costs what four per workgroup on
+    // all 256 CUs cost, and in the split schedule the fifth of the chip it leaves is where the train chain runs beside it)
+    const dim3 gc((rows + 4) / 5), gf(((af.M + 127) / 128) * (h->FC / 64) * FC1_SP_KS);    // FC % 128 == 0 (fb_qnet_create)
+    // split schedule, more than one round of trunk workgroups (one per CU, 256 CUs) with a partial last round: that round's first
+    // workgroup says when it has been placed -- the train chain on the other stream starts then (fb_sampler.h)
+    if (c.fused && p.split && c.only < 0 && gc.x > 256 && gc.x % 256 != 0) { c23.round_flag = &p.split->f->last_round; c23.round_val = p.split->seq; c23.round_blk = (int)(gc.x / 256) * 256; }
+    with_nsp(c.nsp, [&](auto ns) {
+        if (!c.trunk && runs(c, K_CONV2))            // fused: conv1 .. conv3; else conv3 rides in conv2's launch
+            with_bool(c.fused, [&](auto fu) { hipLaunchKernelGGL((conv23_sp_kernel<decltype(ns)::value, 5, decltype(fu)::value>), gc, dim3(512), 0, c.st, c23); });
+        if (runs(c, K_FC1)) hipLaunchKernelGGL(fc1_sp_kernel<decltype(ns)::value>, gf, dim3(256), 0, c.st, af);
+    });
+    // the fc1 launch copies one head parameter per thread: a distributional head (C51 / QR, A N columns) can outgrow a small
+    // launch's threads, and the rest of the copy follows it on the same stream (these nets take the one-stream order)
+    if (c.fused && (c.only < 0 || c.only == K_FC1) && (long long)af.hp_n > (long long)gf.x * 256) {
+        const size_t done = (size_t)gf.x * 256;
+        FB_CHECK_HIP(hipMemcpyAsync(h->hp_act + done, af.hp_src + done, sizeof(float) * ((size_t)af.hp_n - done), hipMemcpyDeviceToDevice, c.st));
     }
-    if (!sp && !trunk) FB_K(K_CONV2) {               // (conv3 rides in the same launch)
-        if (nsp == 3) hipLaunchKernelGGL((conv23_t_kernel<3, false>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
-        else hipLaunchKernelGGL((conv23_t_kernel<1, false>), dim3(maxc, p.ns), dim3(512), 0, st, c23t);
+    return FB_OK;
+}
+
+// the small-batch forward: conv1_pool -> conv23_t (behind the ring-fed trunk neither) -> fc1_fk
+// small batches: the whole K per workgroup (fc1_fk_kernel), which lets training skip the head and loss launches
+static void small_forward(fb_qnet *h, const Plan &p, const PlanCtx &c) {
+    if (!c.trunk) {
+        SplitJob job;
+        const C23T c23t = trunk_args(h, p, c, &job);
+        const int t1 = (c.maxc * 100 + 7) / 8;
+        if (runs(c, K_CONV1))
+            with_bool(p.nib, [&](auto nib) { hipLaunchKernelGGL(conv1_pool_kernel<decltype(nib)::value>, dim3((t1 + 3) / 4, 1, p.ns), dim3(256), 0, c.st, p.sl, h->p1, h->amax, job); });
+        if (runs(c, K_CONV2))                                // (conv3 rides in the same launch)
+            with_nsp(c.nsp, [&](auto ns) { hipLaunchKernelGGL((conv23_t_kernel<decltype(ns)::value, false>), dim3(c.maxc, p.ns), dim3(512), 0, c.st, c23t); });
     }
-    // small batches: the whole K per workgroup (fc1_fk_kernel), which lets training skip the head and loss launches
-    const bool fk = !sp && !big;
-    const bool c51 = h->sup.N > 0;
-    if (fk) FB_K(K_FC1) {
+    if (runs(c, K_FC1)) {
         FkArgs fa;
-        fa.sl = p.sl; fa.h3 = h->h3; fa.hf = h->hf; fa.qpart = p.train && !c51 ? h->qpart : nullptr; fa.FC = h->FC; fa.A = h->A;      // (C51: the head is the loss launches' own work)
-        fa.dueling = h->arch == FB_ARCH_DUELING; fa.stot = stot; fa.off = h->off;
-        hipLaunchKernelGGL(fc1_fk_kernel, dim3((maxc + 15) / 16, h->FC / 16, p.ns), dim3(512), 0, st, fa);
+        fa.sl = p.sl; fa.h3 = h->h3; fa.hf = h->hf; fa.qpart = p.train && !c.c51 ? h->qpart : nullptr; fa.FC = h->FC; fa.A = h->A;      // (C51: the head is the loss launches' own work)
+        fa.dueling = h->arch == FB_ARCH_DUELING; fa.stot = c.stot; fa.off = h->off;
+        hipLaunchKernelGGL(fc1_fk_kernel, dim3((c.maxc + 15) / 16, h->FC / 16, p.ns), dim3(512), 0, c.st, fa);
     }
-    if (c51 && !p.train && !p.no_head) FB_K(K_HEAD) {             // C51: the distributional head (stand-alone launch only; no env rider)
+}
+
+static void launch_dist_head(const fb_qnet *h, const C51HeadArgs &H, int rows, hipStream_t st) {      // (C51 / QR; one wave per row)
+    with_actions(h->A, [&](auto a) {
+        if (is_qr(h)) hipLaunchKernelGGL(qr_head_kernel<decltype(a)::value>, dim3((rows + 3) / 4), dim3(256), 0, st, H);
+        else hipLaunchKernelGGL(c51_head_kernel<decltype(a)::value>, dim3((rows + 3) / 4), dim3(256), 0, st, H);
+    });
+}
+
+// the head: launched on its own, or described into the rider (p.head_rider) for the launch that carries it
+static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
+    if (c.c51 && !p.train && !p.no_head && runs(c, K_HEAD)) {           // C51: the distributional head (stand-alone launch only; no env rider)
         C51HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns; H.params = nullptr;
         for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (a dueling C51 net: its folded head)
         C51Core &C = H.c;
-        C.hf = acting_fused ? h->hf_act : h->hf; C.stot = stot; C.nks = sp ? FC1_SP_KS : 1; C.q = h->q; C.probs = p.probs; C.FC = h->FC; C.A = h->A;
+        C.hf = c.fused ? h->hf_act : h->hf; C.stot = c.stot; C.nks = c.big ? FC1_SP_KS : 1; C.q = h->q; C.probs = p.probs; C.FC = h->FC; C.A = h->A;
         C.off = h->hoff; C.sup = h->sup; C.actions = p.actions; C.epsilon = p.epsilon;
-        C.seed_lo = (uint32_t)p.seed; C.seed_hi = (uint32_t)(p.seed >> 32);
-        C.step_lo = (uint32_t)p.step; C.step_hi = (uint32_t)(p.step >> 32);
-        C.key_of = nullptr; C.stream = FB_STREAM_EPS;
+        put_seed_words(C, p.seed, p.step); C.key_of = nullptr; C.stream = FB_STREAM_EPS;
         if (p.head_rider) {                          // fb_eval_run: describe the work (fb_qnet_c51_eval_head launches it)
             memset(p.head_rider, 0, sizeof(*p.head_rider));
-            p.head_rider->c.hf = C.hf; p.head_rider->c.stot = stot; p.head_rider->c.nks = C.nks;
-            p.head_rider->params = acting_fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params;
-        } else if (is_qr(h) && h->A == 2) hipLaunchKernelGGL(qr_head_kernel<2>, dim3((total + 3) / 4), dim3(256), 0, st, H);
-        else if (is_qr(h)) hipLaunchKernelGGL(qr_head_kernel<MAXA>, dim3((total + 3) / 4), dim3(256), 0, st, H);
-        else if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((total + 3) / 4), dim3(256), 0, st, H);
-        else hipLaunchKernelGGL(c51_head_kernel<MAXA>, dim3((total + 3) / 4), dim3(256), 0, st, H);
+            p.head_rider->c.hf = C.hf; p.head_rider->c.stot = c.stot; p.head_rider->c.nks = C.nks;
+            p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params;
+        } else launch_dist_head(h, H, c.total, c.st);
     }
-    if (!c51 && !(fk && p.train)) FB_K(K_HEAD) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
+    if (!c.c51 && !(!c.big && p.train) && runs(c, K_HEAD)) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
         HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns;
         HeadCore &C = H.c;
-        C.hf = acting_fused ? h->hf_act : h->hf; C.stot = stot; C.nks = sp ? FC1_SP_KS : 1; C.q = h->q; C.FC = h->FC; C.A = h->A;
+        C.hf = c.fused ? h->hf_act : h->hf; C.stot = c.stot; C.nks = c.big ? FC1_SP_KS : 1; C.q = h->q; C.FC = h->FC; C.A = h->A;
         C.dueling = h->arch == FB_ARCH_DUELING; C.off = h->off; C.actions = p.actions; C.epsilon = p.epsilon;
-        C.seed_lo = (uint32_t)p.seed; C.seed_hi = (uint32_t)(p.seed >> 32);
-        C.step_lo = (uint32_t)p.step; C.step_hi = (uint32_t)(p.step >> 32);
+        put_seed_words(C, p.seed, p.step);
         // (the rider of a fused acting forward reads the head's parameters from the copy that forward's fc1 launch took: b_fc1 on)
-        if (p.head_rider) { p.head_rider->c = C; p.head_rider->params = acting_fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params; p.head_rider->on = 1; p.head_rider->on_arrival = nullptr; p.head_rider->arrival_val = 0; }   // rides in the env launch
-        else hipLaunchKernelGGL(head_kernel, dim3((total + 3) / 4), dim3(256), 0, st, H);
+        if (p.head_rider) { p.head_rider->c = C; p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params; p.head_rider->on = 1; p.head_rider->on_arrival = nullptr; p.head_rider->arrival_val = 0; }   // rides in the env launch
+        else hipLaunchKernelGGL(head_kernel, dim3((c.total + 3) / 4), dim3(256), 0, c.st, H);
     }
-    if (p.train) {
-        const int B = p.B, FC = h->FC, rbt = h->nsplit_train == 1;       // bf16 training: operands rounded to bf16
-        float *G = p.G;
-        if (c51 && is_qr(h)) FB_K(K_LOSS) {         // QR: per-sample targets / quantile Huber loss / dhf, then C51's per-unit reductions
-            if (p.tick) h->adam_ticked = !p.apply_adam;
+}
+
+// the loss.  Scalar: large batches only (small ones: fc1_bwd2_kernel's own work).  C51: per-sample distribution / projection / dhf, then
+// the per-unit reductions; QR: per-sample targets / quantile Huber loss / dhf, then C51's per-unit reductions
+static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
+    const int B = p.B, FC = h->FC;
+    if (!c.c51) {                                // (large batches only: run_plan)
+        LossArgs L;
+        L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.off = h->off;
+        L.params = h->params[0]; L.q = h->q; L.hf = h->hf; L.stot = c.stot; L.nks = FC1_SP_KS; L.act = p.a; L.rew = p.r; L.term = p.t; L.isw = p.isw;      // (only large batches come here: fc1_sp_kernel's 4 K slices)
+        L.gamma = p.gamma; L.grad = p.G; L.dhf = h->dhf; L.loss = p.loss; L.abs_err = p.abs_err; L.y_out = p.y; L.gmax = h->gmax;
+        // data-parallel path: the loss kernel advances the Adam step counter as well (once per fb_qnet_apply_adam), so the
+        // apply needs no launch of its own for it
+        // (at most one tick per Adam update: guarded on the device by AdamDev::ticks / applies)
+        L.adam = h->adam; L.tick = p.tick;
+        hipLaunchKernelGGL(loss_head_kernel, dim3(FC / 16), dim3(256), 0, c.st, L);
+        return;
+    }
+    const bool pw = is_per_algo(p.algo);         // (prioritized: weighted loss; the priorities are KL (C51) / l_b (QR))
+    auto shared = [&](auto &L) {                 // the fields C51LossArgs and QRLossArgs have in common
+        L.B = B; L.FC = FC; L.A = h->A; L.nks = c.big ? FC1_SP_KS : 1; L.stot = c.stot; L.off = h->hoff;
+        L.p_on = head_base(h, h->params[0]); L.p_next = head_base(h, p.sl.s[1].params);
+        L.p_tgt = head_base(h, p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params);
+        L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
+        L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
+        L.isw = pw ? p.isw : nullptr; L.abs_err = pw ? p.abs_err : nullptr;
+    };
+    with_actions(h->A, [&](auto a) { with_bool(pw, [&](auto w) {
+        if (is_qr(h)) {
             QRLossArgs L;
-            const bool pw = is_per_algo(p.algo);     // (prioritized: weighted loss, l_b priorities)
-            L.algo = is_double_qr(p.algo) ? FB_ALGO_QR_DOUBLE : FB_ALGO_QR;
-            L.B = B; L.FC = FC; L.A = h->A; L.N = h->sup.N; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->hoff; L.kappa = h->kappa;
-            L.p_on = head_base(h, h->params[0]); L.p_next = head_base(h, p.sl.s[1].params);
-            L.p_tgt = head_base(h, p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params);
-            L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
-            L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
-            L.isw = pw ? p.isw : nullptr; L.abs_err = pw ? p.abs_err : nullptr;
-            if (pw && h->A == 2) hipLaunchKernelGGL((qr_loss_kernel<2, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
-            else if (pw) hipLaunchKernelGGL((qr_loss_kernel<MAXA, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
-            else if (h->A == 2) hipLaunchKernelGGL(qr_loss_kernel<2>, dim3((B + 3) / 4), dim3(256), 0, st, L);
-            else hipLaunchKernelGGL(qr_loss_kernel<MAXA>, dim3((B + 3) / 4), dim3(256), 0, st, L);
-            const C51GradArgs gA{B, FC, h->A, h->sup.N, h->off, h->c51_dl, h->c51_xs, h->c51_lt, h->dhf, p.a, G, p.loss, h->gmax, h->adam, p.tick};
-            if (is_c51d(h)) hipLaunchKernelGGL(c51d_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);      // (gA.off: W_v b_v W_a b_a)
-            else hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);
-        }
-        if (c51 && !is_qr(h)) FB_K(K_LOSS) {        // C51: per-sample distribution / projection / dhf, then the per-unit reductions
-            if (p.tick) h->adam_ticked = !p.apply_adam;
+            shared(L);
+            L.algo = is_double_qr(p.algo) ? FB_ALGO_QR_DOUBLE : FB_ALGO_QR; L.N = h->sup.N; L.kappa = h->kappa;
+            hipLaunchKernelGGL((qr_loss_kernel<decltype(a)::value, decltype(w)::value>), dim3((B + 3) / 4), dim3(256), 0, c.st, L);
+        } else {
             C51LossArgs L;
-            const bool pw = is_per_algo(p.algo);     // (prioritized: weighted loss, KL priorities)
-            L.algo = is_double_c51(p.algo) ? FB_ALGO_C51_DOUBLE : FB_ALGO_C51;
-            L.B = B; L.FC = FC; L.A = h->A; L.nks = fk ? 1 : FC1_SP_KS; L.stot = stot; L.off = h->hoff; L.sup = h->sup;
-            L.p_on = head_base(h, h->params[0]); L.p_next = head_base(h, p.sl.s[1].params);
-            L.p_tgt = head_base(h, p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params);
-            L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
-            L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
-            L.isw = pw ? p.isw : nullptr; L.abs_err = pw ? p.abs_err : nullptr;
-            if (pw && h->A == 2) hipLaunchKernelGGL((c51_loss_kernel<2, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
-            else if (pw) hipLaunchKernelGGL((c51_loss_kernel<MAXA, true>), dim3((B + 3) / 4), dim3(256), 0, st, L);
-            else if (h->A == 2) hipLaunchKernelGGL(c51_loss_kernel<2>, dim3((B + 3) / 4), dim3(256), 0, st, L);
-            else hipLaunchKernelGGL(c51_loss_kernel<MAXA>, dim3((B + 3) / 4), dim3(256), 0, st, L);
-            const C51GradArgs gA{B, FC, h->A, h->sup.N, h->off, h->c51_dl, h->c51_xs, h->c51_lt, h->dhf, p.a, G, p.loss, h->gmax, h->adam, p.tick};
-            if (is_c51d(h)) hipLaunchKernelGGL(c51d_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);      // (gA.off: W_v b_v W_a b_a)
-            else hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, st, gA);
+            shared(L);
+            L.algo = is_double_c51(p.algo) ? FB_ALGO_C51_DOUBLE : FB_ALGO_C51; L.sup = h->sup;
+            hipLaunchKernelGGL((c51_loss_kernel<decltype(a)::value, decltype(w)::value>), dim3((B + 3) / 4), dim3(256), 0, c.st, L);
         }
-        if (!fk && !c51) FB_K(K_LOSS) {
-            LossArgs L;
-            L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.off = h->off;
-            L.params = h->params[0]; L.q = h->q; L.hf = h->hf; L.stot = stot; L.nks = FC1_SP_KS; L.act = p.a; L.rew = p.r; L.term = p.t; L.isw = p.isw;      // (only large batches come here: fc1_sp_kernel's 4 K slices)
-            L.gamma = p.gamma; L.grad = G; L.dhf = h->dhf; L.loss = p.loss; L.abs_err = p.abs_err; L.y_out = p.y; L.gmax = h->gmax;
-            // data-parallel path: the loss kernel advances the Adam step counter as well (once per fb_qnet_apply_adam), so the
-            // apply needs no launch of its own for it
-            // (at most one tick per Adam update: guarded on the device by AdamDev::ticks / applies)
-            if (p.tick) h->adam_ticked = !p.apply_adam;              // stays pending until fb_qnet_apply_adam consumes it
-            L.adam = h->adam; L.tick = p.tick;
-            hipLaunchKernelGGL(loss_head_kernel, dim3(FC / 16), dim3(256), 0, st, L);
-        }
-        // slabs: one chunk of <= 16 MFMAs (32 output pixels) per wave where the slab budget allows it
-        int z3 = (B * 25 + 255) / 256, z1 = (B * 400 + 255) / 256;
-        if (z3 > h->zmax) z3 = h->zmax;
-        if (z1 > h->zmax) z1 = h->zmax;
-        const size_t ss = CONV_PARAMS;
+    }); });
+    const C51GradArgs gA{B, FC, h->A, h->sup.N, h->off, h->c51_dl, h->c51_xs, h->c51_lt, h->dhf, p.a, p.G, p.loss, h->gmax, h->adam, p.tick};
+    if (is_c51d(h)) hipLaunchKernelGGL(c51d_grad_kernel, dim3(FC / 16), dim3(256), 0, c.st, gA);      // (gA.off: W_v b_v W_a b_a)
+    else hipLaunchKernelGGL(c51_grad_kernel, dim3(FC / 16), dim3(256), 0, c.st, gA);
+}
+
+// the fc1 backward.  Small scalar batches: head, loss and fc1's gradients in one launch (fc1_bwd2_kernel); else fc1's gradients from dhf
+static void fc1_backward(fb_qnet *h, const Plan &p, const PlanCtx &c) {
+    const int B = p.B, FC = h->FC;
+    if (!c.big && !c.c51) {
         const int ndx1 = ((B + 31) / 32) * 50;
-        if (fk && !c51) { FB_K(K_FC1_BWD) {
-            Bw1Args L;
-            L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.stot = stot; L.n_dx = ndx1; L.off = h->off;
-            L.params = h->params[0]; L.pnext = p.sl.s[1].params; L.ptarget = p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params;
-            L.hf = h->hf; L.qpart = h->qpart; L.h3 = h->h3; L.act = p.a; L.rew = p.r; L.term = p.t; L.isw = p.isw; L.gamma = p.gamma;
-            L.grad = G; L.dh3 = h->dh3; L.loss = p.loss; L.abs_err = p.abs_err; L.y_out = p.y;
-            if (p.tick) h->adam_ticked = !p.apply_adam;              // stays pending until fb_qnet_apply_adam consumes it
-            L.adam = h->adam; L.tick = p.tick; L.rb = rbt;
-            L.gate = FbGate{nullptr, 0, nullptr};
-            if (p.split && only < 0) L.gate = FbGate{&p.split->f->trunk_done, p.split->seq, &p.split->f->timeouts[2]};
-            hipLaunchKernelGGL(fc1_bwd2_kernel, dim3(ndx1 + (FC / 32) * 7 + (L.gate.flag ? 1 : 0)), dim3(512), 0, st, L);
-        } } else FB_K(K_FC1_BWD) {
-            const int ndx = ((B + 31) / 32) * 50, ntile = ndx + 50 * (FC / 32);        // one workgroup per 32 x 32 tile, data-gradient tiles first
-            const dim3 gb(ntile);
-            const bool std_shape = FC == 512 && B == 256;      // the shapes this path sees (MAXTB = 256): fully unrolled instantiation
-            if (h->nsplit_train == 3) {
-                if (std_shape) hipLaunchKernelGGL((fc1_bwd_big_kernel<3, 4, 2>), gb, dim3(512), 0, st, ndx, h->params[0], h->h3, h->dhf, h->dh3, G, B, FC, (const float *)h->gmax, &h->adam->ovf);
-                else hipLaunchKernelGGL((fc1_bwd_big_kernel<3, 0, 0>), gb, dim3(512), 0, st, ndx, h->params[0], h->h3, h->dhf, h->dh3, G, B, FC, (const float *)h->gmax, &h->adam->ovf);
-            } else {
-                if (std_shape) hipLaunchKernelGGL((fc1_bwd_big_kernel<1, 4, 2>), gb, dim3(512), 0, st, ndx, h->params[0], h->h3, h->dhf, h->dh3, G, B, FC, (const float *)h->gmax, &h->adam->ovf);
-                else hipLaunchKernelGGL((fc1_bwd_big_kernel<1, 0, 0>), gb, dim3(512), 0, st, ndx, h->params[0], h->h3, h->dhf, h->dh3, G, B, FC, (const float *)h->gmax, &h->adam->ovf);
-            }
+        Bw1Args L;
+        L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.stot = c.stot; L.n_dx = ndx1; L.off = h->off;
+        L.params = h->params[0]; L.pnext = p.sl.s[1].params; L.ptarget = p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params;
+        L.hf = h->hf; L.qpart = h->qpart; L.h3 = h->h3; L.act = p.a; L.rew = p.r; L.term = p.t; L.isw = p.isw; L.gamma = p.gamma;
+        L.grad = p.G; L.dh3 = h->dh3; L.loss = p.loss; L.abs_err = p.abs_err; L.y_out = p.y;
+        L.adam = h->adam; L.tick = p.tick; L.rb = h->nsplit_train == 1;       // bf16 training: operands rounded to bf16
+        L.gate = p.split && c.only < 0 ? FbGate{&p.split->f->trunk_done, p.split->seq, &p.split->f->timeouts[2]} : FbGate{nullptr, 0, nullptr};
+        hipLaunchKernelGGL(fc1_bwd2_kernel, dim3(ndx1 + (FC / 32) * 7 + (L.gate.flag ? 1 : 0)), dim3(512), 0, c.st, L);
+        return;
+    }
+    const int ndx = ((B + 31) / 32) * 50, ntile = ndx + 50 * (FC / 32);        // one workgroup per 32 x 32 tile, data-gradient tiles first
+    const bool std_shape = FC == 512 && B == 256;      // the shapes this path sees (MAXTB = 256): fully unrolled instantiation
+    with_nsp(h->nsplit_train, [&](auto ns) { with_bool(std_shape, [&](auto s) {
+        hipLaunchKernelGGL((fc1_bwd_big_kernel<decltype(ns)::value, decltype(s)::value ? 4 : 0, decltype(s)::value ? 2 : 0>), dim3(ntile), dim3(512), 0, c.st,
+                           ndx, h->params[0], h->h3, h->dhf, h->dh3, p.G, B, FC, (const float *)h->gmax, &h->adam->ovf);
+    }); });
+}
+
+struct SlabCounts { int z1, z3; };           // slabs the conv backward left of conv1's / conv3's weight gradient (conv2's: as conv3's)
+// the conv backward in its three shapes: conv_bw (small batches, one launch); conv_bx + conv_dw21; those two with conv_dwg between them
+static SlabCounts conv_backward(fb_qnet *h, const Plan &p, const PlanCtx &c, int span0, int span1) {
+    const int B = p.B, FC = h->FC, rbt = h->nsplit_train == 1;       // bf16 training: operands rounded to bf16
+    // slabs: one chunk of <= 16 MFMAs (32 output pixels) per wave where the slab budget allows it
+    int z3 = min((B * 25 + 255) / 256, h->zmax);
+    const size_t ss = CONV_PARAMS;
+    const AdamSpan span{master(h, 0), h->adam_m, h->adam_v, p.G, h->adam, span0, span1};
+    // split schedule: the fc1 backward launch has waited for the acting trunk on the other stream (its gate workgroup), so W_fc1's Adam
+    // span may ride in the launches below; the last of them waits for that stream's fc1 launch, so the Adam launch may follow
+    const FbGate gate_fc1 = p.split && c.only < 0 ? FbGate{&p.split->f->fc1_done, p.split->seq, &p.split->f->timeouts[3]} : FbGate{nullptr, 0, nullptr};
+    const FbSampleRider srider = p.sample_rider ? *p.sample_rider : FbSampleRider{};
+    // [data-gradient chain per sample + conv3 dW + W_fc1's Adam] and [conv2 dW + conv1 dW] (see conv_bx_kernel)
+    // conv1's weight gradient: two workgroups per sample, each with its own slab (2 B slabs); more than zmax of them are written
+    // to the sub-slab buffer and folded into zmax slabs afterwards, in a fixed order
+    const bool fold1 = 2 * B > h->zmax;
+    const int fold = (2 * B + h->zmax - 1) / h->zmax;
+    const int z1 = fold1 ? (2 * B + fold - 1) / fold : 2 * B;
+    const int n_adam5 = (span1 - span0 + 511) / 512;
+    const BxArgs bx{h->dh3, h->h2, h->p1, h->dh2, h->dp1, h->wsp[0] + wsp_w3t(FC), h->wsp[0] + wsp_w2t(FC)};
+    const Dw1Ring dr{p.ring ? p.ring->c.bits : nullptr, h->ring_fo};
+    float *s1 = fold1 ? h->slabs1 : h->slabs;
+    const size_t st1 = fold1 ? (size_t)CONV1_PARAMS : ss;
+    // large batches (multiples of 16): conv3's and conv2's weight gradients per group of 16 samples in a launch of their own
+    // (conv_dwg_kernel) instead of as 38 + 34 tiles per slab inside the two launches below; one slab per group
+    const bool dwg = c.big && B % 16 == 0;
+    const int zt3 = dwg ? 0 : z3, zt2 = zt3;
+    // small batches: the whole conv backward per sample in ONE launch (conv_bw_kernel); one conv2 / conv3 slab per sample
+    const bool bw = !c.big && B <= h->zmax;
+    // split schedule: W_fc1's Adam span rides in the next launch, and the acting trunk running beside this step on another stream
+    // re-splits W_fc1's planes from those very parameters in its first microseconds
+    if (bw) {
+        z3 = B;
+        const dim3 g(BW_WGS * B + n_adam5 + (srider.k ? 1 : 0) + (gate_fc1.flag ? 1 : 0));
+        if (runs(c, K_CONV3_BWD)) with_nsp(h->nsplit_train, [&](auto ns) { with_bool(p.ring != nullptr, [&](auto r) {
+            hipLaunchKernelGGL((conv_bw_kernel<decltype(ns)::value, decltype(r)::value>), g, dim3(512), 0, c.st,
+                               bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
+        }); });
+    } else {
+        const dim3 g3(B + 38 * zt3 + n_adam5 + (srider.k ? 1 : 0)), g2(34 * zt2 + 2 * B + (gate_fc1.flag ? 1 : 0));
+        if (runs(c, K_CONV3_BWD)) with_nsp(h->nsplit_train, [&](auto ns) {
+            hipLaunchKernelGGL(conv_bx_kernel<decltype(ns)::value>, g3, dim3(512), 0, c.st, bx, B, zt3, h->slabs, ss, n_adam5, span, srider, rbt);
+        });
+        if (dwg) {
+            z3 = B / 16;                                 // (conv2's slab count follows it)
+            const int n3 = z3 * 4, n2 = z3 * 8;
+            if (runs(c, K_CONV2_BWD)) with_nsp(h->nsplit_train, [&](auto ns) {
+                hipLaunchKernelGGL(conv_dwg_kernel<decltype(ns)::value>, dim3(n3 + n2), dim3(512), 0, c.st, n3, h->h2, h->dh3, h->p1, h->dh2, h->slabs, ss, &h->adam->ovf);
+            });
         }
+        if (runs(c, K_CONV2_BWD)) with_bool(p.ring != nullptr, [&](auto r) {
+            hipLaunchKernelGGL((conv_dw21_kernel<2, decltype(r)::value>), g2, dim3(512), 0, c.st,
+                               zt2, B, h->p1, h->dh2, p.s, h->dp1, h->amax, h->slabs, ss, s1, st1, rbt, dr, gate_fc1);
+        });
+    }
+    if (fold1 && runs(c, K_CONV2_BWD)) hipLaunchKernelGGL(slab_fold_kernel, dim3((CONV1_PARAMS + 255) / 256, z1), dim3(256), 0, c.st, h->slabs1, 2 * B, fold, h->slabs, ss);
+    return SlabCounts{z1, z3};
+}
+
+// data-parallel path: the caller needs the complete flat gradient; fused path: Adam sums the slabs itself
+static void reduce_or_adam(fb_qnet *h, const Plan &p, const PlanCtx &c, SlabCounts z, int span1) {
+    if (p.split && c.only < 0) h->split_adam_pending = !p.apply_adam;
+    if (!p.apply_adam && runs(c, K_SLAB)) hipLaunchKernelGGL(slab_reduce_kernel, dim3((CONV_PARAMS / 4 + 255) / 256), dim3(256), 0, c.st, h->slabs, (size_t)CONV_PARAMS, z.z1, z.z3, z.z3, p.G);
+    if (c.only < 0) noisy_sgrad(h, p.G, c.st);   // (a noisy net: sigma's gradient, from the gradient of the effective W_fc1 b_fc1 and head)
+    // split schedule: the Adam launch rewrites the conv planes / biases the acting trunk reads and the parameters its fc1 launch copies for the head
+    if (p.apply_adam && runs(c, K_ADAM)) {
+        AdamFused af;
+        af.p = master(h, 0); af.m = h->adam_m; af.v = h->adam_v; af.g = p.G; af.n = h->ntot; af.ad = h->adam;
+        af.slabs = h->slabs; af.slab_stride = CONV_PARAMS; af.z1 = z.z1; af.z2 = af.z3 = z.z3;
+        af.w1s = h->w1s[0]; af.wsp = h->wsp[0]; af.FC = h->FC; af.tail0 = span1;
+        const long long nrest4 = OFF_W2 / 4 + (OFF_W3 - OFF_B2) / 4 + (OFF_WF1 - OFF_B3) / 4 + (h->ntot / 4 - span1);
+        af.lanes = 4;                                    // slab mode: one chunk of <= 16 slabs per lane
+        af.split = p.split && c.only < 0 ? p.split->f : nullptr; af.split_val = p.split ? p.split->seq : 0;
+        af.n_rest = (int)((nrest4 * af.lanes + 255) / 256);
+        hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest), dim3(256), 0, c.st, af);
+        noisy_materialise(h, 0, 0, false, c.st);
+        c51d_fold(h, 0, c.st);
+    }
+}
+
+static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
+    const PlanCtx c = plan_ctx(h, p, only, st);
+    if (c.trunk && runs(c, K_CONV2)) ring_trunk(h, p, c);
+    if (c.big) {
+        for (int z = 0; z < p.ns;) {
+            const int rc = large_pass(h, p, c, &z);
+            if (rc != FB_OK) return rc;
+        }
+    } else small_forward(h, p, c);
+    head_stage(h, p, c);
+    if (p.train) {
+        // exactly one of the launches that tick the Adam step counter -- the QR, C51 and scalar loss, fc1_bwd2_kernel -- is in a
+        // plan when only < 0, and p.tick is false whenever only >= 0
+        if (p.tick) h->adam_ticked = !p.apply_adam;              // stays pending until fb_qnet_apply_adam consumes it
+        if ((c.c51 || c.big) && runs(c, K_LOSS)) loss_stage(h, p, c);
+        if (runs(c, K_FC1_BWD)) fc1_backward(h, p, c);
         // data-parallel path: from here on G[CONV_PARAMS ..) -- W_fc1, b_fc1, the head: 91 % of the bytes -- is final; the caller's side
         // stream can start reducing it while the conv backward below still runs (fb_qnet_set_grad_event)
         if (!p.apply_adam && only < 0) {
@@ -4509,97 +4612,9 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         // (measured, profiles/r03_notes.md: splitting it between that launch and the conv weight gradients' costs the same ~3.5 us in all
         // -- the span is HBM traffic at ~6.5 TB/s and what it slows is the latency-bound chains beside it, wherever it rides); the
         // data-parallel path exports the gradient instead
-        const int span0 = OFF_WF1 / 4, span1 = p.apply_adam ? (OFF_WF1 + 1600 * FC) / 4 : span0;
-        const AdamSpan span{master(h, 0), h->adam_m, h->adam_v, G, h->adam, span0, span1};
-        // split schedule: the fc1 backward launch has waited for the acting trunk on the other stream (its gate workgroup), so W_fc1's Adam
-        // span may ride in the launches below; the last of them waits for that stream's fc1 launch, so the Adam launch may follow
-        FbGate gate_fc1{nullptr, 0, nullptr};
-        if (p.split && only < 0) gate_fc1 = FbGate{&p.split->f->fc1_done, p.split->seq, &p.split->f->timeouts[3]};
-        FbSampleRider srider;
-        memset(&srider, 0, sizeof(srider));
-        if (p.sample_rider) srider = *p.sample_rider;
-        {
-            // [data-gradient chain per sample + conv3 dW + W_fc1's Adam] and [conv2 dW + conv1 dW] (see conv_bx_kernel)
-            // conv1's weight gradient: two workgroups per sample, each with its own slab (2 B slabs); more than zmax of them are written
-            // to the sub-slab buffer and folded into zmax slabs afterwards, in a fixed order
-            const bool fold1 = 2 * B > h->zmax;
-            const int fold = (2 * B + h->zmax - 1) / h->zmax;
-            z1 = fold1 ? (2 * B + fold - 1) / fold : 2 * B;
-            const int n_adam5 = (span1 - span0 + 511) / 512;
-            const BxArgs bx{h->dh3, h->h2, h->p1, h->dh2, h->dp1, h->wsp[0] + wsp_w3t(FC), h->wsp[0] + wsp_w2t(FC)};
-            // large batches (multiples of 16): conv3's and conv2's weight gradients per group of 16 samples in a launch of their own
-            // (conv_dwg_kernel) instead of as 38 + 34 tiles per slab inside the two launches below; one slab per group
-            const bool dwg = big && B % 16 == 0;
-            const int zt3 = dwg ? 0 : z3, zt2 = zt3;
-            // small batches: the whole conv backward per sample in ONE launch (conv_bw_kernel); one conv2 / conv3 slab per sample
-            const bool bw = fk && B <= h->zmax;
-            // split schedule: W_fc1's Adam span rides in the next launch, and the acting trunk running beside this step on another stream
-            // re-splits W_fc1's planes from those very parameters in its first microseconds
-
-            if (bw) {
-                z3 = B;
-                FB_K(K_CONV3_BWD) {
-                    const Dw1Ring dr{p.ring ? p.ring->c.bits : nullptr, h->ring_fo};
-                    float *s1 = fold1 ? h->slabs1 : h->slabs;
-                    const size_t st1 = fold1 ? (size_t)CONV1_PARAMS : ss;
-                    const dim3 g(BW_WGS * B + n_adam5 + (srider.k ? 1 : 0) + (gate_fc1.flag ? 1 : 0));
-                    if (h->nsplit_train == 3) {
-                        if (p.ring) hipLaunchKernelGGL((conv_bw_kernel<3, true>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
-                        else hipLaunchKernelGGL((conv_bw_kernel<3, false>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
-                    } else {
-                        if (p.ring) hipLaunchKernelGGL((conv_bw_kernel<1, true>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
-                        else hipLaunchKernelGGL((conv_bw_kernel<1, false>), g, dim3(512), 0, st, bx, B, h->slabs, ss, s1, st1, p.s, (const uint8_t *)h->amax, dr, n_adam5, span, srider, rbt, gate_fc1);
-                    }
-                }
-                if (fold1) FB_K(K_CONV2_BWD) hipLaunchKernelGGL(slab_fold_kernel, dim3((CONV1_PARAMS + 255) / 256, z1), dim3(256), 0, st, h->slabs1, 2 * B, fold, h->slabs, ss);
-            } else {
-            FB_K(K_CONV3_BWD) {
-                const dim3 g(B + 38 * zt3 + n_adam5 + (srider.k ? 1 : 0));
-                if (h->nsplit_train == 3) hipLaunchKernelGGL(conv_bx_kernel<3>, g, dim3(512), 0, st, bx, B, zt3, h->slabs, ss, n_adam5, span, srider, rbt);
-                else hipLaunchKernelGGL(conv_bx_kernel<1>, g, dim3(512), 0, st, bx, B, zt3, h->slabs, ss, n_adam5, span, srider, rbt);
-            }
-            if (dwg) {
-                z3 = B / 16;                                 // (conv2's slab count follows: z2 below)
-                FB_K(K_CONV2_BWD) {
-                    const int n3 = z3 * 4, n2 = z3 * 8;
-                    if (h->nsplit_train == 3) hipLaunchKernelGGL(conv_dwg_kernel<3>, dim3(n3 + n2), dim3(512), 0, st, n3, h->h2, h->dh3, h->p1, h->dh2, h->slabs, ss, &h->adam->ovf);
-                    else hipLaunchKernelGGL(conv_dwg_kernel<1>, dim3(n3 + n2), dim3(512), 0, st, n3, h->h2, h->dh3, h->p1, h->dh2, h->slabs, ss, &h->adam->ovf);
-                }
-            }
-            FB_K(K_CONV2_BWD) {
-                const Dw1Ring dr{p.ring ? p.ring->c.bits : nullptr, h->ring_fo};
-                float *s1 = fold1 ? h->slabs1 : h->slabs;
-                const size_t st1 = fold1 ? (size_t)CONV1_PARAMS : ss;
-                const dim3 g(34 * zt2 + 2 * B + (gate_fc1.flag ? 1 : 0));
-                if (p.ring) hipLaunchKernelGGL((conv_dw21_kernel<2, true>), g, dim3(512), 0, st, zt2, B, h->p1, h->dh2, p.s, h->dp1, h->amax, h->slabs, ss, s1, st1, rbt, dr, gate_fc1);
-                else hipLaunchKernelGGL((conv_dw21_kernel<2, false>), g, dim3(512), 0, st, zt2, B, h->p1, h->dh2, p.s, h->dp1, h->amax, h->slabs, ss, s1, st1, rbt, dr, gate_fc1);
-                if (fold1) hipLaunchKernelGGL(slab_fold_kernel, dim3((CONV1_PARAMS + 255) / 256, z1), dim3(256), 0, st, h->slabs1, 2 * B, fold, h->slabs, ss);
-            }
-            }
-        }
-        // data-parallel path: the caller needs the complete flat gradient; fused path: Adam sums the slabs itself
-        const int z2 = z3;
-        if (p.split && only < 0) h->split_adam_pending = !p.apply_adam;
-        if (!p.apply_adam) FB_K(K_SLAB) hipLaunchKernelGGL(slab_reduce_kernel, dim3((CONV_PARAMS / 4 + 255) / 256), dim3(256), 0, st, h->slabs, ss, z1, z2, z3, G);
-        if (only < 0) noisy_sgrad(h, G, st);         // (a noisy net: sigma's gradient, from the gradient of the effective W_fc1 b_fc1 and head)
-        // split schedule: the Adam launch rewrites the conv planes / biases the acting trunk reads and the parameters its fc1 launch copies for the head
-
-        if (p.apply_adam) FB_K(K_ADAM)
-        {
-            AdamFused af;
-            af.p = master(h, 0); af.m = h->adam_m; af.v = h->adam_v; af.g = G; af.n = h->ntot; af.ad = h->adam;
-            af.slabs = h->slabs; af.slab_stride = ss; af.z1 = z1; af.z2 = z2; af.z3 = z3;
-            af.w1s = h->w1s[0]; af.wsp = h->wsp[0]; af.FC = FC; af.tail0 = span1;
-            const long long nrest4 = OFF_W2 / 4 + (OFF_W3 - OFF_B2) / 4 + (OFF_WF1 - OFF_B3) / 4 + (h->ntot / 4 - span1);
-            af.lanes = 4;                                    // slab mode: one chunk of <= 16 slabs per lane
-            af.split = p.split && only < 0 ? p.split->f : nullptr; af.split_val = p.split ? p.split->seq : 0;
-            af.n_rest = (int)((nrest4 * af.lanes + 255) / 256);
-            hipLaunchKernelGGL(adam_fused_kernel, dim3(ADAMF_T2 + ADAMF_T3 + af.n_rest), dim3(256), 0, st, af);
-            noisy_materialise(h, 0, 0, false, st);
-            c51d_fold(h, 0, st);
-        }
+        const int span0 = OFF_WF1 / 4, span1 = p.apply_adam ? (OFF_WF1 + 1600 * h->FC) / 4 : span0;
+        reduce_or_adam(h, p, c, conv_backward(h, p, c, span0, span1), span1);
     }
-#undef FB_K
     FB_LAUNCH_CHECK();
     return FB_OK;
 }
@@ -4607,42 +4622,47 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
 static Plan forward_plan(fb_qnet *h, int which, const uint8_t *states, int n) {
     Plan p; memset(&p, 0, sizeof(p));
     p.sl.s[0] = Slice{h->params[which], states, 0, n, h->w1s[which], 0};
-    p.ns = 1; p.which = which;
+    p.ns = 1;
     return p;
+}
+
+static bool rows_ok(const fb_qnet *h, int n) { return n >= 1 && n <= 3 * h->max_batch; }      // the rows of a plan fit the workspace
+static int copy_q(fb_qnet *h, int n, float *q, hipStream_t st) {      // the Q values of the n rows the last plan ran, to the caller (q may be NULL)
+    if (q) FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)n * h->A, hipMemcpyDeviceToDevice, st));
+    return FB_OK;
 }
 
 extern "C" int fb_qnet_forward(fb_qnet_t h, int which, const uint8_t *states, int batch, float *q, void *stream) {
     FB_REQUIRE(h && states && q && (which == 0 || which == 1), "fb_qnet_forward: bad argument");
-    FB_REQUIRE(batch >= 1 && batch <= 3 * h->max_batch, "fb_qnet_forward: batch %d exceeds 3*max_batch", batch);
+    FB_REQUIRE(rows_ok(h, batch), "fb_qnet_forward: batch %d exceeds 3*max_batch", batch);
     int rc = run_plan(h, forward_plan(h, which, states, batch), -1, fb_stream(stream));
     if (rc != FB_OK) return rc;
-    FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)batch * h->A, hipMemcpyDeviceToDevice, fb_stream(stream)));
-    return FB_OK;
+    return copy_q(h, batch, q, fb_stream(stream));
+}
+
+// fb_qnet_act / fb_qnet_act_nib behind their argument checks (nib: the states are the env's nibble state)
+static int act_states(fb_qnet *h, const uint8_t *states, bool nib, int n, float epsilon, uint64_t seed, uint64_t step, uint8_t *actions, float *q,
+                      hipStream_t st) {
+    Plan p = forward_plan(h, 0, states, n);
+    p.nib = nib;
+    p.actions = actions; p.epsilon = epsilon; p.seed = seed; p.step = step;
+    int rc = run_plan(h, p, -1, st);
+    if (rc != FB_OK) return rc;
+    return copy_q(h, n, q, st);
 }
 
 extern "C" int fb_qnet_act(fb_qnet_t h, const uint8_t *states, int n, float epsilon, uint64_t seed, uint64_t step,
                            uint8_t *actions, float *q, void *stream) {
     FB_REQUIRE(h && states && actions, "fb_qnet_act: NULL argument");
-    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_qnet_act: n %d exceeds 3*max_batch", n);
-    Plan p = forward_plan(h, 0, states, n);
-    p.actions = actions; p.epsilon = epsilon; p.seed = seed; p.step = step;
-    int rc = run_plan(h, p, -1, fb_stream(stream));
-    if (rc != FB_OK) return rc;
-    if (q) FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)n * h->A, hipMemcpyDeviceToDevice, fb_stream(stream)));
-    return FB_OK;
+    FB_REQUIRE(rows_ok(h, n), "fb_qnet_act: n %d exceeds 3*max_batch", n);
+    return act_states(h, states, false, n, epsilon, seed, step, actions, q, fb_stream(stream));
 }
 
 extern "C" int fb_qnet_act_nib(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
                                uint8_t *actions, float *q, void *stream) {
     FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib: NULL argument");
-    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_qnet_act_nib: n %d exceeds 3*max_batch", n);
-    Plan p = forward_plan(h, 0, nib_states, n);
-    p.nib = true;
-    p.actions = actions; p.epsilon = epsilon; p.seed = seed; p.step = step;
-    int rc = run_plan(h, p, -1, fb_stream(stream));
-    if (rc != FB_OK) return rc;
-    if (q) FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)n * h->A, hipMemcpyDeviceToDevice, fb_stream(stream)));
-    return FB_OK;
+    FB_REQUIRE(rows_ok(h, n), "fb_qnet_act_nib: n %d exceeds 3*max_batch", n);
+    return act_states(h, nib_states, true, n, epsilon, seed, step, actions, q, fb_stream(stream));
 }
 
 int fb_qnet_num_actions(fb_qnet_t h) { return h ? h->A : 0; }
@@ -4686,7 +4706,7 @@ int fb_qnet_check_env_noise(fb_qnet_t h, int n, const char *who) {
     FB_REQUIRE(h, "%s: NULL handle", who);
     FB_REQUIRE(h->noisy, "%s: per-env acting noise needs a noisy net (fb_qnet_create_c51_noisy)", who);
     FB_REQUIRE(h->nsplit == 3, "%s: per-env acting noise takes FB_DTYPE_F32 inference only (the net is set to FB_DTYPE_BF16)", who);
-    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "%s: n %d exceeds 3*max_batch", who, n);
+    FB_REQUIRE(rows_ok(h, n), "%s: n %d exceeds 3*max_batch", who, n);
     FB_REQUIRE((unsigned long long)n * (unsigned long long)h->nnet.nz < (1ull << 32), "%s: n * nz = %d * %d must stay below 2^32 (the noise counter)",
                who, n, h->nnet.nz);
     return FB_OK;
@@ -4697,12 +4717,15 @@ int fb_qnet_check_env_noise(fb_qnet_t h, int n, const char *who) {
 // per-env noisy head.  restore: rebuild params[0] (and the folded head) from the net's own sample -- the same launches that built them
 static int act_env_noise(fb_qnet *h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step, uint8_t *actions, float *q,
                          bool restore, hipStream_t st) {
+    FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib_env_noise: NULL argument");
+    int rc = fb_qnet_check_env_noise(h, n, "fb_qnet_act_nib_env_noise");
+    if (rc != FB_OK) return rc;
     const NoisyMat mu{h->mst[0], h->params[0], h->nz_zero, h->nnet, OFF_WF1, 0, h->adam};
     hipLaunchKernelGGL(noisy_mat_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, st, mu);
     c51d_fold(h, 0, st);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true; p.no_head = true;
-    int rc = run_plan(h, p, -1, st);
+    rc = run_plan(h, p, -1, st);
     if (rc != FB_OK) return rc;
     const bool sp = n >= 256;                    // (run_plan's: the fused two-plane trunk + fc1_sp_kernel, else the small-batch kernels)
     const int FC = h->FC, stot = 3 * h->max_batch;
@@ -4710,9 +4733,8 @@ static int act_env_noise(fb_qnet *h, const uint8_t *nib_states, int n, float eps
     const float *sig = h->mst[0] + h->n - OFF_WF1;      // (sigma of mu entry q at sig[q])
     hipLaunchKernelGGL(env_noise_sigsplit_kernel, dim3((unsigned)((200 * FC + 255) / 256)), dim3(256), 0, st, sig, h->wsig, FC, (const AdamDev *)h->adam,
                        (const int *)h->sig_seen);
-    const uint32_t seed_lo = (uint32_t)seed, seed_hi = (uint32_t)(seed >> 32), step_lo = (uint32_t)step, step_hi = (uint32_t)(step >> 32);
-    const EnvScale es{sp ? h->a3s : nullptr, sp ? nullptr : h->h3, pl2, h->a3n, n, h->nnet.nz, seed_lo, seed_hi, step_lo, step_hi, h->adam,
-                      h->sig_seen, &h->adam->ovf};
+    EnvScale es{sp ? h->a3s : nullptr, sp ? nullptr : h->h3, pl2, h->a3n, n, h->nnet.nz, 0, 0, 0, 0, h->adam, h->sig_seen, &h->adam->ovf};
+    put_seed_words(es, seed, step);
     hipLaunchKernelGGL(env_noise_scale_kernel, dim3((unsigned)(((long long)n * 800 + 255) / 256)), dim3(256), 0, st, es);
     const Fc1Args af{h->a3n, pl2, h->zeros, h->wsig + WSP_WF1, h->ht, stot, n, FC, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
     hipLaunchKernelGGL(fc1_sp_kernel<3>, dim3(((n + 127) / 128) * (FC / 64) * FC1_SP_KS), dim3(256), 0, st, af);
@@ -4720,37 +4742,24 @@ static int act_env_noise(fb_qnet *h, const uint8_t *nib_states, int n, float eps
     H.hf = sp ? h->hf_act : h->hf; H.ht = h->ht; H.stot = stot; H.nks = sp ? FC1_SP_KS : 1;
     H.P = head_base(h, h->params[0]); H.hoff = h->hoff; H.sig = sig; H.off = h->off; H.N = h->nnet;
     H.n = n; H.FC = FC; H.A = h->A; H.sup = h->sup; H.q = h->q; H.actions = actions; H.epsilon = epsilon;
-    H.seed_lo = seed_lo; H.seed_hi = seed_hi; H.step_lo = step_lo; H.step_hi = step_hi;
-    H.key_of = nullptr; H.stream = FB_STREAM_EPS;
-    const dim3 gh((n + ENH_WAVES - 1) / ENH_WAVES);
-    if (is_c51d(h)) {
-        if (h->A == 2) hipLaunchKernelGGL((env_noise_head_kernel<2, true>), gh, dim3(64 * ENH_WAVES), 0, st, H);
-        else hipLaunchKernelGGL((env_noise_head_kernel<MAXA, true>), gh, dim3(64 * ENH_WAVES), 0, st, H);
-    } else {
-        if (h->A == 2) hipLaunchKernelGGL((env_noise_head_kernel<2, false>), gh, dim3(64 * ENH_WAVES), 0, st, H);
-        else hipLaunchKernelGGL((env_noise_head_kernel<MAXA, false>), gh, dim3(64 * ENH_WAVES), 0, st, H);
-    }
+    put_seed_words(H, seed, step); H.key_of = nullptr; H.stream = FB_STREAM_EPS;
+    with_actions(h->A, [&](auto a) { with_bool(is_c51d(h), [&](auto d) {
+        hipLaunchKernelGGL((env_noise_head_kernel<decltype(a)::value, decltype(d)::value>), dim3((n + ENH_WAVES - 1) / ENH_WAVES), dim3(64 * ENH_WAVES), 0, st, H);
+    }); });
     if (restore) {
         noisy_materialise(h, 0, OFF_WF1, true, st);
         c51d_fold(h, 0, st);
     }
     FB_LAUNCH_CHECK();
-    if (q) FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)n * h->A, hipMemcpyDeviceToDevice, st));
-    return FB_OK;
+    return copy_q(h, n, q, st);
 }
 
 extern "C" int fb_qnet_act_nib_env_noise(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
                                          uint8_t *actions, float *q, void *stream) {
-    FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib_env_noise: NULL argument");
-    const int rc = fb_qnet_check_env_noise(h, n, "fb_qnet_act_nib_env_noise");
-    if (rc != FB_OK) return rc;
     return act_env_noise(h, nib_states, n, epsilon, seed, step, actions, q, true, fb_stream(stream));
 }
 int fb_qnet_act_nib_env_noise_keep(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
                                    uint8_t *actions, float *q, void *stream) {
-    FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib_env_noise: NULL argument");
-    const int rc = fb_qnet_check_env_noise(h, n, "fb_qnet_act_nib_env_noise");
-    if (rc != FB_OK) return rc;
     return act_env_noise(h, nib_states, n, epsilon, seed, step, actions, q, false, fb_stream(stream));
 }
 
@@ -4769,7 +4778,7 @@ extern "C" int fb_qnet_get_quantiles(fb_qnet_t h, int *n_quantiles_host, float *
 extern "C" int fb_qnet_forward_quantiles(fb_qnet_t h, int which, const uint8_t *states, int batch, float *theta, void *stream) {
     FB_REQUIRE(h && states && theta && (which == 0 || which == 1), "fb_qnet_forward_quantiles: bad argument");
     FB_REQUIRE(is_qr(h), "fb_qnet_forward_quantiles: not a QR net (fb_qnet_create_qr)");
-    FB_REQUIRE(batch >= 1 && batch <= 3 * h->max_batch, "fb_qnet_forward_quantiles: batch %d exceeds 3*max_batch", batch);
+    FB_REQUIRE(rows_ok(h, batch), "fb_qnet_forward_quantiles: batch %d exceeds 3*max_batch", batch);
     Plan p = forward_plan(h, which, states, batch);
     p.probs = theta;                             // (the QR head writes theta there)
     return run_plan(h, p, -1, fb_stream(stream));
@@ -4778,7 +4787,7 @@ extern "C" int fb_qnet_forward_quantiles(fb_qnet_t h, int which, const uint8_t *
 extern "C" int fb_qnet_forward_dist(fb_qnet_t h, int which, const uint8_t *states, int batch, float *probs, void *stream) {
     FB_REQUIRE(h && states && probs && (which == 0 || which == 1), "fb_qnet_forward_dist: bad argument");
     FB_REQUIRE(h->sup.N > 0 && !is_qr(h), "fb_qnet_forward_dist: not a C51 net (fb_qnet_create_c51; a QR net: fb_qnet_forward_quantiles)");
-    FB_REQUIRE(batch >= 1 && batch <= 3 * h->max_batch, "fb_qnet_forward_dist: batch %d exceeds 3*max_batch", batch);
+    FB_REQUIRE(rows_ok(h, batch), "fb_qnet_forward_dist: batch %d exceeds 3*max_batch", batch);
     Plan p = forward_plan(h, which, states, batch);
     p.probs = probs;
     return run_plan(h, p, -1, fb_stream(stream));
@@ -4796,10 +4805,7 @@ int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32
     C.off = h->hoff; C.sup = h->sup; C.actions = hd->c.actions; C.epsilon = hd->c.epsilon;
     C.seed_lo = hd->c.seed_lo; C.seed_hi = hd->c.seed_hi; C.step_lo = hd->c.step_lo; C.step_hi = hd->c.step_hi;
     C.key_of = key_of; C.stream = FB_STREAM_EVAL;
-    if (is_qr(h) && h->A == 2) hipLaunchKernelGGL(qr_head_kernel<2>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
-    else if (is_qr(h)) hipLaunchKernelGGL(qr_head_kernel<MAXA>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
-    else if (h->A == 2) hipLaunchKernelGGL(c51_head_kernel<2>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
-    else hipLaunchKernelGGL(c51_head_kernel<MAXA>, dim3((n + 3) / 4), dim3(256), 0, fb_stream(stream), H);
+    launch_dist_head(h, H, n, fb_stream(stream));
     FB_LAUNCH_CHECK();
     return FB_OK;
 }
@@ -4808,7 +4814,7 @@ hipStream_t fb_qnet_side_stream(fb_qnet_t h) { return h && h->split ? h->split->
 
 int fb_qnet_eval_trunk(fb_qnet_t h, const uint8_t *nib_states, int n, FbHeadRider *head, void *stream) {
     FB_REQUIRE(h && nib_states && head, "fb_qnet_eval_trunk: NULL argument");
-    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_qnet_eval_trunk: n %d exceeds 3*max_batch", n);
+    FB_REQUIRE(rows_ok(h, n), "fb_qnet_eval_trunk: n %d exceeds 3*max_batch", n);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true; p.any_rows = true;
     p.head_rider = head;
@@ -4817,13 +4823,12 @@ int fb_qnet_eval_trunk(fb_qnet_t h, const uint8_t *nib_states, int n, FbHeadRide
 
 extern "C" int fb_eval_q(fb_qnet_t h, const uint8_t *nib_states, int n, float *q, void *stream) {
     FB_REQUIRE(h && nib_states && q, "fb_eval_q: NULL argument");
-    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_eval_q: n %d exceeds 3*max_batch", n);
+    FB_REQUIRE(rows_ok(h, n), "fb_eval_q: n %d exceeds 3*max_batch", n);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true; p.any_rows = true;
     int rc = run_plan(h, p, -1, fb_stream(stream));
     if (rc != FB_OK) return rc;
-    FB_CHECK_HIP(hipMemcpyAsync(q, h->q, sizeof(float) * (size_t)n * h->A, hipMemcpyDeviceToDevice, fb_stream(stream)));
-    return FB_OK;
+    return copy_q(h, n, q, fb_stream(stream));
 }
 
 int fb_qnet_check_step(fb_qnet_t h, int n_envs, int train_batch) {
@@ -4838,7 +4843,7 @@ int fb_qnet_act_nib_rider(fb_qnet_t h, const uint8_t *nib_states, int n, float e
                           uint8_t *actions, FbHeadRider *head, void *stream, const FbSplitCtx *split) {
     FB_REQUIRE(h && nib_states && actions && head, "fb_qnet_act_nib_rider: NULL argument");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_act_nib_rider: a C51 or QR net's head does not ride in the env launch");
-    FB_REQUIRE(n >= 1 && n <= 3 * h->max_batch, "fb_qnet_act_nib: n %d exceeds 3*max_batch", n);
+    FB_REQUIRE(rows_ok(h, n), "fb_qnet_act_nib: n %d exceeds 3*max_batch", n);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true;
     p.actions = actions; p.epsilon = epsilon; p.seed = seed; p.step = step;
@@ -5006,14 +5011,7 @@ extern "C" int fb_qnet_profile_kernel(fb_qnet_t h, int kernel, int reps, int alg
     } else rc = train_plan(h, algo, B, s, a, r, s2, t, nullptr, 0.99, loss, nullptr, nullptr, nullptr, &p);
     if (rc != FB_OK) return rc;
     p.tick = false;
-    {                                            // bring both nets' split planes up to date once, outside the timed launches
-        const int items = wsplit_items(h->FC);
-        for (int n = 0; n < 2; n++) {
-            hipLaunchKernelGGL(wsplit_kernel, dim3((items + 255) / 256), dim3(256), 0, fb_stream(stream), h->params[n], h->wsp[n], h->FC,
-                               (const unsigned *)&h->adam->pver[n], (const unsigned *)&h->adam->wver[n]);
-            hipLaunchKernelGGL(mark_split_kernel, dim3(1), dim3(1), 0, fb_stream(stream), h->adam, n);
-        }
-    }
+    for (int n = 0; n < 2; n++) resplit_now(h, n, fb_stream(stream));      // bring both nets' split planes up to date once, outside the timed launches
     for (int i = 0; i < reps; i++) { rc = run_plan(h, p, kernel, fb_stream(stream)); if (rc != FB_OK) return rc; }
     return FB_OK;
 }
