@@ -144,7 +144,9 @@ def _batch(rng, B, ints=False):
 
 def _check_grads(g, g0, n_head_cols, fc=FC):
     """per tensor.  The head's gradients are continuous in the activations: elementwise, with the scalar tests' bounds.  The rest
-    pass through ReLU / max-pool derivatives, which flip for the rare unit within rounding distance of its kink: relative L2."""
+    pass through ReLU / max-pool derivatives, which flip for the rare unit within rounding distance of its kink: relative L2 here,
+    where the batches are taken as drawn.  On batches whose samples were each drawn clear of the kinks (tests/kinkfree.py) every
+    tensor, the trunk and fc1 included, is compared elementwise: tests/test_gpu_kinkfree_grads.py::test_distributional."""
     tensors = tensor_bounds(fc, 1, "c51", n_head_cols)
     assert tensors[-1][2] == len(g0)
     for k, (_, lo, hi) in enumerate(tensors):

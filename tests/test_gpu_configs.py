@@ -39,7 +39,8 @@ def test_config2_double_dqn_batch256_gradients(torch_cuda, oracle):
     np.testing.assert_allclose(y.cpu().numpy(), y0, rtol=0, atol=1e-4)
     np.testing.assert_allclose(loss.item(), loss0, rtol=1e-4)
     g = grad.cpu().numpy()
-    # with 256 samples a handful of units sit on a ReLU kink (see test_gpu_qnet): compare in aggregate
+    # 256 samples taken as drawn: a handful of units sit on a ReLU kink (see test_gpu_qnet), so compare in aggregate here.  (A kink-free
+    # batch of 256 comes from rejecting SAMPLES, tests/kinkfree.py; tests/test_gpu_kinkfree_grads.py compares it element by element.)
     rel = np.linalg.norm(g - g0) / np.linalg.norm(g0)
     assert rel < 2e-2, rel
     for lo, hi in ((77984, 77984 + 1600 * 512), (77984 + 1600 * 512 + 512, net.n_params)):   # fc1 / head: kink-insensitive

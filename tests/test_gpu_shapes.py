@@ -169,9 +169,11 @@ def scalar_batch(rng, B, A, algo):
 
 def check_scalar_grads(g, g0, fc, A, dueling, kink_free, value_free=False):
     """per tensor.  A kink-free batch (every ReLU input and pool margin above 2e-5): every tensor elementwise with
-    test_train_step_gradients_match_oracle's bounds.  Otherwise (B >= 255, where some of the ~10^7 unit inputs always sit within
-    rounding distance of a kink): fc1 and the head elementwise (test_config2_double_dqn_batch256_gradients), the convolutions in relative
-    L2 (tests/test_gpu_c51.py::_check_grads).  The dueling head's advantage stream at A = 1 has no gradient at all (Q = V); value_free:
+    test_train_step_gradients_match_oracle's bounds.  Otherwise (B >= 255 drawn as one batch: among its ~10^7 unit inputs some sit
+    within rounding distance of a kink, and this test rejects whole batches only): fc1 and the head elementwise
+    (test_config2_double_dqn_batch256_gradients), the convolutions in relative L2 (tests/test_gpu_c51.py::_check_grads).  The margin is
+    a property of one sample, though: tests/kinkfree.py rejects samples one by one, and tests/test_gpu_kinkfree_grads.py compares every
+    tensor elementwise at these batch sizes.  The dueling head's advantage stream at A = 1 has no gradient at all (Q = V); value_free:
     the loss's dQ sums to 0 over the actions (policy gradient), so the value stream's gradient is 0 up to rounding: on W_q's scale."""
     tensors = tensor_bounds(fc, A, arch_of(dueling))
     for k, (name, lo, hi) in enumerate(tensors):
