@@ -15,6 +15,9 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
                                                                                        qrdqnper: with prioritized replay; qrrainbow:
                                                                                        dueling QR head, double target, PER; --n-quantiles,
                                                                                        --kappa)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model mdqn --vec 1024 [--tau 0.03 --alpha 0.9 --clip -1] [--n-step K]
+                                                                                      (Munchausen-DQN on the scalar head: soft bootstrap +
+                                                                                       clipped log-policy bonus; mdqnper: prioritized replay)
     python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy --acting-noise env
                                                                                       (... acting with independent noise per env)
 
@@ -87,8 +90,25 @@ def main():
                         help="--noisy: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
     parser.add_argument("--n-quantiles", type=int, default=None, help="QR models: the number of quantiles N (default 51)")
     parser.add_argument("--kappa", type=float, default=None, help="QR models: the quantile Huber loss's threshold (default 1)")
+    parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper: the softmax temperature (default 0.03)")
+    parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9)")
+    parser.add_argument("--clip", type=float, default=None, help="--model mdqn | mdqnper: the bonus's lower clip l0 (default -1)")
     args = parser.parse_args()
     qr_models = ("qrdqn", "qrdqnper", "qrrainbow")
+    md_models = ("mdqn", "mdqnper")
+    if args.model in md_models:                          # (refused before anything touches the GPU)
+        if not args.vec:
+            parser.error(f"--model {args.model} needs --vec: Munchausen-DQN runs in the vectorised loop only")
+        if args.noisy:
+            parser.error(f"--noisy needs a C51 model (c51, c51per, c51doubleper, rainbow), not --model {args.model}")
+        from .vec import MDQN_DEFAULTS, check_munchausen
+        try:
+            mkw = dict(zip(("tau", "alpha", "clip"), check_munchausen(*(d if v is None else v for v, d in
+                                                                       zip((args.tau, args.alpha, args.clip), MDQN_DEFAULTS)))))
+        except ValueError as e:
+            parser.error(str(e))
+    elif args.tau is not None or args.alpha is not None or args.clip is not None:
+        parser.error(f"--tau / --alpha / --clip need a Munchausen model ({', '.join(md_models)}), not --model {args.model}")
     if args.model in qr_models:                          # (refused before anything touches the GPU)
         if not args.vec:
             parser.error(f"--model {args.model} needs --vec: QR-DQN runs in the vectorised loop only")
@@ -128,12 +148,14 @@ def main():
             raise SystemExit("--vec runs the DQN family; the actor-critic / policy-gradient agents are single-env (as in the reference)")
         algo = {"dqn": "dqn", "ddqn": "nature", "dqnnature": "nature", "duelingdqn": "nature", "prioritydqn": "per", "c51": "c51",
                 "c51per": "c51per", "c51doubleper": "c51doubleper", "rainbow": "c51doubleper", "qrdqn": "qr", "qrdqnper": "qrper",
-                "qrrainbow": "qrdoubleper"}[args.model]
+                "qrrainbow": "qrdoubleper", "mdqn": "mdqn", "mdqnper": "mdqnper"}[args.model]
         arch = "c51dueling" if args.model == "rainbow" else "plain"      # rainbow: dueling C51 head, double target, prioritized replay
         qkw = {}
         if args.model in qr_models:                      # qrrainbow: dueling QR head, double target, prioritized replay
             arch = "qrdueling" if args.model == "qrrainbow" else "qr"
             qkw = dict(n_quantiles=51 if args.n_quantiles is None else args.n_quantiles, kappa=1.0 if args.kappa is None else args.kappa)
+        if args.model in md_models:
+            qkw = mkw
         vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step, noisy=args.noisy,
                       acting_noise=args.acting_noise, **qkw)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)

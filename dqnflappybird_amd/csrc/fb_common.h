@@ -39,8 +39,10 @@ static inline bool is_qr_algo(int algo) {           // trains a QR net
 static inline bool is_double_qr(int algo) { return algo == FB_ALGO_QR_DOUBLE || algo == FB_ALGO_QR_DOUBLE_PER; }       // a* online
 static inline bool is_per_algo(int algo) {          // prioritized memory, importance weights, |TD error| / priority out
     return algo == FB_ALGO_PER || algo == FB_ALGO_C51_PER || algo == FB_ALGO_C51_DOUBLE_PER || algo == FB_ALGO_QR_PER ||
-           algo == FB_ALGO_QR_DOUBLE_PER;
+           algo == FB_ALGO_QR_DOUBLE_PER || algo == FB_ALGO_MDQN_PER;
 }
+static inline bool is_mdqn_algo(int algo) { return algo == FB_ALGO_MDQN || algo == FB_ALGO_MDQN_PER; }      // Munchausen target, a scalar net
+static inline bool is_scalar_algo(int algo) { return (algo >= FB_ALGO_DQN && algo <= FB_ALGO_PER) || is_mdqn_algo(algo); }      // the scalar-head algos the ring-fed calls take
 
 // Hand-offs between kernels of two streams through device words (fb_vec_step's split schedule).  A word only ever grows (the step
 // number).  Stores and polls are relaxed agent-scope atomics (they go to the coherent level, past the XCD's own L2); a reader that goes

@@ -104,6 +104,18 @@ static int qr_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *who
     return FB_OK;
 }
 
+// Munchausen-DQN (include/fbdqn.h): a scalar net; FB_ALGO_MDQN takes a uniform memory, FB_ALGO_MDQN_PER a prioritized one.  Checked by the
+// ring-fed calls before any counter moves or any launch, as the C51 / QR checks beside them
+static int mdqn_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *who) {
+    if (!is_mdqn_algo(algo)) return FB_OK;
+    FB_REQUIRE(!fb_qnet_is_dist(net), "%s: algo %d (Munchausen-DQN) trains a scalar net (FB_ARCH_PLAIN / FB_ARCH_DUELING) only, not a C51 / QR / noisy net", who, algo);
+    if (algo == FB_ALGO_MDQN_PER)
+        FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: FB_ALGO_MDQN_PER trains from a prioritized memory only (FB_ALGO_MDQN takes a uniform one)", who);
+    else
+        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: FB_ALGO_MDQN trains from a uniform memory only (FB_ALGO_MDQN_PER takes a prioritized one)", who);
+    return FB_OK;
+}
+
 // n x (random.sample -> minibatch -> _trainQNetwork) on a memory that is not being pushed to, as one host call.  Each step is the six
 // launches of the ring-fed train step (conv trunk of the 2B states straight from the 1-bit frame ring -> fc1 -> loss + fc1 backward ->
 // conv data gradients -> conv weight gradients -> Adam): no gather, no u8 minibatch.  Only the first draw gets a launch of its own: the
@@ -127,6 +139,8 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
     {
         const int rq = qr_check(replay, net, algo, "fb_train_steps");
         if (rq != FB_OK) return rq;
+        const int rm = mdqn_check(replay, net, algo, "fb_train_steps");
+        if (rm != FB_OK) return rm;
     }
     int rc = fb_replay_check_gamma(replay, gamma, "fb_train_steps");
     if (rc != FB_OK) return rc;
@@ -266,7 +280,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // every argument check of the calls below happens HERE, before the replay's push counter moves or anything is launched: a
     // rejected step must leave the handles exactly as they were (a counted push without its env launch would make every later
     // gather address a ring slot that was never written)
-    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo) || is_qr_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER)", algo);
+    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_MDQN_PER)", algo);
     // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
     // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
     // counter moves
@@ -279,6 +293,8 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     {
         const int rq = qr_check(replay, net, algo, "fb_vec_step");
         if (rq != FB_OK) return rq;
+        const int rm = mdqn_check(replay, net, algo, "fb_vec_step");
+        if (rm != FB_OK) return rm;
     }
     FB_REQUIRE(per == (fb_replay_is_prioritized(replay) != 0), "fb_vec_step: algo %d and the memory's kind (uniform / prioritized) do not match", algo);
     FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_vec_step: n_envs %d does not match the env (%d) / replay (%d) handles",
@@ -449,7 +465,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
 extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo, int batch, const int64_t *idx, const float *isw, uint8_t *a,
                                     float *r, uint8_t *t, double gamma, float *loss, float *abs_err, float *flat_grad, void *stream) {
     FB_REQUIRE(replay && net && idx && a && r && t && loss, "fb_train_from_replay: NULL argument");
-    FB_REQUIRE((algo >= 0 && algo <= 3) || is_c51_algo(algo) || is_qr_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER)", algo);
+    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_MDQN_PER)", algo);
     // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
     // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
     // counter moves
@@ -462,6 +478,8 @@ extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo,
     {
         const int rq = qr_check(replay, net, algo, "fb_train_from_replay");
         if (rq != FB_OK) return rq;
+        const int rm = mdqn_check(replay, net, algo, "fb_train_from_replay");
+        if (rm != FB_OK) return rm;
     }
     FB_REQUIRE(!is_per_algo(algo) || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
     if (is_c51_algo(algo) && is_per_algo(algo))

@@ -1308,6 +1308,24 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs H) {
 struct AdamDev { float b1pow, b2pow, alpha, lr, b1, b2, eps, pad; int ticks, applies; unsigned pver[2], wver[2], wverc[2];
                  unsigned ovf; };      // ovf: waves that split an activation beyond FB_F16_RANGE (note_overflow)
 
+// Munchausen-DQN (include/fbdqn.h): the net's (tau, alpha, l0).  MD instantiations of the two scalar loss bodies read the THIRD slice
+// (rows 2B ..: s through the target net) whatever L.algo says, and L.algo names the loss's form alone there: FB_ALGO_NATURE (FB_ALGO_MDQN)
+// or FB_ALGO_PER (FB_ALGO_MDQN_PER).  The other instantiations are what they were before the parameter existed.
+struct MdPar { float tau, alpha, clip; };
+// V = lse_tau(q-(s', .)) and the bonus alpha max(tau ln pi-(a|s), l0) from the finished Q rows qn = q-(s', .), q3 = q-(s, .); entries
+// c >= A are masked by selects.  One action: the sums are exp(0) = 1, log(1) = 0, so V = qn[0] and the bonus 0 exactly.
+template <int AT, int NQ>
+__device__ __forceinline__ void mdqn_target(const float (&qn)[NQ], const float (&q3)[NQ], int A, int a_b, const MdPar &M, float &V, float &bonus) {
+    float mn = qn[0], m3 = q3[0], qa = q3[0];
+#pragma unroll
+    for (int c = 1; c < AT; c++) { mn = c < A ? fmaxf(mn, qn[c]) : mn; m3 = c < A ? fmaxf(m3, q3[c]) : m3; qa = c == a_b ? q3[c] : qa; }
+    float sn = 0.f, s3 = 0.f;
+#pragma unroll
+    for (int c = 0; c < AT; c++) { sn += c < A ? expf((qn[c] - mn) / M.tau) : 0.f; s3 += c < A ? expf((q3[c] - m3) / M.tau) : 0.f; }
+    V = mn + M.tau * logf(sn);
+    bonus = M.alpha * fmaxf((qa - m3) - M.tau * logf(s3), M.clip);
+}
+
 struct LossArgs {
     int algo, B, FC, A, dueling;
     NetOff off;
@@ -1330,8 +1348,8 @@ struct LossArgs {
 // B <= 32) are requested at the top, together with the Q values / rewards / actions of the target computation --
 // nothing is loaded behind the barrier, and no load sits under a branch (clamped addresses + selects; AT = the
 // number of actions at compile time, MAXA = read it from L.A).
-template <int AT>
-__device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[MAXA], float *dv, float *lterm, float (*part)[16][MAXA + 2], float *wmax) {
+template <int AT, bool MD = false>
+__device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[MAXA], float *dv, float *lterm, float (*part)[16][MAXA + 2], float *wmax, const MdPar M = MdPar{}) {
     const int tid = threadIdx.x, B = L.B, A = AT == MAXA ? L.A : AT;
     const bool lead = blockIdx.x == 0;
     const float *P = L.params;
@@ -1356,7 +1374,7 @@ __device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[
         const int ac = a < A ? a : 0;
         qsv[a] = L.q[(size_t)tb * A + ac];
         qnv[a] = L.q[(size_t)(B + tb) * A + ac];                 // DQN: online(s'); Nature/PER: target(s'); Double: online(s')
-        q3v[a] = L.q[(size_t)((dbl ? 2 * B : 0) + tb) * A + ac]; // Double only: target(s')
+        q3v[a] = L.q[(size_t)((MD || dbl ? 2 * B : 0) + tb) * A + ac]; // Double only: target(s'); Munchausen (MD): target(s)
     }
     const float rf = L.rew[tb];
     const int termb = L.term[tb], a_b = L.act[tb];
@@ -1384,7 +1402,12 @@ __device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[
             for (int a = 1; a < AT; a++) sel = a < A ? fmaxf(sel, qnv[a]) : sel;
         }
         // BrainDQN.py:210-215: python float64 arithmetic on the rewards 0.1 / 3 / -3, then fed as float32
-        const double r = rf == 0.1f ? 0.1 : (double)rf;
+        double r = rf == 0.1f ? 0.1 : (double)rf;
+        if constexpr (MD) {                                      // Munchausen: the soft bootstrap, and the log-policy bonus on the reward
+            float bonus;
+            mdqn_target<AT>(qnv, q3v, A, a_b, M, sel, bonus);
+            r += (double)bonus;
+        }
         const double yd = termb ? r : r + L.gamma * (double)sel;
         const float y = (float)yd;
         float qe = qsv[0];
@@ -1480,6 +1503,16 @@ __global__ __launch_bounds__(256) void loss_head_kernel(LossArgs L) {
     __shared__ float wmax[4];
     if (L.A == 2) loss_head_body<2>(L, dadv, dv, lterm, part, wmax);
     else loss_head_body<MAXA>(L, dadv, dv, lterm, part, wmax);
+}
+// ... with the Munchausen target (FB_ALGO_MDQN / _PER): a kernel of its own, so that loss_head_kernel stays the code it was
+__global__ __launch_bounds__(256) void loss_head_md_kernel(LossArgs L, MdPar M) {
+    __shared__ float dadv[MAXTB][MAXA];
+    __shared__ float dv[MAXTB];
+    __shared__ float lterm[MAXTB];
+    __shared__ float part[16][16][MAXA + 2];
+    __shared__ float wmax[4];
+    if (L.A == 2) loss_head_body<2, true>(L, dadv, dv, lterm, part, wmax, M);
+    else loss_head_body<MAXA, true>(L, dadv, dv, lterm, part, wmax, M);
 }
 
 // fb_qnet_apply_adam on gradients that no fb_qnet_train_step ticked for (guarded on the device, so it is safe to launch always)
@@ -2230,8 +2263,8 @@ constexpr int BW_DW_ROW = 36;                // dhf row stride in LDS (dW role)
 
 // DX: the role is a template argument and the kernel branches ONCE, at the top, into one of two straight-line bodies (a role branch
 // around the pre-loads would put a vmcnt(0) join between them and the prologue's own loads)
-template <int AT, bool DX>
-__device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem) {
+template <int AT, bool DX, bool MD = false>
+__device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem, const MdPar M = MdPar{}) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, B = L.B, FC = L.FC, A = AT == MAXA ? L.A : AT;
     const float *P = L.params;
     float (*dadv)[MAXA] = reinterpret_cast<float (*)[MAXA]>(smem);                  // [MAXTB][MAXA]
@@ -2239,6 +2272,7 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem) {
     // (dadv2: the two-action plain head's dA as packed pairs [b][2], 16-byte aligned per two rows)
     const bool lead = blockIdx.x == 0;
     const bool dbl = L.algo == FB_ALGO_DOUBLE;
+    const bool row3 = MD || dbl;                 // a third slice at rows 2B ..: Double's s' through the target net, Munchausen's (MD) s through it
     const int qs = A + 1, ntile = FC >> 4;
     // ---- role of this workgroup, and EVERY global load its body needs, issued before the target computation: the fc1 sums, the
     // unit parameters, the W_fc1 runs / h3 operands depend on nothing computed here, so the kernel makes one round trip to memory,
@@ -2305,7 +2339,7 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem) {
 #pragma unroll
             for (int c = 0; c <= AT; c++) {
                 const int cc = c < qs ? c : 0;
-                x0[u][c] = q0[cc]; x1[u][c] = q0[(size_t)B * rs + cc]; x2[u][c] = q0[(size_t)(dbl ? 2 * B : 0) * rs + cc];
+                x0[u][c] = q0[cc]; x1[u][c] = q0[(size_t)B * rs + cc]; x2[u][c] = q0[(size_t)(row3 ? 2 * B : 0) * rs + cc];
             }
         }
         keep(rf); keep(isw); keep(termb); keep(a_b);
@@ -2326,7 +2360,7 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem) {
             for (int c = 0; c <= AT; c++) {
                 const int cc = c < qs ? c : 0;
                 const bool on = c < A || (c == A && L.dueling);
-                const float y0 = q0[cc], y1 = q0[(size_t)B * rs + cc], y2 = q0[(size_t)(dbl ? 2 * B : 0) * rs + cc];
+                const float y0 = q0[cc], y1 = q0[(size_t)B * rs + cc], y2 = q0[(size_t)(row3 ? 2 * B : 0) * rs + cc];
                 qsv[c] += on ? y0 : 0.f; qnv[c] += on ? y1 : 0.f; q3v[c] += on ? y2 : 0.f;
             }
         }
@@ -2365,7 +2399,12 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem) {
         }
         if (L.algo != FB_ALGO_PER) isw = 1.f;
         // BrainDQN.py:210-215: python float64 arithmetic on the rewards 0.1 / 3 / -3, then fed as float32
-        const double rr = rf == 0.1f ? 0.1 : (double)rf;
+        double rr = rf == 0.1f ? 0.1 : (double)rf;
+        if constexpr (MD) {                                          // Munchausen: the soft bootstrap, and the log-policy bonus on the reward
+            float bonus;
+            mdqn_target<AT>(qnv, q3v, A, a_b, M, sel, bonus);
+            rr += (double)bonus;
+        }
         const double yd = termb ? rr : rr + L.gamma * (double)sel;
         const float y = (float)yd;
         float qe = qsv[0];
@@ -2579,6 +2618,14 @@ __global__ __launch_bounds__(512) void fc1_bwd2_kernel(Bw1Args L) {
     const bool dx = (int)blockIdx.x < L.n_dx;
     if (L.A == 2) { if (dx) fc1_bwd2_body<2, true>(L, smem_bw); else fc1_bwd2_body<2, false>(L, smem_bw); }
     else { if (dx) fc1_bwd2_body<MAXA, true>(L, smem_bw); else fc1_bwd2_body<MAXA, false>(L, smem_bw); }
+}
+// ... with the Munchausen target (FB_ALGO_MDQN / _PER): a kernel of its own, so that fc1_bwd2_kernel stays the code it was
+__global__ __launch_bounds__(512) void fc1_bwd2_md_kernel(Bw1Args L, MdPar M) {
+    __shared__ float smem_bw[BW_LDS];
+    if (fb_gate_workgroup(L.gate)) return;
+    const bool dx = (int)blockIdx.x < L.n_dx;
+    if (L.A == 2) { if (dx) fc1_bwd2_body<2, true, true>(L, smem_bw, M); else fc1_bwd2_body<2, false, true>(L, smem_bw, M); }
+    else { if (dx) fc1_bwd2_body<MAXA, true, true>(L, smem_bw, M); else fc1_bwd2_body<MAXA, false, true>(L, smem_bw, M); }
 }
 
 // ================================================================== backward
@@ -3815,6 +3862,7 @@ struct fb_qnet {
     FbSplitCtx *split;               // fb_qnet_split_ctx
     C51Sup sup;                      // C51 nets: the support (sup.N = 0: a scalar head); QR nets: sup.N = n_quantiles, the rest 0
     float kappa;                     // QR nets: the quantile Huber loss's threshold
+    MdPar md;                        // scalar nets: Munchausen-DQN's (tau, alpha, l0) (fb_qnet_set_munchausen)
     float *c51_dl, *c51_xs, *c51_lt; // C51 training: logit gradients [max_batch][64], fc1 activations of s [max_batch][FC], loss terms [max_batch]
     // what the C51 head / loss / eval kernels read: hoff (the C51 layout; = off but for a dueling C51 net) from head_base(params[w]).
     // A dueling C51 net (FB_ARCH_C51_DUELING): heff[w] = [b_fc1 | W_eff | b_eff], the folded head of params[w] (c51d_fold_kernel)
@@ -3972,6 +4020,7 @@ static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, floa
 static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out, float sigma0) {
     fb_qnet *h = new fb_qnet();
     memset(h, 0, sizeof(*h));
+    h->md = MdPar{0.03f, 0.9f, -1.f};            // Munchausen-DQN, the paper's values (read by FB_ALGO_MDQN / _PER on a scalar net alone)
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
     h->off = is_c51d(h) ? make_off_c51d(fc_width, n_actions, sup.N)
                         : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
@@ -4453,7 +4502,10 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         // apply needs no launch of its own for it
         // (at most one tick per Adam update: guarded on the device by AdamDev::ticks / applies)
         L.adam = h->adam; L.tick = p.tick;
-        hipLaunchKernelGGL(loss_head_kernel, dim3(FC / 16), dim3(256), 0, c.st, L);
+        if (is_mdqn_algo(p.algo)) {                  // (L.algo: the loss's form alone)
+            L.algo = p.algo == FB_ALGO_MDQN_PER ? FB_ALGO_PER : FB_ALGO_NATURE;
+            hipLaunchKernelGGL(loss_head_md_kernel, dim3(FC / 16), dim3(256), 0, c.st, L, h->md);
+        } else hipLaunchKernelGGL(loss_head_kernel, dim3(FC / 16), dim3(256), 0, c.st, L);
         return;
     }
     const bool pw = is_per_algo(p.algo);         // (prioritized: weighted loss; the priorities are KL (C51) / l_b (QR))
@@ -4495,7 +4547,11 @@ static void fc1_backward(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         L.grad = p.G; L.dh3 = h->dh3; L.loss = p.loss; L.abs_err = p.abs_err; L.y_out = p.y;
         L.adam = h->adam; L.tick = p.tick; L.rb = h->nsplit_train == 1;       // bf16 training: operands rounded to bf16
         L.gate = p.split && c.only < 0 ? FbGate{&p.split->f->trunk_done, p.split->seq, &p.split->f->timeouts[2]} : FbGate{nullptr, 0, nullptr};
-        hipLaunchKernelGGL(fc1_bwd2_kernel, dim3(ndx1 + (FC / 32) * 7 + (L.gate.flag ? 1 : 0)), dim3(512), 0, c.st, L);
+        const dim3 grid(ndx1 + (FC / 32) * 7 + (L.gate.flag ? 1 : 0));
+        if (is_mdqn_algo(p.algo)) {                  // (L.algo: the loss's form alone)
+            L.algo = p.algo == FB_ALGO_MDQN_PER ? FB_ALGO_PER : FB_ALGO_NATURE;
+            hipLaunchKernelGGL(fc1_bwd2_md_kernel, grid, dim3(512), 0, c.st, L, h->md);
+        } else hipLaunchKernelGGL(fc1_bwd2_kernel, grid, dim3(512), 0, c.st, L);
         return;
     }
     const int ndx = ((B + 31) / 32) * 50, ntile = ndx + 50 * (FC / 32);        // one workgroup per 32 x 32 tile, data-gradient tiles first
@@ -4769,6 +4825,25 @@ extern "C" int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_
     return FB_OK;
 }
 
+extern "C" int fb_qnet_set_munchausen(fb_qnet_t h, float tau, float alpha, float clip_lo) {
+    FB_REQUIRE(h, "fb_qnet_set_munchausen: NULL handle");
+    FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
+    FB_REQUIRE(isfinite(tau) && tau > 0.f, "fb_qnet_set_munchausen: tau must be finite and > 0 (got %g)", (double)tau);
+    FB_REQUIRE(alpha >= 0.f && alpha <= 1.f, "fb_qnet_set_munchausen: alpha must be in [0, 1] (got %g)", (double)alpha);
+    FB_REQUIRE(isfinite(clip_lo) && clip_lo <= 0.f, "fb_qnet_set_munchausen: the clip l0 must be finite and <= 0 (got %g)", (double)clip_lo);
+    h->md = MdPar{tau, alpha, clip_lo};
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha_host, float *clip_lo_host) {
+    FB_REQUIRE(h, "fb_qnet_get_munchausen: NULL handle");
+    FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
+    if (tau_host) *tau_host = h->md.tau;
+    if (alpha_host) *alpha_host = h->md.alpha;
+    if (clip_lo_host) *clip_lo_host = h->md.clip;
+    return FB_OK;
+}
+
 extern "C" int fb_qnet_get_quantiles(fb_qnet_t h, int *n_quantiles_host, float *kappa_host) {
     FB_REQUIRE(h && n_quantiles_host && kappa_host, "fb_qnet_get_quantiles: NULL argument");
     *n_quantiles_host = is_qr(h) ? h->sup.N : 0; *kappa_host = is_qr(h) ? h->kappa : 0.f;
@@ -4909,7 +4984,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
                       const uint8_t *t, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
     FB_REQUIRE(h && a && r && t && loss && (ring || (s && s2)), "fb_qnet_train_step: NULL argument");
-    FB_REQUIRE(algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
+    FB_REQUIRE((algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER) || is_mdqn_algo(algo), "fb_qnet_train_step: unknown algo %d", algo);
     {
         const bool c51a = is_c51_algo(algo), qra = is_qr_algo(algo);
         FB_REQUIRE(c51a == (h->sup.N > 0 && !is_qr(h)), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
@@ -4928,7 +5003,8 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
     if (algo == FB_ALGO_DQN || algo == FB_ALGO_PG) p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};               // BrainDQN.py:205 (same net); PG: s2 is forwarded and ignored
     else if (algo == FB_ALGO_DOUBLE || is_double_c51(algo) || is_double_qr(algo)) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
-    else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net (Nature, PER, C51, C51_PER)
+    else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net (Nature, PER, C51, C51_PER, Munchausen)
+    if (is_mdqn_algo(algo)) { p.sl.s[2] = Slice{h->params[1], s, 2 * B, B, h->w1s[1], 0}; p.ns = 3; }     // Munchausen: s through the target net as well (the log-policy bonus)
     p.sl.rb = h->nsplit_train == 1;
     p.train = true; p.algo = algo; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.isw = isw; p.gamma = gamma;
     p.loss = loss; p.abs_err = abs_err; p.y = q_target;

@@ -278,13 +278,18 @@ class VecReplay:
 
 ALGOS = {"dqn": L.ALGO_DQN, "nature": L.ALGO_NATURE, "double": L.ALGO_DOUBLE, "per": L.ALGO_PER, "pg": L.ALGO_PG,
          "c51": L.ALGO_C51, "c51double": L.ALGO_C51_DOUBLE, "c51per": L.ALGO_C51_PER, "c51doubleper": L.ALGO_C51_DOUBLE_PER,
-         "qr": L.ALGO_QR, "qrdouble": L.ALGO_QR_DOUBLE, "qrper": L.ALGO_QR_PER, "qrdoubleper": L.ALGO_QR_DOUBLE_PER}
+         "qr": L.ALGO_QR, "qrdouble": L.ALGO_QR_DOUBLE, "qrper": L.ALGO_QR_PER, "qrdoubleper": L.ALGO_QR_DOUBLE_PER,
+         "mdqn": L.ALGO_MDQN, "mdqnper": L.ALGO_MDQN_PER}
 C51_ALGOS = ("c51", "c51double")                            # C51 on a uniform memory
 C51_PER_ALGOS = ("c51per", "c51doubleper")                  # C51 on a prioritized memory (weighted loss, KL priorities)
 QR_ALGOS = ("qr", "qrdouble")                               # QR-DQN on a uniform memory
 QR_PER_ALGOS = ("qrper", "qrdoubleper")                     # QR-DQN on a prioritized memory (weighted loss, l_b priorities)
 PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the scalar and C51 algos that take a prioritized memory
-PRIORITIZED_ALGOS = PER_ALGOS + QR_PER_ALGOS                # every algo that takes a prioritized memory and its importance weights
+PRIORITIZED_ALGOS = PER_ALGOS + QR_PER_ALGOS                # the algos of before Munchausen-DQN that take a prioritized memory
+MDQN_ALGOS = ("mdqn",)                                      # Munchausen-DQN on a uniform memory (scalar heads; include/fbdqn.h)
+MDQN_PER_ALGOS = ("mdqnper",)                               # Munchausen-DQN on a prioritized memory (FB_ALGO_PER's weights and |TD errors|)
+WEIGHTED_ALGOS = PRIORITIZED_ALGOS + MDQN_PER_ALGOS         # every algo that takes a prioritized memory and its importance weights
+MDQN_DEFAULTS = L.MDQN_DEFAULTS                             # (tau, alpha, l0) of a new scalar net
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
 C51_ARCHS = ("c51", "c51dueling")                         # distributional heads: C51, and the dueling C51 head (Rainbow's)
 QR_ARCHS = ("qr", "qrdueling")                            # quantile heads: QR-DQN, and its dueling form
@@ -331,6 +336,18 @@ def check_quantiles(n_quantiles, kappa, actions=2):
     if not (np.isfinite(k) and k > 0.0):
         raise ValueError(f"kappa must be finite and > 0, got {kappa}")
     return n, k
+
+
+def check_munchausen(tau, alpha, clip):
+    """the argument checks of fb_qnet_set_munchausen, on the host (-> (tau, alpha, l0) as float32-rounded floats)"""
+    t, a, c = (float(np.float32(x)) for x in (tau, alpha, clip))
+    if not (np.isfinite(t) and t > 0.0):
+        raise ValueError(f"tau must be finite and > 0, got {tau}")
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1], got {alpha}")
+    if not (np.isfinite(c) and c <= 0.0):
+        raise ValueError(f"clip (l0) must be finite and <= 0, got {clip}")
+    return t, a, c
 
 
 def bootstrap_gamma(gamma, n):
@@ -478,6 +495,18 @@ class QNet:
 
     def sync_target(self):
         L.check(L.lib().fb_qnet_sync_target(self.h, L.current_stream()), "fb_qnet_sync_target")
+
+    # -- Munchausen-DQN (scalar heads) -----------------------------------------------
+    def set_munchausen(self, tau=MDQN_DEFAULTS[0], alpha=MDQN_DEFAULTS[1], clip=MDQN_DEFAULTS[2]):
+        """(tau, alpha, l0) of algos 'mdqn' / 'mdqnper' (fb_qnet_set_munchausen): the softmax temperature, the bonus's scale and its
+        lower clip; refused on a C51 / QR net and for values outside their ranges, before anything changes"""
+        L.check(L.lib().fb_qnet_set_munchausen(self.h, float(tau), float(alpha), float(clip)), "fb_qnet_set_munchausen")
+
+    def munchausen(self):
+        """the net's current (tau, alpha, l0) (fb_qnet_get_munchausen)"""
+        t, a, c = C.c_float(), C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_get_munchausen(self.h, C.byref(t), C.byref(a), C.byref(c)), "fb_qnet_get_munchausen")
+        return t.value, a.value, c.value
 
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):
@@ -642,7 +671,7 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
     SumTree leaf indices of replay.sample, isw its importance weights; want_abs_err returns |TD error| for update_priorities.
     An n-step memory (replay.set_n_step) is read as (s, a, R, s', done) and bootstrapped with gamma^n; gamma must be the memory's.
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, abs_err f32[B]]) on the device."""
-    if (replay.prioritized or algo in PRIORITIZED_ALGOS) and isw is None:
+    if (replay.prioritized or algo in WEIGHTED_ALGOS) and isw is None:
         raise ValueError("the prioritized step needs the importance weights (isw)")
     _dev_check(idx, flat_grad, isw)
     B, dev = int(idx.numel()), idx.device
@@ -663,7 +692,7 @@ class TrainSteps:
     n-step memory gamma must be the memory's (the steps bootstrap with gamma^n)."""
 
     def __init__(self, replay, net, batch=32, algo="dqn", gamma=0.99):
-        if replay.prioritized or algo in PRIORITIZED_ALGOS:
+        if replay.prioritized or algo in WEIGHTED_ALGOS:
             raise ValueError("TrainSteps is for uniform replay (PER needs the importance weights: use the separate calls)")
         self.replay, self.net, self.batch, self.algo, self.gamma = replay, net, batch, ALGOS[algo], float(gamma)
         dev, B = replay.device, batch
@@ -701,8 +730,8 @@ class VecStep:
             raise ValueError(f"algo {algo!r} trains from a uniform memory only (QR with prioritized replay is 'qrper' / 'qrdoubleper')")
         if algo in QR_ALGOS + QR_PER_ALGOS and dist is not None:
             raise ValueError(f"algo {algo!r}: data-parallel QR is not supported (one GPU only)")
-        if replay.prioritized != (algo in PRIORITIZED_ALGOS):
-            raise ValueError(f"algos {PRIORITIZED_ALGOS} go with a prioritized memory, every other algo with a uniform one (algo {algo!r})")
+        if replay.prioritized != (algo in WEIGHTED_ALGOS):
+            raise ValueError(f"algos {WEIGHTED_ALGOS} go with a prioritized memory, every other algo with a uniform one (algo {algo!r})")
         if dist is not None and flat_grad is None:
             raise ValueError("VecStep(dist=...) needs the flat_grad buffer the gradient is reduced in")
         self.dist, self.mean_loss = dist, int(bool(mean_loss))
@@ -720,7 +749,7 @@ class VecStep:
         self.r = torch.empty(B, dtype=torch.float32, device=dev)
         self.t = torch.empty(B, dtype=torch.uint8, device=dev)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        per = algo in PRIORITIZED_ALGOS                    # Memory.sample's weights (f64, and as the float32 placeholder takes them), |TD errors|
+        per = algo in WEIGHTED_ALGOS                       # Memory.sample's weights (f64, and as the float32 placeholder takes them), |TD errors|
         self.isw = torch.zeros(B, dtype=torch.float64, device=dev) if per else None
         self.isw32 = torch.zeros(B, dtype=torch.float32, device=dev) if per else None
         self.abs_err = torch.zeros(B, dtype=torch.float32, device=dev) if per else None

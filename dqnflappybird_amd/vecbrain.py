@@ -11,18 +11,21 @@ replay ('c51per' / 'c51doubleper') sync every replace_target_iter steps.  arch='
 C51 head (Rainbow's, with 'c51doubleper' and n-step returns: FlappyBirdDQN.py --model rainbow).  noisy=True gives a C51 algo's net
 noisy fc1 and head layers (NoisyNet; with arch='c51dueling', 'c51doubleper' and n-step returns: full Rainbow, --model rainbow --noisy):
 fb_vec_step draws the nets' noise every step, and the epsilon schedule defaults to 0.  QR-DQN ('qr', 'qrdouble', 'qrper',
-'qrdoubleper') trains a quantile head (arch 'qr', or 'qrdueling' for its dueling form) on one GPU and syncs as C51 does.
+'qrdoubleper') trains a quantile head (arch 'qr', or 'qrdueling' for its dueling form) on one GPU and syncs as C51 does.  Munchausen-DQN ('mdqn',
+'mdqnper' with prioritized replay) trains the scalar heads ('plain' or 'dueling') with a soft bootstrap and a clipped log-policy bonus
+(tau, alpha, clip; include/fbdqn.h), syncs its target net every replace_target_iter steps and runs data parallel as 'double' / 'per' do.
 """
 from . import dist as fdist
 
 MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True, "c51per": True, "c51doubleper": True,
-             "qr": True, "qrdouble": True, "qrper": True, "qrdoubleper": True}
+             "qr": True, "qrdouble": True, "qrper": True, "qrdoubleper": True, "mdqn": True, "mdqnper": True}
 C51_ALGOS = ("c51", "c51double")                             # distributional Q-learning (include/fbdqn.h, DESIGN.md section 11)
 C51_PER_ALGOS = ("c51per", "c51doubleper")                   # ... with prioritized replay: weighted loss, KL priorities
 QR_ALGOS = ("qr", "qrdouble")                                # quantile regression (QR-DQN; include/fbdqn.h, DESIGN.md section 12)
 QR_PER_ALGOS = ("qrper", "qrdoubleper")                      # ... with prioritized replay: weighted loss, l_b priorities
-PER_ALGOS = ("per",) + C51_PER_ALGOS + QR_PER_ALGOS          # algos with a prioritized memory
-TARGET_SYNC = ("nature", "double") + C51_ALGOS + C51_PER_ALGOS + QR_ALGOS + QR_PER_ALGOS   # algos whose target net is synced every replace_target_iter steps
+MDQN_ALGOS = ("mdqn", "mdqnper")                             # Munchausen-DQN on the scalar heads (include/fbdqn.h, DESIGN.md section 13)
+PER_ALGOS = ("per",) + C51_PER_ALGOS + QR_PER_ALGOS + ("mdqnper",)      # algos with a prioritized memory
+TARGET_SYNC = ("nature", "double") + C51_ALGOS + C51_PER_ALGOS + QR_ALGOS + QR_PER_ALGOS + MDQN_ALGOS   # algos whose target net is synced every replace_target_iter steps
 C51_HEADS = ("c51", "c51dueling")                            # the heads a C51 algo trains (arch; 'plain' means 'c51')
 QR_HEADS = ("qr", "qrdueling")                               # the heads a QR algo trains (arch; 'plain' means 'qr')
 
@@ -49,6 +52,7 @@ class HipVecBackend:
     c51_noisy = True                                         # ... and noisy C51 nets (net(..., support=..., noisy=True, sigma0=s))
     acting_noise_env = True                                  # ... which can act with noise per env (net.set_acting_noise('env'))
     qr = True                                                # quantile nets (net(..., arch='qr' | 'qrdueling', quantiles=(n_quantiles, kappa)))
+    mdqn = True                                              # Munchausen-DQN: algos 'mdqn' / 'mdqnper' in step(), net.set_munchausen(tau, alpha, clip)
 
     def net(self, actions, fc_width, arch, max_batch, support=None, noisy=False, sigma0=0.5, quantiles=None):
         from .vec import QNet
@@ -141,6 +145,17 @@ def check_checkpoint_quantiles(z, quantiles, head, path):
                          f"({int(quantiles[0])}, {float(quantiles[1])})")
 
 
+def check_checkpoint_munchausen(z, munchausen, path):
+    """a Munchausen-DQN brain takes a checkpoint trained with its own (tau, alpha, l0), or one that records none (any scalar-head
+    checkpoint: the parameters are the same net's); a brain of another algo does not read the key"""
+    if munchausen is None or "munchausen" not in z.files:
+        return
+    saved = tuple(float(x) for x in z["munchausen"].tolist())
+    if saved != tuple(float(x) for x in munchausen):
+        raise ValueError(f"checkpoint {path} was trained with munchausen (tau, alpha, clip) = {saved}, this VecBrain has "
+                         f"{tuple(float(x) for x in munchausen)}")
+
+
 def check_checkpoint_noisy(z, noisy, sigma0, path):
     """a checkpoint's net must be noisy exactly when this brain's is (checkpoints that record nothing hold a non-noisy net)"""
     saved = bool(z["noisy"][0]) if "noisy" in z.files else False
@@ -165,7 +180,7 @@ class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0,
-                 noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0):
+                 noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0, tau=0.03, alpha=0.9, clip=-1.0):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
@@ -176,7 +191,10 @@ class VecBrain:
         acting_noise (noisy nets): 'shared' -- one noise sample per step for all envs -- or 'env': independent noise per env when acting
         (include/fbdqn.h); training is the same in both, and checkpoints do not record it.
         algo 'qr' / 'qrdouble' / 'qrper' / 'qrdoubleper': QR-DQN with n_quantiles quantiles and the quantile Huber loss's kappa (one GPU,
-        any n_step; the PER forms on a prioritized memory), on arch 'qr' ('plain' means it) or 'qrdueling'; no noisy QR nets."""
+        any n_step; the PER forms on a prioritized memory), on arch 'qr' ('plain' means it) or 'qrdueling'; no noisy QR nets.
+        algo 'mdqn' / 'mdqnper': Munchausen-DQN on arch 'plain' or 'dueling' -- the target is a soft (log-sum-exp, temperature tau)
+        bootstrap plus alpha x the log-policy of the taken action, clipped below at clip (include/fbdqn.h); 'mdqnper' on a prioritized
+        memory; any n_step (only the first step's bonus is added), world > 1 as 'double' / 'per'; tau / alpha / clip are ignored otherwise."""
         n_step = int(n_step)
         noisy = bool(noisy)
         if acting_noise not in ("shared", "env"):
@@ -193,7 +211,20 @@ class VecBrain:
                              f"acting_noise='env' needs it")
         self.support = None
         self.quantiles = None
-        if algo in QR_ALGOS + QR_PER_ALGOS:
+        self.munchausen = None
+        if algo in MDQN_ALGOS:
+            from .vec import check_munchausen
+            self.munchausen = check_munchausen(tau, alpha, clip)
+            if arch not in ("plain", "dueling"):
+                raise ValueError(f"algo {algo!r} (Munchausen-DQN) trains the scalar heads: arch must be 'plain' or 'dueling', not {arch!r}")
+            if noisy:
+                raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with the Munchausen-DQN algo {algo!r}")
+            if not getattr(be, "mdqn", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no Munchausen-DQN (mdqn): algo {algo!r} needs it")
+            if algo == "mdqnper" and not getattr(be, "per_one_step", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
+                                 f"algo {algo!r} needs it")
+        elif algo in QR_ALGOS + QR_PER_ALGOS:
             from .vec import check_quantiles
             if arch not in ("plain",) + QR_HEADS:
                 raise ValueError(f"algo {algo!r} builds a QR head on the plain trunk: arch {arch!r} is not one (dueling QR is arch='qrdueling')")
@@ -272,6 +303,8 @@ class VecBrain:
             self.net = be.net(2, fc_width, arch, max(n_envs, batch), quantiles=self.quantiles)
         else:
             self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support) if self.support else be.net(2, fc_width, arch, max(n_envs, batch))
+        if self.munchausen:
+            self.net.set_munchausen(*self.munchausen)
         self.acting_noise = acting_noise
         if acting_noise == "env":
             self.net.set_acting_noise("env")                 # (fb_vec_step reads it: act with per-env noise, draw the online sample after)
@@ -414,6 +447,8 @@ class VecBrain:
             if self.quantiles is not None:                   # QR: the head ('qr' / 'qrdueling') and (N, kappa)
                 shared["head"] = np.array([self.arch])
                 shared["quantiles"] = np.array(self.quantiles, np.float64)
+            if self.munchausen is not None:                  # Munchausen-DQN: (tau, alpha, l0) the nets were trained with
+                shared["munchausen"] = np.array(self.munchausen, np.float64)
             if self.noisy:                                   # online / target / Adam hold [mu | sigma] (checkpoints without it: not noisy)
                 shared["noisy"] = np.array([1], np.int64)
                 shared["sigma0"] = np.array([self.sigma0], np.float64)
@@ -441,6 +476,7 @@ class VecBrain:
         if self.support is not None:
             check_checkpoint_head(z, self.arch, path)
         check_checkpoint_noisy(z, self.noisy, self.sigma0, path)
+        check_checkpoint_munchausen(z, self.munchausen, path)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         self.net.load_params(z["online"], 0)

@@ -444,6 +444,38 @@ int fb_qnet_create_qr(int arch, int fc_width, int n_actions, int n_quantiles, fl
 int fb_qnet_get_quantiles(fb_qnet_t h, int *n_quantiles_host, float *kappa_host);
 int fb_qnet_forward_quantiles(fb_qnet_t h, int which, const uint8_t *states, int batch, float *theta, void *stream);
 
+/* ------------------------------------------------------------------ Munchausen-DQN (Vieillard, Pietquin & Geist, NeurIPS 2020)
+ * Two algos on the SCALAR heads (FB_ARCH_PLAIN and FB_ARCH_DUELING; the dueling combine happens before anything below): the Q head, the
+ * squared TD loss, epsilon-greedy acting and evaluation are FB_ALGO_NATURE's; only the target differs.  With the net's parameters
+ * (tau, alpha, l0) and, for a vector x with m = max_c x_c,  lse_tau(x) = m + tau log sum_c exp((x_c - m) / tau):
+ *   forward     q(s, .) from the online net; q-(s, .) and q-(s', .) from the TARGET net: three slices, s online, s' target, s target
+ *   bonus       alpha max(tau ln pi-(a|s), l0),  tau ln pi-(a|s) = (q-(s, a) - m) - tau log sum_c exp((q-(s, c) - m) / tau)  (<= 0), m = max q-(s, .)
+ *   V           lse_tau(q-(s', .))  (= sum_c pi-(c|s') (q-(s', c) - tau ln pi-(c|s')), pi- = softmax(q- / tau))
+ *   target      y = (R + bonus) + (done ? 0 : Gamma V): bonus and V in fp32 (expf / logf), R and the sums in float64 as the other scalar
+ *               algos form theirs (R = 0.1f reads as 0.1), rounded to float once.  The bonus is added on terminal transitions too.
+ *               Gamma = gamma^n as DESIGN.md section 10 forms it; on an n-step memory R is the n-step return and ONLY THE FIRST step's
+ *               bonus (that of (s, a)) is added -- the memory stores no state between s and s' to form the others from
+ *   loss        mean_b w_b (y_b - q(s_b, a_b))^2, the gradient through q(s, a) only: exactly FB_ALGO_NATURE's (FB_ALGO_MDQN, w = 1) or
+ *               FB_ALGO_PER's (FB_ALGO_MDQN_PER, w = isw) with this y; abs_err = |y - q(s, a)|, q_target = y
+ *   A = 1       lse_tau(x) = x + tau log(1) = x and the bonus is alpha max(0 - tau log(1), l0) = 0: FB_ALGO_MDQN on a one-action net gives
+ *               FB_ALGO_NATURE's loss, y and gradient bit for bit
+ *   worked      tau 0.03, alpha 0.9, l0 -1: q-(s) = (c, c) -> bonus -alpha tau ln 2 = -0.018715...; q-(s) = (0, 2) -> -0.9 for a = 0
+ *               (clipped), -0 for a = 1
+ * FB_ALGO_MDQN takes a uniform memory, FB_ALGO_MDQN_PER a prioritized one and isw, as FB_ALGO_PER does.  FB_ALGO_MDQN is accepted
+ * wherever FB_ALGO_DOUBLE is (fb_qnet_train_step, fb_train_from_replay, fb_train_steps, fb_vec_step on the schedule FB_ALGO_DOUBLE takes
+ * at that shape, flat_grad, fb_vec_step_dp, FB_DTYPE_BF16 training), FB_ALGO_MDQN_PER wherever FB_ALGO_PER is.  FB_ERR_INVALID before any
+ * launch or counter change: these algos on a C51 / QR / noisy net (and a C51 / QR algo on a scalar net, as before), a prioritized memory
+ * for FB_ALGO_MDQN, a uniform memory or no isw for FB_ALGO_MDQN_PER.  The target net syncs as for FB_ALGO_NATURE (the caller's call).
+ * fb_qnet_set_munchausen: the net's (tau, alpha, l0); a new scalar net holds (0.03, 0.9, -1), the paper's.  FB_ERR_INVALID before
+ *   anything changes: tau not finite or <= 0, alpha outside [0, 1], l0 not finite or > 0, a C51 / QR net.  A host-side setting read by
+ *   the calls issued after it (a hipGraph captured earlier keeps the values it was captured with).
+ * fb_qnet_get_munchausen: the current values [host] (any of the pointers may be NULL); FB_ERR_INVALID on a C51 / QR net. */
+/* (13 is no algo and stays refused as unknown by every entry point: callers and tests have used it as the first number past the QR algos) */
+#define FB_ALGO_MDQN 14
+#define FB_ALGO_MDQN_PER 15
+int fb_qnet_set_munchausen(fb_qnet_t h, float tau, float alpha, float clip_lo);
+int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha_host, float *clip_lo_host);
+
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
 int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host);
