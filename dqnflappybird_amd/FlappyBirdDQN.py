@@ -18,6 +18,9 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
     python -m dqnflappybird_amd.FlappyBirdDQN --model mdqn --vec 1024 [--tau 0.03 --alpha 0.9 --clip -1] [--n-step K]
                                                                                       (Munchausen-DQN on the scalar head: soft bootstrap +
                                                                                        clipped log-policy bonus; mdqnper: prioritized replay)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model doubleper --vec 1024 [--n-step K] [--huber 1]
+                                                                                      (Double-DQN's target with prioritized replay on the scalar
+                                                                                       head; --huber D: the Huber loss on any scalar-head model)
     python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy --acting-noise env
                                                                                       (... acting with independent noise per env)
 
@@ -93,9 +96,27 @@ def main():
     parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper: the softmax temperature (default 0.03)")
     parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9)")
     parser.add_argument("--clip", type=float, default=None, help="--model mdqn | mdqnper: the bonus's lower clip l0 (default -1)")
+    parser.add_argument("--huber", type=float, default=None, help="scalar-head models with --vec: the Huber loss's delta (default 0 = the squared loss)")
     args = parser.parse_args()
     qr_models = ("qrdqn", "qrdqnper", "qrrainbow")
     md_models = ("mdqn", "mdqnper")
+    scalar_models = ("dqn", "ddqn", "dqnnature", "duelingdqn", "prioritydqn", "doubleper") + md_models
+    if args.model == "doubleper":                        # (refused before anything touches the GPU)
+        if not args.vec:
+            parser.error("--model doubleper needs --vec: Double-DQN with prioritized replay runs in the vectorised loop only")
+        if args.noisy:
+            parser.error(f"--noisy needs a C51 model (c51, c51per, c51doubleper, rainbow), not --model {args.model}")
+    hkw = {}
+    if args.huber is not None:                           # (refused before anything touches the GPU)
+        if not args.vec:
+            parser.error("--huber needs --vec: the single-env agents are the reference's, with its squared loss")
+        if args.model not in scalar_models:
+            parser.error(f"--huber needs a scalar-head model ({', '.join(scalar_models)}), not --model {args.model}")
+        from .vec import check_huber
+        try:
+            hkw = dict(huber=check_huber(args.huber))
+        except ValueError as e:
+            parser.error(str(e))
     if args.model in md_models:                          # (refused before anything touches the GPU)
         if not args.vec:
             parser.error(f"--model {args.model} needs --vec: Munchausen-DQN runs in the vectorised loop only")
@@ -148,7 +169,7 @@ def main():
             raise SystemExit("--vec runs the DQN family; the actor-critic / policy-gradient agents are single-env (as in the reference)")
         algo = {"dqn": "dqn", "ddqn": "nature", "dqnnature": "nature", "duelingdqn": "nature", "prioritydqn": "per", "c51": "c51",
                 "c51per": "c51per", "c51doubleper": "c51doubleper", "rainbow": "c51doubleper", "qrdqn": "qr", "qrdqnper": "qrper",
-                "qrrainbow": "qrdoubleper", "mdqn": "mdqn", "mdqnper": "mdqnper"}[args.model]
+                "qrrainbow": "qrdoubleper", "mdqn": "mdqn", "mdqnper": "mdqnper", "doubleper": "doubleper"}[args.model]
         arch = "c51dueling" if args.model == "rainbow" else "plain"      # rainbow: dueling C51 head, double target, prioritized replay
         qkw = {}
         if args.model in qr_models:                      # qrrainbow: dueling QR head, double target, prioritized replay
@@ -157,7 +178,7 @@ def main():
         if args.model in md_models:
             qkw = mkw
         vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step, noisy=args.noisy,
-                      acting_noise=args.acting_noise, **qkw)
+                      acting_noise=args.acting_noise, **qkw, **hkw)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)
     else:
         playFlappyBird(args.model, args.steps, verbose=not args.quiet)

@@ -24,6 +24,7 @@ ARCH_QR, ARCH_QR_DUELING = 4, 5                       # quantile-regression head
 ALGO_QR, ALGO_QR_DOUBLE, ALGO_QR_PER, ALGO_QR_DOUBLE_PER = 9, 10, 11, 12
 ALGO_MDQN, ALGO_MDQN_PER = 14, 15                     # Munchausen-DQN on the scalar heads (include/fbdqn.h)
 MDQN_DEFAULTS = (0.03, 0.9, -1.0)                     # (tau, alpha, l0) of a new scalar net: the paper's
+ALGO_DOUBLE_PER = 16                                  # Double-DQN's target on a prioritized memory (include/fbdqn.h)
 NOISE_SAMPLE, NOISE_MEAN = 0, 1                       # include/fbdqn.h FB_NOISE_* (fb_qnet_reset_noise)
 ACT_NOISE_SHARED, ACT_NOISE_PER_ENV = 0, 1            # include/fbdqn.h FB_ACT_NOISE_* (fb_qnet_set_acting_noise)
 DTYPE_F32, DTYPE_BF16 = 0, 1
@@ -89,6 +90,8 @@ SIGNATURES = {
     "fb_qnet_forward_quantiles": [_vp, _i, _vp, _i, _vp, _vp],
     "fb_qnet_set_munchausen": [_vp, _f, _f, _f],
     "fb_qnet_get_munchausen": [_vp, _vp, _vp, _vp],
+    "fb_qnet_set_huber": [_vp, _f],
+    "fb_qnet_get_huber": [_vp, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],

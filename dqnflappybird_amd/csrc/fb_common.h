@@ -39,10 +39,10 @@ static inline bool is_qr_algo(int algo) {           // trains a QR net
 static inline bool is_double_qr(int algo) { return algo == FB_ALGO_QR_DOUBLE || algo == FB_ALGO_QR_DOUBLE_PER; }       // a* online
 static inline bool is_per_algo(int algo) {          // prioritized memory, importance weights, |TD error| / priority out
     return algo == FB_ALGO_PER || algo == FB_ALGO_C51_PER || algo == FB_ALGO_C51_DOUBLE_PER || algo == FB_ALGO_QR_PER ||
-           algo == FB_ALGO_QR_DOUBLE_PER || algo == FB_ALGO_MDQN_PER;
+           algo == FB_ALGO_QR_DOUBLE_PER || algo == FB_ALGO_MDQN_PER || algo == FB_ALGO_DOUBLE_PER;
 }
 static inline bool is_mdqn_algo(int algo) { return algo == FB_ALGO_MDQN || algo == FB_ALGO_MDQN_PER; }      // Munchausen target, a scalar net
-static inline bool is_scalar_algo(int algo) { return (algo >= FB_ALGO_DQN && algo <= FB_ALGO_PER) || is_mdqn_algo(algo); }      // the scalar-head algos the ring-fed calls take
+static inline bool is_scalar_algo(int algo) { return (algo >= FB_ALGO_DQN && algo <= FB_ALGO_PER) || is_mdqn_algo(algo) || algo == FB_ALGO_DOUBLE_PER; }      // the scalar-head algos the ring-fed calls take
 
 // Hand-offs between kernels of two streams through device words (fb_vec_step's split schedule).  A word only ever grows (the step
 // number).  Stores and polls are relaxed agent-scope atomics (they go to the coherent level, past the XCD's own L2); a reader that goes
@@ -204,6 +204,10 @@ int fb_qnet_is_c51(fb_qnet_t h);              // 1: a C51 net (fb_qnet_create_c5
 int fb_qnet_is_qr(fb_qnet_t h);               // 1: a QR net (fb_qnet_create_qr)
 // 1: a distributional head (C51 or QR): the head is its own launch (no env rider, the one-stream order of fb_vec_step)
 int fb_qnet_is_dist(fb_qnet_t h);
+// the extended scalar loss kernels (FB_ALGO_DOUBLE_PER / Huber), instantiated in fb_qnet_x.hip: a code object of their own (see fb_qnet.hip).
+// largs / mdpar: fb_qnet.hip's LossArgs (Bw1Args) and MdPar, as bytes
+void fb_qnet_launch_loss_head_x(int dp, int hu, int md, unsigned grid, hipStream_t st, const void *largs, const void *mdpar, float delta);
+void fb_qnet_launch_fc1_bwd2_x(int dp, int hu, int md, unsigned grid, hipStream_t st, const void *largs, const void *mdpar, float delta);
 // fb_eval_run on a distributional (C51 or QR) net: launch the head fb_qnet_eval_trunk described in *hd (q / actions / epsilon / seeds filled in by the caller),
 // epsilon draws keyed key_of[row] on FB_STREAM_EVAL; the eval step launch then reads the actions (its head rider stays off)
 int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32_t *key_of, void *stream);

@@ -116,6 +116,15 @@ static int mdqn_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *w
     return FB_OK;
 }
 
+// FB_ALGO_DOUBLE_PER (include/fbdqn.h): a scalar net and a prioritized memory, as FB_ALGO_PER.  Checked by the ring-fed calls before any
+// counter moves or any launch, as the checks beside it
+static int dper_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *who) {
+    if (algo != FB_ALGO_DOUBLE_PER) return FB_OK;
+    FB_REQUIRE(!fb_qnet_is_dist(net), "%s: algo %d (FB_ALGO_DOUBLE_PER) trains a scalar net (FB_ARCH_PLAIN / FB_ARCH_DUELING) only, not a C51 / QR / noisy net", who, algo);
+    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: FB_ALGO_DOUBLE_PER trains from a prioritized memory only (FB_ALGO_DOUBLE takes a uniform one)", who);
+    return FB_OK;
+}
+
 // n x (random.sample -> minibatch -> _trainQNetwork) on a memory that is not being pushed to, as one host call.  Each step is the six
 // launches of the ring-fed train step (conv trunk of the 2B states straight from the 1-bit frame ring -> fc1 -> loss + fc1 backward ->
 // conv data gradients -> conv weight gradients -> Adam): no gather, no u8 minibatch.  Only the first draw gets a launch of its own: the
@@ -275,12 +284,12 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
                            int batch, float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
     FB_REQUIRE(env && replay && net && b, "fb_vec_step: NULL handle");
     FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "fb_vec_step: NULL env buffer");
-    const bool per = is_per_algo(algo);      // (FB_ALGO_PER, FB_ALGO_C51_PER, FB_ALGO_C51_DOUBLE_PER)
+    const bool per = is_per_algo(algo);      // (FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 / QR _PER algos)
     if (per && train) FB_REQUIRE(b->isw && b->isw32 && b->abs_err, "fb_vec_step: the prioritized step needs the isw / isw32 / abs_err buffers");
     // every argument check of the calls below happens HERE, before the replay's push counter moves or anything is launched: a
     // rejected step must leave the handles exactly as they were (a counted push without its env launch would make every later
     // gather address a ring slot that was never written)
-    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_MDQN_PER)", algo);
+    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER, FB_ALGO_MDQN .. FB_ALGO_DOUBLE_PER)", algo);
     // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
     // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
     // counter moves
@@ -295,6 +304,8 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
         if (rq != FB_OK) return rq;
         const int rm = mdqn_check(replay, net, algo, "fb_vec_step");
         if (rm != FB_OK) return rm;
+        const int rd = dper_check(replay, net, algo, "fb_vec_step");
+        if (rd != FB_OK) return rd;
     }
     FB_REQUIRE(per == (fb_replay_is_prioritized(replay) != 0), "fb_vec_step: algo %d and the memory's kind (uniform / prioritized) do not match", algo);
     FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_vec_step: n_envs %d does not match the env (%d) / replay (%d) handles",
@@ -465,7 +476,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
 extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo, int batch, const int64_t *idx, const float *isw, uint8_t *a,
                                     float *r, uint8_t *t, double gamma, float *loss, float *abs_err, float *flat_grad, void *stream) {
     FB_REQUIRE(replay && net && idx && a && r && t && loss, "fb_train_from_replay: NULL argument");
-    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_MDQN_PER)", algo);
+    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER, FB_ALGO_MDQN .. FB_ALGO_DOUBLE_PER)", algo);
     // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
     // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
     // counter moves
@@ -480,6 +491,8 @@ extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo,
         if (rq != FB_OK) return rq;
         const int rm = mdqn_check(replay, net, algo, "fb_train_from_replay");
         if (rm != FB_OK) return rm;
+        const int rd = dper_check(replay, net, algo, "fb_train_from_replay");
+        if (rd != FB_OK) return rd;
     }
     FB_REQUIRE(!is_per_algo(algo) || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
     if (is_c51_algo(algo) && is_per_algo(algo))

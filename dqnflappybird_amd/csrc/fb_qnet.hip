@@ -1326,6 +1326,21 @@ __device__ __forceinline__ void mdqn_target(const float (&qn)[NQ], const float (
     bonus = M.alpha * fmaxf((qa - m3) - M.tau * logf(s3), M.clip);
 }
 
+// The scalar loss's two later options (include/fbdqn.h), template parameters of the two loss bodies like MD:
+//   DP  FB_ALGO_DOUBLE_PER: Double's target (a* = the online net's first maximum over s', the value from the third slice: s' through the
+//       target net) whatever L.algo says, and L.algo = FB_ALGO_PER names the loss's form (weighted by isw, a mean)
+//   HU  the Huber (clipped-error) loss with the net's delta > 0: l(d) = d^2 inside |d| <= delta, delta (2 |d| - delta) outside; the
+//       gradient takes clamp(d, -delta, delta) where the squared loss takes d.  Inside the zone both are the squared loss's own
+//       expressions (w * d * d and -scale * w * d with the clamp returning d itself), so they agree with it bit for bit.
+// No load and no branch: selects on values the body holds already.
+template <bool HU>
+__device__ __forceinline__ float td_clamp(float d, float delta) { if constexpr (HU) return fminf(fmaxf(d, -delta), delta); else return d; }
+template <bool HU>
+__device__ __forceinline__ float td_term(float w, float d, float delta) {
+    const float sq = w * d * d;
+    if constexpr (HU) { const float ad = fabsf(d); return ad <= delta ? sq : w * (delta * (2.f * ad - delta)); } else return sq;
+}
+
 struct LossArgs {
     int algo, B, FC, A, dueling;
     NetOff off;
@@ -1348,8 +1363,9 @@ struct LossArgs {
 // B <= 32) are requested at the top, together with the Q values / rewards / actions of the target computation --
 // nothing is loaded behind the barrier, and no load sits under a branch (clamped addresses + selects; AT = the
 // number of actions at compile time, MAXA = read it from L.A).
-template <int AT, bool MD = false>
-__device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[MAXA], float *dv, float *lterm, float (*part)[16][MAXA + 2], float *wmax, const MdPar M = MdPar{}) {
+template <int AT, bool MD = false, bool DP = false, bool HU = false>
+__device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[MAXA], float *dv, float *lterm, float (*part)[16][MAXA + 2], float *wmax, const MdPar M = MdPar{},
+                                               const float delta = 0.f) {
     const int tid = threadIdx.x, B = L.B, A = AT == MAXA ? L.A : AT;
     const bool lead = blockIdx.x == 0;
     const float *P = L.params;
@@ -1367,7 +1383,7 @@ __device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[
         hv[u] = fc1_out(L.hf, L.stot, L.FC, b < B ? b : bg, jj, bias, L.nks);
     }
     const int tb = tid < B ? tid : 0;                            // threads past the batch recompute sample 0 and store nothing
-    const bool dbl = L.algo == FB_ALGO_DOUBLE;
+    const bool dbl = DP || L.algo == FB_ALGO_DOUBLE;
     float qsv[AT], qnv[AT], q3v[AT];
 #pragma unroll
     for (int a = 0; a < AT; a++) {
@@ -1416,9 +1432,9 @@ __device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[
         const float d = y - qe;                                  // q_eval = reduce_sum(Q * onehot)
         const float w = isw;
         const float scale = L.algo == FB_ALGO_DQN ? 2.f : 2.f / (float)B;     // sum vs mean
-        const float g = -scale * w * d;                          // dLoss/dQ[b][a_b]
+        const float g = -scale * w * td_clamp<HU>(d, delta);     // dLoss/dQ[b][a_b]
         if (tid < B) {
-            lterm[tid] = w * d * d;
+            lterm[tid] = td_term<HU>(w, d, delta);
             if (lead && L.abs_err) L.abs_err[tid] = fabsf(d);
             if (lead && L.y_out) L.y_out[tid] = y;
             if (L.dueling) {
@@ -1513,6 +1529,19 @@ __global__ __launch_bounds__(256) void loss_head_md_kernel(LossArgs L, MdPar M) 
     __shared__ float wmax[4];
     if (L.A == 2) loss_head_body<2, true>(L, dadv, dv, lterm, part, wmax, M);
     else loss_head_body<MAXA, true>(L, dadv, dv, lterm, part, wmax, M);
+}
+// ... with FB_ALGO_DOUBLE_PER's target (DP) and / or the Huber loss (HU), on either target: the options are compile-time flags of one
+// extended kernel, instantiated for the four combinations the host asks for (loss_stage), so that the two kernels above stay the code
+// they were and no net with delta = 0 pays for a clamp
+template <bool DP, bool HU, bool MD>
+__global__ __launch_bounds__(256) void loss_head_x_kernel(LossArgs L, MdPar M, float delta) {
+    __shared__ float dadv[MAXTB][MAXA];
+    __shared__ float dv[MAXTB];
+    __shared__ float lterm[MAXTB];
+    __shared__ float part[16][16][MAXA + 2];
+    __shared__ float wmax[4];
+    if (L.A == 2) loss_head_body<2, MD, DP, HU>(L, dadv, dv, lterm, part, wmax, M, delta);
+    else loss_head_body<MAXA, MD, DP, HU>(L, dadv, dv, lterm, part, wmax, M, delta);
 }
 
 // fb_qnet_apply_adam on gradients that no fb_qnet_train_step ticked for (guarded on the device, so it is safe to launch always)
@@ -2263,15 +2292,15 @@ constexpr int BW_DW_ROW = 36;                // dhf row stride in LDS (dW role)
 
 // DX: the role is a template argument and the kernel branches ONCE, at the top, into one of two straight-line bodies (a role branch
 // around the pre-loads would put a vmcnt(0) join between them and the prologue's own loads)
-template <int AT, bool DX, bool MD = false>
-__device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem, const MdPar M = MdPar{}) {
+template <int AT, bool DX, bool MD = false, bool DP = false, bool HU = false>
+__device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem, const MdPar M = MdPar{}, const float delta = 0.f) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, B = L.B, FC = L.FC, A = AT == MAXA ? L.A : AT;
     const float *P = L.params;
     float (*dadv)[MAXA] = reinterpret_cast<float (*)[MAXA]>(smem);                  // [MAXTB][MAXA]
     float *dv = smem + MAXTB * MAXA, *lterm = dv + MAXTB, *dadv2 = lterm + MAXTB, *big = dadv2 + 2 * MAXTB;     // big: role dependent
     // (dadv2: the two-action plain head's dA as packed pairs [b][2], 16-byte aligned per two rows)
     const bool lead = blockIdx.x == 0;
-    const bool dbl = L.algo == FB_ALGO_DOUBLE;
+    const bool dbl = DP || L.algo == FB_ALGO_DOUBLE;
     const bool row3 = MD || dbl;                 // a third slice at rows 2B ..: Double's s' through the target net, Munchausen's (MD) s through it
     const int qs = A + 1, ntile = FC >> 4;
     // ---- role of this workgroup, and EVERY global load its body needs, issued before the target computation: the fc1 sums, the
@@ -2412,7 +2441,7 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem, con
         for (int c = 1; c < AT; c++) qe = c == a_b ? qsv[c] : qe;
         const float d = y - qe;                                      // q_eval = reduce_sum(Q * onehot)
         const float scale = L.algo == FB_ALGO_DQN ? 2.f : 2.f / (float)B;     // sum vs mean
-        const float gq = -scale * isw * d;                           // dLoss/dQ[b][a_b]
+        const float gq = -scale * isw * td_clamp<HU>(d, delta);      // dLoss/dQ[b][a_b]
         // FB_ALGO_PG (BrainPolicyGradient.py:96-100; the actor of BrainActorCritic.py:96-100): Q(s) are LOGITS; loss = mean over
         // gamma (= the number of samples of the whole batch this chunk belongs to) of softmax_cross_entropy(logits, action) x weight,
         // the weight arriving where the rewards do.  dLoss/dlogit[c] = (softmax[c] - onehot[c]) x weight / N; these sum to 0 over c,
@@ -2431,7 +2460,7 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem, con
         }
         const float pgw = rf / (float)L.gamma;
         if (j == 0 && b < B) {
-            lterm[b] = pg ? pgl * pgw : isw * d * d;
+            lterm[b] = pg ? pgl * pgw : td_term<HU>(isw, d, delta);
             if (lead && L.abs_err) L.abs_err[b] = fabsf(d);
             if (lead && L.y_out) L.y_out[b] = y;
             dv[b] = L.dueling && !pg ? gq : 0.f;
@@ -2627,7 +2656,43 @@ __global__ __launch_bounds__(512) void fc1_bwd2_md_kernel(Bw1Args L, MdPar M) {
     if (L.A == 2) { if (dx) fc1_bwd2_body<2, true, true>(L, smem_bw, M); else fc1_bwd2_body<2, false, true>(L, smem_bw, M); }
     else { if (dx) fc1_bwd2_body<MAXA, true, true>(L, smem_bw, M); else fc1_bwd2_body<MAXA, false, true>(L, smem_bw, M); }
 }
+// ... with FB_ALGO_DOUBLE_PER's target (DP) and / or the Huber loss (HU): the extended kernel, as loss_head_x_kernel (the split
+// schedule's gate workgroup included)
+template <bool DP, bool HU, bool MD>
+__global__ __launch_bounds__(512) void fc1_bwd2_x_kernel(Bw1Args L, MdPar M, float delta) {
+    __shared__ float smem_bw[BW_LDS];
+    if (fb_gate_workgroup(L.gate)) return;
+    const bool dx = (int)blockIdx.x < L.n_dx;
+    if (L.A == 2) { if (dx) fc1_bwd2_body<2, true, MD, DP, HU>(L, smem_bw, M, delta); else fc1_bwd2_body<2, false, MD, DP, HU>(L, smem_bw, M, delta); }
+    else { if (dx) fc1_bwd2_body<MAXA, true, MD, DP, HU>(L, smem_bw, M, delta); else fc1_bwd2_body<MAXA, false, MD, DP, HU>(L, smem_bw, M, delta); }
+}
 
+#ifdef FB_QNET_X_TU
+// fb_qnet_x.hip compiles this file up to here: the two extended kernels are instantiated in THAT translation unit, and so live in a code
+// object of their own.  The code object of this file then holds exactly the kernels it held before the options existed, at the offsets
+// they had -- a kernel added here moves every other one (the descriptors in front of the text grow), and the train chain's
+// conv23_t_kernel and adam_fused_kernel measured 0.2 us slower each for that alone (profiles/huber_bench_parent_vs_new.txt).  The
+// launchers take the argument structs as bytes: both units compile the same definitions above.
+}  // namespace
+void fb_qnet_launch_loss_head_x(int dp, int hu, int md, unsigned grid, hipStream_t st, const void *largs, const void *mdpar, float delta) {
+    LossArgs L; MdPar M;
+    memcpy(&L, largs, sizeof(L)); memcpy(&M, mdpar, sizeof(M));
+    const dim3 g(grid), b(256);
+    if (dp && hu) hipLaunchKernelGGL((loss_head_x_kernel<true, true, false>), g, b, 0, st, L, M, delta);
+    else if (dp) hipLaunchKernelGGL((loss_head_x_kernel<true, false, false>), g, b, 0, st, L, M, 0.f);
+    else if (hu && md) hipLaunchKernelGGL((loss_head_x_kernel<false, true, true>), g, b, 0, st, L, M, delta);
+    else hipLaunchKernelGGL((loss_head_x_kernel<false, true, false>), g, b, 0, st, L, M, delta);
+}
+void fb_qnet_launch_fc1_bwd2_x(int dp, int hu, int md, unsigned grid, hipStream_t st, const void *largs, const void *mdpar, float delta) {
+    Bw1Args L; MdPar M;
+    memcpy(&L, largs, sizeof(L)); memcpy(&M, mdpar, sizeof(M));
+    const dim3 g(grid), b(512);
+    if (dp && hu) hipLaunchKernelGGL((fc1_bwd2_x_kernel<true, true, false>), g, b, 0, st, L, M, delta);
+    else if (dp) hipLaunchKernelGGL((fc1_bwd2_x_kernel<true, false, false>), g, b, 0, st, L, M, 0.f);
+    else if (hu && md) hipLaunchKernelGGL((fc1_bwd2_x_kernel<false, true, true>), g, b, 0, st, L, M, delta);
+    else hipLaunchKernelGGL((fc1_bwd2_x_kernel<false, true, false>), g, b, 0, st, L, M, delta);
+}
+#else
 // ================================================================== backward
 // conv weight (+ bias) gradients: dW[(cell, ci)][co] = sum_m X[m @ cell][ci] * dY[m][co], db[co] = sum_m dY[m][co].
 // One workgroup = one 32(ci) x 32(co) tile of one kernel cell; its 8 waves and the gridDim.y slabs split
@@ -3863,6 +3928,7 @@ struct fb_qnet {
     C51Sup sup;                      // C51 nets: the support (sup.N = 0: a scalar head); QR nets: sup.N = n_quantiles, the rest 0
     float kappa;                     // QR nets: the quantile Huber loss's threshold
     MdPar md;                        // scalar nets: Munchausen-DQN's (tau, alpha, l0) (fb_qnet_set_munchausen)
+    float huber;                     // scalar nets: the Huber loss's delta; 0 = the squared loss (fb_qnet_set_huber)
     float *c51_dl, *c51_xs, *c51_lt; // C51 training: logit gradients [max_batch][64], fc1 activations of s [max_batch][FC], loss terms [max_batch]
     // what the C51 head / loss / eval kernels read: hoff (the C51 layout; = off but for a dueling C51 net) from head_base(params[w]).
     // A dueling C51 net (FB_ARCH_C51_DUELING): heff[w] = [b_fc1 | W_eff | b_eff], the folded head of params[w] (c51d_fold_kernel)
@@ -4502,10 +4568,14 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         // apply needs no launch of its own for it
         // (at most one tick per Adam update: guarded on the device by AdamDev::ticks / applies)
         L.adam = h->adam; L.tick = p.tick;
-        if (is_mdqn_algo(p.algo)) {                  // (L.algo: the loss's form alone)
-            L.algo = p.algo == FB_ALGO_MDQN_PER ? FB_ALGO_PER : FB_ALGO_NATURE;
-            hipLaunchKernelGGL(loss_head_md_kernel, dim3(FC / 16), dim3(256), 0, c.st, L, h->md);
-        } else hipLaunchKernelGGL(loss_head_kernel, dim3(FC / 16), dim3(256), 0, c.st, L);
+        const bool dp = p.algo == FB_ALGO_DOUBLE_PER, hu = h->huber > 0.f, md = is_mdqn_algo(p.algo);
+        if (md) L.algo = p.algo == FB_ALGO_MDQN_PER ? FB_ALGO_PER : FB_ALGO_NATURE;      // (L.algo: the loss's form alone)
+        if (dp) L.algo = FB_ALGO_PER;
+        const dim3 grid(FC / 16);
+        // (delta = 0 and an older algo: the kernels and arguments of before the options existed)
+        if (dp || hu) fb_qnet_launch_loss_head_x(dp, hu, md, grid.x, c.st, &L, &h->md, h->huber);      // (the extended kernel: fb_qnet_x.hip's code object)
+        else if (md) hipLaunchKernelGGL(loss_head_md_kernel, grid, dim3(256), 0, c.st, L, h->md);
+        else hipLaunchKernelGGL(loss_head_kernel, grid, dim3(256), 0, c.st, L);
         return;
     }
     const bool pw = is_per_algo(p.algo);         // (prioritized: weighted loss; the priorities are KL (C51) / l_b (QR))
@@ -4548,10 +4618,13 @@ static void fc1_backward(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         L.adam = h->adam; L.tick = p.tick; L.rb = h->nsplit_train == 1;       // bf16 training: operands rounded to bf16
         L.gate = p.split && c.only < 0 ? FbGate{&p.split->f->trunk_done, p.split->seq, &p.split->f->timeouts[2]} : FbGate{nullptr, 0, nullptr};
         const dim3 grid(ndx1 + (FC / 32) * 7 + (L.gate.flag ? 1 : 0));
-        if (is_mdqn_algo(p.algo)) {                  // (L.algo: the loss's form alone)
-            L.algo = p.algo == FB_ALGO_MDQN_PER ? FB_ALGO_PER : FB_ALGO_NATURE;
-            hipLaunchKernelGGL(fc1_bwd2_md_kernel, grid, dim3(512), 0, c.st, L, h->md);
-        } else hipLaunchKernelGGL(fc1_bwd2_kernel, grid, dim3(512), 0, c.st, L);
+        const bool dp = p.algo == FB_ALGO_DOUBLE_PER, hu = h->huber > 0.f, md = is_mdqn_algo(p.algo);
+        if (md) L.algo = p.algo == FB_ALGO_MDQN_PER ? FB_ALGO_PER : FB_ALGO_NATURE;      // (L.algo: the loss's form alone)
+        if (dp) L.algo = FB_ALGO_PER;
+        // (delta = 0 and an older algo: the kernels and arguments of before the options existed)
+        if (dp || hu) fb_qnet_launch_fc1_bwd2_x(dp, hu, md, grid.x, c.st, &L, &h->md, h->huber);       // (the extended kernel: fb_qnet_x.hip's code object)
+        else if (md) hipLaunchKernelGGL(fc1_bwd2_md_kernel, grid, dim3(512), 0, c.st, L, h->md);
+        else hipLaunchKernelGGL(fc1_bwd2_kernel, grid, dim3(512), 0, c.st, L);
         return;
     }
     const int ndx = ((B + 31) / 32) * 50, ntile = ndx + 50 * (FC / 32);        // one workgroup per 32 x 32 tile, data-gradient tiles first
@@ -4844,6 +4917,21 @@ extern "C" int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha
     return FB_OK;
 }
 
+extern "C" int fb_qnet_set_huber(fb_qnet_t h, float delta) {
+    FB_REQUIRE(h, "fb_qnet_set_huber: NULL handle");
+    FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
+    FB_REQUIRE(isfinite(delta) && delta >= 0.f, "fb_qnet_set_huber: delta must be finite and >= 0 (0 = the squared loss; got %g)", (double)delta);
+    h->huber = delta;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_huber(fb_qnet_t h, float *delta_host) {
+    FB_REQUIRE(h && delta_host, "fb_qnet_get_huber: NULL argument");
+    FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
+    *delta_host = h->huber;
+    return FB_OK;
+}
+
 extern "C" int fb_qnet_get_quantiles(fb_qnet_t h, int *n_quantiles_host, float *kappa_host) {
     FB_REQUIRE(h && n_quantiles_host && kappa_host, "fb_qnet_get_quantiles: NULL argument");
     *n_quantiles_host = is_qr(h) ? h->sup.N : 0; *kappa_host = is_qr(h) ? h->kappa : 0.f;
@@ -4984,7 +5072,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
                       const uint8_t *t, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
     FB_REQUIRE(h && a && r && t && loss && (ring || (s && s2)), "fb_qnet_train_step: NULL argument");
-    FB_REQUIRE((algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER) || is_mdqn_algo(algo), "fb_qnet_train_step: unknown algo %d", algo);
+    FB_REQUIRE((algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER) || is_mdqn_algo(algo) || algo == FB_ALGO_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
     {
         const bool c51a = is_c51_algo(algo), qra = is_qr_algo(algo);
         FB_REQUIRE(c51a == (h->sup.N > 0 && !is_qr(h)), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
@@ -4997,12 +5085,13 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "fb_qnet_train_step: batch %d exceeds min(max_batch, %d)", B, MAXTB);
     FB_REQUIRE(algo != FB_ALGO_PG || (B <= 128 && !ring && gamma >= (double)B), "fb_qnet_train_step: FB_ALGO_PG takes chunks of <= 128 gathered states and gamma = the whole batch's sample count (>= %d)", B);
     FB_REQUIRE(!is_per_algo(algo) || isw, "fb_qnet_train_step: PER needs isw (algo %d)", algo);
+    FB_REQUIRE(algo != FB_ALGO_PG || !(h->huber > 0.f), "fb_qnet_train_step: FB_ALGO_PG has no TD error to clip: the net's Huber delta is %g, set it to 0 (fb_qnet_set_huber)", (double)h->huber);
     Plan p; memset(&p, 0, sizeof(p));
     // forward: s through the online net, s' through the net(s) the algorithm asks for
     p.ns = 2;
     p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
     if (algo == FB_ALGO_DQN || algo == FB_ALGO_PG) p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};               // BrainDQN.py:205 (same net); PG: s2 is forwarded and ignored
-    else if (algo == FB_ALGO_DOUBLE || is_double_c51(algo) || is_double_qr(algo)) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
+    else if (algo == FB_ALGO_DOUBLE || algo == FB_ALGO_DOUBLE_PER || is_double_c51(algo) || is_double_qr(algo)) { p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1}; p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1}; p.ns = 3; }
     else p.sl.s[1] = Slice{h->params[1], s2, B, B, h->w1s[1], 1};                                // target net (Nature, PER, C51, C51_PER, Munchausen)
     if (is_mdqn_algo(algo)) { p.sl.s[2] = Slice{h->params[1], s, 2 * B, B, h->w1s[1], 0}; p.ns = 3; }     // Munchausen: s through the target net as well (the log-policy bonus)
     p.sl.rb = h->nsplit_train == 1;
@@ -5101,3 +5190,4 @@ extern "C" const char *fb_qnet_kernel_name(int kernel) {
                                          "(conv1 dW: in conv_bw)", "slab_reduce_kernel", "adam_fused_kernel"};
     return kernel >= 0 && kernel < K_COUNT ? names[kernel] : "";
 }
+#endif  // FB_QNET_X_TU

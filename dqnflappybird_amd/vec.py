@@ -279,7 +279,7 @@ class VecReplay:
 ALGOS = {"dqn": L.ALGO_DQN, "nature": L.ALGO_NATURE, "double": L.ALGO_DOUBLE, "per": L.ALGO_PER, "pg": L.ALGO_PG,
          "c51": L.ALGO_C51, "c51double": L.ALGO_C51_DOUBLE, "c51per": L.ALGO_C51_PER, "c51doubleper": L.ALGO_C51_DOUBLE_PER,
          "qr": L.ALGO_QR, "qrdouble": L.ALGO_QR_DOUBLE, "qrper": L.ALGO_QR_PER, "qrdoubleper": L.ALGO_QR_DOUBLE_PER,
-         "mdqn": L.ALGO_MDQN, "mdqnper": L.ALGO_MDQN_PER}
+         "mdqn": L.ALGO_MDQN, "mdqnper": L.ALGO_MDQN_PER, "doubleper": L.ALGO_DOUBLE_PER}
 C51_ALGOS = ("c51", "c51double")                            # C51 on a uniform memory
 C51_PER_ALGOS = ("c51per", "c51doubleper")                  # C51 on a prioritized memory (weighted loss, KL priorities)
 QR_ALGOS = ("qr", "qrdouble")                               # QR-DQN on a uniform memory
@@ -288,7 +288,9 @@ PER_ALGOS = ("per",) + C51_PER_ALGOS                        # the scalar and C51
 PRIORITIZED_ALGOS = PER_ALGOS + QR_PER_ALGOS                # the algos of before Munchausen-DQN that take a prioritized memory
 MDQN_ALGOS = ("mdqn",)                                      # Munchausen-DQN on a uniform memory (scalar heads; include/fbdqn.h)
 MDQN_PER_ALGOS = ("mdqnper",)                               # Munchausen-DQN on a prioritized memory (FB_ALGO_PER's weights and |TD errors|)
-WEIGHTED_ALGOS = PRIORITIZED_ALGOS + MDQN_PER_ALGOS         # every algo that takes a prioritized memory and its importance weights
+DOUBLE_PER_ALGOS = ("doubleper",)                           # Double-DQN's target on a prioritized memory (scalar heads; include/fbdqn.h)
+WEIGHTED_ALGOS = PRIORITIZED_ALGOS + MDQN_PER_ALGOS + DOUBLE_PER_ALGOS     # every algo that takes a prioritized memory and its importance weights
+SCALAR_ALGOS = ("dqn", "nature", "double", "per", "mdqn", "mdqnper", "doubleper")      # the TD algos of the scalar heads: what the Huber loss applies to
 MDQN_DEFAULTS = L.MDQN_DEFAULTS                             # (tau, alpha, l0) of a new scalar net
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max
 C51_ARCHS = ("c51", "c51dueling")                         # distributional heads: C51, and the dueling C51 head (Rainbow's)
@@ -348,6 +350,15 @@ def check_munchausen(tau, alpha, clip):
     if not (np.isfinite(c) and c <= 0.0):
         raise ValueError(f"clip (l0) must be finite and <= 0, got {clip}")
     return t, a, c
+
+
+def check_huber(delta):
+    """the argument check of fb_qnet_set_huber, on the host (-> delta as a float32-rounded float; 0 = the squared loss)"""
+    with np.errstate(over="ignore"):                   # (a value beyond float32's range is infinite as the float the library takes)
+        d = float(np.float32(delta))
+    if not (np.isfinite(d) and d >= 0.0):
+        raise ValueError(f"huber (delta) must be finite and >= 0, got {delta}")
+    return d
 
 
 def bootstrap_gamma(gamma, n):
@@ -507,6 +518,19 @@ class QNet:
         t, a, c = C.c_float(), C.c_float(), C.c_float()
         L.check(L.lib().fb_qnet_get_munchausen(self.h, C.byref(t), C.byref(a), C.byref(c)), "fb_qnet_get_munchausen")
         return t.value, a.value, c.value
+
+    # -- Huber loss (scalar heads) ------------------------------------------------------
+    def set_huber(self, delta):
+        """the Huber (clipped-error) loss's delta of every scalar TD algo (fb_qnet_set_huber): d^2 inside |d| <= delta, delta (2 |d| -
+        delta) outside, the gradient through clamp(d, -delta, delta); 0 = off, the squared loss.  Refused on a C51 / QR / noisy net
+        and for a NaN, infinite or negative delta, before anything changes"""
+        L.check(L.lib().fb_qnet_set_huber(self.h, float(delta)), "fb_qnet_set_huber")
+
+    def huber(self):
+        """the net's current delta (fb_qnet_get_huber); 0 = the squared loss"""
+        d = C.c_float()
+        L.check(L.lib().fb_qnet_get_huber(self.h, C.byref(d)), "fb_qnet_get_huber")
+        return d.value
 
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):

@@ -14,18 +14,21 @@ fb_vec_step draws the nets' noise every step, and the epsilon schedule defaults 
 'qrdoubleper') trains a quantile head (arch 'qr', or 'qrdueling' for its dueling form) on one GPU and syncs as C51 does.  Munchausen-DQN ('mdqn',
 'mdqnper' with prioritized replay) trains the scalar heads ('plain' or 'dueling') with a soft bootstrap and a clipped log-policy bonus
 (tau, alpha, clip; include/fbdqn.h), syncs its target net every replace_target_iter steps and runs data parallel as 'double' / 'per' do.
+'doubleper' is Double-DQN's target on a prioritized memory (with arch='dueling' and n_step: Rainbow without the distributional head); it
+syncs as 'double' and runs data parallel as 'per'.  huber=delta > 0 gives every scalar algo the Huber (clipped-error) loss.
 """
 from . import dist as fdist
 
 MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True, "c51per": True, "c51doubleper": True,
-             "qr": True, "qrdouble": True, "qrper": True, "qrdoubleper": True, "mdqn": True, "mdqnper": True}
+             "qr": True, "qrdouble": True, "qrper": True, "qrdoubleper": True, "mdqn": True, "mdqnper": True, "doubleper": True}
 C51_ALGOS = ("c51", "c51double")                             # distributional Q-learning (include/fbdqn.h, DESIGN.md section 11)
 C51_PER_ALGOS = ("c51per", "c51doubleper")                   # ... with prioritized replay: weighted loss, KL priorities
 QR_ALGOS = ("qr", "qrdouble")                                # quantile regression (QR-DQN; include/fbdqn.h, DESIGN.md section 12)
 QR_PER_ALGOS = ("qrper", "qrdoubleper")                      # ... with prioritized replay: weighted loss, l_b priorities
 MDQN_ALGOS = ("mdqn", "mdqnper")                             # Munchausen-DQN on the scalar heads (include/fbdqn.h, DESIGN.md section 13)
-PER_ALGOS = ("per",) + C51_PER_ALGOS + QR_PER_ALGOS + ("mdqnper",)      # algos with a prioritized memory
-TARGET_SYNC = ("nature", "double") + C51_ALGOS + C51_PER_ALGOS + QR_ALGOS + QR_PER_ALGOS + MDQN_ALGOS   # algos whose target net is synced every replace_target_iter steps
+PER_ALGOS = ("per",) + C51_PER_ALGOS + QR_PER_ALGOS + ("mdqnper", "doubleper")      # algos with a prioritized memory
+TARGET_SYNC = ("nature", "double", "doubleper") + C51_ALGOS + C51_PER_ALGOS + QR_ALGOS + QR_PER_ALGOS + MDQN_ALGOS   # algos whose target net is synced every replace_target_iter steps
+SCALAR_ALGOS = ("dqn", "nature", "double", "per", "doubleper") + MDQN_ALGOS      # the TD algos of the scalar heads: what huber applies to
 C51_HEADS = ("c51", "c51dueling")                            # the heads a C51 algo trains (arch; 'plain' means 'c51')
 QR_HEADS = ("qr", "qrdueling")                               # the heads a QR algo trains (arch; 'plain' means 'qr')
 
@@ -53,6 +56,8 @@ class HipVecBackend:
     acting_noise_env = True                                  # ... which can act with noise per env (net.set_acting_noise('env'))
     qr = True                                                # quantile nets (net(..., arch='qr' | 'qrdueling', quantiles=(n_quantiles, kappa)))
     mdqn = True                                              # Munchausen-DQN: algos 'mdqn' / 'mdqnper' in step(), net.set_munchausen(tau, alpha, clip)
+    double_per = True                                        # algo 'doubleper' in step(): Double-DQN's target on a prioritized memory
+    huber = True                                             # the Huber loss on the scalar heads: net.set_huber(delta)
 
     def net(self, actions, fc_width, arch, max_batch, support=None, noisy=False, sigma0=0.5, quantiles=None):
         from .vec import QNet
@@ -156,6 +161,17 @@ def check_checkpoint_munchausen(z, munchausen, path):
                          f"{tuple(float(x) for x in munchausen)}")
 
 
+def check_checkpoint_huber(z, huber, path):
+    """a checkpoint's nets were trained with the Huber delta it records (no key: 0, the squared loss -- every checkpoint of before the
+    setting, and every one a brain with delta = 0 writes: save() records the key only when delta > 0, so such a checkpoint is the file
+    it was before the setting existed); a scalar-head brain takes one trained with its own delta only.  Distributional brains (huber None) do not read the key"""
+    if huber is None:
+        return
+    saved = float(z["huber"][0]) if "huber" in z.files else 0.0
+    if saved != float(huber):
+        raise ValueError(f"checkpoint {path} was trained with huber (delta) = {saved}, this VecBrain has huber = {float(huber)}")
+
+
 def check_checkpoint_noisy(z, noisy, sigma0, path):
     """a checkpoint's net must be noisy exactly when this brain's is (checkpoints that record nothing hold a non-noisy net)"""
     saved = bool(z["noisy"][0]) if "noisy" in z.files else False
@@ -180,7 +196,7 @@ class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0,
-                 noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0, tau=0.03, alpha=0.9, clip=-1.0):
+                 noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0, tau=0.03, alpha=0.9, clip=-1.0, huber=0.0):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
@@ -194,7 +210,11 @@ class VecBrain:
         any n_step; the PER forms on a prioritized memory), on arch 'qr' ('plain' means it) or 'qrdueling'; no noisy QR nets.
         algo 'mdqn' / 'mdqnper': Munchausen-DQN on arch 'plain' or 'dueling' -- the target is a soft (log-sum-exp, temperature tau)
         bootstrap plus alpha x the log-policy of the taken action, clipped below at clip (include/fbdqn.h); 'mdqnper' on a prioritized
-        memory; any n_step (only the first step's bonus is added), world > 1 as 'double' / 'per'; tau / alpha / clip are ignored otherwise."""
+        memory; any n_step (only the first step's bonus is added), world > 1 as 'double' / 'per'; tau / alpha / clip are ignored otherwise.
+        algo 'doubleper': 'double''s target (a* from the online net, its value from the target net) with 'per''s weighted loss and
+        priorities, on a prioritized memory; arch 'plain' or 'dueling', any n_step, world > 1 as 'per'.
+        huber=delta > 0 (scalar algos only -- 'dqn', 'nature', 'double', 'per', 'doubleper', 'mdqn', 'mdqnper'): the Huber loss, d^2 inside
+        |d| <= delta and delta (2 |d| - delta) outside (include/fbdqn.h); 0 = the squared loss.  Checkpoints record it."""
         n_step = int(n_step)
         noisy = bool(noisy)
         if acting_noise not in ("shared", "env"):
@@ -212,6 +232,26 @@ class VecBrain:
         self.support = None
         self.quantiles = None
         self.munchausen = None
+        from .vec import check_huber
+        self.huber = check_huber(huber)                      # (refused before anything touches the GPU)
+        if algo not in SCALAR_ALGOS:
+            if self.huber > 0.0:
+                raise ValueError(f"huber = {huber}: the Huber loss is offered on the scalar heads only ({', '.join(SCALAR_ALGOS)}), not with "
+                                 f"algo {algo!r} (QR has its own kappa)")
+            self.huber = None                                # (a distributional brain neither sets nor records it)
+        elif self.huber > 0.0 and not getattr(be, "huber", False):
+            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no Huber loss (huber): huber = {huber} needs it")
+        if algo == "doubleper":
+            if arch not in ("plain", "dueling"):
+                raise ValueError(f"algo {algo!r} trains the scalar heads: arch must be 'plain' or 'dueling', not {arch!r}")
+            if noisy:
+                raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with algo {algo!r}")
+            if not getattr(be, "double_per", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no Double-DQN with prioritized replay (double_per): "
+                                 f"algo {algo!r} needs it")
+            if not getattr(be, "per_one_step", False):
+                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
+                                 f"algo {algo!r} needs it")
         if algo in MDQN_ALGOS:
             from .vec import check_munchausen
             self.munchausen = check_munchausen(tau, alpha, clip)
@@ -305,6 +345,8 @@ class VecBrain:
             self.net = be.net(2, fc_width, arch, max(n_envs, batch), support=self.support) if self.support else be.net(2, fc_width, arch, max(n_envs, batch))
         if self.munchausen:
             self.net.set_munchausen(*self.munchausen)
+        if self.huber:
+            self.net.set_huber(self.huber)
         self.acting_noise = acting_noise
         if acting_noise == "env":
             self.net.set_acting_noise("env")                 # (fb_vec_step reads it: act with per-env noise, draw the online sample after)
@@ -449,6 +491,8 @@ class VecBrain:
                 shared["quantiles"] = np.array(self.quantiles, np.float64)
             if self.munchausen is not None:                  # Munchausen-DQN: (tau, alpha, l0) the nets were trained with
                 shared["munchausen"] = np.array(self.munchausen, np.float64)
+            if self.huber:                                   # the Huber delta the nets were trained with (no key: 0, the squared loss)
+                shared["huber"] = np.array([self.huber], np.float64)
             if self.noisy:                                   # online / target / Adam hold [mu | sigma] (checkpoints without it: not noisy)
                 shared["noisy"] = np.array([1], np.int64)
                 shared["sigma0"] = np.array([self.sigma0], np.float64)
@@ -477,6 +521,7 @@ class VecBrain:
             check_checkpoint_head(z, self.arch, path)
         check_checkpoint_noisy(z, self.noisy, self.sigma0, path)
         check_checkpoint_munchausen(z, self.munchausen, path)
+        check_checkpoint_huber(z, self.huber, path)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         self.net.load_params(z["online"], 0)

@@ -476,6 +476,44 @@ int fb_qnet_forward_quantiles(fb_qnet_t h, int which, const uint8_t *states, int
 int fb_qnet_set_munchausen(fb_qnet_t h, float tau, float alpha, float clip_lo);
 int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha_host, float *clip_lo_host);
 
+/* ------------------------------------------------------------------ Huber (clipped-error) loss and Double-DQN with prioritized replay
+ * Two additions to the SCALAR heads (FB_ARCH_PLAIN and FB_ARCH_DUELING), both on the target / loss side alone: the forward, the dueling
+ * combine, acting, evaluation and everything behind dLoss/dq(s, a) (fc1 / conv backward, Adam) are what they were.
+ *
+ * Huber loss: a per-net setting, delta (fb_qnet_set_huber).  A new scalar net holds delta = 0 = off: the squared TD loss of the algos
+ * above, through the kernels of before the setting existed.  delta finite and > 0 turns it on for FB_ALGO_DQN, _NATURE, _DOUBLE, _PER,
+ * _MDQN, _MDQN_PER and _DOUBLE_PER, in fb_qnet_train_step, fb_train_from_replay, fb_train_steps, fb_vec_step (both schedules),
+ * fb_vec_step_dp, with flat_grad and in FB_DTYPE_BF16 training.  With d = y - q(s, a) and w the importance weight (1 for the uniform algos):
+ *   loss term   w l(d),  l(d) = d^2 for |d| <= delta, else delta (2 |d| - delta): TWICE the textbook Huber loss, so that it IS the d^2 of
+ *               the squared loss inside the zone; value and slope are continuous at |d| = delta (delta^2 and 2 delta).  Formed in fp32 as
+ *               (w * d) * d inside, w * (delta * (2 |d| - delta)) outside; summed (FB_ALGO_DQN) or averaged over the batch as before
+ *   gradient    dLoss/dq(s, a) = -scale w clamp(d, -delta, delta), scale as before (2 for FB_ALGO_DQN's sum, 2 / B for the means), formed as
+ *               ((-scale) * w) * clamp: for |d| <= delta (|d| = delta included: the quadratic branch) loss term and gradient are bit for
+ *               bit the squared loss's, and so delta = 1e30 gives the results of delta = 0
+ *   abs_err     |d|, NOT clipped (the prioritized memory clips its priorities itself); q_target = y, unchanged
+ *   worked      delta 1, B 2, a mean loss, d = (0.5, -3): terms (0.25, 5), loss 2.625, dLoss/dq = (-0.5, +1.0)
+ * fb_qnet_set_huber: FB_ERR_INVALID before anything changes: delta NaN, infinite or < 0; a C51 / QR / noisy net (QR has its own kappa).
+ *   A host-side setting read by the calls issued after it (a hipGraph captured earlier keeps the value it was captured with).
+ * fb_qnet_get_huber: the current delta [host]; FB_ERR_INVALID on a C51 / QR / noisy net.
+ * FB_ALGO_PG has no TD error: on a net whose delta is > 0 it is refused (FB_ERR_INVALID) before anything is launched.
+ *
+ * FB_ALGO_DOUBLE_PER: Double-DQN's target on a prioritized memory ("Rainbow minus the distributional head" with FB_ARCH_DUELING and
+ * n-step returns).
+ *   forward     three slices as FB_ALGO_DOUBLE: s online, s' online, s' target
+ *   target      a* = the FIRST maximum of the online net's q(s', .) (a later action wins only if strictly greater), y = R + (done ? 0 :
+ *               Gamma q-(s', a*)), formed exactly as FB_ALGO_DOUBLE forms it: float64 sums, R = 0.1f read as 0.1, rounded to float once
+ *   loss        mean_b isw_b l(d_b), gradient, abs_err = |d| and q_target = y exactly as FB_ALGO_PER with that y
+ *   hence       with isw == 1 its loss, y and gradient are FB_ALGO_DOUBLE's bit for bit; on a one-action net (a* = 0, target net's value)
+ *               everything is FB_ALGO_PER's bit for bit
+ * Accepted wherever FB_ALGO_PER is: a prioritized memory (n-step ones included) and isw only, fb_qnet_train_step, fb_train_from_replay,
+ * fb_vec_step on FB_ALGO_PER's schedule (sample ahead on the memory's side stream, ring-fed training from 256 envs), flat_grad,
+ * fb_vec_step_dp, FB_DTYPE_BF16 training.  FB_ERR_INVALID before any launch or counter change, as for FB_ALGO_PER: fb_train_steps,
+ * a uniform memory, no isw, a C51 / QR / noisy net.  The target net syncs as for FB_ALGO_DOUBLE (the caller's call). */
+/* (16 is the next number after the Munchausen algos; 13 stays no algo) */
+#define FB_ALGO_DOUBLE_PER 16
+int fb_qnet_set_huber(fb_qnet_t h, float delta);
+int fb_qnet_get_huber(fb_qnet_t h, float *delta_host);
+
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
 int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host);
@@ -584,7 +622,7 @@ typedef struct {
     uint8_t *s, *s2, *a, *t; float *r;              /* gathered minibatch: u8[B,80,80,4] x2, u8[B], u8[B], f32[B] */
     float *loss;                                    /* f32[1] out */
     float *flat_grad;                               /* f32[n_params] or NULL */
-    /* prioritized replay (algo = FB_ALGO_PER, FB_ALGO_C51_PER, FB_ALGO_C51_DOUBLE_PER) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
+    /* prioritized replay (algo = FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 and QR _PER algos) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
      * float32 placeholder takes them (f32[B]), and the |TD errors| Memory.batch_update receives (f32[B]).
      * With the reference-order tree and 4096 envs or more Memory.batch_update of a step runs on the memory's own side stream, beside the NEXT step's acting
      * forward (its result is first needed by that step's Memory.store, which follows it there): idx and abs_err are read after
