@@ -21,6 +21,10 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
     python -m dqnflappybird_amd.FlappyBirdDQN --model doubleper --vec 1024 [--n-step K] [--huber 1]
                                                                                       (Double-DQN's target with prioritized replay on the scalar
                                                                                        head; --huber D: the Huber loss on any scalar-head model)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model doubleper --vec 1024 --n-step 3 --max-grad-norm 10 --polyak 0.005
+                                                                                      (any --vec model: clip the gradient's global norm to G;
+                                                                                       soft target updates with rate RHO after every train step
+                                                                                       in place of the periodic copy)
     python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy --acting-noise env
                                                                                       (... acting with independent noise per env)
 
@@ -81,7 +85,25 @@ def playFlappyBird(model, steps=None, verbose=True):
     return brain
 
 
-def main():
+def optimiser_kwargs(args, parser):
+    """--max-grad-norm / --polyak as VecBrain's keywords; bad values and a missing --vec are parser errors, before anything touches the GPU"""
+    kw = {}
+    if args.max_grad_norm is None and args.polyak is None:
+        return kw
+    if not args.vec:
+        parser.error("--max-grad-norm / --polyak need --vec: the single-env agents are the reference's, which neither clip nor update softly")
+    from .vec import check_max_grad_norm, check_polyak
+    try:
+        if args.max_grad_norm is not None:
+            kw["max_grad_norm"] = check_max_grad_norm(args.max_grad_norm)
+        if args.polyak is not None:
+            kw["polyak"] = check_polyak(args.polyak, allow_off=True)
+    except ValueError as e:
+        parser.error(str(e))
+    return kw
+
+
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("--model")
     parser.add_argument("--steps", type=int, default=None)
@@ -97,7 +119,16 @@ def main():
     parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9)")
     parser.add_argument("--clip", type=float, default=None, help="--model mdqn | mdqnper: the bonus's lower clip l0 (default -1)")
     parser.add_argument("--huber", type=float, default=None, help="scalar-head models with --vec: the Huber loss's delta (default 0 = the squared loss)")
+    parser.add_argument("--max-grad-norm", type=float, default=None, help="--vec: clip the gradient's global norm to G before Adam (default 0 = no clipping)")
+    parser.add_argument("--polyak", type=float, default=None, help="--vec: soft target updates, target += RHO (online - target) after every train step, "
+                                                                    "in place of the periodic copy (default 0 = off)")
+    return parser
+
+
+def main():
+    parser = build_parser()
     args = parser.parse_args()
+    okw = optimiser_kwargs(args, parser)                 # (refused before anything touches the GPU)
     qr_models = ("qrdqn", "qrdqnper", "qrrainbow")
     md_models = ("mdqn", "mdqnper")
     scalar_models = ("dqn", "ddqn", "dqnnature", "duelingdqn", "prioritydqn", "doubleper") + md_models
@@ -178,7 +209,7 @@ def main():
         if args.model in md_models:
             qkw = mkw
         vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step, noisy=args.noisy,
-                      acting_noise=args.acting_noise, **qkw, **hkw)
+                      acting_noise=args.acting_noise, **qkw, **hkw, **okw)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)
     else:
         playFlappyBird(args.model, args.steps, verbose=not args.quiet)

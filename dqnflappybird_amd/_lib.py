@@ -92,6 +92,11 @@ SIGNATURES = {
     "fb_qnet_get_munchausen": [_vp, _vp, _vp, _vp],
     "fb_qnet_set_huber": [_vp, _f],
     "fb_qnet_get_huber": [_vp, _vp],
+    "fb_qnet_set_max_grad_norm": [_vp, _f],
+    "fb_qnet_get_max_grad_norm": [_vp, _vp],
+    "fb_qnet_clip_grad": [_vp, _vp, _vp],
+    "fb_qnet_grad_norm": [_vp, _vp, _vp],
+    "fb_qnet_soft_sync_target": [_vp, _f, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],

@@ -208,6 +208,11 @@ int fb_qnet_is_dist(fb_qnet_t h);
 // largs / mdpar: fb_qnet.hip's LossArgs (Bw1Args) and MdPar, as bytes
 void fb_qnet_launch_loss_head_x(int dp, int hu, int md, unsigned grid, hipStream_t st, const void *largs, const void *mdpar, float delta);
 void fb_qnet_launch_fc1_bwd2_x(int dp, int hu, int md, unsigned grid, hipStream_t st, const void *largs, const void *mdpar, float delta);
+// global-norm gradient clipping and the soft target update, in the same code object: grad_sumsq_kernel + grad_clip_kernel over g[n] (part:
+// 256 float64 partials, out: (norm, c)); target_lerp_kernel, t += rho (o - t) over n floats.  fb_qnet_max_grad_norm: the net's limit, 0 = off
+void fb_qnet_launch_clip_x(hipStream_t st, float *g, long long n, double *part, float G, float *out);
+void fb_qnet_launch_target_lerp_x(hipStream_t st, float *t, const float *o, long long n, float rho);
+float fb_qnet_max_grad_norm(fb_qnet_t h);
 // fb_eval_run on a distributional (C51 or QR) net: launch the head fb_qnet_eval_trunk described in *hd (q / actions / epsilon / seeds filled in by the caller),
 // epsilon draws keyed key_of[row] on FB_STREAM_EVAL; the eval step launch then reads the actions (its head rider stays off)
 int fb_qnet_c51_eval_head(fb_qnet_t h, const FbHeadRider *hd, int n, const int32_t *key_of, void *stream);

@@ -138,6 +138,8 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
     FB_REQUIRE(!is_per_algo(algo), "fb_train_steps: prioritized replay needs the importance weights: use the separate calls (algo %d)", algo);
     FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_train_steps: a noisy net needs a noise key per step, which this call has none of: use fb_vec_step or "
                "fb_qnet_reset_noise + fb_train_from_replay");
+    FB_REQUIRE(!(fb_qnet_max_grad_norm(net) > 0.f), "fb_train_steps: the net clips its gradient (max_grad_norm %g): a clipped step is three calls, which this "
+               "call's riding draws do not span: use fb_train_from_replay or fb_vec_step", (double)fb_qnet_max_grad_norm(net));
     // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
     // here as well so that it comes before any counter moves
     if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
@@ -349,9 +351,10 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // for the env launch's head rider) -> the launch in front of it does not retire before the fc1 launch has; workspaces -> the fused
     // acting forward has its own (hf_act / hp_act); the acting forward against the previous step's Adam and whatever else the caller's
     // stream held at entry -> c_entry.
-    // (C51 and QR nets: the one-stream order below -- the split schedule is specified for the 2-output scalar heads)
+    // (C51 and QR nets: the one-stream order below -- the split schedule is specified for the 2-output scalar heads.  A net that clips its
+    // gradient: likewise -- its step ends with the clip and fb_qnet_apply_adam's launch, which the split hand-over has no place for)
     if (fb_vec_split_flag && train && !per && n_envs >= 256 && batch < 256 && fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 &&
-        !fb_qnet_is_dist(net)) {
+        !fb_qnet_is_dist(net) && !(fb_qnet_max_grad_norm(net) > 0.f)) {
         hipStream_t A = fb_stream(stream);
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(A, &cap);

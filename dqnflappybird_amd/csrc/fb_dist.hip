@@ -105,6 +105,15 @@ extern "C" void fb_dist_destroy(fb_dist_t d) {
     delete d;
 }
 
+// the reduced (and averaged) gradient is the one a net with a norm limit clips; then Adam
+static int clip_and_apply(fb_qnet_t net, float *g, hipStream_t st) {
+    if (fb_qnet_max_grad_norm(net) > 0.f) {
+        const int rc = fb_qnet_clip_grad(net, g, st);
+        if (rc != FB_OK) return rc;
+    }
+    return fb_qnet_apply_adam(net, g, st);
+}
+
 // all-reduce of the flat gradient, then Adam.  overlap = 1: the two-piece schedule (the producer recorded d->grad_ready behind its fc1
 // backward launch); overlap = 0: the whole vector on the step's stream -- no event, no second stream.  Which one wins depends on the
 // machine: on MI355X every cross-stream dependency costs ~5-8 us (measured at world size 1: the two-piece schedule adds 21 us of hops
@@ -117,7 +126,7 @@ static int reduce_and_apply(fb_dist_t d, fb_qnet_t net, float *g, int mean, hipS
     if (!d->overlap) {
         FB_CHECK_NCCL(rccl.AllReduce(g, g, (size_t)n, ncclFloat, ncclSum, d->comm, st));
         if (mean && d->world > 1) hipLaunchKernelGGL(div_kernel, dim3(256), dim3(256), 0, st, g, (long long)n, (float)d->world);
-        return fb_qnet_apply_adam(net, g, st);
+        return clip_and_apply(net, g, st);
     }
     // d->grad_ready must have been recorded by THIS step (behind its fc1 backward launch).  A step that ran without the event installed
     // on the net (fb_qnet_set_grad_event forgotten before fb_qnet_train_step / fb_train_from_replay) has not recorded it, and the side
@@ -131,7 +140,7 @@ static int reduce_and_apply(fb_dist_t d, fb_qnet_t net, float *g, int mean, hipS
     FB_CHECK_NCCL(rccl.AllReduce(g, g, (size_t)split, ncclFloat, ncclSum, d->comm, st));
     if (mean && d->world > 1) hipLaunchKernelGGL(div_kernel, dim3(64), dim3(256), 0, st, g, split, (float)d->world);
     FB_CHECK_HIP(hipStreamWaitEvent(st, d->tail_done, 0));
-    return fb_qnet_apply_adam(net, g, st);
+    return clip_and_apply(net, g, st);
 }
 
 extern "C" int fb_dist_set_overlap(fb_dist_t d, int overlap) {

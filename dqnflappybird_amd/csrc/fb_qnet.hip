@@ -2673,7 +2673,78 @@ __global__ __launch_bounds__(512) void fc1_bwd2_x_kernel(Bw1Args L, MdPar M, flo
 // they had -- a kernel added here moves every other one (the descriptors in front of the text grow), and the train chain's
 // conv23_t_kernel and adam_fused_kernel measured 0.2 us slower each for that alone (profiles/huber_bench_parent_vs_new.txt).  The
 // launchers take the argument structs as bytes: both units compile the same definitions above.
+//
+// Global-norm gradient clipping and the soft target update (include/fbdqn.h) live here for the same reason.
+//   grad_sumsq_kernel   CLIP_WGS workgroups over the flat gradient, whatever its length: thread t of workgroup w squares the float4s
+//                       w * 256 + t, + CLIP_WGS * 256, ... in float64 and adds them in that order; the workgroup adds its 256 sums in a
+//                       fixed tree (clip_tree) and stores ONE float64 partial.  The n % 4 elements behind the last float4 go to the first
+//                       threads of workgroup 0, behind their own range.  No atomics: the partials do not depend on timing
+//   grad_clip_kernel    every workgroup adds the CLIP_WGS partials in the same tree, so all of them hold the same norm = (float) sqrt(sum)
+//                       and c = G / max(norm, G) (c = 1 for G = 0 and for a norm that is not finite), and scales the float4s grad_sumsq's
+//                       workgroup of the same index read; with c == 1 it stores nothing.  Workgroup 0 records (norm, c)
+//   target_lerp_kernel  t += rho * (o - t) in fp32 over the whole master vector in one launch, float4 wide, the n % 4 tail by workgroup 0
+constexpr int CLIP_WGS = 256;
+__device__ __forceinline__ double clip_tree(double v, double *sh) {
+    const int tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float *__restrict__ g, long long n, double *__restrict__ part) {
+    __shared__ double sh[256];
+    const int tid = threadIdx.x;
+    const long long n4 = n >> 2;
+    double acc = 0.0;
+    for (long long q = (long long)blockIdx.x * 256 + tid; q < n4; q += (long long)CLIP_WGS * 256) {
+        const float4 v = reinterpret_cast<const float4 *>(g)[q];
+        acc += (double)v.x * (double)v.x; acc += (double)v.y * (double)v.y; acc += (double)v.z * (double)v.z; acc += (double)v.w * (double)v.w;
+    }
+    if (blockIdx.x == 0 && tid < (int)(n & 3)) { const double x = (double)g[(n4 << 2) + tid]; acc += x * x; }
+    const double s = clip_tree(acc, sh);
+    if (tid == 0) part[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void grad_clip_kernel(float *__restrict__ g, long long n, const double *__restrict__ part, float G, float *__restrict__ out) {
+    __shared__ double sh[256];
+    const int tid = threadIdx.x;
+    static_assert(CLIP_WGS == 256, "one partial per thread");
+    const float norm = (float)sqrt(clip_tree(part[tid], sh));
+    // (a NaN norm fails both comparisons, an infinite one the second: c = 1.  The quotient of two floats, formed in float64 and rounded
+    // once more, is the correctly rounded fp32 quotient)
+    const bool on = G > 0.f && norm > G && norm <= 3.402823466e38f;
+    const float c = on ? (float)((double)G / (double)norm) : 1.f;
+    if (blockIdx.x == 0 && tid == 0) { out[0] = norm; out[1] = c; }
+    if (c == 1.f) return;
+    const long long n4 = n >> 2;
+    for (long long q = (long long)blockIdx.x * 256 + tid; q < n4; q += (long long)CLIP_WGS * 256) {
+        float4 v = reinterpret_cast<float4 *>(g)[q];
+        v.x *= c; v.y *= c; v.z *= c; v.w *= c;
+        reinterpret_cast<float4 *>(g)[q] = v;
+    }
+    if (blockIdx.x == 0 && tid < (int)(n & 3)) g[(n4 << 2) + tid] *= c;
+}
+__global__ __launch_bounds__(256) void target_lerp_kernel(float *__restrict__ t, const float *__restrict__ o, long long n, float rho) {
+    const long long n4 = n >> 2, q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q < n4) {
+        float4 a = reinterpret_cast<float4 *>(t)[q];
+        const float4 b = reinterpret_cast<const float4 *>(o)[q];
+        a.x += rho * (b.x - a.x); a.y += rho * (b.y - a.y); a.z += rho * (b.z - a.z); a.w += rho * (b.w - a.w);
+        reinterpret_cast<float4 *>(t)[q] = a;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) { const long long i = (n4 << 2) + threadIdx.x; t[i] += rho * (o[i] - t[i]); }
+}
 }  // namespace
+void fb_qnet_launch_clip_x(hipStream_t st, float *g, long long n, double *part, float G, float *out) {
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(CLIP_WGS), dim3(256), 0, st, (const float *)g, n, part);
+    hipLaunchKernelGGL(grad_clip_kernel, dim3(CLIP_WGS), dim3(256), 0, st, g, n, (const double *)part, G, out);
+}
+void fb_qnet_launch_target_lerp_x(hipStream_t st, float *t, const float *o, long long n, float rho) {
+    hipLaunchKernelGGL(target_lerp_kernel, dim3((unsigned)(((n >> 2) + 255) / 256 > 0 ? ((n >> 2) + 255) / 256 : 1)), dim3(256), 0, st, t, o, n, rho);
+}
 void fb_qnet_launch_loss_head_x(int dp, int hu, int md, unsigned grid, hipStream_t st, const void *largs, const void *mdpar, float delta) {
     LossArgs L; MdPar M;
     memcpy(&L, largs, sizeof(L)); memcpy(&M, mdpar, sizeof(M));
@@ -3950,6 +4021,11 @@ struct fb_qnet {
     uint16_t *a3n;
     int *sig_seen;
     bool split_adam_pending;         // a split step exported its gradient: the fb_qnet_apply_adam that completes it takes over the Adam launch's waits
+    // global-norm gradient clipping (fb_qnet_set_max_grad_norm): G, 0 = off; clip_part: grad_sumsq_kernel's float64 partials, one per
+    // workgroup; clip_out: (norm, c) of the last fb_qnet_clip_grad
+    float max_grad_norm;
+    double *clip_part;
+    float *clip_out;
 };
 
 static NetOff make_off(int FC, int A, int dueling) {      // A: the head's columns (C51: actions x atoms)
@@ -4131,6 +4207,8 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     alloc((void **)&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc((void **)&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
     if (sup.N) { alloc((void **)&h->c51_dl, Bm * 64 * 4); alloc((void **)&h->c51_xs, Bm * fc_width * 4); alloc((void **)&h->c51_lt, Bm * 4); }
     if (is_c51d(h)) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
+    alloc((void **)&h->clip_part, sizeof(double) * 256); alloc((void **)&h->clip_out, sizeof(float) * 2);
+    if (e == hipSuccess) { const float one = 1.f; e = hipMemcpy(h->clip_out + 1, &one, sizeof(one), hipMemcpyHostToDevice); }      // (no clip yet: norm 0, c 1)
     if (e != hipSuccess) {
         fb_set_error(e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP, "fb_qnet_create: %s", hipGetErrorString(e));
         fb_qnet_destroy(h);
@@ -4150,7 +4228,7 @@ extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
                     h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
                     h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1],
-                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen};
+                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -5068,6 +5146,69 @@ extern "C" int fb_qnet_sync_target(fb_qnet_t h, void *stream) {
     return FB_OK;
 }
 
+// target <- target + rho (online - target) over the master vector; then everything derived from the target's parameters is rebuilt from
+// the new values, in fb_qnet_load_params' order (W_conv1's planes through w1_split_kernel, which also makes the new parameter version)
+extern "C" int fb_qnet_soft_sync_target(fb_qnet_t h, float rho, void *stream) {
+    FB_REQUIRE(h, "fb_qnet_soft_sync_target: NULL handle");
+    FB_REQUIRE(rho > 0.f && rho <= 1.f, "fb_qnet_soft_sync_target: rho must be in (0, 1] (got %g)", (double)rho);
+    if (rho == 1.f) return fb_qnet_sync_target(h, stream);
+    hipStream_t st = fb_stream(stream);
+    fb_qnet_launch_target_lerp_x(st, master(h, 1), master(h, 0), h->ntot, rho);
+    noisy_materialise(h, 1, 0, false, st);       // (with the target net's own noise)
+    hipLaunchKernelGGL(w1_split_kernel, dim3(32), dim3(256), 0, st, h->params[1], h->w1s[1], &h->adam->pver[1]);
+    c51d_fold(h, 1, st);
+    resplit_now(h, 1, st);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_set_max_grad_norm(fb_qnet_t h, float g) {
+    FB_REQUIRE(h, "fb_qnet_set_max_grad_norm: NULL handle");
+    FB_REQUIRE(isfinite(g) && g >= 0.f, "fb_qnet_set_max_grad_norm: the norm limit must be finite and >= 0 (0 = no clipping; got %g)", (double)g);
+    h->max_grad_norm = g;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_max_grad_norm(fb_qnet_t h, float *g_host) {
+    FB_REQUIRE(h && g_host, "fb_qnet_get_max_grad_norm: NULL argument");
+    *g_host = h->max_grad_norm;
+    return FB_OK;
+}
+
+float fb_qnet_max_grad_norm(fb_qnet_t h) { return h ? h->max_grad_norm : 0.f; }
+
+extern "C" int fb_qnet_clip_grad(fb_qnet_t h, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && flat_grad, "fb_qnet_clip_grad: NULL argument");
+    FB_REQUIRE(((uintptr_t)flat_grad & 15) == 0, "fb_qnet_clip_grad: flat_grad must be 16-byte aligned");
+    fb_qnet_launch_clip_x(fb_stream(stream), flat_grad, h->ntot, h->clip_part, h->max_grad_norm, h->clip_out);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_grad_norm(fb_qnet_t h, float *norm_host, float *scale_host) {
+    FB_REQUIRE(h, "fb_qnet_grad_norm: NULL handle");
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    float v[2] = {0.f, 1.f};
+    FB_CHECK_HIP(hipMemcpy(v, h->clip_out, sizeof(v), hipMemcpyDeviceToHost));
+    if (norm_host) *norm_host = v[0];
+    if (scale_host) *scale_host = v[1];
+    return FB_OK;
+}
+
+// a whole train step.  A net with a norm limit whose caller exports nothing: the exporting step into the net's own gradient buffer, the
+// clip, then fb_qnet_apply_adam's launch -- those three public calls, so their results bit for bit (loss, abs_err, q_target: the step's)
+static int run_train(fb_qnet *h, Plan &p, void *stream) {
+    if (!(p.apply_adam && h->max_grad_norm > 0.f)) return run_plan(h, p, -1, fb_stream(stream));
+    p.apply_adam = false;                        // (p.G is h->grad already)
+    const hipEvent_t ev = h->grad_ev;            // (nobody reduces this export: no event)
+    h->grad_ev = nullptr;
+    int rc = run_plan(h, p, -1, fb_stream(stream));
+    h->grad_ev = ev;
+    if (rc == FB_OK) rc = fb_qnet_clip_grad(h, h->grad, stream);
+    if (rc == FB_OK) rc = fb_qnet_apply_adam(h, h->grad, stream);
+    return rc;
+}
+
 static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
                       const uint8_t *t, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
@@ -5114,7 +5255,7 @@ int fb_qnet_train_step_ring(fb_qnet_t h, int algo, int B, const FbRingSrc *ring,
     if (rc != FB_OK) return rc;
     p.sample_rider = rider;
     p.split = split;
-    return run_plan(h, p, -1, fb_stream(stream));
+    return run_train(h, p, stream);
 }
 
 // both nets in one launch (blockIdx.y = net; every thread checks its net's versions) + one marking launch
@@ -5157,7 +5298,7 @@ extern "C" int fb_qnet_train_step(fb_qnet_t h, int algo, int B, const uint8_t *s
     Plan p;
     int rc = train_plan(h, algo, B, s, a, r, s2, t, isw, gamma, loss, abs_err, q_target, flat_grad, &p);
     if (rc != FB_OK) return rc;
-    return run_plan(h, p, -1, fb_stream(stream));
+    return run_train(h, p, stream);
 }
 
 // Measurement aid for bench.py: launch ONE kernel of the train-step plan (`kernel` = KernelId, see

@@ -361,6 +361,26 @@ def check_huber(delta):
     return d
 
 
+def check_max_grad_norm(g):
+    """the argument check of fb_qnet_set_max_grad_norm, on the host (-> the limit as a float32-rounded float; 0 = no clipping)"""
+    with np.errstate(over="ignore"):                   # (a value beyond float32's range is infinite as the float the library takes)
+        v = float(np.float32(g))
+    if not (np.isfinite(v) and v >= 0.0):
+        raise ValueError(f"max_grad_norm must be finite and >= 0, got {g}")
+    return v
+
+
+def check_polyak(rho, allow_off=False):
+    """the argument check of fb_qnet_soft_sync_target, on the host (-> rho as a float32-rounded float in (0, 1]); allow_off: 0 passes
+    as well (VecBrain's "no soft updates")"""
+    v = float(np.float32(rho))
+    if allow_off and v == 0.0:
+        return 0.0
+    if not (0.0 < v <= 1.0):                           # (NaN fails both comparisons)
+        raise ValueError(f"polyak (rho) must be in (0, 1]{' or 0 = off' if allow_off else ''}, got {rho}")
+    return v
+
+
 def bootstrap_gamma(gamma, n):
     """Gamma = g_n of the n-step return (g_0 = 1, g_{k+1} = g_k * gamma in float64): the discount an n-step target bootstraps with,
     and what QNet.train_step takes on a minibatch gathered from an n-step memory.  gamma itself at n = 1."""
@@ -506,6 +526,37 @@ class QNet:
 
     def sync_target(self):
         L.check(L.lib().fb_qnet_sync_target(self.h, L.current_stream()), "fb_qnet_sync_target")
+
+    def soft_sync_target(self, rho):
+        """target <- target + rho (online - target) over the flat vector (fb_qnet_soft_sync_target; [mu | sigma] of a noisy net), with
+        everything derived from the target's parameters rebuilt behind it; rho in (0, 1], rho = 1 is sync_target itself"""
+        L.check(L.lib().fb_qnet_soft_sync_target(self.h, check_polyak(rho), L.current_stream()), "fb_qnet_soft_sync_target")
+
+    # -- gradient clipping by global norm --------------------------------------------
+    def set_max_grad_norm(self, g):
+        """the limit G of the flat gradient's norm (fb_qnet_set_max_grad_norm): 0 = off; G > 0: train_step / train_from_replay / VecStep
+        without flat_grad scale the gradient by G / max(norm, G) before Adam, and a data-parallel step clips behind its reduction.
+        An exported gradient (flat_grad) stays unclipped: clip_grad does it"""
+        L.check(L.lib().fb_qnet_set_max_grad_norm(self.h, check_max_grad_norm(g)), "fb_qnet_set_max_grad_norm")
+
+    @property
+    def max_grad_norm(self):
+        g = C.c_float()
+        L.check(L.lib().fb_qnet_get_max_grad_norm(self.h, C.byref(g)), "fb_qnet_get_max_grad_norm")
+        return g.value
+
+    def clip_grad(self, flat_grad):
+        """clip float32[n_params] in place to the net's limit (fb_qnet_clip_grad); with the limit 0 it only records the norm"""
+        _dev_check(flat_grad)
+        if flat_grad.dtype != torch.float32 or flat_grad.numel() != self.n_params:
+            raise ValueError(f"expected float32[{self.n_params}]")
+        L.check(L.lib().fb_qnet_clip_grad(self.h, L.ptr(flat_grad), L.current_stream()), "fb_qnet_clip_grad")
+
+    def grad_norm(self):
+        """(norm, scale) of the net's last clip (fb_qnet_grad_norm); synchronous: read it when you log, not per step"""
+        n, c = C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_grad_norm(self.h, C.byref(n), C.byref(c)), "fb_qnet_grad_norm")
+        return n.value, c.value
 
     # -- Munchausen-DQN (scalar heads) -----------------------------------------------
     def set_munchausen(self, tau=MDQN_DEFAULTS[0], alpha=MDQN_DEFAULTS[1], clip=MDQN_DEFAULTS[2]):

@@ -16,6 +16,8 @@ fb_vec_step draws the nets' noise every step, and the epsilon schedule defaults 
 (tau, alpha, clip; include/fbdqn.h), syncs its target net every replace_target_iter steps and runs data parallel as 'double' / 'per' do.
 'doubleper' is Double-DQN's target on a prioritized memory (with arch='dueling' and n_step: Rainbow without the distributional head); it
 syncs as 'double' and runs data parallel as 'per'.  huber=delta > 0 gives every scalar algo the Huber (clipped-error) loss.
+max_grad_norm=G > 0 clips the flat gradient's global norm to G before Adam (every algo and head; data parallel: behind the reduction);
+polyak=rho > 0 replaces the periodic target copy by target += rho (online - target) after every train step.
 """
 from . import dist as fdist
 
@@ -58,6 +60,8 @@ class HipVecBackend:
     mdqn = True                                              # Munchausen-DQN: algos 'mdqn' / 'mdqnper' in step(), net.set_munchausen(tau, alpha, clip)
     double_per = True                                        # algo 'doubleper' in step(): Double-DQN's target on a prioritized memory
     huber = True                                             # the Huber loss on the scalar heads: net.set_huber(delta)
+    grad_clip = True                                         # global-norm gradient clipping: net.set_max_grad_norm(G), clip_grad, grad_norm
+    polyak = True                                            # soft target updates: net.soft_sync_target(rho)
 
     def net(self, actions, fc_width, arch, max_batch, support=None, noisy=False, sigma0=0.5, quantiles=None):
         from .vec import QNet
@@ -172,6 +176,13 @@ def check_checkpoint_huber(z, huber, path):
         raise ValueError(f"checkpoint {path} was trained with huber (delta) = {saved}, this VecBrain has huber = {float(huber)}")
 
 
+def checkpoint_optimiser(z):
+    """(max_grad_norm, polyak) a checkpoint records -- 0.0 where it records none: every checkpoint of before the settings, and every one a
+    brain with the setting off writes.  Optimiser settings, like the learning rate: load() reports them (VecBrain.checkpoint_optimiser)
+    and refuses nothing -- a run may be continued with another limit or rate"""
+    return tuple(float(z[k][0]) if k in z.files else 0.0 for k in ("max_grad_norm", "polyak"))
+
+
 def check_checkpoint_noisy(z, noisy, sigma0, path):
     """a checkpoint's net must be noisy exactly when this brain's is (checkpoints that record nothing hold a non-noisy net)"""
     saved = bool(z["noisy"][0]) if "noisy" in z.files else False
@@ -196,7 +207,8 @@ class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0,
-                 noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0, tau=0.03, alpha=0.9, clip=-1.0, huber=0.0):
+                 noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0, tau=0.03, alpha=0.9, clip=-1.0, huber=0.0,
+                 max_grad_norm=0.0, polyak=0.0):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
@@ -214,7 +226,12 @@ class VecBrain:
         algo 'doubleper': 'double''s target (a* from the online net, its value from the target net) with 'per''s weighted loss and
         priorities, on a prioritized memory; arch 'plain' or 'dueling', any n_step, world > 1 as 'per'.
         huber=delta > 0 (scalar algos only -- 'dqn', 'nature', 'double', 'per', 'doubleper', 'mdqn', 'mdqnper'): the Huber loss, d^2 inside
-        |d| <= delta and delta (2 |d| - delta) outside (include/fbdqn.h); 0 = the squared loss.  Checkpoints record it."""
+        |d| <= delta and delta (2 |d| - delta) outside (include/fbdqn.h); 0 = the squared loss.  Checkpoints record it.
+        max_grad_norm=G > 0 (every algo and head): the flat gradient is scaled by G / max(norm, G) before Adam (tf.clip_by_global_norm;
+        include/fbdqn.h); world > 1: the reduced gradient is clipped, so every rank applies the same scale.  run() logs the last norm.
+        polyak=rho in (0, 1] (every algo): after every train step target += rho (online - target) (net.soft_sync_target), and the hard
+        copy every replace_target_iter steps is dropped.  This gives the 'per' family -- 'per', whose target net the reference agent never
+        syncs, included -- a moving target.  Both are optimiser settings: checkpoints record them, load() does not refuse another value."""
         n_step = int(n_step)
         noisy = bool(noisy)
         if acting_noise not in ("shared", "env"):
@@ -241,6 +258,14 @@ class VecBrain:
             self.huber = None                                # (a distributional brain neither sets nor records it)
         elif self.huber > 0.0 and not getattr(be, "huber", False):
             raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no Huber loss (huber): huber = {huber} needs it")
+        from .vec import check_max_grad_norm, check_polyak
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)      # (both refused before anything touches the GPU)
+        self.polyak = check_polyak(polyak, allow_off=True)
+        if self.max_grad_norm > 0.0 and not getattr(be, "grad_clip", False):
+            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no gradient clipping (grad_clip): "
+                             f"max_grad_norm = {max_grad_norm} needs it")
+        if self.polyak > 0.0 and not getattr(be, "polyak", False):
+            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no soft target updates (polyak): polyak = {polyak} needs it")
         if algo == "doubleper":
             if arch not in ("plain", "dueling"):
                 raise ValueError(f"algo {algo!r} trains the scalar heads: arch must be 'plain' or 'dueling', not {arch!r}")
@@ -347,6 +372,8 @@ class VecBrain:
             self.net.set_munchausen(*self.munchausen)
         if self.huber:
             self.net.set_huber(self.huber)
+        if self.max_grad_norm:
+            self.net.set_max_grad_norm(self.max_grad_norm)
         self.acting_noise = acting_noise
         if acting_noise == "env":
             self.net.set_acting_noise("env")                 # (fb_vec_step reads it: act with per-env noise, draw the online sample after)
@@ -383,8 +410,19 @@ class VecBrain:
         else:
             self.one_step = be.step(self.env, self.replay, self.net, batch, algo, gamma, self.grad)
 
+    def _hard_sync_due(self):
+        """the periodic target copy, unless soft updates replace it"""
+        return not self.polyak and self.algo in TARGET_SYNC and self.timeStep % self.replace_target_iter == 0
+
+    def _apply_reduced(self):
+        """data parallel without the library's communicator: all-reduce, clip the reduced gradient (the net never clips an exported one), Adam"""
+        self.reduce()
+        if self.max_grad_norm:
+            self.net.clip_grad(self.grad)
+        self.net.apply_adam(self.grad)
+
     def train_step(self, idx=None):
-        if self.algo in TARGET_SYNC and self.timeStep % self.replace_target_iter == 0:
+        if self._hard_sync_due():
             self.net.sync_target()
         isw = None
         if idx is None:
@@ -397,24 +435,26 @@ class VecBrain:
             loss, abs_err, _ = self.net.train_step(self.algo, s, a, r, s2, t, isw=isw, gamma=self.boot_gamma, flat_grad=self.grad,
                                                    want_aux=self.algo in PER_ALGOS)
         if self.grad is not None:
-            self.reduce()
-            self.net.apply_adam(self.grad)
+            self._apply_reduced()
         if self.algo in PER_ALGOS:
             self.replay.update_priorities(idx, abs_err=abs_err)
+        if self.polyak:
+            self.net.soft_sync_target(self.polyak)
         self.last_loss = loss
 
     def step(self):
         if self.one_step is not None:
             training = self.onlineTimeStep > self.observe
-            if training and self.algo in TARGET_SYNC and self.timeStep % self.replace_target_iter == 0:
+            if training and self._hard_sync_due():
                 self.net.sync_target()                       # acting reads the online net only: same result as syncing before training
             self.one_step(self.epsilon, seed=self.seed + self.rank, step=self.timeStep, train=training)
             if self.epsilon > self.final_epsilon and self.onlineTimeStep > self.observe:
                 self.epsilon -= (self.initial_epsilon - self.final_epsilon) / self.explore
             if training:
-                if self.grad is not None and self.native is None:      # (fb_vec_step_dp has reduced and applied already)
-                    self.reduce()
-                    self.net.apply_adam(self.grad)
+                if self.grad is not None and self.native is None:      # (fb_vec_step_dp has reduced, clipped and applied already)
+                    self._apply_reduced()
+                if self.polyak:
+                    self.net.soft_sync_target(self.polyak)
                 self.last_loss = self.one_step.loss
             self.timeStep += 1
             self.onlineTimeStep += 1
@@ -493,6 +533,10 @@ class VecBrain:
                 shared["munchausen"] = np.array(self.munchausen, np.float64)
             if self.huber:                                   # the Huber delta the nets were trained with (no key: 0, the squared loss)
                 shared["huber"] = np.array([self.huber], np.float64)
+            if self.max_grad_norm:                           # optimiser settings (no key: 0 = off), recorded like huber's: only when on
+                shared["max_grad_norm"] = np.array([self.max_grad_norm], np.float64)
+            if self.polyak:
+                shared["polyak"] = np.array([self.polyak], np.float64)
             if self.noisy:                                   # online / target / Adam hold [mu | sigma] (checkpoints without it: not noisy)
                 shared["noisy"] = np.array([1], np.int64)
                 shared["sigma0"] = np.array([self.sigma0], np.float64)
@@ -522,6 +566,8 @@ class VecBrain:
         check_checkpoint_noisy(z, self.noisy, self.sigma0, path)
         check_checkpoint_munchausen(z, self.munchausen, path)
         check_checkpoint_huber(z, self.huber, path)
+        # (max_grad_norm / polyak: optimiser settings, like the learning rate -- this brain's own values go on, whatever the file records)
+        self.checkpoint_optimiser = checkpoint_optimiser(z)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         self.net.load_params(z["online"], 0)
@@ -549,5 +595,9 @@ class VecBrain:
                     self.net.check_range()                       # (the same sync: an activation beyond the two-plane fp16 range raises here)
                 if hasattr(self.net, "split_stats"):
                     self.net.split_stats()                       # (... and so does a wait between the two streams of fb_vec_step's split schedule that gave up)
+                clip = ""
+                if self.max_grad_norm:                           # (the last train step's; a synchronous read, at the log cadence only)
+                    norm, scale = self.net.grad_norm()
+                    clip = f" / GRAD_NORM {norm:.6g} / CLIP_SCALE {scale:.6g}"
                 print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / EPSILON {self.epsilon:.6f} / GAME_TIMES {ep} / "
-                      f"MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {loss:.6g}", flush=True)
+                      f"MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {loss:.6g}{clip}", flush=True)

@@ -514,6 +514,50 @@ int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha_host, floa
 int fb_qnet_set_huber(fb_qnet_t h, float delta);
 int fb_qnet_get_huber(fb_qnet_t h, float *delta_host);
 
+/* ------------------------------------------------------------------ global-norm gradient clipping and soft (Polyak) target updates
+ * Two optimiser-side settings, both off in a new net; with them off every path, kernel and result is what it was.
+ *
+ * Clipping (tf.clip_by_global_norm; the dueling paper, Rainbow and QR-DQN clip to 10): a per-net limit G (fb_qnet_set_max_grad_norm).
+ *   norm        sqrt(sum_q g[q]^2) over the WHOLE flat gradient (fb_qnet_num_params floats: every tensor of the flat order, for a noisy net
+ *               sigma's part included).  Squares and sums in float64, in a fixed order (a fixed grid, per-thread strides, a fixed tree per
+ *               workgroup, the workgroups' partials in a fixed tree; no atomics): two calls on equal gradients give equal bits.  The sum's
+ *               square root is rounded to fp32 once
+ *   scale       c = G / max(norm, G) in fp32 from that norm, g[q] <- g[q] * c.  norm <= G: c is exactly 1.0f and nothing is stored, the
+ *               gradient stays bit for bit.  A norm that is not finite (an inf or NaN entry): c = 1, the gradient goes on as it would
+ *               without clipping and the recorded norm shows it.  G = 0: the norm is computed and recorded, the gradient untouched (the
+ *               diagnostic use: fb_qnet_clip_grad on an exported gradient of a net that does not clip)
+ *   worked      g = (3, 4), G = 2.5: norm 5, c 0.5, g <- (1.5, 2)
+ * fb_qnet_set_max_grad_norm: G = 0 (a new net) off, finite G > 0 on; negative, NaN or infinite: FB_ERR_INVALID before anything changes.
+ *   Every arch.  A host-side setting read by the calls issued after it (a hipGraph captured earlier keeps the value it was captured with).
+ * fb_qnet_clip_grad: the two launches above on flat_grad ([dev] f32[fb_qnet_num_params], 16-byte aligned, in place) with the net's G, on
+ *   `stream`; capturable.  The net keeps (norm, c) of its last call in two device words.
+ * fb_qnet_grad_norm: those two words [host] (either pointer may be NULL); SYNCHRONOUS, for the log cadence.  (0, 1) before any clip.
+ * Where a net with G > 0 clips:
+ *   flat_grad == NULL   fb_qnet_train_step, fb_train_from_replay, fb_vec_step: the step runs as the exporting step into the net's own
+ *                       gradient buffer, then fb_qnet_clip_grad, then fb_qnet_apply_adam's launch: parameters, both Adam slots and the beta
+ *                       powers are those of the three public calls composed by hand, bit for bit; loss / abs_err / q_target are the
+ *                       (unclipped) step's.  The fused chain's in-launch Adam (W_fc1's span in the conv backward, the slab-summing Adam
+ *                       launch) is not taken
+ *   flat_grad != NULL   the gradient is exported UNCLIPPED, as before: the caller reduces it, then clips (fb_qnet_clip_grad) or hands it
+ *                       to fb_dist_reduce_apply / fb_vec_step_dp, which clip behind the reduction and the averaging, before Adam
+ *   fb_vec_step         takes the one-stream order (as for C51 / QR nets); the split schedule's Adam hand-over is never armed
+ *   fb_train_steps      FB_ERR_INVALID before any launch or counter change (as for a noisy net)
+ *   FB_ALGO_PG          callers sum their chunk gradients and call fb_qnet_apply_adam: they clip the sum with fb_qnet_clip_grad first
+ *   fb_qnet_apply_adam  never clips by itself.
+ *
+ * Soft target update: fb_qnet_soft_sync_target(rho): target <- target + rho * (online - target) in fp32 (formed in that order, no fused
+ * multiply-add) over the vector fb_qnet_sync_target copies ([mu | sigma] of a noisy net), one launch.
+ *   rho         in (0, 1]; 0, negative, > 1 or NaN: FB_ERR_INVALID before any launch.  rho == 1 IS fb_qnet_sync_target (bit-identical)
+ *   afterwards  on `stream`, everything derived from the target's parameters is rebuilt from the NEW values, as fb_qnet_load_params does
+ *               (not copied from the online net): W_conv1's fp16 planes, a new parameter version, a noisy net's effective vector with the
+ *               target's own current sample, the split planes, a dueling distributional net's folded head.  The online net, both noise
+ *               samples and the Adam state are untouched.  Every arch; capturable. */
+int fb_qnet_set_max_grad_norm(fb_qnet_t h, float g);
+int fb_qnet_get_max_grad_norm(fb_qnet_t h, float *g_host);
+int fb_qnet_clip_grad(fb_qnet_t h, float *flat_grad, void *stream);
+int fb_qnet_grad_norm(fb_qnet_t h, float *norm_host, float *scale_host);
+int fb_qnet_soft_sync_target(fb_qnet_t h, float rho, void *stream);
+
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
 int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host);
