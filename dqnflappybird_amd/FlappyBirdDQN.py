@@ -122,13 +122,48 @@ def build_parser():
     parser.add_argument("--max-grad-norm", type=float, default=None, help="--vec: clip the gradient's global norm to G before Adam (default 0 = no clipping)")
     parser.add_argument("--polyak", type=float, default=None, help="--vec: soft target updates, target += RHO (online - target) after every train step, "
                                                                     "in place of the periodic copy (default 0 = off)")
+    parser.add_argument("--rollout", type=int, default=None, help="--model a2c: env steps per update T (default 5, at most 128)")
+    parser.add_argument("--gae-lambda", type=float, default=None, help="--model a2c: lambda of the generalised advantage estimate (default 0.95)")
+    parser.add_argument("--value-coef", type=float, default=None, help="--model a2c: the value loss's coefficient (default 0.5)")
+    parser.add_argument("--entropy-coef", type=float, default=None, help="--model a2c: the entropy bonus's coefficient (default 0.01)")
     return parser
+
+
+def a2c_kwargs(args, parser):
+    """--model a2c's options as VecActorCritic's keywords; everything is refused here, before anything touches the GPU"""
+    given = [n for n, v in (("--rollout", args.rollout), ("--gae-lambda", args.gae_lambda), ("--value-coef", args.value_coef),
+                            ("--entropy-coef", args.entropy_coef)) if v is not None]
+    if args.model != "a2c":
+        if given:
+            parser.error(f"{' / '.join(given)} need --model a2c, not --model {args.model}")
+        return None
+    if not args.vec:
+        parser.error("--model a2c needs --vec: the advantage actor-critic runs in the vectorised loop only")
+    for name, on in (("--noisy", args.noisy), ("--n-step", args.n_step != 1), ("--huber", args.huber is not None), ("--polyak", args.polyak is not None),
+                     ("--tau / --alpha / --clip", args.tau is not None or args.alpha is not None or args.clip is not None),
+                     ("--n-quantiles / --kappa", args.n_quantiles is not None or args.kappa is not None)):
+        if on:
+            parser.error(f"{name} is not an option of --model a2c (--rollout, --gae-lambda, --value-coef, --entropy-coef, --max-grad-norm are)")
+    from .vecac import check_args
+    kw = dict(rollout=5 if args.rollout is None else args.rollout, gae_lambda=0.95 if args.gae_lambda is None else args.gae_lambda,
+              value_coef=0.5 if args.value_coef is None else args.value_coef, entropy_coef=0.01 if args.entropy_coef is None else args.entropy_coef,
+              max_grad_norm=0.0 if args.max_grad_norm is None else args.max_grad_norm)
+    try:
+        check_args(args.vec, kw["rollout"], 0.99, kw["gae_lambda"], kw["value_coef"], kw["entropy_coef"], kw["max_grad_norm"])
+    except ValueError as e:
+        parser.error(str(e))
+    return kw
 
 
 def main():
     parser = build_parser()
     args = parser.parse_args()
     okw = optimiser_kwargs(args, parser)                 # (refused before anything touches the GPU)
+    akw = a2c_kwargs(args, parser)
+    if akw is not None:                                  # the on-policy learner: a class of its own, one GPU (--steps: updates)
+        from .vecac import VecActorCritic
+        VecActorCritic(args.vec, **akw).run(args.steps or 1000, log_every=0 if args.quiet else 100)
+        return
     qr_models = ("qrdqn", "qrdqnper", "qrrainbow")
     md_models = ("mdqn", "mdqnper")
     scalar_models = ("dqn", "ddqn", "dqnnature", "duelingdqn", "prioritydqn", "doubleper") + md_models

@@ -25,6 +25,8 @@ ALGO_QR, ALGO_QR_DOUBLE, ALGO_QR_PER, ALGO_QR_DOUBLE_PER = 9, 10, 11, 12
 ALGO_MDQN, ALGO_MDQN_PER = 14, 15                     # Munchausen-DQN on the scalar heads (include/fbdqn.h)
 MDQN_DEFAULTS = (0.03, 0.9, -1.0)                     # (tau, alpha, l0) of a new scalar net: the paper's
 ALGO_DOUBLE_PER = 16                                  # Double-DQN's target on a prioritized memory (include/fbdqn.h)
+ARCH_AC = 6                                           # advantage actor-critic: the dueling layout read raw (include/fbdqn.h)
+AC_DEFAULTS = (0.5, 0.01)                             # (value_coef, entropy_coef) of a new actor-critic net
 NOISE_SAMPLE, NOISE_MEAN = 0, 1                       # include/fbdqn.h FB_NOISE_* (fb_qnet_reset_noise)
 ACT_NOISE_SHARED, ACT_NOISE_PER_ENV = 0, 1            # include/fbdqn.h FB_ACT_NOISE_* (fb_qnet_set_acting_noise)
 DTYPE_F32, DTYPE_BF16 = 0, 1
@@ -97,6 +99,15 @@ SIGNATURES = {
     "fb_qnet_clip_grad": [_vp, _vp, _vp],
     "fb_qnet_grad_norm": [_vp, _vp, _vp],
     "fb_qnet_soft_sync_target": [_vp, _f, _vp],
+    "fb_qnet_create_ac": [_i, _i, _i, _vp],
+    "fb_qnet_set_ac": [_vp, _f, _f],
+    "fb_qnet_get_ac": [_vp, _vp, _vp],
+    "fb_qnet_forward_ac": [_vp, _vp, _i, _vp, _vp, _vp],
+    "fb_qnet_act_policy_nib": [_vp, _vp, _i, _u64, _u64, _i, _vp, _vp, _vp, _vp, _vp],
+    "fb_ac_gae": [_vp, _vp, _vp, _i, _i, _d, _d, _vp, _vp, _vp],
+    "fb_qnet_ac_train_step": [_vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "fb_ac_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "fb_ac_rollout_step": [_vp, _vp, _vp, _vp, _i, _u64, _u64, _i, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],
@@ -145,6 +156,12 @@ class StepBuffers(C.Structure):
     """fb_step_buffers (include/fbdqn.h)"""
     _fields_ = [(n, C.c_void_p) for n in ("nib", "actions", "frame_bits", "reward", "terminal", "score", "idx", "s", "s2", "a", "t",
                                            "r", "loss", "flat_grad", "isw", "isw32", "abs_err")]
+
+
+class AcRolloutBuffers(C.Structure):
+    """fb_ac_rollout_buffers (include/fbdqn.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("nib", "actions", "frame_bits", "reward", "terminal", "score", "value", "logp")] + [("slots", C.c_int)]
+
 
 _lib = None
 

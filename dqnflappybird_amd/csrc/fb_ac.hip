@@ -1,0 +1,325 @@
+// fb_ac.hip -- advantage actor-critic (A2C) on the batched envs: the kernels of an FB_ARCH_AC net and the fb_ac_* entry points, as a code
+// object of their own (fb_qnet.hip routes to the launchers below and gets no kernel: a kernel added to ITS code object moves the others).
+// include/fbdqn.h pins the semantics.  Head parameters in the dueling layout, read raw: V = h . W_v + b_v, logits = h . W_pi + b_pi.
+//   ac_head_kernel    acting: logits, V, the sampled (or greedy) action and its log-probability; one wave per state
+//   ac_gae_kernel     the advantage scan; one thread per env, t = T-1 .. 0
+//   ac_loss_kernel    training, launch 1 of 2: per sample logits / V, the loss terms, dz, dV, the dhf row and the activation row
+//   ac_grad_kernel    training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_v, W_pi; workgroup 0: b_v, b_pi, the loss, Adam's tick
+// Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
+#include "fb_common.h"
+#include <math.h>
+#include <type_traits>
+
+namespace {
+#include "fb_head.h"
+
+constexpr int AC_MAXB = 256;         // the train step's batch limit (fb_qnet.hip MAXTB)
+
+// the fc1 activations of units j0 .. j0 + 3 of state smp from the partial sums hf[ks][stot][FC]: head_one_t's loads, sums and order
+__device__ __forceinline__ void ac_units4(const float *__restrict__ hf, int stot, int nks, int FC, const float *__restrict__ P, int bf1, int smp, int j0,
+                                          float (&x4)[4]) {
+    float4 t[FC1_KS];
+#pragma unroll
+    for (int ks = 0; ks < FC1_KS; ks++)
+        t[ks] = sel4(ks < nks, *reinterpret_cast<const float4 *>(hf + ((size_t)(ks < nks ? ks : 0) * stot + smp) * FC + j0));
+    const float4 bv = *reinterpret_cast<const float4 *>(P + bf1 + j0);
+    float4 v = t[0];
+#pragma unroll
+    for (int ks = 1; ks < FC1_KS; ks++) { v.x += t[ks].x; v.y += t[ks].y; v.z += t[ks].z; v.w += t[ks].w; }
+    x4[0] = fmaxf(v.x + bv.x, 0.f); x4[1] = fmaxf(v.y + bv.y, 0.f); x4[2] = fmaxf(v.z + bv.z, 0.f); x4[3] = fmaxf(v.w + bv.w, 0.f);
+}
+
+// logits z[0 .. A) and V of state smp on every lane of the wave (xor butterfly: the same bits everywhere).  The logits are formed exactly
+// as head_one_t forms the plain head's outputs over W_pi / b_pi -- a lane takes 4 consecutive units per round, fmaf in unit order, then
+// the butterfly, then the bias -- so fb_qnet_forward on an AC net returns these very bits.  No load under a branch: columns a >= A read
+// column 0 and are never used.
+template <int AT>
+__device__ __forceinline__ void ac_row(const float *__restrict__ hf, int stot, int nks, int FC, int A, const NetOff &off, const float *__restrict__ P,
+                                       int smp, int lane, float (&z)[AT], float &V) {
+    float acc[AT + 1], bq[AT];
+#pragma unroll
+    for (int a = 0; a <= AT; a++) acc[a] = 0.f;
+#pragma unroll
+    for (int a = 0; a < AT; a++) bq[a] = P[off.bq + (a < A ? a : 0)];
+    const float bv = P[off.bv];
+    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
+        float x4[4], w[4][AT], wv[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+#pragma unroll
+            for (int a = 0; a < AT; a++) w[e][a] = P[off.wq + (j0 + e) * A + (a < A ? a : 0)];
+            wv[e] = P[off.wv + j0 + e];
+        }
+        ac_units4(hf, stot, nks, FC, P, off.bf1, smp, j0, x4);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+#pragma unroll
+            for (int a = 0; a < AT; a++) acc[a] = fmaf(x4[e], w[e][a], acc[a]);
+            acc[AT] = fmaf(x4[e], wv[e], acc[AT]);
+        }
+    }
+#pragma unroll
+    for (int a = 0; a <= AT; a++)
+        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o);
+#pragma unroll
+    for (int a = 0; a < AT; a++) z[a] = a < A ? acc[a] + bq[a] : 0.f;
+    V = acc[AT] + bv;
+}
+
+// softmax of the A logits in float32, ascending c (include/fbdqn.h): p, log p, the maximum m and s = sum_c exp(z_c - m)
+template <int AT>
+__device__ __forceinline__ void ac_softmax(const float (&z)[AT], int A, float (&p)[AT], float (&lp)[AT], float &m, float &s) {
+    m = z[0];
+#pragma unroll
+    for (int c = 1; c < AT; c++) m = c < A ? fmaxf(m, z[c]) : m;
+    float e[AT];
+    s = 0.f;
+#pragma unroll
+    for (int c = 0; c < AT; c++) { e[c] = c < A ? expf(z[c] - m) : 0.f; s += e[c]; }
+    const float lse = m + logf(s);
+#pragma unroll
+    for (int c = 0; c < AT; c++) { p[c] = e[c] / s; lp[c] = z[c] - lse; }
+}
+
+template <int AT>
+__global__ __launch_bounds__(256) void ac_head_kernel(AcHeadArgs H) {
+    const int lane = threadIdx.x & 63, smp = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (smp >= H.rows) return;                                   // (wave-uniform)
+    const int A = AT == MAXA ? H.A : AT;
+    float z[AT], V;
+    ac_row<AT>(H.hf, H.stot, H.nks, H.FC, A, H.off, H.P, smp, lane, z, V);
+    if (lane != 0) return;
+    H.value[smp] = V;
+    if (H.logits) {
+#pragma unroll
+        for (int c = 0; c < AT; c++) if (c < A) H.logits[(size_t)smp * A + c] = z[c];
+    }
+    if (!H.actions) return;
+    float p[AT], lp[AT], m, s;
+    ac_softmax<AT>(z, A, p, lp, m, s);
+    int act = 0;
+    if (H.greedy) {                                              // first maximum
+#pragma unroll
+        for (int c = 1; c < AT; c++) if (c < A && z[c] > z[act]) act = c;
+    } else {
+        const fb_u4 o = fb_philox(H.seed_lo, H.seed_hi, (uint32_t)smp, H.step_lo, FB_STREAM_POLICY, H.step_hi);
+        const float u = (float)(o.x >> 8) * (1.0f / 16777216.0f);
+        float cum = 0.f;
+        bool found = false;
+        act = A - 1;
+#pragma unroll
+        for (int c = 0; c < AT; c++) {
+            cum += p[c];
+            if (c < A && !found && u < cum) { act = c; found = true; }
+        }
+    }
+    H.actions[smp] = (uint8_t)act;
+    if (H.logp) {
+        float l = lp[0];
+#pragma unroll
+        for (int c = 1; c < AT; c++) l = c == act ? lp[c] : l;
+        H.logp[smp] = l;
+    }
+}
+
+// ---- generalised advantage estimation, one thread per env: every load and store of a time slot is contiguous across the envs.
+// Everything in double, in the order include/fbdqn.h pins (no contraction: the build has -ffp-contract=off).
+__global__ __launch_bounds__(256) void ac_gae_kernel(const float *__restrict__ rew, const uint8_t *__restrict__ term, const float *__restrict__ val,
+                                                     int T, int N, double gamma, double gl, float *__restrict__ adv, float *__restrict__ ret) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= N) return;
+    double A = 0.0, vn = (double)val[(size_t)T * N + e];
+    for (int t = T - 1; t >= 0; t--) {
+        const size_t k = (size_t)t * N + e;
+        const float rf = rew[k];
+        const bool nd = term[k] == 0;
+        const double v = (double)val[k];
+        const double r = rf == 0.1f ? 0.1 : (double)rf;
+        const double x = nd ? gamma * vn : 0.0;
+        const double d = (r + x) - v;
+        A = d + (nd ? gl * A : 0.0);
+        adv[k] = (float)A;
+        ret[k] = (float)(A + v);
+        vn = v;
+    }
+}
+
+// ---- training, launch 1 of 2: one wave per sample (c51_loss_kernel's grid).  dl[b][16]: dz_c at c < 8, dV at 8, the loss terms
+// L_pi, L_v, H at 9 .. 11.  Every lane holds the same logits, so the softmax, the loss and dz need no further exchange; the dhf and xs rows
+// are written four units per lane.
+template <int AT>
+__global__ __launch_bounds__(256) void ac_loss_kernel(AcLossArgs L) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= L.B) return;                                        // (wave-uniform)
+    const int A = AT == MAXA ? L.A : AT, FC = L.FC;
+    const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;  // (an action past the head reads the last one: stays in bounds)
+    const float adv = L.adv[b], ret = L.ret[b];
+    float z[AT], V, p[AT], lp[AT], m, s;
+    ac_row<AT>(L.hf, L.stot, L.nks, FC, A, L.off, L.P, b, lane, z, V);
+    ac_softmax<AT>(z, A, p, lp, m, s);
+    float H = 0.f, lpa = lp[0];
+#pragma unroll
+    for (int c = 0; c < AT; c++) { H -= c < A ? p[c] * lp[c] : 0.f; lpa = c == ab ? lp[c] : lpa; }
+    const float dv = V - ret;
+    float dz[AT];
+#pragma unroll
+    for (int c = 0; c < AT; c++)
+        dz[c] = c < A ? (adv * (p[c] - (c == ab ? 1.f : 0.f)) + L.ce * p[c] * (lp[c] + H)) / L.nt : 0.f;
+    const float dV = (2.f * L.cv * dv) / L.nt;
+    float o = lane == 8 ? dV : lane == 9 ? -adv * lpa : lane == 10 ? dv * dv : lane == 11 ? H : 0.f;
+#pragma unroll
+    for (int c = 0; c < AT; c++) o = lane == c ? dz[c] : o;
+    if (lane < 16) L.dl[(size_t)b * 16 + lane] = o;
+    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
+        float x4[4], w[4][AT], wv[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+#pragma unroll
+            for (int a = 0; a < AT; a++) w[e][a] = L.P[L.off.wq + (j0 + e) * A + (a < A ? a : 0)];
+            wv[e] = L.P[L.off.wv + j0 + e];
+        }
+        ac_units4(L.hf, L.stot, L.nks, FC, L.P, L.off.bf1, b, j0, x4);
+        float d4[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            float dh = dV * wv[e];
+#pragma unroll
+            for (int a = 0; a < AT; a++) dh = fmaf(dz[a], w[e][a], dh);      // (dz of a >= A is 0)
+            d4[e] = x4[e] > 0.f ? dh : 0.f;
+        }
+        *reinterpret_cast<float4 *>(L.dhf + (size_t)b * FC + j0) = make_float4(d4[0], d4[1], d4[2], d4[3]);
+        *reinterpret_cast<float4 *>(L.xs + (size_t)b * FC + j0) = make_float4(x4[0], x4[1], x4[2], x4[3]);
+    }
+}
+
+// ---- training, launch 2 of 2: one workgroup per 16 fc1 units (c51_grad_kernel's grid): b_fc1's gradient and the tile's maximum |dhf|
+// (fc1_bwd_big_kernel's pre-scale), then thread (unit jl, column c) walks the samples in order: c < A is W_pi's column c, c = 8 is W_v.
+// Workgroup 0 also sums b_pi, b_v and the three loss terms the same way, forms the four loss numbers and ticks Adam.
+__global__ __launch_bounds__(256) void ac_grad_kernel(AcGradArgs L) {
+    __shared__ float dlt[AC_MAXB * 16];
+    __shared__ float xt[AC_MAXB * 16];
+    __shared__ float part[16][16];
+    __shared__ float wmax[4];
+    __shared__ float lsum[3];
+    const int tid = threadIdx.x, B = L.B, FC = L.FC, A = L.A, j00 = blockIdx.x * 16;
+    for (int k = tid; k < B * 16; k += 256) { dlt[k] = L.dl[k]; xt[k] = L.xs[(size_t)(k >> 4) * FC + j00 + (k & 15)]; }
+    const int jl = tid & 15, bg = tid >> 4;
+    float sm = 0.f, mx = 0.f;
+    for (int b = bg; b < B; b += 16) { const float d = L.dhf[(size_t)b * FC + j00 + jl]; sm += d; mx = fmaxf(mx, fabsf(d)); }
+    part[bg][jl] = sm;
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) L.gmax[blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (bg == 0) {
+        float v = part[0][jl];
+#pragma unroll
+        for (int q = 1; q < 16; q++) v += part[q][jl];
+        L.grad[L.off.bf1 + j00 + jl] = v;
+    }
+    const int c = bg, cc = c < A || c == 8 ? c : 0;              // (idle columns walk column 0 and store nothing)
+    float acc = 0.f, gb = 0.f;
+    for (int b = 0; b < B; b++) {
+        const float w = dlt[b * 16 + cc];
+        gb += w;
+        acc = fmaf(xt[b * 16 + jl], w, acc);
+    }
+    if (c < A) L.grad[L.off.wq + (size_t)(j00 + jl) * A + c] = acc;
+    if (c == 8) L.grad[L.off.wv + j00 + jl] = acc;
+    if (blockIdx.x != 0) return;
+    if (jl == 0 && c < A) L.grad[L.off.bq + c] = gb;
+    if (jl == 0 && c == 8) L.grad[L.off.bv] = gb;
+    if (jl == 1 && c >= 9 && c < 12) {                           // (three otherwise idle threads: the loss terms, samples in order)
+        float t = 0.f;
+        for (int b = 0; b < B; b++) t += dlt[b * 16 + c];
+        lsum[c - 9] = t / L.nt;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        L.loss[1] = lsum[0]; L.loss[2] = lsum[1]; L.loss[3] = lsum[2];
+        L.loss[0] = (lsum[0] + L.cv * lsum[1]) - L.ce * lsum[2];
+        FbAdamHead &ad = *L.adam;
+        if (L.tick && ad.ticks == ad.applies) {                  // (as c51_grad_kernel)
+            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
+            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
+            ad.ticks += 1;
+        }
+    }
+}
+
+template <class F> void with_actions(int A, F f) {
+    if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
+}
+}  // namespace
+
+void fb_ac_launch_head(hipStream_t st, const void *args) {
+    AcHeadArgs H;
+    memcpy(&H, args, sizeof(H));
+    with_actions(H.A, [&](auto a) { hipLaunchKernelGGL(ac_head_kernel<decltype(a)::value>, dim3((H.rows + 3) / 4), dim3(256), 0, st, H); });
+}
+
+void fb_ac_launch_loss(hipStream_t st, const void *args) {
+    AcLossArgs L;
+    memcpy(&L, args, sizeof(L));
+    with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(ac_loss_kernel<decltype(a)::value>, dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
+}
+
+void fb_ac_launch_grad(hipStream_t st, const void *args) {
+    AcGradArgs L;
+    memcpy(&L, args, sizeof(L));
+    hipLaunchKernelGGL(ac_grad_kernel, dim3(L.FC / 16), dim3(256), 0, st, L);
+}
+
+extern "C" int fb_ac_gae(const float *reward, const uint8_t *terminal, const float *value, int T, int N, double gamma, double lambda, float *adv,
+                         float *ret, void *stream) {
+    FB_REQUIRE(reward && terminal && value && adv && ret, "fb_ac_gae: NULL argument");
+    FB_REQUIRE(T >= 1 && N >= 1 && ((long long)T + 1) * N < (1LL << 31), "fb_ac_gae: T = %d, N = %d out of range", T, N);
+    FB_REQUIRE(isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "fb_ac_gae: gamma must be in [0, 1] (got %g)", gamma);
+    FB_REQUIRE(isfinite(lambda) && lambda >= 0.0 && lambda <= 1.0, "fb_ac_gae: lambda must be in [0, 1] (got %g)", lambda);
+    hipLaunchKernelGGL(ac_gae_kernel, dim3((N + 255) / 256), dim3(256), 0, fb_stream(stream), reward, terminal, value, T, N, gamma, gamma * lambda, adv, ret);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+extern "C" int fb_ac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *adv, const float *ret,
+                                       int64_t n_total, uint8_t *a_out, float *loss, float *flat_grad, void *stream) {
+    FB_REQUIRE(replay && net && idx && adv && ret && a_out && loss, "fb_ac_train_from_replay: NULL argument");
+    FB_REQUIRE(fb_qnet_is_ac(net), "fb_ac_train_from_replay: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(!fb_replay_is_prioritized(replay), "fb_ac_train_from_replay: the rollout is read from a uniform memory only");
+    int n = 1; double g = 0.0;
+    int rc = fb_replay_get_n_step(replay, &n, &g);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(n == 1, "fb_ac_train_from_replay: the memory has a %d-step view; the rollout is read at n-step 1 only", n);
+    rc = fb_qnet_ac_check_train(net, batch, n_total, "fb_ac_train_from_replay");
+    if (rc != FB_OK) return rc;
+    float *r_scr; uint8_t *t_scr;
+    fb_qnet_ac_scratch(net, &r_scr, &t_scr);
+    FbRingSrc ring;
+    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_scr, t_scr, &ring);
+    if (rc != FB_OK) return rc;
+    if (batch >= 256) {                          // (W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
+        rc = fb_qnet_refresh_planes(net, stream);
+        if (rc != FB_OK) return rc;
+    }
+    return fb_qnet_ac_train_ring(net, batch, &ring, adv, ret, n_total, loss, flat_grad, stream);
+}
+
+extern "C" int fb_ac_rollout_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_ac_rollout_buffers *b, int n_envs, uint64_t seed,
+                                  uint64_t step, int slot, void *stream) {
+    FB_REQUIRE(env && replay && net && b, "fb_ac_rollout_step: NULL handle");
+    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && b->value && b->logp, "fb_ac_rollout_step: NULL buffer");
+    FB_REQUIRE(fb_qnet_is_ac(net), "fb_ac_rollout_step: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(!fb_replay_is_prioritized(replay), "fb_ac_rollout_step: the rollout is stored in a uniform memory only");
+    FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_ac_rollout_step: n_envs %d does not match the env (%d) / replay (%d) handles",
+               n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
+    FB_REQUIRE(n_envs <= fb_qnet_max_rows(net), "fb_ac_rollout_step: %d envs exceed 3*max_batch of the net", n_envs);
+    FB_REQUIRE(slot >= 0 && slot < b->slots, "fb_ac_rollout_step: slot %d outside the buffers' %d rows", slot, b->slots);
+    // (every argument check of the three calls below is made above -- handles, buffers, the net's kind and row count, the env counts --
+    // so nothing is launched and no push is counted before a refusal)
+    const size_t o = (size_t)slot * n_envs;
+    int rc = fb_qnet_act_policy_nib(net, b->nib, n_envs, seed, step, 0, b->actions, b->value + o, b->logp + o, nullptr, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward + o, b->terminal + o, b->score, stream);
+    if (rc != FB_OK) return rc;
+    return fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward + o, b->terminal + o, stream);
+}

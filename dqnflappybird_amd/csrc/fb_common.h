@@ -83,6 +83,7 @@ __device__ __forceinline__ void fb_flag_wait(const unsigned long long *flag, uns
 #define FB_STREAM_EVAL 5u     // epsilon-greedy of fb_eval_run, counter = (env id, eval step): never the training acting stream
 #define FB_STREAM_NOISE 6u    // noisy nets' factorised noise, counter = (element, step_lo, 6, 2 step_hi + net) (fb_qnet_reset_noise)
 #define FB_STREAM_ENV_NOISE 7u  // per-env acting noise of noisy nets, counter = (env * nz + element, step_lo, 7, step_hi) (fb_qnet_act_nib_env_noise)
+#define FB_STREAM_POLICY 8u   // the policy's action draw of an actor-critic net, counter = (row, step_lo, 8, step_hi) (fb_qnet_act_policy_nib)
 
 struct fb_u4 { uint32_t x, y, z, w; };
 
@@ -234,6 +235,31 @@ int fb_qnet_acting_noise(fb_qnet_t h);
 int fb_qnet_check_env_noise(fb_qnet_t h, int n, const char *who);
 int fb_qnet_act_nib_env_noise_keep(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
                                    uint8_t *actions, float *q, void *stream);
+// ---- advantage actor-critic (FB_ARCH_AC): the kernels live in fb_ac.hip, a code object of their own; fb_qnet.hip fills these structs and
+// hands them to the launchers as bytes.  P: the net's parameters (or the fused acting forward's copy, hp_act - off.bf1); off: the dueling
+// layout, wv / bv = W_v b_v, wq / bq = W_pi b_pi
+struct FbAdamHead { float b1pow, b2pow, alpha, lr, b1, b2, eps, pad; int ticks, applies; };      // the front of fb_qnet.hip's AdamDev
+struct AcHeadArgs {
+    const float *hf, *P; int stot, nks, FC, A, rows; NetOff off;
+    float *logits, *value, *logp; uint8_t *actions;              // logits f32[rows][A] or NULL; logp or NULL; actions NULL: no action (forward_ac)
+    int greedy; uint32_t seed_lo, seed_hi, step_lo, step_hi;
+};
+struct AcLossArgs {
+    const float *hf, *P; int stot, nks, FC, A, B; NetOff off;
+    const uint8_t *act; const float *adv, *ret; float nt, cv, ce;      // nt = (float)n_total
+    float *dl, *xs, *dhf;                                        // dl f32[B][16]: dz, dV, the loss terms (fb_ac.hip)
+};
+struct AcGradArgs { int B, FC, A; NetOff off; const float *dl, *xs, *dhf; float nt, cv, ce; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; };
+void fb_ac_launch_head(hipStream_t st, const void *args);
+void fb_ac_launch_loss(hipStream_t st, const void *args);
+void fb_ac_launch_grad(hipStream_t st, const void *args);
+int fb_qnet_is_ac(fb_qnet_t h);               // 1: an actor-critic net (fb_qnet_create_ac)
+// the checks of the two AC training calls (batch, n_total), `who` in the message; the scratch r / t rows the ring-fed trunk fills beside
+// a_out; the ring-fed AC train step behind fb_ac_train_from_replay's checks
+int fb_qnet_ac_check_train(fb_qnet_t h, int batch, int64_t n_total, const char *who);
+void fb_qnet_ac_scratch(fb_qnet_t h, float **r, uint8_t **t);
+int fb_qnet_ac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const float *adv, const float *ret, int64_t n_total, float *loss,
+                          float *flat_grad, void *stream);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);

@@ -4026,7 +4026,18 @@ struct fb_qnet {
     float max_grad_norm;
     double *clip_part;
     float *clip_out;
+    // an actor-critic net (FB_ARCH_AC, fb_qnet_create_ac; kernels: fb_ac.hip): (c_v, c_e) of fb_qnet_set_ac; ac_dl: the loss kernel's
+    // per-sample row [max_batch][16]; ac_xs: fc1 activations of s [max_batch][FC]; ac_r / ac_t: the rows the ring-fed trunk fills beside the actions
+    float ac_cv, ac_ce;
+    float *ac_dl, *ac_xs, *ac_r;
+    uint8_t *ac_t;
 };
+// every field ac_grad_kernel touches through FbAdamHead sits where AdamDev has it
+static_assert(offsetof(AdamDev, b1pow) == offsetof(FbAdamHead, b1pow) && offsetof(AdamDev, b2pow) == offsetof(FbAdamHead, b2pow) &&
+              offsetof(AdamDev, alpha) == offsetof(FbAdamHead, alpha) && offsetof(AdamDev, lr) == offsetof(FbAdamHead, lr) &&
+              offsetof(AdamDev, b1) == offsetof(FbAdamHead, b1) && offsetof(AdamDev, b2) == offsetof(FbAdamHead, b2) &&
+              offsetof(AdamDev, ticks) == offsetof(FbAdamHead, ticks) && offsetof(AdamDev, applies) == offsetof(FbAdamHead, applies),
+              "fb_ac.hip's view of AdamDev");
 
 static NetOff make_off(int FC, int A, int dueling) {      // A: the head's columns (C51: actions x atoms)
     NetOff o;
@@ -4048,6 +4059,8 @@ static NetOff make_off_c51d(int FC, int A, int N) {
 // a folded head: a dueling C51 or dueling QR net (the same layout and fold)
 static bool is_c51d(const fb_qnet *h) { return h->arch == FB_ARCH_C51_DUELING || h->arch == FB_ARCH_QR_DUELING; }
 static bool is_qr(const fb_qnet *h) { return h->arch == FB_ARCH_QR || h->arch == FB_ARCH_QR_DUELING; }
+// an actor-critic net: the dueling layout read raw (W_v b_v: V; W_pi b_pi at wq / bq: the logits, which the plain head reads as "Q")
+static bool is_ac(const fb_qnet *h) { return h->arch == FB_ARCH_AC; }
 // the parameters the C51 kernels read, with h->hoff, for the net whose parameters are `params` (a virtual base for a dueling C51 net:
 // hoff.bf1 lands on heff[w][0], as the acting forward's hp_act copy is read)
 static const float *head_base(const fb_qnet *h, const float *params) {
@@ -4088,6 +4101,7 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
     FB_REQUIRE(arch != FB_ARCH_C51, "fb_qnet_create: a C51 net is made by fb_qnet_create_c51 (it needs the support)");
     FB_REQUIRE(arch != FB_ARCH_C51_DUELING, "fb_qnet_create: a dueling C51 net is made by fb_qnet_create_c51_dueling (it needs the support)");
     FB_REQUIRE(arch != FB_ARCH_QR && arch != FB_ARCH_QR_DUELING, "fb_qnet_create: a QR net is made by fb_qnet_create_qr (it needs N and kappa)");
+    FB_REQUIRE(arch != FB_ARCH_AC, "fb_qnet_create: an actor-critic net is made by fb_qnet_create_ac");
     FB_REQUIRE(arch == FB_ARCH_PLAIN || arch == FB_ARCH_DUELING, "fb_qnet_create: arch must be 0 or 1");
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create: fc_width must be a multiple of 128");
     FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create: n_actions must be in 1..%d", MAXA);
@@ -4143,6 +4157,15 @@ extern "C" int fb_qnet_create_qr(int arch, int fc_width, int n_actions, int n_qu
     return rc;
 }
 
+extern "C" int fb_qnet_create_ac(int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
+    const char *fn = "fb_qnet_create_ac";
+    FB_REQUIRE(out, "%s: out is NULL", fn);
+    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
+    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "%s: n_actions must be in 1..%d", fn, MAXA);
+    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
+    return qnet_create(FB_ARCH_AC, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
+}
+
 // the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
 static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, float sigma0) {
     NoisyNet nn;
@@ -4163,9 +4186,10 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     fb_qnet *h = new fb_qnet();
     memset(h, 0, sizeof(*h));
     h->md = MdPar{0.03f, 0.9f, -1.f};            // Munchausen-DQN, the paper's values (read by FB_ALGO_MDQN / _PER on a scalar net alone)
+    h->ac_cv = 0.5f; h->ac_ce = 0.01f;           // A2C's value and entropy coefficients (read on an actor-critic net alone)
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
     h->off = is_c51d(h) ? make_off_c51d(fc_width, n_actions, sup.N)
-                        : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING);
+                        : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING || arch == FB_ARCH_AC);
     h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
     h->n = h->off.n;
     h->noisy = sigma0 >= 0.f;                    // (fb_qnet_create_c51_noisy: C51 archs, finite sigma0 >= 0)
@@ -4207,6 +4231,10 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     alloc((void **)&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc((void **)&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
     if (sup.N) { alloc((void **)&h->c51_dl, Bm * 64 * 4); alloc((void **)&h->c51_xs, Bm * fc_width * 4); alloc((void **)&h->c51_lt, Bm * 4); }
     if (is_c51d(h)) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
+    if (is_ac(h)) {
+        const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
+        alloc((void **)&h->ac_dl, Bt * 16 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4); alloc((void **)&h->ac_r, Bt * 4); alloc((void **)&h->ac_t, Bt);
+    }
     alloc((void **)&h->clip_part, sizeof(double) * 256); alloc((void **)&h->clip_out, sizeof(float) * 2);
     if (e == hipSuccess) { const float one = 1.f; e = hipMemcpy(h->clip_out + 1, &one, sizeof(one), hipMemcpyHostToDevice); }      // (no clip yet: norm 0, c 1)
     if (e != hipSuccess) {
@@ -4228,7 +4256,7 @@ extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
                     h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
                     h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1],
-                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out};
+                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out, h->ac_dl, h->ac_xs, h->ac_r, h->ac_t};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -4323,12 +4351,14 @@ extern "C" int fb_qnet_overflow_count(fb_qnet_t h, int reset, int64_t *count_hos
 
 extern "C" int fb_qnet_set_inference_dtype(fb_qnet_t h, int dtype) {
     FB_REQUIRE(h && (dtype == FB_DTYPE_F32 || dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: dtype must be FB_DTYPE_F32 or FB_DTYPE_BF16");
+    FB_REQUIRE(!(is_ac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: an actor-critic net computes in FB_DTYPE_F32 only");
     h->nsplit = dtype == FB_DTYPE_BF16 ? 1 : 3;
     return FB_OK;
 }
 
 extern "C" int fb_qnet_set_train_dtype(fb_qnet_t h, int dtype) {
     FB_REQUIRE(h && (dtype == FB_DTYPE_F32 || dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: dtype must be FB_DTYPE_F32 or FB_DTYPE_BF16");
+    FB_REQUIRE(!(is_ac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: an actor-critic net trains in FB_DTYPE_F32 only");
     h->nsplit_train = dtype == FB_DTYPE_BF16 ? 1 : 3;
     return FB_OK;
 }
@@ -4346,7 +4376,7 @@ static void resplit_now(fb_qnet *h, int which, hipStream_t st) {
 extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *stream) {
     FB_REQUIRE(h && (which == 0 || which == 1), "fb_qnet_init_params: bad argument");
     hipLaunchKernelGGL(init_params_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, fb_stream(stream),
-                       master(h, which), h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING || is_c51d(h), (uint32_t)seed,
+                       master(h, which), h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING || is_c51d(h) || is_ac(h), (uint32_t)seed,
                        (uint32_t)(seed >> 32));
     if (is_c51d(h)) {                            // (init_params_kernel's dueling bias is one entry: b_v has N)
         const float b = 0.01f;
@@ -4439,6 +4469,11 @@ struct Plan {
     bool any_rows;
     float *probs;                            // C51 forward plans: the head also writes the probabilities f32[row][A][N] (fb_qnet_forward_dist)
     bool no_head;                            // C51 forward plans: conv1 .. fc1 only (fb_qnet_act_nib_env_noise launches its own head)
+    // an actor-critic net.  Forward plans with ac_value set: the policy head (fb_ac.hip) instead of the plain one -- value f32[rows], logits
+    // f32[rows][A] / logp f32[rows] or NULL, p.actions NULL: no action; ac_greedy: the first maximum instead of a draw.  Train plans: the
+    // advantages, the returns and n_total (p.r / p.isw / p.gamma stay unset)
+    float *ac_value, *ac_logits, *ac_logp; int ac_greedy;
+    const float *ac_adv, *ac_ret; float ac_nt;
 };
 
 // A runtime value as a template argument: f is a generic lambda and gets a tag whose ::value is a constant expression, so that a kernel
@@ -4458,7 +4493,8 @@ template <class T> static void put_seed_words(T &c, uint64_t seed, uint64_t step
 struct PlanCtx {
     int only; hipStream_t st;                // `only` < 0: the whole plan; else the launches of that KernelId alone
     int maxc, total;                         // states of the largest slice / of all slices
-    bool big, trunk, fused, c51;
+    bool big, trunk, fused, c51, ac;
+    bool state_trunk;                        // gathered states through conv1_pool + conv23_t with planes, then large_pass's fc1 alone (plan_ctx)
     int nsp, stot; size_t pl1, pl2;          // stot: rows of the workspace; pl1 / pl2: its plane pitch after conv1 / conv2, conv3
 };
 static bool runs(const PlanCtx &c, int id) { return c.only < 0 || c.only == id; }      // the launches of KernelId `id` are part of this run
@@ -4479,6 +4515,11 @@ static PlanCtx plan_ctx(const fb_qnet *h, const Plan &p, int only, hipStream_t s
     // (conv23_sp_kernel<., 5, true>), five states per workgroup.  Its fc1 partial sums are in hf_act, its head parameters in hp_act
     c.fused = c.big && p.nib && !p.train && !c.trunk && p.ns == 1;
     c.c51 = h->sup.N > 0;
+    c.ac = is_ac(h);
+    // an actor-critic train step on 256 GATHERED states: the per-state conv trunk of the smaller batches, writing conv3's planes, then
+    // fc1_sp -- the arithmetic of the ring-fed form (ring_trunk), so that the two forms of an A2C chunk agree bit for bit at every size
+    // (the large-batch trunk sums conv2 / conv3 in another order).  The ring-fed form is the one the A2C loop runs
+    c.state_trunk = c.ac && p.train && c.big && !c.trunk;
     return c;
 }
 
@@ -4533,7 +4574,7 @@ static int large_pass(fb_qnet *h, const Plan &p, const PlanCtx &c, int *z) {
     if (z1 - z0 > 1) { side.per = s0.count; side.st1 = p.sl.s[z0 + 1].states; side.st2 = z1 - z0 > 2 ? p.sl.s[z0 + 2].states : p.sl.s[z0 + 1].states; }
     if (p.train) { side.p1 = h->p1; side.amax = h->amax; }
     const int t1p = (rows * 100 + 7) / 8, gsp = min(256, (t1p + C1_WAVES - 1) / C1_WAVES);      // one 12-wave workgroup per CU, the waves stride over the tiles
-    if (!c.trunk && !c.fused && runs(c, K_CONV1))
+    if (!c.trunk && !c.state_trunk && !c.fused && runs(c, K_CONV1))
         hipLaunchKernelGGL(conv1_sp_kernel, dim3(gsp), dim3(64 * C1_WAVES), 0, c.st, sl, (const uint8_t *)h->zeros, h->a1s, c.pl1, c.nsp, h->wsp[which], h->FC, pver, (const unsigned *)wver, side, &h->adam->ovf);
     C23Args c23{h->a1s + (size_t)row0 * 3200, c.pl1, h->wsp[which] + WSP_W2, s0.params + OFF_B2, s0.params + OFF_B3, h->a3s + (size_t)row0 * 1600, c.pl2, rows, pver, wver, c.only < 0 ? &h->adam->wverc[which] : nullptr,
                 p.train ? h->h2 + (size_t)row0 * 1600 : nullptr, p.train ? h->h3 + (size_t)row0 * 1600 : nullptr,
@@ -4564,7 +4605,7 @@ static int large_pass(fb_qnet *h, const Plan &p, const PlanCtx &c, int *z) {
     // workgroup says when it has been placed -- the train chain on the other stream starts then (fb_sampler.h)
     if (c.fused && p.split && c.only < 0 && gc.x > 256 && gc.x % 256 != 0) { c23.round_flag = &p.split->f->last_round; c23.round_val = p.split->seq; c23.round_blk = (int)(gc.x / 256) * 256; }
     with_nsp(c.nsp, [&](auto ns) {
-        if (!c.trunk && runs(c, K_CONV2))            // fused: conv1 .. conv3; else conv3 rides in conv2's launch
+        if (!c.trunk && !c.state_trunk && runs(c, K_CONV2))      // fused: conv1 .. conv3; else conv3 rides in conv2's launch
             with_bool(c.fused, [&](auto fu) { hipLaunchKernelGGL((conv23_sp_kernel<decltype(ns)::value, 5, decltype(fu)::value>), gc, dim3(512), 0, c.st, c23); });
         if (runs(c, K_FC1)) hipLaunchKernelGGL(fc1_sp_kernel<decltype(ns)::value>, gf, dim3(256), 0, c.st, af);
     });
@@ -4579,19 +4620,23 @@ static int large_pass(fb_qnet *h, const Plan &p, const PlanCtx &c, int *z) {
 
 // the small-batch forward: conv1_pool -> conv23_t (behind the ring-fed trunk neither) -> fc1_fk
 // small batches: the whole K per workgroup (fc1_fk_kernel), which lets training skip the head and loss launches
+// planes: conv3's output as planes too (fc1_sp_kernel follows: a gathered actor-critic batch of 256, run_plan)
+static void small_trunk(fb_qnet *h, const Plan &p, const PlanCtx &c, bool planes) {
+    SplitJob job;
+    C23T c23t = trunk_args(h, p, c, &job);
+    if (planes) { c23t.a3s = h->a3s; c23t.pl3 = c.pl2; }
+    const int t1 = (c.maxc * 100 + 7) / 8;
+    if (runs(c, K_CONV1))
+        with_bool(p.nib, [&](auto nib) { hipLaunchKernelGGL(conv1_pool_kernel<decltype(nib)::value>, dim3((t1 + 3) / 4, 1, p.ns), dim3(256), 0, c.st, p.sl, h->p1, h->amax, job); });
+    if (runs(c, K_CONV2))                                // (conv3 rides in the same launch)
+        with_nsp(c.nsp, [&](auto ns) { hipLaunchKernelGGL((conv23_t_kernel<decltype(ns)::value, false>), dim3(c.maxc, p.ns), dim3(512), 0, c.st, c23t); });
+}
+
 static void small_forward(fb_qnet *h, const Plan &p, const PlanCtx &c) {
-    if (!c.trunk) {
-        SplitJob job;
-        const C23T c23t = trunk_args(h, p, c, &job);
-        const int t1 = (c.maxc * 100 + 7) / 8;
-        if (runs(c, K_CONV1))
-            with_bool(p.nib, [&](auto nib) { hipLaunchKernelGGL(conv1_pool_kernel<decltype(nib)::value>, dim3((t1 + 3) / 4, 1, p.ns), dim3(256), 0, c.st, p.sl, h->p1, h->amax, job); });
-        if (runs(c, K_CONV2))                                // (conv3 rides in the same launch)
-            with_nsp(c.nsp, [&](auto ns) { hipLaunchKernelGGL((conv23_t_kernel<decltype(ns)::value, false>), dim3(c.maxc, p.ns), dim3(512), 0, c.st, c23t); });
-    }
+    if (!c.trunk) small_trunk(h, p, c, false);
     if (runs(c, K_FC1)) {
         FkArgs fa;
-        fa.sl = p.sl; fa.h3 = h->h3; fa.hf = h->hf; fa.qpart = p.train && !c.c51 ? h->qpart : nullptr; fa.FC = h->FC; fa.A = h->A;      // (C51: the head is the loss launches' own work)
+        fa.sl = p.sl; fa.h3 = h->h3; fa.hf = h->hf; fa.qpart = p.train && !c.c51 && !c.ac ? h->qpart : nullptr; fa.FC = h->FC; fa.A = h->A;      // (C51 / actor-critic: the head is the loss launches' own work)
         fa.dueling = h->arch == FB_ARCH_DUELING; fa.stot = c.stot; fa.off = h->off;
         hipLaunchKernelGGL(fc1_fk_kernel, dim3((c.maxc + 15) / 16, h->FC / 16, p.ns), dim3(512), 0, c.st, fa);
     }
@@ -4620,7 +4665,18 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
             p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params;
         } else launch_dist_head(h, H, c.total, c.st);
     }
-    if (!c.c51 && !(!c.big && p.train) && runs(c, K_HEAD)) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
+    if (c.ac && !p.train && p.ac_value && runs(c, K_HEAD)) {           // an actor-critic net's policy head (fb_ac.hip), a launch of its own
+        AcHeadArgs H;
+        memset(&H, 0, sizeof(H));
+        H.hf = c.fused ? h->hf_act : h->hf; H.P = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;      // (fused: the copy its fc1 launch took)
+        H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A; H.rows = c.total; H.off = h->off;
+        H.logits = p.ac_logits; H.value = p.ac_value; H.logp = p.ac_logp; H.actions = p.actions; H.greedy = p.ac_greedy;
+        put_seed_words(H, p.seed, p.step);
+        fb_ac_launch_head(c.st, &H);
+        return;
+    }
+    // (an actor-critic net without ac_value: the plain head over W_pi b_pi, the logits as "Q"; its train plans: the loss launches' own work)
+    if (!c.c51 && !(p.train && (c.ac || !c.big)) && runs(c, K_HEAD)) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
         HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns;
         HeadCore &C = H.c;
@@ -4637,6 +4693,18 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
 // the per-unit reductions; QR: per-sample targets / quantile Huber loss / dhf, then C51's per-unit reductions
 static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     const int B = p.B, FC = h->FC;
+    if (c.ac) {                                  // actor-critic: per-sample loss / dz / dV / dhf, then the per-unit reductions (fb_ac.hip)
+        AcLossArgs L;
+        memset(&L, 0, sizeof(L));
+        L.hf = h->hf; L.P = h->params[0]; L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B; L.off = h->off;
+        L.act = p.a; L.adv = p.ac_adv; L.ret = p.ac_ret; L.nt = p.ac_nt; L.cv = h->ac_cv; L.ce = h->ac_ce;
+        L.dl = h->ac_dl; L.xs = h->ac_xs; L.dhf = h->dhf;
+        fb_ac_launch_loss(c.st, &L);
+        const AcGradArgs gA{B, FC, h->A, h->off, h->ac_dl, h->ac_xs, h->dhf, p.ac_nt, h->ac_cv, h->ac_ce, p.G, p.loss, h->gmax,
+                            reinterpret_cast<FbAdamHead *>(h->adam), p.tick};
+        fb_ac_launch_grad(c.st, &gA);
+        return;
+    }
     if (!c.c51) {                                // (large batches only: run_plan)
         LossArgs L;
         L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.off = h->off;
@@ -4686,7 +4754,7 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
 // the fc1 backward.  Small scalar batches: head, loss and fc1's gradients in one launch (fc1_bwd2_kernel); else fc1's gradients from dhf
 static void fc1_backward(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     const int B = p.B, FC = h->FC;
-    if (!c.big && !c.c51) {
+    if (!c.big && !c.c51 && !c.ac) {
         const int ndx1 = ((B + 31) / 32) * 50;
         Bw1Args L;
         L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.stot = c.stot; L.n_dx = ndx1; L.off = h->off;
@@ -4796,6 +4864,7 @@ static void reduce_or_adam(fb_qnet *h, const Plan &p, const PlanCtx &c, SlabCoun
 static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
     const PlanCtx c = plan_ctx(h, p, only, st);
     if (c.trunk && runs(c, K_CONV2)) ring_trunk(h, p, c);
+    if (c.state_trunk) small_trunk(h, p, c, true);
     if (c.big) {
         for (int z = 0; z < p.ns;) {
             const int rc = large_pass(h, p, c, &z);
@@ -4807,7 +4876,7 @@ static int run_plan(fb_qnet *h, const Plan &p, int only, hipStream_t st) {
         // exactly one of the launches that tick the Adam step counter -- the QR, C51 and scalar loss, fc1_bwd2_kernel -- is in a
         // plan when only < 0, and p.tick is false whenever only >= 0
         if (p.tick) h->adam_ticked = !p.apply_adam;              // stays pending until fb_qnet_apply_adam consumes it
-        if ((c.c51 || c.big) && runs(c, K_LOSS)) loss_stage(h, p, c);
+        if ((c.c51 || c.ac || c.big) && runs(c, K_LOSS)) loss_stage(h, p, c);
         if (runs(c, K_FC1_BWD)) fc1_backward(h, p, c);
         // data-parallel path: from here on G[CONV_PARAMS ..) -- W_fc1, b_fc1, the head: 91 % of the bytes -- is final; the caller's side
         // stream can start reducing it while the conv backward below still runs (fb_qnet_set_grad_event)
@@ -4876,6 +4945,7 @@ int fb_qnet_num_actions(fb_qnet_t h) { return h ? h->A : 0; }
 int fb_qnet_is_c51(fb_qnet_t h) { return h && h->sup.N > 0 && !is_qr(h); }
 int fb_qnet_is_qr(fb_qnet_t h) { return h && is_qr(h); }
 int fb_qnet_is_dist(fb_qnet_t h) { return h && h->sup.N > 0; }
+int fb_qnet_is_ac(fb_qnet_t h) { return h && is_ac(h); }
 extern "C" int fb_qnet_is_noisy(fb_qnet_t h) { return h && h->noisy ? 1 : 0; }
 
 extern "C" int fb_qnet_reset_noise(fb_qnet_t h, int which, uint64_t seed, uint64_t step, int mode, void *stream) {
@@ -4979,6 +5049,7 @@ extern "C" int fb_qnet_get_support(fb_qnet_t h, int *n_atoms_host, float *v_min_
 extern "C" int fb_qnet_set_munchausen(fb_qnet_t h, float tau, float alpha, float clip_lo) {
     FB_REQUIRE(h, "fb_qnet_set_munchausen: NULL handle");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
+    FB_REQUIRE(!is_ac(h), "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar Q heads only, not an actor-critic net");
     FB_REQUIRE(isfinite(tau) && tau > 0.f, "fb_qnet_set_munchausen: tau must be finite and > 0 (got %g)", (double)tau);
     FB_REQUIRE(alpha >= 0.f && alpha <= 1.f, "fb_qnet_set_munchausen: alpha must be in [0, 1] (got %g)", (double)alpha);
     FB_REQUIRE(isfinite(clip_lo) && clip_lo <= 0.f, "fb_qnet_set_munchausen: the clip l0 must be finite and <= 0 (got %g)", (double)clip_lo);
@@ -4989,6 +5060,7 @@ extern "C" int fb_qnet_set_munchausen(fb_qnet_t h, float tau, float alpha, float
 extern "C" int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha_host, float *clip_lo_host) {
     FB_REQUIRE(h, "fb_qnet_get_munchausen: NULL handle");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
+    FB_REQUIRE(!is_ac(h), "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar Q heads only, not an actor-critic net");
     if (tau_host) *tau_host = h->md.tau;
     if (alpha_host) *alpha_host = h->md.alpha;
     if (clip_lo_host) *clip_lo_host = h->md.clip;
@@ -4998,6 +5070,7 @@ extern "C" int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha
 extern "C" int fb_qnet_set_huber(fb_qnet_t h, float delta) {
     FB_REQUIRE(h, "fb_qnet_set_huber: NULL handle");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
+    FB_REQUIRE(!is_ac(h), "fb_qnet_set_huber: the Huber loss is a setting of the scalar Q heads only, not of an actor-critic net");
     FB_REQUIRE(isfinite(delta) && delta >= 0.f, "fb_qnet_set_huber: delta must be finite and >= 0 (0 = the squared loss; got %g)", (double)delta);
     h->huber = delta;
     return FB_OK;
@@ -5006,6 +5079,7 @@ extern "C" int fb_qnet_set_huber(fb_qnet_t h, float delta) {
 extern "C" int fb_qnet_get_huber(fb_qnet_t h, float *delta_host) {
     FB_REQUIRE(h && delta_host, "fb_qnet_get_huber: NULL argument");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
+    FB_REQUIRE(!is_ac(h), "fb_qnet_get_huber: the Huber loss is a setting of the scalar Q heads only, not of an actor-critic net");
     *delta_host = h->huber;
     return FB_OK;
 }
@@ -5214,6 +5288,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
     FB_REQUIRE(h && a && r && t && loss && (ring || (s && s2)), "fb_qnet_train_step: NULL argument");
     FB_REQUIRE((algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER) || is_mdqn_algo(algo) || algo == FB_ALGO_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
+    FB_REQUIRE(!is_ac(h), "fb_qnet_train_step: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only (got algo %d)", algo);
     {
         const bool c51a = is_c51_algo(algo), qra = is_qr_algo(algo);
         FB_REQUIRE(c51a == (h->sup.N > 0 && !is_qr(h)), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
@@ -5298,6 +5373,91 @@ extern "C" int fb_qnet_train_step(fb_qnet_t h, int algo, int B, const uint8_t *s
     Plan p;
     int rc = train_plan(h, algo, B, s, a, r, s2, t, isw, gamma, loss, abs_err, q_target, flat_grad, &p);
     if (rc != FB_OK) return rc;
+    return run_train(h, p, stream);
+}
+
+// ---- advantage actor-critic (include/fbdqn.h; kernels: fb_ac.hip)
+extern "C" int fb_qnet_set_ac(fb_qnet_t h, float value_coef, float entropy_coef) {
+    FB_REQUIRE(h, "fb_qnet_set_ac: NULL handle");
+    FB_REQUIRE(is_ac(h), "fb_qnet_set_ac: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(isfinite(value_coef) && value_coef >= 0.f, "fb_qnet_set_ac: value_coef must be finite and >= 0 (got %g)", (double)value_coef);
+    FB_REQUIRE(isfinite(entropy_coef) && entropy_coef >= 0.f, "fb_qnet_set_ac: entropy_coef must be finite and >= 0 (got %g)", (double)entropy_coef);
+    h->ac_cv = value_coef; h->ac_ce = entropy_coef;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_ac(fb_qnet_t h, float *value_coef_host, float *entropy_coef_host) {
+    FB_REQUIRE(h, "fb_qnet_get_ac: NULL handle");
+    FB_REQUIRE(is_ac(h), "fb_qnet_get_ac: not an actor-critic net (fb_qnet_create_ac)");
+    if (value_coef_host) *value_coef_host = h->ac_cv;
+    if (entropy_coef_host) *entropy_coef_host = h->ac_ce;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_forward_ac(fb_qnet_t h, const uint8_t *states, int batch, float *logits, float *value, void *stream) {
+    FB_REQUIRE(h && states && logits && value, "fb_qnet_forward_ac: NULL argument");
+    FB_REQUIRE(is_ac(h), "fb_qnet_forward_ac: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(rows_ok(h, batch), "fb_qnet_forward_ac: batch %d exceeds 3*max_batch", batch);
+    Plan p = forward_plan(h, 0, states, batch);
+    p.ac_value = value; p.ac_logits = logits;
+    return run_plan(h, p, -1, fb_stream(stream));
+}
+
+extern "C" int fb_qnet_act_policy_nib(fb_qnet_t h, const uint8_t *nib_states, int n, uint64_t seed, uint64_t step, int greedy, uint8_t *actions,
+                                      float *value, float *logp, float *logits, void *stream) {
+    FB_REQUIRE(h && nib_states && value, "fb_qnet_act_policy_nib: NULL argument");
+    FB_REQUIRE(is_ac(h), "fb_qnet_act_policy_nib: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(actions || !logp, "fb_qnet_act_policy_nib: logp needs actions");
+    FB_REQUIRE(rows_ok(h, n), "fb_qnet_act_policy_nib: n %d exceeds 3*max_batch", n);
+    Plan p = forward_plan(h, 0, nib_states, n);
+    p.nib = true;
+    p.actions = actions; p.seed = seed; p.step = step;
+    p.ac_value = value; p.ac_logits = logits; p.ac_logp = logp; p.ac_greedy = greedy != 0;
+    return run_plan(h, p, -1, fb_stream(stream));
+}
+
+int fb_qnet_ac_check_train(fb_qnet_t h, int B, int64_t n_total, const char *who) {
+    FB_REQUIRE(h && is_ac(h), "%s: not an actor-critic net (fb_qnet_create_ac)", who);
+    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "%s: batch %d exceeds min(max_batch, %d)", who, B, MAXTB);
+    FB_REQUIRE(n_total >= (int64_t)B && n_total <= (int64_t)1 << 40, "%s: n_total %lld must be the whole update's sample count (>= the batch %d)", who, (long long)n_total, B);
+    return FB_OK;
+}
+
+void fb_qnet_ac_scratch(fb_qnet_t h, float **r, uint8_t **t) { *r = h->ac_r; *t = h->ac_t; }
+
+// the train plan of an actor-critic net: ONE slice, s through the online net
+static Plan ac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *adv, const float *ret, int64_t n_total, float *loss,
+                          float *flat_grad, const FbRingSrc *ring) {
+    Plan p; memset(&p, 0, sizeof(p));
+    p.ns = 1;
+    p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
+    p.train = true; p.algo = -1; p.B = B; p.s = s; p.a = a; p.ac_adv = adv; p.ac_ret = ret; p.ac_nt = (float)n_total;
+    p.loss = loss;
+    p.G = flat_grad ? flat_grad : h->grad;
+    p.apply_adam = flat_grad == nullptr; p.tick = true;
+    p.ring = ring;
+    return p;
+}
+
+extern "C" int fb_qnet_ac_train_step(fb_qnet_t h, int B, const uint8_t *s, const uint8_t *a, const float *adv, const float *ret, int64_t n_total,
+                                     float *loss, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && s && a && adv && ret && loss, "fb_qnet_ac_train_step: NULL argument");
+    const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_qnet_ac_train_step");
+    if (rc != FB_OK) return rc;
+    Plan p = ac_train_plan(h, B, s, a, adv, ret, n_total, loss, flat_grad, nullptr);
+    if (B >= 256) {                              // (fc1_sp_kernel reads W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
+        const int rp = fb_qnet_refresh_planes(h, stream);
+        if (rp != FB_OK) return rp;
+    }
+    return run_train(h, p, stream);
+}
+
+int fb_qnet_ac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const float *adv, const float *ret, int64_t n_total, float *loss,
+                          float *flat_grad, void *stream) {
+    FB_REQUIRE(h && ring && ring->idx && ring->a && adv && ret && loss, "fb_ac_train_from_replay: NULL argument");
+    const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_ac_train_from_replay");
+    if (rc != FB_OK) return rc;
+    Plan p = ac_train_plan(h, B, nullptr, ring->a, adv, ret, n_total, loss, flat_grad, ring);
     return run_train(h, p, stream);
 }
 

@@ -112,13 +112,21 @@ def evaluate(net, n_envs, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0
 
 
 def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
-    """The online net of a VecBrain.save checkpoint (plain or dueling, told apart by the parameter count; C51 by its recorded support, and
+    """The online net of a VecBrain.save or VecActorCritic.save checkpoint (an actor-critic net by its recorded head 'ac'; plain or dueling, told apart by the parameter count; C51 by its recorded support, and
     C51 or dueling C51 by its recorded head -- 'c51' where none is recorded; a noisy net by its recorded `noisy` / `sigma0`, in mean
     mode; a QR net by its recorded `quantiles` and head).  max_batch sizes the net's
     workspace: evaluation runs its acting forward in passes of up to 3 * max_batch rows."""
     from .vec import QNet
     z = np.load(path if str(path).endswith(".npz") else str(path) + ".npz")
     online = np.ascontiguousarray(z["online"], np.float32)
+    if "head" in z.files and str(z["head"][0]) == "ac":      # an actor-critic net (VecActorCritic): greedy play is the policy's argmax
+        net = QNet(2, fc_width, "ac", max_batch=max_batch)
+        if net.n_params != online.size:
+            raise ValueError(f"{path}: {online.size} online parameters do not match an actor-critic net of width {fc_width}")
+        if dtype != "f32":
+            raise ValueError(f"{path}: an actor-critic net computes in f32 only (dtype {dtype!r})")
+        net.load_params(online, 0)
+        return net
     if "quantiles" in z.files:                               # a QR net (VecBrain records its head and (N, kappa))
         n_q, kappa = z["quantiles"].tolist()
         head = str(z["head"][0])

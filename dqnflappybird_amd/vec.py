@@ -298,6 +298,9 @@ QR_ARCHS = ("qr", "qrdueling")                            # quantile heads: QR-D
 QR_DEFAULT_QUANTILES = (51, 1.0)                          # n_quantiles, kappa (include/fbdqn.h; the size of C51's default head)
 ACTING_NOISE_MODES = ("shared", "env")                  # noisy nets: one noise sample for all envs when acting, or one per env
 NOISY_DEFAULT_SIGMA0 = 0.5                                # noisy nets: sigma = sigma0 / sqrt(fan_in) at init (Fortunato et al.)
+AC_ARCH = "ac"                                            # advantage actor-critic: V and the policy's logits on the shared trunk (include/fbdqn.h)
+AC_DEFAULTS = L.AC_DEFAULTS                               # (value_coef, entropy_coef) of a new actor-critic net
+AC_MAX_ROLLOUT = 128                                      # the longest rollout VecActorCritic takes
 
 
 def check_sigma0(sigma0):
@@ -352,6 +355,35 @@ def check_munchausen(tau, alpha, clip):
     return t, a, c
 
 
+def check_ac(value_coef, entropy_coef):
+    """the argument checks of fb_qnet_set_ac, on the host (-> (value_coef, entropy_coef) as float32-rounded floats)"""
+    with np.errstate(over="ignore"):
+        cv, ce = float(np.float32(value_coef)), float(np.float32(entropy_coef))
+    if not (np.isfinite(cv) and cv >= 0.0):
+        raise ValueError(f"value_coef must be finite and >= 0, got {value_coef}")
+    if not (np.isfinite(ce) and ce >= 0.0):
+        raise ValueError(f"entropy_coef must be finite and >= 0, got {entropy_coef}")
+    return cv, ce
+
+
+def check_gae(gamma, gae_lambda):
+    """the argument checks of fb_ac_gae, on the host (-> (gamma, lambda) as floats)"""
+    g, l = float(gamma), float(gae_lambda)
+    if not (np.isfinite(g) and 0.0 <= g <= 1.0):
+        raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+    if not (np.isfinite(l) and 0.0 <= l <= 1.0):
+        raise ValueError(f"gae_lambda must be in [0, 1], got {gae_lambda}")
+    return g, l
+
+
+def check_rollout(rollout):
+    """the rollout length of VecActorCritic / AcRolloutStep (-> int in 1..AC_MAX_ROLLOUT)"""
+    t = int(rollout)
+    if not 1 <= t <= AC_MAX_ROLLOUT:
+        raise ValueError(f"rollout must be in 1..{AC_MAX_ROLLOUT}, got {rollout}")
+    return t
+
+
 def check_huber(delta):
     """the argument check of fb_qnet_set_huber, on the host (-> delta as a float32-rounded float; 0 = the squared loss)"""
     with np.errstate(over="ignore"):                   # (a value beyond float32's range is infinite as the float the library takes)
@@ -396,7 +428,7 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
-    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS
+    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH,)
 
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
                  v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0,
@@ -406,7 +438,9 @@ class QNet:
         arch='qr' / 'qrdueling': the quantile head of QR-DQN (n_quantiles quantiles, quantile Huber loss with threshold kappa; include/fbdqn.h)
         and its dueling form; n_quantiles / kappa are ignored otherwise.
         noisy=True (C51 archs only): factorised Gaussian noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the flat
-        vector is [mu | sigma], and the net starts in mean mode (reset_noise, noise; include/fbdqn.h)"""
+        vector is [mu | sigma], and the net starts in mean mode (reset_noise, noise; include/fbdqn.h)
+        arch='ac': an advantage actor-critic net -- the dueling net's parameters read raw, V = h . W_v + b_v and the policy's logits
+        h . W_pi + b_pi (include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values"""
         if arch not in self.ARCHS:
             raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
         self.noisy = bool(noisy)
@@ -434,6 +468,8 @@ class QNet:
         elif arch == "c51dueling":
             L.check(L.lib().fb_qnet_create_c51_dueling(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)),
                     "fb_qnet_create_c51_dueling")
+        elif arch == AC_ARCH:
+            L.check(L.lib().fb_qnet_create_ac(self.FC, self.A, self.max_batch, C.byref(self.h)), "fb_qnet_create_ac")
         elif arch in QR_ARCHS:
             L.check(L.lib().fb_qnet_create_qr(L.ARCH_QR if arch == "qr" else L.ARCH_QR_DUELING, self.FC, self.A, n_quantiles, kappa,
                                               self.max_batch, C.byref(self.h)), "fb_qnet_create_qr")
@@ -582,6 +618,75 @@ class QNet:
         d = C.c_float()
         L.check(L.lib().fb_qnet_get_huber(self.h, C.byref(d)), "fb_qnet_get_huber")
         return d.value
+
+    # -- advantage actor-critic (arch='ac') -------------------------------------------
+    def _need_ac(self, what):
+        if self.arch != AC_ARCH:
+            raise ValueError(f"{what} needs an actor-critic net (QNet(..., arch='ac'))")
+
+    def set_ac(self, value_coef=AC_DEFAULTS[0], entropy_coef=AC_DEFAULTS[1]):
+        """the A2C loss's coefficients (fb_qnet_set_ac): loss = mean(L_pi + value_coef L_v - entropy_coef H); both finite and >= 0"""
+        self._need_ac("set_ac")
+        cv, ce = check_ac(value_coef, entropy_coef)
+        L.check(L.lib().fb_qnet_set_ac(self.h, cv, ce), "fb_qnet_set_ac")
+
+    def ac(self):
+        """the net's current (value_coef, entropy_coef) (fb_qnet_get_ac)"""
+        self._need_ac("ac")
+        cv, ce = C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_get_ac(self.h, C.byref(cv), C.byref(ce)), "fb_qnet_get_ac")
+        return cv.value, ce.value
+
+    def forward_ac(self, states):
+        """u8 states -> (logits f32[B, A], value f32[B]) of the online net (fb_qnet_forward_ac)"""
+        self._need_ac("forward_ac")
+        _dev_check(states)
+        if states.dtype != torch.uint8 or states.dim() != 4 or tuple(states.shape[1:]) != (80, 80, 4):
+            raise ValueError("states must be uint8[B,80,80,4]")
+        B = states.shape[0]
+        z = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
+        v = torch.empty(B, dtype=torch.float32, device=self.device)
+        L.check(L.lib().fb_qnet_forward_ac(self.h, L.ptr(states), B, L.ptr(z), L.ptr(v), L.current_stream()), "fb_qnet_forward_ac")
+        return z, v
+
+    def act_policy_nib(self, nib_states, seed=0, step=0, greedy=False, want_logits=False, value=None, logp=None, actions=None, value_only=False):
+        """sample an action per env from the policy (fb_qnet_act_policy_nib; the draw is keyed (seed, step, row), greedy: the first argmax)
+        -> (actions u8[n], value f32[n], logp f32[n][, logits f32[n, A]]).  value / logp / actions: tensors to write into (a rollout
+        buffer's row).  value_only: no action and no draw -> value alone (the bootstrap V(s_T))"""
+        self._need_ac("act_policy_nib")
+        _dev_check(nib_states, value, logp, actions)
+        if nib_states.dtype != torch.uint8 or nib_states.dim() != 2 or nib_states.shape[1] != L.NIB_STRIDE:
+            raise ValueError(f"nib_states must be uint8[n,{L.NIB_STRIDE}] (VecGameState.track_state())")
+        n = nib_states.shape[0]
+        for name, t, dt in (("value", value, torch.float32), ("logp", logp, torch.float32), ("actions", actions, torch.uint8)):
+            if t is not None and (t.dtype != dt or t.numel() != n):
+                raise ValueError(f"{name} must be {dt}[{n}]")
+        value = torch.empty(n, dtype=torch.float32, device=self.device) if value is None else value
+        if value_only:
+            L.check(L.lib().fb_qnet_act_policy_nib(self.h, L.ptr(nib_states), n, int(seed), int(step), 0, None, L.ptr(value), None, None,
+                                                   L.current_stream()), "fb_qnet_act_policy_nib")
+            return value
+        actions = torch.empty(n, dtype=torch.uint8, device=self.device) if actions is None else actions
+        logp = torch.empty(n, dtype=torch.float32, device=self.device) if logp is None else logp
+        z = torch.empty((n, self.A), dtype=torch.float32, device=self.device) if want_logits else None
+        L.check(L.lib().fb_qnet_act_policy_nib(self.h, L.ptr(nib_states), n, int(seed), int(step), int(bool(greedy)), L.ptr(actions), L.ptr(value),
+                                               L.ptr(logp), L.ptr(z), L.current_stream()), "fb_qnet_act_policy_nib")
+        return (actions, value, logp, z) if want_logits else (actions, value, logp)
+
+    def ac_train_step(self, s, a, adv, ret, n_total=None, flat_grad=None):
+        """one A2C step on <= 256 gathered states (fb_qnet_ac_train_step): n_total = the whole update's sample count (default: this
+        chunk's).  flat_grad=None applies Adam; a float32[n_params] tensor receives the chunk's gradient instead.
+        -> loss f32[4] (device): the chunk's share of (total, policy, value, entropy)"""
+        self._need_ac("ac_train_step")
+        _dev_check(s, a, adv, ret, flat_grad)
+        if s.dtype != torch.uint8 or s.dim() != 4 or tuple(s.shape[1:]) != (80, 80, 4):
+            raise ValueError("s must be uint8[B,80,80,4]")
+        B = s.shape[0]
+        check_ac_batch(B, a, adv, ret, n_total, flat_grad, self.n_params)
+        loss = torch.zeros(4, dtype=torch.float32, device=self.device)
+        L.check(L.lib().fb_qnet_ac_train_step(self.h, B, L.ptr(s), L.ptr(a), L.ptr(adv), L.ptr(ret), int(n_total or B), L.ptr(loss),
+                                              L.ptr(flat_grad), L.current_stream()), "fb_qnet_ac_train_step")
+        return loss
 
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):
@@ -759,6 +864,88 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
                                          L.ptr(loss), L.ptr(ae), L.ptr(flat_grad), L.current_stream()),
             "fb_train_from_replay")
     return (loss, a, r, t, ae) if want_abs_err else (loss, a, r, t)
+
+
+def check_ac_batch(B, a, adv, ret, n_total, flat_grad, n_params):
+    """the shape checks of the two A2C training calls, on the host"""
+    if not 1 <= B <= 256:
+        raise ValueError(f"an A2C chunk holds 1..256 samples, got {B}")
+    if a is not None and (a.dtype != torch.uint8 or a.numel() != B):
+        raise ValueError(f"a must be uint8[{B}]")
+    for name, t in (("adv", adv), ("ret", ret)):
+        if t.dtype != torch.float32 or t.numel() != B:
+            raise ValueError(f"{name} must be float32[{B}]")
+    if n_total is not None and int(n_total) < B:
+        raise ValueError(f"n_total = {n_total} must be the whole update's sample count (>= the chunk's {B})")
+    if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
+        raise ValueError(f"flat_grad must be float32[{n_params}]")
+
+
+def ac_gae(reward, terminal, value, gamma=0.99, gae_lambda=0.95):
+    """generalised advantage estimation on the device (fb_ac_gae): reward f32[T, N], terminal u8[T, N], value f32[T + 1, N] (row T: the
+    bootstrap V(s_T)) -> (adv f32[T, N], ret f32[T, N]); float64 arithmetic in the order include/fbdqn.h pins"""
+    g, l = check_gae(gamma, gae_lambda)
+    _dev_check(reward, terminal, value)
+    if reward.dim() != 2 or reward.dtype != torch.float32:
+        raise ValueError("reward must be float32[T,N]")
+    T, N = reward.shape
+    if terminal.dtype != torch.uint8 or tuple(terminal.shape) != (T, N):
+        raise ValueError(f"terminal must be uint8[{T},{N}]")
+    if value.dtype != torch.float32 or tuple(value.shape) != (T + 1, N):
+        raise ValueError(f"value must be float32[{T + 1},{N}] (row T: the bootstrap value)")
+    adv, ret = torch.empty_like(reward), torch.empty_like(reward)
+    L.check(L.lib().fb_ac_gae(L.ptr(reward), L.ptr(terminal), L.ptr(value), T, N, g, l, L.ptr(adv), L.ptr(ret), L.current_stream()), "fb_ac_gae")
+    return adv, ret
+
+
+def ac_train_from_replay(replay, net, idx, adv, ret, n_total=None, flat_grad=None):
+    """QNet.ac_train_step on the transitions at the deque positions idx of a uniform memory, read from its frame ring in place
+    (fb_ac_train_from_replay) -> (loss f32[4], a u8[B]: the ring's actions)"""
+    if net.arch != AC_ARCH:
+        raise ValueError("ac_train_from_replay needs an actor-critic net (QNet(..., arch='ac'))")
+    if replay.prioritized:
+        raise ValueError("ac_train_from_replay reads the rollout from a uniform memory only")
+    _dev_check(idx, adv, ret, flat_grad)
+    if idx.dtype != torch.int64:
+        raise ValueError("idx must be int64[B]")
+    B, dev = int(idx.numel()), idx.device
+    check_ac_batch(B, None, adv, ret, n_total, flat_grad, net.n_params)
+    a = torch.empty(B, dtype=torch.uint8, device=dev)
+    loss = torch.zeros(4, dtype=torch.float32, device=dev)
+    L.check(L.lib().fb_ac_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(adv), L.ptr(ret), int(n_total or B), L.ptr(a), L.ptr(loss),
+                                            L.ptr(flat_grad), L.current_stream()), "fb_ac_train_from_replay")
+    return loss, a
+
+
+class AcRolloutStep:
+    """One step of an A2C rollout as a single host call (fb_ac_rollout_step): sample the policy (value and log-probability into row
+    `slot` of the rollout buffers) -> frame_step (reward / terminal into row `slot`) -> store.  The results of QNet.act_policy_nib,
+    VecGameState.frame_step and VecReplay.push in that order; the pointers are bound once."""
+
+    def __init__(self, env, replay, net, rollout):
+        if net.arch != AC_ARCH:
+            raise ValueError("AcRolloutStep needs an actor-critic net (QNet(..., arch='ac'))")
+        if replay.prioritized:
+            raise ValueError("AcRolloutStep stores the rollout in a uniform memory only")
+        if getattr(env, "nib", None) is None:
+            raise ValueError("call env.track_state() first: the acting path reads the env kernel's nibble states")
+        self.T = check_rollout(rollout)
+        self.env, self.replay, self.net = env, replay, net
+        dev, N = env.device, env.n
+        self.actions = torch.zeros(N, dtype=torch.uint8, device=dev)
+        self.reward = torch.zeros((self.T, N), dtype=torch.float32, device=dev)
+        self.terminal = torch.zeros((self.T, N), dtype=torch.uint8, device=dev)
+        self.value = torch.zeros((self.T + 1, N), dtype=torch.float32, device=dev)      # (row T: the bootstrap value, the caller's)
+        self.logp = torch.zeros((self.T, N), dtype=torch.float32, device=dev)
+        p = lambda x: x.data_ptr()
+        self.buf = L.AcRolloutBuffers(p(env.nib), p(self.actions), p(env.frame_bits), p(self.reward), p(self.terminal), p(env.score),
+                                      p(self.value), p(self.logp), self.T)
+
+    def __call__(self, slot, seed=0, step=0):
+        """-> actions uint8[N] (device); row `slot` of reward / terminal / value / logp is written"""
+        L.check(L.lib().fb_ac_rollout_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(seed), int(step), int(slot),
+                                           L.current_stream()), "fb_ac_rollout_step")
+        return self.actions
 
 
 class TrainSteps:

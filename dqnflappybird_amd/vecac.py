@@ -1,0 +1,182 @@
+"""VecActorCritic: synchronous advantage actor-critic (A2C) on the vectorised loop, entirely device resident.
+
+    update:  T x [sample the policy for N envs -> frame_step -> store]   (AcRolloutStep, one host call each)
+             -> V(s_T) with the weights the rollout acted with -> GAE (vec.ac_gae)
+             -> the T N fresh transitions in ring-fed chunks of <= 256 (vec.ac_train_from_replay), gradients summed
+             -> [clip the sum] -> Adam, once
+
+The replay memory is not sampled: its frame ring is the rollout's state store (the newest T N deque positions are the rollout,
+in the order of the flattened [T, N] buffers), so no state is ever copied.  One net, one GPU; include/fbdqn.h pins the
+semantics, DESIGN.md section 16 the schedule.  The reference's actor-critic (BrainActorCritic.py: one env, one episode, a second
+network as the critic) stays what --model actorcritic runs; this is the batched algorithm its capacity is for.
+"""
+import numpy as np
+
+AC_HEAD = "ac"                                               # what a checkpoint of this class records as its head
+CHUNK = 256                                                  # samples per ring-fed train chunk (the train step's limit)
+
+
+def rollout_indices(size, rollout, n_envs):
+    """the deque positions of the rollout's T N transitions in a memory that holds `size` (its newest ones), in the order of the
+    flattened [T, N] buffers: position j names (t, e) = divmod(total - size + j, N) (csrc/fb_gather.h)"""
+    tn = int(rollout) * int(n_envs)
+    if size < tn:
+        raise ValueError(f"the memory holds {size} transitions, fewer than the rollout's {tn}")
+    return size - tn + np.arange(tn, dtype=np.int64)
+
+
+def check_args(n_envs, rollout, gamma, gae_lambda, value_coef, entropy_coef, max_grad_norm):
+    """every argument check of VecActorCritic that needs no GPU -> the checked values"""
+    from .vec import check_ac, check_gae, check_max_grad_norm, check_rollout
+    n = int(n_envs)
+    if n < 1:
+        raise ValueError(f"n_envs must be >= 1, got {n_envs}")
+    T = check_rollout(rollout)
+    g, l = check_gae(gamma, gae_lambda)
+    cv, ce = check_ac(value_coef, entropy_coef)
+    return n, T, g, l, cv, ce, check_max_grad_norm(max_grad_norm)
+
+
+class VecActorCritic:
+    def __init__(self, n_envs, rollout=5, gamma=0.99, gae_lambda=0.95, value_coef=0.5, entropy_coef=0.01, max_grad_norm=0.0, fc_width=512,
+                 seed=0, lr=1e-4, capacity=None):
+        """n_envs games, `rollout` steps per update (1..128), GAE(gamma, gae_lambda), loss = mean(L_pi + value_coef L_v - entropy_coef H)
+        over the rollout's rollout x n_envs samples, max_grad_norm=G > 0 clips the summed gradient's global norm before Adam, lr is
+        Adam's (the other hyper-parameters are the library's TF defaults).  capacity: the memory's, at least (rollout + 2) n_envs (the
+        default); it only has to hold the rollout."""
+        self.n, self.T, self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm = check_args(
+            n_envs, rollout, gamma, gae_lambda, value_coef, entropy_coef, max_grad_norm)
+        need = (self.T + 2) * self.n
+        self.capacity = need if capacity is None else int(capacity)
+        if self.capacity < need:
+            raise ValueError(f"capacity {self.capacity} < (rollout + 2) x n_envs = {need}: the memory's ring is the rollout's state store")
+        self.lr = float(lr)
+        if not (np.isfinite(self.lr) and self.lr > 0.0):
+            raise ValueError(f"lr must be finite and > 0, got {lr}")
+        import torch
+        from .vec import AcRolloutStep, QNet, VecGameState, VecReplay
+        self.seed = int(seed)
+        self.fc_width = int(fc_width)
+        self.env = VecGameState(self.n, seed=self.seed)
+        self.replay = VecReplay(self.capacity, self.n)
+        self.replay.seed(self.seed)
+        self.net = QNet(2, self.fc_width, "ac", max_batch=max(self.n, CHUNK))
+        self.net.set_ac(self.value_coef, self.entropy_coef)
+        self.net.set_hparams(lr=self.lr)
+        if self.max_grad_norm:
+            self.net.set_max_grad_norm(self.max_grad_norm)
+        self.net.init_params(seed=self.seed, which=0)
+        self.net.init_params(seed=self.seed + 1, which=1)    # (the target net exists in every net; A2C never reads it)
+        self.nib = self.env.track_state()
+        self.env.observe()
+        self.replay.reset(self.env.frame_bits)
+        self.stats = self.env.track_stats()
+        self.roll = AcRolloutStep(self.env, self.replay, self.net, self.T)
+        self.grad = torch.zeros(self.net.n_params, dtype=torch.float32, device="cuda")
+        self.chunk_grad = torch.zeros_like(self.grad)
+        self.losses = torch.zeros(4, dtype=torch.float32, device="cuda")
+        self.timeStep = 0                                    # env steps per env so far: the key of the policy's draws
+        self.updates = 0
+        self.pushes = 0                                      # pushes since the reset: len(replay) without a device sync
+        self._idx_for = None
+
+    def _indices(self):
+        import torch
+        size = min(self.pushes * self.n, self.capacity)
+        if self._idx_for != size:                            # (constant once the memory is full)
+            self._idx = torch.from_numpy(rollout_indices(size, self.T, self.n)).cuda()
+            self._idx_for = size
+        return self._idx
+
+    def update(self):
+        """one A2C update: the rollout, the advantages, the chunks, Adam -> the update's four loss numbers f32[4] (device)"""
+        from .vec import ac_gae, ac_train_from_replay
+        for t in range(self.T):
+            self.roll(t, seed=self.seed, step=self.timeStep)
+            self.timeStep += 1
+            self.pushes += 1
+        self.net.act_policy_nib(self.nib, value=self.roll.value[self.T], value_only=True)      # V(s_T), the pre-update weights
+        adv, ret = ac_gae(self.roll.reward, self.roll.terminal, self.roll.value, self.gamma, self.gae_lambda)
+        adv, ret = adv.view(-1), ret.view(-1)
+        idx, tn = self._indices(), self.T * self.n
+        self.grad.zero_()
+        self.losses.zero_()
+        for k in range(0, tn, CHUNK):
+            e = min(k + CHUNK, tn)
+            loss, _ = ac_train_from_replay(self.replay, self.net, idx[k:e], adv[k:e], ret[k:e], n_total=tn, flat_grad=self.chunk_grad)
+            self.grad += self.chunk_grad
+            self.losses += loss
+        if self.max_grad_norm:
+            self.net.clip_grad(self.grad)
+        self.net.apply_adam(self.grad)
+        self.updates += 1
+        return self.losses
+
+    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0):
+        """Greedy play (the policy's argmax) of n_envs fresh games with the net as it stands (dqnflappybird_amd.evaluate): changes
+        nothing the training that follows reads"""
+        from .evaluate import evaluate
+        return evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed)
+
+    # ------------------------------------------------------------------ checkpoint / resume
+    @staticmethod
+    def _npz(path):
+        return path if str(path).endswith(".npz") else str(path) + ".npz"
+
+    def save(self, path):
+        """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory,
+        the counters and the A2C settings; `head` = 'ac' tells the file from a VecBrain's"""
+        host = lambda t: t.cpu().numpy()
+        m, v, pows = self.net.adam_state()
+        np.savez(self._npz(path), head=np.array([AC_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
+                 adam_m=host(m), adam_v=host(v), beta_pows=np.asarray(pows, np.float32),
+                 scalars=np.array([self.timeStep, self.updates, self.pushes, self.seed, self.n, self.T, self.fc_width], np.int64),
+                 ac=np.array([self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm, self.lr], np.float64),
+                 env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob())
+
+    def load(self, path):
+        """the inverse of save(), into a VecActorCritic made with the same n_envs, rollout, fc_width, capacity and seed (the envs' pipe-gap
+        streams are keyed by the seed they were created with); the A2C settings of the file replace this object's"""
+        import torch
+        from .vecbrain import checkpoint_head
+        z = np.load(self._npz(path))
+        head = checkpoint_head(z)
+        if head != AC_HEAD:
+            raise ValueError(f"checkpoint {path} holds a {head} head (a VecBrain's), this is a VecActorCritic (head {AC_HEAD!r})")
+        sc = [int(x) for x in z["scalars"]]
+        if (sc[4], sc[5], sc[6]) != (self.n, self.T, self.fc_width):
+            raise ValueError(f"checkpoint {path} was written with (n_envs, rollout, fc_width) = {tuple(sc[4:7])}, this VecActorCritic has "
+                             f"{(self.n, self.T, self.fc_width)}")
+        if sc[3] != self.seed:
+            raise ValueError(f"checkpoint {path} was written with seed {sc[3]}, this VecActorCritic has seed {self.seed} (the envs' pipe-gap "
+                             "streams are keyed by it)")
+        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        self.net.load_params(z["online"], 0)
+        self.net.load_params(z["target"], 1)
+        self.net.set_adam_state(dev(z["adam_m"]), dev(z["adam_v"]), z["beta_pows"])
+        self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm, self.lr = (float(x) for x in z["ac"])
+        self.net.set_ac(self.value_coef, self.entropy_coef)
+        self.net.set_hparams(lr=self.lr)
+        self.net.set_max_grad_norm(self.max_grad_norm)
+        self.env.set_state(z["env_state"])
+        self.nib.copy_(dev(z["nib"]))
+        self.stats[...] = dev(z["stats"])
+        self.replay.load_state_blob(z["replay"])
+        self.timeStep, self.updates, self.pushes = sc[0], sc[1], sc[2]
+        self._idx_for = None
+        torch.cuda.synchronize()
+
+    def run(self, updates, log_every=100):
+        for i in range(updates):
+            losses = self.update()
+            if log_every and (i + 1) % log_every == 0:
+                tot, lpi, lv, ent = losses.tolist()              # the only host sync of the loop, once per log line
+                ep, ssum, smax, pipes = self.stats.tolist()
+                self.net.check_range()
+                clip = ""
+                if self.max_grad_norm:
+                    norm, scale = self.net.grad_norm()
+                    clip = f" / GRAD_NORM {norm:.6g} / CLIP_SCALE {scale:.6g}"
+                print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / POLICY_LOSS {lpi:.6g} / VALUE_LOSS {lv:.6g} / ENTROPY {ent:.6g} / "
+                      f"GAME_TIMES {ep} / MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {tot:.6g}{clip}",
+                      flush=True)

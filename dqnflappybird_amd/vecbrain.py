@@ -553,6 +553,9 @@ class VecBrain:
         (the world size must be the one the checkpoint was written with: the shards are rank-local)."""
         import numpy as np
         z = np.load(self._npz(path))
+        if checkpoint_head(z) == "ac":                       # (an actor-critic net has the dueling net's parameter count: the head tells)
+            raise ValueError(f"checkpoint {path} holds an ac head (a VecActorCritic's), this is a VecBrain: load it with "
+                             "dqnflappybird_amd.vecac.VecActorCritic")
         saved_world = int(z["scalars"][2]) if len(z["scalars"]) > 2 else 1
         if saved_world != self.world:
             raise ValueError(f"checkpoint {path} was written by {saved_world} rank(s), this job has {self.world}")

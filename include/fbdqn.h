@@ -558,6 +558,78 @@ int fb_qnet_clip_grad(fb_qnet_t h, float *flat_grad, void *stream);
 int fb_qnet_grad_norm(fb_qnet_t h, float *norm_host, float *scale_host);
 int fb_qnet_soft_sync_target(fb_qnet_t h, float rho, void *stream);
 
+/* ------------------------------------------------------------------ advantage actor-critic (A2C, Mnih et al. 2016, synchronous form)
+ * The on-policy learner of the vectorised loop: N envs make T steps with the current policy, and ALL T N fresh transitions train one
+ * update.  (The reference's BrainPolicyGradient / BrainActorCritic are one env, one episode, a critic that is a second network trained
+ * online at batch 1: FB_ALGO_PG stands behind those.  This is the batched algorithm, with a shared trunk.)
+ * An AC net (FB_ARCH_AC, fb_qnet_create_ac) has the trunk and fc1 of every net and the DUELING net's head parameters, layout and order,
+ *   W_v[FC,1] b_v[1] W_pi[FC,A] b_pi[A]   (fb_qnet_num_params and fb_qnet_init_params' draws are the dueling net's of that shape)
+ * read RAW, with h = relu(h_fc1):  V(s) = h . W_v + b_v,  logits z(s) = h . W_pi + b_pi.  There is no dueling combine.
+ *   acting      fb_qnet_forward / _act / _act_nib / fb_eval_run / fb_eval_q treat the LOGITS as the Q values (the plain head over W_pi b_pi):
+ *               greedy play is the policy's argmax, epsilon as for a plain net.  fb_qnet_forward_ac returns (z, V) -- z the very bits
+ *               fb_qnet_forward returns.  The target net (FB_NET_TARGET) exists and is unused by A2C
+ *   policy      float32, ascending c:  m = max_c z_c, e_c = expf(z_c - m), p_c = e_c / sum e,  log p_c = z_c - (m + logf(sum e))
+ *   sampling    fb_qnet_act_policy_nib, row r at (seed, step): u = (o.x >> 8) * 2^-24, o = Philox4x32-10(key = (seed_lo, seed_hi), counter =
+ *               (r, step_lo, FB_STREAM_POLICY = 8, step_hi)); the action is the smallest c with u < sum_{c' <= c} p_c' (a running float32 sum),
+ *               A - 1 if there is none; logp = log p_a.  greedy != 0: the first maximum of z, no draw.  A = 1: action 0, logp 0
+ *   advantages  fb_ac_gae (generalised advantage estimation, Schulman et al. 2016) over reward f32[T,N], terminal u8[T,N], value f32[T+1,N]
+ *               (row T: the bootstrap V(s_T)), per env, t = T-1 .. 0, everything in double:
+ *                 r = (rew == 0.1f) ? 0.1 : (double)rew   (the convention of every target here);  nd = !terminal[t]
+ *                 x = nd ? gamma * (double)v[t+1] : 0;  delta = (r + x) - (double)v[t];  A = delta + (nd ? gl * A : 0),  gl = gamma * lambda
+ *                 adv[t] = (float)A;  ret[t] = (float)(A + (double)v[t])
+ *               0 <= gamma, lambda <= 1.  lambda = 1: the discounted return less V; lambda = 0: the one-step TD error
+ *   loss        per sample b of a chunk, N_tot = n_total (the whole update's sample count), c_v / c_e the net's coefficients, fp32:
+ *                 L_pi = -adv_b log p_{a_b}   (adv is a constant)      L_v = (V_b - ret_b)^2      H = -sum_c p_c log p_c
+ *                 loss = (1 / N_tot) sum_b (L_pi + c_v L_v - c_e H)
+ *                 dLoss/dz_c = (adv_b (p_c - 1{c = a_b}) + c_e p_c (log p_c + H)) / N_tot       dLoss/dV = (2 c_v (V_b - ret_b)) / N_tot
+ *               loss[0..3] = the chunk's share of {total, sum L_pi / N_tot, sum L_v / N_tot, sum H / N_tot}; sums over b in ascending order,
+ *               no atomics: equal inputs give equal bits
+ *   training    fb_qnet_ac_train_step on gathered states, fb_ac_train_from_replay on ring positions (the ring-fed trunk; a UNIFORM memory
+ *               at n-step 1; a_out receives the ring's actions): 1 <= batch <= min(max_batch, 256), n_total >= batch.  flat_grad NULL:
+ *               Adam at once (with the net's gradient clipping, as fb_qnet_train_step).  flat_grad != NULL: the chunk's gradient is
+ *               exported only -- the caller sums the chunks of an update, clips the sum with fb_qnet_clip_grad if it wants, and calls
+ *               fb_qnet_apply_adam once, as FB_ALGO_PG callers do.  s is forwarded once (one slice)
+ *   rollout     the replay ring is the rollout's state store: after T fb_ac_rollout_step calls the newest T N deque positions,
+ *               idx = len - T N + k, are the transitions in the order of the flattened [T,N] buffers (position j -> g = total - size + j,
+ *               (t, e) = divmod(g, N)).  fb_ac_rollout_step(slot) = fb_qnet_act_policy_nib (value / logp written at row `slot`) ->
+ *               fb_env_step (reward / terminal written at row `slot`) -> fb_replay_push: three calls in that order on `stream`,
+ *               their results bit for bit.  No riders, no split schedule.  It pushes: not capturable for replay, like fb_vec_step
+ *   refused     FB_ERR_INVALID before any launch or counter change: on an AC net every FB_ALGO_* of fb_qnet_train_step / fb_train_from_replay /
+ *               fb_train_steps / fb_vec_step / fb_vec_step_dp, fb_qnet_set_huber / _get_huber, fb_qnet_set_munchausen / _get_munchausen,
+ *               FB_DTYPE_BF16 for inference or training; fb_qnet_create with arch 6 and fb_qnet_create_c51_noisy with it (no noisy AC net);
+ *               every fb_qnet_*_ac / fb_ac_* call below on a net that is not an AC net.
+ *   not offered PPO (logp is stored so that it can follow), data-parallel A2C, bf16, riders or the split schedule for the rollout step,
+ *               noisy or distributional critics.
+ * fb_qnet_set_ac / fb_qnet_get_ac: (c_v, c_e), 0.5 and 0.01 in a new net; both finite and >= 0.  A host-side setting read by the calls issued
+ *   after it. */
+#define FB_ARCH_AC 6
+typedef struct {
+    uint8_t *nib;                                   /* u8[N,FB_NIB_STRIDE]: the buffer given to fb_env_set_nib_buffer */
+    uint8_t *actions;                               /* u8[N] out */
+    uint64_t *frame_bits;                           /* u64[N,100] out */
+    float *reward; uint8_t *terminal;               /* f32[slots,N], u8[slots,N]: row `slot` out */
+    int32_t *score;                                 /* i32[N] out */
+    float *value, *logp;                            /* f32[slots (+1),N], f32[slots,N]: row `slot` out */
+    int slots;                                      /* rows of reward / terminal / value / logp (the rollout length T) */
+} fb_ac_rollout_buffers;
+int fb_qnet_create_ac(int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
+int fb_qnet_set_ac(fb_qnet_t h, float value_coef, float entropy_coef);
+int fb_qnet_get_ac(fb_qnet_t h, float *value_coef_host, float *entropy_coef_host);
+/* states u8[B,80,80,4] -> logits f32[B,A], value f32[B]; 1 <= B <= 3 * max_batch; the online net */
+int fb_qnet_forward_ac(fb_qnet_t h, const uint8_t *states, int batch, float *logits, float *value, void *stream);
+/* the acting forward of fb_qnet_act_nib (the small-batch kernels below 256 states, the fused trunk from 256 on), then the policy head as
+ * a launch of its own.  actions u8[n] or NULL (NULL: logits / value only, no draw), value f32[n], logp f32[n] or NULL, logits f32[n,A] or NULL */
+int fb_qnet_act_policy_nib(fb_qnet_t h, const uint8_t *nib_states, int n, uint64_t seed, uint64_t step, int greedy, uint8_t *actions,
+                           float *value, float *logp, float *logits, void *stream);
+int fb_ac_gae(const float *reward, const uint8_t *terminal, const float *value, int T, int N, double gamma, double lambda, float *adv,
+              float *ret, void *stream);
+int fb_qnet_ac_train_step(fb_qnet_t h, int batch, const uint8_t *s, const uint8_t *a, const float *adv, const float *ret, int64_t n_total,
+                          float *loss, float *flat_grad, void *stream);
+int fb_ac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *adv, const float *ret,
+                            int64_t n_total, uint8_t *a_out, float *loss, float *flat_grad, void *stream);
+int fb_ac_rollout_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_ac_rollout_buffers *b, int n_envs, uint64_t seed,
+                       uint64_t step, int slot, void *stream);
+
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
 int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host);
