@@ -126,30 +126,45 @@ def build_parser():
     parser.add_argument("--gae-lambda", type=float, default=None, help="--model a2c: lambda of the generalised advantage estimate (default 0.95)")
     parser.add_argument("--value-coef", type=float, default=None, help="--model a2c: the value loss's coefficient (default 0.5)")
     parser.add_argument("--entropy-coef", type=float, default=None, help="--model a2c: the entropy bonus's coefficient (default 0.01)")
+    parser.add_argument("--epochs", type=int, default=None, help="--model ppo: passes over each rollout K (default 4)")
+    parser.add_argument("--minibatches", type=int, default=None, help="--model ppo: minibatches per pass M, a divisor of rollout x envs (default 4)")
+    parser.add_argument("--clip-eps", type=float, default=None, help="--model ppo: the probability ratio is clipped to [1 - E, 1 + E] (default 0.2)")
+    parser.add_argument("--value-clip", type=float, default=None, help="--model ppo: clip the value around the rollout's by C (default 0 = off)")
+    parser.add_argument("--no-adv-norm", action="store_true", help="--model ppo: do not normalise the rollout's advantages")
     return parser
 
 
 def a2c_kwargs(args, parser):
-    """--model a2c's options as VecActorCritic's keywords; everything is refused here, before anything touches the GPU"""
+    """--model a2c's and --model ppo's options as VecActorCritic's keywords; everything is refused here, before anything touches the GPU"""
     given = [n for n, v in (("--rollout", args.rollout), ("--gae-lambda", args.gae_lambda), ("--value-coef", args.value_coef),
                             ("--entropy-coef", args.entropy_coef)) if v is not None]
-    if args.model != "a2c":
+    ppo_given = [n for n, v in (("--epochs", args.epochs), ("--minibatches", args.minibatches), ("--clip-eps", args.clip_eps),
+                                ("--value-clip", args.value_clip), ("--no-adv-norm", args.no_adv_norm or None)) if v is not None]
+    if ppo_given and args.model != "ppo":
+        parser.error(f"{' / '.join(ppo_given)} need --model ppo, not --model {args.model}")
+    if args.model not in ("a2c", "ppo"):
         if given:
             parser.error(f"{' / '.join(given)} need --model a2c, not --model {args.model}")
         return None
     if not args.vec:
-        parser.error("--model a2c needs --vec: the advantage actor-critic runs in the vectorised loop only")
+        parser.error(f"--model {args.model} needs --vec: the advantage actor-critic runs in the vectorised loop only")
     for name, on in (("--noisy", args.noisy), ("--n-step", args.n_step != 1), ("--huber", args.huber is not None), ("--polyak", args.polyak is not None),
                      ("--tau / --alpha / --clip", args.tau is not None or args.alpha is not None or args.clip is not None),
                      ("--n-quantiles / --kappa", args.n_quantiles is not None or args.kappa is not None)):
         if on:
-            parser.error(f"{name} is not an option of --model a2c (--rollout, --gae-lambda, --value-coef, --entropy-coef, --max-grad-norm are)")
-    from .vecac import check_args
+            parser.error(f"{name} is not an option of --model {args.model} (--rollout, --gae-lambda, --value-coef, --entropy-coef, --max-grad-norm"
+                         f"{', --epochs, --minibatches, --clip-eps, --value-clip, --no-adv-norm' if args.model == 'ppo' else ''} are)")
+    from .vecac import check_args, check_ppo_args
     kw = dict(rollout=5 if args.rollout is None else args.rollout, gae_lambda=0.95 if args.gae_lambda is None else args.gae_lambda,
               value_coef=0.5 if args.value_coef is None else args.value_coef, entropy_coef=0.01 if args.entropy_coef is None else args.entropy_coef,
               max_grad_norm=0.0 if args.max_grad_norm is None else args.max_grad_norm)
     try:
         check_args(args.vec, kw["rollout"], 0.99, kw["gae_lambda"], kw["value_coef"], kw["entropy_coef"], kw["max_grad_norm"])
+        if args.model == "ppo":
+            kw.update(algo="ppo", epochs=4 if args.epochs is None else args.epochs, minibatches=4 if args.minibatches is None else args.minibatches,
+                      clip_eps=0.2 if args.clip_eps is None else args.clip_eps, value_clip=0.0 if args.value_clip is None else args.value_clip,
+                      normalize_adv=not args.no_adv_norm)
+            check_ppo_args(args.vec, kw["rollout"], kw["epochs"], kw["minibatches"], kw["clip_eps"], kw["value_clip"])
     except ValueError as e:
         parser.error(str(e))
     return kw

@@ -5,6 +5,10 @@
 //   ac_gae_kernel     the advantage scan; one thread per env, t = T-1 .. 0
 //   ac_loss_kernel    training, launch 1 of 2: per sample logits / V, the loss terms, dz, dV, the dhf row and the activation row
 //   ac_grad_kernel    training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_v, W_pi; workgroup 0: b_v, b_pi, the loss, Adam's tick
+// and PPO on the same rollout (fb_qnet_ppo_train_step, fb_ppo_train_from_replay, fb_ac_normalize_adv, fb_ac_permute):
+//   ppo_loss_kernel     ac_loss_kernel's place in the train step: the clipped-surrogate policy term, the (clipped) value term, two more loss terms
+//   ac_adv_norm_kernel  the rollout's advantages to mean 0, standard deviation 1; ONE workgroup, float64, a pinned order
+//   ac_permute_kernel   a stateless keyed permutation of [0, n): a Feistel network over Philox, cycle-walked; one thread per element
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
 #include "fb_common.h"
 #include <math.h>
@@ -192,15 +196,129 @@ __global__ __launch_bounds__(256) void ac_loss_kernel(AcLossArgs L) {
     }
 }
 
+// ---- PPO's loss (include/fbdqn.h), ac_loss_kernel's grid and outputs: dl[b][16] holds dz at 0 .. 7, dV at 8, L_pi / L_v / H at 9 .. 11
+// and the two terms PPO adds, 1{r outside [1 - eps, 1 + eps]} at 12 and (r - 1) - log r at 13.  Every lane holds the same logits, so
+// the ratio and both clips are wave-uniform arithmetic: no exchange.  SEL: the rollout's four buffers are read at sel[b] (one 8-byte
+// load per wave) instead of at b -- a template argument, so that no load sits under a branch.
+template <int AT, bool SEL>
+__global__ __launch_bounds__(256) void ppo_loss_kernel(PpoLossArgs Q) {
+    const AcLossArgs &L = Q.a;
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= L.B) return;                                        // (wave-uniform)
+    const int A = AT == MAXA ? L.A : AT, FC = L.FC;
+    const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;  // (an action past the head reads the last one: stays in bounds)
+    const long long k = SEL ? Q.sel[b] : (long long)b;
+    const float adv = L.adv[k], ret = L.ret[k], lpo = Q.logp_old[k], vo = Q.value_old[k];
+    float z[AT], V, p[AT], lp[AT], m, s;
+    ac_row<AT>(L.hf, L.stot, L.nks, FC, A, L.off, L.P, b, lane, z, V);
+    ac_softmax<AT>(z, A, p, lp, m, s);
+    float H = 0.f, lpa = lp[0];
+#pragma unroll
+    for (int c = 0; c < AT; c++) { H -= c < A ? p[c] * lp[c] : 0.f; lpa = c == ab ? lp[c] : lpa; }
+    const float lr = lpa - lpo, r = expf(lr), lo = 1.f - Q.eps, hi = 1.f + Q.eps;
+    const float s1 = r * adv, s2 = fminf(fmaxf(r, lo), hi) * adv;
+    const float lpi = -fminf(s1, s2), w = s1 <= s2 ? s1 : 0.f;   // (the clipped branch is flat in r: no gradient)
+    const float e1 = V - ret, d = V - vo, q1 = e1 * e1;
+    const bool plain = Q.vclip == 0.f || fabsf(d) <= Q.vclip;   // the exact unclipped branch: vo + d is never formed
+    const float e2 = (vo + copysignf(Q.vclip, d)) - ret, q2 = e2 * e2;
+    const float lv = plain ? q1 : fmaxf(q1, q2);
+    const float dV = plain || q1 >= q2 ? (2.f * L.cv * e1) / L.nt : 0.f;
+    float dz[AT];
+#pragma unroll
+    for (int c = 0; c < AT; c++)
+        dz[c] = c < A ? (w * (p[c] - (c == ab ? 1.f : 0.f)) + L.ce * p[c] * (lp[c] + H)) / L.nt : 0.f;
+    float o = lane == 8 ? dV : lane == 9 ? lpi : lane == 10 ? lv : lane == 11 ? H : lane == 12 ? (r < lo || r > hi ? 1.f : 0.f)
+              : lane == 13 ? (r - 1.f) - lr : 0.f;
+#pragma unroll
+    for (int c = 0; c < AT; c++) o = lane == c ? dz[c] : o;
+    if (lane < 16) L.dl[(size_t)b * 16 + lane] = o;
+    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {               // the dhf and activation rows, as ac_loss_kernel writes them
+        float x4[4], wq[4][AT], wv[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+#pragma unroll
+            for (int a = 0; a < AT; a++) wq[e][a] = L.P[L.off.wq + (j0 + e) * A + (a < A ? a : 0)];
+            wv[e] = L.P[L.off.wv + j0 + e];
+        }
+        ac_units4(L.hf, L.stot, L.nks, FC, L.P, L.off.bf1, b, j0, x4);
+        float d4[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            float dh = dV * wv[e];
+#pragma unroll
+            for (int a = 0; a < AT; a++) dh = fmaf(dz[a], wq[e][a], dh);     // (dz of a >= A is 0)
+            d4[e] = x4[e] > 0.f ? dh : 0.f;
+        }
+        *reinterpret_cast<float4 *>(L.dhf + (size_t)b * FC + j0) = make_float4(d4[0], d4[1], d4[2], d4[3]);
+        *reinterpret_cast<float4 *>(L.xs + (size_t)b * FC + j0) = make_float4(x4[0], x4[1], x4[2], x4[3]);
+    }
+}
+
+// ---- the rollout's advantages to mean 0 and standard deviation 1, in double, in the order include/fbdqn.h pins: ONE workgroup; thread t
+// sums the elements i = t (mod 256) in ascending order, thread 0 adds the 256 partial sums in ascending t.  out may be adv: an element
+// is read and written by the same thread, and the last read of a pass sits in front of a barrier.
+__global__ __launch_bounds__(256) void ac_adv_norm_kernel(const float *adv, long long n, float *out) {
+    __shared__ double part[256];
+    __shared__ double stat[2];
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    for (long long i = t; i < n; i += 256) acc += (double)adv[i];
+    part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double S = 0.0;
+        for (int q = 0; q < 256; q++) S += part[q];
+        stat[0] = S / (double)n;
+    }
+    __syncthreads();
+    const double mean = stat[0];
+    acc = 0.0;
+    for (long long i = t; i < n; i += 256) { const double d = (double)adv[i] - mean; acc += d * d; }
+    part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double S = 0.0;
+        for (int q = 0; q < 256; q++) S += part[q];
+        stat[1] = sqrt(S / (double)n);
+    }
+    __syncthreads();
+    const double den = stat[1] + 1e-8;
+    for (long long i = t; i < n; i += 256) out[i] = (float)(((double)adv[i] - mean) / den);
+}
+
+// ---- a keyed permutation of [0, n) without state: element i -> the cycle-walked image of i under a 4-round Feistel network on k = 2 half
+// bits, (L, R) <- (R, L ^ (F_r(R) & mask)), F_r(R) = word r of Philox4x32-10(key = seed, counter = (R, draw_lo, FB_STREAM_PERM, draw_hi)).
+// The network is a bijection of [0, 2^k), so walking it until the value is below n is a bijection of [0, n) (the walk of an i < n comes
+// back to i at the latest); 2^k < 4 n: fewer than 4 walks on average.
+__global__ __launch_bounds__(256) void ac_permute_kernel(long long n, uint32_t seed_lo, uint32_t seed_hi, uint32_t draw_lo, uint32_t draw_hi, int half,
+                                                         long long *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t mask = (1u << half) - 1u;
+    uint32_t x = (uint32_t)i;
+    do {
+        uint32_t Lh = x >> half, R = x & mask;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const fb_u4 o = fb_philox(seed_lo, seed_hi, R, draw_lo, FB_STREAM_PERM, draw_hi);
+            const uint32_t F = r == 0 ? o.x : r == 1 ? o.y : r == 2 ? o.z : o.w;
+            const uint32_t nr = Lh ^ (F & mask);
+            Lh = R; R = nr;
+        }
+        x = (Lh << half) | R;
+    } while ((long long)x >= n);
+    out[i] = (long long)x;
+}
+
 // ---- training, launch 2 of 2: one workgroup per 16 fc1 units (c51_grad_kernel's grid): b_fc1's gradient and the tile's maximum |dhf|
 // (fc1_bwd_big_kernel's pre-scale), then thread (unit jl, column c) walks the samples in order: c < A is W_pi's column c, c = 8 is W_v.
-// Workgroup 0 also sums b_pi, b_v and the three loss terms the same way, forms the four loss numbers and ticks Adam.
+// Workgroup 0 also sums b_pi, b_v and the loss terms the same way (nterms: A2C's three, or PPO's five), forms the loss numbers and ticks Adam.
 __global__ __launch_bounds__(256) void ac_grad_kernel(AcGradArgs L) {
     __shared__ float dlt[AC_MAXB * 16];
     __shared__ float xt[AC_MAXB * 16];
     __shared__ float part[16][16];
     __shared__ float wmax[4];
-    __shared__ float lsum[3];
+    __shared__ float lsum[5];
     const int tid = threadIdx.x, B = L.B, FC = L.FC, A = L.A, j00 = blockIdx.x * 16;
     for (int k = tid; k < B * 16; k += 256) { dlt[k] = L.dl[k]; xt[k] = L.xs[(size_t)(k >> 4) * FC + j00 + (k & 15)]; }
     const int jl = tid & 15, bg = tid >> 4;
@@ -229,7 +347,7 @@ __global__ __launch_bounds__(256) void ac_grad_kernel(AcGradArgs L) {
     if (blockIdx.x != 0) return;
     if (jl == 0 && c < A) L.grad[L.off.bq + c] = gb;
     if (jl == 0 && c == 8) L.grad[L.off.bv] = gb;
-    if (jl == 1 && c >= 9 && c < 12) {                           // (three otherwise idle threads: the loss terms, samples in order)
+    if (jl == 1 && c >= 9 && c < 9 + L.nterms) {                 // (otherwise idle threads: the loss terms, samples in order)
         float t = 0.f;
         for (int b = 0; b < B; b++) t += dlt[b * 16 + c];
         lsum[c - 9] = t / L.nt;
@@ -238,6 +356,7 @@ __global__ __launch_bounds__(256) void ac_grad_kernel(AcGradArgs L) {
     if (tid == 0) {
         L.loss[1] = lsum[0]; L.loss[2] = lsum[1]; L.loss[3] = lsum[2];
         L.loss[0] = (lsum[0] + L.cv * lsum[1]) - L.ce * lsum[2];
+        if (L.nterms == 5) { L.loss[4] = lsum[3]; L.loss[5] = lsum[4]; }      // PPO: the clip fraction and the approximate KL
         FbAdamHead &ad = *L.adam;
         if (L.tick && ad.ticks == ad.applies) {                  // (as c51_grad_kernel)
             ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
@@ -262,6 +381,16 @@ void fb_ac_launch_loss(hipStream_t st, const void *args) {
     AcLossArgs L;
     memcpy(&L, args, sizeof(L));
     with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(ac_loss_kernel<decltype(a)::value>, dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
+}
+
+void fb_ac_launch_ppo_loss(hipStream_t st, const void *args) {
+    PpoLossArgs Q;
+    memcpy(&Q, args, sizeof(Q));
+    const dim3 grid((Q.a.B + 3) / 4);
+    with_actions(Q.a.A, [&](auto a) {
+        if (Q.sel) hipLaunchKernelGGL((ppo_loss_kernel<decltype(a)::value, true>), grid, dim3(256), 0, st, Q);
+        else hipLaunchKernelGGL((ppo_loss_kernel<decltype(a)::value, false>), grid, dim3(256), 0, st, Q);
+    });
 }
 
 void fb_ac_launch_grad(hipStream_t st, const void *args) {
@@ -302,6 +431,49 @@ extern "C" int fb_ac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int ba
         if (rc != FB_OK) return rc;
     }
     return fb_qnet_ac_train_ring(net, batch, &ring, adv, ret, n_total, loss, flat_grad, stream);
+}
+
+extern "C" int fb_ppo_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const int64_t *sel, const float *adv,
+                                        const float *ret, const float *logp_old, const float *value_old, int64_t n_total, uint8_t *a_out,
+                                        float *loss, float *flat_grad, void *stream) {
+    FB_REQUIRE(replay && net && idx && adv && ret && logp_old && value_old && a_out && loss, "fb_ppo_train_from_replay: NULL argument");
+    FB_REQUIRE(fb_qnet_is_ac(net), "fb_ppo_train_from_replay: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(!fb_replay_is_prioritized(replay), "fb_ppo_train_from_replay: the rollout is read from a uniform memory only");
+    int n = 1; double g = 0.0;
+    int rc = fb_replay_get_n_step(replay, &n, &g);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(n == 1, "fb_ppo_train_from_replay: the memory has a %d-step view; the rollout is read at n-step 1 only", n);
+    rc = fb_qnet_ac_check_train(net, batch, n_total, "fb_ppo_train_from_replay");
+    if (rc != FB_OK) return rc;
+    float *r_scr; uint8_t *t_scr;
+    fb_qnet_ac_scratch(net, &r_scr, &t_scr);
+    FbRingSrc ring;
+    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_scr, t_scr, &ring);
+    if (rc != FB_OK) return rc;
+    if (batch >= 256) {                          // (as fb_ac_train_from_replay)
+        rc = fb_qnet_refresh_planes(net, stream);
+        if (rc != FB_OK) return rc;
+    }
+    return fb_qnet_ppo_train_ring(net, batch, &ring, sel, adv, ret, logp_old, value_old, n_total, loss, flat_grad, stream);
+}
+
+extern "C" int fb_ac_normalize_adv(const float *adv, int64_t n, float *out, void *stream) {
+    FB_REQUIRE(adv && out, "fb_ac_normalize_adv: NULL argument");
+    FB_REQUIRE(n >= 1 && n < (1LL << 31), "fb_ac_normalize_adv: n = %lld out of range", (long long)n);
+    hipLaunchKernelGGL(ac_adv_norm_kernel, dim3(1), dim3(256), 0, fb_stream(stream), adv, (long long)n, out);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+extern "C" int fb_ac_permute(int64_t n, uint64_t seed, uint64_t draw, int64_t *out, void *stream) {
+    FB_REQUIRE(out, "fb_ac_permute: NULL argument");
+    FB_REQUIRE(n >= 1 && n < (1LL << 31), "fb_ac_permute: n = %lld out of range (1 <= n < 2^31)", (long long)n);
+    int k = 2;
+    while ((1LL << k) < n) k += 2;               // the smallest even bit count with 2^k >= n
+    hipLaunchKernelGGL(ac_permute_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, fb_stream(stream), (long long)n, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), (uint32_t)draw, (uint32_t)(draw >> 32), k / 2, reinterpret_cast<long long *>(out));
+    FB_LAUNCH_CHECK();
+    return FB_OK;
 }
 
 extern "C" int fb_ac_rollout_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_ac_rollout_buffers *b, int n_envs, uint64_t seed,

@@ -84,6 +84,7 @@ __device__ __forceinline__ void fb_flag_wait(const unsigned long long *flag, uns
 #define FB_STREAM_NOISE 6u    // noisy nets' factorised noise, counter = (element, step_lo, 6, 2 step_hi + net) (fb_qnet_reset_noise)
 #define FB_STREAM_ENV_NOISE 7u  // per-env acting noise of noisy nets, counter = (env * nz + element, step_lo, 7, step_hi) (fb_qnet_act_nib_env_noise)
 #define FB_STREAM_POLICY 8u   // the policy's action draw of an actor-critic net, counter = (row, step_lo, 8, step_hi) (fb_qnet_act_policy_nib)
+#define FB_STREAM_PERM 9u     // the round function of PPO's minibatch permutation, counter = (R, draw_lo, 9, draw_hi) (fb_ac_permute)
 
 struct fb_u4 { uint32_t x, y, z, w; };
 
@@ -249,9 +250,16 @@ struct AcLossArgs {
     const uint8_t *act; const float *adv, *ret; float nt, cv, ce;      // nt = (float)n_total
     float *dl, *xs, *dhf;                                        // dl f32[B][16]: dz, dV, the loss terms (fb_ac.hip)
 };
-struct AcGradArgs { int B, FC, A; NetOff off; const float *dl, *xs, *dhf; float nt, cv, ce; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; };
+// PPO's loss launch (ppo_loss_kernel): A2C's arguments, the clip ranges, and the rollout's buffers read at sel[b] (sel NULL: at b)
+struct PpoLossArgs {
+    AcLossArgs a;
+    const long long *sel; const float *logp_old, *value_old; float eps, vclip;
+};
+// nterms: the loss terms of dl's columns 9 .. 9 + nterms - 1 that workgroup 0 sums: 3 for A2C (loss f32[4]), 5 for PPO (loss f32[6])
+struct AcGradArgs { int B, FC, A; NetOff off; const float *dl, *xs, *dhf; float nt, cv, ce; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; int nterms; };
 void fb_ac_launch_head(hipStream_t st, const void *args);
 void fb_ac_launch_loss(hipStream_t st, const void *args);
+void fb_ac_launch_ppo_loss(hipStream_t st, const void *args);
 void fb_ac_launch_grad(hipStream_t st, const void *args);
 int fb_qnet_is_ac(fb_qnet_t h);               // 1: an actor-critic net (fb_qnet_create_ac)
 // the checks of the two AC training calls (batch, n_total), `who` in the message; the scratch r / t rows the ring-fed trunk fills beside
@@ -260,6 +268,9 @@ int fb_qnet_ac_check_train(fb_qnet_t h, int batch, int64_t n_total, const char *
 void fb_qnet_ac_scratch(fb_qnet_t h, float **r, uint8_t **t);
 int fb_qnet_ac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const float *adv, const float *ret, int64_t n_total, float *loss,
                           float *flat_grad, void *stream);
+// the ring-fed PPO train step behind fb_ppo_train_from_replay's checks (sel NULL: the four buffers are read at b)
+int fb_qnet_ppo_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const int64_t *sel, const float *adv, const float *ret,
+                           const float *logp_old, const float *value_old, int64_t n_total, float *loss, float *flat_grad, void *stream);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);

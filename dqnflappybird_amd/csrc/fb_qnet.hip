@@ -343,14 +343,15 @@ __global__ __launch_bounds__(256) void conv1_pool_kernel(Slices sl, float *__res
     const int P = tile * 8 + (i >> 2), pos = i & 3;
     const int b = P / 100, rem = P - b * 100, py = rem / 10, px = rem - py * 10;
     const int oy = 2 * py + (pos >> 1), ox = 2 * px + (pos & 1);
+    const int bs = P < npool ? b : 0;        // the last tile's pixels past the slice read state 0 (zeroed by the select), as conv1_sp_kernel's do: b = count lies past the caller's states
     const uint4 *WB = reinterpret_cast<const uint4 *>(s.w1s) + hl * 32 + j;      // [part][ky][kq][h][co] x 16 B
     f32x16 acc = {0}, acl = {0};
 #pragma unroll 2
     for (int ky = 0; ky < 8; ky++) {
         const int iy = oy * 4 + ky - 2;
         const bool rowok = P < npool && iy >= 0 && iy < 80;
-        const uint8_t *row = NIB ? s.states + (size_t)b * FB_NIB_STRIDE + ((rowok ? iy : 0) + 2) * FB_NIB_PITCH + 4
-                                 : s.states + (((size_t)b * 80 + (rowok ? iy : 0)) * 80) * 4;
+        const uint8_t *row = NIB ? s.states + (size_t)bs * FB_NIB_STRIDE + ((rowok ? iy : 0) + 2) * FB_NIB_PITCH + 4
+                                 : s.states + (((size_t)bs * 80 + (rowok ? iy : 0)) * 80) * 4;
 #pragma unroll
         for (int kq = 0; kq < 2; kq++) {
             const int ix = ox * 4 - 2 + 4 * kq + 2 * hl;         // even: the pixel pair is inside or outside together
@@ -4029,6 +4030,7 @@ struct fb_qnet {
     // an actor-critic net (FB_ARCH_AC, fb_qnet_create_ac; kernels: fb_ac.hip): (c_v, c_e) of fb_qnet_set_ac; ac_dl: the loss kernel's
     // per-sample row [max_batch][16]; ac_xs: fc1 activations of s [max_batch][FC]; ac_r / ac_t: the rows the ring-fed trunk fills beside the actions
     float ac_cv, ac_ce;
+    float ppo_eps, ppo_vclip;        // PPO's clip ranges (fb_qnet_set_ppo): the ratio's epsilon, the value clip (0 = off)
     float *ac_dl, *ac_xs, *ac_r;
     uint8_t *ac_t;
 };
@@ -4187,6 +4189,7 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     memset(h, 0, sizeof(*h));
     h->md = MdPar{0.03f, 0.9f, -1.f};            // Munchausen-DQN, the paper's values (read by FB_ALGO_MDQN / _PER on a scalar net alone)
     h->ac_cv = 0.5f; h->ac_ce = 0.01f;           // A2C's value and entropy coefficients (read on an actor-critic net alone)
+    h->ppo_eps = 0.2f; h->ppo_vclip = 0.f;       // PPO's clip ranges (read by the PPO train steps of an actor-critic net alone)
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
     h->off = is_c51d(h) ? make_off_c51d(fc_width, n_actions, sup.N)
                         : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING || arch == FB_ARCH_AC);
@@ -4474,6 +4477,9 @@ struct Plan {
     // advantages, the returns and n_total (p.r / p.isw / p.gamma stay unset)
     float *ac_value, *ac_logits, *ac_logp; int ac_greedy;
     const float *ac_adv, *ac_ret; float ac_nt;
+    // a PPO train plan of an actor-critic net: the clipped-surrogate loss instead of A2C's; the rollout's log-probabilities and values;
+    // ppo_sel (or NULL): where sample b reads ac_adv / ac_ret / ppo_logp / ppo_value
+    bool ppo; const float *ppo_logp, *ppo_value; const long long *ppo_sel;
 };
 
 // A runtime value as a template argument: f is a generic lambda and gets a tag whose ::value is a constant expression, so that a kernel
@@ -4699,9 +4705,12 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         L.hf = h->hf; L.P = h->params[0]; L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B; L.off = h->off;
         L.act = p.a; L.adv = p.ac_adv; L.ret = p.ac_ret; L.nt = p.ac_nt; L.cv = h->ac_cv; L.ce = h->ac_ce;
         L.dl = h->ac_dl; L.xs = h->ac_xs; L.dhf = h->dhf;
-        fb_ac_launch_loss(c.st, &L);
+        if (p.ppo) {
+            const PpoLossArgs P{L, p.ppo_sel, p.ppo_logp, p.ppo_value, h->ppo_eps, h->ppo_vclip};
+            fb_ac_launch_ppo_loss(c.st, &P);
+        } else fb_ac_launch_loss(c.st, &L);
         const AcGradArgs gA{B, FC, h->A, h->off, h->ac_dl, h->ac_xs, h->dhf, p.ac_nt, h->ac_cv, h->ac_ce, p.G, p.loss, h->gmax,
-                            reinterpret_cast<FbAdamHead *>(h->adam), p.tick};
+                            reinterpret_cast<FbAdamHead *>(h->adam), p.tick, p.ppo ? 5 : 3};
         fb_ac_launch_grad(c.st, &gA);
         return;
     }
@@ -5458,6 +5467,53 @@ int fb_qnet_ac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const float
     const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_ac_train_from_replay");
     if (rc != FB_OK) return rc;
     Plan p = ac_train_plan(h, B, nullptr, ring->a, adv, ret, n_total, loss, flat_grad, ring);
+    return run_train(h, p, stream);
+}
+
+// ---- PPO on an actor-critic net (include/fbdqn.h; kernels: fb_ac.hip): A2C's plan with the clipped-surrogate loss launch
+extern "C" int fb_qnet_set_ppo(fb_qnet_t h, float clip_eps, float value_clip) {
+    FB_REQUIRE(h, "fb_qnet_set_ppo: NULL handle");
+    FB_REQUIRE(is_ac(h), "fb_qnet_set_ppo: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(isfinite(clip_eps) && clip_eps > 0.f, "fb_qnet_set_ppo: clip_eps must be finite and > 0 (got %g)", (double)clip_eps);
+    FB_REQUIRE(isfinite(value_clip) && value_clip >= 0.f, "fb_qnet_set_ppo: value_clip must be finite and >= 0 (got %g)", (double)value_clip);
+    h->ppo_eps = clip_eps; h->ppo_vclip = value_clip;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_ppo(fb_qnet_t h, float *clip_eps_host, float *value_clip_host) {
+    FB_REQUIRE(h, "fb_qnet_get_ppo: NULL handle");
+    FB_REQUIRE(is_ac(h), "fb_qnet_get_ppo: not an actor-critic net (fb_qnet_create_ac)");
+    if (clip_eps_host) *clip_eps_host = h->ppo_eps;
+    if (value_clip_host) *value_clip_host = h->ppo_vclip;
+    return FB_OK;
+}
+
+static Plan ppo_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const int64_t *sel, const float *adv, const float *ret,
+                           const float *logp_old, const float *value_old, int64_t n_total, float *loss, float *flat_grad, const FbRingSrc *ring) {
+    Plan p = ac_train_plan(h, B, s, a, adv, ret, n_total, loss, flat_grad, ring);
+    p.ppo = true; p.ppo_logp = logp_old; p.ppo_value = value_old; p.ppo_sel = reinterpret_cast<const long long *>(sel);
+    return p;
+}
+
+extern "C" int fb_qnet_ppo_train_step(fb_qnet_t h, int B, const uint8_t *s, const uint8_t *a, const float *adv, const float *ret,
+                                      const float *logp_old, const float *value_old, int64_t n_total, float *loss, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && s && a && adv && ret && logp_old && value_old && loss, "fb_qnet_ppo_train_step: NULL argument");
+    const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_qnet_ppo_train_step");
+    if (rc != FB_OK) return rc;
+    Plan p = ppo_train_plan(h, B, s, a, nullptr, adv, ret, logp_old, value_old, n_total, loss, flat_grad, nullptr);
+    if (B >= 256) {                              // (as fb_qnet_ac_train_step)
+        const int rp = fb_qnet_refresh_planes(h, stream);
+        if (rp != FB_OK) return rp;
+    }
+    return run_train(h, p, stream);
+}
+
+int fb_qnet_ppo_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const int64_t *sel, const float *adv, const float *ret,
+                           const float *logp_old, const float *value_old, int64_t n_total, float *loss, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && ring && ring->idx && ring->a && adv && ret && logp_old && value_old && loss, "fb_ppo_train_from_replay: NULL argument");
+    const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_ppo_train_from_replay");
+    if (rc != FB_OK) return rc;
+    Plan p = ppo_train_plan(h, B, nullptr, ring->a, sel, adv, ret, logp_old, value_old, n_total, loss, flat_grad, ring);
     return run_train(h, p, stream);
 }
 

@@ -301,6 +301,7 @@ NOISY_DEFAULT_SIGMA0 = 0.5                                # noisy nets: sigma = 
 AC_ARCH = "ac"                                            # advantage actor-critic: V and the policy's logits on the shared trunk (include/fbdqn.h)
 AC_DEFAULTS = L.AC_DEFAULTS                               # (value_coef, entropy_coef) of a new actor-critic net
 AC_MAX_ROLLOUT = 128                                      # the longest rollout VecActorCritic takes
+PPO_DEFAULTS = L.PPO_DEFAULTS                             # (clip_eps, value_clip) of a new actor-critic net
 
 
 def check_sigma0(sigma0):
@@ -364,6 +365,17 @@ def check_ac(value_coef, entropy_coef):
     if not (np.isfinite(ce) and ce >= 0.0):
         raise ValueError(f"entropy_coef must be finite and >= 0, got {entropy_coef}")
     return cv, ce
+
+
+def check_ppo(clip_eps, value_clip):
+    """the argument checks of fb_qnet_set_ppo, on the host (-> (clip_eps, value_clip) as float32-rounded floats; value_clip 0 = off)"""
+    with np.errstate(over="ignore"):
+        e, c = float(np.float32(clip_eps)), float(np.float32(value_clip))
+    if not (np.isfinite(e) and e > 0.0):
+        raise ValueError(f"clip_eps must be finite and > 0, got {clip_eps}")
+    if not (np.isfinite(c) and c >= 0.0):
+        raise ValueError(f"value_clip must be finite and >= 0, got {value_clip}")
+    return e, c
 
 
 def check_gae(gamma, gae_lambda):
@@ -688,6 +700,36 @@ class QNet:
                                               L.ptr(flat_grad), L.current_stream()), "fb_qnet_ac_train_step")
         return loss
 
+    def set_ppo(self, clip_eps=PPO_DEFAULTS[0], value_clip=PPO_DEFAULTS[1]):
+        """PPO's clip ranges (fb_qnet_set_ppo): the ratio is clipped to [1 - clip_eps, 1 + clip_eps]; value_clip > 0 clips the value
+        around the rollout's, 0 = off.  The loss's coefficients are set_ac's"""
+        self._need_ac("set_ppo")
+        e, c = check_ppo(clip_eps, value_clip)
+        L.check(L.lib().fb_qnet_set_ppo(self.h, e, c), "fb_qnet_set_ppo")
+
+    def ppo(self):
+        """the net's current (clip_eps, value_clip) (fb_qnet_get_ppo)"""
+        self._need_ac("ppo")
+        e, c = C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_get_ppo(self.h, C.byref(e), C.byref(c)), "fb_qnet_get_ppo")
+        return e.value, c.value
+
+    def ppo_train_step(self, s, a, adv, ret, logp_old, value_old, n_total=None, flat_grad=None):
+        """one PPO step on <= 256 gathered states (fb_qnet_ppo_train_step): logp_old / value_old are the rollout's log-probabilities
+        and values, n_total = the minibatch's sample count (default: this chunk's).  flat_grad as for ac_train_step.
+        -> loss f32[6] (device): the chunk's share of (total, policy, value, entropy, clip fraction, approximate KL)"""
+        self._need_ac("ppo_train_step")
+        _dev_check(s, a, adv, ret, logp_old, value_old, flat_grad)
+        if s.dtype != torch.uint8 or s.dim() != 4 or tuple(s.shape[1:]) != (80, 80, 4):
+            raise ValueError("s must be uint8[B,80,80,4]")
+        B = s.shape[0]
+        check_chunk(B, a, n_total, flat_grad, self.n_params)
+        check_ppo_batch(B, None, adv, ret, logp_old, value_old)
+        loss = torch.zeros(6, dtype=torch.float32, device=self.device)
+        L.check(L.lib().fb_qnet_ppo_train_step(self.h, B, L.ptr(s), L.ptr(a), L.ptr(adv), L.ptr(ret), L.ptr(logp_old), L.ptr(value_old),
+                                               int(n_total or B), L.ptr(loss), L.ptr(flat_grad), L.current_stream()), "fb_qnet_ppo_train_step")
+        return loss
+
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):
         if not self.noisy:
@@ -866,19 +908,24 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
     return (loss, a, r, t, ae) if want_abs_err else (loss, a, r, t)
 
 
-def check_ac_batch(B, a, adv, ret, n_total, flat_grad, n_params):
-    """the shape checks of the two A2C training calls, on the host"""
+def check_chunk(B, a, n_total, flat_grad, n_params):
+    """what the A2C and the PPO training calls check alike, on the host: the chunk's size, its actions, n_total, the gradient buffer"""
     if not 1 <= B <= 256:
         raise ValueError(f"an A2C chunk holds 1..256 samples, got {B}")
     if a is not None and (a.dtype != torch.uint8 or a.numel() != B):
         raise ValueError(f"a must be uint8[{B}]")
-    for name, t in (("adv", adv), ("ret", ret)):
-        if t.dtype != torch.float32 or t.numel() != B:
-            raise ValueError(f"{name} must be float32[{B}]")
     if n_total is not None and int(n_total) < B:
         raise ValueError(f"n_total = {n_total} must be the whole update's sample count (>= the chunk's {B})")
     if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
         raise ValueError(f"flat_grad must be float32[{n_params}]")
+
+
+def check_ac_batch(B, a, adv, ret, n_total, flat_grad, n_params):
+    """the shape checks of the two A2C training calls, on the host"""
+    check_chunk(B, a, n_total, flat_grad, n_params)
+    for name, t in (("adv", adv), ("ret", ret)):
+        if t.dtype != torch.float32 or t.numel() != B:
+            raise ValueError(f"{name} must be float32[{B}]")
 
 
 def ac_gae(reward, terminal, value, gamma=0.99, gae_lambda=0.95):
@@ -915,6 +962,73 @@ def ac_train_from_replay(replay, net, idx, adv, ret, n_total=None, flat_grad=Non
     L.check(L.lib().fb_ac_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(adv), L.ptr(ret), int(n_total or B), L.ptr(a), L.ptr(loss),
                                             L.ptr(flat_grad), L.current_stream()), "fb_ac_train_from_replay")
     return loss, a
+
+
+def check_ppo_batch(B, sel, adv, ret, logp_old, value_old):
+    """the shape checks PPO's training calls add to check_ac_batch's: without sel the four buffers hold the chunk's B samples, with sel
+    (int64[B]) they are the rollout's, of one length, read at sel[b]"""
+    if sel is not None and (sel.dtype != torch.int64 or sel.numel() != B):
+        raise ValueError(f"sel must be int64[{B}]")
+    n = B if sel is None else int(adv.numel())
+    if n < 1:
+        raise ValueError("adv is empty")
+    for name, t in (("adv", adv), ("ret", ret), ("logp_old", logp_old), ("value_old", value_old)):
+        if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous float32[{n}]")
+
+
+def ppo_train_from_replay(replay, net, idx, adv, ret, logp_old, value_old, sel=None, n_total=None, flat_grad=None, check_sel=True):
+    """QNet.ppo_train_step on the transitions at the deque positions idx of a uniform memory, read from its frame ring in place
+    (fb_ppo_train_from_replay).  sel int64[B]: sample b reads adv / ret / logp_old / value_old (the rollout's flattened buffers, one
+    length) at sel[b].  The library takes sel as it comes (its ABI carries no length), so sel is checked against the buffers here.
+    THAT CHECK IS A HOST SYNC ON EVERY CALL WITH sel (it reads sel back from the device and waits for the stream): a loop, or anyone
+    who times this call, passes check_sel=False, which is safe for a sel that is in range by construction (a permutation's slice:
+    VecActorCritic, tools/time_ppo.py).  -> (loss f32[6], a u8[B]: the ring's actions)"""
+    if net.arch != AC_ARCH:
+        raise ValueError("ppo_train_from_replay needs an actor-critic net (QNet(..., arch='ac'))")
+    if replay.prioritized:
+        raise ValueError("ppo_train_from_replay reads the rollout from a uniform memory only")
+    _dev_check(idx, sel, adv, ret, logp_old, value_old, flat_grad)
+    if idx.dtype != torch.int64:
+        raise ValueError("idx must be int64[B]")
+    B, dev = int(idx.numel()), idx.device
+    check_chunk(B, None, n_total, flat_grad, net.n_params)
+    check_ppo_batch(B, sel, adv, ret, logp_old, value_old)
+    if sel is not None and check_sel and not bool(((sel >= 0) & (sel < adv.numel())).all()):      # (reads sel back: one host sync)
+        raise ValueError(f"sel must lie in 0..{adv.numel() - 1}, the rollout buffers' positions")
+    a = torch.empty(B, dtype=torch.uint8, device=dev)
+    loss = torch.zeros(6, dtype=torch.float32, device=dev)
+    L.check(L.lib().fb_ppo_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(sel), L.ptr(adv), L.ptr(ret), L.ptr(logp_old), L.ptr(value_old),
+                                             int(n_total or B), L.ptr(a), L.ptr(loss), L.ptr(flat_grad), L.current_stream()),
+            "fb_ppo_train_from_replay")
+    return loss, a
+
+
+def ac_normalize_adv(adv, out=None):
+    """the rollout's advantages to mean 0 and standard deviation 1 on the device (fb_ac_normalize_adv: float64, the order
+    include/fbdqn.h pins) -> out (a new tensor of adv's shape; out=adv normalises in place)"""
+    _dev_check(adv, out)
+    if adv.dtype != torch.float32 or adv.numel() < 1 or not adv.is_contiguous():
+        raise ValueError("adv must be a contiguous, non-empty float32 tensor")
+    out = torch.empty_like(adv) if out is None else out
+    if out.dtype != torch.float32 or out.numel() != adv.numel() or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32[{adv.numel()}]")
+    L.check(L.lib().fb_ac_normalize_adv(L.ptr(adv), int(adv.numel()), L.ptr(out), L.current_stream()), "fb_ac_normalize_adv")
+    return out
+
+
+def ac_permute(n, seed=0, draw=0, out=None, device="cuda"):
+    """a permutation of range(n) as int64[n] on the device, a function of (n, seed, draw) alone (fb_ac_permute: a keyed Feistel
+    network over Philox, cycle-walked; no state)"""
+    n = int(n)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"n must be in 1..2^31 - 1, got {n}")
+    _dev_check(out)
+    out = torch.empty(n, dtype=torch.int64, device=device) if out is None else out
+    if out.dtype != torch.int64 or out.numel() != n or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous int64[{n}]")
+    L.check(L.lib().fb_ac_permute(n, int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1), L.ptr(out), L.current_stream()), "fb_ac_permute")
+    return out
 
 
 class AcRolloutStep:

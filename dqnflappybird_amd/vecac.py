@@ -1,17 +1,22 @@
-"""VecActorCritic: synchronous advantage actor-critic (A2C) on the vectorised loop, entirely device resident.
+"""VecActorCritic: synchronous advantage actor-critic (A2C), or PPO on the same rollout, on the vectorised loop, entirely device resident.
 
     update:  T x [sample the policy for N envs -> frame_step -> store]   (AcRolloutStep, one host call each)
              -> V(s_T) with the weights the rollout acted with -> GAE (vec.ac_gae)
              -> the T N fresh transitions in ring-fed chunks of <= 256 (vec.ac_train_from_replay), gradients summed
              -> [clip the sum] -> Adam, once
 
+    algo="ppo" replaces the last two lines: [normalise the advantages (vec.ac_normalize_adv)] -> K epochs x [a fresh permutation of
+             the T N transitions (vec.ac_permute) -> M minibatches x [ring-fed chunks of <= 256 read through the permutation
+             (vec.ppo_train_from_replay), gradients summed -> [clip] -> Adam]]
+
 The replay memory is not sampled: its frame ring is the rollout's state store (the newest T N deque positions are the rollout,
 in the order of the flattened [T, N] buffers), so no state is ever copied.  One net, one GPU; include/fbdqn.h pins the
-semantics, DESIGN.md section 16 the schedule.  The reference's actor-critic (BrainActorCritic.py: one env, one episode, a second
+semantics, DESIGN.md section 16 the schedule (section 17: PPO).  The reference's actor-critic (BrainActorCritic.py: one env, one episode, a second
 network as the critic) stays what --model actorcritic runs; this is the batched algorithm its capacity is for.
 """
 import numpy as np
 
+ALGOS = ("a2c", "ppo")                                       # what VecActorCritic(algo=...) takes
 AC_HEAD = "ac"                                               # what a checkpoint of this class records as its head
 CHUNK = 256                                                  # samples per ring-fed train chunk (the train step's limit)
 
@@ -37,15 +42,38 @@ def check_args(n_envs, rollout, gamma, gae_lambda, value_coef, entropy_coef, max
     return n, T, g, l, cv, ce, check_max_grad_norm(max_grad_norm)
 
 
+def check_ppo_args(n_envs, rollout, epochs, minibatches, clip_eps, value_clip):
+    """every argument check of VecActorCritic(algo='ppo') that needs no GPU -> (epochs, minibatches, clip_eps, value_clip)"""
+    from .vec import check_ppo
+    k, m, tn = int(epochs), int(minibatches), int(rollout) * int(n_envs)
+    if k < 1:
+        raise ValueError(f"epochs must be >= 1, got {epochs}")
+    if m < 1 or tn % m:
+        raise ValueError(f"minibatches must be >= 1 and divide rollout x n_envs = {tn}, got {minibatches}")
+    return (k, m) + check_ppo(clip_eps, value_clip)
+
+
 class VecActorCritic:
     def __init__(self, n_envs, rollout=5, gamma=0.99, gae_lambda=0.95, value_coef=0.5, entropy_coef=0.01, max_grad_norm=0.0, fc_width=512,
-                 seed=0, lr=1e-4, capacity=None):
+                 seed=0, lr=1e-4, capacity=None, algo="a2c", epochs=4, minibatches=4, clip_eps=0.2, value_clip=0.0, normalize_adv=True):
         """n_envs games, `rollout` steps per update (1..128), GAE(gamma, gae_lambda), loss = mean(L_pi + value_coef L_v - entropy_coef H)
         over the rollout's rollout x n_envs samples, max_grad_norm=G > 0 clips the summed gradient's global norm before Adam, lr is
         Adam's (the other hyper-parameters are the library's TF defaults).  capacity: the memory's, at least (rollout + 2) n_envs (the
-        default); it only has to hold the rollout."""
+        default); it only has to hold the rollout.
+        algo='ppo': each rollout trains `epochs` passes of `minibatches` shuffled minibatches (it must divide rollout x n_envs), an Adam
+        step each, under the ratio clip clip_eps and the value clip value_clip (0 = off); normalize_adv: the rollout's advantages to
+        mean 0, standard deviation 1 first.  algo='a2c' reads none of the five."""
+        if algo not in ALGOS:
+            raise ValueError(f"algo must be one of {ALGOS}, got {algo!r}")
+        self.algo = algo
         self.n, self.T, self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm = check_args(
             n_envs, rollout, gamma, gae_lambda, value_coef, entropy_coef, max_grad_norm)
+        self.normalize_adv = bool(normalize_adv)
+        if algo == "ppo":
+            self.epochs, self.minibatches, self.clip_eps, self.value_clip = check_ppo_args(self.n, self.T, epochs, minibatches, clip_eps, value_clip)
+        else:                                                # (A2C reads none of them: the net keeps the library's defaults)
+            from .vec import PPO_DEFAULTS
+            self.epochs, self.minibatches, self.clip_eps, self.value_clip = (1, 1) + PPO_DEFAULTS
         need = (self.T + 2) * self.n
         self.capacity = need if capacity is None else int(capacity)
         if self.capacity < need:
@@ -63,6 +91,8 @@ class VecActorCritic:
         self.net = QNet(2, self.fc_width, "ac", max_batch=max(self.n, CHUNK))
         self.net.set_ac(self.value_coef, self.entropy_coef)
         self.net.set_hparams(lr=self.lr)
+        if self.algo == "ppo":
+            self.net.set_ppo(self.clip_eps, self.value_clip)
         if self.max_grad_norm:
             self.net.set_max_grad_norm(self.max_grad_norm)
         self.net.init_params(seed=self.seed, which=0)
@@ -74,7 +104,8 @@ class VecActorCritic:
         self.roll = AcRolloutStep(self.env, self.replay, self.net, self.T)
         self.grad = torch.zeros(self.net.n_params, dtype=torch.float32, device="cuda")
         self.chunk_grad = torch.zeros_like(self.grad)
-        self.losses = torch.zeros(4, dtype=torch.float32, device="cuda")
+        self.losses = torch.zeros(6 if self.algo == "ppo" else 4, dtype=torch.float32, device="cuda")
+        self.perm = torch.zeros(self.T * self.n, dtype=torch.int64, device="cuda") if self.algo == "ppo" else None
         self.timeStep = 0                                    # env steps per env so far: the key of the policy's draws
         self.updates = 0
         self.pushes = 0                                      # pushes since the reset: len(replay) without a device sync
@@ -88,17 +119,26 @@ class VecActorCritic:
             self._idx_for = size
         return self._idx
 
-    def update(self):
-        """one A2C update: the rollout, the advantages, the chunks, Adam -> the update's four loss numbers f32[4] (device)"""
-        from .vec import ac_gae, ac_train_from_replay
+    def collect(self):
+        """the rollout: T steps of the N envs with the current policy, V(s_T), GAE -> (adv, ret), float32[T N] each, in the order of the
+        flattened [T, N] buffers (self.roll holds the rollout's rewards, terminals, values and log-probabilities)"""
+        from .vec import ac_gae
         for t in range(self.T):
             self.roll(t, seed=self.seed, step=self.timeStep)
             self.timeStep += 1
             self.pushes += 1
         self.net.act_policy_nib(self.nib, value=self.roll.value[self.T], value_only=True)      # V(s_T), the pre-update weights
         adv, ret = ac_gae(self.roll.reward, self.roll.terminal, self.roll.value, self.gamma, self.gae_lambda)
-        adv, ret = adv.view(-1), ret.view(-1)
+        return adv.view(-1), ret.view(-1)
+
+    def update(self):
+        """one update: the rollout, the advantages, then A2C's chunks and one Adam step -> the update's four loss numbers f32[4], or
+        PPO's epochs of minibatches, an Adam step each -> the last epoch's six loss numbers f32[6], its minibatches' mean (device)"""
+        from .vec import ac_train_from_replay
+        adv, ret = self.collect()
         idx, tn = self._indices(), self.T * self.n
+        if self.algo == "ppo":
+            return self._ppo_epochs(idx, adv, ret, tn)
         self.grad.zero_()
         self.losses.zero_()
         for k in range(0, tn, CHUNK):
@@ -109,6 +149,37 @@ class VecActorCritic:
         if self.max_grad_norm:
             self.net.clip_grad(self.grad)
         self.net.apply_adam(self.grad)
+        self.updates += 1
+        return self.losses
+
+    def _ppo_epochs(self, idx, adv, ret, tn):
+        """K epochs over the rollout: epoch e shuffles with the permutation of draw updates K + e (no state beyond the counter); a
+        minibatch is tn / M consecutive elements of it, read in ring-fed chunks of <= 256: the states at idx[0] + perm, the rollout's
+        advantages, returns, log-probabilities and values at perm"""
+        from .vec import ac_normalize_adv, ac_permute, ppo_train_from_replay
+        if self.normalize_adv:
+            ac_normalize_adv(adv, out=adv)
+        logp, value = self.roll.logp.view(-1), self.roll.value[:self.T].view(-1)
+        mb = tn // self.minibatches
+        for e in range(self.epochs):
+            perm = ac_permute(tn, self.seed, self.updates * self.epochs + e, out=self.perm)
+            pos = perm + idx[:1]                             # (the rollout's deque positions are consecutive: rollout_indices)
+            last = e == self.epochs - 1
+            if last:
+                self.losses.zero_()
+            for lo in range(0, tn, mb):
+                self.grad.zero_()
+                for k in range(lo, lo + mb, CHUNK):
+                    hi = min(k + CHUNK, lo + mb)
+                    loss, _ = ppo_train_from_replay(self.replay, self.net, pos[k:hi], adv, ret, logp, value, sel=perm[k:hi], n_total=mb,
+                                                    flat_grad=self.chunk_grad, check_sel=False)      # (a permutation's slice)
+                    self.grad += self.chunk_grad
+                    if last:
+                        self.losses += loss
+                if self.max_grad_norm:
+                    self.net.clip_grad(self.grad)
+                self.net.apply_adam(self.grad)
+        self.losses /= self.minibatches
         self.updates += 1
         return self.losses
 
@@ -125,14 +196,18 @@ class VecActorCritic:
 
     def save(self, path):
         """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory,
-        the counters and the A2C settings; `head` = 'ac' tells the file from a VecBrain's"""
+        the counters and the A2C settings; `head` = 'ac' tells the file from a VecBrain's, and a PPO run adds its settings as `ppo`
+        (epochs, minibatches, clip_eps, value_clip, normalize_adv): the permutations have no state beyond the update counter"""
+        extra = {}
+        if self.algo == "ppo":
+            extra["ppo"] = np.array([self.epochs, self.minibatches, self.clip_eps, self.value_clip, float(self.normalize_adv)], np.float64)
         host = lambda t: t.cpu().numpy()
         m, v, pows = self.net.adam_state()
         np.savez(self._npz(path), head=np.array([AC_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
                  adam_m=host(m), adam_v=host(v), beta_pows=np.asarray(pows, np.float32),
                  scalars=np.array([self.timeStep, self.updates, self.pushes, self.seed, self.n, self.T, self.fc_width], np.int64),
                  ac=np.array([self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm, self.lr], np.float64),
-                 env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob())
+                 env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob(), **extra)
 
     def load(self, path):
         """the inverse of save(), into a VecActorCritic made with the same n_envs, rollout, fc_width, capacity and seed (the envs' pipe-gap
@@ -143,6 +218,10 @@ class VecActorCritic:
         head = checkpoint_head(z)
         if head != AC_HEAD:
             raise ValueError(f"checkpoint {path} holds a {head} head (a VecBrain's), this is a VecActorCritic (head {AC_HEAD!r})")
+        kind = "ppo" if "ppo" in z.files else "a2c"
+        if kind != self.algo:
+            raise ValueError(f"checkpoint {path} holds {'a PPO' if kind == 'ppo' else 'an A2C'} run, this VecActorCritic runs "
+                             f"algo={self.algo!r}")
         sc = [int(x) for x in z["scalars"]]
         if (sc[4], sc[5], sc[6]) != (self.n, self.T, self.fc_width):
             raise ValueError(f"checkpoint {path} was written with (n_envs, rollout, fc_width) = {tuple(sc[4:7])}, this VecActorCritic has "
@@ -158,6 +237,11 @@ class VecActorCritic:
         self.net.set_ac(self.value_coef, self.entropy_coef)
         self.net.set_hparams(lr=self.lr)
         self.net.set_max_grad_norm(self.max_grad_norm)
+        if self.algo == "ppo":
+            k, m, eps, vclip, norm = (float(x) for x in z["ppo"])
+            self.epochs, self.minibatches, self.clip_eps, self.value_clip = check_ppo_args(self.n, self.T, int(k), int(m), eps, vclip)
+            self.normalize_adv = bool(norm)
+            self.net.set_ppo(self.clip_eps, self.value_clip)
         self.env.set_state(z["env_state"])
         self.nib.copy_(dev(z["nib"]))
         self.stats[...] = dev(z["stats"])
@@ -170,13 +254,15 @@ class VecActorCritic:
         for i in range(updates):
             losses = self.update()
             if log_every and (i + 1) % log_every == 0:
-                tot, lpi, lv, ent = losses.tolist()              # the only host sync of the loop, once per log line
+                tot, lpi, lv, ent, *more = losses.tolist()       # the only host sync of the loop, once per log line
                 ep, ssum, smax, pipes = self.stats.tolist()
                 self.net.check_range()
                 clip = ""
                 if self.max_grad_norm:
                     norm, scale = self.net.grad_norm()
                     clip = f" / GRAD_NORM {norm:.6g} / CLIP_SCALE {scale:.6g}"
+                if more:                                         # PPO
+                    clip += f" / CLIP_FRAC {more[0]:.6g} / APPROX_KL {more[1]:.6g}"
                 print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / POLICY_LOSS {lpi:.6g} / VALUE_LOSS {lv:.6g} / ENTROPY {ent:.6g} / "
                       f"GAME_TIMES {ep} / MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {tot:.6g}{clip}",
                       flush=True)

@@ -598,8 +598,8 @@ int fb_qnet_soft_sync_target(fb_qnet_t h, float rho, void *stream);
  *               fb_train_steps / fb_vec_step / fb_vec_step_dp, fb_qnet_set_huber / _get_huber, fb_qnet_set_munchausen / _get_munchausen,
  *               FB_DTYPE_BF16 for inference or training; fb_qnet_create with arch 6 and fb_qnet_create_c51_noisy with it (no noisy AC net);
  *               every fb_qnet_*_ac / fb_ac_* call below on a net that is not an AC net.
- *   not offered PPO (logp is stored so that it can follow), data-parallel A2C, bf16, riders or the split schedule for the rollout step,
- *               noisy or distributional critics.
+ *   not offered data-parallel A2C, bf16, riders or the split schedule for the rollout step, noisy or distributional critics.  (PPO on the
+ *               same rollout: the block below.)
  * fb_qnet_set_ac / fb_qnet_get_ac: (c_v, c_e), 0.5 and 0.01 in a new net; both finite and >= 0.  A host-side setting read by the calls issued
  *   after it. */
 #define FB_ARCH_AC 6
@@ -629,6 +629,50 @@ int fb_ac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const 
                             int64_t n_total, uint8_t *a_out, float *loss, float *flat_grad, void *stream);
 int fb_ac_rollout_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_ac_rollout_buffers *b, int n_envs, uint64_t seed,
                        uint64_t step, int slot, void *stream);
+
+/* ------------------------------------------------------------------ PPO (Schulman et al. 2017) on the actor-critic rollout
+ * The clipped-surrogate update on an AC net: the rollout, V(s_T) and fb_ac_gae as for A2C, then K epochs of shuffled minibatches over the
+ * SAME T N transitions, each an Adam step.  One GPU, fp32, a uniform memory at n-step 1, as A2C.  z, V, p, log p, H are formed exactly
+ * as in the A2C block; a is the batch's action (the ring's in the ring-fed call); an action >= A reads action A - 1.
+ *   settings    fb_qnet_set_ppo / fb_qnet_get_ppo: (clip_eps, value_clip), 0.2 and 0 in a new AC net; clip_eps finite and > 0, value_clip
+ *               finite and >= 0 (0 = the value term is not clipped).  Host-side settings read by the calls issued after them, like
+ *               fb_qnet_set_ac, whose (c_v, c_e) PPO reads too
+ *   loss        per sample b of a chunk, N_tot = n_total (the MINIBATCH's sample count), fp32, eps = clip_eps:
+ *                 lr = log p_a - logp_old      r = expf(lr)      lo = 1 - eps      hi = 1 + eps
+ *                 s1 = r adv      s2 = fminf(fmaxf(r, lo), hi) adv      L_pi = -fminf(s1, s2)      w = (s1 <= s2) ? s1 : 0
+ *                 dLoss/dz_c = (w (p_c - 1{c = a}) + c_e p_c (log p_c + H)) / N_tot
+ *                 e1 = V - ret      d = V - value_old
+ *                 value_clip == 0 or |d| <= value_clip:   L_v = e1^2      dLoss/dV = 2 c_v e1 / N_tot      (value_old + d is never formed)
+ *                 otherwise:  e2 = (value_old + copysignf(value_clip, d)) - ret      L_v = fmaxf(e1^2, e2^2)
+ *                             dLoss/dV = (e1^2 >= e2^2) ? 2 c_v e1 / N_tot : 0
+ *               loss[0..5] = the chunk's share of {total = L_pi + c_v L_v - c_e H, sum L_pi / N_tot, sum L_v / N_tot, sum H / N_tot,
+ *               clip fraction = sum 1{r < lo or r > hi} / N_tot, approximate KL = sum ((r - 1) - lr) / N_tot}; sums over b in ascending
+ *               order, no atomics: equal inputs give equal bits
+ *   training    fb_qnet_ppo_train_step on gathered states, fb_ppo_train_from_replay on ring positions idx (as fb_ac_train_from_replay):
+ *               1 <= batch <= min(max_batch, 256), n_total >= batch; adv, ret, logp_old, value_old f32; loss f32[6]; flat_grad as for A2C
+ *               (NULL: Adam at once, with the net's clipping; else the chunk's gradient is exported only).  sel (ring-fed call) i64[batch]
+ *               or NULL: sample b reads adv, ret, logp_old and value_old at sel[b] (NULL: at b), so a shuffled minibatch reads the
+ *               flattened [T N] rollout buffers in place; the caller keeps every sel[b] inside them
+ *   normalise   fb_ac_normalize_adv, per rollout, in double: thread t of ONE 256-thread workgroup sums the elements i = t (mod 256) in
+ *               ascending i (from 0.0), one thread adds the 256 partial sums in ascending t: S; mean = S / n; the same two-level sum of
+ *               (x - mean)^2: Q; sd = sqrt(Q / n); out[i] = (float)(((double)x_i - mean) / (sd + 1e-8)).  out may be adv.  1 <= n < 2^31
+ *   shuffle     fb_ac_permute(n, seed, draw, out): out i64[n] is a permutation of [0, n), a function of (n, seed, draw) alone.  k = the
+ *               smallest even bit count with 2^k >= n (k >= 2), half = k / 2, mask = 2^half - 1, x = (L << half) | R; four Feistel
+ *               rounds r = 0 .. 3: (L, R) <- (R, L ^ (F_r(R) & mask)), F_r(R) = word r (x, y, z, w) of Philox4x32-10(key = (seed_lo,
+ *               seed_hi), counter = (R, draw_lo, FB_STREAM_PERM = 9, draw_hi)); out[i] = the first value below n of i's images under
+ *               repeated application (cycle walking: the network is a bijection of [0, 2^k), and 2^k < 4 n).  1 <= n < 2^31
+ *   refused     FB_ERR_INVALID before any launch or counter change: fb_qnet_set_ppo / _get_ppo / fb_qnet_ppo_train_step /
+ *               fb_ppo_train_from_replay on a net that is not an AC net; a prioritized or n-step memory; the batch and n_total rules above
+ *   not offered data-parallel PPO, bf16, per-minibatch advantage normalisation, KL early stopping, annealing, recurrent policies. */
+int fb_qnet_set_ppo(fb_qnet_t h, float clip_eps, float value_clip);
+int fb_qnet_get_ppo(fb_qnet_t h, float *clip_eps_host, float *value_clip_host);
+int fb_qnet_ppo_train_step(fb_qnet_t h, int batch, const uint8_t *s, const uint8_t *a, const float *adv, const float *ret,
+                           const float *logp_old, const float *value_old, int64_t n_total, float *loss /*f32[6]*/, float *flat_grad, void *stream);
+int fb_ppo_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const int64_t *sel, const float *adv,
+                             const float *ret, const float *logp_old, const float *value_old, int64_t n_total, uint8_t *a_out,
+                             float *loss /*f32[6]*/, float *flat_grad, void *stream);
+int fb_ac_normalize_adv(const float *adv, int64_t n, float *out, void *stream);
+int fb_ac_permute(int64_t n, uint64_t seed, uint64_t draw, int64_t *out, void *stream);
 
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
