@@ -116,7 +116,8 @@ def build_parser():
     parser.add_argument("--n-quantiles", type=int, default=None, help="QR models: the number of quantiles N (default 51)")
     parser.add_argument("--kappa", type=float, default=None, help="QR models: the quantile Huber loss's threshold (default 1)")
     parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper: the softmax temperature (default 0.03)")
-    parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9)")
+    parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9); "
+                                                                   "--model sac: the temperature (default 0.2)")
     parser.add_argument("--clip", type=float, default=None, help="--model mdqn | mdqnper: the bonus's lower clip l0 (default -1)")
     parser.add_argument("--huber", type=float, default=None, help="scalar-head models with --vec: the Huber loss's delta (default 0 = the squared loss)")
     parser.add_argument("--max-grad-norm", type=float, default=None, help="--vec: clip the gradient's global norm to G before Adam (default 0 = no clipping)")
@@ -131,7 +132,35 @@ def build_parser():
     parser.add_argument("--clip-eps", type=float, default=None, help="--model ppo: the probability ratio is clipped to [1 - E, 1 + E] (default 0.2)")
     parser.add_argument("--value-clip", type=float, default=None, help="--model ppo: clip the value around the rollout's by C (default 0 = off)")
     parser.add_argument("--no-adv-norm", action="store_true", help="--model ppo: do not normalise the rollout's advantages")
+    parser.add_argument("--target-entropy", type=float, default=None, help="--model sac: the entropy the learned temperature aims at (default 0.98 ln 2)")
+    parser.add_argument("--alpha-lr", type=float, default=None, help="--model sac: the temperature's learning rate (default 0 = --alpha stays fixed)")
     return parser
+
+
+def sac_kwargs(args, parser):
+    """--model sac's options as VecSAC's keywords (--alpha is the temperature there, default 0.2); everything is refused here, by name,
+    before anything touches the GPU"""
+    given = [n for n, v in (("--target-entropy", args.target_entropy), ("--alpha-lr", args.alpha_lr)) if v is not None]
+    if args.model != "sac":
+        if given:
+            parser.error(f"{' / '.join(given)} need --model sac, not --model {args.model}")
+        return None
+    if not args.vec:
+        parser.error("--model sac needs --vec: discrete soft actor-critic runs in the vectorised loop only")
+    for name, on in (("--noisy", args.noisy), ("--n-step", args.n_step != 1), ("--huber", args.huber is not None),
+                     ("--tau / --clip", args.tau is not None or args.clip is not None),
+                     ("--n-quantiles / --kappa", args.n_quantiles is not None or args.kappa is not None)):
+        if on:
+            parser.error(f"{name} is not an option of --model sac (--alpha, --target-entropy, --alpha-lr, --polyak, --max-grad-norm are)")
+    from .vecsac import check_args
+    kw = dict(alpha=0.2 if args.alpha is None else args.alpha, target_entropy=args.target_entropy, alpha_lr=0.0 if args.alpha_lr is None else args.alpha_lr,
+              polyak=0.005 if args.polyak is None else args.polyak, max_grad_norm=0.0 if args.max_grad_norm is None else args.max_grad_norm)
+    try:
+        check_args(args.vec, min(32, args.vec), kw["alpha"], kw["target_entropy"], kw["alpha_lr"], kw["polyak"], 100, 0.99, 1e-4, kw["max_grad_norm"], None)
+    except ValueError as e:
+        parser.error(str(e))
+    kw["batch"] = min(32, args.vec)
+    return kw
 
 
 def a2c_kwargs(args, parser):
@@ -175,6 +204,11 @@ def main():
     args = parser.parse_args()
     okw = optimiser_kwargs(args, parser)                 # (refused before anything touches the GPU)
     akw = a2c_kwargs(args, parser)
+    skw = sac_kwargs(args, parser)
+    if skw is not None:                                  # the off-policy stochastic-policy learner: a class of its own, one GPU
+        from .vecsac import VecSAC
+        VecSAC(args.vec, **skw).run(args.steps or 1000, log_every=0 if args.quiet else 100)
+        return
     if akw is not None:                                  # the on-policy learner: a class of its own, one GPU (--steps: updates)
         from .vecac import VecActorCritic
         VecActorCritic(args.vec, **akw).run(args.steps or 1000, log_every=0 if args.quiet else 100)

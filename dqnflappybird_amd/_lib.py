@@ -27,6 +27,8 @@ MDQN_DEFAULTS = (0.03, 0.9, -1.0)                     # (tau, alpha, l0) of a ne
 ALGO_DOUBLE_PER = 16                                  # Double-DQN's target on a prioritized memory (include/fbdqn.h)
 ARCH_AC = 6                                           # advantage actor-critic: the dueling layout read raw (include/fbdqn.h)
 AC_DEFAULTS = (0.5, 0.01)                             # (value_coef, entropy_coef) of a new actor-critic net
+ARCH_SAC = 7                                          # discrete soft actor-critic: a policy head and two Q heads (include/fbdqn.h)
+SAC_DEFAULTS = (0.2, 0.98, 0.0)                       # (alpha, target_entropy / ln A, alpha_lr) of a new SAC net
 PPO_DEFAULTS = (0.2, 0.0)                             # (clip_eps, value_clip) of a new actor-critic net; value_clip 0 = off
 NOISE_SAMPLE, NOISE_MEAN = 0, 1                       # include/fbdqn.h FB_NOISE_* (fb_qnet_reset_noise)
 ACT_NOISE_SHARED, ACT_NOISE_PER_ENV = 0, 1            # include/fbdqn.h FB_ACT_NOISE_* (fb_qnet_set_acting_noise)
@@ -115,6 +117,15 @@ SIGNATURES = {
     "fb_ppo_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "fb_ac_normalize_adv": [_vp, _i64, _vp, _vp],
     "fb_ac_permute": [_i64, _u64, _u64, _vp, _vp],
+    "fb_qnet_create_sac": [_i, _i, _i, _vp],
+    "fb_qnet_set_sac": [_vp, _f, _f, _f],
+    "fb_qnet_get_sac": [_vp, _vp, _vp, _vp],
+    "fb_qnet_get_sac_state": [_vp, _vp],
+    "fb_qnet_set_sac_state": [_vp, _vp],
+    "fb_qnet_forward_sac": [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp],
+    "fb_qnet_sac_train_step": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
+    "fb_sac_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
+    "fb_sac_step": [_vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _f, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],

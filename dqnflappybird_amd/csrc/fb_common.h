@@ -271,6 +271,30 @@ int fb_qnet_ac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const f
 // the ring-fed PPO train step behind fb_ppo_train_from_replay's checks (sel NULL: the four buffers are read at b)
 int fb_qnet_ppo_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const int64_t *sel, const float *adv, const float *ret,
                            const float *logp_old, const float *value_old, int64_t n_total, float *loss, float *flat_grad, void *stream);
+// ---- discrete soft actor-critic (FB_ARCH_SAC): the kernels live in fb_sac.hip, a code object of their own; fb_qnet.hip fills these structs
+// and hands them to the launchers as bytes.  off: the PLAIN layout, wq / bq = W_pi b_pi; so: the two Q heads behind it.  sw: the net's
+// temperature words (log alpha, m, v, beta1 power, beta2 power)
+struct SacOff { int wq1, bq1, wq2, bq2; };
+struct SacHeadArgs {
+    const float *hf, *P; int stot, nks, FC, A, rows; NetOff off; SacOff so; const float *sw;
+    float *logits, *value, *logp, *q1, *q2; uint8_t *actions;    // each f32 output or NULL; actions NULL: no action (forward_sac)
+    int greedy; uint32_t seed_lo, seed_hi, step_lo, step_hi;
+};
+struct SacLossArgs {
+    const float *hf, *P0, *P1; int stot, nks, FC, A, B; NetOff off; SacOff so; const float *sw;      // P0 / P1: the online / target parameters
+    const uint8_t *act, *term; const float *rew; double gamma;
+    float *dl, *xs, *dhf, *y_out;                                // dl f32[B][16] (fb_sac.hip); y_out f32[B] or NULL
+};
+// temp: the temperature update runs (alpha_lr > 0 and the step applies Adam itself)
+struct SacGradArgs { int B, FC, A; NetOff off; SacOff so; const float *dl, *xs, *dhf; float *grad, *loss, *gmax; FbAdamHead *adam; int tick;
+                     float *sw; float target_entropy, alpha_lr; int temp; };
+void fb_sac_launch_head(hipStream_t st, const void *args);
+void fb_sac_launch_loss(hipStream_t st, const void *args);
+void fb_sac_launch_grad(hipStream_t st, const void *args);
+int fb_qnet_is_sac(fb_qnet_t h);              // 1: a SAC net (fb_qnet_create_sac)
+// the checks of the two SAC training calls, `who` in the message; the ring-fed SAC train step behind fb_sac_train_from_replay's checks
+int fb_qnet_sac_check_train(fb_qnet_t h, int batch, double gamma, const char *who);
+int fb_qnet_sac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);

@@ -4033,6 +4033,12 @@ struct fb_qnet {
     float ppo_eps, ppo_vclip;        // PPO's clip ranges (fb_qnet_set_ppo): the ratio's epsilon, the value clip (0 = off)
     float *ac_dl, *ac_xs, *ac_r;
     uint8_t *ac_t;
+    // a SAC net (FB_ARCH_SAC, fb_qnet_create_sac; kernels: fb_sac.hip): the two Q heads behind the plain layout's W_pi b_pi; the target
+    // entropy and the temperature's learning rate (fb_qnet_set_sac); sac_w: [dev] (log alpha, m, v, beta1 power, beta2 power).  The loss
+    // kernel's per-sample row and the activations of s live in ac_dl / ac_xs
+    SacOff sac_off;
+    float sac_hbar, sac_alr;
+    float *sac_w;
 };
 // every field ac_grad_kernel touches through FbAdamHead sits where AdamDev has it
 static_assert(offsetof(AdamDev, b1pow) == offsetof(FbAdamHead, b1pow) && offsetof(AdamDev, b2pow) == offsetof(FbAdamHead, b2pow) &&
@@ -4063,6 +4069,8 @@ static bool is_c51d(const fb_qnet *h) { return h->arch == FB_ARCH_C51_DUELING ||
 static bool is_qr(const fb_qnet *h) { return h->arch == FB_ARCH_QR || h->arch == FB_ARCH_QR_DUELING; }
 // an actor-critic net: the dueling layout read raw (W_v b_v: V; W_pi b_pi at wq / bq: the logits, which the plain head reads as "Q")
 static bool is_ac(const fb_qnet *h) { return h->arch == FB_ARCH_AC; }
+// a SAC net: the plain layout (W_pi b_pi at wq / bq: the logits, which the plain head reads as "Q"), then W_q1 b_q1 W_q2 b_q2
+static bool is_sac(const fb_qnet *h) { return h->arch == FB_ARCH_SAC; }
 // the parameters the C51 kernels read, with h->hoff, for the net whose parameters are `params` (a virtual base for a dueling C51 net:
 // hoff.bf1 lands on heff[w][0], as the acting forward's hp_act copy is read)
 static const float *head_base(const fb_qnet *h, const float *params) {
@@ -4104,6 +4112,7 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
     FB_REQUIRE(arch != FB_ARCH_C51_DUELING, "fb_qnet_create: a dueling C51 net is made by fb_qnet_create_c51_dueling (it needs the support)");
     FB_REQUIRE(arch != FB_ARCH_QR && arch != FB_ARCH_QR_DUELING, "fb_qnet_create: a QR net is made by fb_qnet_create_qr (it needs N and kappa)");
     FB_REQUIRE(arch != FB_ARCH_AC, "fb_qnet_create: an actor-critic net is made by fb_qnet_create_ac");
+    FB_REQUIRE(arch != FB_ARCH_SAC, "fb_qnet_create: a SAC net is made by fb_qnet_create_sac");
     FB_REQUIRE(arch == FB_ARCH_PLAIN || arch == FB_ARCH_DUELING, "fb_qnet_create: arch must be 0 or 1");
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create: fc_width must be a multiple of 128");
     FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create: n_actions must be in 1..%d", MAXA);
@@ -4168,6 +4177,22 @@ extern "C" int fb_qnet_create_ac(int fc_width, int n_actions, int max_batch, fb_
     return qnet_create(FB_ARCH_AC, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
 }
 
+static int sac_write_words(fb_qnet *h, float alpha);
+
+extern "C" int fb_qnet_create_sac(int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
+    const char *fn = "fb_qnet_create_sac";
+    FB_REQUIRE(out, "%s: out is NULL", fn);
+    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
+    FB_REQUIRE(n_actions >= 2 && n_actions <= MAXA, "%s: n_actions must be in 2..%d", fn, MAXA);
+    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
+    int rc = qnet_create(FB_ARCH_SAC, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
+    if (rc != FB_OK) return rc;
+    (*out)->sac_hbar = 0.98f * logf((float)n_actions); (*out)->sac_alr = 0.f;
+    rc = sac_write_words(*out, 0.2f);            // (behind qnet_create's fb_qnet_set_hparams: the beta powers start at the net's betas)
+    if (rc != FB_OK) { fb_qnet_destroy(*out); *out = nullptr; }
+    return rc;
+}
+
 // the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
 static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, float sigma0) {
     NoisyNet nn;
@@ -4193,6 +4218,11 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
     h->off = is_c51d(h) ? make_off_c51d(fc_width, n_actions, sup.N)
                         : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING || arch == FB_ARCH_AC);
+    if (is_sac(h)) {                             // (the plain layout, then the two Q heads: off.n covers them)
+        h->sac_off.wq1 = h->off.n; h->sac_off.bq1 = h->sac_off.wq1 + fc_width * n_actions;
+        h->sac_off.wq2 = h->sac_off.bq1 + n_actions; h->sac_off.bq2 = h->sac_off.wq2 + fc_width * n_actions;
+        h->off.n = h->sac_off.bq2 + n_actions;
+    }
     h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
     h->n = h->off.n;
     h->noisy = sigma0 >= 0.f;                    // (fb_qnet_create_c51_noisy: C51 archs, finite sigma0 >= 0)
@@ -4238,6 +4268,10 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
         alloc((void **)&h->ac_dl, Bt * 16 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4); alloc((void **)&h->ac_r, Bt * 4); alloc((void **)&h->ac_t, Bt);
     }
+    if (is_sac(h)) {
+        const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
+        alloc((void **)&h->ac_dl, Bt * 16 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4); alloc((void **)&h->sac_w, 8 * 4);
+    }
     alloc((void **)&h->clip_part, sizeof(double) * 256); alloc((void **)&h->clip_out, sizeof(float) * 2);
     if (e == hipSuccess) { const float one = 1.f; e = hipMemcpy(h->clip_out + 1, &one, sizeof(one), hipMemcpyHostToDevice); }      // (no clip yet: norm 0, c 1)
     if (e != hipSuccess) {
@@ -4259,7 +4293,7 @@ extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
                     h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
                     h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1],
-                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out, h->ac_dl, h->ac_xs, h->ac_r, h->ac_t};
+                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out, h->ac_dl, h->ac_xs, h->ac_r, h->ac_t, h->sac_w};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -4355,6 +4389,7 @@ extern "C" int fb_qnet_overflow_count(fb_qnet_t h, int reset, int64_t *count_hos
 extern "C" int fb_qnet_set_inference_dtype(fb_qnet_t h, int dtype) {
     FB_REQUIRE(h && (dtype == FB_DTYPE_F32 || dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: dtype must be FB_DTYPE_F32 or FB_DTYPE_BF16");
     FB_REQUIRE(!(is_ac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: an actor-critic net computes in FB_DTYPE_F32 only");
+    FB_REQUIRE(!(is_sac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: a SAC net computes in FB_DTYPE_F32 only");
     h->nsplit = dtype == FB_DTYPE_BF16 ? 1 : 3;
     return FB_OK;
 }
@@ -4362,6 +4397,7 @@ extern "C" int fb_qnet_set_inference_dtype(fb_qnet_t h, int dtype) {
 extern "C" int fb_qnet_set_train_dtype(fb_qnet_t h, int dtype) {
     FB_REQUIRE(h && (dtype == FB_DTYPE_F32 || dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: dtype must be FB_DTYPE_F32 or FB_DTYPE_BF16");
     FB_REQUIRE(!(is_ac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: an actor-critic net trains in FB_DTYPE_F32 only");
+    FB_REQUIRE(!(is_sac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: a SAC net trains in FB_DTYPE_F32 only");
     h->nsplit_train = dtype == FB_DTYPE_BF16 ? 1 : 3;
     return FB_OK;
 }
@@ -4386,6 +4422,13 @@ extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *
         uint32_t bits;
         memcpy(&bits, &b, 4);
         FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(master(h, which) + h->off.bv), (int)bits, (size_t)h->sup.N, fb_stream(stream)));
+    }
+    if (is_sac(h)) {                             // (the Q heads' weights drew as every weight does, keyed by their own index; their biases)
+        const float b = 0.01f;
+        uint32_t bits;
+        memcpy(&bits, &b, 4);
+        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->sac_off.bq1), (int)bits, (size_t)h->A, fb_stream(stream)));
+        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->sac_off.bq2), (int)bits, (size_t)h->A, fb_stream(stream)));
     }
     if (h->noisy)                                // (mu as the plain net's, then sigma0 / sqrt(fan_in))
         hipLaunchKernelGGL(noisy_sigma_init_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, fb_stream(stream), h->mst[which], h->nnet);
@@ -4480,6 +4523,10 @@ struct Plan {
     // a PPO train plan of an actor-critic net: the clipped-surrogate loss instead of A2C's; the rollout's log-probabilities and values;
     // ppo_sel (or NULL): where sample b reads ac_adv / ac_ret / ppo_logp / ppo_value
     bool ppo; const float *ppo_logp, *ppo_value; const long long *ppo_sel;
+    // a SAC net.  Forward plans with policy_head set: the SAC head (fb_sac.hip) instead of the plain one -- ac_value (or NULL) the soft state
+    // value, ac_logits / ac_logp as above, sac_q1 / sac_q2 f32[rows][A] or NULL.  Train plans: three slices as FB_ALGO_DOUBLE's, p.r / p.t /
+    // p.gamma / p.y as a scalar step's; sac_temp: the temperature update runs (the CALLER exports nothing and alpha_lr > 0)
+    bool policy_head; float *sac_q1, *sac_q2; bool sac_temp;
 };
 
 // A runtime value as a template argument: f is a generic lambda and gets a tag whose ::value is a constant expression, so that a kernel
@@ -4499,7 +4546,7 @@ template <class T> static void put_seed_words(T &c, uint64_t seed, uint64_t step
 struct PlanCtx {
     int only; hipStream_t st;                // `only` < 0: the whole plan; else the launches of that KernelId alone
     int maxc, total;                         // states of the largest slice / of all slices
-    bool big, trunk, fused, c51, ac;
+    bool big, trunk, fused, c51, ac, sac;      // ac: the loss is fb_ac.hip's or fb_sac.hip's two launches (an actor-critic or a SAC net)
     bool state_trunk;                        // gathered states through conv1_pool + conv23_t with planes, then large_pass's fc1 alone (plan_ctx)
     int nsp, stot; size_t pl1, pl2;          // stot: rows of the workspace; pl1 / pl2: its plane pitch after conv1 / conv2, conv3
 };
@@ -4521,7 +4568,8 @@ static PlanCtx plan_ctx(const fb_qnet *h, const Plan &p, int only, hipStream_t s
     // (conv23_sp_kernel<., 5, true>), five states per workgroup.  Its fc1 partial sums are in hf_act, its head parameters in hp_act
     c.fused = c.big && p.nib && !p.train && !c.trunk && p.ns == 1;
     c.c51 = h->sup.N > 0;
-    c.ac = is_ac(h);
+    c.sac = is_sac(h);
+    c.ac = is_ac(h) || c.sac;
     // an actor-critic train step on 256 GATHERED states: the per-state conv trunk of the smaller batches, writing conv3's planes, then
     // fc1_sp -- the arithmetic of the ring-fed form (ring_trunk), so that the two forms of an A2C chunk agree bit for bit at every size
     // (the large-batch trunk sums conv2 / conv3 in another order).  The ring-fed form is the one the A2C loop runs
@@ -4671,7 +4719,17 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
             p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params;
         } else launch_dist_head(h, H, c.total, c.st);
     }
-    if (c.ac && !p.train && p.ac_value && runs(c, K_HEAD)) {           // an actor-critic net's policy head (fb_ac.hip), a launch of its own
+    if (c.sac && !p.train && p.policy_head && runs(c, K_HEAD)) {       // a SAC net's head (fb_sac.hip), a launch of its own
+        SacHeadArgs H;
+        memset(&H, 0, sizeof(H));
+        H.hf = c.fused ? h->hf_act : h->hf; H.P = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;      // (fused: the copy its fc1 launch took)
+        H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A; H.rows = c.total; H.off = h->off; H.so = h->sac_off; H.sw = h->sac_w;
+        H.logits = p.ac_logits; H.value = p.ac_value; H.logp = p.ac_logp; H.q1 = p.sac_q1; H.q2 = p.sac_q2; H.actions = p.actions; H.greedy = p.ac_greedy;
+        put_seed_words(H, p.seed, p.step);
+        fb_sac_launch_head(c.st, &H);
+        return;
+    }
+    if (c.ac && !c.sac && !p.train && p.ac_value && runs(c, K_HEAD)) {  // an actor-critic net's policy head (fb_ac.hip), a launch of its own
         AcHeadArgs H;
         memset(&H, 0, sizeof(H));
         H.hf = c.fused ? h->hf_act : h->hf; H.P = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;      // (fused: the copy its fc1 launch took)
@@ -4699,6 +4757,18 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
 // the per-unit reductions; QR: per-sample targets / quantile Huber loss / dhf, then C51's per-unit reductions
 static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     const int B = p.B, FC = h->FC;
+    if (c.sac) {                                 // SAC: per-sample target / losses / dz / dQ / dhf, then the per-unit reductions (fb_sac.hip)
+        SacLossArgs L;
+        memset(&L, 0, sizeof(L));
+        L.hf = h->hf; L.P0 = h->params[0]; L.P1 = h->params[1]; L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B;
+        L.off = h->off; L.so = h->sac_off; L.sw = h->sac_w; L.act = p.a; L.term = p.t; L.rew = p.r; L.gamma = p.gamma;
+        L.dl = h->ac_dl; L.xs = h->ac_xs; L.dhf = h->dhf; L.y_out = p.y;
+        fb_sac_launch_loss(c.st, &L);
+        const SacGradArgs gA{B, FC, h->A, h->off, h->sac_off, h->ac_dl, h->ac_xs, h->dhf, p.G, p.loss, h->gmax, reinterpret_cast<FbAdamHead *>(h->adam),
+                             p.tick, h->sac_w, h->sac_hbar, h->sac_alr, p.sac_temp ? 1 : 0};
+        fb_sac_launch_grad(c.st, &gA);
+        return;
+    }
     if (c.ac) {                                  // actor-critic: per-sample loss / dz / dV / dhf, then the per-unit reductions (fb_ac.hip)
         AcLossArgs L;
         memset(&L, 0, sizeof(L));
@@ -4955,6 +5025,7 @@ int fb_qnet_is_c51(fb_qnet_t h) { return h && h->sup.N > 0 && !is_qr(h); }
 int fb_qnet_is_qr(fb_qnet_t h) { return h && is_qr(h); }
 int fb_qnet_is_dist(fb_qnet_t h) { return h && h->sup.N > 0; }
 int fb_qnet_is_ac(fb_qnet_t h) { return h && is_ac(h); }
+int fb_qnet_is_sac(fb_qnet_t h) { return h && is_sac(h); }
 extern "C" int fb_qnet_is_noisy(fb_qnet_t h) { return h && h->noisy ? 1 : 0; }
 
 extern "C" int fb_qnet_reset_noise(fb_qnet_t h, int which, uint64_t seed, uint64_t step, int mode, void *stream) {
@@ -5059,6 +5130,7 @@ extern "C" int fb_qnet_set_munchausen(fb_qnet_t h, float tau, float alpha, float
     FB_REQUIRE(h, "fb_qnet_set_munchausen: NULL handle");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
     FB_REQUIRE(!is_ac(h), "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar Q heads only, not an actor-critic net");
+    FB_REQUIRE(!is_sac(h), "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar Q heads only, not a SAC net");
     FB_REQUIRE(isfinite(tau) && tau > 0.f, "fb_qnet_set_munchausen: tau must be finite and > 0 (got %g)", (double)tau);
     FB_REQUIRE(alpha >= 0.f && alpha <= 1.f, "fb_qnet_set_munchausen: alpha must be in [0, 1] (got %g)", (double)alpha);
     FB_REQUIRE(isfinite(clip_lo) && clip_lo <= 0.f, "fb_qnet_set_munchausen: the clip l0 must be finite and <= 0 (got %g)", (double)clip_lo);
@@ -5070,6 +5142,7 @@ extern "C" int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha
     FB_REQUIRE(h, "fb_qnet_get_munchausen: NULL handle");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
     FB_REQUIRE(!is_ac(h), "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar Q heads only, not an actor-critic net");
+    FB_REQUIRE(!is_sac(h), "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar Q heads only, not a SAC net");
     if (tau_host) *tau_host = h->md.tau;
     if (alpha_host) *alpha_host = h->md.alpha;
     if (clip_lo_host) *clip_lo_host = h->md.clip;
@@ -5080,6 +5153,7 @@ extern "C" int fb_qnet_set_huber(fb_qnet_t h, float delta) {
     FB_REQUIRE(h, "fb_qnet_set_huber: NULL handle");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
     FB_REQUIRE(!is_ac(h), "fb_qnet_set_huber: the Huber loss is a setting of the scalar Q heads only, not of an actor-critic net");
+    FB_REQUIRE(!is_sac(h), "fb_qnet_set_huber: the Huber loss is a setting of the scalar Q heads only, not of a SAC net");
     FB_REQUIRE(isfinite(delta) && delta >= 0.f, "fb_qnet_set_huber: delta must be finite and >= 0 (0 = the squared loss; got %g)", (double)delta);
     h->huber = delta;
     return FB_OK;
@@ -5089,6 +5163,7 @@ extern "C" int fb_qnet_get_huber(fb_qnet_t h, float *delta_host) {
     FB_REQUIRE(h && delta_host, "fb_qnet_get_huber: NULL argument");
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
     FB_REQUIRE(!is_ac(h), "fb_qnet_get_huber: the Huber loss is a setting of the scalar Q heads only, not of an actor-critic net");
+    FB_REQUIRE(!is_sac(h), "fb_qnet_get_huber: the Huber loss is a setting of the scalar Q heads only, not of a SAC net");
     *delta_host = h->huber;
     return FB_OK;
 }
@@ -5298,6 +5373,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     FB_REQUIRE(h && a && r && t && loss && (ring || (s && s2)), "fb_qnet_train_step: NULL argument");
     FB_REQUIRE((algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER) || is_mdqn_algo(algo) || algo == FB_ALGO_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
     FB_REQUIRE(!is_ac(h), "fb_qnet_train_step: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only (got algo %d)", algo);
+    FB_REQUIRE(!is_sac(h), "fb_qnet_train_step: a SAC net trains through fb_qnet_sac_train_step / fb_sac_train_from_replay only (got algo %d)", algo);
     {
         const bool c51a = is_c51_algo(algo), qra = is_qr_algo(algo);
         FB_REQUIRE(c51a == (h->sup.N > 0 && !is_qr(h)), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
@@ -5414,14 +5490,15 @@ extern "C" int fb_qnet_forward_ac(fb_qnet_t h, const uint8_t *states, int batch,
 
 extern "C" int fb_qnet_act_policy_nib(fb_qnet_t h, const uint8_t *nib_states, int n, uint64_t seed, uint64_t step, int greedy, uint8_t *actions,
                                       float *value, float *logp, float *logits, void *stream) {
-    FB_REQUIRE(h && nib_states && value, "fb_qnet_act_policy_nib: NULL argument");
-    FB_REQUIRE(is_ac(h), "fb_qnet_act_policy_nib: not an actor-critic net (fb_qnet_create_ac)");
+    FB_REQUIRE(h && nib_states && (value || is_sac(h)), "fb_qnet_act_policy_nib: NULL argument");
+    FB_REQUIRE(is_ac(h) || is_sac(h), "fb_qnet_act_policy_nib: not an actor-critic or SAC net (fb_qnet_create_ac / fb_qnet_create_sac)");
     FB_REQUIRE(actions || !logp, "fb_qnet_act_policy_nib: logp needs actions");
     FB_REQUIRE(rows_ok(h, n), "fb_qnet_act_policy_nib: n %d exceeds 3*max_batch", n);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true;
     p.actions = actions; p.seed = seed; p.step = step;
     p.ac_value = value; p.ac_logits = logits; p.ac_logp = logp; p.ac_greedy = greedy != 0;
+    p.policy_head = true;
     return run_plan(h, p, -1, fb_stream(stream));
 }
 
@@ -5514,6 +5591,114 @@ int fb_qnet_ppo_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const int6
     const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_ppo_train_from_replay");
     if (rc != FB_OK) return rc;
     Plan p = ppo_train_plan(h, B, nullptr, ring->a, sel, adv, ret, logp_old, value_old, n_total, loss, flat_grad, ring);
+    return run_train(h, p, stream);
+}
+
+// ---- discrete soft actor-critic (include/fbdqn.h; kernels: fb_sac.hip)
+// (log alpha, m, v, beta1 power, beta2 power) <- (logf(alpha), 0, 0, the net's beta1, beta2); synchronous
+static int sac_write_words(fb_qnet *h, float alpha) {
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    AdamDev a;
+    FB_CHECK_HIP(hipMemcpy(&a, h->adam, sizeof(a), hipMemcpyDeviceToHost));
+    const float w[8] = {logf(alpha), 0.f, 0.f, a.b1, a.b2, 0.f, 0.f, 0.f};
+    FB_CHECK_HIP(hipMemcpy(h->sac_w, w, sizeof(w), hipMemcpyHostToDevice));
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_set_sac(fb_qnet_t h, float alpha, float target_entropy, float alpha_lr) {
+    FB_REQUIRE(h, "fb_qnet_set_sac: NULL handle");
+    FB_REQUIRE(is_sac(h), "fb_qnet_set_sac: not a SAC net (fb_qnet_create_sac)");
+    FB_REQUIRE(isfinite(alpha) && alpha > 0.f, "fb_qnet_set_sac: alpha must be finite and > 0 (got %g)", (double)alpha);
+    FB_REQUIRE(isfinite(target_entropy), "fb_qnet_set_sac: target_entropy must be finite (got %g)", (double)target_entropy);
+    FB_REQUIRE(isfinite(alpha_lr) && alpha_lr >= 0.f, "fb_qnet_set_sac: alpha_lr must be finite and >= 0 (0 = a fixed temperature; got %g)", (double)alpha_lr);
+    const int rc = sac_write_words(h, alpha);
+    if (rc != FB_OK) return rc;
+    h->sac_hbar = target_entropy; h->sac_alr = alpha_lr;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_sac_state(fb_qnet_t h, float *state_host) {
+    FB_REQUIRE(h && state_host, "fb_qnet_get_sac_state: NULL argument");
+    FB_REQUIRE(is_sac(h), "fb_qnet_get_sac_state: not a SAC net (fb_qnet_create_sac)");
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    FB_CHECK_HIP(hipMemcpy(state_host, h->sac_w, 5 * sizeof(float), hipMemcpyDeviceToHost));
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_set_sac_state(fb_qnet_t h, const float *state_host) {
+    FB_REQUIRE(h && state_host, "fb_qnet_set_sac_state: NULL argument");
+    FB_REQUIRE(is_sac(h), "fb_qnet_set_sac_state: not a SAC net (fb_qnet_create_sac)");
+    FB_REQUIRE(isfinite(state_host[0]), "fb_qnet_set_sac_state: log alpha must be finite (got %g)", (double)state_host[0]);
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    FB_CHECK_HIP(hipMemcpy(h->sac_w, state_host, 5 * sizeof(float), hipMemcpyHostToDevice));
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_sac(fb_qnet_t h, float *alpha_host, float *target_entropy_host, float *alpha_lr_host) {
+    FB_REQUIRE(h, "fb_qnet_get_sac: NULL handle");
+    FB_REQUIRE(is_sac(h), "fb_qnet_get_sac: not a SAC net (fb_qnet_create_sac)");
+    if (alpha_host) {
+        float w[5];
+        const int rc = fb_qnet_get_sac_state(h, w);
+        if (rc != FB_OK) return rc;
+        *alpha_host = expf(w[0]);
+    }
+    if (target_entropy_host) *target_entropy_host = h->sac_hbar;
+    if (alpha_lr_host) *alpha_lr_host = h->sac_alr;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_forward_sac(fb_qnet_t h, int which, const uint8_t *states, int batch, float *logits, float *q1, float *q2, void *stream) {
+    FB_REQUIRE(h && states && logits && q1 && q2 && (which == 0 || which == 1), "fb_qnet_forward_sac: bad argument");
+    FB_REQUIRE(is_sac(h), "fb_qnet_forward_sac: not a SAC net (fb_qnet_create_sac)");
+    FB_REQUIRE(rows_ok(h, batch), "fb_qnet_forward_sac: batch %d exceeds 3*max_batch", batch);
+    Plan p = forward_plan(h, which, states, batch);
+    p.policy_head = true; p.ac_logits = logits; p.sac_q1 = q1; p.sac_q2 = q2;
+    return run_plan(h, p, -1, fb_stream(stream));
+}
+
+int fb_qnet_sac_check_train(fb_qnet_t h, int B, double gamma, const char *who) {
+    FB_REQUIRE(h && is_sac(h), "%s: not a SAC net (fb_qnet_create_sac)", who);
+    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "%s: batch %d exceeds min(max_batch, %d)", who, B, MAXTB);
+    FB_REQUIRE(isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
+    return FB_OK;
+}
+
+// the train plan of a SAC net: FB_ALGO_DOUBLE's three slices -- s and s' through the online net, s' through the target net
+static Plan sac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t, double gamma,
+                           float *loss, float *q_target, float *flat_grad, const FbRingSrc *ring) {
+    Plan p; memset(&p, 0, sizeof(p));
+    p.ns = 3;
+    p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
+    p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};
+    p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1};
+    p.train = true; p.algo = -1; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.gamma = gamma;
+    p.loss = loss; p.y = q_target;
+    p.G = flat_grad ? flat_grad : h->grad;
+    p.apply_adam = flat_grad == nullptr; p.tick = true;
+    p.sac_temp = flat_grad == nullptr && h->sac_alr > 0.f;
+    p.ring = ring;
+    return p;
+}
+
+extern "C" int fb_qnet_sac_train_step(fb_qnet_t h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
+                                      double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && s && a && r && s2 && t && loss, "fb_qnet_sac_train_step: NULL argument");
+    const int rc = fb_qnet_sac_check_train(h, B, gamma, "fb_qnet_sac_train_step");
+    if (rc != FB_OK) return rc;
+    Plan p = sac_train_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, nullptr);
+    if (B >= 256) {                              // (fc1_sp_kernel reads W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
+        const int rp = fb_qnet_refresh_planes(h, stream);
+        if (rp != FB_OK) return rp;
+    }
+    return run_train(h, p, stream);
+}
+
+int fb_qnet_sac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss, "fb_sac_train_from_replay: NULL argument");
+    const int rc = fb_qnet_sac_check_train(h, B, gamma, "fb_sac_train_from_replay");
+    if (rc != FB_OK) return rc;
+    Plan p = sac_train_plan(h, B, nullptr, ring->a, ring->r, nullptr, ring->t, gamma, loss, q_target, flat_grad, ring);
     return run_train(h, p, stream);
 }
 

@@ -1,0 +1,349 @@
+// fb_sac.hip -- discrete soft actor-critic (SAC) on the replay ring: the kernels of an FB_ARCH_SAC net and the fb_sac_* entry points, as a
+// code object of their own (fb_qnet.hip routes to the launchers below and gets no kernel: a kernel added to ITS code object moves the others).
+// include/fbdqn.h pins the semantics.  Head parameters behind b_fc1, read raw: W_pi b_pi (the plain head's place), W_q1 b_q1, W_q2 b_q2;
+// z = h . W_pi + b_pi, Q_i = h . W_qi + b_qi.
+//   sac_head_kernel   acting / forward: logits, Q1, Q2, the soft state value, the sampled (or greedy) action and its log-probability; one wave per state
+//   sac_loss_kernel   training, launch 1 of 2: per sample the soft target, both critic errors, the actor term, dz / dQ, the dhf row and the activation row
+//   sac_grad_kernel   training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_pi, W_q1, W_q2; workgroup 0: the head biases, the six
+//                     loss numbers, Adam's tick and the temperature update
+// Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
+#include "fb_common.h"
+#include <math.h>
+#include <type_traits>
+
+namespace {
+#include "fb_head.h"
+#include "fb_policy.h"
+
+constexpr int SAC_MAXB = 256;        // the train step's batch limit (fb_qnet.hip MAXTB)
+
+// ONE head of state smp on every lane of the wave (xor butterfly: the same bits everywhere): out[c] = h . W[:, c] + b[c], W at wo, b at bo.
+// Formed exactly as head_one_t forms the plain head's outputs -- a lane takes 4 consecutive units per round, fmaf in unit order, then the
+// butterfly, then the bias -- so over W_pi / b_pi these are the very bits fb_qnet_forward returns.  The three heads of a state are formed
+// one after another (one weight tile live at a time: no spill at AT = MAXA).  No load under a branch: columns a >= A read column 0.
+template <int AT>
+__device__ __forceinline__ void sac_head(const float *__restrict__ hf, int stot, int nks, int FC, int A, const float *__restrict__ P, int bf1, int wo, int bo,
+                                         int smp, int lane, float (&out)[AT]) {
+    float acc[AT], bq[AT];
+#pragma unroll
+    for (int a = 0; a < AT; a++) { acc[a] = 0.f; bq[a] = P[bo + (a < A ? a : 0)]; }
+    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
+        float x4[4], w[4][AT];
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int a = 0; a < AT; a++) w[e][a] = P[wo + (j0 + e) * A + (a < A ? a : 0)];
+        ac_units4(hf, stot, nks, FC, P, bf1, smp, j0, x4);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int a = 0; a < AT; a++) acc[a] = fmaf(x4[e], w[e][a], acc[a]);
+    }
+#pragma unroll
+    for (int a = 0; a < AT; a++)
+        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o);
+#pragma unroll
+    for (int a = 0; a < AT; a++) out[a] = a < A ? acc[a] + bq[a] : 0.f;
+}
+
+// the soft state value sum_c p_c (min(Q1_c, Q2_c) - alpha log p_c), ascending c, float32
+template <int AT>
+__device__ __forceinline__ float sac_soft_value(const float (&p)[AT], const float (&lp)[AT], const float (&q1)[AT], const float (&q2)[AT], int A, float alpha) {
+    float V = 0.f;
+#pragma unroll
+    for (int c = 0; c < AT; c++) V += c < A ? p[c] * (fminf(q1[c], q2[c]) - alpha * lp[c]) : 0.f;
+    return V;
+}
+
+template <int AT>
+__global__ __launch_bounds__(256) void sac_head_kernel(SacHeadArgs H) {
+    const int lane = threadIdx.x & 63, smp = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (smp >= H.rows) return;                                   // (wave-uniform)
+    const int A = AT == MAXA ? H.A : AT;
+    const float alpha = expf(H.sw[0]);
+    float z[AT], q1[AT], q2[AT];
+    sac_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off.bf1, H.off.wq, H.off.bq, smp, lane, z);
+    const bool needq = H.value || H.q1 || H.q2;                  // (kernel-uniform)
+#pragma unroll
+    for (int c = 0; c < AT; c++) { q1[c] = 0.f; q2[c] = 0.f; }
+    if (needq) {
+        sac_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off.bf1, H.so.wq1, H.so.bq1, smp, lane, q1);
+        sac_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off.bf1, H.so.wq2, H.so.bq2, smp, lane, q2);
+    }
+    if (lane != 0) return;
+#pragma unroll
+    for (int c = 0; c < AT; c++) if (c < A) {
+        if (H.logits) H.logits[(size_t)smp * A + c] = z[c];
+        if (H.q1) H.q1[(size_t)smp * A + c] = q1[c];
+        if (H.q2) H.q2[(size_t)smp * A + c] = q2[c];
+    }
+    if (!H.actions && !H.value) return;
+    float p[AT], lp[AT], m, s;
+    ac_softmax<AT>(z, A, p, lp, m, s);
+    if (H.value) H.value[smp] = sac_soft_value<AT>(p, lp, q1, q2, A, alpha);
+    if (!H.actions) return;
+    int act = 0;
+    if (H.greedy) {                                              // first maximum
+#pragma unroll
+        for (int c = 1; c < AT; c++) if (c < A && z[c] > z[act]) act = c;
+    } else {                                                     // the draw pinned for an actor-critic net (fb_ac.hip)
+        const fb_u4 o = fb_philox(H.seed_lo, H.seed_hi, (uint32_t)smp, H.step_lo, FB_STREAM_POLICY, H.step_hi);
+        const float u = (float)(o.x >> 8) * (1.0f / 16777216.0f);
+        float cum = 0.f;
+        bool found = false;
+        act = A - 1;
+#pragma unroll
+        for (int c = 0; c < AT; c++) {
+            cum += p[c];
+            if (c < A && !found && u < cum) { act = c; found = true; }
+        }
+    }
+    H.actions[smp] = (uint8_t)act;
+    if (H.logp) {
+        float l = lp[0];
+#pragma unroll
+        for (int c = 1; c < AT; c++) l = c == act ? lp[c] : l;
+        H.logp[smp] = l;
+    }
+}
+
+// ---- training, launch 1 of 2: one wave per sample.  Rows b / B + b / 2 B + b of the fc1 partial sums: s and s' through the online net, s'
+// through the target net.  Every lane holds the same heads, so the target, both losses and the gradients need no further exchange.
+// dl[b][16]: dz_c at c < 8, dQ1(s, a) at 8, dQ2(s, a) at 9, d1^2 / d2^2 / L_pi / H at 10 .. 13, the action at 14, the alpha used at 15.
+template <int AT>
+__global__ __launch_bounds__(256) void sac_loss_kernel(SacLossArgs L) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= L.B) return;                                        // (wave-uniform)
+    const int A = AT == MAXA ? L.A : AT, FC = L.FC, B = L.B;
+    const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;  // (an action past the head reads the last one: stays in bounds)
+    const float rf = L.rew[b];
+    const bool tb = L.term[b] != 0;
+    const float alpha = expf(L.sw[0]);
+    float z[AT], q1[AT], q2[AT], p[AT], lp[AT], m, s;
+    // s' first: the policy from the online net (row B + b), both critics from the target net (row 2 B + b)
+    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.off.wq, L.off.bq, B + b, lane, z);
+    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off.bf1, L.so.wq1, L.so.bq1, 2 * B + b, lane, q1);
+    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off.bf1, L.so.wq2, L.so.bq2, 2 * B + b, lane, q2);
+    ac_softmax<AT>(z, A, p, lp, m, s);
+    const float Vn = sac_soft_value<AT>(p, lp, q1, q2, A, alpha);
+    const double r = rf == 0.1f ? 0.1 : (double)rf;              // (the convention of every target here)
+    const float y = (float)(tb ? r : r + L.gamma * (double)Vn);
+    // s: all three heads of the online net
+    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.off.wq, L.off.bq, b, lane, z);
+    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.so.wq1, L.so.bq1, b, lane, q1);
+    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.so.wq2, L.so.bq2, b, lane, q2);
+    ac_softmax<AT>(z, A, p, lp, m, s);
+    float q1a = q1[0], q2a = q2[0];
+#pragma unroll
+    for (int c = 1; c < AT; c++) { q1a = c == ab ? q1[c] : q1a; q2a = c == ab ? q2[c] : q2a; }
+    const float Bf = (float)B, d1 = q1a - y, d2 = q2a - y;
+    const float dq1 = (2.f * d1) / Bf, dq2 = (2.f * d2) / Bf;
+    float f[AT], Lpi = 0.f, H = 0.f;
+#pragma unroll
+    for (int c = 0; c < AT; c++) {
+        f[c] = alpha * lp[c] - fminf(q1[c], q2[c]);              // (min Q is a constant of the actor term)
+        Lpi += c < A ? p[c] * f[c] : 0.f;
+        H -= c < A ? p[c] * lp[c] : 0.f;
+    }
+    float dz[AT];
+#pragma unroll
+    for (int c = 0; c < AT; c++) dz[c] = c < A ? (p[c] * (f[c] - Lpi)) / Bf : 0.f;
+    float o = lane == 8 ? dq1 : lane == 9 ? dq2 : lane == 10 ? d1 * d1 : lane == 11 ? d2 * d2 : lane == 12 ? Lpi : lane == 13 ? H
+              : lane == 14 ? (float)ab : alpha;
+#pragma unroll
+    for (int c = 0; c < AT; c++) o = lane == c ? dz[c] : o;
+    if (lane < 16) L.dl[(size_t)b * 16 + lane] = o;
+    if (lane == 0 && L.y_out) L.y_out[b] = y;
+    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
+        float x4[4], w[4][AT], w1[4], w2[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+#pragma unroll
+            for (int a = 0; a < AT; a++) w[e][a] = L.P0[L.off.wq + (j0 + e) * A + (a < A ? a : 0)];
+            w1[e] = L.P0[L.so.wq1 + (j0 + e) * A + ab];
+            w2[e] = L.P0[L.so.wq2 + (j0 + e) * A + ab];
+        }
+        ac_units4(L.hf, L.stot, L.nks, FC, L.P0, L.off.bf1, b, j0, x4);
+        float d4[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            float dh = dq1 * w1[e];
+            dh = fmaf(dq2, w2[e], dh);
+#pragma unroll
+            for (int a = 0; a < AT; a++) dh = fmaf(dz[a], w[e][a], dh);       // (dz of a >= A is 0)
+            d4[e] = x4[e] > 0.f ? dh : 0.f;
+        }
+        *reinterpret_cast<float4 *>(L.dhf + (size_t)b * FC + j0) = make_float4(d4[0], d4[1], d4[2], d4[3]);
+        *reinterpret_cast<float4 *>(L.xs + (size_t)b * FC + j0) = make_float4(x4[0], x4[1], x4[2], x4[3]);
+    }
+}
+
+// ---- training, launch 2 of 2: one workgroup per 16 fc1 units (ac_grad_kernel's grid): b_fc1's gradient and the tile's maximum |dhf|
+// (fc1_bwd_big_kernel's pre-scale), then thread (unit jl, column c) walks the samples in order, twice: first c < 8 is W_pi's column c and
+// c >= 8 W_q1's column c - 8, then c < 8 is W_q2's column c.  A critic's column c takes sample b's dQ_i when a_b = c, else 0.
+// Workgroup 0 also sums b_pi, b_q1, b_q2 and the four loss terms the same way, forms the six loss numbers, ticks Adam and -- when the step
+// applies Adam itself and alpha_lr > 0 -- makes the temperature's own Adam step on log alpha (include/fbdqn.h), on one thread.
+__global__ __launch_bounds__(256) void sac_grad_kernel(SacGradArgs L) {
+    __shared__ float dlt[SAC_MAXB * 16];
+    __shared__ float xt[SAC_MAXB * 16];
+    __shared__ float part[16][16];
+    __shared__ float wmax[4];
+    __shared__ float lsum[4];
+    const int tid = threadIdx.x, B = L.B, FC = L.FC, A = L.A, j00 = blockIdx.x * 16;
+    for (int k = tid; k < B * 16; k += 256) { dlt[k] = L.dl[k]; xt[k] = L.xs[(size_t)(k >> 4) * FC + j00 + (k & 15)]; }
+    const int jl = tid & 15, bg = tid >> 4;
+    float sm = 0.f, mx = 0.f;
+    for (int b = bg; b < B; b += 16) { const float d = L.dhf[(size_t)b * FC + j00 + jl]; sm += d; mx = fmaxf(mx, fabsf(d)); }
+    part[bg][jl] = sm;
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) L.gmax[blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (bg == 0) {
+        float v = part[0][jl];
+#pragma unroll
+        for (int q = 1; q < 16; q++) v += part[q][jl];
+        L.grad[L.off.bf1 + j00 + jl] = v;
+    }
+    const int c = bg, col = c & 7;
+    const bool live = col < A;
+    float acc = 0.f, gb = 0.f;
+    if (c < 8) {                                                 // W_pi's column c (idle columns walk column 0 and store nothing)
+        const int cc = live ? col : 0;
+        for (int b = 0; b < B; b++) {
+            const float w = dlt[b * 16 + cc];
+            gb += w;
+            acc = fmaf(xt[b * 16 + jl], w, acc);
+        }
+        if (live) L.grad[L.off.wq + (size_t)(j00 + jl) * A + col] = acc;
+    } else {                                                     // W_q1's column c - 8
+        for (int b = 0; b < B; b++) {
+            const float w = (int)dlt[b * 16 + 14] == col ? dlt[b * 16 + 8] : 0.f;
+            gb += w;
+            acc = fmaf(xt[b * 16 + jl], w, acc);
+        }
+        if (live) L.grad[L.so.wq1 + (size_t)(j00 + jl) * A + col] = acc;
+    }
+    float acc2 = 0.f, gb2 = 0.f;
+    if (c < 8) {                                                 // W_q2's column c
+        for (int b = 0; b < B; b++) {
+            const float w = (int)dlt[b * 16 + 14] == col ? dlt[b * 16 + 9] : 0.f;
+            gb2 += w;
+            acc2 = fmaf(xt[b * 16 + jl], w, acc2);
+        }
+        if (live) L.grad[L.so.wq2 + (size_t)(j00 + jl) * A + col] = acc2;
+    }
+    if (blockIdx.x != 0) return;
+    if (jl == 0 && live) {
+        if (c < 8) { L.grad[L.off.bq + col] = gb; L.grad[L.so.bq2 + col] = gb2; }
+        else L.grad[L.so.bq1 + col] = gb;
+    }
+    if (jl == 1 && c >= 10 && c < 14) {                          // (otherwise idle threads: the loss terms, samples in order)
+        float t = 0.f;
+        for (int b = 0; b < B; b++) t += dlt[b * 16 + c];
+        lsum[c - 10] = t / (float)B;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        L.loss[1] = lsum[0]; L.loss[2] = lsum[1]; L.loss[3] = lsum[2]; L.loss[4] = lsum[3];
+        L.loss[0] = (lsum[0] + lsum[1]) + lsum[2];
+        L.loss[5] = dlt[15];                                     // the alpha the loss kernel used
+        FbAdamHead &ad = *L.adam;
+        if (L.tick && ad.ticks == ad.applies) {                  // (as ac_grad_kernel)
+            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
+            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
+            ad.ticks += 1;
+        }
+        if (L.temp) {                                            // one element of the net's TF-style Adam on log alpha, its own beta powers
+            float la = L.sw[0], mm = L.sw[1], vv = L.sw[2], p1 = L.sw[3], p2 = L.sw[4];
+            const float g = lsum[3] - L.target_entropy;
+            const float at = L.alpha_lr * sqrtf(1.f - p2) / (1.f - p1);
+            p1 *= ad.b1; p2 *= ad.b2;
+            mm += (g - mm) * (1.f - ad.b1); vv += (g * g - vv) * (1.f - ad.b2);
+            la -= (mm * at) / (sqrtf(vv) + ad.eps);
+            L.sw[0] = la; L.sw[1] = mm; L.sw[2] = vv; L.sw[3] = p1; L.sw[4] = p2;
+        }
+    }
+}
+
+template <class F> void with_actions(int A, F f) {
+    if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
+}
+}  // namespace
+
+void fb_sac_launch_head(hipStream_t st, const void *args) {
+    SacHeadArgs H;
+    memcpy(&H, args, sizeof(H));
+    with_actions(H.A, [&](auto a) { hipLaunchKernelGGL(sac_head_kernel<decltype(a)::value>, dim3((H.rows + 3) / 4), dim3(256), 0, st, H); });
+}
+
+void fb_sac_launch_loss(hipStream_t st, const void *args) {
+    SacLossArgs L;
+    memcpy(&L, args, sizeof(L));
+    with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(sac_loss_kernel<decltype(a)::value>, dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
+}
+
+void fb_sac_launch_grad(hipStream_t st, const void *args) {
+    SacGradArgs L;
+    memcpy(&L, args, sizeof(L));
+    hipLaunchKernelGGL(sac_grad_kernel, dim3(L.FC / 16), dim3(256), 0, st, L);
+}
+
+// the memory checks of the two ring-fed SAC calls: a uniform memory at n-step 1
+static int sac_check_memory(fb_replay_t replay, const char *who) {
+    FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: SAC trains from a uniform memory only (prioritized replay is not offered)", who);
+    int n = 1; double g = 0.0;
+    const int rc = fb_replay_get_n_step(replay, &n, &g);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(n == 1, "%s: the memory has a %d-step view; SAC reads it at n-step 1 only", who, n);
+    return FB_OK;
+}
+
+extern "C" int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
+                                        double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
+    const char *who = "fb_sac_train_from_replay";
+    FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
+    FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
+    int rc = sac_check_memory(replay, who);
+    if (rc != FB_OK) return rc;
+    rc = fb_qnet_sac_check_train(net, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    FbRingSrc ring;
+    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_out, t_out, &ring);
+    if (rc != FB_OK) return rc;
+    if (batch >= 256) {                          // (W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
+        rc = fb_qnet_refresh_planes(net, stream);
+        if (rc != FB_OK) return rc;
+    }
+    return fb_qnet_sac_train_ring(net, batch, &ring, gamma, loss, q_target, flat_grad, stream);
+}
+
+extern "C" int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed, uint64_t step,
+                           int train, double gamma, float rho, void *stream) {
+    const char *who = "fb_sac_step";
+    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
+    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && b->idx, "%s: NULL buffer", who);
+    FB_REQUIRE(!train || (b->a && b->r && b->t && b->loss), "%s: a training step needs the a / r / t / loss buffers", who);
+    FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
+    int rc = sac_check_memory(replay, who);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "%s: n_envs %d does not match the env (%d) / replay (%d) handles", who,
+               n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
+    FB_REQUIRE(n_envs <= fb_qnet_max_rows(net), "%s: %d envs exceed 3*max_batch of the net", who, n_envs);
+    rc = fb_qnet_sac_check_train(net, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(rho >= 0.f && rho <= 1.f, "%s: rho must be in [0, 1] (0 = no target update; got %g)", who, (double)rho);
+    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
+    rc = fb_qnet_act_policy_nib(net, b->nib, n_envs, seed, step, 0, b->actions, nullptr, nullptr, nullptr, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
+    if (rc != FB_OK) return rc;
+    if (train) {
+        rc = fb_sac_train_from_replay(replay, net, batch, b->idx, b->a, b->r, b->t, gamma, b->loss, nullptr, b->flat_grad, stream);
+        if (rc != FB_OK) return rc;
+    }
+    if (rho > 0.f) rc = fb_qnet_soft_sync_target(net, rho, stream);
+    return rc;
+}

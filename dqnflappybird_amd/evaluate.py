@@ -127,6 +127,14 @@ def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
             raise ValueError(f"{path}: an actor-critic net computes in f32 only (dtype {dtype!r})")
         net.load_params(online, 0)
         return net
+    if "head" in z.files and str(z["head"][0]) == "sac":     # a SAC net (VecSAC): greedy play is the policy's argmax
+        net = QNet(2, fc_width, "sac", max_batch=max_batch)
+        if net.n_params != online.size:
+            raise ValueError(f"{path}: {online.size} online parameters do not match a SAC net of width {fc_width}")
+        if dtype != "f32":
+            raise ValueError(f"{path}: a SAC net computes in f32 only (dtype {dtype!r})")
+        net.load_params(online, 0)
+        return net
     if "quantiles" in z.files:                               # a QR net (VecBrain records its head and (N, kappa))
         n_q, kappa = z["quantiles"].tolist()
         head = str(z["head"][0])

@@ -302,6 +302,8 @@ AC_ARCH = "ac"                                            # advantage actor-crit
 AC_DEFAULTS = L.AC_DEFAULTS                               # (value_coef, entropy_coef) of a new actor-critic net
 AC_MAX_ROLLOUT = 128                                      # the longest rollout VecActorCritic takes
 PPO_DEFAULTS = L.PPO_DEFAULTS                             # (clip_eps, value_clip) of a new actor-critic net
+SAC_ARCH = "sac"                                          # discrete soft actor-critic: a policy head and two Q heads (include/fbdqn.h)
+SAC_DEFAULTS = L.SAC_DEFAULTS                             # (alpha, target_entropy / ln A, alpha_lr) of a new SAC net
 
 
 def check_sigma0(sigma0):
@@ -378,6 +380,24 @@ def check_ppo(clip_eps, value_clip):
     return e, c
 
 
+def check_sac(alpha, target_entropy, alpha_lr, actions=2):
+    """the argument checks of fb_qnet_set_sac, on the host (-> (alpha, target_entropy, alpha_lr) as float32-rounded floats);
+    target_entropy None: the library's default, 0.98 ln(actions) in float32"""
+    if not 2 <= int(actions) <= 8:
+        raise ValueError(f"actions must be in 2..8 for a SAC net, got {actions}")
+    if target_entropy is None:
+        target_entropy = np.float32(SAC_DEFAULTS[1]) * np.log(np.float32(int(actions)))
+    with np.errstate(over="ignore"):
+        a, h, lr = (float(np.float32(x)) for x in (alpha, target_entropy, alpha_lr))
+    if not (np.isfinite(a) and a > 0.0):
+        raise ValueError(f"alpha must be finite and > 0, got {alpha}")
+    if not np.isfinite(h):
+        raise ValueError(f"target_entropy must be finite, got {target_entropy}")
+    if not (np.isfinite(lr) and lr >= 0.0):
+        raise ValueError(f"alpha_lr must be finite and >= 0 (0 = a fixed temperature), got {alpha_lr}")
+    return a, h, lr
+
+
 def check_gae(gamma, gae_lambda):
     """the argument checks of fb_ac_gae, on the host (-> (gamma, lambda) as floats)"""
     g, l = float(gamma), float(gae_lambda)
@@ -440,7 +460,7 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
-    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH,)
+    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH, SAC_ARCH)
 
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
                  v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0,
@@ -452,7 +472,9 @@ class QNet:
         noisy=True (C51 archs only): factorised Gaussian noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the flat
         vector is [mu | sigma], and the net starts in mean mode (reset_noise, noise; include/fbdqn.h)
         arch='ac': an advantage actor-critic net -- the dueling net's parameters read raw, V = h . W_v + b_v and the policy's logits
-        h . W_pi + b_pi (include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values"""
+        h . W_pi + b_pi (include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values
+        arch='sac': a discrete soft actor-critic net -- the policy's logits h . W_pi + b_pi and two Q heads (2 <= actions <= 8;
+        include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values"""
         if arch not in self.ARCHS:
             raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
         self.noisy = bool(noisy)
@@ -480,6 +502,8 @@ class QNet:
         elif arch == "c51dueling":
             L.check(L.lib().fb_qnet_create_c51_dueling(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)),
                     "fb_qnet_create_c51_dueling")
+        elif arch == SAC_ARCH:
+            L.check(L.lib().fb_qnet_create_sac(self.FC, self.A, self.max_batch, C.byref(self.h)), "fb_qnet_create_sac")
         elif arch == AC_ARCH:
             L.check(L.lib().fb_qnet_create_ac(self.FC, self.A, self.max_batch, C.byref(self.h)), "fb_qnet_create_ac")
         elif arch in QR_ARCHS:
@@ -665,7 +689,8 @@ class QNet:
         """sample an action per env from the policy (fb_qnet_act_policy_nib; the draw is keyed (seed, step, row), greedy: the first argmax)
         -> (actions u8[n], value f32[n], logp f32[n][, logits f32[n, A]]).  value / logp / actions: tensors to write into (a rollout
         buffer's row).  value_only: no action and no draw -> value alone (the bootstrap V(s_T))"""
-        self._need_ac("act_policy_nib")
+        if self.arch != SAC_ARCH:
+            self._need_ac("act_policy_nib")
         _dev_check(nib_states, value, logp, actions)
         if nib_states.dtype != torch.uint8 or nib_states.dim() != 2 or nib_states.shape[1] != L.NIB_STRIDE:
             raise ValueError(f"nib_states must be uint8[n,{L.NIB_STRIDE}] (VecGameState.track_state())")
@@ -729,6 +754,68 @@ class QNet:
         L.check(L.lib().fb_qnet_ppo_train_step(self.h, B, L.ptr(s), L.ptr(a), L.ptr(adv), L.ptr(ret), L.ptr(logp_old), L.ptr(value_old),
                                                int(n_total or B), L.ptr(loss), L.ptr(flat_grad), L.current_stream()), "fb_qnet_ppo_train_step")
         return loss
+
+    # -- discrete soft actor-critic (arch='sac') ---------------------------------------
+    def _need_sac(self, what):
+        if self.arch != SAC_ARCH:
+            raise ValueError(f"{what} needs a SAC net (QNet(..., arch='sac'))")
+
+    def set_sac(self, alpha=SAC_DEFAULTS[0], target_entropy=None, alpha_lr=SAC_DEFAULTS[2]):
+        """the temperature alpha, the target entropy (None: 0.98 ln A) and the temperature's learning rate, 0 = fixed (fb_qnet_set_sac);
+        writes log alpha and clears the temperature's Adam state"""
+        self._need_sac("set_sac")
+        a, h, lr = check_sac(alpha, target_entropy, alpha_lr, self.A)
+        L.check(L.lib().fb_qnet_set_sac(self.h, a, h, lr), "fb_qnet_set_sac")
+
+    def sac(self):
+        """the net's current (alpha, target_entropy, alpha_lr) (fb_qnet_get_sac); synchronous"""
+        self._need_sac("sac")
+        a, h, lr = C.c_float(), C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_get_sac(self.h, C.byref(a), C.byref(h), C.byref(lr)), "fb_qnet_get_sac")
+        return a.value, h.value, lr.value
+
+    def sac_state(self):
+        """(log alpha, m, v, beta1 power, beta2 power) as float32[5] on the host (fb_qnet_get_sac_state); synchronous"""
+        self._need_sac("sac_state")
+        w = np.empty(5, np.float32)
+        L.check(L.lib().fb_qnet_get_sac_state(self.h, L.ptr(w)), "fb_qnet_get_sac_state")
+        return w
+
+    def set_sac_state(self, state):
+        self._need_sac("set_sac_state")
+        w = np.ascontiguousarray(state, np.float32)
+        if w.shape != (5,):
+            raise ValueError("the temperature state is float32[5]: (log alpha, m, v, beta1 power, beta2 power)")
+        L.check(L.lib().fb_qnet_set_sac_state(self.h, L.ptr(w)), "fb_qnet_set_sac_state")
+
+    def forward_sac(self, states, which=L.NET_ONLINE):
+        """u8 states -> (logits, q1, q2), each f32[B, A], of the online or the target net (fb_qnet_forward_sac)"""
+        self._need_sac("forward_sac")
+        _dev_check(states)
+        if states.dtype != torch.uint8 or states.dim() != 4 or tuple(states.shape[1:]) != (80, 80, 4):
+            raise ValueError("states must be uint8[B,80,80,4]")
+        B = states.shape[0]
+        z, q1, q2 = (torch.empty((B, self.A), dtype=torch.float32, device=self.device) for _ in range(3))
+        L.check(L.lib().fb_qnet_forward_sac(self.h, int(which), L.ptr(states), B, L.ptr(z), L.ptr(q1), L.ptr(q2), L.current_stream()),
+                "fb_qnet_forward_sac")
+        return z, q1, q2
+
+    def sac_train_step(self, s, a, r, s2, t, gamma=0.99, flat_grad=None, want_target=True):
+        """one SAC step on <= 256 gathered transitions (fb_qnet_sac_train_step).  flat_grad=None applies Adam (and, with alpha_lr > 0,
+        the temperature's step); a float32[n_params] tensor receives the gradient instead.
+        -> (loss f32[6]: total, mean d1^2, mean d2^2, mean L_pi, mean entropy, the alpha used; q_target f32[B] or None)"""
+        self._need_sac("sac_train_step")
+        _dev_check(s, a, r, s2, t, flat_grad)
+        for name, x in (("s", s), ("s2", s2)):
+            if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (80, 80, 4) or x.shape[0] != s.shape[0]:
+                raise ValueError(f"{name} must be uint8[B,80,80,4]")
+        B = s.shape[0]
+        check_sac_batch(B, a, r, t, flat_grad, self.n_params)
+        loss = torch.zeros(6, dtype=torch.float32, device=self.device)
+        y = torch.empty(B, dtype=torch.float32, device=self.device) if want_target else None
+        L.check(L.lib().fb_qnet_sac_train_step(self.h, B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), float(gamma), L.ptr(loss), L.ptr(y),
+                                               L.ptr(flat_grad), L.current_stream()), "fb_qnet_sac_train_step")
+        return loss, y
 
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):
@@ -928,6 +1015,37 @@ def check_ac_batch(B, a, adv, ret, n_total, flat_grad, n_params):
             raise ValueError(f"{name} must be float32[{B}]")
 
 
+def check_sac_batch(B, a, r, t, flat_grad, n_params):
+    """the shape checks of the two SAC training calls, on the host"""
+    if not 1 <= B <= 256:
+        raise ValueError(f"a SAC batch holds 1..256 samples, got {B}")
+    for name, x, dt in (("a", a, torch.uint8), ("r", r, torch.float32), ("t", t, torch.uint8)):
+        if x is not None and (x.dtype != dt or x.numel() != B):
+            raise ValueError(f"{name} must be {dt}[{B}]")
+    if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
+        raise ValueError(f"flat_grad must be float32[{n_params}]")
+
+
+def sac_train_from_replay(replay, net, idx, gamma=0.99, flat_grad=None, want_target=False):
+    """QNet.sac_train_step on the transitions at the deque positions idx of a uniform memory at n-step 1, read from its frame ring in
+    place (fb_sac_train_from_replay) -> (loss f32[6], a u8[B], r f32[B], t u8[B][, q_target f32[B]])"""
+    if net.arch != SAC_ARCH:
+        raise ValueError("sac_train_from_replay needs a SAC net (QNet(..., arch='sac'))")
+    if replay.prioritized:
+        raise ValueError("sac_train_from_replay trains from a uniform memory only")
+    _dev_check(idx, flat_grad)
+    if idx.dtype != torch.int64:
+        raise ValueError("idx must be int64[B]")
+    B, dev = int(idx.numel()), idx.device
+    check_sac_batch(B, None, None, None, flat_grad, net.n_params)
+    a = torch.empty(B, dtype=torch.uint8, device=dev); r = torch.empty(B, dtype=torch.float32, device=dev)
+    t = torch.empty(B, dtype=torch.uint8, device=dev); loss = torch.zeros(6, dtype=torch.float32, device=dev)
+    y = torch.empty(B, dtype=torch.float32, device=dev) if want_target else None
+    L.check(L.lib().fb_sac_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(a), L.ptr(r), L.ptr(t), float(gamma), L.ptr(loss), L.ptr(y),
+                                             L.ptr(flat_grad), L.current_stream()), "fb_sac_train_from_replay")
+    return (loss, a, r, t, y) if want_target else (loss, a, r, t)
+
+
 def ac_gae(reward, terminal, value, gamma=0.99, gae_lambda=0.95):
     """generalised advantage estimation on the device (fb_ac_gae): reward f32[T, N], terminal u8[T, N], value f32[T + 1, N] (row T: the
     bootstrap V(s_T)) -> (adv f32[T, N], ret f32[T, N]); float64 arithmetic in the order include/fbdqn.h pins"""
@@ -1059,6 +1177,41 @@ class AcRolloutStep:
         """-> actions uint8[N] (device); row `slot` of reward / terminal / value / logp is written"""
         L.check(L.lib().fb_ac_rollout_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(seed), int(step), int(slot),
                                            L.current_stream()), "fb_ac_rollout_step")
+        return self.actions
+
+
+class SacStep:
+    """One whole step of the SAC loop as a single host call (fb_sac_step): sample the policy -> frame_step -> store + sample the
+    minibatch -> (train) the SAC step from the ring -> (polyak > 0) the soft target update.  The results of the separate calls in that
+    order; the pointers are bound once."""
+
+    def __init__(self, env, replay, net, batch=32, gamma=0.99, polyak=0.005, flat_grad=None):
+        if net.arch != SAC_ARCH:
+            raise ValueError("SacStep needs a SAC net (QNet(..., arch='sac'))")
+        if replay.prioritized:
+            raise ValueError("SacStep trains from a uniform memory only")
+        if getattr(env, "nib", None) is None:
+            raise ValueError("call env.track_state() first: the acting path reads the env kernel's nibble states")
+        if not 1 <= int(batch) <= 256:
+            raise ValueError(f"batch must be in 1..256, got {batch}")
+        _dev_check(flat_grad)
+        self.env, self.replay, self.net = env, replay, net
+        self.batch, self.gamma, self.rho, self.flat_grad = int(batch), float(gamma), check_polyak(polyak, allow_off=True), flat_grad
+        dev, B = env.device, self.batch
+        self.actions = torch.zeros(env.n, dtype=torch.uint8, device=dev)
+        self.idx = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.a = torch.empty(B, dtype=torch.uint8, device=dev)
+        self.r = torch.empty(B, dtype=torch.float32, device=dev)
+        self.t = torch.empty(B, dtype=torch.uint8, device=dev)
+        self.loss = torch.zeros(6, dtype=torch.float32, device=dev)
+        p = lambda x: None if x is None else x.data_ptr()
+        self.buf = L.StepBuffers(p(env.nib), p(self.actions), p(env.frame_bits), p(env.reward), p(env.terminal), p(env.score),
+                                 p(self.idx), None, None, p(self.a), p(self.t), p(self.r), p(self.loss), p(flat_grad), None, None, None)
+
+    def __call__(self, seed=0, step=0, train=True):
+        """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the six loss numbers are self.loss"""
+        L.check(L.lib().fb_sac_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, self.batch, int(seed), int(step),
+                                    int(bool(train)), self.gamma, self.rho, L.current_stream()), "fb_sac_step")
         return self.actions
 
 

@@ -556,6 +556,9 @@ class VecBrain:
         if checkpoint_head(z) == "ac":                       # (an actor-critic net has the dueling net's parameter count: the head tells)
             raise ValueError(f"checkpoint {path} holds an ac head (a VecActorCritic's), this is a VecBrain: load it with "
                              "dqnflappybird_amd.vecac.VecActorCritic")
+        if checkpoint_head(z) == "sac":
+            raise ValueError(f"checkpoint {path} holds a sac head (a VecSAC's), this is a VecBrain: load it with "
+                             "dqnflappybird_amd.vecsac.VecSAC")
         saved_world = int(z["scalars"][2]) if len(z["scalars"]) > 2 else 1
         if saved_world != self.world:
             raise ValueError(f"checkpoint {path} was written by {saved_world} rank(s), this job has {self.world}")

@@ -674,6 +674,61 @@ int fb_ppo_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const
 int fb_ac_normalize_adv(const float *adv, int64_t n, float *out, void *stream);
 int fb_ac_permute(int64_t n, uint64_t seed, uint64_t draw, int64_t *out, void *stream);
 
+/* ------------------------------------------------------------------ discrete soft actor-critic (SAC; Haarnoja et al. 2018, Christodoulou 2019)
+ * The off-policy learner of a STOCHASTIC policy: a policy head and two Q heads on the shared trunk, trained from the replay memory with an
+ * entropy bonus whose temperature alpha is fixed or learned.  One GPU, fp32, a uniform memory at n-step 1.
+ * A SAC net (FB_ARCH_SAC, fb_qnet_create_sac; 2 <= A <= 8) has the trunk and fc1 of every net, then three heads read RAW:
+ *   W_pi[FC,A] b_pi[A] W_q1[FC,A] b_q1[A] W_q2[FC,A] b_q2[A]      (W_pi b_pi where a plain net of that shape has its head)
+ * with h = relu(h_fc1):  z = h . W_pi + b_pi,  Q1 = h . W_q1 + b_q1,  Q2 = h . W_q2 + b_q2.
+ *   init        fb_qnet_init_params: element i of the flat vector draws as in every net -- a weight from Philox counter (i, ctr, FB_STREAM_INIT, 0)
+ *               under the seed, a bias 0.01 -- so the trunk, fc1 and W_pi b_pi are the plain net's of that seed bit for bit, and the two Q
+ *               heads, keyed by their own indices, differ from each other
+ *   acting      fb_qnet_forward / _act / _act_nib / fb_eval_run / fb_eval_q treat the LOGITS as the Q values (the plain head over W_pi b_pi):
+ *               greedy play is argmax pi.  fb_qnet_forward_sac returns (z, Q1, Q2) of the online or the target net -- z the very bits
+ *               fb_qnet_forward returns.  fb_qnet_act_policy_nib takes a SAC net as well: softmax, draw, greedy rule, logp and logits as
+ *               pinned for an AC net; value may be NULL, else it receives the soft state value, float32, ascending c from 0:
+ *                 V = sum_c p_c * (fminf(Q1_c, Q2_c) - alpha * log p_c)
+ *   settings    fb_qnet_set_sac(alpha, target_entropy, alpha_lr): alpha finite > 0, target_entropy finite, alpha_lr finite >= 0; 0.2,
+ *               0.98f * logf(A) and 0 in a new net; alpha_lr = 0: a fixed temperature.  The net holds five device words (log alpha, m, v,
+ *               pow1, pow2); set writes (logf(alpha), 0, 0, beta1, beta2) with the net's betas at that time.  fb_qnet_get_sac returns
+ *               expf(log alpha); fb_qnet_get_sac_state / _set_sac_state move the five words (checkpoints).  All four are synchronous.
+ *               Every kernel reads alpha = expf(log alpha) on the device
+ *   train step  per sample b, fp32, sums over c ascending from 0, alpha the value the previous step left; ' marks s':
+ *                 p', lp' = softmax(z(s'; online))       Q1', Q2' from the TARGET net       V' as the soft state value above
+ *                 r = (R == 0.1f) ? 0.1 : (double)R      y = (float)(t ? r : r + gamma * (double)V')      (no gradient through y)
+ *                 d_i = Q_i(s, a) - y       L_q = d_1^2 + d_2^2       dLoss/dQ_i(s, a) = (2 d_i) / B, the other columns 0
+ *                 p, lp = softmax(z(s))     f_c = alpha * lp_c - fminf(Q1_c(s), Q2_c(s))  (min Q a constant)     L_pi = sum_c p_c f_c
+ *                 H = -sum_c p_c lp_c       dLoss/dz_c = (p_c (f_c - L_pi)) / B       (the actor's gradient enters the shared trunk)
+ *               loss[0..5]: m1 = (sum_b d_1^2) / B, m2 likewise, mp = (sum_b L_pi) / B, mh = (sum_b H) / B, sums over b ascending;
+ *               loss = {(m1 + m2) + mp, m1, m2, mp, mh, the alpha used}.  No atomics: equal inputs give equal bits.
+ *               an action >= A reads A - 1.  1 <= batch <= min(max_batch, 256); 0 <= gamma <= 1.  q_target f32[batch] (y) or NULL.
+ *               flat_grad and the net's max_grad_norm as in fb_qnet_train_step.  fb_qnet_sac_train_step takes gathered states,
+ *               fb_sac_train_from_replay ring positions (a_out / r_out / t_out receive the ring's a, r, t); the two agree bit for bit
+ *   temperature when alpha_lr > 0 and the caller exports nothing (flat_grad NULL), behind the net's Adam tick, on one thread, b1 / b2 / eps the net's:
+ *                 g = mh - target_entropy        at = alpha_lr * sqrtf(1 - pow2) / (1 - pow1)        pow1 *= b1   pow2 *= b2
+ *                 m += (g - m) * (1 - b1)        v += (g * g - v) * (1 - b2)        log alpha -= (m * at) / (sqrtf(v) + eps)
+ *               An exporting step and fb_qnet_apply_adam leave the five words alone
+ *   loop step   fb_sac_step = fb_qnet_act_policy_nib (sampled; no value / logp) -> fb_env_step -> fb_replay_push_sample(batch) -> if train:
+ *               fb_sac_train_from_replay (b->loss f32[6], b->flat_grad) -> if rho > 0: fb_qnet_soft_sync_target(rho); those calls in that
+ *               order on `stream`, their results bit for bit.  No riders, no split schedule; it pushes: not capturable, like fb_vec_step
+ *   refused     FB_ERR_INVALID before any launch or counter change: on a SAC net every FB_ALGO_* of fb_qnet_train_step / fb_train_from_replay /
+ *               fb_train_steps / fb_vec_step / fb_vec_step_dp, the A2C and PPO calls, fb_qnet_set_huber / _get_huber, fb_qnet_set_munchausen /
+ *               _get_munchausen, FB_DTYPE_BF16 for inference or training; fb_qnet_create with arch 7 and fb_qnet_create_c51_noisy with it;
+ *               the SAC calls below on a net that is not a SAC net; a prioritized or n-step memory; the batch, gamma and settings rules above
+ *   not offered data-parallel SAC, bf16, prioritized replay, n-step returns, noisy or distributional critics, riders or the split schedule. */
+#define FB_ARCH_SAC 7
+int fb_qnet_create_sac(int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
+int fb_qnet_set_sac(fb_qnet_t h, float alpha, float target_entropy, float alpha_lr);
+int fb_qnet_get_sac(fb_qnet_t h, float *alpha_host, float *target_entropy_host, float *alpha_lr_host);
+int fb_qnet_get_sac_state(fb_qnet_t h, float *state_host /*f32[5]*/);
+int fb_qnet_set_sac_state(fb_qnet_t h, const float *state_host /*f32[5]*/);
+/* states u8[B,80,80,4] -> logits, q1, q2 f32[B,A]; 1 <= B <= 3 * max_batch; which: FB_NET_ONLINE / FB_NET_TARGET */
+int fb_qnet_forward_sac(fb_qnet_t h, int which, const uint8_t *states, int batch, float *logits, float *q1, float *q2, void *stream);
+int fb_qnet_sac_train_step(fb_qnet_t h, int batch, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
+                           double gamma, float *loss /*f32[6]*/, float *q_target, float *flat_grad, void *stream);
+int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
+                             double gamma, float *loss /*f32[6]*/, float *q_target, float *flat_grad, void *stream);
+
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
 int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host);
@@ -812,6 +867,10 @@ int fb_qnet_split_stats(fb_qnet_t net, int64_t *steps_host, int64_t *clean_host)
 int fb_vec_step_set_schedule(int split);
 int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int algo, int batch,
                 float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream);
+/* The vector step of a SAC net (the SAC block above pins it): of *b it reads nib, actions, frame_bits, reward, terminal, score, idx, and for a
+ * training step a, r, t, loss (f32[6]) and flat_grad (or NULL). */
+int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed, uint64_t step,
+                int train, double gamma, float rho, void *stream);
 
 /* fb_replay_gather + fb_qnet_train_step WITHOUT the gathered copies (BrainDQN.py:197-223 from the indices on): the minibatch is
  * described by its indices, the conv trunk reads the replay's 1-bit frames directly (5 x 800 B per transition instead of writing and

@@ -1,0 +1,74 @@
+"""Does the SAC loop LEARN?  One seeded VecSAC run per setting: the windowed score, the policy's entropy and the temperature, then a
+greedy evaluate() on fresh games.  One seed says that the loop runs and learns, not how well.
+
+    python tools/learn_sac.py [--envs 1024] [--steps 60000] [--window 5000] [--alpha-lrs 0,1e-4] [--eval-envs 4096] [--seed 0] [--out FILE]
+                              [--budget-s S  (stop a run after S seconds of wall time)]
+
+Every `window` steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and
+zeroed, so each row is the window's own figure.  Rows go to stdout, and are appended to --out when one is given.
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from dqnflappybird_amd.vecsac import VecSAC  # noqa: E402
+
+
+def run(n_envs, steps, window, alpha_lr, seed, eval_envs, budget_s, emit):
+    sac = VecSAC(n_envs, alpha_lr=alpha_lr, seed=seed)
+    emit(f"# envs {n_envs}  batch {sac.batch}  alpha {sac.alpha:g}  target_entropy {sac.target_entropy:g}  alpha_lr {sac.alpha_lr:g}  "
+         f"polyak {sac.polyak:g}  observe {sac.observe}  lr {sac.lr:g}  seed {seed}")
+    emit("#   env_steps  episodes  mean_score  max_score  pipes/episode    q_loss  policy_loss   entropy     alpha   steps/s")
+    t0 = t_run = time.time()
+    sac.stats.zero_()
+    for k in range(1, steps + 1):
+        losses = sac.step()
+        if k % window == 0 or k == steps:
+            tot, q1, q2, lpi, ent, alpha = losses.tolist()
+            ep, ssum, smax, pipes = sac.stats.tolist()
+            sac.stats.zero_()
+            sac.net.check_range()
+            now = time.time()
+            emit(f"  {k * n_envs:11d} {ep:9d} {ssum / max(ep, 1):11.3f} {smax:10d} {pipes / max(ep, 1):14.3f} {q1 + q2:9.4g} {lpi:12.4g} "
+                 f"{ent:9.4f} {alpha:9.5f} {window / (now - t0):9.0f}")
+            t0 = now
+            if budget_s and now - t_run > budget_s:
+                emit(f"# stopped after {k} steps: the time budget of {budget_s:g} s is spent")
+                break
+    if eval_envs:
+        res = sac.evaluate(n_envs=eval_envs, episodes=1)
+        emit(f"# greedy evaluate() on {eval_envs} fresh games: mean score {res.score.mean():.3f}, median {float(__import__('numpy').median(res.score)):.1f}, "
+             f"max {int(res.score.max())}, mean length {res.length.mean():.1f}")
+    torch.cuda.synchronize()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=60000)
+    ap.add_argument("--window", type=int, default=5000)
+    ap.add_argument("--alpha-lrs", default="0,1e-4")
+    ap.add_argument("--eval-envs", type=int, default=4096)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--budget-s", type=float, default=0.0)
+    ap.add_argument("--out", default=None, help="also append the rows to this file")
+    a = ap.parse_args()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out if a.out else os.devnull, "a") as out:
+        def emit(line):
+            for f in (sys.stdout, out):
+                print(line, file=f); f.flush()
+
+        emit(f"# tools/learn_sac.py on {torch.cuda.get_device_name(0)}: {' '.join(sys.argv[1:])}")
+        for alr in [float(x) for x in a.alpha_lrs.split(",")]:
+            run(a.envs, a.steps, a.window, alr, a.seed, a.eval_envs, a.budget_s, emit)
+
+
+if __name__ == "__main__":
+    main()
