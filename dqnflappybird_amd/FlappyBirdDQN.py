@@ -114,7 +114,12 @@ def build_parser():
     parser.add_argument("--acting-noise", choices=("shared", "env"), default="shared",
                         help="--noisy: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
     parser.add_argument("--n-quantiles", type=int, default=None, help="QR models: the number of quantiles N (default 51)")
-    parser.add_argument("--kappa", type=float, default=None, help="QR models: the quantile Huber loss's threshold (default 1)")
+    parser.add_argument("--kappa", type=float, default=None, help="QR models and --model iqn: the quantile Huber loss's threshold (default 1)")
+    parser.add_argument("--n-tau", type=int, default=None, help="--model iqn: quantile fractions sampled per transition for the online net N (default 8)")
+    parser.add_argument("--n-tau-target", type=int, default=None, help="--model iqn: quantile fractions sampled for the target N' (default 8)")
+    parser.add_argument("--n-tau-act", type=int, default=None, help="--model iqn: the acting grid K (default 32)")
+    parser.add_argument("--cvar", type=float, default=None, help="--model iqn: act on CVaR_ETA, 0 < ETA <= 1 (default 1 = the mean)")
+    parser.add_argument("--double", action="store_true", help="--model iqn: the greedy next action from the online net (Double-DQN's target)")
     parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper: the softmax temperature (default 0.03)")
     parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9); "
                                                                    "--model sac: the temperature (default 0.2)")
@@ -163,6 +168,34 @@ def sac_kwargs(args, parser):
     return kw
 
 
+def iqn_kwargs(args, parser):
+    """--model iqn's options as VecIQN's keywords; everything is refused here, by name, before anything touches the GPU"""
+    given = [n for n, v in (("--n-tau", args.n_tau), ("--n-tau-target", args.n_tau_target), ("--n-tau-act", args.n_tau_act), ("--cvar", args.cvar),
+                            ("--double", args.double or None)) if v is not None]
+    if args.model != "iqn":
+        if given:
+            parser.error(f"{' / '.join(given)} need --model iqn, not --model {args.model}")
+        return None
+    if not args.vec:
+        parser.error("--model iqn needs --vec: implicit quantile networks run in the vectorised loop only")
+    for name, on in (("--noisy", args.noisy), ("--huber", args.huber is not None), ("--n-quantiles", args.n_quantiles is not None),
+                     ("--tau / --alpha / --clip", args.tau is not None or args.alpha is not None or args.clip is not None)):
+        if on:
+            parser.error(f"{name} is not an option of --model iqn (--n-tau, --n-tau-target, --n-tau-act, --kappa, --cvar, --double, --n-step, "
+                         "--polyak, --max-grad-norm are)")
+    from .veciqn import check_args
+    kw = dict(batch=min(32, args.vec), double_q=args.double, n_step=args.n_step, n_tau=8 if args.n_tau is None else args.n_tau,
+              n_tau_next=8 if args.n_tau_target is None else args.n_tau_target, n_tau_act=32 if args.n_tau_act is None else args.n_tau_act,
+              kappa=1.0 if args.kappa is None else args.kappa, cvar=1.0 if args.cvar is None else args.cvar,
+              polyak=0.0 if args.polyak is None else args.polyak, max_grad_norm=0.0 if args.max_grad_norm is None else args.max_grad_norm)
+    try:
+        check_args(args.vec, kw["batch"], kw["n_tau"], kw["n_tau_next"], kw["n_tau_act"], kw["kappa"], kw["cvar"], kw["n_step"], kw["polyak"], 500, 1000,
+                   1_000_000, 0.03, 0.0, 0.99, 1e-6, kw["max_grad_norm"], None)
+    except ValueError as e:
+        parser.error(str(e))
+    return kw
+
+
 def a2c_kwargs(args, parser):
     """--model a2c's and --model ppo's options as VecActorCritic's keywords; everything is refused here, before anything touches the GPU"""
     given = [n for n, v in (("--rollout", args.rollout), ("--gae-lambda", args.gae_lambda), ("--value-coef", args.value_coef),
@@ -205,6 +238,11 @@ def main():
     okw = optimiser_kwargs(args, parser)                 # (refused before anything touches the GPU)
     akw = a2c_kwargs(args, parser)
     skw = sac_kwargs(args, parser)
+    ikw = iqn_kwargs(args, parser)
+    if ikw is not None:                                  # implicit quantile networks: a class of its own, one GPU
+        from .veciqn import VecIQN
+        VecIQN(args.vec, **ikw).run(args.steps or 1000, log_every=0 if args.quiet else 100)
+        return
     if skw is not None:                                  # the off-policy stochastic-policy learner: a class of its own, one GPU
         from .vecsac import VecSAC
         VecSAC(args.vec, **skw).run(args.steps or 1000, log_every=0 if args.quiet else 100)

@@ -29,6 +29,9 @@ ARCH_AC = 6                                           # advantage actor-critic: 
 AC_DEFAULTS = (0.5, 0.01)                             # (value_coef, entropy_coef) of a new actor-critic net
 ARCH_SAC = 7                                          # discrete soft actor-critic: a policy head and two Q heads (include/fbdqn.h)
 SAC_DEFAULTS = (0.2, 0.98, 0.0)                       # (alpha, target_entropy / ln A, alpha_lr) of a new SAC net
+ARCH_IQN = 8                                          # implicit quantile network: the plain layout and a cosine embedding (include/fbdqn.h)
+IQN_DEFAULTS = (8, 8, 32, 1.0)                        # (n_tau, n_tau_next, n_tau_act, kappa) of a new IQN net; its risk setting eta starts at 1
+IQN_COS = 64                                          # include/fbdqn.h FB_IQN_COS
 PPO_DEFAULTS = (0.2, 0.0)                             # (clip_eps, value_clip) of a new actor-critic net; value_clip 0 = off
 NOISE_SAMPLE, NOISE_MEAN = 0, 1                       # include/fbdqn.h FB_NOISE_* (fb_qnet_reset_noise)
 ACT_NOISE_SHARED, ACT_NOISE_PER_ENV = 0, 1            # include/fbdqn.h FB_ACT_NOISE_* (fb_qnet_set_acting_noise)
@@ -126,6 +129,14 @@ SIGNATURES = {
     "fb_qnet_sac_train_step": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
     "fb_sac_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
     "fb_sac_step": [_vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _f, _vp],
+    "fb_qnet_create_iqn": [_i, _i, _i, _i, _i, _f, _i, _vp],
+    "fb_qnet_set_iqn_risk": [_vp, _f],
+    "fb_qnet_get_iqn": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "fb_qnet_forward_iqn": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp],
+    "fb_iqn_draw_taus": [_i, _i, _u64, _u64, _i, _vp, _vp],
+    "fb_qnet_iqn_train_step": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _vp, _vp],
+    "fb_iqn_train_from_replay": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _vp, _vp],
+    "fb_iqn_step": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _i, _d, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],

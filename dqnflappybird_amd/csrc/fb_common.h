@@ -85,6 +85,7 @@ __device__ __forceinline__ void fb_flag_wait(const unsigned long long *flag, uns
 #define FB_STREAM_ENV_NOISE 7u  // per-env acting noise of noisy nets, counter = (env * nz + element, step_lo, 7, step_hi) (fb_qnet_act_nib_env_noise)
 #define FB_STREAM_POLICY 8u   // the policy's action draw of an actor-critic net, counter = (row, step_lo, 8, step_hi) (fb_qnet_act_policy_nib)
 #define FB_STREAM_PERM 9u     // the round function of PPO's minibatch permutation, counter = (R, draw_lo, 9, draw_hi) (fb_ac_permute)
+#define FB_STREAM_TAU 10u     // IQN's quantile fractions, counter = (b * 64 + i, step_lo, 10, step_hi); .x online, .y target (fb_iqn_draw_taus)
 
 struct fb_u4 { uint32_t x, y, z, w; };
 
@@ -295,6 +296,32 @@ int fb_qnet_is_sac(fb_qnet_t h);              // 1: a SAC net (fb_qnet_create_sa
 // the checks of the two SAC training calls, `who` in the message; the ring-fed SAC train step behind fb_sac_train_from_replay's checks
 int fb_qnet_sac_check_train(fb_qnet_t h, int batch, double gamma, const char *who);
 int fb_qnet_sac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
+// ---- implicit quantile networks (FB_ARCH_IQN): the kernels live in fb_iqn.hip, a code object of their own; fb_qnet.hip fills these structs
+// and hands them to the launchers as bytes.  off: the PLAIN layout (wq / bq = W_q b_q); io: the embedding behind it, W_e[64][FC] b_e[FC].
+// A fold block is [b_fc1 | phibar * W_q | b_q]: the plain layout from b_fc1 on, so `block - off.bf1` is read as a plain net's parameters
+struct IqnOff { int we, be; };
+struct IqnFoldArgs { const float *P; float *fold; int FC, A, K; NetOff off; IqnOff io; float eta; };
+// theta f32[rows][M][A] at tau f32[rows][M]
+struct IqnHeadArgs { const float *hf, *P; int stot, nks, FC, A, rows, M; NetOff off; IqnOff io; const float *tau; float *theta; };
+// P0 / P1: the online / target parameters; F: the fold block (minus off.bf1) of the net that chooses a* -- online (double_q) or target --
+// and arow0 the first of its rows of hf (B or 2 B).  tau / tau_next NULL: the draws of (seed, step)
+struct IqnLossArgs {
+    const float *hf, *P0, *P1, *F; int arow0, stot, nks, FC, A, B, N, Np; NetOff off; IqnOff io; float kappa;
+    const uint8_t *act, *term; const float *rew; double gamma; const float *tau, *tau_next;
+    uint32_t seed_lo, seed_hi, step_lo, step_hi;
+    float *dl, *gw, *dhf, *dpre, *ctab, *t_out;                  // dl f32[B][4]; gw f32[B][FC]; dpre f32[B N][FC]; ctab f32[B N][64]; t_out f32[B][Np] or NULL
+};
+struct IqnGradArgs { int B, FC, A, N; NetOff off; IqnOff io; const float *dl, *gw, *dhf, *dpre, *ctab; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; };
+void fb_iqn_launch_fold(hipStream_t st, const void *args);
+void fb_iqn_launch_head(hipStream_t st, const void *args);
+void fb_iqn_launch_loss(hipStream_t st, const void *args);
+void fb_iqn_launch_grad(hipStream_t st, const void *args);
+int fb_qnet_is_iqn(fb_qnet_t h);              // 1: an IQN net (fb_qnet_create_iqn)
+// the checks of the two IQN training calls, `who` in the message; the ring-fed IQN train step behind fb_iqn_train_from_replay's checks
+// (gamma: the bootstrap's discount)
+int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int batch, double gamma, const char *who);
+int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int batch, const FbRingSrc *ring, const float *tau, const float *tau_next, uint64_t seed,
+                           uint64_t step, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);

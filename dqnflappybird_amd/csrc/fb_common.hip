@@ -137,6 +137,7 @@ extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int b
     FB_REQUIRE(replay && net && idx && s && s2 && a && r && t && loss && n_steps >= 1, "fb_train_steps: bad argument");
     FB_REQUIRE(!fb_qnet_is_ac(net), "fb_train_steps: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only");
     FB_REQUIRE(!fb_qnet_is_sac(net), "fb_train_steps: a SAC net trains through fb_qnet_sac_train_step / fb_sac_train_from_replay only");
+    FB_REQUIRE(!fb_qnet_is_iqn(net), "fb_train_steps: an IQN net trains through fb_qnet_iqn_train_step / fb_iqn_train_from_replay only");
     FB_REQUIRE(!is_per_algo(algo), "fb_train_steps: prioritized replay needs the importance weights: use the separate calls (algo %d)", algo);
     FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_train_steps: a noisy net needs a noise key per step, which this call has none of: use fb_vec_step or "
                "fb_qnet_reset_noise + fb_train_from_replay");
@@ -290,6 +291,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "fb_vec_step: NULL env buffer");
     FB_REQUIRE(!fb_qnet_is_ac(net), "fb_vec_step: an actor-critic net steps through fb_ac_rollout_step and trains through fb_ac_train_from_replay only");
     FB_REQUIRE(!fb_qnet_is_sac(net), "fb_vec_step: a SAC net steps through fb_sac_step and trains through fb_sac_train_from_replay only");
+    FB_REQUIRE(!fb_qnet_is_iqn(net), "fb_vec_step: an IQN net steps through fb_iqn_step and trains through fb_iqn_train_from_replay only");
     const bool per = is_per_algo(algo);      // (FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 / QR _PER algos)
     if (per && train) FB_REQUIRE(b->isw && b->isw32 && b->abs_err, "fb_vec_step: the prioritized step needs the isw / isw32 / abs_err buffers");
     // every argument check of the calls below happens HERE, before the replay's push counter moves or anything is launched: a
@@ -485,6 +487,7 @@ extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo,
     FB_REQUIRE(replay && net && idx && a && r && t && loss, "fb_train_from_replay: NULL argument");
     FB_REQUIRE(!fb_qnet_is_ac(net), "fb_train_from_replay: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only");
     FB_REQUIRE(!fb_qnet_is_sac(net), "fb_train_from_replay: a SAC net trains through fb_qnet_sac_train_step / fb_sac_train_from_replay only");
+    FB_REQUIRE(!fb_qnet_is_iqn(net), "fb_train_from_replay: an IQN net trains through fb_qnet_iqn_train_step / fb_iqn_train_from_replay only");
     FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER, FB_ALGO_MDQN .. FB_ALGO_DOUBLE_PER)", algo);
     // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
     // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any

@@ -154,6 +154,7 @@ extern "C" int fb_vec_step_dp(fb_dist_t d, fb_env_t env, fb_replay_t replay, fb_
     FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_vec_step_dp: data parallel does not take a noisy net (noisy nets are C51 nets: one GPU only)");
     FB_REQUIRE(!fb_qnet_is_ac(net), "fb_vec_step_dp: data-parallel A2C is not supported (an actor-critic net steps through fb_ac_rollout_step)");
     FB_REQUIRE(!fb_qnet_is_sac(net), "fb_vec_step_dp: data-parallel SAC is not supported (a SAC net steps through fb_sac_step)");
+    FB_REQUIRE(!fb_qnet_is_iqn(net), "fb_vec_step_dp: data-parallel IQN is not supported (an IQN net steps through fb_iqn_step)");
     FB_REQUIRE(!fb_qnet_is_c51(net) && !is_c51_algo(algo),
                "fb_vec_step_dp: data-parallel C51 is not supported (C51 trains through fb_vec_step, fb_train_from_replay, fb_train_steps)");
     FB_REQUIRE(!fb_qnet_is_qr(net) && !is_qr_algo(algo),

@@ -1,0 +1,415 @@
+// fb_iqn.hip -- implicit quantile networks (IQN) on the replay ring: the kernels of an FB_ARCH_IQN net and the fb_iqn_* entry points, as a
+// code object of their own (fb_qnet.hip routes to the launchers below and gets no kernel: a kernel added to ITS code object moves the others).
+// include/fbdqn.h pins the semantics.  Parameters behind b_fc1: W_q b_q (the plain head's place), then the embedding W_e[64][FC] b_e[FC];
+// theta(tau)_a = b_q[a] + sum_k (h_k phi_k(tau)) W_q[k, a], phi_k = relu(b_e[k] + sum_j cos(pi j tau) W_e[j, k]).
+//   iqn_fold_kernel   phibar over the acting grid and the fold block [b_fc1 | phibar * W_q | b_q] of one net: what every forward-only path reads
+//   iqn_head_kernel   theta at the caller's tau (fb_qnet_forward_iqn); one workgroup per state
+//   iqn_loss_kernel   training, launch 1 of 2: per sample a*, the target quantiles, theta, the pairwise quantile Huber loss, d theta, then the
+//                     dhf row, the W_q-gradient row, the embedding's pre-activation gradients and the cosine rows; one workgroup per sample
+//   iqn_grad_kernel   training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_q, W_e, b_e; workgroup 0: b_q, the loss, Adam's tick
+// Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
+// A lane owns a unit k and keeps W_e[:, k] in 64 registers; the cosine rows sit in LDS and are read as broadcasts; phi is recomputed in the
+// backward pass instead of stored.
+#include "fb_common.h"
+#include <math.h>
+#include <type_traits>
+
+namespace {
+#include "fb_head.h"
+#include "fb_policy.h"
+
+constexpr int IQN_MAXB = 256;        // the train step's batch limit (fb_qnet.hip MAXTB)
+constexpr int IQN_E = FB_IQN_COS;    // cosines of the embedding
+constexpr int IQN_MAXT = 64;         // most tau per state in any call
+
+// c_j(tau): formed in double, rounded once (a float32 argument of up to 198 rad would cost 1e-5)
+__device__ __forceinline__ float iqn_cos(int j, float tau) { return (float)cos(M_PI * (double)j * (double)tau); }
+// the tau of a Philox word: exact in float32, strictly inside (0, 1)
+__device__ __forceinline__ float iqn_tau_of(uint32_t w) { return (float)(2u * (w >> 9) + 1u) * (1.0f / 16777216.0f); }
+__device__ __forceinline__ float iqn_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t step_lo, uint32_t step_hi, int b, int i, bool target) {
+    const fb_u4 o = fb_philox(seed_lo, seed_hi, (uint32_t)(b * 64 + i), step_lo, FB_STREAM_TAU, step_hi);
+    return iqn_tau_of(target ? o.y : o.x);
+}
+
+// the fc1 activation of unit k of state `row` from the partial sums hf[ks][stot][FC]: ac_units4's sums and order, one unit
+__device__ __forceinline__ float iqn_unit(const float *__restrict__ hf, int stot, int nks, int FC, const float *__restrict__ P, int bf1, int row, int k) {
+    float v = hf[(size_t)row * FC + k];
+#pragma unroll
+    for (int ks = 1; ks < FC1_KS; ks++) {
+        const float t = hf[((size_t)(ks < nks ? ks : 0) * stot + row) * FC + k];
+        v += ks < nks ? t : 0.f;
+    }
+    return fmaxf(v + P[bf1 + k], 0.f);
+}
+
+// the plain head of state smp over the parameters P on every lane of the wave: head_one_t's loads, sums and order (as fb_sac.hip's sac_head),
+// so over a fold block these are the very bits fb_qnet_forward returns.  No load under a branch: columns a >= A read column 0.
+template <int AT>
+__device__ __forceinline__ void iqn_plain_head(const float *__restrict__ hf, int stot, int nks, int FC, int A, const float *__restrict__ P, const NetOff &off,
+                                               int smp, int lane, float (&out)[AT]) {
+    float acc[AT], bq[AT];
+#pragma unroll
+    for (int a = 0; a < AT; a++) { acc[a] = 0.f; bq[a] = P[off.bq + (a < A ? a : 0)]; }
+    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
+        float x4[4], w[4][AT];
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int a = 0; a < AT; a++) w[e][a] = P[off.wq + (j0 + e) * A + (a < A ? a : 0)];
+        ac_units4(hf, stot, nks, FC, P, off.bf1, smp, j0, x4);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int a = 0; a < AT; a++) acc[a] = fmaf(x4[e], w[e][a], acc[a]);
+    }
+#pragma unroll
+    for (int a = 0; a < AT; a++)
+        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o);
+#pragma unroll
+    for (int a = 0; a < AT; a++) out[a] = a < A ? acc[a] + bq[a] : 0.f;
+}
+
+// the cosine rows of the taus tq[0 .. M) into ct[M][64] (both LDS), by the whole workgroup; the caller synchronises
+__device__ __forceinline__ void iqn_cos_rows(const float *tq, int M, float *ct, int tid, int nthreads) {
+    for (int q = tid; q < M * IQN_E; q += nthreads) ct[q] = iqn_cos(q & 63, tq[q >> 6]);
+}
+
+// theta of state `row` at the M taus whose cosine rows are ct[M][64] (LDS), by a workgroup of 256: out[m * NC + c] (LDS) for the columns
+// c < NC -- NC = 1: the one column `col`; else the columns 0 .. NC - 1 (c >= A: column 0, never read).  Thread t owns the units t, t + 256,
+// ...: it holds W_e[:, k], forms pre (fmaf over ascending j from b_e[k]), g = h_k * relu(pre) and g * W_q[k, c]; a wave sums its 64 units
+// by the xor butterfly and its lane 0 adds the rounds up in order in part[wave][m][c]; out = b_q[c] + (((p_0 + p_1) + p_2) + p_3).
+// part: LDS, 4 * M * NC floats.  Ends behind a barrier: out is complete.  No load under a branch (a thread past FC reads unit 0, h = 0)
+template <int NC>
+__device__ __forceinline__ void iqn_theta(const float *__restrict__ hf, int stot, int nks, int FC, int A, const float *__restrict__ P, const NetOff &off,
+                                          const IqnOff &io, int row, int col, const float *ct, int M, float *part, float *out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int q = tid; q < 4 * M * NC; q += 256) part[q] = 0.f;
+    __syncthreads();
+    for (int k0 = 0; k0 < FC; k0 += 256) {
+        const bool ok = k0 + tid < FC;
+        const int k = ok ? k0 + tid : 0;
+        float w[IQN_E], wq[NC];
+#pragma unroll
+        for (int j = 0; j < IQN_E; j++) w[j] = P[io.we + j * FC + k];
+#pragma unroll
+        for (int c = 0; c < NC; c++) wq[c] = P[off.wq + k * A + (NC == 1 ? col : (c < A ? c : 0))];
+        const float be = P[io.be + k], hk = iqn_unit(hf, stot, nks, FC, P, off.bf1, row, k), h = ok ? hk : 0.f;
+        for (int m = 0; m < M; m++) {
+            float pre = be;
+#pragma unroll
+            for (int j = 0; j < IQN_E; j++) pre = fmaf(ct[m * IQN_E + j], w[j], pre);
+            const float g = h * fmaxf(pre, 0.f);
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                float v = g * wq[c];
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+                if (lane == 0) part[(wave * M + m) * NC + c] += v;
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < M * NC; q += 256) {
+        const int c = q % NC;
+        const float bq = P[off.bq + (NC == 1 ? col : (c < A ? c : 0))];
+        out[q] = bq + (((part[q] + part[M * NC + q]) + part[2 * M * NC + q]) + part[3 * M * NC + q]);
+    }
+    __syncthreads();
+}
+
+// ---- the fold of one net: 128 units per workgroup (FC % 128 == 0), a thread per unit
+__global__ __launch_bounds__(128) void iqn_fold_kernel(IqnFoldArgs F) {
+    __shared__ float ct[IQN_MAXT * IQN_E];
+    __shared__ float tq[IQN_MAXT];
+    const int tid = threadIdx.x, k = blockIdx.x * 128 + tid, K = F.K, FC = F.FC, A = F.A;
+    if (tid < K) tq[tid] = (float)((double)F.eta * (double)(2 * tid + 1) / (double)(2 * K));
+    __syncthreads();
+    iqn_cos_rows(tq, K, ct, tid, 128);
+    __syncthreads();
+    float w[IQN_E];
+#pragma unroll
+    for (int j = 0; j < IQN_E; j++) w[j] = F.P[F.io.we + j * FC + k];
+    const float be = F.P[F.io.be + k], bf = F.P[F.off.bf1 + k], bq = F.P[F.off.bq + (k < A ? k : 0)];
+    float sm = 0.f;
+    for (int i = 0; i < K; i++) {
+        float pre = be;
+#pragma unroll
+        for (int j = 0; j < IQN_E; j++) pre = fmaf(ct[i * IQN_E + j], w[j], pre);
+        sm += fmaxf(pre, 0.f);
+    }
+    const float pb = sm / (float)K;
+    F.fold[k] = bf;
+    for (int a = 0; a < A; a++) F.fold[FC + k * A + a] = pb * F.P[F.off.wq + k * A + a];
+    if (k < A) F.fold[FC + FC * A + k] = bq;
+}
+
+// ---- fb_qnet_forward_iqn: one workgroup per state
+template <int AT>
+__global__ __launch_bounds__(256) void iqn_head_kernel(IqnHeadArgs H) {
+    __shared__ float ct[IQN_MAXT * IQN_E];
+    __shared__ float part[4 * IQN_MAXT * AT];
+    __shared__ float out[IQN_MAXT * AT];
+    __shared__ float tq[IQN_MAXT];
+    const int tid = threadIdx.x, row = blockIdx.x, M = H.M, A = AT == MAXA ? H.A : AT;
+    const float t = H.tau[(size_t)row * M + (tid < M ? tid : 0)];
+    if (tid < M) tq[tid] = t;
+    __syncthreads();
+    iqn_cos_rows(tq, M, ct, tid, 256);
+    __syncthreads();
+    iqn_theta<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off, H.io, row, 0, ct, M, part, out);
+    for (int q = tid; q < M * AT; q += 256) {
+        const int m = q / AT, c = q - m * AT;
+        if (c < A) H.theta[((size_t)row * M + m) * A + c] = out[q];
+    }
+}
+
+// ---- training, launch 1 of 2: one workgroup per sample.  Rows b / B + b / 2 B + b of the fc1 partial sums: s and s' through the online
+// net, s' through the target net.  dl[b][4]: the action read, sum_i d theta_i, l_b, 0.
+template <int AT>
+__global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
+    __shared__ float ct[2 * IQN_MAXT * IQN_E];                    // the cosine rows of tau (N of them), then of tau' (N')
+    __shared__ float part[4 * IQN_MAXT];
+    __shared__ float tq[2 * IQN_MAXT];
+    __shared__ float th[IQN_MAXT], tg[IQN_MAXT], dth[IQN_MAXT], rowl[IQN_MAXT];
+    const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
+    const int A = AT == MAXA ? L.A : AT, FC = L.FC, B = L.B, N = L.N, Np = L.Np;
+    {   // tau_i at tid < N, tau'_j behind them: the caller's, or the draws of (seed, step).  No load under a branch: without the caller's array a valid word is read and dropped
+        const bool nx = tid >= N;
+        const int cnt = nx ? Np : N, i0 = nx ? tid - N : tid, i = i0 < cnt ? i0 : cnt - 1;
+        const float *src = nx ? L.tau_next : L.tau;
+        const float given = *(src ? src + (size_t)b * cnt + i : L.rew + b);
+        const float drawn = iqn_draw(L.seed_lo, L.seed_hi, L.step_lo, L.step_hi, b, i, nx);
+        if (tid < N + Np) tq[tid] = src ? given : drawn;
+    }
+    __syncthreads();
+    iqn_cos_rows(tq, N + Np, ct, tid, 256);
+    const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;   // (an action past the head reads the last one: stays in bounds)
+    const float rf = L.rew[b];
+    const bool done = L.term[b] != 0;
+    // a*: the first maximum of the plain head over the fold (every wave forms the same bits)
+    float qa[AT];
+    iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
+    int as = 0;
+    float qbest = qa[0];
+#pragma unroll
+    for (int c = 1; c < AT; c++) { const bool up = c < A && qa[c] > qbest; as = up ? c : as; qbest = up ? qa[c] : qbest; }
+    __syncthreads();
+    iqn_theta<1>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off, L.io, 2 * B + b, as, ct + N * IQN_E, Np, part, tg);
+    if (tid < Np) {
+        const double r = rf == 0.1f ? 0.1 : (double)rf;           // (the convention of every target here)
+        const float T = (float)(done ? r : r + L.gamma * (double)tg[tid]);
+        tg[tid] = T;
+        if (L.t_out) L.t_out[(size_t)b * Np + tid] = T;
+    }
+    iqn_theta<1>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off, L.io, b, ab, ct, N, part, th);      // (its first barrier orders tg's stores too)
+    if (tid < N) {                                                // the pairwise quantile Huber loss of row i, j ascending
+        const float kap = L.kappa, ti = tq[tid], thi = th[tid];
+        float l = 0.f, g = 0.f;
+        for (int j = 0; j < Np; j++) {
+            const float u = tg[j] - thi, au = fabsf(u), w = fabsf(ti - (u < 0.f ? 1.f : 0.f));
+            const float hub = au <= kap ? 0.5f * u * u : kap * (au - 0.5f * kap);
+            l += (w * hub) / kap;
+            g += (w * fminf(fmaxf(u, -kap), kap)) / kap;
+        }
+        rowl[tid] = l;
+        dth[tid] = (-(g / (float)Np)) / (float)B;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float l = 0.f, sd = 0.f;
+        for (int i = 0; i < N; i++) { l += rowl[i]; sd += dth[i]; }
+        *reinterpret_cast<float4 *>(L.dl + (size_t)b * 4) = make_float4((float)ab, sd, l / (float)Np, 0.f);
+    }
+    for (int q = tid; q < N * IQN_E; q += 256) L.ctab[(size_t)b * N * IQN_E + q] = ct[q];
+    // backward: phi recomputed per unit; s_k = sum_i d theta_i phi_ik
+    for (int k0 = 0; k0 < FC; k0 += 256) {
+        const bool ok = k0 + tid < FC;
+        const int k = ok ? k0 + tid : 0;
+        float w[IQN_E];
+#pragma unroll
+        for (int j = 0; j < IQN_E; j++) w[j] = L.P0[L.io.we + j * FC + k];
+        const float be = L.P0[L.io.be + k], wq = L.P0[L.off.wq + k * A + ab], h = iqn_unit(L.hf, L.stot, L.nks, FC, L.P0, L.off.bf1, b, k);
+        float s = 0.f;
+        for (int i = 0; i < N; i++) {
+            float pre = be;
+#pragma unroll
+            for (int j = 0; j < IQN_E; j++) pre = fmaf(ct[i * IQN_E + j], w[j], pre);
+            const float d = dth[i];
+            s = fmaf(d, fmaxf(pre, 0.f), s);
+            if (ok) L.dpre[((size_t)b * N + i) * FC + k] = pre > 0.f ? (d * h) * wq : 0.f;
+        }
+        if (ok) {
+            L.gw[(size_t)b * FC + k] = h * s;
+            L.dhf[(size_t)b * FC + k] = h > 0.f ? wq * s : 0.f;
+        }
+    }
+}
+
+// ---- training, launch 2 of 2: one workgroup per 16 fc1 units (sac_grad_kernel's grid): b_fc1's gradient and the tile's maximum |dhf|
+// (fc1_bwd_big_kernel's pre-scale); thread (unit jl, column c < 8) walks the samples in order for W_q's column c, which takes sample b's
+// row when a_b = c, else 0; then thread (unit jl, cosines 4 g .. 4 g + 3) walks the rows (b, i) in order for W_e, the threads of g = 0
+// for b_e as well.  Workgroup 0 also sums b_q and the loss the same way and ticks Adam.
+__global__ __launch_bounds__(256) void iqn_grad_kernel(IqnGradArgs L) {
+    __shared__ float dlt[IQN_MAXB * 4];
+    __shared__ float xt[IQN_MAXB * 16];
+    __shared__ float part[16][16];
+    __shared__ float wmax[4];
+    const int tid = threadIdx.x, B = L.B, FC = L.FC, A = L.A, j00 = blockIdx.x * 16;
+    for (int k = tid; k < B * 4; k += 256) dlt[k] = L.dl[k];
+    for (int k = tid; k < B * 16; k += 256) xt[k] = L.gw[(size_t)(k >> 4) * FC + j00 + (k & 15)];
+    const int jl = tid & 15, bg = tid >> 4;
+    float sm = 0.f, mx = 0.f;
+    for (int b = bg; b < B; b += 16) { const float d = L.dhf[(size_t)b * FC + j00 + jl]; sm += d; mx = fmaxf(mx, fabsf(d)); }
+    part[bg][jl] = sm;
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((tid & 63) == 0) wmax[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) L.gmax[blockIdx.x] = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    if (bg == 0) {
+        float v = part[0][jl];
+#pragma unroll
+        for (int q = 1; q < 16; q++) v += part[q][jl];
+        L.grad[L.off.bf1 + j00 + jl] = v;
+    }
+    const int c = bg;
+    const bool live = c < A;                                      // (A <= 8: the columns sit in bg < 8)
+    float acc = 0.f, gb = 0.f;
+    if (live) {
+        for (int b = 0; b < B; b++) {
+            const bool hit = (int)dlt[b * 4] == c;
+            acc += hit ? xt[b * 16 + jl] : 0.f;
+            gb += hit ? dlt[b * 4 + 1] : 0.f;
+        }
+        L.grad[L.off.wq + (size_t)(j00 + jl) * A + c] = acc;
+    }
+    {
+        const int R = B * L.N;
+        const float *dp = L.dpre + j00 + jl;
+        const float4 *cp = reinterpret_cast<const float4 *>(L.ctab) + bg;
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, be = 0.f;
+#pragma unroll 8
+        for (int r = 0; r < R; r++) {
+            const float d = dp[(size_t)r * FC];
+            const float4 cv = cp[(size_t)r * (IQN_E / 4)];
+            a0 = fmaf(cv.x, d, a0); a1 = fmaf(cv.y, d, a1); a2 = fmaf(cv.z, d, a2); a3 = fmaf(cv.w, d, a3);
+            be += d;
+        }
+        float *gwe = L.grad + L.io.we + (size_t)(bg * 4) * FC + j00 + jl;
+        gwe[0] = a0; gwe[FC] = a1; gwe[2 * (size_t)FC] = a2; gwe[3 * (size_t)FC] = a3;
+        if (bg == 0) L.grad[L.io.be + j00 + jl] = be;
+    }
+    if (blockIdx.x != 0) return;
+    if (jl == 0 && live) L.grad[L.off.bq + c] = gb;
+    if (tid == 0) {
+        float t = 0.f;
+        for (int b = 0; b < B; b++) t += dlt[b * 4 + 2];
+        L.loss[0] = t / (float)B;
+        FbAdamHead &ad = *L.adam;
+        if (L.tick && ad.ticks == ad.applies) {                  // (as ac_grad_kernel)
+            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
+            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
+            ad.ticks += 1;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void iqn_draw_kernel(long long total, int n, uint32_t seed_lo, uint32_t seed_hi, uint32_t step_lo, uint32_t step_hi,
+                                                       int which, float *out) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= total) return;
+    const int b = (int)(q / n), i = (int)(q - (long long)b * n);
+    out[q] = iqn_draw(seed_lo, seed_hi, step_lo, step_hi, b, i, which != 0);
+}
+
+template <class F> void with_actions(int A, F f) {
+    if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
+}
+}  // namespace
+
+void fb_iqn_launch_fold(hipStream_t st, const void *args) {
+    IqnFoldArgs F;
+    memcpy(&F, args, sizeof(F));
+    hipLaunchKernelGGL(iqn_fold_kernel, dim3(F.FC / 128), dim3(128), 0, st, F);
+}
+
+void fb_iqn_launch_head(hipStream_t st, const void *args) {
+    IqnHeadArgs H;
+    memcpy(&H, args, sizeof(H));
+    with_actions(H.A, [&](auto a) { hipLaunchKernelGGL(iqn_head_kernel<decltype(a)::value>, dim3(H.rows), dim3(256), 0, st, H); });
+}
+
+void fb_iqn_launch_loss(hipStream_t st, const void *args) {
+    IqnLossArgs L;
+    memcpy(&L, args, sizeof(L));
+    with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(iqn_loss_kernel<decltype(a)::value>, dim3(L.B), dim3(256), 0, st, L); });
+}
+
+void fb_iqn_launch_grad(hipStream_t st, const void *args) {
+    IqnGradArgs L;
+    memcpy(&L, args, sizeof(L));
+    hipLaunchKernelGGL(iqn_grad_kernel, dim3(L.FC / 16), dim3(256), 0, st, L);
+}
+
+extern "C" int fb_iqn_draw_taus(int batch, int n, uint64_t seed, uint64_t step, int which, float *tau_out, void *stream) {
+    FB_REQUIRE(tau_out, "fb_iqn_draw_taus: tau_out is NULL");
+    FB_REQUIRE(batch >= 1 && batch <= (1 << 20), "fb_iqn_draw_taus: batch %d outside 1..2^20", batch);
+    FB_REQUIRE(n >= 1 && n <= IQN_MAXT, "fb_iqn_draw_taus: n %d outside 1..%d", n, IQN_MAXT);
+    FB_REQUIRE(which == 0 || which == 1, "fb_iqn_draw_taus: which must be 0 (online) or 1 (target)");
+    const long long total = (long long)batch * n;
+    hipLaunchKernelGGL(iqn_draw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, fb_stream(stream), total, n, (uint32_t)seed, (uint32_t)(seed >> 32),
+                       (uint32_t)step, (uint32_t)(step >> 32), which, tau_out);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+// the checks of the two ring-fed IQN calls on the memory: a uniform one, at any n-step view, whose gamma the caller's is
+static int iqn_check_memory(fb_replay_t replay, double gamma, const char *who) {
+    FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: IQN trains from a uniform memory only (prioritized replay is not offered)", who);
+    return fb_replay_check_gamma(replay, gamma, who);
+}
+
+extern "C" int fb_iqn_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, uint8_t *a_out, float *r_out,
+                                        uint8_t *t_out, const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma, float *loss,
+                                        float *q_target, float *flat_grad, void *stream) {
+    const char *who = "fb_iqn_train_from_replay";
+    FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
+    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
+    int rc = iqn_check_memory(replay, gamma, who);
+    if (rc != FB_OK) return rc;
+    rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    FbRingSrc ring;
+    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_out, t_out, &ring);
+    if (rc != FB_OK) return rc;
+    if (batch >= 256) {                          // (W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
+        rc = fb_qnet_refresh_planes(net, stream);
+        if (rc != FB_OK) return rc;
+    }
+    return fb_qnet_iqn_train_ring(net, double_q, batch, &ring, tau, tau_next, seed, step, fb_replay_bootstrap_gamma(replay, gamma), loss, q_target,
+                                  flat_grad, stream);
+}
+
+extern "C" int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
+                           uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
+    const char *who = "fb_iqn_step";
+    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
+    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && b->idx, "%s: NULL buffer", who);
+    FB_REQUIRE(!train || (b->a && b->r && b->t && b->loss), "%s: a training step needs the a / r / t / loss buffers", who);
+    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
+    int rc = iqn_check_memory(replay, gamma, who);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "%s: n_envs %d does not match the env (%d) / replay (%d) handles", who,
+               n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
+    FB_REQUIRE(n_envs <= fb_qnet_max_rows(net), "%s: %d envs exceed 3*max_batch of the net", who, n_envs);
+    rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
+    rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
+    if (rc != FB_OK) return rc;
+    if (train) rc = fb_iqn_train_from_replay(replay, net, double_q, batch, b->idx, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss, nullptr,
+                                             b->flat_grad, stream);
+    return rc;
+}

@@ -4039,6 +4039,14 @@ struct fb_qnet {
     SacOff sac_off;
     float sac_hbar, sac_alr;
     float *sac_w;
+    // an IQN net (FB_ARCH_IQN, fb_qnet_create_iqn; kernels: fb_iqn.hip): the embedding W_e b_e behind the plain layout; N, N', K and the risk
+    // setting eta (kappa: the field above).  heff[w] = [b_fc1 | phibar * W_q | b_q], the fold of params[w] every forward-only path reads as a
+    // plain net's head (iqn_fold_kernel; refolded wherever a dueling C51 net's head is).  Training: the loss kernel's per-sample row in ac_dl
+    // ([.][4]), the W_q-gradient rows in ac_xs, the embedding's pre-activation gradients [Bt N][FC] and the cosine rows [Bt N][64]
+    IqnOff iqn_off;
+    int iqn_n, iqn_np, iqn_k;
+    float iqn_eta;
+    float *iqn_dpre, *iqn_ctab;
 };
 // every field ac_grad_kernel touches through FbAdamHead sits where AdamDev has it
 static_assert(offsetof(AdamDev, b1pow) == offsetof(FbAdamHead, b1pow) && offsetof(AdamDev, b2pow) == offsetof(FbAdamHead, b2pow) &&
@@ -4071,14 +4079,21 @@ static bool is_qr(const fb_qnet *h) { return h->arch == FB_ARCH_QR || h->arch ==
 static bool is_ac(const fb_qnet *h) { return h->arch == FB_ARCH_AC; }
 // a SAC net: the plain layout (W_pi b_pi at wq / bq: the logits, which the plain head reads as "Q"), then W_q1 b_q1 W_q2 b_q2
 static bool is_sac(const fb_qnet *h) { return h->arch == FB_ARCH_SAC; }
+// an IQN net: the plain layout (W_q b_q at wq / bq), then W_e b_e; forward-only paths read the plain head over its fold, heff[w]
+static bool is_iqn(const fb_qnet *h) { return h->arch == FB_ARCH_IQN; }
 // the parameters the C51 kernels read, with h->hoff, for the net whose parameters are `params` (a virtual base for a dueling C51 net:
 // hoff.bf1 lands on heff[w][0], as the acting forward's hp_act copy is read)
 static const float *head_base(const fb_qnet *h, const float *params) {
-    if (!is_c51d(h)) return params;
+    if (!is_c51d(h) && !is_iqn(h)) return params;
     return h->heff[params == h->params[1] ? 1 : 0] - h->off.bf1;
 }
 // refold a dueling C51 net's head after its parameters changed (no-op for other nets)
 static void c51d_fold(fb_qnet *h, int which, hipStream_t st) {
+    if (is_iqn(h)) {                             // (an IQN net: phibar over the acting grid and its fold block, fb_iqn.hip)
+        const IqnFoldArgs F{h->params[which], h->heff[which], h->FC, h->A, h->iqn_k, h->off, h->iqn_off, h->iqn_eta};
+        fb_iqn_launch_fold(st, &F);
+        return;
+    }
     if (!is_c51d(h)) return;
     const C51dFoldArgs F{h->params[which], h->heff[which], h->off, h->FC, h->A, h->sup.N};
     const int tot = h->FC + (h->FC + 1) * h->A * h->sup.N;
@@ -4105,6 +4120,7 @@ static void noisy_sgrad(fb_qnet *h, float *g, hipStream_t st) {
 }
 
 static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out, float sigma0 = -1.f);
+static thread_local int g_iqn_create[3];         // (N, N', K) of the IQN net fb_qnet_create_iqn is making: qnet_create sizes its workspaces by them
 
 extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
     FB_REQUIRE(out, "fb_qnet_create: out is NULL");
@@ -4113,6 +4129,7 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
     FB_REQUIRE(arch != FB_ARCH_QR && arch != FB_ARCH_QR_DUELING, "fb_qnet_create: a QR net is made by fb_qnet_create_qr (it needs N and kappa)");
     FB_REQUIRE(arch != FB_ARCH_AC, "fb_qnet_create: an actor-critic net is made by fb_qnet_create_ac");
     FB_REQUIRE(arch != FB_ARCH_SAC, "fb_qnet_create: a SAC net is made by fb_qnet_create_sac");
+    FB_REQUIRE(arch != FB_ARCH_IQN, "fb_qnet_create: an IQN net is made by fb_qnet_create_iqn (it needs N, N', K and kappa)");
     FB_REQUIRE(arch == FB_ARCH_PLAIN || arch == FB_ARCH_DUELING, "fb_qnet_create: arch must be 0 or 1");
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create: fc_width must be a multiple of 128");
     FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create: n_actions must be in 1..%d", MAXA);
@@ -4193,6 +4210,22 @@ extern "C" int fb_qnet_create_sac(int fc_width, int n_actions, int max_batch, fb
     return rc;
 }
 
+extern "C" int fb_qnet_create_iqn(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch, fb_qnet_t *out) {
+    const char *fn = "fb_qnet_create_iqn";
+    FB_REQUIRE(out, "%s: out is NULL", fn);
+    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
+    FB_REQUIRE(n_actions >= 2 && n_actions <= MAXA, "%s: n_actions must be in 2..%d", fn, MAXA);
+    FB_REQUIRE(n_tau >= 1 && n_tau <= 64, "%s: n_tau=%d outside 1..64", fn, n_tau);
+    FB_REQUIRE(n_tau_next >= 1 && n_tau_next <= 64, "%s: n_tau_next=%d outside 1..64", fn, n_tau_next);
+    FB_REQUIRE(n_tau_act >= 1 && n_tau_act <= 64, "%s: n_tau_act=%d outside 1..64", fn, n_tau_act);
+    FB_REQUIRE(isfinite(kappa) && kappa > 0.f, "%s: kappa must be finite and > 0 (got %g)", fn, (double)kappa);
+    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
+    g_iqn_create[0] = n_tau; g_iqn_create[1] = n_tau_next; g_iqn_create[2] = n_tau_act;
+    const int rc = qnet_create(FB_ARCH_IQN, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
+    if (rc == FB_OK) (*out)->kappa = kappa;
+    return rc;
+}
+
 // the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
 static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, float sigma0) {
     NoisyNet nn;
@@ -4222,6 +4255,11 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
         h->sac_off.wq1 = h->off.n; h->sac_off.bq1 = h->sac_off.wq1 + fc_width * n_actions;
         h->sac_off.wq2 = h->sac_off.bq1 + n_actions; h->sac_off.bq2 = h->sac_off.wq2 + fc_width * n_actions;
         h->off.n = h->sac_off.bq2 + n_actions;
+    }
+    if (is_iqn(h)) {                             // (the plain layout, then the embedding: off.n covers it)
+        h->iqn_off.we = h->off.n; h->iqn_off.be = h->iqn_off.we + FB_IQN_COS * fc_width;
+        h->off.n = h->iqn_off.be + fc_width;
+        h->iqn_n = g_iqn_create[0]; h->iqn_np = g_iqn_create[1]; h->iqn_k = g_iqn_create[2]; h->iqn_eta = 1.f;
     }
     h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
     h->n = h->off.n;
@@ -4263,7 +4301,7 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     alloc((void **)&h->gmax, (size_t)(fc_width / 16) * 4);
     alloc((void **)&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc((void **)&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
     if (sup.N) { alloc((void **)&h->c51_dl, Bm * 64 * 4); alloc((void **)&h->c51_xs, Bm * fc_width * 4); alloc((void **)&h->c51_lt, Bm * 4); }
-    if (is_c51d(h)) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
+    if (is_c51d(h) || is_iqn(h)) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
     if (is_ac(h)) {
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
         alloc((void **)&h->ac_dl, Bt * 16 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4); alloc((void **)&h->ac_r, Bt * 4); alloc((void **)&h->ac_t, Bt);
@@ -4271,6 +4309,11 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     if (is_sac(h)) {
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
         alloc((void **)&h->ac_dl, Bt * 16 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4); alloc((void **)&h->sac_w, 8 * 4);
+    }
+    if (is_iqn(h)) {                             // (sized by the train step's batch limit, not by max_batch: that is the env count)
+        const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
+        alloc((void **)&h->ac_dl, Bt * 4 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4);
+        alloc((void **)&h->iqn_dpre, Bt * h->iqn_n * fc_width * 4); alloc((void **)&h->iqn_ctab, Bt * h->iqn_n * FB_IQN_COS * 4);
     }
     alloc((void **)&h->clip_part, sizeof(double) * 256); alloc((void **)&h->clip_out, sizeof(float) * 2);
     if (e == hipSuccess) { const float one = 1.f; e = hipMemcpy(h->clip_out + 1, &one, sizeof(one), hipMemcpyHostToDevice); }      // (no clip yet: norm 0, c 1)
@@ -4293,7 +4336,8 @@ extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
                     h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
                     h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1],
-                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out, h->ac_dl, h->ac_xs, h->ac_r, h->ac_t, h->sac_w};
+                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out, h->ac_dl, h->ac_xs, h->ac_r, h->ac_t, h->sac_w,
+                    h->iqn_dpre, h->iqn_ctab};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
@@ -4390,6 +4434,7 @@ extern "C" int fb_qnet_set_inference_dtype(fb_qnet_t h, int dtype) {
     FB_REQUIRE(h && (dtype == FB_DTYPE_F32 || dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: dtype must be FB_DTYPE_F32 or FB_DTYPE_BF16");
     FB_REQUIRE(!(is_ac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: an actor-critic net computes in FB_DTYPE_F32 only");
     FB_REQUIRE(!(is_sac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: a SAC net computes in FB_DTYPE_F32 only");
+    FB_REQUIRE(!(is_iqn(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_inference_dtype: an IQN net computes in FB_DTYPE_F32 only");
     h->nsplit = dtype == FB_DTYPE_BF16 ? 1 : 3;
     return FB_OK;
 }
@@ -4398,6 +4443,7 @@ extern "C" int fb_qnet_set_train_dtype(fb_qnet_t h, int dtype) {
     FB_REQUIRE(h && (dtype == FB_DTYPE_F32 || dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: dtype must be FB_DTYPE_F32 or FB_DTYPE_BF16");
     FB_REQUIRE(!(is_ac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: an actor-critic net trains in FB_DTYPE_F32 only");
     FB_REQUIRE(!(is_sac(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: a SAC net trains in FB_DTYPE_F32 only");
+    FB_REQUIRE(!(is_iqn(h) && dtype == FB_DTYPE_BF16), "fb_qnet_set_train_dtype: an IQN net trains in FB_DTYPE_F32 only");
     h->nsplit_train = dtype == FB_DTYPE_BF16 ? 1 : 3;
     return FB_OK;
 }
@@ -4429,6 +4475,12 @@ extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *
         memcpy(&bits, &b, 4);
         FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->sac_off.bq1), (int)bits, (size_t)h->A, fb_stream(stream)));
         FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->sac_off.bq2), (int)bits, (size_t)h->A, fb_stream(stream)));
+    }
+    if (is_iqn(h)) {                             // (W_e drew as every weight does; b_e = 1: a fresh net has phi ~ 1 and starts as the plain net)
+        const float b = 1.0f;
+        uint32_t bits;
+        memcpy(&bits, &b, 4);
+        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->iqn_off.be), (int)bits, (size_t)h->FC, fb_stream(stream)));
     }
     if (h->noisy)                                // (mu as the plain net's, then sigma0 / sqrt(fan_in))
         hipLaunchKernelGGL(noisy_sigma_init_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, fb_stream(stream), h->mst[which], h->nnet);
@@ -4527,6 +4579,10 @@ struct Plan {
     // value, ac_logits / ac_logp as above, sac_q1 / sac_q2 f32[rows][A] or NULL.  Train plans: three slices as FB_ALGO_DOUBLE's, p.r / p.t /
     // p.gamma / p.y as a scalar step's; sac_temp: the temperature update runs (the CALLER exports nothing and alpha_lr > 0)
     bool policy_head; float *sac_q1, *sac_q2; bool sac_temp;
+    // an IQN net.  Forward plans with iqn_theta set: theta f32[rows][iqn_m][A] at iqn_tau instead of the plain head over the fold.  Train
+    // plans: three slices as FB_ALGO_DOUBLE's; iqn_tau / iqn_tau_next (or NULL: the draws of p.seed / p.step), iqn_double: a* from the online net;
+    // p.y: T f32[B][N'] or NULL
+    const float *iqn_tau, *iqn_tau_next; int iqn_m; float *iqn_theta; bool iqn_double;
 };
 
 // A runtime value as a template argument: f is a generic lambda and gets a tag whose ::value is a constant expression, so that a kernel
@@ -4546,7 +4602,7 @@ template <class T> static void put_seed_words(T &c, uint64_t seed, uint64_t step
 struct PlanCtx {
     int only; hipStream_t st;                // `only` < 0: the whole plan; else the launches of that KernelId alone
     int maxc, total;                         // states of the largest slice / of all slices
-    bool big, trunk, fused, c51, ac, sac;      // ac: the loss is fb_ac.hip's or fb_sac.hip's two launches (an actor-critic or a SAC net)
+    bool big, trunk, fused, c51, ac, sac, iqn; // ac: the loss is fb_ac.hip's, fb_sac.hip's or fb_iqn.hip's two launches (an actor-critic, SAC or IQN net)
     bool state_trunk;                        // gathered states through conv1_pool + conv23_t with planes, then large_pass's fc1 alone (plan_ctx)
     int nsp, stot; size_t pl1, pl2;          // stot: rows of the workspace; pl1 / pl2: its plane pitch after conv1 / conv2, conv3
 };
@@ -4569,7 +4625,8 @@ static PlanCtx plan_ctx(const fb_qnet *h, const Plan &p, int only, hipStream_t s
     c.fused = c.big && p.nib && !p.train && !c.trunk && p.ns == 1;
     c.c51 = h->sup.N > 0;
     c.sac = is_sac(h);
-    c.ac = is_ac(h) || c.sac;
+    c.iqn = is_iqn(h);
+    c.ac = is_ac(h) || c.sac || c.iqn;
     // an actor-critic train step on 256 GATHERED states: the per-state conv trunk of the smaller batches, writing conv3's planes, then
     // fc1_sp -- the arithmetic of the ring-fed form (ring_trunk), so that the two forms of an A2C chunk agree bit for bit at every size
     // (the large-batch trunk sums conv2 / conv3 in another order).  The ring-fed form is the one the A2C loop runs
@@ -4729,7 +4786,16 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         fb_sac_launch_head(c.st, &H);
         return;
     }
-    if (c.ac && !c.sac && !p.train && p.ac_value && runs(c, K_HEAD)) {  // an actor-critic net's policy head (fb_ac.hip), a launch of its own
+    if (c.iqn && !p.train && p.iqn_theta && runs(c, K_HEAD)) {         // an IQN net's theta at the caller's tau (fb_iqn.hip), a launch of its own
+        IqnHeadArgs H;
+        memset(&H, 0, sizeof(H));
+        H.hf = c.fused ? h->hf_act : h->hf; H.P = p.sl.s[0].params;
+        H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A; H.rows = c.total; H.M = p.iqn_m; H.off = h->off; H.io = h->iqn_off;
+        H.tau = p.iqn_tau; H.theta = p.iqn_theta;
+        fb_iqn_launch_head(c.st, &H);
+        return;
+    }
+    if (c.ac && !c.sac && !c.iqn && !p.train && p.ac_value && runs(c, K_HEAD)) {  // an actor-critic net's policy head (fb_ac.hip), a launch of its own
         AcHeadArgs H;
         memset(&H, 0, sizeof(H));
         H.hf = c.fused ? h->hf_act : h->hf; H.P = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;      // (fused: the copy its fc1 launch took)
@@ -4743,12 +4809,13 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     if (!c.c51 && !(p.train && (c.ac || !c.big)) && runs(c, K_HEAD)) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
         HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns;
+        for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (an IQN net: its fold; every scalar net: its parameters)
         HeadCore &C = H.c;
         C.hf = c.fused ? h->hf_act : h->hf; C.stot = c.stot; C.nks = c.big ? FC1_SP_KS : 1; C.q = h->q; C.FC = h->FC; C.A = h->A;
         C.dueling = h->arch == FB_ARCH_DUELING; C.off = h->off; C.actions = p.actions; C.epsilon = p.epsilon;
         put_seed_words(C, p.seed, p.step);
         // (the rider of a fused acting forward reads the head's parameters from the copy that forward's fc1 launch took: b_fc1 on)
-        if (p.head_rider) { p.head_rider->c = C; p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params; p.head_rider->on = 1; p.head_rider->on_arrival = nullptr; p.head_rider->arrival_val = 0; }   // rides in the env launch
+        if (p.head_rider) { p.head_rider->c = C; p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params; p.head_rider->on = 1; p.head_rider->on_arrival = nullptr; p.head_rider->arrival_val = 0; }   // rides in the env launch
         else hipLaunchKernelGGL(head_kernel, dim3((c.total + 3) / 4), dim3(256), 0, c.st, H);
     }
 }
@@ -4757,6 +4824,21 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
 // the per-unit reductions; QR: per-sample targets / quantile Huber loss / dhf, then C51's per-unit reductions
 static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     const int B = p.B, FC = h->FC;
+    if (c.iqn) {                                 // IQN: per-sample a* / T / theta / loss / d theta / dhf, then the per-unit reductions (fb_iqn.hip)
+        IqnLossArgs L;
+        memset(&L, 0, sizeof(L));
+        L.hf = h->hf; L.P0 = h->params[0]; L.P1 = h->params[1]; L.F = head_base(h, h->params[p.iqn_double ? 0 : 1]); L.arow0 = p.iqn_double ? B : 2 * B;
+        L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B; L.N = h->iqn_n; L.Np = h->iqn_np;
+        L.off = h->off; L.io = h->iqn_off; L.kappa = h->kappa; L.act = p.a; L.term = p.t; L.rew = p.r; L.gamma = p.gamma;
+        L.tau = p.iqn_tau; L.tau_next = p.iqn_tau_next;
+        put_seed_words(L, p.seed, p.step);
+        L.dl = h->ac_dl; L.gw = h->ac_xs; L.dhf = h->dhf; L.dpre = h->iqn_dpre; L.ctab = h->iqn_ctab; L.t_out = p.y;
+        fb_iqn_launch_loss(c.st, &L);
+        const IqnGradArgs gA{B, FC, h->A, h->iqn_n, h->off, h->iqn_off, h->ac_dl, h->ac_xs, h->dhf, h->iqn_dpre, h->iqn_ctab, p.G, p.loss, h->gmax,
+                             reinterpret_cast<FbAdamHead *>(h->adam), p.tick};
+        fb_iqn_launch_grad(c.st, &gA);
+        return;
+    }
     if (c.sac) {                                 // SAC: per-sample target / losses / dz / dQ / dhf, then the per-unit reductions (fb_sac.hip)
         SacLossArgs L;
         memset(&L, 0, sizeof(L));
@@ -5026,6 +5108,7 @@ int fb_qnet_is_qr(fb_qnet_t h) { return h && is_qr(h); }
 int fb_qnet_is_dist(fb_qnet_t h) { return h && h->sup.N > 0; }
 int fb_qnet_is_ac(fb_qnet_t h) { return h && is_ac(h); }
 int fb_qnet_is_sac(fb_qnet_t h) { return h && is_sac(h); }
+int fb_qnet_is_iqn(fb_qnet_t h) { return h && is_iqn(h); }
 extern "C" int fb_qnet_is_noisy(fb_qnet_t h) { return h && h->noisy ? 1 : 0; }
 
 extern "C" int fb_qnet_reset_noise(fb_qnet_t h, int which, uint64_t seed, uint64_t step, int mode, void *stream) {
@@ -5131,6 +5214,7 @@ extern "C" int fb_qnet_set_munchausen(fb_qnet_t h, float tau, float alpha, float
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
     FB_REQUIRE(!is_ac(h), "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar Q heads only, not an actor-critic net");
     FB_REQUIRE(!is_sac(h), "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar Q heads only, not a SAC net");
+    FB_REQUIRE(!is_iqn(h), "fb_qnet_set_munchausen: Munchausen-DQN trains the scalar Q heads only, not an IQN net (its loss has its own kappa)");
     FB_REQUIRE(isfinite(tau) && tau > 0.f, "fb_qnet_set_munchausen: tau must be finite and > 0 (got %g)", (double)tau);
     FB_REQUIRE(alpha >= 0.f && alpha <= 1.f, "fb_qnet_set_munchausen: alpha must be in [0, 1] (got %g)", (double)alpha);
     FB_REQUIRE(isfinite(clip_lo) && clip_lo <= 0.f, "fb_qnet_set_munchausen: the clip l0 must be finite and <= 0 (got %g)", (double)clip_lo);
@@ -5143,6 +5227,7 @@ extern "C" int fb_qnet_get_munchausen(fb_qnet_t h, float *tau_host, float *alpha
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar heads only, not a C51 / QR net");
     FB_REQUIRE(!is_ac(h), "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar Q heads only, not an actor-critic net");
     FB_REQUIRE(!is_sac(h), "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar Q heads only, not a SAC net");
+    FB_REQUIRE(!is_iqn(h), "fb_qnet_get_munchausen: Munchausen-DQN trains the scalar Q heads only, not an IQN net (its loss has its own kappa)");
     if (tau_host) *tau_host = h->md.tau;
     if (alpha_host) *alpha_host = h->md.alpha;
     if (clip_lo_host) *clip_lo_host = h->md.clip;
@@ -5154,6 +5239,7 @@ extern "C" int fb_qnet_set_huber(fb_qnet_t h, float delta) {
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_set_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
     FB_REQUIRE(!is_ac(h), "fb_qnet_set_huber: the Huber loss is a setting of the scalar Q heads only, not of an actor-critic net");
     FB_REQUIRE(!is_sac(h), "fb_qnet_set_huber: the Huber loss is a setting of the scalar Q heads only, not of a SAC net");
+    FB_REQUIRE(!is_iqn(h), "fb_qnet_set_huber: the Huber loss is a setting of the scalar Q heads only, not of an IQN net (its loss has its own kappa)");
     FB_REQUIRE(isfinite(delta) && delta >= 0.f, "fb_qnet_set_huber: delta must be finite and >= 0 (0 = the squared loss; got %g)", (double)delta);
     h->huber = delta;
     return FB_OK;
@@ -5164,6 +5250,7 @@ extern "C" int fb_qnet_get_huber(fb_qnet_t h, float *delta_host) {
     FB_REQUIRE(h->sup.N == 0, "fb_qnet_get_huber: the Huber loss is a setting of the scalar heads only, not of a C51 / QR / noisy net (QR has its own kappa)");
     FB_REQUIRE(!is_ac(h), "fb_qnet_get_huber: the Huber loss is a setting of the scalar Q heads only, not of an actor-critic net");
     FB_REQUIRE(!is_sac(h), "fb_qnet_get_huber: the Huber loss is a setting of the scalar Q heads only, not of a SAC net");
+    FB_REQUIRE(!is_iqn(h), "fb_qnet_get_huber: the Huber loss is a setting of the scalar Q heads only, not of an IQN net (its loss has its own kappa)");
     *delta_host = h->huber;
     return FB_OK;
 }
@@ -5374,6 +5461,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     FB_REQUIRE((algo >= 0 && algo <= FB_ALGO_QR_DOUBLE_PER) || is_mdqn_algo(algo) || algo == FB_ALGO_DOUBLE_PER, "fb_qnet_train_step: unknown algo %d", algo);
     FB_REQUIRE(!is_ac(h), "fb_qnet_train_step: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only (got algo %d)", algo);
     FB_REQUIRE(!is_sac(h), "fb_qnet_train_step: a SAC net trains through fb_qnet_sac_train_step / fb_sac_train_from_replay only (got algo %d)", algo);
+    FB_REQUIRE(!is_iqn(h), "fb_qnet_train_step: an IQN net trains through fb_qnet_iqn_train_step / fb_iqn_train_from_replay only (got algo %d)", algo);
     {
         const bool c51a = is_c51_algo(algo), qra = is_qr_algo(algo);
         FB_REQUIRE(c51a == (h->sup.N > 0 && !is_qr(h)), c51a ? "fb_qnet_train_step: algo %d (C51) needs a C51 net (fb_qnet_create_c51)"
@@ -5699,6 +5787,91 @@ int fb_qnet_sac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, double gam
     const int rc = fb_qnet_sac_check_train(h, B, gamma, "fb_sac_train_from_replay");
     if (rc != FB_OK) return rc;
     Plan p = sac_train_plan(h, B, nullptr, ring->a, ring->r, nullptr, ring->t, gamma, loss, q_target, flat_grad, ring);
+    return run_train(h, p, stream);
+}
+
+// ---- implicit quantile networks (include/fbdqn.h; kernels: fb_iqn.hip)
+extern "C" int fb_qnet_set_iqn_risk(fb_qnet_t h, float eta) {
+    FB_REQUIRE(h, "fb_qnet_set_iqn_risk: NULL handle");
+    FB_REQUIRE(is_iqn(h), "fb_qnet_set_iqn_risk: not an IQN net (fb_qnet_create_iqn)");
+    FB_REQUIRE(isfinite(eta) && eta > 0.f && eta <= 1.f, "fb_qnet_set_iqn_risk: eta must be in (0, 1] (got %g)", (double)eta);
+    FB_CHECK_HIP(hipDeviceSynchronize());        // (whatever still reads the folds of the old eta)
+    h->iqn_eta = eta;
+    c51d_fold(h, 0, nullptr); c51d_fold(h, 1, nullptr);
+    FB_LAUNCH_CHECK();
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_iqn(fb_qnet_t h, int *n_tau_host, int *n_tau_next_host, int *n_tau_act_host, float *kappa_host, float *eta_host) {
+    FB_REQUIRE(h, "fb_qnet_get_iqn: NULL handle");
+    FB_REQUIRE(is_iqn(h), "fb_qnet_get_iqn: not an IQN net (fb_qnet_create_iqn)");
+    if (n_tau_host) *n_tau_host = h->iqn_n;
+    if (n_tau_next_host) *n_tau_next_host = h->iqn_np;
+    if (n_tau_act_host) *n_tau_act_host = h->iqn_k;
+    if (kappa_host) *kappa_host = h->kappa;
+    if (eta_host) *eta_host = h->iqn_eta;
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_forward_iqn(fb_qnet_t h, int which, const uint8_t *states, int batch, const float *tau, int M, float *theta, void *stream) {
+    FB_REQUIRE(h && states && tau && theta && (which == 0 || which == 1), "fb_qnet_forward_iqn: bad argument");
+    FB_REQUIRE(is_iqn(h), "fb_qnet_forward_iqn: not an IQN net (fb_qnet_create_iqn)");
+    FB_REQUIRE(M >= 1 && M <= 64, "fb_qnet_forward_iqn: M %d outside 1..64", M);
+    FB_REQUIRE(rows_ok(h, batch), "fb_qnet_forward_iqn: batch %d exceeds 3*max_batch", batch);
+    Plan p = forward_plan(h, which, states, batch);
+    p.iqn_tau = tau; p.iqn_m = M; p.iqn_theta = theta;
+    return run_plan(h, p, -1, fb_stream(stream));
+}
+
+int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int B, double gamma, const char *who) {
+    FB_REQUIRE(h && is_iqn(h), "%s: not an IQN net (fb_qnet_create_iqn)", who);
+    FB_REQUIRE(double_q == 0 || double_q == 1, "%s: double_q must be 0 or 1 (got %d)", who, double_q);
+    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "%s: batch %d exceeds min(max_batch, %d)", who, B, MAXTB);
+    FB_REQUIRE(isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
+    return FB_OK;
+}
+
+// the train plan of an IQN net: FB_ALGO_DOUBLE's three slices -- s and s' through the online net, s' through the target net
+static Plan iqn_train_plan(fb_qnet *h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
+                           const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma, float *loss, float *q_target,
+                           float *flat_grad, const FbRingSrc *ring) {
+    Plan p; memset(&p, 0, sizeof(p));
+    p.ns = 3;
+    p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
+    p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};
+    p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1};
+    p.train = true; p.algo = -1; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.gamma = gamma;
+    p.loss = loss; p.y = q_target;
+    p.G = flat_grad ? flat_grad : h->grad;
+    p.apply_adam = flat_grad == nullptr; p.tick = true;
+    p.iqn_tau = tau; p.iqn_tau_next = tau_next; p.iqn_double = double_q != 0; p.seed = seed; p.step = step;
+    p.ring = ring;
+    if (ring && ring->c.nstep > 1)                   // n-step view: s' = frames tt + n - 3 .. tt + n (train_plan's rule)
+        for (int z = 1; z < p.ns; z++) p.sl.s[z].fshift = ring->c.nstep;
+    return p;
+}
+
+extern "C" int fb_qnet_iqn_train_step(fb_qnet_t h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
+                                      const uint8_t *t, const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma,
+                                      float *loss, float *q_target, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && s && a && r && s2 && t && loss, "fb_qnet_iqn_train_step: NULL argument");
+    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_qnet_iqn_train_step");
+    if (rc != FB_OK) return rc;
+    Plan p = iqn_train_plan(h, double_q, B, s, a, r, s2, t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, nullptr);
+    if (B >= 256) {                              // (fc1_sp_kernel reads W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
+        const int rp = fb_qnet_refresh_planes(h, stream);
+        if (rp != FB_OK) return rp;
+    }
+    return run_train(h, p, stream);
+}
+
+int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int B, const FbRingSrc *ring, const float *tau, const float *tau_next, uint64_t seed, uint64_t step,
+                           double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss, "fb_iqn_train_from_replay: NULL argument");
+    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_iqn_train_from_replay");
+    if (rc != FB_OK) return rc;
+    Plan p = iqn_train_plan(h, double_q, B, nullptr, ring->a, ring->r, nullptr, ring->t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, ring);
     return run_train(h, p, stream);
 }
 

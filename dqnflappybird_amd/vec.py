@@ -304,6 +304,8 @@ AC_MAX_ROLLOUT = 128                                      # the longest rollout 
 PPO_DEFAULTS = L.PPO_DEFAULTS                             # (clip_eps, value_clip) of a new actor-critic net
 SAC_ARCH = "sac"                                          # discrete soft actor-critic: a policy head and two Q heads (include/fbdqn.h)
 SAC_DEFAULTS = L.SAC_DEFAULTS                             # (alpha, target_entropy / ln A, alpha_lr) of a new SAC net
+IQN_ARCH = "iqn"                                          # implicit quantile network: the plain layout and a cosine embedding (include/fbdqn.h)
+IQN_DEFAULTS = L.IQN_DEFAULTS                             # (n_tau, n_tau_next, n_tau_act, kappa) of a new IQN net
 
 
 def check_sigma0(sigma0):
@@ -398,6 +400,25 @@ def check_sac(alpha, target_entropy, alpha_lr, actions=2):
     return a, h, lr
 
 
+def check_iqn(n_tau, n_tau_next, n_tau_act, kappa, eta=1.0, actions=2):
+    """the argument checks of fb_qnet_create_iqn and fb_qnet_set_iqn_risk, on the host
+    (-> (n_tau, n_tau_next, n_tau_act, kappa, eta), the floats float32-rounded)"""
+    if not 2 <= int(actions) <= 8:
+        raise ValueError(f"actions must be in 2..8 for an IQN net, got {actions}")
+    ns = []
+    for name, v in (("n_tau", n_tau), ("n_tau_next", n_tau_next), ("n_tau_act", n_tau_act)):
+        if int(v) != v or not 1 <= int(v) <= 64:
+            raise ValueError(f"{name} must be an integer in 1..64, got {v}")
+        ns.append(int(v))
+    with np.errstate(over="ignore"):
+        k, e = float(np.float32(kappa)), float(np.float32(eta))
+    if not (np.isfinite(k) and k > 0.0):
+        raise ValueError(f"kappa must be finite and > 0, got {kappa}")
+    if not (np.isfinite(e) and 0.0 < e <= 1.0):
+        raise ValueError(f"the risk setting eta (CVaR level) must be in (0, 1], got {eta}")
+    return ns[0], ns[1], ns[2], k, e
+
+
 def check_gae(gamma, gae_lambda):
     """the argument checks of fb_ac_gae, on the host (-> (gamma, lambda) as floats)"""
     g, l = float(gamma), float(gae_lambda)
@@ -460,11 +481,12 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
-    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH, SAC_ARCH)
+    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH, SAC_ARCH, IQN_ARCH)
 
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
                  v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0,
-                 n_quantiles=QR_DEFAULT_QUANTILES[0], kappa=QR_DEFAULT_QUANTILES[1]):
+                 n_quantiles=QR_DEFAULT_QUANTILES[0], kappa=QR_DEFAULT_QUANTILES[1], n_tau=IQN_DEFAULTS[0], n_tau_next=IQN_DEFAULTS[1],
+                 n_tau_act=IQN_DEFAULTS[2]):
         """arch='c51': the distributional head of include/fbdqn.h (n_atoms atoms on [v_min, v_max]; the support args are ignored otherwise);
         arch='c51dueling': the dueling C51 head (value and advantage distributions, include/fbdqn.h) on the same support.
         arch='qr' / 'qrdueling': the quantile head of QR-DQN (n_quantiles quantiles, quantile Huber loss with threshold kappa; include/fbdqn.h)
@@ -474,7 +496,10 @@ class QNet:
         arch='ac': an advantage actor-critic net -- the dueling net's parameters read raw, V = h . W_v + b_v and the policy's logits
         h . W_pi + b_pi (include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values
         arch='sac': a discrete soft actor-critic net -- the policy's logits h . W_pi + b_pi and two Q heads (2 <= actions <= 8;
-        include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values"""
+        include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values
+        arch='iqn': an implicit quantile network -- theta(s, a; tau) through a cosine embedding of tau; trains on n_tau / n_tau_next sampled
+        tau with the quantile Huber loss (kappa), acts on the mean over a grid of n_tau_act tau (scaled by set_iqn_risk's eta), which
+        forward / act / act_nib / evaluation return as the Q values (2 <= actions <= 8; include/fbdqn.h)"""
         if arch not in self.ARCHS:
             raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
         self.noisy = bool(noisy)
@@ -488,6 +513,8 @@ class QNet:
             n_atoms, v_min, v_max = check_support(n_atoms, v_min, v_max, actions)
         if arch in QR_ARCHS:
             n_quantiles, kappa = check_quantiles(n_quantiles, kappa, actions)
+        if arch == IQN_ARCH:
+            n_tau, n_tau_next, n_tau_act, kappa, _ = check_iqn(n_tau, n_tau_next, n_tau_act, kappa, 1.0, actions)
         L.require_gpu()
         self.A, self.FC, self.max_batch = int(actions), int(fc_width), int(max_batch)
         self.dueling = arch == "dueling"
@@ -502,6 +529,9 @@ class QNet:
         elif arch == "c51dueling":
             L.check(L.lib().fb_qnet_create_c51_dueling(self.FC, self.A, n_atoms, v_min, v_max, self.max_batch, C.byref(self.h)),
                     "fb_qnet_create_c51_dueling")
+        elif arch == IQN_ARCH:
+            L.check(L.lib().fb_qnet_create_iqn(self.FC, self.A, n_tau, n_tau_next, n_tau_act, kappa, self.max_batch, C.byref(self.h)),
+                    "fb_qnet_create_iqn")
         elif arch == SAC_ARCH:
             L.check(L.lib().fb_qnet_create_sac(self.FC, self.A, self.max_batch, C.byref(self.h)), "fb_qnet_create_sac")
         elif arch == AC_ARCH:
@@ -817,6 +847,59 @@ class QNet:
                                                L.ptr(flat_grad), L.current_stream()), "fb_qnet_sac_train_step")
         return loss, y
 
+    # -- implicit quantile networks (arch='iqn') -----------------------------------------
+    def _need_iqn(self, what):
+        if self.arch != IQN_ARCH:
+            raise ValueError(f"{what} needs an IQN net (QNet(..., arch='iqn'))")
+
+    def set_iqn_risk(self, eta=1.0):
+        """act under CVaR_eta: the acting grid becomes eta (2 i + 1) / (2 K); 1 = risk neutral (fb_qnet_set_iqn_risk); synchronous"""
+        self._need_iqn("set_iqn_risk")
+        e = check_iqn(1, 1, 1, 1.0, eta, self.A)[4]
+        L.check(L.lib().fb_qnet_set_iqn_risk(self.h, e), "fb_qnet_set_iqn_risk")
+
+    def iqn(self):
+        """the net's (n_tau, n_tau_next, n_tau_act, kappa, eta) (fb_qnet_get_iqn)"""
+        self._need_iqn("iqn")
+        n, m, k, ka, e = C.c_int(), C.c_int(), C.c_int(), C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_get_iqn(self.h, C.byref(n), C.byref(m), C.byref(k), C.byref(ka), C.byref(e)), "fb_qnet_get_iqn")
+        return n.value, m.value, k.value, ka.value, e.value
+
+    def forward_iqn(self, states, tau, which=L.NET_ONLINE):
+        """u8 states [B,80,80,4], tau f32[B, M] (1 <= M <= 64) -> theta f32[B, M, A] of the online or the target net (fb_qnet_forward_iqn)"""
+        self._need_iqn("forward_iqn")
+        _dev_check(states, tau)
+        if states.dtype != torch.uint8 or states.dim() != 4 or tuple(states.shape[1:]) != (80, 80, 4):
+            raise ValueError("states must be uint8[B,80,80,4]")
+        B = states.shape[0]
+        if tau.dtype != torch.float32 or tau.dim() != 2 or tau.shape[0] != B or not 1 <= tau.shape[1] <= 64 or not tau.is_contiguous():
+            raise ValueError("tau must be a contiguous float32[B, M] with 1 <= M <= 64")
+        M = tau.shape[1]
+        theta = torch.empty((B, M, self.A), dtype=torch.float32, device=self.device)
+        L.check(L.lib().fb_qnet_forward_iqn(self.h, int(which), L.ptr(states), B, L.ptr(tau), M, L.ptr(theta), L.current_stream()),
+                "fb_qnet_forward_iqn")
+        return theta
+
+    def iqn_train_step(self, s, a, r, s2, t, gamma=0.99, double_q=False, tau=None, tau_next=None, seed=0, step=0, flat_grad=None,
+                       want_target=True):
+        """one IQN step on <= 256 gathered transitions (fb_qnet_iqn_train_step).  tau f32[B, n_tau] / tau_next f32[B, n_tau_next], or None:
+        the draws of (seed, step) (iqn_draw_taus).  flat_grad=None applies Adam; a float32[n_params] tensor receives the gradient instead.
+        -> (loss f32[1], q_target f32[B, n_tau_next] or None)"""
+        self._need_iqn("iqn_train_step")
+        _dev_check(s, a, r, s2, t, flat_grad, tau, tau_next)
+        for name, x in (("s", s), ("s2", s2)):
+            if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (80, 80, 4) or x.shape[0] != s.shape[0]:
+                raise ValueError(f"{name} must be uint8[B,80,80,4]")
+        B = s.shape[0]
+        N, Np = self.iqn()[:2]
+        check_iqn_batch(B, a, r, t, tau, tau_next, N, Np, flat_grad, self.n_params)
+        loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        y = torch.empty((B, Np), dtype=torch.float32, device=self.device) if want_target else None
+        L.check(L.lib().fb_qnet_iqn_train_step(self.h, int(bool(double_q)), B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), L.ptr(tau),
+                                               L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(y), L.ptr(flat_grad),
+                                               L.current_stream()), "fb_qnet_iqn_train_step")
+        return loss, y
+
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):
         if not self.noisy:
@@ -1026,6 +1109,55 @@ def check_sac_batch(B, a, r, t, flat_grad, n_params):
         raise ValueError(f"flat_grad must be float32[{n_params}]")
 
 
+def check_iqn_batch(B, a, r, t, tau, tau_next, n_tau, n_tau_next, flat_grad, n_params):
+    """the shape checks of the two IQN training calls, on the host"""
+    if not 1 <= B <= 256:
+        raise ValueError(f"an IQN batch holds 1..256 samples, got {B}")
+    for name, x, dt in (("a", a, torch.uint8), ("r", r, torch.float32), ("t", t, torch.uint8)):
+        if x is not None and (x.dtype != dt or x.numel() != B):
+            raise ValueError(f"{name} must be {dt}[{B}]")
+    for name, x, n in (("tau", tau, n_tau), ("tau_next", tau_next, n_tau_next)):
+        if x is not None and (x.dtype != torch.float32 or tuple(x.shape) != (B, n) or not x.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous float32[{B}, {n}]")
+    if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
+        raise ValueError(f"flat_grad must be float32[{n_params}]")
+
+
+def iqn_draw_taus(batch, n, seed=0, step=0, which=0, device="cuda"):
+    """the tau the IQN train step draws for (seed, step) when it is given none (fb_iqn_draw_taus; stateless): float32[batch, n], strictly
+    inside (0, 1); which 0: the online tau, 1: the target's tau'"""
+    if not 1 <= int(batch) <= (1 << 20) or not 1 <= int(n) <= 64 or which not in (0, 1):
+        raise ValueError(f"iqn_draw_taus: batch in 1..2^20, n in 1..64, which 0 or 1 (got {batch}, {n}, {which})")
+    L.require_gpu()
+    out = torch.empty((int(batch), int(n)), dtype=torch.float32, device=device)
+    L.check(L.lib().fb_iqn_draw_taus(int(batch), int(n), int(seed), int(step), int(which), L.ptr(out), L.current_stream()), "fb_iqn_draw_taus")
+    return out
+
+
+def iqn_train_from_replay(replay, net, idx, gamma=0.99, double_q=False, tau=None, tau_next=None, seed=0, step=0, flat_grad=None,
+                          want_target=False):
+    """QNet.iqn_train_step on the transitions at the deque positions idx of a uniform memory (any n-step view; gamma must be the memory's),
+    read from its frame ring in place (fb_iqn_train_from_replay)
+    -> (loss f32[1], a u8[B], r f32[B], t u8[B][, q_target f32[B, n_tau_next]])"""
+    if net.arch != IQN_ARCH:
+        raise ValueError("iqn_train_from_replay needs an IQN net (QNet(..., arch='iqn'))")
+    if replay.prioritized:
+        raise ValueError("iqn_train_from_replay trains from a uniform memory only")
+    _dev_check(idx, flat_grad, tau, tau_next)
+    if idx.dtype != torch.int64:
+        raise ValueError("idx must be int64[B]")
+    B, dev = int(idx.numel()), idx.device
+    N, Np = net.iqn()[:2]
+    check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
+    a = torch.empty(B, dtype=torch.uint8, device=dev); r = torch.empty(B, dtype=torch.float32, device=dev)
+    t = torch.empty(B, dtype=torch.uint8, device=dev); loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    y = torch.empty((B, Np), dtype=torch.float32, device=dev) if want_target else None
+    L.check(L.lib().fb_iqn_train_from_replay(replay.h, net.h, int(bool(double_q)), B, L.ptr(idx), L.ptr(a), L.ptr(r), L.ptr(t), L.ptr(tau),
+                                             L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(y), L.ptr(flat_grad),
+                                             L.current_stream()), "fb_iqn_train_from_replay")
+    return (loss, a, r, t, y) if want_target else (loss, a, r, t)
+
+
 def sac_train_from_replay(replay, net, idx, gamma=0.99, flat_grad=None, want_target=False):
     """QNet.sac_train_step on the transitions at the deque positions idx of a uniform memory at n-step 1, read from its frame ring in
     place (fb_sac_train_from_replay) -> (loss f32[6], a u8[B], r f32[B], t u8[B][, q_target f32[B]])"""
@@ -1212,6 +1344,41 @@ class SacStep:
         """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the six loss numbers are self.loss"""
         L.check(L.lib().fb_sac_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, self.batch, int(seed), int(step),
                                     int(bool(train)), self.gamma, self.rho, L.current_stream()), "fb_sac_step")
+        return self.actions
+
+
+class IqnStep:
+    """One whole step of the IQN loop as a single host call (fb_iqn_step): epsilon-greedy on the folded head -> frame_step -> store +
+    sample the minibatch -> (train) the IQN step from the ring, its tau drawn from (seed, step).  The results of the separate calls in
+    that order; the pointers are bound once."""
+
+    def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
+        if net.arch != IQN_ARCH:
+            raise ValueError("IqnStep needs an IQN net (QNet(..., arch='iqn'))")
+        if replay.prioritized:
+            raise ValueError("IqnStep trains from a uniform memory only")
+        if getattr(env, "nib", None) is None:
+            raise ValueError("call env.track_state() first: the acting path reads the env kernel's nibble states")
+        if not 1 <= int(batch) <= 256:
+            raise ValueError(f"batch must be in 1..256, got {batch}")
+        _dev_check(flat_grad)
+        self.env, self.replay, self.net = env, replay, net
+        self.batch, self.gamma, self.double_q, self.flat_grad = int(batch), float(gamma), bool(double_q), flat_grad
+        dev, B = env.device, self.batch
+        self.actions = torch.zeros(env.n, dtype=torch.uint8, device=dev)
+        self.idx = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.a = torch.empty(B, dtype=torch.uint8, device=dev)
+        self.r = torch.empty(B, dtype=torch.float32, device=dev)
+        self.t = torch.empty(B, dtype=torch.uint8, device=dev)
+        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        p = lambda x: None if x is None else x.data_ptr()
+        self.buf = L.StepBuffers(p(env.nib), p(self.actions), p(env.frame_bits), p(env.reward), p(env.terminal), p(env.score),
+                                 p(self.idx), None, None, p(self.a), p(self.t), p(self.r), p(self.loss), p(flat_grad), None, None, None)
+
+    def __call__(self, epsilon=0.0, seed=0, step=0, train=True):
+        """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the loss is self.loss"""
+        L.check(L.lib().fb_iqn_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(self.double_q), self.batch,
+                                    float(epsilon), int(seed), int(step), int(bool(train)), self.gamma, L.current_stream()), "fb_iqn_step")
         return self.actions
 
 

@@ -559,6 +559,9 @@ class VecBrain:
         if checkpoint_head(z) == "sac":
             raise ValueError(f"checkpoint {path} holds a sac head (a VecSAC's), this is a VecBrain: load it with "
                              "dqnflappybird_amd.vecsac.VecSAC")
+        if checkpoint_head(z) == "iqn":
+            raise ValueError(f"checkpoint {path} holds an iqn head (a VecIQN's), this is a VecBrain: load it with "
+                             "dqnflappybird_amd.veciqn.VecIQN")
         saved_world = int(z["scalars"][2]) if len(z["scalars"]) > 2 else 1
         if saved_world != self.world:
             raise ValueError(f"checkpoint {path} was written by {saved_world} rank(s), this job has {self.world}")

@@ -1,0 +1,191 @@
+"""VecIQN: implicit quantile networks (Dabney, Ostrovski, Silver & Munos 2018) on the vectorised loop, entirely device resident.
+
+    step:  epsilon-greedy on the folded head for N envs -> frame_step -> store + draw a minibatch      (vec.IqnStep, ONE host call)
+           -> [after `observe` steps] the IQN train step on the minibatch, read from the replay ring in place:
+              a* from the folded head of the target (or, double_q, the online) net, the target quantiles at sampled tau', the online
+              quantiles at sampled tau, the pairwise quantile Huber loss
+           -> the target net: copied every replace_target_iter steps, or target += polyak (online - target) every train step
+
+One net, one GPU, a uniform memory at any n-step view; include/fbdqn.h pins the semantics, DESIGN.md section 19 the design.  Acting costs
+what a plain net's does: the mean over the acting grid of tau folds into the head (QNet.set_iqn_risk scales the grid: CVaR).
+"""
+import numpy as np
+
+IQN_HEAD = "iqn"                                             # what a checkpoint of this class records as its head
+
+
+def check_args(n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step, polyak, replace_target_iter, observe, explore, initial_epsilon,
+               final_epsilon, gamma, lr, max_grad_norm, capacity):
+    """every argument check of VecIQN that needs no GPU -> the checked values"""
+    from . import _lib as L
+    from .vec import check_iqn, check_max_grad_norm, check_polyak
+    n, b, ob, ex, ns, rti = int(n_envs), int(batch), int(observe), int(explore), int(n_step), int(replace_target_iter)
+    if n < 1:
+        raise ValueError(f"n_envs must be >= 1, got {n_envs}")
+    if not 1 <= b <= 256:
+        raise ValueError(f"batch must be in 1..256, got {batch}")
+    if b > n:
+        raise ValueError(f"batch {b} > n_envs {n}: every step draws a minibatch, the first from one push of n_envs transitions")
+    N, Np, K, ka, eta = check_iqn(n_tau, n_tau_next, n_tau_act, kappa, cvar, 2)
+    if not 1 <= ns <= L.NSTEP_MAX:
+        raise ValueError(f"n_step must be in 1..{L.NSTEP_MAX}, got {n_step}")
+    rho = check_polyak(polyak, allow_off=True)
+    if rti < 1:
+        raise ValueError(f"replace_target_iter must be >= 1, got {replace_target_iter}")
+    if ob < 0:
+        raise ValueError(f"observe must be >= 0, got {observe}")
+    if ob < ns - 1:
+        raise ValueError(f"observe must be >= n_step - 1 = {ns - 1}: the first n_step - 1 steps only store (no n-step transition is complete yet), got {observe}")
+    if ex < 1:
+        raise ValueError(f"explore must be >= 1, got {explore}")
+    e0, e1 = float(initial_epsilon), float(final_epsilon)
+    if not (0.0 <= e1 <= e0 <= 1.0):
+        raise ValueError(f"the epsilon schedule needs 0 <= final_epsilon <= initial_epsilon <= 1, got {initial_epsilon} -> {final_epsilon}")
+    g, l = float(gamma), float(lr)
+    if not (np.isfinite(g) and 0.0 <= g <= 1.0):
+        raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+    if not (np.isfinite(l) and l > 0.0):
+        raise ValueError(f"lr must be finite and > 0, got {lr}")
+    cap = max(65536, 8 * n) if capacity is None else int(capacity)
+    if cap < max(2, ns) * n:
+        raise ValueError(f"capacity {cap} < max(2, n_step) x n_envs = {max(2, ns) * n}")
+    return n, b, N, Np, K, ka, eta, ns, rho, rti, ob, ex, e0, e1, g, l, check_max_grad_norm(max_grad_norm), cap
+
+
+class VecIQN:
+    def __init__(self, n_envs, batch=32, double_q=False, n_step=1, n_tau=8, n_tau_next=8, n_tau_act=32, kappa=1.0, cvar=1.0, polyak=0.0,
+                 replace_target_iter=500, observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99, lr=1e-6,
+                 max_grad_norm=0, fc_width=512, seed=0, capacity=None):
+        """n_envs games; every step trains one minibatch of `batch` transitions (<= n_envs, <= 256) once more than `observe` steps have
+        filled the memory.  n_tau / n_tau_next: the tau sampled per transition for the online / target quantiles; n_tau_act: the acting
+        grid; kappa: the quantile Huber threshold; cvar = eta in (0, 1]: act on CVaR_eta (1 = the mean).  double_q: a* from the online
+        net.  n_step > 1: n-step returns.  The epsilon schedule (observe / explore / initial / final) and the periodic target copy are
+        VecBrain's; polyak > 0 replaces the copy by soft updates; lr is Adam's; max_grad_norm=G > 0 clips the gradient's global norm."""
+        (self.n, self.batch, self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar, self.n_step, self.polyak, self.replace_target_iter,
+         self.observe, self.explore, self.initial_epsilon, self.final_epsilon, self.gamma, self.lr, self.max_grad_norm, self.capacity) = check_args(
+            n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step, polyak, replace_target_iter, observe, explore, initial_epsilon,
+            final_epsilon, gamma, lr, max_grad_norm, capacity)
+        from .vec import IqnStep, QNet, VecGameState, VecReplay
+        self.double_q = bool(double_q)
+        self.seed = int(seed)
+        self.fc_width = int(fc_width)
+        self.epsilon = self.initial_epsilon
+        self.env = VecGameState(self.n, seed=self.seed)
+        self.replay = VecReplay(self.capacity, self.n)
+        self.replay.seed(self.seed)
+        if self.n_step > 1:
+            self.replay.set_n_step(self.n_step, self.gamma)
+        self.net = QNet(2, self.fc_width, "iqn", max_batch=max(self.n, self.batch), n_tau=self.n_tau, n_tau_next=self.n_tau_next,
+                        n_tau_act=self.n_tau_act, kappa=self.kappa)
+        self.net.set_hparams(lr=self.lr)
+        if self.cvar != 1.0:
+            self.net.set_iqn_risk(self.cvar)
+        if self.max_grad_norm:
+            self.net.set_max_grad_norm(self.max_grad_norm)
+        self.net.init_params(seed=self.seed, which=0)
+        self.net.sync_target()
+        self.nib = self.env.track_state()
+        self.env.observe()
+        self.replay.reset(self.env.frame_bits)
+        self.stats = self.env.track_stats()
+        self.one_step = IqnStep(self.env, self.replay, self.net, self.batch, self.gamma, self.double_q)
+        self.loss = self.one_step.loss
+        self.timeStep = 0                                    # env steps per env so far: the key of the epsilon and tau draws
+
+    def step(self):
+        """one vector step -> the loss f32[1] (device)"""
+        if self.timeStep < self.n_step - 1:                  # no n-step transition is complete yet: store without drawing a minibatch
+            actions = self.net.act_nib(self.nib, self.epsilon, seed=self.seed, step=self.timeStep)
+            _, reward, terminal, _ = self.env.frame_step(actions, want_u8=False)
+            self.replay.push(self.env.frame_bits, actions, reward, terminal)
+            self.timeStep += 1
+            return self.loss
+        training = self.timeStep > self.observe
+        if training and not self.polyak and self.timeStep % self.replace_target_iter == 0:
+            self.net.sync_target()                           # (acting reads the online net only: the same as syncing before training)
+        self.one_step(self.epsilon, seed=self.seed, step=self.timeStep, train=training)
+        if self.epsilon > self.final_epsilon and training:
+            self.epsilon -= (self.initial_epsilon - self.final_epsilon) / self.explore
+        if training and self.polyak:
+            self.net.soft_sync_target(self.polyak)
+        self.timeStep += 1
+        return self.loss
+
+    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0):
+        """Greedy play (on the folded head, under the net's risk setting) of n_envs fresh games with the net as it stands
+        (dqnflappybird_amd.evaluate): changes nothing the training that follows reads"""
+        from .evaluate import evaluate
+        return evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed)
+
+    # ------------------------------------------------------------------ checkpoint / resume
+    @staticmethod
+    def _npz(path):
+        return path if str(path).endswith(".npz") else str(path) + ".npz"
+
+    def save(self, path):
+        """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory
+        (with its generator), the counters, epsilon and the settings; `head` = 'iqn' tells the file from the other loops'"""
+        host = lambda t: t.cpu().numpy()
+        m, v, pows = self.net.adam_state()
+        np.savez(self._npz(path), head=np.array([IQN_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
+                 adam_m=host(m), adam_v=host(v), beta_pows=np.asarray(pows, np.float32),
+                 scalars=np.array([self.timeStep, self.seed, self.n, self.batch, self.fc_width, self.observe, self.explore, self.n_step,
+                                   int(self.double_q), self.replace_target_iter], np.int64),
+                 iqn=np.array([self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar], np.float64),
+                 settings=np.array([self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon],
+                                   np.float64),
+                 env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob())
+
+    def load(self, path):
+        """the inverse of save(), into a VecIQN made with the same n_envs, batch, fc_width, n_step, (n_tau, n_tau_next, n_tau_act, kappa),
+        capacity and seed; the other settings of the file replace this object's"""
+        import torch
+        from .vec import IqnStep
+        from .vecbrain import checkpoint_head
+        z = np.load(self._npz(path))
+        head = checkpoint_head(z)
+        if head != IQN_HEAD:
+            raise ValueError(f"checkpoint {path} holds a {head} head (another loop's), this is a VecIQN (head {IQN_HEAD!r})")
+        sc = [int(x) for x in z["scalars"]]
+        if (sc[2], sc[3], sc[4], sc[7]) != (self.n, self.batch, self.fc_width, self.n_step):
+            raise ValueError(f"checkpoint {path} was written with (n_envs, batch, fc_width, n_step) = {(sc[2], sc[3], sc[4], sc[7])}, this "
+                             f"VecIQN has {(self.n, self.batch, self.fc_width, self.n_step)}")
+        if sc[1] != self.seed:
+            raise ValueError(f"checkpoint {path} was written with seed {sc[1]}, this VecIQN has seed {self.seed} (the envs' pipe-gap "
+                             "streams are keyed by it)")
+        q = [float(x) for x in z["iqn"]]
+        mine = (self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa)
+        if (int(q[0]), int(q[1]), int(q[2]), q[3]) != mine:
+            raise ValueError(f"checkpoint {path} was written with (n_tau, n_tau_next, n_tau_act, kappa) = {(int(q[0]), int(q[1]), int(q[2]), q[3])}, "
+                             f"this VecIQN has {mine}")
+        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        self.net.load_params(z["online"], 0)
+        self.net.load_params(z["target"], 1)
+        self.net.set_adam_state(dev(z["adam_m"]), dev(z["adam_v"]), z["beta_pows"])
+        self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon = (float(x) for x in z["settings"])
+        self.cvar = q[4]
+        self.net.set_hparams(lr=self.lr)
+        self.net.set_max_grad_norm(self.max_grad_norm)
+        self.net.set_iqn_risk(self.cvar)
+        self.observe, self.explore, self.double_q, self.replace_target_iter = sc[5], sc[6], bool(sc[8]), sc[9]
+        self.env.set_state(z["env_state"])
+        self.nib.copy_(dev(z["nib"]))
+        self.stats[...] = dev(z["stats"])
+        self.replay.load_state_blob(z["replay"])
+        self.timeStep = sc[0]
+        self.one_step = IqnStep(self.env, self.replay, self.net, self.batch, self.gamma, self.double_q)
+        self.loss = self.one_step.loss
+        torch.cuda.synchronize()
+
+    def run(self, steps, log_every=1000):
+        for i in range(steps):
+            loss = self.step()
+            if log_every and (i + 1) % log_every == 0:
+                ep, ssum, smax, pipes = self.stats.tolist()      # the only host sync of the loop, once per log line
+                self.net.check_range()
+                clip = ""
+                if self.max_grad_norm:
+                    norm, scale = self.net.grad_norm()
+                    clip = f" / GRAD_NORM {norm:.6g} / CLIP_SCALE {scale:.6g}"
+                print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / EPSILON {self.epsilon:.6f} / GAME_TIMES {ep} / "
+                      f"MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {loss.item():.6g}{clip}", flush=True)

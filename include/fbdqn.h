@@ -729,6 +729,68 @@ int fb_qnet_sac_train_step(fb_qnet_t h, int batch, const uint8_t *s, const uint8
 int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
                              double gamma, float *loss /*f32[6]*/, float *q_target, float *flat_grad, void *stream);
 
+/* ------------------------------------------------------------------ implicit quantile networks (IQN; Dabney, Ostrovski, Silver & Munos 2018)
+ * The step after QR-DQN: the net learns the whole quantile function theta(s, a; tau), trains on sampled tau and can act under a distorted
+ * risk measure (CVaR).  One GPU, fp32, a uniform memory at any n-step view.
+ * An IQN net (FB_ARCH_IQN, fb_qnet_create_iqn; 2 <= A <= 8; 1 <= n_tau N, n_tau_next N', n_tau_act K <= 64; kappa finite > 0, all checked
+ * before any allocation) has the PLAIN layout, then the embedding of FB_IQN_COS = 64 cosines (E):
+ *   trunk, W_fc1, b_fc1, W_q[FC,A], b_q[A], W_e[E,FC], b_e[FC]      (W_q b_q where a plain net has its head; one flat vector for Adam,
+ *                                                                     load / store / sync and the clip)
+ *   init        fb_qnet_init_params draws every weight by its own index, as in every net: the trunk, fc1 and W_q b_q are the plain net's of that
+ *               seed bit for bit, W_e draws like any weight.  b_e is filled with 1.0, NOT 0.01: a fresh net has phi ~ 1 and starts as the plain
+ *               net of its seed; the dependence on tau is learned
+ *   theta       h = relu(h_fc1).  c_j(tau) = (float)cos(M_PI * (double)j * (double)tau), j = 0 .. 63 (formed in double, rounded once);
+ *               pre_k(tau) = b_e[k] + sum_j c_j W_e[j,k], fmaf over ascending j from b_e[k];  phi_k = relu(pre_k);
+ *               theta(tau)_a = b_q[a] + sum_k (h_k phi_k) W_q[k,a]   (the order of the sum over k is the kernel's: fixed, no atomics)
+ *   greedy Q    the net holds a risk setting eta (fb_qnet_set_iqn_risk, 0 < eta <= 1, 1 in a new net): CVaR_eta through tau -> eta tau.
+ *               tauhat_i = (float)((double)eta * (2 i + 1) / (2 K)), i < K;  phibar_k = (sum_i phi_k(tauhat_i)) / (float)K, float32, ascending i;
+ *               Wt_q[k,a] = phibar_k * W_q[k,a];  Qbar(s, .) = the plain head over (b_fc1, Wt_q, b_q) -- the mean of theta over the grid,
+ *               since theta is linear in phi.  fb_qnet_forward / _act / _act_nib / fb_eval_run / fb_eval_q return Qbar of the online or the
+ *               target net with the plain net's first-maximum rule, epsilon rule and Philox draws.  The fold (b_fc1, Wt_q, b_q) of a net is
+ *               rebuilt by one small launch behind everything that changes its parameters or eta: Adam (fused or fb_qnet_apply_adam),
+ *               fb_qnet_load_params, _init_params, _sync_target, _soft_sync_target, fb_qnet_set_iqn_risk (on the default stream, then
+ *               synchronised).  fb_qnet_is_dist is 0: for acting purposes an IQN net is a plain net
+ *   forward_iqn theta f32[B][M][A] of the online or target net at the caller's tau f32[B][M]; 1 <= M <= 64, 1 <= B <= 3 * max_batch
+ *   tau draws   fb_iqn_draw_taus(batch, n, seed, step, which, out f32[batch][n]), stateless: o = Philox(key = seed, counter = (b * 64 + i,
+ *               step_lo, FB_STREAM_TAU = 10, step_hi)); tau = (float)(2 * (w >> 9) + 1) * 2^-24 with w = o.x for which = 0 (online) and
+ *               o.y for which = 1 (target): exact in float32, strictly inside (0, 1)
+ *   train step  per sample b, fp32 unless said otherwise:
+ *                 a* = the first maximum of Qbar(s', .) of the TARGET net (double_q = 0) or the online net (double_q = 1)
+ *                 r = (R == 0.1f) ? 0.1 : (double)R      T_j = (float)(done ? r : r + gamma * (double)theta_tgt(s', a*; tau'_j)), j < N'
+ *                 theta_i = theta(s, a_b; tau_i), i < N      u_ij = T_j - theta_i      w_ij = |tau_i - 1{u_ij < 0}|
+ *                 L(u) = u^2 / 2 if |u| <= kappa else kappa (|u| - kappa / 2)
+ *                 l_b = (sum_i (sum_j (w_ij L(u_ij)) / kappa)) / N'        j ascending inside, i ascending outside
+ *                 dl_b/dtheta_i = (-(sum_j (w_ij clamp(u_ij, -kappa, kappa)) / kappa) / N') / B       j ascending; T is a constant
+ *               loss[0] = (sum_b l_b) / B over ascending b.  Gradients reach W_q and b_q (the taken action's column), W_e, b_e, and through
+ *               dhf fc1 and the trunk; every sum runs in a fixed order with no atomics: equal inputs give equal bits.
+ *               tau f32[B][N] / tau_next f32[B][N'] are the caller's, or NULL: the draws above from (seed, step), which 0 / 1, bit for bit.
+ *               an action >= A reads A - 1.  1 <= batch <= min(max_batch, 256); 0 <= gamma <= 1 (an n-step memory: fb_iqn_train_from_replay
+ *               wants the memory's gamma and bootstraps with Gamma = gamma^n as every ring-fed call; fb_qnet_iqn_train_step takes the
+ *               discount of the bootstrap itself).  q_target f32[B][N'] (T) or NULL.  flat_grad, the Adam tick and the net's max_grad_norm
+ *               as in fb_qnet_sac_train_step.  The gathered and the ring-fed call agree bit for bit
+ *   loop step   fb_iqn_step = fb_qnet_act_nib(epsilon) -> fb_env_step -> fb_replay_push_sample(batch) -> if train: fb_iqn_train_from_replay
+ *               (tau from (seed, step); b->loss f32[1], b->flat_grad); those calls in that order on `stream`, after every check of all of
+ *               them, their results bit for bit.  It pushes: not capturable
+ *   refused     FB_ERR_INVALID before any launch or counter change: on an IQN net every FB_ALGO_* of fb_qnet_train_step / fb_train_from_replay /
+ *               fb_train_steps / fb_vec_step / fb_vec_step_dp, the A2C, PPO and SAC calls, fb_qnet_set_huber / _get_huber, _set_munchausen /
+ *               _get_munchausen, the noise calls, fb_qnet_forward_dist / _forward_quantiles, FB_DTYPE_BF16; fb_qnet_create with arch 8; the
+ *               IQN calls on a net that is not an IQN net; a prioritized memory
+ *   not offered prioritized replay, dueling or noisy IQN, bf16, data parallel, riders of the train step, the split schedule. */
+#define FB_ARCH_IQN 8
+#define FB_IQN_COS 64
+int fb_qnet_create_iqn(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch, fb_qnet_t *out);
+int fb_qnet_set_iqn_risk(fb_qnet_t h, float eta);
+int fb_qnet_get_iqn(fb_qnet_t h, int *n_tau_host, int *n_tau_next_host, int *n_tau_act_host, float *kappa_host, float *eta_host);
+int fb_qnet_forward_iqn(fb_qnet_t h, int which, const uint8_t *states, int batch, const float *tau /*f32[B][M]*/, int M,
+                        float *theta /*f32[B][M][A]*/, void *stream);
+int fb_iqn_draw_taus(int batch, int n, uint64_t seed, uint64_t step, int which, float *tau_out /*f32[batch][n]*/, void *stream);
+int fb_qnet_iqn_train_step(fb_qnet_t h, int double_q, int batch, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
+                           const uint8_t *t, const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma,
+                           float *loss /*f32[1]*/, float *q_target, float *flat_grad, void *stream);
+int fb_iqn_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, uint8_t *a_out, float *r_out,
+                             uint8_t *t_out, const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma,
+                             float *loss /*f32[1]*/, float *q_target, float *flat_grad, void *stream);
+
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
 int fb_qnet_num_params(fb_qnet_t h, int64_t *n_host);
@@ -871,6 +933,10 @@ int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_b
  * training step a, r, t, loss (f32[6]) and flat_grad (or NULL). */
 int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed, uint64_t step,
                 int train, double gamma, float rho, void *stream);
+/* The vector step of an IQN net (the IQN block above pins it): of *b it reads nib, actions, frame_bits, reward, terminal, score, idx, and for a
+ * training step a, r, t, loss (f32[1]) and flat_grad (or NULL). */
+int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
+                uint64_t seed, uint64_t step, int train, double gamma, void *stream);
 
 /* fb_replay_gather + fb_qnet_train_step WITHOUT the gathered copies (BrainDQN.py:197-223 from the indices on): the minibatch is
  * described by its indices, the conv trunk reads the replay's 1-bit frames directly (5 x 800 B per transition instead of writing and

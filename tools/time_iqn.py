@@ -1,0 +1,105 @@
+"""What IQN costs: us per fb_iqn_step against fb_vec_step of 'qr' (a QR net, N = 51) and of 'double' (a plain net) under the one-stream
+schedule (fb_vec_step_set_schedule(0)) at the same env count; us per train step alone (exported gradient) of the three; and us per
+acting forward (act_nib) of an IQN net against a plain net's, which should differ by nothing: the fold is refreshed behind Adam, not
+on the acting path.
+
+    python tools/time_iqn.py [--envs 256,1024,4096] [--batch 32] [--steps 300] [--warmup 100] [--repeats 5] [--out FILE]
+
+Rows go to stdout, and are appended to --out when one is given.  Every pipeline is warmed up, then --repeats rounds of --steps timed
+calls, the configurations alternated within each round, in one process.  Reported: the median and the spread of the rounds.  The
+yardstick for a difference is the dependent empty launch (tools/mb/mb_launch, run as a child process first).
+"""
+import argparse
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from dqnflappybird_amd import _lib as L  # noqa: E402
+from dqnflappybird_amd.vec import IqnStep, QNet, VecGameState, VecReplay, VecStep, iqn_train_from_replay, train_from_replay  # noqa: E402
+from tools.time_a2c import launch_floor, timed  # noqa: E402
+
+CONFIGS = {"fb_iqn_step (N 8, N' 8, K 32)": ("iqn", None), "fb_vec_step qr (N 51)": ("qr", "qr"), "fb_vec_step double": ("plain", "double")}
+
+
+def pipeline(n_envs, arch, algo, batch):
+    env = VecGameState(n_envs, seed=1)
+    net = QNet(2, 512, arch, max_batch=max(n_envs, 256))
+    rep = VecReplay(1_000_000, n_envs)
+    rep.seed(3, "cpython")
+    net.init_params(5, which=0); net.init_params(6, which=1)
+    net.set_hparams(lr=1e-6)
+    env.track_state(); env.observe(); rep.reset(env.frame_bits)
+    step = IqnStep(env, rep, net, batch, 0.99) if arch == "iqn" else VecStep(env, rep, net, batch, algo, 0.99)
+    return dict(env=env, net=net, rep=rep, step=step, arch=arch, algo=algo, k=0)
+
+
+def one(p):
+    p["step"](0.1, seed=2, step=p["k"], train=True)
+    p["k"] += 1
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", default="256,1024,4096")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--out", default=None, help="also append the rows to this file")
+    a = ap.parse_args()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out if a.out else os.devnull, "a") as out:
+        def emit(line):
+            for f in (sys.stdout, out):
+                print(line, file=f); f.flush()
+
+        def row(what, n, config, v):
+            emit(f"  {what:13s} {n:5d}  {config:30s} {statistics.median(v):10.1f} {min(v):9.1f} {max(v):9.1f}  us")
+
+        def rounds(fns, warm):
+            for fn in fns.values():
+                for _ in range(warm):
+                    fn()
+            res = {c: [] for c in fns}
+            for _ in range(a.repeats):
+                for c, fn in fns.items():
+                    res[c].append(timed(fn, a.steps))
+            return res
+
+        emit(f"# tools/time_iqn.py on {torch.cuda.get_device_name(0)}: {' '.join(sys.argv[1:])}")
+        floor = launch_floor()                   # (a child process of its own, before this one holds much of the GPU)
+        if isinstance(floor, str):
+            emit(f"# empty dependent launch: {floor}")
+        else:
+            for shape, us in floor:
+                emit(f"# empty dependent launch (tools/mb/mb_launch, {shape}): {us:.2f} us per launch")
+        L.check(L.lib().fb_vec_step_set_schedule(0), "fb_vec_step_set_schedule")      # the one-stream order: what fb_iqn_step runs in
+        emit("#  what           envs  config                             median       min       max")
+        for n_envs in [int(x) for x in a.envs.split(",")]:
+            pipes = {c: pipeline(n_envs, arch, algo, a.batch) for c, (arch, algo) in CONFIGS.items()}
+            for c, v in rounds({c: (lambda p=p: one(p)) for c, p in pipes.items()}, a.warmup).items():
+                row("loop step", n_envs, c, v)
+            idx = (torch.arange(a.batch, dtype=torch.int64) * 7).cuda()
+            grads = {c: torch.zeros(p["net"].n_params, dtype=torch.float32, device="cuda") for c, p in pipes.items()}
+
+            def train_fn(c, p):
+                if p["arch"] == "iqn":
+                    return lambda: iqn_train_from_replay(p["rep"], p["net"], idx, 0.99, seed=2, step=1, flat_grad=grads[c])
+                return lambda: train_from_replay(p["rep"], p["net"], p["algo"], idx, 0.99, flat_grad=grads[c])
+            for c, v in rounds({c: train_fn(c, p) for c, p in pipes.items()}, 20).items():
+                row(f"train B={a.batch}", n_envs, c.replace("fb_iqn_step", "iqn").replace("fb_vec_step ", ""), v)
+            act = {c: (lambda p=p: p["net"].act_nib(p["env"].nib, 0.1, seed=2, step=3)) for c, p in pipes.items() if p["arch"] in ("iqn", "plain")}
+            for c, v in rounds(act, 20).items():
+                row("act_nib", n_envs, "iqn net (folded head)" if "iqn" in c else "plain net", v)
+            del pipes, grads, act
+            torch.cuda.synchronize()
+        L.check(L.lib().fb_vec_step_set_schedule(1), "fb_vec_step_set_schedule")
+
+
+if __name__ == "__main__":
+    main()
