@@ -90,6 +90,13 @@ int fb_env_observe(fb_env_t h, uint8_t *frames, uint64_t *frame_bits, void *stre
  *   0 playery 1 velY 2 playerIndex 3 loopIter 4 basex 5 score 6 nPipes
  *   7..9 pipe x 10..12 pipe gap index (0..7) 13 PLAYER_INDEX_GEN phase 14 rng counter 15 tape cursor */
 int fb_env_get_state(fb_env_t h, int32_t *state_host);
+/* fb_env_set_state refuses (FB_ERR_INVALID) a wing pose outside 0..2, a basex outside {0,-4,..,-44}, a gap index outside 0..7 and a
+ * pipe count outside 1..3; it does not check the rest.  The domain the step and the observation are specified and tested on
+ * (tests/test_gpu_env_sweep.py: equal to the oracle env at every point of it) is what play reaches, for every integer pipe x:
+ *   playery 0..379 (at or below 380 the step has crashed and reset; the observation's bird rows cover y < 384 from a table and
+ *   fall back to the per-pixel path outside, and the ground-only columns 63..79 assume the bird never lies below y = 403),
+ *   velY -9..10, loopIter 0..29, phase 0..3, nPipes 2..3 with pipe x ascending and slots >= nPipes zero (a step may leave 1 pipe
+ *   behind when it removes the first of 2; a third pipe only exists while the first is at x <= 4), rng counter / tape cursor >= 0. */
 int fb_env_set_state(fb_env_t h, const int32_t *state_host);
 /* Replace the Philox pipe-gap stream by an explicit tape of random.randint(0,7) results
  * (i8[N][tape_len], [host], copied); tape_len = 0 switches back to Philox. Synchronous. */

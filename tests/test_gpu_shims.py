@@ -215,6 +215,19 @@ def test_vecbrain_save_load_continues_bit_for_bit(torch_cuda, tmp_path):
     assert (a.env.get_state() == b.env.get_state()).all() and len(a.replay) == len(b.replay)
 
 
+def unpack_nib(nibt):
+    """the env kernel's nibble states u8[N][FB_NIB_STRIDE] -> the 4-frame stacks u8[N,80,80,4] (newest frame last)"""
+    from dqnflappybird_amd import _lib as L                         # [N][FB_NIB_STRIDE]: 84 padded rows of 4 + 40 bytes
+    raw = nibt.cpu().numpy()
+    N = raw.shape[0]
+    full = raw[:, :L.NIB_ROWS * L.NIB_PITCH].reshape(N, L.NIB_ROWS, L.NIB_PITCH)
+    assert not full[:, :2].any() and not full[:, 82:].any() and not full[:, :, :4].any()      # conv1's zero padding
+    assert not raw[:, L.NIB_ROWS * L.NIB_PITCH:].any()
+    b = np.ascontiguousarray(full[:, 2:82, 4:])
+    px = np.stack([b & 0x0F, b >> 4], axis=-1).reshape(N, 6400)     # nibble per pixel
+    return (((px[..., None] >> np.arange(4)) & 1) * 255).astype(np.uint8).reshape(N, 80, 80, 4)
+
+
 @pytest.mark.parametrize("N", [7, 64, 300, 301, 1027])      # < 256: the small-batch kernels; >= 256: the two-plane fp16 acting kernels
 def test_nibble_state_equals_current_state_and_act_nib_is_bit_identical(torch_cuda, N):
     """The env kernel's running 4-frame nibble state == the replay ring's currentState (BrainDQN.py:68,238-239),
@@ -230,15 +243,7 @@ def test_nibble_state_equals_current_state_and_act_nib_is_bit_identical(torch_cu
     env.observe()
     rep.reset(env.frame_bits)
 
-    def unpack(nibt):
-        from dqnflappybird_amd import _lib as L                     # [N][FB_NIB_STRIDE]: 84 padded rows of 4 + 40 bytes
-        raw = nibt.cpu().numpy()
-        full = raw[:, :L.NIB_ROWS * L.NIB_PITCH].reshape(N, L.NIB_ROWS, L.NIB_PITCH)
-        assert not full[:, :2].any() and not full[:, 82:].any() and not full[:, :, :4].any()      # conv1's zero padding
-        assert not raw[:, L.NIB_ROWS * L.NIB_PITCH:].any()
-        b = np.ascontiguousarray(full[:, 2:82, 4:])
-        px = np.stack([b & 0x0F, b >> 4], axis=-1).reshape(N, 6400)   # nibble per pixel
-        return (((px[..., None] >> np.arange(4)) & 1) * 255).astype(np.uint8).reshape(N, 80, 80, 4)
+    unpack = unpack_nib
 
     rng = np.random.default_rng(0)
     for t in range(12):
