@@ -382,26 +382,25 @@ extern "C" int fb_ac_gae(const float *reward, const uint8_t *terminal, const flo
     return FB_OK;
 }
 
-extern "C" int fb_ac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *adv, const float *ret,
-                                       int64_t n_total, uint8_t *a_out, float *loss, float *flat_grad, void *stream) {
-    FB_REQUIRE(replay && net && idx && adv && ret && a_out && loss, "fb_ac_train_from_replay: NULL argument");
-    FB_REQUIRE(fb_qnet_is_ac(net), "fb_ac_train_from_replay: not an actor-critic net (fb_qnet_create_ac)");
-    FB_REQUIRE(!fb_replay_is_prioritized(replay), "fb_ac_train_from_replay: the rollout is read from a uniform memory only");
-    int n = 1; double g = 0.0;
-    int rc = fb_replay_get_n_step(replay, &n, &g);
-    if (rc != FB_OK) return rc;
-    FB_REQUIRE(n == 1, "fb_ac_train_from_replay: the memory has a %d-step view; the rollout is read at n-step 1 only", n);
-    rc = fb_qnet_ac_check_train(net, batch, n_total, "fb_ac_train_from_replay");
+// what the two ring-fed AC training calls do between their NULL checks and their train step: the net's kind, the memory's (uniform, n-step
+// 1), the batch and n_total, then the minibatch described in the ring (r / t go to the net's scratch rows)
+static int ac_ring_src(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, int64_t n_total, uint8_t *a_out, FbRingSrc *ring, const char *who,
+                       void *stream) {
+    FB_REQUIRE(fb_qnet_is_ac(net), "%s: not an actor-critic net (fb_qnet_create_ac)", who);
+    int rc = fb_check_uniform_n1(replay, who, "the rollout is read from a uniform memory only", "the rollout is read");
+    if (rc == FB_OK) rc = fb_qnet_ac_check_train(net, batch, n_total, who);
     if (rc != FB_OK) return rc;
     float *r_scr; uint8_t *t_scr;
     fb_qnet_ac_scratch(net, &r_scr, &t_scr);
+    return fb_ring_src_fresh(replay, net, batch, idx, a_out, r_scr, t_scr, ring, stream);
+}
+
+extern "C" int fb_ac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *adv, const float *ret,
+                                       int64_t n_total, uint8_t *a_out, float *loss, float *flat_grad, void *stream) {
+    FB_REQUIRE(replay && net && idx && adv && ret && a_out && loss, "fb_ac_train_from_replay: NULL argument");
     FbRingSrc ring;
-    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_scr, t_scr, &ring);
+    const int rc = ac_ring_src(replay, net, batch, idx, n_total, a_out, &ring, "fb_ac_train_from_replay", stream);
     if (rc != FB_OK) return rc;
-    if (batch >= 256) {                          // (W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
-        rc = fb_qnet_refresh_planes(net, stream);
-        if (rc != FB_OK) return rc;
-    }
     return fb_qnet_ac_train_ring(net, batch, &ring, adv, ret, n_total, loss, flat_grad, stream);
 }
 
@@ -409,23 +408,9 @@ extern "C" int fb_ppo_train_from_replay(fb_replay_t replay, fb_qnet_t net, int b
                                         const float *ret, const float *logp_old, const float *value_old, int64_t n_total, uint8_t *a_out,
                                         float *loss, float *flat_grad, void *stream) {
     FB_REQUIRE(replay && net && idx && adv && ret && logp_old && value_old && a_out && loss, "fb_ppo_train_from_replay: NULL argument");
-    FB_REQUIRE(fb_qnet_is_ac(net), "fb_ppo_train_from_replay: not an actor-critic net (fb_qnet_create_ac)");
-    FB_REQUIRE(!fb_replay_is_prioritized(replay), "fb_ppo_train_from_replay: the rollout is read from a uniform memory only");
-    int n = 1; double g = 0.0;
-    int rc = fb_replay_get_n_step(replay, &n, &g);
-    if (rc != FB_OK) return rc;
-    FB_REQUIRE(n == 1, "fb_ppo_train_from_replay: the memory has a %d-step view; the rollout is read at n-step 1 only", n);
-    rc = fb_qnet_ac_check_train(net, batch, n_total, "fb_ppo_train_from_replay");
-    if (rc != FB_OK) return rc;
-    float *r_scr; uint8_t *t_scr;
-    fb_qnet_ac_scratch(net, &r_scr, &t_scr);
     FbRingSrc ring;
-    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_scr, t_scr, &ring);
+    const int rc = ac_ring_src(replay, net, batch, idx, n_total, a_out, &ring, "fb_ppo_train_from_replay", stream);
     if (rc != FB_OK) return rc;
-    if (batch >= 256) {                          // (as fb_ac_train_from_replay)
-        rc = fb_qnet_refresh_planes(net, stream);
-        if (rc != FB_OK) return rc;
-    }
     return fb_qnet_ppo_train_ring(net, batch, &ring, sel, adv, ret, logp_old, value_old, n_total, loss, flat_grad, stream);
 }
 
@@ -454,14 +439,13 @@ extern "C" int fb_ac_rollout_step(fb_env_t env, fb_replay_t replay, fb_qnet_t ne
     FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && b->value && b->logp, "fb_ac_rollout_step: NULL buffer");
     FB_REQUIRE(fb_qnet_is_ac(net), "fb_ac_rollout_step: not an actor-critic net (fb_qnet_create_ac)");
     FB_REQUIRE(!fb_replay_is_prioritized(replay), "fb_ac_rollout_step: the rollout is stored in a uniform memory only");
-    FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_ac_rollout_step: n_envs %d does not match the env (%d) / replay (%d) handles",
-               n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
-    FB_REQUIRE(n_envs <= fb_qnet_max_rows(net), "fb_ac_rollout_step: %d envs exceed 3*max_batch of the net", n_envs);
+    int rc = fb_check_step_handles(env, replay, net, n_envs, "fb_ac_rollout_step");
+    if (rc != FB_OK) return rc;
     FB_REQUIRE(slot >= 0 && slot < b->slots, "fb_ac_rollout_step: slot %d outside the buffers' %d rows", slot, b->slots);
     // (every argument check of the three calls below is made above -- handles, buffers, the net's kind and row count, the env counts --
     // so nothing is launched and no push is counted before a refusal)
     const size_t o = (size_t)slot * n_envs;
-    int rc = fb_qnet_act_policy_nib(net, b->nib, n_envs, seed, step, 0, b->actions, b->value + o, b->logp + o, nullptr, stream);
+    rc = fb_qnet_act_policy_nib(net, b->nib, n_envs, seed, step, 0, b->actions, b->value + o, b->logp + o, nullptr, stream);
     if (rc != FB_OK) return rc;
     rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward + o, b->terminal + o, b->score, stream);
     if (rc != FB_OK) return rc;

@@ -322,6 +322,15 @@ int fb_qnet_is_iqn(fb_qnet_t h);              // 1: an IQN net (fb_qnet_create_i
 int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int batch, double gamma, const char *who);
 int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int batch, const FbRingSrc *ring, const float *tau, const float *tau_next, uint64_t seed,
                            uint64_t step, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
+// ---- the refusal rules of the ring-fed entry points (fb_common.hip): made before any counter moves or any launch; FB_OK, else the error
+// code with fb_last_error naming `who`
+int fb_check_q_net(fb_qnet_t net, const char *who, bool steps);       // no AC / SAC / IQN net (steps: `who` steps the envs too)
+int fb_check_algo(fb_replay_t replay, fb_qnet_t net, int algo, const char *who, bool takes_per = true);       // algo against net and memory
+int fb_check_step_handles(fb_env_t env, fb_replay_t replay, fb_qnet_t net, int n_envs, const char *who);      // n_envs: the handles', <= 3 * max_batch
+// a uniform memory ("%s: `uniform_only`") at n-step 1 ("... `reads` at n-step 1 only")
+int fb_check_uniform_n1(fb_replay_t replay, const char *who, const char *uniform_only, const char *reads);
+// fb_replay_ring_src, and W_fc1's planes re-split where the batch reads them (>= 256): what a ring-fed train call does behind its checks
+int fb_ring_src_fresh(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a, float *r, uint8_t *t, FbRingSrc *ring, void *stream);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);

@@ -90,39 +90,85 @@ void fb_mt_init_by_array_host(FbMT *s, const uint32_t *key, int key_length) {
     s->idx = 624;
 }
 
-// QR (include/fbdqn.h): a QR net and a QR algo go together; FB_ALGO_QR / _DOUBLE take a uniform memory, FB_ALGO_QR_PER / _DOUBLE_PER a
-// prioritized one.  Checked by the ring-fed calls before any counter moves or any launch, as the C51 checks beside them
-static int qr_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *who) {
-    if (!is_qr_algo(algo) && !fb_qnet_is_qr(net)) return FB_OK;
-    FB_REQUIRE(is_qr_algo(algo) == (fb_qnet_is_qr(net) != 0),
-               "%s: a QR net takes a QR algo (FB_ALGO_QR, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a QR net only (algo %d)", who, algo);
-    if (is_per_algo(algo))
-        FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: algo %d (QR with prioritized replay) trains from a prioritized memory only", who, algo);
-    else
-        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: algo %d (QR) trains from a uniform memory only (FB_ALGO_QR_PER / _DOUBLE_PER take a "
-                   "prioritized one)", who, algo);
+// ---- the refusal rules of the ring-fed entry points (include/fbdqn.h), in one place.  Every check here runs before any counter moves or
+// any launch goes out: a refused call leaves the handles as they were.
+// The DQN-family calls (fb_train_steps, fb_vec_step, fb_train_from_replay) take no AC / SAC / IQN net.  steps: `who` also steps the envs
+int fb_check_q_net(fb_qnet_t net, const char *who, bool steps) {
+    if (steps) {
+        FB_REQUIRE(!fb_qnet_is_ac(net), "%s: an actor-critic net steps through fb_ac_rollout_step and trains through fb_ac_train_from_replay only", who);
+        FB_REQUIRE(!fb_qnet_is_sac(net), "%s: a SAC net steps through fb_sac_step and trains through fb_sac_train_from_replay only", who);
+        FB_REQUIRE(!fb_qnet_is_iqn(net), "%s: an IQN net steps through fb_iqn_step and trains through fb_iqn_train_from_replay only", who);
+    } else {
+        FB_REQUIRE(!fb_qnet_is_ac(net), "%s: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only", who);
+        FB_REQUIRE(!fb_qnet_is_sac(net), "%s: a SAC net trains through fb_qnet_sac_train_step / fb_sac_train_from_replay only", who);
+        FB_REQUIRE(!fb_qnet_is_iqn(net), "%s: an IQN net trains through fb_qnet_iqn_train_step / fb_iqn_train_from_replay only", who);
+    }
     return FB_OK;
 }
 
-// Munchausen-DQN (include/fbdqn.h): a scalar net; FB_ALGO_MDQN takes a uniform memory, FB_ALGO_MDQN_PER a prioritized one.  Checked by the
-// ring-fed calls before any counter moves or any launch, as the C51 / QR checks beside them
-static int mdqn_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *who) {
-    if (!is_mdqn_algo(algo)) return FB_OK;
-    FB_REQUIRE(!fb_qnet_is_dist(net), "%s: algo %d (Munchausen-DQN) trains a scalar net (FB_ARCH_PLAIN / FB_ARCH_DUELING) only, not a C51 / QR / noisy net", who, algo);
-    if (algo == FB_ALGO_MDQN_PER)
-        FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: FB_ALGO_MDQN_PER trains from a prioritized memory only (FB_ALGO_MDQN takes a uniform one)", who);
-    else
-        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: FB_ALGO_MDQN trains from a uniform memory only (FB_ALGO_MDQN_PER takes a prioritized one)", who);
+// Which algo goes with which net and which memory.  The algo / net matches are train_plan's checks too (fb_qnet.hip); they are made here
+// because train_plan runs behind the draw and the push.  takes_per = false: fb_train_steps, which has refused the prioritized algos
+// already and keeps its own wording of the C51 rule; it leaves an unknown algo to train_plan.
+int fb_check_algo(fb_replay_t replay, fb_qnet_t net, int algo, const char *who, bool takes_per) {
+    const bool prioritized = fb_replay_is_prioritized(replay) != 0;
+    if (takes_per)
+        FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "%s: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER, FB_ALGO_MDQN .. FB_ALGO_DOUBLE_PER)", who, algo);
+    // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one, which
+    // fb_vec_step and fb_train_from_replay check behind this call, each in its own words)
+    if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
+        FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
+                   takes_per ? "%s: a C51 net takes a C51 algo (FB_ALGO_C51, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a C51 net only (algo %d)"
+                             : "%s: a C51 net takes a C51 algo (FB_ALGO_C51 or FB_ALGO_C51_DOUBLE), and those algos take a C51 net only (algo %d)", who, algo);
+        if (!is_per_algo(algo))
+            FB_REQUIRE(!prioritized, "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", who);
+    }
+    // QR: a QR net and a QR algo go together; FB_ALGO_QR / _DOUBLE take a uniform memory, FB_ALGO_QR_PER / _DOUBLE_PER a prioritized one
+    if (is_qr_algo(algo) || fb_qnet_is_qr(net)) {
+        FB_REQUIRE(is_qr_algo(algo) == (fb_qnet_is_qr(net) != 0),
+                   "%s: a QR net takes a QR algo (FB_ALGO_QR, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a QR net only (algo %d)", who, algo);
+        if (is_per_algo(algo))
+            FB_REQUIRE(prioritized, "%s: algo %d (QR with prioritized replay) trains from a prioritized memory only", who, algo);
+        else
+            FB_REQUIRE(!prioritized, "%s: algo %d (QR) trains from a uniform memory only (FB_ALGO_QR_PER / _DOUBLE_PER take a prioritized one)", who, algo);
+    }
+    // Munchausen-DQN: a scalar net; FB_ALGO_MDQN takes a uniform memory, FB_ALGO_MDQN_PER a prioritized one
+    if (is_mdqn_algo(algo)) {
+        FB_REQUIRE(!fb_qnet_is_dist(net), "%s: algo %d (Munchausen-DQN) trains a scalar net (FB_ARCH_PLAIN / FB_ARCH_DUELING) only, not a C51 / QR / noisy net", who, algo);
+        if (algo == FB_ALGO_MDQN_PER)
+            FB_REQUIRE(prioritized, "%s: FB_ALGO_MDQN_PER trains from a prioritized memory only (FB_ALGO_MDQN takes a uniform one)", who);
+        else
+            FB_REQUIRE(!prioritized, "%s: FB_ALGO_MDQN trains from a uniform memory only (FB_ALGO_MDQN_PER takes a prioritized one)", who);
+    }
+    // FB_ALGO_DOUBLE_PER: a scalar net and a prioritized memory, as FB_ALGO_PER
+    if (algo == FB_ALGO_DOUBLE_PER) {
+        FB_REQUIRE(!fb_qnet_is_dist(net), "%s: algo %d (FB_ALGO_DOUBLE_PER) trains a scalar net (FB_ARCH_PLAIN / FB_ARCH_DUELING) only, not a C51 / QR / noisy net", who, algo);
+        FB_REQUIRE(prioritized, "%s: FB_ALGO_DOUBLE_PER trains from a prioritized memory only (FB_ALGO_DOUBLE takes a uniform one)", who);
+    }
     return FB_OK;
 }
 
-// FB_ALGO_DOUBLE_PER (include/fbdqn.h): a scalar net and a prioritized memory, as FB_ALGO_PER.  Checked by the ring-fed calls before any
-// counter moves or any launch, as the checks beside it
-static int dper_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *who) {
-    if (algo != FB_ALGO_DOUBLE_PER) return FB_OK;
-    FB_REQUIRE(!fb_qnet_is_dist(net), "%s: algo %d (FB_ALGO_DOUBLE_PER) trains a scalar net (FB_ARCH_PLAIN / FB_ARCH_DUELING) only, not a C51 / QR / noisy net", who, algo);
-    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: FB_ALGO_DOUBLE_PER trains from a prioritized memory only (FB_ALGO_DOUBLE takes a uniform one)", who);
+int fb_check_step_handles(fb_env_t env, fb_replay_t replay, fb_qnet_t net, int n_envs, const char *who) {
+    FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "%s: n_envs %d does not match the env (%d) / replay (%d) handles", who,
+               n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
+    FB_REQUIRE(n_envs <= fb_qnet_max_rows(net), "%s: %d envs exceed 3*max_batch of the net", who, n_envs);
     return FB_OK;
+}
+
+int fb_check_uniform_n1(fb_replay_t replay, const char *who, const char *uniform_only, const char *reads) {
+    FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: %s", who, uniform_only);
+    int n = 1; double g = 0.0;
+    const int rc = fb_replay_get_n_step(replay, &n, &g);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(n == 1, "%s: the memory has a %d-step view; %s at n-step 1 only", who, n, reads);
+    return FB_OK;
+}
+
+// the conv planes are always current (adam_fused_kernel; init / load / sync re-split eagerly).  Only a batch of >= 256 also reads W_fc1's
+// planes (fc1_sp_kernel), which Adam leaves stale: re-split them on sight (two guarded launches)
+int fb_ring_src_fresh(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a, float *r, uint8_t *t, FbRingSrc *ring, void *stream) {
+    const int rc = fb_replay_ring_src(replay, batch, idx, a, r, t, ring);
+    if (rc != FB_OK || batch < 256) return rc;
+    return fb_qnet_refresh_planes(net, stream);
 }
 
 // n x (random.sample -> minibatch -> _trainQNetwork) on a memory that is not being pushed to, as one host call.  Each step is the six
@@ -135,28 +181,16 @@ static int dper_check(fb_replay_t replay, fb_qnet_t net, int algo, const char *w
 extern "C" int fb_train_steps(fb_replay_t replay, fb_qnet_t net, int algo, int batch, int n_steps, int64_t *idx, uint8_t *s,
                               uint8_t *s2, uint8_t *a, float *r, uint8_t *t, float *loss, double gamma, void *stream) {
     FB_REQUIRE(replay && net && idx && s && s2 && a && r && t && loss && n_steps >= 1, "fb_train_steps: bad argument");
-    FB_REQUIRE(!fb_qnet_is_ac(net), "fb_train_steps: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only");
-    FB_REQUIRE(!fb_qnet_is_sac(net), "fb_train_steps: a SAC net trains through fb_qnet_sac_train_step / fb_sac_train_from_replay only");
-    FB_REQUIRE(!fb_qnet_is_iqn(net), "fb_train_steps: an IQN net trains through fb_qnet_iqn_train_step / fb_iqn_train_from_replay only");
+    int rc = fb_check_q_net(net, "fb_train_steps", false);
+    if (rc != FB_OK) return rc;
     FB_REQUIRE(!is_per_algo(algo), "fb_train_steps: prioritized replay needs the importance weights: use the separate calls (algo %d)", algo);
     FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_train_steps: a noisy net needs a noise key per step, which this call has none of: use fb_vec_step or "
                "fb_qnet_reset_noise + fb_train_from_replay");
     FB_REQUIRE(!(fb_qnet_max_grad_norm(net) > 0.f), "fb_train_steps: the net clips its gradient (max_grad_norm %g): a clipped step is three calls, which this "
                "call's riding draws do not span: use fb_train_from_replay or fb_vec_step", (double)fb_qnet_max_grad_norm(net));
-    // C51 (FB_ALGO_C51 / FB_ALGO_C51_DOUBLE): a C51 net and a uniform memory only -- the algo / net match is train_plan's check, made
-    // here as well so that it comes before any counter moves
-    if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
-        FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
-                   "%s: a C51 net takes a C51 algo (FB_ALGO_C51 or FB_ALGO_C51_DOUBLE), and those algos take a C51 net only (algo %d)", "fb_train_steps", algo);
-        FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_steps");
-    }
-    {
-        const int rq = qr_check(replay, net, algo, "fb_train_steps");
-        if (rq != FB_OK) return rq;
-        const int rm = mdqn_check(replay, net, algo, "fb_train_steps");
-        if (rm != FB_OK) return rm;
-    }
-    int rc = fb_replay_check_gamma(replay, gamma, "fb_train_steps");
+    rc = fb_check_algo(replay, net, algo, "fb_train_steps", false);
+    if (rc != FB_OK) return rc;
+    rc = fb_replay_check_gamma(replay, gamma, "fb_train_steps");
     if (rc != FB_OK) return rc;
     gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: the ring readers deliver (R, done), the target takes Gamma)
     rc = fb_replay_sample(replay, batch, nullptr, idx, nullptr, stream);
@@ -289,32 +323,15 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
                            int batch, float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
     FB_REQUIRE(env && replay && net && b, "fb_vec_step: NULL handle");
     FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "fb_vec_step: NULL env buffer");
-    FB_REQUIRE(!fb_qnet_is_ac(net), "fb_vec_step: an actor-critic net steps through fb_ac_rollout_step and trains through fb_ac_train_from_replay only");
-    FB_REQUIRE(!fb_qnet_is_sac(net), "fb_vec_step: a SAC net steps through fb_sac_step and trains through fb_sac_train_from_replay only");
-    FB_REQUIRE(!fb_qnet_is_iqn(net), "fb_vec_step: an IQN net steps through fb_iqn_step and trains through fb_iqn_train_from_replay only");
+    int rc = fb_check_q_net(net, "fb_vec_step", true);
+    if (rc != FB_OK) return rc;
     const bool per = is_per_algo(algo);      // (FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 / QR _PER algos)
     if (per && train) FB_REQUIRE(b->isw && b->isw32 && b->abs_err, "fb_vec_step: the prioritized step needs the isw / isw32 / abs_err buffers");
     // every argument check of the calls below happens HERE, before the replay's push counter moves or anything is launched: a
     // rejected step must leave the handles exactly as they were (a counted push without its env launch would make every later
     // gather address a ring slot that was never written)
-    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_vec_step: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER, FB_ALGO_MDQN .. FB_ALGO_DOUBLE_PER)", algo);
-    // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
-    // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
-    // counter moves
-    if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
-        FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
-                   "%s: a C51 net takes a C51 algo (FB_ALGO_C51, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a C51 net only (algo %d)", "fb_vec_step", algo);
-        if (!is_per_algo(algo))
-            FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_vec_step");
-    }
-    {
-        const int rq = qr_check(replay, net, algo, "fb_vec_step");
-        if (rq != FB_OK) return rq;
-        const int rm = mdqn_check(replay, net, algo, "fb_vec_step");
-        if (rm != FB_OK) return rm;
-        const int rd = dper_check(replay, net, algo, "fb_vec_step");
-        if (rd != FB_OK) return rd;
-    }
+    rc = fb_check_algo(replay, net, algo, "fb_vec_step");
+    if (rc != FB_OK) return rc;
     FB_REQUIRE(per == (fb_replay_is_prioritized(replay) != 0), "fb_vec_step: algo %d and the memory's kind (uniform / prioritized) do not match", algo);
     FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "fb_vec_step: n_envs %d does not match the env (%d) / replay (%d) handles",
                n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
@@ -419,7 +436,7 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     // an env workgroup has a wave for each of its envs there (up to four envs per workgroup: 8192 envs)
     FbHeadRider hrider;
     const int have_h = fb_env_can_carry_head(env) && fb_qnet_num_actions(net) == 2 && !fb_qnet_is_dist(net);     // (C51 / QR: its own launch)
-    int rc = have_h ? fb_qnet_act_nib_rider(net, b->nib, n_envs, epsilon, seed, step, b->actions, &hrider, stream)
+    rc = have_h ? fb_qnet_act_nib_rider(net, b->nib, n_envs, epsilon, seed, step, b->actions, &hrider, stream)
              : env_noise ? fb_qnet_act_nib_env_noise_keep(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream)
                          : fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
     if (rc != FB_OK) return rc;
@@ -485,45 +502,21 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
 extern "C" int fb_train_from_replay(fb_replay_t replay, fb_qnet_t net, int algo, int batch, const int64_t *idx, const float *isw, uint8_t *a,
                                     float *r, uint8_t *t, double gamma, float *loss, float *abs_err, float *flat_grad, void *stream) {
     FB_REQUIRE(replay && net && idx && a && r && t && loss, "fb_train_from_replay: NULL argument");
-    FB_REQUIRE(!fb_qnet_is_ac(net), "fb_train_from_replay: an actor-critic net trains through fb_qnet_ac_train_step / fb_ac_train_from_replay only");
-    FB_REQUIRE(!fb_qnet_is_sac(net), "fb_train_from_replay: a SAC net trains through fb_qnet_sac_train_step / fb_sac_train_from_replay only");
-    FB_REQUIRE(!fb_qnet_is_iqn(net), "fb_train_from_replay: an IQN net trains through fb_qnet_iqn_train_step / fb_iqn_train_from_replay only");
-    FB_REQUIRE(is_scalar_algo(algo) || is_c51_algo(algo) || is_qr_algo(algo), "fb_train_from_replay: unknown algo %d (0..3, FB_ALGO_C51 .. FB_ALGO_QR_DOUBLE_PER, FB_ALGO_MDQN .. FB_ALGO_DOUBLE_PER)", algo);
-    // C51: a C51 net, and for FB_ALGO_C51 / FB_ALGO_C51_DOUBLE a uniform memory only (FB_ALGO_C51_PER / _DOUBLE_PER: a prioritized one,
-    // checked with the memory's kind below) -- the algo / net match is train_plan's check, made here as well so that it comes before any
-    // counter moves
-    if (is_c51_algo(algo) || fb_qnet_is_c51(net)) {
-        FB_REQUIRE(is_c51_algo(algo) == (fb_qnet_is_c51(net) != 0),
-                   "%s: a C51 net takes a C51 algo (FB_ALGO_C51, _DOUBLE, _PER, _DOUBLE_PER), and those algos take a C51 net only (algo %d)", "fb_train_from_replay", algo);
-        if (!is_per_algo(algo))
-            FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: C51 trains from a uniform memory only (prioritized replay with C51 is not supported)", "fb_train_from_replay");
-    }
-    {
-        const int rq = qr_check(replay, net, algo, "fb_train_from_replay");
-        if (rq != FB_OK) return rq;
-        const int rm = mdqn_check(replay, net, algo, "fb_train_from_replay");
-        if (rm != FB_OK) return rm;
-        const int rd = dper_check(replay, net, algo, "fb_train_from_replay");
-        if (rd != FB_OK) return rd;
-    }
+    int rc = fb_check_q_net(net, "fb_train_from_replay", false);
+    if (rc == FB_OK) rc = fb_check_algo(replay, net, algo, "fb_train_from_replay");
+    if (rc != FB_OK) return rc;
     FB_REQUIRE(!is_per_algo(algo) || isw, "fb_train_from_replay: the prioritized step needs the importance weights");
     if (is_c51_algo(algo) && is_per_algo(algo))
         FB_REQUIRE(fb_replay_is_prioritized(replay), "fb_train_from_replay: algo %d (C51 with prioritized replay) trains from a prioritized memory only", algo);
     FB_REQUIRE(batch >= 1 && batch <= 256, "fb_train_from_replay: batch must be in 1..256");
-    int rc = fb_replay_check_gamma(replay, gamma, "fb_train_from_replay");
+    rc = fb_replay_check_gamma(replay, gamma, "fb_train_from_replay");
     if (rc != FB_OK) return rc;
     rc = fb_replay_check_complete(replay, 0, "fb_train_from_replay");
     if (rc != FB_OK) return rc;
     gamma = fb_replay_bootstrap_gamma(replay, gamma);
     FbRingSrc ring;
-    rc = fb_replay_ring_src(replay, batch, idx, a, r, t, &ring);
+    rc = fb_ring_src_fresh(replay, net, batch, idx, a, r, t, &ring, stream);
     if (rc != FB_OK) return rc;
-    // the conv planes are always current (adam_fused_kernel; init / load / sync re-split eagerly).  Only a batch of >= 256 also reads
-    // W_fc1's planes (fc1_sp_kernel), which Adam leaves stale: re-split them on sight (two guarded launches)
-    if (batch >= 256) {
-        rc = fb_qnet_refresh_planes(net, stream);
-        if (rc != FB_OK) return rc;
-    }
     return fb_qnet_train_step_ring(net, algo, batch, &ring, isw, gamma, loss, abs_err, flat_grad, stream);
 }
 

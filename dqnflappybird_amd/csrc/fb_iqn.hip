@@ -378,12 +378,8 @@ extern "C" int fb_iqn_train_from_replay(fb_replay_t replay, fb_qnet_t net, int d
     rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
     if (rc != FB_OK) return rc;
     FbRingSrc ring;
-    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_out, t_out, &ring);
+    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
     if (rc != FB_OK) return rc;
-    if (batch >= 256) {                          // (W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
-        rc = fb_qnet_refresh_planes(net, stream);
-        if (rc != FB_OK) return rc;
-    }
     return fb_qnet_iqn_train_ring(net, double_q, batch, &ring, tau, tau_next, seed, step, fb_replay_bootstrap_gamma(replay, gamma), loss, q_target,
                                   flat_grad, stream);
 }
@@ -397,10 +393,8 @@ extern "C" int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
     int rc = iqn_check_memory(replay, gamma, who);
     if (rc != FB_OK) return rc;
-    FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "%s: n_envs %d does not match the env (%d) / replay (%d) handles", who,
-               n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
-    FB_REQUIRE(n_envs <= fb_qnet_max_rows(net), "%s: %d envs exceed 3*max_batch of the net", who, n_envs);
-    rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    rc = fb_check_step_handles(env, replay, net, n_envs, who);
+    if (rc == FB_OK) rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
     if (rc != FB_OK) return rc;
     // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
     rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);

@@ -5454,6 +5454,32 @@ static int run_train(fb_qnet *h, Plan &p, void *stream) {
     return rc;
 }
 
+// a train step on gathered states: only a batch of >= 256 reads W_fc1's planes (fc1_sp_kernel), which Adam leaves stale (fb_ring_src_fresh's
+// rule for the ring-fed calls)
+static int run_train_gathered(fb_qnet *h, Plan &p, int B, void *stream) {
+    const int rc = B >= 256 ? fb_qnet_refresh_planes(h, stream) : FB_OK;
+    return rc != FB_OK ? rc : run_train(h, p, stream);
+}
+
+// what every train plan ends with: where the gradient goes and who applies Adam, the ring, and its n-step view (s' = frames tt + n - 3 .. tt + n)
+static void plan_train_tail(fb_qnet *h, Plan &p, float *flat_grad, const FbRingSrc *ring) {
+    p.G = flat_grad ? flat_grad : h->grad;
+    p.apply_adam = flat_grad == nullptr; p.tick = true;
+    p.ring = ring;
+    if (ring && ring->c.nstep > 1)
+        for (int z = 0; z < p.ns; z++) if (p.sl.s[z].fshift) p.sl.s[z].fshift = ring->c.nstep;
+}
+
+// the two checks the training calls of every family share, `who` in the message
+static int check_batch(fb_qnet *h, int B, const char *who) {
+    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "%s: batch %d exceeds min(max_batch, %d)", who, B, MAXTB);
+    return FB_OK;
+}
+static int check_gamma01(double gamma, const char *who) {
+    FB_REQUIRE(isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
+    return FB_OK;
+}
+
 static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
                       const uint8_t *t, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
                       float *flat_grad, Plan *out, const FbRingSrc *ring = nullptr) {
@@ -5471,7 +5497,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
                                         : "fb_qnet_train_step: a QR net trains with FB_ALGO_QR, FB_ALGO_QR_DOUBLE, FB_ALGO_QR_PER or "
                                           "FB_ALGO_QR_DOUBLE_PER only (got algo %d)", algo);
     }
-    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "fb_qnet_train_step: batch %d exceeds min(max_batch, %d)", B, MAXTB);
+    if (const int rb = check_batch(h, B, "fb_qnet_train_step")) return rb;
     FB_REQUIRE(algo != FB_ALGO_PG || (B <= 128 && !ring && gamma >= (double)B), "fb_qnet_train_step: FB_ALGO_PG takes chunks of <= 128 gathered states and gamma = the whole batch's sample count (>= %d)", B);
     FB_REQUIRE(!is_per_algo(algo) || isw, "fb_qnet_train_step: PER needs isw (algo %d)", algo);
     FB_REQUIRE(algo != FB_ALGO_PG || !(h->huber > 0.f), "fb_qnet_train_step: FB_ALGO_PG has no TD error to clip: the net's Huber delta is %g, set it to 0 (fb_qnet_set_huber)", (double)h->huber);
@@ -5486,11 +5512,7 @@ static int train_plan(fb_qnet *h, int algo, int B, const uint8_t *s, const uint8
     p.sl.rb = h->nsplit_train == 1;
     p.train = true; p.algo = algo; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.isw = isw; p.gamma = gamma;
     p.loss = loss; p.abs_err = abs_err; p.y = q_target;
-    p.G = flat_grad ? flat_grad : h->grad;
-    p.apply_adam = flat_grad == nullptr; p.tick = true;
-    p.ring = ring;
-    if (ring && ring->c.nstep > 1)                   // n-step view: s' = frames tt + n - 3 .. tt + n
-        for (int z = 0; z < p.ns; z++) if (p.sl.s[z].fshift) p.sl.s[z].fshift = ring->c.nstep;
+    plan_train_tail(h, p, flat_grad, ring);
     *out = p;
     return FB_OK;
 }
@@ -5592,7 +5614,7 @@ extern "C" int fb_qnet_act_policy_nib(fb_qnet_t h, const uint8_t *nib_states, in
 
 int fb_qnet_ac_check_train(fb_qnet_t h, int B, int64_t n_total, const char *who) {
     FB_REQUIRE(h && is_ac(h), "%s: not an actor-critic net (fb_qnet_create_ac)", who);
-    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "%s: batch %d exceeds min(max_batch, %d)", who, B, MAXTB);
+    if (const int rb = check_batch(h, B, who)) return rb;
     FB_REQUIRE(n_total >= (int64_t)B && n_total <= (int64_t)1 << 40, "%s: n_total %lld must be the whole update's sample count (>= the batch %d)", who, (long long)n_total, B);
     return FB_OK;
 }
@@ -5607,9 +5629,7 @@ static Plan ac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a,
     p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
     p.train = true; p.algo = -1; p.B = B; p.s = s; p.a = a; p.ac_adv = adv; p.ac_ret = ret; p.ac_nt = (float)n_total;
     p.loss = loss;
-    p.G = flat_grad ? flat_grad : h->grad;
-    p.apply_adam = flat_grad == nullptr; p.tick = true;
-    p.ring = ring;
+    plan_train_tail(h, p, flat_grad, ring);
     return p;
 }
 
@@ -5619,11 +5639,7 @@ extern "C" int fb_qnet_ac_train_step(fb_qnet_t h, int B, const uint8_t *s, const
     const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_qnet_ac_train_step");
     if (rc != FB_OK) return rc;
     Plan p = ac_train_plan(h, B, s, a, adv, ret, n_total, loss, flat_grad, nullptr);
-    if (B >= 256) {                              // (fc1_sp_kernel reads W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
-        const int rp = fb_qnet_refresh_planes(h, stream);
-        if (rp != FB_OK) return rp;
-    }
-    return run_train(h, p, stream);
+    return run_train_gathered(h, p, B, stream);
 }
 
 int fb_qnet_ac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const float *adv, const float *ret, int64_t n_total, float *loss,
@@ -5666,11 +5682,7 @@ extern "C" int fb_qnet_ppo_train_step(fb_qnet_t h, int B, const uint8_t *s, cons
     const int rc = fb_qnet_ac_check_train(h, B, n_total, "fb_qnet_ppo_train_step");
     if (rc != FB_OK) return rc;
     Plan p = ppo_train_plan(h, B, s, a, nullptr, adv, ret, logp_old, value_old, n_total, loss, flat_grad, nullptr);
-    if (B >= 256) {                              // (as fb_qnet_ac_train_step)
-        const int rp = fb_qnet_refresh_planes(h, stream);
-        if (rp != FB_OK) return rp;
-    }
-    return run_train(h, p, stream);
+    return run_train_gathered(h, p, B, stream);
 }
 
 int fb_qnet_ppo_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const int64_t *sel, const float *adv, const float *ret,
@@ -5747,14 +5759,13 @@ extern "C" int fb_qnet_forward_sac(fb_qnet_t h, int which, const uint8_t *states
 
 int fb_qnet_sac_check_train(fb_qnet_t h, int B, double gamma, const char *who) {
     FB_REQUIRE(h && is_sac(h), "%s: not a SAC net (fb_qnet_create_sac)", who);
-    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "%s: batch %d exceeds min(max_batch, %d)", who, B, MAXTB);
-    FB_REQUIRE(isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
-    return FB_OK;
+    if (const int rb = check_batch(h, B, who)) return rb;
+    return check_gamma01(gamma, who);
 }
 
-// the train plan of a SAC net: FB_ALGO_DOUBLE's three slices -- s and s' through the online net, s' through the target net
-static Plan sac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t, double gamma,
-                           float *loss, float *q_target, float *flat_grad, const FbRingSrc *ring) {
+// the train plan a SAC and an IQN net share: FB_ALGO_DOUBLE's three slices -- s and s' through the online net, s' through the target net
+static Plan three_slice_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t, double gamma,
+                             float *loss, float *q_target, float *flat_grad, const FbRingSrc *ring) {
     Plan p; memset(&p, 0, sizeof(p));
     p.ns = 3;
     p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
@@ -5762,10 +5773,15 @@ static Plan sac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a
     p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1};
     p.train = true; p.algo = -1; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.gamma = gamma;
     p.loss = loss; p.y = q_target;
-    p.G = flat_grad ? flat_grad : h->grad;
-    p.apply_adam = flat_grad == nullptr; p.tick = true;
+    plan_train_tail(h, p, flat_grad, ring);
+    return p;
+}
+
+// (the ring-fed SAC call takes a memory at n-step 1 only: fb_sac.hip)
+static Plan sac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t, double gamma,
+                           float *loss, float *q_target, float *flat_grad, const FbRingSrc *ring) {
+    Plan p = three_slice_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, ring);
     p.sac_temp = flat_grad == nullptr && h->sac_alr > 0.f;
-    p.ring = ring;
     return p;
 }
 
@@ -5775,11 +5791,7 @@ extern "C" int fb_qnet_sac_train_step(fb_qnet_t h, int B, const uint8_t *s, cons
     const int rc = fb_qnet_sac_check_train(h, B, gamma, "fb_qnet_sac_train_step");
     if (rc != FB_OK) return rc;
     Plan p = sac_train_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, nullptr);
-    if (B >= 256) {                              // (fc1_sp_kernel reads W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
-        const int rp = fb_qnet_refresh_planes(h, stream);
-        if (rp != FB_OK) return rp;
-    }
-    return run_train(h, p, stream);
+    return run_train_gathered(h, p, B, stream);
 }
 
 int fb_qnet_sac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
@@ -5827,28 +5839,15 @@ extern "C" int fb_qnet_forward_iqn(fb_qnet_t h, int which, const uint8_t *states
 int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int B, double gamma, const char *who) {
     FB_REQUIRE(h && is_iqn(h), "%s: not an IQN net (fb_qnet_create_iqn)", who);
     FB_REQUIRE(double_q == 0 || double_q == 1, "%s: double_q must be 0 or 1 (got %d)", who, double_q);
-    FB_REQUIRE(B >= 1 && B <= h->max_batch && B <= MAXTB, "%s: batch %d exceeds min(max_batch, %d)", who, B, MAXTB);
-    FB_REQUIRE(isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
-    return FB_OK;
+    if (const int rb = check_batch(h, B, who)) return rb;
+    return check_gamma01(gamma, who);
 }
 
-// the train plan of an IQN net: FB_ALGO_DOUBLE's three slices -- s and s' through the online net, s' through the target net
 static Plan iqn_train_plan(fb_qnet *h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
                            const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma, float *loss, float *q_target,
                            float *flat_grad, const FbRingSrc *ring) {
-    Plan p; memset(&p, 0, sizeof(p));
-    p.ns = 3;
-    p.sl.s[0] = Slice{h->params[0], s, 0, B, h->w1s[0], 0};
-    p.sl.s[1] = Slice{h->params[0], s2, B, B, h->w1s[0], 1};
-    p.sl.s[2] = Slice{h->params[1], s2, 2 * B, B, h->w1s[1], 1};
-    p.train = true; p.algo = -1; p.B = B; p.s = s; p.a = a; p.r = r; p.t = t; p.gamma = gamma;
-    p.loss = loss; p.y = q_target;
-    p.G = flat_grad ? flat_grad : h->grad;
-    p.apply_adam = flat_grad == nullptr; p.tick = true;
+    Plan p = three_slice_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, ring);
     p.iqn_tau = tau; p.iqn_tau_next = tau_next; p.iqn_double = double_q != 0; p.seed = seed; p.step = step;
-    p.ring = ring;
-    if (ring && ring->c.nstep > 1)                   // n-step view: s' = frames tt + n - 3 .. tt + n (train_plan's rule)
-        for (int z = 1; z < p.ns; z++) p.sl.s[z].fshift = ring->c.nstep;
     return p;
 }
 
@@ -5859,11 +5858,7 @@ extern "C" int fb_qnet_iqn_train_step(fb_qnet_t h, int double_q, int B, const ui
     const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_qnet_iqn_train_step");
     if (rc != FB_OK) return rc;
     Plan p = iqn_train_plan(h, double_q, B, s, a, r, s2, t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, nullptr);
-    if (B >= 256) {                              // (fc1_sp_kernel reads W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
-        const int rp = fb_qnet_refresh_planes(h, stream);
-        if (rp != FB_OK) return rp;
-    }
-    return run_train(h, p, stream);
+    return run_train_gathered(h, p, B, stream);
 }
 
 int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int B, const FbRingSrc *ring, const float *tau, const float *tau_next, uint64_t seed, uint64_t step,

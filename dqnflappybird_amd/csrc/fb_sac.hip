@@ -291,12 +291,7 @@ void fb_sac_launch_grad(hipStream_t st, const void *args) {
 
 // the memory checks of the two ring-fed SAC calls: a uniform memory at n-step 1
 static int sac_check_memory(fb_replay_t replay, const char *who) {
-    FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: SAC trains from a uniform memory only (prioritized replay is not offered)", who);
-    int n = 1; double g = 0.0;
-    const int rc = fb_replay_get_n_step(replay, &n, &g);
-    if (rc != FB_OK) return rc;
-    FB_REQUIRE(n == 1, "%s: the memory has a %d-step view; SAC reads it at n-step 1 only", who, n);
-    return FB_OK;
+    return fb_check_uniform_n1(replay, who, "SAC trains from a uniform memory only (prioritized replay is not offered)", "SAC reads it");
 }
 
 extern "C" int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
@@ -309,12 +304,8 @@ extern "C" int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int b
     rc = fb_qnet_sac_check_train(net, batch, gamma, who);
     if (rc != FB_OK) return rc;
     FbRingSrc ring;
-    rc = fb_replay_ring_src(replay, batch, idx, a_out, r_out, t_out, &ring);
+    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
     if (rc != FB_OK) return rc;
-    if (batch >= 256) {                          // (W_fc1's planes, which Adam leaves stale: fb_train_from_replay's rule)
-        rc = fb_qnet_refresh_planes(net, stream);
-        if (rc != FB_OK) return rc;
-    }
     return fb_qnet_sac_train_ring(net, batch, &ring, gamma, loss, q_target, flat_grad, stream);
 }
 
@@ -327,10 +318,8 @@ extern "C" int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
     int rc = sac_check_memory(replay, who);
     if (rc != FB_OK) return rc;
-    FB_REQUIRE(n_envs == fb_env_num_envs(env) && n_envs == fb_replay_num_envs(replay), "%s: n_envs %d does not match the env (%d) / replay (%d) handles", who,
-               n_envs, fb_env_num_envs(env), fb_replay_num_envs(replay));
-    FB_REQUIRE(n_envs <= fb_qnet_max_rows(net), "%s: %d envs exceed 3*max_batch of the net", who, n_envs);
-    rc = fb_qnet_sac_check_train(net, batch, gamma, who);
+    rc = fb_check_step_handles(env, replay, net, n_envs, who);
+    if (rc == FB_OK) rc = fb_qnet_sac_check_train(net, batch, gamma, who);
     if (rc != FB_OK) return rc;
     FB_REQUIRE(rho >= 0.f && rho <= 1.f, "%s: rho must be in [0, 1] (0 = no target update; got %g)", who, (double)rho);
     // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)

@@ -1078,6 +1078,11 @@ def train_from_replay(replay, net, algo, idx, gamma=0.99, flat_grad=None, isw=No
     return (loss, a, r, t, ae) if want_abs_err else (loss, a, r, t)
 
 
+def _check_flat_grad(flat_grad, n_params):
+    if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
+        raise ValueError(f"flat_grad must be float32[{n_params}]")
+
+
 def check_chunk(B, a, n_total, flat_grad, n_params):
     """what the A2C and the PPO training calls check alike, on the host: the chunk's size, its actions, n_total, the gradient buffer"""
     if not 1 <= B <= 256:
@@ -1086,8 +1091,7 @@ def check_chunk(B, a, n_total, flat_grad, n_params):
         raise ValueError(f"a must be uint8[{B}]")
     if n_total is not None and int(n_total) < B:
         raise ValueError(f"n_total = {n_total} must be the whole update's sample count (>= the chunk's {B})")
-    if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
-        raise ValueError(f"flat_grad must be float32[{n_params}]")
+    _check_flat_grad(flat_grad, n_params)
 
 
 def check_ac_batch(B, a, adv, ret, n_total, flat_grad, n_params):
@@ -1098,29 +1102,37 @@ def check_ac_batch(B, a, adv, ret, n_total, flat_grad, n_params):
             raise ValueError(f"{name} must be float32[{B}]")
 
 
-def check_sac_batch(B, a, r, t, flat_grad, n_params):
+def check_sac_batch(B, a, r, t, flat_grad, n_params, what="a SAC batch"):
     """the shape checks of the two SAC training calls, on the host"""
     if not 1 <= B <= 256:
-        raise ValueError(f"a SAC batch holds 1..256 samples, got {B}")
+        raise ValueError(f"{what} holds 1..256 samples, got {B}")
     for name, x, dt in (("a", a, torch.uint8), ("r", r, torch.float32), ("t", t, torch.uint8)):
         if x is not None and (x.dtype != dt or x.numel() != B):
             raise ValueError(f"{name} must be {dt}[{B}]")
-    if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
-        raise ValueError(f"flat_grad must be float32[{n_params}]")
+    _check_flat_grad(flat_grad, n_params)
 
 
 def check_iqn_batch(B, a, r, t, tau, tau_next, n_tau, n_tau_next, flat_grad, n_params):
-    """the shape checks of the two IQN training calls, on the host"""
-    if not 1 <= B <= 256:
-        raise ValueError(f"an IQN batch holds 1..256 samples, got {B}")
-    for name, x, dt in (("a", a, torch.uint8), ("r", r, torch.float32), ("t", t, torch.uint8)):
-        if x is not None and (x.dtype != dt or x.numel() != B):
-            raise ValueError(f"{name} must be {dt}[{B}]")
+    """the shape checks of the two IQN training calls, on the host: check_sac_batch's, with the two tau tensors in front of flat_grad"""
+    check_sac_batch(B, a, r, t, None, n_params, "an IQN batch")
     for name, x, n in (("tau", tau, n_tau), ("tau_next", tau_next, n_tau_next)):
         if x is not None and (x.dtype != torch.float32 or tuple(x.shape) != (B, n) or not x.is_contiguous()):
             raise ValueError(f"{name} must be a contiguous float32[{B}, {n}]")
-    if flat_grad is not None and (flat_grad.dtype != torch.float32 or flat_grad.numel() != n_params):
-        raise ValueError(f"flat_grad must be float32[{n_params}]")
+    _check_flat_grad(flat_grad, n_params)
+
+
+def _ring_call(name, replay, net, arch, need, reads, idx, n_loss, *tensors):
+    """what the four *_train_from_replay calls of the newer families begin with: the net's arch, a uniform memory, device tensors, idx's
+    dtype -> (B, dev, a u8[B], loss f32[n_loss]), the last two for the library to fill"""
+    if net.arch != arch:
+        raise ValueError(f"{name} needs {need}")
+    if replay.prioritized:
+        raise ValueError(f"{name} {reads} a uniform memory only")
+    _dev_check(idx, *tensors)
+    if idx.dtype != torch.int64:
+        raise ValueError("idx must be int64[B]")
+    B, dev = int(idx.numel()), idx.device
+    return B, dev, torch.empty(B, dtype=torch.uint8, device=dev), torch.zeros(n_loss, dtype=torch.float32, device=dev)
 
 
 def iqn_draw_taus(batch, n, seed=0, step=0, which=0, device="cuda"):
@@ -1139,18 +1151,11 @@ def iqn_train_from_replay(replay, net, idx, gamma=0.99, double_q=False, tau=None
     """QNet.iqn_train_step on the transitions at the deque positions idx of a uniform memory (any n-step view; gamma must be the memory's),
     read from its frame ring in place (fb_iqn_train_from_replay)
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, q_target f32[B, n_tau_next]])"""
-    if net.arch != IQN_ARCH:
-        raise ValueError("iqn_train_from_replay needs an IQN net (QNet(..., arch='iqn'))")
-    if replay.prioritized:
-        raise ValueError("iqn_train_from_replay trains from a uniform memory only")
-    _dev_check(idx, flat_grad, tau, tau_next)
-    if idx.dtype != torch.int64:
-        raise ValueError("idx must be int64[B]")
-    B, dev = int(idx.numel()), idx.device
+    B, dev, a, loss = _ring_call("iqn_train_from_replay", replay, net, IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
+                                 flat_grad, tau, tau_next)
     N, Np = net.iqn()[:2]
     check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
-    a = torch.empty(B, dtype=torch.uint8, device=dev); r = torch.empty(B, dtype=torch.float32, device=dev)
-    t = torch.empty(B, dtype=torch.uint8, device=dev); loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
     y = torch.empty((B, Np), dtype=torch.float32, device=dev) if want_target else None
     L.check(L.lib().fb_iqn_train_from_replay(replay.h, net.h, int(bool(double_q)), B, L.ptr(idx), L.ptr(a), L.ptr(r), L.ptr(t), L.ptr(tau),
                                              L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(y), L.ptr(flat_grad),
@@ -1161,17 +1166,9 @@ def iqn_train_from_replay(replay, net, idx, gamma=0.99, double_q=False, tau=None
 def sac_train_from_replay(replay, net, idx, gamma=0.99, flat_grad=None, want_target=False):
     """QNet.sac_train_step on the transitions at the deque positions idx of a uniform memory at n-step 1, read from its frame ring in
     place (fb_sac_train_from_replay) -> (loss f32[6], a u8[B], r f32[B], t u8[B][, q_target f32[B]])"""
-    if net.arch != SAC_ARCH:
-        raise ValueError("sac_train_from_replay needs a SAC net (QNet(..., arch='sac'))")
-    if replay.prioritized:
-        raise ValueError("sac_train_from_replay trains from a uniform memory only")
-    _dev_check(idx, flat_grad)
-    if idx.dtype != torch.int64:
-        raise ValueError("idx must be int64[B]")
-    B, dev = int(idx.numel()), idx.device
+    B, dev, a, loss = _ring_call("sac_train_from_replay", replay, net, SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", "trains from", idx, 6, flat_grad)
     check_sac_batch(B, None, None, None, flat_grad, net.n_params)
-    a = torch.empty(B, dtype=torch.uint8, device=dev); r = torch.empty(B, dtype=torch.float32, device=dev)
-    t = torch.empty(B, dtype=torch.uint8, device=dev); loss = torch.zeros(6, dtype=torch.float32, device=dev)
+    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
     y = torch.empty(B, dtype=torch.float32, device=dev) if want_target else None
     L.check(L.lib().fb_sac_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(a), L.ptr(r), L.ptr(t), float(gamma), L.ptr(loss), L.ptr(y),
                                              L.ptr(flat_grad), L.current_stream()), "fb_sac_train_from_replay")
@@ -1198,17 +1195,9 @@ def ac_gae(reward, terminal, value, gamma=0.99, gae_lambda=0.95):
 def ac_train_from_replay(replay, net, idx, adv, ret, n_total=None, flat_grad=None):
     """QNet.ac_train_step on the transitions at the deque positions idx of a uniform memory, read from its frame ring in place
     (fb_ac_train_from_replay) -> (loss f32[4], a u8[B]: the ring's actions)"""
-    if net.arch != AC_ARCH:
-        raise ValueError("ac_train_from_replay needs an actor-critic net (QNet(..., arch='ac'))")
-    if replay.prioritized:
-        raise ValueError("ac_train_from_replay reads the rollout from a uniform memory only")
-    _dev_check(idx, adv, ret, flat_grad)
-    if idx.dtype != torch.int64:
-        raise ValueError("idx must be int64[B]")
-    B, dev = int(idx.numel()), idx.device
+    B, _, a, loss = _ring_call("ac_train_from_replay", replay, net, AC_ARCH, "an actor-critic net (QNet(..., arch='ac'))", "reads the rollout from", idx, 4,
+                               adv, ret, flat_grad)
     check_ac_batch(B, None, adv, ret, n_total, flat_grad, net.n_params)
-    a = torch.empty(B, dtype=torch.uint8, device=dev)
-    loss = torch.zeros(4, dtype=torch.float32, device=dev)
     L.check(L.lib().fb_ac_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(adv), L.ptr(ret), int(n_total or B), L.ptr(a), L.ptr(loss),
                                             L.ptr(flat_grad), L.current_stream()), "fb_ac_train_from_replay")
     return loss, a
@@ -1234,20 +1223,12 @@ def ppo_train_from_replay(replay, net, idx, adv, ret, logp_old, value_old, sel=N
     THAT CHECK IS A HOST SYNC ON EVERY CALL WITH sel (it reads sel back from the device and waits for the stream): a loop, or anyone
     who times this call, passes check_sel=False, which is safe for a sel that is in range by construction (a permutation's slice:
     VecActorCritic, tools/time_ppo.py).  -> (loss f32[6], a u8[B]: the ring's actions)"""
-    if net.arch != AC_ARCH:
-        raise ValueError("ppo_train_from_replay needs an actor-critic net (QNet(..., arch='ac'))")
-    if replay.prioritized:
-        raise ValueError("ppo_train_from_replay reads the rollout from a uniform memory only")
-    _dev_check(idx, sel, adv, ret, logp_old, value_old, flat_grad)
-    if idx.dtype != torch.int64:
-        raise ValueError("idx must be int64[B]")
-    B, dev = int(idx.numel()), idx.device
+    B, _, a, loss = _ring_call("ppo_train_from_replay", replay, net, AC_ARCH, "an actor-critic net (QNet(..., arch='ac'))", "reads the rollout from", idx, 6,
+                               sel, adv, ret, logp_old, value_old, flat_grad)
     check_chunk(B, None, n_total, flat_grad, net.n_params)
     check_ppo_batch(B, sel, adv, ret, logp_old, value_old)
     if sel is not None and check_sel and not bool(((sel >= 0) & (sel < adv.numel())).all()):      # (reads sel back: one host sync)
         raise ValueError(f"sel must lie in 0..{adv.numel() - 1}, the rollout buffers' positions")
-    a = torch.empty(B, dtype=torch.uint8, device=dev)
-    loss = torch.zeros(6, dtype=torch.float32, device=dev)
     L.check(L.lib().fb_ppo_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(sel), L.ptr(adv), L.ptr(ret), L.ptr(logp_old), L.ptr(value_old),
                                              int(n_total or B), L.ptr(a), L.ptr(loss), L.ptr(flat_grad), L.current_stream()),
             "fb_ppo_train_from_replay")
@@ -1312,33 +1293,39 @@ class AcRolloutStep:
         return self.actions
 
 
+def _bind_step(self, name, arch, need, env, replay, net, batch, gamma, flat_grad, n_loss):
+    """what SacStep and IqnStep set up alike: the checks, the step's own tensors (loss: f32[n_loss]) and the bound pointers"""
+    if net.arch != arch:
+        raise ValueError(f"{name} needs {need}")
+    if replay.prioritized:
+        raise ValueError(f"{name} trains from a uniform memory only")
+    if getattr(env, "nib", None) is None:
+        raise ValueError("call env.track_state() first: the acting path reads the env kernel's nibble states")
+    if not 1 <= int(batch) <= 256:
+        raise ValueError(f"batch must be in 1..256, got {batch}")
+    _dev_check(flat_grad)
+    self.env, self.replay, self.net = env, replay, net
+    self.batch, self.gamma, self.flat_grad = int(batch), float(gamma), flat_grad
+    dev, B = env.device, self.batch
+    self.actions = torch.zeros(env.n, dtype=torch.uint8, device=dev)
+    self.idx = torch.zeros(B, dtype=torch.int64, device=dev)
+    self.a = torch.empty(B, dtype=torch.uint8, device=dev)
+    self.r = torch.empty(B, dtype=torch.float32, device=dev)
+    self.t = torch.empty(B, dtype=torch.uint8, device=dev)
+    self.loss = torch.zeros(n_loss, dtype=torch.float32, device=dev)
+    p = lambda x: None if x is None else x.data_ptr()
+    self.buf = L.StepBuffers(p(env.nib), p(self.actions), p(env.frame_bits), p(env.reward), p(env.terminal), p(env.score),
+                             p(self.idx), None, None, p(self.a), p(self.t), p(self.r), p(self.loss), p(flat_grad), None, None, None)
+
+
 class SacStep:
     """One whole step of the SAC loop as a single host call (fb_sac_step): sample the policy -> frame_step -> store + sample the
     minibatch -> (train) the SAC step from the ring -> (polyak > 0) the soft target update.  The results of the separate calls in that
     order; the pointers are bound once."""
 
     def __init__(self, env, replay, net, batch=32, gamma=0.99, polyak=0.005, flat_grad=None):
-        if net.arch != SAC_ARCH:
-            raise ValueError("SacStep needs a SAC net (QNet(..., arch='sac'))")
-        if replay.prioritized:
-            raise ValueError("SacStep trains from a uniform memory only")
-        if getattr(env, "nib", None) is None:
-            raise ValueError("call env.track_state() first: the acting path reads the env kernel's nibble states")
-        if not 1 <= int(batch) <= 256:
-            raise ValueError(f"batch must be in 1..256, got {batch}")
-        _dev_check(flat_grad)
-        self.env, self.replay, self.net = env, replay, net
-        self.batch, self.gamma, self.rho, self.flat_grad = int(batch), float(gamma), check_polyak(polyak, allow_off=True), flat_grad
-        dev, B = env.device, self.batch
-        self.actions = torch.zeros(env.n, dtype=torch.uint8, device=dev)
-        self.idx = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.a = torch.empty(B, dtype=torch.uint8, device=dev)
-        self.r = torch.empty(B, dtype=torch.float32, device=dev)
-        self.t = torch.empty(B, dtype=torch.uint8, device=dev)
-        self.loss = torch.zeros(6, dtype=torch.float32, device=dev)
-        p = lambda x: None if x is None else x.data_ptr()
-        self.buf = L.StepBuffers(p(env.nib), p(self.actions), p(env.frame_bits), p(env.reward), p(env.terminal), p(env.score),
-                                 p(self.idx), None, None, p(self.a), p(self.t), p(self.r), p(self.loss), p(flat_grad), None, None, None)
+        _bind_step(self, "SacStep", SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", env, replay, net, batch, gamma, flat_grad, 6)
+        self.rho = check_polyak(polyak, allow_off=True)
 
     def __call__(self, seed=0, step=0, train=True):
         """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the six loss numbers are self.loss"""
@@ -1353,27 +1340,8 @@ class IqnStep:
     that order; the pointers are bound once."""
 
     def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
-        if net.arch != IQN_ARCH:
-            raise ValueError("IqnStep needs an IQN net (QNet(..., arch='iqn'))")
-        if replay.prioritized:
-            raise ValueError("IqnStep trains from a uniform memory only")
-        if getattr(env, "nib", None) is None:
-            raise ValueError("call env.track_state() first: the acting path reads the env kernel's nibble states")
-        if not 1 <= int(batch) <= 256:
-            raise ValueError(f"batch must be in 1..256, got {batch}")
-        _dev_check(flat_grad)
-        self.env, self.replay, self.net = env, replay, net
-        self.batch, self.gamma, self.double_q, self.flat_grad = int(batch), float(gamma), bool(double_q), flat_grad
-        dev, B = env.device, self.batch
-        self.actions = torch.zeros(env.n, dtype=torch.uint8, device=dev)
-        self.idx = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.a = torch.empty(B, dtype=torch.uint8, device=dev)
-        self.r = torch.empty(B, dtype=torch.float32, device=dev)
-        self.t = torch.empty(B, dtype=torch.uint8, device=dev)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        p = lambda x: None if x is None else x.data_ptr()
-        self.buf = L.StepBuffers(p(env.nib), p(self.actions), p(env.frame_bits), p(env.reward), p(env.terminal), p(env.score),
-                                 p(self.idx), None, None, p(self.a), p(self.t), p(self.r), p(self.loss), p(flat_grad), None, None, None)
+        _bind_step(self, "IqnStep", IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1)
+        self.double_q = bool(double_q)
 
     def __call__(self, epsilon=0.0, seed=0, step=0, train=True):
         """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the loss is self.loss"""
