@@ -119,7 +119,7 @@ def build_parser():
     parser.add_argument("--n-tau-target", type=int, default=None, help="--model iqn: quantile fractions sampled for the target N' (default 8)")
     parser.add_argument("--n-tau-act", type=int, default=None, help="--model iqn: the acting grid K (default 32)")
     parser.add_argument("--cvar", type=float, default=None, help="--model iqn: act on CVaR_ETA, 0 < ETA <= 1 (default 1 = the mean)")
-    parser.add_argument("--double", action="store_true", help="--model iqn: the greedy next action from the online net (Double-DQN's target)")
+    parser.add_argument("--double", action="store_true", help="--model iqn | iqnper: the greedy next action from the online net (Double-DQN's target; --model rainbowiqn sets it)")
     parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper: the softmax temperature (default 0.03)")
     parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9); "
                                                                    "--model sac: the temperature (default 0.2)")
@@ -168,23 +168,27 @@ def sac_kwargs(args, parser):
     return kw
 
 
+IQN_MODELS = ("iqn", "iqnper", "rainbowiqn")             # iqnper: IQN on a prioritized memory; rainbowiqn: iqnper with --double
+
+
 def iqn_kwargs(args, parser):
-    """--model iqn's options as VecIQN's keywords; everything is refused here, by name, before anything touches the GPU"""
+    """--model iqn's (iqnper's, rainbowiqn's: the same) options as VecIQN's keywords; everything is refused here, by name, before anything
+    touches the GPU"""
     given = [n for n, v in (("--n-tau", args.n_tau), ("--n-tau-target", args.n_tau_target), ("--n-tau-act", args.n_tau_act), ("--cvar", args.cvar),
                             ("--double", args.double or None)) if v is not None]
-    if args.model != "iqn":
+    if args.model not in IQN_MODELS:
         if given:
             parser.error(f"{' / '.join(given)} need --model iqn, not --model {args.model}")
         return None
     if not args.vec:
-        parser.error("--model iqn needs --vec: implicit quantile networks run in the vectorised loop only")
+        parser.error(f"--model {args.model} needs --vec: implicit quantile networks run in the vectorised loop only")
     for name, on in (("--noisy", args.noisy), ("--huber", args.huber is not None), ("--n-quantiles", args.n_quantiles is not None),
                      ("--tau / --alpha / --clip", args.tau is not None or args.alpha is not None or args.clip is not None)):
         if on:
-            parser.error(f"{name} is not an option of --model iqn (--n-tau, --n-tau-target, --n-tau-act, --kappa, --cvar, --double, --n-step, "
+            parser.error(f"{name} is not an option of --model {args.model} (--n-tau, --n-tau-target, --n-tau-act, --kappa, --cvar, --double, --n-step, "
                          "--polyak, --max-grad-norm are)")
     from .veciqn import check_args
-    kw = dict(batch=min(32, args.vec), double_q=args.double, n_step=args.n_step, n_tau=8 if args.n_tau is None else args.n_tau,
+    kw = dict(batch=min(32, args.vec), double_q=args.double or args.model == "rainbowiqn", n_step=args.n_step, n_tau=8 if args.n_tau is None else args.n_tau,
               n_tau_next=8 if args.n_tau_target is None else args.n_tau_target, n_tau_act=32 if args.n_tau_act is None else args.n_tau_act,
               kappa=1.0 if args.kappa is None else args.kappa, cvar=1.0 if args.cvar is None else args.cvar,
               polyak=0.0 if args.polyak is None else args.polyak, max_grad_norm=0.0 if args.max_grad_norm is None else args.max_grad_norm)
@@ -193,6 +197,7 @@ def iqn_kwargs(args, parser):
                    1_000_000, 0.03, 0.0, 0.99, 1e-6, kw["max_grad_norm"], None)
     except ValueError as e:
         parser.error(str(e))
+    kw["prioritized"] = args.model != "iqn"
     return kw
 
 

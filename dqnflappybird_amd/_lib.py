@@ -137,6 +137,9 @@ SIGNATURES = {
     "fb_qnet_iqn_train_step": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _vp, _vp],
     "fb_iqn_train_from_replay": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _vp, _vp],
     "fb_iqn_step": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _i, _d, _vp],
+    "fb_qnet_iqn_per_train_step": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _vp, _vp, _vp],
+    "fb_iqn_per_train_from_replay": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _vp, _vp, _vp],
+    "fb_iqn_per_step": [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _i, _d, _vp],
     "fb_qnet_destroy": [_vp],
     "fb_qnet_num_params": [_vp, _vp],
     "fb_qnet_init_params": [_vp, _i, _u64, _vp],

@@ -310,6 +310,7 @@ struct IqnLossArgs {
     const uint8_t *act, *term; const float *rew; double gamma; const float *tau, *tau_next;
     uint32_t seed_lo, seed_hi, step_lo, step_hi;
     float *dl, *gw, *dhf, *dpre, *ctab, *t_out;                  // dl f32[B][4]; gw f32[B][FC]; dpre f32[B N][FC]; ctab f32[B N][64]; t_out f32[B][Np] or NULL
+    const float *isw; float *abs_err;                            // the prioritized form: both f32[B], both set (the weights in, l_b out); else both NULL
 };
 struct IqnGradArgs { int B, FC, A, N; NetOff off; IqnOff io; const float *dl, *gw, *dhf, *dpre, *ctab; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; };
 void fb_iqn_launch_fold(hipStream_t st, const void *args);
@@ -322,6 +323,9 @@ int fb_qnet_is_iqn(fb_qnet_t h);              // 1: an IQN net (fb_qnet_create_i
 int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int batch, double gamma, const char *who);
 int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int batch, const FbRingSrc *ring, const float *tau, const float *tau_next, uint64_t seed,
                            uint64_t step, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
+// the same behind fb_iqn_per_train_from_replay's checks: the prioritized form (isw / abs_err f32[batch], both non-NULL)
+int fb_qnet_iqn_per_train_ring(fb_qnet_t h, int double_q, int batch, const FbRingSrc *ring, const float *isw, const float *tau, const float *tau_next,
+                               uint64_t seed, uint64_t step, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream);
 // ---- the refusal rules of the ring-fed entry points (fb_common.hip): made before any counter moves or any launch; FB_OK, else the error
 // code with fb_last_error naming `who`
 int fb_check_q_net(fb_qnet_t net, const char *who, bool steps);       // no AC / SAC / IQN net (steps: `who` steps the envs too)

@@ -5,7 +5,8 @@
 //   iqn_fold_kernel   phibar over the acting grid and the fold block [b_fc1 | phibar * W_q | b_q] of one net: what every forward-only path reads
 //   iqn_head_kernel   theta at the caller's tau (fb_qnet_forward_iqn); one workgroup per state
 //   iqn_loss_kernel   training, launch 1 of 2: per sample a*, the target quantiles, theta, the pairwise quantile Huber loss, d theta, then the
-//                     dhf row, the W_q-gradient row, the embedding's pre-activation gradients and the cosine rows; one workgroup per sample
+//                     dhf row, the W_q-gradient row, the embedding's pre-activation gradients and the cosine rows; one workgroup per sample.
+//                     Its <.., true> instantiation is the prioritized form: importance weights in, the per-sample loss out as the priority
 //   iqn_grad_kernel   training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_q, W_e, b_e; workgroup 0: b_q, the loss, Adam's tick
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
 // A lane owns a unit k and keeps W_e[:, k] in 64 registers; the cosine rows sit in LDS and are read as broadcasts; phi is recomputed in the
@@ -164,7 +165,9 @@ __global__ __launch_bounds__(256) void iqn_head_kernel(IqnHeadArgs H) {
 
 // ---- training, launch 1 of 2: one workgroup per sample.  Rows b / B + b / 2 B + b of the fc1 partial sums: s and s' through the online
 // net, s' through the target net.  dl[b][4]: the action read, sum_i d theta_i, l_b, 0.
-template <int AT>
+// PW, the prioritized form (fb_qnet_iqn_per_train_step): w_b = isw[b] is multiplied into d theta_i LAST, dl[b][2] takes w_b l_b and
+// abs_err[b] the unweighted l_b (the priority); w = 1 leaves the bits of the uniform form.
+template <int AT, bool PW>
 __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
     __shared__ float ct[2 * IQN_MAXT * IQN_E];                    // the cosine rows of tau (N of them), then of tau' (N')
     __shared__ float part[4 * IQN_MAXT];
@@ -185,6 +188,8 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
     const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;   // (an action past the head reads the last one: stays in bounds)
     const float rf = L.rew[b];
     const bool done = L.term[b] != 0;
+    [[maybe_unused]] float wb = 1.f;
+    if constexpr (PW) wb = L.isw[b];
     // a*: the first maximum of the plain head over the fold (every wave forms the same bits)
     float qa[AT];
     iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
@@ -211,13 +216,20 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
             g += (w * fminf(fmaxf(u, -kap), kap)) / kap;
         }
         rowl[tid] = l;
-        dth[tid] = (-(g / (float)Np)) / (float)B;
+        if constexpr (PW) dth[tid] = ((-(g / (float)Np)) / (float)B) * wb;
+        else dth[tid] = (-(g / (float)Np)) / (float)B;
     }
     __syncthreads();
     if (tid == 0) {
         float l = 0.f, sd = 0.f;
         for (int i = 0; i < N; i++) { l += rowl[i]; sd += dth[i]; }
-        *reinterpret_cast<float4 *>(L.dl + (size_t)b * 4) = make_float4((float)ab, sd, l / (float)Np, 0.f);
+        if constexpr (PW) {
+            const float lb = l / (float)Np;
+            *reinterpret_cast<float4 *>(L.dl + (size_t)b * 4) = make_float4((float)ab, sd, wb * lb, 0.f);
+            L.abs_err[b] = lb;
+        } else {
+            *reinterpret_cast<float4 *>(L.dl + (size_t)b * 4) = make_float4((float)ab, sd, l / (float)Np, 0.f);
+        }
     }
     for (int q = tid; q < N * IQN_E; q += 256) L.ctab[(size_t)b * N * IQN_E + q] = ct[q];
     // backward: phi recomputed per unit; s_k = sum_i d theta_i phi_ik
@@ -323,6 +335,7 @@ __global__ __launch_bounds__(256) void iqn_draw_kernel(long long total, int n, u
 template <class F> void with_actions(int A, F f) {
     if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
 }
+template <class F> void with_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 }  // namespace
 
 void fb_iqn_launch_fold(hipStream_t st, const void *args) {
@@ -340,7 +353,11 @@ void fb_iqn_launch_head(hipStream_t st, const void *args) {
 void fb_iqn_launch_loss(hipStream_t st, const void *args) {
     IqnLossArgs L;
     memcpy(&L, args, sizeof(L));
-    with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(iqn_loss_kernel<decltype(a)::value>, dim3(L.B), dim3(256), 0, st, L); });
+    with_actions(L.A, [&](auto a) {           // (isw set: the prioritized form, which also writes abs_err)
+        with_bool(L.isw != nullptr, [&](auto pw) {
+            hipLaunchKernelGGL((iqn_loss_kernel<decltype(a)::value, decltype(pw)::value>), dim3(L.B), dim3(256), 0, st, L);
+        });
+    });
 }
 
 void fb_iqn_launch_grad(hipStream_t st, const void *args) {
@@ -406,4 +423,61 @@ extern "C" int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     if (train) rc = fb_iqn_train_from_replay(replay, net, double_q, batch, b->idx, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss, nullptr,
                                              b->flat_grad, stream);
     return rc;
+}
+
+// ---- prioritized replay (include/fbdqn.h, the prioritized IQN block): calls of their own, the memory's kind never switches what a call does
+// the checks of the two ring-fed prioritized calls on the memory: a prioritized one, at any n-step view, whose gamma the caller's is and whose
+// tree holds a leaf once `pushes_ahead` more pushes are counted (pushes_ahead < 0: a store-only step, which samples nothing)
+static int iqn_per_check_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who) {
+    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (fb_iqn_train_from_replay / fb_iqn_step take a uniform one)", who);
+    const int rc = fb_replay_check_gamma(replay, gamma, who);
+    return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
+}
+
+extern "C" int fb_iqn_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, const float *isw,
+                                            uint8_t *a_out, float *r_out, uint8_t *t_out, const float *tau, const float *tau_next, uint64_t seed,
+                                            uint64_t step, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    const char *who = "fb_iqn_per_train_from_replay";
+    FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
+    FB_REQUIRE(isw && abs_err, "%s: the prioritized step needs the importance weights (isw) and abs_err", who);
+    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
+    int rc = iqn_per_check_memory(replay, gamma, 0, who);
+    if (rc != FB_OK) return rc;
+    rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    FbRingSrc ring;
+    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
+    if (rc != FB_OK) return rc;
+    return fb_qnet_iqn_per_train_ring(net, double_q, batch, &ring, isw, tau, tau_next, seed, step, fb_replay_bootstrap_gamma(replay, gamma), loss, abs_err,
+                                      q_target, flat_grad, stream);
+}
+
+extern "C" int fb_iqn_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch,
+                               float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
+    const char *who = "fb_iqn_per_step";
+    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
+    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "%s: NULL buffer", who);
+    FB_REQUIRE(!train || (b->idx && b->a && b->r && b->t && b->loss), "%s: a training step needs the idx / a / r / t / loss buffers", who);
+    FB_REQUIRE(!train || (b->isw && b->isw32 && b->abs_err), "%s: the prioritized step needs the isw / isw32 / abs_err buffers", who);
+    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
+    // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
+    int rc = iqn_per_check_memory(replay, gamma, train ? 1 : -1, who);
+    if (rc != FB_OK) return rc;
+    rc = fb_check_step_handles(env, replay, net, n_envs, who);
+    if (rc == FB_OK) rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
+    rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, stream);
+    if (rc != FB_OK || !train) return rc;
+    // Memory.sample -> the weighted loss -> Memory.batch_update, in line on `stream` at every env count; abs_err keeps l_b as the loss left it
+    rc = fb_replay_sample_f32(replay, batch, nullptr, b->idx, b->isw, b->isw32, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_iqn_per_train_from_replay(replay, net, double_q, batch, b->idx, b->isw32, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss,
+                                      b->abs_err, nullptr, b->flat_grad, stream);
+    if (rc != FB_OK) return rc;
+    return fb_replay_update_priorities_keep(replay, batch, b->idx, b->abs_err, stream);
 }

@@ -4833,6 +4833,7 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         L.tau = p.iqn_tau; L.tau_next = p.iqn_tau_next;
         put_seed_words(L, p.seed, p.step);
         L.dl = h->ac_dl; L.gw = h->ac_xs; L.dhf = h->dhf; L.dpre = h->iqn_dpre; L.ctab = h->iqn_ctab; L.t_out = p.y;
+        L.isw = p.isw; L.abs_err = p.abs_err;    // (both set: the prioritized form; the uniform calls leave both NULL)
         fb_iqn_launch_loss(c.st, &L);
         const IqnGradArgs gA{B, FC, h->A, h->iqn_n, h->off, h->iqn_off, h->ac_dl, h->ac_xs, h->dhf, h->iqn_dpre, h->iqn_ctab, p.G, p.loss, h->gmax,
                              reinterpret_cast<FbAdamHead *>(h->adam), p.tick};
@@ -5867,6 +5868,30 @@ int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int B, const FbRingSrc *ri
     const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_iqn_train_from_replay");
     if (rc != FB_OK) return rc;
     Plan p = iqn_train_plan(h, double_q, B, nullptr, ring->a, ring->r, nullptr, ring->t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, ring);
+    return run_train(h, p, stream);
+}
+
+// the prioritized form of the two calls above: the same plan with the importance weights in and the per-sample loss out (the loss launch's
+// weighted instantiation, fb_iqn.hip)
+extern "C" int fb_qnet_iqn_per_train_step(fb_qnet_t h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
+                                          const uint8_t *t, const float *isw, const float *tau, const float *tau_next, uint64_t seed, uint64_t step,
+                                          double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && s && a && r && s2 && t && loss, "fb_qnet_iqn_per_train_step: NULL argument");
+    FB_REQUIRE(isw && abs_err, "fb_qnet_iqn_per_train_step: the prioritized step needs the importance weights (isw) and abs_err");
+    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_qnet_iqn_per_train_step");
+    if (rc != FB_OK) return rc;
+    Plan p = iqn_train_plan(h, double_q, B, s, a, r, s2, t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, nullptr);
+    p.isw = isw; p.abs_err = abs_err;
+    return run_train_gathered(h, p, B, stream);
+}
+
+int fb_qnet_iqn_per_train_ring(fb_qnet_t h, int double_q, int B, const FbRingSrc *ring, const float *isw, const float *tau, const float *tau_next,
+                               uint64_t seed, uint64_t step, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss && isw && abs_err, "fb_iqn_per_train_from_replay: NULL argument");
+    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_iqn_per_train_from_replay");
+    if (rc != FB_OK) return rc;
+    Plan p = iqn_train_plan(h, double_q, B, nullptr, ring->a, ring->r, nullptr, ring->t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, ring);
+    p.isw = isw; p.abs_err = abs_err;
     return run_train(h, p, stream);
 }
 

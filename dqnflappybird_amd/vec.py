@@ -900,6 +900,28 @@ class QNet:
                                                L.current_stream()), "fb_qnet_iqn_train_step")
         return loss, y
 
+    def iqn_per_train_step(self, s, a, r, s2, t, isw, gamma=0.99, double_q=False, tau=None, tau_next=None, seed=0, step=0, flat_grad=None,
+                           want_target=True):
+        """iqn_train_step with importance weights isw f32[B] (fb_qnet_iqn_per_train_step): the loss is mean_b w_b l_b, the gradient that of
+        l_b / B times w_b; abs_err[b] = l_b, without the weight, is the priority.  isw = 1 gives iqn_train_step's bits.
+        -> (loss f32[1], abs_err f32[B], q_target f32[B, n_tau_next] or None)"""
+        self._need_iqn("iqn_per_train_step")
+        _dev_check(s, a, r, s2, t, isw, flat_grad, tau, tau_next)
+        for name, x in (("s", s), ("s2", s2)):
+            if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (80, 80, 4) or x.shape[0] != s.shape[0]:
+                raise ValueError(f"{name} must be uint8[B,80,80,4]")
+        B = s.shape[0]
+        N, Np = self.iqn()[:2]
+        check_iqn_batch(B, a, r, t, tau, tau_next, N, Np, flat_grad, self.n_params)
+        check_isw(B, isw)
+        loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        ae = torch.empty(B, dtype=torch.float32, device=self.device)
+        y = torch.empty((B, Np), dtype=torch.float32, device=self.device) if want_target else None
+        L.check(L.lib().fb_qnet_iqn_per_train_step(self.h, int(bool(double_q)), B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), L.ptr(isw),
+                                                   L.ptr(tau), L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(ae),
+                                                   L.ptr(y), L.ptr(flat_grad), L.current_stream()), "fb_qnet_iqn_per_train_step")
+        return loss, ae, y
+
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):
         if not self.noisy:
@@ -1121,12 +1143,20 @@ def check_iqn_batch(B, a, r, t, tau, tau_next, n_tau, n_tau_next, flat_grad, n_p
     _check_flat_grad(flat_grad, n_params)
 
 
-def _ring_call(name, replay, net, arch, need, reads, idx, n_loss, *tensors):
-    """what the four *_train_from_replay calls of the newer families begin with: the net's arch, a uniform memory, device tensors, idx's
-    dtype -> (B, dev, a u8[B], loss f32[n_loss]), the last two for the library to fill"""
+def check_isw(B, isw):
+    """the shape check of the prioritized IQN calls' importance weights, on the host"""
+    if isw is None or isw.dtype != torch.float32 or tuple(isw.shape) != (B,) or not isw.is_contiguous():
+        raise ValueError(f"isw must be a contiguous float32[{B}] (the prioritized step needs the importance weights)")
+
+
+def _ring_call(name, replay, net, arch, need, reads, idx, n_loss, *tensors, prioritized=False):
+    """what the four *_train_from_replay calls of the newer families begin with: the net's arch, a uniform memory (prioritized=True: a
+    prioritized one), device tensors, idx's dtype -> (B, dev, a u8[B], loss f32[n_loss]), the last two for the library to fill"""
     if net.arch != arch:
         raise ValueError(f"{name} needs {need}")
-    if replay.prioritized:
+    if prioritized and not replay.prioritized:
+        raise ValueError(f"{name} {reads} a prioritized memory only")
+    if replay.prioritized and not prioritized:
         raise ValueError(f"{name} {reads} a uniform memory only")
     _dev_check(idx, *tensors)
     if idx.dtype != torch.int64:
@@ -1161,6 +1191,25 @@ def iqn_train_from_replay(replay, net, idx, gamma=0.99, double_q=False, tau=None
                                              L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(y), L.ptr(flat_grad),
                                              L.current_stream()), "fb_iqn_train_from_replay")
     return (loss, a, r, t, y) if want_target else (loss, a, r, t)
+
+
+def iqn_per_train_from_replay(replay, net, idx, isw, gamma=0.99, double_q=False, tau=None, tau_next=None, seed=0, step=0, flat_grad=None,
+                              want_target=False):
+    """QNet.iqn_per_train_step on the transitions at the SumTree leaves idx of a prioritized memory (any n-step view; gamma must be the
+    memory's), read from its frame ring in place (fb_iqn_per_train_from_replay); isw f32[B]: replay.sample's importance weights
+    -> (loss f32[1], a u8[B], r f32[B], t u8[B][, q_target f32[B, n_tau_next]], abs_err f32[B])"""
+    B, dev, a, loss = _ring_call("iqn_per_train_from_replay", replay, net, IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
+                                 flat_grad, tau, tau_next, isw, prioritized=True)
+    N, Np = net.iqn()[:2]
+    check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
+    check_isw(B, isw)
+    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    ae = torch.empty(B, dtype=torch.float32, device=dev)
+    y = torch.empty((B, Np), dtype=torch.float32, device=dev) if want_target else None
+    L.check(L.lib().fb_iqn_per_train_from_replay(replay.h, net.h, int(bool(double_q)), B, L.ptr(idx), L.ptr(isw), L.ptr(a), L.ptr(r), L.ptr(t),
+                                                 L.ptr(tau), L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(ae), L.ptr(y),
+                                                 L.ptr(flat_grad), L.current_stream()), "fb_iqn_per_train_from_replay")
+    return (loss, a, r, t, y, ae) if want_target else (loss, a, r, t, ae)
 
 
 def sac_train_from_replay(replay, net, idx, gamma=0.99, flat_grad=None, want_target=False):
@@ -1293,11 +1342,14 @@ class AcRolloutStep:
         return self.actions
 
 
-def _bind_step(self, name, arch, need, env, replay, net, batch, gamma, flat_grad, n_loss):
-    """what SacStep and IqnStep set up alike: the checks, the step's own tensors (loss: f32[n_loss]) and the bound pointers"""
+def _bind_step(self, name, arch, need, env, replay, net, batch, gamma, flat_grad, n_loss, prioritized=False):
+    """what SacStep, IqnStep and IqnPerStep set up alike: the checks, the step's own tensors (loss: f32[n_loss]) and the bound pointers;
+    prioritized: a prioritized memory instead of a uniform one, and Memory.sample's weights (f64 and f32) and abs_err beside them"""
     if net.arch != arch:
         raise ValueError(f"{name} needs {need}")
-    if replay.prioritized:
+    if prioritized and not replay.prioritized:
+        raise ValueError(f"{name} trains from a prioritized memory only")
+    if replay.prioritized and not prioritized:
         raise ValueError(f"{name} trains from a uniform memory only")
     if getattr(env, "nib", None) is None:
         raise ValueError("call env.track_state() first: the acting path reads the env kernel's nibble states")
@@ -1313,9 +1365,13 @@ def _bind_step(self, name, arch, need, env, replay, net, batch, gamma, flat_grad
     self.r = torch.empty(B, dtype=torch.float32, device=dev)
     self.t = torch.empty(B, dtype=torch.uint8, device=dev)
     self.loss = torch.zeros(n_loss, dtype=torch.float32, device=dev)
+    self.isw = torch.zeros(B, dtype=torch.float64, device=dev) if prioritized else None
+    self.isw32 = torch.zeros(B, dtype=torch.float32, device=dev) if prioritized else None
+    self.abs_err = torch.zeros(B, dtype=torch.float32, device=dev) if prioritized else None
     p = lambda x: None if x is None else x.data_ptr()
     self.buf = L.StepBuffers(p(env.nib), p(self.actions), p(env.frame_bits), p(env.reward), p(env.terminal), p(env.score),
-                             p(self.idx), None, None, p(self.a), p(self.t), p(self.r), p(self.loss), p(flat_grad), None, None, None)
+                             p(self.idx), None, None, p(self.a), p(self.t), p(self.r), p(self.loss), p(flat_grad),
+                             p(self.isw), p(self.isw32), p(self.abs_err))
 
 
 class SacStep:
@@ -1347,6 +1403,22 @@ class IqnStep:
         """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the loss is self.loss"""
         L.check(L.lib().fb_iqn_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(self.double_q), self.batch,
                                     float(epsilon), int(seed), int(step), int(bool(train)), self.gamma, L.current_stream()), "fb_iqn_step")
+        return self.actions
+
+
+class IqnPerStep:
+    """IqnStep on a prioritized memory (fb_iqn_per_step): epsilon-greedy on the folded head -> frame_step -> store -> (train) Memory.sample
+    -> the weighted IQN step from the ring -> Memory.batch_update with the per-sample loss, all in line on one stream.  The results of the
+    separate calls in that order; it owns idx, isw (f64), isw32 and abs_err (l_b as the loss left it)."""
+
+    def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
+        _bind_step(self, "IqnPerStep", IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1, prioritized=True)
+        self.double_q = bool(double_q)
+
+    def __call__(self, epsilon=0.0, seed=0, step=0, train=True):
+        """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the loss is self.loss"""
+        L.check(L.lib().fb_iqn_per_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(self.double_q), self.batch,
+                                        float(epsilon), int(seed), int(step), int(bool(train)), self.gamma, L.current_stream()), "fb_iqn_per_step")
         return self.actions
 
 

@@ -8,6 +8,10 @@
 
 One net, one GPU, a uniform memory at any n-step view; include/fbdqn.h pins the semantics, DESIGN.md section 19 the design.  Acting costs
 what a plain net's does: the mean over the acting grid of tau folds into the head (QNet.set_iqn_risk scales the grid: CVaR).
+
+prioritized=True: a prioritized memory (its n fixed at creation) and vec.IqnPerStep -- store -> Memory.sample -> the IQN step with the
+importance weights -> Memory.batch_update with the per-sample loss, still one host call.  With double_q and n_step = 3: "Rainbow-IQN"
+without the dueling and the noisy head.
 """
 import numpy as np
 
@@ -52,29 +56,46 @@ def check_args(n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step,
     return n, b, N, Np, K, ka, eta, ns, rho, rti, ob, ex, e0, e1, g, l, check_max_grad_norm(max_grad_norm), cap
 
 
+def check_prioritized(prioritized):
+    """VecIQN's `prioritized` setting, checked apart from check_args (whose positional parameters stay as they are) -> bool"""
+    if not isinstance(prioritized, (bool, np.bool_)):
+        raise ValueError(f"prioritized must be True or False, got {prioritized!r}")
+    return bool(prioritized)
+
+
+def replay_kind(prioritized):
+    return "prioritized" if prioritized else "uniform"
+
+
 class VecIQN:
     def __init__(self, n_envs, batch=32, double_q=False, n_step=1, n_tau=8, n_tau_next=8, n_tau_act=32, kappa=1.0, cvar=1.0, polyak=0.0,
                  replace_target_iter=500, observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99, lr=1e-6,
-                 max_grad_norm=0, fc_width=512, seed=0, capacity=None):
+                 max_grad_norm=0, fc_width=512, seed=0, capacity=None, prioritized=False):
         """n_envs games; every step trains one minibatch of `batch` transitions (<= n_envs, <= 256) once more than `observe` steps have
         filled the memory.  n_tau / n_tau_next: the tau sampled per transition for the online / target quantiles; n_tau_act: the acting
         grid; kappa: the quantile Huber threshold; cvar = eta in (0, 1]: act on CVaR_eta (1 = the mean).  double_q: a* from the online
         net.  n_step > 1: n-step returns.  The epsilon schedule (observe / explore / initial / final) and the periodic target copy are
-        VecBrain's; polyak > 0 replaces the copy by soft updates; lr is Adam's; max_grad_norm=G > 0 clips the gradient's global norm."""
+        VecBrain's; polyak > 0 replaces the copy by soft updates; lr is Adam's; max_grad_norm=G > 0 clips the gradient's global norm.
+        prioritized: train from a prioritized memory (importance-weighted loss, the per-sample loss as the priority)."""
         (self.n, self.batch, self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar, self.n_step, self.polyak, self.replace_target_iter,
          self.observe, self.explore, self.initial_epsilon, self.final_epsilon, self.gamma, self.lr, self.max_grad_norm, self.capacity) = check_args(
             n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step, polyak, replace_target_iter, observe, explore, initial_epsilon,
             final_epsilon, gamma, lr, max_grad_norm, capacity)
-        from .vec import IqnStep, QNet, VecGameState, VecReplay
+        self.prioritized = check_prioritized(prioritized)
+        from .vec import QNet, VecGameState, VecReplay
         self.double_q = bool(double_q)
         self.seed = int(seed)
         self.fc_width = int(fc_width)
         self.epsilon = self.initial_epsilon
         self.env = VecGameState(self.n, seed=self.seed)
-        self.replay = VecReplay(self.capacity, self.n)
-        self.replay.seed(self.seed)
-        if self.n_step > 1:
-            self.replay.set_n_step(self.n_step, self.gamma)
+        if self.prioritized:                                 # (a prioritized memory gets its n at creation; its generator is numpy's)
+            self.replay = VecReplay(self.capacity, self.n, prioritized=True, n_step=self.n_step, gamma=self.gamma)
+            self.replay.seed(self.seed)
+        else:
+            self.replay = VecReplay(self.capacity, self.n)
+            self.replay.seed(self.seed)
+            if self.n_step > 1:
+                self.replay.set_n_step(self.n_step, self.gamma)
         self.net = QNet(2, self.fc_width, "iqn", max_batch=max(self.n, self.batch), n_tau=self.n_tau, n_tau_next=self.n_tau_next,
                         n_tau_act=self.n_tau_act, kappa=self.kappa)
         self.net.set_hparams(lr=self.lr)
@@ -88,9 +109,13 @@ class VecIQN:
         self.env.observe()
         self.replay.reset(self.env.frame_bits)
         self.stats = self.env.track_stats()
-        self.one_step = IqnStep(self.env, self.replay, self.net, self.batch, self.gamma, self.double_q)
-        self.loss = self.one_step.loss
+        self._bind()
         self.timeStep = 0                                    # env steps per env so far: the key of the epsilon and tau draws
+
+    def _bind(self):
+        from .vec import IqnPerStep, IqnStep
+        self.one_step = (IqnPerStep if self.prioritized else IqnStep)(self.env, self.replay, self.net, self.batch, self.gamma, self.double_q)
+        self.loss = self.one_step.loss
 
     def step(self):
         """one vector step -> the loss f32[1] (device)"""
@@ -124,7 +149,8 @@ class VecIQN:
 
     def save(self, path):
         """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory
-        (with its generator), the counters, epsilon and the settings; `head` = 'iqn' tells the file from the other loops'"""
+        (with its generator and, prioritized, its tree), the counters, epsilon and the settings; `head` = 'iqn' tells the file from the
+        other loops', `prioritized` the memory's kind (a file without the key is a uniform one's)"""
         host = lambda t: t.cpu().numpy()
         m, v, pows = self.net.adam_state()
         np.savez(self._npz(path), head=np.array([IQN_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
@@ -132,20 +158,24 @@ class VecIQN:
                  scalars=np.array([self.timeStep, self.seed, self.n, self.batch, self.fc_width, self.observe, self.explore, self.n_step,
                                    int(self.double_q), self.replace_target_iter], np.int64),
                  iqn=np.array([self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar], np.float64),
+                 prioritized=np.array([int(self.prioritized)], np.int64),
                  settings=np.array([self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon],
                                    np.float64),
                  env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob())
 
     def load(self, path):
         """the inverse of save(), into a VecIQN made with the same n_envs, batch, fc_width, n_step, (n_tau, n_tau_next, n_tau_act, kappa),
-        capacity and seed; the other settings of the file replace this object's"""
+        capacity, seed and memory kind (prioritized or not); the other settings of the file replace this object's"""
         import torch
-        from .vec import IqnStep
         from .vecbrain import checkpoint_head
         z = np.load(self._npz(path))
         head = checkpoint_head(z)
         if head != IQN_HEAD:
             raise ValueError(f"checkpoint {path} holds a {head} head (another loop's), this is a VecIQN (head {IQN_HEAD!r})")
+        per = bool(int(z["prioritized"][0])) if "prioritized" in z.files else False
+        if per != self.prioritized:
+            raise ValueError(f"checkpoint {path} was written by a VecIQN with a {replay_kind(per)} memory, this VecIQN has a "
+                             f"{replay_kind(self.prioritized)} one (prioritized={self.prioritized})")
         sc = [int(x) for x in z["scalars"]]
         if (sc[2], sc[3], sc[4], sc[7]) != (self.n, self.batch, self.fc_width, self.n_step):
             raise ValueError(f"checkpoint {path} was written with (n_envs, batch, fc_width, n_step) = {(sc[2], sc[3], sc[4], sc[7])}, this "
@@ -173,8 +203,7 @@ class VecIQN:
         self.stats[...] = dev(z["stats"])
         self.replay.load_state_blob(z["replay"])
         self.timeStep = sc[0]
-        self.one_step = IqnStep(self.env, self.replay, self.net, self.batch, self.gamma, self.double_q)
-        self.loss = self.one_step.loss
+        self._bind()
         torch.cuda.synchronize()
 
     def run(self, steps, log_every=1000):

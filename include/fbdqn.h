@@ -797,6 +797,33 @@ int fb_qnet_iqn_train_step(fb_qnet_t h, int double_q, int batch, const uint8_t *
 int fb_iqn_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, uint8_t *a_out, float *r_out,
                              uint8_t *t_out, const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma,
                              float *loss /*f32[1]*/, float *q_target, float *flat_grad, void *stream);
+/* ------------------------------------------------------------------ prioritized IQN: the three calls above with importance weights
+ * Calls of their own -- the memory's kind never switches what one of the three calls above does, they keep refusing a prioritized memory.
+ * With double_q = 1 on an n-step prioritized memory (fb_replay_create_nstep) this is the non-dueling "Rainbow-IQN" configuration.
+ *   train step  fb_qnet_iqn_per_train_step (gathered) / fb_iqn_per_train_from_replay (ring-fed; idx are SumTree leaf indices): the IQN train
+ *               step above -- a*, T, the tau draws, theta, l_b unchanged -- with w_b = isw[b]:
+ *                 dl_b/dtheta_i = ((-(sum_j ...) / N') / B) * w_b      the weight multiplied LAST, as FB_ALGO_QR_PER forms it
+ *                 loss[0] = (sum_b w_b l_b) / B over ascending b       abs_err[b] = l_b, WITHOUT the weight (>= 0): the priority
+ *               w = 1 gives the uniform call's loss, T and gradient bit for bit.  isw / abs_err f32[batch], both required.  No atomics: equal
+ *               inputs give equal bits.  The gathered and the ring-fed call agree bit for bit; an n-step memory as above (the memory's gamma,
+ *               Gamma = gamma^n)
+ *   loop step   fb_iqn_per_step = fb_qnet_act_nib(epsilon) -> fb_env_step -> fb_replay_push -> if train: fb_replay_sample into b->idx / b->isw /
+ *               b->isw32 -> fb_iqn_per_train_from_replay(b->isw32, tau from (seed, step), b->loss, b->abs_err, b->flat_grad) ->
+ *               Memory.batch_update(b->idx, b->abs_err); those calls in that order on `stream`, after every check of all of them, their
+ *               results bit for bit.  Memory.batch_update runs IN LINE at every env count: no side stream, no sample-ahead, no riders (what
+ *               fb_vec_step's prioritized step does from 4096 envs on is not done here).  When it returns b->abs_err holds l_b as the loss
+ *               left it, as fb_vec_step's prioritized step leaves |TD error| (see fb_step_buffers).  It pushes: not capturable
+ *   refused     FB_ERR_INVALID before any launch, push or counter change: a uniform memory; a net that is not an IQN net; NULL isw / abs_err
+ *               (a training fb_iqn_per_step: b->isw, b->isw32, b->abs_err); the batch, double_q and gamma rules above; an n_envs that is
+ *               not the handles'.  FB_ERR_STATE: an n-step prioritized memory whose tree is still empty when the step would sample. */
+int fb_qnet_iqn_per_train_step(fb_qnet_t h, int double_q, int batch, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
+                               const uint8_t *t, const float *isw /*f32[B]*/, const float *tau, const float *tau_next, uint64_t seed,
+                               uint64_t step, double gamma, float *loss /*f32[1]*/, float *abs_err /*f32[B]*/, float *q_target,
+                               float *flat_grad, void *stream);
+int fb_iqn_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, const float *isw /*f32[B]*/,
+                                 uint8_t *a_out, float *r_out, uint8_t *t_out, const float *tau, const float *tau_next, uint64_t seed,
+                                 uint64_t step, double gamma, float *loss /*f32[1]*/, float *abs_err /*f32[B]*/, float *q_target,
+                                 float *flat_grad, void *stream);
 
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);
@@ -906,7 +933,7 @@ typedef struct {
     uint8_t *s, *s2, *a, *t; float *r;              /* gathered minibatch: u8[B,80,80,4] x2, u8[B], u8[B], f32[B] */
     float *loss;                                    /* f32[1] out */
     float *flat_grad;                               /* f32[n_params] or NULL */
-    /* prioritized replay (algo = FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 and QR _PER algos) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
+    /* prioritized replay (algo = FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 and QR _PER algos; fb_iqn_per_step) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
      * float32 placeholder takes them (f32[B]), and the |TD errors| Memory.batch_update receives (f32[B]).
      * With the reference-order tree and 4096 envs or more Memory.batch_update of a step runs on the memory's own side stream, beside the NEXT step's acting
      * forward (its result is first needed by that step's Memory.store, which follows it there): idx and abs_err are read after
@@ -944,6 +971,10 @@ int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_b
  * training step a, r, t, loss (f32[1]) and flat_grad (or NULL). */
 int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
                 uint64_t seed, uint64_t step, int train, double gamma, void *stream);
+/* The vector step of an IQN net on a prioritized memory (the prioritized IQN block above pins it): the buffers fb_iqn_step reads, and for a
+ * training step isw, isw32 and abs_err as well. */
+int fb_iqn_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
+                    uint64_t seed, uint64_t step, int train, double gamma, void *stream);
 
 /* fb_replay_gather + fb_qnet_train_step WITHOUT the gathered copies (BrainDQN.py:197-223 from the indices on): the minibatch is
  * described by its indices, the conv trunk reads the replay's 1-bit frames directly (5 x 800 B per transition instead of writing and

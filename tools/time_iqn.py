@@ -1,7 +1,8 @@
 """What IQN costs: us per fb_iqn_step against fb_vec_step of 'qr' (a QR net, N = 51) and of 'double' (a plain net) under the one-stream
 schedule (fb_vec_step_set_schedule(0)) at the same env count; us per train step alone (exported gradient) of the three; and us per
 acting forward (act_nib) of an IQN net against a plain net's, which should differ by nothing: the fold is refreshed behind Adam, not
-on the acting path.
+on the acting path.  The prioritized forms run beside them on prioritized memories of the same capacity: fb_iqn_per_step and fb_vec_step
+of 'qrper' -- over the uniform step they pay Memory.store's tree part, Memory.sample and Memory.batch_update.
 
     python tools/time_iqn.py [--envs 256,1024,4096] [--batch 32] [--steps 300] [--warmup 100] [--repeats 5] [--out FILE]
 
@@ -19,22 +20,26 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from dqnflappybird_amd import _lib as L  # noqa: E402
-from dqnflappybird_amd.vec import IqnStep, QNet, VecGameState, VecReplay, VecStep, iqn_train_from_replay, train_from_replay  # noqa: E402
+from dqnflappybird_amd.vec import (IqnPerStep, IqnStep, QNet, VecGameState, VecReplay, VecStep, iqn_per_train_from_replay,  # noqa: E402
+                                   iqn_train_from_replay, train_from_replay)
 from tools.time_a2c import launch_floor, timed  # noqa: E402
 
-CONFIGS = {"fb_iqn_step (N 8, N' 8, K 32)": ("iqn", None), "fb_vec_step qr (N 51)": ("qr", "qr"), "fb_vec_step double": ("plain", "double")}
+CONFIGS = {"fb_iqn_step (N 8, N' 8, K 32)": ("iqn", None), "fb_iqn_per_step (N 8, N' 8, K 32)": ("iqn", "per"), "fb_vec_step qr (N 51)": ("qr", "qr"),
+           "fb_vec_step qrper (N 51)": ("qr", "qrper"), "fb_vec_step double": ("plain", "double")}
+CAPACITY = 1_000_000
 
 
 def pipeline(n_envs, arch, algo, batch):
     env = VecGameState(n_envs, seed=1)
     net = QNet(2, 512, arch, max_batch=max(n_envs, 256))
-    rep = VecReplay(1_000_000, n_envs)
-    rep.seed(3, "cpython")
+    per = algo in ("per", "qrper")                   # (a prioritized memory: the numpy generator, the reference-order tree)
+    rep = VecReplay(CAPACITY, n_envs, prioritized=per)
+    rep.seed(3, None if per else "cpython")
     net.init_params(5, which=0); net.init_params(6, which=1)
     net.set_hparams(lr=1e-6)
     env.track_state(); env.observe(); rep.reset(env.frame_bits)
-    step = IqnStep(env, rep, net, batch, 0.99) if arch == "iqn" else VecStep(env, rep, net, batch, algo, 0.99)
-    return dict(env=env, net=net, rep=rep, step=step, arch=arch, algo=algo, k=0)
+    step = (IqnPerStep if per else IqnStep)(env, rep, net, batch, 0.99) if arch == "iqn" else VecStep(env, rep, net, batch, algo, 0.99)
+    return dict(env=env, net=net, rep=rep, step=step, arch=arch, algo=algo, per=per, k=0)
 
 
 def one(p):
@@ -87,13 +92,20 @@ def main():
             idx = (torch.arange(a.batch, dtype=torch.int64) * 7).cuda()
             grads = {c: torch.zeros(p["net"].n_params, dtype=torch.float32, device="cuda") for c, p in pipes.items()}
 
+            leaf, ones = idx + (CAPACITY - 1), torch.ones(a.batch, dtype=torch.float32, device="cuda")      # (a prioritized memory is read at its leaves)
+
             def train_fn(c, p):
+                if p["arch"] == "iqn" and p["per"]:
+                    return lambda: iqn_per_train_from_replay(p["rep"], p["net"], leaf, ones, 0.99, seed=2, step=1, flat_grad=grads[c])
                 if p["arch"] == "iqn":
                     return lambda: iqn_train_from_replay(p["rep"], p["net"], idx, 0.99, seed=2, step=1, flat_grad=grads[c])
+                if p["per"]:
+                    return lambda: train_from_replay(p["rep"], p["net"], p["algo"], leaf, 0.99, flat_grad=grads[c], isw=ones, want_abs_err=True)
                 return lambda: train_from_replay(p["rep"], p["net"], p["algo"], idx, 0.99, flat_grad=grads[c])
             for c, v in rounds({c: train_fn(c, p) for c, p in pipes.items()}, 20).items():
-                row(f"train B={a.batch}", n_envs, c.replace("fb_iqn_step", "iqn").replace("fb_vec_step ", ""), v)
-            act = {c: (lambda p=p: p["net"].act_nib(p["env"].nib, 0.1, seed=2, step=3)) for c, p in pipes.items() if p["arch"] in ("iqn", "plain")}
+                row(f"train B={a.batch}", n_envs, c.replace("fb_iqn_per_step", "iqn per").replace("fb_iqn_step", "iqn").replace("fb_vec_step ", ""), v)
+            act = {c: (lambda p=p: p["net"].act_nib(p["env"].nib, 0.1, seed=2, step=3)) for c, p in pipes.items()
+                   if p["arch"] in ("iqn", "plain") and not p["per"]}
             for c, v in rounds(act, 20).items():
                 row("act_nib", n_envs, "iqn net (folded head)" if "iqn" in c else "plain net", v)
             del pipes, grads, act
