@@ -120,6 +120,8 @@ def build_parser():
     parser.add_argument("--n-tau-act", type=int, default=None, help="--model iqn: the acting grid K (default 32)")
     parser.add_argument("--cvar", type=float, default=None, help="--model iqn: act on CVaR_ETA, 0 < ETA <= 1 (default 1 = the mean)")
     parser.add_argument("--double", action="store_true", help="--model iqn | iqnper: the greedy next action from the online net (Double-DQN's target; --model rainbowiqn sets it)")
+    parser.add_argument("--dueling", action="store_true", help="--model iqn | iqnper | rainbowiqn: the dueling IQN net (value and advantage quantile streams); "
+                                                                "--model rainbowiqn --dueling --n-step 3 is Rainbow-IQN without noisy nets")
     parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper: the softmax temperature (default 0.03)")
     parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9); "
                                                                    "--model sac: the temperature (default 0.2)")
@@ -168,14 +170,14 @@ def sac_kwargs(args, parser):
     return kw
 
 
-IQN_MODELS = ("iqn", "iqnper", "rainbowiqn")             # iqnper: IQN on a prioritized memory; rainbowiqn: iqnper with --double
+IQN_MODELS = ("iqn", "iqnper", "rainbowiqn")             # iqnper: IQN on a prioritized memory; rainbowiqn: iqnper with --double; --dueling: the dueling net in each
 
 
 def iqn_kwargs(args, parser):
     """--model iqn's (iqnper's, rainbowiqn's: the same) options as VecIQN's keywords; everything is refused here, by name, before anything
     touches the GPU"""
     given = [n for n, v in (("--n-tau", args.n_tau), ("--n-tau-target", args.n_tau_target), ("--n-tau-act", args.n_tau_act), ("--cvar", args.cvar),
-                            ("--double", args.double or None)) if v is not None]
+                            ("--double", args.double or None), ("--dueling", args.dueling or None)) if v is not None]
     if args.model not in IQN_MODELS:
         if given:
             parser.error(f"{' / '.join(given)} need --model iqn, not --model {args.model}")
@@ -198,6 +200,8 @@ def iqn_kwargs(args, parser):
     except ValueError as e:
         parser.error(str(e))
     kw["prioritized"] = args.model != "iqn"
+    if args.dueling:                                     # (without the flag VecIQN's keywords are the ones of before)
+        kw["dueling"] = True
     return kw
 
 

@@ -30,6 +30,7 @@ AC_DEFAULTS = (0.5, 0.01)                             # (value_coef, entropy_coe
 ARCH_SAC = 7                                          # discrete soft actor-critic: a policy head and two Q heads (include/fbdqn.h)
 SAC_DEFAULTS = (0.2, 0.98, 0.0)                       # (alpha, target_entropy / ln A, alpha_lr) of a new SAC net
 ARCH_IQN = 8                                          # implicit quantile network: the plain layout and a cosine embedding (include/fbdqn.h)
+ARCH_IQN_DUELING = 9                                  # its dueling form: W_v b_v W_a b_a read as one effective column per action (include/fbdqn.h)
 IQN_DEFAULTS = (8, 8, 32, 1.0)                        # (n_tau, n_tau_next, n_tau_act, kappa) of a new IQN net; its risk setting eta starts at 1
 IQN_COS = 64                                          # include/fbdqn.h FB_IQN_COS
 PPO_DEFAULTS = (0.2, 0.0)                             # (clip_eps, value_clip) of a new actor-critic net; value_clip 0 = off
@@ -130,6 +131,7 @@ SIGNATURES = {
     "fb_sac_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
     "fb_sac_step": [_vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _f, _vp],
     "fb_qnet_create_iqn": [_i, _i, _i, _i, _i, _f, _i, _vp],
+    "fb_qnet_create_iqn_dueling": [_i, _i, _i, _i, _i, _f, _i, _vp],
     "fb_qnet_set_iqn_risk": [_vp, _f],
     "fb_qnet_get_iqn": [_vp, _vp, _vp, _vp, _vp, _vp],
     "fb_qnet_forward_iqn": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp],

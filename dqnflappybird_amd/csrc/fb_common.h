@@ -300,9 +300,12 @@ int fb_qnet_sac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, double
 // and hands them to the launchers as bytes.  off: the PLAIN layout (wq / bq = W_q b_q); io: the embedding behind it, W_e[64][FC] b_e[FC].
 // A fold block is [b_fc1 | phibar * W_q | b_q]: the plain layout from b_fc1 on, so `block - off.bf1` is read as a plain net's parameters
 struct IqnOff { int we, be; };
-struct IqnFoldArgs { const float *P; float *fold; int FC, A, K; NetOff off; IqnOff io; float eta; };
+// A dueling IQN net (FB_ARCH_IQN_DUELING; `dueling` = 1, the last field of every struct below): off is the DUELING layout (wv / bv = W_v b_v,
+// wq / bq = W_a b_a) and the kernels read the effective column We[k, a] = (W_v[k] + W_a[k, a]) - m_k, be[a] where W_q b_q stood; the fold block
+// keeps the plain layout, [b_fc1 | phibar * We | be], and IqnLossArgs::foff holds ITS offsets (the plain layout's; = off for a plain IQN net)
+struct IqnFoldArgs { const float *P; float *fold; int FC, A, K; NetOff off; IqnOff io; float eta; int dueling; };
 // theta f32[rows][M][A] at tau f32[rows][M]
-struct IqnHeadArgs { const float *hf, *P; int stot, nks, FC, A, rows, M; NetOff off; IqnOff io; const float *tau; float *theta; };
+struct IqnHeadArgs { const float *hf, *P; int stot, nks, FC, A, rows, M; NetOff off; IqnOff io; const float *tau; float *theta; int dueling; };
 // P0 / P1: the online / target parameters; F: the fold block (minus off.bf1) of the net that chooses a* -- online (double_q) or target --
 // and arow0 the first of its rows of hf (B or 2 B).  tau / tau_next NULL: the draws of (seed, step)
 struct IqnLossArgs {
@@ -310,14 +313,15 @@ struct IqnLossArgs {
     const uint8_t *act, *term; const float *rew; double gamma; const float *tau, *tau_next;
     uint32_t seed_lo, seed_hi, step_lo, step_hi;
     float *dl, *gw, *dhf, *dpre, *ctab, *t_out;                  // dl f32[B][4]; gw f32[B][FC]; dpre f32[B N][FC]; ctab f32[B N][64]; t_out f32[B][Np] or NULL
-    const float *isw; float *abs_err;                            // the prioritized form: both f32[B], both set (the weights in, l_b out); else both NULL
+    // isw / abs_err, the prioritized form: both f32[B], both set (the weights in, l_b out); else both NULL.  foff: the offsets F is read with
+    const float *isw; float *abs_err; NetOff foff; int dueling;
 };
-struct IqnGradArgs { int B, FC, A, N; NetOff off; IqnOff io; const float *dl, *gw, *dhf, *dpre, *ctab; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; };
+struct IqnGradArgs { int B, FC, A, N; NetOff off; IqnOff io; const float *dl, *gw, *dhf, *dpre, *ctab; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; int dueling; };
 void fb_iqn_launch_fold(hipStream_t st, const void *args);
 void fb_iqn_launch_head(hipStream_t st, const void *args);
 void fb_iqn_launch_loss(hipStream_t st, const void *args);
 void fb_iqn_launch_grad(hipStream_t st, const void *args);
-int fb_qnet_is_iqn(fb_qnet_t h);              // 1: an IQN net (fb_qnet_create_iqn)
+int fb_qnet_is_iqn(fb_qnet_t h);              // 1: an IQN net (fb_qnet_create_iqn, fb_qnet_create_iqn_dueling)
 // the checks of the two IQN training calls, `who` in the message; the ring-fed IQN train step behind fb_iqn_train_from_replay's checks
 // (gamma: the bootstrap's discount)
 int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int batch, double gamma, const char *who);

@@ -9,6 +9,9 @@
 //                     Its <.., true> instantiation is the prioritized form: importance weights in, the per-sample loss out as the priority
 //   iqn_grad_kernel   training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_q, W_e, b_e; workgroup 0: b_q, the loss, Adam's tick
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
+// A dueling net (FB_ARCH_IQN_DUELING; the DU instantiations): W_v b_v W_a b_a where W_q b_q stood, read as the effective column
+// We[k, a] = (W_v[k] + W_a[k, a]) - m_k, be[a] (iqn_eff), formed in place wherever W_q b_q is read; the fold block keeps the plain layout;
+// the gradient kernel splits the column gradients into W_v / b_v (the thread group bg == 8) and W_a / b_a.  DU = false: the statements of before.
 // A lane owns a unit k and keeps W_e[:, k] in 64 registers; the cosine rows sit in LDS and are read as broadcasts; phi is recomputed in the
 // backward pass instead of stored.
 #include "fb_common.h"
@@ -41,6 +44,30 @@ __device__ __forceinline__ float iqn_unit(const float *__restrict__ hf, int stot
         v += ks < nks ? t : 0.f;
     }
     return fmaxf(v + P[bf1 + k], 0.f);
+}
+
+// a dueling net's effective entries of one row: out[a] = (v[0] + row[a]) - (sum_{c < A} row[c]) / (float)A, the sum over ascending c from 0.f
+// (include/fbdqn.h pins it).  v / row: W_v[k] / W_a[k, :], or b_v / b_a.  A + 1 loads, none under a branch: c >= A reads column 0 (dropped)
+template <int AT>
+__device__ __forceinline__ void iqn_eff(const float *__restrict__ v, const float *__restrict__ row, int A, float (&out)[AT]) {
+    float wa[AT], s = 0.f;
+#pragma unroll
+    for (int a = 0; a < AT; a++) wa[a] = row[a < A ? a : 0];
+#pragma unroll
+    for (int a = 0; a < AT; a++) s += a < A ? wa[a] : 0.f;
+    const float m = s / (float)A, wv = v[0];
+#pragma unroll
+    for (int a = 0; a < AT; a++) out[a] = (wv + wa[a]) - m;
+}
+// entry `col` (< A) of the same, without indexing the registers
+template <int AT>
+__device__ __forceinline__ float iqn_eff_col(const float *__restrict__ v, const float *__restrict__ row, int A, int col) {
+    float e[AT];
+    iqn_eff<AT>(v, row, A, e);
+    float r = e[0];
+#pragma unroll
+    for (int a = 1; a < AT; a++) r = a == col ? e[a] : r;
+    return r;
 }
 
 // the plain head of state smp over the parameters P on every lane of the wave: head_one_t's loads, sums and order (as fb_sac.hip's sac_head),
@@ -79,8 +106,9 @@ __device__ __forceinline__ void iqn_cos_rows(const float *tq, int M, float *ct, 
 // c < NC -- NC = 1: the one column `col`; else the columns 0 .. NC - 1 (c >= A: column 0, never read).  Thread t owns the units t, t + 256,
 // ...: it holds W_e[:, k], forms pre (fmaf over ascending j from b_e[k]), g = h_k * relu(pre) and g * W_q[k, c]; a wave sums its 64 units
 // by the xor butterfly and its lane 0 adds the rounds up in order in part[wave][m][c]; out = b_q[c] + (((p_0 + p_1) + p_2) + p_3).
-// part: LDS, 4 * M * NC floats.  Ends behind a barrier: out is complete.  No load under a branch (a thread past FC reads unit 0, h = 0)
-template <int NC>
+// part: LDS, 4 * M * NC floats.  Ends behind a barrier: out is complete.  No load under a branch (a thread past FC reads unit 0, h = 0).
+// DU: a dueling net (AT: its action template), We[k, c] / be[c] where W_q[k, c] / b_q[c] stand
+template <int NC, int AT, bool DU>
 __device__ __forceinline__ void iqn_theta(const float *__restrict__ hf, int stot, int nks, int FC, int A, const float *__restrict__ P, const NetOff &off,
                                           const IqnOff &io, int row, int col, const float *ct, int M, float *part, float *out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -92,8 +120,13 @@ __device__ __forceinline__ void iqn_theta(const float *__restrict__ hf, int stot
         float w[IQN_E], wq[NC];
 #pragma unroll
         for (int j = 0; j < IQN_E; j++) w[j] = P[io.we + j * FC + k];
+        if constexpr (DU) {
+            if constexpr (NC == 1) wq[0] = iqn_eff_col<AT>(P + off.wv + k, P + off.wq + k * A, A, col);
+            else { static_assert(NC == AT, "all columns"); iqn_eff<AT>(P + off.wv + k, P + off.wq + k * A, A, wq); }
+        } else {
 #pragma unroll
-        for (int c = 0; c < NC; c++) wq[c] = P[off.wq + k * A + (NC == 1 ? col : (c < A ? c : 0))];
+            for (int c = 0; c < NC; c++) wq[c] = P[off.wq + k * A + (NC == 1 ? col : (c < A ? c : 0))];
+        }
         const float be = P[io.be + k], hk = iqn_unit(hf, stot, nks, FC, P, off.bf1, row, k), h = ok ? hk : 0.f;
         for (int m = 0; m < M; m++) {
             float pre = be;
@@ -111,13 +144,17 @@ __device__ __forceinline__ void iqn_theta(const float *__restrict__ hf, int stot
     __syncthreads();
     for (int q = tid; q < M * NC; q += 256) {
         const int c = q % NC;
-        const float bq = P[off.bq + (NC == 1 ? col : (c < A ? c : 0))];
+        float bq;
+        if constexpr (DU) bq = iqn_eff_col<AT>(P + off.bv, P + off.bq, A, NC == 1 ? col : (c < A ? c : 0));
+        else bq = P[off.bq + (NC == 1 ? col : (c < A ? c : 0))];
         out[q] = bq + (((part[q] + part[M * NC + q]) + part[2 * M * NC + q]) + part[3 * M * NC + q]);
     }
     __syncthreads();
 }
 
 // ---- the fold of one net: 128 units per workgroup (FC % 128 == 0), a thread per unit
+// DU: [b_fc1 | phibar_k * We[k, a] | be[a]], the same plain layout
+template <bool DU>
 __global__ __launch_bounds__(128) void iqn_fold_kernel(IqnFoldArgs F) {
     __shared__ float ct[IQN_MAXT * IQN_E];
     __shared__ float tq[IQN_MAXT];
@@ -129,7 +166,15 @@ __global__ __launch_bounds__(128) void iqn_fold_kernel(IqnFoldArgs F) {
     float w[IQN_E];
 #pragma unroll
     for (int j = 0; j < IQN_E; j++) w[j] = F.P[F.io.we + j * FC + k];
-    const float be = F.P[F.io.be + k], bf = F.P[F.off.bf1 + k], bq = F.P[F.off.bq + (k < A ? k : 0)];
+    const float be = F.P[F.io.be + k], bf = F.P[F.off.bf1 + k];
+    float bq;
+    [[maybe_unused]] float we[MAXA];                              // (DU: the unit's effective row, every load issued up front: this launch is latency)
+    if constexpr (DU) {
+        iqn_eff<MAXA>(F.P + F.off.wv + k, F.P + F.off.wq + k * A, A, we);
+        bq = iqn_eff_col<MAXA>(F.P + F.off.bv, F.P + F.off.bq, A, k < A ? k : 0);
+    } else {
+        bq = F.P[F.off.bq + (k < A ? k : 0)];
+    }
     float sm = 0.f;
     for (int i = 0; i < K; i++) {
         float pre = be;
@@ -139,12 +184,18 @@ __global__ __launch_bounds__(128) void iqn_fold_kernel(IqnFoldArgs F) {
     }
     const float pb = sm / (float)K;
     F.fold[k] = bf;
-    for (int a = 0; a < A; a++) F.fold[FC + k * A + a] = pb * F.P[F.off.wq + k * A + a];
+    if constexpr (DU) {
+#pragma unroll
+        for (int a = 0; a < MAXA; a++)
+            if (a < A) F.fold[FC + k * A + a] = pb * we[a];
+    } else {
+        for (int a = 0; a < A; a++) F.fold[FC + k * A + a] = pb * F.P[F.off.wq + k * A + a];
+    }
     if (k < A) F.fold[FC + FC * A + k] = bq;
 }
 
 // ---- fb_qnet_forward_iqn: one workgroup per state
-template <int AT>
+template <int AT, bool DU>
 __global__ __launch_bounds__(256) void iqn_head_kernel(IqnHeadArgs H) {
     __shared__ float ct[IQN_MAXT * IQN_E];
     __shared__ float part[4 * IQN_MAXT * AT];
@@ -156,7 +207,7 @@ __global__ __launch_bounds__(256) void iqn_head_kernel(IqnHeadArgs H) {
     __syncthreads();
     iqn_cos_rows(tq, M, ct, tid, 256);
     __syncthreads();
-    iqn_theta<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off, H.io, row, 0, ct, M, part, out);
+    iqn_theta<AT, AT, DU>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off, H.io, row, 0, ct, M, part, out);
     for (int q = tid; q < M * AT; q += 256) {
         const int m = q / AT, c = q - m * AT;
         if (c < A) H.theta[((size_t)row * M + m) * A + c] = out[q];
@@ -167,7 +218,8 @@ __global__ __launch_bounds__(256) void iqn_head_kernel(IqnHeadArgs H) {
 // net, s' through the target net.  dl[b][4]: the action read, sum_i d theta_i, l_b, 0.
 // PW, the prioritized form (fb_qnet_iqn_per_train_step): w_b = isw[b] is multiplied into d theta_i LAST, dl[b][2] takes w_b l_b and
 // abs_err[b] the unweighted l_b (the priority); w = 1 leaves the bits of the uniform form.
-template <int AT, bool PW>
+// DU, a dueling net: theta, T and the backward's column through We / be; a* over the fold with ITS offsets (L.foff, the plain layout's).
+template <int AT, bool PW, bool DU>
 __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
     __shared__ float ct[2 * IQN_MAXT * IQN_E];                    // the cosine rows of tau (N of them), then of tau' (N')
     __shared__ float part[4 * IQN_MAXT];
@@ -192,20 +244,21 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
     if constexpr (PW) wb = L.isw[b];
     // a*: the first maximum of the plain head over the fold (every wave forms the same bits)
     float qa[AT];
-    iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
+    if constexpr (DU) iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qa);
+    else iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
     int as = 0;
     float qbest = qa[0];
 #pragma unroll
     for (int c = 1; c < AT; c++) { const bool up = c < A && qa[c] > qbest; as = up ? c : as; qbest = up ? qa[c] : qbest; }
     __syncthreads();
-    iqn_theta<1>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off, L.io, 2 * B + b, as, ct + N * IQN_E, Np, part, tg);
+    iqn_theta<1, AT, DU>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off, L.io, 2 * B + b, as, ct + N * IQN_E, Np, part, tg);
     if (tid < Np) {
         const double r = rf == 0.1f ? 0.1 : (double)rf;           // (the convention of every target here)
         const float T = (float)(done ? r : r + L.gamma * (double)tg[tid]);
         tg[tid] = T;
         if (L.t_out) L.t_out[(size_t)b * Np + tid] = T;
     }
-    iqn_theta<1>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off, L.io, b, ab, ct, N, part, th);      // (its first barrier orders tg's stores too)
+    iqn_theta<1, AT, DU>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off, L.io, b, ab, ct, N, part, th);      // (its first barrier orders tg's stores too)
     if (tid < N) {                                                // the pairwise quantile Huber loss of row i, j ascending
         const float kap = L.kappa, ti = tq[tid], thi = th[tid];
         float l = 0.f, g = 0.f;
@@ -239,7 +292,10 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
         float w[IQN_E];
 #pragma unroll
         for (int j = 0; j < IQN_E; j++) w[j] = L.P0[L.io.we + j * FC + k];
-        const float be = L.P0[L.io.be + k], wq = L.P0[L.off.wq + k * A + ab], h = iqn_unit(L.hf, L.stot, L.nks, FC, L.P0, L.off.bf1, b, k);
+        float wq;
+        if constexpr (DU) wq = iqn_eff_col<AT>(L.P0 + L.off.wv + k, L.P0 + L.off.wq + k * A, A, ab);
+        else wq = L.P0[L.off.wq + k * A + ab];
+        const float be = L.P0[L.io.be + k], h = iqn_unit(L.hf, L.stot, L.nks, FC, L.P0, L.off.bf1, b, k);
         float s = 0.f;
         for (int i = 0; i < N; i++) {
             float pre = be;
@@ -260,6 +316,9 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
 // (fc1_bwd_big_kernel's pre-scale); thread (unit jl, column c < 8) walks the samples in order for W_q's column c, which takes sample b's
 // row when a_b = c, else 0; then thread (unit jl, cosines 4 g .. 4 g + 3) walks the rows (b, i) in order for W_e, the threads of g = 0
 // for b_e as well.  Workgroup 0 also sums b_q and the loss the same way and ticks Adam.
+// DU, a dueling net: with H_kc the column sum above and G_k = sum_b gw[b, k] (ascending b, walked beside it), dW_a[k, c] = H_kc - G_k / (float)A;
+// the thread group bg == 8 (idle otherwise: A <= 8) walks G_k again for dW_v[k] = G_k; b_a / b_v the same way from dl[b][1]
+template <bool DU>
 __global__ __launch_bounds__(256) void iqn_grad_kernel(IqnGradArgs L) {
     __shared__ float dlt[IQN_MAXB * 4];
     __shared__ float xt[IQN_MAXB * 16];
@@ -285,13 +344,22 @@ __global__ __launch_bounds__(256) void iqn_grad_kernel(IqnGradArgs L) {
     const int c = bg;
     const bool live = c < A;                                      // (A <= 8: the columns sit in bg < 8)
     float acc = 0.f, gb = 0.f;
+    [[maybe_unused]] float gk = 0.f, gs = 0.f;                   // (DU: G_k and sum_b dl[b][1])
     if (live) {
         for (int b = 0; b < B; b++) {
             const bool hit = (int)dlt[b * 4] == c;
             acc += hit ? xt[b * 16 + jl] : 0.f;
             gb += hit ? dlt[b * 4 + 1] : 0.f;
+            if constexpr (DU) { gk += xt[b * 16 + jl]; gs += dlt[b * 4 + 1]; }
         }
-        L.grad[L.off.wq + (size_t)(j00 + jl) * A + c] = acc;
+        if constexpr (DU) L.grad[L.off.wq + (size_t)(j00 + jl) * A + c] = acc - gk / (float)A;
+        else L.grad[L.off.wq + (size_t)(j00 + jl) * A + c] = acc;
+    }
+    if constexpr (DU) {
+        if (bg == 8) {
+            for (int b = 0; b < B; b++) { gk += xt[b * 16 + jl]; gs += dlt[b * 4 + 1]; }
+            L.grad[L.off.wv + j00 + jl] = gk;
+        }
     }
     {
         const int R = B * L.N;
@@ -310,7 +378,12 @@ __global__ __launch_bounds__(256) void iqn_grad_kernel(IqnGradArgs L) {
         if (bg == 0) L.grad[L.io.be + j00 + jl] = be;
     }
     if (blockIdx.x != 0) return;
-    if (jl == 0 && live) L.grad[L.off.bq + c] = gb;
+    if constexpr (DU) {
+        if (jl == 0 && live) L.grad[L.off.bq + c] = gb - gs / (float)A;
+        if (jl == 0 && bg == 8) L.grad[L.off.bv] = gs;
+    } else {
+        if (jl == 0 && live) L.grad[L.off.bq + c] = gb;
+    }
     if (tid == 0) {
         float t = 0.f;
         for (int b = 0; b < B; b++) t += dlt[b * 4 + 2];
@@ -336,18 +409,27 @@ template <class F> void with_actions(int A, F f) {
     if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
 }
 template <class F> void with_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+// the loss launch of either kind of net (L.dueling) at the head's action template and the prioritized form
+template <int AT, bool PW>
+void launch_loss(hipStream_t st, const IqnLossArgs &L) {
+    with_bool(L.dueling != 0, [&](auto du) { hipLaunchKernelGGL((iqn_loss_kernel<AT, PW, decltype(du)::value>), dim3(L.B), dim3(256), 0, st, L); });
+}
 }  // namespace
 
 void fb_iqn_launch_fold(hipStream_t st, const void *args) {
     IqnFoldArgs F;
     memcpy(&F, args, sizeof(F));
-    hipLaunchKernelGGL(iqn_fold_kernel, dim3(F.FC / 128), dim3(128), 0, st, F);
+    with_bool(F.dueling != 0, [&](auto du) { hipLaunchKernelGGL(iqn_fold_kernel<decltype(du)::value>, dim3(F.FC / 128), dim3(128), 0, st, F); });
 }
 
 void fb_iqn_launch_head(hipStream_t st, const void *args) {
     IqnHeadArgs H;
     memcpy(&H, args, sizeof(H));
-    with_actions(H.A, [&](auto a) { hipLaunchKernelGGL(iqn_head_kernel<decltype(a)::value>, dim3(H.rows), dim3(256), 0, st, H); });
+    with_actions(H.A, [&](auto a) {
+        with_bool(H.dueling != 0, [&](auto du) {
+            hipLaunchKernelGGL((iqn_head_kernel<decltype(a)::value, decltype(du)::value>), dim3(H.rows), dim3(256), 0, st, H);
+        });
+    });
 }
 
 void fb_iqn_launch_loss(hipStream_t st, const void *args) {
@@ -355,7 +437,7 @@ void fb_iqn_launch_loss(hipStream_t st, const void *args) {
     memcpy(&L, args, sizeof(L));
     with_actions(L.A, [&](auto a) {           // (isw set: the prioritized form, which also writes abs_err)
         with_bool(L.isw != nullptr, [&](auto pw) {
-            hipLaunchKernelGGL((iqn_loss_kernel<decltype(a)::value, decltype(pw)::value>), dim3(L.B), dim3(256), 0, st, L);
+            launch_loss<decltype(a)::value, decltype(pw)::value>(st, L);
         });
     });
 }
@@ -363,7 +445,7 @@ void fb_iqn_launch_loss(hipStream_t st, const void *args) {
 void fb_iqn_launch_grad(hipStream_t st, const void *args) {
     IqnGradArgs L;
     memcpy(&L, args, sizeof(L));
-    hipLaunchKernelGGL(iqn_grad_kernel, dim3(L.FC / 16), dim3(256), 0, st, L);
+    with_bool(L.dueling != 0, [&](auto du) { hipLaunchKernelGGL(iqn_grad_kernel<decltype(du)::value>, dim3(L.FC / 16), dim3(256), 0, st, L); });
 }
 
 extern "C" int fb_iqn_draw_taus(int batch, int n, uint64_t seed, uint64_t step, int which, float *tau_out, void *stream) {

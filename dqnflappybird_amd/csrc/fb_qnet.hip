@@ -4047,6 +4047,8 @@ struct fb_qnet {
     int iqn_n, iqn_np, iqn_k;
     float iqn_eta;
     float *iqn_dpre, *iqn_ctab;
+    // a dueling IQN net (FB_ARCH_IQN_DUELING, fb_qnet_create_iqn_dueling): off is the DUELING layout (W_v b_v W_a b_a), then W_e b_e; its fold
+    // heff[w] = [b_fc1 | phibar * We | be] keeps the PLAIN layout, whose offsets are hoff: what reads head_base() as a plain net takes hoff
 };
 // every field ac_grad_kernel touches through FbAdamHead sits where AdamDev has it
 static_assert(offsetof(AdamDev, b1pow) == offsetof(FbAdamHead, b1pow) && offsetof(AdamDev, b2pow) == offsetof(FbAdamHead, b2pow) &&
@@ -4080,7 +4082,9 @@ static bool is_ac(const fb_qnet *h) { return h->arch == FB_ARCH_AC; }
 // a SAC net: the plain layout (W_pi b_pi at wq / bq: the logits, which the plain head reads as "Q"), then W_q1 b_q1 W_q2 b_q2
 static bool is_sac(const fb_qnet *h) { return h->arch == FB_ARCH_SAC; }
 // an IQN net: the plain layout (W_q b_q at wq / bq), then W_e b_e; forward-only paths read the plain head over its fold, heff[w]
-static bool is_iqn(const fb_qnet *h) { return h->arch == FB_ARCH_IQN; }
+static bool is_iqn(const fb_qnet *h) { return h->arch == FB_ARCH_IQN || h->arch == FB_ARCH_IQN_DUELING; }
+// a dueling IQN net: the dueling layout (W_v b_v, W_a b_a at wq / bq), then W_e b_e; its fold is a plain net's, read with hoff
+static bool is_iqnd(const fb_qnet *h) { return h->arch == FB_ARCH_IQN_DUELING; }
 // the parameters the C51 kernels read, with h->hoff, for the net whose parameters are `params` (a virtual base for a dueling C51 net:
 // hoff.bf1 lands on heff[w][0], as the acting forward's hp_act copy is read)
 static const float *head_base(const fb_qnet *h, const float *params) {
@@ -4090,7 +4094,7 @@ static const float *head_base(const fb_qnet *h, const float *params) {
 // refold a dueling C51 net's head after its parameters changed (no-op for other nets)
 static void c51d_fold(fb_qnet *h, int which, hipStream_t st) {
     if (is_iqn(h)) {                             // (an IQN net: phibar over the acting grid and its fold block, fb_iqn.hip)
-        const IqnFoldArgs F{h->params[which], h->heff[which], h->FC, h->A, h->iqn_k, h->off, h->iqn_off, h->iqn_eta};
+        const IqnFoldArgs F{h->params[which], h->heff[which], h->FC, h->A, h->iqn_k, h->off, h->iqn_off, h->iqn_eta, is_iqnd(h) ? 1 : 0};
         fb_iqn_launch_fold(st, &F);
         return;
     }
@@ -4210,8 +4214,9 @@ extern "C" int fb_qnet_create_sac(int fc_width, int n_actions, int max_batch, fb
     return rc;
 }
 
-extern "C" int fb_qnet_create_iqn(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch, fb_qnet_t *out) {
-    const char *fn = "fb_qnet_create_iqn";
+// the checks of fb_qnet_create_iqn / _iqn_dueling, before any allocation (`fn` names the caller in the message)
+static int iqn_create(const char *fn, int arch, int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch,
+                      fb_qnet_t *out) {
     FB_REQUIRE(out, "%s: out is NULL", fn);
     FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
     FB_REQUIRE(n_actions >= 2 && n_actions <= MAXA, "%s: n_actions must be in 2..%d", fn, MAXA);
@@ -4221,9 +4226,18 @@ extern "C" int fb_qnet_create_iqn(int fc_width, int n_actions, int n_tau, int n_
     FB_REQUIRE(isfinite(kappa) && kappa > 0.f, "%s: kappa must be finite and > 0 (got %g)", fn, (double)kappa);
     FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
     g_iqn_create[0] = n_tau; g_iqn_create[1] = n_tau_next; g_iqn_create[2] = n_tau_act;
-    const int rc = qnet_create(FB_ARCH_IQN, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
+    const int rc = qnet_create(arch, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
     if (rc == FB_OK) (*out)->kappa = kappa;
     return rc;
+}
+
+extern "C" int fb_qnet_create_iqn(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch, fb_qnet_t *out) {
+    return iqn_create("fb_qnet_create_iqn", FB_ARCH_IQN, fc_width, n_actions, n_tau, n_tau_next, n_tau_act, kappa, max_batch, out);
+}
+
+extern "C" int fb_qnet_create_iqn_dueling(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch,
+                                          fb_qnet_t *out) {
+    return iqn_create("fb_qnet_create_iqn_dueling", FB_ARCH_IQN_DUELING, fc_width, n_actions, n_tau, n_tau_next, n_tau_act, kappa, max_batch, out);
 }
 
 // the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
@@ -4250,18 +4264,18 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
     h->ppo_eps = 0.2f; h->ppo_vclip = 0.f;       // PPO's clip ranges (read by the PPO train steps of an actor-critic net alone)
     h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
     h->off = is_c51d(h) ? make_off_c51d(fc_width, n_actions, sup.N)
-                        : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING || arch == FB_ARCH_AC);
+                        : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING || arch == FB_ARCH_AC || arch == FB_ARCH_IQN_DUELING);
     if (is_sac(h)) {                             // (the plain layout, then the two Q heads: off.n covers them)
         h->sac_off.wq1 = h->off.n; h->sac_off.bq1 = h->sac_off.wq1 + fc_width * n_actions;
         h->sac_off.wq2 = h->sac_off.bq1 + n_actions; h->sac_off.bq2 = h->sac_off.wq2 + fc_width * n_actions;
         h->off.n = h->sac_off.bq2 + n_actions;
     }
-    if (is_iqn(h)) {                             // (the plain layout, then the embedding: off.n covers it)
+    if (is_iqn(h)) {                             // (the plain or the dueling layout, then the embedding: off.n covers it)
         h->iqn_off.we = h->off.n; h->iqn_off.be = h->iqn_off.we + FB_IQN_COS * fc_width;
         h->off.n = h->iqn_off.be + fc_width;
         h->iqn_n = g_iqn_create[0]; h->iqn_np = g_iqn_create[1]; h->iqn_k = g_iqn_create[2]; h->iqn_eta = 1.f;
     }
-    h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : h->off;
+    h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : is_iqnd(h) ? make_off(fc_width, n_actions, 0) : h->off;      // (a dueling IQN net: its fold's)
     h->n = h->off.n;
     h->noisy = sigma0 >= 0.f;                    // (fb_qnet_create_c51_noisy: C51 archs, finite sigma0 >= 0)
     h->ntot = h->noisy ? 2 * h->n - OFF_WF1 : h->n;
@@ -4461,7 +4475,7 @@ static void resplit_now(fb_qnet *h, int which, hipStream_t st) {
 extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *stream) {
     FB_REQUIRE(h && (which == 0 || which == 1), "fb_qnet_init_params: bad argument");
     hipLaunchKernelGGL(init_params_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, fb_stream(stream),
-                       master(h, which), h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING || is_c51d(h) || is_ac(h), (uint32_t)seed,
+                       master(h, which), h->n, h->off, h->FC, h->sup.N ? h->A * h->sup.N : h->A, h->arch == FB_ARCH_DUELING || is_c51d(h) || is_ac(h) || is_iqnd(h), (uint32_t)seed,
                        (uint32_t)(seed >> 32));
     if (is_c51d(h)) {                            // (init_params_kernel's dueling bias is one entry: b_v has N)
         const float b = 0.01f;
@@ -4791,6 +4805,7 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         memset(&H, 0, sizeof(H));
         H.hf = c.fused ? h->hf_act : h->hf; H.P = p.sl.s[0].params;
         H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A; H.rows = c.total; H.M = p.iqn_m; H.off = h->off; H.io = h->iqn_off;
+        H.dueling = is_iqnd(h) ? 1 : 0;
         H.tau = p.iqn_tau; H.theta = p.iqn_theta;
         fb_iqn_launch_head(c.st, &H);
         return;
@@ -4812,7 +4827,7 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (an IQN net: its fold; every scalar net: its parameters)
         HeadCore &C = H.c;
         C.hf = c.fused ? h->hf_act : h->hf; C.stot = c.stot; C.nks = c.big ? FC1_SP_KS : 1; C.q = h->q; C.FC = h->FC; C.A = h->A;
-        C.dueling = h->arch == FB_ARCH_DUELING; C.off = h->off; C.actions = p.actions; C.epsilon = p.epsilon;
+        C.dueling = h->arch == FB_ARCH_DUELING; C.off = h->hoff; C.actions = p.actions; C.epsilon = p.epsilon;      // (hoff: = off but for a dueling IQN net, whose fold is plain)
         put_seed_words(C, p.seed, p.step);
         // (the rider of a fused acting forward reads the head's parameters from the copy that forward's fc1 launch took: b_fc1 on)
         if (p.head_rider) { p.head_rider->c = C; p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params; p.head_rider->on = 1; p.head_rider->on_arrival = nullptr; p.head_rider->arrival_val = 0; }   // rides in the env launch
@@ -4834,9 +4849,10 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         put_seed_words(L, p.seed, p.step);
         L.dl = h->ac_dl; L.gw = h->ac_xs; L.dhf = h->dhf; L.dpre = h->iqn_dpre; L.ctab = h->iqn_ctab; L.t_out = p.y;
         L.isw = p.isw; L.abs_err = p.abs_err;    // (both set: the prioritized form; the uniform calls leave both NULL)
+        L.foff = h->hoff; L.dueling = is_iqnd(h) ? 1 : 0;       // (L.F is a fold: the plain layout's offsets, whatever the net's)
         fb_iqn_launch_loss(c.st, &L);
         const IqnGradArgs gA{B, FC, h->A, h->iqn_n, h->off, h->iqn_off, h->ac_dl, h->ac_xs, h->dhf, h->iqn_dpre, h->iqn_ctab, p.G, p.loss, h->gmax,
-                             reinterpret_cast<FbAdamHead *>(h->adam), p.tick};
+                             reinterpret_cast<FbAdamHead *>(h->adam), p.tick, is_iqnd(h) ? 1 : 0};
         fb_iqn_launch_grad(c.st, &gA);
         return;
     }

@@ -137,9 +137,10 @@ def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
         return net
     if "head" in z.files and str(z["head"][0]) == "iqn":     # an IQN net (VecIQN): greedy play on the folded head, under the file's risk setting
         n_tau, n_tau_next, n_tau_act, kappa, cvar = z["iqn"].tolist()
-        net = QNet(2, fc_width, "iqn", max_batch=max_batch, n_tau=int(n_tau), n_tau_next=int(n_tau_next), n_tau_act=int(n_tau_act), kappa=kappa)
+        dueling = bool(int(z["dueling"][0])) if "dueling" in z.files else False      # (a file without the key: a plain IQN net)
+        net = QNet(2, fc_width, "iqndueling" if dueling else "iqn", max_batch=max_batch, n_tau=int(n_tau), n_tau_next=int(n_tau_next), n_tau_act=int(n_tau_act), kappa=kappa)
         if net.n_params != online.size:
-            raise ValueError(f"{path}: {online.size} online parameters do not match an IQN net of width {fc_width}")
+            raise ValueError(f"{path}: {online.size} online parameters do not match {'a dueling' if dueling else 'an'} IQN net of width {fc_width}")
         if dtype != "f32":
             raise ValueError(f"{path}: an IQN net computes in f32 only (dtype {dtype!r})")
         net.load_params(online, 0)

@@ -305,6 +305,8 @@ PPO_DEFAULTS = L.PPO_DEFAULTS                             # (clip_eps, value_cli
 SAC_ARCH = "sac"                                          # discrete soft actor-critic: a policy head and two Q heads (include/fbdqn.h)
 SAC_DEFAULTS = L.SAC_DEFAULTS                             # (alpha, target_entropy / ln A, alpha_lr) of a new SAC net
 IQN_ARCH = "iqn"                                          # implicit quantile network: the plain layout and a cosine embedding (include/fbdqn.h)
+IQN_DUELING_ARCH = "iqndueling"                           # its dueling form: value and advantage quantile streams, one effective column per action
+IQN_ARCHS = (IQN_ARCH, IQN_DUELING_ARCH)                  # what every IQN call takes
 IQN_DEFAULTS = L.IQN_DEFAULTS                             # (n_tau, n_tau_next, n_tau_act, kappa) of a new IQN net
 
 
@@ -481,7 +483,7 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
-    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH, SAC_ARCH, IQN_ARCH)
+    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH, SAC_ARCH, IQN_ARCH, IQN_DUELING_ARCH)
 
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
                  v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0,
@@ -499,7 +501,9 @@ class QNet:
         include/fbdqn.h); forward / act / act_nib / evaluation treat the logits as the Q values
         arch='iqn': an implicit quantile network -- theta(s, a; tau) through a cosine embedding of tau; trains on n_tau / n_tau_next sampled
         tau with the quantile Huber loss (kappa), acts on the mean over a grid of n_tau_act tau (scaled by set_iqn_risk's eta), which
-        forward / act / act_nib / evaluation return as the Q values (2 <= actions <= 8; include/fbdqn.h)"""
+        forward / act / act_nib / evaluation return as the Q values (2 <= actions <= 8; include/fbdqn.h)
+        arch='iqndueling': the dueling IQN net -- W_v b_v W_a b_a where W_q b_q stand, theta = V(tau) + Adv_a(tau) - mean_a' Adv_a'(tau) read as
+        one effective column per action; every IQN call takes it (include/fbdqn.h)"""
         if arch not in self.ARCHS:
             raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
         self.noisy = bool(noisy)
@@ -513,7 +517,7 @@ class QNet:
             n_atoms, v_min, v_max = check_support(n_atoms, v_min, v_max, actions)
         if arch in QR_ARCHS:
             n_quantiles, kappa = check_quantiles(n_quantiles, kappa, actions)
-        if arch == IQN_ARCH:
+        if arch in IQN_ARCHS:
             n_tau, n_tau_next, n_tau_act, kappa, _ = check_iqn(n_tau, n_tau_next, n_tau_act, kappa, 1.0, actions)
         L.require_gpu()
         self.A, self.FC, self.max_batch = int(actions), int(fc_width), int(max_batch)
@@ -532,6 +536,9 @@ class QNet:
         elif arch == IQN_ARCH:
             L.check(L.lib().fb_qnet_create_iqn(self.FC, self.A, n_tau, n_tau_next, n_tau_act, kappa, self.max_batch, C.byref(self.h)),
                     "fb_qnet_create_iqn")
+        elif arch == IQN_DUELING_ARCH:
+            L.check(L.lib().fb_qnet_create_iqn_dueling(self.FC, self.A, n_tau, n_tau_next, n_tau_act, kappa, self.max_batch, C.byref(self.h)),
+                    "fb_qnet_create_iqn_dueling")
         elif arch == SAC_ARCH:
             L.check(L.lib().fb_qnet_create_sac(self.FC, self.A, self.max_batch, C.byref(self.h)), "fb_qnet_create_sac")
         elif arch == AC_ARCH:
@@ -849,7 +856,7 @@ class QNet:
 
     # -- implicit quantile networks (arch='iqn') -----------------------------------------
     def _need_iqn(self, what):
-        if self.arch != IQN_ARCH:
+        if self.arch not in IQN_ARCHS:
             raise ValueError(f"{what} needs an IQN net (QNet(..., arch='iqn'))")
 
     def set_iqn_risk(self, eta=1.0):
@@ -1152,7 +1159,7 @@ def check_isw(B, isw):
 def _ring_call(name, replay, net, arch, need, reads, idx, n_loss, *tensors, prioritized=False):
     """what the four *_train_from_replay calls of the newer families begin with: the net's arch, a uniform memory (prioritized=True: a
     prioritized one), device tensors, idx's dtype -> (B, dev, a u8[B], loss f32[n_loss]), the last two for the library to fill"""
-    if net.arch != arch:
+    if net.arch not in (arch if isinstance(arch, tuple) else (arch,)):
         raise ValueError(f"{name} needs {need}")
     if prioritized and not replay.prioritized:
         raise ValueError(f"{name} {reads} a prioritized memory only")
@@ -1181,7 +1188,7 @@ def iqn_train_from_replay(replay, net, idx, gamma=0.99, double_q=False, tau=None
     """QNet.iqn_train_step on the transitions at the deque positions idx of a uniform memory (any n-step view; gamma must be the memory's),
     read from its frame ring in place (fb_iqn_train_from_replay)
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, q_target f32[B, n_tau_next]])"""
-    B, dev, a, loss = _ring_call("iqn_train_from_replay", replay, net, IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
+    B, dev, a, loss = _ring_call("iqn_train_from_replay", replay, net, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
                                  flat_grad, tau, tau_next)
     N, Np = net.iqn()[:2]
     check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
@@ -1198,7 +1205,7 @@ def iqn_per_train_from_replay(replay, net, idx, isw, gamma=0.99, double_q=False,
     """QNet.iqn_per_train_step on the transitions at the SumTree leaves idx of a prioritized memory (any n-step view; gamma must be the
     memory's), read from its frame ring in place (fb_iqn_per_train_from_replay); isw f32[B]: replay.sample's importance weights
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, q_target f32[B, n_tau_next]], abs_err f32[B])"""
-    B, dev, a, loss = _ring_call("iqn_per_train_from_replay", replay, net, IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
+    B, dev, a, loss = _ring_call("iqn_per_train_from_replay", replay, net, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
                                  flat_grad, tau, tau_next, isw, prioritized=True)
     N, Np = net.iqn()[:2]
     check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
@@ -1345,7 +1352,7 @@ class AcRolloutStep:
 def _bind_step(self, name, arch, need, env, replay, net, batch, gamma, flat_grad, n_loss, prioritized=False):
     """what SacStep, IqnStep and IqnPerStep set up alike: the checks, the step's own tensors (loss: f32[n_loss]) and the bound pointers;
     prioritized: a prioritized memory instead of a uniform one, and Memory.sample's weights (f64 and f32) and abs_err beside them"""
-    if net.arch != arch:
+    if net.arch not in (arch if isinstance(arch, tuple) else (arch,)):
         raise ValueError(f"{name} needs {need}")
     if prioritized and not replay.prioritized:
         raise ValueError(f"{name} trains from a prioritized memory only")
@@ -1396,7 +1403,7 @@ class IqnStep:
     that order; the pointers are bound once."""
 
     def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
-        _bind_step(self, "IqnStep", IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1)
+        _bind_step(self, "IqnStep", IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1)
         self.double_q = bool(double_q)
 
     def __call__(self, epsilon=0.0, seed=0, step=0, train=True):
@@ -1412,7 +1419,7 @@ class IqnPerStep:
     separate calls in that order; it owns idx, isw (f64), isw32 and abs_err (l_b as the loss left it)."""
 
     def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
-        _bind_step(self, "IqnPerStep", IQN_ARCH, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1, prioritized=True)
+        _bind_step(self, "IqnPerStep", IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1, prioritized=True)
         self.double_q = bool(double_q)
 
     def __call__(self, epsilon=0.0, seed=0, step=0, train=True):

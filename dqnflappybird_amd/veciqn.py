@@ -12,6 +12,9 @@ what a plain net's does: the mean over the acting grid of tau folds into the hea
 prioritized=True: a prioritized memory (its n fixed at creation) and vec.IqnPerStep -- store -> Memory.sample -> the IQN step with the
 importance weights -> Memory.batch_update with the per-sample loss, still one host call.  With double_q and n_step = 3: "Rainbow-IQN"
 without the dueling and the noisy head.
+
+dueling=True: the dueling IQN net (QNet arch 'iqndueling': value and advantage quantile streams, one effective column per action) in the
+same loops; with prioritized, double_q and n_step = 3 this is Rainbow-IQN without noisy nets.
 """
 import numpy as np
 
@@ -63,6 +66,17 @@ def check_prioritized(prioritized):
     return bool(prioritized)
 
 
+def check_dueling(dueling):
+    """VecIQN's `dueling` setting, checked apart from check_args (whose positional parameters stay as they are) -> bool"""
+    if not isinstance(dueling, (bool, np.bool_)):
+        raise ValueError(f"dueling must be True or False, got {dueling!r}")
+    return bool(dueling)
+
+
+def head_kind(dueling):
+    return "dueling" if dueling else "plain"
+
+
 def replay_kind(prioritized):
     return "prioritized" if prioritized else "uniform"
 
@@ -70,18 +84,20 @@ def replay_kind(prioritized):
 class VecIQN:
     def __init__(self, n_envs, batch=32, double_q=False, n_step=1, n_tau=8, n_tau_next=8, n_tau_act=32, kappa=1.0, cvar=1.0, polyak=0.0,
                  replace_target_iter=500, observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99, lr=1e-6,
-                 max_grad_norm=0, fc_width=512, seed=0, capacity=None, prioritized=False):
+                 max_grad_norm=0, fc_width=512, seed=0, capacity=None, prioritized=False, dueling=False):
         """n_envs games; every step trains one minibatch of `batch` transitions (<= n_envs, <= 256) once more than `observe` steps have
         filled the memory.  n_tau / n_tau_next: the tau sampled per transition for the online / target quantiles; n_tau_act: the acting
         grid; kappa: the quantile Huber threshold; cvar = eta in (0, 1]: act on CVaR_eta (1 = the mean).  double_q: a* from the online
         net.  n_step > 1: n-step returns.  The epsilon schedule (observe / explore / initial / final) and the periodic target copy are
         VecBrain's; polyak > 0 replaces the copy by soft updates; lr is Adam's; max_grad_norm=G > 0 clips the gradient's global norm.
-        prioritized: train from a prioritized memory (importance-weighted loss, the per-sample loss as the priority)."""
+        prioritized: train from a prioritized memory (importance-weighted loss, the per-sample loss as the priority).
+        dueling: the dueling IQN net (value and advantage quantile streams) instead of the plain one."""
         (self.n, self.batch, self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar, self.n_step, self.polyak, self.replace_target_iter,
          self.observe, self.explore, self.initial_epsilon, self.final_epsilon, self.gamma, self.lr, self.max_grad_norm, self.capacity) = check_args(
             n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step, polyak, replace_target_iter, observe, explore, initial_epsilon,
             final_epsilon, gamma, lr, max_grad_norm, capacity)
         self.prioritized = check_prioritized(prioritized)
+        self.dueling = check_dueling(dueling)
         from .vec import QNet, VecGameState, VecReplay
         self.double_q = bool(double_q)
         self.seed = int(seed)
@@ -96,7 +112,7 @@ class VecIQN:
             self.replay.seed(self.seed)
             if self.n_step > 1:
                 self.replay.set_n_step(self.n_step, self.gamma)
-        self.net = QNet(2, self.fc_width, "iqn", max_batch=max(self.n, self.batch), n_tau=self.n_tau, n_tau_next=self.n_tau_next,
+        self.net = QNet(2, self.fc_width, "iqndueling" if self.dueling else "iqn", max_batch=max(self.n, self.batch), n_tau=self.n_tau, n_tau_next=self.n_tau_next,
                         n_tau_act=self.n_tau_act, kappa=self.kappa)
         self.net.set_hparams(lr=self.lr)
         if self.cvar != 1.0:
@@ -150,7 +166,7 @@ class VecIQN:
     def save(self, path):
         """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory
         (with its generator and, prioritized, its tree), the counters, epsilon and the settings; `head` = 'iqn' tells the file from the
-        other loops', `prioritized` the memory's kind (a file without the key is a uniform one's)"""
+        other loops', `prioritized` the memory's kind (a file without the key is a uniform one's), `dueling` the net's (without the key: a plain IQN net's)"""
         host = lambda t: t.cpu().numpy()
         m, v, pows = self.net.adam_state()
         np.savez(self._npz(path), head=np.array([IQN_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
@@ -158,14 +174,14 @@ class VecIQN:
                  scalars=np.array([self.timeStep, self.seed, self.n, self.batch, self.fc_width, self.observe, self.explore, self.n_step,
                                    int(self.double_q), self.replace_target_iter], np.int64),
                  iqn=np.array([self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar], np.float64),
-                 prioritized=np.array([int(self.prioritized)], np.int64),
+                 prioritized=np.array([int(self.prioritized)], np.int64), dueling=np.array([int(self.dueling)], np.int64),
                  settings=np.array([self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon],
                                    np.float64),
                  env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob())
 
     def load(self, path):
         """the inverse of save(), into a VecIQN made with the same n_envs, batch, fc_width, n_step, (n_tau, n_tau_next, n_tau_act, kappa),
-        capacity, seed and memory kind (prioritized or not); the other settings of the file replace this object's"""
+        capacity, seed, memory kind (prioritized or not) and head kind (dueling or not); the other settings of the file replace this object's"""
         import torch
         from .vecbrain import checkpoint_head
         z = np.load(self._npz(path))
@@ -188,6 +204,10 @@ class VecIQN:
         if (int(q[0]), int(q[1]), int(q[2]), q[3]) != mine:
             raise ValueError(f"checkpoint {path} was written with (n_tau, n_tau_next, n_tau_act, kappa) = {(int(q[0]), int(q[1]), int(q[2]), q[3])}, "
                              f"this VecIQN has {mine}")
+        du = bool(int(z["dueling"][0])) if "dueling" in z.files else False
+        if du != self.dueling:
+            raise ValueError(f"checkpoint {path} was written by a VecIQN with a {head_kind(du)} IQN head, this VecIQN has a "
+                             f"{head_kind(self.dueling)} one (dueling={self.dueling})")
         dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
         self.net.load_params(z["online"], 0)
         self.net.load_params(z["target"], 1)

@@ -824,6 +824,32 @@ int fb_iqn_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q
                                  uint8_t *a_out, float *r_out, uint8_t *t_out, const float *tau, const float *tau_next, uint64_t seed,
                                  uint64_t step, double gamma, float *loss /*f32[1]*/, float *abs_err /*f32[B]*/, float *q_target,
                                  float *flat_grad, void *stream);
+/* ------------------------------------------------------------------ dueling IQN: value and advantage quantile streams
+ * The linear dueling head of this code base (V and the advantages read straight off fc1, BrainDuelingDQN.py:78-86) on the quantile function:
+ * both streams share g_k(tau) = h_k phi_k(tau), so the combine V(tau) + Adv_a(tau) - mean_a' Adv_a'(tau) is ONE effective column per action.
+ * A dueling IQN net (FB_ARCH_IQN_DUELING, fb_qnet_create_iqn_dueling: fb_qnet_create_iqn's arguments and checks, before any allocation) has
+ * the DUELING layout, then the embedding:
+ *   trunk, W_fc1, b_fc1, W_v[FC,1], b_v[1], W_a[FC,A], b_a[A], W_e[E,FC], b_e[FC]      (one flat vector for Adam, load / store / sync, the clip)
+ *   init        every weight by its own index: the part up to b_a is the FB_ARCH_DUELING net of that seed bit for bit (b_v = 0.01); b_e = 1.0
+ *   forward     all float32:
+ *                 m_k     = (sum_{c<A} W_a[k,c]) / (float)A            ascending c from 0.f
+ *                 We[k,a] = (W_v[k] + W_a[k,a]) - m_k
+ *                 be[a]   = (b_v + b_a[a]) - (sum_c b_a[c]) / (float)A      ascending c from 0.f
+ *                 theta(tau)_a = be[a] + sum_k (h_k phi_k(tau)) We[k,a]     IQN's sum over k, unchanged
+ *               theta, T, a* and the loss are IQN's with We / be where W_q / b_q stand (formed in place wherever they are read)
+ *   greedy Q    the fold block stays in the PLAIN layout, [b_fc1 | phibar_k * We[k,a] | be[a]]: for acting a dueling IQN net is a plain net
+ *               over its fold, as an IQN net is; no acting kernel is its own.  The fold is rebuilt wherever an IQN net's is.
+ *               fb_qnet_is_dist is 0
+ *   gradients   with gw[b,k] the taken column's gradient row of sample b, as IQN forms it:
+ *                 G_k = sum_b gw[b,k]   H_kc = sum_{b: a_b = c} gw[b,k]   (both over ascending b)
+ *                 dW_v[k] = G_k         dW_a[k,c] = H_kc - G_k / (float)A
+ *               b_v and b_a the same way from dl_b = sum_i dl_b/dtheta_i.  W_e, b_e, b_fc1, the trunk, the loss and the Adam tick as IQN's.
+ *               No atomics: equal inputs give equal bits
+ *   calls       every fb_qnet_*iqn* and fb_iqn_* call above, the prioritized ones and both loop steps included, takes either kind of net and
+ *               refuses what it refused; fb_qnet_create with arch 9 is refused
+ *   not offered noisy IQN, bf16, data parallel, riders of the train step, the split schedule. */
+#define FB_ARCH_IQN_DUELING 9
+int fb_qnet_create_iqn_dueling(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch, fb_qnet_t *out);
 
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);

@@ -3,7 +3,7 @@ says that the loop runs and learns, not how well.  The QR run to set beside it i
 steps and seed.
 
     python tools/learn_iqn.py [--envs 1024] [--lr 1e-5] [--steps 2000000] [--window 50000] [--explore 1000000] [--n-step 1] [--double]
-                              [--per] [--cvar 1.0] [--eval-envs 4096] [--seed 1] [--budget-s S] [--out FILE]
+                              [--per] [--dueling] [--cvar 1.0] [--eval-envs 4096] [--seed 1] [--budget-s S] [--out FILE]
 
 Every `window` steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and
 zeroed, so each row is the window's own figure.  Rows go to stdout, and are appended to --out when one is given.
@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--n-step", type=int, default=1)
     ap.add_argument("--double", action="store_true")
     ap.add_argument("--per", action="store_true", help="train from a prioritized memory (VecIQN(prioritized=True))")
+    ap.add_argument("--dueling", action="store_true", help="the dueling IQN net (VecIQN(dueling=True))")
     ap.add_argument("--cvar", type=float, default=1.0)
     ap.add_argument("--eval-envs", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=1)
@@ -46,9 +47,9 @@ def main():
 
         emit(f"# tools/learn_iqn.py on {torch.cuda.get_device_name(0)}: {' '.join(sys.argv[1:])}")
         v = VecIQN(a.envs, lr=a.lr, seed=a.seed, explore=a.explore, n_step=a.n_step, double_q=a.double, cvar=a.cvar, capacity=1_000_000,
-                   prioritized=a.per)
+                   prioritized=a.per, dueling=a.dueling)
         emit(f"# envs {a.envs}  batch {v.batch}  (N, N', K) ({v.n_tau}, {v.n_tau_next}, {v.n_tau_act})  kappa {v.kappa:g}  cvar {v.cvar:g}  "
-             f"double_q {v.double_q}  prioritized {v.prioritized}  n_step {v.n_step}  observe {v.observe}  lr {v.lr:g}  seed {a.seed}")
+             f"double_q {v.double_q}  prioritized {v.prioritized}  dueling {v.dueling}  n_step {v.n_step}  observe {v.observe}  lr {v.lr:g}  seed {a.seed}")
         emit("#   env_steps  train_steps  episodes  mean_score  max_score  pipes/episode       loss   epsilon   steps/s")
         t0 = t_run = time.time()
         v.stats.zero_()

@@ -2,7 +2,9 @@
 schedule (fb_vec_step_set_schedule(0)) at the same env count; us per train step alone (exported gradient) of the three; and us per
 acting forward (act_nib) of an IQN net against a plain net's, which should differ by nothing: the fold is refreshed behind Adam, not
 on the acting path.  The prioritized forms run beside them on prioritized memories of the same capacity: fb_iqn_per_step and fb_vec_step
-of 'qrper' -- over the uniform step they pay Memory.store's tree part, Memory.sample and Memory.batch_update.
+of 'qrper' -- over the uniform step they pay Memory.store's tree part, Memory.sample and Memory.batch_update.  The dueling IQN net
+(arch 'iqndueling') has a row beside every IQN row: its train step forms the effective column in place and splits the head's gradient,
+its acting path is the same plain head over the fold.
 
     python tools/time_iqn.py [--envs 256,1024,4096] [--batch 32] [--steps 300] [--warmup 100] [--repeats 5] [--out FILE]
 
@@ -20,11 +22,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from dqnflappybird_amd import _lib as L  # noqa: E402
-from dqnflappybird_amd.vec import (IqnPerStep, IqnStep, QNet, VecGameState, VecReplay, VecStep, iqn_per_train_from_replay,  # noqa: E402
+from dqnflappybird_amd.vec import (IQN_ARCHS, IqnPerStep, IqnStep, QNet, VecGameState, VecReplay, VecStep, iqn_per_train_from_replay,  # noqa: E402
                                    iqn_train_from_replay, train_from_replay)
 from tools.time_a2c import launch_floor, timed  # noqa: E402
 
-CONFIGS = {"fb_iqn_step (N 8, N' 8, K 32)": ("iqn", None), "fb_iqn_per_step (N 8, N' 8, K 32)": ("iqn", "per"), "fb_vec_step qr (N 51)": ("qr", "qr"),
+CONFIGS = {"fb_iqn_step (N 8, N' 8, K 32)": ("iqn", None), "fb_iqn_step dueling": ("iqndueling", None),
+           "fb_iqn_per_step (N 8, N' 8, K 32)": ("iqn", "per"), "fb_iqn_per_step dueling": ("iqndueling", "per"), "fb_vec_step qr (N 51)": ("qr", "qr"),
            "fb_vec_step qrper (N 51)": ("qr", "qrper"), "fb_vec_step double": ("plain", "double")}
 CAPACITY = 1_000_000
 
@@ -38,7 +41,7 @@ def pipeline(n_envs, arch, algo, batch):
     net.init_params(5, which=0); net.init_params(6, which=1)
     net.set_hparams(lr=1e-6)
     env.track_state(); env.observe(); rep.reset(env.frame_bits)
-    step = (IqnPerStep if per else IqnStep)(env, rep, net, batch, 0.99) if arch == "iqn" else VecStep(env, rep, net, batch, algo, 0.99)
+    step = (IqnPerStep if per else IqnStep)(env, rep, net, batch, 0.99) if arch in IQN_ARCHS else VecStep(env, rep, net, batch, algo, 0.99)
     return dict(env=env, net=net, rep=rep, step=step, arch=arch, algo=algo, per=per, k=0)
 
 
@@ -95,9 +98,9 @@ def main():
             leaf, ones = idx + (CAPACITY - 1), torch.ones(a.batch, dtype=torch.float32, device="cuda")      # (a prioritized memory is read at its leaves)
 
             def train_fn(c, p):
-                if p["arch"] == "iqn" and p["per"]:
+                if p["arch"] in IQN_ARCHS and p["per"]:
                     return lambda: iqn_per_train_from_replay(p["rep"], p["net"], leaf, ones, 0.99, seed=2, step=1, flat_grad=grads[c])
-                if p["arch"] == "iqn":
+                if p["arch"] in IQN_ARCHS:
                     return lambda: iqn_train_from_replay(p["rep"], p["net"], idx, 0.99, seed=2, step=1, flat_grad=grads[c])
                 if p["per"]:
                     return lambda: train_from_replay(p["rep"], p["net"], p["algo"], leaf, 0.99, flat_grad=grads[c], isw=ones, want_abs_err=True)
@@ -105,9 +108,9 @@ def main():
             for c, v in rounds({c: train_fn(c, p) for c, p in pipes.items()}, 20).items():
                 row(f"train B={a.batch}", n_envs, c.replace("fb_iqn_per_step", "iqn per").replace("fb_iqn_step", "iqn").replace("fb_vec_step ", ""), v)
             act = {c: (lambda p=p: p["net"].act_nib(p["env"].nib, 0.1, seed=2, step=3)) for c, p in pipes.items()
-                   if p["arch"] in ("iqn", "plain") and not p["per"]}
+                   if p["arch"] in IQN_ARCHS + ("plain",) and not p["per"]}
             for c, v in rounds(act, 20).items():
-                row("act_nib", n_envs, "iqn net (folded head)" if "iqn" in c else "plain net", v)
+                row("act_nib", n_envs, "dueling iqn net (folded head)" if "dueling" in c else "iqn net (folded head)" if "iqn" in c else "plain net", v)
             del pipes, grads, act
             torch.cuda.synchronize()
         L.check(L.lib().fb_vec_step_set_schedule(1), "fb_vec_step_set_schedule")
