@@ -122,10 +122,12 @@ def build_parser():
     parser.add_argument("--double", action="store_true", help="--model iqn | iqnper: the greedy next action from the online net (Double-DQN's target; --model rainbowiqn sets it)")
     parser.add_argument("--dueling", action="store_true", help="--model iqn | iqnper | rainbowiqn: the dueling IQN net (value and advantage quantile streams); "
                                                                 "--model rainbowiqn --dueling --n-step 3 is Rainbow-IQN without noisy nets")
-    parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper: the softmax temperature (default 0.03)")
-    parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper: the scale of the log-policy bonus (default 0.9); "
+    parser.add_argument("--munchausen", action="store_true", help="--model iqn | iqnper: Munchausen IQN -- the soft target and the log-policy bonus "
+                                                                   "(--tau, --alpha, --clip as for mdqn; not with --double)")
+    parser.add_argument("--tau", type=float, default=None, help="--model mdqn | mdqnper, --munchausen: the softmax temperature (default 0.03)")
+    parser.add_argument("--alpha", type=float, default=None, help="--model mdqn | mdqnper, --munchausen: the scale of the log-policy bonus (default 0.9); "
                                                                    "--model sac: the temperature (default 0.2)")
-    parser.add_argument("--clip", type=float, default=None, help="--model mdqn | mdqnper: the bonus's lower clip l0 (default -1)")
+    parser.add_argument("--clip", type=float, default=None, help="--model mdqn | mdqnper, --munchausen: the bonus's lower clip l0 (default -1)")
     parser.add_argument("--huber", type=float, default=None, help="scalar-head models with --vec: the Huber loss's delta (default 0 = the squared loss)")
     parser.add_argument("--max-grad-norm", type=float, default=None, help="--vec: clip the gradient's global norm to G before Adam (default 0 = no clipping)")
     parser.add_argument("--polyak", type=float, default=None, help="--vec: soft target updates, target += RHO (online - target) after every train step, "
@@ -178,6 +180,10 @@ def iqn_kwargs(args, parser):
     touches the GPU"""
     given = [n for n, v in (("--n-tau", args.n_tau), ("--n-tau-target", args.n_tau_target), ("--n-tau-act", args.n_tau_act), ("--cvar", args.cvar),
                             ("--double", args.double or None), ("--dueling", args.dueling or None)) if v is not None]
+    if args.munchausen and args.model not in ("iqn", "iqnper"):      # (rainbowiqn sets --double, which the soft target has no use for)
+        parser.error(f"--munchausen needs --model iqn or --model iqnper, not --model {args.model}"
+                     + (" (its --double target chooses a greedy next action; the Munchausen target has none)" if args.model == "rainbowiqn" else
+                        " (Munchausen-DQN on the scalar heads is --model mdqn | mdqnper)"))
     if args.model not in IQN_MODELS:
         if given:
             parser.error(f"{' / '.join(given)} need --model iqn, not --model {args.model}")
@@ -185,7 +191,7 @@ def iqn_kwargs(args, parser):
     if not args.vec:
         parser.error(f"--model {args.model} needs --vec: implicit quantile networks run in the vectorised loop only")
     for name, on in (("--noisy", args.noisy), ("--huber", args.huber is not None), ("--n-quantiles", args.n_quantiles is not None),
-                     ("--tau / --alpha / --clip", args.tau is not None or args.alpha is not None or args.clip is not None)):
+                     ("--tau / --alpha / --clip", not args.munchausen and (args.tau is not None or args.alpha is not None or args.clip is not None))):
         if on:
             parser.error(f"{name} is not an option of --model {args.model} (--n-tau, --n-tau-target, --n-tau-act, --kappa, --cvar, --double, --n-step, "
                          "--polyak, --max-grad-norm are)")
@@ -202,6 +208,14 @@ def iqn_kwargs(args, parser):
     kw["prioritized"] = args.model != "iqn"
     if args.dueling:                                     # (without the flag VecIQN's keywords are the ones of before)
         kw["dueling"] = True
+    if args.munchausen:                                  # (the same; --tau is the softmax temperature, VecIQN's `temp`)
+        from .veciqn import check_munchausen
+        try:
+            _, t, a, c = check_munchausen(True, 0.03 if args.tau is None else args.tau, 0.9 if args.alpha is None else args.alpha,
+                                          -1.0 if args.clip is None else args.clip, kw["double_q"])
+        except ValueError as e:
+            parser.error(str(e).replace("munchausen=True with double_q=True", "--munchausen with --double").replace("temp must", "--tau must"))
+        kw.update(munchausen=True, temp=t, alpha=a, clip=c)
     return kw
 
 

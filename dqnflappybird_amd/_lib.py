@@ -134,6 +134,8 @@ SIGNATURES = {
     "fb_qnet_create_iqn_dueling": [_i, _i, _i, _i, _i, _f, _i, _vp],
     "fb_qnet_set_iqn_risk": [_vp, _f],
     "fb_qnet_get_iqn": [_vp, _vp, _vp, _vp, _vp, _vp],
+    "fb_qnet_set_iqn_munchausen": [_vp, _i, _f, _f, _f],
+    "fb_qnet_get_iqn_munchausen": [_vp, _vp, _vp, _vp, _vp],
     "fb_qnet_forward_iqn": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp],
     "fb_iqn_draw_taus": [_i, _i, _u64, _u64, _i, _vp, _vp],
     "fb_qnet_iqn_train_step": [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _d, _vp, _vp, _vp, _vp],

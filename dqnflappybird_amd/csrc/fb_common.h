@@ -316,6 +316,10 @@ struct IqnLossArgs {
     // isw / abs_err, the prioritized form: both f32[B], both set (the weights in, l_b out); else both NULL.  foff: the offsets F is read with
     const float *isw; float *abs_err; NetOff foff; int dueling;
 };
+// What the loss launch takes: IqnLossArgs and, behind its last field, Munchausen IQN's five (fb_qnet_set_iqn_munchausen).  mu = 1: F is the
+// TARGET net's fold, arow0 = 2 B (s') and srow0 = B the first row of the slice that holds s through the target net; (temp, alpha, clip_lo)
+// the net's.  mu = 0: none of the five is read
+struct IqnLossMuArgs : IqnLossArgs { int mu; float temp, alpha, clip_lo; int srow0; };
 struct IqnGradArgs { int B, FC, A, N; NetOff off; IqnOff io; const float *dl, *gw, *dhf, *dpre, *ctab; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; int dueling; };
 void fb_iqn_launch_fold(hipStream_t st, const void *args);
 void fb_iqn_launch_head(hipStream_t st, const void *args);

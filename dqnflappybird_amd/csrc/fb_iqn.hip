@@ -6,7 +6,8 @@
 //   iqn_head_kernel   theta at the caller's tau (fb_qnet_forward_iqn); one workgroup per state
 //   iqn_loss_kernel   training, launch 1 of 2: per sample a*, the target quantiles, theta, the pairwise quantile Huber loss, d theta, then the
 //                     dhf row, the W_q-gradient row, the embedding's pre-activation gradients and the cosine rows; one workgroup per sample.
-//                     Its <.., true> instantiation is the prioritized form: importance weights in, the per-sample loss out as the priority
+//                     Its PW instantiations are the prioritized form: importance weights in, the per-sample loss out as the priority; its MU
+//                     instantiations form the Munchausen target (a soft policy over the target net's Qbar, no a*) in place of the hard one
 //   iqn_grad_kernel   training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_q, W_e, b_e; workgroup 0: b_q, the loss, Adam's tick
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
 // A dueling net (FB_ARCH_IQN_DUELING; the DU instantiations): W_v b_v W_a b_a where W_q b_q stood, read as the effective column
@@ -97,6 +98,25 @@ __device__ __forceinline__ void iqn_plain_head(const float *__restrict__ hf, int
     for (int a = 0; a < AT; a++) out[a] = a < A ? acc[a] + bq[a] : 0.f;
 }
 
+// Munchausen IQN (include/fbdqn.h), from the finished Qbar rows of the target net, qn = Qbar-(s', .) and qs = Qbar-(s, .), in fp32 over
+// ascending c: the soft policy at s', pi_c = e_c / S' with e_c = expf((qn_c - m') / temp), and t_c = (qn_c - m') - temp logf(S') (= temp ln pi_c,
+// never formed as a log of pi_c: finite when e_c underflows); the bonus alpha max((qs_a - m) - temp logf(S), l0) is mdqn_target's
+// expression (fb_qnet.hip).  Entries c >= A are masked by selects (pi_c = 0, t_c = 0)
+template <int AT>
+__device__ __forceinline__ void iqn_mu_policy(const float (&qn)[AT], const float (&qs)[AT], int A, int a_b, float temp, float alpha, float clip,
+                                              float (&pi)[AT], float (&tl)[AT], float &bonus) {
+    float mn = qn[0], ms = qs[0], qa = qs[0];
+#pragma unroll
+    for (int c = 1; c < AT; c++) { mn = c < A ? fmaxf(mn, qn[c]) : mn; ms = c < A ? fmaxf(ms, qs[c]) : ms; qa = c == a_b ? qs[c] : qa; }
+    float e[AT], sn = 0.f, ss = 0.f;
+#pragma unroll
+    for (int c = 0; c < AT; c++) { e[c] = c < A ? expf((qn[c] - mn) / temp) : 0.f; sn += e[c]; ss += c < A ? expf((qs[c] - ms) / temp) : 0.f; }
+    const float ln = temp * logf(sn);
+#pragma unroll
+    for (int c = 0; c < AT; c++) { pi[c] = e[c] / sn; tl[c] = c < A ? (qn[c] - mn) - ln : 0.f; }
+    bonus = alpha * fmaxf((qa - ms) - temp * logf(ss), clip);
+}
+
 // the cosine rows of the taus tq[0 .. M) into ct[M][64] (both LDS), by the whole workgroup; the caller synchronises
 __device__ __forceinline__ void iqn_cos_rows(const float *tq, int M, float *ct, int tid, int nthreads) {
     for (int q = tid; q < M * IQN_E; q += nthreads) ct[q] = iqn_cos(q & 63, tq[q >> 6]);
@@ -108,7 +128,9 @@ __device__ __forceinline__ void iqn_cos_rows(const float *tq, int M, float *ct, 
 // by the xor butterfly and its lane 0 adds the rounds up in order in part[wave][m][c]; out = b_q[c] + (((p_0 + p_1) + p_2) + p_3).
 // part: LDS, 4 * M * NC floats.  Ends behind a barrier: out is complete.  No load under a branch (a thread past FC reads unit 0, h = 0).
 // DU: a dueling net (AT: its action template), We[k, c] / be[c] where W_q[k, c] / b_q[c] stand
-template <int NC, int AT, bool DU>
+// WHO: a tag that gives a second caller of one (NC, AT, DU) a function of its own; the code is the same (the Munchausen loss passes 1: with
+// iqn_head_kernel's instantiation shared between two kernels, the compiler ordered two scalar instructions of the head kernel differently)
+template <int NC, int AT, bool DU, int WHO = 0>
 __device__ __forceinline__ void iqn_theta(const float *__restrict__ hf, int stot, int nks, int FC, int A, const float *__restrict__ P, const NetOff &off,
                                           const IqnOff &io, int row, int col, const float *ct, int M, float *part, float *out) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -219,10 +241,15 @@ __global__ __launch_bounds__(256) void iqn_head_kernel(IqnHeadArgs H) {
 // PW, the prioritized form (fb_qnet_iqn_per_train_step): w_b = isw[b] is multiplied into d theta_i LAST, dl[b][2] takes w_b l_b and
 // abs_err[b] the unweighted l_b (the priority); w = 1 leaves the bits of the uniform form.
 // DU, a dueling net: theta, T and the backward's column through We / be; a* over the fold with ITS offsets (L.foff, the plain layout's).
-template <int AT, bool PW, bool DU>
-__global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
+// MU, Munchausen IQN (include/fbdqn.h): no a*.  q' = Qbar-(s', .) and q = Qbar-(s, .) are the plain head over the TARGET net's fold at rows
+// 2 B + b and L.srow0 + b; theta-(s', c; tau'_j) of EVERY column c comes from one all-columns iqn_theta (the bits of the one-column calls);
+// thread j < N' forms V_j = sum_c pi_c (theta_cj - t_c) and T_j = (float)((R + bonus) + (done ? 0 : Gamma V_j)).  From theta of the online
+// column on it is the code of the other instantiations.  MU = false: the statements of before
+template <int AT, bool PW, bool DU, bool MU>
+__global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossMuArgs L) {
     __shared__ float ct[2 * IQN_MAXT * IQN_E];                    // the cosine rows of tau (N of them), then of tau' (N')
-    __shared__ float part[4 * IQN_MAXT];
+    __shared__ float part[4 * IQN_MAXT * (MU ? AT : 1)];
+    [[maybe_unused]] __shared__ float tall[MU ? IQN_MAXT * AT : 1];      // (MU: theta-(s', c; tau'_j) at [j * AT + c])
     __shared__ float tq[2 * IQN_MAXT];
     __shared__ float th[IQN_MAXT], tg[IQN_MAXT], dth[IQN_MAXT], rowl[IQN_MAXT];
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
@@ -242,21 +269,47 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossArgs L) {
     const bool done = L.term[b] != 0;
     [[maybe_unused]] float wb = 1.f;
     if constexpr (PW) wb = L.isw[b];
-    // a*: the first maximum of the plain head over the fold (every wave forms the same bits)
-    float qa[AT];
-    if constexpr (DU) iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qa);
-    else iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
-    int as = 0;
-    float qbest = qa[0];
+    if constexpr (MU) {
+        // the two Qbar rows of the target net (every wave, every lane forms the same bits), then the soft policy at s' and the bonus at (s, a)
+        float qn[AT], qs[AT];
+        if constexpr (DU) {
+            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qn);
+            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.srow0 + b, lane, qs);
+        } else {
+            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qn);
+            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.srow0 + b, lane, qs);
+        }
+        float pi[AT], tl[AT], bonus;
+        iqn_mu_policy<AT>(qn, qs, A, ab, L.temp, L.alpha, L.clip_lo, pi, tl, bonus);
+        __syncthreads();
+        iqn_theta<AT, AT, DU, 1>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off, L.io, 2 * B + b, 0, ct + N * IQN_E, Np, part, tall);
+        const int j = tid < Np ? tid : 0;                         // (no load under a branch: a thread past N' reads row 0 and drops it)
+        float V = 0.f;
 #pragma unroll
-    for (int c = 1; c < AT; c++) { const bool up = c < A && qa[c] > qbest; as = up ? c : as; qbest = up ? qa[c] : qbest; }
-    __syncthreads();
-    iqn_theta<1, AT, DU>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off, L.io, 2 * B + b, as, ct + N * IQN_E, Np, part, tg);
-    if (tid < Np) {
-        const double r = rf == 0.1f ? 0.1 : (double)rf;           // (the convention of every target here)
-        const float T = (float)(done ? r : r + L.gamma * (double)tg[tid]);
-        tg[tid] = T;
-        if (L.t_out) L.t_out[(size_t)b * Np + tid] = T;
+        for (int c = 0; c < AT; c++) { const float p = pi[c] * (tall[j * AT + c] - tl[c]); V += c < A ? p : 0.f; }
+        if (tid < Np) {
+            const double r = (rf == 0.1f ? 0.1 : (double)rf) + (double)bonus;      // (the convention of every target here; the bonus on terminal samples too)
+            const float T = (float)(done ? r : r + L.gamma * (double)V);
+            tg[tid] = T;
+            if (L.t_out) L.t_out[(size_t)b * Np + tid] = T;
+        }
+    } else {
+        // a*: the first maximum of the plain head over the fold (every wave forms the same bits)
+        float qa[AT];
+        if constexpr (DU) iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qa);
+        else iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
+        int as = 0;
+        float qbest = qa[0];
+#pragma unroll
+        for (int c = 1; c < AT; c++) { const bool up = c < A && qa[c] > qbest; as = up ? c : as; qbest = up ? qa[c] : qbest; }
+        __syncthreads();
+        iqn_theta<1, AT, DU>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off, L.io, 2 * B + b, as, ct + N * IQN_E, Np, part, tg);
+        if (tid < Np) {
+            const double r = rf == 0.1f ? 0.1 : (double)rf;       // (the convention of every target here)
+            const float T = (float)(done ? r : r + L.gamma * (double)tg[tid]);
+            tg[tid] = T;
+            if (L.t_out) L.t_out[(size_t)b * Np + tid] = T;
+        }
     }
     iqn_theta<1, AT, DU>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off, L.io, b, ab, ct, N, part, th);      // (its first barrier orders tg's stores too)
     if (tid < N) {                                                // the pairwise quantile Huber loss of row i, j ascending
@@ -409,10 +462,12 @@ template <class F> void with_actions(int A, F f) {
     if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
 }
 template <class F> void with_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-// the loss launch of either kind of net (L.dueling) at the head's action template and the prioritized form
+// the loss launch of either kind of net (L.dueling), with the hard or the Munchausen target (L.mu), at the head's action template and the prioritized form
 template <int AT, bool PW>
-void launch_loss(hipStream_t st, const IqnLossArgs &L) {
-    with_bool(L.dueling != 0, [&](auto du) { hipLaunchKernelGGL((iqn_loss_kernel<AT, PW, decltype(du)::value>), dim3(L.B), dim3(256), 0, st, L); });
+void launch_loss(hipStream_t st, const IqnLossMuArgs &L) {
+    with_bool(L.dueling != 0, [&](auto du) { with_bool(L.mu != 0, [&](auto mu) {
+        hipLaunchKernelGGL((iqn_loss_kernel<AT, PW, decltype(du)::value, decltype(mu)::value>), dim3(L.B), dim3(256), 0, st, L);
+    }); });
 }
 }  // namespace
 
@@ -432,8 +487,8 @@ void fb_iqn_launch_head(hipStream_t st, const void *args) {
     });
 }
 
-void fb_iqn_launch_loss(hipStream_t st, const void *args) {
-    IqnLossArgs L;
+void fb_iqn_launch_loss(hipStream_t st, const void *args) {        // (args: an IqnLossMuArgs)
+    IqnLossMuArgs L;
     memcpy(&L, args, sizeof(L));
     with_actions(L.A, [&](auto a) {           // (isw set: the prioritized form, which also writes abs_err)
         with_bool(L.isw != nullptr, [&](auto pw) {

@@ -4049,6 +4049,9 @@ struct fb_qnet {
     float *iqn_dpre, *iqn_ctab;
     // a dueling IQN net (FB_ARCH_IQN_DUELING, fb_qnet_create_iqn_dueling): off is the DUELING layout (W_v b_v W_a b_a), then W_e b_e; its fold
     // heff[w] = [b_fc1 | phibar * We | be] keeps the PLAIN layout, whose offsets are hoff: what reads head_base() as a plain net takes hoff
+    // Munchausen IQN (fb_qnet_set_iqn_munchausen): on / off and (temp, alpha, l0); read by the IQN train plans alone
+    int iqn_mu;
+    MdPar iqn_md;
 };
 // every field ac_grad_kernel touches through FbAdamHead sits where AdamDev has it
 static_assert(offsetof(AdamDev, b1pow) == offsetof(FbAdamHead, b1pow) && offsetof(AdamDev, b2pow) == offsetof(FbAdamHead, b2pow) &&
@@ -4274,6 +4277,7 @@ static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup,
         h->iqn_off.we = h->off.n; h->iqn_off.be = h->iqn_off.we + FB_IQN_COS * fc_width;
         h->off.n = h->iqn_off.be + fc_width;
         h->iqn_n = g_iqn_create[0]; h->iqn_np = g_iqn_create[1]; h->iqn_k = g_iqn_create[2]; h->iqn_eta = 1.f;
+        h->iqn_mu = 0; h->iqn_md = MdPar{0.03f, 0.9f, -1.f};      // (Munchausen IQN: off, the paper's values)
     }
     h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : is_iqnd(h) ? make_off(fc_width, n_actions, 0) : h->off;      // (a dueling IQN net: its fold's)
     h->n = h->off.n;
@@ -4596,7 +4600,8 @@ struct Plan {
     // an IQN net.  Forward plans with iqn_theta set: theta f32[rows][iqn_m][A] at iqn_tau instead of the plain head over the fold.  Train
     // plans: three slices as FB_ALGO_DOUBLE's; iqn_tau / iqn_tau_next (or NULL: the draws of p.seed / p.step), iqn_double: a* from the online net;
     // p.y: T f32[B][N'] or NULL
-    const float *iqn_tau, *iqn_tau_next; int iqn_m; float *iqn_theta; bool iqn_double;
+    // iqn_mu: the Munchausen target (the net's setting when the plan was made): the slice at rows B .. is s through the TARGET net
+    const float *iqn_tau, *iqn_tau_next; int iqn_m; float *iqn_theta; bool iqn_double, iqn_mu;
 };
 
 // A runtime value as a template argument: f is a generic lambda and gets a tag whose ::value is a constant expression, so that a kernel
@@ -4840,7 +4845,7 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
 static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     const int B = p.B, FC = h->FC;
     if (c.iqn) {                                 // IQN: per-sample a* / T / theta / loss / d theta / dhf, then the per-unit reductions (fb_iqn.hip)
-        IqnLossArgs L;
+        IqnLossMuArgs L;                         // (IqnLossArgs, then Munchausen's fields: all zero = the hard target)
         memset(&L, 0, sizeof(L));
         L.hf = h->hf; L.P0 = h->params[0]; L.P1 = h->params[1]; L.F = head_base(h, h->params[p.iqn_double ? 0 : 1]); L.arow0 = p.iqn_double ? B : 2 * B;
         L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B; L.N = h->iqn_n; L.Np = h->iqn_np;
@@ -4850,6 +4855,10 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         L.dl = h->ac_dl; L.gw = h->ac_xs; L.dhf = h->dhf; L.dpre = h->iqn_dpre; L.ctab = h->iqn_ctab; L.t_out = p.y;
         L.isw = p.isw; L.abs_err = p.abs_err;    // (both set: the prioritized form; the uniform calls leave both NULL)
         L.foff = h->hoff; L.dueling = is_iqnd(h) ? 1 : 0;       // (L.F is a fold: the plain layout's offsets, whatever the net's)
+        if (p.iqn_mu) {                          // Munchausen: both Qbar rows over the TARGET net's fold, s at rows B .., s' at rows 2 B .. (iqn_train_plan)
+            L.mu = 1; L.temp = h->iqn_md.tau; L.alpha = h->iqn_md.alpha; L.clip_lo = h->iqn_md.clip;
+            L.F = head_base(h, h->params[1]); L.arow0 = 2 * B; L.srow0 = B;
+        }
         fb_iqn_launch_loss(c.st, &L);
         const IqnGradArgs gA{B, FC, h->A, h->iqn_n, h->off, h->iqn_off, h->ac_dl, h->ac_xs, h->dhf, h->iqn_dpre, h->iqn_ctab, p.G, p.loss, h->gmax,
                              reinterpret_cast<FbAdamHead *>(h->adam), p.tick, is_iqnd(h) ? 1 : 0};
@@ -5843,6 +5852,29 @@ extern "C" int fb_qnet_get_iqn(fb_qnet_t h, int *n_tau_host, int *n_tau_next_hos
     return FB_OK;
 }
 
+// Munchausen IQN: a host-side setting the train plans made after it read (fb_qnet_set_huber's pattern)
+extern "C" int fb_qnet_set_iqn_munchausen(fb_qnet_t h, int on, float temp, float alpha, float clip_lo) {
+    FB_REQUIRE(h, "fb_qnet_set_iqn_munchausen: NULL handle");
+    FB_REQUIRE(is_iqn(h), "fb_qnet_set_iqn_munchausen: not an IQN net (fb_qnet_create_iqn; a scalar net takes fb_qnet_set_munchausen)");
+    FB_REQUIRE(on == 0 || on == 1, "fb_qnet_set_iqn_munchausen: on must be 0 or 1 (got %d)", on);
+    FB_REQUIRE(isfinite(temp) && temp > 0.f, "fb_qnet_set_iqn_munchausen: temp must be finite and > 0 (got %g)", (double)temp);
+    FB_REQUIRE(alpha >= 0.f && alpha <= 1.f, "fb_qnet_set_iqn_munchausen: alpha must be in [0, 1] (got %g)", (double)alpha);
+    FB_REQUIRE(isfinite(clip_lo) && clip_lo <= 0.f, "fb_qnet_set_iqn_munchausen: the clip l0 must be finite and <= 0 (got %g)", (double)clip_lo);
+    h->iqn_mu = on;
+    h->iqn_md = MdPar{temp, alpha, clip_lo};
+    return FB_OK;
+}
+
+extern "C" int fb_qnet_get_iqn_munchausen(fb_qnet_t h, int *on_host, float *temp_host, float *alpha_host, float *clip_lo_host) {
+    FB_REQUIRE(h, "fb_qnet_get_iqn_munchausen: NULL handle");
+    FB_REQUIRE(is_iqn(h), "fb_qnet_get_iqn_munchausen: not an IQN net (fb_qnet_create_iqn; a scalar net takes fb_qnet_get_munchausen)");
+    if (on_host) *on_host = h->iqn_mu;
+    if (temp_host) *temp_host = h->iqn_md.tau;
+    if (alpha_host) *alpha_host = h->iqn_md.alpha;
+    if (clip_lo_host) *clip_lo_host = h->iqn_md.clip;
+    return FB_OK;
+}
+
 extern "C" int fb_qnet_forward_iqn(fb_qnet_t h, int which, const uint8_t *states, int batch, const float *tau, int M, float *theta, void *stream) {
     FB_REQUIRE(h && states && tau && theta && (which == 0 || which == 1), "fb_qnet_forward_iqn: bad argument");
     FB_REQUIRE(is_iqn(h), "fb_qnet_forward_iqn: not an IQN net (fb_qnet_create_iqn)");
@@ -5856,6 +5888,7 @@ extern "C" int fb_qnet_forward_iqn(fb_qnet_t h, int which, const uint8_t *states
 int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int B, double gamma, const char *who) {
     FB_REQUIRE(h && is_iqn(h), "%s: not an IQN net (fb_qnet_create_iqn)", who);
     FB_REQUIRE(double_q == 0 || double_q == 1, "%s: double_q must be 0 or 1 (got %d)", who, double_q);
+    FB_REQUIRE(!(h->iqn_mu && double_q), "%s: double_q = 1 on a net with Munchausen on (fb_qnet_set_iqn_munchausen): the soft target has no a* to choose", who);
     if (const int rb = check_batch(h, B, who)) return rb;
     return check_gamma01(gamma, who);
 }
@@ -5865,6 +5898,9 @@ static Plan iqn_train_plan(fb_qnet *h, int double_q, int B, const uint8_t *s, co
                            float *flat_grad, const FbRingSrc *ring) {
     Plan p = three_slice_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, ring);
     p.iqn_tau = tau; p.iqn_tau_next = tau_next; p.iqn_double = double_q != 0; p.seed = seed; p.step = step;
+    // Munchausen: the online net's s' slice is read by double_q alone, which is refused with it; its rows take s through the TARGET net
+    // (fshift 0: plan_train_tail has left it alone), as FB_ALGO_MDQN's third slice does.  Both target slices are consecutive: one pass
+    if (h->iqn_mu) { p.iqn_mu = true; p.sl.s[1] = Slice{h->params[1], s, B, B, h->w1s[1], 0}; }
     return p;
 }
 

@@ -865,6 +865,21 @@ class QNet:
         e = check_iqn(1, 1, 1, 1.0, eta, self.A)[4]
         L.check(L.lib().fb_qnet_set_iqn_risk(self.h, e), "fb_qnet_set_iqn_risk")
 
+    def set_iqn_munchausen(self, on, temp=MDQN_DEFAULTS[0], alpha=MDQN_DEFAULTS[1], clip=MDQN_DEFAULTS[2]):
+        """Munchausen IQN on / off and its (temp, alpha, l0) (fb_qnet_set_iqn_munchausen): the IQN train steps issued after it form the soft
+        target with the log-policy bonus; on refuses double_q.  temp is Munchausen-DQN's tau (tau is the quantile fraction here)"""
+        self._need_iqn("set_iqn_munchausen")
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f"on must be True or False, got {on!r}")
+        L.check(L.lib().fb_qnet_set_iqn_munchausen(self.h, int(on), float(temp), float(alpha), float(clip)), "fb_qnet_set_iqn_munchausen")
+
+    def iqn_munchausen(self):
+        """the net's (on, temp, alpha, l0) (fb_qnet_get_iqn_munchausen)"""
+        self._need_iqn("iqn_munchausen")
+        o, t, a, c = C.c_int(), C.c_float(), C.c_float(), C.c_float()
+        L.check(L.lib().fb_qnet_get_iqn_munchausen(self.h, C.byref(o), C.byref(t), C.byref(a), C.byref(c)), "fb_qnet_get_iqn_munchausen")
+        return bool(o.value), t.value, a.value, c.value
+
     def iqn(self):
         """the net's (n_tau, n_tau_next, n_tau_act, kappa, eta) (fb_qnet_get_iqn)"""
         self._need_iqn("iqn")

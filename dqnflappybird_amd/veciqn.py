@@ -15,6 +15,10 @@ without the dueling and the noisy head.
 
 dueling=True: the dueling IQN net (QNet arch 'iqndueling': value and advantage quantile streams, one effective column per action) in the
 same loops; with prioritized, double_q and n_step = 3 this is Rainbow-IQN without noisy nets.
+
+munchausen=True: Munchausen IQN (Vieillard, Pietquin & Geist 2020) -- the target becomes the soft value under softmax(Qbar- / temp) of the
+target net plus the clipped log-policy bonus alpha max(temp ln pi-(a|s), clip) on the reward (QNet.set_iqn_munchausen); everything else,
+the memory kinds, the dueling net, n-step returns and CVaR acting included, is unchanged.  It has no greedy next action: double_q is refused.
 """
 import numpy as np
 
@@ -73,6 +77,26 @@ def check_dueling(dueling):
     return bool(dueling)
 
 
+def check_munchausen(munchausen, temp, alpha, clip, double_q=False):
+    """VecIQN's Munchausen settings, checked apart from check_args (whose positional parameters stay as they are) -> (on, temp, alpha, l0);
+    the three values are checked whether or not the target is on (the net holds them either way)"""
+    from .vec import check_munchausen as check_values
+    if not isinstance(munchausen, (bool, np.bool_)):
+        raise ValueError(f"munchausen must be True or False, got {munchausen!r}")
+    try:
+        t, a, c = check_values(temp, alpha, clip)
+    except ValueError as e:
+        raise ValueError(str(e).replace("tau must", "temp must")) from None
+    if munchausen and double_q:
+        raise ValueError("munchausen=True with double_q=True: the Munchausen target is a soft value over all actions and has no greedy next action "
+                         "for the online net to choose")
+    return bool(munchausen), t, a, c
+
+
+def target_kind(munchausen):
+    return "Munchausen" if munchausen else "hard"
+
+
 def head_kind(dueling):
     return "dueling" if dueling else "plain"
 
@@ -84,20 +108,23 @@ def replay_kind(prioritized):
 class VecIQN:
     def __init__(self, n_envs, batch=32, double_q=False, n_step=1, n_tau=8, n_tau_next=8, n_tau_act=32, kappa=1.0, cvar=1.0, polyak=0.0,
                  replace_target_iter=500, observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99, lr=1e-6,
-                 max_grad_norm=0, fc_width=512, seed=0, capacity=None, prioritized=False, dueling=False):
+                 max_grad_norm=0, fc_width=512, seed=0, capacity=None, prioritized=False, dueling=False,
+                 munchausen=False, temp=0.03, alpha=0.9, clip=-1.0):
         """n_envs games; every step trains one minibatch of `batch` transitions (<= n_envs, <= 256) once more than `observe` steps have
         filled the memory.  n_tau / n_tau_next: the tau sampled per transition for the online / target quantiles; n_tau_act: the acting
         grid; kappa: the quantile Huber threshold; cvar = eta in (0, 1]: act on CVaR_eta (1 = the mean).  double_q: a* from the online
         net.  n_step > 1: n-step returns.  The epsilon schedule (observe / explore / initial / final) and the periodic target copy are
         VecBrain's; polyak > 0 replaces the copy by soft updates; lr is Adam's; max_grad_norm=G > 0 clips the gradient's global norm.
         prioritized: train from a prioritized memory (importance-weighted loss, the per-sample loss as the priority).
-        dueling: the dueling IQN net (value and advantage quantile streams) instead of the plain one."""
+        dueling: the dueling IQN net (value and advantage quantile streams) instead of the plain one.
+        munchausen: the Munchausen target with the softmax temperature temp, the bonus's scale alpha and its lower clip (not with double_q)."""
         (self.n, self.batch, self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar, self.n_step, self.polyak, self.replace_target_iter,
          self.observe, self.explore, self.initial_epsilon, self.final_epsilon, self.gamma, self.lr, self.max_grad_norm, self.capacity) = check_args(
             n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step, polyak, replace_target_iter, observe, explore, initial_epsilon,
             final_epsilon, gamma, lr, max_grad_norm, capacity)
         self.prioritized = check_prioritized(prioritized)
         self.dueling = check_dueling(dueling)
+        self.munchausen, self.temp, self.alpha, self.clip = check_munchausen(munchausen, temp, alpha, clip, bool(double_q))
         from .vec import QNet, VecGameState, VecReplay
         self.double_q = bool(double_q)
         self.seed = int(seed)
@@ -119,6 +146,8 @@ class VecIQN:
             self.net.set_iqn_risk(self.cvar)
         if self.max_grad_norm:
             self.net.set_max_grad_norm(self.max_grad_norm)
+        if self.munchausen:                                  # (off: the net is never touched)
+            self.net.set_iqn_munchausen(True, self.temp, self.alpha, self.clip)
         self.net.init_params(seed=self.seed, which=0)
         self.net.sync_target()
         self.nib = self.env.track_state()
@@ -166,7 +195,8 @@ class VecIQN:
     def save(self, path):
         """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory
         (with its generator and, prioritized, its tree), the counters, epsilon and the settings; `head` = 'iqn' tells the file from the
-        other loops', `prioritized` the memory's kind (a file without the key is a uniform one's), `dueling` the net's (without the key: a plain IQN net's)"""
+        other loops', `prioritized` the memory's kind (a file without the key is a uniform one's), `dueling` the net's (without the key: a plain IQN net's),
+        `munchausen` = (on, temp, alpha, clip) the target's (without the key: the hard target)"""
         host = lambda t: t.cpu().numpy()
         m, v, pows = self.net.adam_state()
         np.savez(self._npz(path), head=np.array([IQN_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
@@ -175,13 +205,15 @@ class VecIQN:
                                    int(self.double_q), self.replace_target_iter], np.int64),
                  iqn=np.array([self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar], np.float64),
                  prioritized=np.array([int(self.prioritized)], np.int64), dueling=np.array([int(self.dueling)], np.int64),
+                 munchausen=np.array([float(self.munchausen), self.temp, self.alpha, self.clip], np.float64),
                  settings=np.array([self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon],
                                    np.float64),
                  env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob())
 
     def load(self, path):
         """the inverse of save(), into a VecIQN made with the same n_envs, batch, fc_width, n_step, (n_tau, n_tau_next, n_tau_act, kappa),
-        capacity, seed, memory kind (prioritized or not) and head kind (dueling or not); the other settings of the file replace this object's"""
+        capacity, seed, memory kind (prioritized or not), head kind (dueling or not) and target (munchausen or not, and its temp, alpha,
+        clip); the other settings of the file replace this object's"""
         import torch
         from .vecbrain import checkpoint_head
         z = np.load(self._npz(path))
@@ -208,6 +240,13 @@ class VecIQN:
         if du != self.dueling:
             raise ValueError(f"checkpoint {path} was written by a VecIQN with a {head_kind(du)} IQN head, this VecIQN has a "
                              f"{head_kind(self.dueling)} one (dueling={self.dueling})")
+        mu = [float(x) for x in z["munchausen"]] if "munchausen" in z.files else [0.0]
+        if bool(mu[0]) != self.munchausen:
+            raise ValueError(f"checkpoint {path} was written by a VecIQN with the {target_kind(bool(mu[0]))} target, this VecIQN has the "
+                             f"{target_kind(self.munchausen)} one (munchausen={self.munchausen})")
+        if self.munchausen and tuple(mu[1:]) != (self.temp, self.alpha, self.clip):
+            raise ValueError(f"checkpoint {path} was trained with munchausen (temp, alpha, clip) = {tuple(mu[1:])}, this VecIQN has "
+                             f"{(self.temp, self.alpha, self.clip)}")
         dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
         self.net.load_params(z["online"], 0)
         self.net.load_params(z["target"], 1)

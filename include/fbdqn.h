@@ -847,9 +847,40 @@ int fb_iqn_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q
  *               No atomics: equal inputs give equal bits
  *   calls       every fb_qnet_*iqn* and fb_iqn_* call above, the prioritized ones and both loop steps included, takes either kind of net and
  *               refuses what it refused; fb_qnet_create with arch 9 is refused
- *   not offered noisy IQN, bf16, data parallel, riders of the train step, the split schedule. */
+ *   not offered noisy IQN, bf16, data parallel, riders, the split schedule; Munchausen with double_q. */
 #define FB_ARCH_IQN_DUELING 9
 int fb_qnet_create_iqn_dueling(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch, fb_qnet_t *out);
+/* ------------------------------------------------------------------ Munchausen IQN (M-IQN; Vieillard, Pietquin & Geist 2020, section 4)
+ * Munchausen-DQN's soft bootstrap and log-policy bonus on IQN's target.  A setting of an IQN net (either arch): off in a new net, which
+ * then holds (temp, alpha, l0) = (0.03, 0.9, -1).  `temp` is Munchausen-DQN's tau; tau is the quantile fraction everywhere in IQN.  Off: every
+ * call is what it was, bit for bit.  On, for sample b of every IQN training call (gathered, ring-fed, the prioritized ones, both loop steps):
+ *   forward     three slices still: s through the online net, s through the TARGET net (where s' through the online net stood: only
+ *               double_q read it), s' through the target net
+ *   Qbar rows   q' = Qbar-(s', .) and q = Qbar-(s, .): the plain head over the TARGET net's fold block, the bits fb_qnet_forward(FB_NET_TARGET)
+ *               returns and the acting path would read.  The net's CVaR eta is IN them (the fold's grid is eta tauhat): the soft policy is
+ *               over what the agent acts on
+ *   policy      at s', float32, ascending c:  m' = max_c q'_c;  e_c = expf((q'_c - m') / temp);  S' = sum_c e_c (from 0.f);  pi_c = e_c / S';
+ *               t_c = (q'_c - m') - temp * logf(S')   (= temp ln pi_c; never formed as a log of pi_c, so finite when e_c underflows to 0)
+ *   soft value  V_j = sum_c pi_c * (theta_tgt(s', c; tau'_j) - t_c), j < N': ascending c from 0.f, a multiply then an add (no fma); theta_tgt
+ *               of every column has the bits the one-column form of the hard target gives it
+ *   bonus       alpha * fmaxf((q_a - m) - temp * logf(S), l0),  m = max_c q_c, S = sum_c expf((q_c - m) / temp), a = the stored action (one
+ *               >= A reads A - 1): Munchausen-DQN's expression over q
+ *   target      T_j = (float)((r + (double)bonus) + (done ? 0 : gamma * (double)V_j)), r = (R == 0.1f) ? 0.1 : (double)R, float64, rounded
+ *               once.  The bonus is added on terminal transitions too.  An n-step memory: R is the n-step return, gamma the bootstrap's
+ *               Gamma = gamma^n, and only the first step's bonus (that of (s, a)) exists -- Munchausen-DQN's rules
+ *   unchanged   theta_i, u_ij, the loss, dl_b/dtheta_i, abs_err = l_b, the priority convention, the importance weight multiplied last, the
+ *               tau draws, q_target = T, the gradient kernel and everything behind it.  There is no a*, no argmax anywhere
+ *   limits      temp -> 0 with alpha = 0: once every gap of q' is >= 104 temp, pi is exactly one-hot, t = 0 there, and T, the loss and the
+ *               gradient are the hard target's (double_q = 0) bit for bit.  l0 = 0: the bonus is exactly 0 (its argument is <= 0)
+ * fb_qnet_set_iqn_munchausen: FB_ERR_INVALID before anything changes: a net that is not an IQN net, on not 0 / 1, temp not finite or <= 0,
+ *   alpha outside [0, 1], l0 not finite or > 0.  A host-side setting read by the calls issued after it.
+ * fb_qnet_get_iqn_munchausen: the current values [host] (any of the pointers may be NULL); FB_ERR_INVALID on a net that is not an IQN net.
+ * fb_qnet_set_munchausen / _get_munchausen keep refusing an IQN net.
+ *   refused     FB_ERR_INVALID before any launch, push or counter change: double_q = 1 in any IQN training call or loop step on a net with
+ *               the setting on (the soft target has no a* for the online net to choose)
+ *   not offered noisy IQN, bf16, data parallel, riders, the split schedule; Munchausen with double_q. */
+int fb_qnet_set_iqn_munchausen(fb_qnet_t h, int on, float temp, float alpha, float clip_lo);
+int fb_qnet_get_iqn_munchausen(fb_qnet_t h, int *on_host, float *temp_host, float *alpha_host, float *clip_lo_host);
 
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);

@@ -3,7 +3,8 @@ says that the loop runs and learns, not how well.  The QR run to set beside it i
 steps and seed.
 
     python tools/learn_iqn.py [--envs 1024] [--lr 1e-5] [--steps 2000000] [--window 50000] [--explore 1000000] [--n-step 1] [--double]
-                              [--per] [--dueling] [--cvar 1.0] [--eval-envs 4096] [--seed 1] [--budget-s S] [--out FILE]
+                              [--per] [--dueling] [--munchausen [--temp 0.03] [--alpha 0.9] [--clip -1]] [--cvar 1.0] [--eval-envs 4096]
+                              [--seed 1] [--budget-s S] [--out FILE]
 
 Every `window` steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and
 zeroed, so each row is the window's own figure.  Rows go to stdout, and are appended to --out when one is given.
@@ -32,6 +33,10 @@ def main():
     ap.add_argument("--double", action="store_true")
     ap.add_argument("--per", action="store_true", help="train from a prioritized memory (VecIQN(prioritized=True))")
     ap.add_argument("--dueling", action="store_true", help="the dueling IQN net (VecIQN(dueling=True))")
+    ap.add_argument("--munchausen", action="store_true", help="the Munchausen target (VecIQN(munchausen=True)); not with --double")
+    ap.add_argument("--temp", type=float, default=0.03, help="--munchausen: the softmax temperature")
+    ap.add_argument("--alpha", type=float, default=0.9, help="--munchausen: the scale of the log-policy bonus")
+    ap.add_argument("--clip", type=float, default=-1.0, help="--munchausen: the bonus's lower clip l0")
     ap.add_argument("--cvar", type=float, default=1.0)
     ap.add_argument("--eval-envs", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=1)
@@ -47,9 +52,10 @@ def main():
 
         emit(f"# tools/learn_iqn.py on {torch.cuda.get_device_name(0)}: {' '.join(sys.argv[1:])}")
         v = VecIQN(a.envs, lr=a.lr, seed=a.seed, explore=a.explore, n_step=a.n_step, double_q=a.double, cvar=a.cvar, capacity=1_000_000,
-                   prioritized=a.per, dueling=a.dueling)
+                   prioritized=a.per, dueling=a.dueling, munchausen=a.munchausen, temp=a.temp, alpha=a.alpha, clip=a.clip)
         emit(f"# envs {a.envs}  batch {v.batch}  (N, N', K) ({v.n_tau}, {v.n_tau_next}, {v.n_tau_act})  kappa {v.kappa:g}  cvar {v.cvar:g}  "
-             f"double_q {v.double_q}  prioritized {v.prioritized}  dueling {v.dueling}  n_step {v.n_step}  observe {v.observe}  lr {v.lr:g}  seed {a.seed}")
+             f"double_q {v.double_q}  prioritized {v.prioritized}  dueling {v.dueling}  n_step {v.n_step}  observe {v.observe}  lr {v.lr:g}  seed {a.seed}"
+             + (f"  munchausen (temp, alpha, clip) ({v.temp:g}, {v.alpha:g}, {v.clip:g})" if v.munchausen else ""))
         emit("#   env_steps  train_steps  episodes  mean_score  max_score  pipes/episode       loss   epsilon   steps/s")
         t0 = t_run = time.time()
         v.stats.zero_()

@@ -4,7 +4,8 @@ acting forward (act_nib) of an IQN net against a plain net's, which should diffe
 on the acting path.  The prioritized forms run beside them on prioritized memories of the same capacity: fb_iqn_per_step and fb_vec_step
 of 'qrper' -- over the uniform step they pay Memory.store's tree part, Memory.sample and Memory.batch_update.  The dueling IQN net
 (arch 'iqndueling') has a row beside every IQN row: its train step forms the effective column in place and splits the head's gradient,
-its acting path is the same plain head over the fold.
+its acting path is the same plain head over the fold.  Munchausen IQN (QNet.set_iqn_munchausen, the paper's (0.03, 0.9, -1)) has a row
+beside the plain IQN rows: the same three slices, an all-columns theta of the target net and one more plain head inside the loss launch.
 
     python tools/time_iqn.py [--envs 256,1024,4096] [--batch 32] [--steps 300] [--warmup 100] [--repeats 5] [--out FILE]
 
@@ -26,15 +27,19 @@ from dqnflappybird_amd.vec import (IQN_ARCHS, IqnPerStep, IqnStep, QNet, VecGame
                                    iqn_train_from_replay, train_from_replay)
 from tools.time_a2c import launch_floor, timed  # noqa: E402
 
-CONFIGS = {"fb_iqn_step (N 8, N' 8, K 32)": ("iqn", None), "fb_iqn_step dueling": ("iqndueling", None),
-           "fb_iqn_per_step (N 8, N' 8, K 32)": ("iqn", "per"), "fb_iqn_per_step dueling": ("iqndueling", "per"), "fb_vec_step qr (N 51)": ("qr", "qr"),
+MIQN = "munchausen"                                 # (in a config's name: the IQN net of that row has the Munchausen target on)
+CONFIGS = {"fb_iqn_step (N 8, N' 8, K 32)": ("iqn", None), "fb_iqn_step munchausen": ("iqn", None), "fb_iqn_step dueling": ("iqndueling", None),
+           "fb_iqn_per_step (N 8, N' 8, K 32)": ("iqn", "per"), "fb_iqn_per_step munchausen": ("iqn", "per"),
+           "fb_iqn_per_step dueling": ("iqndueling", "per"), "fb_vec_step qr (N 51)": ("qr", "qr"),
            "fb_vec_step qrper (N 51)": ("qr", "qrper"), "fb_vec_step double": ("plain", "double")}
 CAPACITY = 1_000_000
 
 
-def pipeline(n_envs, arch, algo, batch):
+def pipeline(n_envs, arch, algo, batch, munchausen=False):
     env = VecGameState(n_envs, seed=1)
     net = QNet(2, 512, arch, max_batch=max(n_envs, 256))
+    if munchausen:
+        net.set_iqn_munchausen(True)
     per = algo in ("per", "qrper")                   # (a prioritized memory: the numpy generator, the reference-order tree)
     rep = VecReplay(CAPACITY, n_envs, prioritized=per)
     rep.seed(3, None if per else "cpython")
@@ -89,7 +94,7 @@ def main():
         L.check(L.lib().fb_vec_step_set_schedule(0), "fb_vec_step_set_schedule")      # the one-stream order: what fb_iqn_step runs in
         emit("#  what           envs  config                             median       min       max")
         for n_envs in [int(x) for x in a.envs.split(",")]:
-            pipes = {c: pipeline(n_envs, arch, algo, a.batch) for c, (arch, algo) in CONFIGS.items()}
+            pipes = {c: pipeline(n_envs, arch, algo, a.batch, MIQN in c) for c, (arch, algo) in CONFIGS.items()}
             for c, v in rounds({c: (lambda p=p: one(p)) for c, p in pipes.items()}, a.warmup).items():
                 row("loop step", n_envs, c, v)
             idx = (torch.arange(a.batch, dtype=torch.int64) * 7).cuda()
@@ -108,7 +113,7 @@ def main():
             for c, v in rounds({c: train_fn(c, p) for c, p in pipes.items()}, 20).items():
                 row(f"train B={a.batch}", n_envs, c.replace("fb_iqn_per_step", "iqn per").replace("fb_iqn_step", "iqn").replace("fb_vec_step ", ""), v)
             act = {c: (lambda p=p: p["net"].act_nib(p["env"].nib, 0.1, seed=2, step=3)) for c, p in pipes.items()
-                   if p["arch"] in IQN_ARCHS + ("plain",) and not p["per"]}
+                   if p["arch"] in IQN_ARCHS + ("plain",) and not p["per"] and MIQN not in c}
             for c, v in rounds(act, 20).items():
                 row("act_nib", n_envs, "dueling iqn net (folded head)" if "dueling" in c else "iqn net (folded head)" if "iqn" in c else "plain net", v)
             del pipes, grads, act
