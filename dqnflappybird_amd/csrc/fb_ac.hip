@@ -12,7 +12,6 @@
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
 #include "fb_common.h"
 #include <math.h>
-#include <type_traits>
 
 namespace {
 #include "fb_head.h"
@@ -338,26 +337,17 @@ __global__ __launch_bounds__(256) void ac_grad_kernel(AcGradArgs L) {
     }
 }
 
-template <class F> void with_actions(int A, F f) {
-    if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
-}
 }  // namespace
 
-void fb_ac_launch_head(hipStream_t st, const void *args) {
-    AcHeadArgs H;
-    memcpy(&H, args, sizeof(H));
+void fb_ac_launch_head(hipStream_t st, const AcHeadArgs &H) {
     with_actions(H.A, [&](auto a) { hipLaunchKernelGGL(ac_head_kernel<decltype(a)::value>, dim3((H.rows + 3) / 4), dim3(256), 0, st, H); });
 }
 
-void fb_ac_launch_loss(hipStream_t st, const void *args) {
-    AcLossArgs L;
-    memcpy(&L, args, sizeof(L));
+void fb_ac_launch_loss(hipStream_t st, const AcLossArgs &L) {
     with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(ac_loss_kernel<decltype(a)::value>, dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
 }
 
-void fb_ac_launch_ppo_loss(hipStream_t st, const void *args) {
-    PpoLossArgs Q;
-    memcpy(&Q, args, sizeof(Q));
+void fb_ac_launch_ppo_loss(hipStream_t st, const PpoLossArgs &Q) {
     const dim3 grid((Q.a.B + 3) / 4);
     with_actions(Q.a.A, [&](auto a) {
         if (Q.sel) hipLaunchKernelGGL((ppo_loss_kernel<decltype(a)::value, true>), grid, dim3(256), 0, st, Q);
@@ -365,9 +355,7 @@ void fb_ac_launch_ppo_loss(hipStream_t st, const void *args) {
     });
 }
 
-void fb_ac_launch_grad(hipStream_t st, const void *args) {
-    AcGradArgs L;
-    memcpy(&L, args, sizeof(L));
+void fb_ac_launch_grad(hipStream_t st, const AcGradArgs &L) {
     hipLaunchKernelGGL(ac_grad_kernel, dim3(L.FC / 16), dim3(256), 0, st, L);
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 #include "../../include/fbdqn.h"
 
 // ---------------------------------------------------------------- errors
@@ -238,7 +239,7 @@ int fb_qnet_check_env_noise(fb_qnet_t h, int n, const char *who);
 int fb_qnet_act_nib_env_noise_keep(fb_qnet_t h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step,
                                    uint8_t *actions, float *q, void *stream);
 // ---- advantage actor-critic (FB_ARCH_AC): the kernels live in fb_ac.hip, a code object of their own; fb_qnet.hip fills these structs and
-// hands them to the launchers as bytes.  P: the net's parameters (or the fused acting forward's copy, hp_act - off.bf1); off: the dueling
+// hands them to the launchers below.  P: the net's parameters (or the fused acting forward's copy, hp_act - off.bf1); off: the dueling
 // layout, wv / bv = W_v b_v, wq / bq = W_pi b_pi
 struct FbAdamHead { float b1pow, b2pow, alpha, lr, b1, b2, eps, pad; int ticks, applies; };      // the front of fb_qnet.hip's AdamDev
 struct AcHeadArgs {
@@ -258,10 +259,10 @@ struct PpoLossArgs {
 };
 // nterms: the loss terms of dl's columns 9 .. 9 + nterms - 1 that workgroup 0 sums: 3 for A2C (loss f32[4]), 5 for PPO (loss f32[6])
 struct AcGradArgs { int B, FC, A; NetOff off; const float *dl, *xs, *dhf; float nt, cv, ce; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; int nterms; };
-void fb_ac_launch_head(hipStream_t st, const void *args);
-void fb_ac_launch_loss(hipStream_t st, const void *args);
-void fb_ac_launch_ppo_loss(hipStream_t st, const void *args);
-void fb_ac_launch_grad(hipStream_t st, const void *args);
+void fb_ac_launch_head(hipStream_t st, const AcHeadArgs &H);
+void fb_ac_launch_loss(hipStream_t st, const AcLossArgs &L);
+void fb_ac_launch_ppo_loss(hipStream_t st, const PpoLossArgs &Q);
+void fb_ac_launch_grad(hipStream_t st, const AcGradArgs &L);
 int fb_qnet_is_ac(fb_qnet_t h);               // 1: an actor-critic net (fb_qnet_create_ac)
 // the checks of the two AC training calls (batch, n_total), `who` in the message; the scratch r / t rows the ring-fed trunk fills beside
 // a_out; the ring-fed AC train step behind fb_ac_train_from_replay's checks
@@ -273,7 +274,7 @@ int fb_qnet_ac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const f
 int fb_qnet_ppo_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const int64_t *sel, const float *adv, const float *ret,
                            const float *logp_old, const float *value_old, int64_t n_total, float *loss, float *flat_grad, void *stream);
 // ---- discrete soft actor-critic (FB_ARCH_SAC): the kernels live in fb_sac.hip, a code object of their own; fb_qnet.hip fills these structs
-// and hands them to the launchers as bytes.  off: the PLAIN layout, wq / bq = W_pi b_pi; so: the two Q heads behind it.  sw: the net's
+// and hands them to the launchers below.  off: the PLAIN layout, wq / bq = W_pi b_pi; so: the two Q heads behind it.  sw: the net's
 // temperature words (log alpha, m, v, beta1 power, beta2 power)
 struct SacOff { int wq1, bq1, wq2, bq2; };
 struct SacHeadArgs {
@@ -289,15 +290,15 @@ struct SacLossArgs {
 // temp: the temperature update runs (alpha_lr > 0 and the step applies Adam itself)
 struct SacGradArgs { int B, FC, A; NetOff off; SacOff so; const float *dl, *xs, *dhf; float *grad, *loss, *gmax; FbAdamHead *adam; int tick;
                      float *sw; float target_entropy, alpha_lr; int temp; };
-void fb_sac_launch_head(hipStream_t st, const void *args);
-void fb_sac_launch_loss(hipStream_t st, const void *args);
-void fb_sac_launch_grad(hipStream_t st, const void *args);
+void fb_sac_launch_head(hipStream_t st, const SacHeadArgs &H);
+void fb_sac_launch_loss(hipStream_t st, const SacLossArgs &L);
+void fb_sac_launch_grad(hipStream_t st, const SacGradArgs &L);
 int fb_qnet_is_sac(fb_qnet_t h);              // 1: a SAC net (fb_qnet_create_sac)
 // the checks of the two SAC training calls, `who` in the message; the ring-fed SAC train step behind fb_sac_train_from_replay's checks
 int fb_qnet_sac_check_train(fb_qnet_t h, int batch, double gamma, const char *who);
 int fb_qnet_sac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
 // ---- implicit quantile networks (FB_ARCH_IQN): the kernels live in fb_iqn.hip, a code object of their own; fb_qnet.hip fills these structs
-// and hands them to the launchers as bytes.  off: the PLAIN layout (wq / bq = W_q b_q); io: the embedding behind it, W_e[64][FC] b_e[FC].
+// and hands them to the launchers below.  off: the PLAIN layout (wq / bq = W_q b_q); io: the embedding behind it, W_e[64][FC] b_e[FC].
 // A fold block is [b_fc1 | phibar * W_q | b_q]: the plain layout from b_fc1 on, so `block - off.bf1` is read as a plain net's parameters
 struct IqnOff { int we, be; };
 // A dueling IQN net (FB_ARCH_IQN_DUELING; `dueling` = 1, the last field of every struct below): off is the DUELING layout (wv / bv = W_v b_v,
@@ -316,24 +317,23 @@ struct IqnLossArgs {
     // isw / abs_err, the prioritized form: both f32[B], both set (the weights in, l_b out); else both NULL.  foff: the offsets F is read with
     const float *isw; float *abs_err; NetOff foff; int dueling;
 };
-// What the loss launch takes: IqnLossArgs and, behind its last field, Munchausen IQN's five (fb_qnet_set_iqn_munchausen).  mu = 1: F is the
+// What the loss launch takes (fb_iqn_launch_loss's parameter type): IqnLossArgs and, behind its last field, Munchausen IQN's five (fb_qnet_set_iqn_munchausen).  mu = 1: F is the
 // TARGET net's fold, arow0 = 2 B (s') and srow0 = B the first row of the slice that holds s through the target net; (temp, alpha, clip_lo)
 // the net's.  mu = 0: none of the five is read
 struct IqnLossMuArgs : IqnLossArgs { int mu; float temp, alpha, clip_lo; int srow0; };
 struct IqnGradArgs { int B, FC, A, N; NetOff off; IqnOff io; const float *dl, *gw, *dhf, *dpre, *ctab; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; int dueling; };
-void fb_iqn_launch_fold(hipStream_t st, const void *args);
-void fb_iqn_launch_head(hipStream_t st, const void *args);
-void fb_iqn_launch_loss(hipStream_t st, const void *args);
-void fb_iqn_launch_grad(hipStream_t st, const void *args);
+void fb_iqn_launch_fold(hipStream_t st, const IqnFoldArgs &F);
+void fb_iqn_launch_head(hipStream_t st, const IqnHeadArgs &H);
+void fb_iqn_launch_loss(hipStream_t st, const IqnLossMuArgs &L);
+void fb_iqn_launch_grad(hipStream_t st, const IqnGradArgs &L);
 int fb_qnet_is_iqn(fb_qnet_t h);              // 1: an IQN net (fb_qnet_create_iqn, fb_qnet_create_iqn_dueling)
-// the checks of the two IQN training calls, `who` in the message; the ring-fed IQN train step behind fb_iqn_train_from_replay's checks
-// (gamma: the bootstrap's discount)
+// the checks of the IQN training calls, `who` in the message; the ring-fed IQN train step behind the checks of `who` -- fb_iqn_train_from_replay
+// (isw / abs_err NULL), or fb_iqn_per_train_from_replay, the prioritized form (isw / abs_err f32[batch], both non-NULL).  gamma: the
+// bootstrap's discount
 int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int batch, double gamma, const char *who);
-int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int batch, const FbRingSrc *ring, const float *tau, const float *tau_next, uint64_t seed,
-                           uint64_t step, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
-// the same behind fb_iqn_per_train_from_replay's checks: the prioritized form (isw / abs_err f32[batch], both non-NULL)
-int fb_qnet_iqn_per_train_ring(fb_qnet_t h, int double_q, int batch, const FbRingSrc *ring, const float *isw, const float *tau, const float *tau_next,
-                               uint64_t seed, uint64_t step, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream);
+int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int batch, const FbRingSrc *ring, const float *isw, const float *tau, const float *tau_next,
+                           uint64_t seed, uint64_t step, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream,
+                           const char *who);
 // ---- the refusal rules of the ring-fed entry points (fb_common.hip): made before any counter moves or any launch; FB_OK, else the error
 // code with fb_last_error naming `who`
 int fb_check_q_net(fb_qnet_t net, const char *who, bool steps);       // no AC / SAC / IQN net (steps: `who` steps the envs too)

@@ -6,6 +6,13 @@
 constexpr int MAXA = 8;              // actions
 constexpr int FC1_KS = 5;            // most fc1 K slices any forward path produces
 
+// A runtime value as a template argument (host side): f is a generic lambda and gets a tag whose ::value is a constant expression, so that a
+// kernel template has ONE launch statement per call site, hipLaunchKernelGGL((kernel<decltype(tag)::value, ...>), ...), not one per
+// instantiation.  with_actions: the head's action template, 2 (the game's) or MAXA (read it from the arguments)
+template <int V> using IntTag = std::integral_constant<int, V>;
+template <class F> static void with_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_actions(int A, F f) { if (A == 2) f(IntTag<2>{}); else f(IntTag<MAXA>{}); }
+
 __device__ __forceinline__ float4 sel4(bool ok, float4 v) {
     return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
 }

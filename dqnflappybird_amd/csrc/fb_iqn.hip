@@ -17,7 +17,6 @@
 // backward pass instead of stored.
 #include "fb_common.h"
 #include <math.h>
-#include <type_traits>
 
 namespace {
 #include "fb_head.h"
@@ -458,10 +457,6 @@ __global__ __launch_bounds__(256) void iqn_draw_kernel(long long total, int n, u
     out[q] = iqn_draw(seed_lo, seed_hi, step_lo, step_hi, b, i, which != 0);
 }
 
-template <class F> void with_actions(int A, F f) {
-    if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
-}
-template <class F> void with_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
 // the loss launch of either kind of net (L.dueling), with the hard or the Munchausen target (L.mu), at the head's action template and the prioritized form
 template <int AT, bool PW>
 void launch_loss(hipStream_t st, const IqnLossMuArgs &L) {
@@ -471,15 +466,11 @@ void launch_loss(hipStream_t st, const IqnLossMuArgs &L) {
 }
 }  // namespace
 
-void fb_iqn_launch_fold(hipStream_t st, const void *args) {
-    IqnFoldArgs F;
-    memcpy(&F, args, sizeof(F));
+void fb_iqn_launch_fold(hipStream_t st, const IqnFoldArgs &F) {
     with_bool(F.dueling != 0, [&](auto du) { hipLaunchKernelGGL(iqn_fold_kernel<decltype(du)::value>, dim3(F.FC / 128), dim3(128), 0, st, F); });
 }
 
-void fb_iqn_launch_head(hipStream_t st, const void *args) {
-    IqnHeadArgs H;
-    memcpy(&H, args, sizeof(H));
+void fb_iqn_launch_head(hipStream_t st, const IqnHeadArgs &H) {
     with_actions(H.A, [&](auto a) {
         with_bool(H.dueling != 0, [&](auto du) {
             hipLaunchKernelGGL((iqn_head_kernel<decltype(a)::value, decltype(du)::value>), dim3(H.rows), dim3(256), 0, st, H);
@@ -487,9 +478,7 @@ void fb_iqn_launch_head(hipStream_t st, const void *args) {
     });
 }
 
-void fb_iqn_launch_loss(hipStream_t st, const void *args) {        // (args: an IqnLossMuArgs)
-    IqnLossMuArgs L;
-    memcpy(&L, args, sizeof(L));
+void fb_iqn_launch_loss(hipStream_t st, const IqnLossMuArgs &L) {
     with_actions(L.A, [&](auto a) {           // (isw set: the prioritized form, which also writes abs_err)
         with_bool(L.isw != nullptr, [&](auto pw) {
             launch_loss<decltype(a)::value, decltype(pw)::value>(st, L);
@@ -497,9 +486,7 @@ void fb_iqn_launch_loss(hipStream_t st, const void *args) {        // (args: an 
     });
 }
 
-void fb_iqn_launch_grad(hipStream_t st, const void *args) {
-    IqnGradArgs L;
-    memcpy(&L, args, sizeof(L));
+void fb_iqn_launch_grad(hipStream_t st, const IqnGradArgs &L) {
     with_bool(L.dueling != 0, [&](auto du) { hipLaunchKernelGGL(iqn_grad_kernel<decltype(du)::value>, dim3(L.FC / 16), dim3(256), 0, st, L); });
 }
 
@@ -515,10 +502,35 @@ extern "C" int fb_iqn_draw_taus(int batch, int n, uint64_t seed, uint64_t step, 
     return FB_OK;
 }
 
-// the checks of the two ring-fed IQN calls on the memory: a uniform one, at any n-step view, whose gamma the caller's is
+// the checks of the two uniform ring-fed IQN calls on the memory: a uniform one, at any n-step view, whose gamma the caller's is
 static int iqn_check_memory(fb_replay_t replay, double gamma, const char *who) {
     FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: IQN trains from a uniform memory only (prioritized replay is not offered)", who);
     return fb_replay_check_gamma(replay, gamma, who);
+}
+// the checks of the two prioritized ring-fed calls on the memory (include/fbdqn.h, the prioritized IQN block: calls of their own, the memory's
+// kind never switches what a call does): a prioritized one, at any n-step view, whose gamma the caller's is and whose tree holds a leaf once
+// `pushes_ahead` more pushes are counted (pushes_ahead < 0: a store-only step, which samples nothing)
+static int iqn_per_check_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who) {
+    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (fb_iqn_train_from_replay / fb_iqn_step take a uniform one)", who);
+    const int rc = fb_replay_check_gamma(replay, gamma, who);
+    return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
+}
+
+// fb_iqn_train_from_replay (isw / abs_err NULL) and fb_iqn_per_train_from_replay (both set: the weights in, l_b out) behind their
+// NULL-argument checks: the net, the memory of the call's kind, the train step's own checks, then the step on the ring
+static int iqn_train_from_replay(const char *who, fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, const float *isw,
+                                 uint8_t *a_out, float *r_out, uint8_t *t_out, const float *tau, const float *tau_next, uint64_t seed, uint64_t step,
+                                 double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
+    int rc = isw ? iqn_per_check_memory(replay, gamma, 0, who) : iqn_check_memory(replay, gamma, who);
+    if (rc != FB_OK) return rc;
+    rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    FbRingSrc ring;
+    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
+    if (rc != FB_OK) return rc;
+    return fb_qnet_iqn_train_ring(net, double_q, batch, &ring, isw, tau, tau_next, seed, step, fb_replay_bootstrap_gamma(replay, gamma), loss, abs_err,
+                                  q_target, flat_grad, stream, who);
 }
 
 extern "C" int fb_iqn_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, uint8_t *a_out, float *r_out,
@@ -526,49 +538,8 @@ extern "C" int fb_iqn_train_from_replay(fb_replay_t replay, fb_qnet_t net, int d
                                         float *q_target, float *flat_grad, void *stream) {
     const char *who = "fb_iqn_train_from_replay";
     FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
-    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
-    int rc = iqn_check_memory(replay, gamma, who);
-    if (rc != FB_OK) return rc;
-    rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
-    if (rc != FB_OK) return rc;
-    FbRingSrc ring;
-    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
-    if (rc != FB_OK) return rc;
-    return fb_qnet_iqn_train_ring(net, double_q, batch, &ring, tau, tau_next, seed, step, fb_replay_bootstrap_gamma(replay, gamma), loss, q_target,
-                                  flat_grad, stream);
-}
-
-extern "C" int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
-                           uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
-    const char *who = "fb_iqn_step";
-    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
-    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && b->idx, "%s: NULL buffer", who);
-    FB_REQUIRE(!train || (b->a && b->r && b->t && b->loss), "%s: a training step needs the a / r / t / loss buffers", who);
-    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
-    int rc = iqn_check_memory(replay, gamma, who);
-    if (rc != FB_OK) return rc;
-    rc = fb_check_step_handles(env, replay, net, n_envs, who);
-    if (rc == FB_OK) rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
-    if (rc != FB_OK) return rc;
-    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
-    rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
-    if (rc != FB_OK) return rc;
-    if (train) rc = fb_iqn_train_from_replay(replay, net, double_q, batch, b->idx, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss, nullptr,
-                                             b->flat_grad, stream);
-    return rc;
-}
-
-// ---- prioritized replay (include/fbdqn.h, the prioritized IQN block): calls of their own, the memory's kind never switches what a call does
-// the checks of the two ring-fed prioritized calls on the memory: a prioritized one, at any n-step view, whose gamma the caller's is and whose
-// tree holds a leaf once `pushes_ahead` more pushes are counted (pushes_ahead < 0: a store-only step, which samples nothing)
-static int iqn_per_check_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who) {
-    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (fb_iqn_train_from_replay / fb_iqn_step take a uniform one)", who);
-    const int rc = fb_replay_check_gamma(replay, gamma, who);
-    return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
+    return iqn_train_from_replay(who, replay, net, double_q, batch, idx, nullptr, a_out, r_out, t_out, tau, tau_next, seed, step, gamma, loss, nullptr,
+                                 q_target, flat_grad, stream);
 }
 
 extern "C" int fb_iqn_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int double_q, int batch, const int64_t *idx, const float *isw,
@@ -577,36 +548,56 @@ extern "C" int fb_iqn_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, i
     const char *who = "fb_iqn_per_train_from_replay";
     FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
     FB_REQUIRE(isw && abs_err, "%s: the prioritized step needs the importance weights (isw) and abs_err", who);
+    return iqn_train_from_replay(who, replay, net, double_q, batch, idx, isw, a_out, r_out, t_out, tau, tau_next, seed, step, gamma, loss, abs_err,
+                                 q_target, flat_grad, stream);
+}
+
+// what fb_iqn_step and fb_iqn_per_step begin with: the handles and the buffers every step writes (need_idx: the uniform step's push samples
+// into b->idx whether it trains or not)
+static int iqn_step_begin(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, bool need_idx, const char *who) {
+    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
+    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && (!need_idx || b->idx), "%s: NULL buffer", who);
+    return FB_OK;
+}
+// ... and what both do behind their own checks of the buffers, the net and the memory: the handles' and the train call's checks -- every
+// argument check of the calls a step makes is made before the first launch, so nothing is launched and no push is counted before a
+// refusal -- then epsilon-greedy on the folded head and the env step.  The push is the caller's
+static int iqn_act_env_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
+                            uint64_t seed, uint64_t step, double gamma, void *stream, const char *who) {
+    int rc = fb_check_step_handles(env, replay, net, n_envs, who);
+    if (rc == FB_OK) rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
+    if (rc != FB_OK) return rc;
+    return fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+}
+
+extern "C" int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
+                           uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
+    const char *who = "fb_iqn_step";
+    int rc = iqn_step_begin(env, replay, net, b, true, who);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(!train || (b->a && b->r && b->t && b->loss), "%s: a training step needs the a / r / t / loss buffers", who);
     FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
-    int rc = iqn_per_check_memory(replay, gamma, 0, who);
+    rc = iqn_check_memory(replay, gamma, who);
+    if (rc == FB_OK) rc = iqn_act_env_step(env, replay, net, b, n_envs, double_q, batch, epsilon, seed, step, gamma, stream, who);
     if (rc != FB_OK) return rc;
-    rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
-    if (rc != FB_OK) return rc;
-    FbRingSrc ring;
-    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
-    if (rc != FB_OK) return rc;
-    return fb_qnet_iqn_per_train_ring(net, double_q, batch, &ring, isw, tau, tau_next, seed, step, fb_replay_bootstrap_gamma(replay, gamma), loss, abs_err,
-                                      q_target, flat_grad, stream);
+    rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
+    if (rc != FB_OK || !train) return rc;
+    return fb_iqn_train_from_replay(replay, net, double_q, batch, b->idx, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss, nullptr,
+                                    b->flat_grad, stream);
 }
 
 extern "C" int fb_iqn_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch,
                                float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
     const char *who = "fb_iqn_per_step";
-    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
-    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "%s: NULL buffer", who);
+    int rc = iqn_step_begin(env, replay, net, b, false, who);
+    if (rc != FB_OK) return rc;
     FB_REQUIRE(!train || (b->idx && b->a && b->r && b->t && b->loss), "%s: a training step needs the idx / a / r / t / loss buffers", who);
     FB_REQUIRE(!train || (b->isw && b->isw32 && b->abs_err), "%s: the prioritized step needs the isw / isw32 / abs_err buffers", who);
     FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
-    // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
-    int rc = iqn_per_check_memory(replay, gamma, train ? 1 : -1, who);
-    if (rc != FB_OK) return rc;
-    rc = fb_check_step_handles(env, replay, net, n_envs, who);
-    if (rc == FB_OK) rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
-    if (rc != FB_OK) return rc;
-    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
-    rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+    rc = iqn_per_check_memory(replay, gamma, train ? 1 : -1, who);      // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
+    if (rc == FB_OK) rc = iqn_act_env_step(env, replay, net, b, n_envs, double_q, batch, epsilon, seed, step, gamma, stream, who);
     if (rc != FB_OK) return rc;
     rc = fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, stream);
     if (rc != FB_OK || !train) return rc;

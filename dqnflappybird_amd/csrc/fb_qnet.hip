@@ -3967,7 +3967,9 @@ __global__ void init_params_kernel(float *__restrict__ p, long long n, NetOff of
 constexpr int ADAM_GRID = FB_ADAM_GRID;
 
 // ================================================================== host side
+#include <vector>
 struct fb_qnet {
+    std::vector<void *> allocs;      // every device buffer qnet_create allocated, as its alloc() recorded it: what fb_qnet_destroy frees
     int arch, FC, A, max_batch;
     long long n;
     NetOff off;
@@ -4098,7 +4100,7 @@ static const float *head_base(const fb_qnet *h, const float *params) {
 static void c51d_fold(fb_qnet *h, int which, hipStream_t st) {
     if (is_iqn(h)) {                             // (an IQN net: phibar over the acting grid and its fold block, fb_iqn.hip)
         const IqnFoldArgs F{h->params[which], h->heff[which], h->FC, h->A, h->iqn_k, h->off, h->iqn_off, h->iqn_eta, is_iqnd(h) ? 1 : 0};
-        fb_iqn_launch_fold(st, &F);
+        fb_iqn_launch_fold(st, F);
         return;
     }
     if (!is_c51d(h)) return;
@@ -4126,11 +4128,40 @@ static void noisy_sgrad(fb_qnet *h, float *g, hipStream_t st) {
     hipLaunchKernelGGL(noisy_sgrad_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, st, g, (const float *)h->nz[0], h->nnet);
 }
 
-static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out, float sigma0 = -1.f);
-static thread_local int g_iqn_create[3];         // (N, N', K) of the IQN net fb_qnet_create_iqn is making: qnet_create sizes its workspaces by them
+// What a net is made from.  Every fb_qnet_create* checks its arguments, fills one of these and hands it to qnet_create; nothing reaches the
+// handle by another way.  The fields a family does not have stay zero
+struct NetSpec {
+    int arch, fc_width, n_actions, max_batch;
+    C51Sup sup;                      // C51 nets: the support
+    int n_quantiles;                 // QR nets: N
+    float kappa;                     // QR and IQN nets: the quantile Huber loss's threshold
+    bool noisy; float sigma0;        // noisy C51 nets (fb_qnet_create_c51_noisy): finite sigma0 >= 0
+    int n_tau, n_tau_next, n_tau_act;      // IQN nets: N, N', K
+};
+static NetSpec net_spec(int arch, int fc_width, int n_actions, int max_batch) {
+    NetSpec s{};
+    s.arch = arch; s.fc_width = fc_width; s.n_actions = n_actions; s.max_batch = max_batch;
+    return s;
+}
+static int qnet_create(const NetSpec &s, fb_qnet_t *out);
+
+// The checks every creator makes, `fn` naming it in the message.  They stand at three places of a creator's order (the first failing check
+// decides the text): `out` in front of everything, fc_width and n_actions (min_actions: the family's lower bound, 1 or 2) in front of the
+// family's own checks, max_batch behind them
+enum { CREATE_OUT = 1, CREATE_SHAPE = 2, CREATE_BATCH = 4, CREATE_ALL = 7 };
+static int check_create(const char *fn, const NetSpec &s, int min_actions, const fb_qnet_t *out, int which = CREATE_ALL) {
+    if (which & CREATE_OUT) FB_REQUIRE(out, "%s: out is NULL", fn);
+    if (which & CREATE_SHAPE) {
+        FB_REQUIRE(s.fc_width >= 128 && s.fc_width <= 4096 && s.fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
+        FB_REQUIRE(s.n_actions >= min_actions && s.n_actions <= MAXA, "%s: n_actions must be in %d..%d", fn, min_actions, MAXA);
+    }
+    if (which & CREATE_BATCH) FB_REQUIRE(s.max_batch >= 1 && s.max_batch <= (1 << 20), "%s: max_batch out of range", fn);
+    return FB_OK;
+}
 
 extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
-    FB_REQUIRE(out, "fb_qnet_create: out is NULL");
+    const NetSpec s = net_spec(arch, fc_width, n_actions, max_batch);
+    if (const int rc = check_create("fb_qnet_create", s, 1, out, CREATE_OUT)) return rc;
     FB_REQUIRE(arch != FB_ARCH_C51, "fb_qnet_create: a C51 net is made by fb_qnet_create_c51 (it needs the support)");
     FB_REQUIRE(arch != FB_ARCH_C51_DUELING, "fb_qnet_create: a dueling C51 net is made by fb_qnet_create_c51_dueling (it needs the support)");
     FB_REQUIRE(arch != FB_ARCH_QR && arch != FB_ARCH_QR_DUELING, "fb_qnet_create: a QR net is made by fb_qnet_create_qr (it needs N and kappa)");
@@ -4138,34 +4169,32 @@ extern "C" int fb_qnet_create(int arch, int fc_width, int n_actions, int max_bat
     FB_REQUIRE(arch != FB_ARCH_SAC, "fb_qnet_create: a SAC net is made by fb_qnet_create_sac");
     FB_REQUIRE(arch != FB_ARCH_IQN, "fb_qnet_create: an IQN net is made by fb_qnet_create_iqn (it needs N, N', K and kappa)");
     FB_REQUIRE(arch == FB_ARCH_PLAIN || arch == FB_ARCH_DUELING, "fb_qnet_create: arch must be 0 or 1");
-    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "fb_qnet_create: fc_width must be a multiple of 128");
-    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "fb_qnet_create: n_actions must be in 1..%d", MAXA);
-    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "fb_qnet_create: max_batch out of range");
-    return qnet_create(arch, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
+    if (const int rc = check_create("fb_qnet_create", s, 1, out, CREATE_SHAPE | CREATE_BATCH)) return rc;
+    return qnet_create(s, out);
 }
 
-// the checks of fb_qnet_create_c51 / _c51_dueling, before any allocation (`fn` names the caller in the message)
+// the checks of fb_qnet_create_c51 / _c51_dueling / _c51_noisy, before any allocation (`fn` names the caller in the message)
 static int c51_create(const char *fn, int arch, int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out,
-                      float sigma0 = -1.f) {
-    FB_REQUIRE(out, "%s: out is NULL", fn);
-    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
-    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "%s: n_actions must be in 1..%d", fn, MAXA);
+                      bool noisy, float sigma0) {
+    NetSpec s = net_spec(arch, fc_width, n_actions, max_batch);
+    if (const int rc = check_create(fn, s, 1, out, CREATE_OUT | CREATE_SHAPE)) return rc;
     FB_REQUIRE(n_atoms >= 2 && n_atoms <= FB_C51_MAX_ATOMS, "%s: n_atoms=%d outside 2..%d", fn, n_atoms, FB_C51_MAX_ATOMS);
     FB_REQUIRE(n_actions * n_atoms <= 128, "%s: n_actions * n_atoms = %d exceeds 128", fn, n_actions * n_atoms);
     FB_REQUIRE(isfinite(v_min) && isfinite(v_max) && v_min < v_max, "%s: the support needs finite v_min < v_max (got %g, %g)",
                fn, (double)v_min, (double)v_max);
-    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
+    if (const int rc = check_create(fn, s, 1, out, CREATE_BATCH)) return rc;
     const float dz = (v_max - v_min) / (float)(n_atoms - 1);
     FB_REQUIRE(isfinite(dz) && dz > 0.f, "%s: the atom spacing (v_max - v_min) / (n_atoms - 1) is not a positive finite float", fn);
-    return qnet_create(arch, fc_width, n_actions, C51Sup{n_atoms, v_min, v_max, dz}, max_batch, out, sigma0);
+    s.sup = C51Sup{n_atoms, v_min, v_max, dz}; s.noisy = noisy; s.sigma0 = sigma0;
+    return qnet_create(s, out);
 }
 
 extern "C" int fb_qnet_create_c51(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
-    return c51_create("fb_qnet_create_c51", FB_ARCH_C51, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out);
+    return c51_create("fb_qnet_create_c51", FB_ARCH_C51, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out, false, 0.f);
 }
 
 extern "C" int fb_qnet_create_c51_dueling(int fc_width, int n_actions, int n_atoms, float v_min, float v_max, int max_batch, fb_qnet_t *out) {
-    return c51_create("fb_qnet_create_c51_dueling", FB_ARCH_C51_DUELING, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out);
+    return c51_create("fb_qnet_create_c51_dueling", FB_ARCH_C51_DUELING, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out, false, 0.f);
 }
 
 extern "C" int fb_qnet_create_c51_noisy(int arch, int fc_width, int n_actions, int n_atoms, float v_min, float v_max, float sigma0, int max_batch,
@@ -4174,64 +4203,47 @@ extern "C" int fb_qnet_create_c51_noisy(int arch, int fc_width, int n_actions, i
     FB_REQUIRE(arch == FB_ARCH_C51 || arch == FB_ARCH_C51_DUELING, "fb_qnet_create_c51_noisy: arch must be FB_ARCH_C51 (2) or FB_ARCH_C51_DUELING (3), "
                "got %d (noisy layers are offered on the C51 heads only)", arch);
     FB_REQUIRE(isfinite(sigma0) && sigma0 >= 0.f, "fb_qnet_create_c51_noisy: sigma0 must be finite and >= 0 (got %g)", (double)sigma0);
-    return c51_create("fb_qnet_create_c51_noisy", arch, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out, sigma0);
+    return c51_create("fb_qnet_create_c51_noisy", arch, fc_width, n_actions, n_atoms, v_min, v_max, max_batch, out, true, sigma0);
 }
 
 extern "C" int fb_qnet_create_qr(int arch, int fc_width, int n_actions, int n_quantiles, float kappa, int max_batch, fb_qnet_t *out) {
     const char *fn = "fb_qnet_create_qr";
-    FB_REQUIRE(out, "%s: out is NULL", fn);
+    NetSpec s = net_spec(arch, fc_width, n_actions, max_batch);
+    if (const int rc = check_create(fn, s, 1, out, CREATE_OUT)) return rc;
     FB_REQUIRE(arch == FB_ARCH_QR || arch == FB_ARCH_QR_DUELING, "%s: arch must be FB_ARCH_QR (4) or FB_ARCH_QR_DUELING (5), got %d", fn, arch);
-    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
-    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "%s: n_actions must be in 1..%d", fn, MAXA);
+    if (const int rc = check_create(fn, s, 1, out, CREATE_SHAPE)) return rc;
     FB_REQUIRE(n_quantiles >= 2 && n_quantiles <= FB_C51_MAX_ATOMS, "%s: n_quantiles=%d outside 2..%d", fn, n_quantiles, FB_C51_MAX_ATOMS);
     FB_REQUIRE(n_actions * n_quantiles <= 128, "%s: n_actions * n_quantiles = %d exceeds 128", fn, n_actions * n_quantiles);
     FB_REQUIRE(isfinite(kappa) && kappa > 0.f, "%s: kappa must be finite and > 0 (got %g)", fn, (double)kappa);
-    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
-    const int rc = qnet_create(arch, fc_width, n_actions, C51Sup{n_quantiles, 0.f, 0.f, 0.f}, max_batch, out);
-    if (rc == FB_OK) (*out)->kappa = kappa;
-    return rc;
+    if (const int rc = check_create(fn, s, 1, out, CREATE_BATCH)) return rc;
+    s.n_quantiles = n_quantiles; s.kappa = kappa;
+    return qnet_create(s, out);
 }
 
 extern "C" int fb_qnet_create_ac(int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
-    const char *fn = "fb_qnet_create_ac";
-    FB_REQUIRE(out, "%s: out is NULL", fn);
-    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
-    FB_REQUIRE(n_actions >= 1 && n_actions <= MAXA, "%s: n_actions must be in 1..%d", fn, MAXA);
-    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
-    return qnet_create(FB_ARCH_AC, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
+    const NetSpec s = net_spec(FB_ARCH_AC, fc_width, n_actions, max_batch);
+    if (const int rc = check_create("fb_qnet_create_ac", s, 1, out)) return rc;
+    return qnet_create(s, out);
 }
 
-static int sac_write_words(fb_qnet *h, float alpha);
-
 extern "C" int fb_qnet_create_sac(int fc_width, int n_actions, int max_batch, fb_qnet_t *out) {
-    const char *fn = "fb_qnet_create_sac";
-    FB_REQUIRE(out, "%s: out is NULL", fn);
-    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
-    FB_REQUIRE(n_actions >= 2 && n_actions <= MAXA, "%s: n_actions must be in 2..%d", fn, MAXA);
-    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
-    int rc = qnet_create(FB_ARCH_SAC, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
-    if (rc != FB_OK) return rc;
-    (*out)->sac_hbar = 0.98f * logf((float)n_actions); (*out)->sac_alr = 0.f;
-    rc = sac_write_words(*out, 0.2f);            // (behind qnet_create's fb_qnet_set_hparams: the beta powers start at the net's betas)
-    if (rc != FB_OK) { fb_qnet_destroy(*out); *out = nullptr; }
-    return rc;
+    const NetSpec s = net_spec(FB_ARCH_SAC, fc_width, n_actions, max_batch);
+    if (const int rc = check_create("fb_qnet_create_sac", s, 2, out)) return rc;
+    return qnet_create(s, out);
 }
 
 // the checks of fb_qnet_create_iqn / _iqn_dueling, before any allocation (`fn` names the caller in the message)
 static int iqn_create(const char *fn, int arch, int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch,
                       fb_qnet_t *out) {
-    FB_REQUIRE(out, "%s: out is NULL", fn);
-    FB_REQUIRE(fc_width >= 128 && fc_width <= 4096 && fc_width % 128 == 0, "%s: fc_width must be a multiple of 128", fn);
-    FB_REQUIRE(n_actions >= 2 && n_actions <= MAXA, "%s: n_actions must be in 2..%d", fn, MAXA);
+    NetSpec s = net_spec(arch, fc_width, n_actions, max_batch);
+    if (const int rc = check_create(fn, s, 2, out, CREATE_OUT | CREATE_SHAPE)) return rc;
     FB_REQUIRE(n_tau >= 1 && n_tau <= 64, "%s: n_tau=%d outside 1..64", fn, n_tau);
     FB_REQUIRE(n_tau_next >= 1 && n_tau_next <= 64, "%s: n_tau_next=%d outside 1..64", fn, n_tau_next);
     FB_REQUIRE(n_tau_act >= 1 && n_tau_act <= 64, "%s: n_tau_act=%d outside 1..64", fn, n_tau_act);
     FB_REQUIRE(isfinite(kappa) && kappa > 0.f, "%s: kappa must be finite and > 0 (got %g)", fn, (double)kappa);
-    FB_REQUIRE(max_batch >= 1 && max_batch <= (1 << 20), "%s: max_batch out of range", fn);
-    g_iqn_create[0] = n_tau; g_iqn_create[1] = n_tau_next; g_iqn_create[2] = n_tau_act;
-    const int rc = qnet_create(arch, fc_width, n_actions, C51Sup{0, 0.f, 0.f, 0.f}, max_batch, out);
-    if (rc == FB_OK) (*out)->kappa = kappa;
-    return rc;
+    if (const int rc = check_create(fn, s, 2, out, CREATE_BATCH)) return rc;
+    s.n_tau = n_tau; s.n_tau_next = n_tau_next; s.n_tau_act = n_tau_act; s.kappa = kappa;
+    return qnet_create(s, out);
 }
 
 extern "C" int fb_qnet_create_iqn(int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch, fb_qnet_t *out) {
@@ -4242,6 +4254,8 @@ extern "C" int fb_qnet_create_iqn_dueling(int fc_width, int n_actions, int n_tau
                                           fb_qnet_t *out) {
     return iqn_create("fb_qnet_create_iqn_dueling", FB_ARCH_IQN_DUELING, fc_width, n_actions, n_tau, n_tau_next, n_tau_act, kappa, max_batch, out);
 }
+
+static int sac_write_words(fb_qnet *h, float alpha);
 
 // the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
 static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, float sigma0) {
@@ -4259,110 +4273,113 @@ static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, floa
     return nn;
 }
 
-static int qnet_create(int arch, int fc_width, int n_actions, const C51Sup &sup, int max_batch, fb_qnet_t *out, float sigma0) {
-    fb_qnet *h = new fb_qnet();
-    memset(h, 0, sizeof(*h));
+static int qnet_create(const NetSpec &s, fb_qnet_t *out) {
+    const int arch = s.arch, fc_width = s.fc_width, n_actions = s.n_actions, max_batch = s.max_batch;
+    const C51Sup sup = s.n_quantiles ? C51Sup{s.n_quantiles, 0.f, 0.f, 0.f} : s.sup;      // (fb_qnet::sup: a QR net keeps N there)
+    fb_qnet *h = new fb_qnet();                  // (value-initialised: every field zero)
     h->md = MdPar{0.03f, 0.9f, -1.f};            // Munchausen-DQN, the paper's values (read by FB_ALGO_MDQN / _PER on a scalar net alone)
     h->ac_cv = 0.5f; h->ac_ce = 0.01f;           // A2C's value and entropy coefficients (read on an actor-critic net alone)
     h->ppo_eps = 0.2f; h->ppo_vclip = 0.f;       // PPO's clip ranges (read by the PPO train steps of an actor-critic net alone)
-    h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup;
+    h->arch = arch; h->FC = fc_width; h->A = n_actions; h->max_batch = max_batch; h->sup = sup; h->kappa = s.kappa;
     h->off = is_c51d(h) ? make_off_c51d(fc_width, n_actions, sup.N)
                         : make_off(fc_width, sup.N ? n_actions * sup.N : n_actions, arch == FB_ARCH_DUELING || arch == FB_ARCH_AC || arch == FB_ARCH_IQN_DUELING);
     if (is_sac(h)) {                             // (the plain layout, then the two Q heads: off.n covers them)
         h->sac_off.wq1 = h->off.n; h->sac_off.bq1 = h->sac_off.wq1 + fc_width * n_actions;
         h->sac_off.wq2 = h->sac_off.bq1 + n_actions; h->sac_off.bq2 = h->sac_off.wq2 + fc_width * n_actions;
         h->off.n = h->sac_off.bq2 + n_actions;
+        h->sac_hbar = 0.98f * logf((float)n_actions); h->sac_alr = 0.f;
     }
     if (is_iqn(h)) {                             // (the plain or the dueling layout, then the embedding: off.n covers it)
         h->iqn_off.we = h->off.n; h->iqn_off.be = h->iqn_off.we + FB_IQN_COS * fc_width;
         h->off.n = h->iqn_off.be + fc_width;
-        h->iqn_n = g_iqn_create[0]; h->iqn_np = g_iqn_create[1]; h->iqn_k = g_iqn_create[2]; h->iqn_eta = 1.f;
+        h->iqn_n = s.n_tau; h->iqn_np = s.n_tau_next; h->iqn_k = s.n_tau_act; h->iqn_eta = 1.f;
         h->iqn_mu = 0; h->iqn_md = MdPar{0.03f, 0.9f, -1.f};      // (Munchausen IQN: off, the paper's values)
     }
     h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : is_iqnd(h) ? make_off(fc_width, n_actions, 0) : h->off;      // (a dueling IQN net: its fold's)
     h->n = h->off.n;
-    h->noisy = sigma0 >= 0.f;                    // (fb_qnet_create_c51_noisy: C51 archs, finite sigma0 >= 0)
+    h->noisy = s.noisy;
     h->ntot = h->noisy ? 2 * h->n - OFF_WF1 : h->n;
-    if (h->noisy) h->nnet = make_noisy(h->off, arch, fc_width, n_actions, sup.N, sigma0);
+    if (h->noisy) h->nnet = make_noisy(h->off, arch, fc_width, n_actions, sup.N, s.sigma0);
     h->zmax = 64;
     const size_t S = (size_t)3 * max_batch, nb = sizeof(float) * (size_t)h->n, nbt = sizeof(float) * (size_t)h->ntot;
     hipError_t e = hipSuccess;
-    auto alloc = [&](void **p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); };
-    alloc((void **)&h->params[0], nb); alloc((void **)&h->params[1], nb);
-    alloc((void **)&h->adam_m, nbt); alloc((void **)&h->adam_v, nbt); alloc((void **)&h->grad, nbt);
-    if (h->noisy) for (int w = 0; w < 2; w++) { alloc((void **)&h->mst[w], nbt); alloc((void **)&h->nz[w], sizeof(float) * (size_t)h->nnet.nz); }      // (zero noise: mean mode)
+    auto alloc = [&](auto **p, size_t bytes) {   // zeroed device memory, recorded in h->allocs
+        void *q = nullptr;
+        if (e == hipSuccess) e = hipMalloc(&q, bytes);
+        if (e != hipSuccess) return;
+        h->allocs.push_back(q);
+        *p = static_cast<std::remove_reference_t<decltype(**p)> *>(q);
+        e = hipMemset(q, 0, bytes);
+    };
+    alloc(&h->params[0], nb); alloc(&h->params[1], nb);
+    alloc(&h->adam_m, nbt); alloc(&h->adam_v, nbt); alloc(&h->grad, nbt);
+    if (h->noisy) for (int w = 0; w < 2; w++) { alloc(&h->mst[w], nbt); alloc(&h->nz[w], sizeof(float) * (size_t)h->nnet.nz); }      // (zero noise: mean mode)
     if (h->noisy) {
-        alloc((void **)&h->nz_zero, sizeof(float) * (size_t)h->nnet.nz);
-        alloc((void **)&h->wsig, sizeof(uint4) * (size_t)wsp_w3t(fc_width));
-        alloc((void **)&h->a3n, S * 1600 * 6 + 256);
-        alloc((void **)&h->ht, S * fc_width * 4 * FC1_SP_KS);
-        alloc((void **)&h->sig_seen, sizeof(int));
+        alloc(&h->nz_zero, sizeof(float) * (size_t)h->nnet.nz);
+        alloc(&h->wsig, sizeof(uint4) * (size_t)wsp_w3t(fc_width));
+        alloc(&h->a3n, S * 1600 * 6 + 256);
+        alloc(&h->ht, S * fc_width * 4 * FC1_SP_KS);
+        alloc(&h->sig_seen, sizeof(int));
         if (e == hipSuccess) e = hipMemset(h->sig_seen, 0xff, sizeof(int));      // (no planes yet)
     }
-    alloc((void **)&h->slabs, sizeof(float) * (size_t)h->zmax * CONV_PARAMS);
-    if (2 * max_batch > h->zmax) alloc((void **)&h->slabs1, sizeof(float) * (size_t)2 * (max_batch < MAXTB ? max_batch : MAXTB) * CONV1_PARAMS);      // two sub-slabs per sample
-    alloc((void **)&h->adam, sizeof(AdamDev));
-    alloc((void **)&h->w1s[0], 3 * 8192 * 2); alloc((void **)&h->w1s[1], 3 * 8192 * 2);
+    alloc(&h->slabs, sizeof(float) * (size_t)h->zmax * CONV_PARAMS);
+    if (2 * max_batch > h->zmax) alloc(&h->slabs1, sizeof(float) * (size_t)2 * (max_batch < MAXTB ? max_batch : MAXTB) * CONV1_PARAMS);      // two sub-slabs per sample
+    alloc(&h->adam, sizeof(AdamDev));
+    alloc(&h->w1s[0], 3 * 8192 * 2); alloc(&h->w1s[1], 3 * 8192 * 2);
     const size_t wsp_bytes = (size_t)wsp_total(fc_width) * sizeof(uint4);
-    alloc((void **)&h->wsp[0], wsp_bytes); alloc((void **)&h->wsp[1], wsp_bytes);
+    alloc(&h->wsp[0], wsp_bytes); alloc(&h->wsp[1], wsp_bytes);
     h->nsplit = 3; h->nsplit_train = 3;
-    alloc((void **)&h->zeros, 256);
-    alloc((void **)&h->a1s, S * 3200 * 6); alloc((void **)&h->a3s, S * 1600 * 6 + 256);
-    alloc((void **)&h->p1, S * 3200 * 4); alloc((void **)&h->amax, S * 3200);
-    alloc((void **)&h->h2, S * 1600 * 4); alloc((void **)&h->h3, S * 1600 * 4);
-    alloc((void **)&h->hf, S * fc_width * 4 * FC1_KS); alloc((void **)&h->q, S * MAXA * 4);
-    alloc((void **)&h->qpart, (size_t)(fc_width / 16) * S * (MAXA + 1) * 4);
-    alloc((void **)&h->ring_fo, (size_t)max_batch * 4 * sizeof(unsigned long long));
+    alloc(&h->zeros, 256);
+    alloc(&h->a1s, S * 3200 * 6); alloc(&h->a3s, S * 1600 * 6 + 256);
+    alloc(&h->p1, S * 3200 * 4); alloc(&h->amax, S * 3200);
+    alloc(&h->h2, S * 1600 * 4); alloc(&h->h3, S * 1600 * 4);
+    alloc(&h->hf, S * fc_width * 4 * FC1_KS); alloc(&h->q, S * MAXA * 4);
+    alloc(&h->qpart, (size_t)(fc_width / 16) * S * (MAXA + 1) * 4);
+    alloc(&h->ring_fo, (size_t)max_batch * 4 * sizeof(unsigned long long));
     const size_t Bm = max_batch;
-    alloc((void **)&h->dhf, Bm * fc_width * 4); alloc((void **)&h->dh3, Bm * 1600 * 4);
-    alloc((void **)&h->dh2, Bm * 1600 * 4); alloc((void **)&h->dp1, Bm * 3200 * 4);
-    alloc((void **)&h->gmax, (size_t)(fc_width / 16) * 4);
-    alloc((void **)&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc((void **)&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
-    if (sup.N) { alloc((void **)&h->c51_dl, Bm * 64 * 4); alloc((void **)&h->c51_xs, Bm * fc_width * 4); alloc((void **)&h->c51_lt, Bm * 4); }
-    if (is_c51d(h) || is_iqn(h)) for (int w = 0; w < 2; w++) alloc((void **)&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
+    alloc(&h->dhf, Bm * fc_width * 4); alloc(&h->dh3, Bm * 1600 * 4);
+    alloc(&h->dh2, Bm * 1600 * 4); alloc(&h->dp1, Bm * 3200 * 4);
+    alloc(&h->gmax, (size_t)(fc_width / 16) * 4);
+    alloc(&h->hf_act, S * fc_width * 4 * FC1_SP_KS); alloc(&h->hp_act, sizeof(float) * (size_t)(h->n - h->off.bf1));
+    if (sup.N) { alloc(&h->c51_dl, Bm * 64 * 4); alloc(&h->c51_xs, Bm * fc_width * 4); alloc(&h->c51_lt, Bm * 4); }
+    if (is_c51d(h) || is_iqn(h)) for (int w = 0; w < 2; w++) alloc(&h->heff[w], sizeof(float) * (size_t)(h->hoff.n - h->off.bf1));
     if (is_ac(h)) {
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
-        alloc((void **)&h->ac_dl, Bt * 16 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4); alloc((void **)&h->ac_r, Bt * 4); alloc((void **)&h->ac_t, Bt);
+        alloc(&h->ac_dl, Bt * 16 * 4); alloc(&h->ac_xs, Bt * fc_width * 4); alloc(&h->ac_r, Bt * 4); alloc(&h->ac_t, Bt);
     }
     if (is_sac(h)) {
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
-        alloc((void **)&h->ac_dl, Bt * 16 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4); alloc((void **)&h->sac_w, 8 * 4);
+        alloc(&h->ac_dl, Bt * 16 * 4); alloc(&h->ac_xs, Bt * fc_width * 4); alloc(&h->sac_w, 8 * 4);
     }
     if (is_iqn(h)) {                             // (sized by the train step's batch limit, not by max_batch: that is the env count)
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
-        alloc((void **)&h->ac_dl, Bt * 4 * 4); alloc((void **)&h->ac_xs, Bt * fc_width * 4);
-        alloc((void **)&h->iqn_dpre, Bt * h->iqn_n * fc_width * 4); alloc((void **)&h->iqn_ctab, Bt * h->iqn_n * FB_IQN_COS * 4);
+        alloc(&h->ac_dl, Bt * 4 * 4); alloc(&h->ac_xs, Bt * fc_width * 4);
+        alloc(&h->iqn_dpre, Bt * h->iqn_n * fc_width * 4); alloc(&h->iqn_ctab, Bt * h->iqn_n * FB_IQN_COS * 4);
     }
-    alloc((void **)&h->clip_part, sizeof(double) * 256); alloc((void **)&h->clip_out, sizeof(float) * 2);
+    alloc(&h->clip_part, sizeof(double) * 256); alloc(&h->clip_out, sizeof(float) * 2);
     if (e == hipSuccess) { const float one = 1.f; e = hipMemcpy(h->clip_out + 1, &one, sizeof(one), hipMemcpyHostToDevice); }      // (no clip yet: norm 0, c 1)
-    if (e != hipSuccess) {
-        fb_set_error(e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP, "fb_qnet_create: %s", hipGetErrorString(e));
-        fb_qnet_destroy(h);
-        return e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP;
-    }
-    *out = h;
-    {   // wsp has never been split: parameter versions start ahead of the split versions
+    int rc = e == hipSuccess ? FB_OK : fb_set_error(e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP, "fb_qnet_create: %s", hipGetErrorString(e));
+    if (rc == FB_OK) {   // wsp has never been split: parameter versions start ahead of the split versions
         AdamDev a; memset(&a, 0, sizeof(a));
         a.pver[0] = a.pver[1] = 1;
-        if (hipMemcpy(h->adam, &a, sizeof(a), hipMemcpyHostToDevice) != hipSuccess) { fb_qnet_destroy(h); *out = nullptr; return fb_set_error(FB_ERR_HIP, "fb_qnet_create: hipMemcpy failed"); }
+        if (hipMemcpy(h->adam, &a, sizeof(a), hipMemcpyHostToDevice) != hipSuccess) rc = fb_set_error(FB_ERR_HIP, "fb_qnet_create: hipMemcpy failed");
     }
-    return fb_qnet_set_hparams(h, 1e-6f, 0.9f, 0.999f, 1e-8f);
+    if (rc == FB_OK) rc = fb_qnet_set_hparams(h, 1e-6f, 0.9f, 0.999f, 1e-8f);
+    if (rc == FB_OK && is_sac(h)) rc = sac_write_words(h, 0.2f);      // (behind fb_qnet_set_hparams: the beta powers start at the net's betas)
+    if (rc != FB_OK) { fb_qnet_destroy(h); return rc; }                // the single failure exit: whatever was allocated is freed from the same list
+    *out = h;
+    return FB_OK;
 }
 
 extern "C" int fb_qnet_destroy(fb_qnet_t h) {
     if (!h) return FB_OK;
-    void *ptrs[] = {h->zeros, h->wsp[0], h->wsp[1], h->a1s, h->a3s, h->w1s[0], h->w1s[1], h->params[0], h->params[1], h->adam_m, h->adam_v, h->grad, h->slabs, h->slabs1, h->adam, h->p1, h->amax, h->h2,
-                    h->h3, h->hf, h->q, h->qpart, h->dhf, h->dh3, h->dh2, h->dp1, h->ring_fo, h->gmax, h->hf_act, h->hp_act,
-                    h->c51_dl, h->c51_xs, h->c51_lt, h->heff[0], h->heff[1], h->mst[0], h->mst[1], h->nz[0], h->nz[1],
-                    h->nz_zero, h->wsig, h->a3n, h->ht, h->sig_seen, h->clip_part, h->clip_out, h->ac_dl, h->ac_xs, h->ac_r, h->ac_t, h->sac_w,
-                    h->iqn_dpre, h->iqn_ctab};
     if (h->split) {
         FbSplitCtx *c = h->split;
         if (c->tstream) { (void)hipStreamSynchronize(c->tstream); (void)hipStreamDestroy(c->tstream); }
         if (c->f) (void)hipFree(c->f);
         delete c;
     }
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    for (void *p : h->allocs) (void)hipFree(p);
     delete h;
     return FB_OK;
 }
@@ -4604,13 +4621,8 @@ struct Plan {
     const float *iqn_tau, *iqn_tau_next; int iqn_m; float *iqn_theta; bool iqn_double, iqn_mu;
 };
 
-// A runtime value as a template argument: f is a generic lambda and gets a tag whose ::value is a constant expression, so that a kernel
-// template has ONE launch statement per call site, hipLaunchKernelGGL((kernel<decltype(tag)::value, ...>), ...), not one per instantiation
-#include <type_traits>
-template <int V> using IntTag = std::integral_constant<int, V>;
+// (IntTag, with_bool, with_actions: fb_head.h)  nsp: the operands' planes, 3 = fp32-equivalent, 1 = bf16
 template <class F> static void with_nsp(int nsp, F f) { if (nsp == 3) f(IntTag<3>{}); else f(IntTag<1>{}); }
-template <class F> static void with_bool(bool b, F f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-template <class F> static void with_actions(int A, F f) { if (A == 2) f(IntTag<2>{}); else f(IntTag<MAXA>{}); }
 
 template <class T> static void put_seed_words(T &c, uint64_t seed, uint64_t step) {      // the four words the head kernels take
     c.seed_lo = (uint32_t)seed; c.seed_hi = (uint32_t)(seed >> 32);
@@ -4781,48 +4793,54 @@ static void launch_dist_head(const fb_qnet *h, const C51HeadArgs &H, int rows, h
 
 // the head: launched on its own, or described into the rider (p.head_rider) for the launch that carries it
 static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
+    auto shared = [&](auto &H) {                 // the fields every head's struct has: where fc1's partial sums are and the head's shape
+        H.hf = c.fused ? h->hf_act : h->hf; H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A;
+    };
+    auto core = [&](auto &C) {                   // ... and what C51Core and HeadCore add to them (hoff: = off but for a folded head, whose layout is plain)
+        shared(C); C.q = h->q; C.off = h->hoff; C.actions = p.actions; C.epsilon = p.epsilon;
+        put_seed_words(C, p.seed, p.step);
+    };
+    // the heads of fb_ac.hip / fb_sac.hip / fb_iqn.hip, each a launch of its own over all rows.  P: the net's parameters (act_copy: of a
+    // fused acting forward the copy its fc1 launch took)
+    auto side = [&](auto &H, bool act_copy) {
+        memset(&H, 0, sizeof(H));
+        shared(H); H.rows = c.total; H.off = h->off; H.P = act_copy && c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;
+    };
+    auto policy = [&](auto &H) {                 // what an actor-critic and a SAC head put out alike
+        side(H, true);
+        H.logits = p.ac_logits; H.value = p.ac_value; H.logp = p.ac_logp; H.actions = p.actions; H.greedy = p.ac_greedy;
+        put_seed_words(H, p.seed, p.step);
+    };
     if (c.c51 && !p.train && !p.no_head && runs(c, K_HEAD)) {           // C51: the distributional head (stand-alone launch only; no env rider)
         C51HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns; H.params = nullptr;
         for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (a dueling C51 net: its folded head)
         C51Core &C = H.c;
-        C.hf = c.fused ? h->hf_act : h->hf; C.stot = c.stot; C.nks = c.big ? FC1_SP_KS : 1; C.q = h->q; C.probs = p.probs; C.FC = h->FC; C.A = h->A;
-        C.off = h->hoff; C.sup = h->sup; C.actions = p.actions; C.epsilon = p.epsilon;
-        put_seed_words(C, p.seed, p.step); C.key_of = nullptr; C.stream = FB_STREAM_EPS;
+        core(C); C.probs = p.probs; C.sup = h->sup; C.key_of = nullptr; C.stream = FB_STREAM_EPS;
         if (p.head_rider) {                          // fb_eval_run: describe the work (fb_qnet_c51_eval_head launches it)
             memset(p.head_rider, 0, sizeof(*p.head_rider));
             p.head_rider->c.hf = C.hf; p.head_rider->c.stot = c.stot; p.head_rider->c.nks = C.nks;
             p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params;
         } else launch_dist_head(h, H, c.total, c.st);
     }
-    if (c.sac && !p.train && p.policy_head && runs(c, K_HEAD)) {       // a SAC net's head (fb_sac.hip), a launch of its own
+    if (c.sac && !p.train && p.policy_head && runs(c, K_HEAD)) {       // a SAC net's head (fb_sac.hip)
         SacHeadArgs H;
-        memset(&H, 0, sizeof(H));
-        H.hf = c.fused ? h->hf_act : h->hf; H.P = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;      // (fused: the copy its fc1 launch took)
-        H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A; H.rows = c.total; H.off = h->off; H.so = h->sac_off; H.sw = h->sac_w;
-        H.logits = p.ac_logits; H.value = p.ac_value; H.logp = p.ac_logp; H.q1 = p.sac_q1; H.q2 = p.sac_q2; H.actions = p.actions; H.greedy = p.ac_greedy;
-        put_seed_words(H, p.seed, p.step);
-        fb_sac_launch_head(c.st, &H);
+        policy(H);
+        H.so = h->sac_off; H.sw = h->sac_w; H.q1 = p.sac_q1; H.q2 = p.sac_q2;
+        fb_sac_launch_head(c.st, H);
         return;
     }
-    if (c.iqn && !p.train && p.iqn_theta && runs(c, K_HEAD)) {         // an IQN net's theta at the caller's tau (fb_iqn.hip), a launch of its own
+    if (c.iqn && !p.train && p.iqn_theta && runs(c, K_HEAD)) {         // an IQN net's theta at the caller's tau (fb_iqn.hip)
         IqnHeadArgs H;
-        memset(&H, 0, sizeof(H));
-        H.hf = c.fused ? h->hf_act : h->hf; H.P = p.sl.s[0].params;
-        H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A; H.rows = c.total; H.M = p.iqn_m; H.off = h->off; H.io = h->iqn_off;
-        H.dueling = is_iqnd(h) ? 1 : 0;
-        H.tau = p.iqn_tau; H.theta = p.iqn_theta;
-        fb_iqn_launch_head(c.st, &H);
+        side(H, false);
+        H.M = p.iqn_m; H.io = h->iqn_off; H.dueling = is_iqnd(h) ? 1 : 0; H.tau = p.iqn_tau; H.theta = p.iqn_theta;
+        fb_iqn_launch_head(c.st, H);
         return;
     }
-    if (c.ac && !c.sac && !c.iqn && !p.train && p.ac_value && runs(c, K_HEAD)) {  // an actor-critic net's policy head (fb_ac.hip), a launch of its own
+    if (c.ac && !c.sac && !c.iqn && !p.train && p.ac_value && runs(c, K_HEAD)) {  // an actor-critic net's policy head (fb_ac.hip)
         AcHeadArgs H;
-        memset(&H, 0, sizeof(H));
-        H.hf = c.fused ? h->hf_act : h->hf; H.P = c.fused ? h->hp_act - h->off.bf1 : p.sl.s[0].params;      // (fused: the copy its fc1 launch took)
-        H.stot = c.stot; H.nks = c.big ? FC1_SP_KS : 1; H.FC = h->FC; H.A = h->A; H.rows = c.total; H.off = h->off;
-        H.logits = p.ac_logits; H.value = p.ac_value; H.logp = p.ac_logp; H.actions = p.actions; H.greedy = p.ac_greedy;
-        put_seed_words(H, p.seed, p.step);
-        fb_ac_launch_head(c.st, &H);
+        policy(H);
+        fb_ac_launch_head(c.st, H);
         return;
     }
     // (an actor-critic net without ac_value: the plain head over W_pi b_pi, the logits as "Q"; its train plans: the loss launches' own work)
@@ -4831,9 +4849,7 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         H.sl = p.sl; H.nslices = p.ns;
         for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (an IQN net: its fold; every scalar net: its parameters)
         HeadCore &C = H.c;
-        C.hf = c.fused ? h->hf_act : h->hf; C.stot = c.stot; C.nks = c.big ? FC1_SP_KS : 1; C.q = h->q; C.FC = h->FC; C.A = h->A;
-        C.dueling = h->arch == FB_ARCH_DUELING; C.off = h->hoff; C.actions = p.actions; C.epsilon = p.epsilon;      // (hoff: = off but for a dueling IQN net, whose fold is plain)
-        put_seed_words(C, p.seed, p.step);
+        core(C); C.dueling = h->arch == FB_ARCH_DUELING;
         // (the rider of a fused acting forward reads the head's parameters from the copy that forward's fc1 launch took: b_fc1 on)
         if (p.head_rider) { p.head_rider->c = C; p.head_rider->params = c.fused ? h->hp_act - h->off.bf1 : H.sl.s[0].params; p.head_rider->on = 1; p.head_rider->on_arrival = nullptr; p.head_rider->arrival_val = 0; }   // rides in the env launch
         else hipLaunchKernelGGL(head_kernel, dim3((c.total + 3) / 4), dim3(256), 0, c.st, H);
@@ -4844,59 +4860,60 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
 // the per-unit reductions; QR: per-sample targets / quantile Huber loss / dhf, then C51's per-unit reductions
 static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     const int B = p.B, FC = h->FC;
+    auto shared = [&](auto &L) {                 // the fields every family's loss struct has: the shapes, fc1's partial sums of the slices, the actions, dhf out
+        L.B = B; L.FC = FC; L.A = h->A; L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.hf = h->hf; L.act = p.a; L.dhf = h->dhf;
+    };
+    auto transition = [&](auto &L) { L.rew = p.r; L.term = p.t; L.gamma = p.gamma; };      // ... and those of every loss that bootstraps
+    // the losses of fb_ac.hip / fb_sac.hip / fb_iqn.hip: the net's own layout, the per-sample row in ac_dl
+    auto side = [&](auto &L) { memset(&L, 0, sizeof(L)); shared(L); L.off = h->off; L.dl = h->ac_dl; };
+    FbAdamHead *const adam_head = reinterpret_cast<FbAdamHead *>(h->adam);
     if (c.iqn) {                                 // IQN: per-sample a* / T / theta / loss / d theta / dhf, then the per-unit reductions (fb_iqn.hip)
         IqnLossMuArgs L;                         // (IqnLossArgs, then Munchausen's fields: all zero = the hard target)
-        memset(&L, 0, sizeof(L));
-        L.hf = h->hf; L.P0 = h->params[0]; L.P1 = h->params[1]; L.F = head_base(h, h->params[p.iqn_double ? 0 : 1]); L.arow0 = p.iqn_double ? B : 2 * B;
-        L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B; L.N = h->iqn_n; L.Np = h->iqn_np;
-        L.off = h->off; L.io = h->iqn_off; L.kappa = h->kappa; L.act = p.a; L.term = p.t; L.rew = p.r; L.gamma = p.gamma;
+        side(L); transition(L);
+        // a* from the target net's fold at its rows of s' (2 B ..), or (double_q) from the online net's at B ..  Munchausen: both Qbar rows over
+        // the TARGET net's fold, s at rows B .., s' at rows 2 B .. (iqn_train)
+        const bool tgt = p.iqn_mu || !p.iqn_double;
+        L.P0 = h->params[0]; L.P1 = h->params[1]; L.F = head_base(h, h->params[tgt ? 1 : 0]); L.arow0 = tgt ? 2 * B : B;
+        L.N = h->iqn_n; L.Np = h->iqn_np; L.io = h->iqn_off; L.kappa = h->kappa;
         L.tau = p.iqn_tau; L.tau_next = p.iqn_tau_next;
         put_seed_words(L, p.seed, p.step);
-        L.dl = h->ac_dl; L.gw = h->ac_xs; L.dhf = h->dhf; L.dpre = h->iqn_dpre; L.ctab = h->iqn_ctab; L.t_out = p.y;
+        L.gw = h->ac_xs; L.dpre = h->iqn_dpre; L.ctab = h->iqn_ctab; L.t_out = p.y;
         L.isw = p.isw; L.abs_err = p.abs_err;    // (both set: the prioritized form; the uniform calls leave both NULL)
         L.foff = h->hoff; L.dueling = is_iqnd(h) ? 1 : 0;       // (L.F is a fold: the plain layout's offsets, whatever the net's)
-        if (p.iqn_mu) {                          // Munchausen: both Qbar rows over the TARGET net's fold, s at rows B .., s' at rows 2 B .. (iqn_train_plan)
-            L.mu = 1; L.temp = h->iqn_md.tau; L.alpha = h->iqn_md.alpha; L.clip_lo = h->iqn_md.clip;
-            L.F = head_base(h, h->params[1]); L.arow0 = 2 * B; L.srow0 = B;
-        }
-        fb_iqn_launch_loss(c.st, &L);
+        if (p.iqn_mu) { L.mu = 1; L.temp = h->iqn_md.tau; L.alpha = h->iqn_md.alpha; L.clip_lo = h->iqn_md.clip; L.srow0 = B; }
+        fb_iqn_launch_loss(c.st, L);
         const IqnGradArgs gA{B, FC, h->A, h->iqn_n, h->off, h->iqn_off, h->ac_dl, h->ac_xs, h->dhf, h->iqn_dpre, h->iqn_ctab, p.G, p.loss, h->gmax,
-                             reinterpret_cast<FbAdamHead *>(h->adam), p.tick, is_iqnd(h) ? 1 : 0};
-        fb_iqn_launch_grad(c.st, &gA);
+                             adam_head, p.tick, is_iqnd(h) ? 1 : 0};
+        fb_iqn_launch_grad(c.st, gA);
         return;
     }
     if (c.sac) {                                 // SAC: per-sample target / losses / dz / dQ / dhf, then the per-unit reductions (fb_sac.hip)
         SacLossArgs L;
-        memset(&L, 0, sizeof(L));
-        L.hf = h->hf; L.P0 = h->params[0]; L.P1 = h->params[1]; L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B;
-        L.off = h->off; L.so = h->sac_off; L.sw = h->sac_w; L.act = p.a; L.term = p.t; L.rew = p.r; L.gamma = p.gamma;
-        L.dl = h->ac_dl; L.xs = h->ac_xs; L.dhf = h->dhf; L.y_out = p.y;
-        fb_sac_launch_loss(c.st, &L);
-        const SacGradArgs gA{B, FC, h->A, h->off, h->sac_off, h->ac_dl, h->ac_xs, h->dhf, p.G, p.loss, h->gmax, reinterpret_cast<FbAdamHead *>(h->adam),
+        side(L); transition(L);
+        L.P0 = h->params[0]; L.P1 = h->params[1]; L.so = h->sac_off; L.sw = h->sac_w; L.xs = h->ac_xs; L.y_out = p.y;
+        fb_sac_launch_loss(c.st, L);
+        const SacGradArgs gA{B, FC, h->A, h->off, h->sac_off, h->ac_dl, h->ac_xs, h->dhf, p.G, p.loss, h->gmax, adam_head,
                              p.tick, h->sac_w, h->sac_hbar, h->sac_alr, p.sac_temp ? 1 : 0};
-        fb_sac_launch_grad(c.st, &gA);
+        fb_sac_launch_grad(c.st, gA);
         return;
     }
     if (c.ac) {                                  // actor-critic: per-sample loss / dz / dV / dhf, then the per-unit reductions (fb_ac.hip)
         AcLossArgs L;
-        memset(&L, 0, sizeof(L));
-        L.hf = h->hf; L.P = h->params[0]; L.stot = c.stot; L.nks = c.big ? FC1_SP_KS : 1; L.FC = FC; L.A = h->A; L.B = B; L.off = h->off;
-        L.act = p.a; L.adv = p.ac_adv; L.ret = p.ac_ret; L.nt = p.ac_nt; L.cv = h->ac_cv; L.ce = h->ac_ce;
-        L.dl = h->ac_dl; L.xs = h->ac_xs; L.dhf = h->dhf;
-        if (p.ppo) {
-            const PpoLossArgs P{L, p.ppo_sel, p.ppo_logp, p.ppo_value, h->ppo_eps, h->ppo_vclip};
-            fb_ac_launch_ppo_loss(c.st, &P);
-        } else fb_ac_launch_loss(c.st, &L);
+        side(L);
+        L.P = h->params[0]; L.adv = p.ac_adv; L.ret = p.ac_ret; L.nt = p.ac_nt; L.cv = h->ac_cv; L.ce = h->ac_ce; L.xs = h->ac_xs;
+        if (p.ppo) fb_ac_launch_ppo_loss(c.st, PpoLossArgs{L, p.ppo_sel, p.ppo_logp, p.ppo_value, h->ppo_eps, h->ppo_vclip});
+        else fb_ac_launch_loss(c.st, L);
         const AcGradArgs gA{B, FC, h->A, h->off, h->ac_dl, h->ac_xs, h->dhf, p.ac_nt, h->ac_cv, h->ac_ce, p.G, p.loss, h->gmax,
-                            reinterpret_cast<FbAdamHead *>(h->adam), p.tick, p.ppo ? 5 : 3};
-        fb_ac_launch_grad(c.st, &gA);
+                            adam_head, p.tick, p.ppo ? 5 : 3};
+        fb_ac_launch_grad(c.st, gA);
         return;
     }
-    if (!c.c51) {                                // (large batches only: run_plan)
+    if (!c.c51) {                                // (large batches only, run_plan: nks is fc1_sp_kernel's 4 K slices)
         LossArgs L;
-        L.algo = p.algo; L.B = B; L.FC = FC; L.A = h->A; L.dueling = h->arch == FB_ARCH_DUELING; L.off = h->off;
-        L.params = h->params[0]; L.q = h->q; L.hf = h->hf; L.stot = c.stot; L.nks = FC1_SP_KS; L.act = p.a; L.rew = p.r; L.term = p.t; L.isw = p.isw;      // (only large batches come here: fc1_sp_kernel's 4 K slices)
-        L.gamma = p.gamma; L.grad = p.G; L.dhf = h->dhf; L.loss = p.loss; L.abs_err = p.abs_err; L.y_out = p.y; L.gmax = h->gmax;
+        shared(L); transition(L);
+        L.algo = p.algo; L.dueling = h->arch == FB_ARCH_DUELING; L.off = h->off;
+        L.params = h->params[0]; L.q = h->q; L.isw = p.isw;
+        L.grad = p.G; L.loss = p.loss; L.abs_err = p.abs_err; L.y_out = p.y; L.gmax = h->gmax;
         // data-parallel path: the loss kernel advances the Adam step counter as well (once per fb_qnet_apply_adam), so the
         // apply needs no launch of its own for it
         // (at most one tick per Adam update: guarded on the device by AdamDev::ticks / applies)
@@ -4912,23 +4929,22 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         return;
     }
     const bool pw = is_per_algo(p.algo);         // (prioritized: weighted loss; the priorities are KL (C51) / l_b (QR))
-    auto shared = [&](auto &L) {                 // the fields C51LossArgs and QRLossArgs have in common
-        L.B = B; L.FC = FC; L.A = h->A; L.nks = c.big ? FC1_SP_KS : 1; L.stot = c.stot; L.off = h->hoff;
+    auto dist = [&](auto &L) {                   // the fields C51LossArgs and QRLossArgs have in common
+        shared(L); transition(L); L.off = h->hoff;
         L.p_on = head_base(h, h->params[0]); L.p_next = head_base(h, p.sl.s[1].params);
         L.p_tgt = head_base(h, p.ns > 2 ? p.sl.s[2].params : p.sl.s[1].params);
-        L.hf = h->hf; L.act = p.a; L.rew = p.r; L.term = p.t; L.gamma = p.gamma;
-        L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt; L.dhf = h->dhf;
+        L.dl = h->c51_dl; L.xs = h->c51_xs; L.lterm = h->c51_lt;
         L.isw = pw ? p.isw : nullptr; L.abs_err = pw ? p.abs_err : nullptr;
     };
     with_actions(h->A, [&](auto a) { with_bool(pw, [&](auto w) {
         if (is_qr(h)) {
             QRLossArgs L;
-            shared(L);
+            dist(L);
             L.algo = is_double_qr(p.algo) ? FB_ALGO_QR_DOUBLE : FB_ALGO_QR; L.N = h->sup.N; L.kappa = h->kappa;
             hipLaunchKernelGGL((qr_loss_kernel<decltype(a)::value, decltype(w)::value>), dim3((B + 3) / 4), dim3(256), 0, c.st, L);
         } else {
             C51LossArgs L;
-            shared(L);
+            dist(L);
             L.algo = is_double_c51(p.algo) ? FB_ALGO_C51_DOUBLE : FB_ALGO_C51; L.sup = h->sup;
             hipLaunchKernelGGL((c51_loss_kernel<decltype(a)::value, decltype(w)::value>), dim3((B + 3) / 4), dim3(256), 0, c.st, L);
         }
@@ -5893,58 +5909,46 @@ int fb_qnet_iqn_check_train(fb_qnet_t h, int double_q, int B, double gamma, cons
     return check_gamma01(gamma, who);
 }
 
-static Plan iqn_train_plan(fb_qnet *h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
-                           const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma, float *loss, float *q_target,
-                           float *flat_grad, const FbRingSrc *ring) {
+// The IQN train step behind every entry point's NULL-argument checks (`who`: the one the messages name): gathered states (ring NULL) or the
+// ring-fed form; isw / abs_err both set: the prioritized form, the same plan with the importance weights in and the per-sample loss out
+// (the loss launch's weighted instantiation, fb_iqn.hip), else both NULL
+static int iqn_train(const char *who, fb_qnet *h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
+                     const uint8_t *t, const FbRingSrc *ring, const float *isw, const float *tau, const float *tau_next, uint64_t seed, uint64_t step,
+                     double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, who);
+    if (rc != FB_OK) return rc;
     Plan p = three_slice_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, ring);
     p.iqn_tau = tau; p.iqn_tau_next = tau_next; p.iqn_double = double_q != 0; p.seed = seed; p.step = step;
+    p.isw = isw; p.abs_err = abs_err;
     // Munchausen: the online net's s' slice is read by double_q alone, which is refused with it; its rows take s through the TARGET net
     // (fshift 0: plan_train_tail has left it alone), as FB_ALGO_MDQN's third slice does.  Both target slices are consecutive: one pass
     if (h->iqn_mu) { p.iqn_mu = true; p.sl.s[1] = Slice{h->params[1], s, B, B, h->w1s[1], 0}; }
-    return p;
+    return ring ? run_train(h, p, stream) : run_train_gathered(h, p, B, stream);
 }
 
 extern "C" int fb_qnet_iqn_train_step(fb_qnet_t h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
                                       const uint8_t *t, const float *tau, const float *tau_next, uint64_t seed, uint64_t step, double gamma,
                                       float *loss, float *q_target, float *flat_grad, void *stream) {
     FB_REQUIRE(h && s && a && r && s2 && t && loss, "fb_qnet_iqn_train_step: NULL argument");
-    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_qnet_iqn_train_step");
-    if (rc != FB_OK) return rc;
-    Plan p = iqn_train_plan(h, double_q, B, s, a, r, s2, t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, nullptr);
-    return run_train_gathered(h, p, B, stream);
+    return iqn_train("fb_qnet_iqn_train_step", h, double_q, B, s, a, r, s2, t, nullptr, nullptr, tau, tau_next, seed, step, gamma, loss, nullptr, q_target,
+                     flat_grad, stream);
 }
 
-int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int B, const FbRingSrc *ring, const float *tau, const float *tau_next, uint64_t seed, uint64_t step,
-                           double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
-    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss, "fb_iqn_train_from_replay: NULL argument");
-    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_iqn_train_from_replay");
-    if (rc != FB_OK) return rc;
-    Plan p = iqn_train_plan(h, double_q, B, nullptr, ring->a, ring->r, nullptr, ring->t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, ring);
-    return run_train(h, p, stream);
-}
-
-// the prioritized form of the two calls above: the same plan with the importance weights in and the per-sample loss out (the loss launch's
-// weighted instantiation, fb_iqn.hip)
 extern "C" int fb_qnet_iqn_per_train_step(fb_qnet_t h, int double_q, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2,
                                           const uint8_t *t, const float *isw, const float *tau, const float *tau_next, uint64_t seed, uint64_t step,
                                           double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
     FB_REQUIRE(h && s && a && r && s2 && t && loss, "fb_qnet_iqn_per_train_step: NULL argument");
     FB_REQUIRE(isw && abs_err, "fb_qnet_iqn_per_train_step: the prioritized step needs the importance weights (isw) and abs_err");
-    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_qnet_iqn_per_train_step");
-    if (rc != FB_OK) return rc;
-    Plan p = iqn_train_plan(h, double_q, B, s, a, r, s2, t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, nullptr);
-    p.isw = isw; p.abs_err = abs_err;
-    return run_train_gathered(h, p, B, stream);
+    return iqn_train("fb_qnet_iqn_per_train_step", h, double_q, B, s, a, r, s2, t, nullptr, isw, tau, tau_next, seed, step, gamma, loss, abs_err, q_target,
+                     flat_grad, stream);
 }
 
-int fb_qnet_iqn_per_train_ring(fb_qnet_t h, int double_q, int B, const FbRingSrc *ring, const float *isw, const float *tau, const float *tau_next,
-                               uint64_t seed, uint64_t step, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
-    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss && isw && abs_err, "fb_iqn_per_train_from_replay: NULL argument");
-    const int rc = fb_qnet_iqn_check_train(h, double_q, B, gamma, "fb_iqn_per_train_from_replay");
-    if (rc != FB_OK) return rc;
-    Plan p = iqn_train_plan(h, double_q, B, nullptr, ring->a, ring->r, nullptr, ring->t, tau, tau_next, seed, step, gamma, loss, q_target, flat_grad, ring);
-    p.isw = isw; p.abs_err = abs_err;
-    return run_train(h, p, stream);
+int fb_qnet_iqn_train_ring(fb_qnet_t h, int double_q, int B, const FbRingSrc *ring, const float *isw, const float *tau, const float *tau_next,
+                           uint64_t seed, uint64_t step, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream,
+                           const char *who) {
+    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss && !isw == !abs_err, "%s: NULL argument", who);
+    return iqn_train(who, h, double_q, B, nullptr, ring->a, ring->r, nullptr, ring->t, ring, isw, tau, tau_next, seed, step, gamma, loss, abs_err, q_target,
+                     flat_grad, stream);
 }
 
 // Measurement aid for bench.py: launch ONE kernel of the train-step plan (`kernel` = KernelId, see

@@ -9,7 +9,6 @@
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
 #include "fb_common.h"
 #include <math.h>
-#include <type_traits>
 
 namespace {
 #include "fb_head.h"
@@ -266,26 +265,17 @@ __global__ __launch_bounds__(256) void sac_grad_kernel(SacGradArgs L) {
     }
 }
 
-template <class F> void with_actions(int A, F f) {
-    if (A == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, MAXA>{});
-}
 }  // namespace
 
-void fb_sac_launch_head(hipStream_t st, const void *args) {
-    SacHeadArgs H;
-    memcpy(&H, args, sizeof(H));
+void fb_sac_launch_head(hipStream_t st, const SacHeadArgs &H) {
     with_actions(H.A, [&](auto a) { hipLaunchKernelGGL(sac_head_kernel<decltype(a)::value>, dim3((H.rows + 3) / 4), dim3(256), 0, st, H); });
 }
 
-void fb_sac_launch_loss(hipStream_t st, const void *args) {
-    SacLossArgs L;
-    memcpy(&L, args, sizeof(L));
+void fb_sac_launch_loss(hipStream_t st, const SacLossArgs &L) {
     with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(sac_loss_kernel<decltype(a)::value>, dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
 }
 
-void fb_sac_launch_grad(hipStream_t st, const void *args) {
-    SacGradArgs L;
-    memcpy(&L, args, sizeof(L));
+void fb_sac_launch_grad(hipStream_t st, const SacGradArgs &L) {
     hipLaunchKernelGGL(sac_grad_kernel, dim3(L.FC / 16), dim3(256), 0, st, L);
 }
 

@@ -21,6 +21,12 @@ def _dev_check(*tensors):
             raise ValueError("tensors handed to the HIP path must be contiguous CUDA(ROCm) tensors")
 
 
+def _check_states(name, x, rows=None):
+    """`name` must be uint8[B,80,80,4] (rows: with that B)"""
+    if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (80, 80, 4) or (rows is not None and x.shape[0] != rows):
+        raise ValueError(f"{name} must be uint8[B,80,80,4]")
+
+
 class VecGameState:
     """N independent Flappy Bird games on the GPU (game/wrapped_flappy_bird.py:58-183)."""
 
@@ -714,8 +720,7 @@ class QNet:
         """u8 states -> (logits f32[B, A], value f32[B]) of the online net (fb_qnet_forward_ac)"""
         self._need_ac("forward_ac")
         _dev_check(states)
-        if states.dtype != torch.uint8 or states.dim() != 4 or tuple(states.shape[1:]) != (80, 80, 4):
-            raise ValueError("states must be uint8[B,80,80,4]")
+        _check_states("states", states)
         B = states.shape[0]
         z = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
         v = torch.empty(B, dtype=torch.float32, device=self.device)
@@ -753,8 +758,7 @@ class QNet:
         -> loss f32[4] (device): the chunk's share of (total, policy, value, entropy)"""
         self._need_ac("ac_train_step")
         _dev_check(s, a, adv, ret, flat_grad)
-        if s.dtype != torch.uint8 or s.dim() != 4 or tuple(s.shape[1:]) != (80, 80, 4):
-            raise ValueError("s must be uint8[B,80,80,4]")
+        _check_states("s", s)
         B = s.shape[0]
         check_ac_batch(B, a, adv, ret, n_total, flat_grad, self.n_params)
         loss = torch.zeros(4, dtype=torch.float32, device=self.device)
@@ -782,8 +786,7 @@ class QNet:
         -> loss f32[6] (device): the chunk's share of (total, policy, value, entropy, clip fraction, approximate KL)"""
         self._need_ac("ppo_train_step")
         _dev_check(s, a, adv, ret, logp_old, value_old, flat_grad)
-        if s.dtype != torch.uint8 or s.dim() != 4 or tuple(s.shape[1:]) != (80, 80, 4):
-            raise ValueError("s must be uint8[B,80,80,4]")
+        _check_states("s", s)
         B = s.shape[0]
         check_chunk(B, a, n_total, flat_grad, self.n_params)
         check_ppo_batch(B, None, adv, ret, logp_old, value_old)
@@ -829,8 +832,7 @@ class QNet:
         """u8 states -> (logits, q1, q2), each f32[B, A], of the online or the target net (fb_qnet_forward_sac)"""
         self._need_sac("forward_sac")
         _dev_check(states)
-        if states.dtype != torch.uint8 or states.dim() != 4 or tuple(states.shape[1:]) != (80, 80, 4):
-            raise ValueError("states must be uint8[B,80,80,4]")
+        _check_states("states", states)
         B = states.shape[0]
         z, q1, q2 = (torch.empty((B, self.A), dtype=torch.float32, device=self.device) for _ in range(3))
         L.check(L.lib().fb_qnet_forward_sac(self.h, int(which), L.ptr(states), B, L.ptr(z), L.ptr(q1), L.ptr(q2), L.current_stream()),
@@ -844,8 +846,7 @@ class QNet:
         self._need_sac("sac_train_step")
         _dev_check(s, a, r, s2, t, flat_grad)
         for name, x in (("s", s), ("s2", s2)):
-            if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (80, 80, 4) or x.shape[0] != s.shape[0]:
-                raise ValueError(f"{name} must be uint8[B,80,80,4]")
+            _check_states(name, x, s.shape[0])
         B = s.shape[0]
         check_sac_batch(B, a, r, t, flat_grad, self.n_params)
         loss = torch.zeros(6, dtype=torch.float32, device=self.device)
@@ -891,8 +892,7 @@ class QNet:
         """u8 states [B,80,80,4], tau f32[B, M] (1 <= M <= 64) -> theta f32[B, M, A] of the online or the target net (fb_qnet_forward_iqn)"""
         self._need_iqn("forward_iqn")
         _dev_check(states, tau)
-        if states.dtype != torch.uint8 or states.dim() != 4 or tuple(states.shape[1:]) != (80, 80, 4):
-            raise ValueError("states must be uint8[B,80,80,4]")
+        _check_states("states", states)
         B = states.shape[0]
         if tau.dtype != torch.float32 or tau.dim() != 2 or tau.shape[0] != B or not 1 <= tau.shape[1] <= 64 or not tau.is_contiguous():
             raise ValueError("tau must be a contiguous float32[B, M] with 1 <= M <= 64")
@@ -902,24 +902,37 @@ class QNet:
                 "fb_qnet_forward_iqn")
         return theta
 
+    def _iqn_train_step(self, what, s, a, r, s2, t, isw, gamma, double_q, tau, tau_next, seed, step, flat_grad, want_target):
+        """iqn_train_step, and with `what` == 'iqn_per_train_step' its prioritized form (isw in, abs_err out)
+        -> (loss f32[1], abs_err f32[B] or None, q_target f32[B, n_tau_next] or None)"""
+        weighted = what == "iqn_per_train_step"
+        self._need_iqn(what)
+        _dev_check(s, a, r, s2, t, isw, flat_grad, tau, tau_next)
+        for name, x in (("s", s), ("s2", s2)):
+            _check_states(name, x, s.shape[0])
+        B = s.shape[0]
+        N, Np = self.iqn()[:2]
+        check_iqn_batch(B, a, r, t, tau, tau_next, N, Np, flat_grad, self.n_params)
+        if weighted:
+            check_isw(B, isw)
+        loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        ae = torch.empty(B, dtype=torch.float32, device=self.device) if weighted else None
+        y = torch.empty((B, Np), dtype=torch.float32, device=self.device) if want_target else None
+        batch = (self.h, int(bool(double_q)), B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t))
+        draws = (L.ptr(tau), L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss))
+        out = (L.ptr(y), L.ptr(flat_grad), L.current_stream())
+        if weighted:
+            L.check(L.lib().fb_qnet_iqn_per_train_step(*batch, L.ptr(isw), *draws, L.ptr(ae), *out), "fb_qnet_iqn_per_train_step")
+        else:
+            L.check(L.lib().fb_qnet_iqn_train_step(*batch, *draws, *out), "fb_qnet_iqn_train_step")
+        return loss, ae, y
+
     def iqn_train_step(self, s, a, r, s2, t, gamma=0.99, double_q=False, tau=None, tau_next=None, seed=0, step=0, flat_grad=None,
                        want_target=True):
         """one IQN step on <= 256 gathered transitions (fb_qnet_iqn_train_step).  tau f32[B, n_tau] / tau_next f32[B, n_tau_next], or None:
         the draws of (seed, step) (iqn_draw_taus).  flat_grad=None applies Adam; a float32[n_params] tensor receives the gradient instead.
         -> (loss f32[1], q_target f32[B, n_tau_next] or None)"""
-        self._need_iqn("iqn_train_step")
-        _dev_check(s, a, r, s2, t, flat_grad, tau, tau_next)
-        for name, x in (("s", s), ("s2", s2)):
-            if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (80, 80, 4) or x.shape[0] != s.shape[0]:
-                raise ValueError(f"{name} must be uint8[B,80,80,4]")
-        B = s.shape[0]
-        N, Np = self.iqn()[:2]
-        check_iqn_batch(B, a, r, t, tau, tau_next, N, Np, flat_grad, self.n_params)
-        loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        y = torch.empty((B, Np), dtype=torch.float32, device=self.device) if want_target else None
-        L.check(L.lib().fb_qnet_iqn_train_step(self.h, int(bool(double_q)), B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), L.ptr(tau),
-                                               L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(y), L.ptr(flat_grad),
-                                               L.current_stream()), "fb_qnet_iqn_train_step")
+        loss, _, y = self._iqn_train_step("iqn_train_step", s, a, r, s2, t, None, gamma, double_q, tau, tau_next, seed, step, flat_grad, want_target)
         return loss, y
 
     def iqn_per_train_step(self, s, a, r, s2, t, isw, gamma=0.99, double_q=False, tau=None, tau_next=None, seed=0, step=0, flat_grad=None,
@@ -927,22 +940,7 @@ class QNet:
         """iqn_train_step with importance weights isw f32[B] (fb_qnet_iqn_per_train_step): the loss is mean_b w_b l_b, the gradient that of
         l_b / B times w_b; abs_err[b] = l_b, without the weight, is the priority.  isw = 1 gives iqn_train_step's bits.
         -> (loss f32[1], abs_err f32[B], q_target f32[B, n_tau_next] or None)"""
-        self._need_iqn("iqn_per_train_step")
-        _dev_check(s, a, r, s2, t, isw, flat_grad, tau, tau_next)
-        for name, x in (("s", s), ("s2", s2)):
-            if x.dtype != torch.uint8 or x.dim() != 4 or tuple(x.shape[1:]) != (80, 80, 4) or x.shape[0] != s.shape[0]:
-                raise ValueError(f"{name} must be uint8[B,80,80,4]")
-        B = s.shape[0]
-        N, Np = self.iqn()[:2]
-        check_iqn_batch(B, a, r, t, tau, tau_next, N, Np, flat_grad, self.n_params)
-        check_isw(B, isw)
-        loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        ae = torch.empty(B, dtype=torch.float32, device=self.device)
-        y = torch.empty((B, Np), dtype=torch.float32, device=self.device) if want_target else None
-        L.check(L.lib().fb_qnet_iqn_per_train_step(self.h, int(bool(double_q)), B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), L.ptr(isw),
-                                                   L.ptr(tau), L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(ae),
-                                                   L.ptr(y), L.ptr(flat_grad), L.current_stream()), "fb_qnet_iqn_per_train_step")
-        return loss, ae, y
+        return self._iqn_train_step("iqn_per_train_step", s, a, r, s2, t, isw, gamma, double_q, tau, tau_next, seed, step, flat_grad, want_target)
 
     # -- noise (noisy nets) ---------------------------------------------------------
     def _need_noisy(self, what):
@@ -1011,8 +1009,7 @@ class QNet:
         if sup is None:
             raise ValueError("forward_dist needs a C51 net (arch='c51' or 'c51dueling')")
         B = states.shape[0]
-        if states.dtype != torch.uint8 or tuple(states.shape[1:]) != (80, 80, 4):
-            raise ValueError("states must be uint8[B,80,80,4]")
+        _check_states("states", states)
         p = torch.empty((B, self.A, sup[0]), dtype=torch.float32, device=self.device)
         L.check(L.lib().fb_qnet_forward_dist(self.h, which, L.ptr(states), B, L.ptr(p), L.current_stream()), "fb_qnet_forward_dist")
         return p
@@ -1024,8 +1021,7 @@ class QNet:
         if qs is None:
             raise ValueError("forward_quantiles needs a QR net (arch='qr' or 'qrdueling')")
         B = states.shape[0]
-        if states.dtype != torch.uint8 or tuple(states.shape[1:]) != (80, 80, 4):
-            raise ValueError("states must be uint8[B,80,80,4]")
+        _check_states("states", states)
         th = torch.empty((B, self.A, qs[0]), dtype=torch.float32, device=self.device)
         L.check(L.lib().fb_qnet_forward_quantiles(self.h, which, L.ptr(states), B, L.ptr(th), L.current_stream()), "fb_qnet_forward_quantiles")
         return th
@@ -1033,8 +1029,7 @@ class QNet:
     def forward(self, states, which=L.NET_ONLINE):
         _dev_check(states)
         B = states.shape[0]
-        if states.dtype != torch.uint8 or tuple(states.shape[1:]) != (80, 80, 4):
-            raise ValueError("states must be uint8[B,80,80,4]")
+        _check_states("states", states)
         q = self._get(f"q{B}", (B, self.A), torch.float32)
         L.check(L.lib().fb_qnet_forward(self.h, which, L.ptr(states), B, L.ptr(q), L.current_stream()), "fb_qnet_forward")
         return q
@@ -1198,20 +1193,36 @@ def iqn_draw_taus(batch, n, seed=0, step=0, which=0, device="cuda"):
     return out
 
 
+def _iqn_train_from_replay(name, replay, net, idx, isw, gamma, double_q, tau, tau_next, seed, step, flat_grad, want_target):
+    """iqn_train_from_replay, and with `name` == 'iqn_per_train_from_replay' its prioritized form (a prioritized memory, isw in, abs_err out)
+    -> (loss f32[1], a u8[B], r f32[B], t u8[B], q_target f32[B, n_tau_next] or None, abs_err f32[B] or None)"""
+    weighted = name == "iqn_per_train_from_replay"
+    B, dev, a, loss = _ring_call(name, replay, net, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1, flat_grad, tau, tau_next, isw,
+                                 prioritized=weighted)
+    N, Np = net.iqn()[:2]
+    check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
+    if weighted:
+        check_isw(B, isw)
+    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    ae = torch.empty(B, dtype=torch.float32, device=dev) if weighted else None
+    y = torch.empty((B, Np), dtype=torch.float32, device=dev) if want_target else None
+    batch = (replay.h, net.h, int(bool(double_q)), B, L.ptr(idx))
+    art = (L.ptr(a), L.ptr(r), L.ptr(t), L.ptr(tau), L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss))
+    out = (L.ptr(y), L.ptr(flat_grad), L.current_stream())
+    if weighted:
+        L.check(L.lib().fb_iqn_per_train_from_replay(*batch, L.ptr(isw), *art, L.ptr(ae), *out), "fb_iqn_per_train_from_replay")
+    else:
+        L.check(L.lib().fb_iqn_train_from_replay(*batch, *art, *out), "fb_iqn_train_from_replay")
+    return loss, a, r, t, y, ae
+
+
 def iqn_train_from_replay(replay, net, idx, gamma=0.99, double_q=False, tau=None, tau_next=None, seed=0, step=0, flat_grad=None,
                           want_target=False):
     """QNet.iqn_train_step on the transitions at the deque positions idx of a uniform memory (any n-step view; gamma must be the memory's),
     read from its frame ring in place (fb_iqn_train_from_replay)
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, q_target f32[B, n_tau_next]])"""
-    B, dev, a, loss = _ring_call("iqn_train_from_replay", replay, net, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
-                                 flat_grad, tau, tau_next)
-    N, Np = net.iqn()[:2]
-    check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
-    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
-    y = torch.empty((B, Np), dtype=torch.float32, device=dev) if want_target else None
-    L.check(L.lib().fb_iqn_train_from_replay(replay.h, net.h, int(bool(double_q)), B, L.ptr(idx), L.ptr(a), L.ptr(r), L.ptr(t), L.ptr(tau),
-                                             L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(y), L.ptr(flat_grad),
-                                             L.current_stream()), "fb_iqn_train_from_replay")
+    loss, a, r, t, y, _ = _iqn_train_from_replay("iqn_train_from_replay", replay, net, idx, None, gamma, double_q, tau, tau_next, seed, step, flat_grad,
+                                                 want_target)
     return (loss, a, r, t, y) if want_target else (loss, a, r, t)
 
 
@@ -1220,17 +1231,8 @@ def iqn_per_train_from_replay(replay, net, idx, isw, gamma=0.99, double_q=False,
     """QNet.iqn_per_train_step on the transitions at the SumTree leaves idx of a prioritized memory (any n-step view; gamma must be the
     memory's), read from its frame ring in place (fb_iqn_per_train_from_replay); isw f32[B]: replay.sample's importance weights
     -> (loss f32[1], a u8[B], r f32[B], t u8[B][, q_target f32[B, n_tau_next]], abs_err f32[B])"""
-    B, dev, a, loss = _ring_call("iqn_per_train_from_replay", replay, net, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1,
-                                 flat_grad, tau, tau_next, isw, prioritized=True)
-    N, Np = net.iqn()[:2]
-    check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
-    check_isw(B, isw)
-    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
-    ae = torch.empty(B, dtype=torch.float32, device=dev)
-    y = torch.empty((B, Np), dtype=torch.float32, device=dev) if want_target else None
-    L.check(L.lib().fb_iqn_per_train_from_replay(replay.h, net.h, int(bool(double_q)), B, L.ptr(idx), L.ptr(isw), L.ptr(a), L.ptr(r), L.ptr(t),
-                                                 L.ptr(tau), L.ptr(tau_next), int(seed), int(step), float(gamma), L.ptr(loss), L.ptr(ae), L.ptr(y),
-                                                 L.ptr(flat_grad), L.current_stream()), "fb_iqn_per_train_from_replay")
+    loss, a, r, t, y, ae = _iqn_train_from_replay("iqn_per_train_from_replay", replay, net, idx, isw, gamma, double_q, tau, tau_next, seed, step,
+                                                  flat_grad, want_target)
     return (loss, a, r, t, y, ae) if want_target else (loss, a, r, t, ae)
 
 
@@ -1412,36 +1414,34 @@ class SacStep:
         return self.actions
 
 
-class IqnStep:
+class _IqnStep:
+    """what IqnStep and IqnPerStep are: the pointers bound once, and one host call per step (`entry`; prioritized: the kind of memory it takes)"""
+    entry, prioritized = None, False
+
+    def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
+        _bind_step(self, type(self).__name__, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1,
+                   prioritized=self.prioritized)
+        self.double_q = bool(double_q)
+
+    def __call__(self, epsilon=0.0, seed=0, step=0, train=True):
+        """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the loss is self.loss"""
+        L.check(getattr(L.lib(), self.entry)(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(self.double_q), self.batch,
+                                            float(epsilon), int(seed), int(step), int(bool(train)), self.gamma, L.current_stream()), self.entry)
+        return self.actions
+
+
+class IqnStep(_IqnStep):
     """One whole step of the IQN loop as a single host call (fb_iqn_step): epsilon-greedy on the folded head -> frame_step -> store +
     sample the minibatch -> (train) the IQN step from the ring, its tau drawn from (seed, step).  The results of the separate calls in
     that order; the pointers are bound once."""
-
-    def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
-        _bind_step(self, "IqnStep", IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1)
-        self.double_q = bool(double_q)
-
-    def __call__(self, epsilon=0.0, seed=0, step=0, train=True):
-        """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the loss is self.loss"""
-        L.check(L.lib().fb_iqn_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(self.double_q), self.batch,
-                                    float(epsilon), int(seed), int(step), int(bool(train)), self.gamma, L.current_stream()), "fb_iqn_step")
-        return self.actions
+    entry = "fb_iqn_step"
 
 
-class IqnPerStep:
+class IqnPerStep(_IqnStep):
     """IqnStep on a prioritized memory (fb_iqn_per_step): epsilon-greedy on the folded head -> frame_step -> store -> (train) Memory.sample
     -> the weighted IQN step from the ring -> Memory.batch_update with the per-sample loss, all in line on one stream.  The results of the
     separate calls in that order; it owns idx, isw (f64), isw32 and abs_err (l_b as the loss left it)."""
-
-    def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
-        _bind_step(self, "IqnPerStep", IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1, prioritized=True)
-        self.double_q = bool(double_q)
-
-    def __call__(self, epsilon=0.0, seed=0, step=0, train=True):
-        """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the loss is self.loss"""
-        L.check(L.lib().fb_iqn_per_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, int(self.double_q), self.batch,
-                                        float(epsilon), int(seed), int(step), int(bool(train)), self.gamma, L.current_stream()), "fb_iqn_per_step")
-        return self.actions
+    entry, prioritized = "fb_iqn_per_step", True
 
 
 class TrainSteps:
