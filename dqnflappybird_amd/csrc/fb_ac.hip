@@ -19,50 +19,13 @@ namespace {
 
 constexpr int AC_MAXB = 256;         // the train step's batch limit (fb_qnet.hip MAXTB)
 
-// logits z[0 .. A) and V of state smp on every lane of the wave (xor butterfly: the same bits everywhere).  The logits are formed exactly
-// as head_one_t forms the plain head's outputs over W_pi / b_pi -- a lane takes 4 consecutive units per round, fmaf in unit order, then
-// the butterfly, then the bias -- so fb_qnet_forward on an AC net returns these very bits.  No load under a branch: columns a >= A read
-// column 0 and are never used.
-template <int AT>
-__device__ __forceinline__ void ac_row(const float *__restrict__ hf, int stot, int nks, int FC, int A, const NetOff &off, const float *__restrict__ P,
-                                       int smp, int lane, float (&z)[AT], float &V) {
-    float acc[AT + 1], bq[AT];
-#pragma unroll
-    for (int a = 0; a <= AT; a++) acc[a] = 0.f;
-#pragma unroll
-    for (int a = 0; a < AT; a++) bq[a] = P[off.bq + (a < A ? a : 0)];
-    const float bv = P[off.bv];
-    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
-        float x4[4], w[4][AT], wv[4];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-#pragma unroll
-            for (int a = 0; a < AT; a++) w[e][a] = P[off.wq + (j0 + e) * A + (a < A ? a : 0)];
-            wv[e] = P[off.wv + j0 + e];
-        }
-        ac_units4(hf, stot, nks, FC, P, off.bf1, smp, j0, x4);
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-#pragma unroll
-            for (int a = 0; a < AT; a++) acc[a] = fmaf(x4[e], w[e][a], acc[a]);
-            acc[AT] = fmaf(x4[e], wv[e], acc[AT]);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a <= AT; a++)
-        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o);
-#pragma unroll
-    for (int a = 0; a < AT; a++) z[a] = a < A ? acc[a] + bq[a] : 0.f;
-    V = acc[AT] + bv;
-}
-
 template <int AT>
 __global__ __launch_bounds__(256) void ac_head_kernel(AcHeadArgs H) {
     const int lane = threadIdx.x & 63, smp = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (smp >= H.rows) return;                                   // (wave-uniform)
     const int A = AT == MAXA ? H.A : AT;
     float z[AT], V;
-    ac_row<AT>(H.hf, H.stot, H.nks, H.FC, A, H.off, H.P, smp, lane, z, V);
+    row_head<AT, true, const NetOff &>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off, smp, lane, z, &V);
     if (lane != 0) return;
     H.value[smp] = V;
     if (H.logits) {
@@ -72,8 +35,12 @@ __global__ __launch_bounds__(256) void ac_head_kernel(AcHeadArgs H) {
     if (!H.actions) return;
     float p[AT], lp[AT], m, s;
     ac_softmax<AT>(z, A, p, lp, m, s);
+    // The policy draw: greedy takes the first maximum; otherwise word x of Philox(seed, (smp, step) on FB_STREAM_POLICY) gives u and the
+    // action is the first c with u < p_0 + .. + p_c, A - 1 when rounding leaves none; then logp of the action.  fb_sac.hip's sac_head_kernel
+    // holds the same statements.  They are not one function: inlined from a header, these statements index lp[] through 8 KiB of LDS at
+    // AT = MAXA, and a form that indexes nothing changed sac_head_kernel<2>'s instructions, whose step then could not be shown no slower
     int act = 0;
-    if (H.greedy) {                                              // first maximum
+    if (H.greedy) {
 #pragma unroll
         for (int c = 1; c < AT; c++) if (c < A && z[c] > z[act]) act = c;
     } else {
@@ -130,7 +97,7 @@ __global__ __launch_bounds__(256) void ac_loss_kernel(AcLossArgs L) {
     const int a_raw = L.act[b], ab = a_raw < A ? a_raw : A - 1;  // (an action past the head reads the last one: stays in bounds)
     const float adv = L.adv[b], ret = L.ret[b];
     float z[AT], V, p[AT], lp[AT], m, s;
-    ac_row<AT>(L.hf, L.stot, L.nks, FC, A, L.off, L.P, b, lane, z, V);
+    row_head<AT, true, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.P, L.off, b, lane, z, &V);
     ac_softmax<AT>(z, A, p, lp, m, s);
     float H = 0.f, lpa = lp[0];
 #pragma unroll
@@ -181,7 +148,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(PpoLossArgs Q) {
     const long long k = SEL ? Q.sel[b] : (long long)b;
     const float adv = L.adv[k], ret = L.ret[k], lpo = Q.logp_old[k], vo = Q.value_old[k];
     float z[AT], V, p[AT], lp[AT], m, s;
-    ac_row<AT>(L.hf, L.stot, L.nks, FC, A, L.off, L.P, b, lane, z, V);
+    row_head<AT, true, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.P, L.off, b, lane, z, &V);
     ac_softmax<AT>(z, A, p, lp, m, s);
     float H = 0.f, lpa = lp[0];
 #pragma unroll
@@ -284,6 +251,11 @@ __global__ __launch_bounds__(256) void ac_permute_kernel(long long n, uint32_t s
 // ---- training, launch 2 of 2: one workgroup per 16 fc1 units (c51_grad_kernel's grid): b_fc1's gradient and the tile's maximum |dhf|
 // (fc1_bwd_big_kernel's pre-scale), then thread (unit jl, column c) walks the samples in order: c < A is W_pi's column c, c = 8 is W_v.
 // Workgroup 0 also sums b_pi, b_v and the loss terms the same way (nterms: A2C's three, or PPO's five), forms the loss numbers and ticks Adam.
+// The prologue -- thread group bg sums dhf[b][j00 + jl] over b = bg, bg + 16, ..; the 16 partial sums are added in ascending bg into b_fc1's
+// gradient; max |dhf| goes to gmax; one barrier, which also publishes dlt / xt -- stands in sac_grad_kernel and iqn_grad_kernel too,
+// statement for statement.  As one shared function it kept every kernel's registers but moved instructions (one in this kernel, one in
+// sac_grad_kernel, a few in iqn_grad_kernel), and step times within a microsecond of the parent's could not be shown to be no slower
+// (profiles/device_helpers_family_times.txt).
 __global__ __launch_bounds__(256) void ac_grad_kernel(AcGradArgs L) {
     __shared__ float dlt[AC_MAXB * 16];
     __shared__ float xt[AC_MAXB * 16];
@@ -328,12 +300,7 @@ __global__ __launch_bounds__(256) void ac_grad_kernel(AcGradArgs L) {
         L.loss[1] = lsum[0]; L.loss[2] = lsum[1]; L.loss[3] = lsum[2];
         L.loss[0] = (lsum[0] + L.cv * lsum[1]) - L.ce * lsum[2];
         if (L.nterms == 5) { L.loss[4] = lsum[3]; L.loss[5] = lsum[4]; }      // PPO: the clip fraction and the approximate KL
-        FbAdamHead &ad = *L.adam;
-        if (L.tick && ad.ticks == ad.applies) {                  // (as c51_grad_kernel)
-            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
-            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
-            ad.ticks += 1;
-        }
+        adam_tick(L.adam, L.tick);
     }
 }
 

@@ -241,7 +241,7 @@ int fb_qnet_act_nib_env_noise_keep(fb_qnet_t h, const uint8_t *nib_states, int n
 // ---- advantage actor-critic (FB_ARCH_AC): the kernels live in fb_ac.hip, a code object of their own; fb_qnet.hip fills these structs and
 // hands them to the launchers below.  P: the net's parameters (or the fused acting forward's copy, hp_act - off.bf1); off: the dueling
 // layout, wv / bv = W_v b_v, wq / bq = W_pi b_pi
-struct FbAdamHead { float b1pow, b2pow, alpha, lr, b1, b2, eps, pad; int ticks, applies; };      // the front of fb_qnet.hip's AdamDev
+struct FbAdamHead { float b1pow, b2pow, alpha, lr, b1, b2, eps, pad; int ticks, applies; };      // the base of fb_qnet.hip's AdamDev
 struct AcHeadArgs {
     const float *hf, *P; int stot, nks, FC, A, rows; NetOff off;
     float *logits, *value, *logp; uint8_t *actions;              // logits f32[rows][A] or NULL; logp or NULL; actions NULL: no action (forward_ac)

@@ -17,6 +17,30 @@ __device__ __forceinline__ float4 sel4(bool ok, float4 v) {
     return make_float4(ok ? v.x : 0.f, ok ? v.y : 0.f, ok ? v.z : 0.f, ok ? v.w : 0.f);
 }
 
+// Adam's step counter for the update that follows a gradient pass: alpha_t and the beta powers advance (a "tick") only when the
+// previous tick has been consumed by an Adam update (ticks == applies), so a second gradient pass before the apply re-uses it.  On ONE
+// thread of the launch.  AD: fb_qnet.hip's AdamDev, or its base FbAdamHead (the side objects' view)
+template <class AD>
+__device__ __forceinline__ void adam_tick(AD *adam, int tick) {
+    if (tick && adam->ticks == adam->applies) {
+        AD &ad = *adam;
+        ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
+        ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
+        ad.ticks += 1;
+    }
+}
+
+// which slice (and so which net's parameters) row sidx of a head launch over nslices slices belongs to: P <- the slice's parameters;
+// returns the row in hf / q, or -1 past the last slice.  SL: fb_qnet.hip's Slices
+template <class SL>
+__device__ __forceinline__ int slice_row(const SL &sl, int nslices, int sidx, const float *&P) {
+    for (int z = 0; z < nslices; z++) {
+        if (sidx < sl.s[z].count) { P = sl.s[z].params; return sl.s[z].s_off + sidx; }
+        sidx -= sl.s[z].count;
+    }
+    return -1;
+}
+
 // P = the network's flat parameters, smp = row of the state in hf / q / actions.  Returns the action (0 without C.actions).
 // AT = the number of actions when it is known at compile time (2: the game's), MAXA = read it from C.A.
 // key / stream: the epsilon draw's counter (default: the row smp on FB_STREAM_EPS; fb_eval_run: the env id on FB_STREAM_EVAL).

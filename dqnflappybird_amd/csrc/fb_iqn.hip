@@ -70,33 +70,6 @@ __device__ __forceinline__ float iqn_eff_col(const float *__restrict__ v, const 
     return r;
 }
 
-// the plain head of state smp over the parameters P on every lane of the wave: head_one_t's loads, sums and order (as fb_sac.hip's sac_head),
-// so over a fold block these are the very bits fb_qnet_forward returns.  No load under a branch: columns a >= A read column 0.
-template <int AT>
-__device__ __forceinline__ void iqn_plain_head(const float *__restrict__ hf, int stot, int nks, int FC, int A, const float *__restrict__ P, const NetOff &off,
-                                               int smp, int lane, float (&out)[AT]) {
-    float acc[AT], bq[AT];
-#pragma unroll
-    for (int a = 0; a < AT; a++) { acc[a] = 0.f; bq[a] = P[off.bq + (a < A ? a : 0)]; }
-    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
-        float x4[4], w[4][AT];
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-#pragma unroll
-            for (int a = 0; a < AT; a++) w[e][a] = P[off.wq + (j0 + e) * A + (a < A ? a : 0)];
-        ac_units4(hf, stot, nks, FC, P, off.bf1, smp, j0, x4);
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-#pragma unroll
-            for (int a = 0; a < AT; a++) acc[a] = fmaf(x4[e], w[e][a], acc[a]);
-    }
-#pragma unroll
-    for (int a = 0; a < AT; a++)
-        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o);
-#pragma unroll
-    for (int a = 0; a < AT; a++) out[a] = a < A ? acc[a] + bq[a] : 0.f;
-}
-
 // Munchausen IQN (include/fbdqn.h), from the finished Qbar rows of the target net, qn = Qbar-(s', .) and qs = Qbar-(s, .), in fp32 over
 // ascending c: the soft policy at s', pi_c = e_c / S' with e_c = expf((qn_c - m') / temp), and t_c = (qn_c - m') - temp logf(S') (= temp ln pi_c,
 // never formed as a log of pi_c: finite when e_c underflows); the bonus alpha max((qs_a - m) - temp logf(S), l0) is mdqn_target's
@@ -268,15 +241,17 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossMuArgs L) {
     const bool done = L.term[b] != 0;
     [[maybe_unused]] float wb = 1.f;
     if constexpr (PW) wb = L.isw[b];
+    // Qbar of a row: the shared row head over the fold L.F, whose layout is the plain one (a dueling net: ITS offsets, L.foff).  Written as
+    // calls under `if constexpr`: behind a lambda the loss kernels' instructions were ordered differently
     if constexpr (MU) {
         // the two Qbar rows of the target net (every wave, every lane forms the same bits), then the soft policy at s' and the bonus at (s, a)
         float qn[AT], qs[AT];
         if constexpr (DU) {
-            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qn);
-            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.srow0 + b, lane, qs);
+            row_head<AT, false, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qn);
+            row_head<AT, false, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.srow0 + b, lane, qs);
         } else {
-            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qn);
-            iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.srow0 + b, lane, qs);
+            row_head<AT, false, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qn);
+            row_head<AT, false, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.srow0 + b, lane, qs);
         }
         float pi[AT], tl[AT], bonus;
         iqn_mu_policy<AT>(qn, qs, A, ab, L.temp, L.alpha, L.clip_lo, pi, tl, bonus);
@@ -295,8 +270,8 @@ __global__ __launch_bounds__(256) void iqn_loss_kernel(IqnLossMuArgs L) {
     } else {
         // a*: the first maximum of the plain head over the fold (every wave forms the same bits)
         float qa[AT];
-        if constexpr (DU) iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qa);
-        else iqn_plain_head<AT>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
+        if constexpr (DU) row_head<AT, false, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.F, L.foff, L.arow0 + b, lane, qa);
+        else row_head<AT, false, const NetOff &>(L.hf, L.stot, L.nks, FC, A, L.F, L.off, L.arow0 + b, lane, qa);
         int as = 0;
         float qbest = qa[0];
 #pragma unroll
@@ -380,6 +355,7 @@ __global__ __launch_bounds__(256) void iqn_grad_kernel(IqnGradArgs L) {
     for (int k = tid; k < B * 4; k += 256) dlt[k] = L.dl[k];
     for (int k = tid; k < B * 16; k += 256) xt[k] = L.gw[(size_t)(k >> 4) * FC + j00 + (k & 15)];
     const int jl = tid & 15, bg = tid >> 4;
+    // (the gradient tile's prologue: fb_ac.hip's ac_grad_kernel says why each gradient kernel carries these statements itself)
     float sm = 0.f, mx = 0.f;
     for (int b = bg; b < B; b += 16) { const float d = L.dhf[(size_t)b * FC + j00 + jl]; sm += d; mx = fmaxf(mx, fabsf(d)); }
     part[bg][jl] = sm;
@@ -441,7 +417,7 @@ __global__ __launch_bounds__(256) void iqn_grad_kernel(IqnGradArgs L) {
         for (int b = 0; b < B; b++) t += dlt[b * 4 + 2];
         L.loss[0] = t / (float)B;
         FbAdamHead &ad = *L.adam;
-        if (L.tick && ad.ticks == ad.applies) {                  // (as ac_grad_kernel)
+        if (L.tick && ad.ticks == ad.applies) {                  // (adam_tick's statements, fb_head.h: called, it costs the DU kernel 2 VGPRs, 64 for 62)
             ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
             ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
             ad.ticks += 1;

@@ -1285,13 +1285,8 @@ struct HeadArgs { Slices sl; int nslices; HeadCore c; };
 
 __global__ __launch_bounds__(256) void head_kernel(HeadArgs H) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int sidx = blockIdx.x * 4 + wave;
     const float *P = nullptr;
-    int smp = -1;
-    for (int z = 0; z < H.nslices; z++) {
-        if (sidx < H.sl.s[z].count) { P = H.sl.s[z].params; smp = H.sl.s[z].s_off + sidx; break; }
-        sidx -= H.sl.s[z].count;
-    }
+    const int smp = slice_row(H.sl, H.nslices, blockIdx.x * 4 + wave, P);
     if (smp < 0) return;
     head_one(H.c, P, smp, lane);
 }
@@ -1306,8 +1301,10 @@ __global__ __launch_bounds__(256) void head_kernel(HeadArgs H) {
 //                     compares the two ON THE DEVICE and re-splits when they differ.  wverc: the same for the W_conv2 / W_conv3 part
 //                     alone, which is all the small-batch conv2+conv3 kernel needs (conv23_t_kernel; a train-only loop re-splits 70 K
 //                     weights per step, not 890 K)
-struct AdamDev { float b1pow, b2pow, alpha, lr, b1, b2, eps, pad; int ticks, applies; unsigned pver[2], wver[2], wverc[2];
-                 unsigned ovf; };      // ovf: waves that split an activation beyond FB_F16_RANGE (note_overflow)
+// The Adam scalars and the tick bookkeeping are the base FbAdamHead (fb_common.h): what the side code objects see of this struct
+struct AdamDev : FbAdamHead { unsigned pver[2], wver[2], wverc[2];
+                              unsigned ovf; };      // ovf: waves that split an activation beyond FB_F16_RANGE (note_overflow)
+static_assert(sizeof(AdamDev) == sizeof(FbAdamHead) + 7 * sizeof(unsigned), "AdamDev is its base, then its own 7 words: no padding between them");
 
 // Munchausen-DQN (include/fbdqn.h): the net's (tau, alpha, l0).  MD instantiations of the two scalar loss bodies read the THIRD slice
 // (rows 2B ..: s through the target net) whatever L.algo says, and L.algo names the loss's form alone there: FB_ALGO_NATURE (FB_ALGO_MDQN)
@@ -1454,12 +1451,7 @@ __device__ __forceinline__ void loss_head_body(const LossArgs &L, float (*dadv)[
         float s = 0.f;
         for (int b = 0; b < B; b++) s += lterm[b];
         *L.loss = L.algo == FB_ALGO_DQN ? s : s / (float)B;
-        if (L.tick && L.adam->ticks == L.adam->applies) {        // Adam step counter for the update that follows (at most one
-            AdamDev &ad = *L.adam;                               // tick per update: a second gradient pass before the apply re-uses it)
-            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
-            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
-            ad.ticks += 1;
-        }
+        adam_tick(L.adam, L.tick);
     }
     if (lead && tid >= 64 && tid < 64 + A) { const int a = tid - 64; float s = 0.f; for (int b = 0; b < B; b++) s += dadv[b][a]; L.grad[L.off.bq + a] = s; }
     if (lead && tid == 128 && L.dueling) { float s = 0.f; for (int b = 0; b < B; b++) s += dv[b]; L.grad[L.off.bv] = s; }
@@ -1546,12 +1538,7 @@ __global__ __launch_bounds__(256) void loss_head_x_kernel(LossArgs L, MdPar M, f
 }
 
 // fb_qnet_apply_adam on gradients that no fb_qnet_train_step ticked for (guarded on the device, so it is safe to launch always)
-__global__ void adam_tick_kernel(AdamDev *ad) {
-    if (ad->ticks != ad->applies) return;
-    ad->alpha = ad->lr * sqrtf(1.f - ad->b2pow) / (1.f - ad->b1pow);
-    ad->b1pow *= ad->b1; ad->b2pow *= ad->b2;
-    ad->ticks += 1;
-}
+__global__ void adam_tick_kernel(AdamDev *ad) { adam_tick(ad, 1); }
 __global__ void bump_pver_kernel(AdamDev *ad, int which) { ad->pver[which] += 1; }
 __global__ void mark_split_kernel(AdamDev *ad, int which) { ad->wver[which] = ad->pver[which]; ad->wverc[which] = ad->pver[which]; }
 
@@ -1656,13 +1643,8 @@ struct C51HeadArgs { Slices sl; int nslices; const float *params; C51Core c; };
 template <int AT>
 __global__ __launch_bounds__(256) void c51_head_kernel(C51HeadArgs H) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int sidx = blockIdx.x * 4 + wave;
     const float *P = nullptr;
-    int smp = -1;
-    for (int z = 0; z < H.nslices; z++) {
-        if (sidx < H.sl.s[z].count) { P = H.sl.s[z].params; smp = H.sl.s[z].s_off + sidx; break; }
-        sidx -= H.sl.s[z].count;
-    }
+    const int smp = slice_row(H.sl, H.nslices, blockIdx.x * 4 + wave, P);
     if (smp < 0) return;
     c51_head_one<AT>(H.c, H.params ? H.params : P, smp, lane);
 }
@@ -1670,13 +1652,8 @@ __global__ __launch_bounds__(256) void c51_head_kernel(C51HeadArgs H) {
 template <int AT>
 __global__ __launch_bounds__(256) void qr_head_kernel(C51HeadArgs H) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int sidx = blockIdx.x * 4 + wave;
     const float *P = nullptr;
-    int smp = -1;
-    for (int z = 0; z < H.nslices; z++) {
-        if (sidx < H.sl.s[z].count) { P = H.sl.s[z].params; smp = H.sl.s[z].s_off + sidx; break; }
-        sidx -= H.sl.s[z].count;
-    }
+    const int smp = slice_row(H.sl, H.nslices, blockIdx.x * 4 + wave, P);
     if (smp < 0) return;
     c51_head_one<AT, true>(H.c, H.params ? H.params : P, smp, lane);
 }
@@ -1919,7 +1896,7 @@ __device__ __forceinline__ void c51_grad_body(const C51GradArgs &L) {
         float t = 0.f;
         for (int b = 0; b < B; b++) t += L.lterm[b];
         *L.loss = t / (float)B;
-        if (L.tick && L.adam->ticks == L.adam->applies) {        // (as loss_head_body)
+        if (L.tick && L.adam->ticks == L.adam->applies) {        // (adam_tick's statements: calling it here reorders this kernel)
             AdamDev &ad = *L.adam;
             ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
             ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
@@ -2481,12 +2458,7 @@ __device__ __forceinline__ void fc1_bwd2_body(const Bw1Args &L, float *smem, con
         float sum = 0.f;
         for (int b = 0; b < B; b++) sum += lterm[b];
         *L.loss = L.algo == FB_ALGO_DQN || L.algo == FB_ALGO_PG ? sum : sum / (float)B;       // (PG: the 1 / N is in every term)
-        if (L.tick && L.adam->ticks == L.adam->applies) {            // Adam step counter for the update that follows (see AdamDev)
-            AdamDev &ad = *L.adam;
-            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
-            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
-            ad.ticks += 1;
-        }
+        adam_tick(L.adam, L.tick);
     }
     if (lead && tid >= 64 && tid < 64 + A) { const int c = tid - 64; float sum = 0.f; for (int b = 0; b < B; b++) sum += dadv[b][c]; L.grad[L.off.bq + c] = sum; }
     if (lead && tid == 128 && L.dueling) { float sum = 0.f; for (int b = 0; b < B; b++) sum += dv[b]; L.grad[L.off.bv] = sum; }
@@ -4055,12 +4027,6 @@ struct fb_qnet {
     int iqn_mu;
     MdPar iqn_md;
 };
-// every field ac_grad_kernel touches through FbAdamHead sits where AdamDev has it
-static_assert(offsetof(AdamDev, b1pow) == offsetof(FbAdamHead, b1pow) && offsetof(AdamDev, b2pow) == offsetof(FbAdamHead, b2pow) &&
-              offsetof(AdamDev, alpha) == offsetof(FbAdamHead, alpha) && offsetof(AdamDev, lr) == offsetof(FbAdamHead, lr) &&
-              offsetof(AdamDev, b1) == offsetof(FbAdamHead, b1) && offsetof(AdamDev, b2) == offsetof(FbAdamHead, b2) &&
-              offsetof(AdamDev, ticks) == offsetof(FbAdamHead, ticks) && offsetof(AdamDev, applies) == offsetof(FbAdamHead, applies),
-              "fb_ac.hip's view of AdamDev");
 
 static NetOff make_off(int FC, int A, int dueling) {      // A: the head's columns (C51: actions x atoms)
     NetOff o;
@@ -4866,7 +4832,7 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
     auto transition = [&](auto &L) { L.rew = p.r; L.term = p.t; L.gamma = p.gamma; };      // ... and those of every loss that bootstraps
     // the losses of fb_ac.hip / fb_sac.hip / fb_iqn.hip: the net's own layout, the per-sample row in ac_dl
     auto side = [&](auto &L) { memset(&L, 0, sizeof(L)); shared(L); L.off = h->off; L.dl = h->ac_dl; };
-    FbAdamHead *const adam_head = reinterpret_cast<FbAdamHead *>(h->adam);
+    FbAdamHead *const adam_head = h->adam;
     if (c.iqn) {                                 // IQN: per-sample a* / T / theta / loss / d theta / dhf, then the per-unit reductions (fb_iqn.hip)
         IqnLossMuArgs L;                         // (IqnLossArgs, then Munchausen's fields: all zero = the hard target)
         side(L); transition(L);

@@ -16,35 +16,6 @@ namespace {
 
 constexpr int SAC_MAXB = 256;        // the train step's batch limit (fb_qnet.hip MAXTB)
 
-// ONE head of state smp on every lane of the wave (xor butterfly: the same bits everywhere): out[c] = h . W[:, c] + b[c], W at wo, b at bo.
-// Formed exactly as head_one_t forms the plain head's outputs -- a lane takes 4 consecutive units per round, fmaf in unit order, then the
-// butterfly, then the bias -- so over W_pi / b_pi these are the very bits fb_qnet_forward returns.  The three heads of a state are formed
-// one after another (one weight tile live at a time: no spill at AT = MAXA).  No load under a branch: columns a >= A read column 0.
-template <int AT>
-__device__ __forceinline__ void sac_head(const float *__restrict__ hf, int stot, int nks, int FC, int A, const float *__restrict__ P, int bf1, int wo, int bo,
-                                         int smp, int lane, float (&out)[AT]) {
-    float acc[AT], bq[AT];
-#pragma unroll
-    for (int a = 0; a < AT; a++) { acc[a] = 0.f; bq[a] = P[bo + (a < A ? a : 0)]; }
-    for (int j0 = 4 * lane; j0 < FC; j0 += 256) {
-        float x4[4], w[4][AT];
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-#pragma unroll
-            for (int a = 0; a < AT; a++) w[e][a] = P[wo + (j0 + e) * A + (a < A ? a : 0)];
-        ac_units4(hf, stot, nks, FC, P, bf1, smp, j0, x4);
-#pragma unroll
-        for (int e = 0; e < 4; e++)
-#pragma unroll
-            for (int a = 0; a < AT; a++) acc[a] = fmaf(x4[e], w[e][a], acc[a]);
-    }
-#pragma unroll
-    for (int a = 0; a < AT; a++)
-        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o);
-#pragma unroll
-    for (int a = 0; a < AT; a++) out[a] = a < A ? acc[a] + bq[a] : 0.f;
-}
-
 // the soft state value sum_c p_c (min(Q1_c, Q2_c) - alpha log p_c), ascending c, float32
 template <int AT>
 __device__ __forceinline__ float sac_soft_value(const float (&p)[AT], const float (&lp)[AT], const float (&q1)[AT], const float (&q2)[AT], int A, float alpha) {
@@ -61,13 +32,13 @@ __global__ __launch_bounds__(256) void sac_head_kernel(SacHeadArgs H) {
     const int A = AT == MAXA ? H.A : AT;
     const float alpha = expf(H.sw[0]);
     float z[AT], q1[AT], q2[AT];
-    sac_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off.bf1, H.off.wq, H.off.bq, smp, lane, z);
+    row_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, HeadOff{H.off.bf1, H.off.wq, H.off.bq}, smp, lane, z);
     const bool needq = H.value || H.q1 || H.q2;                  // (kernel-uniform)
 #pragma unroll
     for (int c = 0; c < AT; c++) { q1[c] = 0.f; q2[c] = 0.f; }
     if (needq) {
-        sac_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off.bf1, H.so.wq1, H.so.bq1, smp, lane, q1);
-        sac_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, H.off.bf1, H.so.wq2, H.so.bq2, smp, lane, q2);
+        row_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, HeadOff{H.off.bf1, H.so.wq1, H.so.bq1}, smp, lane, q1);
+        row_head<AT>(H.hf, H.stot, H.nks, H.FC, A, H.P, HeadOff{H.off.bf1, H.so.wq2, H.so.bq2}, smp, lane, q2);
     }
     if (lane != 0) return;
 #pragma unroll
@@ -120,17 +91,17 @@ __global__ __launch_bounds__(256) void sac_loss_kernel(SacLossArgs L) {
     const float alpha = expf(L.sw[0]);
     float z[AT], q1[AT], q2[AT], p[AT], lp[AT], m, s;
     // s' first: the policy from the online net (row B + b), both critics from the target net (row 2 B + b)
-    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.off.wq, L.off.bq, B + b, lane, z);
-    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off.bf1, L.so.wq1, L.so.bq1, 2 * B + b, lane, q1);
-    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P1, L.off.bf1, L.so.wq2, L.so.bq2, 2 * B + b, lane, q2);
+    row_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, HeadOff{L.off.bf1, L.off.wq, L.off.bq}, B + b, lane, z);
+    row_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P1, HeadOff{L.off.bf1, L.so.wq1, L.so.bq1}, 2 * B + b, lane, q1);
+    row_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P1, HeadOff{L.off.bf1, L.so.wq2, L.so.bq2}, 2 * B + b, lane, q2);
     ac_softmax<AT>(z, A, p, lp, m, s);
     const float Vn = sac_soft_value<AT>(p, lp, q1, q2, A, alpha);
     const double r = rf == 0.1f ? 0.1 : (double)rf;              // (the convention of every target here)
     const float y = (float)(tb ? r : r + L.gamma * (double)Vn);
     // s: all three heads of the online net
-    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.off.wq, L.off.bq, b, lane, z);
-    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.so.wq1, L.so.bq1, b, lane, q1);
-    sac_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, L.off.bf1, L.so.wq2, L.so.bq2, b, lane, q2);
+    row_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, HeadOff{L.off.bf1, L.off.wq, L.off.bq}, b, lane, z);
+    row_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, HeadOff{L.off.bf1, L.so.wq1, L.so.bq1}, b, lane, q1);
+    row_head<AT>(L.hf, L.stot, L.nks, FC, A, L.P0, HeadOff{L.off.bf1, L.so.wq2, L.so.bq2}, b, lane, q2);
     ac_softmax<AT>(z, A, p, lp, m, s);
     float q1a = q1[0], q2a = q2[0];
 #pragma unroll
@@ -191,6 +162,7 @@ __global__ __launch_bounds__(256) void sac_grad_kernel(SacGradArgs L) {
     const int tid = threadIdx.x, B = L.B, FC = L.FC, A = L.A, j00 = blockIdx.x * 16;
     for (int k = tid; k < B * 16; k += 256) { dlt[k] = L.dl[k]; xt[k] = L.xs[(size_t)(k >> 4) * FC + j00 + (k & 15)]; }
     const int jl = tid & 15, bg = tid >> 4;
+    // (the gradient tile's prologue: fb_ac.hip's ac_grad_kernel says why each gradient kernel carries these statements itself)
     float sm = 0.f, mx = 0.f;
     for (int b = bg; b < B; b += 16) { const float d = L.dhf[(size_t)b * FC + j00 + jl]; sm += d; mx = fmaxf(mx, fabsf(d)); }
     part[bg][jl] = sm;
@@ -247,12 +219,8 @@ __global__ __launch_bounds__(256) void sac_grad_kernel(SacGradArgs L) {
         L.loss[1] = lsum[0]; L.loss[2] = lsum[1]; L.loss[3] = lsum[2]; L.loss[4] = lsum[3];
         L.loss[0] = (lsum[0] + lsum[1]) + lsum[2];
         L.loss[5] = dlt[15];                                     // the alpha the loss kernel used
-        FbAdamHead &ad = *L.adam;
-        if (L.tick && ad.ticks == ad.applies) {                  // (as ac_grad_kernel)
-            ad.alpha = ad.lr * sqrtf(1.f - ad.b2pow) / (1.f - ad.b1pow);
-            ad.b1pow *= ad.b1; ad.b2pow *= ad.b2;
-            ad.ticks += 1;
-        }
+        adam_tick(L.adam, L.tick);
+        const FbAdamHead &ad = *L.adam;
         if (L.temp) {                                            // one element of the net's TF-style Adam on log alpha, its own beta powers
             float la = L.sw[0], mm = L.sw[1], vv = L.sw[2], p1 = L.sw[3], p2 = L.sw[4];
             const float g = lsum[3] - L.target_entropy;
