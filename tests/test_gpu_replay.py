@@ -7,6 +7,8 @@ import random
 import numpy as np
 import pytest
 
+from tests.samplecases import get_leaf           # SumTree.get_leaf on the host (BrainPrioritizedReplyDQN.py:85-100)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -281,17 +283,6 @@ def test_per_fast_mode_tree_is_the_exact_pairwise_sum(torch_cuda, N, cap):
     rep.reset(z8)
     mem = o.Memory(cap)
     rng = np.random.default_rng(N)
-
-    def get_leaf(tree, v):                        # BrainPrioritizedReplyDQN.py:85-100
-        i = 0
-        while 2 * i + 1 < len(tree):
-            l = 2 * i + 1
-            if v <= tree[l]:
-                i = l
-            else:
-                v -= tree[l]
-                i = l + 1
-        return i
 
     for step in range(2 * cap // N + 3):           # wraps the ring, crosses the leaf-depth split
         rep.push(z8, za, zr, za)
