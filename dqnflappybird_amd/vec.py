@@ -474,6 +474,53 @@ def check_polyak(rho, allow_off=False):
     return v
 
 
+def check_n_envs(n_envs):
+    """the env count of a vectorised loop (-> int >= 1)"""
+    n = int(n_envs)
+    if n < 1:
+        raise ValueError(f"n_envs must be >= 1, got {n_envs}")
+    return n
+
+
+def check_ring_batch(batch, n_envs):
+    """the minibatch of a loop that trains from the ring every step (-> int in 1..256, at most n_envs)"""
+    b = int(batch)
+    if not 1 <= b <= 256:
+        raise ValueError(f"batch must be in 1..256, got {batch}")
+    if b > n_envs:
+        raise ValueError(f"batch {b} > n_envs {n_envs}: every step draws a minibatch, the first from one push of n_envs transitions")
+    return b
+
+
+def check_observe(observe):
+    """the steps a loop only stores before it trains (-> int >= 0)"""
+    ob = int(observe)
+    if ob < 0:
+        raise ValueError(f"observe must be >= 0, got {observe}")
+    return ob
+
+
+def check_gamma(gamma):
+    """a loop's discount (-> float in [0, 1])"""
+    g = float(gamma)
+    if not (np.isfinite(g) and 0.0 <= g <= 1.0):
+        raise ValueError(f"gamma must be in [0, 1], got {gamma}")
+    return g
+
+
+def check_lr(lr):
+    """Adam's learning rate (-> finite float > 0)"""
+    l = float(lr)
+    if not (np.isfinite(l) and l > 0.0):
+        raise ValueError(f"lr must be finite and > 0, got {lr}")
+    return l
+
+
+def ring_capacity(capacity, n_envs):
+    """the capacity of a ring-fed loop's memory (-> int; None: max(65536, 8 n_envs))"""
+    return max(65536, 8 * n_envs) if capacity is None else int(capacity)
+
+
 def bootstrap_gamma(gamma, n):
     """Gamma = g_n of the n-step return (g_0 = 1, g_{k+1} = g_k * gamma in float64): the discount an n-step target bootstraps with,
     and what QNet.train_step takes on a minibatch gathered from an n-step memory.  gamma itself at n = 1."""

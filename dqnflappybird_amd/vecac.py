@@ -16,6 +16,8 @@ network as the critic) stays what --model actorcritic runs; this is the batched 
 """
 import numpy as np
 
+from .vecloop import DeviceLoop, clip_text, npz_path, refuse_foreign_head, score_text
+
 ALGOS = ("a2c", "ppo")                                       # what VecActorCritic(algo=...) takes
 AC_HEAD = "ac"                                               # what a checkpoint of this class records as its head
 CHUNK = 256                                                  # samples per ring-fed train chunk (the train step's limit)
@@ -32,10 +34,8 @@ def rollout_indices(size, rollout, n_envs):
 
 def check_args(n_envs, rollout, gamma, gae_lambda, value_coef, entropy_coef, max_grad_norm):
     """every argument check of VecActorCritic that needs no GPU -> the checked values"""
-    from .vec import check_ac, check_gae, check_max_grad_norm, check_rollout
-    n = int(n_envs)
-    if n < 1:
-        raise ValueError(f"n_envs must be >= 1, got {n_envs}")
+    from .vec import check_ac, check_gae, check_max_grad_norm, check_n_envs, check_rollout
+    n = check_n_envs(n_envs)
     T = check_rollout(rollout)
     g, l = check_gae(gamma, gae_lambda)
     cv, ce = check_ac(value_coef, entropy_coef)
@@ -53,7 +53,7 @@ def check_ppo_args(n_envs, rollout, epochs, minibatches, clip_eps, value_clip):
     return (k, m) + check_ppo(clip_eps, value_clip)
 
 
-class VecActorCritic:
+class VecActorCritic(DeviceLoop):
     def __init__(self, n_envs, rollout=5, gamma=0.99, gae_lambda=0.95, value_coef=0.5, entropy_coef=0.01, max_grad_norm=0.0, fc_width=512,
                  seed=0, lr=1e-4, capacity=None, algo="a2c", epochs=4, minibatches=4, clip_eps=0.2, value_clip=0.0, normalize_adv=True):
         """n_envs games, `rollout` steps per update (1..128), GAE(gamma, gae_lambda), loss = mean(L_pi + value_coef L_v - entropy_coef H)
@@ -78,29 +78,12 @@ class VecActorCritic:
         self.capacity = need if capacity is None else int(capacity)
         if self.capacity < need:
             raise ValueError(f"capacity {self.capacity} < (rollout + 2) x n_envs = {need}: the memory's ring is the rollout's state store")
-        self.lr = float(lr)
-        if not (np.isfinite(self.lr) and self.lr > 0.0):
-            raise ValueError(f"lr must be finite and > 0, got {lr}")
         import torch
-        from .vec import AcRolloutStep, QNet, VecGameState, VecReplay
+        from .vec import AcRolloutStep, check_lr
+        self.lr = check_lr(lr)
         self.seed = int(seed)
         self.fc_width = int(fc_width)
-        self.env = VecGameState(self.n, seed=self.seed)
-        self.replay = VecReplay(self.capacity, self.n)
-        self.replay.seed(self.seed)
-        self.net = QNet(2, self.fc_width, "ac", max_batch=max(self.n, CHUNK))
-        self.net.set_ac(self.value_coef, self.entropy_coef)
-        self.net.set_hparams(lr=self.lr)
-        if self.algo == "ppo":
-            self.net.set_ppo(self.clip_eps, self.value_clip)
-        if self.max_grad_norm:
-            self.net.set_max_grad_norm(self.max_grad_norm)
-        self.net.init_params(seed=self.seed, which=0)
-        self.net.init_params(seed=self.seed + 1, which=1)    # (the target net exists in every net; A2C never reads it)
-        self.nib = self.env.track_state()
-        self.env.observe()
-        self.replay.reset(self.env.frame_bits)
-        self.stats = self.env.track_stats()
+        self._build_world("ac", max(self.n, CHUNK), self._setup_net, target_seed=self.seed + 1)      # (the target net exists in every net; A2C never reads it)
         self.roll = AcRolloutStep(self.env, self.replay, self.net, self.T)
         self.grad = torch.zeros(self.net.n_params, dtype=torch.float32, device="cuda")
         self.chunk_grad = torch.zeros_like(self.grad)
@@ -110,6 +93,11 @@ class VecActorCritic:
         self.updates = 0
         self.pushes = 0                                      # pushes since the reset: len(replay) without a device sync
         self._idx_for = None
+
+    def _setup_net(self, net):
+        net.set_ac(self.value_coef, self.entropy_coef)
+        if self.algo == "ppo":
+            net.set_ppo(self.clip_eps, self.value_clip)
 
     def _indices(self):
         import torch
@@ -183,17 +171,7 @@ class VecActorCritic:
         self.updates += 1
         return self.losses
 
-    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0):
-        """Greedy play (the policy's argmax) of n_envs fresh games with the net as it stands (dqnflappybird_amd.evaluate): changes
-        nothing the training that follows reads"""
-        from .evaluate import evaluate
-        return evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed)
-
     # ------------------------------------------------------------------ checkpoint / resume
-    @staticmethod
-    def _npz(path):
-        return path if str(path).endswith(".npz") else str(path) + ".npz"
-
     def save(self, path):
         """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory,
         the counters and the A2C settings; `head` = 'ac' tells the file from a VecBrain's, and a PPO run adds its settings as `ppo`
@@ -201,23 +179,15 @@ class VecActorCritic:
         extra = {}
         if self.algo == "ppo":
             extra["ppo"] = np.array([self.epochs, self.minibatches, self.clip_eps, self.value_clip, float(self.normalize_adv)], np.float64)
-        host = lambda t: t.cpu().numpy()
-        m, v, pows = self.net.adam_state()
-        np.savez(self._npz(path), head=np.array([AC_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
-                 adam_m=host(m), adam_v=host(v), beta_pows=np.asarray(pows, np.float32),
-                 scalars=np.array([self.timeStep, self.updates, self.pushes, self.seed, self.n, self.T, self.fc_width], np.int64),
-                 ac=np.array([self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm, self.lr], np.float64),
-                 env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob(), **extra)
+        self._save(path, AC_HEAD, scalars=np.array([self.timeStep, self.updates, self.pushes, self.seed, self.n, self.T, self.fc_width], np.int64),
+                   ac=np.array([self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm, self.lr], np.float64), **extra)
 
     def load(self, path):
         """the inverse of save(), into a VecActorCritic made with the same n_envs, rollout, fc_width, capacity and seed (the envs' pipe-gap
         streams are keyed by the seed they were created with); the A2C settings of the file replace this object's"""
         import torch
-        from .vecbrain import checkpoint_head
-        z = np.load(self._npz(path))
-        head = checkpoint_head(z)
-        if head != AC_HEAD:
-            raise ValueError(f"checkpoint {path} holds a {head} head (a VecBrain's), this is a VecActorCritic (head {AC_HEAD!r})")
+        z = np.load(npz_path(path))
+        refuse_foreign_head(z, path, lambda head: head != AC_HEAD and f"a {head} head (a VecBrain's), this is a VecActorCritic (head {AC_HEAD!r})")
         kind = "ppo" if "ppo" in z.files else "a2c"
         if kind != self.algo:
             raise ValueError(f"checkpoint {path} holds {'a PPO' if kind == 'ppo' else 'an A2C'} run, this VecActorCritic runs "
@@ -229,10 +199,7 @@ class VecActorCritic:
         if sc[3] != self.seed:
             raise ValueError(f"checkpoint {path} was written with seed {sc[3]}, this VecActorCritic has seed {self.seed} (the envs' pipe-gap "
                              "streams are keyed by it)")
-        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-        self.net.load_params(z["online"], 0)
-        self.net.load_params(z["target"], 1)
-        self.net.set_adam_state(dev(z["adam_m"]), dev(z["adam_v"]), z["beta_pows"])
+        self._restore(z)
         self.gamma, self.gae_lambda, self.value_coef, self.entropy_coef, self.max_grad_norm, self.lr = (float(x) for x in z["ac"])
         self.net.set_ac(self.value_coef, self.entropy_coef)
         self.net.set_hparams(lr=self.lr)
@@ -242,10 +209,6 @@ class VecActorCritic:
             self.epochs, self.minibatches, self.clip_eps, self.value_clip = check_ppo_args(self.n, self.T, int(k), int(m), eps, vclip)
             self.normalize_adv = bool(norm)
             self.net.set_ppo(self.clip_eps, self.value_clip)
-        self.env.set_state(z["env_state"])
-        self.nib.copy_(dev(z["nib"]))
-        self.stats[...] = dev(z["stats"])
-        self.replay.load_state_blob(z["replay"])
         self.timeStep, self.updates, self.pushes = sc[0], sc[1], sc[2]
         self._idx_for = None
         torch.cuda.synchronize()
@@ -255,14 +218,8 @@ class VecActorCritic:
             losses = self.update()
             if log_every and (i + 1) % log_every == 0:
                 tot, lpi, lv, ent, *more = losses.tolist()       # the only host sync of the loop, once per log line
-                ep, ssum, smax, pipes = self.stats.tolist()
-                self.net.check_range()
-                clip = ""
-                if self.max_grad_norm:
-                    norm, scale = self.net.grad_norm()
-                    clip = f" / GRAD_NORM {norm:.6g} / CLIP_SCALE {scale:.6g}"
+                score, clip = score_text(self.net, self.stats), clip_text(self.net, self.max_grad_norm)
                 if more:                                         # PPO
                     clip += f" / CLIP_FRAC {more[0]:.6g} / APPROX_KL {more[1]:.6g}"
                 print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / POLICY_LOSS {lpi:.6g} / VALUE_LOSS {lv:.6g} / ENTROPY {ent:.6g} / "
-                      f"GAME_TIMES {ep} / MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {tot:.6g}{clip}",
-                      flush=True)
+                      f"{score} / LOSS {tot:.6g}{clip}", flush=True)

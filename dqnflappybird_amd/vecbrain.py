@@ -20,6 +20,7 @@ max_grad_norm=G > 0 clips the flat gradient's global norm to G before Adam (ever
 polyak=rho > 0 replaces the periodic target copy by target += rho (online - target) after every train step.
 """
 from . import dist as fdist
+from .vecloop import LOCAL_ARRAYS, checkpoint_head, clip_text, core_arrays, npz_path, refuse_foreign_head, restore_core, score_text, to_device
 
 MEAN_LOSS = {"dqn": False, "nature": True, "double": True, "per": True, "c51": True, "c51double": True, "c51per": True, "c51doubleper": True,
              "qr": True, "qrdouble": True, "qrper": True, "qrdoubleper": True, "mdqn": True, "mdqnper": True, "doubleper": True}
@@ -94,9 +95,7 @@ class HipVecBackend:
         return torch.zeros(n, dtype=torch.float32, device="cuda")
 
     def to_device(self, x):
-        import numpy as np
-        import torch
-        return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        return to_device(x)
 
     def synchronize(self):
         import torch
@@ -117,19 +116,18 @@ class HipVecBackend:
         return lambda: fdist.allreduce_gradients(flat_grad, mean_loss)
 
 
+# the heads of the other loops' checkpoints -> what load() answers to one ("checkpoint <path> holds ...")
+OTHER_LOOPS = {"ac": "an ac head (a VecActorCritic's), this is a VecBrain: load it with dqnflappybird_amd.vecac.VecActorCritic",
+               "sac": "a sac head (a VecSAC's), this is a VecBrain: load it with dqnflappybird_amd.vecsac.VecSAC",
+               "iqn": "an iqn head (a VecIQN's), this is a VecBrain: load it with dqnflappybird_amd.veciqn.VecIQN"}
+
+
 def check_checkpoint_head(z, head, path):
     """a C51 checkpoint's head kind must be this brain's ('c51' or 'c51dueling'; checkpoints that record none hold a C51 head)"""
     saved = str(z["head"][0]) if "head" in z.files else "c51"
     if saved != head:
         raise ValueError(f"checkpoint {path} holds a {saved} head, this VecBrain has a {head} head (C51 and dueling C51 parameters "
                          "do not convert)")
-
-
-def checkpoint_head(z):
-    """the head a checkpoint holds: its recorded `head`, else 'c51' where it records a support, else 'scalar'"""
-    if "head" in z.files:
-        return str(z["head"][0])
-    return "c51" if "support" in z.files else "scalar"
 
 
 def check_checkpoint_quantiles(z, quantiles, head, path):
@@ -203,6 +201,105 @@ def check_checkpoint_support(z, support, path):
         raise ValueError(f"checkpoint {path} was trained on the support {saved} (n_atoms, v_min, v_max), this VecBrain has {tuple(support)}")
 
 
+def backend_name(be):
+    return getattr(be, 'name', type(be).__name__)
+
+
+def require(be, flag, text):
+    """the capability test: a backend that does not offer `flag` refuses: 'the <name> backend <text>'"""
+    if not getattr(be, flag, False):
+        raise ValueError(f"the {backend_name(be)} backend {text}")
+
+
+def resolve_args(be, algo, arch, world, n_step, noisy, acting_noise, initial_epsilon, n_atoms, v_min, v_max, n_quantiles, kappa, tau, alpha, clip,
+                 huber, max_grad_norm, polyak):
+    """every refusal of VecBrain(...) that needs none of the backend's factories, in the order they fire (arguments, then what the backend
+    `be` offers, per head family) -> (arch, support, quantiles, munchausen, huber, max_grad_norm, polyak, initial_epsilon) as the brain
+    holds them: the head's own arch; None for what the algo does not have (huber: None on the distributional heads, which neither set
+    nor record it).  sigma0 is checked where the noisy net is made."""
+    from .vec import check_huber, check_max_grad_norm, check_munchausen, check_polyak, check_quantiles, check_support
+    if acting_noise not in ("shared", "env"):
+        raise ValueError(f"acting_noise must be 'shared' or 'env', got {acting_noise!r}")
+    if acting_noise == "env" and not noisy:
+        raise ValueError("acting_noise='env' needs a noisy net (noisy=True)")
+    if initial_epsilon is None:
+        initial_epsilon = 0.0 if noisy else 0.03
+    if not 1 <= n_step <= 16:
+        raise ValueError(f"n_step must be in 1..16, got {n_step}")
+    if acting_noise == "env":
+        require(be, "acting_noise_env", "has no per-env acting noise (acting_noise_env): acting_noise='env' needs it")
+    support = quantiles = munchausen = None
+    delta = check_huber(huber)
+    if algo not in SCALAR_ALGOS:
+        if delta > 0.0:
+            raise ValueError(f"huber = {huber}: the Huber loss is offered on the scalar heads only ({', '.join(SCALAR_ALGOS)}), not with "
+                             f"algo {algo!r} (QR has its own kappa)")
+        delta = None
+    elif delta > 0.0:
+        require(be, "huber", f"has no Huber loss (huber): huber = {huber} needs it")
+    limit = check_max_grad_norm(max_grad_norm)
+    rho = check_polyak(polyak, allow_off=True)
+    if limit > 0.0:
+        require(be, "grad_clip", f"has no gradient clipping (grad_clip): max_grad_norm = {max_grad_norm} needs it")
+    if rho > 0.0:
+        require(be, "polyak", f"has no soft target updates (polyak): polyak = {polyak} needs it")
+    one_step = f"has no one-call prioritized step (per_one_step): algo {algo!r} needs it"
+    if algo == "doubleper":
+        if arch not in ("plain", "dueling"):
+            raise ValueError(f"algo {algo!r} trains the scalar heads: arch must be 'plain' or 'dueling', not {arch!r}")
+        if noisy:
+            raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with algo {algo!r}")
+        require(be, "double_per", f"has no Double-DQN with prioritized replay (double_per): algo {algo!r} needs it")
+        require(be, "per_one_step", one_step)
+    if algo in MDQN_ALGOS:
+        munchausen = check_munchausen(tau, alpha, clip)
+        if arch not in ("plain", "dueling"):
+            raise ValueError(f"algo {algo!r} (Munchausen-DQN) trains the scalar heads: arch must be 'plain' or 'dueling', not {arch!r}")
+        if noisy:
+            raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with the Munchausen-DQN algo {algo!r}")
+        require(be, "mdqn", f"has no Munchausen-DQN (mdqn): algo {algo!r} needs it")
+        if algo == "mdqnper":
+            require(be, "per_one_step", one_step)
+    elif algo in QR_ALGOS + QR_PER_ALGOS:
+        if arch not in ("plain",) + QR_HEADS:
+            raise ValueError(f"algo {algo!r} builds a QR head on the plain trunk: arch {arch!r} is not one (dueling QR is arch='qrdueling')")
+        if world > 1:
+            raise ValueError(f"algo {algo!r}: data-parallel QR is not supported (world = {world}; one GPU only)")
+        if noisy:
+            raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with the QR algo {algo!r}")
+        require(be, "qr", "has no QR nets")
+        if algo in QR_PER_ALGOS:
+            require(be, "per_one_step", one_step)
+        quantiles = check_quantiles(n_quantiles, kappa)
+        arch = "qrdueling" if arch == "qrdueling" else "qr"
+    elif arch in QR_HEADS:
+        raise ValueError(f"arch {arch!r} is a QR head: it trains with a QR algo ('qr', 'qrdouble', 'qrper', 'qrdoubleper'), not {algo!r}")
+    elif algo in C51_ALGOS + C51_PER_ALGOS:
+        if arch not in ("plain",) + C51_HEADS:
+            raise ValueError(f"algo {algo!r} builds a C51 head on the plain trunk: arch {arch!r} is not one "
+                             f"(dueling C51 is arch='c51dueling')")
+        if world > 1:
+            raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (world = {world}; one GPU only)")
+        require(be, "c51", "has no C51 nets")
+        if arch == "c51dueling":
+            require(be, "c51_dueling", "has no dueling C51 nets")
+        if algo in C51_PER_ALGOS:
+            require(be, "per_one_step", one_step)
+        if noisy:
+            require(be, "c51_noisy", "has no noisy C51 nets")
+        support = check_support(n_atoms, v_min, v_max)
+        arch = "c51dueling" if arch == "c51dueling" else "c51"
+    elif noisy:
+        raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, which train with a C51 algo ('c51', 'c51double', "
+                         f"'c51per', 'c51doubleper'), not {algo!r}")
+    elif arch == "c51dueling":
+        raise ValueError(f"arch {arch!r} is a C51 head: it trains with a C51 algo ('c51', 'c51double', 'c51per', 'c51doubleper'), "
+                         f"not {algo!r}")
+    if n_step > 1 and algo in PER_ALGOS:
+        require(be, "per_n_step", f"offers n-step returns on uniform replay only: algo {algo!r} takes n_step = 1 there")
+    return arch, support, quantiles, munchausen, delta, limit, rho, initial_epsilon
+
+
 class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
@@ -232,121 +329,21 @@ class VecBrain:
         polyak=rho in (0, 1] (every algo): after every train step target += rho (online - target) (net.soft_sync_target), and the hard
         copy every replace_target_iter steps is dropped.  This gives the 'per' family -- 'per', whose target net the reference agent never
         syncs, included -- a moving target.  Both are optimiser settings: checkpoints record them, load() does not refuse another value."""
-        n_step = int(n_step)
-        noisy = bool(noisy)
-        if acting_noise not in ("shared", "env"):
-            raise ValueError(f"acting_noise must be 'shared' or 'env', got {acting_noise!r}")
-        if acting_noise == "env" and not noisy:
-            raise ValueError("acting_noise='env' needs a noisy net (noisy=True)")
-        if initial_epsilon is None:
-            initial_epsilon = 0.0 if noisy else 0.03
-        if not 1 <= n_step <= 16:
-            raise ValueError(f"n_step must be in 1..16, got {n_step}")
-        be = backend or HipVecBackend()
-        if acting_noise == "env" and not getattr(be, "acting_noise_env", False):
-            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no per-env acting noise (acting_noise_env): "
-                             f"acting_noise='env' needs it")
-        self.support = None
-        self.quantiles = None
-        self.munchausen = None
-        from .vec import check_huber
-        self.huber = check_huber(huber)                      # (refused before anything touches the GPU)
-        if algo not in SCALAR_ALGOS:
-            if self.huber > 0.0:
-                raise ValueError(f"huber = {huber}: the Huber loss is offered on the scalar heads only ({', '.join(SCALAR_ALGOS)}), not with "
-                                 f"algo {algo!r} (QR has its own kappa)")
-            self.huber = None                                # (a distributional brain neither sets nor records it)
-        elif self.huber > 0.0 and not getattr(be, "huber", False):
-            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no Huber loss (huber): huber = {huber} needs it")
-        from .vec import check_max_grad_norm, check_polyak
-        self.max_grad_norm = check_max_grad_norm(max_grad_norm)      # (both refused before anything touches the GPU)
-        self.polyak = check_polyak(polyak, allow_off=True)
-        if self.max_grad_norm > 0.0 and not getattr(be, "grad_clip", False):
-            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no gradient clipping (grad_clip): "
-                             f"max_grad_norm = {max_grad_norm} needs it")
-        if self.polyak > 0.0 and not getattr(be, "polyak", False):
-            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no soft target updates (polyak): polyak = {polyak} needs it")
-        if algo == "doubleper":
-            if arch not in ("plain", "dueling"):
-                raise ValueError(f"algo {algo!r} trains the scalar heads: arch must be 'plain' or 'dueling', not {arch!r}")
-            if noisy:
-                raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with algo {algo!r}")
-            if not getattr(be, "double_per", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no Double-DQN with prioritized replay (double_per): "
-                                 f"algo {algo!r} needs it")
-            if not getattr(be, "per_one_step", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
-                                 f"algo {algo!r} needs it")
-        if algo in MDQN_ALGOS:
-            from .vec import check_munchausen
-            self.munchausen = check_munchausen(tau, alpha, clip)
-            if arch not in ("plain", "dueling"):
-                raise ValueError(f"algo {algo!r} (Munchausen-DQN) trains the scalar heads: arch must be 'plain' or 'dueling', not {arch!r}")
-            if noisy:
-                raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with the Munchausen-DQN algo {algo!r}")
-            if not getattr(be, "mdqn", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no Munchausen-DQN (mdqn): algo {algo!r} needs it")
-            if algo == "mdqnper" and not getattr(be, "per_one_step", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
-                                 f"algo {algo!r} needs it")
-        elif algo in QR_ALGOS + QR_PER_ALGOS:
-            from .vec import check_quantiles
-            if arch not in ("plain",) + QR_HEADS:
-                raise ValueError(f"algo {algo!r} builds a QR head on the plain trunk: arch {arch!r} is not one (dueling QR is arch='qrdueling')")
-            if world > 1:
-                raise ValueError(f"algo {algo!r}: data-parallel QR is not supported (world = {world}; one GPU only)")
-            if noisy:
-                raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, not with the QR algo {algo!r}")
-            if not getattr(be, "qr", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no QR nets")
-            if algo in QR_PER_ALGOS and not getattr(be, "per_one_step", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
-                                 f"algo {algo!r} needs it")
-            self.quantiles = check_quantiles(n_quantiles, kappa)
-            arch = "qrdueling" if arch == "qrdueling" else "qr"
-        elif arch in QR_HEADS:
-            raise ValueError(f"arch {arch!r} is a QR head: it trains with a QR algo ('qr', 'qrdouble', 'qrper', 'qrdoubleper'), not {algo!r}")
-        elif algo in C51_ALGOS + C51_PER_ALGOS:
-            from .vec import check_support
-            if arch not in ("plain",) + C51_HEADS:
-                raise ValueError(f"algo {algo!r} builds a C51 head on the plain trunk: arch {arch!r} is not one "
-                                 f"(dueling C51 is arch='c51dueling')")
-            if world > 1:
-                raise ValueError(f"algo {algo!r}: data-parallel C51 is not supported (world = {world}; one GPU only)")
-            if not getattr(be, "c51", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no C51 nets")
-            if arch == "c51dueling" and not getattr(be, "c51_dueling", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no dueling C51 nets")
-            if algo in C51_PER_ALGOS and not getattr(be, "per_one_step", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no one-call prioritized step (per_one_step): "
-                                 f"algo {algo!r} needs it")
-            if noisy and not getattr(be, "c51_noisy", False):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend has no noisy C51 nets")
-            self.support = check_support(n_atoms, v_min, v_max)
-            arch = "c51dueling" if arch == "c51dueling" else "c51"
-        elif noisy:
-            raise ValueError(f"noisy=True: noisy layers are offered on the C51 heads only, which train with a C51 algo ('c51', 'c51double', "
-                             f"'c51per', 'c51doubleper'), not {algo!r}")
-        elif arch == "c51dueling":
-            raise ValueError(f"arch {arch!r} is a C51 head: it trains with a C51 algo ('c51', 'c51double', 'c51per', 'c51doubleper'), "
-                             f"not {algo!r}")
-        if n_step > 1 and algo in PER_ALGOS and not getattr(be, "per_n_step", False):
-            raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend offers n-step returns on uniform replay only: "
-                             f"algo {algo!r} takes n_step = 1 there")
+        n_step, noisy, be = int(n_step), bool(noisy), backend or HipVecBackend()
+        (arch, self.support, self.quantiles, self.munchausen, self.huber, self.max_grad_norm, self.polyak, initial_epsilon) = resolve_args(
+            be, algo, arch, world, n_step, noisy, acting_noise, initial_epsilon, n_atoms, v_min, v_max, n_quantiles, kappa, tau, alpha, clip, huber,
+            max_grad_norm, polyak)                           # (every refusal but the two below comes before anything touches the GPU)
+        from .vec import bootstrap_gamma
         self.be = be
         self.n, self.algo, self.batch, self.gamma = n_envs, algo, batch, gamma
         self.n_step = n_step
-        self.boot_gamma = float(gamma)                       # Gamma = gamma^n as the running product (vec.bootstrap_gamma)
-        if n_step > 1:
-            g = 1.0
-            for _ in range(n_step):
-                g *= float(gamma)
-            self.boot_gamma = g
+        self.boot_gamma = bootstrap_gamma(gamma, n_step)     # Gamma = gamma^n as the running product
         self.rank, self.world = rank, world
         self.observe, self.explore = observe, explore
         self.epsilon, self.initial_epsilon, self.final_epsilon = initial_epsilon, initial_epsilon, final_epsilon
         self.replace_target_iter = replace_target_iter
         self.seed = seed
+        # the world: envs, memory, nets
         self.env = be.env(n_envs, seed + 1000003 * rank)     # envs shard by rank: every rank plays its own games
         if n_step > 1 and algo in PER_ALGOS:                 # ... into its own replay shard (a prioritized one gets n at creation)
             self.replay = be.replay(capacity, n_envs, True, n_step=n_step, gamma=gamma)
@@ -355,7 +352,7 @@ class VecBrain:
         self.replay.seed(seed + rank, sampler)
         if n_step > 1 and algo not in PER_ALGOS:             # (only then: a backend without n-step memories keeps working at n = 1)
             if not hasattr(self.replay, "set_n_step"):
-                raise ValueError(f"the {getattr(be, 'name', type(be).__name__)} backend's replay has no n-step view (n_step = {n_step})")
+                raise ValueError(f"the {backend_name(be)} backend's replay has no n-step view (n_step = {n_step})")
             self.replay.set_n_step(n_step, gamma)
         self.arch = arch
         self.noisy = noisy
@@ -398,7 +395,7 @@ class VecBrain:
         self.stats = self.env.track_stats()                  # [episodes, score sum, score max, pipes passed], kept by the env kernel
         self.last_loss = None
         self.dtype = "f32"
-        # the whole step is one host call (fb_vec_step): uniform replay with the head, random.sample and the Memory append riding in the
+        # the step: the whole of it is one host call (fb_vec_step): uniform replay with the head, random.sample and the Memory append riding in the
         # env launch; prioritized replay with store -> Memory.sample -> weighted train -> batch_update as launches of the same call
         self.native = None
         if self.grad is not None and algo not in PER_ALGOS and hasattr(be, "native"):
@@ -494,10 +491,6 @@ class VecBrain:
         self.dtype = dtype
 
     # ------------------------------------------------------------------ checkpoint / resume of the WHOLE loop
-    @staticmethod
-    def _npz(path):
-        return path if str(path).endswith(".npz") else str(path) + ".npz"
-
     def _local_path(self, path):
         """where this rank's LOCAL state goes: `<path>.rank<r>.npz` (envs, frame stacks, replay shard and stats differ per rank)"""
         base = str(path)[:-4] if str(path).endswith(".npz") else str(path)
@@ -513,15 +506,10 @@ class VecBrain:
         writing `path` -- round 3 -- overwrote each other's rank-local state.)  A barrier closes the call: when it returns on any rank,
         every file of the checkpoint is complete."""
         import numpy as np
-        host = lambda t: t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-        local = dict(env_state=self.env.get_state(), stats=host(self.stats), replay=self.replay.state_blob())
-        if self.nib is not None:
-            local["nib"] = host(self.nib)
-        shared = None
+        shared = core_arrays(self.net if self.rank == 0 else None, self.env, self.nib, self.stats, self.replay)
+        local = {k: shared.pop(k) for k in LOCAL_ARRAYS if k in shared}
         if self.rank == 0:
-            m, v, pows = self.net.adam_state()
-            shared = dict(online=host(self.net.store_params(0)), target=host(self.net.store_params(1)), adam_m=host(m), adam_v=host(v),
-                          beta_pows=np.asarray(pows, np.float32), scalars=np.array([self.timeStep, self.onlineTimeStep, self.world, self.seed], np.int64),
+            shared.update(scalars=np.array([self.timeStep, self.onlineTimeStep, self.world, self.seed], np.int64),
                           epsilon=np.array([self.epsilon], np.float64), n_step=np.array([self.n_step], np.int64))
             if self.support is not None:                     # (scalar-head checkpoints carry no support)
                 shared["support"] = np.array(self.support, np.float64)
@@ -541,27 +529,19 @@ class VecBrain:
                 shared["noisy"] = np.array([1], np.int64)
                 shared["sigma0"] = np.array([self.sigma0], np.float64)
         if self.world == 1:
-            np.savez(self._npz(path), **shared, **local)
+            np.savez(npz_path(path), **shared, **local)
             return
         np.savez(self._local_path(path), **local)
         if self.rank == 0:
-            np.savez(self._npz(path), **shared)
+            np.savez(npz_path(path), **shared)
         fdist.barrier()
 
     def load(self, path):
         """the inverse of save(); at world > 1 every rank reads the replicated part from `path` and its own `<path>.rank<r>.npz`
         (the world size must be the one the checkpoint was written with: the shards are rank-local)."""
         import numpy as np
-        z = np.load(self._npz(path))
-        if checkpoint_head(z) == "ac":                       # (an actor-critic net has the dueling net's parameter count: the head tells)
-            raise ValueError(f"checkpoint {path} holds an ac head (a VecActorCritic's), this is a VecBrain: load it with "
-                             "dqnflappybird_amd.vecac.VecActorCritic")
-        if checkpoint_head(z) == "sac":
-            raise ValueError(f"checkpoint {path} holds a sac head (a VecSAC's), this is a VecBrain: load it with "
-                             "dqnflappybird_amd.vecsac.VecSAC")
-        if checkpoint_head(z) == "iqn":
-            raise ValueError(f"checkpoint {path} holds an iqn head (a VecIQN's), this is a VecBrain: load it with "
-                             "dqnflappybird_amd.veciqn.VecIQN")
+        z = np.load(npz_path(path))
+        refuse_foreign_head(z, path, OTHER_LOOPS.get)        # (an actor-critic net has the dueling net's parameter count: the head tells)
         saved_world = int(z["scalars"][2]) if len(z["scalars"]) > 2 else 1
         if saved_world != self.world:
             raise ValueError(f"checkpoint {path} was written by {saved_world} rank(s), this job has {self.world}")
@@ -579,14 +559,7 @@ class VecBrain:
         self.checkpoint_optimiser = checkpoint_optimiser(z)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
-        self.net.load_params(z["online"], 0)
-        self.net.load_params(z["target"], 1)
-        self.net.set_adam_state(dev(z["adam_m"]), dev(z["adam_v"]), z["beta_pows"])
-        self.env.set_state(zl["env_state"])
-        if self.nib is not None:
-            self.nib.copy_(dev(zl["nib"]))
-        self.stats[...] = dev(zl["stats"])
-        self.replay.load_state_blob(zl["replay"])
+        restore_core(z, self.net, self.env, self.nib, self.stats, self.replay, dev, local=zl)
         self.timeStep, self.onlineTimeStep = int(z["scalars"][0]), int(z["scalars"][1])
         if len(z["scalars"]) > 3:
             self.seed = int(z["scalars"][3])                     # the key of the acting (epsilon-greedy) stream: (seed + rank, timeStep)
@@ -599,14 +572,8 @@ class VecBrain:
             self.step()
             if log_every and (i + 1) % log_every == 0:
                 loss = self.last_loss.item() if self.last_loss is not None else float("nan")
-                ep, ssum, smax, pipes = self.stats.tolist()      # the only host sync of the loop, once per log line
-                if hasattr(self.net, "check_range"):
-                    self.net.check_range()                       # (the same sync: an activation beyond the two-plane fp16 range raises here)
+                score = score_text(self.net, self.stats)
                 if hasattr(self.net, "split_stats"):
-                    self.net.split_stats()                       # (... and so does a wait between the two streams of fb_vec_step's split schedule that gave up)
-                clip = ""
-                if self.max_grad_norm:                           # (the last train step's; a synchronous read, at the log cadence only)
-                    norm, scale = self.net.grad_norm()
-                    clip = f" / GRAD_NORM {norm:.6g} / CLIP_SCALE {scale:.6g}"
-                print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / EPSILON {self.epsilon:.6f} / GAME_TIMES {ep} / "
-                      f"MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {loss:.6g}{clip}", flush=True)
+                    self.net.split_stats()                       # (at the same sync: a wait between the two streams of fb_vec_step's split schedule that gave up raises)
+                clip = clip_text(self.net, self.max_grad_norm)
+                print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / EPSILON {self.epsilon:.6f} / {score} / LOSS {loss:.6g}{clip}", flush=True)

@@ -22,6 +22,8 @@ the memory kinds, the dueling net, n-step returns and CVaR acting included, is u
 """
 import numpy as np
 
+from .vecloop import DeviceLoop, clip_text, npz_path, refuse_foreign_head, score_text
+
 IQN_HEAD = "iqn"                                             # what a checkpoint of this class records as its head
 
 
@@ -29,22 +31,17 @@ def check_args(n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step,
                final_epsilon, gamma, lr, max_grad_norm, capacity):
     """every argument check of VecIQN that needs no GPU -> the checked values"""
     from . import _lib as L
-    from .vec import check_iqn, check_max_grad_norm, check_polyak
-    n, b, ob, ex, ns, rti = int(n_envs), int(batch), int(observe), int(explore), int(n_step), int(replace_target_iter)
-    if n < 1:
-        raise ValueError(f"n_envs must be >= 1, got {n_envs}")
-    if not 1 <= b <= 256:
-        raise ValueError(f"batch must be in 1..256, got {batch}")
-    if b > n:
-        raise ValueError(f"batch {b} > n_envs {n}: every step draws a minibatch, the first from one push of n_envs transitions")
+    from .vec import check_gamma, check_iqn, check_lr, check_max_grad_norm, check_n_envs, check_observe, check_polyak, check_ring_batch, ring_capacity
+    ex, ns, rti = int(explore), int(n_step), int(replace_target_iter)
+    n = check_n_envs(n_envs)
+    b = check_ring_batch(batch, n)
     N, Np, K, ka, eta = check_iqn(n_tau, n_tau_next, n_tau_act, kappa, cvar, 2)
     if not 1 <= ns <= L.NSTEP_MAX:
         raise ValueError(f"n_step must be in 1..{L.NSTEP_MAX}, got {n_step}")
     rho = check_polyak(polyak, allow_off=True)
     if rti < 1:
         raise ValueError(f"replace_target_iter must be >= 1, got {replace_target_iter}")
-    if ob < 0:
-        raise ValueError(f"observe must be >= 0, got {observe}")
+    ob = check_observe(observe)
     if ob < ns - 1:
         raise ValueError(f"observe must be >= n_step - 1 = {ns - 1}: the first n_step - 1 steps only store (no n-step transition is complete yet), got {observe}")
     if ex < 1:
@@ -52,12 +49,8 @@ def check_args(n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step,
     e0, e1 = float(initial_epsilon), float(final_epsilon)
     if not (0.0 <= e1 <= e0 <= 1.0):
         raise ValueError(f"the epsilon schedule needs 0 <= final_epsilon <= initial_epsilon <= 1, got {initial_epsilon} -> {final_epsilon}")
-    g, l = float(gamma), float(lr)
-    if not (np.isfinite(g) and 0.0 <= g <= 1.0):
-        raise ValueError(f"gamma must be in [0, 1], got {gamma}")
-    if not (np.isfinite(l) and l > 0.0):
-        raise ValueError(f"lr must be finite and > 0, got {lr}")
-    cap = max(65536, 8 * n) if capacity is None else int(capacity)
+    g, l = check_gamma(gamma), check_lr(lr)
+    cap = ring_capacity(capacity, n)
     if cap < max(2, ns) * n:
         raise ValueError(f"capacity {cap} < max(2, n_step) x n_envs = {max(2, ns) * n}")
     return n, b, N, Np, K, ka, eta, ns, rho, rti, ob, ex, e0, e1, g, l, check_max_grad_norm(max_grad_norm), cap
@@ -105,7 +98,7 @@ def replay_kind(prioritized):
     return "prioritized" if prioritized else "uniform"
 
 
-class VecIQN:
+class VecIQN(DeviceLoop):
     def __init__(self, n_envs, batch=32, double_q=False, n_step=1, n_tau=8, n_tau_next=8, n_tau_act=32, kappa=1.0, cvar=1.0, polyak=0.0,
                  replace_target_iter=500, observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99, lr=1e-6,
                  max_grad_norm=0, fc_width=512, seed=0, capacity=None, prioritized=False, dueling=False,
@@ -125,37 +118,20 @@ class VecIQN:
         self.prioritized = check_prioritized(prioritized)
         self.dueling = check_dueling(dueling)
         self.munchausen, self.temp, self.alpha, self.clip = check_munchausen(munchausen, temp, alpha, clip, bool(double_q))
-        from .vec import QNet, VecGameState, VecReplay
         self.double_q = bool(double_q)
         self.seed = int(seed)
         self.fc_width = int(fc_width)
         self.epsilon = self.initial_epsilon
-        self.env = VecGameState(self.n, seed=self.seed)
-        if self.prioritized:                                 # (a prioritized memory gets its n at creation; its generator is numpy's)
-            self.replay = VecReplay(self.capacity, self.n, prioritized=True, n_step=self.n_step, gamma=self.gamma)
-            self.replay.seed(self.seed)
-        else:
-            self.replay = VecReplay(self.capacity, self.n)
-            self.replay.seed(self.seed)
-            if self.n_step > 1:
-                self.replay.set_n_step(self.n_step, self.gamma)
-        self.net = QNet(2, self.fc_width, "iqndueling" if self.dueling else "iqn", max_batch=max(self.n, self.batch), n_tau=self.n_tau, n_tau_next=self.n_tau_next,
-                        n_tau_act=self.n_tau_act, kappa=self.kappa)
-        self.net.set_hparams(lr=self.lr)
-        if self.cvar != 1.0:
-            self.net.set_iqn_risk(self.cvar)
-        if self.max_grad_norm:
-            self.net.set_max_grad_norm(self.max_grad_norm)
-        if self.munchausen:                                  # (off: the net is never touched)
-            self.net.set_iqn_munchausen(True, self.temp, self.alpha, self.clip)
-        self.net.init_params(seed=self.seed, which=0)
-        self.net.sync_target()
-        self.nib = self.env.track_state()
-        self.env.observe()
-        self.replay.reset(self.env.frame_bits)
-        self.stats = self.env.track_stats()
+        self._build_world("iqndueling" if self.dueling else "iqn", max(self.n, self.batch), self._setup_net, prioritized=self.prioritized,
+                          n_step=self.n_step, n_tau=self.n_tau, n_tau_next=self.n_tau_next, n_tau_act=self.n_tau_act, kappa=self.kappa)
         self._bind()
         self.timeStep = 0                                    # env steps per env so far: the key of the epsilon and tau draws
+
+    def _setup_net(self, net):
+        if self.cvar != 1.0:
+            net.set_iqn_risk(self.cvar)
+        if self.munchausen:                                  # (off: the net is never touched)
+            net.set_iqn_munchausen(True, self.temp, self.alpha, self.clip)
 
     def _bind(self):
         from .vec import IqnPerStep, IqnStep
@@ -181,45 +157,28 @@ class VecIQN:
         self.timeStep += 1
         return self.loss
 
-    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0):
-        """Greedy play (on the folded head, under the net's risk setting) of n_envs fresh games with the net as it stands
-        (dqnflappybird_amd.evaluate): changes nothing the training that follows reads"""
-        from .evaluate import evaluate
-        return evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed)
-
     # ------------------------------------------------------------------ checkpoint / resume
-    @staticmethod
-    def _npz(path):
-        return path if str(path).endswith(".npz") else str(path) + ".npz"
-
     def save(self, path):
         """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory
         (with its generator and, prioritized, its tree), the counters, epsilon and the settings; `head` = 'iqn' tells the file from the
         other loops', `prioritized` the memory's kind (a file without the key is a uniform one's), `dueling` the net's (without the key: a plain IQN net's),
         `munchausen` = (on, temp, alpha, clip) the target's (without the key: the hard target)"""
-        host = lambda t: t.cpu().numpy()
-        m, v, pows = self.net.adam_state()
-        np.savez(self._npz(path), head=np.array([IQN_HEAD]), online=host(self.net.store_params(0)), target=host(self.net.store_params(1)),
-                 adam_m=host(m), adam_v=host(v), beta_pows=np.asarray(pows, np.float32),
-                 scalars=np.array([self.timeStep, self.seed, self.n, self.batch, self.fc_width, self.observe, self.explore, self.n_step,
-                                   int(self.double_q), self.replace_target_iter], np.int64),
-                 iqn=np.array([self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar], np.float64),
-                 prioritized=np.array([int(self.prioritized)], np.int64), dueling=np.array([int(self.dueling)], np.int64),
-                 munchausen=np.array([float(self.munchausen), self.temp, self.alpha, self.clip], np.float64),
-                 settings=np.array([self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon],
-                                   np.float64),
-                 env_state=self.env.get_state(), nib=host(self.nib), stats=host(self.stats), replay=self.replay.state_blob())
+        self._save(path, IQN_HEAD,
+                   scalars=np.array([self.timeStep, self.seed, self.n, self.batch, self.fc_width, self.observe, self.explore, self.n_step,
+                                     int(self.double_q), self.replace_target_iter], np.int64),
+                   iqn=np.array([self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar], np.float64),
+                   prioritized=np.array([int(self.prioritized)], np.int64), dueling=np.array([int(self.dueling)], np.int64),
+                   munchausen=np.array([float(self.munchausen), self.temp, self.alpha, self.clip], np.float64),
+                   settings=np.array([self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon],
+                                     np.float64))
 
     def load(self, path):
         """the inverse of save(), into a VecIQN made with the same n_envs, batch, fc_width, n_step, (n_tau, n_tau_next, n_tau_act, kappa),
         capacity, seed, memory kind (prioritized or not), head kind (dueling or not) and target (munchausen or not, and its temp, alpha,
         clip); the other settings of the file replace this object's"""
         import torch
-        from .vecbrain import checkpoint_head
-        z = np.load(self._npz(path))
-        head = checkpoint_head(z)
-        if head != IQN_HEAD:
-            raise ValueError(f"checkpoint {path} holds a {head} head (another loop's), this is a VecIQN (head {IQN_HEAD!r})")
+        z = np.load(npz_path(path))
+        refuse_foreign_head(z, path, lambda head: head != IQN_HEAD and f"a {head} head (another loop's), this is a VecIQN (head {IQN_HEAD!r})")
         per = bool(int(z["prioritized"][0])) if "prioritized" in z.files else False
         if per != self.prioritized:
             raise ValueError(f"checkpoint {path} was written by a VecIQN with a {replay_kind(per)} memory, this VecIQN has a "
@@ -247,20 +206,13 @@ class VecIQN:
         if self.munchausen and tuple(mu[1:]) != (self.temp, self.alpha, self.clip):
             raise ValueError(f"checkpoint {path} was trained with munchausen (temp, alpha, clip) = {tuple(mu[1:])}, this VecIQN has "
                              f"{(self.temp, self.alpha, self.clip)}")
-        dev = lambda x: torch.from_numpy(np.ascontiguousarray(x)).cuda()
-        self.net.load_params(z["online"], 0)
-        self.net.load_params(z["target"], 1)
-        self.net.set_adam_state(dev(z["adam_m"]), dev(z["adam_v"]), z["beta_pows"])
+        self._restore(z)
         self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon = (float(x) for x in z["settings"])
         self.cvar = q[4]
         self.net.set_hparams(lr=self.lr)
         self.net.set_max_grad_norm(self.max_grad_norm)
         self.net.set_iqn_risk(self.cvar)
         self.observe, self.explore, self.double_q, self.replace_target_iter = sc[5], sc[6], bool(sc[8]), sc[9]
-        self.env.set_state(z["env_state"])
-        self.nib.copy_(dev(z["nib"]))
-        self.stats[...] = dev(z["stats"])
-        self.replay.load_state_blob(z["replay"])
         self.timeStep = sc[0]
         self._bind()
         torch.cuda.synchronize()
@@ -269,11 +221,5 @@ class VecIQN:
         for i in range(steps):
             loss = self.step()
             if log_every and (i + 1) % log_every == 0:
-                ep, ssum, smax, pipes = self.stats.tolist()      # the only host sync of the loop, once per log line
-                self.net.check_range()
-                clip = ""
-                if self.max_grad_norm:
-                    norm, scale = self.net.grad_norm()
-                    clip = f" / GRAD_NORM {norm:.6g} / CLIP_SCALE {scale:.6g}"
-                print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / EPSILON {self.epsilon:.6f} / GAME_TIMES {ep} / "
-                      f"MEAN_SCORE {ssum / max(ep, 1):.3f} / MAX_SCORE {smax} / PIPES {pipes} / LOSS {loss.item():.6g}{clip}", flush=True)
+                score, clip = score_text(self.net, self.stats), clip_text(self.net, self.max_grad_norm)
+                print(f"TIMESTEP {self.timeStep} / ENVS {self.n} / EPSILON {self.epsilon:.6f} / {score} / LOSS {loss.item():.6g}{clip}", flush=True)
