@@ -141,6 +141,10 @@ def build_parser():
     parser.add_argument("--clip-eps", type=float, default=None, help="--model ppo: the probability ratio is clipped to [1 - E, 1 + E] (default 0.2)")
     parser.add_argument("--value-clip", type=float, default=None, help="--model ppo: clip the value around the rollout's by C (default 0 = off)")
     parser.add_argument("--no-adv-norm", action="store_true", help="--model ppo: do not normalise the rollout's advantages")
+    parser.add_argument("--adv-norm-scope", default=None, help="--model ppo: normalise the advantages over the rollout (the default) or over every minibatch")
+    parser.add_argument("--target-kl", type=float, default=None, help="--model ppo: stop an update's epochs once an epoch's mean approximate KL exceeds "
+                                                                       "1.5 X (default 0 = off)")
+    parser.add_argument("--anneal-lr", action="store_true", help="--model ppo: the learning rate falls linearly to 0 over the run's --steps updates")
     parser.add_argument("--target-entropy", type=float, default=None, help="--model sac: the entropy the learned temperature aims at (default 0.98 ln 2)")
     parser.add_argument("--alpha-lr", type=float, default=None, help="--model sac: the temperature's learning rate (default 0 = --alpha stays fixed)")
     return parser
@@ -224,7 +228,9 @@ def a2c_kwargs(args, parser):
     given = [n for n, v in (("--rollout", args.rollout), ("--gae-lambda", args.gae_lambda), ("--value-coef", args.value_coef),
                             ("--entropy-coef", args.entropy_coef)) if v is not None]
     ppo_given = [n for n, v in (("--epochs", args.epochs), ("--minibatches", args.minibatches), ("--clip-eps", args.clip_eps),
-                                ("--value-clip", args.value_clip), ("--no-adv-norm", args.no_adv_norm or None)) if v is not None]
+                                ("--value-clip", args.value_clip), ("--no-adv-norm", args.no_adv_norm or None),
+                                ("--adv-norm-scope", args.adv_norm_scope), ("--target-kl", args.target_kl), ("--anneal-lr", args.anneal_lr or None))
+                 if v is not None]
     if ppo_given and args.model != "ppo":
         parser.error(f"{' / '.join(ppo_given)} need --model ppo, not --model {args.model}")
     if args.model not in ("a2c", "ppo"):
@@ -238,8 +244,8 @@ def a2c_kwargs(args, parser):
                      ("--n-quantiles / --kappa", args.n_quantiles is not None or args.kappa is not None)):
         if on:
             parser.error(f"{name} is not an option of --model {args.model} (--rollout, --gae-lambda, --value-coef, --entropy-coef, --max-grad-norm"
-                         f"{', --epochs, --minibatches, --clip-eps, --value-clip, --no-adv-norm' if args.model == 'ppo' else ''} are)")
-    from .vecac import check_args, check_ppo_args
+                         f"{', --epochs, --minibatches, --clip-eps, --value-clip, --no-adv-norm, --adv-norm-scope, --target-kl, --anneal-lr' if args.model == 'ppo' else ''} are)")
+    from .vecac import check_args, check_ppo_args, check_ppo_options
     kw = dict(rollout=5 if args.rollout is None else args.rollout, gae_lambda=0.95 if args.gae_lambda is None else args.gae_lambda,
               value_coef=0.5 if args.value_coef is None else args.value_coef, entropy_coef=0.01 if args.entropy_coef is None else args.entropy_coef,
               max_grad_norm=0.0 if args.max_grad_norm is None else args.max_grad_norm)
@@ -250,6 +256,14 @@ def a2c_kwargs(args, parser):
                       clip_eps=0.2 if args.clip_eps is None else args.clip_eps, value_clip=0.0 if args.value_clip is None else args.value_clip,
                       normalize_adv=not args.no_adv_norm)
             check_ppo_args(args.vec, kw["rollout"], kw["epochs"], kw["minibatches"], kw["clip_eps"], kw["value_clip"])
+            if args.adv_norm_scope is not None:              # (without the three flags VecActorCritic's keywords are the ones of before)
+                kw["adv_norm_scope"] = args.adv_norm_scope
+            if args.target_kl is not None:
+                kw["target_kl"] = args.target_kl
+            if args.anneal_lr:                               # (--steps is the run's length in updates: the schedule's end)
+                kw.update(anneal_lr=True, total_updates=args.steps or 1000)
+            check_ppo_options(kw.get("adv_norm_scope", "rollout"), kw.get("target_kl"), kw.get("anneal_lr", False), kw.get("total_updates"), None,
+                              kw["normalize_adv"])
     except ValueError as e:
         parser.error(str(e))
     return kw

@@ -121,6 +121,10 @@ SIGNATURES = {
     "fb_ppo_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "fb_ac_normalize_adv": [_vp, _i64, _vp, _vp],
     "fb_ac_permute": [_i64, _u64, _u64, _vp, _vp],
+    "fb_ac_normalize_adv_sel": [_vp, _vp, _i64, _vp, _vp],
+    "fb_ac_grad_accumulate": [_vp, _vp, _i64, _i, _vp],
+    "fb_ppo_epoch": [_vp, _vp, _i64, _i] + [_vp] * 6 + [_i] + [_vp] * 7,
+    "fb_ppo_epoch_sum": [_vp, _vp, _vp],
     "fb_qnet_create_sac": [_i, _i, _i, _vp],
     "fb_qnet_set_sac": [_vp, _f, _f, _f],
     "fb_qnet_get_sac": [_vp, _vp, _vp, _vp],

@@ -9,6 +9,11 @@
 //   ppo_loss_kernel     ac_loss_kernel's place in the train step: the clipped-surrogate policy term, the (clipped) value term, two more loss terms
 //   ac_adv_norm_kernel  the rollout's advantages to mean 0, standard deviation 1; ONE workgroup, float64, a pinned order
 //   ac_permute_kernel   a stateless keyed permutation of [0, n): a Feistel network over Philox, cycle-walked; one thread per element
+// and one PPO epoch as one host call (fb_ppo_epoch, fb_ppo_epoch_sum, fb_ac_normalize_adv_sel, fb_ac_grad_accumulate):
+//   ac_adv_norm_sel_kernel  ac_adv_norm_kernel over the elements a selection names (one minibatch); ONE workgroup, the same pinned order
+//   ac_grad_accum_kernel    acc = (first ? 0 : acc) + chunk over the flat gradient, float4 where aligned; workgroup 0 may add the chunk's six
+//                           loss numbers to the minibatch's row, and to the epoch's running sum, in the same launch
+//   ppo_epoch_mean_kernel   the epoch's six numbers: the minibatches' rows added in ascending order, divided by their count
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
 #include "fb_common.h"
 #include <math.h>
@@ -224,6 +229,79 @@ __global__ __launch_bounds__(256) void ac_adv_norm_kernel(const float *adv, long
     for (long long i = t; i < n; i += 256) out[i] = (float)(((double)adv[i] - mean) / den);
 }
 
+// ---- ac_adv_norm_kernel over a selection: element j of the sums is adv[sel[j]], and out is written at sel[j] only.  out is not adv (the
+// host refuses it): a minibatch normalised in place would be normalised again in the next epoch.  sel holds distinct positions inside
+// adv / out by the caller's contract (a slice of a permutation), as ppo_loss_kernel's sel.
+__global__ __launch_bounds__(256) void ac_adv_norm_sel_kernel(const float *__restrict__ adv, const long long *__restrict__ sel, long long n,
+                                                              float *__restrict__ out) {
+    __shared__ double part[256];
+    __shared__ double stat[2];
+    const int t = threadIdx.x;
+    double acc = 0.0;
+    for (long long j = t; j < n; j += 256) acc += (double)adv[sel[j]];
+    part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double S = 0.0;
+        for (int q = 0; q < 256; q++) S += part[q];
+        stat[0] = S / (double)n;
+    }
+    __syncthreads();
+    const double mean = stat[0];
+    acc = 0.0;
+    for (long long j = t; j < n; j += 256) { const double d = (double)adv[sel[j]] - mean; acc += d * d; }
+    part[t] = acc;
+    __syncthreads();
+    if (t == 0) {
+        double S = 0.0;
+        for (int q = 0; q < 256; q++) S += part[q];
+        stat[1] = sqrt(S / (double)n);
+    }
+    __syncthreads();
+    const double den = stat[1] + 1e-8;
+    for (long long j = t; j < n; j += 256) { const long long k = sel[j]; out[k] = (float)(((double)adv[k] - mean) / den); }
+}
+
+// ---- the sum of an update's chunk gradients: acc[i] = (first ? 0 : acc[i]) + chunk[i], one fp32 add per element (0.f + x on a first
+// chunk: a -0 becomes +0, as zero_() and += give it).  V4: both pointers 16-byte aligned -- thread i takes float4 i of the n / 4 whole
+// ones, the next n % 4 threads one tail element each; otherwise one element per thread.  row != NULL: workgroup 0 adds the chunk's six
+// loss numbers to the minibatch's row under the same rule (fb_ppo_epoch), so that a chunk costs one launch here, not two; and to run, the
+// epoch's running sum over ALL its chunks (first_run: the epoch's first chunk), which is what a loop that adds every chunk's numbers to
+// one accumulator holds -- the rows' sum is another order of the same additions.
+template <bool V4>
+__global__ __launch_bounds__(256) void ac_grad_accum_kernel(float *__restrict__ acc, const float *__restrict__ chunk, long long n, int first,
+                                                            float *__restrict__ row, float *__restrict__ run, int first_run,
+                                                            const float *__restrict__ six) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (V4) {
+        const long long n4 = n >> 2, k = 4 * n4 + (i - n4);
+        if (i < n4) {
+            const float4 c = reinterpret_cast<const float4 *>(chunk)[i];
+            float4 a = reinterpret_cast<const float4 *>(acc)[i];
+            if (first) a = make_float4(0.f, 0.f, 0.f, 0.f);
+            reinterpret_cast<float4 *>(acc)[i] = make_float4(a.x + c.x, a.y + c.y, a.z + c.z, a.w + c.w);
+        } else if (k < n) {
+            acc[k] = (first ? 0.f : acc[k]) + chunk[k];
+        }
+    } else if (i < n) {
+        acc[i] = (first ? 0.f : acc[i]) + chunk[i];
+    }
+    if (row && blockIdx.x == 0 && threadIdx.x < 6) {
+        const float x = six[threadIdx.x];
+        row[threadIdx.x] = (first ? 0.f : row[threadIdx.x]) + x;
+        run[threadIdx.x] = (first_run ? 0.f : run[threadIdx.x]) + x;
+    }
+}
+
+// ---- the epoch's six numbers: thread c adds rows[m][c] in ascending m from 0.f and divides by the count
+__global__ __launch_bounds__(64) void ppo_epoch_mean_kernel(const float *__restrict__ rows, int minibatches, float *__restrict__ mean) {
+    const int c = threadIdx.x;
+    if (c >= 6) return;
+    float s = 0.f;
+    for (int m = 0; m < minibatches; m++) s += rows[m * 6 + c];
+    mean[c] = s / (float)minibatches;
+}
+
 // ---- a keyed permutation of [0, n) without state: element i -> the cycle-walked image of i under a 4-round Feistel network on k = 2 half
 // bits, (L, R) <- (R, L ^ (F_r(R) & mask)), F_r(R) = word r of Philox4x32-10(key = seed, counter = (R, draw_lo, FB_STREAM_PERM, draw_hi)).
 // The network is a bijection of [0, 2^k), so walking it until the value is below n is a bijection of [0, n) (the walk of an i < n comes
@@ -374,6 +452,94 @@ extern "C" int fb_ac_normalize_adv(const float *adv, int64_t n, float *out, void
     FB_REQUIRE(n >= 1 && n < (1LL << 31), "fb_ac_normalize_adv: n = %lld out of range", (long long)n);
     hipLaunchKernelGGL(ac_adv_norm_kernel, dim3(1), dim3(256), 0, fb_stream(stream), adv, (long long)n, out);
     FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+extern "C" int fb_ac_normalize_adv_sel(const float *adv, const int64_t *sel, int64_t n, float *out, void *stream) {
+    FB_REQUIRE(adv && sel && out, "fb_ac_normalize_adv_sel: NULL argument");
+    FB_REQUIRE(out != adv, "fb_ac_normalize_adv_sel: out must not be adv (a minibatch normalised in place would be normalised again in the next epoch)");
+    FB_REQUIRE(n >= 1 && n < (1LL << 31), "fb_ac_normalize_adv_sel: n = %lld out of range", (long long)n);
+    hipLaunchKernelGGL(ac_adv_norm_sel_kernel, dim3(1), dim3(256), 0, fb_stream(stream), adv, reinterpret_cast<const long long *>(sel), (long long)n, out);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+// acc = (first ? 0 : acc) + chunk, and with row the same rule over the six loss numbers (fb_ppo_epoch's chunk)
+static void launch_grad_accum(hipStream_t st, float *acc, const float *chunk, long long n, int first, float *row, float *run, int first_run,
+                              const float *six) {
+    if ((((uintptr_t)acc | (uintptr_t)chunk) & 15) == 0) {
+        const long long threads = (n >> 2) + (n & 3);
+        hipLaunchKernelGGL(ac_grad_accum_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, acc, chunk, n, first, row, run, first_run, six);
+    } else {
+        hipLaunchKernelGGL(ac_grad_accum_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, acc, chunk, n, first, row, run, first_run, six);
+    }
+}
+
+extern "C" int fb_ac_grad_accumulate(float *acc, const float *chunk, int64_t n, int first, void *stream) {
+    FB_REQUIRE(acc && chunk, "fb_ac_grad_accumulate: NULL argument");
+    FB_REQUIRE(acc != chunk, "fb_ac_grad_accumulate: acc must not be chunk");
+    FB_REQUIRE(n >= 1 && n < (1LL << 31), "fb_ac_grad_accumulate: n = %lld out of range", (long long)n);
+    launch_grad_accum(fb_stream(stream), acc, chunk, (long long)n, first != 0, nullptr, nullptr, 0, nullptr);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+// One PPO epoch as the calls VecActorCritic composes, in their order, on `stream` (include/fbdqn.h).  Everything any of them refuses is
+// refused here first, so that nothing is launched and no host-side state of the net moves before a refusal.  The chunk's six numbers
+// land in epoch_mean, which the last launch then overwrites with the epoch's.
+extern "C" int fb_ppo_epoch(fb_replay_t replay, fb_qnet_t net, int64_t n, int minibatches, const int64_t *pos, const int64_t *sel, const float *adv,
+                            const float *ret, const float *logp_old, const float *value_old, int mb_adv_norm, float *adv_scratch, float *grad,
+                            float *chunk_grad, uint8_t *a_out, float *loss_rows, float *epoch_mean, void *stream) {
+    const char *who = "fb_ppo_epoch";
+    FB_REQUIRE(replay && net && pos && sel && adv && ret && logp_old && value_old && grad && chunk_grad && a_out && loss_rows && epoch_mean,
+               "fb_ppo_epoch: NULL argument");
+    FB_REQUIRE(n >= 1 && n < (1LL << 31), "fb_ppo_epoch: n = %lld out of range", (long long)n);
+    FB_REQUIRE(minibatches >= 1 && n % minibatches == 0, "fb_ppo_epoch: minibatches must be >= 1 and divide n = %lld (got %d)", (long long)n, minibatches);
+    FB_REQUIRE(!mb_adv_norm || adv_scratch, "fb_ppo_epoch: mb_adv_norm needs adv_scratch (f32 of the rollout buffers' size)");
+    FB_REQUIRE(!mb_adv_norm || adv_scratch != adv, "fb_ppo_epoch: adv_scratch must not be adv (a minibatch normalised in place would be normalised "
+               "again in the next epoch)");
+    FB_REQUIRE(grad != chunk_grad, "fb_ppo_epoch: grad must not be chunk_grad");
+    FB_REQUIRE(fb_qnet_is_ac(net), "%s: not an actor-critic net (fb_qnet_create_ac)", who);
+    int rc = fb_check_uniform_n1(replay, who, "the rollout is read from a uniform memory only", "the rollout is read");
+    if (rc != FB_OK) return rc;
+    const int64_t mb = n / minibatches;
+    rc = fb_qnet_ac_check_train(net, (int)(mb < AC_MAXB ? mb : AC_MAXB), mb, who);
+    if (rc != FB_OK) return rc;
+    const bool clip = fb_qnet_max_grad_norm(net) > 0.f;
+    FB_REQUIRE(!clip || ((uintptr_t)grad & 15) == 0, "fb_ppo_epoch: grad must be 16-byte aligned (the net clips it)");
+    int64_t np = 0;
+    rc = fb_qnet_num_params(net, &np);
+    if (rc != FB_OK) return rc;
+    hipStream_t st = fb_stream(stream);
+    for (int m = 0; m < minibatches; m++) {
+        const int64_t lo = (int64_t)m * mb;
+        if (mb_adv_norm) {
+            rc = fb_ac_normalize_adv_sel(adv, sel + lo, mb, adv_scratch, stream);
+            if (rc != FB_OK) return rc;
+        }
+        for (int64_t k = lo; k < lo + mb; k += AC_MAXB) {
+            const int b = (int)(lo + mb - k < AC_MAXB ? lo + mb - k : AC_MAXB);
+            rc = fb_ppo_train_from_replay(replay, net, b, pos + k, sel + k, mb_adv_norm ? adv_scratch : adv, ret, logp_old, value_old, mb, a_out,
+                                          epoch_mean, chunk_grad, stream);
+            if (rc != FB_OK) return rc;
+            launch_grad_accum(st, grad, chunk_grad, (long long)np, k == lo, loss_rows + (size_t)m * 6, fb_qnet_ppo_sum(net), k == 0, epoch_mean);
+        }
+        if (clip) {
+            rc = fb_qnet_clip_grad(net, grad, stream);
+            if (rc != FB_OK) return rc;
+        }
+        rc = fb_qnet_apply_adam(net, grad, stream);
+        if (rc != FB_OK) return rc;
+    }
+    hipLaunchKernelGGL(ppo_epoch_mean_kernel, dim3(1), dim3(64), 0, st, loss_rows, minibatches, epoch_mean);
+    FB_LAUNCH_CHECK();
+    return FB_OK;
+}
+
+extern "C" int fb_ppo_epoch_sum(fb_qnet_t net, float *sum, void *stream) {
+    FB_REQUIRE(net && sum, "fb_ppo_epoch_sum: NULL argument");
+    FB_REQUIRE(fb_qnet_is_ac(net), "fb_ppo_epoch_sum: not an actor-critic net (fb_qnet_create_ac)");
+    FB_CHECK_HIP(hipMemcpyAsync(sum, fb_qnet_ppo_sum(net), 6 * sizeof(float), hipMemcpyDeviceToDevice, fb_stream(stream)));
     return FB_OK;
 }
 

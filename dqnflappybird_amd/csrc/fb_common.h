@@ -268,6 +268,7 @@ int fb_qnet_is_ac(fb_qnet_t h);               // 1: an actor-critic net (fb_qnet
 // a_out; the ring-fed AC train step behind fb_ac_train_from_replay's checks
 int fb_qnet_ac_check_train(fb_qnet_t h, int batch, int64_t n_total, const char *who);
 void fb_qnet_ac_scratch(fb_qnet_t h, float **r, uint8_t **t);
+float *fb_qnet_ppo_sum(fb_qnet_t h);          // [dev] f32[6] of an actor-critic net: fb_ppo_epoch's running sum of the chunks' loss numbers
 int fb_qnet_ac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const float *adv, const float *ret, int64_t n_total, float *loss,
                           float *flat_grad, void *stream);
 // the ring-fed PPO train step behind fb_ppo_train_from_replay's checks (sel NULL: the four buffers are read at b)

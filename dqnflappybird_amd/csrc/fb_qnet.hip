@@ -4026,6 +4026,9 @@ struct fb_qnet {
     // Munchausen IQN (fb_qnet_set_iqn_munchausen): on / off and (temp, alpha, l0); read by the IQN train plans alone
     int iqn_mu;
     MdPar iqn_md;
+    // an actor-critic net: [dev] f32[6], the running sum of the last fb_ppo_epoch's chunk loss numbers (fb_ppo_epoch_sum).  Last, so that
+    // every field above keeps the place it had
+    float *ppo_sum;
 };
 
 static NetOff make_off(int FC, int A, int dueling) {      // A: the head's columns (C51: actions x atoms)
@@ -4312,6 +4315,7 @@ static int qnet_create(const NetSpec &s, fb_qnet_t *out) {
     if (is_ac(h)) {
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
         alloc(&h->ac_dl, Bt * 16 * 4); alloc(&h->ac_xs, Bt * fc_width * 4); alloc(&h->ac_r, Bt * 4); alloc(&h->ac_t, Bt);
+        alloc(&h->ppo_sum, 6 * 4);
     }
     if (is_sac(h)) {
         const size_t Bt = Bm < MAXTB ? Bm : MAXTB;
@@ -5628,6 +5632,7 @@ int fb_qnet_ac_check_train(fb_qnet_t h, int B, int64_t n_total, const char *who)
 }
 
 void fb_qnet_ac_scratch(fb_qnet_t h, float **r, uint8_t **t) { *r = h->ac_r; *t = h->ac_t; }
+float *fb_qnet_ppo_sum(fb_qnet_t h) { return h->ppo_sum; }
 
 // the train plan of an actor-critic net: ONE slice, s through the online net
 static Plan ac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *adv, const float *ret, int64_t n_total, float *loss,

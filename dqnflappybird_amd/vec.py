@@ -1382,6 +1382,89 @@ def ac_permute(n, seed=0, draw=0, out=None, device="cuda"):
     return out
 
 
+def _check_sel(sel, n, check_sel):
+    """sel int64, inside buffers of n elements (check_sel: read back from the device, ONE HOST SYNC, as ppo_train_from_replay's)"""
+    if sel.dtype != torch.int64 or sel.numel() < 1:
+        raise ValueError("sel must be a non-empty int64 tensor")
+    if check_sel and not bool(((sel >= 0) & (sel < n)).all()):
+        raise ValueError(f"sel must lie in 0..{n - 1}, the rollout buffers' positions")
+
+
+def ac_normalize_adv_sel(adv, sel, out, check_sel=True):
+    """the advantages adv[sel] (one minibatch) to mean 0 and standard deviation 1 over themselves, written to out[sel]
+    (fb_ac_normalize_adv_sel: float64, the order include/fbdqn.h pins); the other positions of out are not written, and out is not adv.
+    sel int64[n]: distinct positions (a permutation's slice); check_sel=False skips the range check's host sync -> out"""
+    _dev_check(adv, sel, out)
+    if adv.dtype != torch.float32 or adv.numel() < 1:
+        raise ValueError("adv must be a contiguous, non-empty float32 tensor")
+    if out.dtype != torch.float32 or out.numel() != adv.numel():
+        raise ValueError(f"out must be a contiguous float32[{adv.numel()}]")
+    _check_sel(sel, adv.numel(), check_sel)
+    L.check(L.lib().fb_ac_normalize_adv_sel(L.ptr(adv), L.ptr(sel), int(sel.numel()), L.ptr(out), L.current_stream()), "fb_ac_normalize_adv_sel")
+    return out
+
+
+def ac_grad_accumulate(acc, chunk, first):
+    """acc = (0 if first else acc) + chunk on the device, one fp32 add per element (fb_ac_grad_accumulate): what acc.zero_() and
+    acc += chunk give, in one launch -> acc"""
+    _dev_check(acc, chunk)
+    if acc.dtype != torch.float32 or chunk.dtype != torch.float32 or acc.numel() != chunk.numel() or acc.numel() < 1:
+        raise ValueError("acc and chunk must be non-empty float32 tensors of one length")
+    L.check(L.lib().fb_ac_grad_accumulate(L.ptr(acc), L.ptr(chunk), int(acc.numel()), int(bool(first)), L.current_stream()), "fb_ac_grad_accumulate")
+    return acc
+
+
+def ppo_epoch(replay, net, pos, sel, adv, ret, logp_old, value_old, minibatches, grad, chunk_grad, loss_rows, epoch_mean, a_out=None,
+              adv_scratch=None, check_sel=True):
+    """one PPO epoch as one host call (fb_ppo_epoch): `minibatches` consecutive minibatches of pos / sel (int64[n]: the ring positions and
+    the rollout-buffer indices of the epoch's n transitions), each read in ring-fed chunks of <= 256 whose gradients are summed into grad
+    (chunk_grad: the chunk's), clipped if the net clips, and applied by Adam.  adv_scratch (float32 of adv's size, not adv): every
+    minibatch's advantages are normalised over the minibatch into it first.  loss_rows float32[minibatches, 6] receives the minibatches'
+    six loss numbers, epoch_mean float32[6] their mean.  Bit for bit the composed calls (ppo_train_from_replay, ac_grad_accumulate,
+    QNet.clip_grad, QNet.apply_adam); nothing is read back.  check_sel as for ppo_train_from_replay -> (epoch_mean, a_out u8[256])"""
+    if net.arch != AC_ARCH:
+        raise ValueError("ppo_epoch needs an actor-critic net (QNet(..., arch='ac'))")
+    if replay.prioritized:
+        raise ValueError("ppo_epoch reads the rollout from a uniform memory only")
+    _dev_check(pos, sel, adv, ret, logp_old, value_old, grad, chunk_grad, loss_rows, epoch_mean, a_out, adv_scratch)
+    n, m = int(pos.numel()), int(minibatches)
+    if pos.dtype != torch.int64 or n < 1:
+        raise ValueError("pos must be a non-empty int64 tensor")
+    if sel.numel() != n:
+        raise ValueError(f"sel must be int64[{n}]")
+    if m < 1 or n % m:
+        raise ValueError(f"minibatches must be >= 1 and divide the epoch's {n} transitions, got {minibatches}")
+    check_ppo_batch(n, sel, adv, ret, logp_old, value_old)
+    _check_sel(sel, adv.numel(), check_sel)
+    _check_flat_grad(grad, net.n_params)
+    _check_flat_grad(chunk_grad, net.n_params)
+    if adv_scratch is not None and (adv_scratch.dtype != torch.float32 or adv_scratch.numel() != adv.numel()):
+        raise ValueError(f"adv_scratch must be a contiguous float32[{adv.numel()}]")
+    if loss_rows.dtype != torch.float32 or loss_rows.numel() != 6 * m:
+        raise ValueError(f"loss_rows must be float32[{m}, 6]")
+    if epoch_mean.dtype != torch.float32 or epoch_mean.numel() != 6:
+        raise ValueError("epoch_mean must be float32[6]")
+    a_out = torch.empty(256, dtype=torch.uint8, device=pos.device) if a_out is None else a_out
+    if a_out.dtype != torch.uint8 or a_out.numel() < 256:
+        raise ValueError("a_out must be uint8[256]")
+    L.check(L.lib().fb_ppo_epoch(replay.h, net.h, n, m, L.ptr(pos), L.ptr(sel), L.ptr(adv), L.ptr(ret), L.ptr(logp_old), L.ptr(value_old),
+                                 int(adv_scratch is not None), L.ptr(adv_scratch), L.ptr(grad), L.ptr(chunk_grad), L.ptr(a_out), L.ptr(loss_rows),
+                                 L.ptr(epoch_mean), L.current_stream()), "fb_ppo_epoch")
+    return epoch_mean, a_out
+
+
+def ppo_epoch_sum(net, out):
+    """the running sum of the chunks' six loss numbers over the net's last ppo_epoch, in the order one accumulator fed chunk by chunk
+    adds them (fb_ppo_epoch_sum), into out float32[6] -> out"""
+    if net.arch != AC_ARCH:
+        raise ValueError("ppo_epoch_sum needs an actor-critic net (QNet(..., arch='ac'))")
+    _dev_check(out)
+    if out.dtype != torch.float32 or out.numel() != 6:
+        raise ValueError("out must be float32[6]")
+    L.check(L.lib().fb_ppo_epoch_sum(net.h, L.ptr(out), L.current_stream()), "fb_ppo_epoch_sum")
+    return out
+
+
 class AcRolloutStep:
     """One step of an A2C rollout as a single host call (fb_ac_rollout_step): sample the policy (value and log-probability into row
     `slot` of the rollout buffers) -> frame_step (reward / terminal into row `slot`) -> store.  The results of QNet.act_policy_nib,

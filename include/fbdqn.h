@@ -681,6 +681,53 @@ int fb_ppo_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const
 int fb_ac_normalize_adv(const float *adv, int64_t n, float *out, void *stream);
 int fb_ac_permute(int64_t n, uint64_t seed, uint64_t draw, int64_t *out, void *stream);
 
+/* ------------------------------------------------------------------ PPO: one epoch as one host call, and per-minibatch advantage normalisation
+ * Of the block above's "not offered" items this one offers per-minibatch advantage normalisation (fb_ac_normalize_adv_sel, fb_ppo_epoch's
+ * mb_adv_norm) in the library, and gives the loop above it what KL early stopping and annealing need: fb_ppo_epoch leaves the epoch's mean
+ * approximate KL in epoch_mean[5], which a caller reads between two epochs to stop (there is no device-side gate on Adam), and annealing is
+ * fb_qnet_set_hparams between two updates (VecActorCritic: target_kl, anneal_lr).  Data-parallel PPO, bf16 and recurrent policies stay not
+ * offered.
+ *   normalise   fb_ac_normalize_adv_sel(adv, sel, n, out), per MINIBATCH: the statistics over the n selected elements x_j = adv[sel[j]],
+ *               j < n, only; in double, fb_ac_normalize_adv's two-level order applied to j: thread t of ONE 256-thread workgroup sums
+ *               j = t (mod 256) in ascending j (from 0.0), one thread adds the 256 partial sums in ascending t: S; mean = S / n; the same
+ *               two-level sum of (x_j - mean)^2: Q; sd = sqrt(Q / n); out[sel[j]] = (float)(((double)adv[sel[j]] - mean) / (sd + 1e-8)).
+ *               Positions of out that sel does not name are not written.  out == adv is refused: an element normalised in one epoch would
+ *               be normalised again in the next.  The sel[j] are distinct and inside adv / out by the caller's contract (a slice of a
+ *               permutation), as fb_ppo_train_from_replay's sel.  1 <= n < 2^31.  Vector stores only, no atomics
+ *   accumulate  fb_ac_grad_accumulate(acc, chunk, n, first): acc[i] = (first ? 0.f : acc[i]) + chunk[i], one fp32 add per element: what
+ *               zeroing acc and adding the chunks one by one gives (a -0 of a first chunk becomes +0; NaN and Inf pass through; with
+ *               first != 0 the old acc is not read).  Any n in 1 <= n < 2^31, any alignment; acc != chunk
+ *   epoch       fb_ppo_epoch: ONE PPO epoch over n transitions; pos[k] is element k's ring position, sel[k] its index into the rollout
+ *               buffers adv, ret, logp_old, value_old.  With mb = n / minibatches, for each minibatch m in ascending order:
+ *                 1. mb_adv_norm != 0: fb_ac_normalize_adv_sel(adv, sel + m mb, mb, adv_scratch); the chunks of this minibatch then read
+ *                    adv_scratch in place of adv
+ *                 2. for every chunk of <= 256 consecutive elements k .. of the minibatch, in ascending order:
+ *                    fb_ppo_train_from_replay(replay, net, chunk size, pos + k, sel + k, adv or adv_scratch, ret, logp_old, value_old,
+ *                    n_total = mb, a_out, the chunk's six numbers, chunk_grad); then fb_ac_grad_accumulate(grad, chunk_grad,
+ *                    fb_qnet_num_params, first = the minibatch's first chunk); then loss_rows[m][c] = (first ? 0.f : loss_rows[m][c]) +
+ *                    the chunk's number c, c = 0 .. 5: the chunks' numbers added in fp32, from 0, in ascending chunk order
+ *                 3. the net's max_grad_norm > 0: fb_qnet_clip_grad(net, grad)
+ *                 4. fb_qnet_apply_adam(net, grad)
+ *               afterwards epoch_mean[c] = (sum_m loss_rows[m][c], ascending m from 0.f) / (float)minibatches.  The whole call is, bit for
+ *               bit, the composed calls above on `stream`: parameters, Adam state, grad, a_out (the last chunk's actions).  It launches
+ *               only: no host synchronisation, no host read.  (On the way epoch_mean holds each chunk's six numbers.)
+ *   running sum fb_ppo_epoch_sum(net, sum): sum [dev] f32[6] receives the net's running sum of its LAST fb_ppo_epoch -- the chunks' number c
+ *               added in fp32, from 0.f, in ascending order over ALL chunks of the epoch, minibatch after minibatch (zeros before the
+ *               first epoch): what a caller that adds every chunk's six numbers to one accumulator holds, as VecActorCritic's
+ *               chunk-by-chunk loop does.  The rows' sum behind epoch_mean is another order of the same additions and differs from it in
+ *               the last places wherever a minibatch has more than one chunk.  A copy on `stream`; an AC net only
+ *   refused     FB_ERR_INVALID before any launch or counter change: everything fb_ppo_train_from_replay refuses (a net that is not an AC
+ *               net, a prioritized or n-step memory, a chunk above max_batch); NULL arguments (adv_scratch may be NULL without mb_adv_norm);
+ *               n outside 1 <= n < 2^31; minibatches < 1 or not dividing n; mb_adv_norm without adv_scratch or with adv_scratch == adv;
+ *               grad == chunk_grad; a grad that is not 16-byte aligned on a net that clips */
+int fb_ac_normalize_adv_sel(const float *adv, const int64_t *sel, int64_t n, float *out, void *stream);
+int fb_ac_grad_accumulate(float *acc, const float *chunk, int64_t n, int first, void *stream);
+int fb_ppo_epoch_sum(fb_qnet_t net, float *sum /*[dev] f32[6]*/, void *stream);
+int fb_ppo_epoch(fb_replay_t replay, fb_qnet_t net, int64_t n, int minibatches, const int64_t *pos, const int64_t *sel, const float *adv,
+                 const float *ret, const float *logp_old, const float *value_old, int mb_adv_norm, float *adv_scratch /*f32[rollout size] or NULL*/,
+                 float *grad /*f32[num_params]*/, float *chunk_grad /*f32[num_params]*/, uint8_t *a_out /*u8[256]*/,
+                 float *loss_rows /*f32[minibatches][6]*/, float *epoch_mean /*f32[6]*/, void *stream);
+
 /* ------------------------------------------------------------------ discrete soft actor-critic (SAC; Haarnoja et al. 2018, Christodoulou 2019)
  * The off-policy learner of a STOCHASTIC policy: a policy head and two Q heads on the shared trunk, trained from the replay memory with an
  * entropy bonus whose temperature alpha is fixed or learned.  One GPU, fp32, a uniform memory at n-step 1.

@@ -1,6 +1,8 @@
 """What PPO costs: µs per 256-sample ring-fed PPO chunk against the A2C chunk (the same trunk and backward; the loss launch differs), µs per
 fb_ac_permute and fb_ac_normalize_adv at T N = 5120 and 131 072, and the whole PPO update at 1024 envs x T = 5 with the defaults
-(4 epochs x 4 minibatches of 1280 = 80 chunks, 16 Adam steps).
+(4 epochs x 4 minibatches of 1280 = 80 chunks, 16 Adam steps), then that update chunk by chunk (one_call=False) beside each epoch as one
+host call (one_call=True), beside per-minibatch advantage normalisation and beside the per-epoch read of target_kl, the four alternated
+within every round in one process.
 
     python tools/time_ppo.py [--steps 300] [--warmup 50] [--repeats 5] [--parent DIR] [--out FILE]
     python tools/time_ppo.py --chunk-row --root DIR          (what --parent runs: the A2C chunk row alone, on the tree at DIR)
@@ -144,6 +146,19 @@ def main():
             row(f"{algo} update", N, "env steps per second", [T * N / (u * 1e-6) for u in ups], unit="1/s")
             del ac
             torch.cuda.synchronize()
+        # the PPO update's four forms in ONE process, alternated within each round (target_kl = 1e9 reads after every epoch and never stops)
+        forms = {"one_call=False (composed)": dict(one_call=False), "one_call=True": dict(one_call=True),
+                 "one_call, adv_norm_scope=minibatch": dict(adv_norm_scope="minibatch"), "one_call, target_kl (3 reads)": dict(target_kl=1e9)}
+        acs = {c: VecActorCritic(N, rollout=T, seed=1, algo="ppo", **kw) for c, kw in forms.items()}
+        for ac in acs.values():
+            for _ in range(10):
+                ac.update()
+        res = {c: [] for c in acs}
+        for _ in range(a.repeats):
+            for c, ac in acs.items():
+                res[c].append(timed(torch, ac.update, max(1, a.steps // 10)))
+        for c, v in res.items():
+            row("ppo update", N, c, v)
 
 
 if __name__ == "__main__":
