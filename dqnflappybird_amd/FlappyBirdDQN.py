@@ -109,7 +109,8 @@ def build_parser():
     parser.add_argument("--steps", type=int, default=None)
     parser.add_argument("--quiet", action="store_true")
     parser.add_argument("--vec", type=int, default=0, help="run N vectorised envs (device-resident loop)")
-    parser.add_argument("--n-step", type=int, default=1, help="learn from K-step returns (--vec, uniform replay; 1 = the reference's one-step TD)")
+    parser.add_argument("--n-step", type=int, default=1, help="learn from K-step returns (--vec, uniform replay; --model iqnper | rainbowiqn | sacper: prioritized; "
+                                                                      "1 = the reference's one-step TD)")
     parser.add_argument("--noisy", action="store_true", help="noisy fc1 and head layers, epsilon 0 (--model c51 | c51per | c51doubleper | rainbow, --vec)")
     parser.add_argument("--acting-noise", choices=("shared", "env"), default="shared",
                         help="--noisy: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
@@ -145,34 +146,45 @@ def build_parser():
     parser.add_argument("--target-kl", type=float, default=None, help="--model ppo: stop an update's epochs once an epoch's mean approximate KL exceeds "
                                                                        "1.5 X (default 0 = off)")
     parser.add_argument("--anneal-lr", action="store_true", help="--model ppo: the learning rate falls linearly to 0 over the run's --steps updates")
-    parser.add_argument("--target-entropy", type=float, default=None, help="--model sac: the entropy the learned temperature aims at (default 0.98 ln 2)")
-    parser.add_argument("--alpha-lr", type=float, default=None, help="--model sac: the temperature's learning rate (default 0 = --alpha stays fixed)")
+    parser.add_argument("--target-entropy", type=float, default=None, help="--model sac | sacper: the entropy the learned temperature aims at (default 0.98 ln 2)")
+    parser.add_argument("--alpha-lr", type=float, default=None, help="--model sac | sacper: the temperature's learning rate (default 0 = --alpha stays fixed)")
     return parser
 
 
+SAC_MODELS = ("sac", "sacper")                           # sacper: SAC on a prioritized memory, which also takes --n-step
+
+
 def sac_kwargs(args, parser):
-    """--model sac's options as VecSAC's keywords (--alpha is the temperature there, default 0.2); everything is refused here, by name,
-    before anything touches the GPU"""
+    """--model sac's (sacper's: the same, and --n-step) options as VecSAC's keywords (--alpha is the temperature there, default 0.2);
+    everything is refused here, by name, before anything touches the GPU"""
     given = [n for n, v in (("--target-entropy", args.target_entropy), ("--alpha-lr", args.alpha_lr)) if v is not None]
-    if args.model != "sac":
+    if args.model not in SAC_MODELS:
         if given:
             parser.error(f"{' / '.join(given)} need --model sac, not --model {args.model}")
         return None
+    per = args.model == "sacper"
     if not args.vec:
-        parser.error("--model sac needs --vec: discrete soft actor-critic runs in the vectorised loop only")
-    for name, on in (("--noisy", args.noisy), ("--n-step", args.n_step != 1), ("--huber", args.huber is not None),
+        parser.error(f"--model {args.model} needs --vec: discrete soft actor-critic runs in the vectorised loop only")
+    for name, on in (("--noisy", args.noisy), ("--n-step", args.n_step != 1 and not per), ("--huber", args.huber is not None),
                      ("--tau / --clip", args.tau is not None or args.clip is not None),
                      ("--n-quantiles / --kappa", args.n_quantiles is not None or args.kappa is not None)):
         if on:
-            parser.error(f"{name} is not an option of --model sac (--alpha, --target-entropy, --alpha-lr, --polyak, --max-grad-norm are)")
-    from .vecsac import check_args
+            parser.error(f"{name} is not an option of --model {args.model} (--alpha, --target-entropy, --alpha-lr, --polyak, --max-grad-norm"
+                         f"{', --n-step' if per else ''} are)"
+                         + (" -- n-step SAC runs on the prioritized memory: --model sacper --n-step K" if name == "--n-step" else ""))
+    from .vecsac import check_args, check_replay
     kw = dict(alpha=0.2 if args.alpha is None else args.alpha, target_entropy=args.target_entropy, alpha_lr=0.0 if args.alpha_lr is None else args.alpha_lr,
               polyak=0.005 if args.polyak is None else args.polyak, max_grad_norm=0.0 if args.max_grad_norm is None else args.max_grad_norm)
     try:
-        check_args(args.vec, min(32, args.vec), kw["alpha"], kw["target_entropy"], kw["alpha_lr"], kw["polyak"], 100, 0.99, 1e-4, kw["max_grad_norm"], None)
+        checked = check_args(args.vec, min(32, args.vec), kw["alpha"], kw["target_entropy"], kw["alpha_lr"], kw["polyak"], 100, 0.99, 1e-4,
+                             kw["max_grad_norm"], None)
+        if per:
+            check_replay(True, args.n_step, checked[0], checked[6], checked[10])
     except ValueError as e:
         parser.error(str(e))
     kw["batch"] = min(32, args.vec)
+    if per:                                              # (--model sac: VecSAC's keywords are the ones of before)
+        kw.update(prioritized=True, n_step=args.n_step)
     return kw
 
 

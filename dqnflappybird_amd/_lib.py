@@ -134,6 +134,9 @@ SIGNATURES = {
     "fb_qnet_sac_train_step": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
     "fb_sac_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp],
     "fb_sac_step": [_vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _f, _vp],
+    "fb_qnet_sac_per_train_step": [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp],
+    "fb_sac_per_train_from_replay": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp, _vp],
+    "fb_sac_per_step": [_vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _f, _vp],
     "fb_qnet_create_iqn": [_i, _i, _i, _i, _i, _f, _i, _vp],
     "fb_qnet_create_iqn_dueling": [_i, _i, _i, _i, _i, _f, _i, _vp],
     "fb_qnet_set_iqn_risk": [_vp, _f],

@@ -288,16 +288,23 @@ struct SacLossArgs {
     const uint8_t *act, *term; const float *rew; double gamma;
     float *dl, *xs, *dhf, *y_out;                                // dl f32[B][16] (fb_sac.hip); y_out f32[B] or NULL
 };
+// What the prioritized loss launch takes: SacLossArgs and, behind its last field, isw / abs_err, both f32[B], both set (the weights in,
+// 0.5 (|d1| + |d2|) out).  The uniform launch keeps SacLossArgs, so its kernels are the ones of before the prioritized form existed
+struct SacPerLossArgs : SacLossArgs { const float *isw; float *abs_err; };
 // temp: the temperature update runs (alpha_lr > 0 and the step applies Adam itself)
 struct SacGradArgs { int B, FC, A; NetOff off; SacOff so; const float *dl, *xs, *dhf; float *grad, *loss, *gmax; FbAdamHead *adam; int tick;
                      float *sw; float target_entropy, alpha_lr; int temp; };
 void fb_sac_launch_head(hipStream_t st, const SacHeadArgs &H);
 void fb_sac_launch_loss(hipStream_t st, const SacLossArgs &L);
+void fb_sac_launch_per_loss(hipStream_t st, const SacPerLossArgs &L);
 void fb_sac_launch_grad(hipStream_t st, const SacGradArgs &L);
 int fb_qnet_is_sac(fb_qnet_t h);              // 1: a SAC net (fb_qnet_create_sac)
 // the checks of the two SAC training calls, `who` in the message; the ring-fed SAC train step behind fb_sac_train_from_replay's checks
 int fb_qnet_sac_check_train(fb_qnet_t h, int batch, double gamma, const char *who);
 int fb_qnet_sac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
+// ... and the prioritized one behind fb_sac_per_train_from_replay's (isw / abs_err f32[batch], both non-NULL).  gamma: the bootstrap's discount
+int fb_qnet_sac_per_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const float *isw, double gamma, float *loss, float *abs_err,
+                               float *q_target, float *flat_grad, void *stream);
 // ---- implicit quantile networks (FB_ARCH_IQN): the kernels live in fb_iqn.hip, a code object of their own; fb_qnet.hip fills these structs
 // and hands them to the launchers below.  off: the PLAIN layout (wq / bq = W_q b_q); io: the embedding behind it, W_e[64][FC] b_e[FC].
 // A fold block is [b_fc1 | phibar * W_q | b_q]: the plain layout from b_fc1 on, so `block - off.bf1` is read as a plain net's parameters

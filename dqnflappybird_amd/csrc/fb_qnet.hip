@@ -4858,10 +4858,12 @@ static void loss_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         return;
     }
     if (c.sac) {                                 // SAC: per-sample target / losses / dz / dQ / dhf, then the per-unit reductions (fb_sac.hip)
-        SacLossArgs L;
+        SacPerLossArgs L;                        // (SacLossArgs, then the prioritized form's two fields)
         side(L); transition(L);
         L.P0 = h->params[0]; L.P1 = h->params[1]; L.so = h->sac_off; L.sw = h->sac_w; L.xs = h->ac_xs; L.y_out = p.y;
-        fb_sac_launch_loss(c.st, L);
+        L.isw = p.isw; L.abs_err = p.abs_err;    // (both set: the prioritized form; the uniform calls leave both NULL and launch the kernel of before)
+        if (p.isw) fb_sac_launch_per_loss(c.st, L);
+        else fb_sac_launch_loss(c.st, L);
         const SacGradArgs gA{B, FC, h->A, h->off, h->sac_off, h->ac_dl, h->ac_xs, h->dhf, p.G, p.loss, h->gmax, adam_head,
                              p.tick, h->sac_w, h->sac_hbar, h->sac_alr, p.sac_temp ? 1 : 0};
         fb_sac_launch_grad(c.st, gA);
@@ -5790,11 +5792,13 @@ static Plan three_slice_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t 
     return p;
 }
 
-// (the ring-fed SAC call takes a memory at n-step 1 only: fb_sac.hip)
+// (the uniform ring-fed SAC call takes a memory at n-step 1 only, the prioritized one the memory's n: fb_sac.hip)  isw / abs_err both set: the
+// prioritized form, the same plan with the importance weights in and the priority out (the loss launch's weighted instantiation), else both NULL
 static Plan sac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t, double gamma,
-                           float *loss, float *q_target, float *flat_grad, const FbRingSrc *ring) {
+                           float *loss, float *q_target, float *flat_grad, const FbRingSrc *ring, const float *isw = nullptr, float *abs_err = nullptr) {
     Plan p = three_slice_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, ring);
     p.sac_temp = flat_grad == nullptr && h->sac_alr > 0.f;
+    p.isw = isw; p.abs_err = abs_err;
     return p;
 }
 
@@ -5812,6 +5816,27 @@ int fb_qnet_sac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, double gam
     const int rc = fb_qnet_sac_check_train(h, B, gamma, "fb_sac_train_from_replay");
     if (rc != FB_OK) return rc;
     Plan p = sac_train_plan(h, B, nullptr, ring->a, ring->r, nullptr, ring->t, gamma, loss, q_target, flat_grad, ring);
+    return run_train(h, p, stream);
+}
+
+extern "C" int fb_qnet_sac_per_train_step(fb_qnet_t h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
+                                          const float *isw, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    const char *who = "fb_qnet_sac_per_train_step";
+    FB_REQUIRE(h && s && a && r && s2 && t && loss, "%s: NULL argument", who);
+    FB_REQUIRE(isw && abs_err, "%s: the prioritized step needs the importance weights (isw) and abs_err", who);
+    const int rc = fb_qnet_sac_check_train(h, B, gamma, who);
+    if (rc != FB_OK) return rc;
+    Plan p = sac_train_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, nullptr, isw, abs_err);
+    return run_train_gathered(h, p, B, stream);
+}
+
+int fb_qnet_sac_per_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
+                               float *flat_grad, void *stream) {
+    const char *who = "fb_sac_per_train_from_replay";
+    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss && isw && abs_err, "%s: NULL argument", who);
+    const int rc = fb_qnet_sac_check_train(h, B, gamma, who);
+    if (rc != FB_OK) return rc;
+    Plan p = sac_train_plan(h, B, nullptr, ring->a, ring->r, nullptr, ring->t, gamma, loss, q_target, flat_grad, ring, isw, abs_err);
     return run_train(h, p, stream);
 }
 

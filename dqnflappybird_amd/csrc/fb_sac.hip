@@ -3,7 +3,8 @@
 // include/fbdqn.h pins the semantics.  Head parameters behind b_fc1, read raw: W_pi b_pi (the plain head's place), W_q1 b_q1, W_q2 b_q2;
 // z = h . W_pi + b_pi, Q_i = h . W_qi + b_qi.
 //   sac_head_kernel   acting / forward: logits, Q1, Q2, the soft state value, the sampled (or greedy) action and its log-probability; one wave per state
-//   sac_loss_kernel   training, launch 1 of 2: per sample the soft target, both critic errors, the actor term, dz / dQ, the dhf row and the activation row
+//   sac_loss_kernel   training, launch 1 of 2: per sample the soft target, both critic errors, the actor term, dz / dQ, the dhf row and the activation row.
+//                     Its PW instantiations are the prioritized form: importance weights into the critic terms, the mean |critic error| out as the priority
 //   sac_grad_kernel   training, launch 2 of 2: per 16 fc1 units the gradients of b_fc1, W_pi, W_q1, W_q2; workgroup 0: the head biases, the six
 //                     loss numbers, Adam's tick and the temperature update
 // Behind them run fc1_bwd_big_kernel, the conv backward and Adam of fb_qnet.hip, unchanged.
@@ -80,8 +81,12 @@ __global__ __launch_bounds__(256) void sac_head_kernel(SacHeadArgs H) {
 // ---- training, launch 1 of 2: one wave per sample.  Rows b / B + b / 2 B + b of the fc1 partial sums: s and s' through the online net, s'
 // through the target net.  Every lane holds the same heads, so the target, both losses and the gradients need no further exchange.
 // dl[b][16]: dz_c at c < 8, dQ1(s, a) at 8, dQ2(s, a) at 9, d1^2 / d2^2 / L_pi / H at 10 .. 13, the action at 14, the alpha used at 15.
-template <int AT>
-__global__ __launch_bounds__(256) void sac_loss_kernel(SacLossArgs L) {
+// PW, the prioritized form (fb_qnet_sac_per_train_step; SacPerLossArgs): w_b = isw[b] is multiplied LAST into dQ1 / dQ2 and into slots 10 / 11
+// -- the dhf row and both critics' gradients pick it up through dQ_i -- and abs_err[b] takes 0.5 (|d1| + |d2|), unweighted (the priority);
+// dz, L_pi and H stay unweighted.  w = 1 leaves the bits of the uniform form.  w_b is loaded once the six heads are formed: nothing of it
+// is live across them, and the load is wave-uniform.
+template <int AT, bool PW>
+__global__ __launch_bounds__(256) void sac_loss_kernel(std::conditional_t<PW, SacPerLossArgs, SacLossArgs> L) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= L.B) return;                                        // (wave-uniform)
     const int A = AT == MAXA ? L.A : AT, FC = L.FC, B = L.B;
@@ -107,7 +112,13 @@ __global__ __launch_bounds__(256) void sac_loss_kernel(SacLossArgs L) {
 #pragma unroll
     for (int c = 1; c < AT; c++) { q1a = c == ab ? q1[c] : q1a; q2a = c == ab ? q2[c] : q2a; }
     const float Bf = (float)B, d1 = q1a - y, d2 = q2a - y;
-    const float dq1 = (2.f * d1) / Bf, dq2 = (2.f * d2) / Bf;
+    float dq1 = (2.f * d1) / Bf, dq2 = (2.f * d2) / Bf, wb = 1.f;
+    if constexpr (PW) {
+        wb = L.isw[b];
+        dq1 *= wb; dq2 *= wb;
+        if (lane == 0) L.abs_err[b] = 0.5f * (fabsf(d1) + fabsf(d2));
+    }
+    const auto weighted = [&](float v) { if constexpr (PW) return v * wb; else return v; };      // (the uniform form: the statement of before)
     float f[AT], Lpi = 0.f, H = 0.f;
 #pragma unroll
     for (int c = 0; c < AT; c++) {
@@ -118,7 +129,7 @@ __global__ __launch_bounds__(256) void sac_loss_kernel(SacLossArgs L) {
     float dz[AT];
 #pragma unroll
     for (int c = 0; c < AT; c++) dz[c] = c < A ? (p[c] * (f[c] - Lpi)) / Bf : 0.f;
-    float o = lane == 8 ? dq1 : lane == 9 ? dq2 : lane == 10 ? d1 * d1 : lane == 11 ? d2 * d2 : lane == 12 ? Lpi : lane == 13 ? H
+    float o = lane == 8 ? dq1 : lane == 9 ? dq2 : lane == 10 ? weighted(d1 * d1) : lane == 11 ? weighted(d2 * d2) : lane == 12 ? Lpi : lane == 13 ? H
               : lane == 14 ? (float)ab : alpha;
 #pragma unroll
     for (int c = 0; c < AT; c++) o = lane == c ? dz[c] : o;
@@ -240,7 +251,11 @@ void fb_sac_launch_head(hipStream_t st, const SacHeadArgs &H) {
 }
 
 void fb_sac_launch_loss(hipStream_t st, const SacLossArgs &L) {
-    with_actions(L.A, [&](auto a) { hipLaunchKernelGGL(sac_loss_kernel<decltype(a)::value>, dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
+    with_actions(L.A, [&](auto a) { hipLaunchKernelGGL((sac_loss_kernel<decltype(a)::value, false>), dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
+}
+
+void fb_sac_launch_per_loss(hipStream_t st, const SacPerLossArgs &L) {
+    with_actions(L.A, [&](auto a) { hipLaunchKernelGGL((sac_loss_kernel<decltype(a)::value, true>), dim3((L.B + 3) / 4), dim3(256), 0, st, L); });
 }
 
 void fb_sac_launch_grad(hipStream_t st, const SacGradArgs &L) {
@@ -250,6 +265,14 @@ void fb_sac_launch_grad(hipStream_t st, const SacGradArgs &L) {
 // the memory checks of the two ring-fed SAC calls: a uniform memory at n-step 1
 static int sac_check_memory(fb_replay_t replay, const char *who) {
     return fb_check_uniform_n1(replay, who, "SAC trains from a uniform memory only (prioritized replay is not offered)", "SAC reads it");
+}
+// the memory checks of the two prioritized ring-fed SAC calls (include/fbdqn.h, the prioritized SAC block: calls of their own, the memory's
+// kind never switches what a call does): a prioritized one, at the n it was made with, whose gamma the caller's is and whose tree holds a
+// leaf once `pushes_ahead` more pushes are counted (pushes_ahead < 0: a store-only step, which samples nothing)
+static int sac_per_check_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who) {
+    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (fb_sac_train_from_replay / fb_sac_step take a uniform one)", who);
+    const int rc = fb_replay_check_gamma(replay, gamma, who);
+    return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
 }
 
 extern "C" int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
@@ -289,6 +312,55 @@ extern "C" int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     if (rc != FB_OK) return rc;
     if (train) {
         rc = fb_sac_train_from_replay(replay, net, batch, b->idx, b->a, b->r, b->t, gamma, b->loss, nullptr, b->flat_grad, stream);
+        if (rc != FB_OK) return rc;
+    }
+    if (rho > 0.f) rc = fb_qnet_soft_sync_target(net, rho, stream);
+    return rc;
+}
+
+extern "C" int fb_sac_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *isw, uint8_t *a_out, float *r_out,
+                                            uint8_t *t_out, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    const char *who = "fb_sac_per_train_from_replay";
+    FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
+    FB_REQUIRE(isw && abs_err, "%s: the prioritized step needs the importance weights (isw) and abs_err", who);
+    FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
+    int rc = sac_per_check_memory(replay, gamma, 0, who);
+    if (rc != FB_OK) return rc;
+    rc = fb_qnet_sac_check_train(net, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    FbRingSrc ring;
+    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
+    if (rc != FB_OK) return rc;
+    return fb_qnet_sac_per_train_ring(net, batch, &ring, isw, fb_replay_bootstrap_gamma(replay, gamma), loss, abs_err, q_target, flat_grad, stream);
+}
+
+extern "C" int fb_sac_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed,
+                               uint64_t step, int train, double gamma, float rho, void *stream) {
+    const char *who = "fb_sac_per_step";
+    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
+    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "%s: NULL buffer", who);
+    FB_REQUIRE(!train || (b->idx && b->a && b->r && b->t && b->loss), "%s: a training step needs the idx / a / r / t / loss buffers", who);
+    FB_REQUIRE(!train || (b->isw && b->isw32 && b->abs_err), "%s: the prioritized step needs the isw / isw32 / abs_err buffers", who);
+    FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
+    int rc = sac_per_check_memory(replay, gamma, train ? 1 : -1, who);  // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
+    if (rc == FB_OK) rc = fb_check_step_handles(env, replay, net, n_envs, who);
+    if (rc == FB_OK) rc = fb_qnet_sac_check_train(net, batch, gamma, who);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(rho >= 0.f && rho <= 1.f, "%s: rho must be in [0, 1] (0 = no target update; got %g)", who, (double)rho);
+    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
+    rc = fb_qnet_act_policy_nib(net, b->nib, n_envs, seed, step, 0, b->actions, nullptr, nullptr, nullptr, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+    if (rc != FB_OK) return rc;
+    rc = fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, stream);
+    if (rc != FB_OK) return rc;
+    if (train) {
+        // Memory.sample -> the weighted loss -> Memory.batch_update, in line on `stream` at every env count; abs_err stays as the loss left it
+        rc = fb_replay_sample_f32(replay, batch, nullptr, b->idx, b->isw, b->isw32, stream);
+        if (rc != FB_OK) return rc;
+        rc = fb_sac_per_train_from_replay(replay, net, batch, b->idx, b->isw32, b->a, b->r, b->t, gamma, b->loss, b->abs_err, nullptr, b->flat_grad, stream);
+        if (rc != FB_OK) return rc;
+        rc = fb_replay_update_priorities_keep(replay, batch, b->idx, b->abs_err, stream);
         if (rc != FB_OK) return rc;
     }
     if (rho > 0.f) rc = fb_qnet_soft_sync_target(net, rho, stream);

@@ -902,6 +902,26 @@ class QNet:
                                                L.ptr(flat_grad), L.current_stream()), "fb_qnet_sac_train_step")
         return loss, y
 
+    def sac_per_train_step(self, s, a, r, s2, t, isw, gamma=0.99, flat_grad=None, want_target=True):
+        """sac_train_step with importance weights isw f32[B] (fb_qnet_sac_per_train_step): both critic terms and their gradients are
+        weighted by w_b, the actor term, the entropy and the temperature's step are not; abs_err[b] = 0.5 (|d1| + |d2|), without the
+        weight, is the priority.  isw = 1 gives sac_train_step's bits.  On n-step transitions gamma is the bootstrap's gamma^n.
+        -> (loss f32[6], q_target f32[B] or None, abs_err f32[B])"""
+        self._need_sac("sac_per_train_step")
+        _dev_check(s, a, r, s2, t, isw, flat_grad)
+        for name, x in (("s", s), ("s2", s2)):
+            _check_states(name, x, s.shape[0])
+        B = s.shape[0]
+        check_sac_batch(B, a, r, t, flat_grad, self.n_params)
+        check_isw(B, isw)
+        loss = torch.zeros(6, dtype=torch.float32, device=self.device)
+        ae = torch.empty(B, dtype=torch.float32, device=self.device)
+        y = torch.empty(B, dtype=torch.float32, device=self.device) if want_target else None
+        L.check(L.lib().fb_qnet_sac_per_train_step(self.h, B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), L.ptr(isw), float(gamma),
+                                                   L.ptr(loss), L.ptr(ae), L.ptr(y), L.ptr(flat_grad), L.current_stream()),
+                "fb_qnet_sac_per_train_step")
+        return loss, y, ae
+
     # -- implicit quantile networks (arch='iqn') -----------------------------------------
     def _need_iqn(self, what):
         if self.arch not in IQN_ARCHS:
@@ -1208,7 +1228,7 @@ def check_iqn_batch(B, a, r, t, tau, tau_next, n_tau, n_tau_next, flat_grad, n_p
 
 
 def check_isw(B, isw):
-    """the shape check of the prioritized IQN calls' importance weights, on the host"""
+    """the shape check of the prioritized IQN and SAC calls' importance weights, on the host"""
     if isw is None or isw.dtype != torch.float32 or tuple(isw.shape) != (B,) or not isw.is_contiguous():
         raise ValueError(f"isw must be a contiguous float32[{B}] (the prioritized step needs the importance weights)")
 
@@ -1293,6 +1313,22 @@ def sac_train_from_replay(replay, net, idx, gamma=0.99, flat_grad=None, want_tar
     L.check(L.lib().fb_sac_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(a), L.ptr(r), L.ptr(t), float(gamma), L.ptr(loss), L.ptr(y),
                                              L.ptr(flat_grad), L.current_stream()), "fb_sac_train_from_replay")
     return (loss, a, r, t, y) if want_target else (loss, a, r, t)
+
+
+def sac_per_train_from_replay(replay, net, idx, isw, gamma=0.99, flat_grad=None, want_target=False):
+    """QNet.sac_per_train_step on the transitions at the SumTree leaves idx of a prioritized memory (at the n it was made with; gamma
+    must be the memory's), read from its frame ring in place (fb_sac_per_train_from_replay); isw f32[B]: replay.sample's importance
+    weights -> (loss f32[6], a u8[B], r f32[B], t u8[B][, q_target f32[B]], abs_err f32[B])"""
+    B, dev, a, loss = _ring_call("sac_per_train_from_replay", replay, net, SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", "trains from", idx, 6,
+                                 flat_grad, isw, prioritized=True)
+    check_sac_batch(B, None, None, None, flat_grad, net.n_params)
+    check_isw(B, isw)
+    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    ae = torch.empty(B, dtype=torch.float32, device=dev)
+    y = torch.empty(B, dtype=torch.float32, device=dev) if want_target else None
+    L.check(L.lib().fb_sac_per_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(isw), L.ptr(a), L.ptr(r), L.ptr(t), float(gamma), L.ptr(loss),
+                                                 L.ptr(ae), L.ptr(y), L.ptr(flat_grad), L.current_stream()), "fb_sac_per_train_from_replay")
+    return (loss, a, r, t, y, ae) if want_target else (loss, a, r, t, ae)
 
 
 def ac_gae(reward, terminal, value, gamma=0.99, gae_lambda=0.95):
@@ -1497,7 +1533,7 @@ class AcRolloutStep:
 
 
 def _bind_step(self, name, arch, need, env, replay, net, batch, gamma, flat_grad, n_loss, prioritized=False):
-    """what SacStep, IqnStep and IqnPerStep set up alike: the checks, the step's own tensors (loss: f32[n_loss]) and the bound pointers;
+    """what SacStep, SacPerStep, IqnStep and IqnPerStep set up alike: the checks, the step's own tensors (loss: f32[n_loss]) and the bound pointers;
     prioritized: a prioritized memory instead of a uniform one, and Memory.sample's weights (f64 and f32) and abs_err beside them"""
     if net.arch not in (arch if isinstance(arch, tuple) else (arch,)):
         raise ValueError(f"{name} needs {need}")
@@ -1532,16 +1568,26 @@ class SacStep:
     """One whole step of the SAC loop as a single host call (fb_sac_step): sample the policy -> frame_step -> store + sample the
     minibatch -> (train) the SAC step from the ring -> (polyak > 0) the soft target update.  The results of the separate calls in that
     order; the pointers are bound once."""
+    entry, prioritized = "fb_sac_step", False
 
     def __init__(self, env, replay, net, batch=32, gamma=0.99, polyak=0.005, flat_grad=None):
-        _bind_step(self, "SacStep", SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", env, replay, net, batch, gamma, flat_grad, 6)
+        _bind_step(self, type(self).__name__, SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", env, replay, net, batch, gamma, flat_grad, 6,
+                   prioritized=self.prioritized)
         self.rho = check_polyak(polyak, allow_off=True)
 
     def __call__(self, seed=0, step=0, train=True):
         """-> actions uint8[N] (device); rewards / terminals / scores are the env's tensors, the six loss numbers are self.loss"""
-        L.check(L.lib().fb_sac_step(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, self.batch, int(seed), int(step),
-                                    int(bool(train)), self.gamma, self.rho, L.current_stream()), "fb_sac_step")
+        L.check(getattr(L.lib(), self.entry)(self.env.h, self.replay.h, self.net.h, C.byref(self.buf), self.env.n, self.batch, int(seed), int(step),
+                                            int(bool(train)), self.gamma, self.rho, L.current_stream()), self.entry)
         return self.actions
+
+
+class SacPerStep(SacStep):
+    """SacStep on a prioritized memory (fb_sac_per_step): sample the policy -> frame_step -> store -> (train) Memory.sample -> the
+    weighted SAC step from the ring -> Memory.batch_update with 0.5 (|d1| + |d2|) -> (polyak > 0) the soft target update, all in line on
+    one stream.  The results of the separate calls in that order; it owns idx, isw (f64), isw32 and abs_err (as the loss left it).  On a
+    memory made with n_step > 1 a training step needs n pushes at its draw: the first n - 1 steps are store-only (train=False)."""
+    entry, prioritized = "fb_sac_per_step", True
 
 
 class _IqnStep:

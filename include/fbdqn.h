@@ -783,6 +783,40 @@ int fb_qnet_sac_train_step(fb_qnet_t h, int batch, const uint8_t *s, const uint8
 int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
                              double gamma, float *loss /*f32[6]*/, float *q_target, float *flat_grad, void *stream);
 
+/* ------------------------------------------------------------------ prioritized SAC and n-step returns (Schaul et al. 2016; Horgan et al. 2018, Ape-X)
+ * The SAC step above on a PRIORITIZED memory (fb_replay_create / fb_replay_create_nstep with prioritized = 1), as calls of their own: the
+ * memory's kind never switches what a call does, and the uniform calls above keep refusing a prioritized memory and an n-step view.
+ * Everything not named here is the uniform step's, formula for formula.  With w_b = isw[b] (Memory.sample's importance weights, float32):
+ *   critics     targets, d_1 and d_2 unchanged.  dLoss/dQ_i(s, a) = ((2 d_i) / B) * w_b; the terms summed into m1 / m2 are (d_i * d_i) * w_b.
+ *               w is multiplied LAST in both, so w_b = 1 for every b gives the uniform step's bits in every output.  The weights are not
+ *               validated on the device, as in the other prioritized steps.  The dhf row takes the weight through dQ_i
+ *   actor, temperature   NOT weighted: L_pi, H, dLoss/dz_c and the temperature's Adam step (driven by mh, the unweighted mean entropy) are the
+ *               uniform step's.  The importance weights correct the critic's TD expectation under the skewed draw; the policy-improvement
+ *               step holds under any state distribution, and leaving it alone keeps the temperature's dynamics those of the uniform step
+ *   priority    abs_err[b] = 0.5f * (fabsf(d_1) + fabsf(d_2)), written UNWEIGHTED, in FB_ALGO_PER's |TD error| unit: the memory's own
+ *               (min(|e| + 0.01, 1))^0.6 applies unchanged (fb_replay_update_priorities)
+ *   n-step      on a prioritized memory made with n > 1 the ring delivers (R, done) and s' = the state n steps on:
+ *                 y = done ? R : R + Gamma * V'(s'),   Gamma = gamma^n as the memory forms it, R as r above
+ *               R is the ring's plain n-step return: the intermediate steps carry NO entropy bonus (the soft value enters at the bootstrap
+ *               alone).  fb_sac_per_train_from_replay's gamma must be the memory's; fb_qnet_sac_per_train_step, the gathered call,
+ *               takes Gamma from the caller.  The two agree bit for bit
+ *   loop step   fb_sac_per_step: every argument check of every call below comes first -- nothing is launched and no push is counted before a
+ *               refusal -- then, in this order on `stream`: fb_qnet_act_policy_nib (sampled) -> fb_env_step -> fb_replay_push -> if train:
+ *               fb_replay_sample_f32, fb_sac_per_train_from_replay on b->isw32 / b->abs_err, fb_replay_update_priorities with abs_err left as
+ *               the loss wrote it -> if rho > 0: fb_qnet_soft_sync_target(rho).  Each result is bit for bit that of the separate calls.
+ *               A training step before n pushes exist at its draw returns FB_ERR_STATE before any launch; train = 0 is a store-only step
+ *   refused     FB_ERR_INVALID before any launch or counter change: a net that is not a SAC net; a uniform memory; NULL isw or abs_err; the
+ *               batch, gamma and rho rules of the uniform calls
+ *   not offered uniform n-step SAC through the ring (the gathered route serves it: fb_replay_gather on an n-step view, then
+ *               fb_qnet_sac_train_step with Gamma); data-parallel SAC, bf16, noisy or distributional critics, riders, the split schedule; a
+ *               weighted actor term. */
+int fb_qnet_sac_per_train_step(fb_qnet_t h, int batch, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
+                               const float *isw /*f32[B]*/, double gamma, float *loss /*f32[6]*/, float *abs_err /*f32[B]*/,
+                               float *q_target, float *flat_grad, void *stream);
+int fb_sac_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *isw, uint8_t *a_out,
+                                 float *r_out, uint8_t *t_out, double gamma, float *loss, float *abs_err, float *q_target,
+                                 float *flat_grad, void *stream);
+
 /* ------------------------------------------------------------------ implicit quantile networks (IQN; Dabney, Ostrovski, Silver & Munos 2018)
  * The step after QR-DQN: the net learns the whole quantile function theta(s, a; tau), trains on sampled tau and can act under a distorted
  * risk measure (CVaR).  One GPU, fp32, a uniform memory at any n-step view.
@@ -1037,7 +1071,7 @@ typedef struct {
     uint8_t *s, *s2, *a, *t; float *r;              /* gathered minibatch: u8[B,80,80,4] x2, u8[B], u8[B], f32[B] */
     float *loss;                                    /* f32[1] out */
     float *flat_grad;                               /* f32[n_params] or NULL */
-    /* prioritized replay (algo = FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 and QR _PER algos; fb_iqn_per_step) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
+    /* prioritized replay (algo = FB_ALGO_PER, FB_ALGO_DOUBLE_PER, FB_ALGO_MDQN_PER, the C51 and QR _PER algos; fb_iqn_per_step, fb_sac_per_step) only, else NULL: Memory.sample's importance weights as it returns them (f64[B]) and as the
      * float32 placeholder takes them (f32[B]), and the |TD errors| Memory.batch_update receives (f32[B]).
      * With the reference-order tree and 4096 envs or more Memory.batch_update of a step runs on the memory's own side stream, beside the NEXT step's acting
      * forward (its result is first needed by that step's Memory.store, which follows it there): idx and abs_err are read after
@@ -1071,6 +1105,10 @@ int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_b
  * training step a, r, t, loss (f32[6]) and flat_grad (or NULL). */
 int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed, uint64_t step,
                 int train, double gamma, float rho, void *stream);
+/* The vector step of a SAC net on a prioritized memory (the prioritized SAC block above pins it): the buffers fb_sac_step reads (idx for a
+ * training step only), and for a training step isw, isw32 and abs_err as well. */
+int fb_sac_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed, uint64_t step,
+                    int train, double gamma, float rho, void *stream);
 /* The vector step of an IQN net (the IQN block above pins it): of *b it reads nib, actions, frame_bits, reward, terminal, score, idx, and for a
  * training step a, r, t, loss (f32[1]) and flat_grad (or NULL). */
 int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
