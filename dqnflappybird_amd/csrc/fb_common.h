@@ -299,12 +299,12 @@ void fb_sac_launch_loss(hipStream_t st, const SacLossArgs &L);
 void fb_sac_launch_per_loss(hipStream_t st, const SacPerLossArgs &L);
 void fb_sac_launch_grad(hipStream_t st, const SacGradArgs &L);
 int fb_qnet_is_sac(fb_qnet_t h);              // 1: a SAC net (fb_qnet_create_sac)
-// the checks of the two SAC training calls, `who` in the message; the ring-fed SAC train step behind fb_sac_train_from_replay's checks
+// the checks of the SAC training calls, `who` in the message; the ring-fed SAC train step behind the checks of `who` -- fb_sac_train_from_replay
+// (isw / abs_err NULL), or fb_sac_per_train_from_replay, the prioritized form (isw / abs_err f32[batch], both non-NULL).  gamma: the
+// bootstrap's discount
 int fb_qnet_sac_check_train(fb_qnet_t h, int batch, double gamma, const char *who);
-int fb_qnet_sac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream);
-// ... and the prioritized one behind fb_sac_per_train_from_replay's (isw / abs_err f32[batch], both non-NULL).  gamma: the bootstrap's discount
-int fb_qnet_sac_per_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const float *isw, double gamma, float *loss, float *abs_err,
-                               float *q_target, float *flat_grad, void *stream);
+int fb_qnet_sac_train_ring(fb_qnet_t h, int batch, const FbRingSrc *ring, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
+                           float *flat_grad, void *stream, const char *who);
 // ---- implicit quantile networks (FB_ARCH_IQN): the kernels live in fb_iqn.hip, a code object of their own; fb_qnet.hip fills these structs
 // and hands them to the launchers below.  off: the PLAIN layout (wq / bq = W_q b_q); io: the embedding behind it, W_e[64][FC] b_e[FC].
 // A fold block is [b_fc1 | phibar * W_q | b_q]: the plain layout from b_fc1 on, so `block - off.bf1` is read as a plain net's parameters
@@ -351,6 +351,10 @@ int fb_check_step_handles(fb_env_t env, fb_replay_t replay, fb_qnet_t net, int n
 int fb_check_uniform_n1(fb_replay_t replay, const char *who, const char *uniform_only, const char *reads);
 // fb_replay_ring_src, and W_fc1's planes re-split where the batch reads them (>= 256): what a ring-fed train call does behind its checks
 int fb_ring_src_fresh(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a, float *r, uint8_t *t, FbRingSrc *ring, void *stream);
+// the memory of the prioritized SAC and IQN calls (include/fbdqn.h: calls of their own, the memory's kind never switches what a call does;
+// `uniform_calls` names the family's uniform ones): a prioritized one, whose gamma the caller's is and whose tree holds a leaf once
+// `pushes_ahead` more pushes are counted (pushes_ahead < 0: a store-only step, which samples nothing)
+int fb_check_per_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who, const char *uniform_calls);
 int fb_env_num_envs(fb_env_t h);
 int fb_replay_num_envs(fb_replay_t h);
 int fb_replay_is_prioritized(fb_replay_t h);
@@ -382,3 +386,24 @@ int fb_replay_sample_f32(fb_replay_t h, int batch, const double *uniforms, int64
 int fb_replay_sample_rider(fb_replay_t h, int batch, int64_t *idx, FbSampleRider *rider, int pushes_ahead = 1);
 void fb_mt_init_genrand_host(FbMT *s, uint32_t seed);
 void fb_mt_init_by_array_host(FbMT *s, const uint32_t *key, int n);
+// ---- the fused steps of the replay-fed families (fb_sac_step, fb_iqn_step and their prioritized forms): check -> act -> fb_env_step ->
+// fb_step_store_train.  Every argument check of the calls a step makes is made before the first launch, so nothing is launched and no
+// push is counted before a refusal.
+// fb_check_step_buffers: what a step begins with, the handles and the buffers it writes.  The uniform step's push samples into b->idx
+// whether it trains or not; the prioritized one draws, and needs idx and the weights' buffers, only when it trains
+int fb_check_step_buffers(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int train, bool prioritized, const char *who);
+// what a step ends with (the soft update of SAC aside): the store and, when it trains, the family's ring-fed train call
+// train_call(isw, abs_err) -- uniform: fb_replay_push_sample, train_call(NULL, NULL); prioritized: Memory.store -> Memory.sample -> the
+// weighted loss -> Memory.batch_update, in line on `stream` at every env count; abs_err stays as the loss left it
+template <class TrainCall>
+static inline int fb_step_store_train(fb_replay_t replay, const fb_step_buffers *b, int batch, int train, bool prioritized, void *stream, TrainCall train_call) {
+    if (!prioritized) {
+        const int rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
+        return rc != FB_OK || !train ? rc : train_call(nullptr, nullptr);
+    }
+    int rc = fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, stream);
+    if (rc != FB_OK || !train) return rc;
+    rc = fb_replay_sample_f32(replay, batch, nullptr, b->idx, b->isw, b->isw32, stream);
+    if (rc == FB_OK) rc = train_call(b->isw32, b->abs_err);
+    return rc != FB_OK ? rc : fb_replay_update_priorities_keep(replay, batch, b->idx, b->abs_err, stream);
+}

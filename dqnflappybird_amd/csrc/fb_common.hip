@@ -171,6 +171,25 @@ int fb_ring_src_fresh(fb_replay_t replay, fb_qnet_t net, int batch, const int64_
     return fb_qnet_refresh_planes(net, stream);
 }
 
+int fb_check_per_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who, const char *uniform_calls) {
+    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (%s take a uniform one)", who, uniform_calls);
+    const int rc = fb_replay_check_gamma(replay, gamma, who);
+    return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
+}
+
+int fb_check_step_buffers(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int train, bool prioritized, const char *who) {
+    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
+    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && (prioritized || b->idx), "%s: NULL buffer", who);
+    if (!train) return FB_OK;
+    if (!prioritized) {
+        FB_REQUIRE(b->a && b->r && b->t && b->loss, "%s: a training step needs the a / r / t / loss buffers", who);
+        return FB_OK;
+    }
+    FB_REQUIRE(b->idx && b->a && b->r && b->t && b->loss, "%s: a training step needs the idx / a / r / t / loss buffers", who);
+    FB_REQUIRE(b->isw && b->isw32 && b->abs_err, "%s: the prioritized step needs the isw / isw32 / abs_err buffers", who);
+    return FB_OK;
+}
+
 // n x (random.sample -> minibatch -> _trainQNetwork) on a memory that is not being pushed to, as one host call.  Each step is the six
 // launches of the ring-fed train step (conv trunk of the 2B states straight from the 1-bit frame ring -> fc1 -> loss + fc1 backward ->
 // conv data gradients -> conv weight gradients -> Adam): no gather, no u8 minibatch.  Only the first draw gets a launch of its own: the

@@ -483,13 +483,9 @@ static int iqn_check_memory(fb_replay_t replay, double gamma, const char *who) {
     FB_REQUIRE(!fb_replay_is_prioritized(replay), "%s: IQN trains from a uniform memory only (prioritized replay is not offered)", who);
     return fb_replay_check_gamma(replay, gamma, who);
 }
-// the checks of the two prioritized ring-fed calls on the memory (include/fbdqn.h, the prioritized IQN block: calls of their own, the memory's
-// kind never switches what a call does): a prioritized one, at any n-step view, whose gamma the caller's is and whose tree holds a leaf once
-// `pushes_ahead` more pushes are counted (pushes_ahead < 0: a store-only step, which samples nothing)
+// ... and of the two prioritized ones: a prioritized one, at any n-step view (fb_check_per_memory)
 static int iqn_per_check_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who) {
-    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (fb_iqn_train_from_replay / fb_iqn_step take a uniform one)", who);
-    const int rc = fb_replay_check_gamma(replay, gamma, who);
-    return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
+    return fb_check_per_memory(replay, gamma, pushes_ahead, who, "fb_iqn_train_from_replay / fb_iqn_step");
 }
 
 // fb_iqn_train_from_replay (isw / abs_err NULL) and fb_iqn_per_train_from_replay (both set: the weights in, l_b out) behind their
@@ -528,60 +524,33 @@ extern "C" int fb_iqn_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, i
                                  q_target, flat_grad, stream);
 }
 
-// what fb_iqn_step and fb_iqn_per_step begin with: the handles and the buffers every step writes (need_idx: the uniform step's push samples
-// into b->idx whether it trains or not)
-static int iqn_step_begin(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, bool need_idx, const char *who) {
-    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
-    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && (!need_idx || b->idx), "%s: NULL buffer", who);
-    return FB_OK;
-}
-// ... and what both do behind their own checks of the buffers, the net and the memory: the handles' and the train call's checks -- every
-// argument check of the calls a step makes is made before the first launch, so nothing is launched and no push is counted before a
-// refusal -- then epsilon-greedy on the folded head and the env step.  The push is the caller's
-static int iqn_act_env_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
-                            uint64_t seed, uint64_t step, double gamma, void *stream, const char *who) {
-    int rc = fb_check_step_handles(env, replay, net, n_envs, who);
+// fb_iqn_step and fb_iqn_per_step (fb_common.h, the fused steps): the checks, epsilon-greedy on the folded head, the env step, the store
+// and the train call
+static int iqn_step(const char *who, bool prioritized, fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q,
+                    int batch, float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
+    int rc = fb_check_step_buffers(env, replay, net, b, train, prioritized, who);
+    if (rc != FB_OK) return rc;
+    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
+    // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
+    rc = prioritized ? iqn_per_check_memory(replay, gamma, train ? 1 : -1, who) : iqn_check_memory(replay, gamma, who);
+    if (rc == FB_OK) rc = fb_check_step_handles(env, replay, net, n_envs, who);
     if (rc == FB_OK) rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
     if (rc != FB_OK) return rc;
     rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
+    if (rc == FB_OK) rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
     if (rc != FB_OK) return rc;
-    return fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+    return fb_step_store_train(replay, b, batch, train, prioritized, stream, [&](const float *isw, float *abs_err) {
+        return iqn_train_from_replay(who, replay, net, double_q, batch, b->idx, isw, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss, abs_err,
+                                     nullptr, b->flat_grad, stream);
+    });
 }
 
 extern "C" int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,
                            uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
-    const char *who = "fb_iqn_step";
-    int rc = iqn_step_begin(env, replay, net, b, true, who);
-    if (rc != FB_OK) return rc;
-    FB_REQUIRE(!train || (b->a && b->r && b->t && b->loss), "%s: a training step needs the a / r / t / loss buffers", who);
-    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
-    rc = iqn_check_memory(replay, gamma, who);
-    if (rc == FB_OK) rc = iqn_act_env_step(env, replay, net, b, n_envs, double_q, batch, epsilon, seed, step, gamma, stream, who);
-    if (rc != FB_OK) return rc;
-    rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
-    if (rc != FB_OK || !train) return rc;
-    return fb_iqn_train_from_replay(replay, net, double_q, batch, b->idx, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss, nullptr,
-                                    b->flat_grad, stream);
+    return iqn_step("fb_iqn_step", false, env, replay, net, b, n_envs, double_q, batch, epsilon, seed, step, train, gamma, stream);
 }
 
 extern "C" int fb_iqn_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch,
                                float epsilon, uint64_t seed, uint64_t step, int train, double gamma, void *stream) {
-    const char *who = "fb_iqn_per_step";
-    int rc = iqn_step_begin(env, replay, net, b, false, who);
-    if (rc != FB_OK) return rc;
-    FB_REQUIRE(!train || (b->idx && b->a && b->r && b->t && b->loss), "%s: a training step needs the idx / a / r / t / loss buffers", who);
-    FB_REQUIRE(!train || (b->isw && b->isw32 && b->abs_err), "%s: the prioritized step needs the isw / isw32 / abs_err buffers", who);
-    FB_REQUIRE(fb_qnet_is_iqn(net), "%s: not an IQN net (fb_qnet_create_iqn)", who);
-    rc = iqn_per_check_memory(replay, gamma, train ? 1 : -1, who);      // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
-    if (rc == FB_OK) rc = iqn_act_env_step(env, replay, net, b, n_envs, double_q, batch, epsilon, seed, step, gamma, stream, who);
-    if (rc != FB_OK) return rc;
-    rc = fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, stream);
-    if (rc != FB_OK || !train) return rc;
-    // Memory.sample -> the weighted loss -> Memory.batch_update, in line on `stream` at every env count; abs_err keeps l_b as the loss left it
-    rc = fb_replay_sample_f32(replay, batch, nullptr, b->idx, b->isw, b->isw32, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_iqn_per_train_from_replay(replay, net, double_q, batch, b->idx, b->isw32, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss,
-                                      b->abs_err, nullptr, b->flat_grad, stream);
-    if (rc != FB_OK) return rc;
-    return fb_replay_update_priorities_keep(replay, batch, b->idx, b->abs_err, stream);
+    return iqn_step("fb_iqn_per_step", true, env, replay, net, b, n_envs, double_q, batch, epsilon, seed, step, train, gamma, stream);
 }

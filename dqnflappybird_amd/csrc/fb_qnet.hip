@@ -5792,52 +5792,37 @@ static Plan three_slice_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t 
     return p;
 }
 
-// (the uniform ring-fed SAC call takes a memory at n-step 1 only, the prioritized one the memory's n: fb_sac.hip)  isw / abs_err both set: the
-// prioritized form, the same plan with the importance weights in and the priority out (the loss launch's weighted instantiation), else both NULL
-static Plan sac_train_plan(fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t, double gamma,
-                           float *loss, float *q_target, float *flat_grad, const FbRingSrc *ring, const float *isw = nullptr, float *abs_err = nullptr) {
+// The SAC train step behind every entry point's NULL-argument checks (`who`: the one the messages name): gathered states (ring NULL) or the
+// ring-fed form; isw / abs_err both set: the prioritized form, the same plan with the importance weights in and the priority out (the loss
+// launch's weighted instantiation, fb_sac.hip), else both NULL.  The temperature update runs when the CALLER exports nothing and alpha_lr > 0
+// (the uniform ring-fed call takes a memory at n-step 1 only, the prioritized one the memory's n: fb_sac.hip)
+static int sac_train(const char *who, fb_qnet *h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
+                     const FbRingSrc *ring, const float *isw, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
+    const int rc = fb_qnet_sac_check_train(h, B, gamma, who);
+    if (rc != FB_OK) return rc;
     Plan p = three_slice_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, ring);
     p.sac_temp = flat_grad == nullptr && h->sac_alr > 0.f;
     p.isw = isw; p.abs_err = abs_err;
-    return p;
+    return ring ? run_train(h, p, stream) : run_train_gathered(h, p, B, stream);
 }
 
 extern "C" int fb_qnet_sac_train_step(fb_qnet_t h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
                                       double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
     FB_REQUIRE(h && s && a && r && s2 && t && loss, "fb_qnet_sac_train_step: NULL argument");
-    const int rc = fb_qnet_sac_check_train(h, B, gamma, "fb_qnet_sac_train_step");
-    if (rc != FB_OK) return rc;
-    Plan p = sac_train_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, nullptr);
-    return run_train_gathered(h, p, B, stream);
-}
-
-int fb_qnet_sac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
-    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss, "fb_sac_train_from_replay: NULL argument");
-    const int rc = fb_qnet_sac_check_train(h, B, gamma, "fb_sac_train_from_replay");
-    if (rc != FB_OK) return rc;
-    Plan p = sac_train_plan(h, B, nullptr, ring->a, ring->r, nullptr, ring->t, gamma, loss, q_target, flat_grad, ring);
-    return run_train(h, p, stream);
+    return sac_train("fb_qnet_sac_train_step", h, B, s, a, r, s2, t, nullptr, nullptr, gamma, loss, nullptr, q_target, flat_grad, stream);
 }
 
 extern "C" int fb_qnet_sac_per_train_step(fb_qnet_t h, int B, const uint8_t *s, const uint8_t *a, const float *r, const uint8_t *s2, const uint8_t *t,
                                           const float *isw, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
-    const char *who = "fb_qnet_sac_per_train_step";
-    FB_REQUIRE(h && s && a && r && s2 && t && loss, "%s: NULL argument", who);
-    FB_REQUIRE(isw && abs_err, "%s: the prioritized step needs the importance weights (isw) and abs_err", who);
-    const int rc = fb_qnet_sac_check_train(h, B, gamma, who);
-    if (rc != FB_OK) return rc;
-    Plan p = sac_train_plan(h, B, s, a, r, s2, t, gamma, loss, q_target, flat_grad, nullptr, isw, abs_err);
-    return run_train_gathered(h, p, B, stream);
+    FB_REQUIRE(h && s && a && r && s2 && t && loss, "fb_qnet_sac_per_train_step: NULL argument");
+    FB_REQUIRE(isw && abs_err, "fb_qnet_sac_per_train_step: the prioritized step needs the importance weights (isw) and abs_err");
+    return sac_train("fb_qnet_sac_per_train_step", h, B, s, a, r, s2, t, nullptr, isw, gamma, loss, abs_err, q_target, flat_grad, stream);
 }
 
-int fb_qnet_sac_per_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
-                               float *flat_grad, void *stream) {
-    const char *who = "fb_sac_per_train_from_replay";
-    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss && isw && abs_err, "%s: NULL argument", who);
-    const int rc = fb_qnet_sac_check_train(h, B, gamma, who);
-    if (rc != FB_OK) return rc;
-    Plan p = sac_train_plan(h, B, nullptr, ring->a, ring->r, nullptr, ring->t, gamma, loss, q_target, flat_grad, ring, isw, abs_err);
-    return run_train(h, p, stream);
+int fb_qnet_sac_train_ring(fb_qnet_t h, int B, const FbRingSrc *ring, const float *isw, double gamma, float *loss, float *abs_err, float *q_target,
+                           float *flat_grad, void *stream, const char *who) {
+    FB_REQUIRE(h && ring && ring->idx && ring->a && ring->r && ring->t && loss && !isw == !abs_err, "%s: NULL argument", who);
+    return sac_train(who, h, B, nullptr, ring->a, ring->r, nullptr, ring->t, ring, isw, gamma, loss, abs_err, q_target, flat_grad, stream);
 }
 
 // ---- implicit quantile networks (include/fbdqn.h; kernels: fb_iqn.hip)

@@ -262,60 +262,35 @@ void fb_sac_launch_grad(hipStream_t st, const SacGradArgs &L) {
     hipLaunchKernelGGL(sac_grad_kernel, dim3(L.FC / 16), dim3(256), 0, st, L);
 }
 
-// the memory checks of the two ring-fed SAC calls: a uniform memory at n-step 1
+// the memory of the two uniform ring-fed SAC calls: a uniform one at n-step 1
 static int sac_check_memory(fb_replay_t replay, const char *who) {
     return fb_check_uniform_n1(replay, who, "SAC trains from a uniform memory only (prioritized replay is not offered)", "SAC reads it");
 }
-// the memory checks of the two prioritized ring-fed SAC calls (include/fbdqn.h, the prioritized SAC block: calls of their own, the memory's
-// kind never switches what a call does): a prioritized one, at the n it was made with, whose gamma the caller's is and whose tree holds a
-// leaf once `pushes_ahead` more pushes are counted (pushes_ahead < 0: a store-only step, which samples nothing)
+// ... and of the two prioritized ones: a prioritized one, at the n it was made with (fb_check_per_memory)
 static int sac_per_check_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who) {
-    FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (fb_sac_train_from_replay / fb_sac_step take a uniform one)", who);
-    const int rc = fb_replay_check_gamma(replay, gamma, who);
-    return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
+    return fb_check_per_memory(replay, gamma, pushes_ahead, who, "fb_sac_train_from_replay / fb_sac_step");
 }
 
-extern "C" int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
-                                        double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
-    const char *who = "fb_sac_train_from_replay";
-    FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
+// fb_sac_train_from_replay (isw / abs_err NULL) and fb_sac_per_train_from_replay (both set: the weights in, the priority out) behind their
+// NULL-argument checks: the net, the memory of the call's kind, the train step's own checks, then the step on the ring
+static int sac_train_from_replay(const char *who, fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *isw, uint8_t *a_out,
+                                 float *r_out, uint8_t *t_out, double gamma, float *loss, float *abs_err, float *q_target, float *flat_grad, void *stream) {
     FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
-    int rc = sac_check_memory(replay, who);
+    int rc = isw ? sac_per_check_memory(replay, gamma, 0, who) : sac_check_memory(replay, who);
     if (rc != FB_OK) return rc;
     rc = fb_qnet_sac_check_train(net, batch, gamma, who);
     if (rc != FB_OK) return rc;
     FbRingSrc ring;
     rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
     if (rc != FB_OK) return rc;
-    return fb_qnet_sac_train_ring(net, batch, &ring, gamma, loss, q_target, flat_grad, stream);
+    return fb_qnet_sac_train_ring(net, batch, &ring, isw, fb_replay_bootstrap_gamma(replay, gamma), loss, abs_err, q_target, flat_grad, stream, who);
 }
 
-extern "C" int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed, uint64_t step,
-                           int train, double gamma, float rho, void *stream) {
-    const char *who = "fb_sac_step";
-    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
-    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score && b->idx, "%s: NULL buffer", who);
-    FB_REQUIRE(!train || (b->a && b->r && b->t && b->loss), "%s: a training step needs the a / r / t / loss buffers", who);
-    FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
-    int rc = sac_check_memory(replay, who);
-    if (rc != FB_OK) return rc;
-    rc = fb_check_step_handles(env, replay, net, n_envs, who);
-    if (rc == FB_OK) rc = fb_qnet_sac_check_train(net, batch, gamma, who);
-    if (rc != FB_OK) return rc;
-    FB_REQUIRE(rho >= 0.f && rho <= 1.f, "%s: rho must be in [0, 1] (0 = no target update; got %g)", who, (double)rho);
-    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
-    rc = fb_qnet_act_policy_nib(net, b->nib, n_envs, seed, step, 0, b->actions, nullptr, nullptr, nullptr, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
-    if (rc != FB_OK) return rc;
-    if (train) {
-        rc = fb_sac_train_from_replay(replay, net, batch, b->idx, b->a, b->r, b->t, gamma, b->loss, nullptr, b->flat_grad, stream);
-        if (rc != FB_OK) return rc;
-    }
-    if (rho > 0.f) rc = fb_qnet_soft_sync_target(net, rho, stream);
-    return rc;
+extern "C" int fb_sac_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, uint8_t *a_out, float *r_out, uint8_t *t_out,
+                                        double gamma, float *loss, float *q_target, float *flat_grad, void *stream) {
+    const char *who = "fb_sac_train_from_replay";
+    FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
+    return sac_train_from_replay(who, replay, net, batch, idx, nullptr, a_out, r_out, t_out, gamma, loss, nullptr, q_target, flat_grad, stream);
 }
 
 extern "C" int fb_sac_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, int batch, const int64_t *idx, const float *isw, uint8_t *a_out, float *r_out,
@@ -323,46 +298,36 @@ extern "C" int fb_sac_per_train_from_replay(fb_replay_t replay, fb_qnet_t net, i
     const char *who = "fb_sac_per_train_from_replay";
     FB_REQUIRE(replay && net && idx && a_out && r_out && t_out && loss, "%s: NULL argument", who);
     FB_REQUIRE(isw && abs_err, "%s: the prioritized step needs the importance weights (isw) and abs_err", who);
-    FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
-    int rc = sac_per_check_memory(replay, gamma, 0, who);
-    if (rc != FB_OK) return rc;
-    rc = fb_qnet_sac_check_train(net, batch, gamma, who);
-    if (rc != FB_OK) return rc;
-    FbRingSrc ring;
-    rc = fb_ring_src_fresh(replay, net, batch, idx, a_out, r_out, t_out, &ring, stream);
-    if (rc != FB_OK) return rc;
-    return fb_qnet_sac_per_train_ring(net, batch, &ring, isw, fb_replay_bootstrap_gamma(replay, gamma), loss, abs_err, q_target, flat_grad, stream);
+    return sac_train_from_replay(who, replay, net, batch, idx, isw, a_out, r_out, t_out, gamma, loss, abs_err, q_target, flat_grad, stream);
 }
 
-extern "C" int fb_sac_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed,
-                               uint64_t step, int train, double gamma, float rho, void *stream) {
-    const char *who = "fb_sac_per_step";
-    FB_REQUIRE(env && replay && net && b, "%s: NULL handle", who);
-    FB_REQUIRE(b->nib && b->actions && b->frame_bits && b->reward && b->terminal && b->score, "%s: NULL buffer", who);
-    FB_REQUIRE(!train || (b->idx && b->a && b->r && b->t && b->loss), "%s: a training step needs the idx / a / r / t / loss buffers", who);
-    FB_REQUIRE(!train || (b->isw && b->isw32 && b->abs_err), "%s: the prioritized step needs the isw / isw32 / abs_err buffers", who);
+// fb_sac_step and fb_sac_per_step (fb_common.h, the fused steps): the checks, the policy's draw, the env step, the store and the train
+// call, the soft target update
+static int sac_step(const char *who, bool prioritized, fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch,
+                    uint64_t seed, uint64_t step, int train, double gamma, float rho, void *stream) {
+    int rc = fb_check_step_buffers(env, replay, net, b, train, prioritized, who);
+    if (rc != FB_OK) return rc;
     FB_REQUIRE(fb_qnet_is_sac(net), "%s: not a SAC net (fb_qnet_create_sac)", who);
-    int rc = sac_per_check_memory(replay, gamma, train ? 1 : -1, who);  // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
+    // (a prioritized n-step memory samples after this step's push: it needs n pushes by then)
+    rc = prioritized ? sac_per_check_memory(replay, gamma, train ? 1 : -1, who) : sac_check_memory(replay, who);
     if (rc == FB_OK) rc = fb_check_step_handles(env, replay, net, n_envs, who);
     if (rc == FB_OK) rc = fb_qnet_sac_check_train(net, batch, gamma, who);
     if (rc != FB_OK) return rc;
     FB_REQUIRE(rho >= 0.f && rho <= 1.f, "%s: rho must be in [0, 1] (0 = no target update; got %g)", who, (double)rho);
-    // (every argument check of the calls below is made above, so nothing is launched and no push is counted before a refusal)
     rc = fb_qnet_act_policy_nib(net, b->nib, n_envs, seed, step, 0, b->actions, nullptr, nullptr, nullptr, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
-    if (rc != FB_OK) return rc;
-    rc = fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, stream);
-    if (rc != FB_OK) return rc;
-    if (train) {
-        // Memory.sample -> the weighted loss -> Memory.batch_update, in line on `stream` at every env count; abs_err stays as the loss left it
-        rc = fb_replay_sample_f32(replay, batch, nullptr, b->idx, b->isw, b->isw32, stream);
-        if (rc != FB_OK) return rc;
-        rc = fb_sac_per_train_from_replay(replay, net, batch, b->idx, b->isw32, b->a, b->r, b->t, gamma, b->loss, b->abs_err, nullptr, b->flat_grad, stream);
-        if (rc != FB_OK) return rc;
-        rc = fb_replay_update_priorities_keep(replay, batch, b->idx, b->abs_err, stream);
-        if (rc != FB_OK) return rc;
-    }
-    if (rho > 0.f) rc = fb_qnet_soft_sync_target(net, rho, stream);
-    return rc;
+    if (rc == FB_OK) rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
+    if (rc == FB_OK) rc = fb_step_store_train(replay, b, batch, train, prioritized, stream, [&](const float *isw, float *abs_err) {
+        return sac_train_from_replay(who, replay, net, batch, b->idx, isw, b->a, b->r, b->t, gamma, b->loss, abs_err, nullptr, b->flat_grad, stream);
+    });
+    return rc != FB_OK || rho <= 0.f ? rc : fb_qnet_soft_sync_target(net, rho, stream);
+}
+
+extern "C" int fb_sac_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed, uint64_t step,
+                           int train, double gamma, float rho, void *stream) {
+    return sac_step("fb_sac_step", false, env, replay, net, b, n_envs, batch, seed, step, train, gamma, rho, stream);
+}
+
+extern "C" int fb_sac_per_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int batch, uint64_t seed,
+                               uint64_t step, int train, double gamma, float rho, void *stream) {
+    return sac_step("fb_sac_per_step", true, env, replay, net, b, n_envs, batch, seed, step, train, gamma, rho, stream);
 }

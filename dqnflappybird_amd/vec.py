@@ -886,41 +886,41 @@ class QNet:
                 "fb_qnet_forward_sac")
         return z, q1, q2
 
-    def sac_train_step(self, s, a, r, s2, t, gamma=0.99, flat_grad=None, want_target=True):
-        """one SAC step on <= 256 gathered transitions (fb_qnet_sac_train_step).  flat_grad=None applies Adam (and, with alpha_lr > 0,
-        the temperature's step); a float32[n_params] tensor receives the gradient instead.
-        -> (loss f32[6]: total, mean d1^2, mean d2^2, mean L_pi, mean entropy, the alpha used; q_target f32[B] or None)"""
-        self._need_sac("sac_train_step")
-        _dev_check(s, a, r, s2, t, flat_grad)
+    def _sac_train_step(self, what, s, a, r, s2, t, isw, gamma, flat_grad, want_target):
+        """sac_train_step, and with `what` == 'sac_per_train_step' its prioritized form (isw in, abs_err out)
+        -> (loss f32[6], q_target f32[B] or None, abs_err f32[B] or None)"""
+        weighted = what == "sac_per_train_step"
+        self._need_sac(what)
+        _dev_check(s, a, r, s2, t, isw, flat_grad)
         for name, x in (("s", s), ("s2", s2)):
             _check_states(name, x, s.shape[0])
         B = s.shape[0]
         check_sac_batch(B, a, r, t, flat_grad, self.n_params)
+        if weighted:
+            check_isw(B, isw)
         loss = torch.zeros(6, dtype=torch.float32, device=self.device)
+        ae = torch.empty(B, dtype=torch.float32, device=self.device) if weighted else None
         y = torch.empty(B, dtype=torch.float32, device=self.device) if want_target else None
-        L.check(L.lib().fb_qnet_sac_train_step(self.h, B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), float(gamma), L.ptr(loss), L.ptr(y),
-                                               L.ptr(flat_grad), L.current_stream()), "fb_qnet_sac_train_step")
-        return loss, y
+        batch = (self.h, B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t))
+        out = (L.ptr(y), L.ptr(flat_grad), L.current_stream())
+        if weighted:
+            L.check(L.lib().fb_qnet_sac_per_train_step(*batch, L.ptr(isw), float(gamma), L.ptr(loss), L.ptr(ae), *out), "fb_qnet_sac_per_train_step")
+        else:
+            L.check(L.lib().fb_qnet_sac_train_step(*batch, float(gamma), L.ptr(loss), *out), "fb_qnet_sac_train_step")
+        return loss, y, ae
+
+    def sac_train_step(self, s, a, r, s2, t, gamma=0.99, flat_grad=None, want_target=True):
+        """one SAC step on <= 256 gathered transitions (fb_qnet_sac_train_step).  flat_grad=None applies Adam (and, with alpha_lr > 0,
+        the temperature's step); a float32[n_params] tensor receives the gradient instead.
+        -> (loss f32[6]: total, mean d1^2, mean d2^2, mean L_pi, mean entropy, the alpha used; q_target f32[B] or None)"""
+        return QNet._sac_train_step(self, "sac_train_step", s, a, r, s2, t, None, gamma, flat_grad, want_target)[:2]
 
     def sac_per_train_step(self, s, a, r, s2, t, isw, gamma=0.99, flat_grad=None, want_target=True):
         """sac_train_step with importance weights isw f32[B] (fb_qnet_sac_per_train_step): both critic terms and their gradients are
         weighted by w_b, the actor term, the entropy and the temperature's step are not; abs_err[b] = 0.5 (|d1| + |d2|), without the
         weight, is the priority.  isw = 1 gives sac_train_step's bits.  On n-step transitions gamma is the bootstrap's gamma^n.
         -> (loss f32[6], q_target f32[B] or None, abs_err f32[B])"""
-        self._need_sac("sac_per_train_step")
-        _dev_check(s, a, r, s2, t, isw, flat_grad)
-        for name, x in (("s", s), ("s2", s2)):
-            _check_states(name, x, s.shape[0])
-        B = s.shape[0]
-        check_sac_batch(B, a, r, t, flat_grad, self.n_params)
-        check_isw(B, isw)
-        loss = torch.zeros(6, dtype=torch.float32, device=self.device)
-        ae = torch.empty(B, dtype=torch.float32, device=self.device)
-        y = torch.empty(B, dtype=torch.float32, device=self.device) if want_target else None
-        L.check(L.lib().fb_qnet_sac_per_train_step(self.h, B, L.ptr(s), L.ptr(a), L.ptr(r), L.ptr(s2), L.ptr(t), L.ptr(isw), float(gamma),
-                                                   L.ptr(loss), L.ptr(ae), L.ptr(y), L.ptr(flat_grad), L.current_stream()),
-                "fb_qnet_sac_per_train_step")
-        return loss, y, ae
+        return QNet._sac_train_step(self, "sac_per_train_step", s, a, r, s2, t, isw, gamma, flat_grad, want_target)
 
     # -- implicit quantile networks (arch='iqn') -----------------------------------------
     def _need_iqn(self, what):
@@ -1209,7 +1209,7 @@ def check_ac_batch(B, a, adv, ret, n_total, flat_grad, n_params):
 
 
 def check_sac_batch(B, a, r, t, flat_grad, n_params, what="a SAC batch"):
-    """the shape checks of the two SAC training calls, on the host"""
+    """the shape checks of the SAC training calls, on the host"""
     if not 1 <= B <= 256:
         raise ValueError(f"{what} holds 1..256 samples, got {B}")
     for name, x, dt in (("a", a, torch.uint8), ("r", r, torch.float32), ("t", t, torch.uint8)):
@@ -1303,15 +1303,31 @@ def iqn_per_train_from_replay(replay, net, idx, isw, gamma=0.99, double_q=False,
     return (loss, a, r, t, y, ae) if want_target else (loss, a, r, t, ae)
 
 
+def _sac_train_from_replay(name, replay, net, idx, isw, gamma, flat_grad, want_target):
+    """sac_train_from_replay, and with `name` == 'sac_per_train_from_replay' its prioritized form (a prioritized memory, isw in, abs_err out)
+    -> (loss f32[6], a u8[B], r f32[B], t u8[B], q_target f32[B] or None, abs_err f32[B] or None)"""
+    weighted = name == "sac_per_train_from_replay"
+    B, dev, a, loss = _ring_call(name, replay, net, SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", "trains from", idx, 6, flat_grad, isw, prioritized=weighted)
+    check_sac_batch(B, None, None, None, flat_grad, net.n_params)
+    if weighted:
+        check_isw(B, isw)
+    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    ae = torch.empty(B, dtype=torch.float32, device=dev) if weighted else None
+    y = torch.empty(B, dtype=torch.float32, device=dev) if want_target else None
+    batch = (replay.h, net.h, B, L.ptr(idx))
+    art = (L.ptr(a), L.ptr(r), L.ptr(t), float(gamma), L.ptr(loss))
+    out = (L.ptr(y), L.ptr(flat_grad), L.current_stream())
+    if weighted:
+        L.check(L.lib().fb_sac_per_train_from_replay(*batch, L.ptr(isw), *art, L.ptr(ae), *out), "fb_sac_per_train_from_replay")
+    else:
+        L.check(L.lib().fb_sac_train_from_replay(*batch, *art, *out), "fb_sac_train_from_replay")
+    return loss, a, r, t, y, ae
+
+
 def sac_train_from_replay(replay, net, idx, gamma=0.99, flat_grad=None, want_target=False):
     """QNet.sac_train_step on the transitions at the deque positions idx of a uniform memory at n-step 1, read from its frame ring in
     place (fb_sac_train_from_replay) -> (loss f32[6], a u8[B], r f32[B], t u8[B][, q_target f32[B]])"""
-    B, dev, a, loss = _ring_call("sac_train_from_replay", replay, net, SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", "trains from", idx, 6, flat_grad)
-    check_sac_batch(B, None, None, None, flat_grad, net.n_params)
-    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
-    y = torch.empty(B, dtype=torch.float32, device=dev) if want_target else None
-    L.check(L.lib().fb_sac_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(a), L.ptr(r), L.ptr(t), float(gamma), L.ptr(loss), L.ptr(y),
-                                             L.ptr(flat_grad), L.current_stream()), "fb_sac_train_from_replay")
+    loss, a, r, t, y, _ = _sac_train_from_replay("sac_train_from_replay", replay, net, idx, None, gamma, flat_grad, want_target)
     return (loss, a, r, t, y) if want_target else (loss, a, r, t)
 
 
@@ -1319,15 +1335,7 @@ def sac_per_train_from_replay(replay, net, idx, isw, gamma=0.99, flat_grad=None,
     """QNet.sac_per_train_step on the transitions at the SumTree leaves idx of a prioritized memory (at the n it was made with; gamma
     must be the memory's), read from its frame ring in place (fb_sac_per_train_from_replay); isw f32[B]: replay.sample's importance
     weights -> (loss f32[6], a u8[B], r f32[B], t u8[B][, q_target f32[B]], abs_err f32[B])"""
-    B, dev, a, loss = _ring_call("sac_per_train_from_replay", replay, net, SAC_ARCH, "a SAC net (QNet(..., arch='sac'))", "trains from", idx, 6,
-                                 flat_grad, isw, prioritized=True)
-    check_sac_batch(B, None, None, None, flat_grad, net.n_params)
-    check_isw(B, isw)
-    r, t = torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
-    ae = torch.empty(B, dtype=torch.float32, device=dev)
-    y = torch.empty(B, dtype=torch.float32, device=dev) if want_target else None
-    L.check(L.lib().fb_sac_per_train_from_replay(replay.h, net.h, B, L.ptr(idx), L.ptr(isw), L.ptr(a), L.ptr(r), L.ptr(t), float(gamma), L.ptr(loss),
-                                                 L.ptr(ae), L.ptr(y), L.ptr(flat_grad), L.current_stream()), "fb_sac_per_train_from_replay")
+    loss, a, r, t, y, ae = _sac_train_from_replay("sac_per_train_from_replay", replay, net, idx, isw, gamma, flat_grad, want_target)
     return (loss, a, r, t, y, ae) if want_target else (loss, a, r, t, ae)
 
 
