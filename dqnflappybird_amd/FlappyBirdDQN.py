@@ -27,6 +27,9 @@ and the getAction -> frame_step -> preprocess -> setPerception loop, on the MI35
                                                                                        in place of the periodic copy)
     python -m dqnflappybird_amd.FlappyBirdDQN --model rainbow --vec 1024 --n-step 3 --noisy --acting-noise env
                                                                                       (... acting with independent noise per env)
+    python -m dqnflappybird_amd.FlappyBirdDQN --model rainbowiqn --dueling --vec 1024 --n-step 3 --sigma0 0.5 --acting-noise env
+                                                                                      (full Rainbow-IQN: noisy fc1 and head layers on the
+                                                                                       IQN net at sigma0 0.5, epsilon 0; --sigma0 takes any IQN model)
 
 `actorcritic` / `policygradient` are out of scope (broken in the reference).
 """
@@ -113,7 +116,10 @@ def build_parser():
                                                                       "1 = the reference's one-step TD)")
     parser.add_argument("--noisy", action="store_true", help="noisy fc1 and head layers, epsilon 0 (--model c51 | c51per | c51doubleper | rainbow, --vec)")
     parser.add_argument("--acting-noise", choices=("shared", "env"), default="shared",
-                        help="--noisy: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
+                        help="--noisy / --sigma0: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
+    parser.add_argument("--sigma0", type=float, default=None, metavar="S",
+                        help="--model iqn | iqnper | rainbowiqn: noisy fc1 and head layers at sigma0 = S (0.5 is Fortunato et al.'s), epsilon 0; "
+                             "--model rainbowiqn --dueling --n-step 3 --sigma0 0.5 --acting-noise env is full Rainbow-IQN")
     parser.add_argument("--n-quantiles", type=int, default=None, help="QR models: the number of quantiles N (default 51)")
     parser.add_argument("--kappa", type=float, default=None, help="QR models and --model iqn: the quantile Huber loss's threshold (default 1)")
     parser.add_argument("--n-tau", type=int, default=None, help="--model iqn: quantile fractions sampled per transition for the online net N (default 8)")
@@ -203,6 +209,9 @@ def iqn_kwargs(args, parser):
     if args.model not in IQN_MODELS:
         if given:
             parser.error(f"{' / '.join(given)} need --model iqn, not --model {args.model}")
+        if args.sigma0 is not None:
+            parser.error(f"--sigma0 needs an IQN model ({', '.join(IQN_MODELS)}), not --model {args.model}"
+                         + (" (its noisy layers are --noisy, at sigma0 0.5)" if args.model in ("c51", "c51per", "c51doubleper", "rainbow") else ""))
         return None
     if not args.vec:
         parser.error(f"--model {args.model} needs --vec: implicit quantile networks run in the vectorised loop only")
@@ -211,6 +220,8 @@ def iqn_kwargs(args, parser):
         if on:
             parser.error(f"{name} is not an option of --model {args.model} (--n-tau, --n-tau-target, --n-tau-act, --kappa, --cvar, --double, --n-step, "
                          "--polyak, --max-grad-norm are)")
+    if args.acting_noise != "shared" and args.sigma0 is None:
+        parser.error(f"--acting-noise {args.acting_noise} needs --noisy (the IQN models' noisy layers: --sigma0 S)")
     from .veciqn import check_args
     kw = dict(batch=min(32, args.vec), double_q=args.double or args.model == "rainbowiqn", n_step=args.n_step, n_tau=8 if args.n_tau is None else args.n_tau,
               n_tau_next=8 if args.n_tau_target is None else args.n_tau_target, n_tau_act=32 if args.n_tau_act is None else args.n_tau_act,
@@ -222,6 +233,13 @@ def iqn_kwargs(args, parser):
     except ValueError as e:
         parser.error(str(e))
     kw["prioritized"] = args.model != "iqn"
+    if args.sigma0 is not None:                          # (without the flag VecIQN's keywords are the ones of before)
+        from .veciqn import check_noisy
+        try:
+            _, s0, an = check_noisy(True, args.sigma0, args.acting_noise)
+        except ValueError as e:
+            parser.error(str(e).replace("sigma0 must", "--sigma0 must"))
+        kw.update(noisy=True, sigma0=s0, acting_noise=an)
     if args.dueling:                                     # (without the flag VecIQN's keywords are the ones of before)
         kw["dueling"] = True
     if args.munchausen:                                  # (the same; --tau is the softmax temperature, VecIQN's `temp`)

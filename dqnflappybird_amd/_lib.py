@@ -139,6 +139,7 @@ SIGNATURES = {
     "fb_sac_per_step": [_vp, _vp, _vp, _vp, _i, _i, _u64, _u64, _i, _d, _f, _vp],
     "fb_qnet_create_iqn": [_i, _i, _i, _i, _i, _f, _i, _vp],
     "fb_qnet_create_iqn_dueling": [_i, _i, _i, _i, _i, _f, _i, _vp],
+    "fb_qnet_create_iqn_noisy": [_i, _i, _i, _i, _i, _i, _f, _f, _i, _vp],
     "fb_qnet_set_iqn_risk": [_vp, _f],
     "fb_qnet_get_iqn": [_vp, _vp, _vp, _vp, _vp, _vp],
     "fb_qnet_set_iqn_munchausen": [_vp, _i, _f, _f, _f],

@@ -330,6 +330,26 @@ struct IqnLossArgs {
 // the net's.  mu = 0: none of the five is read
 struct IqnLossMuArgs : IqnLossArgs { int mu; float temp, alpha, clip_lo; int srow0; };
 struct IqnGradArgs { int B, FC, A, N; NetOff off; IqnOff io; const float *dl, *gw, *dhf, *dpre, *ctab; float *grad, *loss, *gmax; FbAdamHead *adam; int tick; int dueling; };
+// ---- noisy IQN nets (fb_qnet_create_iqn_noisy, include/fbdqn.h).  The fold launch's noisy variant takes IqnFoldArgs and, behind its last
+// field, pbar f32[FC]: phibar of the acting grid, which the per-env head scales sigma's head rows by (the plain launch keeps IqnFoldArgs)
+struct IqnFoldNzArgs : IqnFoldArgs { float *pbar; };
+// the fc1 stage of the per-env acting forward (fb_qnet.hip, the C51 and the IQN path alike): behind the argument checks it materialises
+// mu into the online net's effective vector, refolds, runs conv1 .. fc1 of the n nibble states and sigma's fc1 GEMM over the per-env scaled
+// activations.  *o: the mu fc1 partials hf[nks][stot][FC], sigma's t partials ht[FC1_SP_KS][stot][FC], sig with sigma of mu entry q at sig[q]
+struct FbEnvNoiseFc1 { const float *hf, *ht, *sig; int stot, nks, nkt; };      // nkt: the t partials (fb_qnet.hip's FC1_SP_KS)
+int fb_qnet_env_noise_fc1(fb_qnet_t h, const uint8_t *nib_states, int n, uint64_t seed, uint64_t step, FbEnvNoiseFc1 *o, void *stream);
+// the per-env scalar head (iqn_env_noise_head_kernel).  F / foff: the MU fold block (minus off.bf1) and its plain offsets; sig / off: sigma in
+// the net's own layout; nz and the e_* offsets: the noise vector's length and where fc1's eps_out, the V layer's and the Q / advantage
+// layer's eps_in / eps_out start in it; key_of (or NULL: the row) keys the noise and the epsilon draw, the latter on `stream`
+struct IqnEnvNoiseArgs {
+    const float *hf, *ht; int stot, nks, nkt;
+    const float *F; NetOff foff; const float *sig; NetOff off; const float *pbar;
+    int n, FC, A, nz, e_fc1_out, e_v_in, e_v_out, e_q_in, e_q_out;
+    float *q; uint8_t *actions; float epsilon; uint32_t seed_lo, seed_hi, step_lo, step_hi;
+    const int32_t *key_of; uint32_t stream; int dueling;
+};
+void fb_iqn_launch_fold_noisy(hipStream_t st, const IqnFoldNzArgs &F);
+void fb_iqn_launch_env_noise_head(hipStream_t st, const IqnEnvNoiseArgs &H);
 void fb_iqn_launch_fold(hipStream_t st, const IqnFoldArgs &F);
 void fb_iqn_launch_head(hipStream_t st, const IqnHeadArgs &H);
 void fb_iqn_launch_loss(hipStream_t st, const IqnLossMuArgs &L);

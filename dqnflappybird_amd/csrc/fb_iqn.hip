@@ -148,8 +148,10 @@ __device__ __forceinline__ void iqn_theta(const float *__restrict__ hf, int stot
 
 // ---- the fold of one net: 128 units per workgroup (FC % 128 == 0), a thread per unit
 // DU: [b_fc1 | phibar_k * We[k, a] | be[a]], the same plain layout
-template <bool DU>
-__global__ __launch_bounds__(128) void iqn_fold_kernel(IqnFoldArgs F) {
+// NZ, a noisy net (fb_qnet_create_iqn_noisy): phibar_k itself is left in F.pbar[k] as well, for the per-env head below.  NZ = false: the
+// statements and the argument block of before
+template <bool DU, bool NZ = false>
+__global__ __launch_bounds__(128) void iqn_fold_kernel(std::conditional_t<NZ, IqnFoldNzArgs, IqnFoldArgs> F) {
     __shared__ float ct[IQN_MAXT * IQN_E];
     __shared__ float tq[IQN_MAXT];
     const int tid = threadIdx.x, k = blockIdx.x * 128 + tid, K = F.K, FC = F.FC, A = F.A;
@@ -177,6 +179,7 @@ __global__ __launch_bounds__(128) void iqn_fold_kernel(IqnFoldArgs F) {
         sm += fmaxf(pre, 0.f);
     }
     const float pb = sm / (float)K;
+    if constexpr (NZ) F.pbar[k] = pb;
     F.fold[k] = bf;
     if constexpr (DU) {
 #pragma unroll
@@ -186,6 +189,134 @@ __global__ __launch_bounds__(128) void iqn_fold_kernel(IqnFoldArgs F) {
         for (int a = 0; a < A; a++) F.fold[FC + k * A + a] = pb * F.P[F.off.wq + k * A + a];
     }
     if (k < A) F.fold[FC + FC * A + k] = bq;
+}
+
+// ---- per-env acting noise on a noisy IQN net (fb_qnet_act_nib_env_noise, include/fbdqn.h): the scalar head of env e under ITS effective
+// weights, from the fc1 stage's two sets of partial sums.  One wave per env, eight envs per workgroup (env_noise_head_kernel's pattern,
+// fb_qnet.hip): the head's rows are the same for every env, so the workgroup stages the rows of 256 units -- the mu fold's, sigma's Q /
+// advantage layer's, (dueling) sigma's V layer's, and phibar -- in LDS at a time, coalesced, and each wave runs its chains from there.
+// Lane l owns the units 4 l .. 4 l + 3 of a stage, which is head_one_t's dealing (fb_head.h): the mu logit b_q[a] + sum_k h_k F[k, a] is
+// formed with that function's sums, in its order, so that sigma = 0 gives fb_qnet_act_nib's bits.  h_k = relu((mu partials + b_k) +
+// f(eo_k) (t_k + sigma_b_k)); the noise term of a layer, f(eo_a) (sum_k sigma_W[k, a] (h_k f(ei_k) phibar_k) + sigma_b[a]), is added
+// behind the mu logit -- dueling: nV + nA_a - (1/A) sum_c nA_c.  Draw k of env e: fb_qnet.hip's env_noise_f, Philox(key = seed, counter =
+// (e nz + k, step_lo, FB_STREAM_ENV_NOISE, step_hi)).  Plain stores, no atomics; no load under a branch (clamped addresses, masked values).
+// A draw is Philox, a logarithm and a full-range cosine: unrolled twelve times per stage it cost 256 VGPRs and scratch at AT = 8.  So a
+// thread forms its draws of a stage in ONE rolled loop and parks them in LDS words only it reads (dr: no barrier needed), and the FMA
+// chains read them back
+__device__ __forceinline__ float iqn_env_noise_f(uint32_t seed_lo, uint32_t seed_hi, uint32_t c0, uint32_t step_lo, uint32_t step_hi) {
+    const fb_u4 r = fb_philox(seed_lo, seed_hi, c0, step_lo, FB_STREAM_ENV_NOISE, step_hi);
+    const float u1 = ((r.x >> 8) + 1) * (1.0f / 16777216.0f), u2 = (r.y >> 8) * (1.0f / 16777216.0f);
+    const float z = sqrtf(-2.f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+    return copysignf(sqrtf(fabsf(z)), z);
+}
+constexpr int IEN_WAVES = 8, IEN_UC = 256;      // envs per workgroup; units per stage (one round of head_one_t)
+template <int AT, bool DU>
+__global__ __launch_bounds__(64 * IEN_WAVES) void iqn_env_noise_head_kernel(IqnEnvNoiseArgs H) {
+    constexpr int T = 64 * IEN_WAVES, PER = (IEN_UC * AT + T - 1) / T;
+    __shared__ __attribute__((aligned(16))) float lm[IEN_UC * AT];      // the mu fold's rows [unit][A]
+    __shared__ __attribute__((aligned(16))) float ls[IEN_UC * AT];      // sigma's Q / advantage rows [unit][A]
+    __shared__ float lv[DU ? IEN_UC : 1], lp[IEN_UC];                   // sigma's V row; phibar
+    constexpr int ND = DU ? 12 : 8;                                     // a thread's parked draws: 2 or 3 kinds x 4 units
+    __shared__ float dr[ND * T];
+    const int tid = threadIdx.x, lane = tid & 63, row = blockIdx.x * IEN_WAVES + (tid >> 6);
+    const bool live = row < H.n;
+    const int smp = live ? row : H.n - 1;                        // (a wave past n stages and waits with the others, stores nothing)
+    const int A = AT == MAXA ? H.A : AT, FC = H.FC;
+    const int key = H.key_of ? H.key_of[smp] : smp;
+    const uint32_t base = (uint32_t)key * (uint32_t)H.nz;
+    auto draw = [&](int k) { return iqn_env_noise_f(H.seed_lo, H.seed_hi, base + (uint32_t)k, H.step_lo, H.step_hi); };
+    float acc[AT], ns[AT], nv = 0.f;
+#pragma unroll
+    for (int a = 0; a < AT; a++) { acc[a] = 0.f; ns[a] = 0.f; }
+    for (int k0 = 0; k0 < FC; k0 += IEN_UC) {
+        const int cu = min(IEN_UC, FC - k0), cq = cu * A;          // this stage's units (FC % 128 == 0: 128 or 256) and row entries
+        const float *__restrict__ gm = H.F + H.foff.wq + (size_t)k0 * A, *__restrict__ gs = H.sig + H.off.wq + (size_t)k0 * A;
+        float tm[PER], ts[PER];
+#pragma unroll
+        for (int r = 0; r < PER; r++) { const int i = min(tid + r * T, cq - 1); tm[r] = gm[i]; ts[r] = gs[i]; }
+        const int iu = min(tid, cu - 1);
+        const float tp = H.pbar[k0 + iu], tv = DU ? H.sig[H.off.wv + k0 + iu] : 0.f;
+        // this lane's four units: fc1's mu sum (head_one_t's), sigma's t sum, the two biases
+        const bool ok = 4 * lane < cu;
+        const int j0 = k0 + (ok ? 4 * lane : 0);
+        float4 t[FC1_KS], tt[FC1_KS];
+#pragma unroll
+        for (int ks = 0; ks < FC1_KS; ks++) {
+            t[ks] = sel4(ks < H.nks, *reinterpret_cast<const float4 *>(H.hf + ((size_t)(ks < H.nks ? ks : 0) * H.stot + smp) * FC + j0));
+            tt[ks] = sel4(ks < H.nkt, *reinterpret_cast<const float4 *>(H.ht + ((size_t)(ks < H.nkt ? ks : 0) * H.stot + smp) * FC + j0));
+        }
+        const float4 bv = *reinterpret_cast<const float4 *>(H.F + H.foff.bf1 + j0);
+        float sb[4];
+#pragma unroll
+        for (int e = 0; e < 4; e++) sb[e] = H.sig[H.off.bf1 + j0 + e];
+        float4 v = t[0], u = tt[0];
+#pragma unroll
+        for (int ks = 1; ks < FC1_KS; ks++) {
+            v.x += t[ks].x; v.y += t[ks].y; v.z += t[ks].z; v.w += t[ks].w;
+            u.x += tt[ks].x; u.y += tt[ks].y; u.z += tt[ks].z; u.w += tt[ks].w;
+        }
+        const float pre[4] = {v.x + bv.x, v.y + bv.y, v.z + bv.z, v.w + bv.w}, tu[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll 1
+        for (int i = 0; i < ND; i++) {                 // f(eo) of fc1, f(ei) of the Q / advantage layer, (dueling) f(ei) of the V layer
+            const int kind = i >> 2, off = kind == 0 ? H.e_fc1_out : kind == 1 ? H.e_q_in : H.e_v_in;
+            dr[i * T + tid] = draw(off + j0 + (i & 3));
+        }
+        __syncthreads();                                          // (the previous stage's rows are no longer read)
+#pragma unroll
+        for (int r = 0; r < PER; r++) { const int i = tid + r * T; if (i < cq) { lm[i] = tm[r]; ls[i] = ts[r]; } }
+        if (tid < cu) { lp[tid] = tp; if (DU) lv[tid] = tv; }
+        __syncthreads();
+        if (ok) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int kl = 4 * lane + e;
+                const float x = fmaxf(pre[e] + dr[e * T + tid] * (tu[e] + sb[e]), 0.f);
+                const float xp = x * lp[kl], xq = xp * dr[(4 + e) * T + tid];
+#pragma unroll
+                for (int a = 0; a < AT; a++) {
+                    const int o = kl * A + (a < A ? a : 0);
+                    acc[a] = fmaf(x, lm[o], acc[a]);              // (columns a >= A are never read)
+                    ns[a] = fmaf(xq, ls[o], ns[a]);
+                }
+                if (DU) nv = fmaf(xp * dr[(8 + e) * T + tid], lv[kl], nv);
+            }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < AT; a++)
+        for (int o = 32; o > 0; o >>= 1) { acc[a] += __shfl_xor(acc[a], o); ns[a] += __shfl_xor(ns[a], o); }
+    if (DU) for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o);
+    // f(eo) of the Q / advantage layer's columns, then of the V layer's one: ONE draw per lane -- lane a < AT column a's, lane AT the V
+    // layer's (the lanes behind it repeat that one) -- handed round by shuffles
+    const float dout = draw(lane < AT ? H.e_q_out + (lane < A ? lane : 0) : H.e_v_out);
+    float qv[AT], nq[AT], mean = 0.f;
+#pragma unroll
+    for (int a = 0; a < AT; a++) {
+        const int c = a < A ? a : 0;
+        qv[a] = a < A ? acc[a] + H.F[H.foff.bq + c] : 0.f;
+        nq[a] = __shfl(dout, a) * (ns[a] + H.sig[H.off.bq + c]);
+        if (a < A) mean += nq[a];
+    }
+    if (DU) {
+        mean /= (float)A;
+        const float vn = __shfl(dout, AT) * (nv + H.sig[H.off.bv]);
+#pragma unroll
+        for (int a = 0; a < AT; a++) qv[a] += (vn + nq[a]) - mean;
+    } else {
+#pragma unroll
+        for (int a = 0; a < AT; a++) qv[a] += nq[a];
+    }
+    if (lane == 0 && live) {                                      // (head_one_t's)
+#pragma unroll
+        for (int a = 0; a < AT; a++) if (a < A) H.q[(size_t)smp * A + a] = qv[a];
+        int best = 0;
+#pragma unroll
+        for (int a = 1; a < AT; a++) if (a < A && qv[a] > qv[best]) best = a;
+        const fb_u4 o = fb_philox(H.seed_lo, H.seed_hi, (uint32_t)key, H.step_lo, H.stream, H.step_hi);
+        const float u = (float)(o.x >> 8) * (1.0f / 16777216.0f);
+        if (u <= H.epsilon) best = (int)(((unsigned long long)o.y * (unsigned)A) >> 32);
+        H.actions[smp] = (uint8_t)best;
+    }
 }
 
 // ---- fb_qnet_forward_iqn: one workgroup per state
@@ -446,6 +577,19 @@ void fb_iqn_launch_fold(hipStream_t st, const IqnFoldArgs &F) {
     with_bool(F.dueling != 0, [&](auto du) { hipLaunchKernelGGL(iqn_fold_kernel<decltype(du)::value>, dim3(F.FC / 128), dim3(128), 0, st, F); });
 }
 
+void fb_iqn_launch_fold_noisy(hipStream_t st, const IqnFoldNzArgs &F) {
+    with_bool(F.dueling != 0, [&](auto du) { hipLaunchKernelGGL((iqn_fold_kernel<decltype(du)::value, true>), dim3(F.FC / 128), dim3(128), 0, st, F); });
+}
+
+void fb_iqn_launch_env_noise_head(hipStream_t st, const IqnEnvNoiseArgs &H) {
+    with_actions(H.A, [&](auto a) {
+        with_bool(H.dueling != 0, [&](auto du) {
+            hipLaunchKernelGGL((iqn_env_noise_head_kernel<decltype(a)::value, decltype(du)::value>), dim3((H.n + IEN_WAVES - 1) / IEN_WAVES), dim3(64 * IEN_WAVES),
+                               0, st, H);
+        });
+    });
+}
+
 void fb_iqn_launch_head(hipStream_t st, const IqnHeadArgs &H) {
     with_actions(H.A, [&](auto a) {
         with_bool(H.dueling != 0, [&](auto du) {
@@ -535,14 +679,29 @@ static int iqn_step(const char *who, bool prioritized, fb_env_t env, fb_replay_t
     rc = prioritized ? iqn_per_check_memory(replay, gamma, train ? 1 : -1, who) : iqn_check_memory(replay, gamma, who);
     if (rc == FB_OK) rc = fb_check_step_handles(env, replay, net, n_envs, who);
     if (rc == FB_OK) rc = fb_qnet_iqn_check_train(net, double_q, batch, gamma, who);
+    // a noisy net (include/fbdqn.h, fb_vec_step's order).  Shared mode: the online net's sample of this step is drawn before acting, which
+    // reads it through the fold.  Per-env mode: the acting forward draws per env from mu and sigma, and the online sample is drawn behind
+    // the store (it also rebuilds what that forward left at mu).  The target net's sample is drawn in front of the train step
+    const bool noisy = fb_qnet_is_noisy(net) != 0, env_noise = noisy && fb_qnet_acting_noise(net) == FB_ACT_NOISE_PER_ENV;
+    if (rc == FB_OK && env_noise) rc = fb_qnet_check_env_noise(net, n_envs, who);
     if (rc != FB_OK) return rc;
-    rc = fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
+    if (noisy && !env_noise) rc = fb_qnet_reset_noise(net, 0, seed, step, FB_NOISE_SAMPLE, stream);
+    if (rc == FB_OK)
+        rc = env_noise ? fb_qnet_act_nib_env_noise_keep(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream)
+                       : fb_qnet_act_nib(net, b->nib, n_envs, epsilon, seed, step, b->actions, nullptr, stream);
     if (rc == FB_OK) rc = fb_env_step(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, stream);
     if (rc != FB_OK) return rc;
-    return fb_step_store_train(replay, b, batch, train, prioritized, stream, [&](const float *isw, float *abs_err) {
+    bool online_drawn = !env_noise;
+    rc = fb_step_store_train(replay, b, batch, train, prioritized, stream, [&](const float *isw, float *abs_err) {
+        int rn = FB_OK;
+        if (env_noise) { rn = fb_qnet_reset_noise(net, 0, seed, step, FB_NOISE_SAMPLE, stream); online_drawn = true; }
+        if (rn == FB_OK && noisy) rn = fb_qnet_reset_noise(net, 1, seed, step, FB_NOISE_SAMPLE, stream);
+        if (rn != FB_OK) return rn;
         return iqn_train_from_replay(who, replay, net, double_q, batch, b->idx, isw, b->a, b->r, b->t, nullptr, nullptr, seed, step, gamma, b->loss, abs_err,
                                      nullptr, b->flat_grad, stream);
     });
+    if (rc == FB_OK && !online_drawn) rc = fb_qnet_reset_noise(net, 0, seed, step, FB_NOISE_SAMPLE, stream);      // (a store-only step in the per-env mode)
+    return rc;
 }
 
 extern "C" int fb_iqn_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int double_q, int batch, float epsilon,

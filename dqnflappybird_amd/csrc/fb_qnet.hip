@@ -1965,7 +1965,8 @@ __global__ __launch_bounds__(256) void noise_draw_kernel(float *__restrict__ nz,
 
 // the effective parameters of a net from q0 on (0: the trunk changed as well).  ad (or NULL): a new parameter version for the W_fc1
 // planes the forward re-splits, the conv planes staying current if they were
-struct NoisyMat { const float *mst; float *eff; const float *nz; NoisyNet N; int q0, which; AdamDev *ad; };
+// ne: the end of the noisy range [OFF_WF1, ne) -- N.n, but for an IQN net, whose W_e b_e behind it have no sigma and are copied as the trunk is
+struct NoisyMat { const float *mst; float *eff; const float *nz; NoisyNet N; int q0, which; AdamDev *ad; int ne; };
 __global__ __launch_bounds__(256) void noisy_mat_kernel(NoisyMat a) {
     if (a.ad && blockIdx.x == 0 && threadIdx.x == 0) {
         const unsigned v = a.ad->pver[a.which];
@@ -1975,22 +1976,22 @@ __global__ __launch_bounds__(256) void noisy_mat_kernel(NoisyMat a) {
     const int q = a.q0 + blockIdx.x * 256 + threadIdx.x;
     if (q >= a.N.n) return;
     const float mu = a.mst[q];
-    if (q < OFF_WF1) { a.eff[q] = mu; return; }
+    if (q < OFF_WF1 || q >= a.ne) { a.eff[q] = mu; return; }
     const float s = a.mst[a.N.n + q - OFF_WF1], e = noisy_factor(a.N, a.nz, q);
     a.eff[q] = s == 0.f || e == 0.f ? mu : fmaf(s, e, mu);           // (exactly mu without noise)
 }
 
 // sigma's gradient, behind every gradient of the effective parameters: g[n + q - OFF_WF1] = g[q] e(q)
-__global__ __launch_bounds__(256) void noisy_sgrad_kernel(float *__restrict__ g, const float *__restrict__ nz, NoisyNet N) {
+__global__ __launch_bounds__(256) void noisy_sgrad_kernel(float *__restrict__ g, const float *__restrict__ nz, NoisyNet N, int ne) {
     const int q = OFF_WF1 + blockIdx.x * 256 + threadIdx.x;
-    if (q >= N.n) return;
+    if (q >= ne) return;
     g[N.n + q - OFF_WF1] = g[q] * noisy_factor(N, nz, q);
 }
 
 // sigma's initial values, sigma0 / sqrt(fan_in) per layer (weights and biases)
-__global__ __launch_bounds__(256) void noisy_sigma_init_kernel(float *__restrict__ p, NoisyNet N) {
+__global__ __launch_bounds__(256) void noisy_sigma_init_kernel(float *__restrict__ p, NoisyNet N, int ne) {
     const int q = OFF_WF1 + blockIdx.x * 256 + threadIdx.x;
-    if (q >= N.n) return;
+    if (q >= ne) return;
     p[N.n + q - OFF_WF1] = noisy_layer(N, q).sig;
 }
 
@@ -4029,6 +4030,11 @@ struct fb_qnet {
     // an actor-critic net: [dev] f32[6], the running sum of the last fb_ppo_epoch's chunk loss numbers (fb_ppo_epoch_sum).  Last, so that
     // every field above keeps the place it had
     float *ppo_sum;
+    // a noisy IQN net (fb_qnet_create_iqn_noisy): fc1 and the head layers are noisy as a noisy C51 net's (mst / nz / nnet above;
+    // iqn_off.we = noisy_end: W_e b_e have no sigma).  iqn_pbar[w]: phibar[FC] of net w's acting grid, left by the noisy fold launch for the per-env head
+    // noisy_end: where the noisy range [OFF_WF1, noisy_end) of any noisy net ends.  (Behind every field of before)
+    float *iqn_pbar[2];
+    int noisy_end;
 };
 
 static NetOff make_off(int FC, int A, int dueling) {      // A: the head's columns (C51: actions x atoms)
@@ -4069,7 +4075,8 @@ static const float *head_base(const fb_qnet *h, const float *params) {
 static void c51d_fold(fb_qnet *h, int which, hipStream_t st) {
     if (is_iqn(h)) {                             // (an IQN net: phibar over the acting grid and its fold block, fb_iqn.hip)
         const IqnFoldArgs F{h->params[which], h->heff[which], h->FC, h->A, h->iqn_k, h->off, h->iqn_off, h->iqn_eta, is_iqnd(h) ? 1 : 0};
-        fb_iqn_launch_fold(st, F);
+        if (h->noisy) fb_iqn_launch_fold_noisy(st, IqnFoldNzArgs{F, h->iqn_pbar[which]});      // (... and phibar itself, for the per-env head)
+        else fb_iqn_launch_fold(st, F);
         return;
     }
     if (!is_c51d(h)) return;
@@ -4084,7 +4091,7 @@ static float *master(const fb_qnet *h, int which) { return h->noisy ? h->mst[whi
 // version (noise only: the conv planes stay current).  No-op for other nets
 static void noisy_materialise(fb_qnet *h, int which, int q0, bool bump, hipStream_t st) {
     if (!h->noisy) return;
-    const NoisyMat a{h->mst[which], h->params[which], h->nz[which], h->nnet, q0, which, bump ? h->adam : nullptr};
+    const NoisyMat a{h->mst[which], h->params[which], h->nz[which], h->nnet, q0, which, bump ? h->adam : nullptr, h->noisy_end};
     hipLaunchKernelGGL(noisy_mat_kernel, dim3((unsigned)((h->n - q0 + 255) / 256)), dim3(256), 0, st, a);
 }
 // a noisy net whose online sigma the host replaced (init / load): the per-env acting path's sigma_W_fc1 planes are stale
@@ -4094,7 +4101,7 @@ static void env_noise_invalidate(fb_qnet *h, int which, hipStream_t st) {
 // a noisy net: sigma's gradient into g[n ..) from the effective parameters' gradient in g[OFF_WF1, n)
 static void noisy_sgrad(fb_qnet *h, float *g, hipStream_t st) {
     if (!h->noisy) return;
-    hipLaunchKernelGGL(noisy_sgrad_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, st, g, (const float *)h->nz[0], h->nnet);
+    hipLaunchKernelGGL(noisy_sgrad_kernel, dim3((unsigned)((h->noisy_end - OFF_WF1 + 255) / 256)), dim3(256), 0, st, g, (const float *)h->nz[0], h->nnet, h->noisy_end);
 }
 
 // What a net is made from.  Every fb_qnet_create* checks its arguments, fills one of these and hands it to qnet_create; nothing reaches the
@@ -4104,7 +4111,7 @@ struct NetSpec {
     C51Sup sup;                      // C51 nets: the support
     int n_quantiles;                 // QR nets: N
     float kappa;                     // QR and IQN nets: the quantile Huber loss's threshold
-    bool noisy; float sigma0;        // noisy C51 nets (fb_qnet_create_c51_noisy): finite sigma0 >= 0
+    bool noisy; float sigma0;        // noisy C51 / IQN nets (fb_qnet_create_c51_noisy / _iqn_noisy): finite sigma0 >= 0
     int n_tau, n_tau_next, n_tau_act;      // IQN nets: N, N', K
 };
 static NetSpec net_spec(int arch, int fc_width, int n_actions, int max_batch) {
@@ -4203,9 +4210,10 @@ extern "C" int fb_qnet_create_sac(int fc_width, int n_actions, int max_batch, fb
 
 // the checks of fb_qnet_create_iqn / _iqn_dueling, before any allocation (`fn` names the caller in the message)
 static int iqn_create(const char *fn, int arch, int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, int max_batch,
-                      fb_qnet_t *out) {
+                      fb_qnet_t *out, bool noisy = false, float sigma0 = 0.f) {
     NetSpec s = net_spec(arch, fc_width, n_actions, max_batch);
     if (const int rc = check_create(fn, s, 2, out, CREATE_OUT | CREATE_SHAPE)) return rc;
+    s.noisy = noisy; s.sigma0 = sigma0;
     FB_REQUIRE(n_tau >= 1 && n_tau <= 64, "%s: n_tau=%d outside 1..64", fn, n_tau);
     FB_REQUIRE(n_tau_next >= 1 && n_tau_next <= 64, "%s: n_tau_next=%d outside 1..64", fn, n_tau_next);
     FB_REQUIRE(n_tau_act >= 1 && n_tau_act <= 64, "%s: n_tau_act=%d outside 1..64", fn, n_tau_act);
@@ -4224,9 +4232,20 @@ extern "C" int fb_qnet_create_iqn_dueling(int fc_width, int n_actions, int n_tau
     return iqn_create("fb_qnet_create_iqn_dueling", FB_ARCH_IQN_DUELING, fc_width, n_actions, n_tau, n_tau_next, n_tau_act, kappa, max_batch, out);
 }
 
+// a noisy IQN net (include/fbdqn.h): fb_qnet_create_iqn's checks, then sigma0's, before any allocation
+extern "C" int fb_qnet_create_iqn_noisy(int dueling, int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, float sigma0,
+                                        int max_batch, fb_qnet_t *out) {
+    const char *fn = "fb_qnet_create_iqn_noisy";
+    FB_REQUIRE(out, "%s: out is NULL", fn);
+    FB_REQUIRE(dueling == 0 || dueling == 1, "%s: dueling must be 0 or 1 (got %d)", fn, dueling);
+    FB_REQUIRE(isfinite(sigma0) && sigma0 >= 0.f, "%s: sigma0 must be finite and >= 0 (got %g)", fn, (double)sigma0);
+    return iqn_create(fn, dueling ? FB_ARCH_IQN_DUELING : FB_ARCH_IQN, fc_width, n_actions, n_tau, n_tau_next, n_tau_act, kappa, max_batch, out, true, sigma0);
+}
+
 static int sac_write_words(fb_qnet *h, float alpha);
 
-// the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N)
+// the noise layers of a noisy net: fc1 (1600 -> FC), then the head's (C51: FC -> A N; dueling C51: FC -> N, FC -> A N; IQN: FC -> A; dueling
+// IQN: FC -> 1, FC -> A)
 static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, float sigma0) {
     NoisyNet nn;
     memset(&nn, 0, sizeof(nn));
@@ -4237,7 +4256,8 @@ static NoisyNet make_noisy(const NetOff &o, int arch, int FC, int A, int N, floa
     };
     add(OFF_WF1, 1600, FC);
     if (arch == FB_ARCH_C51_DUELING) add(o.wv, FC, N);
-    add(o.wq, FC, A * N);
+    if (arch == FB_ARCH_IQN_DUELING) add(o.wv, FC, 1);
+    add(o.wq, FC, N ? A * N : A);
     nn.n = o.n;
     return nn;
 }
@@ -4267,7 +4287,8 @@ static int qnet_create(const NetSpec &s, fb_qnet_t *out) {
     h->hoff = is_c51d(h) ? make_off(fc_width, n_actions * sup.N, 0) : is_iqnd(h) ? make_off(fc_width, n_actions, 0) : h->off;      // (a dueling IQN net: its fold's)
     h->n = h->off.n;
     h->noisy = s.noisy;
-    h->ntot = h->noisy ? 2 * h->n - OFF_WF1 : h->n;
+    h->noisy_end = is_iqn(h) ? h->iqn_off.we : (int)h->n;      // (where sigma's range [OFF_WF1, .) ends: an IQN net's W_e b_e have none)
+    h->ntot = h->noisy ? h->n + h->noisy_end - OFF_WF1 : h->n;
     if (h->noisy) h->nnet = make_noisy(h->off, arch, fc_width, n_actions, sup.N, s.sigma0);
     h->zmax = 64;
     const size_t S = (size_t)3 * max_batch, nb = sizeof(float) * (size_t)h->n, nbt = sizeof(float) * (size_t)h->ntot;
@@ -4289,6 +4310,7 @@ static int qnet_create(const NetSpec &s, fb_qnet_t *out) {
         alloc(&h->a3n, S * 1600 * 6 + 256);
         alloc(&h->ht, S * fc_width * 4 * FC1_SP_KS);
         alloc(&h->sig_seen, sizeof(int));
+        if (is_iqn(h)) for (int w = 0; w < 2; w++) alloc(&h->iqn_pbar[w], sizeof(float) * (size_t)fc_width);
         if (e == hipSuccess) e = hipMemset(h->sig_seen, 0xff, sizeof(int));      // (no planes yet)
     }
     alloc(&h->slabs, sizeof(float) * (size_t)h->zmax * CONV_PARAMS);
@@ -4485,10 +4507,10 @@ extern "C" int fb_qnet_init_params(fb_qnet_t h, int which, uint64_t seed, void *
         const float b = 1.0f;
         uint32_t bits;
         memcpy(&bits, &b, 4);
-        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(h->params[which] + h->iqn_off.be), (int)bits, (size_t)h->FC, fb_stream(stream)));
+        FB_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)(master(h, which) + h->iqn_off.be), (int)bits, (size_t)h->FC, fb_stream(stream)));
     }
     if (h->noisy)                                // (mu as the plain net's, then sigma0 / sqrt(fan_in))
-        hipLaunchKernelGGL(noisy_sigma_init_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, fb_stream(stream), h->mst[which], h->nnet);
+        hipLaunchKernelGGL(noisy_sigma_init_kernel, dim3((unsigned)((h->noisy_end - OFF_WF1 + 255) / 256)), dim3(256), 0, fb_stream(stream), h->mst[which], h->nnet, h->noisy_end);
     noisy_materialise(h, which, 0, false, fb_stream(stream));
     env_noise_invalidate(h, which, fb_stream(stream));
     c51d_fold(h, which, fb_stream(stream));
@@ -4571,7 +4593,7 @@ struct Plan {
     // depend on how many other states share the launch (the small-batch kernels below 256 states round differently)
     bool any_rows;
     float *probs;                            // C51 forward plans: the head also writes the probabilities f32[row][A][N] (fb_qnet_forward_dist)
-    bool no_head;                            // C51 forward plans: conv1 .. fc1 only (fb_qnet_act_nib_env_noise launches its own head)
+    bool no_head;                            // C51 / IQN forward plans: conv1 .. fc1 only (fb_qnet_act_nib_env_noise launches its own head)
     // an actor-critic net.  Forward plans with ac_value set: the policy head (fb_ac.hip) instead of the plain one -- value f32[rows], logits
     // f32[rows][A] / logp f32[rows] or NULL, p.actions NULL: no action; ac_greedy: the first maximum instead of a draw.  Train plans: the
     // advantages, the returns and n_total (p.r / p.isw / p.gamma stay unset)
@@ -4814,7 +4836,7 @@ static void head_stage(fb_qnet *h, const Plan &p, const PlanCtx &c) {
         return;
     }
     // (an actor-critic net without ac_value: the plain head over W_pi b_pi, the logits as "Q"; its train plans: the loss launches' own work)
-    if (!c.c51 && !(p.train && (c.ac || !c.big)) && runs(c, K_HEAD)) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
+    if (!c.c51 && !p.no_head && !(p.train && (c.ac || !c.big)) && runs(c, K_HEAD)) {    // (small-batch training gets Q from fc1_fk_kernel's shares instead)
         HeadArgs H;
         H.sl = p.sl; H.nslices = p.ns;
         for (int z = 0; z < p.ns; z++) H.sl.s[z].params = head_base(h, p.sl.s[z].params);      // (an IQN net: its fold; every scalar net: its parameters)
@@ -5166,20 +5188,17 @@ int fb_qnet_check_env_noise(fb_qnet_t h, int n, const char *who) {
     return FB_OK;
 }
 
-// the per-env acting forward (include/fbdqn.h): mu into params[0] (zero noise), the acting forward's conv1 .. fc1 on it, then the
-// noise: sigma_W_fc1's planes (when sigma moved), the scaled activations' planes, sigma's fc1 GEMM (fc1_sp_kernel, unchanged), the
-// per-env noisy head.  restore: rebuild params[0] (and the folded head) from the net's own sample -- the same launches that built them
-static int act_env_noise(fb_qnet *h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step, uint8_t *actions, float *q,
-                         bool restore, hipStream_t st) {
-    FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib_env_noise: NULL argument");
-    int rc = fb_qnet_check_env_noise(h, n, "fb_qnet_act_nib_env_noise");
-    if (rc != FB_OK) return rc;
-    const NoisyMat mu{h->mst[0], h->params[0], h->nz_zero, h->nnet, OFF_WF1, 0, h->adam};
+// the fc1 stage of the per-env acting forward (include/fbdqn.h), shared by the C51 and the IQN path: mu into params[0] (zero noise) and
+// its fold, the acting forward's conv1 .. fc1 on it, then the noise: sigma_W_fc1's planes (when sigma moved), the scaled activations'
+// planes, sigma's fc1 GEMM (fc1_sp_kernel, unchanged).  *o: where the head that follows finds the two sets of fc1 partial sums
+int fb_qnet_env_noise_fc1(fb_qnet_t h, const uint8_t *nib_states, int n, uint64_t seed, uint64_t step, FbEnvNoiseFc1 *o, void *stream) {
+    hipStream_t st = fb_stream(stream);
+    const NoisyMat mu{h->mst[0], h->params[0], h->nz_zero, h->nnet, OFF_WF1, 0, h->adam, h->noisy_end};
     hipLaunchKernelGGL(noisy_mat_kernel, dim3((unsigned)((h->n - OFF_WF1 + 255) / 256)), dim3(256), 0, st, mu);
     c51d_fold(h, 0, st);
     Plan p = forward_plan(h, 0, nib_states, n);
     p.nib = true; p.no_head = true;
-    rc = run_plan(h, p, -1, st);
+    const int rc = run_plan(h, p, -1, st);
     if (rc != FB_OK) return rc;
     const bool sp = n >= 256;                    // (run_plan's: the fused two-plane trunk + fc1_sp_kernel, else the small-batch kernels)
     const int FC = h->FC, stot = 3 * h->max_batch;
@@ -5192,14 +5211,42 @@ static int act_env_noise(fb_qnet *h, const uint8_t *nib_states, int n, float eps
     hipLaunchKernelGGL(env_noise_scale_kernel, dim3((unsigned)(((long long)n * 800 + 255) / 256)), dim3(256), 0, st, es);
     const Fc1Args af{h->a3n, pl2, h->zeros, h->wsig + WSP_WF1, h->ht, stot, n, FC, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
     hipLaunchKernelGGL(fc1_sp_kernel<3>, dim3(((n + 127) / 128) * (FC / 64) * FC1_SP_KS), dim3(256), 0, st, af);
-    EnvNoiseHead H;
-    H.hf = sp ? h->hf_act : h->hf; H.ht = h->ht; H.stot = stot; H.nks = sp ? FC1_SP_KS : 1;
-    H.P = head_base(h, h->params[0]); H.hoff = h->hoff; H.sig = sig; H.off = h->off; H.N = h->nnet;
-    H.n = n; H.FC = FC; H.A = h->A; H.sup = h->sup; H.q = h->q; H.actions = actions; H.epsilon = epsilon;
-    put_seed_words(H, seed, step); H.key_of = nullptr; H.stream = FB_STREAM_EPS;
-    with_actions(h->A, [&](auto a) { with_bool(is_c51d(h), [&](auto d) {
-        hipLaunchKernelGGL((env_noise_head_kernel<decltype(a)::value, decltype(d)::value>), dim3((n + ENH_WAVES - 1) / ENH_WAVES), dim3(64 * ENH_WAVES), 0, st, H);
-    }); });
+    o->hf = sp ? h->hf_act : h->hf; o->ht = h->ht; o->stot = stot; o->nks = sp ? FC1_SP_KS : 1; o->nkt = FC1_SP_KS; o->sig = sig;
+    return FB_OK;
+}
+
+// the per-env acting forward: the fc1 stage above, then the per-env noisy head -- a C51 net's (env_noise_head_kernel) or an IQN net's
+// (fb_iqn.hip).  restore: rebuild params[0] (and the folded head) from the net's own sample -- the same launches that built them
+static int act_env_noise(fb_qnet *h, const uint8_t *nib_states, int n, float epsilon, uint64_t seed, uint64_t step, uint8_t *actions, float *q,
+                         bool restore, hipStream_t st) {
+    FB_REQUIRE(h && nib_states && actions, "fb_qnet_act_nib_env_noise: NULL argument");
+    int rc = fb_qnet_check_env_noise(h, n, "fb_qnet_act_nib_env_noise");
+    if (rc != FB_OK) return rc;
+    FbEnvNoiseFc1 f1;
+    rc = fb_qnet_env_noise_fc1(h, nib_states, n, seed, step, &f1, st);
+    if (rc != FB_OK) return rc;
+    const int FC = h->FC;
+    if (is_iqn(h)) {
+        IqnEnvNoiseArgs H;
+        memset(&H, 0, sizeof(H));
+        H.hf = f1.hf; H.ht = f1.ht; H.stot = f1.stot; H.nks = f1.nks; H.nkt = f1.nkt; H.sig = f1.sig;
+        H.F = head_base(h, h->params[0]); H.foff = h->hoff; H.off = h->off; H.pbar = h->iqn_pbar[0];
+        H.n = n; H.FC = FC; H.A = h->A; H.nz = h->nnet.nz; H.dueling = is_iqnd(h) ? 1 : 0;
+        const NoisyLayer LV = h->nnet.l[1], LQ = h->nnet.l[h->nnet.nl - 1];
+        H.e_fc1_out = h->nnet.l[0].eout; H.e_v_in = LV.ein; H.e_v_out = LV.eout; H.e_q_in = LQ.ein; H.e_q_out = LQ.eout;
+        H.q = h->q; H.actions = actions; H.epsilon = epsilon;
+        put_seed_words(H, seed, step); H.key_of = nullptr; H.stream = FB_STREAM_EPS;
+        fb_iqn_launch_env_noise_head(st, H);
+    } else {
+        EnvNoiseHead H;
+        H.hf = f1.hf; H.ht = f1.ht; H.stot = f1.stot; H.nks = f1.nks;
+        H.P = head_base(h, h->params[0]); H.hoff = h->hoff; H.sig = f1.sig; H.off = h->off; H.N = h->nnet;
+        H.n = n; H.FC = FC; H.A = h->A; H.sup = h->sup; H.q = h->q; H.actions = actions; H.epsilon = epsilon;
+        put_seed_words(H, seed, step); H.key_of = nullptr; H.stream = FB_STREAM_EPS;
+        with_actions(h->A, [&](auto a) { with_bool(is_c51d(h), [&](auto d) {
+            hipLaunchKernelGGL((env_noise_head_kernel<decltype(a)::value, decltype(d)::value>), dim3((n + ENH_WAVES - 1) / ENH_WAVES), dim3(64 * ENH_WAVES), 0, st, H);
+        }); });
+    }
     if (restore) {
         noisy_materialise(h, 0, OFF_WF1, true, st);
         c51d_fold(h, 0, st);

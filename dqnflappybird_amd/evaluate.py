@@ -138,9 +138,12 @@ def qnet_from_checkpoint(path, fc_width=512, dtype="f32", max_batch=1024):
     if "head" in z.files and str(z["head"][0]) == "iqn":     # an IQN net (VecIQN): greedy play on the folded head, under the file's risk setting
         n_tau, n_tau_next, n_tau_act, kappa, cvar = z["iqn"].tolist()
         dueling = bool(int(z["dueling"][0])) if "dueling" in z.files else False      # (a file without the key: a plain IQN net)
-        net = QNet(2, fc_width, "iqndueling" if dueling else "iqn", max_batch=max_batch, n_tau=int(n_tau), n_tau_next=int(n_tau_next), n_tau_act=int(n_tau_act), kappa=kappa)
+        noisy = "noisy" in z.files and bool(z["noisy"][0])                           # (... nor `noisy`: not noisy; a noisy net starts in mean mode)
+        from .veciqn import iqn_arch
+        kw = dict(sigma0=float(z["sigma0"][0])) if noisy else {}
+        net = QNet(2, fc_width, iqn_arch(dueling, noisy), max_batch=max_batch, n_tau=int(n_tau), n_tau_next=int(n_tau_next), n_tau_act=int(n_tau_act), kappa=kappa, **kw)
         if net.n_params != online.size:
-            raise ValueError(f"{path}: {online.size} online parameters do not match {'a dueling' if dueling else 'an'} IQN net of width {fc_width}")
+            raise ValueError(f"{path}: {online.size} online parameters do not match {'a dueling' if dueling else 'an'} {'noisy ' if noisy else ''}IQN net of width {fc_width}")
         if dtype != "f32":
             raise ValueError(f"{path}: an IQN net computes in f32 only (dtype {dtype!r})")
         net.load_params(online, 0)

@@ -314,6 +314,9 @@ IQN_ARCH = "iqn"                                          # implicit quantile ne
 IQN_DUELING_ARCH = "iqndueling"                           # its dueling form: value and advantage quantile streams, one effective column per action
 IQN_ARCHS = (IQN_ARCH, IQN_DUELING_ARCH)                  # what every IQN call takes
 IQN_DEFAULTS = L.IQN_DEFAULTS                             # (n_tau, n_tau_next, n_tau_act, kappa) of a new IQN net
+IQN_NOISY_ARCHS = ("iqnnoisy", "iqnduelingnoisy")         # noisy IQN: fc1 and the head layers are factorised Gaussian layers (include/fbdqn.h)
+IQN_ALL_ARCHS = IQN_ARCHS + IQN_NOISY_ARCHS               # what every IQN call takes
+IQN_DUELING_ARCHS = (IQN_DUELING_ARCH, "iqnduelingnoisy")
 
 
 def check_sigma0(sigma0):
@@ -326,7 +329,10 @@ def check_sigma0(sigma0):
 
 def noise_size(fc_width, actions, n_atoms, arch):
     """the length of a noisy net's f(eps) vector (fb_qnet_get_noise): per layer fan_in + fan_out -- fc1, then the head's layer(s)"""
-    fc, an = int(fc_width), int(actions) * int(n_atoms)
+    fc = int(fc_width)
+    if arch in IQN_NOISY_ARCHS:                  # (scalar layers: FC -> A, and the dueling net's V layer FC -> 1 in front of it; n_atoms is not read)
+        return 1600 + fc + (fc + 1 if arch in IQN_DUELING_ARCHS else 0) + fc + int(actions)
+    an = int(actions) * int(n_atoms)
     return 1600 + fc + (fc + int(n_atoms) if arch == "c51dueling" else 0) + fc + an
 
 
@@ -536,7 +542,7 @@ class QNet:
     """The reference Q-network (BrainDQN.py:119-163) with forward, backward and TF-Adam as HIP
     kernels.  `arch='dueling'` builds the head of BrainDuelingDQN.py:78-86."""
 
-    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH, SAC_ARCH, IQN_ARCH, IQN_DUELING_ARCH)
+    ARCHS = ("plain", "dueling") + C51_ARCHS + QR_ARCHS + (AC_ARCH, SAC_ARCH, IQN_ARCH, IQN_DUELING_ARCH) + IQN_NOISY_ARCHS
 
     def __init__(self, actions=2, fc_width=512, arch="plain", max_batch=32, device="cuda", n_atoms=C51_DEFAULT_SUPPORT[0],
                  v_min=C51_DEFAULT_SUPPORT[1], v_max=C51_DEFAULT_SUPPORT[2], noisy=False, sigma0=NOISY_DEFAULT_SIGMA0,
@@ -556,13 +562,18 @@ class QNet:
         tau with the quantile Huber loss (kappa), acts on the mean over a grid of n_tau_act tau (scaled by set_iqn_risk's eta), which
         forward / act / act_nib / evaluation return as the Q values (2 <= actions <= 8; include/fbdqn.h)
         arch='iqndueling': the dueling IQN net -- W_v b_v W_a b_a where W_q b_q stand, theta = V(tau) + Adv_a(tau) - mean_a' Adv_a'(tau) read as
-        one effective column per action; every IQN call takes it (include/fbdqn.h)"""
+        one effective column per action; every IQN call takes it (include/fbdqn.h)
+        arch='iqnnoisy' / 'iqnduelingnoisy': the noisy forms of the two -- fc1 and the head layers (W_q b_q; dueling: the V and the advantage
+        layer) are factorised Gaussian layers at sigma0, the tau embedding stays deterministic; .noisy is True, the noise calls and every IQN
+        call take it (include/fbdqn.h).  noisy=True stays the C51 archs' keyword"""
         if arch not in self.ARCHS:
             raise ValueError(f"arch must be one of {self.ARCHS}, got {arch!r}")
         self.noisy = bool(noisy)
         self.sigma0 = None
         self.acting_noise = "shared"
-        if self.noisy:
+        if arch in IQN_NOISY_ARCHS:                  # (noisy by name: noisy=True says nothing more)
+            self.sigma0 = check_sigma0(sigma0)
+        elif self.noisy:
             if arch not in C51_ARCHS:
                 raise ValueError(f"noisy layers are offered on the C51 heads only ({C51_ARCHS}), not arch {arch!r}")
             self.sigma0 = check_sigma0(sigma0)
@@ -570,7 +581,7 @@ class QNet:
             n_atoms, v_min, v_max = check_support(n_atoms, v_min, v_max, actions)
         if arch in QR_ARCHS:
             n_quantiles, kappa = check_quantiles(n_quantiles, kappa, actions)
-        if arch in IQN_ARCHS:
+        if arch in IQN_ALL_ARCHS:
             n_tau, n_tau_next, n_tau_act, kappa, _ = check_iqn(n_tau, n_tau_next, n_tau_act, kappa, 1.0, actions)
         L.require_gpu()
         self.A, self.FC, self.max_batch = int(actions), int(fc_width), int(max_batch)
@@ -578,7 +589,11 @@ class QNet:
         self.arch = arch
         self.device = torch.device(device)
         self.h = C.c_void_p()
-        if self.noisy:
+        if arch in IQN_NOISY_ARCHS:
+            self.noisy = True
+            L.check(L.lib().fb_qnet_create_iqn_noisy(1 if arch in IQN_DUELING_ARCHS else 0, self.FC, self.A, n_tau, n_tau_next, n_tau_act, kappa,
+                                                     self.sigma0, self.max_batch, C.byref(self.h)), "fb_qnet_create_iqn_noisy")
+        elif self.noisy:
             L.check(L.lib().fb_qnet_create_c51_noisy(L.ARCH_C51 if arch == "c51" else L.ARCH_C51_DUELING, self.FC, self.A, n_atoms, v_min, v_max,
                                                      self.sigma0, self.max_batch, C.byref(self.h)), "fb_qnet_create_c51_noisy")
         elif arch == "c51":
@@ -924,7 +939,7 @@ class QNet:
 
     # -- implicit quantile networks (arch='iqn') -----------------------------------------
     def _need_iqn(self, what):
-        if self.arch not in IQN_ARCHS:
+        if self.arch not in IQN_ALL_ARCHS:
             raise ValueError(f"{what} needs an IQN net (QNet(..., arch='iqn'))")
 
     def set_iqn_risk(self, eta=1.0):
@@ -1036,8 +1051,9 @@ class QNet:
 
     @property
     def noise_size(self):
-        sup = self.support
-        return noise_size(self.FC, self.A, sup[0], self.arch) if self.noisy else 0
+        if not self.noisy:
+            return 0
+        return noise_size(self.FC, self.A, 0 if self.arch in IQN_NOISY_ARCHS else self.support[0], self.arch)
 
     def noise(self, which=L.NET_ONLINE):
         """net `which`'s current f(eps) vector, float32[noise_size] on the device (per layer: f(eps_in), then f(eps_out))"""
@@ -1264,7 +1280,7 @@ def _iqn_train_from_replay(name, replay, net, idx, isw, gamma, double_q, tau, ta
     """iqn_train_from_replay, and with `name` == 'iqn_per_train_from_replay' its prioritized form (a prioritized memory, isw in, abs_err out)
     -> (loss f32[1], a u8[B], r f32[B], t u8[B], q_target f32[B, n_tau_next] or None, abs_err f32[B] or None)"""
     weighted = name == "iqn_per_train_from_replay"
-    B, dev, a, loss = _ring_call(name, replay, net, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1, flat_grad, tau, tau_next, isw,
+    B, dev, a, loss = _ring_call(name, replay, net, IQN_ALL_ARCHS, "an IQN net (QNet(..., arch='iqn'))", "trains from", idx, 1, flat_grad, tau, tau_next, isw,
                                  prioritized=weighted)
     N, Np = net.iqn()[:2]
     check_iqn_batch(B, None, None, None, tau, tau_next, N, Np, flat_grad, net.n_params)
@@ -1603,7 +1619,7 @@ class _IqnStep:
     entry, prioritized = None, False
 
     def __init__(self, env, replay, net, batch=32, gamma=0.99, double_q=False, flat_grad=None):
-        _bind_step(self, type(self).__name__, IQN_ARCHS, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1,
+        _bind_step(self, type(self).__name__, IQN_ALL_ARCHS, "an IQN net (QNet(..., arch='iqn'))", env, replay, net, batch, gamma, flat_grad, 1,
                    prioritized=self.prioritized)
         self.double_q = bool(double_q)
 

@@ -19,6 +19,11 @@ same loops; with prioritized, double_q and n_step = 3 this is Rainbow-IQN withou
 munchausen=True: Munchausen IQN (Vieillard, Pietquin & Geist 2020) -- the target becomes the soft value under softmax(Qbar- / temp) of the
 target net plus the clipped log-policy bonus alpha max(temp ln pi-(a|s), clip) on the reward (QNet.set_iqn_munchausen); everything else,
 the memory kinds, the dueling net, n-step returns and CVaR acting included, is unchanged.  It has no greedy next action: double_q is refused.
+
+noisy=True: noisy IQN (Fortunato et al. 2018) -- fc1 and the head layers are factorised Gaussian layers at sigma0 (QNet archs 'iqnnoisy' /
+'iqnduelingnoisy'), the step draws the nets' noise, and the epsilon schedule defaults to 0.  acting_noise='shared': one sample per step for
+all envs; 'env': independent noise per env when acting.  With prioritized, dueling, double_q and n_step = 3: full Rainbow-IQN (Toromanoff et
+al. 2019).
 """
 import numpy as np
 
@@ -86,6 +91,32 @@ def check_munchausen(munchausen, temp, alpha, clip, double_q=False):
     return bool(munchausen), t, a, c
 
 
+def check_noisy(noisy, sigma0, acting_noise):
+    """VecIQN's noisy-net settings, checked apart from check_args (whose positional parameters stay as they are) -> (noisy, sigma0,
+    acting_noise); sigma0 is checked whether or not the layers are on"""
+    from .vec import ACTING_NOISE_MODES, check_sigma0
+    if not isinstance(noisy, (bool, np.bool_)):
+        raise ValueError(f"noisy must be True or False, got {noisy!r}")
+    try:
+        s0 = check_sigma0(sigma0)
+    except (TypeError, ValueError):
+        raise ValueError(f"sigma0 must be finite and >= 0, got {sigma0!r}") from None
+    if acting_noise not in ACTING_NOISE_MODES:
+        raise ValueError(f"acting_noise must be 'shared' or 'env', got {acting_noise!r}")
+    if acting_noise == "env" and not noisy:
+        raise ValueError("acting_noise='env' needs a noisy net (noisy=True)")
+    return bool(noisy), s0, acting_noise
+
+
+def net_kind(noisy):
+    return "a noisy net" if noisy else "a non-noisy net"
+
+
+def iqn_arch(dueling, noisy):
+    """the QNet arch of a VecIQN's net"""
+    return ("iqnduelingnoisy" if dueling else "iqnnoisy") if noisy else ("iqndueling" if dueling else "iqn")
+
+
 def target_kind(munchausen):
     return "Munchausen" if munchausen else "hard"
 
@@ -99,10 +130,12 @@ def replay_kind(prioritized):
 
 
 class VecIQN(DeviceLoop):
+    noisy, sigma0, acting_noise = False, 0.5, "shared"       # (what __init__ sets per instance: a loop without noisy layers)
+
     def __init__(self, n_envs, batch=32, double_q=False, n_step=1, n_tau=8, n_tau_next=8, n_tau_act=32, kappa=1.0, cvar=1.0, polyak=0.0,
-                 replace_target_iter=500, observe=1000, explore=1_000_000, initial_epsilon=0.03, final_epsilon=0.0, gamma=0.99, lr=1e-6,
+                 replace_target_iter=500, observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99, lr=1e-6,
                  max_grad_norm=0, fc_width=512, seed=0, capacity=None, prioritized=False, dueling=False,
-                 munchausen=False, temp=0.03, alpha=0.9, clip=-1.0):
+                 munchausen=False, temp=0.03, alpha=0.9, clip=-1.0, noisy=False, sigma0=0.5, acting_noise="shared"):
         """n_envs games; every step trains one minibatch of `batch` transitions (<= n_envs, <= 256) once more than `observe` steps have
         filled the memory.  n_tau / n_tau_next: the tau sampled per transition for the online / target quantiles; n_tau_act: the acting
         grid; kappa: the quantile Huber threshold; cvar = eta in (0, 1]: act on CVaR_eta (1 = the mean).  double_q: a* from the online
@@ -110,7 +143,12 @@ class VecIQN(DeviceLoop):
         VecBrain's; polyak > 0 replaces the copy by soft updates; lr is Adam's; max_grad_norm=G > 0 clips the gradient's global norm.
         prioritized: train from a prioritized memory (importance-weighted loss, the per-sample loss as the priority).
         dueling: the dueling IQN net (value and advantage quantile streams) instead of the plain one.
-        munchausen: the Munchausen target with the softmax temperature temp, the bonus's scale alpha and its lower clip (not with double_q)."""
+        munchausen: the Munchausen target with the softmax temperature temp, the bonus's scale alpha and its lower clip (not with double_q).
+        noisy: noisy fc1 and head layers, sigma initialised to sigma0 / sqrt(fan_in); the exploration comes from the noise, so
+        initial_epsilon defaults to 0 (0.03 without noise); an explicit initial_epsilon is honoured.  acting_noise: 'shared' -- one noise
+        sample per step for all envs -- or 'env': independent noise per env when acting (training is the same in both)."""
+        if initial_epsilon is None:                          # (noisy itself is checked below, behind the checks of before)
+            initial_epsilon = 0.0 if isinstance(noisy, (bool, np.bool_)) and noisy else 0.03
         (self.n, self.batch, self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar, self.n_step, self.polyak, self.replace_target_iter,
          self.observe, self.explore, self.initial_epsilon, self.final_epsilon, self.gamma, self.lr, self.max_grad_norm, self.capacity) = check_args(
             n_envs, batch, n_tau, n_tau_next, n_tau_act, kappa, cvar, n_step, polyak, replace_target_iter, observe, explore, initial_epsilon,
@@ -118,12 +156,14 @@ class VecIQN(DeviceLoop):
         self.prioritized = check_prioritized(prioritized)
         self.dueling = check_dueling(dueling)
         self.munchausen, self.temp, self.alpha, self.clip = check_munchausen(munchausen, temp, alpha, clip, bool(double_q))
+        self.noisy, self.sigma0, self.acting_noise = check_noisy(noisy, sigma0, acting_noise)
         self.double_q = bool(double_q)
         self.seed = int(seed)
         self.fc_width = int(fc_width)
         self.epsilon = self.initial_epsilon
-        self._build_world("iqndueling" if self.dueling else "iqn", max(self.n, self.batch), self._setup_net, prioritized=self.prioritized,
-                          n_step=self.n_step, n_tau=self.n_tau, n_tau_next=self.n_tau_next, n_tau_act=self.n_tau_act, kappa=self.kappa)
+        noisy_kw = dict(sigma0=self.sigma0) if self.noisy else {}
+        self._build_world(iqn_arch(self.dueling, self.noisy), max(self.n, self.batch), self._setup_net, prioritized=self.prioritized,
+                          n_step=self.n_step, n_tau=self.n_tau, n_tau_next=self.n_tau_next, n_tau_act=self.n_tau_act, kappa=self.kappa, **noisy_kw)
         self._bind()
         self.timeStep = 0                                    # env steps per env so far: the key of the epsilon and tau draws
 
@@ -132,6 +172,8 @@ class VecIQN(DeviceLoop):
             net.set_iqn_risk(self.cvar)
         if self.munchausen:                                  # (off: the net is never touched)
             net.set_iqn_munchausen(True, self.temp, self.alpha, self.clip)
+        if self.acting_noise == "env":                       # (the fused step reads it: act with per-env noise, draw the online sample after)
+            net.set_acting_noise("env")
 
     def _bind(self):
         from .vec import IqnPerStep, IqnStep
@@ -141,7 +183,13 @@ class VecIQN(DeviceLoop):
     def step(self):
         """one vector step -> the loss f32[1] (device)"""
         if self.timeStep < self.n_step - 1:                  # no n-step transition is complete yet: store without drawing a minibatch
-            actions = self.net.act_nib(self.nib, self.epsilon, seed=self.seed, step=self.timeStep)
+            if self.noisy and self.acting_noise == "shared":   # (the fused step's order: the online sample in front of acting ...)
+                self.net.reset_noise(0, self.seed, self.timeStep)
+            if self.acting_noise == "env":
+                actions = self.net.act_nib_env_noise(self.nib, self.epsilon, seed=self.seed, step=self.timeStep)
+                self.net.reset_noise(0, self.seed, self.timeStep)      # (... or, per-env acting, behind it)
+            else:
+                actions = self.net.act_nib(self.nib, self.epsilon, seed=self.seed, step=self.timeStep)
             _, reward, terminal, _ = self.env.frame_step(actions, want_u8=False)
             self.replay.push(self.env.frame_bits, actions, reward, terminal)
             self.timeStep += 1
@@ -157,13 +205,33 @@ class VecIQN(DeviceLoop):
         self.timeStep += 1
         return self.loss
 
+    def _last_noise(self):
+        """the online sample the last step left: drawn at (seed, timeStep - 1); mean mode before the first step"""
+        if self.timeStep > 0:
+            self.net.reset_noise(0, self.seed, self.timeStep - 1)
+        else:
+            self.net.mean_noise(0)
+
+    def evaluate(self, n_envs=4096, episodes=1, max_steps=100_000, epsilon=0.0, env_seed=0, act_seed=0, noise="mean"):
+        """DeviceLoop.evaluate; a noisy net plays with its mean weights (noise='sample': one sample keyed by act_seed), and its online
+        sample of the last step is put back afterwards"""
+        from .evaluate import evaluate
+        res = evaluate(self.net, n_envs, episodes, max_steps, epsilon, env_seed, act_seed, noise=noise)
+        if self.noisy:
+            self._last_noise()
+        return res
+
     # ------------------------------------------------------------------ checkpoint / resume
     def save(self, path):
         """everything the loop needs to continue bit for bit: the nets, Adam, every env's state and frame stack, the stats, the memory
         (with its generator and, prioritized, its tree), the counters, epsilon and the settings; `head` = 'iqn' tells the file from the
         other loops', `prioritized` the memory's kind (a file without the key is a uniform one's), `dueling` the net's (without the key: a plain IQN net's),
-        `munchausen` = (on, temp, alpha, clip) the target's (without the key: the hard target)"""
-        self._save(path, IQN_HEAD,
+        `munchausen` = (on, temp, alpha, clip) the target's (without the key: the hard target); a noisy net adds `noisy`, `sigma0` and
+        `acting_noise` (without them: not noisy), and its nets and Adam slots hold [mu | sigma]"""
+        own = {}
+        if self.noisy:
+            own = dict(noisy=np.array([1], np.int64), sigma0=np.array([self.sigma0], np.float64), acting_noise=np.array([self.acting_noise]))
+        self._save(path, IQN_HEAD, **own,
                    scalars=np.array([self.timeStep, self.seed, self.n, self.batch, self.fc_width, self.observe, self.explore, self.n_step,
                                      int(self.double_q), self.replace_target_iter], np.int64),
                    iqn=np.array([self.n_tau, self.n_tau_next, self.n_tau_act, self.kappa, self.cvar], np.float64),
@@ -175,7 +243,7 @@ class VecIQN(DeviceLoop):
     def load(self, path):
         """the inverse of save(), into a VecIQN made with the same n_envs, batch, fc_width, n_step, (n_tau, n_tau_next, n_tau_act, kappa),
         capacity, seed, memory kind (prioritized or not), head kind (dueling or not) and target (munchausen or not, and its temp, alpha,
-        clip); the other settings of the file replace this object's"""
+        clip) and noisy layers (noisy or not, sigma0, acting_noise); the other settings of the file replace this object's"""
         import torch
         z = np.load(npz_path(path))
         refuse_foreign_head(z, path, lambda head: head != IQN_HEAD and f"a {head} head (another loop's), this is a VecIQN (head {IQN_HEAD!r})")
@@ -206,6 +274,16 @@ class VecIQN(DeviceLoop):
         if self.munchausen and tuple(mu[1:]) != (self.temp, self.alpha, self.clip):
             raise ValueError(f"checkpoint {path} was trained with munchausen (temp, alpha, clip) = {tuple(mu[1:])}, this VecIQN has "
                              f"{(self.temp, self.alpha, self.clip)}")
+        nz = bool(int(z["noisy"][0])) if "noisy" in z.files else False
+        if nz != self.noisy:
+            raise ValueError(f"checkpoint {path} holds {net_kind(nz)}, this VecIQN has {net_kind(self.noisy)} (noisy={self.noisy}: the parameter "
+                             "vectors differ)")
+        if self.noisy:
+            s0, an = float(z["sigma0"][0]), str(z["acting_noise"][0])
+            if s0 != self.sigma0:
+                raise ValueError(f"checkpoint {path} was written with sigma0 = {s0}, this VecIQN has sigma0 = {self.sigma0}")
+            if an != self.acting_noise:
+                raise ValueError(f"checkpoint {path} was written with acting_noise = {an!r}, this VecIQN has acting_noise = {self.acting_noise!r}")
         self._restore(z)
         self.gamma, self.polyak, self.max_grad_norm, self.lr, self.epsilon, self.initial_epsilon, self.final_epsilon = (float(x) for x in z["settings"])
         self.cvar = q[4]
@@ -214,6 +292,8 @@ class VecIQN(DeviceLoop):
         self.net.set_iqn_risk(self.cvar)
         self.observe, self.explore, self.double_q, self.replace_target_iter = sc[5], sc[6], bool(sc[8]), sc[9]
         self.timeStep = sc[0]
+        if self.noisy:
+            self._last_noise()
         self._bind()
         torch.cuda.synchronize()
 

@@ -962,6 +962,51 @@ int fb_qnet_create_iqn_dueling(int fc_width, int n_actions, int n_tau, int n_tau
  *   not offered noisy IQN, bf16, data parallel, riders, the split schedule; Munchausen with double_q. */
 int fb_qnet_set_iqn_munchausen(fb_qnet_t h, int on, float temp, float alpha, float clip_lo);
 int fb_qnet_get_iqn_munchausen(fb_qnet_t h, int *on_host, float *temp_host, float *alpha_host, float *clip_lo_host);
+/* ------------------------------------------------------------------ noisy IQN (Fortunato et al. 2018 on the IQN net; with the dueling head,
+ * prioritized replay and n-step returns: Rainbow-IQN, Toromanoff et al. 2019)
+ *
+ * This block supersedes the "not offered ... noisy IQN" lines of the four IQN blocks above.
+ * A noisy IQN net is an IQN (arch 8) or dueling IQN (arch 9) net whose fc1 (1600 -> FC) and head layers are factorised Gaussian layers, as a
+ * noisy C51 net's.  Plain head: W_q b_q, FC -> A.  Dueling head: the V layer FC -> 1 and the advantage layer FC -> A, separate layers with
+ * separate noise.  The conv trunk and the tau embedding W_e b_e stay deterministic.
+ *   made by     fb_qnet_create_iqn_noisy(dueling 0 / 1, ...): fb_qnet_create_iqn's checks plus sigma0 finite and >= 0, before any allocation.
+ *               fb_qnet_create_c51_noisy with arch 8 / 9, fb_qnet_create(8 | 9, ...) and the noise calls on a non-noisy net keep their refusals
+ *   layout      the master vector is [mu | sigma].  mu is the net's IQN layout, unchanged: n_mu = the non-noisy net's count.  sigma covers the
+ *               entries q in [OFF_WF1, off.we) -- W_fc1 b_fc1 and the head; W_e b_e have no sigma -- and sits at n_mu + q - OFF_WF1.
+ *               fb_qnet_num_params = n_mu + (off.we - OFF_WF1).  Load, store, flat_grad, the Adam state, both target syncs, the soft sync and
+ *               the global-norm clip cover the whole vector
+ *   init        mu is the non-noisy net's bits for the same seed (b_e = 1.0 is kept); sigma = sigma0 / sqrt(fan_in) per layer, weights and biases
+ *   noise       per layer, in the layout's order: f(eps_in)[fan_in], then f(eps_out)[fan_out].  nz = (1600 + FC) + (FC + A); dueling:
+ *               (1600 + FC) + (FC + 1) + (FC + A).  The draws are those of FB_NOISE_SAMPLE / FB_NOISE_MEAN above: Philox stream 6, counter
+ *               (element, step_lo, 6, 2 step_hi + net).  A new net is in mean mode
+ *   effective   params[w] = mu + sigma (.) e on [OFF_WF1, off.we), mu elsewhere; rebuilt behind every change (init, load, both syncs, the
+ *               fused Adam, fb_qnet_apply_adam, fb_qnet_reset_noise), and the IQN fold follows each rebuild.  So every forward-only path
+ *               (fb_qnet_act_nib, fb_eval_run, fb_eval_q, the env launch's head rider, fb_qnet_forward, fb_qnet_forward_iqn) sees the current
+ *               sample; the shared mode has no acting kernel of its own
+ *   gradient    the IQN kernels yield the effective weights' gradient, which is mu's; sigma's is g[n_mu + q - OFF_WF1] = g[q] e(q); W_e b_e
+ *               gradients pass through untouched.  In mean mode sigma's gradient is 0 and mu trains bit for bit as the non-noisy IQN net
+ *   per-env     FB_ACT_NOISE_PER_ENV, fb_qnet_act_nib_env_noise's draws: stream 7, counter (e nz + k, step_lo, 7, step_hi).  fc1 as documented
+ *               for C51: h_k = relu((mu partials + b_k) + f(eo_k) (t_k + sigma_b_k)).  Plain head:
+ *                 Qbar_e(a) = [b_q[a] + sum_k phibar_k W_q^mu[k, a] h_k] + f(eo_a) (sum_k phibar_k sigma_W[k, a] f(ei_k) h_k + sigma_b[a])
+ *               The bracket is the mu logit over the mu fold, with the plain head's arithmetic; the noise term is added after it.  phibar is
+ *               the acting grid's mean embedding (K points, risk eta) from mu's W_e b_e: theta is linear in phi and the noise does not depend
+ *               on tau, so this is exactly the grid mean of theta under env e's effective weights.  Dueling: the noise term of column a is
+ *               nV + nA_a - (1/A) sum_c nA_c, nV and nA_c formed as the plain head's noise term over the V and advantage layers' own sigma and
+ *               noise.  epsilon-greedy is fb_qnet_act_nib's, on the same Philox stream.  At sigma = 0 the call is mean-mode fb_qnet_act_nib
+ *               bit for bit, actions and Q.  The call reads no net's sample and leaves samples, effective vectors, folds, parameters and Adam
+ *               state as they were
+ *   steps       fb_iqn_step / fb_iqn_per_step on a noisy net are bit for bit the composed public calls.  Shared mode: fb_qnet_reset_noise(0,
+ *               SAMPLE, seed, step) -> fb_qnet_act_nib -> env step -> store / sample -> fb_qnet_reset_noise(1, ...) -> train.  Per-env mode:
+ *               fb_qnet_act_nib_env_noise(seed, step) -> env step -> store / sample -> fb_qnet_reset_noise(0) -> fb_qnet_reset_noise(1) ->
+ *               train (fb_vec_step's order).  The tau draws (stream 10) are unchanged.  double_q, n-step, prioritized replay, CVaR, Polyak,
+ *               gradient clipping and Munchausen compose
+ *   takes it    fb_qnet_is_noisy, _reset_noise, _get_noise, _set_acting_noise, _act_nib_env_noise; every fb_qnet_iqn_* / fb_iqn_* call,
+ *               fb_qnet_set_iqn_risk and fb_qnet_set_iqn_munchausen
+ *   refused     before any launch or counter change: fb_vec_step*, fb_train_steps, FB_DTYPE_BF16, data parallel, the scalar / C51 / QR algos,
+ *               n nz >= 2^32 in the per-env call
+ *   not offered noisy QR / scalar / SAC nets, one launch for draw + rebuild + fold, the split schedule, riders. */
+int fb_qnet_create_iqn_noisy(int dueling, int fc_width, int n_actions, int n_tau, int n_tau_next, int n_tau_act, float kappa, float sigma0,
+                             int max_batch, fb_qnet_t *out);
 
 int fb_qnet_create(int arch, int fc_width, int n_actions, int max_batch, fb_qnet_t *out);
 int fb_qnet_destroy(fb_qnet_t h);

@@ -4,6 +4,7 @@ steps and seed.
 
     python tools/learn_iqn.py [--envs 1024] [--lr 1e-5] [--steps 2000000] [--window 50000] [--explore 1000000] [--n-step 1] [--double]
                               [--per] [--dueling] [--munchausen [--temp 0.03] [--alpha 0.9] [--clip -1]] [--cvar 1.0] [--eval-envs 4096]
+                              [--sigma0 S [--acting-noise shared|env]]
                               [--seed 1] [--budget-s S] [--out FILE]
 
 Every `window` steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and
@@ -38,6 +39,8 @@ def main():
     ap.add_argument("--alpha", type=float, default=0.9, help="--munchausen: the scale of the log-policy bonus")
     ap.add_argument("--clip", type=float, default=-1.0, help="--munchausen: the bonus's lower clip l0")
     ap.add_argument("--cvar", type=float, default=1.0)
+    ap.add_argument("--sigma0", type=float, default=None, help="noisy fc1 and head layers at this sigma0 (VecIQN(noisy=True)): epsilon 0")
+    ap.add_argument("--acting-noise", choices=("shared", "env"), default="shared", help="--sigma0: one acting sample for all envs, or one per env")
     ap.add_argument("--eval-envs", type=int, default=4096)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--budget-s", type=float, default=0.0, help="stop the run after this many seconds (0 = run all its steps)")
@@ -52,10 +55,12 @@ def main():
 
         emit(f"# tools/learn_iqn.py on {torch.cuda.get_device_name(0)}: {' '.join(sys.argv[1:])}")
         v = VecIQN(a.envs, lr=a.lr, seed=a.seed, explore=a.explore, n_step=a.n_step, double_q=a.double, cvar=a.cvar, capacity=1_000_000,
-                   prioritized=a.per, dueling=a.dueling, munchausen=a.munchausen, temp=a.temp, alpha=a.alpha, clip=a.clip)
+                   prioritized=a.per, dueling=a.dueling, munchausen=a.munchausen, temp=a.temp, alpha=a.alpha, clip=a.clip,
+                   **(dict(noisy=True, sigma0=a.sigma0, acting_noise=a.acting_noise) if a.sigma0 is not None else {}))
         emit(f"# envs {a.envs}  batch {v.batch}  (N, N', K) ({v.n_tau}, {v.n_tau_next}, {v.n_tau_act})  kappa {v.kappa:g}  cvar {v.cvar:g}  "
              f"double_q {v.double_q}  prioritized {v.prioritized}  dueling {v.dueling}  n_step {v.n_step}  observe {v.observe}  lr {v.lr:g}  seed {a.seed}"
-             + (f"  munchausen (temp, alpha, clip) ({v.temp:g}, {v.alpha:g}, {v.clip:g})" if v.munchausen else ""))
+             + (f"  munchausen (temp, alpha, clip) ({v.temp:g}, {v.alpha:g}, {v.clip:g})" if v.munchausen else "")
+             + (f"  noisy sigma0 {v.sigma0:g} acting_noise {v.acting_noise}" if v.noisy else ""))
         emit("#   env_steps  train_steps  episodes  mean_score  max_score  pipes/episode       loss   epsilon   steps/s")
         t0 = t_run = time.time()
         v.stats.zero_()
