@@ -114,6 +114,8 @@ def build_parser():
     parser.add_argument("--vec", type=int, default=0, help="run N vectorised envs (device-resident loop)")
     parser.add_argument("--n-step", type=int, default=1, help="learn from K-step returns (--vec, uniform replay; --model iqnper | rainbowiqn | sacper: prioritized; "
                                                                       "1 = the reference's one-step TD)")
+    parser.add_argument("--priority-init", choices=("max", "td"), default=None, help="--model prioritydqn | doubleper with --vec: a new transition's priority -- "
+                        "max (the default: the tree's maximum, the reference's) or td (the |TD error| of the Q-values computed to act, Ape-X)")
     parser.add_argument("--noisy", action="store_true", help="noisy fc1 and head layers, epsilon 0 (--model c51 | c51per | c51doubleper | rainbow, --vec)")
     parser.add_argument("--acting-noise", choices=("shared", "env"), default="shared",
                         help="--noisy / --sigma0: act with one noise sample for all envs (shared, the default) or independent noise per env (env)")
@@ -299,9 +301,25 @@ def a2c_kwargs(args, parser):
     return kw
 
 
+PRIORITY_INIT_MODELS = ("prioritydqn", "doubleper")      # the models whose acting Q-values give a stored transition's |TD error|
+
+
+def priority_init_kwargs(args, parser):
+    """--priority-init -> VecBrain's keyword; every other model refuses td by name (before anything touches the GPU)"""
+    if args.priority_init is None:
+        return {}
+    if args.priority_init == "td":
+        if args.model not in PRIORITY_INIT_MODELS:
+            parser.error(f"--priority-init td needs --model {' | '.join(PRIORITY_INIT_MODELS)}, not --model {args.model}")
+        if not args.vec:
+            parser.error("--priority-init td needs --vec: the single-env agents are the reference's, which store at the tree's maximum")
+    return dict(priority_init=args.priority_init) if args.vec and args.model in PRIORITY_INIT_MODELS else {}
+
+
 def main():
     parser = build_parser()
     args = parser.parse_args()
+    pkw = priority_init_kwargs(args, parser)             # (refused before anything touches the GPU)
     okw = optimiser_kwargs(args, parser)                 # (refused before anything touches the GPU)
     akw = a2c_kwargs(args, parser)
     skw = sac_kwargs(args, parser)
@@ -398,7 +416,7 @@ def main():
         if args.model in md_models:
             qkw = mkw
         vb = VecBrain(args.vec, algo=algo, arch=arch, rank=rank, world=world, n_step=args.n_step, noisy=args.noisy,
-                      acting_noise=args.acting_noise, **qkw, **hkw, **okw)
+                      acting_noise=args.acting_noise, **qkw, **hkw, **okw, **pkw)
         vb.run(args.steps or 1000, log_every=0 if (args.quiet or rank) else 100)
     else:
         playFlappyBird(args.model, args.steps, verbose=not args.quiet)

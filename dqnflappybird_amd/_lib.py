@@ -38,6 +38,7 @@ NOISE_SAMPLE, NOISE_MEAN = 0, 1                       # include/fbdqn.h FB_NOISE
 ACT_NOISE_SHARED, ACT_NOISE_PER_ENV = 0, 1            # include/fbdqn.h FB_ACT_NOISE_* (fb_qnet_set_acting_noise)
 DTYPE_F32, DTYPE_BF16 = 0, 1
 PER_EXACT, PER_FAST = 0, 1
+PER_INIT_MAX, PER_INIT_TD = 0, 1
 NIB_PITCH, NIB_ROWS, NIB_STRIDE = 44, 84, 3712       # include/fbdqn.h FB_NIB_*
 EVAL_MAX_ENVS, EVAL_MAX_EPISODES = 65536, 64         # include/fbdqn.h FB_EVAL_MAX_*
 NSTEP_MAX = 16                                        # include/fbdqn.h FB_NSTEP_MAX
@@ -75,6 +76,13 @@ SIGNATURES = {
     "fb_replay_profile_gather": [_vp, _i] + [_vp] * 6 + [_i, _vp],
     "fb_replay_update_priorities": [_vp, _i, _vp, _vp, _vp, _vp],
     "fb_replay_set_per_mode": [_vp, _i],
+    "fb_replay_set_priority_init": [_vp, _i],
+    "fb_replay_get_priority_init": [_vp, _vp],
+    "fb_replay_set_prime_gamma": [_vp, _d],
+    "fb_replay_get_prime_gamma": [_vp, _vp],
+    "fb_replay_prime_priorities": [_vp, _vp, _vp, _i, _vp],
+    "fb_replay_get_prime_state": [_vp, _vp, _sz, _vp, _vp],
+    "fb_replay_set_prime_state": [_vp, _vp, _sz, _i64, _i64],
     "fb_replay_set_n_step": [_vp, _i, _d],
     "fb_replay_get_n_step": [_vp, _vp, _vp],
     "fb_replay_create_nstep": [_i64, _i, _i, _i, _d, _vp],

@@ -385,6 +385,13 @@ int fb_replay_check_gamma(fb_replay_t h, double gamma, const char *who);
 // once `pushes_ahead` more pushes are counted -- fewer than n pushes since the reset; FB_OK for every other memory
 int fb_replay_check_complete(fb_replay_t h, int pushes_ahead, const char *who);
 double fb_replay_bootstrap_gamma(fb_replay_t h, double gamma);
+// FB_PER_INIT_TD memories (fb_replay_set_priority_init): the setting; at n = 1 the gamma a step trains with must be the one the memory
+// forms its TD priorities with (FB_ERR_INVALID naming `who` otherwise; FB_OK for every other memory); the online net's acting output
+int fb_replay_priority_init(fb_replay_t h);
+int fb_replay_check_prime_gamma(fb_replay_t h, double gamma, const char *who);
+// fb_replay_prime_priorities between fb_replay_begin_push_rider (the push is counted) and fb_replay_finish_push (its leaves are stored)
+int fb_replay_prime_before_finish(fb_replay_t h, const float *q, const uint8_t *actions, int n_actions, void *stream);
+const float *fb_qnet_acting_q(fb_qnet_t h);
 int fb_replay_update_priorities_keep(fb_replay_t h, int batch, const int64_t *idx, const float *abs_err, void *stream);       // in line, abs_err left untouched (fb_vec_step)
 int fb_replay_update_priorities_ahead(fb_replay_t h, int batch, const int64_t *idx, const float *abs_err, void *stream);      // batch_update on the side stream (see fb_replay.hip); 1 when issued
 int fb_replay_per_store_ahead(fb_replay_t h, void *stream);

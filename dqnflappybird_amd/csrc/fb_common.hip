@@ -173,6 +173,8 @@ int fb_ring_src_fresh(fb_replay_t replay, fb_qnet_t net, int batch, const int64_
 
 int fb_check_per_memory(fb_replay_t replay, double gamma, int pushes_ahead, const char *who, const char *uniform_calls) {
     FB_REQUIRE(fb_replay_is_prioritized(replay), "%s: trains from a prioritized memory only (%s take a uniform one)", who, uniform_calls);
+    FB_REQUIRE(fb_replay_priority_init(replay) != FB_PER_INIT_TD, "%s: does not take a FB_PER_INIT_TD memory (its priorities are losses, not |TD| of scalar "
+               "Q-values: fb_replay_set_priority_init)", who);
     const int rc = fb_replay_check_gamma(replay, gamma, who);
     return rc != FB_OK || pushes_ahead < 0 ? rc : fb_replay_check_complete(replay, pushes_ahead, who);
 }
@@ -364,6 +366,16 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
         const int rc2 = train ? fb_replay_check_complete(replay, 1, "fb_vec_step") : FB_OK;
         if (rc2 != FB_OK) return rc2;
     }
+    // a memory whose new leaves get their acting-time |TD error| (FB_PER_INIT_TD, include/fbdqn.h): the max-target scalar algos only
+    const bool prime = per && fb_replay_priority_init(replay) == FB_PER_INIT_TD;
+    if (prime) {
+        FB_REQUIRE(algo != FB_ALGO_MDQN_PER, "fb_vec_step: FB_ALGO_MDQN_PER does not take a FB_PER_INIT_TD memory (its target is a soft value, not a max)");
+        FB_REQUIRE((algo == FB_ALGO_PER || algo == FB_ALGO_DOUBLE_PER) && !fb_qnet_is_dist(net) && !fb_qnet_is_noisy(net),
+                   "fb_vec_step: a FB_PER_INIT_TD memory takes FB_ALGO_PER / FB_ALGO_DOUBLE_PER on a scalar net only, not a C51 / QR / noisy one "
+                   "(their priorities are losses, not |TD| of means) (algo %d)", algo);
+        const int rc3 = fb_replay_check_prime_gamma(replay, gamma, "fb_vec_step");
+        if (rc3 != FB_OK) return rc3;
+    }
     gamma = fb_replay_bootstrap_gamma(replay, gamma);       // (n-step memory: every train step below bootstraps with Gamma = gamma^n)
     // a noisy net: the online net's noise of this step, drawn before acting (acting and the train step below share it); the target net's
     // is drawn in front of the train step (target_noise)
@@ -469,6 +481,15 @@ extern "C" int fb_vec_step(fb_env_t env, fb_replay_t replay, fb_qnet_t net, cons
     rc = fb_env_step_rider(env, b->actions, nullptr, b->frame_bits, b->reward, b->terminal, b->score, have_s ? &srider : nullptr,
                            have_p ? &prider : nullptr, have_h ? &hrider : nullptr, stream);
     if (rc != FB_OK) return rc;
+    // FB_PER_INIT_TD: the leaves the previous push stored get |TD| from the Q-values just computed (their bootstrap state is the one just
+    // evaluated), and Q(s, a) of this step is recorded for the push that will complete it.  The header's order is act -> prime -> env
+    // step; the launch sits BEHIND the env launch because that is where the Q-values and actions come from when the acting head rides in it
+    // -- same results: the env launch writes the ring's row and frame of THIS step and nothing of the tree, the prime reads older rows, the
+    // tree and the pointer as the previous push left them, and the tree part of this push follows below
+    if (prime) {
+        rc = fb_replay_prime_before_finish(replay, fb_qnet_acting_q(net), b->actions, fb_qnet_num_actions(net), stream);      // (the push rider has counted the push)
+        if (rc != FB_OK) return rc;
+    }
     if (!have_p) {
         if (train && !have_s && !per) rc = fb_replay_push_sample(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, batch, b->idx, stream);
         else rc = fb_replay_push(replay, nullptr, b->frame_bits, b->actions, b->reward, b->terminal, stream);

@@ -151,6 +151,7 @@ extern "C" int fb_dist_set_overlap(fb_dist_t d, int overlap) {
 
 extern "C" int fb_vec_step_dp(fb_dist_t d, fb_env_t env, fb_replay_t replay, fb_qnet_t net, const fb_step_buffers *b, int n_envs, int algo,
                               int batch, float epsilon, uint64_t seed, uint64_t step, int train, double gamma, int mean_loss, void *stream) {
+    FB_REQUIRE(fb_replay_priority_init(replay) != FB_PER_INIT_TD, "fb_vec_step_dp: data parallel does not take a FB_PER_INIT_TD memory (fb_replay_set_priority_init)");
     FB_REQUIRE(!fb_qnet_is_noisy(net), "fb_vec_step_dp: data parallel does not take a noisy net (noisy nets are C51 nets: one GPU only)");
     FB_REQUIRE(!fb_qnet_is_ac(net), "fb_vec_step_dp: data-parallel A2C is not supported (an actor-critic net steps through fb_ac_rollout_step)");
     FB_REQUIRE(!fb_qnet_is_sac(net), "fb_vec_step_dp: data-parallel SAC is not supported (a SAC net steps through fb_sac_step)");

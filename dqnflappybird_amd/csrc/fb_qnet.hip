@@ -5139,6 +5139,7 @@ extern "C" int fb_qnet_act_nib(fb_qnet_t h, const uint8_t *nib_states, int n, fl
 }
 
 int fb_qnet_num_actions(fb_qnet_t h) { return h ? h->A : 0; }
+const float *fb_qnet_acting_q(fb_qnet_t h) { return h ? h->q : nullptr; }      // f32[n][A] of the rows the last plan ran
 int fb_qnet_is_c51(fb_qnet_t h) { return h && h->sup.N > 0 && !is_qr(h); }
 int fb_qnet_is_qr(fb_qnet_t h) { return h && is_qr(h); }
 int fb_qnet_is_dist(fb_qnet_t h) { return h && h->sup.N > 0; }

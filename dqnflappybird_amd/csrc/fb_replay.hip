@@ -739,6 +739,71 @@ __global__ __launch_bounds__(256) void per_sample_kernel(ReplayParams P, int n, 
     if (tid == 0) { P.dev->beta = beta; P.dev->philox_calls = call + 1; }
 }
 
+// FB_PER_INIT_TD (include/fbdqn.h, fb_replay_prime_priorities): the N leaves the last push stored at max_p get the priority of their
+// acting-time TD error, and this step's Q(s, a) is recorded for the push that will complete it.  One launch, one workgroup:
+//   1) thread e (strided): (R, done) of time slot `steps - n`, env e -- the ring's own n-step read (fb_nstep_return, which at n = 1 is the
+//      row itself) --, y = done ? R : R + Gamma max_a q[e][a] in float64, delta = (float)|y - rec_old[e]|, p = batch_update's formula as
+//      per_update_fast_kernel has it; leaf of data slot (per_pointer - N + e) mod cap: tree = maxt = mint = p.  Then rec_new[e] = q[e][a_e].
+//      (rec_old and rec_new are different rows of the record ring, so the order of the two inside the pass does not matter.)
+//   2) the ancestors, per_store_fast_kernel's range walk: per segment (no ring wrap, no depth change inside one) one level per pass, a
+//      barrier between passes, every node left + right / max / min of its children (per_refresh_node).  All leaves are final before the
+//      first pass; an ancestor two segments share is refreshed by both walks, the later one reading final children.
+// No atomics, no reductions: every value written is a function of the leaves alone, whatever the thread order.
+// (defined behind every other kernel of this file, so that those keep their places in the code object)
+struct PrimeArgs {
+    long long steps;                 // pushes counted so far (S): the leaves are those of time slot S - n
+    int do_prime;                    // the record holds time slot S - n and push S stored N leaves
+    double Gamma;                    // the bootstrap discount (gamma^n as the ring's running product; the memory's prime gamma at n = 1)
+    const float *q; const uint8_t *actions; int A;
+    const float *rec_old; float *rec_new;
+};
+
+__global__ __launch_bounds__(1024) void per_prime_kernel(ReplayParams P, PrimeArgs K) {
+    const int tid = threadIdx.x;
+    const long long N = P.n_envs;
+    const long long s0 = (P.dev->per_pointer - N + P.cap) % P.cap;      // first data slot of the last store (N <= cap)
+    if (K.do_prime) {
+        const FbGatherCtx G = gather_ctx(P);
+        for (long long e = tid; e < N; e += 1024) {
+            float R; uint8_t done;
+            fb_nstep_return(G, K.steps - P.nstep, (int)e, R, done);
+            float m = K.q[e * K.A];
+            for (int a = 1; a < K.A; a++) { const float v = K.q[e * K.A + a]; m = v > m ? v : m; }
+            double y = (double)R;
+            if (!done) { const double boot = K.Gamma * (double)m; y = y + boot; }
+            const float delta = (float)fabs(y - (double)K.rec_old[e]);
+            const float ee = delta + 0.01f;
+            const float c = ee < 1.0f ? ee : 1.0f;
+            const double p = (double)(float)pow((double)c, (double)0.6f);
+            long long slot = s0 + e;
+            if (slot >= P.cap) slot -= P.cap;
+            const long long leaf = slot + P.cap - 1;
+            P.tree[leaf] = p; P.maxt[leaf] = p; P.mint[leaf] = p;
+        }
+    }
+    for (long long e = tid; e < N; e += 1024) {
+        int a = K.actions[e];
+        if (a >= K.A) { P.dev->error = 1; a = 0; }
+        K.rec_new[e] = K.q[e * K.A + a];
+    }
+    if (!K.do_prime) return;                                     // (uniform over the block)
+    const int Dmax = node_depth(2 * P.cap - 2);
+    const long long deep0 = ((1ll << Dmax) - 1) - (P.cap - 1);
+    long long left = N, lo = s0;
+    while (left > 0) {
+        long long n = left < P.cap - lo ? left : P.cap - lo;
+        if (lo < deep0 && lo + n > deep0) n = deep0 - lo;
+        long long a = lo + P.cap - 1, b = a + n - 1;             // heap range of this segment's leaves
+        while (a > 0) {
+            __threadfence_block();
+            __syncthreads();
+            a = (a - 1) >> 1; b = (b - 1) >> 1;
+            for (long long i = a + tid; i <= b; i += 1024) per_refresh_node(P, i);
+        }
+        left -= n; lo = (lo + n) % P.cap;
+    }
+}
+
 }  // namespace
 
 struct fb_replay {
@@ -753,6 +818,12 @@ struct fb_replay {
     bool store_ahead;                // the tree part of the next fb_replay_push has been issued already; that push joins it
     bool upd_pending;                // a batch_update runs on the side stream (fb_replay_update_priorities_ahead): whatever touches the tree next joins it
     bool store_forked;               // the run-ahead store was ordered behind the caller's stream by an event of its own (a sample behind it needs no second one)
+    // FB_PER_INIT_TD (fb_replay_prime_priorities): the record of acting-time Q(s_t, a_t), a ring of n + 1 rows of f32[N]; rows
+    // prime_first .. prime_last (push counts at their record, consecutive) are held, -1 = none
+    int prio_init;                   // FB_PER_INIT_MAX | FB_PER_INIT_TD
+    float *rec;
+    long long prime_first, prime_last;
+    double prime_gamma;              // the one-step discount of an n = 1 memory's TD errors (an n-step memory has its own)
     const void *side_for; bool side_checked; int side_ok; int side_prio;      // the caller's stream `side` has been checked against (fb_side_stream_beside; NULL is a stream too), the verdict, its priority
 };
 
@@ -786,6 +857,7 @@ static int replay_create(int64_t capacity, int n_envs, int kind, int ring_n, fb_
     ReplayParams &P = h->P;
     P.cap = capacity; P.n_envs = n_envs; P.kind = kind;
     P.nstep = 1; P.gamma = 0.0;
+    h->prime_first = h->prime_last = -1; h->prime_gamma = 0.99;
     P.t_f = (int)((capacity + n_envs - 1) / n_envs) + ring_n + 5;
     const size_t slots = (size_t)P.t_f * n_envs;
     // (the ring and its rows start as zeros: slots that have never been pushed to hold nothing of an earlier allocation, and equal
@@ -860,7 +932,7 @@ extern "C" int fb_replay_create_nstep(int64_t capacity, int n_envs, int kind, in
 extern "C" int fb_replay_destroy(fb_replay_t h) {
     if (!h) return FB_OK;
     ReplayParams &P = h->P;
-    void *ptrs[] = {P.bits, P.act, P.rew, P.term, P.dev, P.mt, P.tree, P.maxt, P.mint};
+    void *ptrs[] = {P.bits, P.act, P.rew, P.term, P.dev, P.mt, P.tree, P.maxt, P.mint, h->rec};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->side) { (void)hipStreamSynchronize(h->side); (void)hipStreamDestroy(h->side); }
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -889,6 +961,7 @@ extern "C" int fb_replay_seed(fb_replay_t h, int rng_kind, uint64_t seed) {
 extern "C" int fb_replay_reset(fb_replay_t h, const uint8_t *frames, const uint64_t *frame_bits, void *stream) {
     FB_REQUIRE(h, "fb_replay_reset: NULL handle");
     h->host_steps = 0;
+    h->prime_first = h->prime_last = -1;     // (the record of acting-time Q-values belongs to the life that ends here)
     ReplayParams &P = h->P;
     hipStream_t st = fb_stream(stream);
     if (P.kind == FB_REPLAY_PER) {
@@ -1223,7 +1296,119 @@ int fb_replay_update_priorities_ahead(fb_replay_t h, int batch, const int64_t *i
 extern "C" int fb_replay_set_per_mode(fb_replay_t h, int mode) {
     FB_REQUIRE(h && (mode == FB_PER_EXACT || mode == FB_PER_FAST), "fb_replay_set_per_mode: mode must be FB_PER_EXACT or FB_PER_FAST");
     FB_REQUIRE(h->P.kind == FB_REPLAY_PER, "fb_replay_set_per_mode: not a prioritized memory");
+    FB_REQUIRE(mode == FB_PER_FAST || h->prio_init != FB_PER_INIT_TD,
+               "fb_replay_set_per_mode: FB_PER_EXACT is refused while the memory's priority init is FB_PER_INIT_TD (the reference has no such "
+               "operation, so there is no update order to reproduce)");
     h->per_mode = mode;
+    return FB_OK;
+}
+
+// ---- FB_PER_INIT_TD: initial priorities from acting-time TD errors (include/fbdqn.h)
+static size_t prime_rec_floats(const fb_replay *h) { return (size_t)(h->P.nstep + 1) * (size_t)h->P.n_envs; }
+
+extern "C" int fb_replay_set_priority_init(fb_replay_t h, int mode) {
+    FB_REQUIRE(h && (mode == FB_PER_INIT_MAX || mode == FB_PER_INIT_TD), "fb_replay_set_priority_init: mode must be FB_PER_INIT_MAX or FB_PER_INIT_TD");
+    FB_REQUIRE(h->P.kind == FB_REPLAY_PER, "fb_replay_set_priority_init: not a prioritized memory");
+    if (mode == FB_PER_INIT_TD) {
+        FB_REQUIRE(h->per_mode == FB_PER_FAST, "fb_replay_set_priority_init: FB_PER_INIT_TD needs a memory in FB_PER_FAST (fb_replay_set_per_mode); the "
+                   "reference's exact mode has no update order for it");
+        FB_REQUIRE(h->P.cap >= h->P.n_envs, "fb_replay_set_priority_init: FB_PER_INIT_TD needs capacity %lld >= n_envs %d (one push must not wrap onto itself)",
+                   (long long)h->P.cap, h->P.n_envs);
+        if (!h->rec) {
+            FB_CHECK_HIP(hipMalloc(&h->rec, prime_rec_floats(h) * sizeof(float)));
+            FB_CHECK_HIP(hipMemset(h->rec, 0, prime_rec_floats(h) * sizeof(float)));
+        }
+    }
+    h->prio_init = mode;
+    h->prime_first = h->prime_last = -1;     // switching clears the record
+    return FB_OK;
+}
+
+extern "C" int fb_replay_get_priority_init(fb_replay_t h, int *mode_host) {
+    FB_REQUIRE(h && mode_host, "fb_replay_get_priority_init: NULL argument");
+    *mode_host = h->prio_init;
+    return FB_OK;
+}
+int fb_replay_priority_init(fb_replay_t h) { return h ? h->prio_init : FB_PER_INIT_MAX; }
+
+extern "C" int fb_replay_set_prime_gamma(fb_replay_t h, double gamma) {
+    FB_REQUIRE(h && h->P.kind == FB_REPLAY_PER, "fb_replay_set_prime_gamma: not a prioritized memory");
+    FB_REQUIRE(gamma >= 0.0 && gamma <= 1.0, "fb_replay_set_prime_gamma: gamma %.17g is outside [0, 1]", gamma);
+    FB_REQUIRE(h->P.nstep == 1 || gamma == h->P.gamma, "fb_replay_set_prime_gamma: gamma %.17g differs from the gamma %.17g of the memory's %d-step view",
+               gamma, h->P.gamma, h->P.nstep);
+    h->prime_gamma = gamma;
+    return FB_OK;
+}
+
+extern "C" int fb_replay_get_prime_gamma(fb_replay_t h, double *gamma_host) {
+    FB_REQUIRE(h && gamma_host && h->P.kind == FB_REPLAY_PER, "fb_replay_get_prime_gamma: bad argument");
+    *gamma_host = h->P.nstep == 1 ? h->prime_gamma : h->P.gamma;
+    return FB_OK;
+}
+
+int fb_replay_check_prime_gamma(fb_replay_t h, double gamma, const char *who) {
+    if (h->prio_init != FB_PER_INIT_TD || h->P.nstep > 1) return FB_OK;      // (an n-step memory: fb_replay_check_gamma)
+    FB_REQUIRE(gamma == h->prime_gamma, "%s: gamma %.17g differs from the gamma %.17g the memory's FB_PER_INIT_TD priorities are formed with "
+               "(fb_replay_set_prime_gamma)", who, gamma, h->prime_gamma);
+    return FB_OK;
+}
+
+// S: the pushes the tree has seen the store of -- the memory's count, or one less between fb_replay_begin_push_rider and fb_replay_finish_push
+static int prime_at(fb_replay *h, long long S, const float *q, const uint8_t *actions, int n_actions, void *stream) {
+    FB_REQUIRE(h && q && actions, "fb_replay_prime_priorities: NULL argument");
+    FB_REQUIRE(h->P.kind == FB_REPLAY_PER && h->prio_init == FB_PER_INIT_TD, "fb_replay_prime_priorities: the memory's priority init is not FB_PER_INIT_TD "
+               "(fb_replay_set_priority_init)");
+    FB_REQUIRE(n_actions >= 1 && n_actions <= 256, "fb_replay_prime_priorities: n_actions %d is outside 1..256", n_actions);
+    const ReplayParams &P = h->P;
+    hipStream_t st = fb_stream(stream);
+    const int rcj = per_join(h, st);
+    if (rcj != FB_OK) return rcj;
+    const long long rows = P.nstep + 1;
+    PrimeArgs K;
+    K.steps = S;
+    // the last push stored N leaves (S >= n) and the record holds their time slot S - n
+    K.do_prime = S >= P.nstep && h->prime_first >= 0 && h->prime_first <= S - P.nstep && h->prime_last >= S - 1 ? 1 : 0;
+    K.Gamma = fb_replay_bootstrap_gamma(h, h->prime_gamma);
+    K.q = q; K.actions = actions; K.A = n_actions;
+    K.rec_old = h->rec + (size_t)((S - P.nstep + rows) % rows) * P.n_envs;
+    K.rec_new = h->rec + (size_t)(S % rows) * P.n_envs;
+    hipLaunchKernelGGL(per_prime_kernel, dim3(1), dim3(1024), 0, st, P, K);
+    FB_LAUNCH_CHECK();
+    if (h->prime_first < 0 || (h->prime_last != S && h->prime_last != S - 1)) h->prime_first = S;      // (the first row, or a gap: what was recorded before it is not consecutive)
+    h->prime_last = S;
+    return FB_OK;
+}
+
+extern "C" int fb_replay_prime_priorities(fb_replay_t h, const float *q, const uint8_t *actions, int n_actions, void *stream) {
+    return prime_at(h, h ? h->host_steps : 0, q, actions, n_actions, stream);
+}
+
+// fb_vec_step's: the same call between fb_replay_begin_push_rider -- which has counted the push the env launch carries -- and
+// fb_replay_finish_push, which stores its leaves: the tree and the record still stand where they stood before that push was counted
+int fb_replay_prime_before_finish(fb_replay_t h, const float *q, const uint8_t *actions, int n_actions, void *stream) {
+    return prime_at(h, h ? h->host_steps - 1 : 0, q, actions, n_actions, stream);
+}
+
+extern "C" int fb_replay_get_prime_state(fb_replay_t h, float *rows_host, size_t floats, int64_t *first_host, int64_t *last_host) {
+    FB_REQUIRE(h && rows_host && first_host && last_host, "fb_replay_get_prime_state: NULL argument");
+    FB_REQUIRE(h->prio_init == FB_PER_INIT_TD && h->rec, "fb_replay_get_prime_state: the memory's priority init is not FB_PER_INIT_TD");
+    FB_REQUIRE(floats == prime_rec_floats(h), "fb_replay_get_prime_state: the record is (n + 1) x n_envs = %zu floats, %zu given", prime_rec_floats(h), floats);
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    FB_CHECK_HIP(hipMemcpy(rows_host, h->rec, floats * sizeof(float), hipMemcpyDeviceToHost));
+    *first_host = h->prime_first; *last_host = h->prime_last;
+    return FB_OK;
+}
+
+extern "C" int fb_replay_set_prime_state(fb_replay_t h, const float *rows_host, size_t floats, int64_t first, int64_t last) {
+    FB_REQUIRE(h && rows_host, "fb_replay_set_prime_state: NULL argument");
+    FB_REQUIRE(h->prio_init == FB_PER_INIT_TD && h->rec, "fb_replay_set_prime_state: the memory's priority init is not FB_PER_INIT_TD");
+    FB_REQUIRE(floats == prime_rec_floats(h), "fb_replay_set_prime_state: the record is (n + 1) x n_envs = %zu floats, %zu given", prime_rec_floats(h), floats);
+    FB_REQUIRE((first == -1 && last == -1) || (first >= 0 && first <= last && last <= h->host_steps),
+               "fb_replay_set_prime_state: rows %lld .. %lld are not a range of push counts up to the memory's %lld", (long long)first, (long long)last,
+               h->host_steps);
+    FB_CHECK_HIP(hipDeviceSynchronize());
+    FB_CHECK_HIP(hipMemcpy(h->rec, rows_host, floats * sizeof(float), hipMemcpyHostToDevice));
+    h->prime_first = first; h->prime_last = last;
     return FB_OK;
 }
 
@@ -1341,6 +1526,8 @@ extern "C" int fb_replay_load_state(fb_replay_t h, const void *blob_host, size_t
                "n = %d (%d)", hd.t_f - t_f1 + 1, hd.t_f, h->P.t_f - t_f1 + 1, h->P.t_f);
     FB_REQUIRE(hd.total_bytes == need && bytes >= need, "fb_replay_load_state: the checkpoint holds %llu bytes, this memory's state is %zu (%zu given)",
                (unsigned long long)hd.total_bytes, need, bytes);
+    FB_REQUIRE(h->prio_init != FB_PER_INIT_TD || hd.per_mode == FB_PER_FAST, "fb_replay_load_state: the checkpoint is of a memory in FB_PER_EXACT; this one's "
+               "priority init is FB_PER_INIT_TD, which takes FB_PER_FAST only");
     FB_CHECK_HIP(hipDeviceSynchronize());
     BlobPart parts[9];
     const int n = blob_parts(h, parts);
@@ -1350,5 +1537,6 @@ extern "C" int fb_replay_load_state(fb_replay_t h, const void *blob_host, size_t
         o += (parts[i].bytes + 15) & ~(size_t)15;
     }
     h->host_steps = hd.host_steps; h->P.rng_kind = hd.rng_kind; h->per_mode = hd.per_mode; h->P.seed_lo = hd.seed_lo; h->P.seed_hi = hd.seed_hi;
+    h->prime_first = h->prime_last = -1;     // (the blob keeps its format: the record travels through fb_replay_set_prime_state, behind this call)
     return FB_OK;
 }

@@ -233,6 +233,49 @@ class VecReplay:
         L.check(L.lib().fb_replay_set_per_mode(self.h, {"exact": L.PER_EXACT, "fast": L.PER_FAST}[mode]),
                 "fb_replay_set_per_mode")
 
+    def set_priority_init(self, mode="max", gamma=None):
+        """Which priority a new transition's leaf gets: 'max' (the tree's maximum, the reference's Memory.store) or 'td' (the |TD error|
+        of the Q-values the actor computed, written one step later by prime(); fb_replay_set_priority_init: a prioritized memory in the
+        fast mode only).  Switching clears the record of acting-time Q-values.  gamma: the one-step discount of those TD errors on an
+        n = 1 memory (0.99 until set; an n-step memory uses its own, and a gamma given here must equal it)."""
+        if mode not in PRIORITY_INITS:
+            raise ValueError(f"priority_init must be one of {PRIORITY_INITS}, got {mode!r}")
+        L.check(L.lib().fb_replay_set_priority_init(self.h, {"max": L.PER_INIT_MAX, "td": L.PER_INIT_TD}[mode]),
+                "fb_replay_set_priority_init")
+        if gamma is not None:
+            L.check(L.lib().fb_replay_set_prime_gamma(self.h, float(gamma)), "fb_replay_set_prime_gamma")
+
+    @property
+    def priority_init(self):
+        v = C.c_int()
+        L.check(L.lib().fb_replay_get_priority_init(self.h, C.byref(v)), "fb_replay_get_priority_init")
+        return PRIORITY_INITS[v.value]
+
+    def prime(self, q, actions):
+        """fb_replay_prime_priorities: q float32[N,A] = Q(s, .) of the current states and the actions uint8[N] taken there, once per
+        step between the acting forward and the push.  The leaves the last push stored get the priority of their |TD error| (when the
+        record holds their Q(s_t, a_t)), then q[e, actions[e]] is recorded."""
+        _dev_check(q, actions)
+        if q.dtype != torch.float32 or q.dim() != 2 or q.shape[0] != self.n or not q.is_contiguous():
+            raise ValueError(f"q must be a contiguous float32[{self.n}, A] tensor")
+        if actions.dtype != torch.uint8 or actions.numel() != self.n:
+            raise ValueError(f"actions must be uint8[{self.n}]")
+        L.check(L.lib().fb_replay_prime_priorities(self.h, L.ptr(q), L.ptr(actions), int(q.shape[1]), L.current_stream()),
+                "fb_replay_prime_priorities")
+
+    def prime_state(self):
+        """(rows float32[n + 1, N], first, last): the record of acting-time Q-values and the push counts of the oldest and newest rows
+        held (-1, -1: none).  With state_blob() it is what a resumed 'td' memory needs to continue bit for bit."""
+        rows = np.empty((self.n_step[0] + 1, self.n), np.float32)
+        first, last = C.c_int64(), C.c_int64()
+        L.check(L.lib().fb_replay_get_prime_state(self.h, L.ptr(rows), rows.size, C.byref(first), C.byref(last)),
+                "fb_replay_get_prime_state")
+        return rows, first.value, last.value
+
+    def load_prime_state(self, rows, first, last):
+        rows = np.ascontiguousarray(rows, np.float32)
+        L.check(L.lib().fb_replay_set_prime_state(self.h, L.ptr(rows), rows.size, int(first), int(last)), "fb_replay_set_prime_state")
+
     def set_n_step(self, n, gamma):
         """View the memory with n-step returns (fb_replay_set_n_step; uniform memories, 1 <= n <= 16, capacity >= n * n_envs): sample /
         gather / the ring-fed train calls then see (s_t, a_t, R, s_{t+n}, done) and bootstrap with gamma^n.  n = 1 restores the one-step
@@ -296,6 +339,7 @@ MDQN_ALGOS = ("mdqn",)                                      # Munchausen-DQN on 
 MDQN_PER_ALGOS = ("mdqnper",)                               # Munchausen-DQN on a prioritized memory (FB_ALGO_PER's weights and |TD errors|)
 DOUBLE_PER_ALGOS = ("doubleper",)                           # Double-DQN's target on a prioritized memory (scalar heads; include/fbdqn.h)
 WEIGHTED_ALGOS = PRIORITIZED_ALGOS + MDQN_PER_ALGOS + DOUBLE_PER_ALGOS     # every algo that takes a prioritized memory and its importance weights
+PRIORITY_INITS = ("max", "td")                             # a new leaf's priority: the tree's maximum, or the acting-time |TD error| (VecReplay.set_priority_init)
 SCALAR_ALGOS = ("dqn", "nature", "double", "per", "mdqn", "mdqnper", "doubleper")      # the TD algos of the scalar heads: what the Huber loss applies to
 MDQN_DEFAULTS = L.MDQN_DEFAULTS                             # (tau, alpha, l0) of a new scalar net
 C51_DEFAULT_SUPPORT = (51, -10.0, 10.0)                  # n_atoms, v_min, v_max

@@ -43,6 +43,7 @@ class HipVecBackend:
     name = "hip-gfx950"
     per_one_step = True                                      # fb_vec_step runs the prioritized step too (store, Memory.sample, train, batch_update)
     per_n_step = True                                        # prioritized memories with n-step returns (replay(..., n_step, gamma))
+    per_priority_init = True                                 # new leaves at their acting-time |TD error| (replay.set_priority_init('td'), primed inside step())
 
     def env(self, n_envs, seed):
         from .vec import VecGameState
@@ -300,12 +301,43 @@ def resolve_args(be, algo, arch, world, n_step, noisy, acting_noise, initial_eps
     return arch, support, quantiles, munchausen, delta, limit, rho, initial_epsilon
 
 
+PRIORITY_INIT_ALGOS = ("per", "doubleper")                   # ... which the acting Q-values give for a max target on a scalar head only
+
+
+def check_priority_init(be, algo, world, priority_init):
+    """the refusals of VecBrain(priority_init=...), before anything touches the GPU -> the setting.  'td' (Ape-X initial priorities,
+    include/fbdqn.h fb_replay_set_priority_init): algo 'per' / 'doubleper', one rank, a backend with per_priority_init and the one-call
+    prioritized step that issues the prime (per_one_step: the composed-calls fallback of step() never primes)"""
+    from .vec import PRIORITY_INITS
+    if priority_init not in PRIORITY_INITS:
+        raise ValueError(f"priority_init must be one of {PRIORITY_INITS}, got {priority_init!r}")
+    if priority_init == "max":
+        return priority_init
+    if algo == "mdqnper":
+        raise ValueError(f"priority_init='td' is not offered with algo {algo!r}: its target is a soft value, not the max the acting Q-values give")
+    if algo not in PRIORITY_INIT_ALGOS:
+        raise ValueError(f"priority_init='td' needs algo 'per' or 'doubleper' (|TD| of a scalar head's max target), not {algo!r}")
+    if world > 1:
+        raise ValueError(f"priority_init='td': data parallel is not supported (world = {world}; one GPU only)")
+    require(be, "per_priority_init", "has no TD initial priorities (per_priority_init): priority_init='td' needs it")
+    require(be, "per_one_step", "has no one-call prioritized step (per_one_step): priority_init='td' is primed inside it")
+    return priority_init
+
+
+def check_checkpoint_priority_init(z, priority_init, path):
+    """a checkpoint's memory was filled under the setting it records (no key: 'max' -- every checkpoint of before the setting, and every
+    one a 'max' brain writes); a brain takes one written under its own setting only"""
+    saved = str(z["priority_init"][0]) if "priority_init" in z.files else "max"
+    if saved != priority_init:
+        raise ValueError(f"checkpoint {path} was written with priority_init = {saved!r}, this VecBrain has priority_init = {priority_init!r}")
+
+
 class VecBrain:
     def __init__(self, n_envs, algo="dqn", arch="plain", batch=32, capacity=1_000_000, fc_width=512, seed=0,
                  observe=1000, explore=1_000_000, initial_epsilon=None, final_epsilon=0.0, gamma=0.99,
                  replace_target_iter=500, sampler=None, rank=0, world=1, backend=None, n_step=1, n_atoms=51, v_min=-10.0, v_max=10.0,
                  noisy=False, sigma0=0.5, acting_noise="shared", n_quantiles=51, kappa=1.0, tau=0.03, alpha=0.9, clip=-1.0, huber=0.0,
-                 max_grad_norm=0.0, polyak=0.0):
+                 max_grad_norm=0.0, polyak=0.0, priority_init="max"):
         """n_step > 1: learn from n-step returns (include/fbdqn.h: the uniform replay's n-step view, fb_replay_set_n_step; a prioritized
         memory created with n-step returns, fb_replay_create_nstep, on a backend with per_n_step).
         algo 'c51' / 'c51double': distributional Q-learning on n_atoms atoms over [v_min, v_max] (one GPU, uniform replay, plain trunk);
@@ -328,8 +360,12 @@ class VecBrain:
         include/fbdqn.h); world > 1: the reduced gradient is clipped, so every rank applies the same scale.  run() logs the last norm.
         polyak=rho in (0, 1] (every algo): after every train step target += rho (online - target) (net.soft_sync_target), and the hard
         copy every replace_target_iter steps is dropped.  This gives the 'per' family -- 'per', whose target net the reference agent never
-        syncs, included -- a moving target.  Both are optimiser settings: checkpoints record them, load() does not refuse another value."""
+        syncs, included -- a moving target.  Both are optimiser settings: checkpoints record them, load() does not refuse another value.
+        priority_init='td' (algo 'per' / 'doubleper', world 1): a new transition's leaf gets the |TD error| of the Q-values computed to act
+        (Ape-X; include/fbdqn.h fb_replay_prime_priorities) one step after its store instead of waiting at the tree's maximum to be
+        sampled; the memory runs in its fast mode.  'max': the reference's Memory.store.  Checkpoints record it."""
         n_step, noisy, be = int(n_step), bool(noisy), backend or HipVecBackend()
+        self.priority_init = check_priority_init(be, algo, world, priority_init)
         (arch, self.support, self.quantiles, self.munchausen, self.huber, self.max_grad_norm, self.polyak, initial_epsilon) = resolve_args(
             be, algo, arch, world, n_step, noisy, acting_noise, initial_epsilon, n_atoms, v_min, v_max, n_quantiles, kappa, tau, alpha, clip, huber,
             max_grad_norm, polyak)                           # (every refusal but the two below comes before anything touches the GPU)
@@ -354,6 +390,9 @@ class VecBrain:
             if not hasattr(self.replay, "set_n_step"):
                 raise ValueError(f"the {backend_name(be)} backend's replay has no n-step view (n_step = {n_step})")
             self.replay.set_n_step(n_step, gamma)
+        if self.priority_init == "td":                       # (the level-wise tree: the reference has no update order for this store)
+            self.replay.set_per_mode("fast")
+            self.replay.set_priority_init("td", gamma)
         self.arch = arch
         self.noisy = noisy
         self.sigma0 = None
@@ -525,6 +564,9 @@ class VecBrain:
                 shared["max_grad_norm"] = np.array([self.max_grad_norm], np.float64)
             if self.polyak:
                 shared["polyak"] = np.array([self.polyak], np.float64)
+            if self.priority_init == "td":                   # (no key: 'max'; world 1 only) with the record of acting-time Q-values
+                rows, first, last = self.replay.prime_state()
+                shared.update(priority_init=np.array(["td"]), prime_rows=rows, prime_span=np.array([first, last], np.int64))
             if self.noisy:                                   # online / target / Adam hold [mu | sigma] (checkpoints without it: not noisy)
                 shared["noisy"] = np.array([1], np.int64)
                 shared["sigma0"] = np.array([self.sigma0], np.float64)
@@ -555,11 +597,14 @@ class VecBrain:
         check_checkpoint_noisy(z, self.noisy, self.sigma0, path)
         check_checkpoint_munchausen(z, self.munchausen, path)
         check_checkpoint_huber(z, self.huber, path)
+        check_checkpoint_priority_init(z, self.priority_init, path)
         # (max_grad_norm / polyak: optimiser settings, like the learning rate -- this brain's own values go on, whatever the file records)
         self.checkpoint_optimiser = checkpoint_optimiser(z)
         zl = np.load(self._local_path(path)) if self.world > 1 else z
         dev = self.be.to_device if hasattr(self.be, "to_device") else np.ascontiguousarray
         restore_core(z, self.net, self.env, self.nib, self.stats, self.replay, dev, local=zl)
+        if self.priority_init == "td":                       # (behind the memory's blob, which clears the record)
+            self.replay.load_prime_state(z["prime_rows"], *z["prime_span"].tolist())
         self.timeStep, self.onlineTimeStep = int(z["scalars"][0]), int(z["scalars"][1])
         if len(z["scalars"]) > 3:
             self.seed = int(z["scalars"][3])                     # the key of the acting (epsilon-greedy) stream: (seed + rank, timeStep)

@@ -194,6 +194,45 @@ int fb_replay_update_priorities(fb_replay_t h, int batch, const int64_t *idx, fl
 #define FB_PER_EXACT 0
 #define FB_PER_FAST 1
 int fb_replay_set_per_mode(fb_replay_t h, int mode);
+/* Which priority a NEW transition's leaf gets (prioritized memories only):
+ *   FB_PER_INIT_MAX (default) the tree's maximum, the reference's Memory.store: a leaf gets a TD-based priority only once it has been
+ *                sampled and trained on.  With this setting every call is what it was before the setting existed.
+ *   FB_PER_INIT_TD  the |TD error| the actor can form from the Q-values it computed to act (Ape-X, Horgan et al. 2018).  Accepted on a
+ *                prioritized memory in FB_PER_FAST with capacity >= n_envs only: the reference has no such operation, so FB_PER_EXACT has
+ *                no update order to reproduce.  A uniform memory, a FB_PER_EXACT memory, capacity < n_envs: FB_ERR_INVALID before anything
+ *                is allocated.  While it is on, fb_replay_set_per_mode(FB_PER_EXACT) and fb_replay_load_state of a FB_PER_EXACT blob are
+ *                FB_ERR_INVALID.  The store itself is unchanged (fb_replay_push writes max_p); the leaves are rewritten one step later by
+ * fb_replay_prime_priorities(h, q f32[N,A] [dev], actions u8[N] [dev], n_actions, stream), issued once per step AFTER the acting forward
+ *   has produced q = Q(s_S, .) and the actions a_S for the current state (S = pushes since the reset) and BEFORE push S + 1.  In this order:
+ *   1. Prime -- only if push S stored N leaves (S >= n) and the record holds rec[t] for their time slot t = S - n.  For env e
+ *        y     = done ? R : R + Gamma * max_a q[e,a]      in float64 (product, then sum: no fused multiply-add); (R, done) is the ring's
+ *                n-step read of transition (t, e) exactly as fb_replay_gather delivers it (n = 1: the row itself), Gamma = gamma^n as
+ *                the running product of the memory's gamma; at n = 1, where the memory holds no discount, the value of
+ *                fb_replay_set_prime_gamma (0.99, the reference's GAMMA, until set)
+ *        delta = (float)|y - (double)rec[t][e]|
+ *        p     = (float)pow((double)min(delta + 0.01f, 1.0f), (double)0.6f)            Memory.batch_update's formula
+ *      and the leaf of data slot (data_pointer - N + e) mod capacity -- the leaves push S stored, in env order -- becomes p in the sum,
+ *      max and min heaps; every ancestor is recomputed level by level as in FB_PER_FAST.  No atomics and no reductions: the tree is a
+ *      function of its leaves alone.  A leaf among them that step S's fb_replay_update_priorities already updated IS OVERWRITTEN by
+ *      its acting-time value.  Otherwise (the first n calls after a reset, after a switch of the setting, after fb_replay_load_state
+ *      without fb_replay_set_prime_state, after a step without this call) the leaves keep their max_p.
+ *   2. Record -- rec[S][e] = q[e, actions[e]] in a ring of n + 1 rows of f32[N] the memory owns (an action >= n_actions raises the
+ *      memory's index error, reported by fb_replay_size, and records q[e,0]).
+ *   FB_ERR_INVALID: a memory that is not FB_PER_INIT_TD, NULL q / actions, n_actions outside 1..256.
+ * fb_replay_set_priority_init and fb_replay_reset clear the record.  fb_replay_get_prime_state / _set_prime_state read and write the
+ * record ([host] f32[(n + 1) * N], `floats` must say so) and the two counters first / last (the push counts of the oldest and newest
+ * consecutive rows held, -1 / -1 = none); synchronous; with them behind fb_replay_save_state / fb_replay_load_state a checkpoint resumes
+ * bit for bit.  The memory's state blob keeps its format.
+ * fb_vec_step on a FB_PER_INIT_TD memory issues the call itself (see there). */
+#define FB_PER_INIT_MAX 0
+#define FB_PER_INIT_TD 1
+int fb_replay_set_priority_init(fb_replay_t h, int mode);
+int fb_replay_get_priority_init(fb_replay_t h, int *mode_host);
+int fb_replay_set_prime_gamma(fb_replay_t h, double gamma);       /* n-step memory: must equal the memory's gamma */
+int fb_replay_get_prime_gamma(fb_replay_t h, double *gamma_host);
+int fb_replay_prime_priorities(fb_replay_t h, const float *q, const uint8_t *actions, int n_actions, void *stream);
+int fb_replay_get_prime_state(fb_replay_t h, float *rows_host, size_t floats, int64_t *first_host, int64_t *last_host);
+int fb_replay_set_prime_state(fb_replay_t h, const float *rows_host, size_t floats, int64_t first, int64_t last);
 /* n-step returns (Ape-X / R2D2 style) as a different READ of the same ring -- nothing new is stored, the state blob is unchanged.
  * With n steps and discount gamma, transition t of env e (the deque position j of the one-step memory, see below) is
  *   s      frames t-3 .. t of env e (as at n = 1), a = act[t]
@@ -1095,6 +1134,13 @@ const char *fb_qnet_kernel_name(int kernel);
  * All pointers [dev], caller owned; nib is the buffer given to fb_env_set_nib_buffer.  train = 0 stops after the
  * store (the reference's OBSERVE phase).  flat_grad as in fb_qnet_train_step (data parallel: all-reduce it, then
  * fb_qnet_apply_adam).
+ * A prioritized memory set to FB_PER_INIT_TD (fb_replay_set_priority_init): the call issues fb_replay_prime_priorities itself, on the online
+ * net's acting output (f32 in either inference dtype) -- act (fb_qnet_act_nib) -> prime -> env step -> push, its store at max_p ->
+ * Memory.sample -> train -> Memory.batch_update: the results of exactly those calls in that order, and at sampling time only the N newest
+ * leaves are still at max_p.  (Inside the call the acting head still rides in the env launch and the prime launch sits behind it, in front
+ * of the push's tree part: the env launch writes nothing the prime reads.)  Refused with FB_ERR_INVALID before any launch or counter change on such a memory: FB_ALGO_MDQN_PER (its target is not a max);
+ * every C51 / QR / noisy algo and net (their priorities are losses, not |TD| of means); at n = 1 a gamma that is not the memory's
+ * fb_replay_set_prime_gamma; fb_vec_step_dp; fb_sac_per_step, fb_iqn_per_step and their training calls.
  *
  * hipGraph capture.  State that decides what a launch does lives on the device (parameter / plane versions, Adam's step counter, the
  * sampler's generator, SumTree pointer / size, beta), so a captured call replays correctly -- with ONE exception: the replay memory's

@@ -12,6 +12,7 @@ across episode ends.  A score curve can.  The reference's own evidence is logs_b
                                 [--algo doubleper] [--huber D  (any scalar algo: the Huber loss's delta)]
                                 [--max-grad-norm G  (clip the gradient's global norm; the rows then carry the last step's norm and scale)]
                                 [--polyak RHO  (soft target updates after every train step, no periodic copy)]
+                                [--priority-init td  (--algo per | doubleper: new leaves at their acting-time |TD error|, not the tree's maximum)]
 
 One VecBrain run per (envs, lr); one train step per loop step once onlineTimeStep > OBSERVE, as in the reference.  Every `window`
 steps the device stats buffer (episodes ended, score sum, score max, pipes passed: kept by the env kernel) is read and zeroed, so each
@@ -34,11 +35,11 @@ from dqnflappybird_amd.vecbrain import VecBrain  # noqa: E402
 
 def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore, n_step=1, eval_envs=0, support=(51, -10.0, 10.0), noisy=False,
         initial_epsilon=None, acting_noise="shared", quantiles=(51, 1.0), munchausen=(0.03, 0.9, -1.0), huber=0.0, max_grad_norm=0.0,
-        polyak=0.0):
+        polyak=0.0, priority_init="max"):
     vb = VecBrain(n_envs, algo=algo, arch=arch, capacity=1_000_000, seed=seed, explore=explore, n_step=n_step,
                   n_atoms=support[0], v_min=support[1], v_max=support[2], noisy=noisy, initial_epsilon=initial_epsilon,
                   acting_noise=acting_noise, n_quantiles=quantiles[0], kappa=quantiles[1], tau=munchausen[0], alpha=munchausen[1],
-                  clip=munchausen[2], huber=huber, max_grad_norm=max_grad_norm, polyak=polyak)
+                  clip=munchausen[2], huber=huber, max_grad_norm=max_grad_norm, polyak=polyak, priority_init=priority_init)
     vb.net.set_hparams(lr=lr)
     head = f"# envs {n_envs}  algo {algo}/{arch}  n_step {n_step}  lr {lr:g}  batch {vb.batch}  observe {vb.observe}  explore {vb.explore}  eps {vb.initial_epsilon} -> {vb.final_epsilon}  {f'soft target updates, rho {vb.polyak:g}' if vb.polyak else 'target never synced (PER: the reference agent never syncs it)' if algo == 'per' else f'target sync / {vb.replace_target_iter}'}"
     if vb.support:
@@ -51,6 +52,8 @@ def run(n_envs, lr, steps, window, algo, arch, seed, out, budget_s, explore, n_s
         head += f"  huber delta {vb.huber:g}"
     if vb.max_grad_norm:
         head += f"  max_grad_norm {vb.max_grad_norm:g}"
+    if vb.priority_init != "max":
+        head += f"  priority_init {vb.priority_init} (fast tree)"
     if vb.noisy:
         head += f"  noisy (sigma0 {vb.sigma0:g}, acting noise {vb.acting_noise})"
     cols = "#   train_steps   env_steps  epsilon  episodes  mean_score  max_score  pipes/episode      loss   steps/s"
@@ -125,6 +128,7 @@ def main():
     ap.add_argument("--huber", type=float, default=0.0, help="scalar algos: the Huber loss's delta (0 = the squared loss)")
     ap.add_argument("--max-grad-norm", type=float, default=0.0, help="clip the gradient's global norm to this before Adam (0 = no clipping)")
     ap.add_argument("--polyak", type=float, default=0.0, help="soft target updates with this rate after every train step, no periodic copy (0 = off)")
+    ap.add_argument("--priority-init", choices=("max", "td"), default="max", help="--algo per / doubleper: a new transition's priority (VecBrain(priority_init=...))")
     ap.add_argument("--vmin", type=float, default=-10.0)
     ap.add_argument("--vmax", type=float, default=10.0)
     ap.add_argument("--eval-envs", type=int, default=0, help="end each run with VecBrain.evaluate() on this many games (0 = no evaluation)")
@@ -140,7 +144,8 @@ def main():
         for n_envs in [int(x) for x in a.envs.split(",")]:
             for lr in [float(x) for x in a.lrs.split(",")]:
                 run(n_envs, lr, a.steps, a.window, a.algo, a.arch, a.seed, out, a.budget_s, a.explore, a.n_step, a.eval_envs, (a.atoms, a.vmin, a.vmax),
-                    a.noisy, a.initial_epsilon, a.acting_noise, (a.quantiles, a.kappa), (a.tau, a.alpha, a.clip), a.huber, a.max_grad_norm, a.polyak)
+                    a.noisy, a.initial_epsilon, a.acting_noise, (a.quantiles, a.kappa), (a.tau, a.alpha, a.clip), a.huber, a.max_grad_norm, a.polyak,
+                    a.priority_init)
 
 
 if __name__ == "__main__":
